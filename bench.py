@@ -2,7 +2,8 @@
 """Benchmark of the XPBD particle step on MI355X (driver contract: one JSON line on rank 0).
 
     python bench.py                         # 1 GPU, BASELINE config 3: 4096 batches, 4 coincident per site
-    python bench.py --batches 256 --overlap 1      # BASELINE config 2 (the latency case; also reported by default)
+    python bench.py --full                  # the same line plus every other measurement (see below)
+    python bench.py --batches 256 --overlap 1      # BASELINE config 2 (the latency case; also reported with --full)
     python bench.py --batches 16384 --overlap 1    # one GPU's share of BASELINE config 4 / the whole of it on one GPU
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -11,9 +12,15 @@ A "step" is one SimulationHandler:_step (dt = 1/60, 2 sub-steps x 3 collision pa
 simulation_handler.lua:1722) over every particle of the workload.  Inputs are resident in HBM
 before the timed region (the handler owns the particle arrays on the device).
 
+A plain run sets up, warms up (--warmup), times --steps steps and prints the line.  --full adds what takes runs of
+its own: the per-kernel profiling leg, config 3's later windows, the config-2 latency block and the CPU baseline
+(--profile-steps, --no-windows, --no-latency and --no-cpu-baseline trim it).  --dump-outputs DIR writes what the
+last timed step computed -- every batch's position and every particle's x, y, vx, vy (float64) -- as DIR/<name>.npy;
+the inputs depend on the arguments only, so two builds can be compared output for output.
+
 Workload at N = 1: the largest single-GPU configuration of BASELINE.json -- config 3 (4096 batches, every
 four consecutive batches on one centre: 704,512 particles in 1024 dense islands).  Config 2 (256 separate
-batches, one island per CU: a latency test) is timed in the same run and reported as `latency_config2`.
+batches, one island per CU: a latency test) is timed in the same run with --full and reported as `latency_config2`.
 
 Multi-GPU: the plane is cut into N x-slabs of `--batches` batches each (weak scaling); every
 rank steps its slab with its own handler and the ranks exchange the cell boxes of their
@@ -28,8 +35,8 @@ steps_per_sec is the lock-step rate of the whole job.  The reference Lua path ca
 roofline: SURVEY.md 8d's byte model prices a step at 592 B per particle.  Large scenes run the PACKED pipeline
 (one launch per phase, csrc/eggsim_packed.hip): `kernel_ms` is then the HIP-event time of ALL launches that step the
 white particles in one step (events around the white stream's launch sequence, inside the timed region; the yolk
-launches run beside them on their own stream); a short profiling leg after the timed region puts events around
-every launch: `kernels` lists them, `dominant_kernel` names the kind with the largest share.
+launches run beside them on their own stream); with --full a short profiling leg after the timed region puts events
+around every launch: `kernels` lists them, `dominant_kernel` names the kind with the largest share.
 Small scenes run the fused step kernel: one launch per step, timed inside the timed region.  `traffic` and
 `valu` are rocprofv3 counter measurements of the same workload committed under profiles/ (they cannot be taken
 from inside the process); they are attached only when the workload matches.
@@ -51,6 +58,8 @@ ALGO_BYTES_PER_PARTICLE_STEP = 592.0  # SURVEY.md 8d / BASELINE.md: FP64 SoA, st
 HBM_PEAK_GBS = 8000.0                 # MI355X_MICROARCH.md: 8 TB/s spec
 PITCH = 160.0                         # px between batch centres (BASELINE config 2: islands never touch)
 COUNTER_FILES = [os.path.join(ROOT, "profiles", n) for n in ("r03_counters.json", "r02_counters.json")]  # written by scripts/collect_counters.sh; newest first
+DUMP_BYTES = 64 << 20                 # --dump-outputs writes at most this much over all ranks
+DUMP_FIELDS = ("x", "y", "vx", "vy")
 
 
 def site_pitch(overlap=1):
@@ -199,6 +208,28 @@ def latency_config2(torch, device, steps=200, warmup=30):
     return out
 
 
+def dump_outputs(h, out_dir, budget, prefix=""):
+    """What a caller of the timed path reads after its last step, as float64 DIR/<prefix><name>.npy: every batch's
+    position (get_position, in list_ids order) and every particle's DUMP_FIELDS per type.  When the particle fields
+    would exceed `budget` bytes, the same fixed seeded sample of particle indices is written for each field."""
+    from egg_fluid_simulation_amd import WHITE, YOLK
+    os.makedirs(out_dir, exist_ok=True)
+    bx, by = h.get_positions(h.list_ids())
+    arrays = {"batch_x": bx, "batch_y": by}
+    counts = h.get_n_particles()
+    room = (budget - 16 * bx.size - 4096) // (8 * len(DUMP_FIELDS))  # particles that fit (4 KB: the .npy headers)
+    keep = min(1.0, room / max(1, sum(counts)))
+    rng = np.random.default_rng(0)
+    for w, tag in ((WHITE, "white"), (YOLK, "yolk")):
+        n = counts[w]
+        sel = None if keep >= 1.0 else np.sort(rng.choice(n, int(n * keep), replace=False))
+        for f in DUMP_FIELDS:
+            a = h.download(w, f)
+            arrays["%s_%s" % (tag, f)] = a if sel is None else a[sel]
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -208,13 +239,16 @@ def main():
     ap.add_argument("--overlap", type=int, default=4, help="coincident batches per site (4 = BASELINE config 3, 1 = separate batches)")
     ap.add_argument("--tile-target", type=int, default=0, help="pack independent islands into tiles of this size")
     ap.add_argument("--no-fuse", action="store_true", help="one launch per particle type even on a full chip (A/B testing)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-latency", action="store_true", help="skip the config-2 latency block")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: the per-kernel leg, config 3's later windows, the config-2 latency block, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-latency", action="store_true", help="--full: skip the config-2 latency block")
     ap.add_argument("--packed", type=int, default=-1, help="packed pipeline: -1 automatic, 0 never, 1 always (A/B testing)")
     ap.add_argument("--group-particles", type=int, default=0, help="packed pipeline: particles per executor wave (0 = default)")
-    ap.add_argument("--profile-steps", type=int, default=-1, help="steps of the per-kernel timing leg (a replay of the timed region on a fresh scene; -1: as many as --steps, 0: none)")
-    ap.add_argument("--no-windows", action="store_true", help="skip the later timing windows of config 3 (config3_protocol, config3_late)")
-    ap.add_argument("--late-warmup", type=int, default=600, help="warm-up steps of the config3_late window")
+    ap.add_argument("--profile-steps", type=int, default=-1, help="--full: steps of the per-kernel timing leg (a replay of the timed region on a fresh scene; -1: as many as --steps, 0: none)")
+    ap.add_argument("--no-windows", action="store_true", help="--full: skip the later timing windows of config 3 (config3_protocol, config3_late)")
+    ap.add_argument("--late-warmup", type=int, default=600, help="--full: warm-up steps of the config3_late window")
     args = ap.parse_args()
     if args.profile_steps < 0:
         args.profile_steps = args.steps
@@ -276,6 +310,8 @@ def main():
         h.step_end(True)
 
     elapsed, s0, s1 = timed_run(h, one_step, args.steps, args.warmup, torch, dist, 1)
+    if args.dump_outputs:
+        dump_outputs(h, args.dump_outputs, DUMP_BYTES // world, "rank%d_" % rank if world > 1 else "")
 
     pairs = float(s1["pair_solves"] - s0["pair_solves"])
     follows = float(s1["follow_solves"] - s0["follow_solves"])
@@ -296,7 +332,7 @@ def main():
     # not stationary (config 3's dependency chains deepen step by step), so the leg REPLAYS the timed region's steps
     # on a fresh scene -- the same steps a `rocprofv3 --kernel-trace --stats` of this command averages over
     per_kernel = None
-    if rank == 0 and s1["packed"][WHITE] and args.profile_steps > 0:
+    if args.full and rank == 0 and s1["packed"][WHITE] and args.profile_steps > 0:
         hp = h
         if world == 1:
             hp = make_handler()
@@ -341,6 +377,11 @@ def main():
             dominant = {"kernel": dom["kernel"], "avg_launch_ms": dom["avg_ms"], "launches_per_step": dom["launches_per_step"],
                         "share_of_launch_time": dom["ms_per_step"] / sum_of_launches,
                         "sum_of_white_launches_ms_per_step": sum_of_launches}
+        elif packed:  # no per-kernel leg ran: the same timed-region events, without the per-launch breakdown
+            kernel_ms = kernel_ms_white
+            algo_bytes = ALGO_BYTES_PER_PARTICLE_STEP * n_white
+            kernel_name = "packed pipeline, white particles (per-launch breakdown: --full)"
+            dominant = None
         else:
             kernel_ms = kernel_ms_white
             algo_bytes = ALGO_BYTES_PER_PARTICLE_STEP * ((n_white + n_yolk) if fused else n_white)
@@ -389,7 +430,7 @@ def main():
         }
         if world == 1:
             del h
-            if (args.batches, args.overlap) == (4096, 4) and not args.no_windows:
+            if args.full and (args.batches, args.overlap) == (4096, 4) and not args.no_windows:
                 # the headline config is a transient: besides the driver's window (value), the BASELINE.md protocol window
                 # and a late one, each with its own ms_per_step / frac / levels_per_pass
                 if (args.warmup, args.steps) != (10, 100):
@@ -397,9 +438,9 @@ def main():
                 else:
                     out["config3_protocol"] = "the timed region of this line (10 warm-up + 100 steps)"
                 out["config3_late"] = steady_window(make_handler, args.late_warmup, 50, n_white)
-            if not args.no_latency:
+            if args.full and not args.no_latency:
                 out["latency_config2"] = latency_config2(torch, local_rank)
-            out["cpu_baseline"] = None if args.no_cpu_baseline else cpu_baseline(args.batches, args.overlap)
+            out["cpu_baseline"] = cpu_baseline(args.batches, args.overlap) if args.full and not args.no_cpu_baseline else None
         else:
             out["cpu_baseline"] = None
         print(json.dumps(out))

@@ -13,6 +13,5 @@ bash scripts/collect_counters.sh b16k --batches 16384 --overlap 1 > gpurun_out/c
 bash scripts/collect_counters.sh b4k --batches 4096 --overlap 1 > gpurun_out/campaign_cnt_b4k.log 2>&1
 echo "counters done"
 timeout -k 10 120 scripts/micro/build/chain_floor > gpurun_out/chain_floor.txt 2>&1
-timeout -k 10 300 python bench.py > gpurun_out/bench_default.json 2> gpurun_out/bench_default.err
-tail -1 gpurun_out/bench_default.json | cut -c1-300
+timeout -k 10 600 python bench.py --full | tail -1
 exit 0
