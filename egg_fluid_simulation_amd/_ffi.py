@@ -41,6 +41,10 @@ OPT_FUSE_TYPES = 9
 OPT_PACKED = 10
 OPT_GROUP_PARTICLES = 11
 OPT_LEVEL_WALK = 12
+OPT_SOLVER_ORDER = 13  # 0 exact (default), 1 relaxed
+OPT_RELAXATION = 14    # omega of the relaxed pass, in (0, 2]
+SOLVER_EXACT, SOLVER_RELAXED = 0, 1
+RELAXATION_DEFAULT = 1.8  # EGG_RELAXATION_DEFAULT
 PK_VARIANT_LEVELS_INORDER, PK_VARIANT_LEVELS_OOO, PK_VARIANT_EXEC, PK_VARIANT_EXEC_CHAIN, PK_VARIANT_SORT_LDS, PK_VARIANT_SORT_DIRECT = 1, 2, 4, 8, 16, 32
 PK_VARIANT_PASS_FUSED = 64
 
@@ -75,7 +79,8 @@ class EggStats(C.Structure):
                 ("kernel_ms", C.c_double * 2), ("kernel_ms_sum", C.c_double * 2), ("timed_steps", C.c_int64),
                 ("max_pass_visits", C.c_int64 * 2), ("budget", C.c_double * 2), ("fused_launch", C.c_int64),
                 ("packed", C.c_int64 * 2), ("pk_kernel_ms", (C.c_double * 10) * 2), ("pk_kernel_launches", (C.c_int64 * 10) * 2),
-                ("host_ms", C.c_double * 3), ("max_levels", C.c_int64 * 2), ("pk_variants", C.c_int64 * 2)]
+                ("host_ms", C.c_double * 3), ("max_levels", C.c_int64 * 2), ("pk_variants", C.c_int64 * 2),
+                ("relaxed_steps", C.c_int64)]
 
 
 class EggRenderConfig(C.Structure):  # egg_render_config

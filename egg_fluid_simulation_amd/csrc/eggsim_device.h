@@ -261,3 +261,26 @@ struct EggCompositeArgs {
 struct EggStepArgs4 {
     EggStepArgs a[4];
 };
+
+// The relaxed-order path (eggsim_relaxed.hip): one particle type, one thread per particle.  A
+// collision pass is a Jacobi pass over a spatial hash built fresh from the pass's start positions: open-addressed cell
+// table (64-bit cell keys, linear probing), particles grouped by cell, ascending index inside a cell.
+#define EGG_RX_EMPTY_KEY 0xFFFFFFFFFFFFFFFFull
+struct EggRelaxedArgs {
+    int32_t n;
+    uint32_t table_mask;  // hash slots - 1 (a power of two, at least twice the particle count)
+    int32_t pass;         // collision pass of the step (its pair counter is status[1 + pass])
+    const double *x_in, *y_in, *vx_in, *vy_in;  // [cur]
+    double *x_out, *y_out, *vx_out, *vy_out;    // [cur ^ 1]
+    const double *inv_mass, *radius;
+    const int32_t *p_atom;                        // atom of each particle
+    const double *atom_tx, *atom_ty, *atom_fd;    // follow target and target distance of each atom
+    double2 *pos, *pos_next, *prev;               // positions of this pass / after it, start of the sub-step
+    double2 *spos, *swr;                          // (x, y) and (inverse mass, radius) grouped by cell
+    int32_t *pslot, *tmp, *sidx;                  // hash slot of each particle, scatter scratch, particle of a grouped slot
+    unsigned long long *hkey;                     // [table] cell key of a slot, EGG_RX_EMPTY_KEY when free
+    uint32_t *hcount, *hstart;                    // [table + 1] particles per slot; their first grouped slot (exclusive scan)
+    unsigned long long *status;                   // [0] a cell out of range or a NaN position, [1 + pass] pairs counted
+    double damping, sub_delta, eps, follow_compliance;
+    double collision_compliance, overlap, cell_size, omega;
+};

@@ -7,6 +7,7 @@
 //   eggsim_host_step.hip    _step: environment scalars, kernel launches, validation / re-run / commit
 //   eggsim_host_abi.hip     the extern "C" entry points of include/eggsim.h (except the renderer's)
 //   eggsim_host_render.hip  egg_render* : the headless renderer's host side
+//   eggsim_host_relaxed.hip _step in relaxed order (EGG_OPT_SOLVER_ORDER = 1): the launches of eggsim_relaxed.hip
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -55,6 +56,14 @@ extern "C" __global__ void egg_pk_sort_kernel(EggPackedArgs A);
 extern "C" __global__ void egg_pk_sort_direct_kernel(EggPackedArgs A);
 extern "C" __global__ void egg_pk_end_kernel(EggPackedArgs A);
 extern "C" __global__ void egg_pk_reduce_kernel(EggPackedArgs A, int n_passes);
+extern "C" __global__ void egg_rx_atoms_kernel(const int32_t *, const int32_t *, int, int32_t *);
+extern "C" __global__ void egg_rx_begin_kernel(EggRelaxedArgs A);
+extern "C" __global__ void egg_rx_mid_kernel(EggRelaxedArgs A);
+extern "C" __global__ void egg_rx_end_kernel(EggRelaxedArgs A);
+extern "C" __global__ void egg_rx_insert_kernel(EggRelaxedArgs A);
+extern "C" __global__ void egg_rx_scatter_kernel(EggRelaxedArgs A);
+extern "C" __global__ void egg_rx_rank_kernel(EggRelaxedArgs A);
+extern "C" __global__ void egg_rx_gather_kernel(EggRelaxedArgs A);
 extern "C" __global__ void egg_render_count_kernel(EggRenderArgs A);
 extern "C" __global__ void egg_render_fill_kernel(EggRenderArgs A);
 extern "C" __global__ void egg_render_scan_kernel(EggRenderArgs A);
@@ -195,6 +204,21 @@ struct PackedClass {
     int threads_lists = 64, threads_lists_stale = 64;
 };
 
+// The relaxed-order path's buffers of one particle type (eggsim_host_relaxed.hip), allocated at its first step.
+struct RelaxedBufs {
+    DevBuf<double2> pos, pos_next, prev, spos, swr;
+    DevBuf<int32_t> pslot, tmp, sidx, p_atom;
+    DevBuf<unsigned long long> hkey, status;
+    DevBuf<uint32_t> hcount, hstart;
+    DevBuf<double> targets;               // [3][atoms]: follow x, follow y, target distance
+    DevBuf<unsigned char> scan_tmp;       // hipcub scan scratch
+    size_t scan_bytes = 0;
+    uint32_t table = 0;                   // hash slots the buffers are sized for
+    uint64_t atoms_gen = ~0ull;           // System::atoms_gen p_atom was built for
+    PinnedBuf<unsigned long long> h_status;
+    PinnedBuf<double> h_targets;
+};
+
 struct System {  // one particle type
     egg_config cfg{};
     int64_t n = 0;
@@ -202,6 +226,7 @@ struct System {  // one particle type
     DevBuf<double> x[2], y[2], vx[2], vy[2], inv_mass, radius, mass_t;
     // atoms (host + device mirrors)
     std::vector<Atom> atoms;
+    uint64_t atoms_gen = 0;  // counts the rebuilds of `atoms` (upload_atoms)
     DevBuf<int32_t> d_atom_offset, d_atom_count, d_atom_batch;
     // what a step launch reports, in ONE device buffer so that one copy brings it back: two status blocks
     // (the launch writes one and re-initialises the other for the next launch), the atoms' end-of-step cell
@@ -275,6 +300,7 @@ struct System {  // one particle type
     std::vector<PkStamp> pk_stamps;
     size_t pk_stamps_used = 0;
     EggStatus *h_status = nullptr;  // the most recent launch's status block inside stage_down (pinned)
+    RelaxedBufs rx;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
@@ -313,6 +339,8 @@ struct egg_handle {
     bool lds_lane_ordered = false;  // one ds_add_rtn serves same-address lanes in ascending lane order (probed at create)
     int opt_packed = -1;      // packed pipeline: -1 automatic (large scenes), 0 never, 1 every eligible class
     int opt_group_particles = 0;  // particles one wave of the packed executor keeps in LDS (16 B each): 0 = by scene size (retile), at most 1280
+    int opt_solver_order = 0;       // EGG_OPT_SOLVER_ORDER: 0 exact (the reference's pair order), 1 relaxed
+    double opt_relaxation = EGG_RELAXATION_DEFAULT;  // EGG_OPT_RELAXATION: omega of the relaxed pass
     int opt_force_global_state = 0;  // test hook: run every tile through the global-memory-state kernel  // threads per particle in the step kernel's workgroups (pair dataflow spreading)
     hipDeviceProp_t prop{};
     size_t lds_limit = 64 * 1024;  // dynamic LDS a step-kernel workgroup may use
@@ -392,6 +420,12 @@ Env make_env(const egg_config &c, double sub_delta, int64_t n);
 // return (egg_step_begin); kEnd = finish a begun step: validate, re-run if needed, commit (egg_step_end)
 enum { kWhole = 0, kPrepare = 1, kBegin = 2, kEnd = 3 };
 int do_step(egg_handle *h, double delta, int S, int C, int phase = kWhole);  // L:1722-1989
+// the step's config scalars of type w: mass / radius re-derived after a config change (L:1731-1744, L:1420-1430)
+int follow_config(egg_handle *h, int w, bool launch);
+
+// eggsim_host_relaxed.hip
+int relaxed_step(egg_handle *h, double delta, int S, int C);
+void leave_relaxed(egg_handle *h);  // back to exact order: the next exact step re-tiles from the current positions
 
 }  // namespace egghost
 

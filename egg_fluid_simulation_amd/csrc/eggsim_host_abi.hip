@@ -401,12 +401,14 @@ int egg_update(egg_handle *h, double delta, double step_delta, int32_t n_substep
 int egg_prepare_step(egg_handle *h, double step_delta, int32_t n_substeps, int32_t n_collision_steps) {
     if (!h || n_substeps < 1 || n_collision_steps < 1 || !(step_delta >= 0)) return EGG_ERR_INVALID_ARGUMENT;
     REJECT_IN_FLIGHT(h, "egg_prepare_step");
+    if (h->opt_solver_order == EGG_SOLVER_RELAXED) return EGG_OK;  // no tiles or claims to form
     (void)hipSetDevice(h->device);
     return do_step(h, step_delta, n_substeps, n_collision_steps, kPrepare);
 }
 
 int egg_step_begin(egg_handle *h, double delta, int32_t n_substeps, int32_t n_collision_steps) {
     if (!h || n_substeps < 1 || n_collision_steps < 1 || std::isnan(delta)) return EGG_ERR_INVALID_ARGUMENT;
+    if (h->opt_solver_order == EGG_SOLVER_RELAXED) return fail(h, EGG_ERR_UNSUPPORTED, "egg_step_begin: relaxed order: single-device steps only");
     if (h->in_flight) return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_step_begin: a step is already in flight");
     (void)hipSetDevice(h->device);
     int rc = do_step(h, delta, n_substeps, n_collision_steps, kBegin);
@@ -421,6 +423,7 @@ int egg_step_begin(egg_handle *h, double delta, int32_t n_substeps, int32_t n_co
 
 int egg_step_end(egg_handle *h, int32_t commit) {
     if (!h) return EGG_ERR_INVALID_ARGUMENT;
+    if (h->opt_solver_order == EGG_SOLVER_RELAXED) return fail(h, EGG_ERR_UNSUPPORTED, "egg_step_end: relaxed order: single-device steps only");
     if (!h->in_flight) return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_step_end: no step in flight");
     (void)hipSetDevice(h->device);
     h->in_flight = false;
@@ -563,6 +566,8 @@ int egg_get_bounds_many(egg_handle *h, int64_t n, const int64_t *ids, double *lo
 
 int egg_get_claims_many(egg_handle *h, int64_t n, const int64_t *ids, double *boxes, double *cell_sizes) {
     if (!h || n < 0 || (n > 0 && (!ids || !boxes))) return EGG_ERR_INVALID_ARGUMENT;
+    if (h->opt_solver_order == EGG_SOLVER_RELAXED)  // (claims exist only for the exact order's tiles)
+        return fail(h, EGG_ERR_UNSUPPORTED, "egg_get_claims_many: relaxed order: single-device steps only");
     std::vector<double> lx((size_t)n), ly((size_t)n), hx((size_t)n), hy((size_t)n);
     // reuse the bounds path to make sure boxes / claims are current
     int rc = egg_get_bounds_many(h, n, ids, lx.data(), ly.data(), hx.data(), hy.data());
@@ -878,6 +883,22 @@ int egg_set_option(egg_handle *h, int option, double value) {
             if (!(value >= 0 && value <= 10240)) return fail(h, EGG_ERR_INVALID_ARGUMENT, "group particles must be in [0, 10240]");
             h->opt_group_particles = (int)value;
             h->sys[0].tiling_dirty = h->sys[1].tiling_dirty = true;
+            return EGG_OK;
+        case EGG_OPT_SOLVER_ORDER:
+            REJECT_IN_FLIGHT(h, "egg_set_option(EGG_OPT_SOLVER_ORDER)");
+            if (!(value == EGG_SOLVER_EXACT || value == EGG_SOLVER_RELAXED))
+                return fail(h, EGG_ERR_INVALID_ARGUMENT, "solver order must be 0 (exact) or 1 (relaxed)");
+            if ((int)value != h->opt_solver_order) {
+                if (value == EGG_SOLVER_EXACT) leave_relaxed(h);
+                else
+                    for (int w = 0; w < 2; ++w) h->sys[w].meta_dirty = true;  // the relaxed path uploads the follow targets afresh
+            }
+            h->opt_solver_order = (int)value;
+            return EGG_OK;
+        case EGG_OPT_RELAXATION:
+            REJECT_IN_FLIGHT(h, "egg_set_option(EGG_OPT_RELAXATION)");
+            if (!(value > 0.0 && value <= 2.0)) return fail(h, EGG_ERR_INVALID_ARGUMENT, "relaxation must be in (0, 2]");
+            h->opt_relaxation = value;
             return EGG_OK;
         case EGG_OPT_FORCE_SINGLE_TILE:
             h->opt_force_single = value != 0;

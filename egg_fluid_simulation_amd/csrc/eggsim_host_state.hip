@@ -143,6 +143,7 @@ int upload_atoms(egg_handle *h, int which) {
             off += B.n[which];
             s.atoms.push_back(a);
         }
+        ++s.atoms_gen;
         const size_t na = s.atoms.size();
         std::vector<int32_t> o(na), c(na), bb(na);
         for (size_t k = 0; k < na; ++k) {

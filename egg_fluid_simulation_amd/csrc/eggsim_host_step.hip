@@ -473,10 +473,34 @@ int prepare_tiles(egg_handle *h) {
     return EGG_OK;
 }
 
+int follow_config(egg_handle *h, int w, bool launch) {
+    System &s = h->sys[w];
+    bool upd_mass = !s.has_env || s.cfg.min_mass != s.env_min_mass || s.cfg.max_mass != s.env_max_mass;
+    bool upd_radius = !s.has_env || s.cfg.min_radius != s.env_min_radius || s.cfg.max_radius != s.env_max_radius;
+    if (launch && s.has_env && (upd_mass || upd_radius) && s.n > 0) {
+        const int threads = 256;
+        hipLaunchKernelGGL(egg_rederive_kernel, dim3((unsigned)((s.n + threads - 1) / threads)), dim3(threads), 0,
+                           s.stream, s.mass_t.p, s.inv_mass.p, s.radius.p, (int)s.n, upd_mass ? 1 : 0,
+                           s.cfg.min_mass, s.cfg.max_mass, upd_radius ? 1 : 0, s.cfg.min_radius, s.cfg.max_radius);
+        HIP_TRY(h, hipGetLastError());
+        // the step that reads these arrays may be launched on the OTHER type's stream (one fused launch
+        // for both types): finish here -- config changes are rare, the wait costs nothing that matters
+        HIP_TRY(h, hipStreamSynchronize(s.stream));
+        h->stats.kernel_launches++;
+    }
+    s.has_env = true;
+    s.env_min_mass = s.cfg.min_mass;
+    s.env_max_mass = s.cfg.max_mass;
+    s.env_min_radius = s.cfg.min_radius;
+    s.env_max_radius = s.cfg.max_radius;
+    return EGG_OK;
+}
+
 // phase: kWhole = the complete step; kPrepare = tiles/claims only; kBegin = launch the first attempt and
 // return (egg_step_begin); kEnd = finish a begun step: validate, re-run if needed, commit (egg_step_end)
 
 int do_step(egg_handle *h, double delta, int S, int C, int phase) {  // L:1722-1989
+    if (h->opt_solver_order == 1) return relaxed_step(h, delta, S, C);  // (egg_prepare_step / egg_step_begin never get here)
     const double sub_delta = std::max(delta / S, h->sys[0].cfg.eps);
     // One collision pass per sub-step: the reference never clears its hash lists inside the step, so the
     // kernel keeps one generation of cells per sub-step (PassCtx); the ring is sized for up to 8.
@@ -494,24 +518,8 @@ int do_step(egg_handle *h, double delta, int S, int C, int phase) {  // L:1722-1
         System &s = h->sys[w];
         env[w] = make_env(s.cfg, sub_delta, h->budget_particles[w] >= 0 ? h->budget_particles[w] : s.n);
         // mass / radius follow a config change at the next step (L:1731-1744, L:1420-1430)
-        bool upd_mass = !s.has_env || s.cfg.min_mass != s.env_min_mass || s.cfg.max_mass != s.env_max_mass;
-        bool upd_radius = !s.has_env || s.cfg.min_radius != s.env_min_radius || s.cfg.max_radius != s.env_max_radius;
-        if (phase != kEnd && s.has_env && (upd_mass || upd_radius) && s.n > 0) {
-            const int threads = 256;
-            hipLaunchKernelGGL(egg_rederive_kernel, dim3((unsigned)((s.n + threads - 1) / threads)), dim3(threads), 0,
-                               s.stream, s.mass_t.p, s.inv_mass.p, s.radius.p, (int)s.n, upd_mass ? 1 : 0,
-                               s.cfg.min_mass, s.cfg.max_mass, upd_radius ? 1 : 0, s.cfg.min_radius, s.cfg.max_radius);
-            HIP_TRY(h, hipGetLastError());
-            // the step that reads these arrays may be launched on the OTHER type's stream (one fused launch
-            // for both types): finish here -- config changes are rare, the wait costs nothing that matters
-            HIP_TRY(h, hipStreamSynchronize(s.stream));
-            h->stats.kernel_launches++;
-        }
-        s.has_env = true;
-        s.env_min_mass = s.cfg.min_mass;
-        s.env_max_mass = s.cfg.max_mass;
-        s.env_min_radius = s.cfg.min_radius;
-        s.env_max_radius = s.cfg.max_radius;
+        const int rc = follow_config(h, w, phase != kEnd);
+        if (rc != EGG_OK) return rc;
         if (env[w].cell != s.tiled_cell_size) {
             s.tiling_dirty = true;
             s.aabb_valid = false;

@@ -192,32 +192,6 @@ __device__ inline void pk_build_grid(const Tile &t, int gh, int buf, uint32_t *t
     __syncthreads();
 }
 
-// pre-solve (L:1393-1432) + follow constraint (L:1435-1471) of one particle, exactly as in egg_step_body
-__device__ __forceinline__ void pk_pre_follow(const EggPackedArgs &A, double2 ps, double2 &v, double im, double fx, double fy,
-                                              double target, double2 &out) {
-    v.x = v.x * A.damping;
-    v.y = v.y * A.damping;
-    double x = ps.x + A.sub_delta * v.x;
-    double y = ps.y + A.sub_delta * v.y;
-    const double dx = fx - x, dy = fy - y;
-    const double current = sqrt(dx * dx + dy * dy);
-    if (im > A.eps && current > target) {
-        double nx, ny;
-        if (current < A.eps) {
-            nx = 0.0;
-            ny = 0.0;
-        } else {
-            nx = dx / current;
-            ny = dy / current;
-        }
-        const double violation = current - target;
-        const double lambda = violation / (im + A.follow_compliance);
-        x = x + nx * lambda * im;
-        y = y + ny * lambda * im;
-    }
-    out = make_double2(x, y);
-}
-
 #define EGG_NEG_LEVEL (-0x40000000)
 
 }  // namespace
@@ -257,7 +231,7 @@ extern "C" __global__ void __launch_bounds__(256) egg_pk_begin_kernel(EggPackedA
     double2 v = make_double2(A.vx_in[g], A.vy_in[g]);
     const double2 wr = make_double2(A.inv_mass[g], A.radius[g]);
     double2 out;
-    pk_pre_follow(A, ps, v, wr.x, A.atom_tx[atom], A.atom_ty[atom], A.atom_fd[atom], out);
+    egg_pre_follow(A.damping, A.sub_delta, A.eps, A.follow_compliance, ps, v, wr.x, A.atom_tx[atom], A.atom_ty[atom], A.atom_fd[atom], out);
     ((double2 *)A.pk_prev)[p] = ps;
     ((double2 *)A.pk_pos)[p] = out;
     ((double2 *)A.pk_wr)[p] = wr;
@@ -272,7 +246,7 @@ extern "C" __global__ void __launch_bounds__(256) egg_pk_mid_kernel(EggPackedArg
     double2 v = make_double2((ps.x - pv.x) / A.sub_delta, (ps.y - pv.y) / A.sub_delta);
     const double im = ((const double2 *)A.pk_wr)[p].x;
     double2 out;
-    pk_pre_follow(A, ps, v, im, A.atom_tx[atom], A.atom_ty[atom], A.atom_fd[atom], out);
+    egg_pre_follow(A.damping, A.sub_delta, A.eps, A.follow_compliance, ps, v, im, A.atom_tx[atom], A.atom_ty[atom], A.atom_fd[atom], out);
     ((double2 *)A.pk_prev)[p] = ps;  // (the velocity itself is never stored: post-solve recomputes it from the two positions)
     ((double2 *)A.pk_pos)[p] = out;
 }

@@ -556,4 +556,32 @@ __device__ inline int enum_stale_multi(const Tile &t, const PassCtx &c, int i, u
     return count;
 }
 
+// pre-solve (L:1393-1432) + follow constraint (L:1435-1471) of one particle, exactly as in egg_step_body: the packed
+// pipeline (eggsim_packed.hip) and the relaxed-order path (eggsim_relaxed.hip) share it
+__device__ __forceinline__ void egg_pre_follow(double damping, double sub_delta, double eps, double follow_compliance,
+                                               double2 ps, double2 &v, double im, double fx, double fy, double target,
+                                               double2 &out) {
+    v.x = v.x * damping;
+    v.y = v.y * damping;
+    double x = ps.x + sub_delta * v.x;
+    double y = ps.y + sub_delta * v.y;
+    const double dx = fx - x, dy = fy - y;
+    const double current = sqrt(dx * dx + dy * dy);
+    if (im > eps && current > target) {
+        double nx, ny;
+        if (current < eps) {
+            nx = 0.0;
+            ny = 0.0;
+        } else {
+            nx = dx / current;
+            ny = dy / current;
+        }
+        const double violation = current - target;
+        const double lambda = violation / (im + follow_compliance);
+        x = x + nx * lambda * im;
+        y = y + ny * lambda * im;
+    }
+    out = make_double2(x, y);
+}
+
 }  // namespace

@@ -570,7 +570,7 @@ class SimulationHandler:
                     max_pass_visits=list(s.max_pass_visits), budget=list(s.budget), fused_launch=int(s.fused_launch),
                     packed=list(s.packed), pk_kernel_ms=[list(r) for r in s.pk_kernel_ms],
                     pk_kernel_launches=[list(r) for r in s.pk_kernel_launches], host_ms=list(s.host_ms), max_levels=list(s.max_levels),
-                    pk_variants=list(s.pk_variants))
+                    pk_variants=list(s.pk_variants), relaxed_steps=s.relaxed_steps)
 
     def selftest_arith(self, n=1 << 24, seed=1):
         """mismatches of the kernel's hand-expanded f64 division against `/` on n random operand pairs"""
@@ -580,3 +580,20 @@ class SimulationHandler:
 
     def set_option(self, option, value):
         self._check(self._lib.egg_set_option(self._h, int(option), float(value)))
+
+    _SOLVER_ORDERS = {"exact": _ffi.SOLVER_EXACT, "relaxed": _ffi.SOLVER_RELAXED}
+
+    def set_solver_order(self, order, relaxation=None):
+        """"exact" (default): the reference's sequential pair order, bit for bit.  "relaxed": every collision pass a
+        Jacobi pass with constraint averaging, scaled by `relaxation` in (0, 2] (None keeps the current value) --
+        plausible and deterministic, several times faster on large scenes, but not the reference's numbers
+        (DESIGN.md section 2.7).  Relaxed steps are single-device: step_begin / step_end / get_claims raise EggError."""
+        if order not in self._SOLVER_ORDERS:
+            raise EggError("solver order must be 'exact' or 'relaxed', not %r" % (order,))
+        if relaxation is not None:
+            self.set_option(_ffi.OPT_RELAXATION, relaxation)
+        self.set_option(_ffi.OPT_SOLVER_ORDER, self._SOLVER_ORDERS[order])
+        self._solver_order = order
+
+    def get_solver_order(self):
+        return getattr(self, "_solver_order", "exact")

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define EGGSIM_ABI_VERSION 2
+#define EGGSIM_ABI_VERSION 3
 
 typedef struct egg_handle egg_handle;
 
@@ -290,6 +290,8 @@ typedef struct {
     int64_t max_levels[2];
     /* packed pipeline: which kernel variants the classes of that type run (EGG_PK_VARIANT_* bits; several classes may differ) */
     int64_t pk_variants[2];
+    /* _step calls executed in relaxed order (EGG_OPT_SOLVER_ORDER = 1); included in `steps` */
+    int64_t relaxed_steps;
 } egg_stats;
 int egg_get_stats(egg_handle *h, egg_stats *out);
 
@@ -312,8 +314,17 @@ enum {
     EGG_OPT_FUSE_TYPES,             /* 1 (default): white and yolk tiles share one launch when the chip holds several tiles per CU; 0: one launch per type */
     EGG_OPT_PACKED,                 /* packed pipeline (one launch per phase, pair projections of many islands packed into full waves): -1 automatic (large scenes), 0 never, 1 whenever a launch class is eligible */
     EGG_OPT_GROUP_PARTICLES,        /* packed pipeline: particles whose positions one wave of the pair executor keeps in LDS (0, the default: by scene size, 320..1280) */
-    EGG_OPT_LEVEL_WALK              /* packed pipeline, the pass that gives every pair its dependency level: 0 (default) by regime -- out of order for dense islands (> 256 particles) while the groups are no more than the chip's SIMDs, in order otherwise --, 1 always in order, 2 out of order everywhere */
+    EGG_OPT_LEVEL_WALK,             /* packed pipeline, the pass that gives every pair its dependency level: 0 (default) by regime -- out of order for dense islands (> 256 particles) while the groups are no more than the chip's SIMDs, in order otherwise --, 1 always in order, 2 out of order everywhere */
+    EGG_OPT_SOLVER_ORDER,           /* 0 (default): exact -- the reference's sequential Gauss-Seidel pair order, bit for bit; 1: relaxed --
+                                     * every collision pass a Jacobi pass with constraint averaging: plausible,
+                                     * deterministic, not the reference's numbers.  Relaxed steps are single-device only: egg_step_begin,
+                                     * egg_step_end and egg_get_claims_many return EGG_ERR_UNSUPPORTED, egg_prepare_step does nothing.
+                                     * Refused while a step is in flight. */
+    EGG_OPT_RELAXATION              /* omega of the relaxed pass, in (0, 2] (default EGG_RELAXATION_DEFAULT).  Refused while a step is in flight. */
 };
+#define EGG_SOLVER_EXACT 0
+#define EGG_SOLVER_RELAXED 1
+#define EGG_RELAXATION_DEFAULT 1.8
 int egg_set_option(egg_handle *h, int option, double value);
 
 /* ---- several GPUs in one process (csrc/eggsim_group.cpp) -------------------------------------------------------
