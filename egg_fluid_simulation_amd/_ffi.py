@@ -131,6 +131,8 @@ _SIGNATURES = {
     "egg_group_step": (C.c_int, [C.c_void_p, C.c_double, C.c_int32, C.c_int32]),
     "egg_group_owner": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "egg_group_get_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "egg_group_set_solver_order": (C.c_int, [C.c_void_p, C.c_int32, C.c_double]),
+    "egg_group_get_halo_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "egg_remove": (C.c_int, [C.c_void_p, C.c_int64]),
     "egg_set_target": (C.c_int, [C.c_void_p, C.c_int64, C.c_double, C.c_double]),
     "egg_set_targets_many": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -284,3 +284,45 @@ struct EggRelaxedArgs {
     double damping, sub_delta, eps, follow_compliance;
     double collision_compliance, overlap, cell_size, omega;
 };
+
+// Device groups ("Several devices"): the group instantiations of the relaxed kernels
+// (egg_rx_*_group_kernel) take these besides.  Entries are the n local particles, then the ghosts.
+struct EggRxGroupFields {
+    const int32_t *ekey;                 // [n + ghost capacity] global key of every entry
+    int32_t *sloc;                       // [n + ghost capacity] entry of a grouped slot
+    const unsigned long long *n_ghost;   // ghost entries of this pass (written by egg_rx_unpack_kernel)
+    const double2 *gwr;                  // [ghost capacity] (inverse mass, radius) of the ghosts
+    unsigned long long *box;             // 4 words: cell box of the positions the kernel writes (EGG_RX_BOX_*), or nullptr
+};
+struct EggRelaxedGroupArgs {
+    EggRelaxedArgs a;
+    EggRxGroupFields g;
+};
+
+// A ghost record: a particle of a sender j that lies within one cell of a receiver k's cell box (40 bytes).
+struct EggGhost {
+    double x, y, inv_mass, radius;
+    int64_t key;  // global key
+};
+#define EGG_RX_MAX_GROUP 16  // handles of one group that relaxed order supports
+// Cell box words (zero = empty): [0] max of 2^32 - u(cx), [1] max of u(cx), [2] / [3] the same for cy, u(c) = c + 2^30 + 1.
+#define EGG_RX_BOX_BIAS 0x40000001ll
+struct EggRxPackArgs {  // sender side: one launch per pass packs for every receiver
+    int32_t n, n_recv;                   // local particles; receivers
+    double cell_size;
+    const double2 *pos;
+    const double *inv_mass, *radius;
+    const int32_t *ekey;
+    const unsigned long long *box[EGG_RX_MAX_GROUP];  // each receiver's box for this pass (in the receiver's memory)
+    EggGhost *send[EGG_RX_MAX_GROUP];                 // this sender's buffer for each receiver (capacity n)
+    unsigned long long *count[EGG_RX_MAX_GROUP];      // records in it (in this sender's memory, zero at the step's start)
+};
+struct EggRxUnpackArgs {  // receiver side: pulls every sender's records for it into the ghost entries
+    int32_t n, n_send;                   // local particles; senders
+    double2 *pos;                        // positions of this pass; ghosts go to [n + g]
+    double2 *gwr;
+    int32_t *ekey;
+    unsigned long long *n_ghost;
+    const EggGhost *recs[EGG_RX_MAX_GROUP];           // in the senders' memory
+    const unsigned long long *count[EGG_RX_MAX_GROUP];
+};

@@ -18,6 +18,10 @@
 //   * the collision budget 0.05 N^2 (L:1752-1753) counts the particles of all devices (EGG_OPT_BUDGET_PARTICLES_*);
 //     the visits of the step in flight are added up over the devices BEFORE it is committed, and a budget that could
 //     bind is refused (exact-budget mode needs all particles of a type in one tile).
+//
+// In relaxed order (egg_group_set_solver_order) there are no claims, budget or re-runs: the step
+// is eggsim_host_relaxed_group.hip's (every pass over local particles plus ghosts of the neighbours', no hand-over),
+// and afterwards a batch whose position lies more than `halo` px outside its slab moves to the slab that holds it.
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
@@ -30,6 +34,15 @@
 #include <vector>
 
 #include "../../include/eggsim.h"
+
+namespace egghost {  // eggsim_host_relaxed_group.hip
+int relaxed_group_peers(egg_handle *const *hs, int n, std::string *error);
+int relaxed_group_step(egg_handle *const *hs, int n, double delta, int S, int C, int64_t halo_records[1], std::string *error);
+}
+
+namespace {
+constexpr int64_t kGhostRecordBytes = 40;  // EggGhost (eggsim_device.h): x, y, inverse mass, radius, global key
+}
 
 struct egg_group {
     std::vector<egg_handle *> h;
@@ -45,6 +58,8 @@ struct egg_group {
     double elapsed = 0, alpha = 0;
     int64_t migrations = 0, discarded_steps = 0;
     int64_t committed_visits[2] = {0, 0};
+    int order = EGG_SOLVER_EXACT;
+    int64_t halo_passes = 0, halo_records = 0;  // relaxed group steps: collision passes, ghost records received
     std::string error;
 };
 
@@ -237,7 +252,48 @@ int rebalance(egg_group *g, double delta, int S, int C) {
     return gfail(g, EGG_ERR_INTERNAL, "egg_group: batch hand-over did not settle");
 }
 
+// relaxed order: after a committed step, batches whose position lies more than `halo` px outside their slab move to the
+// slab that holds it (where they sit does not change the results: the halo makes every device see what one would)
+int rebalance_relaxed(egg_group *g) {
+    const int n = (int)g->h.size();
+    std::vector<std::vector<int64_t>> gids((size_t)n), lids((size_t)n);
+    for (size_t i = 0; i < g->batch.size(); ++i)
+        if (g->batch[i].alive) {
+            gids[(size_t)g->batch[i].owner].push_back((int64_t)i + 1);
+            lids[(size_t)g->batch[i].owner].push_back(g->batch[i].local);
+        }
+    std::map<int64_t, int> plan;
+    for (int k = 0; k < n; ++k) {
+        const size_t m = lids[(size_t)k].size();
+        if (!m) continue;
+        std::vector<double> xs(m), ys(m);
+        GTRY(g, k, egg_get_positions_many(g->h[(size_t)k], (int64_t)m, lids[(size_t)k].data(), xs.data(), ys.data()));
+        for (size_t j = 0; j < m; ++j) {
+            const double x = xs[j];
+            if (x < g->cuts[(size_t)k] - g->halo || x >= g->cuts[(size_t)k + 1] + g->halo) {
+                const int dest = slab_of(g, x);
+                if (dest != k) plan[gids[(size_t)k][j]] = dest;
+            }
+        }
+    }
+    return plan.empty() ? EGG_OK : move_batches(g, plan);
+}
+
+int group_step_relaxed(egg_group *g, double delta, int S, int C) {
+    const size_t n = g->h.size();
+    if (n == 1) {
+        GTRY(g, 0, egg_step(g->h[0], delta, S, C));
+        return EGG_OK;
+    }
+    std::string err;
+    const int rc = egghost::relaxed_group_step(g->h.data(), (int)n, delta, S, C, &g->halo_records, &err);
+    if (rc != EGG_OK) return gfail(g, rc, "%s", err.c_str());
+    g->halo_passes += (int64_t)S * C;
+    return rebalance_relaxed(g);
+}
+
 int group_step(egg_group *g, double delta, int S, int C) {  // one _step (L:1722) on every device
+    if (g->order == EGG_SOLVER_RELAXED) return group_step_relaxed(g, delta, S, C);
     const size_t n = g->h.size();
     int rc = sync_budget(g);
     if (rc != EGG_OK) return rc;
@@ -449,6 +505,34 @@ int egg_group_get_counters(const egg_group *g, int64_t *migrations, int64_t *dis
     if (!g) return EGG_ERR_INVALID_ARGUMENT;
     if (migrations) *migrations = g->migrations;
     if (discarded_steps) *discarded_steps = g->discarded_steps;
+    return EGG_OK;
+}
+
+int egg_group_set_solver_order(egg_group *g, int32_t order, double relaxation) {
+    if (!g) return EGG_ERR_INVALID_ARGUMENT;
+    if (order != EGG_SOLVER_EXACT && order != EGG_SOLVER_RELAXED)
+        return gfail(g, EGG_ERR_INVALID_ARGUMENT, "egg_group_set_solver_order: solver order must be 0 (exact) or 1 (relaxed)");
+    if (std::isnan(relaxation) || relaxation > 2)
+        return gfail(g, EGG_ERR_INVALID_ARGUMENT, "egg_group_set_solver_order: relaxation must be in (0, 2] (<= 0 keeps the current value)");
+    if (order == EGG_SOLVER_RELAXED && g->h.size() > 1) {  // the ghost halo reads the other devices' memory
+        std::string err;
+        const int rc = egghost::relaxed_group_peers(g->h.data(), (int)g->h.size(), &err);
+        if (rc != EGG_OK) return gfail(g, rc, "egg_group_set_solver_order: %s", err.c_str());
+    }
+    if (relaxation > 0)
+        for (size_t k = 0; k < g->h.size(); ++k) GTRY(g, k, egg_set_option(g->h[k], EGG_OPT_RELAXATION, relaxation));
+    // (back to exact: every handle leaves relaxed order and re-tiles; the exact protocol hands islands over again)
+    for (size_t k = 0; k < g->h.size(); ++k) GTRY(g, k, egg_set_option(g->h[k], EGG_OPT_SOLVER_ORDER, (double)order));
+    if (order != g->order) g->budget_stale = true;
+    g->order = order;
+    return EGG_OK;
+}
+
+int egg_group_get_halo_counters(const egg_group *g, int64_t *passes, int64_t *records, int64_t *bytes) {
+    if (!g) return EGG_ERR_INVALID_ARGUMENT;
+    if (passes) *passes = g->halo_passes;
+    if (records) *records = g->halo_records;
+    if (bytes) *bytes = g->halo_records * kGhostRecordBytes;
     return EGG_OK;
 }
 

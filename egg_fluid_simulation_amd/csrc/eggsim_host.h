@@ -8,6 +8,7 @@
 //   eggsim_host_abi.hip     the extern "C" entry points of include/eggsim.h (except the renderer's)
 //   eggsim_host_render.hip  egg_render* : the headless renderer's host side
 //   eggsim_host_relaxed.hip _step in relaxed order (EGG_OPT_SOLVER_ORDER = 1): the launches of eggsim_relaxed.hip
+//   eggsim_host_relaxed_group.hip  the same step over the handles of a device group, with per-pass ghost halos
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -64,6 +65,15 @@ extern "C" __global__ void egg_rx_insert_kernel(EggRelaxedArgs A);
 extern "C" __global__ void egg_rx_scatter_kernel(EggRelaxedArgs A);
 extern "C" __global__ void egg_rx_rank_kernel(EggRelaxedArgs A);
 extern "C" __global__ void egg_rx_gather_kernel(EggRelaxedArgs A);
+extern "C" __global__ void egg_rx_begin_group_kernel(EggRelaxedGroupArgs A);
+extern "C" __global__ void egg_rx_mid_group_kernel(EggRelaxedGroupArgs A);
+extern "C" __global__ void egg_rx_insert_group_kernel(EggRelaxedGroupArgs A);
+extern "C" __global__ void egg_rx_scatter_group_kernel(EggRelaxedGroupArgs A);
+extern "C" __global__ void egg_rx_rank_group_kernel(EggRelaxedGroupArgs A);
+extern "C" __global__ void egg_rx_gather_group_kernel(EggRelaxedGroupArgs A);
+extern "C" __global__ void egg_rx_gkey_kernel(const int32_t *, const int32_t *, const int32_t *, int, int32_t *);
+extern "C" __global__ void egg_rx_pack_kernel(EggRxPackArgs P);
+extern "C" __global__ void egg_rx_unpack_kernel(EggRxUnpackArgs U);
 extern "C" __global__ void egg_render_count_kernel(EggRenderArgs A);
 extern "C" __global__ void egg_render_fill_kernel(EggRenderArgs A);
 extern "C" __global__ void egg_render_scan_kernel(EggRenderArgs A);
@@ -217,6 +227,19 @@ struct RelaxedBufs {
     uint64_t atoms_gen = ~0ull;           // System::atoms_gen p_atom was built for
     PinnedBuf<unsigned long long> h_status;
     PinnedBuf<double> h_targets;
+    // device groups (eggsim_host_relaxed_group.hip): entries n.. are ghosts of the other handles' particles
+    DevBuf<int32_t> ekey, sloc, abase;    // [n + ghosts] global keys, [n + ghosts] entry of a grouped slot, [atoms] key base
+    DevBuf<double2> gwr;                  // [ghosts] (inverse mass, radius)
+    DevBuf<EggGhost> send;                // [receivers][n] this handle's ghost records for the others
+    std::vector<uint64_t> key_sig;        // every handle's atoms_gen when the keys were built
+    hipEvent_t ev_box[2] = {nullptr, nullptr}, ev_pack[2] = {nullptr, nullptr};  // by pass parity
+    RelaxedBufs() = default;
+    RelaxedBufs(const RelaxedBufs &) = delete;
+    RelaxedBufs &operator=(const RelaxedBufs &) = delete;
+    ~RelaxedBufs() {
+        for (hipEvent_t e : {ev_box[0], ev_box[1], ev_pack[0], ev_pack[1]})
+            if (e) (void)hipEventDestroy(e);
+    }
 };
 
 struct System {  // one particle type
@@ -426,6 +449,15 @@ int follow_config(egg_handle *h, int w, bool launch);
 // eggsim_host_relaxed.hip
 int relaxed_step(egg_handle *h, double delta, int S, int C);
 void leave_relaxed(egg_handle *h);  // back to exact order: the next exact step re-tiles from the current positions
+int reserve_relaxed(egg_handle *h, System &s, int S, int C, size_t ghosts, size_t words);
+int upload_relaxed_targets(egg_handle *h, System &s);
+EggRelaxedArgs relaxed_args(egg_handle *h, int w, const Env &env);
+void relaxed_commit(egg_handle *h, const Env env[2], int S, int C, double ms);
+
+// eggsim_host_relaxed_group.hip: the relaxed step of a device group (called by eggsim_group.cpp, which declares them
+// itself: it sees only include/eggsim.h).  0 or an EGG_ERR_* code; on failure *error names the device and the reason.
+int relaxed_group_peers(egg_handle *const *hs, int n, std::string *error);
+int relaxed_group_step(egg_handle *const *hs, int n, double delta, int S, int C, int64_t halo_records[1], std::string *error);
 
 }  // namespace egghost
 

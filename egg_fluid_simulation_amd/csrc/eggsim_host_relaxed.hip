@@ -9,22 +9,21 @@
 
 namespace egghost {
 
-namespace {
-
-// buffers of one type for n particles; the cell table has at least 2 n slots (a probe always finds a free one)
-int reserve_relaxed(egg_handle *h, System &s, int S, int C) {
+// buffers of one type for n particles and `ghosts` ghost entries (device groups); the cell table has at least
+// 2 (n + ghosts) slots (a probe always finds a free one); `words` status words (0: the single handle's 1 + S C)
+int reserve_relaxed(egg_handle *h, System &s, int S, int C, size_t ghosts, size_t words) {
     RelaxedBufs &r = s.rx;
-    const size_t n = (size_t)s.n;
+    const size_t n = (size_t)s.n, ne = n + ghosts;
     uint32_t table = 1024;
-    while ((size_t)table < 2 * n) table <<= 1;
-    HIP_TRY(h, r.pos.reserve(n, false, s.stream));
-    HIP_TRY(h, r.pos_next.reserve(n, false, s.stream));
+    while ((size_t)table < 2 * ne) table <<= 1;
+    HIP_TRY(h, r.pos.reserve(ne, false, s.stream));
+    HIP_TRY(h, r.pos_next.reserve(ne, false, s.stream));
     HIP_TRY(h, r.prev.reserve(n, false, s.stream));
-    HIP_TRY(h, r.spos.reserve(n, false, s.stream));
-    HIP_TRY(h, r.swr.reserve(n, false, s.stream));
-    HIP_TRY(h, r.pslot.reserve(n, false, s.stream));
-    HIP_TRY(h, r.tmp.reserve(n, false, s.stream));
-    HIP_TRY(h, r.sidx.reserve(n, false, s.stream));
+    HIP_TRY(h, r.spos.reserve(ne, false, s.stream));
+    HIP_TRY(h, r.swr.reserve(ne, false, s.stream));
+    HIP_TRY(h, r.pslot.reserve(ne, false, s.stream));
+    HIP_TRY(h, r.tmp.reserve(ne, false, s.stream));
+    HIP_TRY(h, r.sidx.reserve(ne, false, s.stream));
     if (r.p_atom.cap < n) r.atoms_gen = ~0ull;  // (a new array: rebuilt below)
     HIP_TRY(h, r.p_atom.reserve(n, false, s.stream));
     if (table != r.table) {
@@ -37,7 +36,7 @@ int reserve_relaxed(egg_handle *h, System &s, int S, int C) {
         r.scan_bytes = bytes;
         r.table = table;
     }
-    const size_t words = 1 + (size_t)S * C;
+    if (!words) words = 1 + (size_t)S * C;
     HIP_TRY(h, r.status.reserve(words, false, s.stream));
     HIP_TRY(h, r.h_status.reserve(words));
     return EGG_OK;
@@ -71,8 +70,8 @@ int upload_relaxed_targets(egg_handle *h, System &s) {
     return EGG_OK;
 }
 
-// every launch of one type's step on its stream
-int launch_relaxed(egg_handle *h, int w, const Env &env, int S, int C, int *launches) {
+// the kernels' arguments for one type's step (the group fields null: a single handle)
+EggRelaxedArgs relaxed_args(egg_handle *h, int w, const Env &env) {
     System &s = h->sys[w];
     RelaxedBufs &r = s.rx;
     const int n = (int)s.n;
@@ -115,6 +114,17 @@ int launch_relaxed(egg_handle *h, int w, const Env &env, int S, int C, int *laun
     A.overlap = s.cfg.collision_overlap_factor;
     A.cell_size = env.cell;
     A.omega = h->opt_relaxation;
+    return A;
+}
+
+namespace {
+
+// every launch of one type's step on its stream
+int launch_relaxed(egg_handle *h, int w, const Env &env, int S, int C, int *launches) {
+    System &s = h->sys[w];
+    RelaxedBufs &r = s.rx;
+    const int n = (int)s.n;
+    EggRelaxedArgs A = relaxed_args(h, w, env);
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
     int k = 0;
     HIP_TRY(h, hipMemsetAsync(r.status.p, 0, (1 + (size_t)S * C) * 8, s.stream));
@@ -161,7 +171,7 @@ int relaxed_step(egg_handle *h, double delta, int S, int C) {  // L:1722-1989, c
         System &s = h->sys[w];
         if (s.n == 0) continue;
         if (s.n > (int64_t)(1 << 29)) return fail(h, EGG_ERR_UNSUPPORTED, "relaxed order: more than 2^29 particles of one type");
-        int rc = reserve_relaxed(h, s, S, C);
+        int rc = reserve_relaxed(h, s, S, C, 0, 0);
         if (rc == EGG_OK) rc = upload_relaxed_targets(h, s);
         if (rc != EGG_OK) return rc;
         if (h->opt_timing) HIP_TRY(h, hipEventRecord(s.ev0, s.stream));
@@ -186,7 +196,12 @@ int relaxed_step(egg_handle *h, double delta, int S, int C) {  // L:1722-1989, c
     }
     if (bad)  // nothing is committed: [cur] still holds the state before the step
         return fail(h, EGG_ERR_UNSUPPORTED, "relaxed order: a position is NaN or its spatial-hash cell lies outside +-2^30");
-    // commit
+    relaxed_commit(h, env, S, C, ms);
+    return EGG_OK;
+}
+
+// the commit of a relaxed step whose end kernels have run: flip cur, statistics from the status words read back
+void relaxed_commit(egg_handle *h, const Env env[2], int S, int C, double ms) {
     for (int w = 0; w < 2; ++w) {
         System &s = h->sys[w];
         h->stats.budget[w] = env[w].budget;
@@ -213,7 +228,6 @@ int relaxed_step(egg_handle *h, double delta, int S, int C) {  // L:1722-1989, c
     }
     h->stats.steps++;
     h->stats.relaxed_steps++;
-    return EGG_OK;
 }
 
 void leave_relaxed(egg_handle *h) {

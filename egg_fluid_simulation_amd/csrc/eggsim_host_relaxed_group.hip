@@ -1,0 +1,312 @@
+// eggsim_host_relaxed_group.hip -- one relaxed-order _step over the handles of a device group
+// (eggsim_group.cpp), with a per-pass ghost halo instead of hand-overs.  The results equal one relaxed handle holding
+// every batch, bit for bit.
+//
+// Per particle type and collision pass p, on every handle k that holds particles of the type:
+//   * the kernel that wrote the positions of pass p (egg_rx_begin / mid, or the gather of pass p - 1) recorded their
+//     cell box into k's status words; k records ev_box;
+//   * every sender j waits for the ev_box of the others, packs its particles within one cell of each receiver's box
+//     into its own send buffers (egg_rx_pack_kernel), records ev_pack;
+//   * k waits for the ev_pack of the others, pulls their records for it into its ghost entries (egg_rx_unpack_kernel)
+//     and runs insert .. gather over local particles + ghosts.  The gather writes local positions only.
+// Every event is recorded on the host before any wait on it is enqueued: streams of different handles may share a
+// hardware queue, and a wait must never sit in a queue ahead of the work it waits for.  Pass p + 1's pack waits for
+// the receiver's box of p + 1, which the receiver records after it has read pass p's records: a send buffer is never
+// overwritten while it is being read.
+//
+// The step commits on every handle or on none: the status words of all handles come back after the passes (one host
+// synchronise), and the end kernels that write [cur ^ 1] run only if no handle flagged a bad cell.
+#include <hipcub/hipcub.hpp>
+
+#include "eggsim_host.h"
+
+namespace egghost {
+
+namespace {
+
+// status words of one type in a group step: P = S C passes, nq handles holding the type
+struct Layout {
+    size_t P, nq;
+    size_t box(size_t p) const { return 1 + P + 4 * p; }          // 4 words: cell box of pass p's positions
+    size_t ghosts(size_t p) const { return 1 + 5 * P + p; }       // ghost entries this handle received in pass p
+    size_t sent(size_t p, size_t m) const { return 1 + 6 * P + p * nq + m; }  // records sent to participant m in pass p
+    size_t words() const { return 1 + 6 * P + P * nq; }
+};
+
+int device_fail(egg_handle *const *hs, int k, std::string *error, int rc) {
+    char buf[64];
+    snprintf(buf, sizeof buf, "device %d: ", k);
+    *error = buf + hs[k]->error;
+    return rc;
+}
+
+#define GK_TRY(k, expr)                                                                                            \
+    do {                                                                                                           \
+        const int _rc = (expr);                                                                                    \
+        if (_rc != EGG_OK) return device_fail(hs, (k), error, _rc);                                                \
+    } while (0)
+
+#define GK_HIP(k, expr) GK_TRY(k, [&]() -> int { HIP_TRY(hs[k], (expr)); return EGG_OK; }())
+
+}  // namespace
+
+int relaxed_group_peers(egg_handle *const *hs, int n, std::string *error) {
+    if (n > EGG_RX_MAX_GROUP) {
+        *error = "relaxed order: a device group of more than 16 handles";
+        return EGG_ERR_UNSUPPORTED;
+    }
+    for (int a = 0; a < n; ++a)
+        for (int b = 0; b < n; ++b) {
+            const int da = hs[a]->device, db = hs[b]->device;
+            if (da == db) continue;  // handles on one device need nothing
+            int can = 0;
+            if (hipDeviceCanAccessPeer(&can, da, db) != hipSuccess || !can) {
+                char buf[160];
+                snprintf(buf, sizeof buf, "relaxed order: device %d cannot access device %d (peer access is needed for the ghost halo)", da, db);
+                *error = buf;
+                return EGG_ERR_UNSUPPORTED;
+            }
+            (void)hipSetDevice(da);
+            const hipError_t e = hipDeviceEnablePeerAccess(db, 0);
+            if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) {
+                (void)hipGetLastError();
+                char buf[160];
+                snprintf(buf, sizeof buf, "relaxed order: enabling peer access from device %d to %d failed: %s", da, db, hipGetErrorString(e));
+                *error = buf;
+                return EGG_ERR_UNSUPPORTED;
+            }
+            (void)hipGetLastError();  // (hipErrorPeerAccessAlreadyEnabled is sticky as the last error)
+        }
+    return EGG_OK;
+}
+
+int relaxed_group_step(egg_handle *const *hs, int nh, double delta, int S, int C, int64_t halo_records[1], std::string *error) {
+    if (nh > EGG_RX_MAX_GROUP) {
+        *error = "relaxed order: a device group of more than 16 handles";
+        return EGG_ERR_UNSUPPORTED;
+    }
+    Env env[EGG_RX_MAX_GROUP][2];
+    int launches[EGG_RX_MAX_GROUP] = {0};
+    for (int k = 0; k < nh; ++k) {
+        egg_handle *h = hs[k];
+        (void)hipSetDevice(h->device);
+        const double sub_delta = std::max(delta / S, h->sys[0].cfg.eps);
+        for (int w = 0; w < 2; ++w) {
+            System &s = h->sys[w];
+            env[k][w] = make_env(s.cfg, sub_delta, h->budget_particles[w] >= 0 ? h->budget_particles[w] : s.n);
+            GK_TRY(k, follow_config(h, w, true));
+            GK_TRY(k, upload_atoms(h, w));
+        }
+    }
+    const size_t P = (size_t)S * C;
+    std::vector<int> q[2];
+    Layout L[2];
+    EggRelaxedGroupArgs A[2][EGG_RX_MAX_GROUP];
+    int64_t entries[2][EGG_RX_MAX_GROUP] = {};  // local particles + ghost capacity
+    for (int w = 0; w < 2; ++w) {
+        int64_t total = 0;
+        for (int k = 0; k < nh; ++k)
+            if (hs[k]->sys[w].n > 0) {
+                q[w].push_back(k);
+                total += hs[k]->sys[w].n;
+            }
+        if (total > (int64_t)(1 << 29)) {
+            *error = "relaxed order: more than 2^29 particles of one type in the group";
+            return EGG_ERR_UNSUPPORTED;
+        }
+        L[w] = Layout{P, q[w].size()};
+        if (q[w].empty()) continue;
+        // global keys: a batch's particles start at the sum of the type's counts over the live batches of smaller id
+        // (every handle lays its batches out in ascending id: the key of particle i is base + its place in its atom)
+        std::vector<uint64_t> sig((size_t)nh);
+        for (int k = 0; k < nh; ++k) sig[(size_t)k] = hs[k]->sys[w].atoms_gen;
+        std::vector<std::pair<int64_t, int64_t>> sizes;  // (batch key, particles)
+        bool any_rebuild = false;
+        for (int k : q[w])
+            any_rebuild |= hs[k]->sys[w].rx.key_sig != sig || hs[k]->sys[w].rx.ekey.cap < (size_t)total;
+        if (any_rebuild)
+            for (int k = 0; k < nh; ++k)
+                for (const Atom &a : hs[k]->sys[w].atoms) sizes.emplace_back(hs[k]->batches[(size_t)a.batch].key, (int64_t)a.count);
+        std::sort(sizes.begin(), sizes.end());
+        std::vector<int64_t> base(sizes.size());
+        for (size_t b = 0, acc = 0; b < sizes.size(); ++b) {
+            base[b] = (int64_t)acc;
+            acc += (size_t)sizes[b].second;
+        }
+        for (int k : q[w]) {
+            egg_handle *h = hs[k];
+            System &s = h->sys[w];
+            RelaxedBufs &r = s.rx;
+            (void)hipSetDevice(h->device);
+            const size_t n = (size_t)s.n, ghosts = (size_t)(total - s.n);
+            entries[w][k] = total;
+            GK_TRY(k, reserve_relaxed(h, s, S, C, ghosts, L[w].words()));
+            GK_TRY(k, upload_relaxed_targets(h, s));
+            const bool rebuild = r.key_sig != sig || r.ekey.cap < n + ghosts;  // (or a new array)
+            GK_HIP(k, r.ekey.reserve(n + ghosts, false, s.stream));
+            GK_HIP(k, r.sloc.reserve(n + ghosts, false, s.stream));
+            GK_HIP(k, r.gwr.reserve(std::max<size_t>(ghosts, 1), false, s.stream));
+            GK_HIP(k, r.send.reserve(q[w].size() * n, false, s.stream));
+            for (hipEvent_t *e : {&r.ev_box[0], &r.ev_box[1], &r.ev_pack[0], &r.ev_pack[1]})
+                if (!*e) GK_HIP(k, hipEventCreateWithFlags(e, hipEventDisableTiming));
+            if (rebuild) {
+                const size_t na = s.atoms.size();
+                std::vector<int32_t> ab(na + 1, 0);
+                for (size_t a = 0; a < na; ++a) {
+                    const std::pair<int64_t, int64_t> key(h->batches[(size_t)s.atoms[a].batch].key, (int64_t)s.atoms[a].count);
+                    ab[a] = (int32_t)base[(size_t)(std::lower_bound(sizes.begin(), sizes.end(), key) - sizes.begin())];
+                }
+                GK_HIP(k, r.abase.reserve(na + 1, false, s.stream));
+                GK_HIP(k, hipMemcpyAsync(r.abase.p, ab.data(), (na + 1) * 4, hipMemcpyHostToDevice, s.stream));
+                hipLaunchKernelGGL(egg_rx_gkey_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s.stream,
+                                   r.p_atom.p, s.d_atom_offset.p, r.abase.p, (int)n, r.ekey.p);
+                ++launches[k];
+                GK_HIP(k, hipStreamSynchronize(s.stream));  // (ab is pageable host memory; membership changes only)
+                r.key_sig = sig;
+            }
+            GK_HIP(k, hipMemsetAsync(r.status.p, 0, L[w].words() * 8, s.stream));
+            EggRelaxedGroupArgs &a = A[w][k];
+            a.a = relaxed_args(h, w, env[k][w]);
+            a.g = EggRxGroupFields{};
+            a.g.ekey = r.ekey.p;
+            a.g.sloc = r.sloc.p;
+            a.g.gwr = r.gwr.p;
+        }
+    }
+    // the passes, one type after the other (the types are independent: their streams overlap)
+    for (int w = 0; w < 2; ++w) {
+        const std::vector<int> &Q = q[w];
+        const size_t nq = Q.size();
+        for (int sub = 0; sub < S; ++sub) {
+            for (size_t m = 0; m < nq; ++m) {
+                const int k = Q[m];
+                System &s = hs[k]->sys[w];
+                EggRelaxedGroupArgs &a = A[w][k];
+                (void)hipSetDevice(hs[k]->device);
+                a.g.box = s.rx.status.p + L[w].box((size_t)sub * C);
+                hipLaunchKernelGGL(sub == 0 ? egg_rx_begin_group_kernel : egg_rx_mid_group_kernel, dim3((unsigned)((s.n + 255) / 256)),
+                                   dim3(256), 0, s.stream, a);
+                ++launches[k];
+            }
+            for (int c = 0; c < C; ++c) {
+                const size_t p = (size_t)sub * C + c;
+                const int par = (int)(p & 1);
+                for (size_t m = 0; m < nq; ++m) {
+                    const int k = Q[m];
+                    (void)hipSetDevice(hs[k]->device);
+                    GK_HIP(k, hipEventRecord(hs[k]->sys[w].rx.ev_box[par], hs[k]->sys[w].stream));
+                }
+                for (size_t mj = 0; mj < nq && nq > 1; ++mj) {  // senders
+                    const int j = Q[mj];
+                    System &s = hs[j]->sys[w];
+                    (void)hipSetDevice(hs[j]->device);
+                    EggRxPackArgs pk{};
+                    pk.n = (int)s.n;
+                    pk.cell_size = env[j][w].cell;
+                    pk.pos = A[w][j].a.pos;
+                    pk.inv_mass = s.inv_mass.p;
+                    pk.radius = s.radius.p;
+                    pk.ekey = s.rx.ekey.p;
+                    for (size_t mk = 0; mk < nq; ++mk) {
+                        if (mk == mj) continue;
+                        const int k = Q[mk];
+                        GK_HIP(j, hipStreamWaitEvent(s.stream, hs[k]->sys[w].rx.ev_box[par], 0));
+                        pk.box[pk.n_recv] = hs[k]->sys[w].rx.status.p + L[w].box(p);
+                        pk.send[pk.n_recv] = s.rx.send.p + mk * (size_t)s.n;
+                        pk.count[pk.n_recv] = s.rx.status.p + L[w].sent(p, mk);
+                        ++pk.n_recv;
+                    }
+                    hipLaunchKernelGGL(egg_rx_pack_kernel, dim3((unsigned)((s.n + 255) / 256)), dim3(256), 0, s.stream, pk);
+                    ++launches[j];
+                    GK_HIP(j, hipEventRecord(s.rx.ev_pack[par], s.stream));
+                }
+                for (size_t mk = 0; mk < nq; ++mk) {  // receivers
+                    const int k = Q[mk];
+                    egg_handle *h = hs[k];
+                    System &s = h->sys[w];
+                    RelaxedBufs &r = s.rx;
+                    EggRelaxedGroupArgs &a = A[w][k];
+                    (void)hipSetDevice(h->device);
+                    a.a.pass = (int)p;
+                    a.g.n_ghost = r.status.p + L[w].ghosts(p);
+                    if (nq > 1) {
+                        EggRxUnpackArgs up{};
+                        up.n = (int)s.n;
+                        up.pos = a.a.pos;
+                        up.gwr = r.gwr.p;
+                        up.ekey = r.ekey.p;
+                        up.n_ghost = r.status.p + L[w].ghosts(p);
+                        int64_t most = 0;
+                        for (size_t mj = 0; mj < nq; ++mj) {
+                            if (mj == mk) continue;
+                            System &sj = hs[Q[mj]]->sys[w];
+                            GK_HIP(k, hipStreamWaitEvent(s.stream, sj.rx.ev_pack[par], 0));
+                            up.recs[up.n_send] = sj.rx.send.p + mk * (size_t)sj.n;
+                            up.count[up.n_send] = sj.rx.status.p + L[w].sent(p, mk);
+                            ++up.n_send;
+                            most = std::max(most, sj.n);
+                        }
+                        hipLaunchKernelGGL(egg_rx_unpack_kernel, dim3((unsigned)((most + 255) / 256), (unsigned)up.n_send), dim3(256), 0,
+                                           s.stream, up);
+                        ++launches[k];
+                    }
+                    a.g.box = c + 1 < C ? r.status.p + L[w].box(p + 1) : nullptr;  // (the next sub-step's begins in mid)
+                    const dim3 grid((unsigned)((entries[w][k] + 255) / 256)), block(256);  // (ghost count read on the device)
+                    GK_HIP(k, hipMemsetAsync(r.hkey.p, 0xFF, (size_t)r.table * 8, s.stream));
+                    GK_HIP(k, hipMemsetAsync(r.hcount.p, 0, ((size_t)r.table + 1) * 4, s.stream));
+                    hipLaunchKernelGGL(egg_rx_insert_group_kernel, grid, block, 0, s.stream, a);
+                    size_t bytes = r.scan_bytes;
+                    GK_HIP(k, hipcub::DeviceScan::ExclusiveSum(r.scan_tmp.p, bytes, r.hcount.p, r.hstart.p, (int)r.table + 1, s.stream));
+                    hipLaunchKernelGGL(egg_rx_scatter_group_kernel, grid, block, 0, s.stream, a);
+                    hipLaunchKernelGGL(egg_rx_rank_group_kernel, grid, block, 0, s.stream, a);
+                    hipLaunchKernelGGL(egg_rx_gather_group_kernel, grid, block, 0, s.stream, a);
+                    launches[k] += 5;
+                    std::swap(a.a.pos, a.a.pos_next);
+                }
+            }
+        }
+    }
+    // all handles or none: the status words (bad cells, pair counts, ghost counts) of every handle, then the end kernels
+    for (int w = 0; w < 2; ++w)
+        for (int k : q[w]) {
+            System &s = hs[k]->sys[w];
+            (void)hipSetDevice(hs[k]->device);
+            GK_HIP(k, hipGetLastError());
+            GK_HIP(k, hipMemcpyAsync(s.rx.h_status.p, s.rx.status.p, L[w].words() * 8, hipMemcpyDeviceToHost, s.stream));
+        }
+    bool bad = false;
+    for (int w = 0; w < 2; ++w)
+        for (int k : q[w]) {
+            System &s = hs[k]->sys[w];
+            (void)hipSetDevice(hs[k]->device);
+            GK_HIP(k, wait_step(s.stream));
+            bad |= s.rx.h_status.p[0] != 0;
+        }
+    if (bad) {  // nothing is committed anywhere: every [cur] and [cur ^ 1] is as before the step
+        *error = "relaxed order: a position is NaN or its spatial-hash cell lies outside +-2^30";
+        return EGG_ERR_UNSUPPORTED;
+    }
+    int64_t records = 0;
+    for (int w = 0; w < 2; ++w)
+        for (int k : q[w]) {
+            System &s = hs[k]->sys[w];
+            (void)hipSetDevice(hs[k]->device);
+            hipLaunchKernelGGL(egg_rx_end_kernel, dim3((unsigned)((s.n + 255) / 256)), dim3(256), 0, s.stream, A[w][k].a);
+            ++launches[k];
+            GK_HIP(k, hipGetLastError());
+            for (size_t p = 0; p < P; ++p) records += (int64_t)s.rx.h_status.p[L[w].ghosts(p)];
+        }
+    for (int w = 0; w < 2; ++w)
+        for (int k : q[w]) {
+            (void)hipSetDevice(hs[k]->device);
+            GK_HIP(k, wait_step(hs[k]->sys[w].stream));
+        }
+    for (int k = 0; k < nh; ++k) {
+        hs[k]->stats.kernel_launches += launches[k];
+        relaxed_commit(hs[k], env[k], S, C, 0.0);
+    }
+    halo_records[0] += records;
+    return EGG_OK;
+}
+
+}  // namespace egghost

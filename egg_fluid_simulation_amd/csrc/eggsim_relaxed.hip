@@ -14,6 +14,12 @@
 //   egg_rx_gather_kernel   the 3x3 cells of every particle in the reference's loop order (x offset outer, y inner,
 //                          L:1568-1569), the pair corrections in that order, the averaged move
 //
+// In a device group (eggsim_host_relaxed_group.hip) every particle has a global key, its index in one handle holding
+// every batch, and the pass runs over the local particles plus read-only ghosts of the neighbours': the kernels that
+// write positions record their cell box, egg_rx_pack_kernel (sender) and egg_rx_unpack_kernel (receiver) move the
+// ghosts, and the key replaces the index in the rank order, the pair orientation and the pair count.  On a single
+// handle (the G = false instantiations) the key is the index and nothing else changes.
+//
 // All arithmetic is IEEE double in the order of the definition: compile with -ffp-contract=off.
 #include <hip/hip_runtime.h>
 #include "eggsim_device.h"
@@ -40,6 +46,41 @@ __device__ __forceinline__ unsigned long long rx_key(int32_t cx, int32_t cy) {
     return ((unsigned long long)(uint32_t)(cx + 0x40000000) << 32) | (unsigned long long)(uint32_t)(cy + 0x40000000);
 }
 
+// Cell box of the positions a wave writes (group only): every lane calls it, one atomic per word and wave.
+__device__ __forceinline__ void rx_box(unsigned long long *box, bool have, double2 p, double cell) {
+    int32_t cx = 0, cy = 0;
+    if (have) (void)rx_cell(p, cell, cx, cy);  // (a bad cell was or will be flagged by the insert kernel)
+    const unsigned long long ux = (unsigned long long)((long long)cx + EGG_RX_BOX_BIAS);
+    const unsigned long long uy = (unsigned long long)((long long)cy + EGG_RX_BOX_BIAS);
+    unsigned long long w0 = have ? (1ull << 32) - ux : 0ull, w1 = have ? ux : 0ull;
+    unsigned long long w2 = have ? (1ull << 32) - uy : 0ull, w3 = have ? uy : 0ull;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        w0 = max(w0, __shfl_xor(w0, d, 64));
+        w1 = max(w1, __shfl_xor(w1, d, 64));
+        w2 = max(w2, __shfl_xor(w2, d, 64));
+        w3 = max(w3, __shfl_xor(w3, d, 64));
+    }
+    if ((threadIdx.x & 63) == 0 && w1) {
+        atomicMax(&box[0], w0);
+        atomicMax(&box[1], w1);
+        atomicMax(&box[2], w2);
+        atomicMax(&box[3], w3);
+    }
+}
+
+// Wave-aggregated append: the lanes with `take` get consecutive slots of *counter; returns this lane's slot.
+__device__ __forceinline__ int rx_append(unsigned long long *counter, bool take) {
+    const unsigned long long mask = __ballot(take);
+    if (!mask) return 0;
+    const int lane = (int)(threadIdx.x & 63);
+    const int leader = __ffsll((long long)mask) - 1;
+    unsigned long long base = 0;
+    if (lane == leader) base = atomicAdd(counter, (unsigned long long)__popcll(mask));
+    base = __shfl(base, leader, 64);
+    return (int)base + __popcll(mask & ((1ull << lane) - 1ull));
+}
+
 __device__ __forceinline__ uint32_t rx_hash(unsigned long long k) {  // the 64-bit finaliser of MurmurHash3
     k ^= k >> 33;
     k *= 0xff51afd7ed558ccdull;
@@ -60,33 +101,53 @@ extern "C" __global__ void __launch_bounds__(256) egg_rx_atoms_kernel(const int3
     for (int q = threadIdx.x; q < cnt; q += 256) p_atom[g0 + q] = a;
 }
 
-// Start of a step: pre-solve + follow of the first sub-step from the committed state.
-extern "C" __global__ void __launch_bounds__(256) egg_rx_begin_kernel(EggRelaxedArgs A) {
+// The kernels that take part in a device group come in two instantiations: G = false is the single handle's (the key
+// is the index, no ghosts, no box; EggRelaxedArgs alone), G = true the group's (EggRelaxedGroupArgs).  The G = false
+// instantiations compile to the same instructions as the kernels before groups existed.  (rx_insert and rx_gather
+// take the arguments by value: by reference, the compiler schedules them differently.)
+template <bool G>
+__device__ __forceinline__ void rx_begin(const EggRelaxedArgs &A, const EggRxGroupFields &X) {
     const int i = (int)(blockIdx.x * 256 + threadIdx.x);
-    if (i >= A.n) return;
-    const int atom = A.p_atom[i];
-    const double2 ps = make_double2(A.x_in[i], A.y_in[i]);
-    double2 v = make_double2(A.vx_in[i], A.vy_in[i]);
-    double2 out;
-    egg_pre_follow(A.damping, A.sub_delta, A.eps, A.follow_compliance, ps, v, A.inv_mass[i], A.atom_tx[atom],
-                   A.atom_ty[atom], A.atom_fd[atom], out);
-    A.prev[i] = ps;
-    A.pos[i] = out;
+    const bool live = i < A.n;
+    if (!G && !live) return;
+    double2 out = make_double2(0.0, 0.0);
+    if (live) {
+        const int atom = A.p_atom[i];
+        const double2 ps = make_double2(A.x_in[i], A.y_in[i]);
+        double2 v = make_double2(A.vx_in[i], A.vy_in[i]);
+        egg_pre_follow(A.damping, A.sub_delta, A.eps, A.follow_compliance, ps, v, A.inv_mass[i], A.atom_tx[atom],
+                       A.atom_ty[atom], A.atom_fd[atom], out);
+        A.prev[i] = ps;
+        A.pos[i] = out;
+    }
+    if (G) rx_box(X.box, live, out, A.cell_size);
 }
 
-// Between two sub-steps: post-solve of the one (L:1690-1693), pre-solve + follow of the next.
-extern "C" __global__ void __launch_bounds__(256) egg_rx_mid_kernel(EggRelaxedArgs A) {
+template <bool G>
+__device__ __forceinline__ void rx_mid(const EggRelaxedArgs &A, const EggRxGroupFields &X) {
     const int i = (int)(blockIdx.x * 256 + threadIdx.x);
-    if (i >= A.n) return;
-    const int atom = A.p_atom[i];
-    const double2 ps = A.pos[i], pv = A.prev[i];
-    double2 v = make_double2((ps.x - pv.x) / A.sub_delta, (ps.y - pv.y) / A.sub_delta);
-    double2 out;
-    egg_pre_follow(A.damping, A.sub_delta, A.eps, A.follow_compliance, ps, v, A.inv_mass[i], A.atom_tx[atom],
-                   A.atom_ty[atom], A.atom_fd[atom], out);
-    A.prev[i] = ps;
-    A.pos[i] = out;
+    const bool live = i < A.n;
+    if (!G && !live) return;
+    double2 out = make_double2(0.0, 0.0);
+    if (live) {
+        const int atom = A.p_atom[i];
+        const double2 ps = A.pos[i], pv = A.prev[i];
+        double2 v = make_double2((ps.x - pv.x) / A.sub_delta, (ps.y - pv.y) / A.sub_delta);
+        egg_pre_follow(A.damping, A.sub_delta, A.eps, A.follow_compliance, ps, v, A.inv_mass[i], A.atom_tx[atom],
+                       A.atom_ty[atom], A.atom_fd[atom], out);
+        A.prev[i] = ps;
+        A.pos[i] = out;
+    }
+    if (G) rx_box(X.box, live, out, A.cell_size);
 }
+
+// Start of a step: pre-solve + follow of the first sub-step from the committed state.
+extern "C" __global__ void __launch_bounds__(256) egg_rx_begin_kernel(EggRelaxedArgs A) { rx_begin<false>(A, EggRxGroupFields{}); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_begin_group_kernel(EggRelaxedGroupArgs A) { rx_begin<true>(A.a, A.g); }
+
+// Between two sub-steps: post-solve of the one (L:1690-1693), pre-solve + follow of the next.
+extern "C" __global__ void __launch_bounds__(256) egg_rx_mid_kernel(EggRelaxedArgs A) { rx_mid<false>(A, EggRxGroupFields{}); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_mid_group_kernel(EggRelaxedGroupArgs A) { rx_mid<true>(A.a, A.g); }
 
 // End of the step: post-solve of the last sub-step into the [cur ^ 1] arrays -- unless a pass flagged a bad cell: the
 // step then fails and [cur ^ 1] keeps the positions at the start of the last committed step (EGG_FIELD_LAST_X / Y).
@@ -100,11 +161,19 @@ extern "C" __global__ void __launch_bounds__(256) egg_rx_end_kernel(EggRelaxedAr
     A.vy_out[i] = (ps.y - pv.y) / A.sub_delta;
 }
 
-// Cell of every particle, its slot in the cell table, the slot's particle count.  (The table is at least twice as
-// large as the particle count: a probe always ends.)
-extern "C" __global__ void __launch_bounds__(256) egg_rx_insert_kernel(EggRelaxedArgs A) {
+
+// Entries of the pass: the local particles and, in a group, this pass's ghosts.
+template <bool G>
+__device__ __forceinline__ int rx_entries(const EggRelaxedArgs &A, const EggRxGroupFields &X) {
+    return G ? A.n + (int)*X.n_ghost : A.n;
+}
+
+// Cell of every entry, its slot in the cell table, the slot's count.  (The table is at least twice as large as the
+// entry count: a probe always ends.)
+template <bool G>
+__device__ __forceinline__ void rx_insert(EggRelaxedArgs A, const EggRxGroupFields &X) {
     const int i = (int)(blockIdx.x * 256 + threadIdx.x);
-    if (i >= A.n) return;
+    if (i >= rx_entries<G>(A, X)) return;
     int32_t cx, cy;
     if (!rx_cell(A.pos[i], A.cell_size, cx, cy)) A.status[0] = 1;  // (the step fails; cell (0, 0) keeps the pass in bounds)
     const unsigned long long key = rx_key(cx, cy);
@@ -118,37 +187,47 @@ extern "C" __global__ void __launch_bounds__(256) egg_rx_insert_kernel(EggRelaxe
     A.pslot[i] = (int32_t)h;
 }
 
-// Every particle into its slot's range of grouped positions [hstart[h], hstart[h + 1]), in whatever order the
-// atomics give (the counts are used up: nothing reads them afterwards).
-extern "C" __global__ void __launch_bounds__(256) egg_rx_scatter_kernel(EggRelaxedArgs A) {
+// Every entry into its slot's range of grouped positions [hstart[h], hstart[h + 1]), in whatever order the atomics
+// give, as its key (the counts are used up: nothing reads them afterwards).
+template <bool G>
+__device__ __forceinline__ void rx_scatter(const EggRelaxedArgs &A, const EggRxGroupFields &X) {
     const int i = (int)(blockIdx.x * 256 + threadIdx.x);
-    if (i >= A.n) return;
+    if (i >= rx_entries<G>(A, X)) return;
     const int h = A.pslot[i];
     const uint32_t k = atomicSub(&A.hcount[h], 1u) - 1u;
-    A.tmp[A.hstart[h] + k] = i;
+    A.tmp[A.hstart[h] + k] = G ? X.ekey[i] : i;
 }
 
-// Inside a cell: ascending particle index (a particle's place = how many of its cell's particles have a smaller one),
-// with the grouped copies of what the gather reads.
-extern "C" __global__ void __launch_bounds__(256) egg_rx_rank_kernel(EggRelaxedArgs A) {
+// Inside a cell: ascending key (a particle's place = how many of its cell's particles have a smaller one), with the
+// grouped copies of what the gather reads.  sidx holds the key; sloc (group only) the entry.
+template <bool G>
+__device__ __forceinline__ void rx_rank(const EggRelaxedArgs &A, const EggRxGroupFields &X) {
     const int i = (int)(blockIdx.x * 256 + threadIdx.x);
-    if (i >= A.n) return;
+    if (i >= rx_entries<G>(A, X)) return;
+    const int key = G ? X.ekey[i] : i;
     const int h = A.pslot[i];
     const int st = (int)A.hstart[h], en = (int)A.hstart[h + 1];
     int rank = 0;
-    for (int e = st; e < en; ++e) rank += A.tmp[e] < i ? 1 : 0;
+    for (int e = st; e < en; ++e) rank += A.tmp[e] < key ? 1 : 0;
     const int t = st + rank;
-    A.sidx[t] = i;
+    A.sidx[t] = key;
+    if (G) X.sloc[t] = i;
     A.spos[t] = A.pos[i];
-    A.swr[t] = make_double2(A.inv_mass[i], A.radius[i]);
+    A.swr[t] = (!G || i < A.n) ? make_double2(A.inv_mass[i], A.radius[i]) : X.gwr[i - A.n];
 }
 
-// The relaxed pass of DESIGN.md section 2.7, one thread per grouped slot (threads of a wave share cells).
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_kernel(EggRelaxedArgs A) {
+// The relaxed pass of DESIGN.md section 2.7, one thread per grouped slot (threads of a wave share cells).  i is the
+// key; in a group a ghost's slot gathers nothing (its own device moves it), and the gather records the box of what it
+// writes when the pass is not the sub-step's last.
+template <bool G>
+__device__ __forceinline__ void rx_gather(EggRelaxedArgs A, const EggRxGroupFields &X) {
     const int t = (int)(blockIdx.x * 256 + threadIdx.x);
     int pairs = 0;
-    if (t < A.n) {
+    bool local = false;  // (group: the slot holds one of this device's particles; gout is its new position)
+    double2 gout = make_double2(0.0, 0.0);
+    if (G ? t < rx_entries<G>(A, X) && X.sloc[t] < A.n : t < A.n) {
         const int i = A.sidx[t];
+        const int me = G ? X.sloc[t] : i;
         const double2 p = A.spos[t], wr = A.swr[t];
         int32_t cx, cy;
         (void)rx_cell(p, A.cell_size, cx, cy);  // (a bad cell was flagged by the insert kernel)
@@ -218,10 +297,94 @@ extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_kernel(EggRelaxe
             out.x = p.x + (sx * A.omega) / (double)n_fired;
             out.y = p.y + (sy * A.omega) / (double)n_fired;
         }
-        A.pos_next[i] = out;
+        A.pos_next[me] = out;
+        if (G) {
+            local = true;
+            gout = out;
+        }
     }
-    // pairs counted (each once: by its smaller index), one atomic per wave
+    // pairs counted (each once: by its smaller key, on the device that holds it), one atomic per wave
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) pairs += __shfl_xor(pairs, d, 64);
     if ((threadIdx.x & 63) == 0 && pairs) atomicAdd(&A.status[1 + A.pass], (unsigned long long)pairs);
+    if (G && X.box) rx_box(X.box, local, gout, A.cell_size);
+}
+
+extern "C" __global__ void __launch_bounds__(256) egg_rx_insert_kernel(EggRelaxedArgs A) { rx_insert<false>(A, EggRxGroupFields{}); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_insert_group_kernel(EggRelaxedGroupArgs A) { rx_insert<true>(A.a, A.g); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_scatter_kernel(EggRelaxedArgs A) { rx_scatter<false>(A, EggRxGroupFields{}); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_scatter_group_kernel(EggRelaxedGroupArgs A) { rx_scatter<true>(A.a, A.g); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_rank_kernel(EggRelaxedArgs A) { rx_rank<false>(A, EggRxGroupFields{}); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_rank_group_kernel(EggRelaxedGroupArgs A) { rx_rank<true>(A.a, A.g); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_kernel(EggRelaxedArgs A) { rx_gather<false>(A, EggRxGroupFields{}); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_kernel(EggRelaxedGroupArgs A) { rx_gather<true>(A.a, A.g); }
+
+// ---- device groups ----
+
+// global key of every local particle: abase[atom] = particles of the type in the group's batches with smaller ids
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gkey_kernel(const int32_t *p_atom, const int32_t *atom_offset,
+                                                                     const int32_t *abase, int n, int32_t *ekey) {
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (i >= n) return;
+    const int a = p_atom[i];
+    ekey[i] = abase[a] + (i - atom_offset[a]);
+}
+
+// Sender: every local particle whose cell lies in a receiver's cell box grown by one cell on each side goes into that
+// receiver's send buffer, in any order (the receiver's rank kernel orders by key).  At most one record per particle
+// and receiver: a buffer of capacity n cannot overflow.
+extern "C" __global__ void __launch_bounds__(256) egg_rx_pack_kernel(EggRxPackArgs P) {
+    __shared__ long long bx[EGG_RX_MAX_GROUP][4];  // lo x, hi x, lo y, hi y, grown
+    if (threadIdx.x < (unsigned)P.n_recv) {
+        const unsigned long long *b = P.box[threadIdx.x];
+        const unsigned long long w0 = b[0], w1 = b[1], w2 = b[2], w3 = b[3];
+        if (w1 == 0) {  // the receiver wrote no position: nothing is near it
+            bx[threadIdx.x][0] = bx[threadIdx.x][2] = 1;
+            bx[threadIdx.x][1] = bx[threadIdx.x][3] = 0;
+        } else {
+            bx[threadIdx.x][0] = (long long)((1ull << 32) - w0) - EGG_RX_BOX_BIAS - 1;
+            bx[threadIdx.x][1] = (long long)w1 - EGG_RX_BOX_BIAS + 1;
+            bx[threadIdx.x][2] = (long long)((1ull << 32) - w2) - EGG_RX_BOX_BIAS - 1;
+            bx[threadIdx.x][3] = (long long)w3 - EGG_RX_BOX_BIAS + 1;
+        }
+    }
+    __syncthreads();
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    const bool live = i < P.n;
+    int32_t cx = 0, cy = 0;
+    double2 p = make_double2(0.0, 0.0);
+    if (live) {
+        p = P.pos[i];
+        (void)rx_cell(p, P.cell_size, cx, cy);
+    }
+    for (int k = 0; k < P.n_recv; ++k) {
+        const bool take = live && cx >= bx[k][0] && cx <= bx[k][1] && cy >= bx[k][2] && cy <= bx[k][3];
+        const int slot = rx_append(P.count[k], take);
+        if (take) {
+            EggGhost g;
+            g.x = p.x;
+            g.y = p.y;
+            g.inv_mass = P.inv_mass[i];
+            g.radius = P.radius[i];
+            g.key = P.ekey[i];
+            P.send[k][slot] = g;
+        }
+    }
+}
+
+// Receiver: the records every sender packed for it, appended to the ghost entries [n, n + n_ghost).  Grid: x over the
+// largest sender capacity, y over the senders.
+extern "C" __global__ void __launch_bounds__(256) egg_rx_unpack_kernel(EggRxUnpackArgs U) {
+    const int s = (int)blockIdx.y;
+    const int q = (int)(blockIdx.x * 256 + threadIdx.x);
+    const int cnt = (int)*U.count[s];
+    if ((int)(blockIdx.x * 256) >= cnt) return;  // (uniform over the workgroup)
+    const bool take = q < cnt;
+    const int slot = rx_append(U.n_ghost, take);
+    if (take) {
+        const EggGhost r = U.recs[s][q];
+        U.pos[U.n + slot] = make_double2(r.x, r.y);
+        U.gwr[slot] = make_double2(r.inv_mass, r.radius);
+        U.ekey[U.n + slot] = (int32_t)r.key;
+    }
 }

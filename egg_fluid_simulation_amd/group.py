@@ -46,6 +46,7 @@ class SimulationGroup:
         if rc != _ffi.EGG_OK:
             raise EggError("[ERROR] In SimulationGroup.new: " + self._lib.egg_last_error(None).decode())
         self._g = g
+        self._n_issued = 0  # ids issued so far (1 .. _n_issued; never reused)
         self.handles = [_Borrowed(self._lib, self._lib.egg_group_handle(self._g, k)) for k in range(len(devices))]
 
     def __del__(self):
@@ -69,6 +70,7 @@ class SimulationGroup:
             self._g, float(x), float(y), float("nan") if white_radius is None else float(white_radius),
             float("nan") if yolk_radius is None else float(yolk_radius),
             _ffi.DEFAULT_COUNT if white_n is None else int(white_n), _ffi.DEFAULT_COUNT if yolk_n is None else int(yolk_n), C.byref(out)))
+        self._n_issued = max(self._n_issued, out.value)
         return out.value
 
     def remove(self, batch_id):
@@ -103,26 +105,52 @@ class SimulationGroup:
         self._check(self._lib.egg_group_get_counters(self._g, C.byref(m), C.byref(d)))
         return dict(migrations=m.value, discarded_steps=d.value)
 
-    def particles(self, which):
-        """{global id: (x[n], y[n])} over all devices (the batches of a handle are laid out in ascending global id)"""
+    _SOLVER_ORDERS = SimulationHandler._SOLVER_ORDERS
+
+    def set_solver_order(self, order, relaxation=None):
+        """SimulationHandler.set_solver_order for every device handle.  In relaxed order a step runs every collision
+        pass on all devices at once, each over its own particles plus ghost copies of its neighbours' particles near
+        it: no batch is handed over before a step, and the results equal one relaxed handle's bit for bit (DESIGN.md
+        section 2.7).  `relaxation` None keeps the current value."""
+        if order not in self._SOLVER_ORDERS:
+            raise EggError("solver order must be 'exact' or 'relaxed', not %r" % (order,))
+        if relaxation is None:
+            omega = -1.0
+        else:
+            omega = float(relaxation)
+            if not (0.0 < omega <= 2.0):  # (the C entry point reads <= 0 as "keep": refuse it here, as a handle does)
+                raise EggError("relaxation must be in (0, 2], not %r" % (relaxation,))
+        self._check(self._lib.egg_group_set_solver_order(self._g, self._SOLVER_ORDERS[order], omega))
+        self._solver_order = order
+
+    def get_solver_order(self):
+        return getattr(self, "_solver_order", "exact")
+
+    def halo_counters(self):
+        """cumulative over relaxed group steps: collision passes, ghost records received, their bytes"""
+        p, r, b = C.c_int64(), C.c_int64(), C.c_int64()
+        self._check(self._lib.egg_group_get_halo_counters(self._g, C.byref(p), C.byref(r), C.byref(b)))
+        return dict(passes=p.value, records=r.value, bytes=b.value)
+
+    def particles(self, which, fields=("x", "y")):
+        """{global id: (x[n], y[n])} over all devices (the batches of a handle are laid out in ascending global id);
+        `fields` picks other per-particle fields (SimulationHandler.download names)"""
         out = {}
         owners = {}
-        gid = 1
-        while True:
+        for gid in range(1, self._n_issued + 1):  # removed ids are skipped, not the end
             try:
                 owners[gid] = self.owner(gid)
             except EggError:
-                break
-            gid += 1
+                continue
         for k, h in enumerate(self.handles):
             mine = sorted(g for g, (dev, _l) in owners.items() if dev == k)
             if not mine:
                 continue
-            x, y = h.download(which, "x"), h.download(which, "y")
+            cols = [h.download(which, f) for f in fields]
             off = 0
             for g in mine:
                 nw, ny = h.get_n_particles(owners[g][1])
                 n = nw if which == _ffi.WHITE else ny
-                out[g] = (x[off:off + n], y[off:off + n])
+                out[g] = tuple(c[off:off + n] for c in cols)
                 off += n
         return out

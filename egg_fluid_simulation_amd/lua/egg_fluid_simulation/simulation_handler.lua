@@ -63,6 +63,9 @@ typedef struct {
 } egg_render_params;
 int egg_default_render_params(egg_render_params *p);
 int egg_render(egg_handle *h, const egg_render_params *p, float *rgba);
+typedef struct egg_group egg_group;
+int egg_group_set_solver_order(egg_group *g, int32_t order, double relaxation);
+int egg_group_get_halo_counters(const egg_group *g, int64_t *passes, int64_t *records, int64_t *bytes);
 ]]
 
 local lib = ffi.load(os.getenv("EGGSIM_LIB") or "eggsim")

@@ -587,7 +587,8 @@ class SimulationHandler:
         """"exact" (default): the reference's sequential pair order, bit for bit.  "relaxed": every collision pass a
         Jacobi pass with constraint averaging, scaled by `relaxation` in (0, 2] (None keeps the current value) --
         plausible and deterministic, several times faster on large scenes, but not the reference's numbers
-        (DESIGN.md section 2.7).  Relaxed steps are single-device: step_begin / step_end / get_claims raise EggError."""
+        (DESIGN.md section 2.7).  A relaxed handle steps alone or inside a SimulationGroup
+        (SimulationGroup.set_solver_order): step_begin / step_end / get_claims raise EggError."""
         if order not in self._SOLVER_ORDERS:
             raise EggError("solver order must be 'exact' or 'relaxed', not %r" % (order,))
         if relaxation is not None:

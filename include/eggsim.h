@@ -317,9 +317,9 @@ enum {
     EGG_OPT_LEVEL_WALK,             /* packed pipeline, the pass that gives every pair its dependency level: 0 (default) by regime -- out of order for dense islands (> 256 particles) while the groups are no more than the chip's SIMDs, in order otherwise --, 1 always in order, 2 out of order everywhere */
     EGG_OPT_SOLVER_ORDER,           /* 0 (default): exact -- the reference's sequential Gauss-Seidel pair order, bit for bit; 1: relaxed --
                                      * every collision pass a Jacobi pass with constraint averaging: plausible,
-                                     * deterministic, not the reference's numbers.  Relaxed steps are single-device only: egg_step_begin,
-                                     * egg_step_end and egg_get_claims_many return EGG_ERR_UNSUPPORTED, egg_prepare_step does nothing.
-                                     * Refused while a step is in flight. */
+                                     * deterministic, not the reference's numbers.  A relaxed handle steps only by itself or inside an
+                                     * egg_group (egg_group_set_solver_order): egg_step_begin, egg_step_end and egg_get_claims_many
+                                     * return EGG_ERR_UNSUPPORTED, egg_prepare_step does nothing.  Refused while a step is in flight. */
     EGG_OPT_RELAXATION              /* omega of the relaxed pass, in (0, 2] (default EGG_RELAXATION_DEFAULT).  Refused while a step is in flight. */
 };
 #define EGG_SOLVER_EXACT 0
@@ -334,7 +334,11 @@ int egg_set_option(egg_handle *h, int option, double value);
  * added; batches whose claims for a step come within one spatial-hash cell of each other across devices are handed to
  * ONE device before that step runs (exact Gauss-Seidel order cannot cross a cut), so the results equal a
  * single handle's bit for bit.  A collision budget 0.05 N^2 (L:1752-1753) that could bind across devices is refused with
- * EGG_ERR_UNSUPPORTED.  The same device ordinal may appear more than once (several handles on one GPU: testing).
+ * EGG_ERR_UNSUPPORTED.  In relaxed order (egg_group_set_solver_order) nothing is handed over before a step: every
+ * collision pass runs on every device over its own particles plus read-only ghost copies of its neighbours' particles
+ * near it, and the results equal ONE relaxed handle holding every batch, bit for bit.  The same
+ * device ordinal may appear more than once (several handles on one GPU: testing); different ordinals need peer access
+ * for relaxed order.
  * egg_fluid_simulation_amd/sharding.py is the same protocol between processes over RCCL. */
 typedef struct egg_group egg_group;
 int egg_group_create(const egg_config *white, const egg_config *yolk, int32_t n_devices, const int32_t *devices,
@@ -357,6 +361,12 @@ int egg_group_step(egg_group *g, double delta, int32_t n_substeps, int32_t n_col
 /* which device index holds batch `id` now, and under which id of that device's handle */
 int egg_group_owner(const egg_group *g, int64_t id, int32_t *device_index, int64_t *local_id);
 int egg_group_get_counters(const egg_group *g, int64_t *migrations, int64_t *discarded_steps);
+/* EGG_OPT_SOLVER_ORDER / EGG_OPT_RELAXATION for every handle of the group (same values and ranges; relaxation <= 0 keeps
+ * the current value).  Relaxed order over handles on different devices needs peer access between them: EGG_ERR_UNSUPPORTED
+ * otherwise.  Refused values change nothing. */
+int egg_group_set_solver_order(egg_group *g, int32_t order, double relaxation);
+/* cumulative over relaxed group steps, both types: collision passes, ghost records the devices received, their bytes */
+int egg_group_get_halo_counters(const egg_group *g, int64_t *passes, int64_t *records, int64_t *bytes);
 
 #ifdef __cplusplus
 }
