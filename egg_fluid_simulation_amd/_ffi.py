@@ -133,6 +133,22 @@ _SIGNATURES = {
     "egg_group_get_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "egg_group_set_solver_order": (C.c_int, [C.c_void_p, C.c_int32, C.c_double]),
     "egg_group_get_halo_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "egg_group_set_config": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(EggConfig)]),
+    "egg_group_get_config": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(EggConfig)]),
+    "egg_group_get_target": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "egg_group_list_ids": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]),
+    "egg_group_get_n_particles": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "egg_group_get_elapsed": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "egg_group_download_particles": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64]),
+    "egg_group_get_environment": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(EggEnvironment)]),
+    "egg_group_set_render_config": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(EggRenderConfig)]),
+    "egg_group_get_render_config": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(EggRenderConfig)]),
+    "egg_group_set_render_flags": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    "egg_group_set_add_color": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double]),
+    "egg_group_set_color": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double]),
+    "egg_group_render": (C.c_int, [C.c_void_p, C.POINTER(EggRenderParams), C.c_void_p]),
+    "egg_group_render_canvas": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                          C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "egg_remove": (C.c_int, [C.c_void_p, C.c_int64]),
     "egg_set_target": (C.c_int, [C.c_void_p, C.c_int64, C.c_double, C.c_double]),
     "egg_set_targets_many": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -326,3 +326,20 @@ struct EggRxUnpackArgs {  // receiver side: pulls every sender's records for it 
     const EggGhost *recs[EGG_RX_MAX_GROUP];           // in the senders' memory
     const unsigned long long *count[EGG_RX_MAX_GROUP];
 };
+
+// ---------------------------------------------------------------------------------------------
+// Draw of a device group (eggsim_render_group.hip): the particles of ONE source handle and type are copied into the
+// render device's shadow arrays, which hold every particle of the group in global-key order.  A RUN is a stretch of
+// source particles whose destinations are consecutive too (whole batches; neighbouring batches whose keys are
+// neighbours in the group merge into one run).
+#define EGG_GATHER_FIELDS 7  // x, y, last_x, last_y, vx, vy, radius: the instanced-draw record (L:513-517)
+#define EGG_GATHER_BLOCK 256
+struct EggGatherArgs {
+    const double *src[EGG_GATHER_FIELDS];  // the source handle's arrays (peer memory when it sits on another device)
+    double *dst[EGG_GATHER_FIELDS];        // shadow arrays on the render device
+    const int32_t *run_src;    // [n_runs + 1] first source particle of every run, ascending; run_src[n_runs] = n
+    const int32_t *run_dst;    // [n_runs] where that particle goes
+    const int32_t *block_run;  // [blocks] the run that holds the first particle of every workgroup
+    int32_t n, n_runs, n_fields;
+    int32_t total;             // particles the shadow arrays hold
+};

@@ -16,8 +16,9 @@
 //     (egg_export_batch -> egg_import_batch), and the step is run again;
 //   * an island that has left its slab's halo without meeting anything moves to the slab it is in after the step;
 //   * the collision budget 0.05 N^2 (L:1752-1753) counts the particles of all devices (EGG_OPT_BUDGET_PARTICLES_*);
-//     the visits of the step in flight are added up over the devices BEFORE it is committed, and a budget that could
-//     bind is refused (exact-budget mode needs all particles of a type in one tile).
+//     the visits of the step in flight are added up over the devices BEFORE it is committed; when the budget could
+//     bind, the step is discarded and every batch goes to device 0, which steps them as one handle does (exact-budget
+//     mode needs all particles of a type in one tile) until batches are added or removed.
 //
 // In relaxed order (egg_group_set_solver_order) there are no claims, budget or re-runs: the step
 // is eggsim_host_relaxed_group.hip's (every pass over local particles plus ghosts of the neighbours', no hand-over),
@@ -34,6 +35,7 @@
 #include <vector>
 
 #include "../../include/eggsim.h"
+#include "eggsim_group_draw.h"
 
 namespace egghost {  // eggsim_host_relaxed_group.hip
 int relaxed_group_peers(egg_handle *const *hs, int n, std::string *error);
@@ -55,11 +57,22 @@ struct egg_group {
     };
     std::vector<Rec> batch;  // index = global id - 1
     bool budget_stale = true;
+    bool consolidated = false;  // exact order: the budget may bind, device 0 holds and steps every batch (group_step_consolidated)
     double elapsed = 0, alpha = 0;
     int64_t migrations = 0, discarded_steps = 0;
     int64_t committed_visits[2] = {0, 0};
     int order = EGG_SOLVER_EXACT;
     int64_t halo_passes = 0, halo_records = 0;  // relaxed group steps: collision passes, ghost records received
+    int64_t steps = 0;  // _step calls committed by the group
+    // render attributes (never read by the solver): they live here, per global id / per type, so that a hand-over
+    // between handles cannot lose them.  pcolor: [id - 1][type][rgba], the colour the batch's particles carry
+    // (L:978-990, L:1110-1129); own_color: [id - 1][type], the batch's colour table is its own (a colour argument of
+    // add) and not the config's (L:49-50)
+    egg_render_config render_cfg[2];
+    int use_particle_color = 0, use_lighting = 1;  // L:448-449
+    std::vector<float> pcolor;
+    std::vector<unsigned char> own_color;
+    egghost::GroupDraw *draw = nullptr;  // device side of draws, created by the first one
     std::string error;
 };
 
@@ -292,11 +305,35 @@ int group_step_relaxed(egg_group *g, double delta, int S, int C) {
     return rebalance_relaxed(g);
 }
 
+int group_step_any(egg_group *g, double delta, int S, int C);
+
 int group_step(egg_group *g, double delta, int S, int C) {  // one _step (L:1722) on every device
+    const int rc = group_step_any(g, delta, S, C);
+    if (rc == EGG_OK) g->steps++;
+    return rc;
+}
+
+// A collision budget 0.05 N^2 (L:1752-1753) that may bind (few batches: the yolk's does for nine or fewer) cuts passes
+// short, and where it cuts depends on every visit before it: device 0 takes every batch and steps them as the single handle
+// it then is; the other handles step empty.  Nothing strays back while the membership stays the same.
+int group_step_consolidated(egg_group *g, double delta, int S, int C) {
+    std::map<int64_t, int> plan;
+    for (size_t i = 0; i < g->batch.size(); ++i)
+        if (g->batch[i].alive && g->batch[i].owner != 0) plan[(int64_t)i + 1] = 0;
+    int rc = plan.empty() ? EGG_OK : move_batches(g, plan);
+    if (rc != EGG_OK) return rc;
+    for (size_t k = 0; k < g->h.size(); ++k) GTRY(g, k, egg_step(g->h[k], delta, S, C));
+    g->committed_visits[0] = g->committed_visits[1] = 0;
+    return EGG_OK;
+}
+
+int group_step_any(egg_group *g, double delta, int S, int C) {
     if (g->order == EGG_SOLVER_RELAXED) return group_step_relaxed(g, delta, S, C);
     const size_t n = g->h.size();
+    if (g->budget_stale) g->consolidated = false;  // batches came or went: the budget is another one
     int rc = sync_budget(g);
     if (rc != EGG_OK) return rc;
+    if (g->consolidated && n > 1) return group_step_consolidated(g, delta, S, C);
     if (n == 1) {
         GTRY(g, 0, egg_step(g->h[0], delta, S, C));
         return EGG_OK;
@@ -315,10 +352,11 @@ int group_step(egg_group *g, double delta, int S, int C) {  // one _step (L:1722
     std::map<int64_t, int> plan;
     int conflicts = 0;
     plan_moves(g, cl, cell, plan, conflicts);
-    // the budget guard: what the step in flight visited, summed over the devices, against the global budget
-    int64_t visits[2] = {g->committed_visits[0], g->committed_visits[1]};
-    double budget[2] = {0, 0};
-    {
+    // the budget guard: what the step in flight visited, summed over the devices, against the global budget.
+    // 1: the budget may bind (the step has been discarded); < 0: an error (discarded too)
+    auto budget_trips = [&]() -> int {
+        int64_t visits[2] = {g->committed_visits[0], g->committed_visits[1]};
+        double budget[2] = {0, 0};
         int64_t sum[2] = {0, 0};
         for (size_t k = 0; k < n; ++k) {
             int64_t v[2] = {0, 0};
@@ -333,15 +371,19 @@ int group_step(egg_group *g, double delta, int S, int C) {  // one _step (L:1722
                 budget[w] = std::max(budget[w], b[w]);
             }
         }
-        for (int w = 0; w < 2; ++w) visits[w] = std::max(visits[w], sum[w]);
-    }
-    for (int w = 0; w < 2; ++w)
-        if ((double)visits[w] > std::max(1.0, std::ceil(budget[w]))) {
-            discard();
-            return gfail(g, EGG_ERR_UNSUPPORTED,
-                         "collision budget may bind across devices (type %d: up to %lld visits in a pass, budget %.2f): "
-                         "exact-budget mode needs all particles of the type on one device", w, (long long)visits[w], budget[w]);
-        }
+        for (int w = 0; w < 2; ++w)
+            if ((double)std::max(visits[w], sum[w]) > std::max(1.0, std::ceil(budget[w]))) {
+                // exact-budget mode needs all particles of the type in one tile, hence on one device
+                discard();
+                g->discarded_steps++;
+                g->consolidated = true;
+                return 1;
+            }
+        return 0;
+    };
+    int trips = budget_trips();
+    if (trips < 0) return trips;
+    if (trips) return group_step_consolidated(g, delta, S, C);
     auto note_committed = [&]() {
         g->committed_visits[0] = g->committed_visits[1] = 0;
         for (size_t k = 0; k < n; ++k) {
@@ -364,10 +406,37 @@ int group_step(egg_group *g, double delta, int S, int C) {  // one _step (L:1722
     rc = rebalance(g, delta, S, C);
     if (rc != EGG_OK) return rc;
     for (size_t k = 0; k < n; ++k) GTRY(g, k, egg_step_begin(g->h[k], delta, S, C));
+    trips = budget_trips();  // (islands that met on one device visit more pairs than they did apart)
+    if (trips < 0) return trips;
+    if (trips) return group_step_consolidated(g, delta, S, C);
     for (size_t k = 0; k < n; ++k) GTRY(g, k, egg_step_end(g->h[k], 1));
     note_committed();
     return EGG_OK;
 }
+
+bool live(const egg_group *g, int64_t id) { return id >= 1 && id <= (int64_t)g->batch.size() && g->batch[(size_t)id - 1].alive; }
+
+egghost::GroupView view_of(egg_group *g) {
+    egghost::GroupView v;
+    v.hs = g->h.data();
+    v.n = (int)g->h.size();
+    v.cfg = g->render_cfg;
+    v.use_particle_color = g->use_particle_color;
+    v.use_lighting = g->use_lighting;
+    v.pcolor = g->pcolor.data();
+    v.n_ids = (int64_t)g->batch.size();
+    v.stepped = g->steps > 0;
+    v.alpha = g->alpha;
+    if (!g->draw) g->draw = egghost::group_draw_create();
+    return v;
+}
+
+int gdone(egg_group *g, int rc, const std::string &err) {
+    if (rc != EGG_OK) g->error = err;
+    return rc;
+}
+
+float clamp01(double v) { return (float)std::min(std::max(v, 0.0), 1.0); }
 
 }  // namespace
 
@@ -394,12 +463,14 @@ int egg_group_create(const egg_config *white, const egg_config *yolk, int32_t n_
         }
         g->h.push_back(h);
     }
+    for (int w = 0; w < 2; ++w) (void)egg_default_render_config(w, &g->render_cfg[w]);
     *out = g;
     return EGG_OK;
 }
 
 void egg_group_destroy(egg_group *g) {
     if (!g) return;
+    if (g->draw) egghost::group_draw_destroy(g->draw);  // (before the render handle goes)
     for (egg_handle *h : g->h) egg_destroy(h);
     delete g;
 }
@@ -429,8 +500,15 @@ int egg_group_add(egg_group *g, double x, double y, double white_radius, double 
     r.local = lid;
     r.alive = true;
     g->batch.push_back(r);
+    for (int w = 0; w < 2; ++w) {  // L:978-990: the batch colour (here: the config's) or plain white
+        const float white[4] = {1, 1, 1, 1};
+        const float *c = g->use_particle_color ? g->render_cfg[w].color : white;
+        g->pcolor.insert(g->pcolor.end(), c, c + 4);
+        g->own_color.push_back(0);
+    }
     g->budget_stale = true;
     if (out_id) *out_id = gid;
+    if (rc > 0) g->error = egg_last_error(g->h[(size_t)k]);  // the "few particles" warning (L:114-120): the batch exists
     return rc;
 }
 
@@ -454,7 +532,8 @@ int egg_group_set_target(egg_group *g, int64_t id, double x, double y) {
         return EGG_WARN_UNKNOWN_ID;  // L:259
     }
     const egg_group::Rec &r = g->batch[(size_t)id - 1];
-    return egg_set_target(g->h[(size_t)r.owner], r.local, x, y);
+    GTRY(g, r.owner, egg_set_target(g->h[(size_t)r.owner], r.local, x, y));
+    return EGG_OK;
 }
 
 int egg_group_get_position(egg_group *g, int64_t id, double *x, double *y) {
@@ -534,6 +613,142 @@ int egg_group_get_halo_counters(const egg_group *g, int64_t *passes, int64_t *re
     if (records) *records = g->halo_records;
     if (bytes) *bytes = g->halo_records * kGhostRecordBytes;
     return EGG_OK;
+}
+
+int egg_group_set_config(egg_group *g, int which, const egg_config *cfg) {
+    if (!g || !cfg || (which != EGG_WHITE && which != EGG_YOLK)) return EGG_ERR_INVALID_ARGUMENT;
+    for (size_t k = 0; k < g->h.size(); ++k)  // (refused by one handle = refused by the first: the checks do not depend on the handle)
+        GTRY(g, k, egg_set_config(g->h[k], which, cfg));
+    g->budget_stale = true;
+    return EGG_OK;
+}
+
+int egg_group_get_config(const egg_group *g, int which, egg_config *cfg) {
+    if (!g || !cfg || (which != EGG_WHITE && which != EGG_YOLK)) return EGG_ERR_INVALID_ARGUMENT;
+    return egg_get_config(g->h[0], which, cfg);
+}
+
+int egg_group_get_target(const egg_group *g, int64_t id, double *x, double *y) {  // L:268-278
+    if (!g || !x || !y) return EGG_ERR_INVALID_ARGUMENT;
+    if (!live(g, id))
+        return gfail(const_cast<egg_group *>(g), EGG_ERR_UNKNOWN_ID, "In SimulationHandler.get_target_position: no batch with id `%lld`", (long long)id);
+    const egg_group::Rec &r = g->batch[(size_t)id - 1];
+    return egg_get_target(g->h[(size_t)r.owner], r.local, x, y);
+}
+
+int egg_group_list_ids(const egg_group *g, int64_t cap, int64_t *ids, int64_t *n) {  // L:399-405
+    if (!g || !n) return EGG_ERR_INVALID_ARGUMENT;
+    int64_t k = 0;
+    for (size_t i = 0; i < g->batch.size(); ++i) {
+        if (!g->batch[i].alive) continue;
+        if (ids && k < cap) ids[k] = (int64_t)i + 1;
+        ++k;
+    }
+    *n = k;
+    return EGG_OK;
+}
+
+int egg_group_get_n_particles(const egg_group *g, int64_t id, int64_t *n_white, int64_t *n_yolk) {  // L:409-419
+    if (!g || !n_white || !n_yolk) return EGG_ERR_INVALID_ARGUMENT;
+    if (id < 0) {
+        *n_white = *n_yolk = 0;
+        for (egg_handle *h : g->h) {
+            int64_t nw = 0, ny = 0;
+            (void)egg_get_n_particles(h, -1, &nw, &ny);
+            *n_white += nw;
+            *n_yolk += ny;
+        }
+        return EGG_OK;
+    }
+    if (!live(g, id))
+        return gfail(const_cast<egg_group *>(g), EGG_ERR_UNKNOWN_ID, "In SimulationHandler:get_n_particles: no batch with id `%lld`", (long long)id);
+    const egg_group::Rec &r = g->batch[(size_t)id - 1];
+    return egg_get_n_particles(g->h[(size_t)r.owner], r.local, n_white, n_yolk);
+}
+
+int egg_group_get_elapsed(const egg_group *g, double *elapsed, double *interpolation_alpha) {
+    if (!g) return EGG_ERR_INVALID_ARGUMENT;
+    if (elapsed) *elapsed = g->elapsed;
+    if (interpolation_alpha) *interpolation_alpha = g->alpha;
+    return EGG_OK;
+}
+
+int egg_group_download_particles(egg_group *g, int which, int field, double *dst, int64_t cap) {
+    if (!g || !dst || (which != EGG_WHITE && which != EGG_YOLK) || field < 0 || field >= EGG_N_FIELDS) return EGG_ERR_INVALID_ARGUMENT;
+    const egghost::GroupView v = view_of(g);
+    std::string err;
+    return gdone(g, egghost::group_draw_download(g->draw, v, which, field, dst, cap, &err), err);
+}
+
+int egg_group_get_environment(egg_group *g, int which, egg_environment *out) {
+    if (!g || !out || (which != EGG_WHITE && which != EGG_YOLK)) return EGG_ERR_INVALID_ARGUMENT;
+    const egghost::GroupView v = view_of(g);
+    std::string err;
+    return gdone(g, egghost::group_draw_environment(g->draw, v, which, out, &err), err);
+}
+
+int egg_group_set_render_config(egg_group *g, int which, const egg_render_config *cfg) {
+    if (!g || !cfg || (which != EGG_WHITE && which != EGG_YOLK)) return EGG_ERR_INVALID_ARGUMENT;
+    if (!(cfg->outline_thickness >= 0) || !(cfg->texture_scale > 0) || !std::isfinite(cfg->motion_blur) ||
+        !std::isfinite(cfg->highlight_strength) || !std::isfinite(cfg->shadow_strength) || !(cfg->outline_thickness <= 256))
+        return gfail(g, EGG_ERR_INVALID_ARGUMENT, "egg_group_set_render_config: value out of range");
+    g->render_cfg[which] = *cfg;
+    // config.color is a new table now (L:1307-1311): batches that shared the old one keep it for themselves
+    for (size_t i = 0; i < g->batch.size(); ++i) g->own_color[2 * i + (size_t)which] = 1;
+    return EGG_OK;
+}
+
+int egg_group_get_render_config(const egg_group *g, int which, egg_render_config *cfg) {
+    if (!g || !cfg || (which != EGG_WHITE && which != EGG_YOLK)) return EGG_ERR_INVALID_ARGUMENT;
+    *cfg = g->render_cfg[which];
+    return EGG_OK;
+}
+
+int egg_group_set_render_flags(egg_group *g, int32_t use_particle_color, int32_t use_lighting) {
+    if (!g) return EGG_ERR_INVALID_ARGUMENT;
+    g->use_particle_color = use_particle_color != 0;
+    g->use_lighting = use_lighting != 0;
+    return EGG_OK;
+}
+
+int egg_group_set_add_color(egg_group *g, int64_t id, int which, double r, double gr, double b, double a) {
+    if (!g || (which != EGG_WHITE && which != EGG_YOLK)) return EGG_ERR_INVALID_ARGUMENT;
+    if (!live(g, id)) return gfail(g, EGG_ERR_UNKNOWN_ID, "egg_group_set_add_color: no batch with id `%lld`", (long long)id);
+    if (std::isnan(r) || std::isnan(gr) || std::isnan(b) || std::isnan(a))  // L:87-103
+        return gfail(g, EGG_ERR_INVALID_ARGUMENT, "In SimulationHandler.add: %s color component is not a number", which == EGG_WHITE ? "white" : "yolk");
+    g->own_color[2 * (size_t)(id - 1) + (size_t)which] = 1;
+    if (g->use_particle_color) {  // add does not clamp (L:978-984)
+        const float c[4] = {(float)r, (float)gr, (float)b, (float)a};
+        memcpy(&g->pcolor[8 * (size_t)(id - 1) + 4 * (size_t)which], c, sizeof c);
+    }
+    return EGG_OK;
+}
+
+int egg_group_set_color(egg_group *g, int64_t id, int which, double r, double gr, double b, double a) {
+    if (!g || (which != EGG_WHITE && which != EGG_YOLK)) return EGG_ERR_INVALID_ARGUMENT;
+    if (std::isnan(r) || std::isnan(gr) || std::isnan(b) || std::isnan(a))
+        return gfail(g, EGG_ERR_INVALID_ARGUMENT, "egg_group_set_color: a colour component is not a number");
+    if (!live(g, id))
+        return gfail(g, EGG_WARN_UNKNOWN_ID, "In SimulationHandler.%s: no batch with id `%lld`",
+                     which == EGG_WHITE ? "set_white_color" : "set_egg_yolk_color", (long long)id);
+    const float c[4] = {clamp01(r), clamp01(gr), clamp01(b), clamp01(a)};  // _assert_color (L:300-319)
+    memcpy(&g->pcolor[8 * (size_t)(id - 1) + 4 * (size_t)which], c, sizeof c);
+    if (!g->own_color[2 * (size_t)(id - 1) + (size_t)which]) memcpy(g->render_cfg[which].color, c, sizeof c);  // the shared table (L:49-50, L:349-350)
+    return EGG_OK;
+}
+
+int egg_group_render(egg_group *g, const egg_render_params *p, float *rgba) {
+    if (!g || !p) return EGG_ERR_INVALID_ARGUMENT;
+    const egghost::GroupView v = view_of(g);
+    std::string err;
+    return gdone(g, egghost::group_draw_render(g->draw, v, p, rgba, &err), err);
+}
+
+int egg_group_render_canvas(egg_group *g, int which, float *rgba, int64_t cap_pixels, int32_t *w, int32_t *hgt, double *x0, double *y0) {
+    if (!g || (which != EGG_WHITE && which != EGG_YOLK)) return EGG_ERR_INVALID_ARGUMENT;
+    const egghost::GroupView v = view_of(g);
+    std::string err;
+    return gdone(g, egghost::group_draw_canvas(g->draw, v, which, rgba, cap_pixels, w, hgt, x0, y0, &err), err);
 }
 
 }  // extern "C"

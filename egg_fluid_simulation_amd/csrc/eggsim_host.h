@@ -9,6 +9,7 @@
 //   eggsim_host_render.hip  egg_render* : the headless renderer's host side
 //   eggsim_host_relaxed.hip _step in relaxed order (EGG_OPT_SOLVER_ORDER = 1): the launches of eggsim_relaxed.hip
 //   eggsim_host_relaxed_group.hip  the same step over the handles of a device group, with per-pass ghost halos
+//   eggsim_host_render_group.hip   draw / environment / download of a device group: gather to one device (eggsim_render_group.hip)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -74,6 +75,7 @@ extern "C" __global__ void egg_rx_gather_group_kernel(EggRelaxedGroupArgs A);
 extern "C" __global__ void egg_rx_gkey_kernel(const int32_t *, const int32_t *, const int32_t *, int, int32_t *);
 extern "C" __global__ void egg_rx_pack_kernel(EggRxPackArgs P);
 extern "C" __global__ void egg_rx_unpack_kernel(EggRxUnpackArgs U);
+extern "C" __global__ void egg_group_gather_kernel(EggGatherArgs A);
 extern "C" __global__ void egg_render_count_kernel(EggRenderArgs A);
 extern "C" __global__ void egg_render_fill_kernel(EggRenderArgs A);
 extern "C" __global__ void egg_render_scan_kernel(EggRenderArgs A);
@@ -413,6 +415,34 @@ inline double clampd(double x, double lo, double hi) {  // math.lua:16-26
 }
 inline double mixd(double lo, double hi, double t) { return lo * (1 - t) + hi * t; }  // math.lua:33-35
 
+// What the renderer and the environment reductions read.  A handle fills it from its own System (render_source_of); a
+// device group fills it from the shadow arrays on its render device and its own records (eggsim_host_render_group.hip).
+struct RenderSource {
+    egg_handle *h = nullptr;                 // device, LDS limit, error text, launch count: the handle / a group's render handle
+    egg_handle::Render *R = nullptr;         // canvases with their grow-only sizes, screen, scratch of the passes
+    const egg_render_config *cfg = nullptr;  // [2]
+    int use_particle_color = 0, use_lighting = 1;
+    bool stepped = false;                    // a _step has run: there are no canvases before (L:1997-1999)
+    double alpha = 0;                        // interpolation_alpha of the last update (L:216)
+    double max_radius = 0;                   // the larger config max_radius: sizes the density texture (L:626-629)
+    hipStream_t stream = nullptr;            // the passes run here ...
+    hipStream_t also_wait = nullptr;         // ... after everything on this stream has finished (may be null)
+    struct Type {
+        const double *x = nullptr, *y = nullptr, *last_x = nullptr, *last_y = nullptr, *vx = nullptr, *vy = nullptr, *radius = nullptr;
+        const int32_t *atom_offset = nullptr;  // first particle of every atom, ascending
+        int64_t n = 0;
+        std::vector<float> atom_color;         // rgba per atom: the colour its particles carry (L:1110-1129)
+        hipStream_t env_stream = nullptr;      // stream and scratch (16 words) of the environment reductions
+        DevBuf<unsigned long long> *d_env = nullptr;
+    } t[2];
+};
+int render_source_of(egg_handle *h, RenderSource &S);  // eggsim_host_render.hip
+int render_from(RenderSource &S, const egg_render_params *p, float *rgba, const char *name);
+int render_canvas_from(egg_handle *h, egg_handle::Render &R, const char *name, int which, float *rgba, int64_t cap_pixels, int32_t *w,
+                       int32_t *hgt, double *x0, double *y0);
+// the reductions of egg_get_environment over the arrays of T (eggsim_host_abi.hip)
+int environment_of(egg_handle *h, bool stepped, const RenderSource::Type &T, egg_environment *out);
+
 Batch *find_batch(egg_handle *h, int64_t id);
 const Batch *find_batch(const egg_handle *h, int64_t id);
 
@@ -457,6 +487,17 @@ void relaxed_commit(egg_handle *h, const Env env[2], int S, int C, double ms);
 // eggsim_host_relaxed_group.hip: the relaxed step of a device group (called by eggsim_group.cpp, which declares them
 // itself: it sees only include/eggsim.h).  0 or an EGG_ERR_* code; on failure *error names the device and the reason.
 int relaxed_group_peers(egg_handle *const *hs, int n, std::string *error);
+int group_peers(egg_handle *const *hs, int n, const char *who, const char *what, std::string *error);
+// the atoms of all handles of a group in ascending batch key = the group's particle layout order (global keys), per type;
+// shared by the relaxed group step (ghost keys) and the group's draw (eggsim_host_render_group.hip).  The atoms of every
+// handle must be current (upload_atoms).
+struct GroupKeys {
+    std::vector<std::pair<int64_t, int64_t>> sizes;  // (batch key, particles of the type), ascending
+    std::vector<int64_t> base;                       // global key of the first particle of each
+    int64_t total = 0;
+    int64_t base_of(int64_t key, int64_t count) const;
+};
+void group_keys(egg_handle *const *hs, int n, int w, GroupKeys &K);
 int relaxed_group_step(egg_handle *const *hs, int n, double delta, int S, int C, int64_t halo_records[1], std::string *error);
 
 }  // namespace egghost

@@ -775,9 +775,26 @@ int egg_get_environment(egg_handle *h, int which, egg_environment *out) {
     if (!h || !out || which < 0 || which > 1) return EGG_ERR_INVALID_ARGUMENT;
     HIP_TRY(h, hipSetDevice(h->device));
     System &s = h->sys[which];
+    RenderSource::Type T;
+    T.x = s.x[s.cur].p;
+    T.y = s.y[s.cur].p;
+    T.last_x = s.x[s.cur ^ 1].p;
+    T.last_y = s.y[s.cur ^ 1].p;
+    T.vx = s.vx[s.cur].p;
+    T.vy = s.vy[s.cur].p;
+    T.radius = s.radius.p;
+    T.n = s.n;
+    T.env_stream = s.stream;
+    T.d_env = &s.d_env;
+    return environment_of(h, h->stats.steps > 0, T, out);
+}
+
+}  // extern "C"
+
+int egghost::environment_of(egg_handle *h, bool stepped, const RenderSource::Type &T, egg_environment *out) {
     const double inf = std::numeric_limits<double>::infinity();
     *out = egg_environment{inf, inf, -inf, -inf, 0, 0, 0, 0, 0, 0};  // L:1358-1390
-    if (h->stats.steps == 0 || s.n == 0) return EGG_OK;
+    if (!stepped || T.n == 0) return EGG_OK;
     auto key = [](double d) {
         unsigned long long u;
         memcpy(&u, &d, 8);
@@ -791,20 +808,20 @@ int egg_get_environment(egg_handle *h, int which, egg_environment *out) {
     };
     // scratch: 6 ordered keys + 4 sums, in the type's scratch-free status staging area would alias live data,
     // so a small dedicated buffer
-    HIP_TRY(h, s.d_env.reserve(16, false, s.stream));
+    hipStream_t st = T.env_stream;
+    DevBuf<unsigned long long> &d_env = *T.d_env;
+    HIP_TRY(h, d_env.reserve(16, false, st));
     unsigned long long init[6] = {key(inf), key(inf), key(-inf), key(-inf), key(0.0), key(0.0)};
-    HIP_TRY(h, hipMemcpyAsync(s.d_env.p, init, sizeof init, hipMemcpyHostToDevice, s.stream));
-    const int n = (int)s.n;
+    HIP_TRY(h, hipMemcpyAsync(d_env.p, init, sizeof init, hipMemcpyHostToDevice, st));
+    const int n = (int)T.n;
     const int blocks = std::min(1024, (n + 255) / 256);
-    hipLaunchKernelGGL(egg_env_bounds_kernel, dim3((unsigned)blocks), dim3(256), 0, s.stream, s.x[s.cur].p, s.y[s.cur].p,
-                       s.vx[s.cur].p, s.vy[s.cur].p, s.radius.p, n, s.d_env.p);
-    hipLaunchKernelGGL(egg_env_sums_kernel, dim3(4), dim3(EGG_WAVE), 0, s.stream, s.x[s.cur].p, s.y[s.cur].p,
-                       s.x[s.cur ^ 1].p, s.y[s.cur ^ 1].p, n, (double *)(s.d_env.p + 6));
+    hipLaunchKernelGGL(egg_env_bounds_kernel, dim3((unsigned)blocks), dim3(256), 0, st, T.x, T.y, T.vx, T.vy, T.radius, n, d_env.p);
+    hipLaunchKernelGGL(egg_env_sums_kernel, dim3(4), dim3(EGG_WAVE), 0, st, T.x, T.y, T.last_x, T.last_y, n, (double *)(d_env.p + 6));
     HIP_TRY(h, hipGetLastError());
     h->stats.kernel_launches += 2;
     unsigned long long back[10];
-    HIP_TRY(h, hipMemcpyAsync(back, s.d_env.p, sizeof back, hipMemcpyDeviceToHost, s.stream));
-    HIP_TRY(h, hipStreamSynchronize(s.stream));
+    HIP_TRY(h, hipMemcpyAsync(back, d_env.p, sizeof back, hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
     double sums[4];
     memcpy(sums, back + 6, sizeof sums);
     out->min_x = unkey(back[0]);
@@ -819,6 +836,8 @@ int egg_get_environment(egg_handle *h, int which, egg_environment *out) {
     out->last_centroid_y = sums[3] / (double)n;
     return EGG_OK;
 }
+
+extern "C" {
 
 
 int egg_get_stats(egg_handle *h, egg_stats *out) {

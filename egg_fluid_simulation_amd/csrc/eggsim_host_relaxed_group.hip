@@ -50,11 +50,37 @@ int device_fail(egg_handle *const *hs, int k, std::string *error, int rc) {
 
 }  // namespace
 
+// The global key of a particle: its index in ONE handle holding every live batch of the group in
+// ascending batch key.  The atoms of all handles, sorted by key, with the running sum of their particle counts.
+void group_keys(egg_handle *const *hs, int n, int w, GroupKeys &K) {
+    K.sizes.clear();
+    for (int k = 0; k < n; ++k)
+        for (const Atom &a : hs[k]->sys[w].atoms) K.sizes.emplace_back(hs[k]->batches[(size_t)a.batch].key, (int64_t)a.count);
+    std::sort(K.sizes.begin(), K.sizes.end());
+    K.base.resize(K.sizes.size());
+    int64_t acc = 0;
+    for (size_t b = 0; b < K.sizes.size(); ++b) {
+        K.base[b] = acc;
+        acc += K.sizes[b].second;
+    }
+    K.total = acc;
+}
+
+int64_t GroupKeys::base_of(int64_t key, int64_t count) const {
+    const std::pair<int64_t, int64_t> e(key, count);
+    return base[(size_t)(std::lower_bound(sizes.begin(), sizes.end(), e) - sizes.begin())];
+}
+
 int relaxed_group_peers(egg_handle *const *hs, int n, std::string *error) {
     if (n > EGG_RX_MAX_GROUP) {
         *error = "relaxed order: a device group of more than 16 handles";
         return EGG_ERR_UNSUPPORTED;
     }
+    return group_peers(hs, n, "relaxed order", "the ghost halo", error);
+}
+
+// peer access between every pair of different devices of the group, both ways; `who` / `what` word the refusal
+int group_peers(egg_handle *const *hs, int n, const char *who, const char *what, std::string *error) {
     for (int a = 0; a < n; ++a)
         for (int b = 0; b < n; ++b) {
             const int da = hs[a]->device, db = hs[b]->device;
@@ -62,7 +88,7 @@ int relaxed_group_peers(egg_handle *const *hs, int n, std::string *error) {
             int can = 0;
             if (hipDeviceCanAccessPeer(&can, da, db) != hipSuccess || !can) {
                 char buf[160];
-                snprintf(buf, sizeof buf, "relaxed order: device %d cannot access device %d (peer access is needed for the ghost halo)", da, db);
+                snprintf(buf, sizeof buf, "%s: device %d cannot access device %d (peer access is needed for %s)", who, da, db, what);
                 *error = buf;
                 return EGG_ERR_UNSUPPORTED;
             }
@@ -71,7 +97,7 @@ int relaxed_group_peers(egg_handle *const *hs, int n, std::string *error) {
             if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) {
                 (void)hipGetLastError();
                 char buf[160];
-                snprintf(buf, sizeof buf, "relaxed order: enabling peer access from device %d to %d failed: %s", da, db, hipGetErrorString(e));
+                snprintf(buf, sizeof buf, "%s: enabling peer access from device %d to %d failed: %s", who, da, db, hipGetErrorString(e));
                 *error = buf;
                 return EGG_ERR_UNSUPPORTED;
             }
@@ -120,19 +146,11 @@ int relaxed_group_step(egg_handle *const *hs, int nh, double delta, int S, int C
         // (every handle lays its batches out in ascending id: the key of particle i is base + its place in its atom)
         std::vector<uint64_t> sig((size_t)nh);
         for (int k = 0; k < nh; ++k) sig[(size_t)k] = hs[k]->sys[w].atoms_gen;
-        std::vector<std::pair<int64_t, int64_t>> sizes;  // (batch key, particles)
+        GroupKeys keys;
         bool any_rebuild = false;
         for (int k : q[w])
             any_rebuild |= hs[k]->sys[w].rx.key_sig != sig || hs[k]->sys[w].rx.ekey.cap < (size_t)total;
-        if (any_rebuild)
-            for (int k = 0; k < nh; ++k)
-                for (const Atom &a : hs[k]->sys[w].atoms) sizes.emplace_back(hs[k]->batches[(size_t)a.batch].key, (int64_t)a.count);
-        std::sort(sizes.begin(), sizes.end());
-        std::vector<int64_t> base(sizes.size());
-        for (size_t b = 0, acc = 0; b < sizes.size(); ++b) {
-            base[b] = (int64_t)acc;
-            acc += (size_t)sizes[b].second;
-        }
+        if (any_rebuild) group_keys(hs, nh, w, keys);
         for (int k : q[w]) {
             egg_handle *h = hs[k];
             System &s = h->sys[w];
@@ -152,10 +170,7 @@ int relaxed_group_step(egg_handle *const *hs, int nh, double delta, int S, int C
             if (rebuild) {
                 const size_t na = s.atoms.size();
                 std::vector<int32_t> ab(na + 1, 0);
-                for (size_t a = 0; a < na; ++a) {
-                    const std::pair<int64_t, int64_t> key(h->batches[(size_t)s.atoms[a].batch].key, (int64_t)s.atoms[a].count);
-                    ab[a] = (int32_t)base[(size_t)(std::lower_bound(sizes.begin(), sizes.end(), key) - sizes.begin())];
-                }
+                for (size_t a = 0; a < na; ++a) ab[a] = (int32_t)keys.base_of(h->batches[(size_t)s.atoms[a].batch].key, s.atoms[a].count);
                 GK_HIP(k, r.abase.reserve(na + 1, false, s.stream));
                 GK_HIP(k, hipMemcpyAsync(r.abase.p, ab.data(), (na + 1) * 4, hipMemcpyHostToDevice, s.stream));
                 hipLaunchKernelGGL(egg_rx_gkey_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s.stream,

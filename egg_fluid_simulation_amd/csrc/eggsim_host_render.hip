@@ -90,9 +90,8 @@ int egg_default_render_params(egg_render_params *p) {
 namespace {
 
 // the density texture: simulation_handler_particle_texture.glsl drawn by _initialize_particle_texture (L:620-682)
-int render_texture(egg_handle *h) {
-    egg_handle::Render &R = h->render;
-    const double radius = std::max(h->sys[0].cfg.max_radius, h->sys[1].cfg.max_radius) * 4;  // L:626-629, L:455
+int render_texture(egg_handle *h, egg_handle::Render &R, double max_radius, hipStream_t st) {
+    const double radius = max_radius * 4;  // L:626-629, L:455
     if (radius == R.texture_radius && R.tsize > 0) return EGG_OK;
     const double padding = 3;  // L:454
     const double size_d = (radius + padding) * 2;
@@ -108,7 +107,6 @@ int render_texture(egg_handle *h) {
             const double q = 2.0 * std::sqrt((u - 0.5) * (u - 0.5) + (v - 0.5) * (v - 0.5));  // 1 - dist
             R.texture_host[(size_t)j * size + i] = (float)std::exp((-4.0 * kPi / 3.0) * q * q);
         }
-    hipStream_t st = h->sys[0].stream;
     HIP_TRY(h, R.texture.reserve((size_t)size * size, false, st));
     HIP_TRY(h, hipMemcpyAsync(R.texture.p, R.texture_host.data(), (size_t)size * size * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(h, hipStreamSynchronize(st));
@@ -118,29 +116,26 @@ int render_texture(egg_handle *h) {
 }
 
 // pass 1 of one type into R.canvas[which] (cw x ch), centred on the interpolated centroid
-int render_splat(egg_handle *h, int which, const egg_environment &env, double t, int cw, int ch, int use_instancing) {
-    egg_handle::Render &R = h->render;
-    System &s = h->sys[which];
-    hipStream_t st = h->sys[0].stream;
-    int rc = upload_atoms(h, which);
-    if (rc != EGG_OK) return rc;
-    const size_t na = s.atoms.size();
-    std::vector<float> colors(4 * na);
-    for (size_t k = 0; k < na; ++k) memcpy(&colors[4 * k], h->batches[(size_t)s.atoms[k].batch].pcolor[which], 16);
+int render_splat(RenderSource &S, int which, const egg_environment &env, double t, int cw, int ch, int use_instancing) {
+    egg_handle *h = S.h;
+    egg_handle::Render &R = *S.R;
+    const RenderSource::Type &s = S.t[which];
+    hipStream_t st = S.stream;
+    const size_t na = s.atom_color.size() / 4;
     HIP_TRY(h, R.atom_color.reserve(na, false, st));
-    HIP_TRY(h, hipMemcpyAsync(R.atom_color.p, colors.data(), na * 16, hipMemcpyHostToDevice, st));
-    HIP_TRY(h, hipStreamSynchronize(st));  // (`colors` is pageable and goes out of scope)
+    HIP_TRY(h, hipMemcpyAsync(R.atom_color.p, s.atom_color.data(), na * 16, hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipStreamSynchronize(st));  // (the colours are pageable)
 
     EggRenderArgs A;
     memset(&A, 0, sizeof A);
-    A.x = s.x[s.cur].p;
-    A.y = s.y[s.cur].p;
-    A.last_x = s.x[s.cur ^ 1].p;  // positions at the start of the most recent _step (L:1795-1815)
-    A.last_y = s.y[s.cur ^ 1].p;
-    A.vx = s.vx[s.cur].p;
-    A.vy = s.vy[s.cur].p;
-    A.radius = s.radius.p;
-    A.atom_offset = s.d_atom_offset.p;
+    A.x = s.x;
+    A.y = s.y;
+    A.last_x = s.last_x;
+    A.last_y = s.last_y;
+    A.vx = s.vx;
+    A.vy = s.vy;
+    A.radius = s.radius;
+    A.atom_offset = s.atom_offset;
     A.atom_color = R.atom_color.p;
     A.n = (int32_t)s.n;
     A.n_atoms = (int32_t)na;
@@ -149,8 +144,8 @@ int render_splat(egg_handle *h, int which, const egg_environment &env, double t,
     const double pcx = env.last_centroid_x * (1 - t) + env.centroid_x * t, pcy = env.last_centroid_y * (1 - t) + env.centroid_y * t;
     A.tx = (float)(cw / 2.0 - pcx);
     A.ty = (float)(ch / 2.0 - pcy);
-    A.texture_scale = (float)R.cfg[which].texture_scale;
-    A.motion_blur = (float)R.cfg[which].motion_blur;
+    A.texture_scale = (float)S.cfg[which].texture_scale;
+    A.motion_blur = (float)S.cfg[which].motion_blur;
     A.premultiply = use_instancing ? 0 : 1;
     A.cw = cw;
     A.ch = ch;
@@ -192,20 +187,59 @@ int render_splat(egg_handle *h, int which, const egg_environment &env, double t,
 
 }  // namespace
 
-int egg_render(egg_handle *h, const egg_render_params *p, float *rgba) {
-    if (!h || !p) return EGG_ERR_INVALID_ARGUMENT;
-    REJECT_IN_FLIGHT(h, "egg_render");
+}  // extern "C"
+
+namespace egghost {
+
+// A handle's own arrays as the renderer's source.
+int render_source_of(egg_handle *h, RenderSource &S) {
+    S.h = h;
+    S.R = &h->render;
+    S.cfg = h->render.cfg;
+    S.use_particle_color = h->render.use_particle_color;
+    S.use_lighting = h->render.use_lighting;
+    S.stepped = h->stats.steps > 0;
+    S.alpha = h->interpolation_alpha;
+    S.max_radius = std::max(h->sys[0].cfg.max_radius, h->sys[1].cfg.max_radius);
+    S.stream = h->sys[0].stream;
+    S.also_wait = h->sys[1].stream;
+    for (int w = 0; w < 2; ++w) {
+        System &s = h->sys[w];
+        const int rc = upload_atoms(h, w);
+        if (rc != EGG_OK) return rc;
+        RenderSource::Type &T = S.t[w];
+        T.x = s.x[s.cur].p;
+        T.y = s.y[s.cur].p;
+        T.last_x = s.x[s.cur ^ 1].p;  // positions at the start of the most recent _step (L:1795-1815)
+        T.last_y = s.y[s.cur ^ 1].p;
+        T.vx = s.vx[s.cur].p;
+        T.vy = s.vy[s.cur].p;
+        T.radius = s.radius.p;
+        T.atom_offset = s.d_atom_offset.p;
+        T.n = s.n;
+        T.env_stream = s.stream;
+        T.d_env = &s.d_env;
+        const size_t na = s.atoms.size();
+        T.atom_color.resize(4 * na);
+        for (size_t k = 0; k < na; ++k) memcpy(&T.atom_color[4 * k], h->batches[(size_t)s.atoms[k].batch].pcolor[w], 16);
+    }
+    return EGG_OK;
+}
+
+// draw(): both passes over the particles S describes.  Errors go to S.h under `name`.
+int render_from(RenderSource &S, const egg_render_params *p, float *rgba, const char *name) {
+    egg_handle *h = S.h;
     if (p->screen_w <= 0 || p->screen_h <= 0 || (int64_t)p->screen_w * p->screen_h > ((int64_t)1 << 28))
-        return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_render: screen of %d x %d px", p->screen_w, p->screen_h);
+        return fail(h, EGG_ERR_INVALID_ARGUMENT, "%s: screen of %d x %d px", name, p->screen_w, p->screen_h);
     if (!(p->threshold >= 0 && p->threshold <= 1) || !(p->smoothness >= 0) || !std::isfinite(p->origin_x) || !std::isfinite(p->origin_y))
-        return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_render: threshold / smoothness / origin out of range");
+        return fail(h, EGG_ERR_INVALID_ARGUMENT, "%s: threshold / smoothness / origin out of range", name);
     for (int w = 0; w < 2; ++w)
         if (p->canvas_w[w] < 0 || p->canvas_h[w] < 0 || p->canvas_w[w] > 16384 || p->canvas_h[w] > 16384)
-            return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_render: canvas size out of range");
+            return fail(h, EGG_ERR_INVALID_ARGUMENT, "%s: canvas size out of range", name);
     HIP_TRY(h, hipSetDevice(h->device));
-    egg_handle::Render &R = h->render;
-    hipStream_t st = h->sys[0].stream;
-    HIP_TRY(h, hipStreamSynchronize(h->sys[1].stream));
+    egg_handle::Render &R = *S.R;
+    hipStream_t st = S.stream;
+    if (S.also_wait) HIP_TRY(h, hipStreamSynchronize(S.also_wait));
     const size_t npx = (size_t)p->screen_w * p->screen_h;
     HIP_TRY(h, R.screen.reserve(npx, false, st));
     hipLaunchKernelGGL(egg_render_clear_kernel, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, st, R.screen.p, npx,
@@ -213,31 +247,31 @@ int egg_render(egg_handle *h, const egg_render_params *p, float *rgba) {
     HIP_TRY(h, hipGetLastError());
     h->stats.kernel_launches++;
     // the canvases exist from the first _step on and only while both types have particles (L:1936-1938, L:1997-1999, L:2118)
-    const bool drawable = h->stats.steps > 0 && h->sys[0].n > 0 && h->sys[1].n > 0;
+    const bool drawable = S.stepped && S.t[0].n > 0 && S.t[1].n > 0;
     R.canvas_valid = false;
     if (drawable) {
-        const double t = std::isnan(p->interpolation_alpha) ? h->interpolation_alpha : clampd(p->interpolation_alpha, 0, 1);
-        int rc = render_texture(h);
+        const double t = std::isnan(p->interpolation_alpha) ? S.alpha : clampd(p->interpolation_alpha, 0, 1);
+        int rc = render_texture(h, R, S.max_radius, st);
         if (rc != EGG_OK) return rc;
         egg_environment env[2];
         EggCompositeArgs C;
         memset(&C, 0, sizeof C);
         for (int w = 0; w < 2; ++w) {
-            rc = egg_get_environment(h, w, &env[w]);
+            rc = environment_of(h, S.stepped, S.t[w], &env[w]);
             if (rc != EGG_OK) return rc;
-            const egg_render_config &cfg = R.cfg[w];
+            const egg_render_config &cfg = S.cfg[w];
             int cw = p->canvas_w[w], ch = p->canvas_h[w];
             if (cw == 0 || ch == 0) {  // resize_canvas_maybe (L:1935-1975)
                 const double padding = env[w].max_radius * cfg.texture_scale * (1 + std::max(1.0, env[w].max_velocity) * cfg.motion_blur);
                 const double nw = std::min(std::ceil((env[w].max_x - env[w].min_x) + 2 * padding), 2560.0);
                 const double nh = std::min(std::ceil((env[w].max_y - env[w].min_y) + 2 * padding), 2560.0);
-                if (!(nw >= 1) || !(nh >= 1)) return fail(h, EGG_ERR_UNSUPPORTED, "egg_render: particle bounds are not finite");
+                if (!(nw >= 1) || !(nh >= 1)) return fail(h, EGG_ERR_UNSUPPORTED, "%s: particle bounds are not finite", name);
                 R.canvas_w[w] = std::max(R.canvas_w[w], (int)nw);
                 R.canvas_h[w] = std::max(R.canvas_h[w], (int)nh);
                 if (cw == 0) cw = R.canvas_w[w];
                 if (ch == 0) ch = R.canvas_h[w];
             }
-            rc = render_splat(h, w, env[w], t, cw, ch, p->use_instancing);
+            rc = render_splat(S, w, env[w], t, cw, ch, p->use_instancing);
             if (rc != EGG_OK) return rc;
             // _draw_canvases places the canvas around the CURRENT centroid (L:2131-2132), pass 1 drew around the interpolated one
             R.canvas_x0[w] = env[w].centroid_x - 0.5 * cw;
@@ -260,8 +294,8 @@ int egg_render(egg_handle *h, const egg_render_params *p, float *rgba) {
         C.n_layers = 2;
         C.threshold = (float)p->threshold;
         C.smoothness = (float)p->smoothness;
-        C.use_particle_color = R.use_particle_color;
-        C.use_lighting = R.use_lighting;
+        C.use_particle_color = S.use_particle_color;
+        C.use_lighting = S.use_lighting;
         hipLaunchKernelGGL(egg_render_composite_kernel, dim3((unsigned)((p->screen_w + 15) / 16), (unsigned)((p->screen_h + 15) / 16)),
                            dim3(256), 0, st, C);
         HIP_TRY(h, hipGetLastError());
@@ -277,10 +311,10 @@ int egg_render(egg_handle *h, const egg_render_params *p, float *rgba) {
     return EGG_OK;
 }
 
-int egg_render_canvas(egg_handle *h, int which, float *rgba, int64_t cap_pixels, int32_t *w, int32_t *hgt, double *x0, double *y0) {
-    if (!h || (which != EGG_WHITE && which != EGG_YOLK)) return EGG_ERR_INVALID_ARGUMENT;
-    egg_handle::Render &R = h->render;
-    if (!R.canvas_valid) return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_render_canvas: no canvas (egg_render has not drawn anything)");
+// the density canvas of `which` as the last draw into R left it
+int render_canvas_from(egg_handle *h, egg_handle::Render &R, const char *name, int which, float *rgba, int64_t cap_pixels, int32_t *w,
+                       int32_t *hgt, double *x0, double *y0) {
+    if (!R.canvas_valid) return fail(h, EGG_ERR_INVALID_ARGUMENT, "%s_canvas: no canvas (%s has not drawn anything)", name, name);
     HIP_TRY(h, hipSetDevice(h->device));
     const int cw = R.last_w[which], ch = R.last_h[which];
     if (w) *w = cw;
@@ -289,16 +323,34 @@ int egg_render_canvas(egg_handle *h, int which, float *rgba, int64_t cap_pixels,
     if (y0) *y0 = R.canvas_y0[which];
     if (rgba) {
         if (cap_pixels < (int64_t)cw * ch)
-            return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_render_canvas: buffer holds %lld of %lld pixels", (long long)cap_pixels, (long long)cw * ch);
+            return fail(h, EGG_ERR_INVALID_ARGUMENT, "%s_canvas: buffer holds %lld of %lld pixels", name, (long long)cap_pixels, (long long)cw * ch);
         HIP_TRY(h, hipMemcpy(rgba, R.canvas[which].p, (size_t)cw * ch * 16, hipMemcpyDeviceToHost));
     }
     return EGG_OK;
 }
 
+}  // namespace egghost
+
+extern "C" {
+
+int egg_render(egg_handle *h, const egg_render_params *p, float *rgba) {
+    if (!h || !p) return EGG_ERR_INVALID_ARGUMENT;
+    REJECT_IN_FLIGHT(h, "egg_render");
+    HIP_TRY(h, hipSetDevice(h->device));
+    RenderSource S;
+    const int rc = render_source_of(h, S);
+    return rc != EGG_OK ? rc : render_from(S, p, rgba, "egg_render");
+}
+
+int egg_render_canvas(egg_handle *h, int which, float *rgba, int64_t cap_pixels, int32_t *w, int32_t *hgt, double *x0, double *y0) {
+    if (!h || (which != EGG_WHITE && which != EGG_YOLK)) return EGG_ERR_INVALID_ARGUMENT;
+    return render_canvas_from(h, h->render, "egg_render", which, rgba, cap_pixels, w, hgt, x0, y0);
+}
+
 int egg_render_particle_texture(egg_handle *h, float *alpha, int64_t cap, int32_t *size) {
     if (!h) return EGG_ERR_INVALID_ARGUMENT;
     HIP_TRY(h, hipSetDevice(h->device));
-    int rc = render_texture(h);
+    int rc = render_texture(h, h->render, std::max(h->sys[0].cfg.max_radius, h->sys[1].cfg.max_radius), h->sys[0].stream);
     if (rc != EGG_OK) return rc;
     const int n = h->render.tsize;
     if (size) *size = n;

@@ -1,14 +1,12 @@
 """SimulationGroup -- several GPUs of ONE process behind the SimulationHandler surface (ctypes twin of the egg_group_*
 entry points of include/eggsim.h; csrc/eggsim_group.cpp).  One device handle per x-slab, global batch ids, batches
-handed between devices when their claims meet across a cut; results equal a single handler's bit for bit.
+handed between devices when their claims meet across a cut; results equal a single handler's bit for bit, draw()
+included: its particles are gathered to the device of handle 0 in one global order and drawn there.
 (Between processes -- one per GPU, RCCL -- the same protocol is sharding.ShardedSimulationHandler.)"""
 import ctypes as C
-import math
-
-import numpy as np
 
 from . import _ffi
-from .simulation_handler import EggError, SimulationHandler
+from .simulation_handler import EggError, SimulationHandler, _HandlerSurface
 
 
 class _Borrowed(SimulationHandler):
@@ -21,20 +19,20 @@ class _Borrowed(SimulationHandler):
         self._h = None
 
 
-class SimulationGroup:
+class SimulationGroup(_HandlerSurface):
+    """The reference's `SimulationHandler` class over a device group: every public method of the class, with the
+    signatures, argument checks, warnings and error texts of SimulationHandler (shared code: _HandlerSurface).  Whatever
+    it returns or draws equals, bit for bit, what one SimulationHandler holding the same batches returns or draws."""
+
+    _PREFIX = "egg_group_"
+
+    def _ptr(self):
+        return self._g
+
     def __init__(self, devices, cuts=None, white_config=None, yolk_config=None):
-        tmpl = SimulationHandler.__new__(SimulationHandler)  # config validation of the reference (L:1253-1320), no device
-        from .default_config import default_configs
-        import copy
-        if white_config is None and yolk_config is None:
-            white_config, yolk_config = default_configs()
-        if yolk_config is None:
-            yolk_config = white_config
-        tmpl._white_config, tmpl._yolk_config = {}, {}
-        tmpl._mass_distribution_variance, tmpl._max_collision_fraction = 4, 0.05
-        tmpl._load_config(copy.deepcopy(white_config), True)
-        tmpl._load_config(copy.deepcopy(yolk_config), False)
         self._lib = _ffi.load()
+        self._g = None
+        self._init_host_state(white_config, yolk_config)
         devs = (C.c_int32 * len(devices))(*[int(d) for d in devices])
         cut = None
         if cuts is not None:
@@ -42,12 +40,13 @@ class SimulationGroup:
                 raise EggError("[ERROR] In SimulationGroup.new: need len(devices) + 1 cuts")
             cut = (C.c_double * len(cuts))(*[float(c) for c in cuts])
         g = C.c_void_p()
-        rc = self._lib.egg_group_create(C.byref(tmpl._c_config(True)), C.byref(tmpl._c_config(False)), len(devices), devs, cut, C.byref(g))
+        rc = self._lib.egg_group_create(C.byref(self._c_config(True)), C.byref(self._c_config(False)), len(devices), devs, cut, C.byref(g))
         if rc != _ffi.EGG_OK:
             raise EggError("[ERROR] In SimulationGroup.new: " + self._lib.egg_last_error(None).decode())
         self._g = g
         self._n_issued = 0  # ids issued so far (1 .. _n_issued; never reused)
         self.handles = [_Borrowed(self._lib, self._lib.egg_group_handle(self._g, k)) for k in range(len(devices))]
+        self._send_render_config()
 
     def __del__(self):
         self.close()
@@ -59,40 +58,17 @@ class SimulationGroup:
             self._lib.egg_group_destroy(self._g)
             self._g = None
 
-    def _check(self, rc):
-        if rc < 0:
-            raise EggError("[ERROR] " + self._lib.egg_group_last_error(self._g).decode())
-        return rc
-
-    def add(self, x, y, white_radius=None, yolk_radius=None, white_n=None, yolk_n=None):
-        out = C.c_int64()
-        self._check(self._lib.egg_group_add(
-            self._g, float(x), float(y), float("nan") if white_radius is None else float(white_radius),
-            float("nan") if yolk_radius is None else float(yolk_radius),
-            _ffi.DEFAULT_COUNT if white_n is None else int(white_n), _ffi.DEFAULT_COUNT if yolk_n is None else int(yolk_n), C.byref(out)))
-        self._n_issued = max(self._n_issued, out.value)
-        return out.value
-
-    def remove(self, batch_id):
-        self._check(self._lib.egg_group_remove(self._g, int(batch_id)))
-
-    def set_target_position(self, batch_id, x, y):
-        self._check(self._lib.egg_group_set_target(self._g, int(batch_id), float(x), float(y)))
-
-    def get_position(self, batch_id):
-        x, y = C.c_double(), C.c_double()
-        self._check(self._lib.egg_group_get_position(self._g, int(batch_id), C.byref(x), C.byref(y)))
-        return x.value, y.value
-
-    def update(self, delta, step_delta=None, n_substeps=None, n_collision_steps=None):
-        n = C.c_int32()
-        self._check(self._lib.egg_group_update(self._g, float(delta), 1 / 60 if step_delta is None else float(step_delta),
-                                               2 if n_substeps is None else int(math.ceil(n_substeps)),
-                                               3 if n_collision_steps is None else int(math.ceil(n_collision_steps)), C.byref(n)))
-        return n.value
-
-    def step(self, delta=1 / 60, n_substeps=2, n_collision_steps=3):
-        self._check(self._lib.egg_group_step(self._g, float(delta), int(n_substeps), int(n_collision_steps)))
+    def add(self, x, y, white_radius=None, yolk_radius=None, white_color=None, yolk_color=None,
+            white_n_particles=None, yolk_n_particles=None, white_n=None, yolk_n=None):  # L:27-135
+        """SimulationHandler.add; `white_n` / `yolk_n` are older names of the two counts"""
+        if white_n_particles is None:
+            white_n_particles = white_n
+        if yolk_n_particles is None:
+            yolk_n_particles = yolk_n
+        gid = _HandlerSurface.add(self, x, y, white_radius, yolk_radius, white_color, yolk_color, white_n_particles,
+                                  yolk_n_particles)
+        self._n_issued = max(self._n_issued, gid)
+        return gid
 
     def owner(self, batch_id):
         k, lid = C.c_int32(), C.c_int64()

@@ -11,6 +11,7 @@ Error conventions (log.lua:9-88): where the reference calls `log.error` /
 """
 import copy
 import ctypes as C
+import functools
 import math
 import warnings
 
@@ -80,17 +81,27 @@ _SOLVER_KEYS = ["damping", "follow_strength", "cohesion_strength", "cohesion_int
                 "max_radius"]
 
 
-class SimulationHandler:
-    """`SimulationHandler(white_config, yolk_config)` (L:11-15, L:425-459)."""
+class _HandlerSurface:
+    """The part of the reference's class that SimulationHandler (one device handle, `egg_*`) and SimulationGroup (a device
+    group, `egg_group_*`) share: argument checks, warnings, error texts and the calls, which differ only in the prefix of the
+    C entry point and the pointer they pass (`_PREFIX`, `_ptr`)."""
 
-    def __init__(self, white_config=None, yolk_config=None, device=0):
+    _PREFIX = "egg_"
+
+    def _ptr(self):
+        return self._h
+
+    def _c(self, name):
+        """the C entry point `name` of this object's kind, bound to its handle"""
+        return functools.partial(getattr(self._lib, self._PREFIX + name), self._ptr())
+
+    def _init_host_state(self, white_config, yolk_config):
+        """config tables (validated like the reference, L:1253-1320), hidden constants and render switches; no device"""
         if white_config is None and yolk_config is None:
             white_config, yolk_config = default_configs()
         if yolk_config is None:  # L:426
             yolk_config = white_config
         _assert_types(white_config, "table", yolk_config, "table")
-        self._lib = _ffi.load()
-        self._h = None
         self._white_config = {}
         self._yolk_config = {}
         self._load_config(copy.deepcopy(white_config), True)
@@ -104,21 +115,6 @@ class SimulationHandler:
         self._thresholding_smoothness = 0.01
         self._use_particle_color_flag = False
         self._use_lighting_flag = True
-        h = C.c_void_p()
-        rc = self._lib.egg_create(C.byref(self._c_config(True)), C.byref(self._c_config(False)), int(device),
-                                  C.byref(h))
-        if rc != _ffi.EGG_OK:
-            raise EggError("[ERROR] In SimulationHandler.new: " + self._lib.egg_last_error(None).decode())
-        self._h = h
-        self._send_render_config()
-
-    def __del__(self):
-        self.close()
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.egg_destroy(self._h)
-            self._h = None
 
     # ------------------------------------------------------------------ config
     def _load_config(self, config, white_or_yolk):  # L:1253-1320
@@ -177,7 +173,7 @@ class SimulationHandler:
         # this object's config tables are the authority for the render keys (colour tables may be shared with batches,
         # L:49-50); the library gets a copy whenever they may have changed
         for which in range(2):
-            self._check(self._lib.egg_set_render_config(self._h, which, C.byref(self._c_render_config(which == 0))))
+            self._check(self._c("set_render_config")(which, C.byref(self._c_render_config(which == 0))))
 
     def _c_render_config(self, white_or_yolk):
         """the render keys of a config table (simulation_handler_default_config.lua:22-36) as egg_render_config"""
@@ -198,7 +194,7 @@ class SimulationHandler:
     @_use_particle_color.setter
     def _use_particle_color(self, flag):
         self._use_particle_color_flag = bool(flag)
-        self._check(self._lib.egg_set_render_flags(self._h, int(self._use_particle_color_flag), int(self._use_lighting_flag)))
+        self._check(self._c("set_render_flags")(int(self._use_particle_color_flag), int(self._use_lighting_flag)))
 
     @property
     def _use_lighting(self):
@@ -207,18 +203,18 @@ class SimulationHandler:
     @_use_lighting.setter
     def _use_lighting(self, flag):
         self._use_lighting_flag = bool(flag)
-        self._check(self._lib.egg_set_render_flags(self._h, int(self._use_particle_color_flag), int(self._use_lighting_flag)))
+        self._check(self._c("set_render_flags")(int(self._use_particle_color_flag), int(self._use_lighting_flag)))
 
     def set_white_config(self, config):  # L:226-229
         _assert_types(config, "table")
         self._load_config(copy.deepcopy(config), True)
-        self._check(self._lib.egg_set_config(self._h, _ffi.WHITE, C.byref(self._c_config(True))))
+        self._check(self._c("set_config")(_ffi.WHITE, C.byref(self._c_config(True))))
         self._send_render_config()
 
     def set_yolk_config(self, config):  # L:233-236
         _assert_types(config, "table")
         self._load_config(copy.deepcopy(config), False)
-        self._check(self._lib.egg_set_config(self._h, _ffi.YOLK, C.byref(self._c_config(False))))
+        self._check(self._c("set_config")(_ffi.YOLK, C.byref(self._c_config(False))))
         self._send_render_config()
 
     def get_white_config(self):  # L:240-242
@@ -229,7 +225,7 @@ class SimulationHandler:
 
     # ------------------------------------------------------------ error mapping
     def _message(self):
-        return self._lib.egg_last_error(self._h).decode()
+        return self._c("last_error")().decode()
 
     def _check(self, rc):
         if rc == _ffi.EGG_OK:
@@ -269,7 +265,7 @@ class SimulationHandler:
                     warnings.warn("In SimulationHandler.add: %s color component `%s` is outside of [0, 1]"
                                   % (name, cname), EggWarning)
         out = C.c_int64()
-        rc = self._lib.egg_add(self._h, float(x), float(y),
+        rc = self._c("add")(float(x), float(y),
                                float("nan") if white_radius is None else float(white_radius),
                                float("nan") if yolk_radius is None else float(yolk_radius),
                                _ffi.DEFAULT_COUNT if white_n_particles is None else int(math.ceil(white_n_particles)),
@@ -281,8 +277,186 @@ class SimulationHandler:
         self._batch_colors[out.value] = [white_color, yolk_color]
         for which, color in enumerate((white_color, yolk_color)):
             if given[which]:
-                self._lib.egg_set_add_color(self._h, out.value, which, *[float(c) for c in color[:4]])
+                self._c("set_add_color")(out.value, which, *[float(c) for c in color[:4]])
         return out.value
+
+    def remove(self, batch_id):  # L:140-155
+        _assert_types(batch_id, "number")
+        rc = self._check(self._c("remove")(int(batch_id)))
+        if rc == _ffi.EGG_OK:
+            self._batch_colors.pop(int(batch_id), None)
+
+    def draw(self, screen_size=(800, 600), origin=(0.0, 0.0), interpolation_alpha=None, clear=(0.0, 0.0, 0.0, 0.0),
+             canvas_sizes=None, use_instancing=True):  # L:159-162
+        """`draw()` without a window: _update_canvases + _draw_canvases (L:1995-2175) as HIP kernels into a float32
+        RGBA image of screen_size = (width, height); world px = screen px + origin.  Returns an (H, W, 4) array.
+        canvas_sizes = [(w, h) white, (w, h) yolk] overrides the sizes resize_canvas_maybe would pick (L:1935-1975)."""
+        p = _ffi.EggRenderParams()
+        self._check(self._lib.egg_default_render_params(C.byref(p)))
+        p.screen_w, p.screen_h = int(screen_size[0]), int(screen_size[1])
+        p.origin_x, p.origin_y = float(origin[0]), float(origin[1])
+        if interpolation_alpha is not None:
+            p.interpolation_alpha = float(interpolation_alpha)
+        p.threshold = float(self._thresholding_threshold)
+        p.smoothness = float(self._thresholding_smoothness)
+        p.use_instancing = int(bool(use_instancing))
+        if canvas_sizes is not None:
+            for which in range(2):
+                p.canvas_w[which], p.canvas_h[which] = int(canvas_sizes[which][0]), int(canvas_sizes[which][1])
+        p.clear[:] = [float(c) for c in clear]
+        # (the render config is NOT re-sent here: egg_set_render_config means "set_*_config was called" -- a new colour
+        # table, L:1307-1311 -- and would end the sharing of the old one between the config and its colourless batches)
+        image = np.empty((p.screen_h, p.screen_w, 4), dtype=np.float32)
+        self._check(self._c("render")(C.byref(p), image.ctypes.data_as(C.c_void_p)))
+        return image
+
+    def render_canvas(self, which):
+        """the density canvas of `which` as the last draw() left it: ((h, w, 4) float32 array, (x0, y0) in world px)"""
+        w, h, x0, y0 = C.c_int32(), C.c_int32(), C.c_double(), C.c_double()
+        self._check(self._c("render_canvas")(int(which), None, 0, C.byref(w), C.byref(h), C.byref(x0), C.byref(y0)))
+        canvas = np.empty((h.value, w.value, 4), dtype=np.float32)
+        self._check(self._c("render_canvas")(int(which), canvas.ctypes.data_as(C.c_void_p), w.value * h.value,
+                                                None, None, None, None))
+        return canvas, (x0.value, y0.value)
+
+    # ------------------------------------------------------------------ update
+    def update(self, delta, step_delta=None, n_substeps=None, n_collision_steps=None):  # L:168-222
+        if step_delta is None:
+            step_delta = 1 / 60
+        if n_substeps is None:
+            n_substeps = 2
+        if n_collision_steps is None:
+            n_collision_steps = 3
+        _assert_types(delta, "number", step_delta, "number", n_substeps, "number", n_collision_steps, "number")
+        if _is_nan(n_substeps) or _is_nan(n_collision_steps):
+            raise EggError("[ERROR] In SimulationHandler.update: `n_substeps` is not a number > 0")
+        n_substeps = math.ceil(n_substeps)  # L:181-182
+        n_collision_steps = math.ceil(n_collision_steps)
+        n = C.c_int32()
+        self._check(self._c("update")(float(delta), float(step_delta), int(n_substeps),
+                                         int(n_collision_steps), C.byref(n)))
+        return n.value
+
+    def step(self, delta=1 / 60, n_substeps=2, n_collision_steps=3):
+        """`_step` directly (L:1722); not part of the reference's public surface."""
+        self._check(self._c("step")(float(delta), int(n_substeps), int(n_collision_steps)))
+
+    # ---------------------------------------------------------------- targets
+    def set_target_position(self, batch_id, x, y):  # L:254-264
+        _assert_types(batch_id, "number", x, "number", y, "number")
+        self._check(self._c("set_target")(int(batch_id), float(x), float(y)))
+
+    def get_target_position(self, batch_id):  # L:268-278
+        _assert_types(batch_id, "number")
+        x, y = C.c_double(), C.c_double()
+        self._check(self._c("get_target")(int(batch_id), C.byref(x), C.byref(y)))
+        return x.value, y.value
+
+    def get_position(self, batch_id):  # L:281-295
+        _assert_types(batch_id, "number")
+        x, y = C.c_double(), C.c_double()
+        self._check(self._c("get_position")(int(batch_id), C.byref(x), C.byref(y)))
+        return x.value, y.value
+
+    # ----------------------------------------------------------------- colors
+    # render attributes: kept on the host, never read by the solver (L:297-395)
+    def _set_color(self, scope, which, batch_id, r, g, b, a):
+        if a is None:
+            a = 1
+        _assert_types(batch_id, "number")
+        _assert_types(r, "number", g, "number", b, "number", a, "number")
+        if any(c > 1 or c < 0 for c in (r, g, b, a)):
+            warnings.warn("In SimulationHandler.%s: color component is outside of [0, 1]" % scope, EggWarning)
+        rgba = [min(max(c, 0), 1) for c in (r, g, b, a)]
+        if int(batch_id) not in self._batch_colors:
+            warnings.warn("In SimulationHandler.%s: no batch with id `%s`" % (scope, batch_id), EggWarning)
+            return
+        # in place (L:349-350, L:386-387): a batch created without a colour shares the config's table
+        table = self._batch_colors[int(batch_id)][which]
+        if isinstance(table, list):
+            table[:] = rgba
+        else:
+            self._batch_colors[int(batch_id)][which] = rgba
+        # its particles (L:1110-1129) and, when the batch shares the config's table, the config's colour: the library
+        # applies the same aliasing as the tables above
+        self._c("set_color")(int(batch_id), int(which), *[float(c) for c in rgba])
+
+    def set_white_color(self, batch_id, r, g, b, a=None, *outline):  # L:365-394
+        self._set_color("set_white_color", 0, batch_id, r, g, b, a)
+
+    def set_yolk_color(self, batch_id, r, g, b, a=None, *outline):  # L:328-357
+        self._set_color("set_egg_yolk_color", 1, batch_id, r, g, b, a)
+
+    # ------------------------------------------------------------ bookkeeping
+    def list_ids(self):  # L:399-405
+        n = C.c_int64()
+        self._check(self._c("list_ids")(0, None, C.byref(n)))
+        ids = np.empty(n.value, dtype=np.int64)
+        self._check(self._c("list_ids")(n.value, ids.ctypes.data, C.byref(n)))
+        return [int(i) for i in ids]
+
+    def get_n_particles(self, batch_or_nil=None):  # L:409-419
+        w, y = C.c_int64(), C.c_int64()
+        self._check(self._c("get_n_particles")(-1 if batch_or_nil is None else int(batch_or_nil),
+                                                  C.byref(w), C.byref(y)))
+        return w.value, y.value
+
+    @property
+    def elapsed(self):
+        e, a = C.c_double(), C.c_double()
+        self._c("get_elapsed")(C.byref(e), C.byref(a))
+        return e.value
+
+    @property
+    def interpolation_alpha(self):
+        e, a = C.c_double(), C.c_double()
+        self._c("get_elapsed")(C.byref(e), C.byref(a))
+        return a.value
+
+    def download(self, which, field):
+        """One particle field (name from _ffi.FIELDS) of every particle, particle-index order."""
+        w, y = self.get_n_particles()
+        n = w if which == _ffi.WHITE else y
+        out = np.empty(n, dtype=np.float64)
+        self._check(self._c("download_particles")(which, _ffi.FIELD_ID[field], out.ctypes.data, n))
+        return out
+
+    def download_instance_data(self, which):
+        """The reference's instanced-draw record per particle (L:513-517, L:744-813):
+        columns x, y, last_x, last_y, vx, vy, radius."""
+        cols = [self.download(which, f) for f in ("x", "y", "last_x", "last_y", "vx", "vy", "radius")]
+        return np.stack(cols, axis=1) if cols[0].size else np.zeros((0, 7))
+
+    def get_environment(self, which):
+        """the reductions the reference keeps per particle type for :draw() -- AABB incl. radius, centroid, largest
+        radius and speed, centroid at the start of the last step (simulation_handler.lua:1669-1718, 1795-1815)"""
+        e = _ffi.EggEnvironment()
+        self._check(self._c("get_environment")(int(which), C.byref(e)))
+        return {k: getattr(e, k) for k in _ffi.ENVIRONMENT_FIELDS}
+
+
+class SimulationHandler(_HandlerSurface):
+    """`SimulationHandler(white_config, yolk_config)` (L:11-15, L:425-459)."""
+
+    def __init__(self, white_config=None, yolk_config=None, device=0):
+        self._lib = _ffi.load()
+        self._h = None
+        self._init_host_state(white_config, yolk_config)
+        h = C.c_void_p()
+        rc = self._lib.egg_create(C.byref(self._c_config(True)), C.byref(self._c_config(False)), int(device),
+                                  C.byref(h))
+        if rc != _ffi.EGG_OK:
+            raise EggError("[ERROR] In SimulationHandler.new: " + self._lib.egg_last_error(None).decode())
+        self._h = h
+        self._send_render_config()
+
+    def __del__(self):
+        self.close()
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.egg_destroy(self._h)
+            self._h = None
 
     def add_many(self, xs, ys, white_radius=None, yolk_radius=None, white_n_particles=None,
                  yolk_n_particles=None):
@@ -344,45 +518,6 @@ class SimulationHandler:
         self._check(self._lib.egg_import_batch(self._h, C.byref(c), ws.ctypes.data, ys.ctypes.data, C.byref(out)))
         return out.value
 
-    def remove(self, batch_id):  # L:140-155
-        _assert_types(batch_id, "number")
-        rc = self._check(self._lib.egg_remove(self._h, int(batch_id)))
-        if rc == _ffi.EGG_OK:
-            self._batch_colors.pop(int(batch_id), None)
-
-    def draw(self, screen_size=(800, 600), origin=(0.0, 0.0), interpolation_alpha=None, clear=(0.0, 0.0, 0.0, 0.0),
-             canvas_sizes=None, use_instancing=True):  # L:159-162
-        """`draw()` without a window: _update_canvases + _draw_canvases (L:1995-2175) as HIP kernels into a float32
-        RGBA image of screen_size = (width, height); world px = screen px + origin.  Returns an (H, W, 4) array.
-        canvas_sizes = [(w, h) white, (w, h) yolk] overrides the sizes resize_canvas_maybe would pick (L:1935-1975)."""
-        p = _ffi.EggRenderParams()
-        self._check(self._lib.egg_default_render_params(C.byref(p)))
-        p.screen_w, p.screen_h = int(screen_size[0]), int(screen_size[1])
-        p.origin_x, p.origin_y = float(origin[0]), float(origin[1])
-        if interpolation_alpha is not None:
-            p.interpolation_alpha = float(interpolation_alpha)
-        p.threshold = float(self._thresholding_threshold)
-        p.smoothness = float(self._thresholding_smoothness)
-        p.use_instancing = int(bool(use_instancing))
-        if canvas_sizes is not None:
-            for which in range(2):
-                p.canvas_w[which], p.canvas_h[which] = int(canvas_sizes[which][0]), int(canvas_sizes[which][1])
-        p.clear[:] = [float(c) for c in clear]
-        # (the render config is NOT re-sent here: egg_set_render_config means "set_*_config was called" -- a new colour
-        # table, L:1307-1311 -- and would end the sharing of the old one between the config and its colourless batches)
-        image = np.empty((p.screen_h, p.screen_w, 4), dtype=np.float32)
-        self._check(self._lib.egg_render(self._h, C.byref(p), image.ctypes.data_as(C.c_void_p)))
-        return image
-
-    def render_canvas(self, which):
-        """the density canvas of `which` as the last draw() left it: ((h, w, 4) float32 array, (x0, y0) in world px)"""
-        w, h, x0, y0 = C.c_int32(), C.c_int32(), C.c_double(), C.c_double()
-        self._check(self._lib.egg_render_canvas(self._h, int(which), None, 0, C.byref(w), C.byref(h), C.byref(x0), C.byref(y0)))
-        canvas = np.empty((h.value, w.value, 4), dtype=np.float32)
-        self._check(self._lib.egg_render_canvas(self._h, int(which), canvas.ctypes.data_as(C.c_void_p), w.value * h.value,
-                                                None, None, None, None))
-        return canvas, (x0.value, y0.value)
-
     def particle_texture(self):
         """alpha of the particle density texture (L:620-682) the splat pass samples"""
         n = C.c_int32()
@@ -390,28 +525,6 @@ class SimulationHandler:
         tex = np.empty((n.value, n.value), dtype=np.float32)
         self._check(self._lib.egg_render_particle_texture(self._h, tex.ctypes.data_as(C.c_void_p), tex.size, None))
         return tex
-
-    # ------------------------------------------------------------------ update
-    def update(self, delta, step_delta=None, n_substeps=None, n_collision_steps=None):  # L:168-222
-        if step_delta is None:
-            step_delta = 1 / 60
-        if n_substeps is None:
-            n_substeps = 2
-        if n_collision_steps is None:
-            n_collision_steps = 3
-        _assert_types(delta, "number", step_delta, "number", n_substeps, "number", n_collision_steps, "number")
-        if _is_nan(n_substeps) or _is_nan(n_collision_steps):
-            raise EggError("[ERROR] In SimulationHandler.update: `n_substeps` is not a number > 0")
-        n_substeps = math.ceil(n_substeps)  # L:181-182
-        n_collision_steps = math.ceil(n_collision_steps)
-        n = C.c_int32()
-        self._check(self._lib.egg_update(self._h, float(delta), float(step_delta), int(n_substeps),
-                                         int(n_collision_steps), C.byref(n)))
-        return n.value
-
-    def step(self, delta=1 / 60, n_substeps=2, n_collision_steps=3):
-        """`_step` directly (L:1722); not part of the reference's public surface."""
-        self._check(self._lib.egg_step(self._h, float(delta), int(n_substeps), int(n_collision_steps)))
 
     def step_begin(self, delta=1 / 60, n_substeps=2, n_collision_steps=3):
         """launch a `_step` without waiting for it (see egg_step_begin)"""
@@ -431,29 +544,12 @@ class SimulationHandler:
         """form the tiles/claims of the next step without running it (multi-GPU exchange)"""
         self._check(self._lib.egg_prepare_step(self._h, float(step_delta), int(n_substeps), int(n_collision_steps)))
 
-    # ---------------------------------------------------------------- targets
-    def set_target_position(self, batch_id, x, y):  # L:254-264
-        _assert_types(batch_id, "number", x, "number", y, "number")
-        self._check(self._lib.egg_set_target(self._h, int(batch_id), float(x), float(y)))
-
     def set_target_positions(self, ids, xs, ys):
         ids = np.ascontiguousarray(ids, dtype=np.int64)
         xs = np.ascontiguousarray(xs, dtype=np.float64)
         ys = np.ascontiguousarray(ys, dtype=np.float64)
         self._check(self._lib.egg_set_targets_many(self._h, ids.shape[0], ids.ctypes.data, xs.ctypes.data,
                                                    ys.ctypes.data))
-
-    def get_target_position(self, batch_id):  # L:268-278
-        _assert_types(batch_id, "number")
-        x, y = C.c_double(), C.c_double()
-        self._check(self._lib.egg_get_target(self._h, int(batch_id), C.byref(x), C.byref(y)))
-        return x.value, y.value
-
-    def get_position(self, batch_id):  # L:281-295
-        _assert_types(batch_id, "number")
-        x, y = C.c_double(), C.c_double()
-        self._check(self._lib.egg_get_position(self._h, int(batch_id), C.byref(x), C.byref(y)))
-        return x.value, y.value
 
     def get_positions(self, ids):
         ids = np.ascontiguousarray(ids, dtype=np.int64)
@@ -479,85 +575,9 @@ class SimulationHandler:
         self._check(self._lib.egg_get_claims_many(self._h, ids.shape[0], ids.ctypes.data, out.ctypes.data, cells.ctypes.data))
         return out, (float(cells[0]), float(cells[1]))
 
-    # ----------------------------------------------------------------- colors
-    # render attributes: kept on the host, never read by the solver (L:297-395)
-    def _set_color(self, scope, which, batch_id, r, g, b, a):
-        if a is None:
-            a = 1
-        _assert_types(batch_id, "number")
-        _assert_types(r, "number", g, "number", b, "number", a, "number")
-        if any(c > 1 or c < 0 for c in (r, g, b, a)):
-            warnings.warn("In SimulationHandler.%s: color component is outside of [0, 1]" % scope, EggWarning)
-        rgba = [min(max(c, 0), 1) for c in (r, g, b, a)]
-        if int(batch_id) not in self._batch_colors:
-            warnings.warn("In SimulationHandler.%s: no batch with id `%s`" % (scope, batch_id), EggWarning)
-            return
-        # in place (L:349-350, L:386-387): a batch created without a colour shares the config's table
-        table = self._batch_colors[int(batch_id)][which]
-        if isinstance(table, list):
-            table[:] = rgba
-        else:
-            self._batch_colors[int(batch_id)][which] = rgba
-        # its particles (L:1110-1129) and, when the batch shares the config's table, the config's colour: the library
-        # applies the same aliasing as the tables above
-        self._lib.egg_set_color(self._h, int(batch_id), int(which), *[float(c) for c in rgba])
-
-    def set_white_color(self, batch_id, r, g, b, a=None, *outline):  # L:365-394
-        self._set_color("set_white_color", 0, batch_id, r, g, b, a)
-
-    def set_yolk_color(self, batch_id, r, g, b, a=None, *outline):  # L:328-357
-        self._set_color("set_egg_yolk_color", 1, batch_id, r, g, b, a)
-
-    # ------------------------------------------------------------ bookkeeping
-    def list_ids(self):  # L:399-405
-        n = C.c_int64()
-        self._check(self._lib.egg_list_ids(self._h, 0, None, C.byref(n)))
-        ids = np.empty(n.value, dtype=np.int64)
-        self._check(self._lib.egg_list_ids(self._h, n.value, ids.ctypes.data, C.byref(n)))
-        return [int(i) for i in ids]
-
-    def get_n_particles(self, batch_or_nil=None):  # L:409-419
-        w, y = C.c_int64(), C.c_int64()
-        self._check(self._lib.egg_get_n_particles(self._h, -1 if batch_or_nil is None else int(batch_or_nil),
-                                                  C.byref(w), C.byref(y)))
-        return w.value, y.value
-
-    @property
-    def elapsed(self):
-        e, a = C.c_double(), C.c_double()
-        self._lib.egg_get_elapsed(self._h, C.byref(e), C.byref(a))
-        return e.value
-
-    @property
-    def interpolation_alpha(self):
-        e, a = C.c_double(), C.c_double()
-        self._lib.egg_get_elapsed(self._h, C.byref(e), C.byref(a))
-        return a.value
-
     # ---------------------------------------------------------- device access
     def synchronize(self):
         self._check(self._lib.egg_synchronize(self._h))
-
-    def download(self, which, field):
-        """One particle field (name from _ffi.FIELDS) of every particle, particle-index order."""
-        w, y = self.get_n_particles()
-        n = w if which == _ffi.WHITE else y
-        out = np.empty(n, dtype=np.float64)
-        self._check(self._lib.egg_download_particles(self._h, which, _ffi.FIELD_ID[field], out.ctypes.data, n))
-        return out
-
-    def download_instance_data(self, which):
-        """The reference's instanced-draw record per particle (L:513-517, L:744-813):
-        columns x, y, last_x, last_y, vx, vy, radius."""
-        cols = [self.download(which, f) for f in ("x", "y", "last_x", "last_y", "vx", "vy", "radius")]
-        return np.stack(cols, axis=1) if cols[0].size else np.zeros((0, 7))
-
-    def get_environment(self, which):
-        """the reductions the reference keeps per particle type for :draw() -- AABB incl. radius, centroid, largest
-        radius and speed, centroid at the start of the last step (simulation_handler.lua:1669-1718, 1795-1815)"""
-        e = _ffi.EggEnvironment()
-        self._check(self._lib.egg_get_environment(self._h, int(which), C.byref(e)))
-        return {k: getattr(e, k) for k in _ffi.ENVIRONMENT_FIELDS}
 
     def stats(self):
         s = _ffi.EggStats()

@@ -333,8 +333,8 @@ int egg_set_option(egg_handle *h, int option, double value);
  * NULL with one device), global batch ids.  A batch is stepped by the device whose slab held its position when it was
  * added; batches whose claims for a step come within one spatial-hash cell of each other across devices are handed to
  * ONE device before that step runs (exact Gauss-Seidel order cannot cross a cut), so the results equal a
- * single handle's bit for bit.  A collision budget 0.05 N^2 (L:1752-1753) that could bind across devices is refused with
- * EGG_ERR_UNSUPPORTED.  In relaxed order (egg_group_set_solver_order) nothing is handed over before a step: every
+ * single handle's bit for bit.  A collision budget 0.05 N^2 (L:1752-1753) that could bind (few batches) needs every particle
+ * of the type in one tile: the group then hands every batch to device 0 and steps there until batches are added or removed.  In relaxed order (egg_group_set_solver_order) nothing is handed over before a step: every
  * collision pass runs on every device over its own particles plus read-only ghost copies of its neighbours' particles
  * near it, and the results equal ONE relaxed handle holding every batch, bit for bit.  The same
  * device ordinal may appear more than once (several handles on one GPU: testing); different ordinals need peer access
@@ -367,6 +367,48 @@ int egg_group_get_counters(const egg_group *g, int64_t *migrations, int64_t *dis
 int egg_group_set_solver_order(egg_group *g, int32_t order, double relaxation);
 /* cumulative over relaxed group steps, both types: collision passes, ghost records the devices received, their bytes */
 int egg_group_get_halo_counters(const egg_group *g, int64_t *passes, int64_t *records, int64_t *bytes);
+
+/* ---- the rest of the SimulationHandler surface on a group.  One rule: whatever a group returns or draws equals, bit for
+ * bit, what ONE handle holding the same batches (added in the same order) returns or draws -- in exact and in relaxed
+ * order, wherever the cuts are and wherever hand-overs have put the batches.  Particle order is the group's global key:
+ * the particle's index in one handle holding every live batch in ascending global id. */
+/* set_white_config / set_yolk_config, get_*_config (L:226-248): the solver keys, for every handle of the group; the next
+ * _step re-derives mass and radius exactly as one handle does (L:1731-1744) */
+int egg_group_set_config(egg_group *g, int which, const egg_config *cfg);
+int egg_group_get_config(const egg_group *g, int which, egg_config *cfg);
+/* get_target_position (L:268-278) */
+int egg_group_get_target(const egg_group *g, int64_t id, double *x, double *y);
+/* list_ids (L:399-405): ascending global ids of the live batches; returns the count in *n, copies min(*n, cap) ids */
+int egg_group_list_ids(const egg_group *g, int64_t cap, int64_t *ids, int64_t *n);
+/* get_n_particles(id) / get_n_particles() with id < 0: totals over the group (L:409-419) */
+int egg_group_get_n_particles(const egg_group *g, int64_t id, int64_t *n_white, int64_t *n_yolk);
+/* elapsed / interpolation_alpha of egg_group_update (L:199-216) */
+int egg_group_get_elapsed(const egg_group *g, double *elapsed, double *interpolation_alpha);
+/* egg_download_particles over the group: one field of every particle of `which` in global-key order (doubles) */
+int egg_group_download_particles(egg_group *g, int which, int field, double *dst, int64_t cap);
+/* egg_get_environment over the group: the reductions run over all particles of the type in global-key order on the
+ * device of handle 0, so all ten fields equal one handle's (the centroid sums are serial in particle order) */
+int egg_group_get_environment(egg_group *g, int which, egg_environment *out);
+/* Render attributes live in the GROUP (per global id / per type), not in its handles: a hand-over cannot lose them.
+ * Semantics exactly as egg_set_render_config .. egg_set_color above, the reference's aliasing included: the render keys
+ * of set_*_config give the config a NEW colour table (L:1307-1311); a batch created without a colour shares the
+ * config's table (L:49-50), so egg_group_set_color on it retints the config; components clamp in egg_group_set_color
+ * (L:300-319) and do not in egg_group_set_add_color (L:978-984); unknown id: EGG_WARN_UNKNOWN_ID from egg_group_set_color.
+ * egg_group_add keeps its signature: call egg_group_set_add_color right after it for a colour argument of add (L:22-23). */
+int egg_group_set_render_config(egg_group *g, int which, const egg_render_config *cfg);
+int egg_group_get_render_config(const egg_group *g, int which, egg_render_config *cfg);
+int egg_group_set_render_flags(egg_group *g, int32_t use_particle_color, int32_t use_lighting);
+int egg_group_set_add_color(egg_group *g, int64_t id, int which, double r, double gr, double b, double a);
+int egg_group_set_color(egg_group *g, int64_t id, int which, double r, double gr, double b, double a);
+/* draw() of the group (L:158-161), as egg_render: every particle is gathered to the device of handle 0 in global-key
+ * order (peer access between different ordinals: EGG_ERR_UNSUPPORTED without it), then the passes of egg_render run
+ * there.  Nothing is drawn before the group's first _step or while the GROUP has no particles of one type; the canvases
+ * grow only, over the group's draws (L:1957-1970); interpolation_alpha = NaN takes the group's (egg_group_update).
+ * Refused while a handle of the group has a step in flight.  At most 2^31 - 1 particles of a type. */
+int egg_group_render(egg_group *g, const egg_render_params *p, float *rgba);
+/* the density canvas of `which` as the last egg_group_render left it (egg_render_canvas) */
+int egg_group_render_canvas(egg_group *g, int which, float *rgba, int64_t cap_pixels, int32_t *w, int32_t *hgt, double *x0,
+                            double *y0);
 
 #ifdef __cplusplus
 }
