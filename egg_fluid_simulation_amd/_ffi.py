@@ -96,6 +96,14 @@ class EggRenderParams(C.Structure):  # egg_render_params
                 ("clear", C.c_float * 4)]
 
 
+class EggRxBox(C.Structure):  # egg_rx_box: a cell box of the relaxed halo between processes
+    _fields_ = [("lo_x", C.c_int32), ("lo_y", C.c_int32), ("hi_x", C.c_int32), ("hi_y", C.c_int32), ("empty", C.c_int32)]
+
+
+RX_BOX_INTS = 5        # int32 fields of egg_rx_box
+RX_RECORD_WORDS = 5    # 64-bit words of a ghost record: x, y, inverse mass, radius (doubles), global key (int64)
+RX_RECORD_BYTES = 40
+
 PK_KINDS = ["egg_pk_begin_kernel", "egg_pk_mid_kernel", "egg_pk_lists_fresh_kernel", "egg_pk_lists_stale_kernel",
             "egg_pk_levels_kernel", "egg_pk_sort_kernel", "egg_pk_exec_kernel", "egg_pk_end_kernel", "egg_pk_reduce_kernel",
             "egg_pk_pass_kernel"]
@@ -183,6 +191,15 @@ _SIGNATURES = {
     "egg_render_canvas": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                     C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "egg_render_particle_texture": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]),
+    "egg_rx_set_keys": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]),
+    "egg_rx_begin": (C.c_int, [C.c_void_p, C.c_double, C.c_int32, C.c_int32]),
+    "egg_rx_substep": (C.c_int, [C.c_void_p, C.c_int32]),
+    "egg_rx_get_boxes": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "egg_rx_pack": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "egg_rx_fetch": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "egg_rx_run_pass": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "egg_rx_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64 * 2), C.POINTER(C.c_int64)]),
+    "egg_rx_end": (C.c_int, [C.c_void_p, C.c_int32]),
 }
 
 EXPORTED_SYMBOLS = sorted(_SIGNATURES)

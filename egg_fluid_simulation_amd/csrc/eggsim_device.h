@@ -327,6 +327,33 @@ struct EggRxUnpackArgs {  // receiver side: pulls every sender's records for it 
     const unsigned long long *count[EGG_RX_MAX_GROUP];
 };
 
+// Several processes ("Several processes"; eggsim_relaxed_wire.hip): the same halo when the
+// other handles live in other processes.  Nothing of another handle is addressable: the destinations' boxes arrive
+// as a small array in the sender's own memory, and the ghosts travel as MESSAGES -- word 0 the record count, then
+// the 40-byte EggGhost records, contiguous -- which the host hands to the wire and the receiver reads from local memory.
+#define EGG_RX_WIRE_BOX 5          // int32 per box: lo_x, lo_y, hi_x, hi_y (cells), empty flag -- egg_rx_box
+#define EGG_RX_WIRE_RECORD_WORDS 5 // 64-bit words of a record
+struct EggRxWirePackArgs {  // sender side: one launch packs for up to EGG_RX_MAX_GROUP destinations
+    int32_t n, n_dest;                   // local particles; destinations of this launch
+    double cell_size;
+    const double2 *pos;
+    const double *inv_mass, *radius;
+    const int32_t *ekey;
+    const int32_t *boxes;                // [n_dest][EGG_RX_WIRE_BOX]: the destinations' boxes for this pass
+    unsigned long long *msg;             // [n_dest] messages of `stride` words each (capacity n records, header zeroed)
+    long long stride;
+};
+struct EggRxWireUnpackArgs {  // receiver side: up to EGG_RX_MAX_GROUP received messages into the ghost entries
+    int32_t n, n_src;                    // local particles; messages of this launch
+    int32_t cap_ghost;                   // ghost entries the arrays hold
+    double2 *pos;                        // positions of this pass; ghosts go to [n + g]
+    double2 *gwr;
+    int32_t *ekey;
+    unsigned long long *n_ghost;
+    const unsigned long long *msg[EGG_RX_MAX_GROUP];  // in this handle's memory
+    int32_t cap[EGG_RX_MAX_GROUP];                    // records the host was told each message holds
+};
+
 // ---------------------------------------------------------------------------------------------
 // Draw of a device group (eggsim_render_group.hip): the particles of ONE source handle and type are copied into the
 // render device's shadow arrays, which hold every particle of the group in global-key order.  A RUN is a stretch of

@@ -9,6 +9,7 @@
 //   eggsim_host_render.hip  egg_render* : the headless renderer's host side
 //   eggsim_host_relaxed.hip _step in relaxed order (EGG_OPT_SOLVER_ORDER = 1): the launches of eggsim_relaxed.hip
 //   eggsim_host_relaxed_group.hip  the same step over the handles of a device group, with per-pass ghost halos
+//   eggsim_host_relaxed_wire.hip   the same step driven pass by pass through the C ABI (egg_rx_*): one handle per process
 //   eggsim_host_render_group.hip   draw / environment / download of a device group: gather to one device (eggsim_render_group.hip)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -21,6 +22,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <memory>
 #include <numeric>
 #include <string>
 #include <vector>
@@ -75,6 +77,8 @@ extern "C" __global__ void egg_rx_gather_group_kernel(EggRelaxedGroupArgs A);
 extern "C" __global__ void egg_rx_gkey_kernel(const int32_t *, const int32_t *, const int32_t *, int, int32_t *);
 extern "C" __global__ void egg_rx_pack_kernel(EggRxPackArgs P);
 extern "C" __global__ void egg_rx_unpack_kernel(EggRxUnpackArgs U);
+extern "C" __global__ void egg_rx_wire_pack_kernel(EggRxWirePackArgs P);
+extern "C" __global__ void egg_rx_wire_unpack_kernel(EggRxWireUnpackArgs U);
 extern "C" __global__ void egg_group_gather_kernel(EggGatherArgs A);
 extern "C" __global__ void egg_render_count_kernel(EggRenderArgs A);
 extern "C" __global__ void egg_render_fill_kernel(EggRenderArgs A);
@@ -234,6 +238,11 @@ struct RelaxedBufs {
     DevBuf<double2> gwr;                  // [ghosts] (inverse mass, radius)
     DevBuf<EggGhost> send;                // [receivers][n] this handle's ghost records for the others
     std::vector<uint64_t> key_sig;        // every handle's atoms_gen when the keys were built
+    // several processes (eggsim_host_relaxed_wire.hip): messages = word 0 the record count, then the records
+    DevBuf<unsigned long long> wsend, wrecv;  // [destinations][1 + 5 n] packed here; staging copies of the received ones
+    DevBuf<int32_t> wbox;                     // [destinations][EGG_RX_WIRE_BOX] the destinations' boxes of a pass
+    PinnedBuf<int32_t> h_wbox;
+    PinnedBuf<unsigned long long> h_wcount;   // [destinations] record counts of the last pack
     hipEvent_t ev_box[2] = {nullptr, nullptr}, ev_pack[2] = {nullptr, nullptr};  // by pass parity
     RelaxedBufs() = default;
     RelaxedBufs(const RelaxedBufs &) = delete;
@@ -337,6 +346,9 @@ inline int32_t *d_aabb(System &s) { return s.d_out.p + 2 * kStatInts; }
 inline int32_t *d_disp(System &s) { return s.d_out.p + 2 * kStatInts + 4 * s.atoms.size(); }
 
 }  // namespace egghost
+namespace egghost {
+struct WireStep;  // a relaxed step in flight between egg_rx_begin and egg_rx_end (eggsim_host_relaxed_wire.hip)
+}
 using namespace egghost;
 
 struct egg_handle {
@@ -372,6 +384,8 @@ struct egg_handle {
     bool in_flight = false;        // egg_step_begin without its egg_step_end
     double flight_delta = 0;
     int flight_s = 0, flight_c = 0;
+    bool wire_active = false;      // egg_rx_begin without its egg_rx_end
+    std::shared_ptr<egghost::WireStep> wire;  // global keys and the step in flight, allocated by the first egg_rx_* call
     // headless renderer (eggsim_render.hip)
     struct Render {
         egg_render_config cfg[2];
@@ -397,6 +411,7 @@ int fail(egg_handle *h, int code, const char *fmt, ...);
 #define REJECT_IN_FLIGHT(h, name)                                                                      \
     do {                                                                                               \
         if ((h)->in_flight) return fail(h, EGG_ERR_INVALID_ARGUMENT, name ": a step is in flight (egg_step_begin without egg_step_end)"); \
+        if ((h)->wire_active) return fail(h, EGG_ERR_INVALID_ARGUMENT, name ": a step is in flight (egg_rx_begin without egg_rx_end)"); \
     } while (0)
 
 #define HIP_TRY(h, expr)                                                                               \

@@ -1,0 +1,97 @@
+// eggsim_relaxed_wire.hip -- gfx950 kernels of the relaxed-order ghost halo between PROCESSES (DESIGN.md section 2.7,
+// "Several processes"; host: eggsim_host_relaxed_wire.hip).  The pass itself is eggsim_relaxed.hip's, in its group
+// instantiations (local entries + ghosts with keys); only the two kernels that move the ghosts differ from the device
+// group's: no pointer here leads into another handle's memory.
+//
+//   egg_rx_wire_pack_kernel    sender: the destinations' cell boxes come from a small array in the sender's own memory
+//                              (the host filled it from the wire); per destination ONE contiguous message --
+//                              word 0 the record count, then the EggGhost records -- that the host copies to the wire
+//   egg_rx_wire_unpack_kernel  receiver: messages in local memory (a staging copy of the received tensors) into the
+//                              ghost entries [n, n + ghosts)
+//
+// Plain vector loads and stores; the appends are wave-aggregated (one atomic per wave and destination).
+#include <hip/hip_runtime.h>
+#include "eggsim_device.h"
+
+namespace {
+
+// cell of a position, as rx_cell of eggsim_relaxed.hip: (0, 0) for a NaN coordinate or a cell outside +-2^30 (the
+// insert kernel of the pass flags it, and the step fails on every rank)
+__device__ __forceinline__ void wire_cell(double2 p, double cell, int32_t &cx, int32_t &cy) {
+    const double fx = floor(p.x / cell), fy = floor(p.y / cell);
+    const bool ok = fx >= -0x1p30 && fx <= 0x1p30 && fy >= -0x1p30 && fy <= 0x1p30;
+    cx = ok ? (int32_t)fx : 0;
+    cy = ok ? (int32_t)fy : 0;
+}
+
+// Wave-aggregated append, as rx_append of eggsim_relaxed.hip: the lanes with `take` get consecutive slots of *counter.
+__device__ __forceinline__ int wire_append(unsigned long long *counter, bool take) {
+    const unsigned long long mask = __ballot(take);
+    if (!mask) return 0;
+    const int lane = (int)(threadIdx.x & 63);
+    const int leader = __ffsll((long long)mask) - 1;
+    unsigned long long base = 0;
+    if (lane == leader) base = atomicAdd(counter, (unsigned long long)__popcll(mask));
+    base = __shfl(base, leader, 64);
+    return (int)base + __popcll(mask & ((1ull << lane) - 1ull));
+}
+
+}  // namespace
+
+// Sender: every local particle whose cell lies in a destination's cell box grown by one cell on each side goes into
+// that destination's message, in any order (the receiver's rank kernel orders by key).  A particle goes to a
+// destination at most once: a message with room for n records cannot overflow.
+extern "C" __global__ void __launch_bounds__(256) egg_rx_wire_pack_kernel(EggRxWirePackArgs P) {
+    __shared__ int32_t bx[EGG_RX_MAX_GROUP][4];  // lo x, hi x, lo y, hi y, grown (|cell| <= 2^30: no overflow)
+    if (threadIdx.x < (unsigned)P.n_dest) {
+        const int32_t *b = P.boxes + (size_t)threadIdx.x * EGG_RX_WIRE_BOX;
+        if (b[4]) {  // the destination wrote no position: nothing is near it
+            bx[threadIdx.x][0] = bx[threadIdx.x][2] = 1;
+            bx[threadIdx.x][1] = bx[threadIdx.x][3] = 0;
+        } else {
+            bx[threadIdx.x][0] = b[0] - 1;
+            bx[threadIdx.x][1] = b[2] + 1;
+            bx[threadIdx.x][2] = b[1] - 1;
+            bx[threadIdx.x][3] = b[3] + 1;
+        }
+    }
+    __syncthreads();
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    const bool live = i < P.n;
+    int32_t cx = 0, cy = 0;
+    EggGhost g{};
+    if (live) {
+        const double2 p = P.pos[i];
+        wire_cell(p, P.cell_size, cx, cy);
+        g.x = p.x;
+        g.y = p.y;
+        g.inv_mass = P.inv_mass[i];
+        g.radius = P.radius[i];
+        g.key = P.ekey[i];
+    }
+    for (int k = 0; k < P.n_dest; ++k) {
+        const bool take = live && cx >= bx[k][0] && cx <= bx[k][1] && cy >= bx[k][2] && cy <= bx[k][3];
+        unsigned long long *m = P.msg + (size_t)k * (size_t)P.stride;
+        const int slot = wire_append(m, take);
+        if (take) reinterpret_cast<EggGhost *>(m + 1)[slot] = g;
+    }
+}
+
+// Receiver: the records of every received message, appended to the ghost entries [n, n + n_ghost).  Grid: x over the
+// largest message, y over the messages.  A message never yields more records than the host was told it holds.
+extern "C" __global__ void __launch_bounds__(256) egg_rx_wire_unpack_kernel(EggRxWireUnpackArgs U) {
+    const int s = (int)blockIdx.y;
+    const int q = (int)(blockIdx.x * 256 + threadIdx.x);
+    const unsigned long long *m = U.msg[s];
+    const unsigned long long said = m[0];
+    const int cnt = said < (unsigned long long)U.cap[s] ? (int)said : U.cap[s];
+    if ((int)(blockIdx.x * 256) >= cnt) return;  // (uniform over the workgroup)
+    const bool take = q < cnt;
+    const int slot = wire_append(U.n_ghost, take);
+    if (take && slot < U.cap_ghost) {
+        const EggGhost r = reinterpret_cast<const EggGhost *>(m + 1)[q];
+        U.pos[U.n + slot] = make_double2(r.x, r.y);
+        U.gwr[slot] = make_double2(r.inv_mass, r.radius);
+        U.ekey[U.n + slot] = (int32_t)r.key;
+    }
+}

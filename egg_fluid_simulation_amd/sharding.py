@@ -30,8 +30,16 @@ Collectives: ONE small all_reduce per step (4 flags: conflict seen / budget susp
 slab's halo / a claim reaches past a whole neighbouring slab) tells every rank whether the launched step may be
 committed; everything else on the data path is neighbour point-to-point.  The rare hand-over round exchanges its
 plan with two all_gathers of fixed-shape integer tensors (no pickling).
+
+Relaxed order (ShardedSimulationHandler.set_solver_order("relaxed"), DESIGN.md section 2.7 "Several processes") needs none of
+this: a Jacobi pass reads only the positions at the start of the pass, so every rank runs every collision pass over its
+own particles plus read-only ghost copies of the other ranks' particles near its cell box.  HaloExchange carries the
+boxes (one all_gather per pass) and the 40-byte ghost records (point to point, only between ranks whose boxes are
+within one cell of each other); nothing is handed over before a step, no step is re-run, and the results equal ONE
+relaxed handler holding every batch, bit for bit.
 """
 import math
+import time
 
 import numpy as np
 
@@ -225,12 +233,139 @@ class BoundaryExchange:
         return self.finish(raise_on_conflict)
 
 
+class HaloExchange:
+    """Per-pass exchange of the relaxed-order ghost halo between the ranks ("Several processes").
+
+    Per collision pass p, on every rank:
+      1. source.rx_get_boxes(p): this rank's cell box per type (lo_x, lo_y, hi_x, hi_y, empty; int32);
+      2. ONE all_gather of the [2, 5] int32 boxes: every rank knows every box of the pass;
+      3. the PARTNERS of a rank are the ranks whose box of some type lies within one cell of its own box of that type
+         (a symmetric relation both sides compute from the same gathered boxes -- nothing else decides who talks);
+      4. source.rx_pack(p, partners' boxes) -> record counts; a fixed-shape count message (2 int64) goes to every
+         partner and one comes back; then, where a count is not zero, ONE payload message of the announced size:
+         the white message followed by the yolk message, each `count, records...` in 64-bit words (5 per record);
+      5. the caller runs the pass over its particles + the received messages (received()).
+    Nothing is pickled and every message size is fixed or announced.  `source` is a SimulationHandler or anything with
+    its rx_get_boxes / rx_pack / rx_fetch (tests inject a numpy model)."""
+
+    BOX = 5            # int32 per box
+    RECORD_WORDS = 5   # 64-bit words per ghost record
+    RECORD_BYTES = 40
+
+    def __init__(self, source, rank, world, group=None, device=None):
+        self.source, self.rank, self.world = source, int(rank), int(world)
+        self.dist = group
+        self.passes = self.records = 0          # passes exchanged; ghost records received
+        self.collectives = self.messages = 0    # all_gathers; point-to-point messages sent
+        self.host_seconds = 0.0                 # wall time spent in exchange()
+        self.host_syncs = 0                     # source calls that wait for the device (boxes; pack and fetch with partners)
+        self.partners, self.boxes = [], None    # of the last exchange
+        self._recv, self._send, self._counts_in = [], [], np.zeros((0, 2), dtype=np.int64)
+        if self.world > 1:
+            import torch
+            self.torch = torch
+            if device is None:
+                device = "cuda" if group.get_backend() == "nccl" else "cpu"
+            self.device = device
+            self._on_gpu = str(device).startswith("cuda")
+
+    @property
+    def bytes(self):
+        return self.RECORD_BYTES * self.records
+
+    @staticmethod
+    def near(a, b):
+        """two boxes (lo_x, lo_y, hi_x, hi_y, empty) are within one cell of each other: a particle of the one can lie in
+        the other grown by one cell"""
+        return bool(not a[4] and not b[4] and a[0] - 1 <= b[2] and b[0] - 1 <= a[2] and a[1] - 1 <= b[3] and b[1] - 1 <= a[3])
+
+    def _wait(self, ops):
+        if not ops:
+            return
+        for req in self.dist.batch_isend_irecv(ops):
+            req.wait()
+        if self._on_gpu:  # the receives ran on torch's stream: complete before anyone else reads the tensors
+            self.torch.cuda.current_stream().synchronize()
+
+    def exchange(self, p):
+        """the halo of pass p; returns (pointers [n, 2], counts [n, 2]) of the received messages for rx_run_pass.  The
+        tensors behind the pointers live until the next exchange()."""
+        t0 = time.perf_counter()
+        torch, dist = self.torch, self.dist
+        mine = np.ascontiguousarray(self.source.rx_get_boxes(p), dtype=np.int32).reshape(2, self.BOX)
+        box = torch.from_numpy(mine.reshape(-1).copy()).to(self.device)
+        parts = [torch.zeros(2 * self.BOX, dtype=torch.int32, device=self.device) for _ in range(self.world)]
+        dist.all_gather(parts, box)
+        self.collectives += 1
+        boxes = np.stack([q.cpu().numpy() for q in parts]).reshape(self.world, 2, self.BOX)
+        partners = [k for k in range(self.world)
+                    if k != self.rank and any(self.near(boxes[self.rank, w], boxes[k, w]) for w in (0, 1))]
+        self.partners, self.boxes = partners, boxes
+        n = len(partners)
+        out_counts = np.asarray(self.source.rx_pack(p, boxes[partners]), dtype=np.int64).reshape(n, 2)
+        # counts: fixed shape, both ways
+        cs = [torch.from_numpy(out_counts[i].copy()).to(self.device) for i in range(n)]
+        cr = [torch.zeros(2, dtype=torch.int64, device=self.device) for _ in range(n)]
+        ops = []
+        for i, k in enumerate(partners):
+            ops.append(dist.P2POp(dist.isend, cs[i], k))
+            ops.append(dist.P2POp(dist.irecv, cr[i], k))
+        self._wait(ops)
+        self.messages += n
+        in_counts = np.array([c.cpu().numpy() for c in cr], dtype=np.int64).reshape(n, 2)
+        # payloads: [white message | yolk message], only where something travels
+        W = self.RECORD_WORDS
+        send = [torch.empty(2 + W * int(c.sum()), dtype=torch.int64, device=self.device) if c.sum() else None for c in out_counts]
+        recv = [torch.empty(2 + W * int(c.sum()), dtype=torch.int64, device=self.device) if c.sum() else None for c in in_counts]
+        ptr = np.zeros((n, 2), dtype=np.uint64)
+        for i, t in enumerate(send):
+            if t is not None:
+                ptr[i] = (t.data_ptr(), t.data_ptr() + 8 * (1 + W * int(out_counts[i, 0])))
+        if n:
+            self.source.rx_fetch(ptr)  # (complete when it returns: the sends may start)
+        self.host_syncs += 3 if n else 1
+        ops = []
+        for i, k in enumerate(partners):
+            if send[i] is not None:
+                ops.append(dist.P2POp(dist.isend, send[i], k))
+                self.messages += 1
+            if recv[i] is not None:
+                ops.append(dist.P2POp(dist.irecv, recv[i], k))
+        self._wait(ops)
+        rptr = np.zeros((n, 2), dtype=np.uint64)
+        for i, t in enumerate(recv):
+            if t is not None:
+                rptr[i] = (t.data_ptr(), t.data_ptr() + 8 * (1 + W * int(in_counts[i, 0])))
+        self._send, self._recv, self._counts_in = send, recv, in_counts
+        self.passes += 1
+        self.records += int(in_counts.sum())
+        self.host_seconds += time.perf_counter() - t0
+        return rptr, in_counts
+
+    def received(self, which):
+        """the ghost records of type `which` received in the last exchange: int64 words [m, 5] (view the first four columns
+        as float64 for x, y, inverse mass, radius; the fifth is the global key)"""
+        W, rows = self.RECORD_WORDS, []
+        for t, c in zip(self._recv, self._counts_in):
+            if t is None or c[which] == 0:
+                continue
+            words = t.cpu().numpy()
+            off = 0 if which == 0 else 1 + W * int(c[0])
+            assert int(words[off]) == int(c[which]), "message header and announced count differ"
+            rows.append(words[off + 1:off + 1 + W * int(c[which])].reshape(-1, W))
+        return np.concatenate(rows) if rows else np.zeros((0, W), dtype=np.int64)
+
+
 class ShardedSimulationHandler:
     """SimulationHandler spread over the ranks of a process group, one x-slab per rank.
 
     SPMD: every rank makes the same add / set_target_position / update calls with the same
     arguments; batch ids are global.  `make_handler` builds the local device handler (tests inject
     their own).  Results equal a single handler's bit for bit (tests/test_gpu_sharded.py).
+
+    set_solver_order("relaxed") switches every rank to relaxed order (the same call on every rank): step() then runs
+    every collision pass with a ghost halo between the ranks (HaloExchange) instead of handing batches over, and the
+    results equal ONE relaxed handler holding every batch, bit for bit (tests/test_gpu_sharded_relaxed.py).
     """
 
     STATE_FIELDS = 9
@@ -256,6 +391,10 @@ class ShardedSimulationHandler:
         self.exchange = BoundaryExchange(None, rank, self.world, lo, hi, group=group, halo_px=halo_px,
                                          interact_px=interact_px, bounds_fn=self._bounds, device=device)
         self.device = self.exchange.device if self.world > 1 else "cpu"
+        self._order = "exact"
+        self._keys_stale = True   # the global keys of relaxed order: rebuilt after adds and hand-overs
+        self.halo = HaloExchange(self.local, rank, self.world, group=group, device=self.device) if self.world > 1 else None
+        self._halo_passes = 0     # (world == 1 counts its passes here: there is no exchange)
 
     # ------------------------------------------------------------------ API
     def add(self, x, y, white_radius=50.0, yolk_radius=15.0):
@@ -269,7 +408,24 @@ class ShardedSimulationHandler:
             self.local_id[gid] = lid
             self.global_id[lid] = gid
         self._budget_stale = True  # summed over the ranks before the next step
+        self._keys_stale = True
         return gid
+
+    def set_solver_order(self, order, relaxation=None):
+        """"exact" (default) or "relaxed" with omega `relaxation` (None keeps the current value), on every rank alike.
+        Back in "exact" the handlers re-tile and the exact protocol hands islands over again."""
+        self.local.set_solver_order(order, relaxation)
+        self._order = order
+        self._budget_stale = True
+
+    def get_solver_order(self):
+        return self._order
+
+    def halo_counters(self):
+        """relaxed steps of this rank, summed over the run: collision passes, ghost records received, their bytes"""
+        if self.halo is None:
+            return dict(passes=self._halo_passes, records=0, bytes=0)
+        return dict(passes=self.halo.passes, records=self.halo.records, bytes=self.halo.bytes)
 
     def set_target_position(self, gid, x, y):
         if self.owner[gid] == self.rank:
@@ -304,7 +460,11 @@ class ShardedSimulationHandler:
         self._step_args = (delta, n_substeps, n_collision_steps)
         if self.world == 1:
             self.local.step(delta, n_substeps, n_collision_steps)
+            if self._order == "relaxed":
+                self._halo_passes += n_substeps * n_collision_steps
             return 0
+        if self._order == "relaxed":
+            return self._step_relaxed(delta, n_substeps, n_collision_steps)
         self._sync_budget()
         self.local.step_begin(delta, n_substeps, n_collision_steps)  # fixes this step's claims, launches the kernels
         self.exchange.post(claims_fixed=True)
@@ -357,6 +517,87 @@ class ShardedSimulationHandler:
         moved = self.rebalance()
         self.local.step(delta, n_substeps, n_collision_steps)
         self._note_committed()
+        return moved
+
+    # ------------------------------------------------------------ relaxed order
+    def _step_relaxed(self, delta, n_substeps, n_collision_steps):
+        """One relaxed `_step` on every rank: no budget sync, no claims, nothing handed over before it and nothing
+        re-run.  Every pass exchanges its halo; ONE all_reduce after the passes decides on all ranks together whether
+        the step is committed (a NaN or out-of-range cell anywhere fails it everywhere, nothing committed)."""
+        loc, torch, dist = self.local, self.torch, self.dist
+        self._sync_keys()
+        loc.rx_begin(delta, n_substeps, n_collision_steps)
+        try:
+            for sub in range(n_substeps):
+                loc.rx_substep(sub)
+                for c in range(n_collision_steps):
+                    p = sub * n_collision_steps + c
+                    pointers, counts = self.halo.exchange(p)
+                    loc.rx_run_pass(p, pointers, counts)
+            bad, _pairs, _records = loc.rx_check()
+        except BaseException:
+            loc.rx_end(False)
+            raise
+        flag = torch.tensor([1.0 if bad else 0.0], dtype=torch.float64, device=self.device)
+        dist.all_reduce(flag, op=dist.ReduceOp.MAX)
+        if flag.item() != 0.0:
+            loc.rx_end(False)
+            raise EggError("[ERROR] relaxed order: a position is NaN or its spatial-hash cell lies outside +-2^30 "
+                           "(on this rank or another): nothing was committed on any rank")
+        loc.rx_end(True)
+        return self._rebalance_relaxed()
+
+    def _sync_keys(self):
+        """global keys: a batch's particles start at the sum of the type's particle counts over
+        the batches OF ALL RANKS with a smaller id.  One all_gather of (gid, n_white, n_yolk) rows, only after a batch
+        was added or handed over."""
+        if not self._keys_stale:
+            return
+        rows = [[g] + list(self.local.get_n_particles(l)) for g, l in sorted(self.local_id.items())]
+        parts = self._all_gather_rows(np.array(rows, dtype=np.float64).reshape(-1, 3))
+        table = np.concatenate(parts).astype(np.int64)
+        table = table[np.argsort(table[:, 0], kind="stable")]
+        for which in (0, 1):
+            n = table[:, 1 + which]
+            self.local.rx_set_keys(which, table[:, 0], np.cumsum(n) - n, int(n.sum()))
+        self._keys_stale = False
+
+    def _rebalance_relaxed(self):
+        """After a committed relaxed step: a batch whose position lies more than halo_px outside its slab moves to the
+        slab that holds it (the device group's rule).  It only balances load: the halo makes every rank see what one
+        handler would, wherever a batch sits."""
+        torch, dist = self.torch, self.dist
+        lo, hi, halo = self.exchange.slab_lo, self.exchange.slab_hi, self.exchange.halo_px
+        rows = []
+        gids = sorted(self.local_id)
+        if gids:
+            xs, _ys = self.local.get_positions([self.local_id[g] for g in gids])
+            for g, x in zip(gids, xs):
+                if x < lo - halo or x >= hi + halo:
+                    dest = int(self.layout.owner_of([x])[0])
+                    if dest != self.rank:
+                        rows.append([self.rank, dest, g])
+        n = torch.tensor([float(len(rows))], dtype=torch.float64, device=self.device)
+        dist.all_reduce(n, op=dist.ReduceOp.SUM)
+        if n.item() == 0.0:
+            return 0
+        parts = self._all_gather_rows(np.array(rows, dtype=np.float64).reshape(-1, 3))
+        moves = {}
+        for part in parts:
+            for src, dest, g in part:
+                moves.setdefault((int(src), int(dest)), []).append(int(g))
+        # every rank walks the same ordered list of (source, destination) pairs: the earliest unfinished transfer never
+        # waits for a later one
+        for (src, dest), gs in sorted(moves.items()):
+            if self.rank == src:
+                self._send_batches(sorted(gs), dest)
+            elif self.rank == dest:
+                self._recv_batches(len(gs), src)
+            for g in gs:
+                self.owner[g] = dest
+        moved = sum(len(gs) for gs in moves.values())
+        self.migrations += moved
+        self._keys_stale = True
         return moved
 
     def _note_committed(self):
@@ -573,4 +814,5 @@ class ShardedSimulationHandler:
                     self.owner[g] = r + 1
             moved_total += n_moves
             self.migrations += n_moves
+            self._keys_stale = True
         raise SlabConflict("rank %d: batch hand-over did not settle" % self.rank)

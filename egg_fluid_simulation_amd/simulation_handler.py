@@ -607,8 +607,9 @@ class SimulationHandler(_HandlerSurface):
         """"exact" (default): the reference's sequential pair order, bit for bit.  "relaxed": every collision pass a
         Jacobi pass with constraint averaging, scaled by `relaxation` in (0, 2] (None keeps the current value) --
         plausible and deterministic, several times faster on large scenes, but not the reference's numbers
-        (DESIGN.md section 2.7).  A relaxed handle steps alone or inside a SimulationGroup
-        (SimulationGroup.set_solver_order): step_begin / step_end / get_claims raise EggError."""
+        (DESIGN.md section 2.7).  A relaxed handle steps alone, inside a SimulationGroup
+        (SimulationGroup.set_solver_order) or pass by pass under a ShardedSimulationHandler (the rx_* methods):
+        step_begin / step_end / get_claims raise EggError."""
         if order not in self._SOLVER_ORDERS:
             raise EggError("solver order must be 'exact' or 'relaxed', not %r" % (order,))
         if relaxation is not None:
@@ -618,3 +619,54 @@ class SimulationHandler(_HandlerSurface):
 
     def get_solver_order(self):
         return getattr(self, "_solver_order", "exact")
+
+    # ------------------------------------------------- relaxed order between processes (egg_rx_*, include/eggsim.h)
+    # One relaxed _step driven pass by pass; ShardedSimulationHandler carries boxes and ghost messages between the ranks.
+    # Boxes are int32 arrays [..., 5]: lo_x, lo_y, hi_x, hi_y (cells), empty flag.  Messages are given by ADDRESS (host
+    # memory or memory of this handle's device, e.g. torch.Tensor.data_ptr()); 0 means none.
+    def rx_set_keys(self, which, keys, bases, total):
+        """global key bases of the batches with keys `keys` (this handle's at least) and the type's total over all ranks"""
+        keys = np.ascontiguousarray(keys, dtype=np.int64)
+        bases = np.ascontiguousarray(bases, dtype=np.int64)
+        self._check(self._lib.egg_rx_set_keys(self._h, int(which), keys.shape[0], keys.ctypes.data, bases.ctypes.data, int(total)))
+
+    def rx_begin(self, delta=1 / 60, n_substeps=2, n_collision_steps=3):
+        self._check(self._lib.egg_rx_begin(self._h, float(delta), int(n_substeps), int(n_collision_steps)))
+
+    def rx_substep(self, sub):
+        self._check(self._lib.egg_rx_substep(self._h, int(sub)))
+
+    def rx_get_boxes(self, pass_index):
+        """[2, 5] int32: this handle's cell box per type at the start of the pass (waits for the device)"""
+        out = np.zeros((2, _ffi.RX_BOX_INTS), dtype=np.int32)
+        self._check(self._lib.egg_rx_get_boxes(self._h, int(pass_index), out.ctypes.data))
+        return out
+
+    def rx_pack(self, pass_index, boxes):
+        """boxes [n_dest, 2, 5] int32 -> counts [n_dest, 2]: records packed for every destination and type"""
+        boxes = np.ascontiguousarray(boxes, dtype=np.int32).reshape(-1, 2, _ffi.RX_BOX_INTS)
+        counts = np.zeros((boxes.shape[0], 2), dtype=np.int64)
+        self._check(self._lib.egg_rx_pack(self._h, int(pass_index), boxes.shape[0], boxes.ctypes.data, counts.ctypes.data))
+        return counts
+
+    def rx_fetch(self, pointers):
+        """pointers [n_dest, 2]: where the messages of the last rx_pack go (8 * (1 + 5 * count) bytes each; 0 skips);
+        they are complete when this returns"""
+        ptrs = np.ascontiguousarray(pointers, dtype=np.uint64).reshape(-1, 2)
+        self._check(self._lib.egg_rx_fetch(self._h, ptrs.shape[0], ptrs.ctypes.data))
+
+    def rx_run_pass(self, pass_index, pointers, counts):
+        """the pass over the local particles + the ghosts of the received messages (pointers / counts [n_src, 2]).  The
+        messages must be complete, and host buffers must live until the next rx_get_boxes / rx_check / rx_end returns."""
+        ptrs = np.ascontiguousarray(pointers, dtype=np.uint64).reshape(-1, 2)
+        counts = np.ascontiguousarray(counts, dtype=np.int64).reshape(-1, 2)
+        self._check(self._lib.egg_rx_run_pass(self._h, int(pass_index), ptrs.shape[0], ptrs.ctypes.data, counts.ctypes.data))
+
+    def rx_check(self):
+        """(bad, [pairs white, pairs yolk], ghost records received) of the step in flight, before anything is committed"""
+        bad, pairs, rec = C.c_int32(), (C.c_int64 * 2)(), C.c_int64()
+        self._check(self._lib.egg_rx_check(self._h, C.byref(bad), C.byref(pairs), C.byref(rec)))
+        return bool(bad.value), list(pairs), rec.value
+
+    def rx_end(self, commit=True):
+        self._check(self._lib.egg_rx_end(self._h, 1 if commit else 0))

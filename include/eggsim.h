@@ -317,8 +317,8 @@ enum {
     EGG_OPT_LEVEL_WALK,             /* packed pipeline, the pass that gives every pair its dependency level: 0 (default) by regime -- out of order for dense islands (> 256 particles) while the groups are no more than the chip's SIMDs, in order otherwise --, 1 always in order, 2 out of order everywhere */
     EGG_OPT_SOLVER_ORDER,           /* 0 (default): exact -- the reference's sequential Gauss-Seidel pair order, bit for bit; 1: relaxed --
                                      * every collision pass a Jacobi pass with constraint averaging: plausible,
-                                     * deterministic, not the reference's numbers.  A relaxed handle steps only by itself or inside an
-                                     * egg_group (egg_group_set_solver_order): egg_step_begin, egg_step_end and egg_get_claims_many
+                                     * deterministic, not the reference's numbers.  A relaxed handle steps by itself, inside an
+                                     * egg_group (egg_group_set_solver_order) or pass by pass (egg_rx_*): egg_step_begin, egg_step_end and egg_get_claims_many
                                      * return EGG_ERR_UNSUPPORTED, egg_prepare_step does nothing.  Refused while a step is in flight. */
     EGG_OPT_RELAXATION              /* omega of the relaxed pass, in (0, 2] (default EGG_RELAXATION_DEFAULT).  Refused while a step is in flight. */
 };
@@ -409,6 +409,60 @@ int egg_group_render(egg_group *g, const egg_render_params *p, float *rgba);
 /* the density canvas of `which` as the last egg_group_render left it (egg_render_canvas) */
 int egg_group_render_canvas(egg_group *g, int which, float *rgba, int64_t cap_pixels, int32_t *w, int32_t *hgt, double *x0,
                             double *y0);
+
+/* ---- relaxed order over several PROCESSES (csrc/eggsim_host_relaxed_wire.hip) -------------
+ * One relaxed _step of ONE handle, driven pass by pass by a host that moves the ghost halo itself (one process per GPU:
+ * egg_fluid_simulation_amd/sharding.py over torch.distributed / RCCL).  The handle knows nothing about the other
+ * ranks: cell boxes go out and come in as egg_rx_box, ghost particles as messages.  When every rank drives its handle
+ * through the sequence below and delivers every message, the ranks' particles end up with the bits ONE relaxed handle
+ * holding all batches gives.  With S sub-steps and C collision passes, pass p = sub * C + c:
+ *
+ *   egg_rx_set_keys (per type, when the membership of ANY rank changed)
+ *   egg_rx_begin
+ *   for sub in 0 .. S-1:  egg_rx_substep(sub)
+ *       for c in 0 .. C-1:  egg_rx_get_boxes(p)  ->  the ranks exchange boxes  ->  egg_rx_pack(p) + egg_rx_fetch
+ *                           ->  the messages travel  ->  egg_rx_run_pass(p)
+ *   egg_rx_check  ->  the ranks agree whether ANY of them flagged a bad position  ->  egg_rx_end(commit)
+ *
+ * A MESSAGE is one contiguous run of 64-bit words: word 0 the record count m, then m records of 5 words (40 bytes):
+ * x, y, inverse mass, radius (doubles), global key (int64) -- 8 * (1 + 5 m) bytes.
+ * All device work goes to the handle's own (non-blocking) streams.  A buffer the caller hands in is read from the
+ * moment of the call: its contents must be complete (the caller has waited for its receive and synchronised the stream
+ * that filled it), and a buffer in host memory must stay valid until the next egg_rx_get_boxes / egg_rx_check /
+ * egg_rx_end of the handle returns.  A buffer a call fills is complete when the call returns.  Buffers may be host
+ * memory or memory of the handle's device (hipMemcpyDefault), as for egg_export_batch.
+ * Between egg_rx_begin and egg_rx_end the state-mutating entry points are refused.  The handle must be in relaxed order;
+ * egg_step, egg_step_begin, egg_step_end and egg_get_claims_many behave as they do on any relaxed handle. */
+typedef struct {
+    int32_t lo_x, lo_y, hi_x, hi_y; /* spatial-hash cells, inclusive */
+    int32_t empty;                  /* 1: no particle of the type on this handle (the other fields are 0) */
+} egg_rx_box;
+/* Global keys of type `which`: keys[i] is the key (egg_add_many_keyed / egg_batch_info.key) of a batch, bases[i] the number
+ * of particles of the type in all batches OF ALL RANKS with a smaller key, total the type's particle count over all
+ * ranks (at most 2^29: EGG_ERR_UNSUPPORTED).  Every batch of this handle must be listed; others may be.  The device
+ * copy is rebuilt at the next egg_rx_begin only when the values or the handle's batches changed. */
+int egg_rx_set_keys(egg_handle *h, int which, int64_t n, const int64_t *keys, const int64_t *bases, int64_t total);
+/* reserves room for the local particles + (total - local) ghosts per type, clears the status words; launches nothing
+ * that writes the uncommitted state */
+int egg_rx_begin(egg_handle *h, double delta, int32_t n_substeps, int32_t n_collision_steps);
+/* pre-solve + follow of sub-step `sub` (after the post-solve of the one before); records the cell box of what it wrote */
+int egg_rx_substep(egg_handle *h, int32_t sub);
+/* the cell boxes of this handle's positions at the start of pass `pass`, per type (waits for the streams) */
+int egg_rx_get_boxes(egg_handle *h, int32_t pass, egg_rx_box boxes[2]);
+/* packs, for each of n_dest destinations, the local particles within one cell of its box: boxes[2 * k + type];
+ * counts[2 * k + type] = records in the message for destination k (waits for the streams) */
+int egg_rx_pack(egg_handle *h, int32_t pass, int32_t n_dest, const egg_rx_box *boxes, int64_t *counts);
+/* copies the messages of the last egg_rx_pack out: out[2 * k + type] receives 8 * (1 + 5 * count) bytes, NULL skips it */
+int egg_rx_fetch(egg_handle *h, int32_t n_dest, void *const *out);
+/* the collision pass over the local particles + the ghosts of n_src received messages: msgs[2 * k + type] with
+ * counts[2 * k + type] records (NULL or 0: none).  Writes local positions only and records the next pass's box. */
+int egg_rx_run_pass(egg_handle *h, int32_t pass, int32_t n_src, const void *const *msgs, const int64_t *counts);
+/* after the last pass, before anything is committed: *bad = 1 when a position of this handle is NaN or its cell lies
+ * outside +-2^30; pairs[type] = pairs this handle counted; *ghost_records = ghost records it received in the step */
+int egg_rx_check(egg_handle *h, int32_t *bad, int64_t pairs[2], int64_t *ghost_records);
+/* commit = 1 (after egg_rx_check, refused when it reported bad): post-solve of the last sub-step, the step counts as one
+ * relaxed _step.  commit = 0, at any point after egg_rx_begin: the state is as before egg_rx_begin. */
+int egg_rx_end(egg_handle *h, int32_t commit);
 
 #ifdef __cplusplus
 }
