@@ -104,6 +104,10 @@ RX_BOX_INTS = 5        # int32 fields of egg_rx_box
 RX_RECORD_WORDS = 5    # 64-bit words of a ghost record: x, y, inverse mass, radius (doubles), global key (int64)
 RX_RECORD_BYTES = 40
 
+# the draw record of a particle (egg_draw_pack, egg_draw_source_*): a message is double[7][n] in this field order
+DRAW_FIELDS = ("x", "y", "last_x", "last_y", "vx", "vy", "radius")
+DRAW_RECORD_BYTES = 56
+
 PK_KINDS = ["egg_pk_begin_kernel", "egg_pk_mid_kernel", "egg_pk_lists_fresh_kernel", "egg_pk_lists_stale_kernel",
             "egg_pk_levels_kernel", "egg_pk_sort_kernel", "egg_pk_exec_kernel", "egg_pk_end_kernel", "egg_pk_reduce_kernel",
             "egg_pk_pass_kernel"]
@@ -200,6 +204,15 @@ _SIGNATURES = {
     "egg_rx_run_pass": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "egg_rx_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64 * 2), C.POINTER(C.c_int64)]),
     "egg_rx_end": (C.c_int, [C.c_void_p, C.c_int32]),
+    "egg_draw_pack": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),
+    "egg_draw_source_layout": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "egg_draw_source_place": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "egg_draw_source_render": (C.c_int, [C.c_void_p, C.POINTER(EggRenderParams), C.POINTER(EggRenderConfig), C.c_int32, C.c_int32,
+                                         C.c_int32, C.c_double, C.c_void_p]),
+    "egg_draw_source_render_canvas": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                                C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "egg_draw_source_environment": (C.c_int, [C.c_void_p, C.c_int, C.c_int32, C.POINTER(EggEnvironment)]),
+    "egg_draw_source_download": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64]),
 }
 
 EXPORTED_SYMBOLS = sorted(_SIGNATURES)

@@ -370,3 +370,11 @@ struct EggGatherArgs {
     int32_t n, n_runs, n_fields;
     int32_t total;             // particles the shadow arrays hold
 };
+
+// egg_draw_pack_kernel (eggsim_draw_pack.hip): the seven draw fields of one handle's particles of a type into ONE message,
+// field after field (dst[f * n + i]), particles in the handle's own order.
+struct EggDrawPackArgs {
+    const double *src[EGG_GATHER_FIELDS];
+    double *dst;  // [EGG_GATHER_FIELDS * n]
+    int32_t n;
+};

@@ -11,6 +11,7 @@
 //   eggsim_host_relaxed_group.hip  the same step over the handles of a device group, with per-pass ghost halos
 //   eggsim_host_relaxed_wire.hip   the same step driven pass by pass through the C ABI (egg_rx_*): one handle per process
 //   eggsim_host_render_group.hip   draw / environment / download of a device group: gather to one device (eggsim_render_group.hip)
+//   eggsim_host_draw_source.hip    the same for a scene sharded over processes: egg_draw_pack on every rank, egg_draw_source_* on one
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -80,6 +81,7 @@ extern "C" __global__ void egg_rx_unpack_kernel(EggRxUnpackArgs U);
 extern "C" __global__ void egg_rx_wire_pack_kernel(EggRxWirePackArgs P);
 extern "C" __global__ void egg_rx_wire_unpack_kernel(EggRxWireUnpackArgs U);
 extern "C" __global__ void egg_group_gather_kernel(EggGatherArgs A);
+extern "C" __global__ void egg_draw_pack_kernel(EggDrawPackArgs A);
 extern "C" __global__ void egg_render_count_kernel(EggRenderArgs A);
 extern "C" __global__ void egg_render_fill_kernel(EggRenderArgs A);
 extern "C" __global__ void egg_render_scan_kernel(EggRenderArgs A);
@@ -348,6 +350,7 @@ inline int32_t *d_disp(System &s) { return s.d_out.p + 2 * kStatInts + 4 * s.ato
 }  // namespace egghost
 namespace egghost {
 struct WireStep;  // a relaxed step in flight between egg_rx_begin and egg_rx_end (eggsim_host_relaxed_wire.hip)
+struct DrawSource;  // particles placed by egg_draw_source_place, their canvases and scratch (eggsim_host_draw_source.hip)
 }
 using namespace egghost;
 
@@ -382,10 +385,16 @@ struct egg_handle {
     hipDeviceProp_t prop{};
     size_t lds_limit = 64 * 1024;  // dynamic LDS a step-kernel workgroup may use
     bool in_flight = false;        // egg_step_begin without its egg_step_end
+    // x / y [cur ^ 1] as egg_step_begin found them, per type: the positions at the start of the last committed step
+    // (last_x / last_y of draw(), L:1795-1815) live in the buffer the launched step writes; a discard puts them back
+    DevBuf<double> flight_last[2][2];
+    hipEvent_t flight_saved = nullptr;
     double flight_delta = 0;
     int flight_s = 0, flight_c = 0;
     bool wire_active = false;      // egg_rx_begin without its egg_rx_end
     std::shared_ptr<egghost::WireStep> wire;  // global keys and the step in flight, allocated by the first egg_rx_* call
+    std::shared_ptr<egghost::DrawSource> draw_source;  // allocated by the first egg_draw_source_* call
+    DevBuf<double> draw_pack;      // egg_draw_pack into host memory: the message before its one copy out
     // headless renderer (eggsim_render.hip)
     struct Render {
         egg_render_config cfg[2];
@@ -514,6 +523,21 @@ struct GroupKeys {
 };
 void group_keys(egg_handle *const *hs, int n, int w, GroupKeys &K);
 int relaxed_group_step(egg_handle *const *hs, int n, double delta, int S, int C, int64_t halo_records[1], std::string *error);
+
+// eggsim_host_render_group.hip: what the draw of a device group and the draw of a scene sharded over processes
+// (eggsim_host_draw_source.hip) share.  Shadow arrays hold x, y, last_x, last_y, vx, vy, radius (kDrawFields) of ALL
+// particles of a type in global-key order on the render device.
+struct DrawShadow {
+    DevBuf<double> f[EGG_GATHER_FIELDS];
+    DevBuf<int32_t> atom_offset;
+    DevBuf<unsigned long long> d_env;
+};
+extern const int kDrawFields[EGG_GATHER_FIELDS];
+const double *draw_field_of(System &s, int field);
+void gather_table(const std::vector<int32_t> &run_src, const std::vector<int32_t> &run_dst, int64_t n, std::vector<int32_t> &tab);
+int launch_gather(egg_handle *rh, hipStream_t st, const double *const *src, DrawShadow &sh, int n_fields, const int32_t *table,
+                  int32_t n_runs, int64_t n, int64_t total);
+void shadow_source(DrawShadow &sh, int64_t total, hipStream_t env_stream, RenderSource::Type &S);
 
 }  // namespace egghost
 

@@ -167,6 +167,7 @@ void egg_destroy(egg_handle *h) {
         }
         if (s.stream) (void)hipStreamDestroy(s.stream);
     }
+    if (h->flight_saved) (void)hipEventDestroy(h->flight_saved);
     delete h;
 }
 
@@ -411,6 +412,20 @@ int egg_step_begin(egg_handle *h, double delta, int32_t n_substeps, int32_t n_co
     if (h->opt_solver_order == EGG_SOLVER_RELAXED) return fail(h, EGG_ERR_UNSUPPORTED, "egg_step_begin: relaxed order: single-device steps only");
     if (h->in_flight) return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_step_begin: a step is already in flight");
     (void)hipSetDevice(h->device);
+    // keep last_x / last_y for a discard: two copies per type on the white stream, which the yolk stream then waits for
+    // (a launch may go to either); 32 B of traffic per particle beside the step's several hundred
+    if (!h->flight_saved) HIP_TRY(h, hipEventCreateWithFlags(&h->flight_saved, hipEventDisableTiming));
+    for (int w = 0; w < 2; ++w) {
+        System &s = h->sys[w];
+        if (s.n == 0) continue;
+        double *last[2] = {s.x[s.cur ^ 1].p, s.y[s.cur ^ 1].p};
+        for (int a = 0; a < 2; ++a) {
+            HIP_TRY(h, h->flight_last[w][a].reserve((size_t)s.n, false, h->sys[0].stream));
+            HIP_TRY(h, hipMemcpyAsync(h->flight_last[w][a].p, last[a], (size_t)s.n * 8, hipMemcpyDeviceToDevice, h->sys[0].stream));
+        }
+    }
+    HIP_TRY(h, hipEventRecord(h->flight_saved, h->sys[0].stream));
+    HIP_TRY(h, hipStreamWaitEvent(h->sys[1].stream, h->flight_saved, 0));
     int rc = do_step(h, delta, n_substeps, n_collision_steps, kBegin);
     if (rc == EGG_OK) {
         h->in_flight = true;
@@ -428,12 +443,21 @@ int egg_step_end(egg_handle *h, int32_t commit) {
     (void)hipSetDevice(h->device);
     h->in_flight = false;
     if (!commit) {
-        // discard: the launches wrote the inactive buffers only; wait for them and forget
+        // discard: the launches wrote the inactive buffers only; wait for them, put the last positions back (they
+        // live in those buffers) and forget
         for (int w = 0; w < 2; ++w) {
             HIP_TRY(h, hipStreamSynchronize(h->sys[w].stream));
             h->sys[w].aabb_on_device = false;
             h->sys[w].out_copied = false;
         }
+        for (int w = 0; w < 2; ++w) {
+            System &s = h->sys[w];
+            if (s.n == 0) continue;
+            double *last[2] = {s.x[s.cur ^ 1].p, s.y[s.cur ^ 1].p};
+            for (int a = 0; a < 2; ++a)
+                HIP_TRY(h, hipMemcpyAsync(last[a], h->flight_last[w][a].p, (size_t)s.n * 8, hipMemcpyDeviceToDevice, h->sys[0].stream));
+        }
+        HIP_TRY(h, hipStreamSynchronize(h->sys[0].stream));
         return EGG_OK;
     }
     return do_step(h, h->flight_delta, h->flight_s, h->flight_c, kEnd);

@@ -21,9 +21,7 @@ namespace egghost {
 struct GroupDraw {
     egg_handle::Render R;  // canvases with their grow-only sizes, screen, scratch: the group's, not handle 0's
     struct Type {
-        DevBuf<double> f[EGG_GATHER_FIELDS];
-        DevBuf<int32_t> atom_offset;
-        DevBuf<unsigned long long> d_env;
+        DrawShadow sh;  // the shadow arrays, atom_offset, reduction scratch
         GroupKeys keys;
         std::vector<uint64_t> sig;              // every handle's atoms_gen when the tables below were built
         std::vector<DevBuf<int32_t>> tables;    // per source handle: run_src [runs + 1], run_dst [runs], block_run [blocks]
@@ -36,6 +34,78 @@ struct GroupDraw {
             if (e) (void)hipEventDestroy(e);
     }
 };
+
+// ---- shared with the draw of a scene sharded over processes (eggsim_host_draw_source.hip)
+
+const double *draw_field_of(System &s, int field) {
+    switch (field) {
+        case EGG_FIELD_X: return s.x[s.cur].p;
+        case EGG_FIELD_Y: return s.y[s.cur].p;
+        case EGG_FIELD_VX: return s.vx[s.cur].p;
+        case EGG_FIELD_VY: return s.vy[s.cur].p;
+        case EGG_FIELD_LAST_X: return s.x[s.cur ^ 1].p;  // positions at the start of the most recent _step (L:1795-1815)
+        case EGG_FIELD_LAST_Y: return s.y[s.cur ^ 1].p;
+        case EGG_FIELD_RADIUS: return s.radius.p;
+        case EGG_FIELD_INV_MASS: return s.inv_mass.p;
+        case EGG_FIELD_MASS_T: return s.mass_t.p;
+        default: return nullptr;
+    }
+}
+
+const int kDrawFields[EGG_GATHER_FIELDS] = {EGG_FIELD_X,  EGG_FIELD_Y,  EGG_FIELD_LAST_X, EGG_FIELD_LAST_Y,
+                                            EGG_FIELD_VX, EGG_FIELD_VY, EGG_FIELD_RADIUS};
+
+// run_src [runs + 1] (the last entry is n), run_dst [runs], block_run [blocks]: what egg_group_gather_kernel reads
+void gather_table(const std::vector<int32_t> &run_src, const std::vector<int32_t> &run_dst, int64_t n, std::vector<int32_t> &tab) {
+    const size_t nr = run_src.size(), nb = ((size_t)n + EGG_GATHER_BLOCK - 1) / EGG_GATHER_BLOCK;
+    tab = run_src;
+    tab.push_back((int32_t)n);
+    tab.insert(tab.end(), run_dst.begin(), run_dst.end());
+    size_t r = 0;
+    for (size_t b = 0; b < nb; ++b) {
+        const int32_t first = (int32_t)(b * EGG_GATHER_BLOCK);
+        while (r + 1 < nr && first >= run_src[r + 1]) ++r;
+        tab.push_back((int32_t)r);
+    }
+}
+
+// one launch of egg_group_gather_kernel on `st`: n particles of src[0 .. n_fields) into their places in the shadow arrays
+int launch_gather(egg_handle *rh, hipStream_t st, const double *const *src, DrawShadow &sh, int n_fields, const int32_t *table,
+                  int32_t n_runs, int64_t n, int64_t total) {
+    EggGatherArgs A;
+    memset(&A, 0, sizeof A);
+    for (int f = 0; f < n_fields; ++f) {
+        A.src[f] = src[f];
+        A.dst[f] = sh.f[f].p;
+    }
+    A.run_src = table;
+    A.run_dst = A.run_src + n_runs + 1;
+    A.block_run = A.run_dst + n_runs;
+    A.n = (int32_t)n;
+    A.n_runs = n_runs;
+    A.n_fields = n_fields;
+    A.total = (int32_t)total;
+    hipLaunchKernelGGL(egg_group_gather_kernel, dim3((unsigned)(((size_t)n + EGG_GATHER_BLOCK - 1) / EGG_GATHER_BLOCK)),
+                       dim3(EGG_GATHER_BLOCK), 0, st, A);
+    HIP_TRY(rh, hipGetLastError());
+    rh->stats.kernel_launches++;
+    return EGG_OK;
+}
+
+// the shadow arrays as the renderer's source of one type (the colours are the caller's)
+void shadow_source(DrawShadow &sh, int64_t total, hipStream_t env_stream, RenderSource::Type &S) {
+    S.x = sh.f[0].p;
+    S.y = sh.f[1].p;
+    S.last_x = sh.f[2].p;
+    S.last_y = sh.f[3].p;
+    S.vx = sh.f[4].p;
+    S.vy = sh.f[5].p;
+    S.radius = sh.f[6].p;
+    S.atom_offset = sh.atom_offset.p;
+    S.n = total;
+    S.env_stream = env_stream;
+    S.d_env = &sh.d_env;
+}
 
 namespace {
 
@@ -53,24 +123,6 @@ int device_fail(const GroupView &V, int k, std::string *error, int rc) {
     } while (0)
 
 #define GD_HIP(k, expr) GD_TRY(k, [&]() -> int { HIP_TRY(V.hs[k], (expr)); return EGG_OK; }())
-
-const double *field_of(System &s, int field) {
-    switch (field) {
-        case EGG_FIELD_X: return s.x[s.cur].p;
-        case EGG_FIELD_Y: return s.y[s.cur].p;
-        case EGG_FIELD_VX: return s.vx[s.cur].p;
-        case EGG_FIELD_VY: return s.vy[s.cur].p;
-        case EGG_FIELD_LAST_X: return s.x[s.cur ^ 1].p;  // positions at the start of the most recent _step (L:1795-1815)
-        case EGG_FIELD_LAST_Y: return s.y[s.cur ^ 1].p;
-        case EGG_FIELD_RADIUS: return s.radius.p;
-        case EGG_FIELD_INV_MASS: return s.inv_mass.p;
-        case EGG_FIELD_MASS_T: return s.mass_t.p;
-        default: return nullptr;
-    }
-}
-
-const int kDrawFields[EGG_GATHER_FIELDS] = {EGG_FIELD_X,  EGG_FIELD_Y,  EGG_FIELD_LAST_X, EGG_FIELD_LAST_Y,
-                                            EGG_FIELD_VX, EGG_FIELD_VY, EGG_FIELD_RADIUS};
 
 int refuse_in_flight(const GroupView &V, const char *name, std::string *error) {
     for (int k = 0; k < V.n; ++k)
@@ -107,8 +159,8 @@ int update_tables(GroupDraw *D, const GroupView &V, int w, std::string *error) {
     std::vector<int32_t> off(na + 1);
     for (size_t b = 0; b < na; ++b) off[b] = (int32_t)T.keys.base[b];
     off[na] = (int32_t)T.keys.total;
-    GD_HIP(0, T.atom_offset.reserve(na + 1, false, st));
-    GD_HIP(0, hipMemcpyAsync(T.atom_offset.p, off.data(), (na + 1) * 4, hipMemcpyHostToDevice, st));
+    GD_HIP(0, T.sh.atom_offset.reserve(na + 1, false, st));
+    GD_HIP(0, hipMemcpyAsync(T.sh.atom_offset.p, off.data(), (na + 1) * 4, hipMemcpyHostToDevice, st));
     std::vector<std::vector<int32_t>> host((size_t)V.n);
     for (int k = 0; k < V.n; ++k) {
         egg_handle *h = V.hs[k];
@@ -124,18 +176,9 @@ int update_tables(GroupDraw *D, const GroupView &V, int w, std::string *error) {
             }
             next_dst = base + a.count;
         }
-        const size_t nr = run_src.size(), nb = ((size_t)s.n + EGG_GATHER_BLOCK - 1) / EGG_GATHER_BLOCK;
-        run_src.push_back((int32_t)s.n);
         std::vector<int32_t> &tab = host[(size_t)k];
-        tab = run_src;
-        tab.insert(tab.end(), run_dst.begin(), run_dst.end());
-        size_t r = 0;
-        for (size_t b = 0; b < nb; ++b) {
-            const int32_t first = (int32_t)(b * EGG_GATHER_BLOCK);
-            while (r + 1 < nr && first >= run_src[r + 1]) ++r;
-            tab.push_back((int32_t)r);
-        }
-        T.n_runs[(size_t)k] = (int32_t)nr;
+        gather_table(run_src, run_dst, s.n, tab);
+        T.n_runs[(size_t)k] = (int32_t)run_src.size();
         GD_HIP(0, T.tables[(size_t)k].reserve(tab.size(), false, st));
         GD_HIP(0, hipMemcpyAsync(T.tables[(size_t)k].p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, st));
     }
@@ -161,7 +204,7 @@ int gather(GroupDraw *D, const GroupView &V, int w, const int *fields, int n_fie
     const size_t total = (size_t)T.keys.total;
     if (total == 0) return EGG_OK;
     (void)hipSetDevice(rh->device);
-    for (int f = 0; f < n_fields; ++f) GD_HIP(0, T.f[f].reserve(total, false, st));
+    for (int f = 0; f < n_fields; ++f) GD_HIP(0, T.sh.f[f].reserve(total, false, st));
     if (D->ev.size() < 2 * (size_t)V.n) D->ev.resize(2 * (size_t)V.n, nullptr);
     for (int k = 0; k < V.n; ++k) {
         egg_handle *h = V.hs[k];
@@ -175,41 +218,16 @@ int gather(GroupDraw *D, const GroupView &V, int w, const int *fields, int n_fie
         }
         (void)hipSetDevice(rh->device);
         for (int q = 0; q < 2; ++q) GD_HIP(0, hipStreamWaitEvent(st, D->ev[2 * (size_t)k + q], 0));
-        const size_t nr = (size_t)T.n_runs[(size_t)k];
-        EggGatherArgs A;
-        memset(&A, 0, sizeof A);
-        for (int f = 0; f < n_fields; ++f) {
-            A.src[f] = field_of(s, fields[f]);
-            A.dst[f] = T.f[f].p;
-        }
-        A.run_src = T.tables[(size_t)k].p;
-        A.run_dst = A.run_src + nr + 1;
-        A.block_run = A.run_dst + nr;
-        A.n = (int32_t)s.n;
-        A.n_runs = (int32_t)nr;
-        A.n_fields = n_fields;
-        A.total = (int32_t)total;
-        hipLaunchKernelGGL(egg_group_gather_kernel, dim3((unsigned)(((size_t)s.n + EGG_GATHER_BLOCK - 1) / EGG_GATHER_BLOCK)),
-                           dim3(EGG_GATHER_BLOCK), 0, st, A);
-        GD_HIP(0, hipGetLastError());
-        rh->stats.kernel_launches++;
+        const double *src[EGG_GATHER_FIELDS] = {};
+        for (int f = 0; f < n_fields; ++f) src[f] = draw_field_of(s, fields[f]);
+        GD_TRY(0, launch_gather(rh, st, src, T.sh, n_fields, T.tables[(size_t)k].p, T.n_runs[(size_t)k], s.n, (int64_t)total));
     }
     return EGG_OK;
 }
 
 void fill_type(GroupDraw *D, const GroupView &V, int w, RenderSource::Type &S, bool colors) {
     GroupDraw::Type &T = D->t[w];
-    S.x = T.f[0].p;
-    S.y = T.f[1].p;
-    S.last_x = T.f[2].p;
-    S.last_y = T.f[3].p;
-    S.vx = T.f[4].p;
-    S.vy = T.f[5].p;
-    S.radius = T.f[6].p;
-    S.atom_offset = T.atom_offset.p;
-    S.n = T.keys.total;
-    S.env_stream = V.hs[0]->sys[0].stream;
-    S.d_env = &T.d_env;
+    shadow_source(T.sh, T.keys.total, V.hs[0]->sys[0].stream, S);
     if (!colors) return;
     const size_t na = T.keys.sizes.size();
     S.atom_color.assign(4 * na, 1.0f);
@@ -294,7 +312,7 @@ int group_draw_download(GroupDraw *D, const GroupView &V, int which, int field, 
     }
     (void)hipSetDevice(rh->device);
     hipStream_t st = rh->sys[0].stream;
-    GD_HIP(0, hipMemcpyAsync(dst, T.f[0].p, (size_t)total * 8, hipMemcpyDeviceToHost, st));
+    GD_HIP(0, hipMemcpyAsync(dst, T.sh.f[0].p, (size_t)total * 8, hipMemcpyDeviceToHost, st));
     GD_HIP(0, hipStreamSynchronize(st));
     return EGG_OK;
 }

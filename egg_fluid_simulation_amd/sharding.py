@@ -37,13 +37,21 @@ own particles plus read-only ghost copies of the other ranks' particles near its
 boxes (one all_gather per pass) and the 40-byte ghost records (point to point, only between ranks whose boxes are
 within one cell of each other); nothing is handed over before a step, no step is re-run, and the results equal ONE
 relaxed handler holding every batch, bit for bit.
+
+draw(), the environment and the particle download depend on particle ORDER (the screen blend and the serial centroid
+sums), so they gather to one render rank ("Several processes"): per type every other rank sends
+ONE message -- the seven draw fields of its particles, packed by egg_draw_pack -- and the render rank places the
+messages in global-key order (egg_draw_source_*) and runs the single handle's renderer over them, unchanged.
 """
+import copy
 import math
 import time
+import warnings
 
 import numpy as np
 
-from .simulation_handler import EggError
+from . import _ffi
+from .simulation_handler import EggError, EggWarning, _HandlerSurface, _assert_types, _is_nan
 
 
 class SlabConflict(RuntimeError):
@@ -356,12 +364,31 @@ class HaloExchange:
         return np.concatenate(rows) if rows else np.zeros((0, W), dtype=np.int64)
 
 
-class ShardedSimulationHandler:
-    """SimulationHandler spread over the ranks of a process group, one x-slab per rank.
+class ShardedSimulationHandler(_HandlerSurface):
+    """The reference's `SimulationHandler` class spread over the ranks of a process group, one x-slab per rank: every
+    public method of the class with the signatures, argument checks, warnings and error texts of SimulationHandler
+    (shared code: _HandlerSurface).
 
-    SPMD: every rank makes the same add / set_target_position / update calls with the same
-    arguments; batch ids are global.  `make_handler` builds the local device handler (tests inject
-    their own).  Results equal a single handler's bit for bit (tests/test_gpu_sharded.py).
+    SPMD: every rank makes the same calls with the same arguments; batch ids are global.  `make_handler` builds the
+    local device handler (tests inject their own).  Whatever it returns or draws equals, bit for bit, what ONE
+    SimulationHandler holding every batch, added in the same order, returns or draws (tests/test_gpu_sharded.py,
+    tests/test_gpu_sharded_draw.py) -- in exact and in relaxed order, before and after hand-overs and removes.
+
+    State that is a function of the call sequence lives on EVERY rank, keyed by global id: configs, render configs and
+    switches, per-batch colours with the reference's aliasing (a batch added without a colour shares the config's
+    colour table, L:49-50, L:349), targets, radii, particle counts, the id list.  add / remove / set_* / get_n_particles /
+    list_ids / get_target_position need no communication beyond the count table; get_position is one broadcast from
+    the owner.
+
+    add, remove and set_target_position reach the device on the OWNER only.  If its handle refuses the call (a step left
+    open on that rank by hand: nothing in this class does that), the owner raises with its tables unchanged while the
+    other ranks have applied the call: the ranks then disagree, and the object is to be discarded.  Argument errors are
+    raised on every rank before anything changes.
+
+    draw(), get_environment(), download(), download_instance_data() are COLLECTIVE (every rank calls them) and ANSWER
+    ON THE RENDER RANK (`root`, rank 0 by default): the image / dict / array there, None on the other ranks;
+    render_canvas() answers on the render rank without communication.  A refusal on any rank (a step in flight, a limit
+    of DESIGN.md section 7 on the render rank) raises EggError on EVERY rank.
 
     set_solver_order("relaxed") switches every rank to relaxed order (the same call on every rank): step() then runs
     every collision pass with a ghost halo between the ranks (HaloExchange) instead of handing batches over, and the
@@ -370,11 +397,15 @@ class ShardedSimulationHandler:
 
     STATE_FIELDS = 9
 
-    def __init__(self, layout, rank, group, make_handler, halo_px=64.0, interact_px=(8.0, 12.0), device=None):
+    def __init__(self, layout, rank, group, make_handler, halo_px=64.0, interact_px=(8.0, 12.0), device=None, root=0):
         import torch
         self.torch, self.dist = torch, group
         self.layout, self.rank, self.world = layout, int(rank), layout.world
+        self.root = int(root)     # the render rank
+        if not 0 <= self.root < self.world:
+            raise ValueError("root must be a rank of the layout")
         self.local = make_handler()
+        self._lib = getattr(self.local, "_lib", None)
         self.owner = {}       # global id -> rank
         self.local_id = {}    # global id -> id in self.local (batches this rank owns)
         self.global_id = {}   # local id -> global id
@@ -384,32 +415,171 @@ class ShardedSimulationHandler:
         self.bytes_handed_over = 0
         self._committed_visits = [0, 0]  # most pairs one pass of the last committed step visited, per type
         self._elapsed = 0.0
-        self.interpolation_alpha = 0.0
+        self._alpha = 0.0
+        self._n_steps = 0         # committed _steps: nothing is drawn before the first (L:1997-1999)
         self._budget_stale = True
         self._step_args = (1 / 60, 2, 3)
         lo, hi = layout.bounds(rank)
         self.exchange = BoundaryExchange(None, rank, self.world, lo, hi, group=group, halo_px=halo_px,
                                          interact_px=interact_px, bounds_fn=self._bounds, device=device)
         self.device = self.exchange.device if self.world > 1 else "cpu"
+        self._on_gpu = str(self.device).startswith("cuda")
         self._order = "exact"
-        self._keys_stale = True   # the global keys of relaxed order: rebuilt after adds and hand-overs
+        self._keys_stale = True   # the global keys of relaxed order: rebuilt after adds, removes and hand-overs
         self.halo = HaloExchange(self.local, rank, self.world, group=group, device=self.device) if self.world > 1 else None
         self._halo_passes = 0     # (world == 1 counts its passes here: there is no exchange)
+        # replicated host state: the config tables start as the local handler's (every rank builds the same)
+        self._init_host_state(copy.deepcopy(getattr(self.local, "_white_config", None)),
+                              copy.deepcopy(getattr(self.local, "_yolk_config", None)))
+        self._targets = {}        # global id -> (x, y)
+        self._counts = {}         # global id -> (white particles, yolk particles): gathered from the owners
+        # what the device library keeps per handle for its own draw, kept here per GLOBAL id so that a hand-over cannot
+        # lose it: the render keys as last sent, the rgba a batch's particles carry (L:978-990, L:1110-1129) and whether
+        # its colour table is its own (L:49-50)
+        self._rcfg = [self._c_render_config(True), self._c_render_config(False)]
+        self._pcolor = {}
+        self._own_color = {}
+        self._draw = dict(draws=0, messages=0, bytes=0, host_seconds=0.0)
 
     # ------------------------------------------------------------------ API
-    def add(self, x, y, white_radius=50.0, yolk_radius=15.0):
+    def add(self, x, y, white_radius=50.0, yolk_radius=15.0, white_color=None, yolk_color=None, white_n_particles=None,
+            yolk_n_particles=None, white_n=None, yolk_n=None):  # L:27-135
+        """SimulationHandler.add (the radii keep this class's defaults; None takes the reference's); `white_n` / `yolk_n`
+        are other names of the two counts"""
+        for long, short, name in ((white_n_particles, white_n, "white"), (yolk_n_particles, yolk_n, "yolk")):
+            if long is not None and short is not None and long != short:
+                raise EggError("[ERROR] In SimulationHandler.add: %s_n_particles and %s_n are two names of one count and "
+                               "differ (%r, %r)" % (name, name, long, short))
+        if white_n_particles is None:
+            white_n_particles = white_n
+        if yolk_n_particles is None:
+            yolk_n_particles = yolk_n
+        white_color, yolk_color, given = self._check_add(x, y, white_radius, yolk_radius, white_color, yolk_color,
+                                                         white_n_particles, yolk_n_particles)
+        if not (math.isfinite(x) and math.isfinite(y)):  # (refused on every rank, not by the owner's handle alone)
+            raise EggError("[ERROR] In SimulationHandler.add: position is not a finite number")
         gid = self.next_gid
-        self.next_gid += 1
         r = int(self.layout.owner_of([x])[0])
-        self.owner[gid] = r
-        self.radii[gid] = (white_radius, yolk_radius)
         if r == self.rank:
-            lid = int(self.local.add_many_keyed([x], [y], [gid], white_radius, yolk_radius)[0])
+            counts = {}  # (the overrides travel only when given: add_many_keyed keeps its positional form)
+            if white_n_particles is not None:
+                counts["white_n_particles"] = int(math.ceil(white_n_particles))
+            if yolk_n_particles is not None:
+                counts["yolk_n_particles"] = int(math.ceil(yolk_n_particles))
+            lid = int(self.local.add_many_keyed([x], [y], [gid], white_radius, yolk_radius, **counts)[0])
             self.local_id[gid] = lid
             self.global_id[lid] = gid
+        self.next_gid += 1
+        self.owner[gid] = r
+        self.radii[gid] = (white_radius, yolk_radius)
+        self._targets[gid] = (float(x), float(y))
+        # colours: L:978-990 (the particles take the batch colour only while _use_particle_color is set; add does not
+        # clamp), L:49-50 (no colour argument: the batch shares the config's table)
+        self._batch_colors[gid] = [white_color, yolk_color]
+        self._own_color[gid] = [bool(given[0]), bool(given[1])]
+        pc = np.ones((2, 4), dtype=np.float32)
+        if self._use_particle_color_flag:
+            for which, color in enumerate((white_color, yolk_color)):
+                pc[which] = list(color[:4]) if given[which] else list(self._rcfg[which].color)
+        self._pcolor[gid] = pc
         self._budget_stale = True  # summed over the ranks before the next step
         self._keys_stale = True
         return gid
+
+    def remove(self, batch_id):  # L:140-155
+        _assert_types(batch_id, "number")
+        gid = int(batch_id)
+        if gid not in self.owner:
+            warnings.warn("In SimulationHandler.remove: no batch with id `%d`" % gid, EggWarning)
+            return
+        if self.owner[gid] == self.rank:
+            lid = self.local_id[gid]
+            self.local.remove(lid)
+            del self.local_id[gid], self.global_id[lid]
+        for table in (self.owner, self.radii, self._targets, self._counts, self._batch_colors, self._own_color, self._pcolor):
+            table.pop(gid, None)
+        self._budget_stale = True
+        self._keys_stale = True
+
+    def list_ids(self):  # L:399-405
+        return sorted(self.owner)
+
+    def get_n_particles(self, batch_or_nil=None):  # L:409-419
+        if batch_or_nil is not None and int(batch_or_nil) not in self.owner:
+            raise EggError("[ERROR] In SimulationHandler:get_n_particles: no batch with id `%d`" % int(batch_or_nil))
+        self._sync_counts()
+        if batch_or_nil is not None:
+            return self._counts[int(batch_or_nil)]
+        return (sum(c[0] for c in self._counts.values()), sum(c[1] for c in self._counts.values()))
+
+    def get_target_position(self, batch_id):  # L:268-278
+        _assert_types(batch_id, "number")
+        if int(batch_id) not in self.owner:
+            raise EggError("[ERROR] In SimulationHandler.get_target_position: no batch with id `%d`" % int(batch_id))
+        return self._targets[int(batch_id)]
+
+    def get_position(self, batch_id):  # L:281-295
+        """the owner's egg_get_position (the reference's serial centroid), the same value on every rank: one
+        fixed-shape broadcast from the owner"""
+        _assert_types(batch_id, "number")
+        gid = int(batch_id)
+        if gid not in self.owner:
+            raise EggError("[ERROR] In SimulationHandler.get_position: no batch with id `%d`" % gid)
+        src, err, rec = self.owner[gid], None, [0.0, 0.0, 0.0]
+        if src == self.rank:
+            try:
+                rec[0], rec[1] = self.local.get_position(self.local_id[gid])
+            except EggError as e:
+                err, rec[2] = e, 1.0
+        if self.world > 1:
+            t = self.torch.tensor(rec, dtype=self.torch.float64).to(self.device)
+            self.dist.broadcast(t, src)
+            rec = t.tolist()
+        if err is not None:
+            raise err
+        if rec[2] != 0.0:
+            raise EggError("[ERROR] In SimulationHandler.get_position: refused on rank %d, which owns batch `%d`" % (src, gid))
+        return rec[0], rec[1]
+
+    # configs: validated on every rank by _HandlerSurface, then applied to the local handle; the re-derivation of mass
+    # and radius is per particle (L:1731-1744) and lands on the same bits wherever the particle lives
+    def _apply_config(self, white_or_yolk):
+        self.local.set_solver_config(_ffi.WHITE if white_or_yolk else _ffi.YOLK, self._c_config(white_or_yolk))
+        self._send_render_config()
+        self._budget_stale = True
+
+    def _send_render_config(self):  # egg_set_render_config, per global id
+        for which in range(2):
+            c = self._c_render_config(which == 0)
+            ok = (0 <= c.outline_thickness <= 256 and c.texture_scale > 0 and
+                  all(math.isfinite(v) for v in (c.motion_blur, c.highlight_strength, c.shadow_strength)))
+            if not ok:
+                raise EggError("[ERROR] egg_set_render_config: value out of range")
+            self._rcfg[which] = c
+            for own in self._own_color.values():  # config.color is a new table now (L:1307-1311)
+                own[which] = True
+
+    def _apply_render_flags(self):
+        pass  # (the switches are read at add and at draw)
+
+    def _message(self):  # (_check of a library call that takes no handle)
+        return self._lib.egg_last_error(None).decode()
+
+    def _apply_color(self, gid, which, rgba):  # egg_set_color, per global id
+        if any(_is_nan(c) for c in rgba):
+            return
+        c = np.array([float(v) for v in rgba], dtype=np.float32)
+        self._pcolor[gid][which] = c
+        if not self._own_color[gid][which]:  # the shared table (L:49-50, L:349-350)
+            self._rcfg[which].color[:] = [float(v) for v in c]
+
+    @property
+    def elapsed(self):
+        return self._elapsed
+
+    @property
+    def interpolation_alpha(self):
+        return self._alpha
 
     def set_solver_order(self, order, relaxation=None):
         """"exact" (default) or "relaxed" with omega `relaxation` (None keeps the current value), on every rank alike.
@@ -427,18 +597,28 @@ class ShardedSimulationHandler:
             return dict(passes=self._halo_passes, records=0, bytes=0)
         return dict(passes=self.halo.passes, records=self.halo.records, bytes=self.halo.bytes)
 
-    def set_target_position(self, gid, x, y):
+    def set_target_position(self, batch_id, x, y):  # L:254-264
+        _assert_types(batch_id, "number", x, "number", y, "number")
+        gid = int(batch_id)
+        if gid not in self.owner:
+            warnings.warn("In SimulationHandler.set_target_position: no batch with id `%d`" % gid, EggWarning)
+            return
         if self.owner[gid] == self.rank:
             self.local.set_target_position(self.local_id[gid], x, y)
+        self._targets[gid] = (float(x), float(y))
 
     def update(self, delta, step_delta=None, n_substeps=None, n_collision_steps=None):
         """The reference's fixed-step accumulator (simulation_handler.lua:199-216) around the exchanging step():
         every `_step` gets its own claim exchange (the claims of one exchange cover one step only)."""
-        step_delta = 1 / 60 if step_delta is None else step_delta
-        n_substeps = 2 if n_substeps is None else int(math.ceil(n_substeps))
-        n_collision_steps = 3 if n_collision_steps is None else int(math.ceil(n_collision_steps))
-        if not (step_delta > 0) or n_substeps < 1 or n_collision_steps < 1:
-            raise EggError("[ERROR] In SimulationHandler.update: invalid step_delta / n_substeps / n_collision_steps")
+        step_delta, n_substeps, n_collision_steps = self._check_update(delta, step_delta, n_substeps, n_collision_steps)
+        for bad, text in ((_is_nan(delta), "`delta` is not a number"),  # egg_update's refusals
+                          (step_delta < 0 or _is_nan(step_delta), "`step_delta` is not a number > 0"),
+                          (step_delta == 0, "`step_delta` is 0"),
+                          (n_substeps < 1, "`n_substeps` is not a number > 0"),
+                          (n_collision_steps < 1, "`n_collision_steps` is not a number > 0")):
+            if bad:
+                raise EggError("[ERROR] In SimulationHandler.update: " + text)
+        n_substeps, n_collision_steps = int(n_substeps), int(n_collision_steps)
         self._elapsed = self._elapsed + delta
         n_steps = 0
         max_n_steps = max(4.0, 4 * math.ceil((1 / 60) / step_delta))
@@ -449,10 +629,16 @@ class ShardedSimulationHandler:
             if n_steps > max_n_steps:  # death-spiral guard, L:208-213
                 self._elapsed = 0
                 break
-        self.interpolation_alpha = min(max(self._elapsed / step_delta, 0.0), 1.0)
+        self._alpha = min(max(self._elapsed / step_delta, 0.0), 1.0)
         return n_steps
 
     def step(self, delta=1 / 60, n_substeps=2, n_collision_steps=3):
+        """`_step` directly (L:1722); returns the batches handed over"""
+        moved = self._step(delta, n_substeps, n_collision_steps)
+        self._n_steps += 1  # (a refused step raised)
+        return moved
+
+    def _step(self, delta, n_substeps, n_collision_steps):
         """One `_step` on every rank with the neighbour exchange hidden behind the kernels: post the
         claims, launch the local step, then look at the neighbours' claims; only if some pair of batches
         on different ranks could interact is the launched step discarded, the batches handed over and
@@ -547,16 +733,29 @@ class ShardedSimulationHandler:
         loc.rx_end(True)
         return self._rebalance_relaxed()
 
+    def _sync_counts(self):
+        """(white, yolk) particle counts of every live batch on every rank: the owners of the batches nobody has counted
+        yet report them in one all_gather of (gid, n_white, n_yolk) rows; nothing travels while no batch was added"""
+        if all(g in self._counts for g in self.owner):  # (the same on every rank: both tables are replicated)
+            return
+        rows = [[g] + list(self.local.get_n_particles(l)) for g, l in sorted(self.local_id.items()) if g not in self._counts]
+        rows = np.array(rows, dtype=np.float64).reshape(-1, 3)
+        for part in (self._all_gather_rows(rows) if self.world > 1 else [rows]):
+            for g, nw, ny in part:
+                self._counts[int(g)] = (int(nw), int(ny))
+
+    def _key_table(self):
+        """int64 [live batches, 3]: (gid, n_white, n_yolk) in ascending global id -- the particle order of ONE handle
+        holding every batch: a batch's particles start at the sum of the counts before it"""
+        self._sync_counts()
+        return np.array([[g, self._counts[g][0], self._counts[g][1]] for g in sorted(self.owner)], dtype=np.int64).reshape(-1, 3)
+
     def _sync_keys(self):
         """global keys: a batch's particles start at the sum of the type's particle counts over
-        the batches OF ALL RANKS with a smaller id.  One all_gather of (gid, n_white, n_yolk) rows, only after a batch
-        was added or handed over."""
+        the batches OF ALL RANKS with a smaller id.  Rebuilt only after a batch was added, removed or handed over."""
         if not self._keys_stale:
             return
-        rows = [[g] + list(self.local.get_n_particles(l)) for g, l in sorted(self.local_id.items())]
-        parts = self._all_gather_rows(np.array(rows, dtype=np.float64).reshape(-1, 3))
-        table = np.concatenate(parts).astype(np.int64)
-        table = table[np.argsort(table[:, 0], kind="stable")]
+        table = self._key_table()
         for which in (0, 1):
             n = table[:, 1 + which]
             self.local.rx_set_keys(which, table[:, 0], np.cumsum(n) - n, int(n.sum()))
@@ -638,6 +837,149 @@ class ShardedSimulationHandler:
         """{global id: (x[n], y[n])} of this rank's batches"""
         x, y, b = self.local.download(which, "x"), self.local.download(which, "y"), self.local.download(which, "batch_id")
         return {self.global_id[int(l)]: (x[b == l], y[b == l]) for l in np.unique(b)}
+
+    # ------------------------------------------------------------ draw: gather to the render rank
+    def draw_counters(self):
+        """this rank's share of the draws so far (draw, get_environment and download each count as one): messages and bytes
+        it sent or received, wall time it spent in them.  A message is 56 B per particle + one 8 B status word."""
+        return dict(self._draw)
+
+    @staticmethod
+    def _runs(counts, bases):
+        """run tables of one message: its batches in the sender's order (ascending global id) with `counts` particles each go
+        to `bases`; batches whose destinations follow each other share a run"""
+        src, dst, at, nxt = [], [], 0, None
+        for n, b in zip(counts, bases):
+            if b != nxt:
+                src.append(at)
+                dst.append(int(b))
+            at += int(n)
+            nxt = int(b) + int(n)
+        return src, dst
+
+    def _gather(self, which):
+        """Type `which` of every rank into the render rank's external draw source, in global-key order.  Per non-render
+        rank ONE message: double[7][n] packed by the library straight into the tensor that is sent (device memory with
+        "nccl", host memory with gloo), then one status word (1.0: the pack was refused).  Its size and the place of every
+        batch in it follow from the replicated tables: a rank's particles lie in ascending global id.  Returns the error
+        of this rank (or, on the render rank, of a sender), None when the type is placed."""
+        table = self._key_table()
+        gids, n = table[:, 0], table[:, 1 + which]
+        base, total = np.cumsum(n) - n, int(n.sum())
+        owners = np.array([self.owner[int(g)] for g in gids], dtype=np.int64)
+        held = [int(n[owners == r].sum()) for r in range(self.world)]
+        F, err, recv = len(_ffi.DRAW_FIELDS), None, {}
+        if self.world > 1:
+            torch, dist = self.torch, self.dist
+            ops = []
+            if self.rank != self.root:
+                msg = torch.empty(F * held[self.rank] + 1, dtype=torch.float64, device=self.device)
+                try:
+                    self.local.draw_pack(which, msg.data_ptr(), held[self.rank])  # (complete when it returns)
+                except EggError as e:
+                    err = e
+                msg[-1:].fill_(0.0 if err is None else 1.0)
+                ops.append(dist.P2POp(dist.isend, msg, self.root))
+                sizes = [msg.numel()]
+            else:
+                for r in range(self.world):
+                    if r != self.root:
+                        recv[r] = torch.empty(F * held[r] + 1, dtype=torch.float64, device=self.device)
+                        ops.append(dist.P2POp(dist.irecv, recv[r], r))
+                sizes = [t.numel() for t in recv.values()]
+            for req in dist.batch_isend_irecv(ops):
+                req.wait()
+            if self._on_gpu:  # the receives ran on torch's stream: complete before the library reads the tensors
+                torch.cuda.current_stream().synchronize()
+            self._draw["messages"] += len(sizes)
+            self._draw["bytes"] += 8 * sum(sizes)
+        if self.rank != self.root:
+            return err
+        refused = [r for r, t in recv.items() if float(t[-1]) != 0.0]
+        if refused:
+            return EggError("[ERROR] In ShardedSimulationHandler.draw: rank %d could not pack its particles" % refused[0])
+        try:
+            colors = np.array([self._pcolor[int(g)][which] for g in gids], dtype=np.float32).reshape(-1, 4)
+            self.local.draw_source_layout(which, total, base, colors)
+            for r in range(self.world):
+                m = owners == r
+                if r != self.rank and not m.any():
+                    continue  # a rank that owns nothing of the type is normal
+                src, dst = self._runs(n[m], base[m])
+                self.local.draw_source_place(which, 0 if r == self.rank else recv[r].data_ptr(), held[r], src, dst)
+        except EggError as e:
+            err = e
+        return err
+
+    def _agree(self, err):
+        """ONE flag all-reduce: a refusal on any rank raises on every rank, never on one while the others wait"""
+        flag = 0.0 if err is None else 1.0
+        if self.world > 1:
+            t = self.torch.tensor([flag], dtype=self.torch.float64).to(self.device)
+            self.dist.all_reduce(t, op=self.dist.ReduceOp.MAX)
+            flag = t.item()
+        if err is not None:
+            raise err
+        if flag != 0.0:
+            raise EggError("[ERROR] In ShardedSimulationHandler.draw: refused on another rank (its error says why); "
+                           "nothing was drawn on any rank")
+
+    def _collective(self, types, on_root):
+        t0 = time.perf_counter()
+        err = None
+        for which in types:
+            e = self._gather(which)
+            err = err or e
+        out = None
+        if self.rank == self.root and err is None:
+            try:
+                out = on_root()
+            except EggError as e:
+                err = e
+        self._draw["draws"] += 1
+        self._draw["host_seconds"] += time.perf_counter() - t0
+        self._agree(err)
+        return out
+
+    def draw(self, screen_size=(800, 600), origin=(0.0, 0.0), interpolation_alpha=None, clear=(0.0, 0.0, 0.0, 0.0),
+             canvas_sizes=None, use_instancing=True):  # L:159-162
+        """SimulationHandler.draw over the sharded scene.  Collective; returns the (H, W, 4) image on the render rank and
+        None on the other ranks.  Nothing is drawn before the first `_step` or while the SCENE has no particles of a type
+        (a rank that owns nothing is normal); interpolation_alpha None takes this object's; the canvases grow only, over
+        this object's draws."""
+        p = self._render_params(screen_size, origin, interpolation_alpha, clear, canvas_sizes, use_instancing)
+        return self._collective((0, 1), lambda: self.local.draw_source_render(
+            p, self._rcfg, self._use_particle_color_flag, self._use_lighting_flag, self._n_steps > 0, self._alpha))
+
+    def render_canvas(self, which):
+        """the density canvas of `which` as the last draw() left it, on the render rank (None elsewhere; no communication)"""
+        return self.local.draw_source_render_canvas(which) if self.rank == self.root else None
+
+    def get_environment(self, which):
+        """SimulationHandler.get_environment over the sharded scene.  Collective; the dict on the render rank, None elsewhere."""
+        return self._collective((which,), lambda: self.local.draw_source_environment(which, self._n_steps > 0))
+
+    def download(self, which, field):
+        """One of the seven draw fields (_ffi.DRAW_FIELDS) or "batch_id" (global ids) of every particle of the scene in
+        global-key order.  Collective; the array on the render rank, None elsewhere."""
+        if field != "batch_id" and field not in _ffi.DRAW_FIELDS:
+            raise EggError("[ERROR] In ShardedSimulationHandler.download: only %s and batch_id travel to the render rank, "
+                           "not `%s` (particles() reads the local handler)" % (", ".join(_ffi.DRAW_FIELDS), field))
+        table = self._key_table()
+        if field == "batch_id":
+            out = np.repeat(table[:, 0], table[:, 1 + which]).astype(np.float64)
+            return out if self.rank == self.root else None
+        total = int(table[:, 1 + which].sum())
+        return self._collective((which,), lambda: self.local.draw_source_download(which, field, total))
+
+    def download_instance_data(self, which):
+        """SimulationHandler.download_instance_data over the sharded scene: one gather.  Collective; render rank only."""
+        total = int(self._key_table()[:, 1 + which].sum())
+
+        def on_root():
+            cols = [self.local.draw_source_download(which, f, total) for f in _ffi.DRAW_FIELDS]
+            return np.stack(cols, axis=1) if total else np.zeros((0, 7))
+        return self._collective((which,), on_root)
 
     # ------------------------------------------------------------ internals
     def _bounds(self):

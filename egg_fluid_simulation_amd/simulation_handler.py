@@ -191,10 +191,13 @@ class _HandlerSurface:
     def _use_particle_color(self):
         return self._use_particle_color_flag
 
+    def _apply_render_flags(self):
+        self._check(self._c("set_render_flags")(int(self._use_particle_color_flag), int(self._use_lighting_flag)))
+
     @_use_particle_color.setter
     def _use_particle_color(self, flag):
         self._use_particle_color_flag = bool(flag)
-        self._check(self._c("set_render_flags")(int(self._use_particle_color_flag), int(self._use_lighting_flag)))
+        self._apply_render_flags()
 
     @property
     def _use_lighting(self):
@@ -203,19 +206,22 @@ class _HandlerSurface:
     @_use_lighting.setter
     def _use_lighting(self, flag):
         self._use_lighting_flag = bool(flag)
-        self._check(self._c("set_render_flags")(int(self._use_particle_color_flag), int(self._use_lighting_flag)))
+        self._apply_render_flags()
+
+    def _apply_config(self, white_or_yolk):
+        """the validated config table of one type to the device (ShardedSimulationHandler has its own)"""
+        self._check(self._c("set_config")(_ffi.WHITE if white_or_yolk else _ffi.YOLK, C.byref(self._c_config(white_or_yolk))))
+        self._send_render_config()
 
     def set_white_config(self, config):  # L:226-229
         _assert_types(config, "table")
         self._load_config(copy.deepcopy(config), True)
-        self._check(self._c("set_config")(_ffi.WHITE, C.byref(self._c_config(True))))
-        self._send_render_config()
+        self._apply_config(True)
 
     def set_yolk_config(self, config):  # L:233-236
         _assert_types(config, "table")
         self._load_config(copy.deepcopy(config), False)
-        self._check(self._c("set_config")(_ffi.YOLK, C.byref(self._c_config(False))))
-        self._send_render_config()
+        self._apply_config(False)
 
     def get_white_config(self):  # L:240-242
         return copy.deepcopy(self._white_config)
@@ -238,6 +244,27 @@ class _HandlerSurface:
     # --------------------------------------------------------------------- add
     def add(self, x, y, white_radius=None, yolk_radius=None, white_color=None, yolk_color=None,
             white_n_particles=None, yolk_n_particles=None):  # L:27-135
+        white_color, yolk_color, given = self._check_add(x, y, white_radius, yolk_radius, white_color, yolk_color,
+                                                         white_n_particles, yolk_n_particles)
+        out = C.c_int64()
+        rc = self._c("add")(float(x), float(y),
+                               float("nan") if white_radius is None else float(white_radius),
+                               float("nan") if yolk_radius is None else float(yolk_radius),
+                               _ffi.DEFAULT_COUNT if white_n_particles is None else int(math.ceil(white_n_particles)),
+                               _ffi.DEFAULT_COUNT if yolk_n_particles is None else int(math.ceil(yolk_n_particles)),
+                               C.byref(out))
+        self._check(rc)
+        # L:49-50, L:124-129: a batch created without a colour shares the CONFIG's colour table (set_*_color on it then
+        # changes config.color too); the device library is told which tables are the batch's own
+        self._batch_colors[out.value] = [white_color, yolk_color]
+        for which, color in enumerate((white_color, yolk_color)):
+            if given[which]:
+                self._c("set_add_color")(out.value, which, *[float(c) for c in color[:4]])
+        return out.value
+
+    def _check_add(self, x, y, white_radius, yolk_radius, white_color, yolk_color, white_n_particles, yolk_n_particles):
+        """the argument checks of add (L:27-108), in the reference's order; returns the two colour tables (the config's
+        where none was given) and which of them were given"""
         _assert_types(x, "number", y, "number")
         given = (white_color is not None, yolk_color is not None)
         white_color = white_color if white_color is not None else self._white_config.get("color", [1, 1, 1, 1])
@@ -264,21 +291,7 @@ class _HandlerSurface:
                 if color[i] < 0 or color[i] > 1:
                     warnings.warn("In SimulationHandler.add: %s color component `%s` is outside of [0, 1]"
                                   % (name, cname), EggWarning)
-        out = C.c_int64()
-        rc = self._c("add")(float(x), float(y),
-                               float("nan") if white_radius is None else float(white_radius),
-                               float("nan") if yolk_radius is None else float(yolk_radius),
-                               _ffi.DEFAULT_COUNT if white_n_particles is None else int(math.ceil(white_n_particles)),
-                               _ffi.DEFAULT_COUNT if yolk_n_particles is None else int(math.ceil(yolk_n_particles)),
-                               C.byref(out))
-        self._check(rc)
-        # L:49-50, L:124-129: a batch created without a colour shares the CONFIG's colour table (set_*_color on it then
-        # changes config.color too); the device library is told which tables are the batch's own
-        self._batch_colors[out.value] = [white_color, yolk_color]
-        for which, color in enumerate((white_color, yolk_color)):
-            if given[which]:
-                self._c("set_add_color")(out.value, which, *[float(c) for c in color[:4]])
-        return out.value
+        return white_color, yolk_color, given
 
     def remove(self, batch_id):  # L:140-155
         _assert_types(batch_id, "number")
@@ -291,6 +304,15 @@ class _HandlerSurface:
         """`draw()` without a window: _update_canvases + _draw_canvases (L:1995-2175) as HIP kernels into a float32
         RGBA image of screen_size = (width, height); world px = screen px + origin.  Returns an (H, W, 4) array.
         canvas_sizes = [(w, h) white, (w, h) yolk] overrides the sizes resize_canvas_maybe would pick (L:1935-1975)."""
+        p = self._render_params(screen_size, origin, interpolation_alpha, clear, canvas_sizes, use_instancing)
+        # (the render config is NOT re-sent here: egg_set_render_config means "set_*_config was called" -- a new colour
+        # table, L:1307-1311 -- and would end the sharing of the old one between the config and its colourless batches)
+        image = np.empty((p.screen_h, p.screen_w, 4), dtype=np.float32)
+        self._check(self._c("render")(C.byref(p), image.ctypes.data_as(C.c_void_p)))
+        return image
+
+    def _render_params(self, screen_size, origin, interpolation_alpha, clear, canvas_sizes, use_instancing):
+        """draw()'s arguments as egg_render_params"""
         p = _ffi.EggRenderParams()
         self._check(self._lib.egg_default_render_params(C.byref(p)))
         p.screen_w, p.screen_h = int(screen_size[0]), int(screen_size[1])
@@ -304,11 +326,7 @@ class _HandlerSurface:
             for which in range(2):
                 p.canvas_w[which], p.canvas_h[which] = int(canvas_sizes[which][0]), int(canvas_sizes[which][1])
         p.clear[:] = [float(c) for c in clear]
-        # (the render config is NOT re-sent here: egg_set_render_config means "set_*_config was called" -- a new colour
-        # table, L:1307-1311 -- and would end the sharing of the old one between the config and its colourless batches)
-        image = np.empty((p.screen_h, p.screen_w, 4), dtype=np.float32)
-        self._check(self._c("render")(C.byref(p), image.ctypes.data_as(C.c_void_p)))
-        return image
+        return p
 
     def render_canvas(self, which):
         """the density canvas of `which` as the last draw() left it: ((h, w, 4) float32 array, (x0, y0) in world px)"""
@@ -321,6 +339,15 @@ class _HandlerSurface:
 
     # ------------------------------------------------------------------ update
     def update(self, delta, step_delta=None, n_substeps=None, n_collision_steps=None):  # L:168-222
+        step_delta, n_substeps, n_collision_steps = self._check_update(delta, step_delta, n_substeps, n_collision_steps)
+        n = C.c_int32()
+        self._check(self._c("update")(float(delta), float(step_delta), int(n_substeps),
+                                         int(n_collision_steps), C.byref(n)))
+        return n.value
+
+    @staticmethod
+    def _check_update(delta, step_delta, n_substeps, n_collision_steps):
+        """defaults, type checks and rounding of update's arguments (L:168-182)"""
         if step_delta is None:
             step_delta = 1 / 60
         if n_substeps is None:
@@ -332,10 +359,7 @@ class _HandlerSurface:
             raise EggError("[ERROR] In SimulationHandler.update: `n_substeps` is not a number > 0")
         n_substeps = math.ceil(n_substeps)  # L:181-182
         n_collision_steps = math.ceil(n_collision_steps)
-        n = C.c_int32()
-        self._check(self._c("update")(float(delta), float(step_delta), int(n_substeps),
-                                         int(n_collision_steps), C.byref(n)))
-        return n.value
+        return step_delta, n_substeps, n_collision_steps
 
     def step(self, delta=1 / 60, n_substeps=2, n_collision_steps=3):
         """`_step` directly (L:1722); not part of the reference's public surface."""
@@ -377,9 +401,12 @@ class _HandlerSurface:
             table[:] = rgba
         else:
             self._batch_colors[int(batch_id)][which] = rgba
+        self._apply_color(int(batch_id), int(which), rgba)
+
+    def _apply_color(self, batch_id, which, rgba):
         # its particles (L:1110-1129) and, when the batch shares the config's table, the config's colour: the library
         # applies the same aliasing as the tables above
-        self._c("set_color")(int(batch_id), int(which), *[float(c) for c in rgba])
+        self._c("set_color")(batch_id, which, *[float(c) for c in rgba])
 
     def set_white_color(self, batch_id, r, g, b, a=None, *outline):  # L:365-394
         self._set_color("set_white_color", 0, batch_id, r, g, b, a)
@@ -474,7 +501,8 @@ class SimulationHandler(_HandlerSurface):
             _ffi.DEFAULT_COUNT if yolk_n_particles is None else int(yolk_n_particles), ids.ctypes.data))
         return ids
 
-    def add_many_keyed(self, xs, ys, keys, white_radius=None, yolk_radius=None):
+    def add_many_keyed(self, xs, ys, keys, white_radius=None, yolk_radius=None, white_n_particles=None,
+                       yolk_n_particles=None):
         """`add_many` with explicit global-order keys (multi-GPU sharding, see include/eggsim.h)"""
         xs = np.ascontiguousarray(xs, dtype=np.float64)
         ys = np.ascontiguousarray(ys, dtype=np.float64)
@@ -483,9 +511,15 @@ class SimulationHandler(_HandlerSurface):
         self._check(self._lib.egg_add_many_keyed(
             self._h, xs.shape[0], xs.ctypes.data, ys.ctypes.data,
             float("nan") if white_radius is None else float(white_radius),
-            float("nan") if yolk_radius is None else float(yolk_radius), _ffi.DEFAULT_COUNT, _ffi.DEFAULT_COUNT,
+            float("nan") if yolk_radius is None else float(yolk_radius),
+            _ffi.DEFAULT_COUNT if white_n_particles is None else int(white_n_particles),
+            _ffi.DEFAULT_COUNT if yolk_n_particles is None else int(yolk_n_particles),
             keys.ctypes.data, ids.ctypes.data))
         return ids
+
+    def set_solver_config(self, which, c_config):
+        """egg_set_config with an _ffi.EggConfig somebody else validated (ShardedSimulationHandler owns the tables)"""
+        self._check(self._lib.egg_set_config(self._h, int(which), C.byref(c_config)))
 
     def export_batch(self, batch_id):
         """(info dict, white_state[9, n_w], yolk_state[9, n_y]) of a batch: everything another handler
@@ -574,6 +608,51 @@ class SimulationHandler(_HandlerSurface):
         cells = np.empty(2, dtype=np.float64)
         self._check(self._lib.egg_get_claims_many(self._h, ids.shape[0], ids.ctypes.data, out.ctypes.data, cells.ctypes.data))
         return out, (float(cells[0]), float(cells[1]))
+
+    # ------------------------------------------- draw of a scene sharded over processes (egg_draw_*, include/eggsim.h)
+    # A message is double[7][n] (_ffi.DRAW_FIELDS), given by ADDRESS: host memory or memory of this handle's device.
+    def draw_pack(self, which, pointer, cap_particles):
+        """this handle's particles of `which` as one message at `pointer` (complete when this returns)"""
+        self._check(self._lib.egg_draw_pack(self._h, int(which), C.c_void_p(int(pointer)), int(cap_particles)))
+
+    def draw_source_layout(self, which, total, atom_offset, atom_color):
+        """the layout of `which` over all ranks: atom_offset [atoms] int64 ascending from 0, atom_color [atoms, 4]"""
+        off = np.ascontiguousarray(atom_offset, dtype=np.int64)
+        col = np.ascontiguousarray(atom_color, dtype=np.float32).reshape(-1, 4)
+        self._check(self._lib.egg_draw_source_layout(self._h, int(which), int(total), off.shape[0], off.ctypes.data, col.ctypes.data))
+
+    def draw_source_place(self, which, pointer, n, run_src, run_dst):
+        """one message (pointer 0: this handle's own particles) into its places; the message must be complete"""
+        rs = np.ascontiguousarray(run_src, dtype=np.int64)
+        rd = np.ascontiguousarray(run_dst, dtype=np.int64)
+        self._check(self._lib.egg_draw_source_place(self._h, int(which), C.c_void_p(int(pointer)) if pointer else None, int(n),
+                                                    rs.shape[0], rs.ctypes.data, rd.ctypes.data))
+
+    def draw_source_render(self, params, render_configs, use_particle_color, use_lighting, stepped, interpolation_alpha):
+        """egg_render over the placed particles; render_configs = (white, yolk) _ffi.EggRenderConfig"""
+        cfg = (_ffi.EggRenderConfig * 2)(*render_configs)
+        image = np.empty((params.screen_h, params.screen_w, 4), dtype=np.float32)
+        self._check(self._lib.egg_draw_source_render(self._h, C.byref(params), cfg, int(bool(use_particle_color)), int(bool(use_lighting)),
+                                                     int(bool(stepped)), float(interpolation_alpha), image.ctypes.data_as(C.c_void_p)))
+        return image
+
+    def draw_source_render_canvas(self, which):
+        w, h, x0, y0 = C.c_int32(), C.c_int32(), C.c_double(), C.c_double()
+        self._check(self._lib.egg_draw_source_render_canvas(self._h, int(which), None, 0, C.byref(w), C.byref(h), C.byref(x0), C.byref(y0)))
+        canvas = np.empty((h.value, w.value, 4), dtype=np.float32)
+        self._check(self._lib.egg_draw_source_render_canvas(self._h, int(which), canvas.ctypes.data_as(C.c_void_p), w.value * h.value,
+                                                            None, None, None, None))
+        return canvas, (x0.value, y0.value)
+
+    def draw_source_environment(self, which, stepped):
+        e = _ffi.EggEnvironment()
+        self._check(self._lib.egg_draw_source_environment(self._h, int(which), int(bool(stepped)), C.byref(e)))
+        return {k: getattr(e, k) for k in _ffi.ENVIRONMENT_FIELDS}
+
+    def draw_source_download(self, which, field, n):
+        out = np.empty(int(n), dtype=np.float64)
+        self._check(self._lib.egg_draw_source_download(self._h, int(which), _ffi.FIELD_ID[field], out.ctypes.data, int(n)))
+        return out
 
     # ---------------------------------------------------------- device access
     def synchronize(self):

@@ -134,7 +134,8 @@ int egg_prepare_step(egg_handle *h, double step_delta, int32_t n_substeps, int32
 /* A _step in two halves, so that a caller can overlap its own work (the multi-GPU neighbour exchange)
  * with the kernels: egg_step_begin forms the tiles and launches; egg_step_end(commit = 1) waits,
  * validates, re-runs if needed and commits -- begin + end(1) == egg_step; egg_step_end(commit = 0)
- * discards the launched step (the state is double-buffered, nothing was committed). */
+ * discards the launched step (the state is double-buffered, nothing was committed; the positions at the start of
+ * the last committed step, which draw() reads and which share the buffer a launched step writes, are put back). */
 int egg_step_begin(egg_handle *h, double delta, int32_t n_substeps, int32_t n_collision_steps);
 int egg_step_end(egg_handle *h, int32_t commit);
 /* Between egg_step_begin and egg_step_end: waits for the launched step and reports, per type, the most pairs it
@@ -463,6 +464,49 @@ int egg_rx_check(egg_handle *h, int32_t *bad, int64_t pairs[2], int64_t *ghost_r
 /* commit = 1 (after egg_rx_check, refused when it reported bad): post-solve of the last sub-step, the step counts as one
  * relaxed _step.  commit = 0, at any point after egg_rx_begin: the state is as before egg_rx_begin. */
 int egg_rx_end(egg_handle *h, int32_t commit);
+
+/* ---- draw() of a scene sharded over several PROCESSES (csrc/eggsim_host_draw_source.hip) ----
+ * One process per GPU (egg_fluid_simulation_amd/sharding.py): draw() depends on particle order twice -- the screen blend
+ * and the serial centroid sums (L:1669-1718, L:2057-2058) --, so every rank sends the draw record of its particles to ONE
+ * render rank, which puts them into the order of one handle holding every batch (the global key of egg_rx_set_keys) and
+ * runs the passes of egg_render over them, unchanged.  The handle knows nothing about the other ranks:
+ *
+ *   every rank:    egg_draw_pack(type)  ->  the message travels (or stays, on the render rank)
+ *   render rank:   egg_draw_source_layout(type)  ->  egg_draw_source_place(type) once per message and once for its own
+ *                  particles  ->  egg_draw_source_render / _environment / _download / _render_canvas
+ *
+ * A MESSAGE holds the seven draw fields x, y, last_x, last_y, vx, vy, radius (L:513-517, L:744-813) of n particles, field
+ * after field: double[7][n], 56 n bytes, particles in the sending handle's own order (ascending batch key).  Buffers may
+ * be host memory or memory of the handle's device, as for egg_rx_fetch; a buffer a call fills is complete when the call
+ * returns, a buffer a call reads must be complete (the caller has waited for its receive and synchronised the stream
+ * that filled it) and may go when the call returns.  The shadow arrays (56 B per particle of the whole scene on the
+ * render device), the canvases with their grow-only sizes (L:1957-1970) and the scratch of the passes belong to this
+ * external source, not to the handle's own egg_render. */
+/* the message of this handle's particles of `which` into `out` (room for cap_particles >= its particle count): one
+ * kernel launch on the type's stream.  Refused while a step is in flight (egg_step_begin or egg_rx_begin open). */
+int egg_draw_pack(egg_handle *h, int which, void *out, int64_t cap_particles);
+/* (a) the layout of type `which` over all ranks: `total` particles (at most 2^31 - 1: EGG_ERR_UNSUPPORTED, as when the
+ * render device has no room for them), atom_offset[k] the global key of the first particle of the k-th live batch in
+ * ascending key, atom_color[4 k ..] the rgba its particles carry (L:978-990, L:1110-1129).  Forgets what was placed. */
+int egg_draw_source_layout(egg_handle *h, int which, int64_t total, int64_t n_atoms, const int64_t *atom_offset, const float *atom_color);
+/* (b) one message of n particles into its places: run r covers the particles run_src[r] .. run_src[r + 1] - 1 of the
+ * message (run_src[0] = 0, ascending; the last run ends at n) and goes to run_dst[r] ..; a run is a stretch whose
+ * destinations are consecutive (whole batches).  msg = NULL places this handle's own particles from its arrays without a
+ * copy (n = its particle count; refused while a step is in flight).  Every run is checked against the message and the
+ * layout before anything is launched; every particle of the layout must be placed exactly once before (c). */
+int egg_draw_source_place(egg_handle *h, int which, const void *msg, int64_t n, int64_t n_runs, const int64_t *run_src, const int64_t *run_dst);
+/* (c) draw() (L:158-161) as egg_render over the placed particles.  cfg[2], the two switches (L:448-449), `stepped` (a
+ * _step has run: nothing is drawn before, L:1997-1999) and interpolation_alpha (taken where p->interpolation_alpha is
+ * NaN) are the caller's: the sharded scene owns them, not this handle.  Nothing is drawn while a type has no particles. */
+int egg_draw_source_render(egg_handle *h, const egg_render_params *p, const egg_render_config *cfg, int32_t use_particle_color,
+                           int32_t use_lighting, int32_t stepped, double interpolation_alpha, float *rgba);
+/* the density canvas of `which` as the last egg_draw_source_render left it (egg_render_canvas) */
+int egg_draw_source_render_canvas(egg_handle *h, int which, float *rgba, int64_t cap_pixels, int32_t *w, int32_t *hgt, double *x0,
+                                  double *y0);
+/* egg_get_environment over the placed particles of `which` (L:1669-1718, L:1795-1815) */
+int egg_draw_source_environment(egg_handle *h, int which, int32_t stepped, egg_environment *out);
+/* egg_download_particles over the placed particles: `field` is one of the seven draw fields (EGG_FIELD_*) */
+int egg_draw_source_download(egg_handle *h, int which, int field, double *dst, int64_t cap);
 
 #ifdef __cplusplus
 }
