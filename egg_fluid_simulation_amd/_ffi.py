@@ -213,6 +213,13 @@ _SIGNATURES = {
                                                 C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "egg_draw_source_environment": (C.c_int, [C.c_void_p, C.c_int, C.c_int32, C.POINTER(EggEnvironment)]),
     "egg_draw_source_download": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64]),
+    "egg_draw_source_instances": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    "egg_get_instances": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_uint64)]),
+    "egg_instances_begin": (C.c_int, [C.c_void_p, C.c_int32]),
+    "egg_instances_end": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
+                                    C.POINTER(C.c_uint64)]),
+    "egg_group_get_instances": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64),
+                                          C.POINTER(C.c_uint64)]),
 }
 
 EXPORTED_SYMBOLS = sorted(_SIGNATURES)

@@ -378,3 +378,16 @@ struct EggDrawPackArgs {
     double *dst;  // [EGG_GATHER_FIELDS * n]
     int32_t n;
 };
+
+// egg_instances_kernel (eggsim_instances.hip): the reference's two per-particle meshes (L:513-523) of n particles -- the
+// data mesh, seven floats per particle (egg_instance, 28 B), and the colour mesh, rgba per particle -- from seven source
+// arrays: a handle's own, a group's shadow arrays or the external draw source's.
+#define EGG_INSTANCE_BLOCK 256
+struct EggInstanceArgs {
+    const double *src[EGG_GATHER_FIELDS];  // x, y, last_x, last_y, vx, vy, radius
+    float *data;                  // [7 n], 16-byte aligned; null: colour only
+    float4 *color;                // [n]; null: data only
+    const int32_t *atom_offset;   // [n_atoms] first particle of every atom, ascending from 0 (read when color != null)
+    const float4 *atom_color;     // [n_atoms] the rgba an atom's particles carry
+    int32_t n, n_atoms;
+};

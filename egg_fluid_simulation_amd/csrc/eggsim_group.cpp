@@ -73,6 +73,9 @@ struct egg_group {
     std::vector<float> pcolor;
     std::vector<unsigned char> own_color;
     egghost::GroupDraw *draw = nullptr;  // device side of draws, created by the first one
+    // counts the successful calls that can change a particle's colour or the group's particle count
+    // (egg_group_get_instances); hand-overs change neither
+    uint64_t color_version = 1;
     std::string error;
 };
 
@@ -507,6 +510,7 @@ int egg_group_add(egg_group *g, double x, double y, double white_radius, double 
         g->own_color.push_back(0);
     }
     g->budget_stale = true;
+    g->color_version++;
     if (out_id) *out_id = gid;
     if (rc > 0) g->error = egg_last_error(g->h[(size_t)k]);  // the "few particles" warning (L:114-120): the batch exists
     return rc;
@@ -522,6 +526,7 @@ int egg_group_remove(egg_group *g, int64_t id) {
     GTRY(g, r.owner, egg_remove(g->h[(size_t)r.owner], r.local));
     r.alive = false;
     g->budget_stale = true;
+    g->color_version++;
     return EGG_OK;
 }
 
@@ -695,6 +700,7 @@ int egg_group_set_render_config(egg_group *g, int which, const egg_render_config
     g->render_cfg[which] = *cfg;
     // config.color is a new table now (L:1307-1311): batches that shared the old one keep it for themselves
     for (size_t i = 0; i < g->batch.size(); ++i) g->own_color[2 * i + (size_t)which] = 1;
+    g->color_version++;
     return EGG_OK;
 }
 
@@ -708,6 +714,7 @@ int egg_group_set_render_flags(egg_group *g, int32_t use_particle_color, int32_t
     if (!g) return EGG_ERR_INVALID_ARGUMENT;
     g->use_particle_color = use_particle_color != 0;
     g->use_lighting = use_lighting != 0;
+    g->color_version++;
     return EGG_OK;
 }
 
@@ -721,6 +728,7 @@ int egg_group_set_add_color(egg_group *g, int64_t id, int which, double r, doubl
         const float c[4] = {(float)r, (float)gr, (float)b, (float)a};
         memcpy(&g->pcolor[8 * (size_t)(id - 1) + 4 * (size_t)which], c, sizeof c);
     }
+    g->color_version++;
     return EGG_OK;
 }
 
@@ -734,6 +742,7 @@ int egg_group_set_color(egg_group *g, int64_t id, int which, double r, double gr
     const float c[4] = {clamp01(r), clamp01(gr), clamp01(b), clamp01(a)};  // _assert_color (L:300-319)
     memcpy(&g->pcolor[8 * (size_t)(id - 1) + 4 * (size_t)which], c, sizeof c);
     if (!g->own_color[2 * (size_t)(id - 1) + (size_t)which]) memcpy(g->render_cfg[which].color, c, sizeof c);  // the shared table (L:49-50, L:349-350)
+    g->color_version++;
     return EGG_OK;
 }
 
@@ -742,6 +751,14 @@ int egg_group_render(egg_group *g, const egg_render_params *p, float *rgba) {
     const egghost::GroupView v = view_of(g);
     std::string err;
     return gdone(g, egghost::group_draw_render(g->draw, v, p, rgba, &err), err);
+}
+
+int egg_group_get_instances(egg_group *g, int which, egg_instance *data, float *color, int64_t cap, int64_t *n, uint64_t *color_version) {
+    if (!g || (which != EGG_WHITE && which != EGG_YOLK) || cap < 0) return EGG_ERR_INVALID_ARGUMENT;
+    const egghost::GroupView v = view_of(g);
+    if (color_version) *color_version = g->color_version;
+    std::string err;
+    return gdone(g, egghost::group_draw_instances(g->draw, v, which, data, color, cap, n, &err), err);
 }
 
 int egg_group_render_canvas(egg_group *g, int which, float *rgba, int64_t cap_pixels, int32_t *w, int32_t *hgt, double *x0, double *y0) {

@@ -1,6 +1,6 @@
 // eggsim_group_draw.h -- what eggsim_group.cpp (plain C++, a client of include/eggsim.h) and
 // eggsim_host_render_group.hip share: the calls behind egg_group_render, egg_group_render_canvas,
-// egg_group_get_environment and egg_group_download_particles.  0 or an EGG_ERR_* code; on failure *error has the reason.
+// egg_group_get_environment, egg_group_download_particles and egg_group_get_instances.  0 or an EGG_ERR_* code; on failure *error has the reason.
 #pragma once
 #include <cstdint>
 #include <string>
@@ -30,5 +30,7 @@ int group_draw_canvas(GroupDraw *d, const GroupView &v, int which, float *rgba, 
                       double *y0, std::string *error);
 int group_draw_environment(GroupDraw *d, const GroupView &v, int which, egg_environment *out, std::string *error);
 int group_draw_download(GroupDraw *d, const GroupView &v, int which, int field, double *dst, int64_t cap, std::string *error);
+int group_draw_instances(GroupDraw *d, const GroupView &v, int which, egg_instance *data, float *color, int64_t cap, int64_t *n,
+                         std::string *error);
 
 }  // namespace egghost

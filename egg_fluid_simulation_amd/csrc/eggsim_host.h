@@ -12,6 +12,7 @@
 //   eggsim_host_relaxed_wire.hip   the same step driven pass by pass through the C ABI (egg_rx_*): one handle per process
 //   eggsim_host_render_group.hip   draw / environment / download of a device group: gather to one device (eggsim_render_group.hip)
 //   eggsim_host_draw_source.hip    the same for a scene sharded over processes: egg_draw_pack on every rank, egg_draw_source_* on one
+//   eggsim_host_instances.hip      egg_get_instances / egg_instances_begin / _end: the instanced-draw record packed on the device
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -82,6 +83,7 @@ extern "C" __global__ void egg_rx_wire_pack_kernel(EggRxWirePackArgs P);
 extern "C" __global__ void egg_rx_wire_unpack_kernel(EggRxWireUnpackArgs U);
 extern "C" __global__ void egg_group_gather_kernel(EggGatherArgs A);
 extern "C" __global__ void egg_draw_pack_kernel(EggDrawPackArgs A);
+extern "C" __global__ void egg_instances_kernel(EggInstanceArgs A);
 extern "C" __global__ void egg_render_count_kernel(EggRenderArgs A);
 extern "C" __global__ void egg_render_fill_kernel(EggRenderArgs A);
 extern "C" __global__ void egg_render_scan_kernel(EggRenderArgs A);
@@ -351,6 +353,7 @@ inline int32_t *d_disp(System &s) { return s.d_out.p + 2 * kStatInts + 4 * s.ato
 namespace egghost {
 struct WireStep;  // a relaxed step in flight between egg_rx_begin and egg_rx_end (eggsim_host_relaxed_wire.hip)
 struct DrawSource;  // particles placed by egg_draw_source_place, their canvases and scratch (eggsim_host_draw_source.hip)
+struct InstanceState;  // staging and pinned buffers of egg_get_instances / egg_instances_begin (eggsim_host_instances.hip)
 }
 using namespace egghost;
 
@@ -395,6 +398,10 @@ struct egg_handle {
     std::shared_ptr<egghost::WireStep> wire;  // global keys and the step in flight, allocated by the first egg_rx_* call
     std::shared_ptr<egghost::DrawSource> draw_source;  // allocated by the first egg_draw_source_* call
     DevBuf<double> draw_pack;      // egg_draw_pack into host memory: the message before its one copy out
+    // counts the successful calls that can change a particle's colour or the particle count (egg_get_instances: a host
+    // re-uploads its colour mesh only when this has moved)
+    uint64_t color_version = 1;
+    std::shared_ptr<egghost::InstanceState> instances;  // allocated by the first egg_get_instances / egg_instances_begin
     // headless renderer (eggsim_render.hip)
     struct Render {
         egg_render_config cfg[2];
@@ -466,6 +473,14 @@ int render_canvas_from(egg_handle *h, egg_handle::Render &R, const char *name, i
                        int32_t *hgt, double *x0, double *y0);
 // the reductions of egg_get_environment over the arrays of T (eggsim_host_abi.hip)
 int environment_of(egg_handle *h, bool stepped, const RenderSource::Type &T, egg_environment *out);
+// eggsim_host_instances.hip: the two meshes of egg_get_instances from the arrays T describes -- a handle's own, a
+// group's shadow arrays, the external draw source's -- into data / color (host or device memory, either may be null).
+// One launch of egg_instances_kernel on `st` of h's device, which is idle when this returns; whatever else wrote the
+// arrays must have finished or been put in front of `st`.  Errors go to h under `name`.
+int instances_from(egg_handle *h, hipStream_t st, const RenderSource::Type &T, const char *name, egg_instance *data, float *color,
+                   int64_t cap, int64_t *n);
+// memory of h's device (a kernel may touch it) or anything else (reached through hipMemcpyDefault)
+bool on_device_of(const egg_handle *h, const void *p);
 
 Batch *find_batch(egg_handle *h, int64_t id);
 const Batch *find_batch(const egg_handle *h, int64_t id);

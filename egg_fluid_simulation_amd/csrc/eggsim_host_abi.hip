@@ -263,6 +263,7 @@ static int add_many_impl(egg_handle *h, int64_t n, const double *xs, const doubl
         h->n_alive++;
         if (out_ids) out_ids[k] = b.id;
     }
+    h->color_version++;  // (more particles: the colour mesh of egg_get_instances is another one)
     if (white_n < 10 || yolk_n < 5) {  // L:114-120: warning only
         fail(h, EGG_WARN_FEW_PARTICLES,
              "In SimulationHandler.add: only %lld white / %lld yolk particles will be created; consider "
@@ -313,6 +314,7 @@ int egg_remove(egg_handle *h, int64_t id) {  // L:140-155, L:1037-1106
     b->alive = false;
     h->n_alive--;
     h->order.erase(std::remove(h->order.begin(), h->order.end(), (int32_t)(id - 1)), h->order.end());
+    h->color_version++;
     return EGG_OK;
 }
 
@@ -773,6 +775,7 @@ int egg_import_batch(egg_handle *h, const egg_batch_info *info, const double *wh
     h->batches.push_back(b);
     h->n_alive++;
     if (info->key >= h->next_key) h->next_key = info->key + 1;
+    h->color_version++;
     if (out_id) *out_id = b.id;
     return EGG_OK;
 }

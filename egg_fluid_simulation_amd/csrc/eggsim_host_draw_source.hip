@@ -12,7 +12,7 @@
 // Everything after the placement is the single handle's renderer and reductions, unchanged (render_from,
 // environment_of, render_canvas_from).  The shadow arrays, the canvases with their grow-only sizes and the scratch of the
 // passes belong to the DrawSource, not to the handle's own draw state (egg_render), as GroupDraw keeps them apart from
-// handle 0's.  All device work goes to the stream of the handle's white type; every entry point returns with it idle.
+// handle 0's.  egg_draw_source_instances packs the placed particles into the reference's two meshes (eggsim_host_instances.hip).  All device work goes to the stream of the handle's white type; every entry point returns with it idle.
 #include "eggsim_host.h"
 
 namespace egghost {
@@ -29,10 +29,6 @@ struct DrawSource {
     } t[2];
 };
 
-namespace {
-
-constexpr int64_t kMaxDrawParticles = std::numeric_limits<int32_t>::max();
-
 // memory of this handle's device (a kernel may touch it) or anything else (reached through hipMemcpyDefault)
 bool on_device_of(const egg_handle *h, const void *p) {
     hipPointerAttribute_t a;
@@ -42,6 +38,10 @@ bool on_device_of(const egg_handle *h, const void *p) {
     }
     return a.type == hipMemoryTypeDevice && a.device == h->device;
 }
+
+namespace {
+
+constexpr int64_t kMaxDrawParticles = std::numeric_limits<int32_t>::max();
 
 DrawSource &source_of(egg_handle *h) {
     if (!h->draw_source) h->draw_source = std::make_shared<DrawSource>();
@@ -235,6 +235,18 @@ int egg_draw_source_download(egg_handle *h, int which, int field, double *dst, i
     HIP_TRY(h, hipMemcpyAsync(dst, T.sh.f[f].p, (size_t)T.total * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(h, hipStreamSynchronize(st));
     return EGG_OK;
+}
+
+int egg_draw_source_instances(egg_handle *h, int which, egg_instance *data, float *color, int64_t cap, int64_t *n) {
+    if (!h || (which != EGG_WHITE && which != EGG_YOLK) || cap < 0) return EGG_ERR_INVALID_ARGUMENT;
+    DrawSource::Type &T = source_of(h).t[which];
+    const int rc = need_complete(h, T, which, "egg_draw_source_instances");
+    if (rc != EGG_OK) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    RenderSource::Type S;
+    shadow_source(T.sh, T.total, h->sys[0].stream, S);  // (every placement ended with that stream idle)
+    S.atom_color = T.atom_color;
+    return instances_from(h, h->sys[0].stream, S, "egg_draw_source_instances", data, color, cap, n);
 }
 
 }  // extern "C"

@@ -29,6 +29,7 @@ int egg_set_render_config(egg_handle *h, int which, const egg_render_config *cfg
     // config.color is a new table now -- whatever its values: set_*_config deep-copies (L:1307-1311) --, so batches that
     // shared the old one keep it for themselves.  (Call this where the reference calls set_*_config, not once per frame.)
     for (Batch &b : h->batches) b.own_color[which] = true;
+    h->color_version++;  // (every successful call that CAN change a particle's colour counts: egg_get_instances)
     return EGG_OK;
 }
 
@@ -42,6 +43,7 @@ int egg_set_render_flags(egg_handle *h, int32_t use_particle_color, int32_t use_
     if (!h) return EGG_ERR_INVALID_ARGUMENT;
     h->render.use_particle_color = use_particle_color != 0;
     h->render.use_lighting = use_lighting != 0;
+    h->color_version++;
     return EGG_OK;
 }
 
@@ -58,6 +60,7 @@ int egg_set_add_color(egg_handle *h, int64_t id, int which, double r, double g, 
         const float c[4] = {(float)r, (float)g, (float)b, (float)a};
         memcpy(B->pcolor[which], c, sizeof c);
     }
+    h->color_version++;
     return EGG_OK;
 }
 
@@ -72,6 +75,7 @@ int egg_set_color(egg_handle *h, int64_t id, int which, double r, double g, doub
     const float c[4] = {clamp01(r), clamp01(g), clamp01(b), clamp01(a)};  // _assert_color (L:300-319)
     memcpy(B->pcolor[which], c, sizeof c);
     if (!B->own_color[which]) memcpy(h->render.cfg[which].color, c, sizeof c);  // the shared table (L:49-50, L:349-350)
+    h->color_version++;
     return EGG_OK;
 }
 

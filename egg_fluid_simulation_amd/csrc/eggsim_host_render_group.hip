@@ -287,6 +287,20 @@ int group_draw_environment(GroupDraw *D, const GroupView &V, int which, egg_envi
     return rc;
 }
 
+// the two meshes of egg_get_instances over the group: the draw's gather, then the pack on the render device
+int group_draw_instances(GroupDraw *D, const GroupView &V, int which, egg_instance *data, float *color, int64_t cap, int64_t *n,
+                         std::string *error) {
+    egg_handle *rh = V.hs[0];
+    int rc = gather(D, V, which, kDrawFields, EGG_GATHER_FIELDS, "egg_group_get_instances", error);
+    if (rc != EGG_OK) return rc;
+    RenderSource::Type T;
+    fill_type(D, V, which, T, color != nullptr);
+    (void)hipSetDevice(rh->device);
+    rc = instances_from(rh, rh->sys[0].stream, T, "egg_group_get_instances", data, color, cap, n);  // (the gather's stream)
+    if (rc != EGG_OK) *error = rh->error;
+    return rc;
+}
+
 int group_draw_download(GroupDraw *D, const GroupView &V, int which, int field, double *dst, int64_t cap, std::string *error) {
     egg_handle *rh = V.hs[0];
     GroupDraw::Type &T = D->t[which];

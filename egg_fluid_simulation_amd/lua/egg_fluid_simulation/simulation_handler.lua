@@ -9,7 +9,8 @@
 ---   SimulationHandler(white_config, yolk_config), :add, :remove, :update, :set_target_position,
 ---   :get_target_position, :get_position, :set_white_config/:set_yolk_config, :get_*_config,
 ---   :list_ids, :get_n_particles, :set_white_color, :set_yolk_color.  In a LOVE host :draw stays with the reference's
----   own shaders: :get_instance_data() returns the instanced-draw record (x, y, last_x, last_y, vx, vy, radius) and
+---   own shaders: :instances() returns the data mesh and the colour mesh of a type as the reference's vertex format lays
+---   them out (packed on the device, one call per frame; :get_instance_data() is the older per-field form) and
 ---   :get_environment() what sizes and places the canvases.  Without a window, :render_to_image() runs the same
 ---   passes as HIP kernels (include/eggsim.h, "headless renderer") into a float32 RGBA buffer.
 
@@ -40,6 +41,12 @@ int egg_get_position(egg_handle *h, int64_t id, double *x, double *y);
 int egg_get_n_particles(const egg_handle *h, int64_t id, int64_t *n_white, int64_t *n_yolk);
 int egg_list_ids(const egg_handle *h, int64_t cap, int64_t *ids, int64_t *n);
 int egg_download_particles(egg_handle *h, int which, int field, double *dst, int64_t cap);
+typedef struct { float x, y, last_x, last_y, vx, vy, radius; } egg_instance;
+int egg_get_instances(egg_handle *h, int which, egg_instance *data, float *color, int64_t cap, int64_t *n,
+                      uint64_t *color_version);
+int egg_instances_begin(egg_handle *h, int32_t type_mask);
+int egg_instances_end(egg_handle *h, int which, const egg_instance **data, const float **color, int64_t *n,
+                      uint64_t *color_version);
 typedef struct { double min_x, min_y, max_x, max_y, centroid_x, centroid_y, max_radius, max_velocity,
                  last_centroid_x, last_centroid_y; } egg_environment;
 int egg_get_environment(egg_handle *h, int which, egg_environment *out);
@@ -347,6 +354,21 @@ function SimulationHandler:get_instance_data(white_or_yolk)
     return out, n
 end
 
+--- The reference's two per-particle meshes (simulation_handler.lua:513-523), packed on the device: returns
+--- data (const egg_instance*: x, y, last_x, last_y, vx, vy, radius as float, 28 bytes per particle = the data mesh's
+--- vertex format), color (const float*: rgba per particle = the colour mesh's), n and color_version, ready for
+--- love.data.newByteData(ffi.string(data, n * 28)) / mesh:setVertices.  The pointers are pinned buffers of the handle:
+--- valid until the second following :instances() of the same type.  color_version stands while no call changed a colour
+--- or the particle count: skip the colour upload while it does (simulation_handler.lua:519-520).
+function SimulationHandler:instances(white_or_yolk)
+    local which = white_or_yolk and 0 or 1
+    self:_check(lib.egg_instances_begin(self._h, which == 0 and 1 or 2))
+    local data, color = ffi.new("const egg_instance*[1]"), ffi.new("const float*[1]")
+    local n, version = ffi.new("int64_t[1]"), ffi.new("uint64_t[1]")
+    self:_check(lib.egg_instances_end(self._h, which, data, color, n, version))
+    return data[0], color[0], tonumber(n[0]), tonumber(version[0])
+end
+
 --- the fields the reference's environments hold for :draw(): particle AABB incl. radius, centroid, largest
 --- radius / speed, centroid at the start of the last step (simulation_handler.lua:1669-1718, 1795-1815,
 --- used at 1946-1950, 2007, 2132 to size and place the canvases)
@@ -360,7 +382,7 @@ function SimulationHandler:get_environment(white_or_yolk)
 end
 
 function SimulationHandler:draw()
-    -- in a LOVE host: feed :get_instance_data() and :get_environment() to the reference's shaders and canvas code
+    -- in a LOVE host: feed :instances() and :get_environment() to the reference's shaders and canvas code
     -- (simulation_handler.lua:1995-2175); without a window use :render_to_image()
 end
 

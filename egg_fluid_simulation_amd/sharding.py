@@ -385,7 +385,7 @@ class ShardedSimulationHandler(_HandlerSurface):
     other ranks have applied the call: the ranks then disagree, and the object is to be discarded.  Argument errors are
     raised on every rank before anything changes.
 
-    draw(), get_environment(), download(), download_instance_data() are COLLECTIVE (every rank calls them) and ANSWER
+    draw(), get_environment(), download(), download_instance_data(), instances() are COLLECTIVE (every rank calls them) and ANSWER
     ON THE RENDER RANK (`root`, rank 0 by default): the image / dict / array there, None on the other ranks;
     render_canvas() answers on the render rank without communication.  A refusal on any rank (a step in flight, a limit
     of DESIGN.md section 7 on the render rank) raises EggError on EVERY rank.
@@ -400,6 +400,9 @@ class ShardedSimulationHandler(_HandlerSurface):
     def __init__(self, layout, rank, group, make_handler, halo_px=64.0, interact_px=(8.0, 12.0), device=None, root=0):
         import torch
         self.torch, self.dist = torch, group
+        # instances(): counts the calls that can change a particle's colour or the particle count, as the library does per
+        # handle (egg_get_instances); replicated, since every rank makes the same calls
+        self._color_version = 1
         self.layout, self.rank, self.world = layout, int(rank), layout.world
         self.root = int(root)     # the render rank
         if not 0 <= self.root < self.world:
@@ -484,6 +487,7 @@ class ShardedSimulationHandler(_HandlerSurface):
         self._pcolor[gid] = pc
         self._budget_stale = True  # summed over the ranks before the next step
         self._keys_stale = True
+        self._color_version += 1
         return gid
 
     def remove(self, batch_id):  # L:140-155
@@ -500,6 +504,7 @@ class ShardedSimulationHandler(_HandlerSurface):
             table.pop(gid, None)
         self._budget_stale = True
         self._keys_stale = True
+        self._color_version += 1
 
     def list_ids(self):  # L:399-405
         return sorted(self.owner)
@@ -558,9 +563,10 @@ class ShardedSimulationHandler(_HandlerSurface):
             self._rcfg[which] = c
             for own in self._own_color.values():  # config.color is a new table now (L:1307-1311)
                 own[which] = True
+        self._color_version += 1
 
     def _apply_render_flags(self):
-        pass  # (the switches are read at add and at draw)
+        self._color_version += 1  # (the switches themselves are read at add and at draw)
 
     def _message(self):  # (_check of a library call that takes no handle)
         return self._lib.egg_last_error(None).decode()
@@ -572,6 +578,7 @@ class ShardedSimulationHandler(_HandlerSurface):
         self._pcolor[gid][which] = c
         if not self._own_color[gid][which]:  # the shared table (L:49-50, L:349-350)
             self._rcfg[which].color[:] = [float(v) for v in c]
+        self._color_version += 1
 
     @property
     def elapsed(self):
@@ -980,6 +987,13 @@ class ShardedSimulationHandler(_HandlerSurface):
             cols = [self.local.draw_source_download(which, f, total) for f in _ffi.DRAW_FIELDS]
             return np.stack(cols, axis=1) if total else np.zeros((0, 7))
         return self._collective((which,), on_root)
+
+    def instances(self, which, color=True):
+        """SimulationHandler.instances over the sharded scene: ONE gather, then the pack on the render rank's device
+        (egg_draw_source_instances).  Collective; (data, color, color_version) on the render rank, None elsewhere."""
+        total = int(self._key_table()[:, 1 + which].sum())
+        out = self._collective((which,), lambda: self.local.draw_source_instances(which, total, color))
+        return None if out is None else (out[0], out[1], self._color_version)
 
     # ------------------------------------------------------------ internals
     def _bounds(self):

@@ -454,6 +454,21 @@ class _HandlerSurface:
         cols = [self.download(which, f) for f in ("x", "y", "last_x", "last_y", "vx", "vy", "radius")]
         return np.stack(cols, axis=1) if cols[0].size else np.zeros((0, 7))
 
+    def instances(self, which, color=True):
+        """The reference's two per-particle meshes of type `which`, packed on the device (egg_get_instances, L:513-523):
+        (data, color, color_version) -- data (n, 7) float32 with the columns of download_instance_data, each value its
+        double rounded to nearest even; color (n, 4) float32 rgba, the colour the splat of draw() reads for the particle
+        (None with color=False); color_version an int that goes up whenever a call that can change a colour or the
+        particle count succeeds and stands still over update(): skip the colour upload while it stands."""
+        w, y = self.get_n_particles()
+        n = w if which == _ffi.WHITE else y
+        data = np.empty((n, 7), dtype=np.float32)
+        col = np.empty((n, 4), dtype=np.float32) if color else None
+        got, version = C.c_int64(), C.c_uint64()
+        self._check(self._c("get_instances")(int(which), data.ctypes.data_as(C.c_void_p),
+                                              col.ctypes.data_as(C.c_void_p) if color else None, n, C.byref(got), C.byref(version)))
+        return data, col, int(version.value)
+
     def get_environment(self, which):
         """the reductions the reference keeps per particle type for :draw() -- AABB incl. radius, centroid, largest
         radius and speed, centroid at the start of the last step (simulation_handler.lua:1669-1718, 1795-1815)"""
@@ -653,6 +668,51 @@ class SimulationHandler(_HandlerSurface):
         out = np.empty(int(n), dtype=np.float64)
         self._check(self._lib.egg_draw_source_download(self._h, int(which), _ffi.FIELD_ID[field], out.ctypes.data, int(n)))
         return out
+
+    def draw_source_instances(self, which, n, color=True):
+        """the two meshes of instances() over the placed particles: ((n, 7) float32, (n, 4) float32 or None)"""
+        data = np.empty((int(n), 7), dtype=np.float32)
+        col = np.empty((int(n), 4), dtype=np.float32) if color else None
+        got = C.c_int64()
+        self._check(self._lib.egg_draw_source_instances(self._h, int(which), data.ctypes.data_as(C.c_void_p),
+                                                        col.ctypes.data_as(C.c_void_p) if color else None, int(n), C.byref(got)))
+        return data, col
+
+    # ------------------------------------------- the instanced-draw record in two halves (egg_instances_begin / _end)
+    def instances_to(self, which, data_ptr, color_ptr, cap):
+        """instances() into caller-owned buffers given by ADDRESS (host memory or memory of this handle's device, e.g.
+        torch.Tensor.data_ptr(); 0 skips a mesh); returns (n, color_version).  Complete when this returns."""
+        got, version = C.c_int64(), C.c_uint64()
+        self._check(self._lib.egg_get_instances(self._h, int(which), C.c_void_p(int(data_ptr)) if data_ptr else None,
+                                                C.c_void_p(int(color_ptr)) if color_ptr else None, int(cap), C.byref(got),
+                                                C.byref(version)))
+        return got.value, int(version.value)
+
+    def instances_begin(self, types=(0, 1)):
+        """Launch the pack of instances() for `types` and the copy into pinned buffers the handle owns; returns at once.
+        The host draws, or starts the next update(), meanwhile: later work of the handle runs behind the pack on the
+        device.  Every type of `types` is fetched with instances_end before the next instances_begin."""
+        mask = 0
+        for w in types:
+            mask |= 1 << int(w)
+        self._check(self._lib.egg_instances_begin(self._h, mask))
+
+    def instances_end(self, which):
+        """Wait for instances_begin's copy of `which`: (data, color, color_version) as instances() returns them, but as
+        numpy VIEWS of the handle's pinned buffers (read-only, nothing is copied).  Lifetime: two buffers alternate, so
+        a view stays valid until the SECOND following instances_begin, and no longer than the handler itself; copy what
+        must live longer.  While color_version stands the colour mesh is not packed again and `color` is a view of the
+        last one."""
+        d, c, n, version = C.c_void_p(), C.c_void_p(), C.c_int64(), C.c_uint64()
+        self._check(self._lib.egg_instances_end(self._h, int(which), C.byref(d), C.byref(c), C.byref(n), C.byref(version)))
+
+        def view(ptr, cols):
+            if n.value == 0 or not ptr.value:
+                return np.zeros((0, cols), dtype=np.float32)
+            a = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_float)), shape=(n.value, cols))
+            a.flags.writeable = False
+            return a
+        return view(d, 7), view(c, 4), int(version.value)
 
     # ---------------------------------------------------------- device access
     def synchronize(self):

@@ -179,6 +179,40 @@ enum {
  * record (L:513-517, L:744-813). */
 int egg_download_particles(egg_handle *h, int which, int field, double *dst, int64_t cap);
 
+/* ---- the instanced-draw record, packed on the device (csrc/eggsim_instances.hip) ----
+ * The reference uploads two per-particle meshes every frame (L:513-523, L:744-877): the data mesh -- floatvec4
+ * (x, y, last_x, last_y), floatvec2 (vx, vy), float radius: egg_instance below -- and the colour mesh, floatvec4 rgba,
+ * which it re-uploads only when colours change (L:519-520).  These entry points hand a host both meshes as its vertex
+ * format lays them out, ready for love.data / mesh:setVertices: one kernel launch per type packs them on the device.
+ * Each float is the round-to-nearest-even narrowing of the double egg_download_particles returns for that field;
+ * particles are in particle-index order; nothing is interpolated (the reference's shader does that, L:2057-2058).  A
+ * particle's colour is the rgba the splat of egg_render reads for it (L:978-990, L:1110-1129, the shared config table of
+ * L:49-50 included).  color_version goes up whenever a call that can change any particle's colour or the particle count
+ * succeeds (egg_set_color, egg_set_add_color, egg_set_render_flags, egg_set_render_config, egg_add*, egg_remove,
+ * egg_import_batch) and stands still otherwise: a host skips its colour upload while the version stands. */
+typedef struct { float x, y, last_x, last_y, vx, vy, radius; } egg_instance;   /* 28 B, L:513-517 */
+
+/* synchronous: data[n] and, when color != NULL, color[4 n]; *n = particle count of `which`; dst host or device memory */
+int egg_get_instances(egg_handle *h, int which, egg_instance *data, float *color, int64_t cap, int64_t *n,
+                      uint64_t *color_version);
+/* two halves: begin launches the pack and the copy into pinned buffers the handle owns and returns at once;
+ * end waits for that and hands out the pointers, valid until the second following begin (two buffers alternate) */
+int egg_instances_begin(egg_handle *h, int32_t type_mask);
+int egg_instances_end(egg_handle *h, int which, const egg_instance **data, const float **color, int64_t *n,
+                      uint64_t *color_version);
+/* Details of the three calls above.  cap: particles `data` (and `color`) have room for; smaller than the particle count is
+ * EGG_ERR_INVALID_ARGUMENT, nothing is written.  Zero particles is valid (*n = 0).  data may be NULL (colour only), n and
+ * color_version may be NULL.  Before the first _step last_x / last_y are whatever egg_download_particles returns then.
+ * type_mask: bit EGG_WHITE and / or bit EGG_YOLK (1, 2 or 3); egg_instances_end is called once per type of the mask, in
+ * any order, and the begin is closed when every type of the mask has been handed out.  The handle skips its own colour
+ * pack and copy while color_version stands: *color then points at the last one.  Later work of the handle (a _step, an
+ * add, a remove) may be started between begin and end: what it enqueues on the handle's streams runs behind the pack, and
+ * the pack reads the particle arrays and tables of its own only, nothing the host rewrites.  egg_instances_end itself only
+ * waits and is never refused.  Refused while a step is in
+ * flight (egg_step_begin or egg_rx_begin open), like egg_draw_pack; egg_instances_begin and egg_get_instances also while
+ * a begin is open.  (egg_group_get_instances and egg_draw_source_instances, below, are the same pack over a device group
+ * and over a scene sharded over processes.) */
+
 /* The per-type reductions the reference's _post_solve / update_last_positions keep in its environment
  * (L:1669-1718, L:1795-1815) -- what :draw() sizes and places its canvases with (L:1946-1950, L:2007,
  * L:2132).  Computed on demand from the device arrays, bounds and maxima in parallel, the centroid sums
@@ -410,6 +444,12 @@ int egg_group_render(egg_group *g, const egg_render_params *p, float *rgba);
 /* the density canvas of `which` as the last egg_group_render left it (egg_render_canvas) */
 int egg_group_render_canvas(egg_group *g, int which, float *rgba, int64_t cap_pixels, int32_t *w, int32_t *hgt, double *x0,
                             double *y0);
+/* egg_get_instances over the group (the two meshes of L:513-523): the gather of egg_group_render, then the pack on the
+ * device of handle 0, particles in global-key order; data and colour equal one handle's, bit for bit.  color_version is
+ * the group's: it goes up with egg_group_add / _remove / _set_color / _set_add_color / _set_render_flags /
+ * _set_render_config, not with hand-overs. */
+int egg_group_get_instances(egg_group *g, int which, egg_instance *data, float *color, int64_t cap, int64_t *n,
+                            uint64_t *color_version);
 
 /* ---- relaxed order over several PROCESSES (csrc/eggsim_host_relaxed_wire.hip) -------------
  * One relaxed _step of ONE handle, driven pass by pass by a host that moves the ghost halo itself (one process per GPU:
@@ -507,6 +547,10 @@ int egg_draw_source_render_canvas(egg_handle *h, int which, float *rgba, int64_t
 int egg_draw_source_environment(egg_handle *h, int which, int32_t stepped, egg_environment *out);
 /* egg_download_particles over the placed particles: `field` is one of the seven draw fields (EGG_FIELD_*) */
 int egg_draw_source_download(egg_handle *h, int which, int field, double *dst, int64_t cap);
+/* egg_get_instances over the placed particles (the two meshes of L:513-523), colours from the layout's atom_color; the
+ * colour version is the caller's: the sharded scene owns the colours.  It reads the shadow arrays, not the handle's own:
+ * like egg_draw_source_download it is not refused while a step of the handle is in flight. */
+int egg_draw_source_instances(egg_handle *h, int which, egg_instance *data, float *color, int64_t cap, int64_t *n);
 
 #ifdef __cplusplus
 }
