@@ -327,6 +327,30 @@ struct EggRxUnpackArgs {  // receiver side: pulls every sender's records for it 
     const unsigned long long *count[EGG_RX_MAX_GROUP];
 };
 
+#if defined(__HIPCC__)
+// What the kernels of eggsim_relaxed.hip and eggsim_relaxed_wire.hip share.
+// cell of a position; false, and cell (0, 0), for a NaN coordinate or a cell outside +-2^30
+static __device__ __forceinline__ bool rx_cell(double2 p, double cell, int32_t &cx, int32_t &cy) {
+    const double fx = floor(p.x / cell), fy = floor(p.y / cell);
+    const bool ok = fx >= -0x1p30 && fx <= 0x1p30 && fy >= -0x1p30 && fy <= 0x1p30;
+    cx = ok ? (int32_t)fx : 0;
+    cy = ok ? (int32_t)fy : 0;
+    return ok;
+}
+
+// Wave-aggregated append: the lanes with `take` get consecutive slots of *counter; returns this lane's slot.
+static __device__ __forceinline__ int rx_append(unsigned long long *counter, bool take) {
+    const unsigned long long mask = __ballot(take);
+    if (!mask) return 0;
+    const int lane = (int)(threadIdx.x & 63);
+    const int leader = __ffsll((long long)mask) - 1;
+    unsigned long long base = 0;
+    if (lane == leader) base = atomicAdd(counter, (unsigned long long)__popcll(mask));
+    base = __shfl(base, leader, 64);
+    return (int)base + __popcll(mask & ((1ull << lane) - 1ull));
+}
+#endif
+
 // Several processes ("Several processes"; eggsim_relaxed_wire.hip): the same halo when the
 // other handles live in other processes.  Nothing of another handle is addressable: the destinations' boxes arrive
 // as a small array in the sender's own memory, and the ghosts travel as MESSAGES -- word 0 the record count, then

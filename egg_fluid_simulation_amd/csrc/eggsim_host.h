@@ -7,9 +7,10 @@
 //   eggsim_host_step.hip    _step: environment scalars, kernel launches, validation / re-run / commit
 //   eggsim_host_abi.hip     the extern "C" entry points of include/eggsim.h (except the renderer's)
 //   eggsim_host_render.hip  egg_render* : the headless renderer's host side
-//   eggsim_host_relaxed.hip _step in relaxed order (EGG_OPT_SOLVER_ORDER = 1): the launches of eggsim_relaxed.hip
-//   eggsim_host_relaxed_group.hip  the same step over the handles of a device group, with per-pass ghost halos
-//   eggsim_host_relaxed_wire.hip   the same step driven pass by pass through the C ABI (egg_rx_*): one handle per process
+//   eggsim_host_relaxed.hip _step in relaxed order (EGG_OPT_SOLVER_ORDER = 1): the driver of one (handle, type) -- every
+//                           launch of eggsim_relaxed.hip's pass -- and the single handle's step built from it
+//   eggsim_host_relaxed_group.hip  that driver over the handles of a device group: the events and peer pack / unpack between passes
+//   eggsim_host_relaxed_wire.hip   that driver cut into the C ABI's egg_rx_* calls: one handle per process, the host carries the halo
 //   eggsim_host_render_group.hip   draw / environment / download of a device group: gather to one device (eggsim_render_group.hip)
 //   eggsim_host_draw_source.hip    the same for a scene sharded over processes: egg_draw_pack on every rank, egg_draw_source_* on one
 //   eggsim_host_instances.hip      egg_get_instances / egg_instances_begin / _end: the instanced-draw record packed on the device
@@ -23,6 +24,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <limits>
 #include <memory>
 #include <numeric>
@@ -515,13 +517,44 @@ int do_step(egg_handle *h, double delta, int S, int C, int phase = kWhole);  // 
 // the step's config scalars of type w: mass / radius re-derived after a config change (L:1731-1744, L:1420-1430)
 int follow_config(egg_handle *h, int w, bool launch);
 
-// eggsim_host_relaxed.hip
+// eggsim_host_relaxed.hip: a relaxed step of one (handle, type), written once; relaxed_step, relaxed_group_step and the
+// egg_rx_* entry points are built from it and agree bit for bit.
+constexpr int64_t kRelaxedMaxParticles = (int64_t)1 << 29;  // of one type, over everything that shares a step
+#define EGG_RX_TOO_MANY_TEXT "relaxed order: more than 2^29 particles of one type"
+constexpr char kRelaxedBadCellText[] = "relaxed order: a position is NaN or its spatial-hash cell lies outside +-2^30";
+// Status words of one type: [0] bad cell, [1 + p] pairs of pass p (P = S C passes); with a halo besides, per pass, the
+// cell box of its positions, the ghost entries received and -- device groups, nq handles holding the type -- the
+// records sent to each of them.
+struct RelaxedLayout {
+    size_t P = 0, nq = 0;
+    bool halo = false;  // ghosts of other handles' particles take part: the group instantiations of the kernels
+    size_t box(size_t p) const { return 1 + P + 4 * p; }                      // 4 words
+    size_t ghosts(size_t p) const { return 1 + 5 * P + p; }
+    size_t sent(size_t p, size_t m) const { return 1 + 6 * P + p * nq + m; }  // to participant m
+    size_t words() const { return halo ? 1 + 6 * P + P * nq : 1 + P; }
+};
+struct RelaxedStep {  // one type of one handle in a relaxed step
+    egg_handle *h = nullptr;
+    int w = 0, C = 0;
+    Env env{};
+    RelaxedLayout L;
+    EggRelaxedGroupArgs A{};  // (A.g stays null without a halo)
+    int64_t ghost_cap = 0;    // a pass runs over n + ghost_cap entries
+    int launches = 0;         // kernel launches so far: into the statistics at the commit
+};
+// key base of a local atom (batch key, particle count) into *base: EGG_OK, or the status it failed the handle with
+using KeyBaseFn = std::function<int(int64_t, int64_t, int32_t *)>;
+int prepare_step(egg_handle *h, double delta, int S, RelaxedStep st[2]);
+int prepare_type(RelaxedStep &st, int C, size_t ghosts, const RelaxedLayout &L, const std::vector<uint64_t> &sig,
+                 const KeyBaseFn &base_of);
+int launch_substep(RelaxedStep &st, int sub);
+int launch_pass(RelaxedStep &st, int p);
+int read_status(RelaxedStep &st);
+bool bad_cell(const RelaxedStep &st);
+int launch_end(RelaxedStep &st);
+void relaxed_commit(egg_handle *h, const RelaxedStep st[2], int S, int C, double ms);
 int relaxed_step(egg_handle *h, double delta, int S, int C);
 void leave_relaxed(egg_handle *h);  // back to exact order: the next exact step re-tiles from the current positions
-int reserve_relaxed(egg_handle *h, System &s, int S, int C, size_t ghosts, size_t words);
-int upload_relaxed_targets(egg_handle *h, System &s);
-EggRelaxedArgs relaxed_args(egg_handle *h, int w, const Env &env);
-void relaxed_commit(egg_handle *h, const Env env[2], int S, int C, double ms);
 
 // eggsim_host_relaxed_group.hip: the relaxed step of a device group (called by eggsim_group.cpp, which declares them
 // itself: it sees only include/eggsim.h).  0 or an EGG_ERR_* code; on failure *error names the device and the reason.

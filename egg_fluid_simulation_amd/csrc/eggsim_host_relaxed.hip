@@ -3,15 +3,25 @@
 // every collision pass is a Jacobi pass over a cell table built fresh from the pass's positions.  The double-buffer
 // contract is the exact path's: the step reads x / y / vx / vy[cur], writes the end-of-step state into [cur ^ 1], and
 // the commit flips cur.  See eggsim_host.h.
+//
+// The DRIVER of a relaxed step of one (handle, type) lives here, once: RelaxedStep (eggsim_host.h) with prepare_step,
+// prepare_type, launch_substep, launch_pass, read_status, launch_end and relaxed_commit.  Three paths are built from it:
+//   relaxed_step (below)                                one handle, everything enqueued in one go
+//   relaxed_group_step (eggsim_host_relaxed_group.hip)  the handles of a device group; adds the peer halo between passes
+//   egg_rx_* (eggsim_host_relaxed_wire.hip)             one handle per process; the host carries the halo between calls
+// With a halo (RelaxedLayout::halo) the entries of a pass are the local particles plus ghosts and the kernels are the
+// group instantiations; without, the plain ones.  Nothing else differs, and the three paths agree bit for bit.
 #include <hipcub/hipcub.hpp>
 
 #include "eggsim_host.h"
 
 namespace egghost {
 
-// buffers of one type for n particles and `ghosts` ghost entries (device groups); the cell table has at least
-// 2 (n + ghosts) slots (a probe always finds a free one); `words` status words (0: the single handle's 1 + S C)
-int reserve_relaxed(egg_handle *h, System &s, int S, int C, size_t ghosts, size_t words) {
+namespace {
+
+// buffers of one type for n particles and `ghosts` ghost entries; the cell table has at least 2 (n + ghosts) slots (a
+// probe always finds a free one); `words` status words
+int reserve_relaxed(egg_handle *h, System &s, size_t ghosts, size_t words) {
     RelaxedBufs &r = s.rx;
     const size_t n = (size_t)s.n, ne = n + ghosts;
     uint32_t table = 1024;
@@ -36,7 +46,6 @@ int reserve_relaxed(egg_handle *h, System &s, int S, int C, size_t ghosts, size_
         r.scan_bytes = bytes;
         r.table = table;
     }
-    if (!words) words = 1 + (size_t)S * C;
     HIP_TRY(h, r.status.reserve(words, false, s.stream));
     HIP_TRY(h, r.h_status.reserve(words));
     return EGG_OK;
@@ -70,7 +79,7 @@ int upload_relaxed_targets(egg_handle *h, System &s) {
     return EGG_OK;
 }
 
-// the kernels' arguments for one type's step (the group fields null: a single handle)
+// the kernels' arguments for one type's step
 EggRelaxedArgs relaxed_args(egg_handle *h, int w, const Env &env) {
     System &s = h->sys[w];
     RelaxedBufs &r = s.rx;
@@ -117,69 +126,161 @@ EggRelaxedArgs relaxed_args(egg_handle *h, int w, const Env &env) {
     return A;
 }
 
-namespace {
+}  // namespace
 
-// every launch of one type's step on its stream
-int launch_relaxed(egg_handle *h, int w, const Env &env, int S, int C, int *launches) {
-    System &s = h->sys[w];
-    RelaxedBufs &r = s.rx;
-    const int n = (int)s.n;
-    EggRelaxedArgs A = relaxed_args(h, w, env);
-    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    int k = 0;
-    HIP_TRY(h, hipMemsetAsync(r.status.p, 0, (1 + (size_t)S * C) * 8, s.stream));
-    for (int sub = 0; sub < S; ++sub) {
-        hipLaunchKernelGGL(sub == 0 ? egg_rx_begin_kernel : egg_rx_mid_kernel, grid, block, 0, s.stream, A);
-        ++k;
-        for (int c = 0; c < C; ++c) {
-            A.pass = sub * C + c;
-            HIP_TRY(h, hipMemsetAsync(r.hkey.p, 0xFF, (size_t)r.table * 8, s.stream));
-            HIP_TRY(h, hipMemsetAsync(r.hcount.p, 0, ((size_t)r.table + 1) * 4, s.stream));
-            hipLaunchKernelGGL(egg_rx_insert_kernel, grid, block, 0, s.stream, A);
-            size_t bytes = r.scan_bytes;
-            HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(r.scan_tmp.p, bytes, r.hcount.p, r.hstart.p, (int)r.table + 1, s.stream));
-            hipLaunchKernelGGL(egg_rx_scatter_kernel, grid, block, 0, s.stream, A);
-            hipLaunchKernelGGL(egg_rx_rank_kernel, grid, block, 0, s.stream, A);
-            hipLaunchKernelGGL(egg_rx_gather_kernel, grid, block, 0, s.stream, A);
-            k += 5;
-            std::swap(A.pos, A.pos_next);  // Jacobi: the next pass starts from this one's result
-        }
+// per step: the environment scalars of both types (a type without particles has them too: the commit reports its
+// budget), config changes and the atoms
+int prepare_step(egg_handle *h, double delta, int S, RelaxedStep st[2]) {
+    const double sub_delta = std::max(delta / S, h->sys[0].cfg.eps);
+    for (int w = 0; w < 2; ++w) {
+        System &s = h->sys[w];
+        st[w] = RelaxedStep{};
+        st[w].h = h;
+        st[w].w = w;
+        st[w].env = make_env(s.cfg, sub_delta, h->budget_particles[w] >= 0 ? h->budget_particles[w] : s.n);
+        int rc = follow_config(h, w, true);
+        if (rc == EGG_OK) rc = upload_atoms(h, w);
+        if (rc != EGG_OK) return rc;
     }
-    hipLaunchKernelGGL(egg_rx_end_kernel, grid, block, 0, s.stream, A);
-    ++k;
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(r.h_status.p, r.status.p, (1 + (size_t)S * C) * 8, hipMemcpyDeviceToHost, s.stream));
-    *launches += k;
     return EGG_OK;
 }
 
-}  // namespace
+// per populated type: buffers for the local particles + `ghosts` ghost entries, targets, kernel arguments.  With a halo
+// every entry has a global key: the keys of the local particles are rebuilt when `sig` (whatever the keys depend on)
+// differs from the one they were built for, from the key base base_of gives for every local atom (EGG_OK, or the
+// status it failed the handle with).
+int prepare_type(RelaxedStep &st, int C, size_t ghosts, const RelaxedLayout &L, const std::vector<uint64_t> &sig,
+                 const KeyBaseFn &base_of) {
+    egg_handle *h = st.h;
+    System &s = h->sys[st.w];
+    RelaxedBufs &r = s.rx;
+    const size_t n = (size_t)s.n;
+    st.L = L;
+    st.C = C;
+    st.ghost_cap = (int64_t)ghosts;
+    int rc = reserve_relaxed(h, s, ghosts, L.words());
+    if (rc == EGG_OK) rc = upload_relaxed_targets(h, s);
+    if (rc != EGG_OK) return rc;
+    st.A.a = relaxed_args(h, st.w, st.env);
+    st.A.g = EggRxGroupFields{};
+    if (!L.halo) return EGG_OK;
+    const bool rebuild = r.key_sig != sig || r.ekey.cap < n + ghosts;  // (or a new array)
+    HIP_TRY(h, r.ekey.reserve(n + ghosts, false, s.stream));
+    HIP_TRY(h, r.sloc.reserve(n + ghosts, false, s.stream));
+    HIP_TRY(h, r.gwr.reserve(std::max<size_t>(ghosts, 1), false, s.stream));
+    if (rebuild) {
+        // a batch's particles are consecutive in key order, as they are in the handle: key = base + place in the atom
+        const size_t na = s.atoms.size();
+        std::vector<int32_t> ab(na + 1, 0);
+        for (size_t a = 0; a < na; ++a) {
+            rc = base_of(h->batches[(size_t)s.atoms[a].batch].key, s.atoms[a].count, &ab[a]);
+            if (rc != EGG_OK) return rc;
+        }
+        HIP_TRY(h, r.abase.reserve(na + 1, false, s.stream));
+        HIP_TRY(h, hipMemcpyAsync(r.abase.p, ab.data(), (na + 1) * 4, hipMemcpyHostToDevice, s.stream));
+        hipLaunchKernelGGL(egg_rx_gkey_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s.stream, r.p_atom.p,
+                           s.d_atom_offset.p, r.abase.p, (int)n, r.ekey.p);
+        ++st.launches;
+        HIP_TRY(h, hipStreamSynchronize(s.stream));  // (ab is pageable host memory; membership changes only)
+        r.key_sig = sig;
+    }
+    st.A.g.ekey = r.ekey.p;
+    st.A.g.sloc = r.sloc.p;
+    st.A.g.gwr = r.gwr.p;
+    return EGG_OK;
+}
+
+// sub-step `sub` begins: pre-solve and follow into the positions of its first pass (and their cell box, with a halo).
+// The step's status words start at zero.
+int launch_substep(RelaxedStep &st, int sub) {
+    System &s = st.h->sys[st.w];
+    const dim3 grid((unsigned)((s.n + 255) / 256)), block(256);
+    if (sub == 0) HIP_TRY(st.h, hipMemsetAsync(s.rx.status.p, 0, st.L.words() * 8, s.stream));
+    if (st.L.halo) {
+        st.A.g.box = s.rx.status.p + st.L.box((size_t)sub * st.C);
+        hipLaunchKernelGGL(sub == 0 ? egg_rx_begin_group_kernel : egg_rx_mid_group_kernel, grid, block, 0, s.stream, st.A);
+    } else {
+        hipLaunchKernelGGL(sub == 0 ? egg_rx_begin_kernel : egg_rx_mid_kernel, grid, block, 0, s.stream, st.A.a);
+    }
+    ++st.launches;
+    return EGG_OK;
+}
+
+// collision pass p over the entries: cell table, grouping, the Jacobi gather.  With a halo the ghosts of the pass are in
+// place behind the local positions (their count in the status words), and the gather records the cell box of the
+// positions it writes for the next pass of the sub-step (the next sub-step's is recorded by its mid kernel).
+int launch_pass(RelaxedStep &st, int p) {
+    egg_handle *h = st.h;
+    System &s = h->sys[st.w];
+    RelaxedBufs &r = s.rx;
+    EggRelaxedGroupArgs &a = st.A;
+    a.a.pass = p;
+    if (st.L.halo) {
+        a.g.n_ghost = r.status.p + st.L.ghosts((size_t)p);
+        a.g.box = p % st.C + 1 < st.C ? r.status.p + st.L.box((size_t)p + 1) : nullptr;
+    }
+    const dim3 grid((unsigned)((s.n + st.ghost_cap + 255) / 256)), block(256);  // (the ghost count is read on the device)
+    HIP_TRY(h, hipMemsetAsync(r.hkey.p, 0xFF, (size_t)r.table * 8, s.stream));
+    HIP_TRY(h, hipMemsetAsync(r.hcount.p, 0, ((size_t)r.table + 1) * 4, s.stream));
+    if (st.L.halo)
+        hipLaunchKernelGGL(egg_rx_insert_group_kernel, grid, block, 0, s.stream, a);
+    else
+        hipLaunchKernelGGL(egg_rx_insert_kernel, grid, block, 0, s.stream, a.a);
+    size_t bytes = r.scan_bytes;
+    HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(r.scan_tmp.p, bytes, r.hcount.p, r.hstart.p, (int)r.table + 1, s.stream));
+    if (st.L.halo) {
+        hipLaunchKernelGGL(egg_rx_scatter_group_kernel, grid, block, 0, s.stream, a);
+        hipLaunchKernelGGL(egg_rx_rank_group_kernel, grid, block, 0, s.stream, a);
+        hipLaunchKernelGGL(egg_rx_gather_group_kernel, grid, block, 0, s.stream, a);
+    } else {
+        hipLaunchKernelGGL(egg_rx_scatter_kernel, grid, block, 0, s.stream, a.a);
+        hipLaunchKernelGGL(egg_rx_rank_kernel, grid, block, 0, s.stream, a.a);
+        hipLaunchKernelGGL(egg_rx_gather_kernel, grid, block, 0, s.stream, a.a);
+    }
+    st.launches += 5;
+    std::swap(a.a.pos, a.a.pos_next);  // Jacobi: the next pass starts from this one's result
+    return EGG_OK;
+}
+
+// the status words on their way to h_status; bad_cell() reads them once the stream has been waited for
+int read_status(RelaxedStep &st) {
+    System &s = st.h->sys[st.w];
+    HIP_TRY(st.h, hipGetLastError());
+    HIP_TRY(st.h, hipMemcpyAsync(s.rx.h_status.p, s.rx.status.p, st.L.words() * 8, hipMemcpyDeviceToHost, s.stream));
+    return EGG_OK;
+}
+
+bool bad_cell(const RelaxedStep &st) { return st.h->sys[st.w].rx.h_status.p[0] != 0; }
+
+// post-solve: the end-of-step state into [cur ^ 1]
+int launch_end(RelaxedStep &st) {
+    System &s = st.h->sys[st.w];
+    hipLaunchKernelGGL(egg_rx_end_kernel, dim3((unsigned)((s.n + 255) / 256)), dim3(256), 0, s.stream, st.A.a);
+    ++st.launches;
+    HIP_TRY(st.h, hipGetLastError());
+    return EGG_OK;
+}
 
 int relaxed_step(egg_handle *h, double delta, int S, int C) {  // L:1722-1989, collision passes relaxed
-    const double sub_delta = std::max(delta / S, h->sys[0].cfg.eps);
-    Env env[2];
-    for (int w = 0; w < 2; ++w) {
-        System &s = h->sys[w];
-        env[w] = make_env(s.cfg, sub_delta, h->budget_particles[w] >= 0 ? h->budget_particles[w] : s.n);
-        int rc = follow_config(h, w, true);
-        if (rc != EGG_OK) return rc;
-        rc = upload_atoms(h, w);
-        if (rc != EGG_OK) return rc;
-    }
-    int launches = 0;
+    RelaxedStep st[2];
+    int rc = prepare_step(h, delta, S, st);
+    if (rc != EGG_OK) return rc;
     for (int w = 0; w < 2; ++w) {
         System &s = h->sys[w];
         if (s.n == 0) continue;
-        if (s.n > (int64_t)(1 << 29)) return fail(h, EGG_ERR_UNSUPPORTED, "relaxed order: more than 2^29 particles of one type");
-        int rc = reserve_relaxed(h, s, S, C, 0, 0);
-        if (rc == EGG_OK) rc = upload_relaxed_targets(h, s);
+        if (s.n > kRelaxedMaxParticles) return fail(h, EGG_ERR_UNSUPPORTED, EGG_RX_TOO_MANY_TEXT);
+        rc = prepare_type(st[w], C, 0, RelaxedLayout{(size_t)S * C, 0, false}, {}, nullptr);
         if (rc != EGG_OK) return rc;
         if (h->opt_timing) HIP_TRY(h, hipEventRecord(s.ev0, s.stream));
-        rc = launch_relaxed(h, w, env[w], S, C, &launches);
+        for (int sub = 0; sub < S && rc == EGG_OK; ++sub) {
+            rc = launch_substep(st[w], sub);
+            for (int c = 0; c < C && rc == EGG_OK; ++c) rc = launch_pass(st[w], sub * C + c);
+        }
+        if (rc == EGG_OK) rc = launch_end(st[w]);
+        if (rc == EGG_OK) rc = read_status(st[w]);
         if (rc != EGG_OK) return rc;
         if (h->opt_timing) HIP_TRY(h, hipEventRecord(s.ev1, s.stream));
     }
-    h->stats.kernel_launches += launches;
     double ms = 0;
     bool bad = false;
     for (int w = 0; w < 2; ++w) {
@@ -192,19 +293,22 @@ int relaxed_step(egg_handle *h, double delta, int S, int C) {  // L:1722-1989, c
             h->stats.kernel_ms[w] = (double)t;
             ms = std::max(ms, (double)t);
         }
-        bad |= s.rx.h_status.p[0] != 0;
+        bad |= bad_cell(st[w]);
     }
-    if (bad)  // nothing is committed: [cur] still holds the state before the step
-        return fail(h, EGG_ERR_UNSUPPORTED, "relaxed order: a position is NaN or its spatial-hash cell lies outside +-2^30");
-    relaxed_commit(h, env, S, C, ms);
+    if (bad) {  // nothing is committed: [cur] still holds the state before the step
+        h->stats.kernel_launches += st[0].launches + st[1].launches;
+        return fail(h, EGG_ERR_UNSUPPORTED, "%s", kRelaxedBadCellText);
+    }
+    relaxed_commit(h, st, S, C, ms);
     return EGG_OK;
 }
 
 // the commit of a relaxed step whose end kernels have run: flip cur, statistics from the status words read back
-void relaxed_commit(egg_handle *h, const Env env[2], int S, int C, double ms) {
+void relaxed_commit(egg_handle *h, const RelaxedStep st[2], int S, int C, double ms) {
     for (int w = 0; w < 2; ++w) {
         System &s = h->sys[w];
-        h->stats.budget[w] = env[w].budget;
+        h->stats.kernel_launches += st[w].launches;
+        h->stats.budget[w] = st[w].env.budget;
         h->stats.max_pass_visits[w] = 0;
         if (!h->opt_timing || s.n == 0) h->stats.kernel_ms[w] = 0;
         if (s.n == 0) continue;

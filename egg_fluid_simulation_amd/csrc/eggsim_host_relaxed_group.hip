@@ -1,6 +1,7 @@
 // eggsim_host_relaxed_group.hip -- one relaxed-order _step over the handles of a device group
 // (eggsim_group.cpp), with a per-pass ghost halo instead of hand-overs.  The results equal one relaxed handle holding
-// every batch, bit for bit.
+// every batch, bit for bit.  The step of each (handle, type) is the driver of eggsim_host_relaxed.hip (RelaxedStep);
+// what is written here is what a group adds: the global keys, the events and the peer pack / unpack between passes.
 //
 // Per particle type and collision pass p, on every handle k that holds particles of the type:
 //   * the kernel that wrote the positions of pass p (egg_rx_begin / mid, or the gather of pass p - 1) recorded their
@@ -16,22 +17,17 @@
 //
 // The step commits on every handle or on none: the status words of all handles come back after the passes (one host
 // synchronise), and the end kernels that write [cur ^ 1] run only if no handle flagged a bad cell.
-#include <hipcub/hipcub.hpp>
-
 #include "eggsim_host.h"
 
 namespace egghost {
 
 namespace {
 
-// status words of one type in a group step: P = S C passes, nq handles holding the type
-struct Layout {
-    size_t P, nq;
-    size_t box(size_t p) const { return 1 + P + 4 * p; }          // 4 words: cell box of pass p's positions
-    size_t ghosts(size_t p) const { return 1 + 5 * P + p; }       // ghost entries this handle received in pass p
-    size_t sent(size_t p, size_t m) const { return 1 + 6 * P + p * nq + m; }  // records sent to participant m in pass p
-    size_t words() const { return 1 + 6 * P + P * nq; }
-};
+int group_too_large(int n, std::string *error) {
+    if (n <= EGG_RX_MAX_GROUP) return EGG_OK;
+    *error = "relaxed order: a device group of more than 16 handles";
+    return EGG_ERR_UNSUPPORTED;
+}
 
 int device_fail(egg_handle *const *hs, int k, std::string *error, int rc) {
     char buf[64];
@@ -72,10 +68,7 @@ int64_t GroupKeys::base_of(int64_t key, int64_t count) const {
 }
 
 int relaxed_group_peers(egg_handle *const *hs, int n, std::string *error) {
-    if (n > EGG_RX_MAX_GROUP) {
-        *error = "relaxed order: a device group of more than 16 handles";
-        return EGG_ERR_UNSUPPORTED;
-    }
+    if (group_too_large(n, error) != EGG_OK) return EGG_ERR_UNSUPPORTED;
     return group_peers(hs, n, "relaxed order", "the ghost halo", error);
 }
 
@@ -107,28 +100,14 @@ int group_peers(egg_handle *const *hs, int n, const char *who, const char *what,
 }
 
 int relaxed_group_step(egg_handle *const *hs, int nh, double delta, int S, int C, int64_t halo_records[1], std::string *error) {
-    if (nh > EGG_RX_MAX_GROUP) {
-        *error = "relaxed order: a device group of more than 16 handles";
-        return EGG_ERR_UNSUPPORTED;
-    }
-    Env env[EGG_RX_MAX_GROUP][2];
-    int launches[EGG_RX_MAX_GROUP] = {0};
+    if (group_too_large(nh, error) != EGG_OK) return EGG_ERR_UNSUPPORTED;
+    RelaxedStep st[EGG_RX_MAX_GROUP][2];
     for (int k = 0; k < nh; ++k) {
-        egg_handle *h = hs[k];
-        (void)hipSetDevice(h->device);
-        const double sub_delta = std::max(delta / S, h->sys[0].cfg.eps);
-        for (int w = 0; w < 2; ++w) {
-            System &s = h->sys[w];
-            env[k][w] = make_env(s.cfg, sub_delta, h->budget_particles[w] >= 0 ? h->budget_particles[w] : s.n);
-            GK_TRY(k, follow_config(h, w, true));
-            GK_TRY(k, upload_atoms(h, w));
-        }
+        (void)hipSetDevice(hs[k]->device);
+        GK_TRY(k, prepare_step(hs[k], delta, S, st[k]));
     }
     const size_t P = (size_t)S * C;
     std::vector<int> q[2];
-    Layout L[2];
-    EggRelaxedGroupArgs A[2][EGG_RX_MAX_GROUP];
-    int64_t entries[2][EGG_RX_MAX_GROUP] = {};  // local particles + ghost capacity
     for (int w = 0; w < 2; ++w) {
         int64_t total = 0;
         for (int k = 0; k < nh; ++k)
@@ -136,12 +115,12 @@ int relaxed_group_step(egg_handle *const *hs, int nh, double delta, int S, int C
                 q[w].push_back(k);
                 total += hs[k]->sys[w].n;
             }
-        if (total > (int64_t)(1 << 29)) {
-            *error = "relaxed order: more than 2^29 particles of one type in the group";
+        if (total > kRelaxedMaxParticles) {
+            *error = EGG_RX_TOO_MANY_TEXT " in the group";
             return EGG_ERR_UNSUPPORTED;
         }
-        L[w] = Layout{P, q[w].size()};
         if (q[w].empty()) continue;
+        const RelaxedLayout L{P, q[w].size(), true};
         // global keys: a batch's particles start at the sum of the type's counts over the live batches of smaller id
         // (every handle lays its batches out in ascending id: the key of particle i is base + its place in its atom)
         std::vector<uint64_t> sig((size_t)nh);
@@ -151,57 +130,29 @@ int relaxed_group_step(egg_handle *const *hs, int nh, double delta, int S, int C
         for (int k : q[w])
             any_rebuild |= hs[k]->sys[w].rx.key_sig != sig || hs[k]->sys[w].rx.ekey.cap < (size_t)total;
         if (any_rebuild) group_keys(hs, nh, w, keys);
+        const KeyBaseFn base_of = [&keys](int64_t key, int64_t count, int32_t *base) {
+            *base = (int32_t)keys.base_of(key, count);
+            return (int)EGG_OK;
+        };
         for (int k : q[w]) {
-            egg_handle *h = hs[k];
-            System &s = h->sys[w];
+            System &s = hs[k]->sys[w];
             RelaxedBufs &r = s.rx;
-            (void)hipSetDevice(h->device);
-            const size_t n = (size_t)s.n, ghosts = (size_t)(total - s.n);
-            entries[w][k] = total;
-            GK_TRY(k, reserve_relaxed(h, s, S, C, ghosts, L[w].words()));
-            GK_TRY(k, upload_relaxed_targets(h, s));
-            const bool rebuild = r.key_sig != sig || r.ekey.cap < n + ghosts;  // (or a new array)
-            GK_HIP(k, r.ekey.reserve(n + ghosts, false, s.stream));
-            GK_HIP(k, r.sloc.reserve(n + ghosts, false, s.stream));
-            GK_HIP(k, r.gwr.reserve(std::max<size_t>(ghosts, 1), false, s.stream));
-            GK_HIP(k, r.send.reserve(q[w].size() * n, false, s.stream));
+            (void)hipSetDevice(hs[k]->device);
+            GK_TRY(k, prepare_type(st[k][w], C, (size_t)(total - s.n), L, sig, base_of));
+            GK_HIP(k, r.send.reserve(q[w].size() * (size_t)s.n, false, s.stream));
             for (hipEvent_t *e : {&r.ev_box[0], &r.ev_box[1], &r.ev_pack[0], &r.ev_pack[1]})
                 if (!*e) GK_HIP(k, hipEventCreateWithFlags(e, hipEventDisableTiming));
-            if (rebuild) {
-                const size_t na = s.atoms.size();
-                std::vector<int32_t> ab(na + 1, 0);
-                for (size_t a = 0; a < na; ++a) ab[a] = (int32_t)keys.base_of(h->batches[(size_t)s.atoms[a].batch].key, s.atoms[a].count);
-                GK_HIP(k, r.abase.reserve(na + 1, false, s.stream));
-                GK_HIP(k, hipMemcpyAsync(r.abase.p, ab.data(), (na + 1) * 4, hipMemcpyHostToDevice, s.stream));
-                hipLaunchKernelGGL(egg_rx_gkey_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s.stream,
-                                   r.p_atom.p, s.d_atom_offset.p, r.abase.p, (int)n, r.ekey.p);
-                ++launches[k];
-                GK_HIP(k, hipStreamSynchronize(s.stream));  // (ab is pageable host memory; membership changes only)
-                r.key_sig = sig;
-            }
-            GK_HIP(k, hipMemsetAsync(r.status.p, 0, L[w].words() * 8, s.stream));
-            EggRelaxedGroupArgs &a = A[w][k];
-            a.a = relaxed_args(h, w, env[k][w]);
-            a.g = EggRxGroupFields{};
-            a.g.ekey = r.ekey.p;
-            a.g.sloc = r.sloc.p;
-            a.g.gwr = r.gwr.p;
         }
     }
     // the passes, one type after the other (the types are independent: their streams overlap)
     for (int w = 0; w < 2; ++w) {
         const std::vector<int> &Q = q[w];
         const size_t nq = Q.size();
+        const RelaxedLayout L{P, nq, true};
         for (int sub = 0; sub < S; ++sub) {
             for (size_t m = 0; m < nq; ++m) {
-                const int k = Q[m];
-                System &s = hs[k]->sys[w];
-                EggRelaxedGroupArgs &a = A[w][k];
-                (void)hipSetDevice(hs[k]->device);
-                a.g.box = s.rx.status.p + L[w].box((size_t)sub * C);
-                hipLaunchKernelGGL(sub == 0 ? egg_rx_begin_group_kernel : egg_rx_mid_group_kernel, dim3((unsigned)((s.n + 255) / 256)),
-                                   dim3(256), 0, s.stream, a);
-                ++launches[k];
+                (void)hipSetDevice(hs[Q[m]]->device);
+                GK_TRY(Q[m], launch_substep(st[Q[m]][w], sub));
             }
             for (int c = 0; c < C; ++c) {
                 const size_t p = (size_t)sub * C + c;
@@ -217,8 +168,8 @@ int relaxed_group_step(egg_handle *const *hs, int nh, double delta, int S, int C
                     (void)hipSetDevice(hs[j]->device);
                     EggRxPackArgs pk{};
                     pk.n = (int)s.n;
-                    pk.cell_size = env[j][w].cell;
-                    pk.pos = A[w][j].a.pos;
+                    pk.cell_size = st[j][w].env.cell;
+                    pk.pos = st[j][w].A.a.pos;
                     pk.inv_mass = s.inv_mass.p;
                     pk.radius = s.radius.p;
                     pk.ekey = s.rx.ekey.p;
@@ -226,13 +177,13 @@ int relaxed_group_step(egg_handle *const *hs, int nh, double delta, int S, int C
                         if (mk == mj) continue;
                         const int k = Q[mk];
                         GK_HIP(j, hipStreamWaitEvent(s.stream, hs[k]->sys[w].rx.ev_box[par], 0));
-                        pk.box[pk.n_recv] = hs[k]->sys[w].rx.status.p + L[w].box(p);
+                        pk.box[pk.n_recv] = hs[k]->sys[w].rx.status.p + L.box(p);
                         pk.send[pk.n_recv] = s.rx.send.p + mk * (size_t)s.n;
-                        pk.count[pk.n_recv] = s.rx.status.p + L[w].sent(p, mk);
+                        pk.count[pk.n_recv] = s.rx.status.p + L.sent(p, mk);
                         ++pk.n_recv;
                     }
                     hipLaunchKernelGGL(egg_rx_pack_kernel, dim3((unsigned)((s.n + 255) / 256)), dim3(256), 0, s.stream, pk);
-                    ++launches[j];
+                    ++st[j][w].launches;
                     GK_HIP(j, hipEventRecord(s.rx.ev_pack[par], s.stream));
                 }
                 for (size_t mk = 0; mk < nq; ++mk) {  // receivers
@@ -240,43 +191,29 @@ int relaxed_group_step(egg_handle *const *hs, int nh, double delta, int S, int C
                     egg_handle *h = hs[k];
                     System &s = h->sys[w];
                     RelaxedBufs &r = s.rx;
-                    EggRelaxedGroupArgs &a = A[w][k];
                     (void)hipSetDevice(h->device);
-                    a.a.pass = (int)p;
-                    a.g.n_ghost = r.status.p + L[w].ghosts(p);
                     if (nq > 1) {
                         EggRxUnpackArgs up{};
                         up.n = (int)s.n;
-                        up.pos = a.a.pos;
+                        up.pos = st[k][w].A.a.pos;
                         up.gwr = r.gwr.p;
                         up.ekey = r.ekey.p;
-                        up.n_ghost = r.status.p + L[w].ghosts(p);
+                        up.n_ghost = r.status.p + L.ghosts(p);
                         int64_t most = 0;
                         for (size_t mj = 0; mj < nq; ++mj) {
                             if (mj == mk) continue;
                             System &sj = hs[Q[mj]]->sys[w];
                             GK_HIP(k, hipStreamWaitEvent(s.stream, sj.rx.ev_pack[par], 0));
                             up.recs[up.n_send] = sj.rx.send.p + mk * (size_t)sj.n;
-                            up.count[up.n_send] = sj.rx.status.p + L[w].sent(p, mk);
+                            up.count[up.n_send] = sj.rx.status.p + L.sent(p, mk);
                             ++up.n_send;
                             most = std::max(most, sj.n);
                         }
                         hipLaunchKernelGGL(egg_rx_unpack_kernel, dim3((unsigned)((most + 255) / 256), (unsigned)up.n_send), dim3(256), 0,
                                            s.stream, up);
-                        ++launches[k];
+                        ++st[k][w].launches;
                     }
-                    a.g.box = c + 1 < C ? r.status.p + L[w].box(p + 1) : nullptr;  // (the next sub-step's begins in mid)
-                    const dim3 grid((unsigned)((entries[w][k] + 255) / 256)), block(256);  // (ghost count read on the device)
-                    GK_HIP(k, hipMemsetAsync(r.hkey.p, 0xFF, (size_t)r.table * 8, s.stream));
-                    GK_HIP(k, hipMemsetAsync(r.hcount.p, 0, ((size_t)r.table + 1) * 4, s.stream));
-                    hipLaunchKernelGGL(egg_rx_insert_group_kernel, grid, block, 0, s.stream, a);
-                    size_t bytes = r.scan_bytes;
-                    GK_HIP(k, hipcub::DeviceScan::ExclusiveSum(r.scan_tmp.p, bytes, r.hcount.p, r.hstart.p, (int)r.table + 1, s.stream));
-                    hipLaunchKernelGGL(egg_rx_scatter_group_kernel, grid, block, 0, s.stream, a);
-                    hipLaunchKernelGGL(egg_rx_rank_group_kernel, grid, block, 0, s.stream, a);
-                    hipLaunchKernelGGL(egg_rx_gather_group_kernel, grid, block, 0, s.stream, a);
-                    launches[k] += 5;
-                    std::swap(a.a.pos, a.a.pos_next);
+                    GK_TRY(k, launch_pass(st[k][w], (int)p));
                 }
             }
         }
@@ -284,42 +221,33 @@ int relaxed_group_step(egg_handle *const *hs, int nh, double delta, int S, int C
     // all handles or none: the status words (bad cells, pair counts, ghost counts) of every handle, then the end kernels
     for (int w = 0; w < 2; ++w)
         for (int k : q[w]) {
-            System &s = hs[k]->sys[w];
             (void)hipSetDevice(hs[k]->device);
-            GK_HIP(k, hipGetLastError());
-            GK_HIP(k, hipMemcpyAsync(s.rx.h_status.p, s.rx.status.p, L[w].words() * 8, hipMemcpyDeviceToHost, s.stream));
+            GK_TRY(k, read_status(st[k][w]));
         }
     bool bad = false;
     for (int w = 0; w < 2; ++w)
         for (int k : q[w]) {
-            System &s = hs[k]->sys[w];
             (void)hipSetDevice(hs[k]->device);
-            GK_HIP(k, wait_step(s.stream));
-            bad |= s.rx.h_status.p[0] != 0;
+            GK_HIP(k, wait_step(hs[k]->sys[w].stream));
+            bad |= bad_cell(st[k][w]);
         }
     if (bad) {  // nothing is committed anywhere: every [cur] and [cur ^ 1] is as before the step
-        *error = "relaxed order: a position is NaN or its spatial-hash cell lies outside +-2^30";
+        *error = kRelaxedBadCellText;
         return EGG_ERR_UNSUPPORTED;
     }
     int64_t records = 0;
     for (int w = 0; w < 2; ++w)
         for (int k : q[w]) {
-            System &s = hs[k]->sys[w];
             (void)hipSetDevice(hs[k]->device);
-            hipLaunchKernelGGL(egg_rx_end_kernel, dim3((unsigned)((s.n + 255) / 256)), dim3(256), 0, s.stream, A[w][k].a);
-            ++launches[k];
-            GK_HIP(k, hipGetLastError());
-            for (size_t p = 0; p < P; ++p) records += (int64_t)s.rx.h_status.p[L[w].ghosts(p)];
+            GK_TRY(k, launch_end(st[k][w]));
+            for (size_t p = 0; p < P; ++p) records += (int64_t)hs[k]->sys[w].rx.h_status.p[st[k][w].L.ghosts(p)];
         }
     for (int w = 0; w < 2; ++w)
         for (int k : q[w]) {
             (void)hipSetDevice(hs[k]->device);
             GK_HIP(k, wait_step(hs[k]->sys[w].stream));
         }
-    for (int k = 0; k < nh; ++k) {
-        hs[k]->stats.kernel_launches += launches[k];
-        relaxed_commit(hs[k], env[k], S, C, 0.0);
-    }
+    for (int k = 0; k < nh; ++k) relaxed_commit(hs[k], st[k], S, C, 0.0);
     halo_records[0] += records;
     return EGG_OK;
 }

@@ -1,7 +1,8 @@
 // eggsim_host_relaxed_wire.hip -- one relaxed-order _step of ONE handle, driven pass by pass
 // through the C ABI (egg_rx_*, include/eggsim.h) by a host that carries the ghost halo between processes
-// (egg_fluid_simulation_amd/sharding.py).  It is relaxed_group_step (eggsim_host_relaxed_group.hip) cut at every place
-// where that reads another handle's memory or waits for another handle's event:
+// (egg_fluid_simulation_amd/sharding.py).  The step of each type is the driver of eggsim_host_relaxed.hip (RelaxedStep),
+// cut into calls at every place where relaxed_group_step (eggsim_host_relaxed_group.hip) reads another handle's memory or
+// waits for another handle's event.  What differs between the two:
 //
 //   group step                                          here
 //   ev_box of the others, their status words            egg_rx_get_boxes -> the host's all-gather -> boxes of egg_rx_pack
@@ -12,8 +13,6 @@
 //
 // The pass kernels are the group instantiations, unchanged: entries = local particles + ghosts with keys.  Everything is
 // enqueued on the handle's own streams; every call that hands data to the host waits for them first.
-#include <hipcub/hipcub.hpp>
-
 #include "eggsim_host.h"
 
 namespace egghost {
@@ -28,10 +27,7 @@ struct WireStep {
     int S = 0, C = 0;
     int sub_done = 0, pass_done = 0;  // sub-steps begun, passes run
     bool checked = false, bad = false;
-    Env env[2];
-    EggRelaxedGroupArgs A[2];
-    int64_t ghost_cap[2] = {0, 0};
-    int launches = 0;
+    RelaxedStep st[2];
     // the last egg_rx_pack
     int packed_pass = -1, n_dest = 0;
     std::vector<int64_t> counts;  // [n_dest][2]
@@ -39,16 +35,6 @@ struct WireStep {
 };
 
 namespace {
-
-struct Layout {  // status words of one type: P = S C passes
-    size_t P;
-    size_t box(size_t p) const { return 1 + P + 4 * p; }     // 4 words: cell box of pass p's positions
-    size_t ghosts(size_t p) const { return 1 + 5 * P + p; }  // ghost entries received in pass p
-    size_t words() const { return 1 + 6 * P; }
-};
-
-constexpr int64_t kMaxParticles = (int64_t)1 << 29;
-const char *const kBadText = "relaxed order: a position is NaN or its spatial-hash cell lies outside +-2^30";
 
 WireStep &wire_of(egg_handle *h) {
     if (!h->wire) h->wire = std::make_shared<WireStep>();
@@ -84,8 +70,7 @@ int egg_rx_set_keys(egg_handle *h, int which, int64_t n, const int64_t *keys, co
     if (!h || (which != EGG_WHITE && which != EGG_YOLK) || n < 0 || (n > 0 && (!keys || !bases)) || total < 0)
         return h ? fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_rx_set_keys: invalid arguments") : EGG_ERR_INVALID_ARGUMENT;
     REJECT_IN_FLIGHT(h, "egg_rx_set_keys");
-    if (total > kMaxParticles)
-        return fail(h, EGG_ERR_UNSUPPORTED, "relaxed order: more than 2^29 particles of one type over all ranks");
+    if (total > kRelaxedMaxParticles) return fail(h, EGG_ERR_UNSUPPORTED, EGG_RX_TOO_MANY_TEXT " over all ranks");
     std::vector<std::pair<int64_t, int64_t>> v((size_t)n);
     for (int64_t i = 0; i < n; ++i) {
         if (bases[i] < 0 || bases[i] > total) return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_rx_set_keys: a base lies outside [0, total]");
@@ -109,60 +94,24 @@ int egg_rx_begin(egg_handle *h, double delta, int32_t n_substeps, int32_t n_coll
     (void)hipSetDevice(h->device);
     WireStep &W = wire_of(h);
     const int S = n_substeps, C = n_collision_steps;
-    const double sub_delta = std::max(delta / S, h->sys[0].cfg.eps);
+    int rc = prepare_step(h, delta, S, W.st);
+    if (rc != EGG_OK) return rc;
     for (int w = 0; w < 2; ++w) {
         System &s = h->sys[w];
-        W.env[w] = make_env(s.cfg, sub_delta, h->budget_particles[w] >= 0 ? h->budget_particles[w] : s.n);
-        int rc = follow_config(h, w, true);
-        if (rc == EGG_OK) rc = upload_atoms(h, w);
-        if (rc != EGG_OK) return rc;
-    }
-    const Layout L{(size_t)S * C};
-    int launches = 0;
-    for (int w = 0; w < 2; ++w) {
-        System &s = h->sys[w];
-        RelaxedBufs &r = s.rx;
-        W.ghost_cap[w] = 0;
         if (s.n == 0) continue;
         const int64_t total = W.total[w];
         if (total < s.n) return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_rx_begin: the global keys of type %d are not set (egg_rx_set_keys)", w);
-        // key base of every local atom (a batch's particles are consecutive in key order, as they are in the handle)
-        const size_t na = s.atoms.size();
-        std::vector<int32_t> ab(na + 1, 0);
-        for (size_t a = 0; a < na; ++a) {
-            const int64_t key = h->batches[(size_t)s.atoms[a].batch].key;
+        const KeyBaseFn base_of = [&](int64_t key, int64_t count, int32_t *base) {
             auto it = std::lower_bound(W.keys[w].begin(), W.keys[w].end(), std::make_pair(key, (int64_t)-1));
-            if (it == W.keys[w].end() || it->first != key || it->second + s.atoms[a].count > total)
+            if (it == W.keys[w].end() || it->first != key || it->second + count > total)
                 return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_rx_begin: no (valid) global key base for the batch with key %lld, type %d",
                             (long long)key, w);
-            ab[a] = (int32_t)it->second;
-        }
-        const size_t n = (size_t)s.n, ghosts = (size_t)(total - s.n);
-        int rc = reserve_relaxed(h, s, S, C, ghosts, L.words());
-        if (rc == EGG_OK) rc = upload_relaxed_targets(h, s);
+            *base = (int32_t)it->second;
+            return (int)EGG_OK;
+        };
+        rc = prepare_type(W.st[w], C, (size_t)(total - s.n), RelaxedLayout{(size_t)S * C, 0, true},
+                          {~0ull, s.atoms_gen, W.keys_gen[w]}, base_of);
         if (rc != EGG_OK) return rc;
-        const std::vector<uint64_t> sig{~0ull, s.atoms_gen, W.keys_gen[w]};
-        const bool rebuild = r.key_sig != sig || r.ekey.cap < n + ghosts;  // (or a new array)
-        HIP_TRY(h, r.ekey.reserve(n + ghosts, false, s.stream));
-        HIP_TRY(h, r.sloc.reserve(n + ghosts, false, s.stream));
-        HIP_TRY(h, r.gwr.reserve(std::max<size_t>(ghosts, 1), false, s.stream));
-        if (rebuild) {
-            HIP_TRY(h, r.abase.reserve(na + 1, false, s.stream));
-            HIP_TRY(h, hipMemcpyAsync(r.abase.p, ab.data(), (na + 1) * 4, hipMemcpyHostToDevice, s.stream));
-            hipLaunchKernelGGL(egg_rx_gkey_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s.stream, r.p_atom.p,
-                               s.d_atom_offset.p, r.abase.p, (int)n, r.ekey.p);
-            ++launches;
-            HIP_TRY(h, hipStreamSynchronize(s.stream));  // (ab is pageable host memory; membership changes only)
-            r.key_sig = sig;
-        }
-        HIP_TRY(h, hipMemsetAsync(r.status.p, 0, L.words() * 8, s.stream));
-        EggRelaxedGroupArgs &a = W.A[w];
-        a.a = relaxed_args(h, w, W.env[w]);
-        a.g = EggRxGroupFields{};
-        a.g.ekey = r.ekey.p;
-        a.g.sloc = r.sloc.p;
-        a.g.gwr = r.gwr.p;
-        W.ghost_cap[w] = (int64_t)ghosts;
     }
     HIP_TRY(h, hipGetLastError());
     W.delta = delta;
@@ -170,7 +119,6 @@ int egg_rx_begin(egg_handle *h, double delta, int32_t n_substeps, int32_t n_coll
     W.C = C;
     W.sub_done = W.pass_done = 0;
     W.checked = W.bad = false;
-    W.launches = launches;
     W.packed_pass = -1;
     W.n_dest = 0;
     h->wire_active = true;
@@ -186,15 +134,10 @@ int egg_rx_substep(egg_handle *h, int32_t sub) {
         return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_rx_substep: sub-step %d is out of sequence (%d begun, %d passes run)", (int)sub,
                     W.sub_done, W.pass_done);
     (void)hipSetDevice(h->device);
-    const Layout L{(size_t)W.S * W.C};
     for (int w = 0; w < 2; ++w) {
-        System &s = h->sys[w];
-        if (s.n == 0) continue;
-        EggRelaxedGroupArgs &a = W.A[w];
-        a.g.box = s.rx.status.p + L.box((size_t)sub * W.C);
-        hipLaunchKernelGGL(sub == 0 ? egg_rx_begin_group_kernel : egg_rx_mid_group_kernel, dim3((unsigned)((s.n + 255) / 256)), dim3(256), 0,
-                           s.stream, a);
-        ++W.launches;
+        if (h->sys[w].n == 0) continue;
+        rc = launch_substep(W.st[w], sub);
+        if (rc != EGG_OK) return rc;
     }
     HIP_TRY(h, hipGetLastError());
     ++W.sub_done;
@@ -208,12 +151,11 @@ int egg_rx_get_boxes(egg_handle *h, int32_t pass, egg_rx_box boxes[2]) {
     if (rc != EGG_OK) return rc;
     WireStep &W = *h->wire;
     (void)hipSetDevice(h->device);
-    const Layout L{(size_t)W.S * W.C};
     for (int w = 0; w < 2; ++w) {
         System &s = h->sys[w];
         if (s.n == 0) continue;
-        HIP_TRY(h, hipMemcpyAsync(s.rx.h_status.p + L.box((size_t)pass), s.rx.status.p + L.box((size_t)pass), 4 * 8, hipMemcpyDeviceToHost,
-                                  s.stream));
+        const size_t at = W.st[w].L.box((size_t)pass);
+        HIP_TRY(h, hipMemcpyAsync(s.rx.h_status.p + at, s.rx.status.p + at, 4 * 8, hipMemcpyDeviceToHost, s.stream));
     }
     rc = wait_both(h);
     if (rc != EGG_OK) return rc;
@@ -222,7 +164,7 @@ int egg_rx_get_boxes(egg_handle *h, int32_t pass, egg_rx_box boxes[2]) {
         egg_rx_box &b = boxes[w];
         b = egg_rx_box{0, 0, 0, 0, 1};
         if (s.n == 0) continue;
-        const unsigned long long *q = s.rx.h_status.p + L.box((size_t)pass);
+        const unsigned long long *q = s.rx.h_status.p + W.st[w].L.box((size_t)pass);
         if (q[1] == 0) continue;  // (cannot happen with particles; the words say "empty")
         b.lo_x = (int32_t)((long long)((1ull << 32) - q[0]) - EGG_RX_BOX_BIAS);
         b.hi_x = (int32_t)((long long)q[1] - EGG_RX_BOX_BIAS);
@@ -269,8 +211,8 @@ int egg_rx_pack(egg_handle *h, int32_t pass, int32_t n_dest, const egg_rx_box *b
         HIP_TRY(h, hipMemcpyAsync(r.wbox.p, r.h_wbox.p, nd * EGG_RX_WIRE_BOX * 4, hipMemcpyHostToDevice, s.stream));
         EggRxWirePackArgs pk{};
         pk.n = (int)s.n;
-        pk.cell_size = W.env[w].cell;
-        pk.pos = W.A[w].a.pos;
+        pk.cell_size = W.st[w].env.cell;
+        pk.pos = W.st[w].A.a.pos;
         pk.inv_mass = s.inv_mass.p;
         pk.radius = s.radius.p;
         pk.ekey = r.ekey.p;
@@ -280,7 +222,7 @@ int egg_rx_pack(egg_handle *h, int32_t pass, int32_t n_dest, const egg_rx_box *b
             pk.boxes = r.wbox.p + k0 * EGG_RX_WIRE_BOX;
             pk.msg = r.wsend.p + k0 * stride;
             hipLaunchKernelGGL(egg_rx_wire_pack_kernel, dim3((unsigned)((s.n + 255) / 256)), dim3(256), 0, s.stream, pk);
-            ++W.launches;
+            ++W.st[w].launches;
         }
         HIP_TRY(h, hipGetLastError());
         for (size_t k = 0; k < nd; ++k)
@@ -333,9 +275,6 @@ int egg_rx_run_pass(egg_handle *h, int32_t pass, int32_t n_src, const void *cons
     if (rc != EGG_OK) return rc;
     WireStep &W = *h->wire;
     (void)hipSetDevice(h->device);
-    const Layout L{(size_t)W.S * W.C};
-    const size_t p = (size_t)pass;
-    const int c = pass % W.C;
     // every message is checked before anything is enqueued
     for (int w = 0; w < 2; ++w) {
         int64_t sum = 0;
@@ -344,17 +283,14 @@ int egg_rx_run_pass(egg_handle *h, int32_t pass, int32_t n_src, const void *cons
             if (cnt < 0 || (cnt > 0 && !msgs[2 * k + (size_t)w])) return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_rx_run_pass: invalid message %d", (int)k);
             sum += cnt;
         }
-        if (sum > W.ghost_cap[w])
+        if (sum > W.st[w].ghost_cap)
             return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_rx_run_pass: %lld ghost records of type %d, the other ranks hold %lld particles",
-                        (long long)sum, w, (long long)W.ghost_cap[w]);
+                        (long long)sum, w, (long long)W.st[w].ghost_cap);
     }
     for (int w = 0; w < 2; ++w) {
         System &s = h->sys[w];
         RelaxedBufs &r = s.rx;
         if (s.n == 0) continue;
-        EggRelaxedGroupArgs &a = W.A[w];
-        a.a.pass = pass;
-        a.g.n_ghost = r.status.p + L.ghosts(p);
         // staging copies of the messages in this handle's memory, then the unpack (16 messages per launch)
         size_t words = 0;
         for (size_t k = 0; k < (size_t)n_src; ++k)
@@ -363,17 +299,17 @@ int egg_rx_run_pass(egg_handle *h, int32_t pass, int32_t n_src, const void *cons
             HIP_TRY(h, r.wrecv.reserve(words, false, s.stream));
             EggRxWireUnpackArgs up{};
             up.n = (int)s.n;
-            up.cap_ghost = (int)W.ghost_cap[w];
-            up.pos = a.a.pos;
+            up.cap_ghost = (int)W.st[w].ghost_cap;
+            up.pos = W.st[w].A.a.pos;
             up.gwr = r.gwr.p;
             up.ekey = r.ekey.p;
-            up.n_ghost = r.status.p + L.ghosts(p);
+            up.n_ghost = r.status.p + W.st[w].L.ghosts((size_t)pass);
             int64_t most = 0;
             size_t off = 0;
             auto flush = [&]() {
                 if (!up.n_src) return;
                 hipLaunchKernelGGL(egg_rx_wire_unpack_kernel, dim3((unsigned)((most + 255) / 256), (unsigned)up.n_src), dim3(256), 0, s.stream, up);
-                ++W.launches;
+                ++W.st[w].launches;
                 up.n_src = 0;
                 most = 0;
             };
@@ -391,19 +327,8 @@ int egg_rx_run_pass(egg_handle *h, int32_t pass, int32_t n_src, const void *cons
             }
             flush();
         }
-        a.g.box = c + 1 < W.C ? r.status.p + L.box(p + 1) : nullptr;  // (the next sub-step's begins in mid)
-        const int64_t entries = s.n + W.ghost_cap[w];
-        const dim3 grid((unsigned)((entries + 255) / 256)), block(256);  // (ghost count read on the device)
-        HIP_TRY(h, hipMemsetAsync(r.hkey.p, 0xFF, (size_t)r.table * 8, s.stream));
-        HIP_TRY(h, hipMemsetAsync(r.hcount.p, 0, ((size_t)r.table + 1) * 4, s.stream));
-        hipLaunchKernelGGL(egg_rx_insert_group_kernel, grid, block, 0, s.stream, a);
-        size_t bytes = r.scan_bytes;
-        HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(r.scan_tmp.p, bytes, r.hcount.p, r.hstart.p, (int)r.table + 1, s.stream));
-        hipLaunchKernelGGL(egg_rx_scatter_group_kernel, grid, block, 0, s.stream, a);
-        hipLaunchKernelGGL(egg_rx_rank_group_kernel, grid, block, 0, s.stream, a);
-        hipLaunchKernelGGL(egg_rx_gather_group_kernel, grid, block, 0, s.stream, a);
-        W.launches += 5;
-        std::swap(a.a.pos, a.a.pos_next);
+        rc = launch_pass(W.st[w], pass);
+        if (rc != EGG_OK) return rc;
         HIP_TRY(h, hipGetLastError());
     }
     ++W.pass_done;
@@ -417,11 +342,10 @@ int egg_rx_check(egg_handle *h, int32_t *bad, int64_t pairs[2], int64_t *ghost_r
     WireStep &W = *h->wire;
     if (W.pass_done != W.S * W.C) return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_rx_check: %d of %d passes have run", W.pass_done, W.S * W.C);
     (void)hipSetDevice(h->device);
-    const Layout L{(size_t)W.S * W.C};
     for (int w = 0; w < 2; ++w) {
-        System &s = h->sys[w];
-        if (s.n == 0) continue;
-        HIP_TRY(h, hipMemcpyAsync(s.rx.h_status.p, s.rx.status.p, L.words() * 8, hipMemcpyDeviceToHost, s.stream));
+        if (h->sys[w].n == 0) continue;
+        rc = read_status(W.st[w]);
+        if (rc != EGG_OK) return rc;
     }
     rc = wait_both(h);
     if (rc != EGG_OK) return rc;
@@ -431,10 +355,10 @@ int egg_rx_check(egg_handle *h, int32_t *bad, int64_t pairs[2], int64_t *ghost_r
         System &s = h->sys[w];
         if (pairs) pairs[w] = 0;
         if (s.n == 0) continue;
-        W.bad |= s.rx.h_status.p[0] != 0;
-        for (size_t p = 0; p < L.P; ++p) {
+        W.bad |= bad_cell(W.st[w]);
+        for (size_t p = 0; p < W.st[w].L.P; ++p) {
             if (pairs) pairs[w] += (int64_t)s.rx.h_status.p[1 + p];
-            records += (int64_t)s.rx.h_status.p[L.ghosts(p)];
+            records += (int64_t)s.rx.h_status.p[W.st[w].L.ghosts(p)];
         }
     }
     W.checked = true;
@@ -454,19 +378,16 @@ int egg_rx_end(egg_handle *h, int32_t commit) {
     if (!commit || W.bad) {  // nothing wrote [cur ^ 1]: wait for what was enqueued and forget it
         rc = wait_both(h);
         if (rc != EGG_OK) return rc;
-        return commit ? fail(h, EGG_ERR_UNSUPPORTED, "%s", kBadText) : EGG_OK;
+        return commit ? fail(h, EGG_ERR_UNSUPPORTED, "%s", kRelaxedBadCellText) : EGG_OK;
     }
     for (int w = 0; w < 2; ++w) {
-        System &s = h->sys[w];
-        if (s.n == 0) continue;
-        hipLaunchKernelGGL(egg_rx_end_kernel, dim3((unsigned)((s.n + 255) / 256)), dim3(256), 0, s.stream, W.A[w].a);
-        ++W.launches;
-        HIP_TRY(h, hipGetLastError());
+        if (h->sys[w].n == 0) continue;
+        rc = launch_end(W.st[w]);
+        if (rc != EGG_OK) return rc;
     }
     rc = wait_both(h);
     if (rc != EGG_OK) return rc;
-    h->stats.kernel_launches += W.launches;
-    relaxed_commit(h, W.env, W.S, W.C, 0.0);
+    relaxed_commit(h, W.st, W.S, W.C, 0.0);
     return EGG_OK;
 }
 

@@ -33,15 +33,7 @@ namespace {
 __constant__ double kRxDirX[8] = {1.0, EGG_RX_S, 0.0, -EGG_RX_S, -1.0, -EGG_RX_S, 0.0, EGG_RX_S};
 __constant__ double kRxDirY[8] = {0.0, EGG_RX_S, 1.0, EGG_RX_S, 0.0, -EGG_RX_S, -1.0, -EGG_RX_S};
 
-// cell of a position; false for a NaN coordinate or a cell outside +-2^30
-__device__ __forceinline__ bool rx_cell(double2 p, double cell, int32_t &cx, int32_t &cy) {
-    const double fx = floor(p.x / cell), fy = floor(p.y / cell);
-    const bool ok = fx >= -0x1p30 && fx <= 0x1p30 && fy >= -0x1p30 && fy <= 0x1p30;
-    cx = ok ? (int32_t)fx : 0;
-    cy = ok ? (int32_t)fy : 0;
-    return ok;
-}
-
+// (rx_cell and rx_append: eggsim_device.h, shared with eggsim_relaxed_wire.hip)
 __device__ __forceinline__ unsigned long long rx_key(int32_t cx, int32_t cy) {
     return ((unsigned long long)(uint32_t)(cx + 0x40000000) << 32) | (unsigned long long)(uint32_t)(cy + 0x40000000);
 }
@@ -67,18 +59,6 @@ __device__ __forceinline__ void rx_box(unsigned long long *box, bool have, doubl
         atomicMax(&box[2], w2);
         atomicMax(&box[3], w3);
     }
-}
-
-// Wave-aggregated append: the lanes with `take` get consecutive slots of *counter; returns this lane's slot.
-__device__ __forceinline__ int rx_append(unsigned long long *counter, bool take) {
-    const unsigned long long mask = __ballot(take);
-    if (!mask) return 0;
-    const int lane = (int)(threadIdx.x & 63);
-    const int leader = __ffsll((long long)mask) - 1;
-    unsigned long long base = 0;
-    if (lane == leader) base = atomicAdd(counter, (unsigned long long)__popcll(mask));
-    base = __shfl(base, leader, 64);
-    return (int)base + __popcll(mask & ((1ull << lane) - 1ull));
 }
 
 __device__ __forceinline__ uint32_t rx_hash(unsigned long long k) {  // the 64-bit finaliser of MurmurHash3

@@ -9,34 +9,10 @@
 //   egg_rx_wire_unpack_kernel  receiver: messages in local memory (a staging copy of the received tensors) into the
 //                              ghost entries [n, n + ghosts)
 //
-// Plain vector loads and stores; the appends are wave-aggregated (one atomic per wave and destination).
+// Plain vector loads and stores; the appends are wave-aggregated (one atomic per wave and destination; rx_append and
+// rx_cell of eggsim_device.h, shared with eggsim_relaxed.hip).
 #include <hip/hip_runtime.h>
 #include "eggsim_device.h"
-
-namespace {
-
-// cell of a position, as rx_cell of eggsim_relaxed.hip: (0, 0) for a NaN coordinate or a cell outside +-2^30 (the
-// insert kernel of the pass flags it, and the step fails on every rank)
-__device__ __forceinline__ void wire_cell(double2 p, double cell, int32_t &cx, int32_t &cy) {
-    const double fx = floor(p.x / cell), fy = floor(p.y / cell);
-    const bool ok = fx >= -0x1p30 && fx <= 0x1p30 && fy >= -0x1p30 && fy <= 0x1p30;
-    cx = ok ? (int32_t)fx : 0;
-    cy = ok ? (int32_t)fy : 0;
-}
-
-// Wave-aggregated append, as rx_append of eggsim_relaxed.hip: the lanes with `take` get consecutive slots of *counter.
-__device__ __forceinline__ int wire_append(unsigned long long *counter, bool take) {
-    const unsigned long long mask = __ballot(take);
-    if (!mask) return 0;
-    const int lane = (int)(threadIdx.x & 63);
-    const int leader = __ffsll((long long)mask) - 1;
-    unsigned long long base = 0;
-    if (lane == leader) base = atomicAdd(counter, (unsigned long long)__popcll(mask));
-    base = __shfl(base, leader, 64);
-    return (int)base + __popcll(mask & ((1ull << lane) - 1ull));
-}
-
-}  // namespace
 
 // Sender: every local particle whose cell lies in a destination's cell box grown by one cell on each side goes into
 // that destination's message, in any order (the receiver's rank kernel orders by key).  A particle goes to a
@@ -62,7 +38,7 @@ extern "C" __global__ void __launch_bounds__(256) egg_rx_wire_pack_kernel(EggRxW
     EggGhost g{};
     if (live) {
         const double2 p = P.pos[i];
-        wire_cell(p, P.cell_size, cx, cy);
+        (void)rx_cell(p, P.cell_size, cx, cy);  // ((0, 0) for a bad cell: the insert kernel of the pass flags it)
         g.x = p.x;
         g.y = p.y;
         g.inv_mass = P.inv_mass[i];
@@ -72,7 +48,7 @@ extern "C" __global__ void __launch_bounds__(256) egg_rx_wire_pack_kernel(EggRxW
     for (int k = 0; k < P.n_dest; ++k) {
         const bool take = live && cx >= bx[k][0] && cx <= bx[k][1] && cy >= bx[k][2] && cy <= bx[k][3];
         unsigned long long *m = P.msg + (size_t)k * (size_t)P.stride;
-        const int slot = wire_append(m, take);
+        const int slot = rx_append(m, take);
         if (take) reinterpret_cast<EggGhost *>(m + 1)[slot] = g;
     }
 }
@@ -87,7 +63,7 @@ extern "C" __global__ void __launch_bounds__(256) egg_rx_wire_unpack_kernel(EggR
     const int cnt = said < (unsigned long long)U.cap[s] ? (int)said : U.cap[s];
     if ((int)(blockIdx.x * 256) >= cnt) return;  // (uniform over the workgroup)
     const bool take = q < cnt;
-    const int slot = wire_append(U.n_ghost, take);
+    const int slot = rx_append(U.n_ghost, take);
     if (take && slot < U.cap_ghost) {
         const EggGhost r = reinterpret_cast<const EggGhost *>(m + 1)[q];
         U.pos[U.n + slot] = make_double2(r.x, r.y);

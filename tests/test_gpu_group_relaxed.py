@@ -92,6 +92,39 @@ def test_four_batches_across_cuts(egg, n_handles, S, C, omega):
     assert g.counters()["discarded_steps"] == 0
 
 
+@pytest.mark.parametrize("S,C", [(2, 3), (1, 1)])
+@pytest.mark.parametrize("n_handles", [2, 3])
+def test_launches_of_one_step(egg, n_handles, S, C):
+    """The launch sequence of a relaxed group step, counted per handle: per type the handle holds, the single handle's
+    S + 5 S C + 1 (begin / mid, five launches per pass, end) and, when another handle holds the type too, one pack and
+    one unpack launch per pass.  The group's step then reads the batch positions of every handle that owns batches for
+    its stray rule: one centroid launch (egg_get_positions_many).  Taken over the second step: the first also builds
+    the atom and key tables."""
+    centers = [tuple(c) for c in load_golden("four_batches")["centers"]]
+    g, h = _pair(egg, CUTS[n_handles])
+    ids = _add_both(g, h, centers, 50, 15)
+    for i, c in zip(ids, centers):
+        _move_both(g, h, i, *circle_target(c, 0))
+    g.step(1 / 60, S, C)
+    owners = [g.owner(i)[0] for i in ids]
+    before = [b.stats()["kernel_launches"] for b in g.handles]
+    for i, c in zip(ids, centers):
+        _move_both(g, h, i, *circle_target(c, 1))
+    g.step(1 / 60, S, C)
+    assert [g.owner(i)[0] for i in ids] == owners  # (nothing migrated: the handles hold what they held)
+    delta = [b.stats()["kernel_launches"] - n for b, n in zip(g.handles, before)]
+    held = [b.get_n_particles() for b in g.handles]
+    print("group of %d S=%d C=%d: launches %s, particles %s" % (n_handles, S, C, delta, held))
+    assert sum(1 for n in held if n[WHITE] > 0) >= 2
+    for k, b in enumerate(g.handles):
+        want = 1 if k in owners else 0  # the stray rule's centroid launch
+        for w in (WHITE, YOLK):
+            if held[k][w] > 0:
+                shared = sum(1 for n in held if n[w] > 0) > 1
+                want += S + 5 * S * C + 1 + (2 * S * C if shared else 0)
+        assert delta[k] == want, "handle %d" % k
+
+
 def test_group_matches_the_model(egg):
     centers = [tuple(c) for c in load_golden("four_batches")["centers"]]
     g = egg.SimulationGroup([0, 0, 0], cuts=CUTS[3])

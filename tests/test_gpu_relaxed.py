@@ -124,6 +124,22 @@ def test_parity_with_model(egg, S, C, omega):
     assert h.stats()["max_pass_visits"][0] == max(m.relaxed_pass_pairs[0::2])
 
 
+@pytest.mark.parametrize("S,C", [(2, 3), (1, 1)])
+def test_launches_of_one_step(egg, S, C):
+    """The launch sequence of a relaxed step, counted: per populated type S begin / mid kernels, five launches per
+    collision pass (insert, scan, scatter, rank, gather) and the end kernel.  Taken over the second step: the first
+    also builds the per-particle atom table."""
+    h, m = _pair(egg)
+    centers, ids = _four_batches(h, m)
+    _step_both(h, m, ids, centers, 0, S, C)
+    before = h.stats()["kernel_launches"]
+    _step_both(h, m, ids, centers, 1, S, C)
+    delta = h.stats()["kernel_launches"] - before
+    print("single handle S=%d C=%d: %d launches" % (S, C, delta))
+    assert all(n > 0 for n in h.get_n_particles())
+    assert delta == 2 * (S + 5 * S * C + 1)
+
+
 def test_coincident_batches(egg):
     h, m = _pair(egg)
     centers = [(300.0, 300.0)] * 4 + [(700.0, 300.0)]

@@ -31,7 +31,8 @@ BAD_X = 1.0e12  # cells beyond +-2^30: the case test_gpu_relaxed.py uses
 def _four_batches_runs(world):
     centers = [tuple(float(v) for v in c) for c in load_golden("four_batches")["centers"]]
     cuts = [-2000.0, 10.0, 2000.0] if world == 2 else [-2000.0, -10.0, 20.0, 2000.0]  # through the cluster
-    return [dict(cuts=cuts, centers=centers, S=S, C=C, omega=omega, steps=8, target="circle")
+    return [dict(cuts=cuts, centers=centers, S=S, C=C, omega=omega, steps=8, target="circle",
+                 probe=(S, C) in ((2, 3), (1, 1)) and omega == 1.0)  # probe: _probe_launches after the run
             for S, C in ((2, 3), (1, 1), (3, 2)) for omega in (1.0, 1.8)]
 
 
@@ -149,6 +150,40 @@ def _state(sh):
     return out
 
 
+def _probe_launches(sh, run):
+    """one more step after a run's results are taken: the increase of the handle's kernel_launches from its start to
+    its commit (the stray rule after the commit launches a centroid kernel of its own), the particles the handle holds
+    per type and, per pass, (partners, white records received, yolk records received)"""
+    passes, exchange, rebalance, after = [], sh.halo.exchange, sh._rebalance_relaxed, []
+
+    def spy(p):
+        pointers, counts = exchange(p)
+        passes.append((len(sh.halo.partners), int(counts[:, 0].sum()), int(counts[:, 1].sum())))
+        return pointers, counts
+
+    def committed():
+        after.append(sh.local.stats()["kernel_launches"])
+        return rebalance()
+
+    sh.halo.exchange, sh._rebalance_relaxed = spy, committed
+    # a hand-over after a step makes the next one rebuild the atom and key tables (one launch each per type): the step
+    # counted is one that follows a step without hand-over (sh.migrations is the same number on every rank)
+    handed_over = True
+    for _ in range(4):
+        del passes[:], after[:]
+        moved = sh.migrations
+        n = list(sh.local.get_n_particles())
+        before = sh.local.stats()["kernel_launches"]
+        sh.step(1 / 60, run["S"], run["C"])
+        if not handed_over:
+            break
+        handed_over = sh.migrations != moved
+    else:
+        raise AssertionError("the scene kept handing batches over")
+    del sh.halo.exchange, sh._rebalance_relaxed
+    return dict(delta=after[0] - before, n=n, passes=passes)
+
+
 def _worker(rank, world, port, name, q):
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -195,6 +230,8 @@ def _worker(rank, world, port, name, q):
                            relaxed=st["relaxed_steps"], redo=st["redo_steps"], halo=sh.halo_counters(), owner=dict(sh.owner),
                            migrations=sh.migrations, claim_bytes=sh.exchange.bytes_exchanged, n_local=len(sh.local_id),
                            order=sh.get_solver_order(), collectives=sh.halo.collectives)
+                if run.get("probe"):
+                    res["launches"] = _probe_launches(sh, run)
             results.append(res)
         q.put((rank, "ok", results))
     except Exception:
@@ -313,6 +350,21 @@ def egg():
 
 # ------------------------------------------------------------------------------------------------ tests
 
+def _check_launches(got, run, what):
+    """The launch sequence of a relaxed step driven through egg_rx_*, counted: per type the rank holds, the single
+    handle's S + 5 S C + 1 (begin / mid, five launches per pass, end), one pack launch per pass that has partners and
+    one unpack launch per pass in which records of the type arrived (at most 16 partners: one launch each)."""
+    S, C = run["S"], run["C"]
+    print("%s: %s" % (what, got))
+    assert len(got["passes"]) == S * C
+    want = 0
+    for w in (0, 1):
+        if got["n"][w] > 0:
+            want += S + 5 * S * C + 1
+            want += sum(1 for p in got["passes"] if p[0] > 0) + sum(1 for p in got["passes"] if p[1 + w] > 0)
+    assert got["delta"] == want, what
+
+
 @pytest.mark.parametrize("world", [2, 3])
 def test_four_batches_cut_through_the_cluster_match_the_model(world):
     """scene 1: (S, C) in {(2, 3), (1, 1), (3, 2)} x omega in {1.0, 1.8}, moving targets, against RelaxedModel"""
@@ -327,6 +379,10 @@ def test_four_batches_cut_through_the_cluster_match_the_model(world):
             assert res[r][i]["relaxed"] == res[r][i]["steps"] == run["steps"]
         assert sum(res[r][i]["halo"]["records"] for r in range(world)) > 0, what
         assert all(res[r][i]["halo"]["records"] > 0 for r in range(world) if res[r][i]["n_local"]), what
+        assert ("launches" in res[0][i]) == ((run["S"], run["C"]) in ((2, 3), (1, 1)) and run["omega"] == 1.0)
+        for r in range(world):
+            if "launches" in res[r][i]:
+                _check_launches(res[r][i]["launches"], run, "%s rank %d" % (what, r))
 
 
 @pytest.mark.parametrize("name,world", [("swap2", 2), ("swap4", 4)])
