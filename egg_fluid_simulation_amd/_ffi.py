@@ -43,7 +43,9 @@ OPT_GROUP_PARTICLES = 11
 OPT_LEVEL_WALK = 12
 OPT_SOLVER_ORDER = 13  # 0 exact (default), 1 relaxed
 OPT_RELAXATION = 14    # omega of the relaxed pass, in (0, 2]
+OPT_COHESION = 15      # 0 as the reference: cohesion moves nothing (default), 1 effective (relaxed order only)
 SOLVER_EXACT, SOLVER_RELAXED = 0, 1
+COHESION_REFERENCE, COHESION_EFFECTIVE = 0, 1
 RELAXATION_DEFAULT = 1.8  # EGG_RELAXATION_DEFAULT
 PK_VARIANT_LEVELS_INORDER, PK_VARIANT_LEVELS_OOO, PK_VARIANT_EXEC, PK_VARIANT_EXEC_CHAIN, PK_VARIANT_SORT_LDS, PK_VARIANT_SORT_DIRECT = 1, 2, 4, 8, 16, 32
 PK_VARIANT_PASS_FUSED = 64
@@ -80,7 +82,7 @@ class EggStats(C.Structure):
                 ("max_pass_visits", C.c_int64 * 2), ("budget", C.c_double * 2), ("fused_launch", C.c_int64),
                 ("packed", C.c_int64 * 2), ("pk_kernel_ms", (C.c_double * 10) * 2), ("pk_kernel_launches", (C.c_int64 * 10) * 2),
                 ("host_ms", C.c_double * 3), ("max_levels", C.c_int64 * 2), ("pk_variants", C.c_int64 * 2),
-                ("relaxed_steps", C.c_int64)]
+                ("relaxed_steps", C.c_int64), ("cohesion_solves", C.c_int64)]
 
 
 class EggRenderConfig(C.Structure):  # egg_render_config
@@ -101,7 +103,8 @@ class EggRxBox(C.Structure):  # egg_rx_box: a cell box of the relaxed halo betwe
 
 
 RX_BOX_INTS = 5        # int32 fields of egg_rx_box
-RX_RECORD_WORDS = 5    # 64-bit words of a ghost record: x, y, inverse mass, radius (doubles), global key (int64)
+RX_RECORD_WORDS = 5    # 64-bit words of a ghost record: x, y, inverse mass, radius (doubles), global key (int64; with
+                       # effective cohesion the batch tag in its upper 32 bits)
 RX_RECORD_BYTES = 40
 
 # the draw record of a particle (egg_draw_pack, egg_draw_source_*): a message is double[7][n] in this field order
@@ -144,6 +147,7 @@ _SIGNATURES = {
     "egg_group_owner": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "egg_group_get_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "egg_group_set_solver_order": (C.c_int, [C.c_void_p, C.c_int32, C.c_double]),
+    "egg_group_set_cohesion": (C.c_int, [C.c_void_p, C.c_int32]),
     "egg_group_get_halo_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "egg_group_set_config": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(EggConfig)]),
     "egg_group_get_config": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(EggConfig)]),

@@ -299,11 +299,38 @@ struct EggRelaxedGroupArgs {
     EggRxGroupFields g;
 };
 
+// Effective cohesion (EGG_OPT_COHESION = 1, DESIGN.md section 2.7, "Cohesion"): the cohesive instantiations of the rank
+// and gather kernels (egg_rx_*_coh_kernel) take these besides.  A batch TAG is equal for two particles exactly when they
+// belong to one batch: the atom index on a single handle, the atom's key base (atom_tag) in a group or over the wire.
+struct EggRxCohesionFields {
+    double compliance;                   // _strength_to_compliance(cohesion_strength, sub_delta) (L:1772)
+    double factor;                       // cohesion_interaction_distance_factor
+    const int32_t *atom_tag;             // [atoms] tag of a local atom; nullptr: the atom index itself
+    const int32_t *gtag;                 // [ghost capacity] tags of the ghosts (group instantiations)
+    int32_t *stag;                       // [n + ghost capacity] tag of a grouped slot, next to spos / swr
+    unsigned long long *solves;          // one word: pairs whose cohesion branch fired in this step
+};
+struct EggRelaxedCohArgs {
+    EggRelaxedArgs a;
+    EggRxCohesionFields c;
+};
+struct EggRelaxedGroupCohArgs {
+    EggRelaxedArgs a;
+    EggRxGroupFields g;
+    EggRxCohesionFields c;
+};
+
 // A ghost record: a particle of a sender j that lies within one cell of a receiver k's cell box (40 bytes).
 struct EggGhost {
     double x, y, inv_mass, radius;
-    int64_t key;  // global key
+    int64_t key;  // global key (below 2^29); with effective cohesion the batch tag in the upper 32 bits, zero otherwise
 };
+// the key word of a record: atom_tag is null with cohesion off (the word is then the key alone, as ever)
+#if defined(__HIPCC__)
+static __device__ __forceinline__ int64_t rx_key_word(int32_t key, const int32_t *p_atom, const int32_t *atom_tag, int i) {
+    return atom_tag ? (int64_t)(((unsigned long long)(uint32_t)atom_tag[p_atom[i]] << 32) | (uint32_t)key) : (int64_t)key;
+}
+#endif
 #define EGG_RX_MAX_GROUP 16  // handles of one group that relaxed order supports
 // Cell box words (zero = empty): [0] max of 2^32 - u(cx), [1] max of u(cx), [2] / [3] the same for cy, u(c) = c + 2^30 + 1.
 #define EGG_RX_BOX_BIAS 0x40000001ll
@@ -313,6 +340,7 @@ struct EggRxPackArgs {  // sender side: one launch per pass packs for every rece
     const double2 *pos;
     const double *inv_mass, *radius;
     const int32_t *ekey;
+    const int32_t *p_atom, *atom_tag;    // effective cohesion: the batch tag travels in the key word (null otherwise)
     const unsigned long long *box[EGG_RX_MAX_GROUP];  // each receiver's box for this pass (in the receiver's memory)
     EggGhost *send[EGG_RX_MAX_GROUP];                 // this sender's buffer for each receiver (capacity n)
     unsigned long long *count[EGG_RX_MAX_GROUP];      // records in it (in this sender's memory, zero at the step's start)
@@ -322,6 +350,7 @@ struct EggRxUnpackArgs {  // receiver side: pulls every sender's records for it 
     double2 *pos;                        // positions of this pass; ghosts go to [n + g]
     double2 *gwr;
     int32_t *ekey;
+    int32_t *gtag;                       // effective cohesion: the ghosts' batch tags, beside gwr (null otherwise)
     unsigned long long *n_ghost;
     const EggGhost *recs[EGG_RX_MAX_GROUP];           // in the senders' memory
     const unsigned long long *count[EGG_RX_MAX_GROUP];
@@ -363,6 +392,7 @@ struct EggRxWirePackArgs {  // sender side: one launch packs for up to EGG_RX_MA
     const double2 *pos;
     const double *inv_mass, *radius;
     const int32_t *ekey;
+    const int32_t *p_atom, *atom_tag;    // effective cohesion: the batch tag travels in the key word (null otherwise)
     const int32_t *boxes;                // [n_dest][EGG_RX_WIRE_BOX]: the destinations' boxes for this pass
     unsigned long long *msg;             // [n_dest] messages of `stride` words each (capacity n records, header zeroed)
     long long stride;
@@ -373,6 +403,7 @@ struct EggRxWireUnpackArgs {  // receiver side: up to EGG_RX_MAX_GROUP received 
     double2 *pos;                        // positions of this pass; ghosts go to [n + g]
     double2 *gwr;
     int32_t *ekey;
+    int32_t *gtag;                       // effective cohesion: the ghosts' batch tags, beside gwr (null otherwise)
     unsigned long long *n_ghost;
     const unsigned long long *msg[EGG_RX_MAX_GROUP];  // in this handle's memory
     int32_t cap[EGG_RX_MAX_GROUP];                    // records the host was told each message holds

@@ -62,6 +62,7 @@ struct egg_group {
     int64_t migrations = 0, discarded_steps = 0;
     int64_t committed_visits[2] = {0, 0};
     int order = EGG_SOLVER_EXACT;
+    int cohesion = EGG_COHESION_REFERENCE;  // egg_group_set_cohesion: every handle's EGG_OPT_COHESION
     int64_t halo_passes = 0, halo_records = 0;  // relaxed group steps: collision passes, ghost records received
     int64_t steps = 0;  // _step calls committed by the group
     // render attributes (never read by the solver): they live here, per global id / per type, so that a hand-over
@@ -598,6 +599,8 @@ int egg_group_set_solver_order(egg_group *g, int32_t order, double relaxation) {
         return gfail(g, EGG_ERR_INVALID_ARGUMENT, "egg_group_set_solver_order: solver order must be 0 (exact) or 1 (relaxed)");
     if (std::isnan(relaxation) || relaxation > 2)
         return gfail(g, EGG_ERR_INVALID_ARGUMENT, "egg_group_set_solver_order: relaxation must be in (0, 2] (<= 0 keeps the current value)");
+    if (order == EGG_SOLVER_EXACT && g->cohesion != EGG_COHESION_REFERENCE)
+        return gfail(g, EGG_ERR_UNSUPPORTED, "egg_group_set_solver_order: exact order has no effective cohesion: switch cohesion off first (egg_group_set_cohesion)");
     if (order == EGG_SOLVER_RELAXED && g->h.size() > 1) {  // the ghost halo reads the other devices' memory
         std::string err;
         const int rc = egghost::relaxed_group_peers(g->h.data(), (int)g->h.size(), &err);
@@ -609,6 +612,23 @@ int egg_group_set_solver_order(egg_group *g, int32_t order, double relaxation) {
     for (size_t k = 0; k < g->h.size(); ++k) GTRY(g, k, egg_set_option(g->h[k], EGG_OPT_SOLVER_ORDER, (double)order));
     if (order != g->order) g->budget_stale = true;
     g->order = order;
+    return EGG_OK;
+}
+
+int egg_group_set_cohesion(egg_group *g, int32_t mode) {
+    if (!g) return EGG_ERR_INVALID_ARGUMENT;
+    if (mode != EGG_COHESION_REFERENCE && mode != EGG_COHESION_EFFECTIVE)
+        return gfail(g, EGG_ERR_INVALID_ARGUMENT, "egg_group_set_cohesion: cohesion must be 0 (as the reference) or 1 (effective)");
+    if (mode == EGG_COHESION_EFFECTIVE && g->order != EGG_SOLVER_RELAXED)
+        return gfail(g, EGG_ERR_UNSUPPORTED, "egg_group_set_cohesion: effective cohesion needs relaxed order (egg_group_set_solver_order first)");
+    for (size_t k = 0; k < g->h.size(); ++k) {
+        const int rc = egg_set_option(g->h[k], EGG_OPT_COHESION, (double)mode);
+        if (rc < 0) {  // (a handle somebody drives by hand: a step in flight, another order) -- the others go back
+            for (size_t j = 0; j < k; ++j) (void)egg_set_option(g->h[j], EGG_OPT_COHESION, (double)g->cohesion);
+            return gfail(g, rc, "device %d: %s", (int)k, egg_last_error(g->h[k]));
+        }
+    }
+    g->cohesion = mode;
     return EGG_OK;
 }
 

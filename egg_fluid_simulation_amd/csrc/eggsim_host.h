@@ -78,6 +78,10 @@ extern "C" __global__ void egg_rx_insert_group_kernel(EggRelaxedGroupArgs A);
 extern "C" __global__ void egg_rx_scatter_group_kernel(EggRelaxedGroupArgs A);
 extern "C" __global__ void egg_rx_rank_group_kernel(EggRelaxedGroupArgs A);
 extern "C" __global__ void egg_rx_gather_group_kernel(EggRelaxedGroupArgs A);
+extern "C" __global__ void egg_rx_rank_coh_kernel(EggRelaxedCohArgs A);
+extern "C" __global__ void egg_rx_gather_coh_kernel(EggRelaxedCohArgs A);
+extern "C" __global__ void egg_rx_rank_group_coh_kernel(EggRelaxedGroupCohArgs A);
+extern "C" __global__ void egg_rx_gather_group_coh_kernel(EggRelaxedGroupCohArgs A);
 extern "C" __global__ void egg_rx_gkey_kernel(const int32_t *, const int32_t *, const int32_t *, int, int32_t *);
 extern "C" __global__ void egg_rx_pack_kernel(EggRxPackArgs P);
 extern "C" __global__ void egg_rx_unpack_kernel(EggRxUnpackArgs U);
@@ -242,6 +246,8 @@ struct RelaxedBufs {
     // device groups (eggsim_host_relaxed_group.hip): entries n.. are ghosts of the other handles' particles
     DevBuf<int32_t> ekey, sloc, abase;    // [n + ghosts] global keys, [n + ghosts] entry of a grouped slot, [atoms] key base
     DevBuf<double2> gwr;                  // [ghosts] (inverse mass, radius)
+    DevBuf<int32_t> stag, gtag;           // effective cohesion, allocated once it has been on: [n + ghosts] batch tag of a
+                                          // grouped slot, [ghosts] the ghosts' tags
     DevBuf<EggGhost> send;                // [receivers][n] this handle's ghost records for the others
     std::vector<uint64_t> key_sig;        // every handle's atoms_gen when the keys were built
     // several processes (eggsim_host_relaxed_wire.hip): messages = word 0 the record count, then the records
@@ -386,6 +392,7 @@ struct egg_handle {
     int opt_group_particles = 0;  // particles one wave of the packed executor keeps in LDS (16 B each): 0 = by scene size (retile), at most 1280
     int opt_solver_order = 0;       // EGG_OPT_SOLVER_ORDER: 0 exact (the reference's pair order), 1 relaxed
     double opt_relaxation = EGG_RELAXATION_DEFAULT;  // EGG_OPT_RELAXATION: omega of the relaxed pass
+    int opt_cohesion = 0;           // EGG_OPT_COHESION: 0 dead as in the reference, 1 effective (relaxed order only)
     int opt_force_global_state = 0;  // test hook: run every tile through the global-memory-state kernel  // threads per particle in the step kernel's workgroups (pair dataflow spreading)
     hipDeviceProp_t prop{};
     size_t lds_limit = 64 * 1024;  // dynamic LDS a step-kernel workgroup may use
@@ -508,6 +515,7 @@ int retile(egg_handle *h, int which);
 // eggsim_host_step.hip
 struct Env {  // scalars of update_environment (L:1726-1774)
     double sub_delta, damping, follow_c, collision_c, budget, cell;
+    double cohesion_c;  // L:1772 (read by effective cohesion only: the reference's cohesion never moves a particle)
 };
 Env make_env(const egg_config &c, double sub_delta, int64_t n);
 // phase: kWhole = the complete step; kPrepare = tiles/claims only; kBegin = launch the first attempt and
@@ -524,14 +532,16 @@ constexpr int64_t kRelaxedMaxParticles = (int64_t)1 << 29;  // of one type, over
 constexpr char kRelaxedBadCellText[] = "relaxed order: a position is NaN or its spatial-hash cell lies outside +-2^30";
 // Status words of one type: [0] bad cell, [1 + p] pairs of pass p (P = S C passes); with a halo besides, per pass, the
 // cell box of its positions, the ghost entries received and -- device groups, nq handles holding the type -- the
-// records sent to each of them.
+// records sent to each of them.  With effective cohesion one more word, the last: the pairs that cohered.
 struct RelaxedLayout {
     size_t P = 0, nq = 0;
     bool halo = false;  // ghosts of other handles' particles take part: the group instantiations of the kernels
+    bool cohesion = false;  // (set by prepare_type from the handle's option)
     size_t box(size_t p) const { return 1 + P + 4 * p; }                      // 4 words
     size_t ghosts(size_t p) const { return 1 + 5 * P + p; }
     size_t sent(size_t p, size_t m) const { return 1 + 6 * P + p * nq + m; }  // to participant m
-    size_t words() const { return halo ? 1 + 6 * P + P * nq : 1 + P; }
+    size_t cohered() const { return halo ? 1 + 6 * P + P * nq : 1 + P; }
+    size_t words() const { return cohered() + (cohesion ? 1 : 0); }
 };
 struct RelaxedStep {  // one type of one handle in a relaxed step
     egg_handle *h = nullptr;
@@ -539,6 +549,7 @@ struct RelaxedStep {  // one type of one handle in a relaxed step
     Env env{};
     RelaxedLayout L;
     EggRelaxedGroupArgs A{};  // (A.g stays null without a halo)
+    EggRxCohesionFields coh{};  // effective cohesion (L.cohesion): compliance and factor of the type, the tag arrays
     int64_t ghost_cap = 0;    // a pass runs over n + ghost_cap entries
     int launches = 0;         // kernel launches so far: into the statistics at the commit
 };

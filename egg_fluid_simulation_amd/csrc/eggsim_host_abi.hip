@@ -934,6 +934,8 @@ int egg_set_option(egg_handle *h, int option, double value) {
             REJECT_IN_FLIGHT(h, "egg_set_option(EGG_OPT_SOLVER_ORDER)");
             if (!(value == EGG_SOLVER_EXACT || value == EGG_SOLVER_RELAXED))
                 return fail(h, EGG_ERR_INVALID_ARGUMENT, "solver order must be 0 (exact) or 1 (relaxed)");
+            if (value == EGG_SOLVER_EXACT && h->opt_cohesion != EGG_COHESION_REFERENCE)
+                return fail(h, EGG_ERR_UNSUPPORTED, "exact order has no effective cohesion: switch cohesion off first (EGG_OPT_COHESION = 0)");
             if ((int)value != h->opt_solver_order) {
                 if (value == EGG_SOLVER_EXACT) leave_relaxed(h);
                 else
@@ -945,6 +947,14 @@ int egg_set_option(egg_handle *h, int option, double value) {
             REJECT_IN_FLIGHT(h, "egg_set_option(EGG_OPT_RELAXATION)");
             if (!(value > 0.0 && value <= 2.0)) return fail(h, EGG_ERR_INVALID_ARGUMENT, "relaxation must be in (0, 2]");
             h->opt_relaxation = value;
+            return EGG_OK;
+        case EGG_OPT_COHESION:
+            REJECT_IN_FLIGHT(h, "egg_set_option(EGG_OPT_COHESION)");
+            if (!(value == EGG_COHESION_REFERENCE || value == EGG_COHESION_EFFECTIVE))
+                return fail(h, EGG_ERR_INVALID_ARGUMENT, "cohesion must be 0 (as the reference: it moves nothing) or 1 (effective)");
+            if (value == EGG_COHESION_EFFECTIVE && h->opt_solver_order != EGG_SOLVER_RELAXED)
+                return fail(h, EGG_ERR_UNSUPPORTED, "effective cohesion needs relaxed order (EGG_OPT_SOLVER_ORDER = 1 first)");
+            h->opt_cohesion = (int)value;
             return EGG_OK;
         case EGG_OPT_FORCE_SINGLE_TILE:
             h->opt_force_single = value != 0;

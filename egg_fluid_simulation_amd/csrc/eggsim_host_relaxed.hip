@@ -11,6 +11,9 @@
 //   egg_rx_* (eggsim_host_relaxed_wire.hip)             one handle per process; the host carries the halo between calls
 // With a halo (RelaxedLayout::halo) the entries of a pass are the local particles plus ghosts and the kernels are the
 // group instantiations; without, the plain ones.  Nothing else differs, and the three paths agree bit for bit.
+// With effective cohesion (EGG_OPT_COHESION = 1, RelaxedLayout::cohesion) launch_pass picks the cohesive instantiations
+// of the rank and gather kernels and RelaxedStep::coh carries the type's compliance, factor and tag arrays; a step with
+// cohesion off launches what it always launched, so all three paths pick cohesion up from here.
 #include <hipcub/hipcub.hpp>
 
 #include "eggsim_host.h"
@@ -156,13 +159,22 @@ int prepare_type(RelaxedStep &st, int C, size_t ghosts, const RelaxedLayout &L, 
     RelaxedBufs &r = s.rx;
     const size_t n = (size_t)s.n;
     st.L = L;
+    st.L.cohesion = h->opt_cohesion == EGG_COHESION_EFFECTIVE;
     st.C = C;
     st.ghost_cap = (int64_t)ghosts;
-    int rc = reserve_relaxed(h, s, ghosts, L.words());
+    int rc = reserve_relaxed(h, s, ghosts, st.L.words());
     if (rc == EGG_OK) rc = upload_relaxed_targets(h, s);
     if (rc != EGG_OK) return rc;
     st.A.a = relaxed_args(h, st.w, st.env);
     st.A.g = EggRxGroupFields{};
+    st.coh = EggRxCohesionFields{};
+    if (st.L.cohesion) {  // the tag of a particle without a halo is its atom; with one, the atom's key base (below)
+        HIP_TRY(h, r.stag.reserve(n + ghosts, false, s.stream));
+        st.coh.compliance = st.env.cohesion_c;
+        st.coh.factor = s.cfg.cohesion_interaction_distance_factor;
+        st.coh.stag = r.stag.p;
+        st.coh.solves = r.status.p + st.L.cohered();
+    }
     if (!L.halo) return EGG_OK;
     const bool rebuild = r.key_sig != sig || r.ekey.cap < n + ghosts;  // (or a new array)
     HIP_TRY(h, r.ekey.reserve(n + ghosts, false, s.stream));
@@ -187,6 +199,11 @@ int prepare_type(RelaxedStep &st, int C, size_t ghosts, const RelaxedLayout &L, 
     st.A.g.ekey = r.ekey.p;
     st.A.g.sloc = r.sloc.p;
     st.A.g.gwr = r.gwr.p;
+    if (st.L.cohesion) {
+        HIP_TRY(h, r.gtag.reserve(std::max<size_t>(ghosts, 1), false, s.stream));
+        st.coh.atom_tag = r.abase.p;
+        st.coh.gtag = r.gtag.p;
+    }
     return EGG_OK;
 }
 
@@ -230,12 +247,24 @@ int launch_pass(RelaxedStep &st, int p) {
     HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(r.scan_tmp.p, bytes, r.hcount.p, r.hstart.p, (int)r.table + 1, s.stream));
     if (st.L.halo) {
         hipLaunchKernelGGL(egg_rx_scatter_group_kernel, grid, block, 0, s.stream, a);
-        hipLaunchKernelGGL(egg_rx_rank_group_kernel, grid, block, 0, s.stream, a);
-        hipLaunchKernelGGL(egg_rx_gather_group_kernel, grid, block, 0, s.stream, a);
+        if (st.L.cohesion) {
+            const EggRelaxedGroupCohArgs k{a.a, a.g, st.coh};
+            hipLaunchKernelGGL(egg_rx_rank_group_coh_kernel, grid, block, 0, s.stream, k);
+            hipLaunchKernelGGL(egg_rx_gather_group_coh_kernel, grid, block, 0, s.stream, k);
+        } else {
+            hipLaunchKernelGGL(egg_rx_rank_group_kernel, grid, block, 0, s.stream, a);
+            hipLaunchKernelGGL(egg_rx_gather_group_kernel, grid, block, 0, s.stream, a);
+        }
     } else {
         hipLaunchKernelGGL(egg_rx_scatter_kernel, grid, block, 0, s.stream, a.a);
-        hipLaunchKernelGGL(egg_rx_rank_kernel, grid, block, 0, s.stream, a.a);
-        hipLaunchKernelGGL(egg_rx_gather_kernel, grid, block, 0, s.stream, a.a);
+        if (st.L.cohesion) {
+            const EggRelaxedCohArgs k{a.a, st.coh};
+            hipLaunchKernelGGL(egg_rx_rank_coh_kernel, grid, block, 0, s.stream, k);
+            hipLaunchKernelGGL(egg_rx_gather_coh_kernel, grid, block, 0, s.stream, k);
+        } else {
+            hipLaunchKernelGGL(egg_rx_rank_kernel, grid, block, 0, s.stream, a.a);
+            hipLaunchKernelGGL(egg_rx_gather_kernel, grid, block, 0, s.stream, a.a);
+        }
     }
     st.launches += 5;
     std::swap(a.a.pos, a.a.pos_next);  // Jacobi: the next pass starts from this one's result
@@ -320,6 +349,7 @@ void relaxed_commit(egg_handle *h, const RelaxedStep st[2], int S, int C, double
             most = std::max(most, v);
         }
         h->stats.max_pass_visits[w] = most;
+        if (st[w].L.cohesion) h->stats.cohesion_solves += (int64_t)s.rx.h_status.p[st[w].L.cohered()];
         h->stats.follow_solves += s.n * S;
         // the exact path's host copies of the atoms' cells describe older positions now
         s.aabb_valid = s.aabb_on_device = s.disp_valid = false;

@@ -102,6 +102,11 @@ int group_peers(egg_handle *const *hs, int n, const char *who, const char *what,
 int relaxed_group_step(egg_handle *const *hs, int nh, double delta, int S, int C, int64_t halo_records[1], std::string *error) {
     if (group_too_large(nh, error) != EGG_OK) return EGG_ERR_UNSUPPORTED;
     RelaxedStep st[EGG_RX_MAX_GROUP][2];
+    for (int k = 1; k < nh; ++k)
+        if (hs[k]->opt_cohesion != hs[0]->opt_cohesion) {  // (a ghost's batch tag travels only when its sender coheres)
+            *error = "relaxed order: the handles of the group differ in EGG_OPT_COHESION (egg_group_set_cohesion sets all)";
+            return EGG_ERR_INVALID_ARGUMENT;
+        }
     for (int k = 0; k < nh; ++k) {
         (void)hipSetDevice(hs[k]->device);
         GK_TRY(k, prepare_step(hs[k], delta, S, st[k]));
@@ -173,6 +178,10 @@ int relaxed_group_step(egg_handle *const *hs, int nh, double delta, int S, int C
                     pk.inv_mass = s.inv_mass.p;
                     pk.radius = s.radius.p;
                     pk.ekey = s.rx.ekey.p;
+                    if (st[j][w].L.cohesion) {
+                        pk.p_atom = s.rx.p_atom.p;
+                        pk.atom_tag = st[j][w].coh.atom_tag;
+                    }
                     for (size_t mk = 0; mk < nq; ++mk) {
                         if (mk == mj) continue;
                         const int k = Q[mk];
@@ -198,6 +207,7 @@ int relaxed_group_step(egg_handle *const *hs, int nh, double delta, int S, int C
                         up.pos = st[k][w].A.a.pos;
                         up.gwr = r.gwr.p;
                         up.ekey = r.ekey.p;
+                        up.gtag = st[k][w].L.cohesion ? r.gtag.p : nullptr;
                         up.n_ghost = r.status.p + L.ghosts(p);
                         int64_t most = 0;
                         for (size_t mj = 0; mj < nq; ++mj) {

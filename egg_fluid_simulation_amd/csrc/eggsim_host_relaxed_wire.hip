@@ -216,6 +216,10 @@ int egg_rx_pack(egg_handle *h, int32_t pass, int32_t n_dest, const egg_rx_box *b
         pk.inv_mass = s.inv_mass.p;
         pk.radius = s.radius.p;
         pk.ekey = r.ekey.p;
+        if (W.st[w].L.cohesion) {
+            pk.p_atom = r.p_atom.p;
+            pk.atom_tag = W.st[w].coh.atom_tag;
+        }
         pk.stride = (long long)stride;
         for (size_t k0 = 0; k0 < nd; k0 += EGG_RX_MAX_GROUP) {
             pk.n_dest = (int)std::min<size_t>(EGG_RX_MAX_GROUP, nd - k0);
@@ -303,6 +307,7 @@ int egg_rx_run_pass(egg_handle *h, int32_t pass, int32_t n_src, const void *cons
             up.pos = W.st[w].A.a.pos;
             up.gwr = r.gwr.p;
             up.ekey = r.ekey.p;
+            up.gtag = W.st[w].L.cohesion ? r.gtag.p : nullptr;
             up.n_ghost = r.status.p + W.st[w].L.ghosts((size_t)pass);
             int64_t most = 0;
             size_t off = 0;

@@ -16,6 +16,7 @@ Env make_env(const egg_config &c, double sub_delta, int64_t n) {
     e.damping = 1 - clampd(c.damping, 0, 1);
     e.follow_c = compliance(c.follow_strength);
     e.collision_c = compliance(c.collision_strength);
+    e.cohesion_c = compliance(c.cohesion_strength);
     double nn = (double)n;
     e.budget = c.max_collision_fraction * (nn * nn);
     e.cell = cell_size_of(c);

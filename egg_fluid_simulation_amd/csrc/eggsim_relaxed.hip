@@ -20,6 +20,12 @@
 // ghosts, and the key replaces the index in the rank order, the pair orientation and the pair count.  On a single
 // handle (the G = false instantiations) the key is the index and nothing else changes.
 //
+// With effective cohesion (EGG_OPT_COHESION = 1; DESIGN.md section 2.7, "Cohesion") the rank and gather kernels run in
+// their cohesive instantiations (K = true, egg_rx_*_coh_kernel): the rank kernel writes a batch tag per grouped slot, and
+// a same-batch pair beyond the collision distance but within cohesion_interaction_distance_factor (ra + rb) is pulled
+// back to the collision distance through the collision correction's own arithmetic with the cohesion compliance.  The
+// K = false instantiations are the kernels as they were.
+//
 // All arithmetic is IEEE double in the order of the definition: compile with -ffp-contract=off.
 #include <hip/hip_runtime.h>
 #include "eggsim_device.h"
@@ -179,9 +185,10 @@ __device__ __forceinline__ void rx_scatter(const EggRelaxedArgs &A, const EggRxG
 }
 
 // Inside a cell: ascending key (a particle's place = how many of its cell's particles have a smaller one), with the
-// grouped copies of what the gather reads.  sidx holds the key; sloc (group only) the entry.
-template <bool G>
-__device__ __forceinline__ void rx_rank(const EggRelaxedArgs &A, const EggRxGroupFields &X) {
+// grouped copies of what the gather reads.  sidx holds the key; sloc (group only) the entry; stag (cohesive only) the
+// batch tag.
+template <bool G, bool K>
+__device__ __forceinline__ void rx_rank(const EggRelaxedArgs &A, const EggRxGroupFields &X, const EggRxCohesionFields &Ch) {
     const int i = (int)(blockIdx.x * 256 + threadIdx.x);
     if (i >= rx_entries<G>(A, X)) return;
     const int key = G ? X.ekey[i] : i;
@@ -194,21 +201,32 @@ __device__ __forceinline__ void rx_rank(const EggRelaxedArgs &A, const EggRxGrou
     if (G) X.sloc[t] = i;
     A.spos[t] = A.pos[i];
     A.swr[t] = (!G || i < A.n) ? make_double2(A.inv_mass[i], A.radius[i]) : X.gwr[i - A.n];
+    if (K) {
+        if (!G || i < A.n) {
+            const int atom = A.p_atom[i];
+            Ch.stag[t] = Ch.atom_tag ? Ch.atom_tag[atom] : atom;
+        } else {
+            Ch.stag[t] = Ch.gtag[i - A.n];
+        }
+    }
 }
 
 // The relaxed pass of DESIGN.md section 2.7, one thread per grouped slot (threads of a wave share cells).  i is the
 // key; in a group a ghost's slot gathers nothing (its own device moves it), and the gather records the box of what it
-// writes when the pass is not the sub-step's last.
-template <bool G>
-__device__ __forceinline__ void rx_gather(EggRelaxedArgs A, const EggRxGroupFields &X) {
+// writes when the pass is not the sub-step's last.  K: a pair that does not collide may cohere -- same tag, within reach
+// -- and then runs the collision correction's arithmetic with the cohesion compliance (one path for both kinds).
+template <bool G, bool K>
+__device__ __forceinline__ void rx_gather(EggRelaxedArgs A, const EggRxGroupFields &X, const EggRxCohesionFields &Ch) {
     const int t = (int)(blockIdx.x * 256 + threadIdx.x);
     int pairs = 0;
+    int cohered = 0;  // (K only)
     bool local = false;  // (group: the slot holds one of this device's particles; gout is its new position)
     double2 gout = make_double2(0.0, 0.0);
     if (G ? t < rx_entries<G>(A, X) && X.sloc[t] < A.n : t < A.n) {
         const int i = A.sidx[t];
         const int me = G ? X.sloc[t] : i;
         const double2 p = A.spos[t], wr = A.swr[t];
+        const int32_t tag = K ? Ch.stag[t] : 0;
         int32_t cx, cy;
         (void)rx_cell(p, A.cell_size, cx, cy);  // (a bad cell was flagged by the insert kernel)
         double sx = 0.0, sy = 0.0;
@@ -236,9 +254,16 @@ __device__ __forceinline__ void rx_gather(EggRelaxedArgs A, const EggRxGroupFiel
                     const double dx = pb.x - pa.x, dy = pb.y - pa.y;
                     const double d2 = dx * dx + dy * dy;
                     const double min_distance = A.overlap * (ra + rb);
-                    if (!(d2 <= min_distance * min_distance)) continue;
+                    double compliance = A.collision_compliance;
+                    if (!(d2 <= min_distance * min_distance)) {
+                        if (!K) continue;
+                        const double reach = Ch.factor * (ra + rb);
+                        if (!(Ch.stag[e] == tag && d2 <= reach * reach)) continue;
+                        compliance = Ch.compliance;  // cohesion: back to the collision distance, never closer
+                        cohered += j > i ? 1 : 0;
+                    }
                     ++n_fired;
-                    const double divisor = wsum + A.collision_compliance;
+                    const double divisor = wsum + compliance;
                     if (divisor < A.eps) {  // _enforce_distance returns zeros (L:1527-1529)
                         sx = sx + 0.0;
                         sy = sy + 0.0;
@@ -287,6 +312,11 @@ __device__ __forceinline__ void rx_gather(EggRelaxedArgs A, const EggRxGroupFiel
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) pairs += __shfl_xor(pairs, d, 64);
     if ((threadIdx.x & 63) == 0 && pairs) atomicAdd(&A.status[1 + A.pass], (unsigned long long)pairs);
+    if (K) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) cohered += __shfl_xor(cohered, d, 64);
+        if ((threadIdx.x & 63) == 0 && cohered) atomicAdd(Ch.solves, (unsigned long long)cohered);
+    }
     if (G && X.box) rx_box(X.box, local, gout, A.cell_size);
 }
 
@@ -294,10 +324,15 @@ extern "C" __global__ void __launch_bounds__(256) egg_rx_insert_kernel(EggRelaxe
 extern "C" __global__ void __launch_bounds__(256) egg_rx_insert_group_kernel(EggRelaxedGroupArgs A) { rx_insert<true>(A.a, A.g); }
 extern "C" __global__ void __launch_bounds__(256) egg_rx_scatter_kernel(EggRelaxedArgs A) { rx_scatter<false>(A, EggRxGroupFields{}); }
 extern "C" __global__ void __launch_bounds__(256) egg_rx_scatter_group_kernel(EggRelaxedGroupArgs A) { rx_scatter<true>(A.a, A.g); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_rank_kernel(EggRelaxedArgs A) { rx_rank<false>(A, EggRxGroupFields{}); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_rank_group_kernel(EggRelaxedGroupArgs A) { rx_rank<true>(A.a, A.g); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_kernel(EggRelaxedArgs A) { rx_gather<false>(A, EggRxGroupFields{}); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_kernel(EggRelaxedGroupArgs A) { rx_gather<true>(A.a, A.g); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_rank_kernel(EggRelaxedArgs A) { rx_rank<false, false>(A, EggRxGroupFields{}, EggRxCohesionFields{}); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_rank_group_kernel(EggRelaxedGroupArgs A) { rx_rank<true, false>(A.a, A.g, EggRxCohesionFields{}); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_kernel(EggRelaxedArgs A) { rx_gather<false, false>(A, EggRxGroupFields{}, EggRxCohesionFields{}); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_kernel(EggRelaxedGroupArgs A) { rx_gather<true, false>(A.a, A.g, EggRxCohesionFields{}); }
+// effective cohesion
+extern "C" __global__ void __launch_bounds__(256) egg_rx_rank_coh_kernel(EggRelaxedCohArgs A) { rx_rank<false, true>(A.a, EggRxGroupFields{}, A.c); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_rank_group_coh_kernel(EggRelaxedGroupCohArgs A) { rx_rank<true, true>(A.a, A.g, A.c); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_coh_kernel(EggRelaxedCohArgs A) { rx_gather<false, true>(A.a, EggRxGroupFields{}, A.c); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_coh_kernel(EggRelaxedGroupCohArgs A) { rx_gather<true, true>(A.a, A.g, A.c); }
 
 // ---- device groups ----
 
@@ -346,7 +381,7 @@ extern "C" __global__ void __launch_bounds__(256) egg_rx_pack_kernel(EggRxPackAr
             g.y = p.y;
             g.inv_mass = P.inv_mass[i];
             g.radius = P.radius[i];
-            g.key = P.ekey[i];
+            g.key = rx_key_word(P.ekey[i], P.p_atom, P.atom_tag, i);
             P.send[k][slot] = g;
         }
     }
@@ -366,5 +401,6 @@ extern "C" __global__ void __launch_bounds__(256) egg_rx_unpack_kernel(EggRxUnpa
         U.pos[U.n + slot] = make_double2(r.x, r.y);
         U.gwr[slot] = make_double2(r.inv_mass, r.radius);
         U.ekey[U.n + slot] = (int32_t)r.key;
+        if (U.gtag) U.gtag[slot] = (int32_t)(r.key >> 32);
     }
 }

@@ -43,7 +43,7 @@ extern "C" __global__ void __launch_bounds__(256) egg_rx_wire_pack_kernel(EggRxW
         g.y = p.y;
         g.inv_mass = P.inv_mass[i];
         g.radius = P.radius[i];
-        g.key = P.ekey[i];
+        g.key = rx_key_word(P.ekey[i], P.p_atom, P.atom_tag, i);
     }
     for (int k = 0; k < P.n_dest; ++k) {
         const bool take = live && cx >= bx[k][0] && cx <= bx[k][1] && cy >= bx[k][2] && cy <= bx[k][3];
@@ -69,5 +69,6 @@ extern "C" __global__ void __launch_bounds__(256) egg_rx_wire_unpack_kernel(EggR
         U.pos[U.n + slot] = make_double2(r.x, r.y);
         U.gwr[slot] = make_double2(r.inv_mass, r.radius);
         U.ekey[U.n + slot] = (int32_t)r.key;
+        if (U.gtag) U.gtag[slot] = (int32_t)(r.key >> 32);
     }
 }

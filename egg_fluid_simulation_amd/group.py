@@ -102,6 +102,19 @@ class SimulationGroup(_HandlerSurface):
     def get_solver_order(self):
         return getattr(self, "_solver_order", "exact")
 
+    _COHESION_MODES = SimulationHandler._COHESION_MODES
+
+    def set_cohesion(self, mode):
+        """SimulationHandler.set_cohesion for every device handle (relaxed order only).  A same-batch pair across a cut
+        coheres too: a ghost carries its batch tag, in a record that stays 40 bytes."""
+        if mode not in self._COHESION_MODES:
+            raise EggError("cohesion must be 'reference' or 'effective', not %r" % (mode,))
+        self._check(self._lib.egg_group_set_cohesion(self._g, self._COHESION_MODES[mode]))
+        self._cohesion = mode
+
+    def get_cohesion(self):
+        return getattr(self, "_cohesion", "reference")
+
     def halo_counters(self):
         """cumulative over relaxed group steps: collision passes, ghost records received, their bytes"""
         p, r, b = C.c_int64(), C.c_int64(), C.c_int64()

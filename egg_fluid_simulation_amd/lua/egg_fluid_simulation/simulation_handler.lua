@@ -70,8 +70,10 @@ typedef struct {
 } egg_render_params;
 int egg_default_render_params(egg_render_params *p);
 int egg_render(egg_handle *h, const egg_render_params *p, float *rgba);
+int egg_set_option(egg_handle *h, int option, double value);
 typedef struct egg_group egg_group;
 int egg_group_set_solver_order(egg_group *g, int32_t order, double relaxation);
+int egg_group_set_cohesion(egg_group *g, int32_t mode);
 int egg_group_get_halo_counters(const egg_group *g, int64_t *passes, int64_t *records, int64_t *bytes);
 ]]
 
@@ -380,6 +382,28 @@ function SimulationHandler:get_environment(white_or_yolk)
              centroid_y = v.centroid_y, max_radius = v.max_radius, max_velocity = v.max_velocity,
              last_centroid_x = v.last_centroid_x, last_centroid_y = v.last_centroid_y }
 end
+
+-- Not in the reference: the opt-in, non-parity modes of include/eggsim.h (EGG_OPT_SOLVER_ORDER = 13, EGG_OPT_RELAXATION = 14,
+-- EGG_OPT_COHESION = 15; DESIGN.md section 2.7).
+local _solver_orders = { exact = 0, relaxed = 1 }
+local _cohesion_modes = { reference = 0, effective = 1 }
+
+--- "exact" (default) or "relaxed", omega `relaxation` in (0, 2] (nil keeps the current value)
+function SimulationHandler:set_solver_order(order, relaxation)
+    if _solver_orders[order] == nil then log.error("In SimulationHandler.set_solver_order: expected `exact` or `relaxed`") return end
+    if relaxation ~= nil and self:_check(lib.egg_set_option(self._h, 14, relaxation)) ~= 0 then return end
+    if self:_check(lib.egg_set_option(self._h, 13, _solver_orders[order])) == 0 then self._solver_order = order end
+end
+function SimulationHandler:get_solver_order() return self._solver_order or "exact" end
+
+--- "reference" (default): cohesion_strength / cohesion_interaction_distance_factor move nothing, as in the reference;
+--- "effective": same-batch particles within factor * (ra + rb) are pulled back to the collision distance.  Relaxed
+--- order only: refused in exact order, and set_solver_order("exact") is refused while cohesion is effective.
+function SimulationHandler:set_cohesion(mode)
+    if _cohesion_modes[mode] == nil then log.error("In SimulationHandler.set_cohesion: expected `reference` or `effective`") return end
+    if self:_check(lib.egg_set_option(self._h, 15, _cohesion_modes[mode])) == 0 then self._cohesion = mode end
+end
+function SimulationHandler:get_cohesion() return self._cohesion or "reference" end
 
 function SimulationHandler:draw()
     -- in a LOVE host: feed :instances() and :get_environment() to the reference's shaders and canvas code

@@ -598,6 +598,15 @@ class ShardedSimulationHandler(_HandlerSurface):
     def get_solver_order(self):
         return self._order
 
+    def set_cohesion(self, mode):
+        """SimulationHandler.set_cohesion on every rank alike (the same call on every rank; relaxed order only).  A ghost
+        carries its batch tag in the upper half of its key word: a record stays 40 bytes."""
+        self.local.set_cohesion(mode)
+        self._cohesion = mode
+
+    def get_cohesion(self):
+        return getattr(self, "_cohesion", "reference")
+
     def halo_counters(self):
         """relaxed steps of this rank, summed over the run: collision passes, ghost records received, their bytes"""
         if self.halo is None:

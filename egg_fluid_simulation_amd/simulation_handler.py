@@ -729,7 +729,7 @@ class SimulationHandler(_HandlerSurface):
                     max_pass_visits=list(s.max_pass_visits), budget=list(s.budget), fused_launch=int(s.fused_launch),
                     packed=list(s.packed), pk_kernel_ms=[list(r) for r in s.pk_kernel_ms],
                     pk_kernel_launches=[list(r) for r in s.pk_kernel_launches], host_ms=list(s.host_ms), max_levels=list(s.max_levels),
-                    pk_variants=list(s.pk_variants), relaxed_steps=s.relaxed_steps)
+                    pk_variants=list(s.pk_variants), relaxed_steps=s.relaxed_steps, cohesion_solves=s.cohesion_solves)
 
     def selftest_arith(self, n=1 << 24, seed=1):
         """mismatches of the kernel's hand-expanded f64 division against `/` on n random operand pairs"""
@@ -758,6 +758,23 @@ class SimulationHandler(_HandlerSurface):
 
     def get_solver_order(self):
         return getattr(self, "_solver_order", "exact")
+
+    _COHESION_MODES = {"reference": _ffi.COHESION_REFERENCE, "effective": _ffi.COHESION_EFFECTIVE}
+
+    def set_cohesion(self, mode):
+        """"reference" (default): `cohesion_strength` and `cohesion_interaction_distance_factor` move no particle, as in
+        the reference.  "effective": in a relaxed pass a same-batch pair beyond the collision distance but within
+        cohesion_interaction_distance_factor * (ra + rb) is pulled back to the collision distance with the cohesion
+        compliance ("Cohesion"); stats()["cohesion_solves"] counts those pairs.  Relaxed order
+        only: raises EggError on a handle in exact order, and set_solver_order("exact") raises while cohesion is
+        effective."""
+        if mode not in self._COHESION_MODES:
+            raise EggError("cohesion must be 'reference' or 'effective', not %r" % (mode,))
+        self.set_option(_ffi.OPT_COHESION, self._COHESION_MODES[mode])
+        self._cohesion = mode
+
+    def get_cohesion(self):
+        return getattr(self, "_cohesion", "reference")
 
     # ------------------------------------------------- relaxed order between processes (egg_rx_*, include/eggsim.h)
     # One relaxed _step driven pass by pass; ShardedSimulationHandler carries boxes and ghost messages between the ranks.

@@ -327,6 +327,9 @@ typedef struct {
     int64_t pk_variants[2];
     /* _step calls executed in relaxed order (EGG_OPT_SOLVER_ORDER = 1); included in `steps` */
     int64_t relaxed_steps;
+    /* effective cohesion (EGG_OPT_COHESION = 1): distinct pairs whose cohesion branch fired, summed over passes; each pair
+     * counted once, by the holder of its smaller key, as pair_solves counts ("Cohesion") */
+    int64_t cohesion_solves;
 } egg_stats;
 int egg_get_stats(egg_handle *h, egg_stats *out);
 
@@ -355,10 +358,18 @@ enum {
                                      * deterministic, not the reference's numbers.  A relaxed handle steps by itself, inside an
                                      * egg_group (egg_group_set_solver_order) or pass by pass (egg_rx_*): egg_step_begin, egg_step_end and egg_get_claims_many
                                      * return EGG_ERR_UNSUPPORTED, egg_prepare_step does nothing.  Refused while a step is in flight. */
-    EGG_OPT_RELAXATION              /* omega of the relaxed pass, in (0, 2] (default EGG_RELAXATION_DEFAULT).  Refused while a step is in flight. */
+    EGG_OPT_RELAXATION,             /* omega of the relaxed pass, in (0, 2] (default EGG_RELAXATION_DEFAULT).  Refused while a step is in flight. */
+    EGG_OPT_COHESION                /* 0 (default): as the reference -- cohesion_strength and cohesion_interaction_distance_factor move no
+                                     * particle (L:1608-1613 give same-batch pairs an interaction distance of 0); 1: effective -- in a relaxed
+                                     * pass a same-batch pair beyond the collision distance overlap (ra + rb) but within factor (ra + rb) is
+                                     * pulled back to the collision distance with the cohesion compliance ("Cohesion").
+                                     * Relaxed order only: 1 is EGG_ERR_UNSUPPORTED on a handle in exact order, and EGG_OPT_SOLVER_ORDER = 0 is
+                                     * EGG_ERR_UNSUPPORTED while cohesion is 1 (switch cohesion off first).  Refused while a step is in flight. */
 };
 #define EGG_SOLVER_EXACT 0
 #define EGG_SOLVER_RELAXED 1
+#define EGG_COHESION_REFERENCE 0
+#define EGG_COHESION_EFFECTIVE 1
 #define EGG_RELAXATION_DEFAULT 1.8
 int egg_set_option(egg_handle *h, int option, double value);
 
@@ -400,6 +411,10 @@ int egg_group_get_counters(const egg_group *g, int64_t *migrations, int64_t *dis
  * the current value).  Relaxed order over handles on different devices needs peer access between them: EGG_ERR_UNSUPPORTED
  * otherwise.  Refused values change nothing. */
 int egg_group_set_solver_order(egg_group *g, int32_t order, double relaxation);
+/* EGG_OPT_COHESION for every handle of the group, with its rules (relaxed order only; back to exact order only with
+ * cohesion off).  A refused value changes no handle.  Ghost records stay 40 bytes: a ghost's batch tag travels in the upper
+ * 32 bits of its key word. */
+int egg_group_set_cohesion(egg_group *g, int32_t mode);
 /* cumulative over relaxed group steps, both types: collision passes, ghost records the devices received, their bytes */
 int egg_group_get_halo_counters(const egg_group *g, int64_t *passes, int64_t *records, int64_t *bytes);
 
@@ -466,7 +481,9 @@ int egg_group_get_instances(egg_group *g, int which, egg_instance *data, float *
  *   egg_rx_check  ->  the ranks agree whether ANY of them flagged a bad position  ->  egg_rx_end(commit)
  *
  * A MESSAGE is one contiguous run of 64-bit words: word 0 the record count m, then m records of 5 words (40 bytes):
- * x, y, inverse mass, radius (doubles), global key (int64) -- 8 * (1 + 5 m) bytes.
+ * x, y, inverse mass, radius (doubles), global key (int64) -- 8 * (1 + 5 m) bytes.  The key is below 2^29; with
+ * EGG_OPT_COHESION = 1 on the sender the upper 32 bits of the key word hold the particle's batch tag (the key base of
+ * its batch), and they are zero otherwise.  Every rank sets EGG_OPT_COHESION alike.
  * All device work goes to the handle's own (non-blocking) streams.  A buffer the caller hands in is read from the
  * moment of the call: its contents must be complete (the caller has waited for its receive and synchronised the stream
  * that filled it), and a buffer in host memory must stay valid until the next egg_rx_get_boxes / egg_rx_check /
