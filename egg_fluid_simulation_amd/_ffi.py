@@ -44,6 +44,7 @@ OPT_LEVEL_WALK = 12
 OPT_SOLVER_ORDER = 13  # 0 exact (default), 1 relaxed
 OPT_RELAXATION = 14    # omega of the relaxed pass, in (0, 2]
 OPT_COHESION = 15      # 0 as the reference: cohesion moves nothing (default), 1 effective (relaxed order only)
+OPT_FORCE_CELL_HASH = 16  # test hook: 1 = the LDS hash table keys every tile's cells (exact order only)
 SOLVER_EXACT, SOLVER_RELAXED = 0, 1
 COHESION_REFERENCE, COHESION_EFFECTIVE = 0, 1
 RELAXATION_DEFAULT = 1.8  # EGG_RELAXATION_DEFAULT
@@ -82,7 +83,8 @@ class EggStats(C.Structure):
                 ("max_pass_visits", C.c_int64 * 2), ("budget", C.c_double * 2), ("fused_launch", C.c_int64),
                 ("packed", C.c_int64 * 2), ("pk_kernel_ms", (C.c_double * 10) * 2), ("pk_kernel_launches", (C.c_int64 * 10) * 2),
                 ("host_ms", C.c_double * 3), ("max_levels", C.c_int64 * 2), ("pk_variants", C.c_int64 * 2),
-                ("relaxed_steps", C.c_int64), ("cohesion_solves", C.c_int64)]
+                ("relaxed_steps", C.c_int64), ("cohesion_solves", C.c_int64),
+                ("cell_hash", C.c_int64 * 2)]
 
 
 class EggRenderConfig(C.Structure):  # egg_render_config

@@ -393,6 +393,7 @@ struct egg_handle {
     int opt_solver_order = 0;       // EGG_OPT_SOLVER_ORDER: 0 exact (the reference's pair order), 1 relaxed
     double opt_relaxation = EGG_RELAXATION_DEFAULT;  // EGG_OPT_RELAXATION: omega of the relaxed pass
     int opt_cohesion = 0;           // EGG_OPT_COHESION: 0 dead as in the reference, 1 effective (relaxed order only)
+    int opt_force_cell_hash = 0;     // test hook: every launch class keys its cells by the LDS hash table, never the dense grid
     int opt_force_global_state = 0;  // test hook: run every tile through the global-memory-state kernel  // threads per particle in the step kernel's workgroups (pair dataflow spreading)
     hipDeviceProp_t prop{};
     size_t lds_limit = 64 * 1024;  // dynamic LDS a step-kernel workgroup may use

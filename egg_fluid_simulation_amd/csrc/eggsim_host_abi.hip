@@ -908,6 +908,10 @@ int egg_set_option(egg_handle *h, int option, double value) {
             h->opt_force_global_state = value != 0;
             h->sys[0].tiling_dirty = h->sys[1].tiling_dirty = true;
             return EGG_OK;
+        case EGG_OPT_FORCE_CELL_HASH:
+            h->opt_force_cell_hash = value != 0;
+            h->sys[0].tiling_dirty = h->sys[1].tiling_dirty = true;
+            return EGG_OK;
         case EGG_OPT_BUDGET_PARTICLES_WHITE:
         case EGG_OPT_BUDGET_PARTICLES_YOLK:
             h->budget_particles[option == EGG_OPT_BUDGET_PARTICLES_WHITE ? 0 : 1] = value < 0 ? -1 : (int64_t)value;

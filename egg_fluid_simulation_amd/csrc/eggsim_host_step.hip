@@ -30,6 +30,7 @@ int launch_prologue(egg_handle *h, int which, hipStream_t stream) {
     s.aabb_on_device = false;  // the launch overwrites the atoms' boxes
     s.out_copied = false;
     s.wait_stream = stream;
+    h->stats.cell_hash[which] = 0;  // counted as the launch arguments are filled (a re-run counts afresh)
     const size_t na = s.atoms.size();
     if (s.meta_dirty) {
         auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
@@ -99,6 +100,7 @@ void fill_args(egg_handle *h, int which, const LaunchClass &lc, const Env &env, 
     A.amax = lc.amax;
     A.ccap = lc.ccap;
     A.use_grid = lc.use_grid;
+    if (!lc.use_grid) h->stats.cell_hash[which]++;
     A.lcap = lc.lcap;
     // more tiles than the chip can hold at one per CU: idle waves yield their issue slots
     A.spin_sleep = (h->opt_spin_sleep < 0) ? ((lc.n_tiles > 2 * h->prop.multiProcessorCount || lc.global_state) ? 1 : 0)
@@ -193,6 +195,7 @@ void fill_packed_args(egg_handle *h, int which, const PackedClass &pc, const Env
     A.amax = lc.amax;
     A.ccap = lc.ccap;
     A.use_grid = lc.use_grid;
+    if (!lc.use_grid) h->stats.cell_hash[which]++;
     A.sub_delta = env.sub_delta;
     A.damping = env.damping;
     A.follow_compliance = env.follow_c;

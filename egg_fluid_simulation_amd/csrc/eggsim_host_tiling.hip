@@ -318,7 +318,7 @@ int retile(egg_handle *h, int which) {
         lc.n_tiles = (int)(t1 - t0);
         lc.nmax = (int)((nmax + 7) & ~7ll);
         lc.amax = amax;
-        if (max_cells <= std::max<int64_t>(2048, 8 * (int64_t)lc.nmax) && max_cells <= 16384) {
+        if (!h->opt_force_cell_hash && max_cells <= std::max<int64_t>(2048, 8 * (int64_t)lc.nmax) && max_cells <= 16384) {
             lc.use_grid = 1;
             lc.ccap = (int)((max_cells + 63) & ~63ll);
         } else {

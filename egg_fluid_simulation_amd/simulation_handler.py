@@ -729,7 +729,8 @@ class SimulationHandler(_HandlerSurface):
                     max_pass_visits=list(s.max_pass_visits), budget=list(s.budget), fused_launch=int(s.fused_launch),
                     packed=list(s.packed), pk_kernel_ms=[list(r) for r in s.pk_kernel_ms],
                     pk_kernel_launches=[list(r) for r in s.pk_kernel_launches], host_ms=list(s.host_ms), max_levels=list(s.max_levels),
-                    pk_variants=list(s.pk_variants), relaxed_steps=s.relaxed_steps, cohesion_solves=s.cohesion_solves)
+                    pk_variants=list(s.pk_variants), relaxed_steps=s.relaxed_steps, cohesion_solves=s.cohesion_solves,
+                    cell_hash=list(s.cell_hash))
 
     def selftest_arith(self, n=1 << 24, seed=1):
         """mismatches of the kernel's hand-expanded f64 division against `/` on n random operand pairs"""

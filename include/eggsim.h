@@ -330,6 +330,9 @@ typedef struct {
     /* effective cohesion (EGG_OPT_COHESION = 1): distinct pairs whose cohesion branch fired, summed over passes; each pair
      * counted once, by the holder of its smaller key, as pair_solves counts ("Cohesion") */
     int64_t cohesion_solves;
+    /* launch classes of that type whose tiles keyed their cells by the LDS hash table instead of the dense grid in the most
+     * recent exact-order _step (0: every class ran on the dense grid; DESIGN.md section 2.1, "Cells") */
+    int64_t cell_hash[2];
 } egg_stats;
 int egg_get_stats(egg_handle *h, egg_stats *out);
 
@@ -359,12 +362,15 @@ enum {
                                      * egg_group (egg_group_set_solver_order) or pass by pass (egg_rx_*): egg_step_begin, egg_step_end and egg_get_claims_many
                                      * return EGG_ERR_UNSUPPORTED, egg_prepare_step does nothing.  Refused while a step is in flight. */
     EGG_OPT_RELAXATION,             /* omega of the relaxed pass, in (0, 2] (default EGG_RELAXATION_DEFAULT).  Refused while a step is in flight. */
-    EGG_OPT_COHESION                /* 0 (default): as the reference -- cohesion_strength and cohesion_interaction_distance_factor move no
+    EGG_OPT_COHESION,               /* 0 (default): as the reference -- cohesion_strength and cohesion_interaction_distance_factor move no
                                      * particle (L:1608-1613 give same-batch pairs an interaction distance of 0); 1: effective -- in a relaxed
                                      * pass a same-batch pair beyond the collision distance overlap (ra + rb) but within factor (ra + rb) is
                                      * pulled back to the collision distance with the cohesion compliance ("Cohesion").
                                      * Relaxed order only: 1 is EGG_ERR_UNSUPPORTED on a handle in exact order, and EGG_OPT_SOLVER_ORDER = 0 is
                                      * EGG_ERR_UNSUPPORTED while cohesion is 1 (switch cohesion off first).  Refused while a step is in flight. */
+    EGG_OPT_FORCE_CELL_HASH         /* test hook: 1 = every launch class of both types keys its cells by the LDS hash table (the fallback of tiles whose
+                                     * claim box is too large for a dense grid), sized by the usual rule; 0 (default): by the size of the claim box.
+                                     * Exact order only: relaxed order has a hash table of its own and ignores the option. */
 };
 #define EGG_SOLVER_EXACT 0
 #define EGG_SOLVER_RELAXED 1

@@ -29,7 +29,9 @@ def _enum_values(text, first):
 def test_option_value_and_modes():
     from egg_fluid_simulation_amd import _ffi
     opts = _enum_values(_header(), "EGG_OPT_CLAIM_MARGIN_CELLS")
-    assert opts["EGG_OPT_COHESION"] == opts["EGG_OPT_RELAXATION"] + 1 == max(opts.values()) == _ffi.OPT_COHESION
+    assert opts["EGG_OPT_COHESION"] == opts["EGG_OPT_RELAXATION"] + 1 == _ffi.OPT_COHESION == 15
+    # (options appended since keep these numbers: the only one behind it is the cell-hash test hook, tests/test_abi.py)
+    assert [k for k, v in opts.items() if v > opts["EGG_OPT_COHESION"]] == ["EGG_OPT_FORCE_CELL_HASH"]
     assert opts["EGG_OPT_SOLVER_ORDER"] == _ffi.OPT_SOLVER_ORDER and opts["EGG_OPT_RELAXATION"] == _ffi.OPT_RELAXATION
     defines = dict(re.findall(r"#define (EGG_COHESION_[A-Z]+) (\d+)", _header()))
     assert defines == {"EGG_COHESION_REFERENCE": "0", "EGG_COHESION_EFFECTIVE": "1"}
@@ -41,10 +43,11 @@ def test_stats_end_with_the_new_counter():
     body = re.search(r"typedef struct\s*\{((?:(?!typedef).)*?)\}\s*egg_stats\s*;", re.sub(r"/\*.*?\*/", " ", _header(), flags=re.S),
                      flags=re.S).group(1)
     fields = re.findall(r"([a-z_]+)(?:\[[^;]*\])*\s*;", body)
-    assert fields[-2:] == ["relaxed_steps", "cohesion_solves"]
+    # (fields appended since leave the counter where it was: only cell_hash[2] stands behind it, tests/test_abi.py)
+    assert fields[-3:] == ["relaxed_steps", "cohesion_solves", "cell_hash"]
     assert [f[0] for f in _ffi.EggStats._fields_] == fields
-    assert _ffi.EggStats._fields_[-1] == ("cohesion_solves", C.c_int64)
-    assert _ffi.EggStats.cohesion_solves.offset == C.sizeof(_ffi.EggStats) - 8
+    assert _ffi.EggStats._fields_[-2] == ("cohesion_solves", C.c_int64)
+    assert _ffi.EggStats.cohesion_solves.offset == C.sizeof(_ffi.EggStats) - 8 - 16 == _ffi.EggStats.relaxed_steps.offset + 8
 
 
 def test_group_entry_point_and_record_size():

@@ -25,11 +25,14 @@ def _same(h, o, tag):
     assert h.stats()["pair_solves"] == o.total_visited, tag
 
 
-@pytest.mark.parametrize("seed", list(range(1, 11)))
-def test_random_session_matches_oracle(egg, oracle_mod, seed):
+def random_session(egg, oracle_mod, seed, configure=None):
+    """one session of `seed` on a fresh handler (after configure(h), if given) and a fresh oracle, compared every six
+    steps and at the end; returns the handler"""
     from egg_fluid_simulation_amd.default_config import default_configs
     rng = np.random.default_rng(seed)
     h, o = egg.SimulationHandler(), oracle_mod.Oracle()
+    if configure:
+        configure(h)
     live = {}  # id -> [x, y, vx, vy] of the target
 
     def add():
@@ -77,6 +80,12 @@ def test_random_session_matches_oracle(egg, oracle_mod, seed):
     _same(h, o, (seed, "end"))
     for i in live:
         assert h.get_position(i) == o.get_position(i)
+    return h
+
+
+@pytest.mark.parametrize("seed", list(range(1, 11)))
+def test_random_session_matches_oracle(egg, oracle_mod, seed):
+    random_session(egg, oracle_mod, seed)
 
 
 def test_crowded_scene_on_a_shared_chip(egg, oracle_mod):

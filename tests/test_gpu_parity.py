@@ -160,7 +160,7 @@ def test_result_is_independent_of_tiling(egg):
     xs, ys = _grid(36)  # the forced single tile (5652 white particles) runs in the global-memory-state kernel
     ref = None
     for opts in ({}, {_ffi.OPT_TILE_TARGET_PARTICLES: 0}, {_ffi.OPT_FUSE_TYPES: 0}, {_ffi.OPT_TILE_TARGET_PARTICLES: 700}, {_ffi.OPT_CLAIM_MARGIN_CELLS: 6},
-                 {_ffi.OPT_FORCE_SINGLE_TILE: 1}):
+                 {_ffi.OPT_FORCE_SINGLE_TILE: 1}, {_ffi.OPT_FORCE_CELL_HASH: 1}):
         h = egg.SimulationHandler()
         for k, v in opts.items():
             h.set_option(k, v)
@@ -175,6 +175,8 @@ def test_result_is_independent_of_tiling(egg):
             assert h.stats()["n_tiles"][0] == 36
         else:
             assert all(np.array_equal(a, b) for a, b in zip(ref, state)), opts
+        if _ffi.OPT_FORCE_CELL_HASH in opts:
+            assert all(c > 0 for c in h.stats()["cell_hash"]), h.stats()["cell_hash"]
 
 
 @pytest.mark.skipif(os.environ.get("EGGSIM_PACKED") == "1", reason="asserts the one-launch mode; EGGSIM_PACKED=1 forces the packed pipeline")
