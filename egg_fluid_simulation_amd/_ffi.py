@@ -100,6 +100,17 @@ class EggRenderParams(C.Structure):  # egg_render_params
                 ("clear", C.c_float * 4)]
 
 
+class EggCollider(C.Structure):  # egg_collider: a static collider of the relaxed pass (40 bytes)
+    _fields_ = [("kind", C.c_int32), ("type_mask", C.c_int32), ("p", C.c_double * 4)]
+
+
+MAX_COLLIDERS = 64  # EGG_MAX_COLLIDERS
+COLLIDER_HALF_PLANE, COLLIDER_DISC, COLLIDER_CONTAINER, COLLIDER_SEGMENT = 0, 1, 2, 3
+COLLIDER_KINDS = ("half_plane", "disc", "container", "segment")  # by EGG_COLLIDER_* value
+COLLIDER_PARAMS = (("nx", "ny", "off"), ("cx", "cy", "R"), ("cx", "cy", "R"), ("x0", "y0", "x1", "y1"))
+COLLIDER_TYPES = {"white": 1, "yolk": 2, "both": 3}  # type_mask
+
+
 class EggRxBox(C.Structure):  # egg_rx_box: a cell box of the relaxed halo between processes
     _fields_ = [("lo_x", C.c_int32), ("lo_y", C.c_int32), ("hi_x", C.c_int32), ("hi_y", C.c_int32), ("empty", C.c_int32)]
 
@@ -150,6 +161,12 @@ _SIGNATURES = {
     "egg_group_get_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "egg_group_set_solver_order": (C.c_int, [C.c_void_p, C.c_int32, C.c_double]),
     "egg_group_set_cohesion": (C.c_int, [C.c_void_p, C.c_int32]),
+    "egg_set_colliders": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggCollider)]),
+    "egg_get_colliders": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggCollider), C.POINTER(C.c_int32)]),
+    "egg_get_collider_hits": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "egg_group_set_colliders": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggCollider)]),
+    "egg_group_get_colliders": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggCollider), C.POINTER(C.c_int32)]),
+    "egg_group_get_collider_hits": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "egg_group_get_halo_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "egg_group_set_config": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(EggConfig)]),
     "egg_group_get_config": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(EggConfig)]),

@@ -320,6 +320,45 @@ struct EggRelaxedGroupCohArgs {
     EggRxCohesionFields c;
 };
 
+// Static colliders (egg_set_colliders, DESIGN.md section 2.7, "Colliders"): the collider instantiations of the gather
+// kernel (egg_rx_gather*_col_kernel) take these besides.  The list is the handle's, in a small device buffer written when
+// it is set; a record has the layout of the ABI's egg_collider (40 bytes), the half-plane's normal already normalised.
+#define EGG_RX_MAX_COLLIDERS 64
+#define EGG_RX_COLLIDER_HALF_PLANE 0  // = EGG_COLLIDER_* of include/eggsim.h
+#define EGG_RX_COLLIDER_DISC 1
+#define EGG_RX_COLLIDER_CONTAINER 2
+#define EGG_RX_COLLIDER_SEGMENT 3
+struct EggCollider {
+    int32_t kind, type_mask;
+    double p[4];
+};
+struct EggRxColliderFields {
+    const EggCollider *list;             // [count], applied in this order; every lane reads the same record
+    int32_t count;
+    int32_t type_bit;                    // 1 white, 2 yolk: a collider applies when its type_mask has the bit
+    unsigned long long *hits;            // one word: (collider, particle, pass) triples that moved a particle in this step
+};
+struct EggRelaxedColArgs {
+    EggRelaxedArgs a;
+    EggRxColliderFields d;
+};
+struct EggRelaxedGroupColArgs {
+    EggRelaxedArgs a;
+    EggRxGroupFields g;
+    EggRxColliderFields d;
+};
+struct EggRelaxedCohColArgs {
+    EggRelaxedArgs a;
+    EggRxCohesionFields c;
+    EggRxColliderFields d;
+};
+struct EggRelaxedGroupCohColArgs {
+    EggRelaxedArgs a;
+    EggRxGroupFields g;
+    EggRxCohesionFields c;
+    EggRxColliderFields d;
+};
+
 // A ghost record: a particle of a sender j that lies within one cell of a receiver k's cell box (40 bytes).
 struct EggGhost {
     double x, y, inv_mass, radius;

@@ -82,6 +82,10 @@ extern "C" __global__ void egg_rx_rank_coh_kernel(EggRelaxedCohArgs A);
 extern "C" __global__ void egg_rx_gather_coh_kernel(EggRelaxedCohArgs A);
 extern "C" __global__ void egg_rx_rank_group_coh_kernel(EggRelaxedGroupCohArgs A);
 extern "C" __global__ void egg_rx_gather_group_coh_kernel(EggRelaxedGroupCohArgs A);
+extern "C" __global__ void egg_rx_gather_col_kernel(EggRelaxedColArgs A);
+extern "C" __global__ void egg_rx_gather_group_col_kernel(EggRelaxedGroupColArgs A);
+extern "C" __global__ void egg_rx_gather_coh_col_kernel(EggRelaxedCohColArgs A);
+extern "C" __global__ void egg_rx_gather_group_coh_col_kernel(EggRelaxedGroupCohColArgs A);
 extern "C" __global__ void egg_rx_gkey_kernel(const int32_t *, const int32_t *, const int32_t *, int, int32_t *);
 extern "C" __global__ void egg_rx_pack_kernel(EggRxPackArgs P);
 extern "C" __global__ void egg_rx_unpack_kernel(EggRxUnpackArgs U);
@@ -393,6 +397,11 @@ struct egg_handle {
     int opt_solver_order = 0;       // EGG_OPT_SOLVER_ORDER: 0 exact (the reference's pair order), 1 relaxed
     double opt_relaxation = EGG_RELAXATION_DEFAULT;  // EGG_OPT_RELAXATION: omega of the relaxed pass
     int opt_cohesion = 0;           // EGG_OPT_COHESION: 0 dead as in the reference, 1 effective (relaxed order only)
+    // static colliders (egg_set_colliders; relaxed order only): the list as egg_get_colliders returns it, its copy on the
+    // device (written when the list is set, never per step), and the hits of committed steps per type
+    std::vector<egg_collider> colliders;
+    DevBuf<EggCollider> d_colliders;
+    int64_t collider_hits[2] = {0, 0};
     int opt_force_cell_hash = 0;     // test hook: every launch class keys its cells by the LDS hash table, never the dense grid
     int opt_force_global_state = 0;  // test hook: run every tile through the global-memory-state kernel  // threads per particle in the step kernel's workgroups (pair dataflow spreading)
     hipDeviceProp_t prop{};
@@ -533,16 +542,19 @@ constexpr int64_t kRelaxedMaxParticles = (int64_t)1 << 29;  // of one type, over
 constexpr char kRelaxedBadCellText[] = "relaxed order: a position is NaN or its spatial-hash cell lies outside +-2^30";
 // Status words of one type: [0] bad cell, [1 + p] pairs of pass p (P = S C passes); with a halo besides, per pass, the
 // cell box of its positions, the ghost entries received and -- device groups, nq handles holding the type -- the
-// records sent to each of them.  With effective cohesion one more word, the last: the pairs that cohered.
+// records sent to each of them.  With effective cohesion one more word: the pairs that cohered.  With colliders one
+// more, the last: their hits.
 struct RelaxedLayout {
     size_t P = 0, nq = 0;
     bool halo = false;  // ghosts of other handles' particles take part: the group instantiations of the kernels
     bool cohesion = false;  // (set by prepare_type from the handle's option)
+    bool colliders = false;  // (set by prepare_type: the handle's collider list is not empty)
     size_t box(size_t p) const { return 1 + P + 4 * p; }                      // 4 words
     size_t ghosts(size_t p) const { return 1 + 5 * P + p; }
     size_t sent(size_t p, size_t m) const { return 1 + 6 * P + p * nq + m; }  // to participant m
     size_t cohered() const { return halo ? 1 + 6 * P + P * nq : 1 + P; }
-    size_t words() const { return cohered() + (cohesion ? 1 : 0); }
+    size_t hits() const { return cohered() + (cohesion ? 1 : 0); }
+    size_t words() const { return hits() + (colliders ? 1 : 0); }
 };
 struct RelaxedStep {  // one type of one handle in a relaxed step
     egg_handle *h = nullptr;
@@ -551,6 +563,7 @@ struct RelaxedStep {  // one type of one handle in a relaxed step
     RelaxedLayout L;
     EggRelaxedGroupArgs A{};  // (A.g stays null without a halo)
     EggRxCohesionFields coh{};  // effective cohesion (L.cohesion): compliance and factor of the type, the tag arrays
+    EggRxColliderFields col{};  // static colliders (L.colliders): the handle's list, the type's bit, the hit counter
     int64_t ghost_cap = 0;    // a pass runs over n + ghost_cap entries
     int launches = 0;         // kernel launches so far: into the statistics at the commit
 };

@@ -940,6 +940,8 @@ int egg_set_option(egg_handle *h, int option, double value) {
                 return fail(h, EGG_ERR_INVALID_ARGUMENT, "solver order must be 0 (exact) or 1 (relaxed)");
             if (value == EGG_SOLVER_EXACT && h->opt_cohesion != EGG_COHESION_REFERENCE)
                 return fail(h, EGG_ERR_UNSUPPORTED, "exact order has no effective cohesion: switch cohesion off first (EGG_OPT_COHESION = 0)");
+            if (value == EGG_SOLVER_EXACT && !h->colliders.empty())
+                return fail(h, EGG_ERR_UNSUPPORTED, "exact order has no colliders: clear the list first (egg_set_colliders with n = 0)");
             if ((int)value != h->opt_solver_order) {
                 if (value == EGG_SOLVER_EXACT) leave_relaxed(h);
                 else
@@ -967,6 +969,74 @@ int egg_set_option(egg_handle *h, int option, double value) {
         default:
             return fail(h, EGG_ERR_INVALID_ARGUMENT, "unknown option %d", option);
     }
+}
+
+// Static colliders of the relaxed pass ("Colliders").  Everything is checked before anything
+// changes: a refused call leaves the list, its device copy and the counters as they were.
+int egg_set_colliders(egg_handle *h, int32_t n, const egg_collider *c) {
+    if (!h) return EGG_ERR_INVALID_ARGUMENT;
+    REJECT_IN_FLIGHT(h, "egg_set_colliders");
+    if (n < 0 || n > EGG_MAX_COLLIDERS)
+        return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_colliders: n = %d, a list holds 0 .. %d colliders", (int)n, EGG_MAX_COLLIDERS);
+    if (n > 0 && !c) return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_colliders: n = %d without a list", (int)n);
+    static_assert(sizeof(egg_collider) == 40 && sizeof(EggCollider) == sizeof(egg_collider), "a collider record is 40 bytes");
+    static_assert(EGG_MAX_COLLIDERS == EGG_RX_MAX_COLLIDERS && EGG_COLLIDER_HALF_PLANE == EGG_RX_COLLIDER_HALF_PLANE &&
+                      EGG_COLLIDER_DISC == EGG_RX_COLLIDER_DISC && EGG_COLLIDER_CONTAINER == EGG_RX_COLLIDER_CONTAINER &&
+                      EGG_COLLIDER_SEGMENT == EGG_RX_COLLIDER_SEGMENT,
+                  "the kernel's collider constants are the ABI's");
+    std::vector<egg_collider> list((size_t)n);
+    for (int32_t k = 0; k < n; ++k) {
+        egg_collider &o = list[(size_t)k];
+        o = c[k];
+        static const char *const names[4] = {"half-plane", "disc", "container", "segment"};
+        if (o.kind < EGG_COLLIDER_HALF_PLANE || o.kind > EGG_COLLIDER_SEGMENT)
+            return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_colliders: collider %d: unknown kind %d", (int)k, (int)o.kind);
+        if (o.type_mask < 1 || o.type_mask > 3)
+            return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_colliders: collider %d: type_mask %d (bit 0 white, bit 1 yolk, never 0)", (int)k,
+                        (int)o.type_mask);
+        const int used = o.kind == EGG_COLLIDER_SEGMENT ? 4 : 3;
+        for (int q = 0; q < 4; ++q) {
+            if (q >= used) o.p[q] = 0.0;  // (not a parameter of the kind)
+            if (!std::isfinite(o.p[q]))
+                return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_colliders: collider %d (%s): parameter %d is not finite", (int)k,
+                            names[o.kind], q);
+        }
+        if ((o.kind == EGG_COLLIDER_DISC || o.kind == EGG_COLLIDER_CONTAINER) && o.p[2] < 0)
+            return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_colliders: collider %d (%s): radius %g is negative", (int)k, names[o.kind], o.p[2]);
+        if (o.kind == EGG_COLLIDER_HALF_PLANE) {  // the normal is normalised once, here
+            const double len = std::sqrt(o.p[0] * o.p[0] + o.p[1] * o.p[1]);
+            if (!(len >= h->sys[0].cfg.eps) || !std::isfinite(len))
+                return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_colliders: collider %d (half-plane): the normal's length %g is below eps or not finite",
+                            (int)k, len);
+            o.p[0] = o.p[0] / len;
+            o.p[1] = o.p[1] / len;
+        }
+    }
+    if (n > 0 && h->opt_solver_order != EGG_SOLVER_RELAXED)
+        return fail(h, EGG_ERR_UNSUPPORTED, "egg_set_colliders: colliders need relaxed order (EGG_OPT_SOLVER_ORDER = 1 first)");
+    if (n > 0) {  // (no step is running: every step ends with its streams waited for)
+        HIP_TRY(h, hipSetDevice(h->device));
+        HIP_TRY(h, h->d_colliders.reserve(EGG_MAX_COLLIDERS, false, nullptr));
+        HIP_TRY(h, hipMemcpy(h->d_colliders.p, list.data(), (size_t)n * sizeof(egg_collider), hipMemcpyHostToDevice));
+    }
+    h->colliders.swap(list);
+    return EGG_OK;
+}
+
+int egg_get_colliders(const egg_handle *h, int32_t cap, egg_collider *c, int32_t *n) {
+    if (!h) return EGG_ERR_INVALID_ARGUMENT;
+    const int32_t have = (int32_t)h->colliders.size();
+    if (n) *n = have;
+    if (c && cap > 0) memcpy(c, h->colliders.data(), (size_t)std::min(cap, have) * sizeof(egg_collider));
+    return EGG_OK;
+}
+
+int egg_get_collider_hits(egg_handle *h, int64_t hits[2]) {
+    if (!h) return EGG_ERR_INVALID_ARGUMENT;
+    if (!hits) return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_get_collider_hits: hits is NULL");
+    hits[0] = h->collider_hits[0];
+    hits[1] = h->collider_hits[1];
+    return EGG_OK;
 }
 
 }  // extern "C"

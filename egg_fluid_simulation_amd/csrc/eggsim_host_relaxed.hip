@@ -14,6 +14,8 @@
 // With effective cohesion (EGG_OPT_COHESION = 1, RelaxedLayout::cohesion) launch_pass picks the cohesive instantiations
 // of the rank and gather kernels and RelaxedStep::coh carries the type's compliance, factor and tag arrays; a step with
 // cohesion off launches what it always launched, so all three paths pick cohesion up from here.
+// With static colliders (egg_set_colliders, RelaxedLayout::colliders) launch_pass picks the collider instantiation of the
+// gather kernel and RelaxedStep::col carries the handle's list; with an empty list a step launches what it always launched.
 #include <hipcub/hipcub.hpp>
 
 #include "eggsim_host.h"
@@ -160,6 +162,7 @@ int prepare_type(RelaxedStep &st, int C, size_t ghosts, const RelaxedLayout &L, 
     const size_t n = (size_t)s.n;
     st.L = L;
     st.L.cohesion = h->opt_cohesion == EGG_COHESION_EFFECTIVE;
+    st.L.colliders = !h->colliders.empty();
     st.C = C;
     st.ghost_cap = (int64_t)ghosts;
     int rc = reserve_relaxed(h, s, ghosts, st.L.words());
@@ -174,6 +177,13 @@ int prepare_type(RelaxedStep &st, int C, size_t ghosts, const RelaxedLayout &L, 
         st.coh.factor = s.cfg.cohesion_interaction_distance_factor;
         st.coh.stag = r.stag.p;
         st.coh.solves = r.status.p + st.L.cohered();
+    }
+    st.col = EggRxColliderFields{};
+    if (st.L.colliders) {
+        st.col.list = h->d_colliders.p;
+        st.col.count = (int32_t)h->colliders.size();
+        st.col.type_bit = 1 << st.w;
+        st.col.hits = r.status.p + st.L.hits();
     }
     if (!L.halo) return EGG_OK;
     const bool rebuild = r.key_sig != sig || r.ekey.cap < n + ghosts;  // (or a new array)
@@ -250,20 +260,32 @@ int launch_pass(RelaxedStep &st, int p) {
         if (st.L.cohesion) {
             const EggRelaxedGroupCohArgs k{a.a, a.g, st.coh};
             hipLaunchKernelGGL(egg_rx_rank_group_coh_kernel, grid, block, 0, s.stream, k);
-            hipLaunchKernelGGL(egg_rx_gather_group_coh_kernel, grid, block, 0, s.stream, k);
+            if (st.L.colliders)
+                hipLaunchKernelGGL(egg_rx_gather_group_coh_col_kernel, grid, block, 0, s.stream, EggRelaxedGroupCohColArgs{a.a, a.g, st.coh, st.col});
+            else
+                hipLaunchKernelGGL(egg_rx_gather_group_coh_kernel, grid, block, 0, s.stream, k);
         } else {
             hipLaunchKernelGGL(egg_rx_rank_group_kernel, grid, block, 0, s.stream, a);
-            hipLaunchKernelGGL(egg_rx_gather_group_kernel, grid, block, 0, s.stream, a);
+            if (st.L.colliders)
+                hipLaunchKernelGGL(egg_rx_gather_group_col_kernel, grid, block, 0, s.stream, EggRelaxedGroupColArgs{a.a, a.g, st.col});
+            else
+                hipLaunchKernelGGL(egg_rx_gather_group_kernel, grid, block, 0, s.stream, a);
         }
     } else {
         hipLaunchKernelGGL(egg_rx_scatter_kernel, grid, block, 0, s.stream, a.a);
         if (st.L.cohesion) {
             const EggRelaxedCohArgs k{a.a, st.coh};
             hipLaunchKernelGGL(egg_rx_rank_coh_kernel, grid, block, 0, s.stream, k);
-            hipLaunchKernelGGL(egg_rx_gather_coh_kernel, grid, block, 0, s.stream, k);
+            if (st.L.colliders)
+                hipLaunchKernelGGL(egg_rx_gather_coh_col_kernel, grid, block, 0, s.stream, EggRelaxedCohColArgs{a.a, st.coh, st.col});
+            else
+                hipLaunchKernelGGL(egg_rx_gather_coh_kernel, grid, block, 0, s.stream, k);
         } else {
             hipLaunchKernelGGL(egg_rx_rank_kernel, grid, block, 0, s.stream, a.a);
-            hipLaunchKernelGGL(egg_rx_gather_kernel, grid, block, 0, s.stream, a.a);
+            if (st.L.colliders)
+                hipLaunchKernelGGL(egg_rx_gather_col_kernel, grid, block, 0, s.stream, EggRelaxedColArgs{a.a, st.col});
+            else
+                hipLaunchKernelGGL(egg_rx_gather_kernel, grid, block, 0, s.stream, a.a);
         }
     }
     st.launches += 5;
@@ -350,6 +372,7 @@ void relaxed_commit(egg_handle *h, const RelaxedStep st[2], int S, int C, double
         }
         h->stats.max_pass_visits[w] = most;
         if (st[w].L.cohesion) h->stats.cohesion_solves += (int64_t)s.rx.h_status.p[st[w].L.cohered()];
+        if (st[w].L.colliders) h->collider_hits[w] += (int64_t)s.rx.h_status.p[st[w].L.hits()];
         h->stats.follow_solves += s.n * S;
         // the exact path's host copies of the atoms' cells describe older positions now
         s.aabb_valid = s.aabb_on_device = s.disp_valid = false;

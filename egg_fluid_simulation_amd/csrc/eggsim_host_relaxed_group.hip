@@ -107,6 +107,13 @@ int relaxed_group_step(egg_handle *const *hs, int nh, double delta, int S, int C
             *error = "relaxed order: the handles of the group differ in EGG_OPT_COHESION (egg_group_set_cohesion sets all)";
             return EGG_ERR_INVALID_ARGUMENT;
         }
+    for (int k = 1; k < nh; ++k) {
+        const std::vector<egg_collider> &a = hs[0]->colliders, &b = hs[k]->colliders;
+        if (a.size() != b.size() || (!a.empty() && memcmp(a.data(), b.data(), a.size() * sizeof(egg_collider)) != 0)) {
+            *error = "relaxed order: the handles of the group differ in their colliders (egg_group_set_colliders sets all)";
+            return EGG_ERR_INVALID_ARGUMENT;
+        }
+    }
     for (int k = 0; k < nh; ++k) {
         (void)hipSetDevice(hs[k]->device);
         GK_TRY(k, prepare_step(hs[k], delta, S, st[k]));

@@ -26,6 +26,11 @@
 // back to the collision distance through the collision correction's own arithmetic with the cohesion compliance.  The
 // K = false instantiations are the kernels as they were.
 //
+// With static colliders (egg_set_colliders; DESIGN.md section 2.7, "Colliders") the gather kernel runs in its collider
+// instantiations (D = true, egg_rx_gather*_col_kernel): the position a particle is about to get is projected out of /
+// into every collider of the handle's list whose mask covers the type, in list order, before it is written.  The
+// D = false instantiations are the kernels as they were.
+//
 // All arithmetic is IEEE double in the order of the definition: compile with -ffp-contract=off.
 #include <hip/hip_runtime.h>
 #include "eggsim_device.h"
@@ -74,6 +79,68 @@ __device__ __forceinline__ uint32_t rx_hash(unsigned long long k) {  // the 64-b
     k *= 0xc4ceb9fe1a85ec53ull;
     k ^= k >> 33;
     return (uint32_t)k;
+}
+
+// Step 5b of the relaxed pass: the colliders of the list whose mask covers the type, in list order, each on the result
+// of the one before it.  i: the particle's key (picks the way out of a disc's centre); r: its radius.  Every lane of a
+// wave reads the same record and takes the same branch on its kind.  Every comparison is false for a NaN: such a
+// position stays.  Returns the colliders that moved the particle.
+__device__ __forceinline__ int rx_collide(const EggRxColliderFields &Co, int i, double r, double2 &out) {
+    int hits = 0;
+    for (int c = 0; c < Co.count; ++c) {
+        const EggCollider col = Co.list[c];
+        if (!(col.type_mask & Co.type_bit)) continue;
+        const double x = out.x, y = out.y;
+        if (col.kind == EGG_RX_COLLIDER_HALF_PLANE) {  // p = (nx, ny, off): keeps n . pos - off >= r
+            const double s = (col.p[0] * x + col.p[1] * y) - (col.p[2] + r);
+            if (s < 0.0) {
+                out.x = x - s * col.p[0];
+                out.y = y - s * col.p[1];
+                ++hits;
+            }
+            continue;
+        }
+        double cx = col.p[0], cy = col.p[1], R = col.p[2];
+        if (col.kind == EGG_RX_COLLIDER_SEGMENT) {  // p = (x0, y0, x1, y1): a disc of radius 0 at the nearest point
+            const double ex = col.p[2] - col.p[0], ey = col.p[3] - col.p[1];
+            const double l2 = ex * ex + ey * ey;
+            double t = l2 == 0.0 ? 0.0 : ((x - col.p[0]) * ex + (y - col.p[1]) * ey) / l2;
+            if (t < 0.0) t = 0.0;
+            if (t > 1.0) t = 1.0;
+            cx = col.p[0] + t * ex;
+            cy = col.p[1] + t * ey;
+            R = 0.0;
+        }
+        const double dx = x - cx, dy = y - cy;
+        const double d2 = dx * dx + dy * dy;
+        if (col.kind == EGG_RX_COLLIDER_CONTAINER) {  // p = (cx, cy, R): stays inside
+            double m = R - r;
+            if (m < 0.0) m = 0.0;
+            if (d2 > m * m) {
+                const double d = sqrt(d2);
+                out.x = cx + (dx / d) * m;
+                out.y = cy + (dy / d) * m;
+                ++hits;
+            }
+        } else {  // disc, p = (cx, cy, R): stays outside
+            const double m = R + r;
+            if (d2 < m * m) {
+                const double d = sqrt(d2);
+                double ux, uy;
+                if (d2 == 0.0) {
+                    ux = kRxDirX[i & 7];
+                    uy = kRxDirY[i & 7];
+                } else {
+                    ux = dx / d;
+                    uy = dy / d;
+                }
+                out.x = cx + ux * m;
+                out.y = cy + uy * m;
+                ++hits;
+            }
+        }
+    }
+    return hits;
 }
 
 }  // namespace
@@ -214,12 +281,15 @@ __device__ __forceinline__ void rx_rank(const EggRelaxedArgs &A, const EggRxGrou
 // The relaxed pass of DESIGN.md section 2.7, one thread per grouped slot (threads of a wave share cells).  i is the
 // key; in a group a ghost's slot gathers nothing (its own device moves it), and the gather records the box of what it
 // writes when the pass is not the sub-step's last.  K: a pair that does not collide may cohere -- same tag, within reach
-// -- and then runs the collision correction's arithmetic with the cohesion compliance (one path for both kinds).
-template <bool G, bool K>
-__device__ __forceinline__ void rx_gather(EggRelaxedArgs A, const EggRxGroupFields &X, const EggRxCohesionFields &Ch) {
+// -- and then runs the collision correction's arithmetic with the cohesion compliance (one path for both kinds).  D: the
+// new position goes through the colliders before it is written (whether or not a pair fired).
+template <bool G, bool K, bool D>
+__device__ __forceinline__ void rx_gather(EggRelaxedArgs A, const EggRxGroupFields &X, const EggRxCohesionFields &Ch,
+                                          const EggRxColliderFields &Co) {
     const int t = (int)(blockIdx.x * 256 + threadIdx.x);
     int pairs = 0;
     int cohered = 0;  // (K only)
+    int hits = 0;     // (D only)
     bool local = false;  // (group: the slot holds one of this device's particles; gout is its new position)
     double2 gout = make_double2(0.0, 0.0);
     if (G ? t < rx_entries<G>(A, X) && X.sloc[t] < A.n : t < A.n) {
@@ -302,6 +372,7 @@ __device__ __forceinline__ void rx_gather(EggRelaxedArgs A, const EggRxGroupFiel
             out.x = p.x + (sx * A.omega) / (double)n_fired;
             out.y = p.y + (sy * A.omega) / (double)n_fired;
         }
+        if (D) hits = rx_collide(Co, i, wr.y, out);
         A.pos_next[me] = out;
         if (G) {
             local = true;
@@ -317,6 +388,11 @@ __device__ __forceinline__ void rx_gather(EggRelaxedArgs A, const EggRxGroupFiel
         for (int d = 32; d >= 1; d >>= 1) cohered += __shfl_xor(cohered, d, 64);
         if ((threadIdx.x & 63) == 0 && cohered) atomicAdd(Ch.solves, (unsigned long long)cohered);
     }
+    if (D) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) hits += __shfl_xor(hits, d, 64);
+        if ((threadIdx.x & 63) == 0 && hits) atomicAdd(Co.hits, (unsigned long long)hits);
+    }
     if (G && X.box) rx_box(X.box, local, gout, A.cell_size);
 }
 
@@ -326,13 +402,18 @@ extern "C" __global__ void __launch_bounds__(256) egg_rx_scatter_kernel(EggRelax
 extern "C" __global__ void __launch_bounds__(256) egg_rx_scatter_group_kernel(EggRelaxedGroupArgs A) { rx_scatter<true>(A.a, A.g); }
 extern "C" __global__ void __launch_bounds__(256) egg_rx_rank_kernel(EggRelaxedArgs A) { rx_rank<false, false>(A, EggRxGroupFields{}, EggRxCohesionFields{}); }
 extern "C" __global__ void __launch_bounds__(256) egg_rx_rank_group_kernel(EggRelaxedGroupArgs A) { rx_rank<true, false>(A.a, A.g, EggRxCohesionFields{}); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_kernel(EggRelaxedArgs A) { rx_gather<false, false>(A, EggRxGroupFields{}, EggRxCohesionFields{}); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_kernel(EggRelaxedGroupArgs A) { rx_gather<true, false>(A.a, A.g, EggRxCohesionFields{}); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_kernel(EggRelaxedArgs A) { rx_gather<false, false, false>(A, EggRxGroupFields{}, EggRxCohesionFields{}, EggRxColliderFields{}); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_kernel(EggRelaxedGroupArgs A) { rx_gather<true, false, false>(A.a, A.g, EggRxCohesionFields{}, EggRxColliderFields{}); }
 // effective cohesion
 extern "C" __global__ void __launch_bounds__(256) egg_rx_rank_coh_kernel(EggRelaxedCohArgs A) { rx_rank<false, true>(A.a, EggRxGroupFields{}, A.c); }
 extern "C" __global__ void __launch_bounds__(256) egg_rx_rank_group_coh_kernel(EggRelaxedGroupCohArgs A) { rx_rank<true, true>(A.a, A.g, A.c); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_coh_kernel(EggRelaxedCohArgs A) { rx_gather<false, true>(A.a, EggRxGroupFields{}, A.c); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_coh_kernel(EggRelaxedGroupCohArgs A) { rx_gather<true, true>(A.a, A.g, A.c); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_coh_kernel(EggRelaxedCohArgs A) { rx_gather<false, true, false>(A.a, EggRxGroupFields{}, A.c, EggRxColliderFields{}); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_coh_kernel(EggRelaxedGroupCohArgs A) { rx_gather<true, true, false>(A.a, A.g, A.c, EggRxColliderFields{}); }
+// static colliders
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_col_kernel(EggRelaxedColArgs A) { rx_gather<false, false, true>(A.a, EggRxGroupFields{}, EggRxCohesionFields{}, A.d); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_col_kernel(EggRelaxedGroupColArgs A) { rx_gather<true, false, true>(A.a, A.g, EggRxCohesionFields{}, A.d); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_coh_col_kernel(EggRelaxedCohColArgs A) { rx_gather<false, true, true>(A.a, EggRxGroupFields{}, A.c, A.d); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_coh_col_kernel(EggRelaxedGroupCohColArgs A) { rx_gather<true, true, true>(A.a, A.g, A.c, A.d); }
 
 // ---- device groups ----
 

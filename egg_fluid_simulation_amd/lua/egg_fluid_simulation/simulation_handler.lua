@@ -71,6 +71,10 @@ typedef struct {
 int egg_default_render_params(egg_render_params *p);
 int egg_render(egg_handle *h, const egg_render_params *p, float *rgba);
 int egg_set_option(egg_handle *h, int option, double value);
+typedef struct { int32_t kind; int32_t type_mask; double p[4]; } egg_collider;
+int egg_set_colliders(egg_handle *h, int32_t n, const egg_collider *c);
+int egg_get_colliders(const egg_handle *h, int32_t cap, egg_collider *c, int32_t *n);
+int egg_get_collider_hits(egg_handle *h, int64_t hits[2]);
 typedef struct egg_group egg_group;
 int egg_group_set_solver_order(egg_group *g, int32_t order, double relaxation);
 int egg_group_set_cohesion(egg_group *g, int32_t mode);
@@ -404,6 +408,53 @@ function SimulationHandler:set_cohesion(mode)
     if self:_check(lib.egg_set_option(self._h, 15, _cohesion_modes[mode])) == 0 then self._cohesion = mode end
 end
 function SimulationHandler:get_cohesion() return self._cohesion or "reference" end
+
+-- Not in the reference, which has no boundary of any kind: static colliders of the relaxed pass (egg_set_colliders in
+-- include/eggsim.h; DESIGN.md section 2.7, "Colliders").  Relaxed order only.
+local _collider_kinds = { half_plane = 0, disc = 1, container = 2, segment = 3 }
+local _collider_names = { [0] = "half_plane", "disc", "container", "segment" }
+local _collider_n_params = { [0] = 3, 3, 3, 4 }
+local _collider_types = { white = 1, yolk = 2, both = 3 }
+local _collider_type_names = { "white", "yolk", "both" }
+
+--- the ordered list of at most 64 colliders, each `{ "half_plane", nx, ny, off }`, `{ "disc", cx, cy, R }`,
+--- `{ "container", cx, cy, R }` or `{ "segment", x0, y0, x1, y1 }` with an optional `types = "both" | "white" | "yolk"`;
+--- applied in list order to every particle's new position in a relaxed pass.  `{}` clears the list.
+function SimulationHandler:set_colliders(colliders)
+    local n = #colliders
+    local arr = ffi.new("egg_collider[?]", math.max(n, 1))
+    for k, c in ipairs(colliders) do
+        local kind = _collider_kinds[c[1]]
+        local mask = _collider_types[c.types or "both"]
+        if kind == nil or mask == nil or #c ~= 1 + _collider_n_params[kind] then
+            log.error("In SimulationHandler.set_colliders: collider " .. k .. ": expected { kind, parameters..., types = ... }")
+            return
+        end
+        arr[k - 1].kind, arr[k - 1].type_mask = kind, mask
+        for q = 1, _collider_n_params[kind] do arr[k - 1].p[q - 1] = c[q + 1] end
+    end
+    self:_check(lib.egg_set_colliders(self._h, n, arr))
+end
+
+--- the list as stored (a half-plane's normal normalised), in the shapes set_colliders takes
+function SimulationHandler:get_colliders()
+    local arr, n = ffi.new("egg_collider[64]"), ffi.new("int32_t[1]")
+    if self:_check(lib.egg_get_colliders(self._h, 64, arr, n)) ~= 0 then return {} end
+    local out = {}
+    for k = 0, n[0] - 1 do
+        local c = { _collider_names[arr[k].kind], types = _collider_type_names[arr[k].type_mask] }
+        for q = 1, _collider_n_params[arr[k].kind] do c[q + 1] = arr[k].p[q - 1] end
+        out[k + 1] = c
+    end
+    return out
+end
+
+--- white, yolk: how often a collider moved a particle in a pass of a committed step
+function SimulationHandler:collider_hits()
+    local hits = ffi.new("int64_t[2]")
+    self:_check(lib.egg_get_collider_hits(self._h, hits))
+    return tonumber(hits[0]), tonumber(hits[1])
+end
 
 function SimulationHandler:draw()
     -- in a LOVE host: feed :instances() and :get_environment() to the reference's shaders and canvas code

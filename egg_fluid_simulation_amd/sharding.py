@@ -607,6 +607,20 @@ class ShardedSimulationHandler(_HandlerSurface):
     def get_cohesion(self):
         return getattr(self, "_cohesion", "reference")
 
+    def set_colliders(self, colliders):
+        """SimulationHandler.set_colliders on every rank alike (the same call on every rank; relaxed order only).  Nothing
+        new travels: every rank projects the particles it owns, before their positions go out as ghosts."""
+        self.local.set_colliders(colliders)
+
+    def get_colliders(self):
+        return self.local.get_colliders()
+
+    def collider_hits(self):
+        """SimulationHandler.collider_hits summed over the ranks (a collective: every rank calls it)"""
+        tot = self.torch.tensor(self.local.collider_hits(), dtype=self.torch.int64, device=self.device)
+        self.dist.all_reduce(tot, op=self.dist.ReduceOp.SUM)
+        return [int(v) for v in tot.tolist()]
+
     def halo_counters(self):
         """relaxed steps of this rank, summed over the run: collision passes, ghost records received, their bytes"""
         if self.halo is None:

@@ -95,6 +95,72 @@ class _HandlerSurface:
         """the C entry point `name` of this object's kind, bound to its handle"""
         return functools.partial(getattr(self._lib, self._PREFIX + name), self._ptr())
 
+    # ------------------------------------------------ static colliders (egg_set_colliders, DESIGN.md section 2.7)
+    @staticmethod
+    def _c_colliders(colliders):
+        """a list of tuples `(kind, a, b, c[, d][, types])` or dicts `{"kind": ..., <parameter names>, "types": ...}` as an
+        egg_collider array; what only the host can check (shape, names) is checked here, the values by the library"""
+        colliders = list(colliders)
+        arr = (_ffi.EggCollider * max(len(colliders), 1))()
+        for k, c in enumerate(colliders):
+            if isinstance(c, dict):
+                kind, types = c.get("kind"), c.get("types", "both")
+            else:
+                c = tuple(c)
+                kind = c[0] if c else None
+                types = "both"
+            if kind not in _ffi.COLLIDER_KINDS:
+                raise EggError("collider %d: kind must be one of %s, not %r" % (k, ", ".join(_ffi.COLLIDER_KINDS), kind))
+            code = _ffi.COLLIDER_KINDS.index(kind)
+            names = _ffi.COLLIDER_PARAMS[code]
+            if isinstance(c, dict):
+                extra = set(c) - set(names) - {"kind", "types"}
+                if extra or not all(n in c for n in names):
+                    raise EggError("collider %d (%s): expected the keys %s" % (k, kind, ", ".join(names)))
+                values = [c[n] for n in names]
+            else:
+                values = list(c[1:])
+                if len(values) == len(names) + 1 and isinstance(values[-1], str):
+                    types = values.pop()
+                if len(values) != len(names):
+                    raise EggError("collider %d (%s): expected (%r, %s[, types])" % (k, kind, kind, ", ".join(names)))
+            if not isinstance(types, str) or types not in _ffi.COLLIDER_TYPES:
+                raise EggError("collider %d: types must be 'both', 'white' or 'yolk', not %r" % (k, types))
+            try:
+                values = [float(v) for v in values]
+            except (TypeError, ValueError):
+                raise EggError("collider %d (%s): the parameters must be numbers" % (k, kind)) from None
+            arr[k].kind, arr[k].type_mask = code, _ffi.COLLIDER_TYPES[types]
+            for q, v in enumerate(values):
+                arr[k].p[q] = v
+        return len(colliders), arr
+
+    def set_colliders(self, colliders):
+        """The ordered list of static colliders, at most 64 ("Colliders"; relaxed order only):
+        `("half_plane", nx, ny, off)` keeps n . pos - off >= radius, `("disc", cx, cy, R)` is an obstacle,
+        `("container", cx, cy, R)` keeps particles inside, `("segment", x0, y0, x1, y1)` is a wall of zero thickness; each
+        takes an optional last element (or dict key) types = "both" | "white" | "yolk", and each may be a dict with "kind"
+        and the parameter names.  In a relaxed pass every particle's new position is projected collider after collider,
+        in list order.  `[]` clears the list.  Raises EggError for a bad list (nothing changes) and for a non-empty list on
+        a handle in exact order; set_solver_order("exact") raises while the list is not empty."""
+        n, arr = self._c_colliders(colliders)
+        self._check(self._c("set_colliders")(n, arr))
+
+    def get_colliders(self):
+        """the list as stored, as tuples `(kind, parameters..., types)`: a half-plane's normal comes back normalised"""
+        arr = (_ffi.EggCollider * _ffi.MAX_COLLIDERS)()
+        n = C.c_int32()
+        self._check(self._c("get_colliders")(_ffi.MAX_COLLIDERS, arr, C.byref(n)))
+        types = {v: k for k, v in _ffi.COLLIDER_TYPES.items()}
+        return [(_ffi.COLLIDER_KINDS[c.kind],) + tuple(c.p[:len(_ffi.COLLIDER_PARAMS[c.kind])]) + (types[c.type_mask],)
+                for c in arr[:n.value]]
+
+    def collider_hits(self):
+        """[white, yolk]: how often a collider moved a particle in a pass of a committed step, since creation"""
+        hits = (C.c_int64 * 2)()
+        self._check(self._c("get_collider_hits")(hits))
+        return list(hits)
+
     def _init_host_state(self, white_config, yolk_config):
         """config tables (validated like the reference, L:1253-1320), hidden constants and render switches; no device"""
         if white_config is None and yolk_config is None:

@@ -379,6 +379,44 @@ enum {
 #define EGG_RELAXATION_DEFAULT 1.8
 int egg_set_option(egg_handle *h, int option, double value);
 
+/* ---- static colliders (not in the reference, which has no boundary of any kind; DESIGN.md section 2.7, "Colliders") ----
+ * A handle holds an ordered list of at most EGG_MAX_COLLIDERS colliders.  In a RELAXED collision pass the position a
+ * particle of a type in `type_mask` (bit 0 white, bit 1 yolk) is about to get is projected rigidly, collider after
+ * collider in list order, each on the result of the one before -- whether or not a pair fired for it.  r is the
+ * particle's radius; FP64 in exactly this order, no contraction; every comparison is false for a NaN.
+ *   HALF_PLANE p = (nx, ny, off, -): keeps n . pos - off >= r.  s = (nx x + ny y) - (off + r); s < 0: x -= s nx, y -= s ny.
+ *              The normal is normalised when the list is set (len = sqrt(nx nx + ny ny); nx / len, ny / len are stored
+ *              and returned by egg_get_colliders).
+ *   DISC       p = (cx, cy, R, -): an obstacle.  dx = x - cx, dy = y - cy, d2 = dx dx + dy dy, m = R + r; d2 < m m:
+ *              d = sqrt(d2), x = cx + (dx / d) m, y = cy + (dy / d) m; at d2 == 0 the unit vector is the one a coincident
+ *              pair with key difference (key & 7) takes, the key being the particle's index in one handle holding
+ *              every batch (the global key in a group or between processes).
+ *   CONTAINER  p = (cx, cy, R, -): the particle stays inside.  m = max(R - r, 0); d2 > m m: x = cx + (dx / d) m, y likewise.
+ *   SEGMENT    p = (x0, y0, x1, y1): a wall of zero thickness.  e = p1 - p0, l2 = e . e,
+ *              t = l2 == 0 ? 0 : clamp(((x - x0) ex + (y - y0) ey) / l2, 0, 1), q = p0 + t e; then DISC with centre q, R = 0.
+ * Parameters a kind does not use are stored as 0.  The projection has no compliance, mass, friction or omega; velocities
+ * follow from the post-solve, so a wall absorbs the normal velocity.  Colliders are not drawn.  Applied in list order, a
+ * particle in a corner satisfies the last collider exactly and the earlier ones only approximately.
+ * Relaxed order only, as EGG_OPT_COHESION = 1: a non-empty list on a handle in exact order is EGG_ERR_UNSUPPORTED, and
+ * EGG_OPT_SOLVER_ORDER = 0 is EGG_ERR_UNSUPPORTED while the list is not empty; an empty list is always accepted.
+ * egg_set_colliders checks everything before it changes anything: EGG_ERR_INVALID_ARGUMENT, with the collider's index in
+ * the message, for n outside 0 .. EGG_MAX_COLLIDERS, an unknown kind, a mask that is 0 or has bits beyond 3, a parameter
+ * that is not finite, R < 0, a normal shorter than the white config's eps.  Refused while a step is in flight.  The list
+ * goes to the device when it is set, never per step; with an empty list a step launches exactly what it launches without. */
+#define EGG_MAX_COLLIDERS 64
+enum { EGG_COLLIDER_HALF_PLANE = 0, EGG_COLLIDER_DISC = 1, EGG_COLLIDER_CONTAINER = 2, EGG_COLLIDER_SEGMENT = 3 };
+typedef struct {
+    int32_t kind;      /* EGG_COLLIDER_* */
+    int32_t type_mask; /* bit 0 white, bit 1 yolk; never 0 */
+    double p[4];
+} egg_collider; /* 40 bytes */
+int egg_set_colliders(egg_handle *h, int32_t n, const egg_collider *c); /* n == 0 clears */
+/* the list as stored (normals normalised): the count in *n, min(*n, cap) colliders copied */
+int egg_get_colliders(const egg_handle *h, int32_t cap, egg_collider *c, int32_t *n);
+/* hits per type since the handle was created: one collider moving one particle in one pass is one hit.  Only committed
+ * steps count: a step that fails or is discarded adds nothing. */
+int egg_get_collider_hits(egg_handle *h, int64_t hits[2]);
+
 /* ---- several GPUs in one process (csrc/eggsim_group.cpp) -------------------------------------------------------
  * The multi-device form of the handle for a host that is ONE process (the LuaJIT wrapper): one egg_handle per device
  * behind one egg_group, x-slabs [cuts[k], cuts[k + 1]) of the plane per device (cuts: n_devices + 1 ascending values;
@@ -421,6 +459,12 @@ int egg_group_set_solver_order(egg_group *g, int32_t order, double relaxation);
  * cohesion off).  A refused value changes no handle.  Ghost records stay 40 bytes: a ghost's batch tag travels in the upper
  * 32 bits of its key word. */
 int egg_group_set_cohesion(egg_group *g, int32_t mode);
+/* egg_set_colliders for every handle of the group alike, with its rules (relaxed order only; back to exact order only
+ * with an empty list); a refused list changes no handle.  Every device projects only the particles it owns, before their
+ * positions travel as ghosts: the results equal one handle's.  The hits are summed over the handles. */
+int egg_group_set_colliders(egg_group *g, int32_t n, const egg_collider *c);
+int egg_group_get_colliders(const egg_group *g, int32_t cap, egg_collider *c, int32_t *n);
+int egg_group_get_collider_hits(egg_group *g, int64_t hits[2]);
 /* cumulative over relaxed group steps, both types: collision passes, ghost records the devices received, their bytes */
 int egg_group_get_halo_counters(const egg_group *g, int64_t *passes, int64_t *records, int64_t *bytes);
 
