@@ -111,6 +111,17 @@ COLLIDER_PARAMS = (("nx", "ny", "off"), ("cx", "cy", "R"), ("cx", "cy", "R"), ("
 COLLIDER_TYPES = {"white": 1, "yolk": 2, "both": 3}  # type_mask
 
 
+class EggForce(C.Structure):  # egg_force: a force field of the relaxed step (40 bytes)
+    _fields_ = [("kind", C.c_int32), ("type_mask", C.c_int32), ("p", C.c_double * 4)]
+
+
+MAX_FORCES = 16  # EGG_MAX_FORCES
+FORCE_UNIFORM, FORCE_RADIAL, FORCE_VORTEX = 0, 1, 2
+FORCE_KINDS = ("uniform", "radial", "vortex")  # by EGG_FORCE_* value
+FORCE_PARAMS = (("gx", "gy"), ("cx", "cy", "strength", "R"), ("cx", "cy", "strength", "R"))
+FORCE_TYPES = COLLIDER_TYPES  # type_mask
+
+
 class EggRxBox(C.Structure):  # egg_rx_box: a cell box of the relaxed halo between processes
     _fields_ = [("lo_x", C.c_int32), ("lo_y", C.c_int32), ("hi_x", C.c_int32), ("hi_y", C.c_int32), ("empty", C.c_int32)]
 
@@ -167,6 +178,10 @@ _SIGNATURES = {
     "egg_group_set_colliders": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggCollider)]),
     "egg_group_get_colliders": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggCollider), C.POINTER(C.c_int32)]),
     "egg_group_get_collider_hits": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "egg_set_forces": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggForce)]),
+    "egg_get_forces": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggForce), C.POINTER(C.c_int32)]),
+    "egg_group_set_forces": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggForce)]),
+    "egg_group_get_forces": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggForce), C.POINTER(C.c_int32)]),
     "egg_group_get_halo_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "egg_group_set_config": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(EggConfig)]),
     "egg_group_get_config": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(EggConfig)]),

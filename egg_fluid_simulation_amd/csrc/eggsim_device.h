@@ -359,6 +359,32 @@ struct EggRelaxedGroupCohColArgs {
     EggRxColliderFields d;
 };
 
+// Force fields (egg_set_forces, DESIGN.md section 2.7, "Forces"): the force instantiations of the kernels that begin a
+// sub-step (egg_rx_begin*_frc_kernel, egg_rx_mid*_frc_kernel) take these besides.  The list is the handle's, in a small
+// device buffer written when it is set; a record has the layout of the ABI's egg_force (40 bytes).
+#define EGG_RX_MAX_FORCES 16
+#define EGG_RX_FORCE_UNIFORM 0  // = EGG_FORCE_* of include/eggsim.h
+#define EGG_RX_FORCE_RADIAL 1
+#define EGG_RX_FORCE_VORTEX 2
+struct EggForce {
+    int32_t kind, type_mask;
+    double p[4];
+};
+struct EggRxForceFields {
+    const EggForce *list;                // [count], summed in this order; every lane reads the same record
+    int32_t count;
+    int32_t type_bit;                    // 1 white, 2 yolk: a field acts when its type_mask has the bit
+};
+struct EggRelaxedFrcArgs {
+    EggRelaxedArgs a;
+    EggRxForceFields f;
+};
+struct EggRelaxedGroupFrcArgs {
+    EggRelaxedArgs a;
+    EggRxGroupFields g;
+    EggRxForceFields f;
+};
+
 // A ghost record: a particle of a sender j that lies within one cell of a receiver k's cell box (40 bytes).
 struct EggGhost {
     double x, y, inv_mass, radius;

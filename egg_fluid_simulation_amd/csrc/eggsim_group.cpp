@@ -64,6 +64,7 @@ struct egg_group {
     int order = EGG_SOLVER_EXACT;
     int cohesion = EGG_COHESION_REFERENCE;  // egg_group_set_cohesion: every handle's EGG_OPT_COHESION
     std::vector<egg_collider> colliders;    // egg_group_set_colliders: every handle's list, as given
+    std::vector<egg_force> forces;          // egg_group_set_forces: every handle's list, as given
     int64_t halo_passes = 0, halo_records = 0;  // relaxed group steps: collision passes, ghost records received
     int64_t steps = 0;  // _step calls committed by the group
     // render attributes (never read by the solver): they live here, per global id / per type, so that a hand-over
@@ -604,6 +605,8 @@ int egg_group_set_solver_order(egg_group *g, int32_t order, double relaxation) {
         return gfail(g, EGG_ERR_UNSUPPORTED, "egg_group_set_solver_order: exact order has no effective cohesion: switch cohesion off first (egg_group_set_cohesion)");
     if (order == EGG_SOLVER_EXACT && !g->colliders.empty())
         return gfail(g, EGG_ERR_UNSUPPORTED, "egg_group_set_solver_order: exact order has no colliders: clear the list first (egg_group_set_colliders with n = 0)");
+    if (order == EGG_SOLVER_EXACT && !g->forces.empty())
+        return gfail(g, EGG_ERR_UNSUPPORTED, "egg_group_set_solver_order: exact order has no force fields: clear the list first (egg_group_set_forces with n = 0)");
     if (order == EGG_SOLVER_RELAXED && g->h.size() > 1) {  // the ghost halo reads the other devices' memory
         std::string err;
         const int rc = egghost::relaxed_group_peers(g->h.data(), (int)g->h.size(), &err);
@@ -664,6 +667,24 @@ int egg_group_get_collider_hits(egg_group *g, int64_t hits[2]) {
         hits[1] += one[1];
     }
     return EGG_OK;
+}
+
+int egg_group_set_forces(egg_group *g, int32_t n, const egg_force *f) {
+    if (!g) return EGG_ERR_INVALID_ARGUMENT;
+    for (size_t k = 0; k < g->h.size(); ++k) {
+        const int rc = egg_set_forces(g->h[k], n, f);
+        if (rc < 0) {  // (handle 0 refuses a bad list before any handle has changed; a later one: the others go back)
+            for (size_t j = 0; j < k; ++j) (void)egg_set_forces(g->h[j], (int32_t)g->forces.size(), g->forces.data());
+            return gfail(g, rc, "device %d: %s", (int)k, egg_last_error(g->h[k]));
+        }
+    }
+    g->forces.assign(f, f + (n > 0 ? n : 0));
+    return EGG_OK;
+}
+
+int egg_group_get_forces(const egg_group *g, int32_t cap, egg_force *f, int32_t *n) {
+    if (!g || g->h.empty()) return EGG_ERR_INVALID_ARGUMENT;
+    return egg_get_forces(g->h[0], cap, f, n);  // (as stored: every handle holds the same list)
 }
 
 int egg_group_get_halo_counters(const egg_group *g, int64_t *passes, int64_t *records, int64_t *bytes) {

@@ -86,6 +86,10 @@ extern "C" __global__ void egg_rx_gather_col_kernel(EggRelaxedColArgs A);
 extern "C" __global__ void egg_rx_gather_group_col_kernel(EggRelaxedGroupColArgs A);
 extern "C" __global__ void egg_rx_gather_coh_col_kernel(EggRelaxedCohColArgs A);
 extern "C" __global__ void egg_rx_gather_group_coh_col_kernel(EggRelaxedGroupCohColArgs A);
+extern "C" __global__ void egg_rx_begin_frc_kernel(EggRelaxedFrcArgs A);
+extern "C" __global__ void egg_rx_mid_frc_kernel(EggRelaxedFrcArgs A);
+extern "C" __global__ void egg_rx_begin_group_frc_kernel(EggRelaxedGroupFrcArgs A);
+extern "C" __global__ void egg_rx_mid_group_frc_kernel(EggRelaxedGroupFrcArgs A);
 extern "C" __global__ void egg_rx_gkey_kernel(const int32_t *, const int32_t *, const int32_t *, int, int32_t *);
 extern "C" __global__ void egg_rx_pack_kernel(EggRxPackArgs P);
 extern "C" __global__ void egg_rx_unpack_kernel(EggRxUnpackArgs U);
@@ -402,6 +406,10 @@ struct egg_handle {
     std::vector<egg_collider> colliders;
     DevBuf<EggCollider> d_colliders;
     int64_t collider_hits[2] = {0, 0};
+    // force fields (egg_set_forces; relaxed order only): the list as egg_get_forces returns it and its copy on the device
+    // (written when the list is set, never per step)
+    std::vector<egg_force> forces;
+    DevBuf<EggForce> d_forces;
     int opt_force_cell_hash = 0;     // test hook: every launch class keys its cells by the LDS hash table, never the dense grid
     int opt_force_global_state = 0;  // test hook: run every tile through the global-memory-state kernel  // threads per particle in the step kernel's workgroups (pair dataflow spreading)
     hipDeviceProp_t prop{};
@@ -549,6 +557,7 @@ struct RelaxedLayout {
     bool halo = false;  // ghosts of other handles' particles take part: the group instantiations of the kernels
     bool cohesion = false;  // (set by prepare_type from the handle's option)
     bool colliders = false;  // (set by prepare_type: the handle's collider list is not empty)
+    bool forces = false;     // (set by prepare_type: the handle's force list is not empty; no status word of its own)
     size_t box(size_t p) const { return 1 + P + 4 * p; }                      // 4 words
     size_t ghosts(size_t p) const { return 1 + 5 * P + p; }
     size_t sent(size_t p, size_t m) const { return 1 + 6 * P + p * nq + m; }  // to participant m
@@ -564,6 +573,7 @@ struct RelaxedStep {  // one type of one handle in a relaxed step
     EggRelaxedGroupArgs A{};  // (A.g stays null without a halo)
     EggRxCohesionFields coh{};  // effective cohesion (L.cohesion): compliance and factor of the type, the tag arrays
     EggRxColliderFields col{};  // static colliders (L.colliders): the handle's list, the type's bit, the hit counter
+    EggRxForceFields frc{};     // force fields (L.forces): the handle's list, the type's bit
     int64_t ghost_cap = 0;    // a pass runs over n + ghost_cap entries
     int launches = 0;         // kernel launches so far: into the statistics at the commit
 };

@@ -942,6 +942,8 @@ int egg_set_option(egg_handle *h, int option, double value) {
                 return fail(h, EGG_ERR_UNSUPPORTED, "exact order has no effective cohesion: switch cohesion off first (EGG_OPT_COHESION = 0)");
             if (value == EGG_SOLVER_EXACT && !h->colliders.empty())
                 return fail(h, EGG_ERR_UNSUPPORTED, "exact order has no colliders: clear the list first (egg_set_colliders with n = 0)");
+            if (value == EGG_SOLVER_EXACT && !h->forces.empty())
+                return fail(h, EGG_ERR_UNSUPPORTED, "exact order has no force fields: clear the list first (egg_set_forces with n = 0)");
             if ((int)value != h->opt_solver_order) {
                 if (value == EGG_SOLVER_EXACT) leave_relaxed(h);
                 else
@@ -1036,6 +1038,56 @@ int egg_get_collider_hits(egg_handle *h, int64_t hits[2]) {
     if (!hits) return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_get_collider_hits: hits is NULL");
     hits[0] = h->collider_hits[0];
     hits[1] = h->collider_hits[1];
+    return EGG_OK;
+}
+
+// Force fields of the relaxed step ("Forces").  Everything is checked before anything changes: a
+// refused call leaves the list and its device copy as they were.
+int egg_set_forces(egg_handle *h, int32_t n, const egg_force *f) {
+    if (!h) return EGG_ERR_INVALID_ARGUMENT;
+    REJECT_IN_FLIGHT(h, "egg_set_forces");
+    if (n < 0 || n > EGG_MAX_FORCES)
+        return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_forces: n = %d, a list holds 0 .. %d fields", (int)n, EGG_MAX_FORCES);
+    if (n > 0 && !f) return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_forces: n = %d without a list", (int)n);
+    static_assert(sizeof(egg_force) == 40 && sizeof(EggForce) == sizeof(egg_force), "a force record is 40 bytes");
+    static_assert(EGG_MAX_FORCES == EGG_RX_MAX_FORCES && EGG_FORCE_UNIFORM == EGG_RX_FORCE_UNIFORM &&
+                      EGG_FORCE_RADIAL == EGG_RX_FORCE_RADIAL && EGG_FORCE_VORTEX == EGG_RX_FORCE_VORTEX,
+                  "the kernel's force constants are the ABI's");
+    std::vector<egg_force> list((size_t)n);
+    for (int32_t k = 0; k < n; ++k) {
+        egg_force &o = list[(size_t)k];
+        o = f[k];
+        static const char *const names[3] = {"uniform", "radial", "vortex"};
+        if (o.kind < EGG_FORCE_UNIFORM || o.kind > EGG_FORCE_VORTEX)
+            return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_forces: field %d: unknown kind %d", (int)k, (int)o.kind);
+        if (o.type_mask < 1 || o.type_mask > 3)
+            return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_forces: field %d: type_mask %d (bit 0 white, bit 1 yolk, never 0)", (int)k,
+                        (int)o.type_mask);
+        const int used = o.kind == EGG_FORCE_UNIFORM ? 2 : 4;
+        for (int q = 0; q < 4; ++q) {
+            if (q >= used) o.p[q] = 0.0;  // (not a parameter of the kind)
+            if (!std::isfinite(o.p[q]))
+                return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_forces: field %d (%s): parameter %d is not finite", (int)k, names[o.kind], q);
+        }
+        if (o.kind != EGG_FORCE_UNIFORM && !(o.p[3] > 0))
+            return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_forces: field %d (%s): radius %g is not positive", (int)k, names[o.kind], o.p[3]);
+    }
+    if (n > 0 && h->opt_solver_order != EGG_SOLVER_RELAXED)
+        return fail(h, EGG_ERR_UNSUPPORTED, "egg_set_forces: force fields need relaxed order (EGG_OPT_SOLVER_ORDER = 1 first)");
+    if (n > 0) {  // (no step is running: every step ends with its streams waited for)
+        HIP_TRY(h, hipSetDevice(h->device));
+        HIP_TRY(h, h->d_forces.reserve(EGG_MAX_FORCES, false, nullptr));
+        HIP_TRY(h, hipMemcpy(h->d_forces.p, list.data(), (size_t)n * sizeof(egg_force), hipMemcpyHostToDevice));
+    }
+    h->forces.swap(list);
+    return EGG_OK;
+}
+
+int egg_get_forces(const egg_handle *h, int32_t cap, egg_force *f, int32_t *n) {
+    if (!h) return EGG_ERR_INVALID_ARGUMENT;
+    const int32_t have = (int32_t)h->forces.size();
+    if (n) *n = have;
+    if (f && cap > 0) memcpy(f, h->forces.data(), (size_t)std::min(cap, have) * sizeof(egg_force));
     return EGG_OK;
 }
 

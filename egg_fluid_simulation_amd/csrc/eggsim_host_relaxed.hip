@@ -16,6 +16,8 @@
 // cohesion off launches what it always launched, so all three paths pick cohesion up from here.
 // With static colliders (egg_set_colliders, RelaxedLayout::colliders) launch_pass picks the collider instantiation of the
 // gather kernel and RelaxedStep::col carries the handle's list; with an empty list a step launches what it always launched.
+// With force fields (egg_set_forces, RelaxedLayout::forces) launch_substep picks the force instantiation of the begin / mid
+// kernel and RelaxedStep::frc carries the handle's list; with an empty list a step launches what it always launched.
 #include <hipcub/hipcub.hpp>
 
 #include "eggsim_host.h"
@@ -163,6 +165,7 @@ int prepare_type(RelaxedStep &st, int C, size_t ghosts, const RelaxedLayout &L, 
     st.L = L;
     st.L.cohesion = h->opt_cohesion == EGG_COHESION_EFFECTIVE;
     st.L.colliders = !h->colliders.empty();
+    st.L.forces = !h->forces.empty();
     st.C = C;
     st.ghost_cap = (int64_t)ghosts;
     int rc = reserve_relaxed(h, s, ghosts, st.L.words());
@@ -184,6 +187,12 @@ int prepare_type(RelaxedStep &st, int C, size_t ghosts, const RelaxedLayout &L, 
         st.col.count = (int32_t)h->colliders.size();
         st.col.type_bit = 1 << st.w;
         st.col.hits = r.status.p + st.L.hits();
+    }
+    st.frc = EggRxForceFields{};
+    if (st.L.forces) {
+        st.frc.list = h->d_forces.p;
+        st.frc.count = (int32_t)h->forces.size();
+        st.frc.type_bit = 1 << st.w;
     }
     if (!L.halo) return EGG_OK;
     const bool rebuild = r.key_sig != sig || r.ekey.cap < n + ghosts;  // (or a new array)
@@ -225,7 +234,14 @@ int launch_substep(RelaxedStep &st, int sub) {
     if (sub == 0) HIP_TRY(st.h, hipMemsetAsync(s.rx.status.p, 0, st.L.words() * 8, s.stream));
     if (st.L.halo) {
         st.A.g.box = s.rx.status.p + st.L.box((size_t)sub * st.C);
-        hipLaunchKernelGGL(sub == 0 ? egg_rx_begin_group_kernel : egg_rx_mid_group_kernel, grid, block, 0, s.stream, st.A);
+        if (st.L.forces)
+            hipLaunchKernelGGL(sub == 0 ? egg_rx_begin_group_frc_kernel : egg_rx_mid_group_frc_kernel, grid, block, 0, s.stream,
+                               EggRelaxedGroupFrcArgs{st.A.a, st.A.g, st.frc});
+        else
+            hipLaunchKernelGGL(sub == 0 ? egg_rx_begin_group_kernel : egg_rx_mid_group_kernel, grid, block, 0, s.stream, st.A);
+    } else if (st.L.forces) {
+        hipLaunchKernelGGL(sub == 0 ? egg_rx_begin_frc_kernel : egg_rx_mid_frc_kernel, grid, block, 0, s.stream,
+                           EggRelaxedFrcArgs{st.A.a, st.frc});
     } else {
         hipLaunchKernelGGL(sub == 0 ? egg_rx_begin_kernel : egg_rx_mid_kernel, grid, block, 0, s.stream, st.A.a);
     }

@@ -114,6 +114,13 @@ int relaxed_group_step(egg_handle *const *hs, int nh, double delta, int S, int C
             return EGG_ERR_INVALID_ARGUMENT;
         }
     }
+    for (int k = 1; k < nh; ++k) {
+        const std::vector<egg_force> &a = hs[0]->forces, &b = hs[k]->forces;
+        if (a.size() != b.size() || (!a.empty() && memcmp(a.data(), b.data(), a.size() * sizeof(egg_force)) != 0)) {
+            *error = "relaxed order: the handles of the group differ in their force fields (egg_group_set_forces sets all)";
+            return EGG_ERR_INVALID_ARGUMENT;
+        }
+    }
     for (int k = 0; k < nh; ++k) {
         (void)hipSetDevice(hs[k]->device);
         GK_TRY(k, prepare_step(hs[k], delta, S, st[k]));

@@ -31,6 +31,11 @@
 // into every collider of the handle's list whose mask covers the type, in list order, before it is written.  The
 // D = false instantiations are the kernels as they were.
 //
+// With force fields (egg_set_forces; DESIGN.md section 2.7, "Forces") the kernels that begin a sub-step run in their force
+// instantiations (F = true, egg_rx_begin*_frc_kernel, egg_rx_mid*_frc_kernel): the fields of the handle's list whose mask
+// covers the type accelerate the velocity the pre-solve is about to damp.  The F = false instantiations are the kernels
+// as they were.
+//
 // All arithmetic is IEEE double in the order of the definition: compile with -ffp-contract=off.
 #include <hip/hip_runtime.h>
 #include "eggsim_device.h"
@@ -143,6 +148,42 @@ __device__ __forceinline__ int rx_collide(const EggRxColliderFields &Co, int i, 
     return hits;
 }
 
+// The force step in front of the pre-solve: the accelerations of the fields whose mask covers the type at the position ps
+// the sub-step starts from, summed in list order, into the velocity v the pre-solve is about to damp.  A particle the
+// follow constraint treats as immovable (!(im > eps)) takes none.  Every lane of a wave reads the same record and takes
+// the same branch on its kind.  Every comparison is false for a NaN: such a position takes nothing from a bounded field.
+__device__ __forceinline__ void rx_force(const EggRxForceFields &Fo, double sub_delta, double eps, double im, double2 ps,
+                                         double2 &v) {
+    if (!(im > eps)) return;
+    double ax = 0.0, ay = 0.0;
+    for (int c = 0; c < Fo.count; ++c) {
+        const EggForce f = Fo.list[c];
+        if (!(f.type_mask & Fo.type_bit)) continue;
+        if (f.kind == EGG_RX_FORCE_UNIFORM) {  // p = (gx, gy)
+            ax = ax + f.p[0];
+            ay = ay + f.p[1];
+            continue;
+        }
+        // radial and vortex, p = (cx, cy, strength, R): linear falloff down to 0 at R, nothing at the centre
+        const double dx = f.p[0] - ps.x, dy = f.p[1] - ps.y;
+        const double d2 = dx * dx + dy * dy;
+        if (d2 < f.p[3] * f.p[3] && d2 > 0.0) {
+            const double d = sqrt(d2);
+            const double w = 1.0 - d / f.p[3];
+            const double s = f.p[2] * w;
+            if (f.kind == EGG_RX_FORCE_RADIAL) {  // towards the centre for a positive strength
+                ax = ax + (dx / d) * s;
+                ay = ay + (dy / d) * s;
+            } else {  // vortex: along the radius turned by a quarter
+                ax = ax + (-(dy / d)) * s;
+                ay = ay + (dx / d) * s;
+            }
+        }
+    }
+    v.x = v.x + sub_delta * ax;
+    v.y = v.y + sub_delta * ay;
+}
+
 }  // namespace
 
 // per-particle atom index (run when the atoms change): one workgroup per atom
@@ -158,8 +199,10 @@ extern "C" __global__ void __launch_bounds__(256) egg_rx_atoms_kernel(const int3
 // is the index, no ghosts, no box; EggRelaxedArgs alone), G = true the group's (EggRelaxedGroupArgs).  The G = false
 // instantiations compile to the same instructions as the kernels before groups existed.  (rx_insert and rx_gather
 // take the arguments by value: by reference, the compiler schedules them differently.)
-template <bool G>
-__device__ __forceinline__ void rx_begin(const EggRelaxedArgs &A, const EggRxGroupFields &X) {
+// F: the force fields act on the velocity before the pre-solve (rx_force); the F = false instantiations compile to the
+// same instructions as the kernels before forces existed.
+template <bool G, bool F>
+__device__ __forceinline__ void rx_begin(const EggRelaxedArgs &A, const EggRxGroupFields &X, const EggRxForceFields &Fo) {
     const int i = (int)(blockIdx.x * 256 + threadIdx.x);
     const bool live = i < A.n;
     if (!G && !live) return;
@@ -168,6 +211,7 @@ __device__ __forceinline__ void rx_begin(const EggRelaxedArgs &A, const EggRxGro
         const int atom = A.p_atom[i];
         const double2 ps = make_double2(A.x_in[i], A.y_in[i]);
         double2 v = make_double2(A.vx_in[i], A.vy_in[i]);
+        if (F) rx_force(Fo, A.sub_delta, A.eps, A.inv_mass[i], ps, v);
         egg_pre_follow(A.damping, A.sub_delta, A.eps, A.follow_compliance, ps, v, A.inv_mass[i], A.atom_tx[atom],
                        A.atom_ty[atom], A.atom_fd[atom], out);
         A.prev[i] = ps;
@@ -176,8 +220,8 @@ __device__ __forceinline__ void rx_begin(const EggRelaxedArgs &A, const EggRxGro
     if (G) rx_box(X.box, live, out, A.cell_size);
 }
 
-template <bool G>
-__device__ __forceinline__ void rx_mid(const EggRelaxedArgs &A, const EggRxGroupFields &X) {
+template <bool G, bool F>
+__device__ __forceinline__ void rx_mid(const EggRelaxedArgs &A, const EggRxGroupFields &X, const EggRxForceFields &Fo) {
     const int i = (int)(blockIdx.x * 256 + threadIdx.x);
     const bool live = i < A.n;
     if (!G && !live) return;
@@ -186,6 +230,7 @@ __device__ __forceinline__ void rx_mid(const EggRelaxedArgs &A, const EggRxGroup
         const int atom = A.p_atom[i];
         const double2 ps = A.pos[i], pv = A.prev[i];
         double2 v = make_double2((ps.x - pv.x) / A.sub_delta, (ps.y - pv.y) / A.sub_delta);
+        if (F) rx_force(Fo, A.sub_delta, A.eps, A.inv_mass[i], ps, v);
         egg_pre_follow(A.damping, A.sub_delta, A.eps, A.follow_compliance, ps, v, A.inv_mass[i], A.atom_tx[atom],
                        A.atom_ty[atom], A.atom_fd[atom], out);
         A.prev[i] = ps;
@@ -195,12 +240,18 @@ __device__ __forceinline__ void rx_mid(const EggRelaxedArgs &A, const EggRxGroup
 }
 
 // Start of a step: pre-solve + follow of the first sub-step from the committed state.
-extern "C" __global__ void __launch_bounds__(256) egg_rx_begin_kernel(EggRelaxedArgs A) { rx_begin<false>(A, EggRxGroupFields{}); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_begin_group_kernel(EggRelaxedGroupArgs A) { rx_begin<true>(A.a, A.g); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_begin_kernel(EggRelaxedArgs A) { rx_begin<false, false>(A, EggRxGroupFields{}, EggRxForceFields{}); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_begin_group_kernel(EggRelaxedGroupArgs A) { rx_begin<true, false>(A.a, A.g, EggRxForceFields{}); }
+// force fields
+extern "C" __global__ void __launch_bounds__(256) egg_rx_begin_frc_kernel(EggRelaxedFrcArgs A) { rx_begin<false, true>(A.a, EggRxGroupFields{}, A.f); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_begin_group_frc_kernel(EggRelaxedGroupFrcArgs A) { rx_begin<true, true>(A.a, A.g, A.f); }
 
 // Between two sub-steps: post-solve of the one (L:1690-1693), pre-solve + follow of the next.
-extern "C" __global__ void __launch_bounds__(256) egg_rx_mid_kernel(EggRelaxedArgs A) { rx_mid<false>(A, EggRxGroupFields{}); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_mid_group_kernel(EggRelaxedGroupArgs A) { rx_mid<true>(A.a, A.g); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_mid_kernel(EggRelaxedArgs A) { rx_mid<false, false>(A, EggRxGroupFields{}, EggRxForceFields{}); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_mid_group_kernel(EggRelaxedGroupArgs A) { rx_mid<true, false>(A.a, A.g, EggRxForceFields{}); }
+// force fields
+extern "C" __global__ void __launch_bounds__(256) egg_rx_mid_frc_kernel(EggRelaxedFrcArgs A) { rx_mid<false, true>(A.a, EggRxGroupFields{}, A.f); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_mid_group_frc_kernel(EggRelaxedGroupFrcArgs A) { rx_mid<true, true>(A.a, A.g, A.f); }
 
 // End of the step: post-solve of the last sub-step into the [cur ^ 1] arrays -- unless a pass flagged a bad cell: the
 // step then fails and [cur ^ 1] keeps the positions at the start of the last committed step (EGG_FIELD_LAST_X / Y).

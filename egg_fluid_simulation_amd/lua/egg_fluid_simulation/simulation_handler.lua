@@ -75,6 +75,9 @@ typedef struct { int32_t kind; int32_t type_mask; double p[4]; } egg_collider;
 int egg_set_colliders(egg_handle *h, int32_t n, const egg_collider *c);
 int egg_get_colliders(const egg_handle *h, int32_t cap, egg_collider *c, int32_t *n);
 int egg_get_collider_hits(egg_handle *h, int64_t hits[2]);
+typedef struct { int32_t kind; int32_t type_mask; double p[4]; } egg_force;
+int egg_set_forces(egg_handle *h, int32_t n, const egg_force *f);
+int egg_get_forces(const egg_handle *h, int32_t cap, egg_force *f, int32_t *n);
 typedef struct egg_group egg_group;
 int egg_group_set_solver_order(egg_group *g, int32_t order, double relaxation);
 int egg_group_set_cohesion(egg_group *g, int32_t mode);
@@ -454,6 +457,45 @@ function SimulationHandler:collider_hits()
     local hits = ffi.new("int64_t[2]")
     self:_check(lib.egg_get_collider_hits(self._h, hits))
     return tonumber(hits[0]), tonumber(hits[1])
+end
+
+-- Not in the reference, which has no forces as it has no boundary: force fields of the relaxed step (egg_set_forces in
+-- include/eggsim.h; DESIGN.md section 2.7, "Forces").  Relaxed order only.
+local _force_kinds = { uniform = 0, radial = 1, vortex = 2 }
+local _force_names = { [0] = "uniform", "radial", "vortex" }
+local _force_n_params = { [0] = 2, 4, 4 }
+
+--- the ordered list of at most 16 force fields as accelerations in px/s^2, each `{ "uniform", gx, gy }`,
+--- `{ "radial", cx, cy, strength, R }` or `{ "vortex", cx, cy, strength, R }` with an optional
+--- `types = "both" | "white" | "yolk"`; their sum accelerates every particle before the pre-solve of every sub-step of a
+--- relaxed step.  `{}` clears the list.
+function SimulationHandler:set_forces(forces)
+    local n = #forces
+    local arr = ffi.new("egg_force[?]", math.max(n, 1))
+    for k, f in ipairs(forces) do
+        local kind = _force_kinds[f[1]]
+        local mask = _collider_types[f.types or "both"]
+        if kind == nil or mask == nil or #f ~= 1 + _force_n_params[kind] then
+            log.error("In SimulationHandler.set_forces: field " .. k .. ": expected { kind, parameters..., types = ... }")
+            return
+        end
+        arr[k - 1].kind, arr[k - 1].type_mask = kind, mask
+        for q = 1, _force_n_params[kind] do arr[k - 1].p[q - 1] = f[q + 1] end
+    end
+    self:_check(lib.egg_set_forces(self._h, n, arr))
+end
+
+--- the list as stored, in the shapes set_forces takes
+function SimulationHandler:get_forces()
+    local arr, n = ffi.new("egg_force[16]"), ffi.new("int32_t[1]")
+    if self:_check(lib.egg_get_forces(self._h, 16, arr, n)) ~= 0 then return {} end
+    local out = {}
+    for k = 0, n[0] - 1 do
+        local f = { _force_names[arr[k].kind], types = _collider_type_names[arr[k].type_mask] }
+        for q = 1, _force_n_params[arr[k].kind] do f[q + 1] = arr[k].p[q - 1] end
+        out[k + 1] = f
+    end
+    return out
 end
 
 function SimulationHandler:draw()

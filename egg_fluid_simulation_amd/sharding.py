@@ -621,6 +621,14 @@ class ShardedSimulationHandler(_HandlerSurface):
         self.dist.all_reduce(tot, op=self.dist.ReduceOp.SUM)
         return [int(v) for v in tot.tolist()]
 
+    def set_forces(self, forces):
+        """SimulationHandler.set_forces on every rank alike (the same call on every rank; relaxed order only).  Nothing
+        new travels: every rank accelerates the particles it owns."""
+        self.local.set_forces(forces)
+
+    def get_forces(self):
+        return self.local.get_forces()
+
     def halo_counters(self):
         """relaxed steps of this rank, summed over the run: collision passes, ghost records received, their bytes"""
         if self.halo is None:

@@ -161,6 +161,67 @@ class _HandlerSurface:
         self._check(self._c("get_collider_hits")(hits))
         return list(hits)
 
+    # ------------------------------------------------ force fields (egg_set_forces)
+    @staticmethod
+    def _c_forces(forces):
+        """a list of tuples `(kind, parameters...[, types])` or dicts `{"kind": ..., <parameter names>, "types": ...}` as an
+        egg_force array; what only the host can check (shape, names) is checked here, the values by the library"""
+        forces = list(forces)
+        arr = (_ffi.EggForce * max(len(forces), 1))()
+        for k, f in enumerate(forces):
+            if isinstance(f, dict):
+                kind, types = f.get("kind"), f.get("types", "both")
+            else:
+                f = tuple(f)
+                kind = f[0] if f else None
+                types = "both"
+            if kind not in _ffi.FORCE_KINDS:
+                raise EggError("field %d: kind must be one of %s, not %r" % (k, ", ".join(_ffi.FORCE_KINDS), kind))
+            code = _ffi.FORCE_KINDS.index(kind)
+            names = _ffi.FORCE_PARAMS[code]
+            if isinstance(f, dict):
+                extra = set(f) - set(names) - {"kind", "types"}
+                if extra or not all(n in f for n in names):
+                    raise EggError("field %d (%s): expected the keys %s" % (k, kind, ", ".join(names)))
+                values = [f[n] for n in names]
+            else:
+                values = list(f[1:])
+                if len(values) == len(names) + 1 and isinstance(values[-1], str):
+                    types = values.pop()
+                if len(values) != len(names):
+                    raise EggError("field %d (%s): expected (%r, %s[, types])" % (k, kind, kind, ", ".join(names)))
+            if not isinstance(types, str) or types not in _ffi.FORCE_TYPES:
+                raise EggError("field %d: types must be 'both', 'white' or 'yolk', not %r" % (k, types))
+            try:
+                values = [float(v) for v in values]
+            except (TypeError, ValueError):
+                raise EggError("field %d (%s): the parameters must be numbers" % (k, kind)) from None
+            arr[k].kind, arr[k].type_mask = code, _ffi.FORCE_TYPES[types]
+            for q, v in enumerate(values):
+                arr[k].p[q] = v
+        return len(forces), arr
+
+    def set_forces(self, forces):
+        """The ordered list of force fields, at most 16 ("Forces"; relaxed order only), as
+        accelerations in px/s^2: `("uniform", gx, gy)` is gravity or wind, `("radial", cx, cy, strength, R)` pulls towards
+        (cx, cy) (pushes away for a negative strength) within R with a linear falloff, `("vortex", cx, cy, strength, R)`
+        stirs around (cx, cy); each takes an optional last element (or dict key) types = "both" | "white" | "yolk", and
+        each may be a dict with "kind" and the parameter names.  In every sub-step of a relaxed step the fields' sum
+        accelerates a particle's velocity before the pre-solve damps it.  `[]` clears the list.  Raises EggError for a bad
+        list (nothing changes) and for a non-empty list on a handle in exact order; set_solver_order("exact") raises while
+        the list is not empty."""
+        n, arr = self._c_forces(forces)
+        self._check(self._c("set_forces")(n, arr))
+
+    def get_forces(self):
+        """the list as stored, as tuples `(kind, parameters..., types)`"""
+        arr = (_ffi.EggForce * _ffi.MAX_FORCES)()
+        n = C.c_int32()
+        self._check(self._c("get_forces")(_ffi.MAX_FORCES, arr, C.byref(n)))
+        types = {v: k for k, v in _ffi.FORCE_TYPES.items()}
+        return [(_ffi.FORCE_KINDS[f.kind],) + tuple(f.p[:len(_ffi.FORCE_PARAMS[f.kind])]) + (types[f.type_mask],)
+                for f in arr[:n.value]]
+
     def _init_host_state(self, white_config, yolk_config):
         """config tables (validated like the reference, L:1253-1320), hidden constants and render switches; no device"""
         if white_config is None and yolk_config is None:

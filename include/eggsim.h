@@ -417,6 +417,41 @@ int egg_get_colliders(const egg_handle *h, int32_t cap, egg_collider *c, int32_t
  * steps count: a step that fails or is discarded adds nothing. */
 int egg_get_collider_hits(egg_handle *h, int64_t hits[2]);
 
+/* ---- force fields (not in the reference, which has no forces as it has no boundary; DESIGN.md section 2.7, "Forces") ----
+ * A handle holds an ordered list of at most EGG_MAX_FORCES fields.  The values are accelerations in px/s^2 and do not depend
+ * on mass.  In every sub-step of a RELAXED step, for every particle of a type, the force step runs before the pre-solve,
+ * which then runs unchanged (it damps, integrates and applies the follow constraint).  (x, y) is the position at the start
+ * of the sub-step, (vx, vy) the velocity the pre-solve is about to damp, im the inverse mass:
+ *   1. !(im > eps): the particle takes no force (the follow constraint's own test for an immovable particle).
+ *   2. ax = +0.0, ay = +0.0; for every field with the type in `type_mask` (bit 0 white, bit 1 yolk), in list order:
+ *      UNIFORM p = (gx, gy, -, -): ax = ax + gx, ay = ay + gy.
+ *      RADIAL  p = (cx, cy, strength, R): dx = cx - x, dy = cy - y, d2 = dx dx + dy dy; d2 < R R && d2 > 0:
+ *              d = sqrt(d2), w = 1 - d / R, s = strength w, ax = ax + (dx / d) s, ay = ay + (dy / d) s.  A positive strength
+ *              attracts, a negative one repels; the falloff is linear, down to 0 at the edge; at d2 == 0 nothing.
+ *      VORTEX  p = (cx, cy, strength, R): the same dx, dy, d2, d, w, s and condition;
+ *              ax = ax + (-(dy / d)) s, ay = ay + (dx / d) s.
+ *   3. vx = vx + sub_delta ax, vy = vy + sub_delta ay.
+ * FP64 in exactly this order, no contraction; every comparison is false for a NaN.  The force is damped together with the
+ * velocity, so a particle in free fall reaches a terminal speed.  Parameters a kind does not use are stored as 0.  An
+ * acceleration that throws a particle beyond cell +-2^30 fails the step as any such position does, with nothing committed.
+ * The fields do not move and are not drawn; a caller re-sets the list between steps to vary them.
+ * Relaxed order only, as the colliders: a non-empty list on a handle in exact order is EGG_ERR_UNSUPPORTED, and
+ * EGG_OPT_SOLVER_ORDER = 0 is EGG_ERR_UNSUPPORTED while the list is not empty; an empty list is always accepted.
+ * egg_set_forces checks everything before it changes anything: EGG_ERR_INVALID_ARGUMENT, with the field's index in the
+ * message, for n outside 0 .. EGG_MAX_FORCES, an unknown kind, a mask that is 0 or has bits beyond 3, a parameter that is
+ * not finite, R <= 0 for RADIAL or VORTEX.  Refused while a step is in flight.  The list goes to the device when it is set,
+ * never per step; with an empty list a step launches exactly what it launches without, and with one as many kernels. */
+#define EGG_MAX_FORCES 16
+enum { EGG_FORCE_UNIFORM = 0, EGG_FORCE_RADIAL = 1, EGG_FORCE_VORTEX = 2 };
+typedef struct {
+    int32_t kind;      /* EGG_FORCE_* */
+    int32_t type_mask; /* bit 0 white, bit 1 yolk; never 0 */
+    double p[4];
+} egg_force; /* 40 bytes */
+int egg_set_forces(egg_handle *h, int32_t n, const egg_force *f); /* n == 0 clears */
+/* the list as stored: the count in *n, min(*n, cap) fields copied */
+int egg_get_forces(const egg_handle *h, int32_t cap, egg_force *f, int32_t *n);
+
 /* ---- several GPUs in one process (csrc/eggsim_group.cpp) -------------------------------------------------------
  * The multi-device form of the handle for a host that is ONE process (the LuaJIT wrapper): one egg_handle per device
  * behind one egg_group, x-slabs [cuts[k], cuts[k + 1]) of the plane per device (cuts: n_devices + 1 ascending values;
@@ -465,6 +500,11 @@ int egg_group_set_cohesion(egg_group *g, int32_t mode);
 int egg_group_set_colliders(egg_group *g, int32_t n, const egg_collider *c);
 int egg_group_get_colliders(const egg_group *g, int32_t cap, egg_collider *c, int32_t *n);
 int egg_group_get_collider_hits(egg_group *g, int64_t hits[2]);
+/* egg_set_forces for every handle of the group alike, with its rules (relaxed order only; back to exact order only with
+ * an empty list); a refused list changes no handle.  Every device accelerates only the particles it owns: the results
+ * equal one handle's.  A group whose handles differ in their lists refuses to step. */
+int egg_group_set_forces(egg_group *g, int32_t n, const egg_force *f);
+int egg_group_get_forces(const egg_group *g, int32_t cap, egg_force *f, int32_t *n);
 /* cumulative over relaxed group steps, both types: collision passes, ghost records the devices received, their bytes */
 int egg_group_get_halo_counters(const egg_group *g, int64_t *passes, int64_t *records, int64_t *bytes);
 
