@@ -127,6 +127,7 @@ class EggRxBox(C.Structure):  # egg_rx_box: a cell box of the relaxed halo betwe
 
 
 RX_BOX_INTS = 5        # int32 fields of egg_rx_box
+RX_VISCOSITY_PASS = 0x40000000  # EGG_RX_VISCOSITY_PASS: + sub addresses the viscosity pass of sub-step sub
 RX_RECORD_WORDS = 5    # 64-bit words of a ghost record: x, y, inverse mass, radius (doubles), global key (int64; with
                        # effective cohesion the batch tag in its upper 32 bits)
 RX_RECORD_BYTES = 40
@@ -182,6 +183,12 @@ _SIGNATURES = {
     "egg_get_forces": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggForce), C.POINTER(C.c_int32)]),
     "egg_group_set_forces": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggForce)]),
     "egg_group_get_forces": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggForce), C.POINTER(C.c_int32)]),
+    "egg_set_viscosity": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "egg_get_viscosity": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "egg_get_viscosity_pairs": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "egg_group_set_viscosity": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "egg_group_get_viscosity": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "egg_group_get_viscosity_pairs": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "egg_group_get_halo_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "egg_group_set_config": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(EggConfig)]),
     "egg_group_get_config": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(EggConfig)]),

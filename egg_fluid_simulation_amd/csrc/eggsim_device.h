@@ -385,7 +385,26 @@ struct EggRelaxedGroupFrcArgs {
     EggRxForceFields f;
 };
 
-// A ghost record: a particle of a sender j that lies within one cell of a receiver k's cell box (40 bytes).
+// Viscosity (egg_set_viscosity, DESIGN.md section 2.7, "Viscosity"): one more pass per sub-step, after its last collision
+// pass.  insert / scan / scatter are the collision pass's; the viscous rank kernel (egg_rx_rank*_visc_kernel) writes every
+// entry's displacement of the sub-step u = pos - prev into the grouped swr slot, and the viscosity gather
+// (egg_rx_gather*_visc_kernel) blends u with the weighted mean of the neighbours' within one cell size and rewrites prev.
+struct EggRxViscFields {
+    double c;                            // the type's coefficient, in (0, 1]
+    unsigned long long *pairs;           // one word: distinct pairs within the cell size, over the step's viscosity passes
+};
+struct EggRelaxedViscArgs {
+    EggRelaxedArgs a;
+    EggRxViscFields v;
+};
+struct EggRelaxedGroupViscArgs {
+    EggRelaxedArgs a;
+    EggRxGroupFields g;  // (gwr: the ghosts' u)
+    EggRxViscFields v;
+};
+
+// A ghost record: a particle of a sender j that lies within one cell of a receiver k's cell box (40 bytes).  In a viscosity
+// pass the two words inv_mass and radius carry u.x and u.y instead (the receiver's unpack copies them as they are).
 struct EggGhost {
     double x, y, inv_mass, radius;
     int64_t key;  // global key (below 2^29); with effective cohesion the batch tag in the upper 32 bits, zero otherwise
@@ -410,6 +429,10 @@ struct EggRxPackArgs {  // sender side: one launch per pass packs for every rece
     EggGhost *send[EGG_RX_MAX_GROUP];                 // this sender's buffer for each receiver (capacity n)
     unsigned long long *count[EGG_RX_MAX_GROUP];      // records in it (in this sender's memory, zero at the step's start)
 };
+struct EggRxPackViscArgs {  // the viscosity pass's pack (egg_rx_pack_visc_kernel): the payload words carry pos - prev
+    EggRxPackArgs p;
+    const double2 *prev;
+};
 struct EggRxUnpackArgs {  // receiver side: pulls every sender's records for it into the ghost entries
     int32_t n, n_send;                   // local particles; senders
     double2 *pos;                        // positions of this pass; ghosts go to [n + g]
@@ -430,6 +453,13 @@ static __device__ __forceinline__ bool rx_cell(double2 p, double cell, int32_t &
     cx = ok ? (int32_t)fx : 0;
     cy = ok ? (int32_t)fy : 0;
     return ok;
+}
+
+// The test the four senders of the ghost halo share (egg_rx_pack*_kernel, egg_rx_wire_pack*_kernel): a particle's cell
+// against a receiver's grown cell box, lo x, hi x, lo y, hi y.
+template <typename T>
+static __device__ __forceinline__ bool rx_in_box(const T *bx, int32_t cx, int32_t cy) {
+    return cx >= bx[0] && cx <= bx[1] && cy >= bx[2] && cy <= bx[3];
 }
 
 // Wave-aggregated append: the lanes with `take` get consecutive slots of *counter; returns this lane's slot.
@@ -461,6 +491,10 @@ struct EggRxWirePackArgs {  // sender side: one launch packs for up to EGG_RX_MA
     const int32_t *boxes;                // [n_dest][EGG_RX_WIRE_BOX]: the destinations' boxes for this pass
     unsigned long long *msg;             // [n_dest] messages of `stride` words each (capacity n records, header zeroed)
     long long stride;
+};
+struct EggRxWirePackViscArgs {  // the viscosity pass's pack (egg_rx_wire_pack_visc_kernel): the payload words carry pos - prev
+    EggRxWirePackArgs p;
+    const double2 *prev;
 };
 struct EggRxWireUnpackArgs {  // receiver side: up to EGG_RX_MAX_GROUP received messages into the ghost entries
     int32_t n, n_src;                    // local particles; messages of this launch

@@ -65,6 +65,7 @@ struct egg_group {
     int cohesion = EGG_COHESION_REFERENCE;  // egg_group_set_cohesion: every handle's EGG_OPT_COHESION
     std::vector<egg_collider> colliders;    // egg_group_set_colliders: every handle's list, as given
     std::vector<egg_force> forces;          // egg_group_set_forces: every handle's list, as given
+    double viscosity[2] = {0.0, 0.0};       // egg_group_set_viscosity: every handle's coefficients
     int64_t halo_passes = 0, halo_records = 0;  // relaxed group steps: collision passes, ghost records received
     int64_t steps = 0;  // _step calls committed by the group
     // render attributes (never read by the solver): they live here, per global id / per type, so that a hand-over
@@ -307,7 +308,7 @@ int group_step_relaxed(egg_group *g, double delta, int S, int C) {
     std::string err;
     const int rc = egghost::relaxed_group_step(g->h.data(), (int)n, delta, S, C, &g->halo_records, &err);
     if (rc != EGG_OK) return gfail(g, rc, "%s", err.c_str());
-    g->halo_passes += (int64_t)S * C;
+    g->halo_passes += (int64_t)S * C + (g->viscosity[0] != 0.0 || g->viscosity[1] != 0.0 ? S : 0);  // (+ the viscosity passes)
     return rebalance_relaxed(g);
 }
 
@@ -607,6 +608,8 @@ int egg_group_set_solver_order(egg_group *g, int32_t order, double relaxation) {
         return gfail(g, EGG_ERR_UNSUPPORTED, "egg_group_set_solver_order: exact order has no colliders: clear the list first (egg_group_set_colliders with n = 0)");
     if (order == EGG_SOLVER_EXACT && !g->forces.empty())
         return gfail(g, EGG_ERR_UNSUPPORTED, "egg_group_set_solver_order: exact order has no force fields: clear the list first (egg_group_set_forces with n = 0)");
+    if (order == EGG_SOLVER_EXACT && (g->viscosity[0] != 0.0 || g->viscosity[1] != 0.0))
+        return gfail(g, EGG_ERR_UNSUPPORTED, "egg_group_set_solver_order: exact order has no viscosity: set both coefficients to 0 first (egg_group_set_viscosity)");
     if (order == EGG_SOLVER_RELAXED && g->h.size() > 1) {  // the ghost halo reads the other devices' memory
         std::string err;
         const int rc = egghost::relaxed_group_peers(g->h.data(), (int)g->h.size(), &err);
@@ -685,6 +688,36 @@ int egg_group_set_forces(egg_group *g, int32_t n, const egg_force *f) {
 int egg_group_get_forces(const egg_group *g, int32_t cap, egg_force *f, int32_t *n) {
     if (!g || g->h.empty()) return EGG_ERR_INVALID_ARGUMENT;
     return egg_get_forces(g->h[0], cap, f, n);  // (as stored: every handle holds the same list)
+}
+
+int egg_group_set_viscosity(egg_group *g, const double c[2]) {
+    if (!g || g->h.empty()) return EGG_ERR_INVALID_ARGUMENT;
+    for (size_t k = 0; k < g->h.size(); ++k) {
+        const int rc = egg_set_viscosity(g->h[k], c);
+        if (rc < 0) {  // (handle 0 refuses bad values before any handle has changed; a later one: the others go back)
+            for (size_t j = 0; j < k; ++j) (void)egg_set_viscosity(g->h[j], g->viscosity);
+            return gfail(g, rc, "device %d: %s", (int)k, egg_last_error(g->h[k]));
+        }
+    }
+    return egg_get_viscosity(g->h[0], g->viscosity);  // (as stored)
+}
+
+int egg_group_get_viscosity(const egg_group *g, double c[2]) {
+    if (!g || g->h.empty()) return EGG_ERR_INVALID_ARGUMENT;
+    return egg_get_viscosity(g->h[0], c);  // (every handle holds the same coefficients)
+}
+
+int egg_group_get_viscosity_pairs(egg_group *g, int64_t pairs[2]) {
+    if (!g) return EGG_ERR_INVALID_ARGUMENT;
+    if (!pairs) return gfail(g, EGG_ERR_INVALID_ARGUMENT, "egg_group_get_viscosity_pairs: pairs is NULL");
+    pairs[0] = pairs[1] = 0;
+    for (size_t k = 0; k < g->h.size(); ++k) {
+        int64_t one[2] = {0, 0};
+        GTRY(g, k, egg_get_viscosity_pairs(g->h[k], one));
+        pairs[0] += one[0];
+        pairs[1] += one[1];
+    }
+    return EGG_OK;
 }
 
 int egg_group_get_halo_counters(const egg_group *g, int64_t *passes, int64_t *records, int64_t *bytes) {

@@ -90,6 +90,12 @@ extern "C" __global__ void egg_rx_begin_frc_kernel(EggRelaxedFrcArgs A);
 extern "C" __global__ void egg_rx_mid_frc_kernel(EggRelaxedFrcArgs A);
 extern "C" __global__ void egg_rx_begin_group_frc_kernel(EggRelaxedGroupFrcArgs A);
 extern "C" __global__ void egg_rx_mid_group_frc_kernel(EggRelaxedGroupFrcArgs A);
+extern "C" __global__ void egg_rx_rank_visc_kernel(EggRelaxedArgs A);
+extern "C" __global__ void egg_rx_rank_group_visc_kernel(EggRelaxedGroupArgs A);
+extern "C" __global__ void egg_rx_gather_visc_kernel(EggRelaxedViscArgs A);
+extern "C" __global__ void egg_rx_gather_group_visc_kernel(EggRelaxedGroupViscArgs A);
+extern "C" __global__ void egg_rx_pack_visc_kernel(EggRxPackViscArgs P);
+extern "C" __global__ void egg_rx_wire_pack_visc_kernel(EggRxWirePackViscArgs P);
 extern "C" __global__ void egg_rx_gkey_kernel(const int32_t *, const int32_t *, const int32_t *, int, int32_t *);
 extern "C" __global__ void egg_rx_pack_kernel(EggRxPackArgs P);
 extern "C" __global__ void egg_rx_unpack_kernel(EggRxUnpackArgs U);
@@ -410,6 +416,10 @@ struct egg_handle {
     // (written when the list is set, never per step)
     std::vector<egg_force> forces;
     DevBuf<EggForce> d_forces;
+    // viscosity (egg_set_viscosity; relaxed order only): the coefficient per type, 0 = off, and the pairs the viscosity
+    // passes of committed steps counted per type
+    double viscosity[2] = {0.0, 0.0};
+    int64_t viscosity_pairs[2] = {0, 0};
     int opt_force_cell_hash = 0;     // test hook: every launch class keys its cells by the LDS hash table, never the dense grid
     int opt_force_global_state = 0;  // test hook: run every tile through the global-memory-state kernel  // threads per particle in the step kernel's workgroups (pair dataflow spreading)
     hipDeviceProp_t prop{};
@@ -551,19 +561,24 @@ constexpr char kRelaxedBadCellText[] = "relaxed order: a position is NaN or its 
 // Status words of one type: [0] bad cell, [1 + p] pairs of pass p (P = S C passes); with a halo besides, per pass, the
 // cell box of its positions, the ghost entries received and -- device groups, nq handles holding the type -- the
 // records sent to each of them.  With effective cohesion one more word: the pairs that cohered.  With colliders one
-// more, the last: their hits.
+// more: their hits.  With viscosity the halo words cover V = S more passes, the viscosity pass of sub-step `sub` being
+// halo pass P + sub, and one more word, the last, holds the pairs the viscosity passes counted.  V = 0 is the layout
+// without.
 struct RelaxedLayout {
     size_t P = 0, nq = 0;
     bool halo = false;  // ghosts of other handles' particles take part: the group instantiations of the kernels
     bool cohesion = false;  // (set by prepare_type from the handle's option)
     bool colliders = false;  // (set by prepare_type: the handle's collider list is not empty)
     bool forces = false;     // (set by prepare_type: the handle's force list is not empty; no status word of its own)
+    size_t V = 0;            // (set by prepare_type: the sub-steps, when the type's viscosity coefficient is not zero)
+    size_t H() const { return P + V; }                                        // passes with a halo
     size_t box(size_t p) const { return 1 + P + 4 * p; }                      // 4 words
-    size_t ghosts(size_t p) const { return 1 + 5 * P + p; }
-    size_t sent(size_t p, size_t m) const { return 1 + 6 * P + p * nq + m; }  // to participant m
-    size_t cohered() const { return halo ? 1 + 6 * P + P * nq : 1 + P; }
+    size_t ghosts(size_t p) const { return 1 + P + 4 * H() + p; }
+    size_t sent(size_t p, size_t m) const { return 1 + P + 5 * H() + p * nq + m; }  // to participant m
+    size_t cohered() const { return halo ? 1 + P + 5 * H() + H() * nq : 1 + P; }
     size_t hits() const { return cohered() + (cohesion ? 1 : 0); }
-    size_t words() const { return hits() + (colliders ? 1 : 0); }
+    size_t visc() const { return hits() + (colliders ? 1 : 0); }
+    size_t words() const { return visc() + (V ? 1 : 0); }
 };
 struct RelaxedStep {  // one type of one handle in a relaxed step
     egg_handle *h = nullptr;
@@ -574,6 +589,7 @@ struct RelaxedStep {  // one type of one handle in a relaxed step
     EggRxCohesionFields coh{};  // effective cohesion (L.cohesion): compliance and factor of the type, the tag arrays
     EggRxColliderFields col{};  // static colliders (L.colliders): the handle's list, the type's bit, the hit counter
     EggRxForceFields frc{};     // force fields (L.forces): the handle's list, the type's bit
+    EggRxViscFields visc{};     // viscosity (L.V): the type's coefficient, the pair counter
     int64_t ghost_cap = 0;    // a pass runs over n + ghost_cap entries
     int launches = 0;         // kernel launches so far: into the statistics at the commit
 };
@@ -584,6 +600,7 @@ int prepare_type(RelaxedStep &st, int C, size_t ghosts, const RelaxedLayout &L, 
                  const KeyBaseFn &base_of);
 int launch_substep(RelaxedStep &st, int sub);
 int launch_pass(RelaxedStep &st, int p);
+int launch_viscosity(RelaxedStep &st, int sub);
 int read_status(RelaxedStep &st);
 bool bad_cell(const RelaxedStep &st);
 int launch_end(RelaxedStep &st);

@@ -944,6 +944,8 @@ int egg_set_option(egg_handle *h, int option, double value) {
                 return fail(h, EGG_ERR_UNSUPPORTED, "exact order has no colliders: clear the list first (egg_set_colliders with n = 0)");
             if (value == EGG_SOLVER_EXACT && !h->forces.empty())
                 return fail(h, EGG_ERR_UNSUPPORTED, "exact order has no force fields: clear the list first (egg_set_forces with n = 0)");
+            if (value == EGG_SOLVER_EXACT && (h->viscosity[0] != 0.0 || h->viscosity[1] != 0.0))
+                return fail(h, EGG_ERR_UNSUPPORTED, "exact order has no viscosity: set both coefficients to 0 first (egg_set_viscosity)");
             if ((int)value != h->opt_solver_order) {
                 if (value == EGG_SOLVER_EXACT) leave_relaxed(h);
                 else
@@ -1088,6 +1090,35 @@ int egg_get_forces(const egg_handle *h, int32_t cap, egg_force *f, int32_t *n) {
     const int32_t have = (int32_t)h->forces.size();
     if (n) *n = have;
     if (f && cap > 0) memcpy(f, h->forces.data(), (size_t)std::min(cap, have) * sizeof(egg_force));
+    return EGG_OK;
+}
+
+// Viscosity of the relaxed step ("Viscosity").  Everything is checked before anything changes.
+int egg_set_viscosity(egg_handle *h, const double c[2]) {
+    if (!h) return EGG_ERR_INVALID_ARGUMENT;
+    REJECT_IN_FLIGHT(h, "egg_set_viscosity");
+    if (!c) return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_viscosity: c is NULL");
+    for (int w = 0; w < 2; ++w)
+        if (!(c[w] >= 0.0 && c[w] <= 1.0))
+            return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_viscosity: the %s coefficient %g lies outside [0, 1]", w ? "yolk" : "white", c[w]);
+    if ((c[0] != 0.0 || c[1] != 0.0) && h->opt_solver_order != EGG_SOLVER_RELAXED)
+        return fail(h, EGG_ERR_UNSUPPORTED, "egg_set_viscosity: viscosity needs relaxed order (EGG_OPT_SOLVER_ORDER = 1 first)");
+    for (int w = 0; w < 2; ++w) h->viscosity[w] = c[w] == 0.0 ? 0.0 : c[w];  // (-0.0 is stored as +0.0)
+    return EGG_OK;
+}
+
+int egg_get_viscosity(const egg_handle *h, double c[2]) {
+    if (!h || !c) return EGG_ERR_INVALID_ARGUMENT;
+    c[0] = h->viscosity[0];
+    c[1] = h->viscosity[1];
+    return EGG_OK;
+}
+
+int egg_get_viscosity_pairs(egg_handle *h, int64_t pairs[2]) {
+    if (!h) return EGG_ERR_INVALID_ARGUMENT;
+    if (!pairs) return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_get_viscosity_pairs: pairs is NULL");
+    pairs[0] = h->viscosity_pairs[0];
+    pairs[1] = h->viscosity_pairs[1];
     return EGG_OK;
 }
 

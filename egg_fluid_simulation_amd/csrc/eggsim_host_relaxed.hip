@@ -18,6 +18,10 @@
 // gather kernel and RelaxedStep::col carries the handle's list; with an empty list a step launches what it always launched.
 // With force fields (egg_set_forces, RelaxedLayout::forces) launch_substep picks the force instantiation of the begin / mid
 // kernel and RelaxedStep::frc carries the handle's list; with an empty list a step launches what it always launched.
+// With viscosity (egg_set_viscosity, RelaxedLayout::V) every sub-step of a type whose coefficient is not zero ends with
+// launch_viscosity, one more pass of the driver -- insert, scan, scatter, the viscous rank kernel, the viscosity gather --
+// and the sub-step's last collision pass records the cell box that pass's halo needs; RelaxedStep::visc carries the
+// coefficient and the pair counter.  With both coefficients zero a step launches what it always launched.
 #include <hipcub/hipcub.hpp>
 
 #include "eggsim_host.h"
@@ -166,6 +170,7 @@ int prepare_type(RelaxedStep &st, int C, size_t ghosts, const RelaxedLayout &L, 
     st.L.cohesion = h->opt_cohesion == EGG_COHESION_EFFECTIVE;
     st.L.colliders = !h->colliders.empty();
     st.L.forces = !h->forces.empty();
+    st.L.V = h->viscosity[st.w] > 0.0 ? L.P / (size_t)C : 0;
     st.C = C;
     st.ghost_cap = (int64_t)ghosts;
     int rc = reserve_relaxed(h, s, ghosts, st.L.words());
@@ -193,6 +198,11 @@ int prepare_type(RelaxedStep &st, int C, size_t ghosts, const RelaxedLayout &L, 
         st.frc.list = h->d_forces.p;
         st.frc.count = (int32_t)h->forces.size();
         st.frc.type_bit = 1 << st.w;
+    }
+    st.visc = EggRxViscFields{};
+    if (st.L.V) {
+        st.visc.c = h->viscosity[st.w];
+        st.visc.pairs = r.status.p + st.L.visc();
     }
     if (!L.halo) return EGG_OK;
     const bool rebuild = r.key_sig != sig || r.ekey.cap < n + ghosts;  // (or a new array)
@@ -251,7 +261,8 @@ int launch_substep(RelaxedStep &st, int sub) {
 
 // collision pass p over the entries: cell table, grouping, the Jacobi gather.  With a halo the ghosts of the pass are in
 // place behind the local positions (their count in the status words), and the gather records the cell box of the
-// positions it writes for the next pass of the sub-step (the next sub-step's is recorded by its mid kernel).
+// positions it writes for the next pass of the sub-step (the next sub-step's is recorded by its mid kernel) -- with
+// viscosity also the sub-step's last, for the viscosity pass that follows it.
 int launch_pass(RelaxedStep &st, int p) {
     egg_handle *h = st.h;
     System &s = h->sys[st.w];
@@ -260,7 +271,9 @@ int launch_pass(RelaxedStep &st, int p) {
     a.a.pass = p;
     if (st.L.halo) {
         a.g.n_ghost = r.status.p + st.L.ghosts((size_t)p);
-        a.g.box = p % st.C + 1 < st.C ? r.status.p + st.L.box((size_t)p + 1) : nullptr;
+        a.g.box = p % st.C + 1 < st.C ? r.status.p + st.L.box((size_t)p + 1)
+                  : st.L.V            ? r.status.p + st.L.box(st.L.P + (size_t)(p / st.C))
+                                      : nullptr;
     }
     const dim3 grid((unsigned)((s.n + st.ghost_cap + 255) / 256)), block(256);  // (the ghost count is read on the device)
     HIP_TRY(h, hipMemsetAsync(r.hkey.p, 0xFF, (size_t)r.table * 8, s.stream));
@@ -309,6 +322,40 @@ int launch_pass(RelaxedStep &st, int p) {
     return EGG_OK;
 }
 
+// the viscosity pass of sub-step `sub`, after its last collision pass (only with L.V): the cell structure of a collision
+// pass over the same entries -- with a halo the ghosts of halo pass P + sub, whose records carry u -- then the viscous rank
+// kernel and the viscosity gather, which rewrites prev.  Positions stay: nothing is swapped and no box is recorded.
+int launch_viscosity(RelaxedStep &st, int sub) {
+    egg_handle *h = st.h;
+    System &s = h->sys[st.w];
+    RelaxedBufs &r = s.rx;
+    EggRelaxedGroupArgs &a = st.A;
+    if (st.L.halo) {
+        a.g.n_ghost = r.status.p + st.L.ghosts(st.L.P + (size_t)sub);
+        a.g.box = nullptr;
+    }
+    const dim3 grid((unsigned)((s.n + st.ghost_cap + 255) / 256)), block(256);  // (the ghost count is read on the device)
+    HIP_TRY(h, hipMemsetAsync(r.hkey.p, 0xFF, (size_t)r.table * 8, s.stream));
+    HIP_TRY(h, hipMemsetAsync(r.hcount.p, 0, ((size_t)r.table + 1) * 4, s.stream));
+    if (st.L.halo)
+        hipLaunchKernelGGL(egg_rx_insert_group_kernel, grid, block, 0, s.stream, a);
+    else
+        hipLaunchKernelGGL(egg_rx_insert_kernel, grid, block, 0, s.stream, a.a);
+    size_t bytes = r.scan_bytes;
+    HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(r.scan_tmp.p, bytes, r.hcount.p, r.hstart.p, (int)r.table + 1, s.stream));
+    if (st.L.halo) {
+        hipLaunchKernelGGL(egg_rx_scatter_group_kernel, grid, block, 0, s.stream, a);
+        hipLaunchKernelGGL(egg_rx_rank_group_visc_kernel, grid, block, 0, s.stream, a);
+        hipLaunchKernelGGL(egg_rx_gather_group_visc_kernel, grid, block, 0, s.stream, EggRelaxedGroupViscArgs{a.a, a.g, st.visc});
+    } else {
+        hipLaunchKernelGGL(egg_rx_scatter_kernel, grid, block, 0, s.stream, a.a);
+        hipLaunchKernelGGL(egg_rx_rank_visc_kernel, grid, block, 0, s.stream, a.a);
+        hipLaunchKernelGGL(egg_rx_gather_visc_kernel, grid, block, 0, s.stream, EggRelaxedViscArgs{a.a, st.visc});
+    }
+    st.launches += 5;
+    return EGG_OK;
+}
+
 // the status words on their way to h_status; bad_cell() reads them once the stream has been waited for
 int read_status(RelaxedStep &st) {
     System &s = st.h->sys[st.w];
@@ -342,6 +389,7 @@ int relaxed_step(egg_handle *h, double delta, int S, int C) {  // L:1722-1989, c
         for (int sub = 0; sub < S && rc == EGG_OK; ++sub) {
             rc = launch_substep(st[w], sub);
             for (int c = 0; c < C && rc == EGG_OK; ++c) rc = launch_pass(st[w], sub * C + c);
+            if (rc == EGG_OK && st[w].L.V) rc = launch_viscosity(st[w], sub);
         }
         if (rc == EGG_OK) rc = launch_end(st[w]);
         if (rc == EGG_OK) rc = read_status(st[w]);
@@ -389,6 +437,7 @@ void relaxed_commit(egg_handle *h, const RelaxedStep st[2], int S, int C, double
         h->stats.max_pass_visits[w] = most;
         if (st[w].L.cohesion) h->stats.cohesion_solves += (int64_t)s.rx.h_status.p[st[w].L.cohered()];
         if (st[w].L.colliders) h->collider_hits[w] += (int64_t)s.rx.h_status.p[st[w].L.hits()];
+        if (st[w].L.V) h->viscosity_pairs[w] += (int64_t)s.rx.h_status.p[st[w].L.visc()];
         h->stats.follow_solves += s.n * S;
         // the exact path's host copies of the atoms' cells describe older positions now
         s.aabb_valid = s.aabb_on_device = s.disp_valid = false;

@@ -10,6 +10,10 @@
 //     into its own send buffers (egg_rx_pack_kernel), records ev_pack;
 //   * k waits for the ev_pack of the others, pulls their records for it into its ghost entries (egg_rx_unpack_kernel)
 //     and runs insert .. gather over local particles + ghosts.  The gather writes local positions only.
+// With viscosity (egg_set_viscosity) a type whose coefficient is not zero runs one more such exchange per sub-step, after
+// its last collision pass: the box is the one that pass's gather recorded, the pack is egg_rx_pack_visc_kernel (the records
+// carry u = pos - prev where a collision pass's carry inverse mass and radius), the unpack is the same and the pass is
+// launch_viscosity.  The events alternate over the exchanges in the order they run.
 // Every event is recorded on the host before any wait on it is enqueued: streams of different handles may share a
 // hardware queue, and a wait must never sit in a queue ahead of the work it waits for.  Pass p + 1's pack waits for
 // the receiver's box of p + 1, which the receiver records after it has read pass p's records: a send buffer is never
@@ -121,6 +125,11 @@ int relaxed_group_step(egg_handle *const *hs, int nh, double delta, int S, int C
             return EGG_ERR_INVALID_ARGUMENT;
         }
     }
+    for (int k = 1; k < nh; ++k)
+        if (memcmp(hs[0]->viscosity, hs[k]->viscosity, sizeof hs[0]->viscosity) != 0) {  // (a ghost's u travels only when its sender smooths)
+            *error = "relaxed order: the handles of the group differ in their viscosity (egg_group_set_viscosity sets all)";
+            return EGG_ERR_INVALID_ARGUMENT;
+        }
     for (int k = 0; k < nh; ++k) {
         (void)hipSetDevice(hs[k]->device);
         GK_TRY(k, prepare_step(hs[k], delta, S, st[k]));
@@ -139,7 +148,8 @@ int relaxed_group_step(egg_handle *const *hs, int nh, double delta, int S, int C
             return EGG_ERR_UNSUPPORTED;
         }
         if (q[w].empty()) continue;
-        const RelaxedLayout L{P, q[w].size(), true};
+        RelaxedLayout L{P, q[w].size(), true};
+        L.V = hs[0]->viscosity[w] > 0.0 ? (size_t)S : 0;
         // global keys: a batch's particles start at the sum of the type's counts over the live batches of smaller id
         // (every handle lays its batches out in ascending id: the key of particle i is base + its place in its atom)
         std::vector<uint64_t> sig((size_t)nh);
@@ -167,78 +177,96 @@ int relaxed_group_step(egg_handle *const *hs, int nh, double delta, int S, int C
     for (int w = 0; w < 2; ++w) {
         const std::vector<int> &Q = q[w];
         const size_t nq = Q.size();
-        const RelaxedLayout L{P, nq, true};
+        RelaxedLayout L{P, nq, true};
+        L.V = nq && hs[0]->viscosity[w] > 0.0 ? (size_t)S : 0;
+        size_t seq = 0;  // exchanges so far: the events alternate
+        // the halo of halo pass p (a collision pass, or P + sub: the viscosity pass of sub-step sub) and the pass itself
+        const auto halo_pass = [&](size_t p, bool visc, int sub) -> int {
+            const int par = (int)(seq++ & 1);
+            for (size_t m = 0; m < nq; ++m) {
+                const int k = Q[m];
+                (void)hipSetDevice(hs[k]->device);
+                GK_HIP(k, hipEventRecord(hs[k]->sys[w].rx.ev_box[par], hs[k]->sys[w].stream));
+            }
+            for (size_t mj = 0; mj < nq && nq > 1; ++mj) {  // senders
+                const int j = Q[mj];
+                System &s = hs[j]->sys[w];
+                (void)hipSetDevice(hs[j]->device);
+                EggRxPackArgs pk{};
+                pk.n = (int)s.n;
+                pk.cell_size = st[j][w].env.cell;
+                pk.pos = st[j][w].A.a.pos;
+                pk.inv_mass = s.inv_mass.p;
+                pk.radius = s.radius.p;
+                pk.ekey = s.rx.ekey.p;
+                if (st[j][w].L.cohesion) {
+                    pk.p_atom = s.rx.p_atom.p;
+                    pk.atom_tag = st[j][w].coh.atom_tag;
+                }
+                for (size_t mk = 0; mk < nq; ++mk) {
+                    if (mk == mj) continue;
+                    const int k = Q[mk];
+                    GK_HIP(j, hipStreamWaitEvent(s.stream, hs[k]->sys[w].rx.ev_box[par], 0));
+                    pk.box[pk.n_recv] = hs[k]->sys[w].rx.status.p + L.box(p);
+                    pk.send[pk.n_recv] = s.rx.send.p + mk * (size_t)s.n;
+                    pk.count[pk.n_recv] = s.rx.status.p + L.sent(p, mk);
+                    ++pk.n_recv;
+                }
+                if (visc)
+                    hipLaunchKernelGGL(egg_rx_pack_visc_kernel, dim3((unsigned)((s.n + 255) / 256)), dim3(256), 0, s.stream,
+                                       EggRxPackViscArgs{pk, st[j][w].A.a.prev});
+                else
+                    hipLaunchKernelGGL(egg_rx_pack_kernel, dim3((unsigned)((s.n + 255) / 256)), dim3(256), 0, s.stream, pk);
+                ++st[j][w].launches;
+                GK_HIP(j, hipEventRecord(s.rx.ev_pack[par], s.stream));
+            }
+            for (size_t mk = 0; mk < nq; ++mk) {  // receivers
+                const int k = Q[mk];
+                egg_handle *h = hs[k];
+                System &s = h->sys[w];
+                RelaxedBufs &r = s.rx;
+                (void)hipSetDevice(h->device);
+                if (nq > 1) {
+                    EggRxUnpackArgs up{};
+                    up.n = (int)s.n;
+                    up.pos = st[k][w].A.a.pos;
+                    up.gwr = r.gwr.p;
+                    up.ekey = r.ekey.p;
+                    up.gtag = st[k][w].L.cohesion ? r.gtag.p : nullptr;
+                    up.n_ghost = r.status.p + L.ghosts(p);
+                    int64_t most = 0;
+                    for (size_t mj = 0; mj < nq; ++mj) {
+                        if (mj == mk) continue;
+                        System &sj = hs[Q[mj]]->sys[w];
+                        GK_HIP(k, hipStreamWaitEvent(s.stream, sj.rx.ev_pack[par], 0));
+                        up.recs[up.n_send] = sj.rx.send.p + mk * (size_t)sj.n;
+                        up.count[up.n_send] = sj.rx.status.p + L.sent(p, mk);
+                        ++up.n_send;
+                        most = std::max(most, sj.n);
+                    }
+                    hipLaunchKernelGGL(egg_rx_unpack_kernel, dim3((unsigned)((most + 255) / 256), (unsigned)up.n_send), dim3(256), 0,
+                                       s.stream, up);
+                    ++st[k][w].launches;
+                }
+                if (visc)
+                    GK_TRY(k, launch_viscosity(st[k][w], sub));
+                else
+                    GK_TRY(k, launch_pass(st[k][w], (int)p));
+            }
+            return EGG_OK;
+        };
         for (int sub = 0; sub < S; ++sub) {
             for (size_t m = 0; m < nq; ++m) {
                 (void)hipSetDevice(hs[Q[m]]->device);
                 GK_TRY(Q[m], launch_substep(st[Q[m]][w], sub));
             }
             for (int c = 0; c < C; ++c) {
-                const size_t p = (size_t)sub * C + c;
-                const int par = (int)(p & 1);
-                for (size_t m = 0; m < nq; ++m) {
-                    const int k = Q[m];
-                    (void)hipSetDevice(hs[k]->device);
-                    GK_HIP(k, hipEventRecord(hs[k]->sys[w].rx.ev_box[par], hs[k]->sys[w].stream));
-                }
-                for (size_t mj = 0; mj < nq && nq > 1; ++mj) {  // senders
-                    const int j = Q[mj];
-                    System &s = hs[j]->sys[w];
-                    (void)hipSetDevice(hs[j]->device);
-                    EggRxPackArgs pk{};
-                    pk.n = (int)s.n;
-                    pk.cell_size = st[j][w].env.cell;
-                    pk.pos = st[j][w].A.a.pos;
-                    pk.inv_mass = s.inv_mass.p;
-                    pk.radius = s.radius.p;
-                    pk.ekey = s.rx.ekey.p;
-                    if (st[j][w].L.cohesion) {
-                        pk.p_atom = s.rx.p_atom.p;
-                        pk.atom_tag = st[j][w].coh.atom_tag;
-                    }
-                    for (size_t mk = 0; mk < nq; ++mk) {
-                        if (mk == mj) continue;
-                        const int k = Q[mk];
-                        GK_HIP(j, hipStreamWaitEvent(s.stream, hs[k]->sys[w].rx.ev_box[par], 0));
-                        pk.box[pk.n_recv] = hs[k]->sys[w].rx.status.p + L.box(p);
-                        pk.send[pk.n_recv] = s.rx.send.p + mk * (size_t)s.n;
-                        pk.count[pk.n_recv] = s.rx.status.p + L.sent(p, mk);
-                        ++pk.n_recv;
-                    }
-                    hipLaunchKernelGGL(egg_rx_pack_kernel, dim3((unsigned)((s.n + 255) / 256)), dim3(256), 0, s.stream, pk);
-                    ++st[j][w].launches;
-                    GK_HIP(j, hipEventRecord(s.rx.ev_pack[par], s.stream));
-                }
-                for (size_t mk = 0; mk < nq; ++mk) {  // receivers
-                    const int k = Q[mk];
-                    egg_handle *h = hs[k];
-                    System &s = h->sys[w];
-                    RelaxedBufs &r = s.rx;
-                    (void)hipSetDevice(h->device);
-                    if (nq > 1) {
-                        EggRxUnpackArgs up{};
-                        up.n = (int)s.n;
-                        up.pos = st[k][w].A.a.pos;
-                        up.gwr = r.gwr.p;
-                        up.ekey = r.ekey.p;
-                        up.gtag = st[k][w].L.cohesion ? r.gtag.p : nullptr;
-                        up.n_ghost = r.status.p + L.ghosts(p);
-                        int64_t most = 0;
-                        for (size_t mj = 0; mj < nq; ++mj) {
-                            if (mj == mk) continue;
-                            System &sj = hs[Q[mj]]->sys[w];
-                            GK_HIP(k, hipStreamWaitEvent(s.stream, sj.rx.ev_pack[par], 0));
-                            up.recs[up.n_send] = sj.rx.send.p + mk * (size_t)sj.n;
-                            up.count[up.n_send] = sj.rx.status.p + L.sent(p, mk);
-                            ++up.n_send;
-                            most = std::max(most, sj.n);
-                        }
-                        hipLaunchKernelGGL(egg_rx_unpack_kernel, dim3((unsigned)((most + 255) / 256), (unsigned)up.n_send), dim3(256), 0,
-                                           s.stream, up);
-                        ++st[k][w].launches;
-                    }
-                    GK_TRY(k, launch_pass(st[k][w], (int)p));
-                }
+                const int rc = halo_pass((size_t)sub * C + c, false, sub);
+                if (rc != EGG_OK) return rc;
+            }
+            if (L.V) {
+                const int rc = halo_pass(P + (size_t)sub, true, sub);
+                if (rc != EGG_OK) return rc;
             }
         }
     }
@@ -264,7 +292,7 @@ int relaxed_group_step(egg_handle *const *hs, int nh, double delta, int S, int C
         for (int k : q[w]) {
             (void)hipSetDevice(hs[k]->device);
             GK_TRY(k, launch_end(st[k][w]));
-            for (size_t p = 0; p < P; ++p) records += (int64_t)hs[k]->sys[w].rx.h_status.p[st[k][w].L.ghosts(p)];
+            for (size_t p = 0; p < st[k][w].L.H(); ++p) records += (int64_t)hs[k]->sys[w].rx.h_status.p[st[k][w].L.ghosts(p)];
         }
     for (int w = 0; w < 2; ++w)
         for (int k : q[w]) {

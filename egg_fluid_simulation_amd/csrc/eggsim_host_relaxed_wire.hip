@@ -11,6 +11,10 @@
 //                                                       egg_rx_wire_unpack_kernel
 //   status words of all handles, then the end kernels   egg_rx_check -> the host's all-reduce -> egg_rx_end(commit)
 //
+// With viscosity (egg_set_viscosity) the sequence has one more pass per sub-step, addressed as EGG_RX_VISCOSITY_PASS + sub
+// after the sub-step's collision passes: the same calls, for the types whose coefficient is not zero (the other type reports
+// an empty box, packs nothing and runs nothing); egg_rx_pack uses egg_rx_wire_pack_visc_kernel, whose records carry u.
+//
 // The pass kernels are the group instantiations, unchanged: entries = local particles + ghosts with keys.  Everything is
 // enqueued on the handle's own streams; every call that hands data to the host waits for them first.
 #include "eggsim_host.h"
@@ -26,6 +30,7 @@ struct WireStep {
     double delta = 0;
     int S = 0, C = 0;
     int sub_done = 0, pass_done = 0;  // sub-steps begun, passes run
+    int visc_done = 0;                // viscosity passes run (one per sub-step while a type's coefficient is not zero)
     bool checked = false, bad = false;
     RelaxedStep st[2];
     // the last egg_rx_pack
@@ -46,14 +51,38 @@ int need_active(egg_handle *h, const char *name) {
     return EGG_OK;
 }
 
+// The step has viscosity passes: decided from the handle's coefficients, not from the layout of the types it holds, so
+// that a handle without particles of a type (or of any) walks the same sequence as the ranks that have them.  (The
+// coefficients cannot change while the step is in flight.)
+bool any_viscosity(const egg_handle *h) { return h->viscosity[0] > 0.0 || h->viscosity[1] > 0.0; }
+
+// the pass that runs next: a collision pass, or the viscosity pass of a sub-step whose collision passes have all run
+int next_pass(const egg_handle *h, const WireStep &W) {
+    if (any_viscosity(h) && W.visc_done < W.sub_done && W.pass_done == (W.visc_done + 1) * W.C)
+        return EGG_RX_VISCOSITY_PASS + W.visc_done;
+    return W.pass_done;
+}
+
 // pass `pass` is the next to run and its sub-step has begun
 int need_pass(egg_handle *h, const WireStep &W, int pass, const char *name) {
     const int rc = need_active(h, name);
     if (rc != EGG_OK) return rc;
-    if (pass != W.pass_done || pass >= W.sub_done * W.C)
-        return fail(h, EGG_ERR_INVALID_ARGUMENT, "%s: pass %d is out of sequence (%d passes run, %d sub-steps begun)", name, pass,
-                    W.pass_done, W.sub_done);
+    if (pass >= EGG_RX_VISCOSITY_PASS && !any_viscosity(h))
+        return fail(h, EGG_ERR_INVALID_ARGUMENT, "%s: pass %d addresses a viscosity pass, and both coefficients are 0", name, pass);
+    if (pass != next_pass(h, W) || (pass < EGG_RX_VISCOSITY_PASS && pass >= W.sub_done * W.C))
+        return fail(h, EGG_ERR_INVALID_ARGUMENT, "%s: pass %d is out of sequence (%d passes run, %d sub-steps begun, %d viscosity passes run)",
+                    name, pass, W.pass_done, W.sub_done, W.visc_done);
     return EGG_OK;
+}
+
+// a pass of the ABI as the layout counts it: the viscosity pass of sub-step sub is halo pass P + sub
+size_t halo_pass(const RelaxedStep &st, int pass) {
+    return pass >= EGG_RX_VISCOSITY_PASS ? st.L.P + (size_t)(pass - EGG_RX_VISCOSITY_PASS) : (size_t)pass;
+}
+
+// type w takes part in `pass`: it has particles and, in a viscosity pass, a coefficient
+bool in_pass(egg_handle *h, const WireStep &W, int w, int pass) {
+    return h->sys[w].n > 0 && (pass < EGG_RX_VISCOSITY_PASS || h->viscosity[w] > 0.0);
 }
 
 int wait_both(egg_handle *h) {
@@ -117,7 +146,7 @@ int egg_rx_begin(egg_handle *h, double delta, int32_t n_substeps, int32_t n_coll
     W.delta = delta;
     W.S = S;
     W.C = C;
-    W.sub_done = W.pass_done = 0;
+    W.sub_done = W.pass_done = W.visc_done = 0;
     W.checked = W.bad = false;
     W.packed_pass = -1;
     W.n_dest = 0;
@@ -130,9 +159,9 @@ int egg_rx_substep(egg_handle *h, int32_t sub) {
     int rc = need_active(h, "egg_rx_substep");
     if (rc != EGG_OK) return rc;
     WireStep &W = *h->wire;
-    if (sub != W.sub_done || sub >= W.S || W.pass_done != sub * W.C)
-        return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_rx_substep: sub-step %d is out of sequence (%d begun, %d passes run)", (int)sub,
-                    W.sub_done, W.pass_done);
+    if (sub != W.sub_done || sub >= W.S || W.pass_done != sub * W.C || (any_viscosity(h) && W.visc_done != sub))
+        return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_rx_substep: sub-step %d is out of sequence (%d begun, %d passes run, %d viscosity passes run)",
+                    (int)sub, W.sub_done, W.pass_done, W.visc_done);
     (void)hipSetDevice(h->device);
     for (int w = 0; w < 2; ++w) {
         if (h->sys[w].n == 0) continue;
@@ -153,8 +182,8 @@ int egg_rx_get_boxes(egg_handle *h, int32_t pass, egg_rx_box boxes[2]) {
     (void)hipSetDevice(h->device);
     for (int w = 0; w < 2; ++w) {
         System &s = h->sys[w];
-        if (s.n == 0) continue;
-        const size_t at = W.st[w].L.box((size_t)pass);
+        if (!in_pass(h, W, w, pass)) continue;
+        const size_t at = W.st[w].L.box(halo_pass(W.st[w], pass));
         HIP_TRY(h, hipMemcpyAsync(s.rx.h_status.p + at, s.rx.status.p + at, 4 * 8, hipMemcpyDeviceToHost, s.stream));
     }
     rc = wait_both(h);
@@ -163,8 +192,8 @@ int egg_rx_get_boxes(egg_handle *h, int32_t pass, egg_rx_box boxes[2]) {
         System &s = h->sys[w];
         egg_rx_box &b = boxes[w];
         b = egg_rx_box{0, 0, 0, 0, 1};
-        if (s.n == 0) continue;
-        const unsigned long long *q = s.rx.h_status.p + W.st[w].L.box((size_t)pass);
+        if (!in_pass(h, W, w, pass)) continue;
+        const unsigned long long *q = s.rx.h_status.p + W.st[w].L.box(halo_pass(W.st[w], pass));
         if (q[1] == 0) continue;  // (cannot happen with particles; the words say "empty")
         b.lo_x = (int32_t)((long long)((1ull << 32) - q[0]) - EGG_RX_BOX_BIAS);
         b.hi_x = (int32_t)((long long)q[1] - EGG_RX_BOX_BIAS);
@@ -190,7 +219,7 @@ int egg_rx_pack(egg_handle *h, int32_t pass, int32_t n_dest, const egg_rx_box *b
     for (int w = 0; w < 2; ++w) {
         System &s = h->sys[w];
         RelaxedBufs &r = s.rx;
-        if (s.n == 0) continue;
+        if (!in_pass(h, W, w, pass)) continue;
         const size_t stride = 1 + (size_t)EGG_RX_WIRE_RECORD_WORDS * (size_t)s.n;
         W.stride[w] = stride;
         HIP_TRY(h, r.wsend.reserve(nd * stride, false, s.stream));
@@ -225,7 +254,11 @@ int egg_rx_pack(egg_handle *h, int32_t pass, int32_t n_dest, const egg_rx_box *b
             pk.n_dest = (int)std::min<size_t>(EGG_RX_MAX_GROUP, nd - k0);
             pk.boxes = r.wbox.p + k0 * EGG_RX_WIRE_BOX;
             pk.msg = r.wsend.p + k0 * stride;
-            hipLaunchKernelGGL(egg_rx_wire_pack_kernel, dim3((unsigned)((s.n + 255) / 256)), dim3(256), 0, s.stream, pk);
+            if (pass >= EGG_RX_VISCOSITY_PASS)
+                hipLaunchKernelGGL(egg_rx_wire_pack_visc_kernel, dim3((unsigned)((s.n + 255) / 256)), dim3(256), 0, s.stream,
+                                   EggRxWirePackViscArgs{pk, W.st[w].A.a.prev});
+            else
+                hipLaunchKernelGGL(egg_rx_wire_pack_kernel, dim3((unsigned)((s.n + 255) / 256)), dim3(256), 0, s.stream, pk);
             ++W.st[w].launches;
         }
         HIP_TRY(h, hipGetLastError());
@@ -236,7 +269,7 @@ int egg_rx_pack(egg_handle *h, int32_t pass, int32_t n_dest, const egg_rx_box *b
     if (rc != EGG_OK) return rc;
     for (int w = 0; w < 2; ++w) {
         System &s = h->sys[w];
-        if (s.n == 0) continue;
+        if (!in_pass(h, W, w, pass)) continue;
         for (size_t k = 0; k < nd; ++k) {
             const int64_t c = (int64_t)s.rx.h_wcount.p[k];
             if (c < 0 || c > s.n) return fail(h, EGG_ERR_INTERNAL, "egg_rx_pack: a message holds %lld records of %lld particles", (long long)c, (long long)s.n);
@@ -252,7 +285,7 @@ int egg_rx_fetch(egg_handle *h, int32_t n_dest, void *const *out) {
     int rc = need_active(h, "egg_rx_fetch");
     if (rc != EGG_OK) return rc;
     WireStep &W = *h->wire;
-    if (W.packed_pass != W.pass_done || n_dest != W.n_dest)
+    if (W.packed_pass != next_pass(h, W) || n_dest != W.n_dest)
         return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_rx_fetch: no egg_rx_pack of this pass for %d destinations", (int)n_dest);
     (void)hipSetDevice(h->device);
     for (int w = 0; w < 2; ++w) {
@@ -261,7 +294,7 @@ int egg_rx_fetch(egg_handle *h, int32_t n_dest, void *const *out) {
             void *dst = out[2 * k + (size_t)w];
             if (!dst) continue;
             const size_t words = 1 + (size_t)EGG_RX_WIRE_RECORD_WORDS * (size_t)W.counts[2 * k + (size_t)w];
-            if (s.n == 0) {  // an empty message
+            if (!in_pass(h, W, w, W.packed_pass)) {  // an empty message
                 const unsigned long long zero = 0;
                 HIP_TRY(h, hipMemcpy(dst, &zero, 8, hipMemcpyDefault));  // (dst may be device memory)
                 continue;
@@ -280,6 +313,7 @@ int egg_rx_run_pass(egg_handle *h, int32_t pass, int32_t n_src, const void *cons
     WireStep &W = *h->wire;
     (void)hipSetDevice(h->device);
     // every message is checked before anything is enqueued
+    const bool visc = pass >= EGG_RX_VISCOSITY_PASS;
     for (int w = 0; w < 2; ++w) {
         int64_t sum = 0;
         for (size_t k = 0; k < (size_t)n_src; ++k) {
@@ -294,7 +328,7 @@ int egg_rx_run_pass(egg_handle *h, int32_t pass, int32_t n_src, const void *cons
     for (int w = 0; w < 2; ++w) {
         System &s = h->sys[w];
         RelaxedBufs &r = s.rx;
-        if (s.n == 0) continue;
+        if (!in_pass(h, W, w, pass)) continue;
         // staging copies of the messages in this handle's memory, then the unpack (16 messages per launch)
         size_t words = 0;
         for (size_t k = 0; k < (size_t)n_src; ++k)
@@ -308,7 +342,7 @@ int egg_rx_run_pass(egg_handle *h, int32_t pass, int32_t n_src, const void *cons
             up.gwr = r.gwr.p;
             up.ekey = r.ekey.p;
             up.gtag = W.st[w].L.cohesion ? r.gtag.p : nullptr;
-            up.n_ghost = r.status.p + W.st[w].L.ghosts((size_t)pass);
+            up.n_ghost = r.status.p + W.st[w].L.ghosts(halo_pass(W.st[w], pass));
             int64_t most = 0;
             size_t off = 0;
             auto flush = [&]() {
@@ -332,11 +366,11 @@ int egg_rx_run_pass(egg_handle *h, int32_t pass, int32_t n_src, const void *cons
             }
             flush();
         }
-        rc = launch_pass(W.st[w], pass);
+        rc = visc ? launch_viscosity(W.st[w], pass - EGG_RX_VISCOSITY_PASS) : launch_pass(W.st[w], pass);
         if (rc != EGG_OK) return rc;
         HIP_TRY(h, hipGetLastError());
     }
-    ++W.pass_done;
+    ++(visc ? W.visc_done : W.pass_done);
     return EGG_OK;
 }
 
@@ -346,6 +380,8 @@ int egg_rx_check(egg_handle *h, int32_t *bad, int64_t pairs[2], int64_t *ghost_r
     if (rc != EGG_OK) return rc;
     WireStep &W = *h->wire;
     if (W.pass_done != W.S * W.C) return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_rx_check: %d of %d passes have run", W.pass_done, W.S * W.C);
+    if (any_viscosity(h) && W.visc_done != W.S)
+        return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_rx_check: %d of %d viscosity passes have run", W.visc_done, W.S);
     (void)hipSetDevice(h->device);
     for (int w = 0; w < 2; ++w) {
         if (h->sys[w].n == 0) continue;
@@ -361,10 +397,9 @@ int egg_rx_check(egg_handle *h, int32_t *bad, int64_t pairs[2], int64_t *ghost_r
         if (pairs) pairs[w] = 0;
         if (s.n == 0) continue;
         W.bad |= bad_cell(W.st[w]);
-        for (size_t p = 0; p < W.st[w].L.P; ++p) {
+        for (size_t p = 0; p < W.st[w].L.P; ++p)
             if (pairs) pairs[w] += (int64_t)s.rx.h_status.p[1 + p];
-            records += (int64_t)s.rx.h_status.p[W.st[w].L.ghosts(p)];
-        }
+        for (size_t p = 0; p < W.st[w].L.H(); ++p) records += (int64_t)s.rx.h_status.p[W.st[w].L.ghosts(p)];
     }
     W.checked = true;
     *bad = W.bad ? 1 : 0;

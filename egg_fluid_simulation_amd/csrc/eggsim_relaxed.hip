@@ -36,6 +36,13 @@
 // covers the type accelerate the velocity the pre-solve is about to damp.  The F = false instantiations are the kernels
 // as they were.
 //
+// With viscosity (egg_set_viscosity; DESIGN.md section 2.7, "Viscosity") every sub-step of a type whose coefficient is not
+// zero ends with one more pass over the same cell structure (insert, scan and scatter are the collision pass's):
+// egg_rx_rank*_visc_kernel groups every entry's displacement of the sub-step u = pos - prev beside its position, and
+// egg_rx_gather*_visc_kernel blends a particle's u with the weighted mean of its neighbours' within one cell size and
+// rewrites prev.  Positions are not touched.  In a group the ghosts' u arrive in the record words that carry inverse mass
+// and radius in a collision pass (egg_rx_pack_visc_kernel).  Nothing of it runs while both coefficients are zero.
+//
 // All arithmetic is IEEE double in the order of the definition: compile with -ffp-contract=off.
 #include <hip/hip_runtime.h>
 #include "eggsim_device.h"
@@ -466,6 +473,89 @@ extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_col_kernel
 extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_coh_col_kernel(EggRelaxedCohColArgs A) { rx_gather<false, true, true>(A.a, EggRxGroupFields{}, A.c, A.d); }
 extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_coh_col_kernel(EggRelaxedGroupCohColArgs A) { rx_gather<true, true, true>(A.a, A.g, A.c, A.d); }
 
+// ---- viscosity ----
+
+// The viscous rank kernel: rx_rank's order inside a cell, with u = pos - prev of the entry in the grouped swr slot (a
+// ghost's u arrived in its record).  A neighbour's inverse mass and radius are not needed in this pass.
+template <bool G>
+__device__ __forceinline__ void rx_rank_visc(const EggRelaxedArgs &A, const EggRxGroupFields &X) {
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (i >= rx_entries<G>(A, X)) return;
+    const int key = G ? X.ekey[i] : i;
+    const int h = A.pslot[i];
+    const int st = (int)A.hstart[h], en = (int)A.hstart[h + 1];
+    int rank = 0;
+    for (int e = st; e < en; ++e) rank += A.tmp[e] < key ? 1 : 0;
+    const int t = st + rank;
+    const double2 p = A.pos[i];
+    A.sidx[t] = key;
+    if (G) X.sloc[t] = i;
+    A.spos[t] = p;
+    if (!G || i < A.n) {
+        const double2 pv = A.prev[i];
+        A.swr[t] = make_double2(p.x - pv.x, p.y - pv.y);
+    } else {
+        A.swr[t] = X.gwr[i - A.n];
+    }
+}
+
+// The viscosity pass (XSPH), one thread per grouped slot, candidates and visit order of rx_gather.  Every neighbour j
+// within the cell size H adds w = 1 - d / H to sw and w (u_j - u_i) to (sx, sy); the particle's new displacement is
+// u_i + c (s / sw), written as prev = p - that.  Neighbours are read from the grouped copies only and nothing reads another
+// particle's prev: the write in place has no race.  A ghost's slot gathers nothing.  A pair is counted by the holder of
+// its smaller key, one atomic per wave.
+template <bool G>
+__device__ __forceinline__ void rx_gather_visc(EggRelaxedArgs A, const EggRxGroupFields &X, const EggRxViscFields &V) {
+    const int t = (int)(blockIdx.x * 256 + threadIdx.x);
+    int pairs = 0;
+    if (G ? t < rx_entries<G>(A, X) && X.sloc[t] < A.n : t < A.n) {
+        const int i = A.sidx[t];
+        const int me = G ? X.sloc[t] : i;
+        const double2 p = A.spos[t], u = A.swr[t];
+        const double H = A.cell_size, H2 = H * H;
+        int32_t cx, cy;
+        (void)rx_cell(p, A.cell_size, cx, cy);  // (a bad cell was flagged by the insert kernel)
+        double sw = 0.0, sx = 0.0, sy = 0.0;
+        for (int ox = -1; ox <= 1; ++ox) {
+            for (int oy = -1; oy <= 1; ++oy) {
+                const unsigned long long key = rx_key(cx + ox, cy + oy);
+                uint32_t h = rx_hash(key) & A.table_mask;
+                unsigned long long k;
+                while ((k = A.hkey[h]) != key && k != EGG_RX_EMPTY_KEY) h = (h + 1) & A.table_mask;
+                if (k == EGG_RX_EMPTY_KEY) continue;
+                const int st = (int)A.hstart[h], en = (int)A.hstart[h + 1];
+                for (int e = st; e < en; ++e) {
+                    const int j = A.sidx[e];
+                    if (j == i) continue;
+                    const double2 q = A.spos[e];
+                    const double dx = q.x - p.x, dy = q.y - p.y;
+                    const double d2 = dx * dx + dy * dy;
+                    if (!(d2 < H2)) continue;
+                    const double2 uq = A.swr[e];
+                    pairs += j > i ? 1 : 0;
+                    const double d = sqrt(d2);
+                    const double w = 1.0 - d / H;
+                    sw = sw + w;
+                    sx = sx + w * (uq.x - u.x);
+                    sy = sy + w * (uq.y - u.y);
+                }
+            }
+        }
+        if (A.inv_mass[me] > A.eps && sw > 0.0) {
+            const double nux = u.x + V.c * (sx / sw), nuy = u.y + V.c * (sy / sw);
+            A.prev[me] = make_double2(p.x - nux, p.y - nuy);
+        }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) pairs += __shfl_xor(pairs, d, 64);
+    if ((threadIdx.x & 63) == 0 && pairs) atomicAdd(V.pairs, (unsigned long long)pairs);
+}
+
+extern "C" __global__ void __launch_bounds__(256) egg_rx_rank_visc_kernel(EggRelaxedArgs A) { rx_rank_visc<false>(A, EggRxGroupFields{}); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_rank_group_visc_kernel(EggRelaxedGroupArgs A) { rx_rank_visc<true>(A.a, A.g); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_visc_kernel(EggRelaxedViscArgs A) { rx_gather_visc<false>(A.a, EggRxGroupFields{}, A.v); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_visc_kernel(EggRelaxedGroupViscArgs A) { rx_gather_visc<true>(A.a, A.g, A.v); }
+
 // ---- device groups ----
 
 // global key of every local particle: abase[atom] = particles of the type in the group's batches with smaller ids
@@ -505,7 +595,7 @@ extern "C" __global__ void __launch_bounds__(256) egg_rx_pack_kernel(EggRxPackAr
         (void)rx_cell(p, P.cell_size, cx, cy);
     }
     for (int k = 0; k < P.n_recv; ++k) {
-        const bool take = live && cx >= bx[k][0] && cx <= bx[k][1] && cy >= bx[k][2] && cy <= bx[k][3];
+        const bool take = live && rx_in_box(bx[k], cx, cy);
         const int slot = rx_append(P.count[k], take);
         if (take) {
             EggGhost g;
@@ -513,6 +603,50 @@ extern "C" __global__ void __launch_bounds__(256) egg_rx_pack_kernel(EggRxPackAr
             g.y = p.y;
             g.inv_mass = P.inv_mass[i];
             g.radius = P.radius[i];
+            g.key = rx_key_word(P.ekey[i], P.p_atom, P.atom_tag, i);
+            P.send[k][slot] = g;
+        }
+    }
+}
+
+// The viscosity pass's sender: the same selection -- the take test is shared (rx_in_box); the box decode is written out
+// again, because behind a shared helper or as a template egg_rx_pack_kernel no longer compiles to the instructions it had --
+// and the two payload words of a record carry u = pos - prev instead of inverse mass and radius.
+extern "C" __global__ void __launch_bounds__(256) egg_rx_pack_visc_kernel(EggRxPackViscArgs V) {
+    const EggRxPackArgs &P = V.p;
+    __shared__ long long bx[EGG_RX_MAX_GROUP][4];  // lo x, hi x, lo y, hi y, grown
+    if (threadIdx.x < (unsigned)P.n_recv) {
+        const unsigned long long *b = P.box[threadIdx.x];
+        const unsigned long long w0 = b[0], w1 = b[1], w2 = b[2], w3 = b[3];
+        if (w1 == 0) {  // the receiver wrote no position: nothing is near it
+            bx[threadIdx.x][0] = bx[threadIdx.x][2] = 1;
+            bx[threadIdx.x][1] = bx[threadIdx.x][3] = 0;
+        } else {
+            bx[threadIdx.x][0] = (long long)((1ull << 32) - w0) - EGG_RX_BOX_BIAS - 1;
+            bx[threadIdx.x][1] = (long long)w1 - EGG_RX_BOX_BIAS + 1;
+            bx[threadIdx.x][2] = (long long)((1ull << 32) - w2) - EGG_RX_BOX_BIAS - 1;
+            bx[threadIdx.x][3] = (long long)w3 - EGG_RX_BOX_BIAS + 1;
+        }
+    }
+    __syncthreads();
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    const bool live = i < P.n;
+    int32_t cx = 0, cy = 0;
+    double2 p = make_double2(0.0, 0.0);
+    if (live) {
+        p = P.pos[i];
+        (void)rx_cell(p, P.cell_size, cx, cy);
+    }
+    for (int k = 0; k < P.n_recv; ++k) {
+        const bool take = live && rx_in_box(bx[k], cx, cy);
+        const int slot = rx_append(P.count[k], take);
+        if (take) {
+            EggGhost g;
+            g.x = p.x;
+            g.y = p.y;
+            const double2 pv = V.prev[i];
+            g.inv_mass = p.x - pv.x;
+            g.radius = p.y - pv.y;
             g.key = rx_key_word(P.ekey[i], P.p_atom, P.atom_tag, i);
             P.send[k][slot] = g;
         }

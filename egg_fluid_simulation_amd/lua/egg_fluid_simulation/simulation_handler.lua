@@ -78,6 +78,9 @@ int egg_get_collider_hits(egg_handle *h, int64_t hits[2]);
 typedef struct { int32_t kind; int32_t type_mask; double p[4]; } egg_force;
 int egg_set_forces(egg_handle *h, int32_t n, const egg_force *f);
 int egg_get_forces(const egg_handle *h, int32_t cap, egg_force *f, int32_t *n);
+int egg_set_viscosity(egg_handle *h, const double c[2]);
+int egg_get_viscosity(const egg_handle *h, double c[2]);
+int egg_get_viscosity_pairs(egg_handle *h, int64_t pairs[2]);
 typedef struct egg_group egg_group;
 int egg_group_set_solver_order(egg_group *g, int32_t order, double relaxation);
 int egg_group_set_cohesion(egg_group *g, int32_t mode);
@@ -496,6 +499,31 @@ function SimulationHandler:get_forces()
         out[k + 1] = f
     end
     return out
+end
+
+-- Not in the reference, whose cohesion_strength moves nothing: XSPH viscosity of the relaxed step (egg_set_viscosity in
+-- include/eggsim.h; DESIGN.md section 2.7, "Viscosity").  Relaxed order only.
+
+--- a coefficient in [0, 1] per particle type, 0 (the default) = off: after the last collision pass of every sub-step of a
+--- relaxed step a particle's displacement of the sub-step is blended with the weighted mean of its neighbours' within one
+--- spatial-hash cell size, so motion relative to the neighbours dies out and common motion stays
+function SimulationHandler:set_viscosity(white, yolk)
+    local c = ffi.new("double[2]", white or 0, yolk or 0)
+    self:_check(lib.egg_set_viscosity(self._h, c))
+end
+
+--- white, yolk: the coefficients as stored
+function SimulationHandler:viscosity()
+    local c = ffi.new("double[2]")
+    self:_check(lib.egg_get_viscosity(self._h, c))
+    return c[0], c[1]
+end
+
+--- white, yolk: distinct pairs within the cell size over the viscosity passes of committed steps
+function SimulationHandler:viscosity_pairs()
+    local pairs = ffi.new("int64_t[2]")
+    self:_check(lib.egg_get_viscosity_pairs(self._h, pairs))
+    return tonumber(pairs[0]), tonumber(pairs[1])
 end
 
 function SimulationHandler:draw()

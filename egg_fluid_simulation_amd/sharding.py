@@ -629,8 +629,31 @@ class ShardedSimulationHandler(_HandlerSurface):
     def get_forces(self):
         return self.local.get_forces()
 
+    def set_viscosity(self, white=0.0, yolk=0.0):
+        """SimulationHandler.set_viscosity on every rank alike (the same call on every rank; relaxed order only).  A type
+        whose coefficient is not 0 exchanges one more halo per sub-step, after its last collision pass: the ghost records
+        of that pass carry the sender's displacement of the sub-step where a collision pass's carry inverse mass and
+        radius, so a record stays 40 bytes."""
+        self.local.set_viscosity(white, yolk)
+
+    def viscosity(self):
+        return self.local.viscosity()
+
+    def viscosity_pairs(self):
+        """SimulationHandler.viscosity_pairs summed over the ranks (a collective: every rank calls it)"""
+        if self.world == 1:
+            return self.local.viscosity_pairs()
+        tot = self.torch.tensor(self.local.viscosity_pairs(), dtype=self.torch.int64, device=self.device)
+        self.dist.all_reduce(tot, op=self.dist.ReduceOp.SUM)
+        return [int(v) for v in tot.tolist()]
+
+    def _viscous(self):
+        """the coefficients the local handle holds: what the library decides a step's pass sequence from"""
+        return self.local.viscosity()
+
     def halo_counters(self):
-        """relaxed steps of this rank, summed over the run: collision passes, ghost records received, their bytes"""
+        """relaxed steps of this rank, summed over the run: passes with a halo (the collision passes and, while a viscosity
+        coefficient is not 0, one viscosity pass per sub-step), ghost records received, their bytes"""
         if self.halo is None:
             return dict(passes=self._halo_passes, records=0, bytes=0)
         return dict(passes=self.halo.passes, records=self.halo.records, bytes=self.halo.bytes)
@@ -685,7 +708,7 @@ class ShardedSimulationHandler(_HandlerSurface):
         if self.world == 1:
             self.local.step(delta, n_substeps, n_collision_steps)
             if self._order == "relaxed":
-                self._halo_passes += n_substeps * n_collision_steps
+                self._halo_passes += n_substeps * n_collision_steps + (n_substeps if any(self._viscous()) else 0)
             return 0
         if self._order == "relaxed":
             return self._step_relaxed(delta, n_substeps, n_collision_steps)
@@ -750,12 +773,17 @@ class ShardedSimulationHandler(_HandlerSurface):
         the step is committed (a NaN or out-of-range cell anywhere fails it everywhere, nothing committed)."""
         loc, torch, dist = self.local, self.torch, self.dist
         self._sync_keys()
+        viscous = any(self._viscous())
         loc.rx_begin(delta, n_substeps, n_collision_steps)
         try:
             for sub in range(n_substeps):
                 loc.rx_substep(sub)
                 for c in range(n_collision_steps):
                     p = sub * n_collision_steps + c
+                    pointers, counts = self.halo.exchange(p)
+                    loc.rx_run_pass(p, pointers, counts)
+                if viscous:  # the viscosity pass of the sub-step: the same exchange, the records carry displacements
+                    p = _ffi.RX_VISCOSITY_PASS + sub
                     pointers, counts = self.halo.exchange(p)
                     loc.rx_run_pass(p, pointers, counts)
             bad, _pairs, _records = loc.rx_check()

@@ -222,6 +222,43 @@ class _HandlerSurface:
         return [(_ffi.FORCE_KINDS[f.kind],) + tuple(f.p[:len(_ffi.FORCE_PARAMS[f.kind])]) + (types[f.type_mask],)
                 for f in arr[:n.value]]
 
+    # ------------------------------------------------ viscosity (egg_set_viscosity)
+    @staticmethod
+    def _c_viscosity(white, yolk):
+        """the two coefficients as the double[2] egg_set_viscosity takes; the range is checked here as the library checks it"""
+        arr = (C.c_double * 2)()
+        for w, (name, v) in enumerate((("white", white), ("yolk", yolk))):
+            try:
+                v = float(v)
+            except (TypeError, ValueError):
+                raise EggError("viscosity: the %s coefficient must be a number, not %r" % (name, v)) from None
+            if not (0.0 <= v <= 1.0):  # (false for a NaN)
+                raise EggError("viscosity: the %s coefficient %r lies outside [0, 1]" % (name, v))
+            arr[w] = v
+        return arr
+
+    def set_viscosity(self, white=0.0, yolk=0.0):
+        """XSPH viscosity per particle type, each coefficient in [0, 1], 0 = off ("Viscosity"; relaxed
+        order only).  In every sub-step of a relaxed step, after its last collision pass, a particle's displacement of the
+        sub-step is blended with the weighted mean of its neighbours' within one spatial-hash cell size: relative motion
+        inside an egg dies out, common motion stays (which `damping` cannot tell apart).  Positions are not touched; the
+        committed velocity is the smoothed one.  Raises EggError for a value outside [0, 1] (nothing changes) and for a
+        non-zero coefficient on a handle in exact order; set_solver_order("exact") raises while a coefficient is not 0."""
+        arr = self._c_viscosity(white, yolk)  # (refused here before any device call)
+        self._check(self._c("set_viscosity")(arr))
+
+    def viscosity(self):
+        """(white, yolk): the coefficients as stored"""
+        c = (C.c_double * 2)()
+        self._check(self._c("get_viscosity")(c))
+        return (c[0], c[1])
+
+    def viscosity_pairs(self):
+        """[white, yolk]: distinct pairs within the cell size, over the viscosity passes of committed steps, since creation"""
+        pairs = (C.c_int64 * 2)()
+        self._check(self._c("get_viscosity_pairs")(pairs))
+        return list(pairs)
+
     def _init_host_state(self, white_config, yolk_config):
         """config tables (validated like the reference, L:1253-1320), hidden constants and render switches; no device"""
         if white_config is None and yolk_config is None:

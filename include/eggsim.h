@@ -452,6 +452,35 @@ int egg_set_forces(egg_handle *h, int32_t n, const egg_force *f); /* n == 0 clea
 /* the list as stored: the count in *n, min(*n, cap) fields copied */
 int egg_get_forces(const egg_handle *h, int32_t cap, egg_force *f, int32_t *n);
 
+/* ---- viscosity (not in the reference, whose cohesion_strength moves nothing; DESIGN.md section 2.7, "Viscosity") ----
+ * XSPH velocity smoothing with a coefficient c per particle type, 0 (the default) = off.  For a type with c in (0, 1], every
+ * sub-step of a RELAXED step runs one more pass after its last collision pass (that pass's collider projection included)
+ * and before the post-solve.  Positions are not touched: the pass rewrites the start-of-sub-step positions `prev` from
+ * which the post-solve takes the velocity, so the committed velocity and the next sub-step's prediction are the smoothed
+ * ones and every collision distance and collider constraint stays as the last pass left it.  With p_i the position of
+ * particle i, u_i = (p_i.x - prev_i.x, p_i.y - prev_i.y) its displacement in this sub-step (every u taken before any prev
+ * is rewritten) and H the type's spatial-hash cell size of the step:
+ *   1. cells are built fresh from the positions, as in a collision pass;
+ *   2. candidates and visit order are a collision pass's: 3x3 cells, x offset outer, y offset inner, ascending key inside
+ *      a cell, j != i;
+ *   3. for each candidate j: dx = p_j.x - p_i.x, dy = p_j.y - p_i.y, d2 = dx dx + dy dy; !(d2 < H H): skipped; otherwise
+ *      d = sqrt(d2), w = 1 - d / H, sw = sw + w, sx = sx + w (u_j.x - u_i.x), sy = sy + w (u_j.y - u_i.y); the three sums
+ *      start at +0.0 (a coincident pair has w = 1; the 3x3 cells cover the whole disc of radius H);
+ *   4. !(inv_mass_i > eps) or !(sw > 0): prev_i keeps its bits;
+ *   5. otherwise nux = u_i.x + c (sx / sw), nuy = u_i.y + c (sy / sw), prev_i = (p_i.x - nux, p_i.y - nuy): a convex blend of
+ *      the particle's displacement and its neighbours' weighted mean, stable for every c in [0, 1].
+ * FP64 in exactly this order, no contraction; every comparison is false for a NaN.  Pairs of any batch smooth each other;
+ * white and yolk never interact.  pair_solves and max_pass_visits do not change; egg_get_viscosity_pairs counts, per type,
+ * the distinct pairs with d2 < H H over the viscosity passes of committed steps (a failed or discarded step adds nothing).
+ * Relaxed order only, as the colliders: a non-zero coefficient on a handle in exact order is EGG_ERR_UNSUPPORTED, and
+ * EGG_OPT_SOLVER_ORDER = 0 is EGG_ERR_UNSUPPORTED while a coefficient is not zero; both zero is always accepted.  A
+ * coefficient outside [0, 1] or NaN is EGG_ERR_INVALID_ARGUMENT and changes nothing.  Refused while a step is in flight.
+ * With both coefficients zero a step launches exactly what it launches without; a type with c > 0 adds five launches per
+ * sub-step. */
+int egg_set_viscosity(egg_handle *h, const double c[2]); /* c[EGG_WHITE], c[EGG_YOLK] */
+int egg_get_viscosity(const egg_handle *h, double c[2]);
+int egg_get_viscosity_pairs(egg_handle *h, int64_t pairs[2]);
+
 /* ---- several GPUs in one process (csrc/eggsim_group.cpp) -------------------------------------------------------
  * The multi-device form of the handle for a host that is ONE process (the LuaJIT wrapper): one egg_handle per device
  * behind one egg_group, x-slabs [cuts[k], cuts[k + 1]) of the plane per device (cuts: n_devices + 1 ascending values;
@@ -505,7 +534,15 @@ int egg_group_get_collider_hits(egg_group *g, int64_t hits[2]);
  * equal one handle's.  A group whose handles differ in their lists refuses to step. */
 int egg_group_set_forces(egg_group *g, int32_t n, const egg_force *f);
 int egg_group_get_forces(const egg_group *g, int32_t cap, egg_force *f, int32_t *n);
-/* cumulative over relaxed group steps, both types: collision passes, ghost records the devices received, their bytes */
+/* egg_set_viscosity for every handle of the group alike, with its rules (relaxed order only; back to exact order only with
+ * both coefficients zero); refused values change no handle.  In a viscosity pass a ghost record carries the displacement u
+ * in the two words that carry inverse mass and radius in a collision pass: a record stays 40 bytes.  The results equal one
+ * handle's; the pairs are summed over the handles.  A group whose handles differ in their coefficients refuses to step. */
+int egg_group_set_viscosity(egg_group *g, const double c[2]);
+int egg_group_get_viscosity(const egg_group *g, double c[2]);
+int egg_group_get_viscosity_pairs(egg_group *g, int64_t pairs[2]);
+/* cumulative over relaxed group steps, both types: passes with a halo (the collision passes and, while a coefficient is not
+ * zero, one viscosity pass per sub-step), ghost records the devices received, their bytes */
 int egg_group_get_halo_counters(const egg_group *g, int64_t *passes, int64_t *records, int64_t *bytes);
 
 /* ---- the rest of the SimulationHandler surface on a group.  One rule: whatever a group returns or draws equals, bit for
@@ -568,7 +605,15 @@ int egg_group_get_instances(egg_group *g, int which, egg_instance *data, float *
  *   for sub in 0 .. S-1:  egg_rx_substep(sub)
  *       for c in 0 .. C-1:  egg_rx_get_boxes(p)  ->  the ranks exchange boxes  ->  egg_rx_pack(p) + egg_rx_fetch
  *                           ->  the messages travel  ->  egg_rx_run_pass(p)
+ *       with viscosity (a coefficient of egg_set_viscosity is not zero), v = EGG_RX_VISCOSITY_PASS + sub:
+ *                           egg_rx_get_boxes(v)  ->  boxes  ->  egg_rx_pack(v) + egg_rx_fetch  ->  messages  ->  egg_rx_run_pass(v)
  *   egg_rx_check  ->  the ranks agree whether ANY of them flagged a bad position  ->  egg_rx_end(commit)
+ *
+ * The viscosity pass of sub-step `sub` comes after the sub-step's C collision passes and before the next egg_rx_substep /
+ * egg_rx_check, which are refused until it has run.  It takes the types whose coefficient is not zero: the other type
+ * reports an empty box, packs no record and runs nothing.  Its records have the same 5 words; words 2 and 3 carry the
+ * sender's displacement (u.x, u.y) of the sub-step instead of inverse mass and radius.  EGG_RX_VISCOSITY_PASS + sub is
+ * refused while both coefficients are zero.  Every rank sets the coefficients alike.
  *
  * A MESSAGE is one contiguous run of 64-bit words: word 0 the record count m, then m records of 5 words (40 bytes):
  * x, y, inverse mass, radius (doubles), global key (int64) -- 8 * (1 + 5 m) bytes.  The key is below 2^29; with
@@ -581,6 +626,7 @@ int egg_group_get_instances(egg_group *g, int which, egg_instance *data, float *
  * memory or memory of the handle's device (hipMemcpyDefault), as for egg_export_batch.
  * Between egg_rx_begin and egg_rx_end the state-mutating entry points are refused.  The handle must be in relaxed order;
  * egg_step, egg_step_begin, egg_step_end and egg_get_claims_many behave as they do on any relaxed handle. */
+#define EGG_RX_VISCOSITY_PASS 0x40000000
 typedef struct {
     int32_t lo_x, lo_y, hi_x, hi_y; /* spatial-hash cells, inclusive */
     int32_t empty;                  /* 1: no particle of the type on this handle (the other fields are 0) */
