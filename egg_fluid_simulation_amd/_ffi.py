@@ -104,6 +104,10 @@ class EggCollider(C.Structure):  # egg_collider: a static collider of the relaxe
     _fields_ = [("kind", C.c_int32), ("type_mask", C.c_int32), ("p", C.c_double * 4)]
 
 
+class EggColliderSurface(C.Structure):  # egg_collider_surface: friction and surface velocity of a collider (24 bytes)
+    _fields_ = [("friction", C.c_double), ("vx", C.c_double), ("vy", C.c_double)]
+
+
 MAX_COLLIDERS = 64  # EGG_MAX_COLLIDERS
 COLLIDER_HALF_PLANE, COLLIDER_DISC, COLLIDER_CONTAINER, COLLIDER_SEGMENT = 0, 1, 2, 3
 COLLIDER_KINDS = ("half_plane", "disc", "container", "segment")  # by EGG_COLLIDER_* value
@@ -176,6 +180,12 @@ _SIGNATURES = {
     "egg_set_colliders": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggCollider)]),
     "egg_get_colliders": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggCollider), C.POINTER(C.c_int32)]),
     "egg_get_collider_hits": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "egg_set_collider_surfaces": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggColliderSurface)]),
+    "egg_get_collider_surfaces": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggColliderSurface), C.POINTER(C.c_int32)]),
+    "egg_get_collider_grips": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "egg_group_set_collider_surfaces": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggColliderSurface)]),
+    "egg_group_get_collider_surfaces": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggColliderSurface), C.POINTER(C.c_int32)]),
+    "egg_group_get_collider_grips": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "egg_group_set_colliders": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggCollider)]),
     "egg_group_get_colliders": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggCollider), C.POINTER(C.c_int32)]),
     "egg_group_get_collider_hits": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),

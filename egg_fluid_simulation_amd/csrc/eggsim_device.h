@@ -359,6 +359,43 @@ struct EggRelaxedGroupCohColArgs {
     EggRxColliderFields d;
 };
 
+// Collider surfaces (egg_set_collider_surfaces, DESIGN.md section 2.7, "Collider surfaces"): the surface instantiations of
+// the gather kernel (egg_rx_gather*_col_srf_kernel) take these besides the collider fields.  The records are parallel to
+// the collider list, in a small device buffer written when they are set; a record has the layout of the ABI's
+// egg_collider_surface (24 bytes).
+struct EggSurface {
+    double friction, vx, vy;
+};
+struct EggRxSurfaceFields {
+    const EggSurface *list;              // [the collider count]; every lane reads the same record
+    double sub_delta;                    // h of step 5c
+    unsigned long long *grips;           // one word: friction applications (stick or slide) in this step
+};
+struct EggRelaxedColSrfArgs {
+    EggRelaxedArgs a;
+    EggRxColliderFields d;
+    EggRxSurfaceFields s;
+};
+struct EggRelaxedGroupColSrfArgs {
+    EggRelaxedArgs a;
+    EggRxGroupFields g;
+    EggRxColliderFields d;
+    EggRxSurfaceFields s;
+};
+struct EggRelaxedCohColSrfArgs {
+    EggRelaxedArgs a;
+    EggRxCohesionFields c;
+    EggRxColliderFields d;
+    EggRxSurfaceFields s;
+};
+struct EggRelaxedGroupCohColSrfArgs {
+    EggRelaxedArgs a;
+    EggRxGroupFields g;
+    EggRxCohesionFields c;
+    EggRxColliderFields d;
+    EggRxSurfaceFields s;
+};
+
 // Force fields (egg_set_forces, DESIGN.md section 2.7, "Forces"): the force instantiations of the kernels that begin a
 // sub-step (egg_rx_begin*_frc_kernel, egg_rx_mid*_frc_kernel) take these besides.  The list is the handle's, in a small
 // device buffer written when it is set; a record has the layout of the ABI's egg_force (40 bytes).

@@ -64,6 +64,7 @@ struct egg_group {
     int order = EGG_SOLVER_EXACT;
     int cohesion = EGG_COHESION_REFERENCE;  // egg_group_set_cohesion: every handle's EGG_OPT_COHESION
     std::vector<egg_collider> colliders;    // egg_group_set_colliders: every handle's list, as given
+    std::vector<egg_collider_surface> surfaces;  // egg_group_set_collider_surfaces: every handle's records, as given
     std::vector<egg_force> forces;          // egg_group_set_forces: every handle's list, as given
     double viscosity[2] = {0.0, 0.0};       // egg_group_set_viscosity: every handle's coefficients
     int64_t halo_passes = 0, halo_records = 0;  // relaxed group steps: collision passes, ghost records received
@@ -646,11 +647,46 @@ int egg_group_set_colliders(egg_group *g, int32_t n, const egg_collider *c) {
     for (size_t k = 0; k < g->h.size(); ++k) {
         const int rc = egg_set_colliders(g->h[k], n, c);
         if (rc < 0) {  // (handle 0 refuses a bad list before any handle has changed; a later one: the others go back)
-            for (size_t j = 0; j < k; ++j) (void)egg_set_colliders(g->h[j], (int32_t)g->colliders.size(), g->colliders.data());
+            for (size_t j = 0; j < k; ++j) {  // (with their surfaces, which a list that is set resets)
+                (void)egg_set_colliders(g->h[j], (int32_t)g->colliders.size(), g->colliders.data());
+                (void)egg_set_collider_surfaces(g->h[j], (int32_t)g->surfaces.size(), g->surfaces.data());
+            }
             return gfail(g, rc, "device %d: %s", (int)k, egg_last_error(g->h[k]));
         }
     }
     g->colliders.assign(c, c + (n > 0 ? n : 0));
+    g->surfaces.clear();  // (every handle has reset its own)
+    return EGG_OK;
+}
+
+int egg_group_set_collider_surfaces(egg_group *g, int32_t n, const egg_collider_surface *s) {
+    if (!g) return EGG_ERR_INVALID_ARGUMENT;
+    for (size_t k = 0; k < g->h.size(); ++k) {
+        const int rc = egg_set_collider_surfaces(g->h[k], n, s);
+        if (rc < 0) {  // (handle 0 refuses bad records before any handle has changed; a later one: the others go back)
+            for (size_t j = 0; j < k; ++j) (void)egg_set_collider_surfaces(g->h[j], (int32_t)g->surfaces.size(), g->surfaces.data());
+            return gfail(g, rc, "device %d: %s", (int)k, egg_last_error(g->h[k]));
+        }
+    }
+    g->surfaces.assign(s, s + (n > 0 ? n : 0));
+    return EGG_OK;
+}
+
+int egg_group_get_collider_surfaces(const egg_group *g, int32_t cap, egg_collider_surface *s, int32_t *n) {
+    if (!g || g->h.empty()) return EGG_ERR_INVALID_ARGUMENT;
+    return egg_get_collider_surfaces(g->h[0], cap, s, n);  // (as stored: every handle holds the same records)
+}
+
+int egg_group_get_collider_grips(egg_group *g, int64_t grips[2]) {
+    if (!g) return EGG_ERR_INVALID_ARGUMENT;
+    if (!grips) return gfail(g, EGG_ERR_INVALID_ARGUMENT, "egg_group_get_collider_grips: grips is NULL");
+    grips[0] = grips[1] = 0;
+    for (size_t k = 0; k < g->h.size(); ++k) {
+        int64_t one[2] = {0, 0};
+        GTRY(g, k, egg_get_collider_grips(g->h[k], one));
+        grips[0] += one[0];
+        grips[1] += one[1];
+    }
     return EGG_OK;
 }
 

@@ -86,6 +86,10 @@ extern "C" __global__ void egg_rx_gather_col_kernel(EggRelaxedColArgs A);
 extern "C" __global__ void egg_rx_gather_group_col_kernel(EggRelaxedGroupColArgs A);
 extern "C" __global__ void egg_rx_gather_coh_col_kernel(EggRelaxedCohColArgs A);
 extern "C" __global__ void egg_rx_gather_group_coh_col_kernel(EggRelaxedGroupCohColArgs A);
+extern "C" __global__ void egg_rx_gather_col_srf_kernel(EggRelaxedColSrfArgs A);
+extern "C" __global__ void egg_rx_gather_group_col_srf_kernel(EggRelaxedGroupColSrfArgs A);
+extern "C" __global__ void egg_rx_gather_coh_col_srf_kernel(EggRelaxedCohColSrfArgs A);
+extern "C" __global__ void egg_rx_gather_group_coh_col_srf_kernel(EggRelaxedGroupCohColSrfArgs A);
 extern "C" __global__ void egg_rx_begin_frc_kernel(EggRelaxedFrcArgs A);
 extern "C" __global__ void egg_rx_mid_frc_kernel(EggRelaxedFrcArgs A);
 extern "C" __global__ void egg_rx_begin_group_frc_kernel(EggRelaxedGroupFrcArgs A);
@@ -412,6 +416,13 @@ struct egg_handle {
     std::vector<egg_collider> colliders;
     DevBuf<EggCollider> d_colliders;
     int64_t collider_hits[2] = {0, 0};
+    // collider surfaces (egg_set_collider_surfaces): empty = every surface is the default, else one record per collider;
+    // the copy on the device (written when they are set, never per step); whether any friction > 0 -- only then does a
+    // step launch the surface instantiations -- and the grips of committed steps per type
+    std::vector<egg_collider_surface> surfaces;
+    DevBuf<EggSurface> d_surfaces;
+    bool surfaces_grip = false;
+    int64_t collider_grips[2] = {0, 0};
     // force fields (egg_set_forces; relaxed order only): the list as egg_get_forces returns it and its copy on the device
     // (written when the list is set, never per step)
     std::vector<egg_force> forces;
@@ -563,7 +574,7 @@ constexpr char kRelaxedBadCellText[] = "relaxed order: a position is NaN or its 
 // records sent to each of them.  With effective cohesion one more word: the pairs that cohered.  With colliders one
 // more: their hits.  With viscosity the halo words cover V = S more passes, the viscosity pass of sub-step `sub` being
 // halo pass P + sub, and one more word, the last, holds the pairs the viscosity passes counted.  V = 0 is the layout
-// without.
+// without.  With collider surfaces of which one has friction one more word behind all of these: the grips.
 struct RelaxedLayout {
     size_t P = 0, nq = 0;
     bool halo = false;  // ghosts of other handles' particles take part: the group instantiations of the kernels
@@ -571,6 +582,7 @@ struct RelaxedLayout {
     bool colliders = false;  // (set by prepare_type: the handle's collider list is not empty)
     bool forces = false;     // (set by prepare_type: the handle's force list is not empty; no status word of its own)
     size_t V = 0;            // (set by prepare_type: the sub-steps, when the type's viscosity coefficient is not zero)
+    bool surfaces = false;   // (set by prepare_type: a collider surface of the handle has friction > 0)
     size_t H() const { return P + V; }                                        // passes with a halo
     size_t box(size_t p) const { return 1 + P + 4 * p; }                      // 4 words
     size_t ghosts(size_t p) const { return 1 + P + 4 * H() + p; }
@@ -578,7 +590,8 @@ struct RelaxedLayout {
     size_t cohered() const { return halo ? 1 + P + 5 * H() + H() * nq : 1 + P; }
     size_t hits() const { return cohered() + (cohesion ? 1 : 0); }
     size_t visc() const { return hits() + (colliders ? 1 : 0); }
-    size_t words() const { return visc() + (V ? 1 : 0); }
+    size_t grips() const { return visc() + (V ? 1 : 0); }
+    size_t words() const { return grips() + (surfaces ? 1 : 0); }
 };
 struct RelaxedStep {  // one type of one handle in a relaxed step
     egg_handle *h = nullptr;
@@ -588,6 +601,7 @@ struct RelaxedStep {  // one type of one handle in a relaxed step
     EggRelaxedGroupArgs A{};  // (A.g stays null without a halo)
     EggRxCohesionFields coh{};  // effective cohesion (L.cohesion): compliance and factor of the type, the tag arrays
     EggRxColliderFields col{};  // static colliders (L.colliders): the handle's list, the type's bit, the hit counter
+    EggRxSurfaceFields srf{};   // collider surfaces (L.surfaces): the handle's records, the sub-step, the grip counter
     EggRxForceFields frc{};     // force fields (L.forces): the handle's list, the type's bit
     EggRxViscFields visc{};     // viscosity (L.V): the type's coefficient, the pair counter
     int64_t ghost_cap = 0;    // a pass runs over n + ghost_cap entries

@@ -1024,6 +1024,8 @@ int egg_set_colliders(egg_handle *h, int32_t n, const egg_collider *c) {
         HIP_TRY(h, hipMemcpy(h->d_colliders.p, list.data(), (size_t)n * sizeof(egg_collider), hipMemcpyHostToDevice));
     }
     h->colliders.swap(list);
+    h->surfaces.clear();  // (the indices no longer mean anything: every surface is the default again)
+    h->surfaces_grip = false;
     return EGG_OK;
 }
 
@@ -1032,6 +1034,59 @@ int egg_get_colliders(const egg_handle *h, int32_t cap, egg_collider *c, int32_t
     const int32_t have = (int32_t)h->colliders.size();
     if (n) *n = have;
     if (c && cap > 0) memcpy(c, h->colliders.data(), (size_t)std::min(cap, have) * sizeof(egg_collider));
+    return EGG_OK;
+}
+
+// Collider surfaces ("Collider surfaces"): one record per collider, or none (all default).
+// Everything is checked before anything changes.
+int egg_set_collider_surfaces(egg_handle *h, int32_t n, const egg_collider_surface *sf) {
+    if (!h) return EGG_ERR_INVALID_ARGUMENT;
+    REJECT_IN_FLIGHT(h, "egg_set_collider_surfaces");
+    static_assert(sizeof(egg_collider_surface) == 24 && sizeof(EggSurface) == sizeof(egg_collider_surface), "a surface record is 24 bytes");
+    if (n != 0 && n != (int32_t)h->colliders.size())
+        return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_collider_surfaces: n = %d, the list holds %d colliders (n is that, or 0)", (int)n,
+                    (int)h->colliders.size());
+    if (n > 0 && !sf) return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_collider_surfaces: n = %d without records", (int)n);
+    std::vector<egg_collider_surface> list((size_t)n);
+    bool grip = false;
+    for (int32_t k = 0; k < n; ++k) {
+        egg_collider_surface &o = list[(size_t)k];
+        o = sf[k];
+        if (!std::isfinite(o.friction) || o.friction < 0)
+            return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_collider_surfaces: collider %d: friction %g is negative or not finite", (int)k,
+                        o.friction);
+        if (!std::isfinite(o.vx) || !std::isfinite(o.vy))
+            return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_collider_surfaces: collider %d: the velocity (%g, %g) is not finite", (int)k, o.vx,
+                        o.vy);
+        o.friction = o.friction + 0.0;  // (-0.0 is stored as +0.0, in every field: handles set alike compare alike)
+        o.vx = o.vx + 0.0;
+        o.vy = o.vy + 0.0;
+        grip |= o.friction > 0.0;
+    }
+    if (n > 0) {  // (no step is running: every step ends with its streams waited for)
+        HIP_TRY(h, hipSetDevice(h->device));
+        HIP_TRY(h, h->d_surfaces.reserve(EGG_MAX_COLLIDERS, false, nullptr));
+        HIP_TRY(h, hipMemcpy(h->d_surfaces.p, list.data(), (size_t)n * sizeof(egg_collider_surface), hipMemcpyHostToDevice));
+    }
+    h->surfaces.swap(list);
+    h->surfaces_grip = grip;
+    return EGG_OK;
+}
+
+int egg_get_collider_surfaces(const egg_handle *h, int32_t cap, egg_collider_surface *sf, int32_t *n) {
+    if (!h) return EGG_ERR_INVALID_ARGUMENT;
+    const int32_t have = (int32_t)h->colliders.size();
+    if (n) *n = have;
+    for (int32_t k = 0; sf && k < std::min(cap, have); ++k)
+        sf[k] = h->surfaces.empty() ? egg_collider_surface{0.0, 0.0, 0.0} : h->surfaces[(size_t)k];
+    return EGG_OK;
+}
+
+int egg_get_collider_grips(egg_handle *h, int64_t grips[2]) {
+    if (!h) return EGG_ERR_INVALID_ARGUMENT;
+    if (!grips) return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_get_collider_grips: grips is NULL");
+    grips[0] = h->collider_grips[0];
+    grips[1] = h->collider_grips[1];
     return EGG_OK;
 }
 

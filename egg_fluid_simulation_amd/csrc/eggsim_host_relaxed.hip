@@ -16,6 +16,9 @@
 // cohesion off launches what it always launched, so all three paths pick cohesion up from here.
 // With static colliders (egg_set_colliders, RelaxedLayout::colliders) launch_pass picks the collider instantiation of the
 // gather kernel and RelaxedStep::col carries the handle's list; with an empty list a step launches what it always launched.
+// With collider surfaces (egg_set_collider_surfaces, RelaxedLayout::surfaces) of which at least one has friction > 0
+// launch_pass picks the surface twin of the collider instantiation and RelaxedStep::srf carries the records; while every
+// friction is zero -- a surface velocity alone does nothing -- a step launches what it launches without surfaces.
 // With force fields (egg_set_forces, RelaxedLayout::forces) launch_substep picks the force instantiation of the begin / mid
 // kernel and RelaxedStep::frc carries the handle's list; with an empty list a step launches what it always launched.
 // With viscosity (egg_set_viscosity, RelaxedLayout::V) every sub-step of a type whose coefficient is not zero ends with
@@ -169,6 +172,7 @@ int prepare_type(RelaxedStep &st, int C, size_t ghosts, const RelaxedLayout &L, 
     st.L = L;
     st.L.cohesion = h->opt_cohesion == EGG_COHESION_EFFECTIVE;
     st.L.colliders = !h->colliders.empty();
+    st.L.surfaces = st.L.colliders && h->surfaces_grip;
     st.L.forces = !h->forces.empty();
     st.L.V = h->viscosity[st.w] > 0.0 ? L.P / (size_t)C : 0;
     st.C = C;
@@ -192,6 +196,12 @@ int prepare_type(RelaxedStep &st, int C, size_t ghosts, const RelaxedLayout &L, 
         st.col.count = (int32_t)h->colliders.size();
         st.col.type_bit = 1 << st.w;
         st.col.hits = r.status.p + st.L.hits();
+    }
+    st.srf = EggRxSurfaceFields{};
+    if (st.L.surfaces) {
+        st.srf.list = h->d_surfaces.p;
+        st.srf.sub_delta = st.env.sub_delta;
+        st.srf.grips = r.status.p + st.L.grips();
     }
     st.frc = EggRxForceFields{};
     if (st.L.forces) {
@@ -289,13 +299,19 @@ int launch_pass(RelaxedStep &st, int p) {
         if (st.L.cohesion) {
             const EggRelaxedGroupCohArgs k{a.a, a.g, st.coh};
             hipLaunchKernelGGL(egg_rx_rank_group_coh_kernel, grid, block, 0, s.stream, k);
-            if (st.L.colliders)
+            if (st.L.surfaces)
+                hipLaunchKernelGGL(egg_rx_gather_group_coh_col_srf_kernel, grid, block, 0, s.stream,
+                                   EggRelaxedGroupCohColSrfArgs{a.a, a.g, st.coh, st.col, st.srf});
+            else if (st.L.colliders)
                 hipLaunchKernelGGL(egg_rx_gather_group_coh_col_kernel, grid, block, 0, s.stream, EggRelaxedGroupCohColArgs{a.a, a.g, st.coh, st.col});
             else
                 hipLaunchKernelGGL(egg_rx_gather_group_coh_kernel, grid, block, 0, s.stream, k);
         } else {
             hipLaunchKernelGGL(egg_rx_rank_group_kernel, grid, block, 0, s.stream, a);
-            if (st.L.colliders)
+            if (st.L.surfaces)
+                hipLaunchKernelGGL(egg_rx_gather_group_col_srf_kernel, grid, block, 0, s.stream,
+                                   EggRelaxedGroupColSrfArgs{a.a, a.g, st.col, st.srf});
+            else if (st.L.colliders)
                 hipLaunchKernelGGL(egg_rx_gather_group_col_kernel, grid, block, 0, s.stream, EggRelaxedGroupColArgs{a.a, a.g, st.col});
             else
                 hipLaunchKernelGGL(egg_rx_gather_group_kernel, grid, block, 0, s.stream, a);
@@ -305,13 +321,18 @@ int launch_pass(RelaxedStep &st, int p) {
         if (st.L.cohesion) {
             const EggRelaxedCohArgs k{a.a, st.coh};
             hipLaunchKernelGGL(egg_rx_rank_coh_kernel, grid, block, 0, s.stream, k);
-            if (st.L.colliders)
+            if (st.L.surfaces)
+                hipLaunchKernelGGL(egg_rx_gather_coh_col_srf_kernel, grid, block, 0, s.stream,
+                                   EggRelaxedCohColSrfArgs{a.a, st.coh, st.col, st.srf});
+            else if (st.L.colliders)
                 hipLaunchKernelGGL(egg_rx_gather_coh_col_kernel, grid, block, 0, s.stream, EggRelaxedCohColArgs{a.a, st.coh, st.col});
             else
                 hipLaunchKernelGGL(egg_rx_gather_coh_kernel, grid, block, 0, s.stream, k);
         } else {
             hipLaunchKernelGGL(egg_rx_rank_kernel, grid, block, 0, s.stream, a.a);
-            if (st.L.colliders)
+            if (st.L.surfaces)
+                hipLaunchKernelGGL(egg_rx_gather_col_srf_kernel, grid, block, 0, s.stream, EggRelaxedColSrfArgs{a.a, st.col, st.srf});
+            else if (st.L.colliders)
                 hipLaunchKernelGGL(egg_rx_gather_col_kernel, grid, block, 0, s.stream, EggRelaxedColArgs{a.a, st.col});
             else
                 hipLaunchKernelGGL(egg_rx_gather_kernel, grid, block, 0, s.stream, a.a);
@@ -437,6 +458,7 @@ void relaxed_commit(egg_handle *h, const RelaxedStep st[2], int S, int C, double
         h->stats.max_pass_visits[w] = most;
         if (st[w].L.cohesion) h->stats.cohesion_solves += (int64_t)s.rx.h_status.p[st[w].L.cohered()];
         if (st[w].L.colliders) h->collider_hits[w] += (int64_t)s.rx.h_status.p[st[w].L.hits()];
+        if (st[w].L.surfaces) h->collider_grips[w] += (int64_t)s.rx.h_status.p[st[w].L.grips()];
         if (st[w].L.V) h->viscosity_pairs[w] += (int64_t)s.rx.h_status.p[st[w].L.visc()];
         h->stats.follow_solves += s.n * S;
         // the exact path's host copies of the atoms' cells describe older positions now

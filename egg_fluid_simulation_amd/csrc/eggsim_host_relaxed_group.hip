@@ -117,6 +117,11 @@ int relaxed_group_step(egg_handle *const *hs, int nh, double delta, int S, int C
             *error = "relaxed order: the handles of the group differ in their colliders (egg_group_set_colliders sets all)";
             return EGG_ERR_INVALID_ARGUMENT;
         }
+        const std::vector<egg_collider_surface> &sa = hs[0]->surfaces, &sb = hs[k]->surfaces;
+        if (sa.size() != sb.size() || (!sa.empty() && memcmp(sa.data(), sb.data(), sa.size() * sizeof(egg_collider_surface)) != 0)) {
+            *error = "relaxed order: the handles of the group differ in their collider surfaces (egg_group_set_collider_surfaces sets all)";
+            return EGG_ERR_INVALID_ARGUMENT;
+        }
     }
     for (int k = 1; k < nh; ++k) {
         const std::vector<egg_force> &a = hs[0]->forces, &b = hs[k]->forces;

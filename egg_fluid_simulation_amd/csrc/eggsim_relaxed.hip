@@ -31,6 +31,12 @@
 // into every collider of the handle's list whose mask covers the type, in list order, before it is written.  The
 // D = false instantiations are the kernels as they were.
 //
+// With collider surfaces (egg_set_collider_surfaces; DESIGN.md section 2.7, "Collider surfaces") of which at least one has
+// friction > 0 the collider instantiations run as their surface twins (D = true and S = true,
+// egg_rx_gather*_col_srf_kernel): right after a collider with friction has projected a particle, step 5c removes the
+// tangential part of the particle's displacement over the sub-step, relative to the surface's velocity, up to friction
+// times the depth the projection has just corrected.  The S = false instantiations are the kernels as they were.
+//
 // With force fields (egg_set_forces; DESIGN.md section 2.7, "Forces") the kernels that begin a sub-step run in their force
 // instantiations (F = true, egg_rx_begin*_frc_kernel, egg_rx_mid*_frc_kernel): the fields of the handle's list whose mask
 // covers the type accelerate the velocity the pre-solve is about to damp.  The F = false instantiations are the kernels
@@ -93,15 +99,49 @@ __device__ __forceinline__ uint32_t rx_hash(unsigned long long k) {  // the 64-b
     return (uint32_t)k;
 }
 
+// Step 5c of the relaxed pass: position-based Coulomb friction of the collider that has just projected the particle to
+// `out`.  (nx, ny) and pen are the projection's normal and the depth it corrected, pv the particle's position at the
+// start of the sub-step, h the sub-step.  The tangential part of the displacement relative to the surface is removed:
+// all of it up to friction * pen (stick), that much of it beyond (slide).  Every comparison is false for a NaN.  Returns
+// 1 for an application, 0 when the surface has no friction or there is no tangential displacement.
+__device__ __forceinline__ int rx_grip(const EggSurface &sf, double h, double2 pv, double nx, double ny, double pen,
+                                       double2 &out) {
+    if (!(sf.friction > 0.0)) return 0;
+    const double ex = (out.x - pv.x) - h * sf.vx;
+    const double ey = (out.y - pv.y) - h * sf.vy;
+    const double dn = ex * nx + ey * ny;
+    const double tx = ex - dn * nx;
+    const double ty = ey - dn * ny;
+    const double tl2 = tx * tx + ty * ty;
+    if (!(tl2 > 0.0)) return 0;
+    const double tl = sqrt(tl2);
+    const double lim = sf.friction * pen;
+    if (tl <= lim) {  // stick
+        out.x = out.x - tx;
+        out.y = out.y - ty;
+    } else {  // slide
+        const double f = lim / tl;
+        out.x = out.x - tx * f;
+        out.y = out.y - ty * f;
+    }
+    return 1;
+}
+
 // Step 5b of the relaxed pass: the colliders of the list whose mask covers the type, in list order, each on the result
 // of the one before it.  i: the particle's key (picks the way out of a disc's centre); r: its radius.  Every lane of a
 // wave reads the same record and takes the same branch on its kind.  Every comparison is false for a NaN: such a
 // position stays.  Returns the colliders that moved the particle.
-__device__ __forceinline__ int rx_collide(const EggRxColliderFields &Co, int i, double r, double2 &out) {
+// S: step 5c, the surface of a collider that has just moved the particle (rx_grip); pv is the particle's position at the
+// start of the sub-step, grips counts the applications.  The surface record is read like the collider record.
+template <bool S>
+__device__ __forceinline__ int rx_collide(const EggRxColliderFields &Co, const EggRxSurfaceFields &Su, int i, double r,
+                                          double2 pv, double2 &out, int &grips) {
     int hits = 0;
     for (int c = 0; c < Co.count; ++c) {
         const EggCollider col = Co.list[c];
         if (!(col.type_mask & Co.type_bit)) continue;
+        EggSurface sf{};
+        if (S) sf = Su.list[c];
         const double x = out.x, y = out.y;
         if (col.kind == EGG_RX_COLLIDER_HALF_PLANE) {  // p = (nx, ny, off): keeps n . pos - off >= r
             const double s = (col.p[0] * x + col.p[1] * y) - (col.p[2] + r);
@@ -109,6 +149,7 @@ __device__ __forceinline__ int rx_collide(const EggRxColliderFields &Co, int i, 
                 out.x = x - s * col.p[0];
                 out.y = y - s * col.p[1];
                 ++hits;
+                if (S) grips += rx_grip(sf, Su.sub_delta, pv, col.p[0], col.p[1], -s, out);
             }
             continue;
         }
@@ -133,6 +174,7 @@ __device__ __forceinline__ int rx_collide(const EggRxColliderFields &Co, int i, 
                 out.x = cx + (dx / d) * m;
                 out.y = cy + (dy / d) * m;
                 ++hits;
+                if (S) grips += rx_grip(sf, Su.sub_delta, pv, dx / d, dy / d, d - m, out);
             }
         } else {  // disc, p = (cx, cy, R): stays outside
             const double m = R + r;
@@ -149,6 +191,7 @@ __device__ __forceinline__ int rx_collide(const EggRxColliderFields &Co, int i, 
                 out.x = cx + ux * m;
                 out.y = cy + uy * m;
                 ++hits;
+                if (S) grips += rx_grip(sf, Su.sub_delta, pv, ux, uy, m - d, out);
             }
         }
     }
@@ -340,14 +383,17 @@ __device__ __forceinline__ void rx_rank(const EggRelaxedArgs &A, const EggRxGrou
 // key; in a group a ghost's slot gathers nothing (its own device moves it), and the gather records the box of what it
 // writes when the pass is not the sub-step's last.  K: a pair that does not collide may cohere -- same tag, within reach
 // -- and then runs the collision correction's arithmetic with the cohesion compliance (one path for both kinds).  D: the
-// new position goes through the colliders before it is written (whether or not a pair fired).
-template <bool G, bool K, bool D>
+// new position goes through the colliders before it is written (whether or not a pair fired).  S (with D only): a
+// collider's surface acts right after its projection (step 5c); prev[me] is read once, for that.
+template <bool G, bool K, bool D, bool S>
 __device__ __forceinline__ void rx_gather(EggRelaxedArgs A, const EggRxGroupFields &X, const EggRxCohesionFields &Ch,
-                                          const EggRxColliderFields &Co) {
+                                          const EggRxColliderFields &Co, const EggRxSurfaceFields &Su) {
+    static_assert(D || !S, "surfaces belong to colliders");
     const int t = (int)(blockIdx.x * 256 + threadIdx.x);
     int pairs = 0;
     int cohered = 0;  // (K only)
     int hits = 0;     // (D only)
+    int grips = 0;    // (S only)
     bool local = false;  // (group: the slot holds one of this device's particles; gout is its new position)
     double2 gout = make_double2(0.0, 0.0);
     if (G ? t < rx_entries<G>(A, X) && X.sloc[t] < A.n : t < A.n) {
@@ -430,7 +476,7 @@ __device__ __forceinline__ void rx_gather(EggRelaxedArgs A, const EggRxGroupFiel
             out.x = p.x + (sx * A.omega) / (double)n_fired;
             out.y = p.y + (sy * A.omega) / (double)n_fired;
         }
-        if (D) hits = rx_collide(Co, i, wr.y, out);
+        if (D) hits = rx_collide<S>(Co, Su, i, wr.y, S ? A.prev[me] : make_double2(0.0, 0.0), out, grips);
         A.pos_next[me] = out;
         if (G) {
             local = true;
@@ -451,6 +497,11 @@ __device__ __forceinline__ void rx_gather(EggRelaxedArgs A, const EggRxGroupFiel
         for (int d = 32; d >= 1; d >>= 1) hits += __shfl_xor(hits, d, 64);
         if ((threadIdx.x & 63) == 0 && hits) atomicAdd(Co.hits, (unsigned long long)hits);
     }
+    if (S) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) grips += __shfl_xor(grips, d, 64);
+        if ((threadIdx.x & 63) == 0 && grips) atomicAdd(Su.grips, (unsigned long long)grips);
+    }
     if (G && X.box) rx_box(X.box, local, gout, A.cell_size);
 }
 
@@ -460,18 +511,24 @@ extern "C" __global__ void __launch_bounds__(256) egg_rx_scatter_kernel(EggRelax
 extern "C" __global__ void __launch_bounds__(256) egg_rx_scatter_group_kernel(EggRelaxedGroupArgs A) { rx_scatter<true>(A.a, A.g); }
 extern "C" __global__ void __launch_bounds__(256) egg_rx_rank_kernel(EggRelaxedArgs A) { rx_rank<false, false>(A, EggRxGroupFields{}, EggRxCohesionFields{}); }
 extern "C" __global__ void __launch_bounds__(256) egg_rx_rank_group_kernel(EggRelaxedGroupArgs A) { rx_rank<true, false>(A.a, A.g, EggRxCohesionFields{}); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_kernel(EggRelaxedArgs A) { rx_gather<false, false, false>(A, EggRxGroupFields{}, EggRxCohesionFields{}, EggRxColliderFields{}); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_kernel(EggRelaxedGroupArgs A) { rx_gather<true, false, false>(A.a, A.g, EggRxCohesionFields{}, EggRxColliderFields{}); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_kernel(EggRelaxedArgs A) { rx_gather<false, false, false, false>(A, EggRxGroupFields{}, EggRxCohesionFields{}, EggRxColliderFields{}, EggRxSurfaceFields{}); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_kernel(EggRelaxedGroupArgs A) { rx_gather<true, false, false, false>(A.a, A.g, EggRxCohesionFields{}, EggRxColliderFields{}, EggRxSurfaceFields{}); }
 // effective cohesion
 extern "C" __global__ void __launch_bounds__(256) egg_rx_rank_coh_kernel(EggRelaxedCohArgs A) { rx_rank<false, true>(A.a, EggRxGroupFields{}, A.c); }
 extern "C" __global__ void __launch_bounds__(256) egg_rx_rank_group_coh_kernel(EggRelaxedGroupCohArgs A) { rx_rank<true, true>(A.a, A.g, A.c); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_coh_kernel(EggRelaxedCohArgs A) { rx_gather<false, true, false>(A.a, EggRxGroupFields{}, A.c, EggRxColliderFields{}); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_coh_kernel(EggRelaxedGroupCohArgs A) { rx_gather<true, true, false>(A.a, A.g, A.c, EggRxColliderFields{}); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_coh_kernel(EggRelaxedCohArgs A) { rx_gather<false, true, false, false>(A.a, EggRxGroupFields{}, A.c, EggRxColliderFields{}, EggRxSurfaceFields{}); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_coh_kernel(EggRelaxedGroupCohArgs A) { rx_gather<true, true, false, false>(A.a, A.g, A.c, EggRxColliderFields{}, EggRxSurfaceFields{}); }
 // static colliders
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_col_kernel(EggRelaxedColArgs A) { rx_gather<false, false, true>(A.a, EggRxGroupFields{}, EggRxCohesionFields{}, A.d); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_col_kernel(EggRelaxedGroupColArgs A) { rx_gather<true, false, true>(A.a, A.g, EggRxCohesionFields{}, A.d); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_coh_col_kernel(EggRelaxedCohColArgs A) { rx_gather<false, true, true>(A.a, EggRxGroupFields{}, A.c, A.d); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_coh_col_kernel(EggRelaxedGroupCohColArgs A) { rx_gather<true, true, true>(A.a, A.g, A.c, A.d); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_col_kernel(EggRelaxedColArgs A) { rx_gather<false, false, true, false>(A.a, EggRxGroupFields{}, EggRxCohesionFields{}, A.d, EggRxSurfaceFields{}); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_col_kernel(EggRelaxedGroupColArgs A) { rx_gather<true, false, true, false>(A.a, A.g, EggRxCohesionFields{}, A.d, EggRxSurfaceFields{}); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_coh_col_kernel(EggRelaxedCohColArgs A) { rx_gather<false, true, true, false>(A.a, EggRxGroupFields{}, A.c, A.d, EggRxSurfaceFields{}); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_coh_col_kernel(EggRelaxedGroupCohColArgs A) { rx_gather<true, true, true, false>(A.a, A.g, A.c, A.d, EggRxSurfaceFields{}); }
+
+// collider surfaces
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_col_srf_kernel(EggRelaxedColSrfArgs A) { rx_gather<false, false, true, true>(A.a, EggRxGroupFields{}, EggRxCohesionFields{}, A.d, A.s); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_col_srf_kernel(EggRelaxedGroupColSrfArgs A) { rx_gather<true, false, true, true>(A.a, A.g, EggRxCohesionFields{}, A.d, A.s); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_coh_col_srf_kernel(EggRelaxedCohColSrfArgs A) { rx_gather<false, true, true, true>(A.a, EggRxGroupFields{}, A.c, A.d, A.s); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_coh_col_srf_kernel(EggRelaxedGroupCohColSrfArgs A) { rx_gather<true, true, true, true>(A.a, A.g, A.c, A.d, A.s); }
 
 // ---- viscosity ----
 

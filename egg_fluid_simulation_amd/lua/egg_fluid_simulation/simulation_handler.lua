@@ -81,6 +81,10 @@ int egg_get_forces(const egg_handle *h, int32_t cap, egg_force *f, int32_t *n);
 int egg_set_viscosity(egg_handle *h, const double c[2]);
 int egg_get_viscosity(const egg_handle *h, double c[2]);
 int egg_get_viscosity_pairs(egg_handle *h, int64_t pairs[2]);
+typedef struct { double friction; double vx, vy; } egg_collider_surface;
+int egg_set_collider_surfaces(egg_handle *h, int32_t n, const egg_collider_surface *s);
+int egg_get_collider_surfaces(const egg_handle *h, int32_t cap, egg_collider_surface *s, int32_t *n);
+int egg_get_collider_grips(egg_handle *h, int64_t grips[2]);
 typedef struct egg_group egg_group;
 int egg_group_set_solver_order(egg_group *g, int32_t order, double relaxation);
 int egg_group_set_cohesion(egg_group *g, int32_t mode);
@@ -460,6 +464,44 @@ function SimulationHandler:collider_hits()
     local hits = ffi.new("int64_t[2]")
     self:_check(lib.egg_get_collider_hits(self._h, hits))
     return tonumber(hits[0]), tonumber(hits[1])
+end
+
+-- Not in the reference: collider surfaces (egg_set_collider_surfaces in include/eggsim.h; DESIGN.md section 2.7,
+-- "Collider surfaces").
+
+local _max_colliders = 64  -- EGG_MAX_COLLIDERS
+
+--- one surface per collider of the current list: `false` for the default, a number `mu` (Coulomb friction, >= 0) or
+--- `{ mu, vx, vy }` with the surface's velocity in px/s.  `{}` resets every surface to the default, and so does set_colliders.
+function SimulationHandler:set_collider_surfaces(surfaces)
+    local n = #surfaces
+    local arr = ffi.new("egg_collider_surface[?]", math.max(n, 1))
+    for k = 1, n do  -- (not ipairs: a nil hole must not end the walk short of n)
+        local s = surfaces[k]
+        if s == false then s = { 0, 0, 0 } elseif type(s) == "number" then s = { s, 0, 0 } end
+        if type(s) ~= "table" or #s ~= 3 then
+            log.error("In SimulationHandler.set_collider_surfaces: surface " .. k .. ": expected false, mu or { mu, vx, vy }")
+            return
+        end
+        arr[k - 1].friction, arr[k - 1].vx, arr[k - 1].vy = s[1], s[2], s[3]
+    end
+    self:_check(lib.egg_set_collider_surfaces(self._h, n, arr))
+end
+
+--- the surfaces as stored, one `{ mu, vx, vy }` per collider (defaults included)
+function SimulationHandler:get_collider_surfaces()
+    local arr, n = ffi.new("egg_collider_surface[?]", _max_colliders), ffi.new("int32_t[1]")
+    if self:_check(lib.egg_get_collider_surfaces(self._h, _max_colliders, arr, n)) ~= 0 then return {} end
+    local out = {}
+    for k = 0, n[0] - 1 do out[k + 1] = { arr[k].friction, arr[k].vx, arr[k].vy } end
+    return out
+end
+
+--- white, yolk: friction applications (stick or slide) in the passes of committed steps
+function SimulationHandler:collider_grips()
+    local grips = ffi.new("int64_t[2]")
+    self:_check(lib.egg_get_collider_grips(self._h, grips))
+    return tonumber(grips[0]), tonumber(grips[1])
 end
 
 -- Not in the reference, which has no forces as it has no boundary: force fields of the relaxed step (egg_set_forces in

@@ -621,6 +621,20 @@ class ShardedSimulationHandler(_HandlerSurface):
         self.dist.all_reduce(tot, op=self.dist.ReduceOp.SUM)
         return [int(v) for v in tot.tolist()]
 
+    def set_collider_surfaces(self, surfaces):
+        """SimulationHandler.set_collider_surfaces on every rank alike (the same call on every rank).  Nothing new travels:
+        every rank applies friction to the particles it owns, from their own start-of-sub-step positions."""
+        self.local.set_collider_surfaces(surfaces)
+
+    def get_collider_surfaces(self):
+        return self.local.get_collider_surfaces()
+
+    def collider_grips(self):
+        """SimulationHandler.collider_grips summed over the ranks (a collective: every rank calls it)"""
+        tot = self.torch.tensor(self.local.collider_grips(), dtype=self.torch.int64, device=self.device)
+        self.dist.all_reduce(tot, op=self.dist.ReduceOp.SUM)
+        return [int(v) for v in tot.tolist()]
+
     def set_forces(self, forces):
         """SimulationHandler.set_forces on every rank alike (the same call on every rank; relaxed order only).  Nothing
         new travels: every rank accelerates the particles it owns."""

@@ -161,6 +161,51 @@ class _HandlerSurface:
         self._check(self._c("get_collider_hits")(hits))
         return list(hits)
 
+    # ------------------------------------------------ collider surfaces (egg_set_collider_surfaces)
+    @staticmethod
+    def _c_surfaces(surfaces):
+        """a list with one element per collider -- None (the default surface), a number mu, or (mu, vx, vy) -- as an
+        egg_collider_surface array; the shape is checked here, the values by the library"""
+        surfaces = list(surfaces)
+        arr = (_ffi.EggColliderSurface * max(len(surfaces), 1))()
+        for k, sf in enumerate(surfaces):
+            if sf is None:
+                sf = (0.0, 0.0, 0.0)
+            elif isinstance(sf, (int, float)):
+                sf = (sf, 0.0, 0.0)
+            try:
+                sf = tuple(float(v) for v in sf)
+            except (TypeError, ValueError):
+                raise EggError("collider surface %d: expected None, a number mu or (mu, vx, vy), not %r" % (k, sf)) from None
+            if len(sf) != 3:
+                raise EggError("collider surface %d: expected None, a number mu or (mu, vx, vy), not %r" % (k, sf))
+            arr[k].friction, arr[k].vx, arr[k].vy = sf
+        return len(surfaces), arr
+
+    def set_collider_surfaces(self, surfaces):
+        """One surface per collider of the current list ("Collider surfaces"): `None` for the default,
+        a number `mu` (Coulomb friction, >= 0), or `(mu, vx, vy)` with the surface's velocity in px/s.  Right after a collider
+        with mu > 0 has projected a particle, the tangential part of the particle's displacement over the sub-step, relative
+        to the surface, is removed up to mu times the depth just corrected: a floor holds what lies on it, a moving surface
+        drags it.  `[]` resets every surface to the default, and so does set_colliders.  Raises EggError (nothing changes)
+        for a length that is not the collider count, a friction that is negative or not finite, a velocity that is not
+        finite."""
+        n, arr = self._c_surfaces(surfaces)
+        self._check(self._c("set_collider_surfaces")(n, arr))
+
+    def get_collider_surfaces(self):
+        """the surfaces as stored, one `(mu, vx, vy)` per collider (defaults included)"""
+        arr = (_ffi.EggColliderSurface * _ffi.MAX_COLLIDERS)()
+        n = C.c_int32()
+        self._check(self._c("get_collider_surfaces")(_ffi.MAX_COLLIDERS, arr, C.byref(n)))
+        return [(sf.friction, sf.vx, sf.vy) for sf in arr[:n.value]]
+
+    def collider_grips(self):
+        """[white, yolk]: friction applications (stick or slide) in the passes of committed steps, since creation"""
+        grips = (C.c_int64 * 2)()
+        self._check(self._c("get_collider_grips")(grips))
+        return list(grips)
+
     # ------------------------------------------------ force fields (egg_set_forces, DESIGN.md section 2.7)
     @staticmethod
     def _c_forces(forces):

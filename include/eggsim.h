@@ -417,6 +417,43 @@ int egg_get_colliders(const egg_handle *h, int32_t cap, egg_collider *c, int32_t
  * steps count: a step that fails or is discarded adds nothing. */
 int egg_get_collider_hits(egg_handle *h, int64_t hits[2]);
 
+/* ---- collider surfaces: Coulomb friction and surface velocity ("Collider surfaces") ----
+ * Every collider of the list may carry a SURFACE: a friction coefficient mu >= 0 and a surface velocity (vx, vy) in px/s.
+ * The default surface is all zeros, and a list whose surfaces are all default behaves exactly as one without surfaces.
+ * Step 5c sits inside the collider loop: it applies to collider k when its mask covers the type, its condition held in
+ * this pass (a hit) and mu_k > 0.0, right after that collider's projection has been written into (x, y) and before the
+ * next collider sees the result.  prev is the particle's position at the start of the sub-step, h the sub-step
+ * (delta / n_sub_steps, at least eps); n and pen are the projection's own values:
+ *   HALF_PLANE        n = (nx, ny) as stored, pen = -s
+ *   DISC and SEGMENT  n = the unit vector the projection used (the coincident pair's at d2 == 0), pen = m - d (d = 0 at
+ *                     the centre; a segment has m = 0 + r)
+ *   CONTAINER         n = (dx / d, dy / d), pen = d - m
+ * FP64 in exactly this order, no contraction, sqrt and / correctly rounded; every comparison is false for a NaN:
+ *   ex = (x - prev.x) - h vx, ey = (y - prev.y) - h vy, dn = ex nx + ey ny, tx = ex - dn nx, ty = ey - dn ny,
+ *   tl2 = tx tx + ty ty; !(tl2 > 0.0): nothing happens and nothing is counted; otherwise tl = sqrt(tl2), lim = mu pen;
+ *   tl <= lim (stick): x = x - tx, y = y - ty; else (slide): f = lim / tl, x = x - tx f, y = y - ty f.
+ * Either branch is one GRIP.  The tangential part of the sub-step's displacement relative to the surface is removed up to
+ * mu times the depth the collider has just corrected; velocities follow from the post-solve, so a gripped particle loses
+ * tangential velocity and a surface with a velocity drags what touches it (a conveyor; a pan the caller moves by setting
+ * the list again).  The viscosity pass rewrites prev only after the sub-step's last collision pass: friction reads the
+ * un-smoothed start of the sub-step.  The tangential move leaves a half-plane's constraint exact and a circle's by second
+ * order, which the next pass projects again.
+ * egg_set_collider_surfaces: n must equal the current collider count, or 0 (every surface back to default).  Everything is
+ * checked before anything changes: EGG_ERR_INVALID_ARGUMENT, with the collider's index in the message, for an n that does
+ * not match, a friction that is negative or not finite, a velocity that is not finite.  egg_set_colliders resets every
+ * surface to default (the indices no longer mean anything).  A -0.0 is stored as +0.0.  Refused while a step is in flight.  The records go to the
+ * device when they are set, never per step; while no friction is > 0 -- a velocity alone does nothing -- a step launches
+ * exactly what it launches without surfaces. */
+typedef struct {
+    double friction; /* mu >= 0 */
+    double vx, vy;   /* px/s */
+} egg_collider_surface; /* 24 bytes */
+int egg_set_collider_surfaces(egg_handle *h, int32_t n, const egg_collider_surface *s);
+/* the surfaces as stored, one per collider (defaults included): the count in *n, min(*n, cap) records copied */
+int egg_get_collider_surfaces(const egg_handle *h, int32_t cap, egg_collider_surface *s, int32_t *n);
+/* grips per type since the handle was created, over committed steps only: a step that fails or is discarded adds nothing */
+int egg_get_collider_grips(egg_handle *h, int64_t grips[2]);
+
 /* ---- force fields (not in the reference, which has no forces as it has no boundary; DESIGN.md section 2.7, "Forces") ----
  * A handle holds an ordered list of at most EGG_MAX_FORCES fields.  The values are accelerations in px/s^2 and do not depend
  * on mass.  In every sub-step of a RELAXED step, for every particle of a type, the force step runs before the pre-solve,
@@ -529,6 +566,11 @@ int egg_group_set_cohesion(egg_group *g, int32_t mode);
 int egg_group_set_colliders(egg_group *g, int32_t n, const egg_collider *c);
 int egg_group_get_colliders(const egg_group *g, int32_t cap, egg_collider *c, int32_t *n);
 int egg_group_get_collider_hits(egg_group *g, int64_t hits[2]);
+/* egg_set_collider_surfaces for every handle of the group alike, with its rules; a refused call changes no handle, and
+ * egg_group_set_colliders resets the surfaces.  A step is refused while the handles differ.  The grips are summed. */
+int egg_group_set_collider_surfaces(egg_group *g, int32_t n, const egg_collider_surface *s);
+int egg_group_get_collider_surfaces(const egg_group *g, int32_t cap, egg_collider_surface *s, int32_t *n);
+int egg_group_get_collider_grips(egg_group *g, int64_t grips[2]);
 /* egg_set_forces for every handle of the group alike, with its rules (relaxed order only; back to exact order only with
  * an empty list); a refused list changes no handle.  Every device accelerates only the particles it owns: the results
  * equal one handle's.  A group whose handles differ in their lists refuses to step. */
