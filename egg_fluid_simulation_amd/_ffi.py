@@ -110,8 +110,14 @@ class EggColliderSurface(C.Structure):  # egg_collider_surface: friction and sur
 
 MAX_COLLIDERS = 64  # EGG_MAX_COLLIDERS
 COLLIDER_HALF_PLANE, COLLIDER_DISC, COLLIDER_CONTAINER, COLLIDER_SEGMENT = 0, 1, 2, 3
-COLLIDER_KINDS = ("half_plane", "disc", "container", "segment")  # by EGG_COLLIDER_* value
+COLLIDER_KINDS = ("half_plane", "disc", "container", "segment")  # by EGG_COLLIDER_* value: the kinds 0 .. 3
 COLLIDER_PARAMS = (("nx", "ny", "off"), ("cx", "cy", "R"), ("cx", "cy", "R"), ("x0", "y0", "x1", "y1"))
+COLLIDER_WALL = 5  # EGG_COLLIDER_WALL: a segment that sweeps the sub-step's path (4 is not a kind and stays refused)
+# every kind, the wall included: name -> EGG_COLLIDER_* value, value -> name, value -> parameter names
+COLLIDER_CODES = dict({n: i for i, n in enumerate(COLLIDER_KINDS)}, wall=COLLIDER_WALL)
+COLLIDER_NAMES = {v: n for n, v in COLLIDER_CODES.items()}
+COLLIDER_PARAM_NAMES = dict(enumerate(COLLIDER_PARAMS))
+COLLIDER_PARAM_NAMES[COLLIDER_WALL] = COLLIDER_PARAMS[COLLIDER_SEGMENT]
 COLLIDER_TYPES = {"white": 1, "yolk": 2, "both": 3}  # type_mask
 
 

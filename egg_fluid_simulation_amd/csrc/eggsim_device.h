@@ -328,6 +328,7 @@ struct EggRelaxedGroupCohArgs {
 #define EGG_RX_COLLIDER_DISC 1
 #define EGG_RX_COLLIDER_CONTAINER 2
 #define EGG_RX_COLLIDER_SEGMENT 3
+#define EGG_RX_COLLIDER_WALL 5  // (4 is not a kind) a segment that sweeps the sub-step's path (the *_col_wall instantiations only)
 struct EggCollider {
     int32_t kind, type_mask;
     double p[4];
@@ -362,7 +363,8 @@ struct EggRelaxedGroupCohColArgs {
 // Collider surfaces (egg_set_collider_surfaces, DESIGN.md section 2.7, "Collider surfaces"): the surface instantiations of
 // the gather kernel (egg_rx_gather*_col_srf_kernel) take these besides the collider fields.  The records are parallel to
 // the collider list, in a small device buffer written when they are set; a record has the layout of the ABI's
-// egg_collider_surface (24 bytes).
+// egg_collider_surface (24 bytes).  The wall instantiations (egg_rx_gather*_col_wall_kernel, "Walls") take the same
+// arguments: while the list holds a wall the records exist for every collider, defaults included.
 struct EggSurface {
     double friction, vx, vy;
 };

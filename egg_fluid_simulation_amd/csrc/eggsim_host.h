@@ -90,6 +90,10 @@ extern "C" __global__ void egg_rx_gather_col_srf_kernel(EggRelaxedColSrfArgs A);
 extern "C" __global__ void egg_rx_gather_group_col_srf_kernel(EggRelaxedGroupColSrfArgs A);
 extern "C" __global__ void egg_rx_gather_coh_col_srf_kernel(EggRelaxedCohColSrfArgs A);
 extern "C" __global__ void egg_rx_gather_group_coh_col_srf_kernel(EggRelaxedGroupCohColSrfArgs A);
+extern "C" __global__ void egg_rx_gather_col_wall_kernel(EggRelaxedColSrfArgs A);
+extern "C" __global__ void egg_rx_gather_group_col_wall_kernel(EggRelaxedGroupColSrfArgs A);
+extern "C" __global__ void egg_rx_gather_coh_col_wall_kernel(EggRelaxedCohColSrfArgs A);
+extern "C" __global__ void egg_rx_gather_group_coh_col_wall_kernel(EggRelaxedGroupCohColSrfArgs A);
 extern "C" __global__ void egg_rx_begin_frc_kernel(EggRelaxedFrcArgs A);
 extern "C" __global__ void egg_rx_mid_frc_kernel(EggRelaxedFrcArgs A);
 extern "C" __global__ void egg_rx_begin_group_frc_kernel(EggRelaxedGroupFrcArgs A);
@@ -415,6 +419,8 @@ struct egg_handle {
     // device (written when the list is set, never per step), and the hits of committed steps per type
     std::vector<egg_collider> colliders;
     DevBuf<EggCollider> d_colliders;
+    bool colliders_wall = false;  // the list holds an EGG_COLLIDER_WALL: a step launches the wall instantiations, which
+                                  // read the surface records -- d_surfaces then holds one per collider, defaults included
     int64_t collider_hits[2] = {0, 0};
     // collider surfaces (egg_set_collider_surfaces): empty = every surface is the default, else one record per collider;
     // the copy on the device (written when they are set, never per step); whether any friction > 0 -- only then does a
@@ -574,7 +580,8 @@ constexpr char kRelaxedBadCellText[] = "relaxed order: a position is NaN or its 
 // records sent to each of them.  With effective cohesion one more word: the pairs that cohered.  With colliders one
 // more: their hits.  With viscosity the halo words cover V = S more passes, the viscosity pass of sub-step `sub` being
 // halo pass P + sub, and one more word, the last, holds the pairs the viscosity passes counted.  V = 0 is the layout
-// without.  With collider surfaces of which one has friction one more word behind all of these: the grips.
+// without.  With collider surfaces of which one has friction, or with a wall in the list, one more word behind all of
+// these: the grips.
 struct RelaxedLayout {
     size_t P = 0, nq = 0;
     bool halo = false;  // ghosts of other handles' particles take part: the group instantiations of the kernels
@@ -582,7 +589,8 @@ struct RelaxedLayout {
     bool colliders = false;  // (set by prepare_type: the handle's collider list is not empty)
     bool forces = false;     // (set by prepare_type: the handle's force list is not empty; no status word of its own)
     size_t V = 0;            // (set by prepare_type: the sub-steps, when the type's viscosity coefficient is not zero)
-    bool surfaces = false;   // (set by prepare_type: a collider surface of the handle has friction > 0)
+    bool surfaces = false;   // (set by prepare_type: a collider surface of the handle has friction > 0, or walls)
+    bool walls = false;      // (set by prepare_type: the handle's list holds a wall; implies surfaces)
     size_t H() const { return P + V; }                                        // passes with a halo
     size_t box(size_t p) const { return 1 + P + 4 * p; }                      // 4 words
     size_t ghosts(size_t p) const { return 1 + P + 4 * H() + p; }

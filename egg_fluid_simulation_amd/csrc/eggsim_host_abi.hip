@@ -986,19 +986,21 @@ int egg_set_colliders(egg_handle *h, int32_t n, const egg_collider *c) {
     static_assert(sizeof(egg_collider) == 40 && sizeof(EggCollider) == sizeof(egg_collider), "a collider record is 40 bytes");
     static_assert(EGG_MAX_COLLIDERS == EGG_RX_MAX_COLLIDERS && EGG_COLLIDER_HALF_PLANE == EGG_RX_COLLIDER_HALF_PLANE &&
                       EGG_COLLIDER_DISC == EGG_RX_COLLIDER_DISC && EGG_COLLIDER_CONTAINER == EGG_RX_COLLIDER_CONTAINER &&
-                      EGG_COLLIDER_SEGMENT == EGG_RX_COLLIDER_SEGMENT,
+                      EGG_COLLIDER_SEGMENT == EGG_RX_COLLIDER_SEGMENT && EGG_COLLIDER_WALL == EGG_RX_COLLIDER_WALL,
                   "the kernel's collider constants are the ABI's");
     std::vector<egg_collider> list((size_t)n);
+    bool wall = false;
     for (int32_t k = 0; k < n; ++k) {
         egg_collider &o = list[(size_t)k];
         o = c[k];
-        static const char *const names[4] = {"half-plane", "disc", "container", "segment"};
-        if (o.kind < EGG_COLLIDER_HALF_PLANE || o.kind > EGG_COLLIDER_SEGMENT)
+        static const char *const names[6] = {"half-plane", "disc", "container", "segment", "", "wall"};  // (4 is not a kind)
+        if ((o.kind < EGG_COLLIDER_HALF_PLANE || o.kind > EGG_COLLIDER_SEGMENT) && o.kind != EGG_COLLIDER_WALL)
             return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_colliders: collider %d: unknown kind %d", (int)k, (int)o.kind);
         if (o.type_mask < 1 || o.type_mask > 3)
             return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_colliders: collider %d: type_mask %d (bit 0 white, bit 1 yolk, never 0)", (int)k,
                         (int)o.type_mask);
-        const int used = o.kind == EGG_COLLIDER_SEGMENT ? 4 : 3;
+        const int used = o.kind == EGG_COLLIDER_SEGMENT || o.kind == EGG_COLLIDER_WALL ? 4 : 3;
+        wall |= o.kind == EGG_COLLIDER_WALL;
         for (int q = 0; q < 4; ++q) {
             if (q >= used) o.p[q] = 0.0;  // (not a parameter of the kind)
             if (!std::isfinite(o.p[q]))
@@ -1021,9 +1023,15 @@ int egg_set_colliders(egg_handle *h, int32_t n, const egg_collider *c) {
     if (n > 0) {  // (no step is running: every step ends with its streams waited for)
         HIP_TRY(h, hipSetDevice(h->device));
         HIP_TRY(h, h->d_colliders.reserve(EGG_MAX_COLLIDERS, false, nullptr));
+        if (wall) {  // the wall instantiations read a surface record per collider: the defaults, until some are set
+            const std::vector<egg_collider_surface> zeros((size_t)n, egg_collider_surface{0.0, 0.0, 0.0});
+            HIP_TRY(h, h->d_surfaces.reserve(EGG_MAX_COLLIDERS, false, nullptr));
+            HIP_TRY(h, hipMemcpy(h->d_surfaces.p, zeros.data(), (size_t)n * sizeof(egg_collider_surface), hipMemcpyHostToDevice));
+        }
         HIP_TRY(h, hipMemcpy(h->d_colliders.p, list.data(), (size_t)n * sizeof(egg_collider), hipMemcpyHostToDevice));
     }
     h->colliders.swap(list);
+    h->colliders_wall = wall;
     h->surfaces.clear();  // (the indices no longer mean anything: every surface is the default again)
     h->surfaces_grip = false;
     return EGG_OK;
@@ -1067,6 +1075,11 @@ int egg_set_collider_surfaces(egg_handle *h, int32_t n, const egg_collider_surfa
         HIP_TRY(h, hipSetDevice(h->device));
         HIP_TRY(h, h->d_surfaces.reserve(EGG_MAX_COLLIDERS, false, nullptr));
         HIP_TRY(h, hipMemcpy(h->d_surfaces.p, list.data(), (size_t)n * sizeof(egg_collider_surface), hipMemcpyHostToDevice));
+    } else if (h->colliders_wall) {  // (the wall instantiations go on reading the records: the defaults again)
+        const std::vector<egg_collider_surface> zeros(h->colliders.size(), egg_collider_surface{0.0, 0.0, 0.0});
+        HIP_TRY(h, hipSetDevice(h->device));
+        HIP_TRY(h, h->d_surfaces.reserve(EGG_MAX_COLLIDERS, false, nullptr));
+        HIP_TRY(h, hipMemcpy(h->d_surfaces.p, zeros.data(), zeros.size() * sizeof(egg_collider_surface), hipMemcpyHostToDevice));
     }
     h->surfaces.swap(list);
     h->surfaces_grip = grip;

@@ -19,6 +19,9 @@
 // With collider surfaces (egg_set_collider_surfaces, RelaxedLayout::surfaces) of which at least one has friction > 0
 // launch_pass picks the surface twin of the collider instantiation and RelaxedStep::srf carries the records; while every
 // friction is zero -- a surface velocity alone does nothing -- a step launches what it launches without surfaces.
+// While the list holds a wall (EGG_COLLIDER_WALL, RelaxedLayout::walls) launch_pass picks the wall twin of the surface
+// instantiation, whether or not a friction is set: RelaxedStep::srf is then always filled, and the handle's records on the
+// device hold one per collider, defaults included.  A list without a wall launches what it launched.
 // With force fields (egg_set_forces, RelaxedLayout::forces) launch_substep picks the force instantiation of the begin / mid
 // kernel and RelaxedStep::frc carries the handle's list; with an empty list a step launches what it always launched.
 // With viscosity (egg_set_viscosity, RelaxedLayout::V) every sub-step of a type whose coefficient is not zero ends with
@@ -172,7 +175,8 @@ int prepare_type(RelaxedStep &st, int C, size_t ghosts, const RelaxedLayout &L, 
     st.L = L;
     st.L.cohesion = h->opt_cohesion == EGG_COHESION_EFFECTIVE;
     st.L.colliders = !h->colliders.empty();
-    st.L.surfaces = st.L.colliders && h->surfaces_grip;
+    st.L.walls = st.L.colliders && h->colliders_wall;
+    st.L.surfaces = st.L.colliders && (h->surfaces_grip || st.L.walls);
     st.L.forces = !h->forces.empty();
     st.L.V = h->viscosity[st.w] > 0.0 ? L.P / (size_t)C : 0;
     st.C = C;
@@ -299,7 +303,10 @@ int launch_pass(RelaxedStep &st, int p) {
         if (st.L.cohesion) {
             const EggRelaxedGroupCohArgs k{a.a, a.g, st.coh};
             hipLaunchKernelGGL(egg_rx_rank_group_coh_kernel, grid, block, 0, s.stream, k);
-            if (st.L.surfaces)
+            if (st.L.walls)
+                hipLaunchKernelGGL(egg_rx_gather_group_coh_col_wall_kernel, grid, block, 0, s.stream,
+                                   EggRelaxedGroupCohColSrfArgs{a.a, a.g, st.coh, st.col, st.srf});
+            else if (st.L.surfaces)
                 hipLaunchKernelGGL(egg_rx_gather_group_coh_col_srf_kernel, grid, block, 0, s.stream,
                                    EggRelaxedGroupCohColSrfArgs{a.a, a.g, st.coh, st.col, st.srf});
             else if (st.L.colliders)
@@ -308,7 +315,10 @@ int launch_pass(RelaxedStep &st, int p) {
                 hipLaunchKernelGGL(egg_rx_gather_group_coh_kernel, grid, block, 0, s.stream, k);
         } else {
             hipLaunchKernelGGL(egg_rx_rank_group_kernel, grid, block, 0, s.stream, a);
-            if (st.L.surfaces)
+            if (st.L.walls)
+                hipLaunchKernelGGL(egg_rx_gather_group_col_wall_kernel, grid, block, 0, s.stream,
+                                   EggRelaxedGroupColSrfArgs{a.a, a.g, st.col, st.srf});
+            else if (st.L.surfaces)
                 hipLaunchKernelGGL(egg_rx_gather_group_col_srf_kernel, grid, block, 0, s.stream,
                                    EggRelaxedGroupColSrfArgs{a.a, a.g, st.col, st.srf});
             else if (st.L.colliders)
@@ -321,7 +331,10 @@ int launch_pass(RelaxedStep &st, int p) {
         if (st.L.cohesion) {
             const EggRelaxedCohArgs k{a.a, st.coh};
             hipLaunchKernelGGL(egg_rx_rank_coh_kernel, grid, block, 0, s.stream, k);
-            if (st.L.surfaces)
+            if (st.L.walls)
+                hipLaunchKernelGGL(egg_rx_gather_coh_col_wall_kernel, grid, block, 0, s.stream,
+                                   EggRelaxedCohColSrfArgs{a.a, st.coh, st.col, st.srf});
+            else if (st.L.surfaces)
                 hipLaunchKernelGGL(egg_rx_gather_coh_col_srf_kernel, grid, block, 0, s.stream,
                                    EggRelaxedCohColSrfArgs{a.a, st.coh, st.col, st.srf});
             else if (st.L.colliders)
@@ -330,7 +343,9 @@ int launch_pass(RelaxedStep &st, int p) {
                 hipLaunchKernelGGL(egg_rx_gather_coh_kernel, grid, block, 0, s.stream, k);
         } else {
             hipLaunchKernelGGL(egg_rx_rank_kernel, grid, block, 0, s.stream, a.a);
-            if (st.L.surfaces)
+            if (st.L.walls)
+                hipLaunchKernelGGL(egg_rx_gather_col_wall_kernel, grid, block, 0, s.stream, EggRelaxedColSrfArgs{a.a, st.col, st.srf});
+            else if (st.L.surfaces)
                 hipLaunchKernelGGL(egg_rx_gather_col_srf_kernel, grid, block, 0, s.stream, EggRelaxedColSrfArgs{a.a, st.col, st.srf});
             else if (st.L.colliders)
                 hipLaunchKernelGGL(egg_rx_gather_col_kernel, grid, block, 0, s.stream, EggRelaxedColArgs{a.a, st.col});

@@ -37,6 +37,11 @@
 // tangential part of the particle's displacement over the sub-step, relative to the surface's velocity, up to friction
 // times the depth the projection has just corrected.  The S = false instantiations are the kernels as they were.
 //
+// While the list holds a wall (EGG_COLLIDER_WALL; DESIGN.md section 2.7, "Walls") the surface twins run as their wall twins
+// (D, S and W = true, egg_rx_gather*_col_wall_kernel): a wall is a segment that also sweeps the particle's path over the
+// sub-step, prev[me] to the position now, and puts a particle that has crossed it back on the side it started from.  The
+// W = false instantiations are the kernels as they were.
+//
 // With force fields (egg_set_forces; DESIGN.md section 2.7, "Forces") the kernels that begin a sub-step run in their force
 // instantiations (F = true, egg_rx_begin*_frc_kernel, egg_rx_mid*_frc_kernel): the fields of the handle's list whose mask
 // covers the type accelerate the velocity the pre-solve is about to damp.  The F = false instantiations are the kernels
@@ -133,7 +138,10 @@ __device__ __forceinline__ int rx_grip(const EggSurface &sf, double h, double2 p
 // position stays.  Returns the colliders that moved the particle.
 // S: step 5c, the surface of a collider that has just moved the particle (rx_grip); pv is the particle's position at the
 // start of the sub-step, grips counts the applications.  The surface record is read like the collider record.
-template <bool S>
+// W (with S only): the list may hold walls.  A wall is a segment whose first question is whether the straight path from pv
+// to the position now meets it: then the particle goes back to its radius from the nearest point, on pv's side.  pv does
+// not change inside a sub-step, so every pass sweeps from the same start.
+template <bool S, bool W>
 __device__ __forceinline__ int rx_collide(const EggRxColliderFields &Co, const EggRxSurfaceFields &Su, int i, double r,
                                           double2 pv, double2 &out, int &grips) {
     int hits = 0;
@@ -154,15 +162,28 @@ __device__ __forceinline__ int rx_collide(const EggRxColliderFields &Co, const E
             continue;
         }
         double cx = col.p[0], cy = col.p[1], R = col.p[2];
-        if (col.kind == EGG_RX_COLLIDER_SEGMENT) {  // p = (x0, y0, x1, y1): a disc of radius 0 at the nearest point
+        bool caught = false;         // (W only: the particle's path over the sub-step has crossed the wall)
+        double a0 = 0.0, l2 = 0.0;   // (W only, read when caught: the side of pv, the wall's squared length)
+        if (col.kind == EGG_RX_COLLIDER_SEGMENT || (W && col.kind == EGG_RX_COLLIDER_WALL)) {
+            // p = (x0, y0, x1, y1): a disc of radius 0 at the nearest point
             const double ex = col.p[2] - col.p[0], ey = col.p[3] - col.p[1];
-            const double l2 = ex * ex + ey * ey;
+            l2 = ex * ex + ey * ey;
             double t = l2 == 0.0 ? 0.0 : ((x - col.p[0]) * ex + (y - col.p[1]) * ey) / l2;
             if (t < 0.0) t = 0.0;
             if (t > 1.0) t = 1.0;
             cx = col.p[0] + t * ex;
             cy = col.p[1] + t * ey;
             R = 0.0;
+            if (W && col.kind == EGG_RX_COLLIDER_WALL) {  // the sweep: which side the sub-step started on, which side now
+                a0 = ex * (pv.y - col.p[1]) - ey * (pv.x - col.p[0]);
+                const double a1 = ex * (y - col.p[1]) - ey * (x - col.p[0]);
+                if ((a0 > 0.0 && a1 <= 0.0) || (a0 < 0.0 && a1 >= 0.0)) {  // (a0 != 0, so l2 != 0)
+                    const double u = a0 / (a0 - a1);
+                    const double hx = pv.x + u * (x - pv.x), hy = pv.y + u * (y - pv.y);  // where the path meets the line
+                    const double tc = ((hx - col.p[0]) * ex + (hy - col.p[1]) * ey) / l2;
+                    caught = tc >= 0.0 && tc <= 1.0;  // ... and that is on the wall
+                }
+            }
         }
         const double dx = x - cx, dy = y - cy;
         const double d2 = dx * dx + dy * dy;
@@ -178,20 +199,29 @@ __device__ __forceinline__ int rx_collide(const EggRxColliderFields &Co, const E
             }
         } else {  // disc, p = (cx, cy, R): stays outside
             const double m = R + r;
-            if (d2 < m * m) {
+            if ((W && caught) || d2 < m * m) {
                 const double d = sqrt(d2);
-                double ux, uy;
-                if (d2 == 0.0) {
-                    ux = kRxDirX[i & 7];
-                    uy = kRxDirY[i & 7];
+                double ux, uy, pen;
+                if (W && caught) {  // back to its radius from the nearest point, along the unit normal towards pv's side
+                    const double l = sqrt(l2);
+                    const double ex = col.p[2] - col.p[0], ey = col.p[3] - col.p[1];
+                    ux = a0 > 0.0 ? (-ey) / l : ey / l;
+                    uy = a0 > 0.0 ? ex / l : (-ex) / l;
+                    pen = m + d;
                 } else {
-                    ux = dx / d;
-                    uy = dy / d;
+                    if (d2 == 0.0) {
+                        ux = kRxDirX[i & 7];
+                        uy = kRxDirY[i & 7];
+                    } else {
+                        ux = dx / d;
+                        uy = dy / d;
+                    }
+                    pen = m - d;
                 }
                 out.x = cx + ux * m;
                 out.y = cy + uy * m;
                 ++hits;
-                if (S) grips += rx_grip(sf, Su.sub_delta, pv, ux, uy, m - d, out);
+                if (S) grips += rx_grip(sf, Su.sub_delta, pv, ux, uy, pen, out);
             }
         }
     }
@@ -384,11 +414,13 @@ __device__ __forceinline__ void rx_rank(const EggRelaxedArgs &A, const EggRxGrou
 // writes when the pass is not the sub-step's last.  K: a pair that does not collide may cohere -- same tag, within reach
 // -- and then runs the collision correction's arithmetic with the cohesion compliance (one path for both kinds).  D: the
 // new position goes through the colliders before it is written (whether or not a pair fired).  S (with D only): a
-// collider's surface acts right after its projection (step 5c); prev[me] is read once, for that.
-template <bool G, bool K, bool D, bool S>
+// collider's surface acts right after its projection (step 5c); prev[me] is read once, for that.  W (with S only): the
+// list may hold walls, which sweep from the same prev[me].
+template <bool G, bool K, bool D, bool S, bool W>
 __device__ __forceinline__ void rx_gather(EggRelaxedArgs A, const EggRxGroupFields &X, const EggRxCohesionFields &Ch,
                                           const EggRxColliderFields &Co, const EggRxSurfaceFields &Su) {
     static_assert(D || !S, "surfaces belong to colliders");
+    static_assert(S || !W, "the wall instantiations are surface instantiations");
     const int t = (int)(blockIdx.x * 256 + threadIdx.x);
     int pairs = 0;
     int cohered = 0;  // (K only)
@@ -476,7 +508,7 @@ __device__ __forceinline__ void rx_gather(EggRelaxedArgs A, const EggRxGroupFiel
             out.x = p.x + (sx * A.omega) / (double)n_fired;
             out.y = p.y + (sy * A.omega) / (double)n_fired;
         }
-        if (D) hits = rx_collide<S>(Co, Su, i, wr.y, S ? A.prev[me] : make_double2(0.0, 0.0), out, grips);
+        if (D) hits = rx_collide<S, W>(Co, Su, i, wr.y, S ? A.prev[me] : make_double2(0.0, 0.0), out, grips);
         A.pos_next[me] = out;
         if (G) {
             local = true;
@@ -511,24 +543,30 @@ extern "C" __global__ void __launch_bounds__(256) egg_rx_scatter_kernel(EggRelax
 extern "C" __global__ void __launch_bounds__(256) egg_rx_scatter_group_kernel(EggRelaxedGroupArgs A) { rx_scatter<true>(A.a, A.g); }
 extern "C" __global__ void __launch_bounds__(256) egg_rx_rank_kernel(EggRelaxedArgs A) { rx_rank<false, false>(A, EggRxGroupFields{}, EggRxCohesionFields{}); }
 extern "C" __global__ void __launch_bounds__(256) egg_rx_rank_group_kernel(EggRelaxedGroupArgs A) { rx_rank<true, false>(A.a, A.g, EggRxCohesionFields{}); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_kernel(EggRelaxedArgs A) { rx_gather<false, false, false, false>(A, EggRxGroupFields{}, EggRxCohesionFields{}, EggRxColliderFields{}, EggRxSurfaceFields{}); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_kernel(EggRelaxedGroupArgs A) { rx_gather<true, false, false, false>(A.a, A.g, EggRxCohesionFields{}, EggRxColliderFields{}, EggRxSurfaceFields{}); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_kernel(EggRelaxedArgs A) { rx_gather<false, false, false, false, false>(A, EggRxGroupFields{}, EggRxCohesionFields{}, EggRxColliderFields{}, EggRxSurfaceFields{}); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_kernel(EggRelaxedGroupArgs A) { rx_gather<true, false, false, false, false>(A.a, A.g, EggRxCohesionFields{}, EggRxColliderFields{}, EggRxSurfaceFields{}); }
 // effective cohesion
 extern "C" __global__ void __launch_bounds__(256) egg_rx_rank_coh_kernel(EggRelaxedCohArgs A) { rx_rank<false, true>(A.a, EggRxGroupFields{}, A.c); }
 extern "C" __global__ void __launch_bounds__(256) egg_rx_rank_group_coh_kernel(EggRelaxedGroupCohArgs A) { rx_rank<true, true>(A.a, A.g, A.c); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_coh_kernel(EggRelaxedCohArgs A) { rx_gather<false, true, false, false>(A.a, EggRxGroupFields{}, A.c, EggRxColliderFields{}, EggRxSurfaceFields{}); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_coh_kernel(EggRelaxedGroupCohArgs A) { rx_gather<true, true, false, false>(A.a, A.g, A.c, EggRxColliderFields{}, EggRxSurfaceFields{}); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_coh_kernel(EggRelaxedCohArgs A) { rx_gather<false, true, false, false, false>(A.a, EggRxGroupFields{}, A.c, EggRxColliderFields{}, EggRxSurfaceFields{}); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_coh_kernel(EggRelaxedGroupCohArgs A) { rx_gather<true, true, false, false, false>(A.a, A.g, A.c, EggRxColliderFields{}, EggRxSurfaceFields{}); }
 // static colliders
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_col_kernel(EggRelaxedColArgs A) { rx_gather<false, false, true, false>(A.a, EggRxGroupFields{}, EggRxCohesionFields{}, A.d, EggRxSurfaceFields{}); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_col_kernel(EggRelaxedGroupColArgs A) { rx_gather<true, false, true, false>(A.a, A.g, EggRxCohesionFields{}, A.d, EggRxSurfaceFields{}); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_coh_col_kernel(EggRelaxedCohColArgs A) { rx_gather<false, true, true, false>(A.a, EggRxGroupFields{}, A.c, A.d, EggRxSurfaceFields{}); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_coh_col_kernel(EggRelaxedGroupCohColArgs A) { rx_gather<true, true, true, false>(A.a, A.g, A.c, A.d, EggRxSurfaceFields{}); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_col_kernel(EggRelaxedColArgs A) { rx_gather<false, false, true, false, false>(A.a, EggRxGroupFields{}, EggRxCohesionFields{}, A.d, EggRxSurfaceFields{}); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_col_kernel(EggRelaxedGroupColArgs A) { rx_gather<true, false, true, false, false>(A.a, A.g, EggRxCohesionFields{}, A.d, EggRxSurfaceFields{}); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_coh_col_kernel(EggRelaxedCohColArgs A) { rx_gather<false, true, true, false, false>(A.a, EggRxGroupFields{}, A.c, A.d, EggRxSurfaceFields{}); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_coh_col_kernel(EggRelaxedGroupCohColArgs A) { rx_gather<true, true, true, false, false>(A.a, A.g, A.c, A.d, EggRxSurfaceFields{}); }
 
 // collider surfaces
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_col_srf_kernel(EggRelaxedColSrfArgs A) { rx_gather<false, false, true, true>(A.a, EggRxGroupFields{}, EggRxCohesionFields{}, A.d, A.s); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_col_srf_kernel(EggRelaxedGroupColSrfArgs A) { rx_gather<true, false, true, true>(A.a, A.g, EggRxCohesionFields{}, A.d, A.s); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_coh_col_srf_kernel(EggRelaxedCohColSrfArgs A) { rx_gather<false, true, true, true>(A.a, EggRxGroupFields{}, A.c, A.d, A.s); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_coh_col_srf_kernel(EggRelaxedGroupCohColSrfArgs A) { rx_gather<true, true, true, true>(A.a, A.g, A.c, A.d, A.s); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_col_srf_kernel(EggRelaxedColSrfArgs A) { rx_gather<false, false, true, true, false>(A.a, EggRxGroupFields{}, EggRxCohesionFields{}, A.d, A.s); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_col_srf_kernel(EggRelaxedGroupColSrfArgs A) { rx_gather<true, false, true, true, false>(A.a, A.g, EggRxCohesionFields{}, A.d, A.s); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_coh_col_srf_kernel(EggRelaxedCohColSrfArgs A) { rx_gather<false, true, true, true, false>(A.a, EggRxGroupFields{}, A.c, A.d, A.s); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_coh_col_srf_kernel(EggRelaxedGroupCohColSrfArgs A) { rx_gather<true, true, true, true, false>(A.a, A.g, A.c, A.d, A.s); }
+
+// walls (the arguments are the surface instantiations')
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_col_wall_kernel(EggRelaxedColSrfArgs A) { rx_gather<false, false, true, true, true>(A.a, EggRxGroupFields{}, EggRxCohesionFields{}, A.d, A.s); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_col_wall_kernel(EggRelaxedGroupColSrfArgs A) { rx_gather<true, false, true, true, true>(A.a, A.g, EggRxCohesionFields{}, A.d, A.s); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_coh_col_wall_kernel(EggRelaxedCohColSrfArgs A) { rx_gather<false, true, true, true, true>(A.a, EggRxGroupFields{}, A.c, A.d, A.s); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_coh_col_wall_kernel(EggRelaxedGroupCohColSrfArgs A) { rx_gather<true, true, true, true, true>(A.a, A.g, A.c, A.d, A.s); }
 
 // ---- viscosity ----
 

@@ -421,14 +421,15 @@ function SimulationHandler:get_cohesion() return self._cohesion or "reference" e
 
 -- Not in the reference, which has no boundary of any kind: static colliders of the relaxed pass (egg_set_colliders in
 -- include/eggsim.h; DESIGN.md section 2.7, "Colliders").  Relaxed order only.
-local _collider_kinds = { half_plane = 0, disc = 1, container = 2, segment = 3 }
-local _collider_names = { [0] = "half_plane", "disc", "container", "segment" }
-local _collider_n_params = { [0] = 3, 3, 3, 4 }
+local _collider_kinds = { half_plane = 0, disc = 1, container = 2, segment = 3, wall = 5 }  -- (4 is not a kind)
+local _collider_names = { [0] = "half_plane", "disc", "container", "segment", [5] = "wall" }
+local _collider_n_params = { [0] = 3, 3, 3, 4, [5] = 4 }
 local _collider_types = { white = 1, yolk = 2, both = 3 }
 local _collider_type_names = { "white", "yolk", "both" }
 
 --- the ordered list of at most 64 colliders, each `{ "half_plane", nx, ny, off }`, `{ "disc", cx, cy, R }`,
---- `{ "container", cx, cy, R }` or `{ "segment", x0, y0, x1, y1 }` with an optional `types = "both" | "white" | "yolk"`;
+--- `{ "container", cx, cy, R }`, `{ "segment", x0, y0, x1, y1 }` or `{ "wall", x0, y0, x1, y1 }` (a segment that fast
+--- particles cannot cross: it sweeps the sub-step's path) with an optional `types = "both" | "white" | "yolk"`;
 --- applied in list order to every particle's new position in a relaxed pass.  `{}` clears the list.
 function SimulationHandler:set_colliders(colliders)
     local n = #colliders

@@ -109,10 +109,10 @@ class _HandlerSurface:
                 c = tuple(c)
                 kind = c[0] if c else None
                 types = "both"
-            if kind not in _ffi.COLLIDER_KINDS:
-                raise EggError("collider %d: kind must be one of %s, not %r" % (k, ", ".join(_ffi.COLLIDER_KINDS), kind))
-            code = _ffi.COLLIDER_KINDS.index(kind)
-            names = _ffi.COLLIDER_PARAMS[code]
+            if not isinstance(kind, str) or kind not in _ffi.COLLIDER_CODES:
+                raise EggError("collider %d: kind must be one of %s, not %r" % (k, ", ".join(_ffi.COLLIDER_CODES), kind))
+            code = _ffi.COLLIDER_CODES[kind]
+            names = _ffi.COLLIDER_PARAM_NAMES[code]
             if isinstance(c, dict):
                 extra = set(c) - set(names) - {"kind", "types"}
                 if extra or not all(n in c for n in names):
@@ -138,7 +138,10 @@ class _HandlerSurface:
     def set_colliders(self, colliders):
         """The ordered list of static colliders, at most 64 ("Colliders"; relaxed order only):
         `("half_plane", nx, ny, off)` keeps n . pos - off >= radius, `("disc", cx, cy, R)` is an obstacle,
-        `("container", cx, cy, R)` keeps particles inside, `("segment", x0, y0, x1, y1)` is a wall of zero thickness; each
+        `("container", cx, cy, R)` keeps particles inside, `("segment", x0, y0, x1, y1)` is a wall of zero thickness that looks only
+        at where a pass has put a particle -- what moves more than its radius past it in one sub-step gets through --,
+        `("wall", x0, y0, x1, y1)` is the same wall swept: a particle that starts a sub-step on one side cannot end a pass
+        on the other; each
         takes an optional last element (or dict key) types = "both" | "white" | "yolk", and each may be a dict with "kind"
         and the parameter names.  In a relaxed pass every particle's new position is projected collider after collider,
         in list order.  `[]` clears the list.  Raises EggError for a bad list (nothing changes) and for a non-empty list on
@@ -152,7 +155,7 @@ class _HandlerSurface:
         n = C.c_int32()
         self._check(self._c("get_colliders")(_ffi.MAX_COLLIDERS, arr, C.byref(n)))
         types = {v: k for k, v in _ffi.COLLIDER_TYPES.items()}
-        return [(_ffi.COLLIDER_KINDS[c.kind],) + tuple(c.p[:len(_ffi.COLLIDER_PARAMS[c.kind])]) + (types[c.type_mask],)
+        return [(_ffi.COLLIDER_NAMES[c.kind],) + tuple(c.p[:len(_ffi.COLLIDER_PARAM_NAMES[c.kind])]) + (types[c.type_mask],)
                 for c in arr[:n.value]]
 
     def collider_hits(self):

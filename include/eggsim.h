@@ -394,6 +394,24 @@ int egg_set_option(egg_handle *h, int option, double value);
  *   CONTAINER  p = (cx, cy, R, -): the particle stays inside.  m = max(R - r, 0); d2 > m m: x = cx + (dx / d) m, y likewise.
  *   SEGMENT    p = (x0, y0, x1, y1): a wall of zero thickness.  e = p1 - p0, l2 = e . e,
  *              t = l2 == 0 ? 0 : clamp(((x - x0) ex + (y - y0) ey) / l2, 0, 1), q = p0 + t e; then DISC with centre q, R = 0.
+ *              It looks only at the position a pass has produced: a particle carried more than r past it inside one
+ *              sub-step lands on the far side and is pushed on.  A segment does not hold what moves fast; a WALL does.
+ *   WALL       p = (x0, y0, x1, y1): a two-sided thin wall that sweeps.  A particle that starts a sub-step on one side
+ *              cannot end a pass on the other, however far the pass moved it.  prev is the particle's position at the
+ *              start of the sub-step (what step 5c reads).  e, l2, t, q as SEGMENT; dx = x - qx, dy = y - qy,
+ *              d2 = dx dx + dy dy, m = 0 + r; then
+ *                a0 = ex (prev.y - y0) - ey (prev.x - x0), a1 = ex (y - y0) - ey (x - x0);
+ *                opp = (a0 > 0 && a1 <= 0) || (a0 < 0 && a1 >= 0); caught = false; if opp: u = a0 / (a0 - a1),
+ *                hx = prev.x + u (x - prev.x), hy = prev.y + u (y - prev.y), tc = ((hx - x0) ex + (hy - y0) ey) / l2,
+ *                caught = tc >= 0 && tc <= 1.
+ *              caught: l = sqrt(l2), d = sqrt(d2), n = a0 > 0 ? ((-ey) / l, ex / l) : (ey / l, (-ex) / l) -- the unit normal
+ *              towards prev's side --, x = qx + nx m, y = qy + ny m: one hit; for step 5c the normal is n and pen = m + d.
+ *              Not caught: SEGMENT's rule, bit for bit.  A path that passes beyond an end (tc outside [0, 1]) goes round
+ *              the wall; a sub-step that starts exactly on the line (a0 == 0) has no side and is not caught; a
+ *              degenerate wall (l2 == 0, so a0 == 0) never catches and acts as SEGMENT's point; a NaN prev or position is
+ *              not caught.  prev does not change inside a sub-step, so every pass sweeps from the same start (the
+ *              viscosity pass rewrites prev only after the sub-step's last collision pass).  The sweep is against the
+ *              list as it is: not against a list the caller changes between steps.  A catch adds no counter of its own.
  * Parameters a kind does not use are stored as 0.  The projection has no compliance, mass, friction or omega; velocities
  * follow from the post-solve, so a wall absorbs the normal velocity.  Colliders are not drawn.  Applied in list order, a
  * particle in a corner satisfies the last collider exactly and the earlier ones only approximately.
@@ -402,9 +420,11 @@ int egg_set_option(egg_handle *h, int option, double value);
  * egg_set_colliders checks everything before it changes anything: EGG_ERR_INVALID_ARGUMENT, with the collider's index in
  * the message, for n outside 0 .. EGG_MAX_COLLIDERS, an unknown kind, a mask that is 0 or has bits beyond 3, a parameter
  * that is not finite, R < 0, a normal shorter than the white config's eps.  Refused while a step is in flight.  The list
- * goes to the device when it is set, never per step; with an empty list a step launches exactly what it launches without. */
+ * goes to the device when it is set, never per step; with an empty list a step launches exactly what it launches without,
+ * and a list without a WALL launches exactly what it launched before there were walls. */
 #define EGG_MAX_COLLIDERS 64
 enum { EGG_COLLIDER_HALF_PLANE = 0, EGG_COLLIDER_DISC = 1, EGG_COLLIDER_CONTAINER = 2, EGG_COLLIDER_SEGMENT = 3 };
+enum { EGG_COLLIDER_WALL = 5 }; /* 4 is not a kind: it was refused as unknown before there were walls, and it stays refused */
 typedef struct {
     int32_t kind;      /* EGG_COLLIDER_* */
     int32_t type_mask; /* bit 0 white, bit 1 yolk; never 0 */
@@ -427,6 +447,7 @@ int egg_get_collider_hits(egg_handle *h, int64_t hits[2]);
  *   HALF_PLANE        n = (nx, ny) as stored, pen = -s
  *   DISC and SEGMENT  n = the unit vector the projection used (the coincident pair's at d2 == 0), pen = m - d (d = 0 at
  *                     the centre; a segment has m = 0 + r)
+ *   WALL              caught: n = the unit normal towards prev's side, pen = m + d; not caught: as SEGMENT
  *   CONTAINER         n = (dx / d, dy / d), pen = d - m
  * FP64 in exactly this order, no contraction, sqrt and / correctly rounded; every comparison is false for a NaN:
  *   ex = (x - prev.x) - h vx, ey = (y - prev.y) - h vy, dn = ex nx + ey ny, tx = ex - dn nx, ty = ey - dn ny,
