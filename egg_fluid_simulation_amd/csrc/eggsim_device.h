@@ -442,6 +442,27 @@ struct EggRelaxedGroupViscArgs {
     EggRxViscFields v;
 };
 
+// White-yolk coupling (egg_set_coupling, DESIGN.md section 2.7, "Coupling"): one cross-type pass per sub-step, before its
+// first collision pass.  Both types build their cell table at the shared cell size H (insert / scan / scatter / rank are
+// the collision pass's, with A.cell_size = H), and egg_rx_couple_kernel walks the OTHER type's table from the own type's
+// grouped slots.  A single handle only: the key of a particle is its index within its type.
+struct EggRxCoupleFields {
+    const unsigned long long *hkey;      // the other type's table, as its rank kernel has left it
+    const uint32_t *hstart;
+    const int32_t *sidx;
+    const double2 *spos, *swr;
+    uint32_t table_mask;
+    int32_t white_is_self;               // 1: the own type is white = side a of every pair, and counts the pairs that fire
+    double factor;                       // coupling distance = factor (ra + rb)
+    double compliance;                   // _strength_to_compliance(strength, sub_delta) (L:1337-1341)
+    double eps;                          // the white config's, on both sides: one pair, one expression
+    unsigned long long *solves;          // one word (white side): cross pairs that fired in this step
+};
+struct EggRelaxedCoupleArgs {
+    EggRelaxedArgs a;
+    EggRxCoupleFields c;
+};
+
 // A ghost record: a particle of a sender j that lies within one cell of a receiver k's cell box (40 bytes).  In a viscosity
 // pass the two words inv_mass and radius carry u.x and u.y instead (the receiver's unpack copies them as they are).
 struct EggGhost {

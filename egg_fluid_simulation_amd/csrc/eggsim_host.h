@@ -101,6 +101,7 @@ extern "C" __global__ void egg_rx_mid_group_frc_kernel(EggRelaxedGroupFrcArgs A)
 extern "C" __global__ void egg_rx_rank_visc_kernel(EggRelaxedArgs A);
 extern "C" __global__ void egg_rx_rank_group_visc_kernel(EggRelaxedGroupArgs A);
 extern "C" __global__ void egg_rx_gather_visc_kernel(EggRelaxedViscArgs A);
+extern "C" __global__ void egg_rx_couple_kernel(EggRelaxedCoupleArgs K);
 extern "C" __global__ void egg_rx_gather_group_visc_kernel(EggRelaxedGroupViscArgs A);
 extern "C" __global__ void egg_rx_pack_visc_kernel(EggRxPackViscArgs P);
 extern "C" __global__ void egg_rx_wire_pack_visc_kernel(EggRxWirePackViscArgs P);
@@ -437,6 +438,13 @@ struct egg_handle {
     // passes of committed steps counted per type
     double viscosity[2] = {0.0, 0.0};
     int64_t viscosity_pairs[2] = {0, 0};
+    // white-yolk coupling (egg_set_coupling; relaxed order, one handle only): the distance factor, 0 = off, the strength,
+    // the cross pairs that fired in committed steps, and the four events of a coupled step (created by the first one):
+    // built[w] = type w's table at the coupling cell size is complete, read[w] = type w's couple kernel has read the other
+    // type's table
+    double coupling_factor = 0.0, coupling_strength = 1.0;
+    int64_t coupling_solves = 0;
+    hipEvent_t couple_built[2] = {nullptr, nullptr}, couple_read[2] = {nullptr, nullptr};
     int opt_force_cell_hash = 0;     // test hook: every launch class keys its cells by the LDS hash table, never the dense grid
     int opt_force_global_state = 0;  // test hook: run every tile through the global-memory-state kernel  // threads per particle in the step kernel's workgroups (pair dataflow spreading)
     hipDeviceProp_t prop{};
@@ -581,7 +589,7 @@ constexpr char kRelaxedBadCellText[] = "relaxed order: a position is NaN or its 
 // more: their hits.  With viscosity the halo words cover V = S more passes, the viscosity pass of sub-step `sub` being
 // halo pass P + sub, and one more word, the last, holds the pairs the viscosity passes counted.  V = 0 is the layout
 // without.  With collider surfaces of which one has friction, or with a wall in the list, one more word behind all of
-// these: the grips.
+// these: the grips.  With coupling one more word behind all of these, on the white type only: the cross pairs that fired.
 struct RelaxedLayout {
     size_t P = 0, nq = 0;
     bool halo = false;  // ghosts of other handles' particles take part: the group instantiations of the kernels
@@ -591,6 +599,8 @@ struct RelaxedLayout {
     size_t V = 0;            // (set by prepare_type: the sub-steps, when the type's viscosity coefficient is not zero)
     bool surfaces = false;   // (set by prepare_type: a collider surface of the handle has friction > 0, or walls)
     bool walls = false;      // (set by prepare_type: the handle's list holds a wall; implies surfaces)
+    bool coupling = false;   // (set by prepare_type: the step runs coupling passes -- no halo, factor > 0, both types populated)
+    bool coupled_word = false;  // (set by prepare_type: coupling, and the type is white: it holds the counter word)
     size_t H() const { return P + V; }                                        // passes with a halo
     size_t box(size_t p) const { return 1 + P + 4 * p; }                      // 4 words
     size_t ghosts(size_t p) const { return 1 + P + 4 * H() + p; }
@@ -599,7 +609,8 @@ struct RelaxedLayout {
     size_t hits() const { return cohered() + (cohesion ? 1 : 0); }
     size_t visc() const { return hits() + (colliders ? 1 : 0); }
     size_t grips() const { return visc() + (V ? 1 : 0); }
-    size_t words() const { return grips() + (surfaces ? 1 : 0); }
+    size_t coupled() const { return grips() + (surfaces ? 1 : 0); }
+    size_t words() const { return coupled() + (coupled_word ? 1 : 0); }
 };
 struct RelaxedStep {  // one type of one handle in a relaxed step
     egg_handle *h = nullptr;
@@ -612,6 +623,7 @@ struct RelaxedStep {  // one type of one handle in a relaxed step
     EggRxSurfaceFields srf{};   // collider surfaces (L.surfaces): the handle's records, the sub-step, the grip counter
     EggRxForceFields frc{};     // force fields (L.forces): the handle's list, the type's bit
     EggRxViscFields visc{};     // viscosity (L.V): the type's coefficient, the pair counter
+    double couple_cell = 0, couple_c = 0;  // coupling (L.coupling): the shared cell size H, the compliance of the strength
     int64_t ghost_cap = 0;    // a pass runs over n + ghost_cap entries
     int launches = 0;         // kernel launches so far: into the statistics at the commit
 };
@@ -623,6 +635,8 @@ int prepare_type(RelaxedStep &st, int C, size_t ghosts, const RelaxedLayout &L, 
 int launch_substep(RelaxedStep &st, int sub);
 int launch_pass(RelaxedStep &st, int p);
 int launch_viscosity(RelaxedStep &st, int sub);
+int launch_coupling_tables(RelaxedStep &st);
+int launch_coupling(RelaxedStep &st, RelaxedStep &other);
 int read_status(RelaxedStep &st);
 bool bad_cell(const RelaxedStep &st);
 int launch_end(RelaxedStep &st);

@@ -168,6 +168,10 @@ void egg_destroy(egg_handle *h) {
         if (s.stream) (void)hipStreamDestroy(s.stream);
     }
     if (h->flight_saved) (void)hipEventDestroy(h->flight_saved);
+    for (int w = 0; w < 2; ++w) {
+        if (h->couple_built[w]) (void)hipEventDestroy(h->couple_built[w]);
+        if (h->couple_read[w]) (void)hipEventDestroy(h->couple_read[w]);
+    }
     delete h;
 }
 
@@ -946,6 +950,8 @@ int egg_set_option(egg_handle *h, int option, double value) {
                 return fail(h, EGG_ERR_UNSUPPORTED, "exact order has no force fields: clear the list first (egg_set_forces with n = 0)");
             if (value == EGG_SOLVER_EXACT && (h->viscosity[0] != 0.0 || h->viscosity[1] != 0.0))
                 return fail(h, EGG_ERR_UNSUPPORTED, "exact order has no viscosity: set both coefficients to 0 first (egg_set_viscosity)");
+            if (value == EGG_SOLVER_EXACT && h->coupling_factor > 0.0)
+                return fail(h, EGG_ERR_UNSUPPORTED, "exact order has no white-yolk coupling: set the factor to 0 first (egg_set_coupling)");
             if ((int)value != h->opt_solver_order) {
                 if (value == EGG_SOLVER_EXACT) leave_relaxed(h);
                 else
@@ -1187,6 +1193,36 @@ int egg_get_viscosity_pairs(egg_handle *h, int64_t pairs[2]) {
     if (!pairs) return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_get_viscosity_pairs: pairs is NULL");
     pairs[0] = h->viscosity_pairs[0];
     pairs[1] = h->viscosity_pairs[1];
+    return EGG_OK;
+}
+
+// White-yolk coupling of the relaxed step ("Coupling").  Everything is checked before anything
+// changes.
+int egg_set_coupling(egg_handle *h, double factor, double strength) {
+    if (!h) return EGG_ERR_INVALID_ARGUMENT;
+    REJECT_IN_FLIGHT(h, "egg_set_coupling");
+    if (!(factor >= 0.0 && std::isfinite(factor)))
+        return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_coupling: the factor %g is not a finite number >= 0", factor);
+    if (!(strength >= 0.0 && strength <= 1.0))
+        return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_coupling: the strength %g lies outside [0, 1]", strength);
+    if (factor > 0.0 && h->opt_solver_order != EGG_SOLVER_RELAXED)
+        return fail(h, EGG_ERR_UNSUPPORTED, "egg_set_coupling: coupling needs relaxed order (EGG_OPT_SOLVER_ORDER = 1 first)");
+    h->coupling_factor = factor == 0.0 ? 0.0 : factor;  // (-0.0 is stored as +0.0)
+    h->coupling_strength = strength == 0.0 ? 0.0 : strength;
+    return EGG_OK;
+}
+
+int egg_get_coupling(const egg_handle *h, double *factor, double *strength) {
+    if (!h || !factor || !strength) return EGG_ERR_INVALID_ARGUMENT;
+    *factor = h->coupling_factor;
+    *strength = h->coupling_strength;
+    return EGG_OK;
+}
+
+int egg_get_coupling_solves(egg_handle *h, int64_t *solves) {
+    if (!h) return EGG_ERR_INVALID_ARGUMENT;
+    if (!solves) return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_get_coupling_solves: solves is NULL");
+    *solves = h->coupling_solves;
     return EGG_OK;
 }
 

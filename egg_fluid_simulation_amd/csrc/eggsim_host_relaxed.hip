@@ -28,6 +28,12 @@
 // launch_viscosity, one more pass of the driver -- insert, scan, scatter, the viscous rank kernel, the viscosity gather --
 // and the sub-step's last collision pass records the cell box that pass's halo needs; RelaxedStep::visc carries the
 // coefficient and the pair counter.  With both coefficients zero a step launches what it always launched.
+// With white-yolk coupling (egg_set_coupling, RelaxedLayout::coupling: factor > 0, both types populated, no halo) every
+// sub-step runs a cross-type pass between its begin / mid kernel and its first collision pass: launch_coupling_tables
+// builds the type's table at the shared cell size H, launch_coupling walks the OTHER type's table.  The two types run on
+// their own streams, so four events order them (built[w], read[w]), and relaxed_step enqueues sub-step by sub-step across
+// both types: a wait on an event that has not been recorded yet waits for nothing.  With the factor zero, or one type
+// empty, a step enqueues and launches what it always did.
 #include <hipcub/hipcub.hpp>
 
 #include "eggsim_host.h"
@@ -179,6 +185,8 @@ int prepare_type(RelaxedStep &st, int C, size_t ghosts, const RelaxedLayout &L, 
     st.L.surfaces = st.L.colliders && (h->surfaces_grip || st.L.walls);
     st.L.forces = !h->forces.empty();
     st.L.V = h->viscosity[st.w] > 0.0 ? L.P / (size_t)C : 0;
+    st.L.coupling = !L.halo && h->coupling_factor > 0.0 && h->sys[0].n > 0 && h->sys[1].n > 0;
+    st.L.coupled_word = st.L.coupling && st.w == 0;
     st.C = C;
     st.ghost_cap = (int64_t)ghosts;
     int rc = reserve_relaxed(h, s, ghosts, st.L.words());
@@ -217,6 +225,19 @@ int prepare_type(RelaxedStep &st, int C, size_t ghosts, const RelaxedLayout &L, 
     if (st.L.V) {
         st.visc.c = h->viscosity[st.w];
         st.visc.pairs = r.status.p + st.L.visc();
+    }
+    if (st.L.coupling) {  // both types share the cell size and the compliance
+        st.couple_cell = std::max(1.0, h->coupling_factor * (h->sys[0].cfg.max_radius + h->sys[1].cfg.max_radius));
+        // a coupling distance is at most H, and the pass squares it: with H H finite nothing in the pair arithmetic overflows
+        if (!std::isfinite(st.couple_cell * st.couple_cell))
+            return fail(h, EGG_ERR_INVALID_ARGUMENT, "relaxed order: the coupling cell size %g (factor %g times the two max_radius) has no finite square",
+                        st.couple_cell, h->coupling_factor);
+        const double alpha = 1 - clampd(h->coupling_strength, 0, 1);  // L:1337-1341
+        st.couple_c = alpha / (st.env.sub_delta * st.env.sub_delta);
+        for (int k = 0; k < 2; ++k) {
+            if (!h->couple_built[k]) HIP_TRY(h, hipEventCreateWithFlags(&h->couple_built[k], hipEventDisableTiming));
+            if (!h->couple_read[k]) HIP_TRY(h, hipEventCreateWithFlags(&h->couple_read[k], hipEventDisableTiming));
+        }
     }
     if (!L.halo) return EGG_OK;
     const bool rebuild = r.key_sig != sig || r.ekey.cap < n + ghosts;  // (or a new array)
@@ -392,6 +413,56 @@ int launch_viscosity(RelaxedStep &st, int sub) {
     return EGG_OK;
 }
 
+// The coupling pass of a sub-step, first half (only with L.coupling): the type's cell table over the positions its
+// begin / mid kernel has just written, at the shared cell size H, into the table buffers of the collision passes (free
+// until the sub-step's first one).  built[w] tells the other type's stream that the table is complete.
+int launch_coupling_tables(RelaxedStep &st) {
+    egg_handle *h = st.h;
+    System &s = h->sys[st.w];
+    RelaxedBufs &r = s.rx;
+    EggRelaxedArgs a = st.A.a;
+    a.cell_size = st.couple_cell;
+    const dim3 grid((unsigned)((s.n + 255) / 256)), block(256);
+    HIP_TRY(h, hipMemsetAsync(r.hkey.p, 0xFF, (size_t)r.table * 8, s.stream));
+    HIP_TRY(h, hipMemsetAsync(r.hcount.p, 0, ((size_t)r.table + 1) * 4, s.stream));
+    hipLaunchKernelGGL(egg_rx_insert_kernel, grid, block, 0, s.stream, a);
+    size_t bytes = r.scan_bytes;
+    HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(r.scan_tmp.p, bytes, r.hcount.p, r.hstart.p, (int)r.table + 1, s.stream));
+    hipLaunchKernelGGL(egg_rx_scatter_kernel, grid, block, 0, s.stream, a);
+    hipLaunchKernelGGL(egg_rx_rank_kernel, grid, block, 0, s.stream, a);
+    st.launches += 4;
+    HIP_TRY(h, hipEventRecord(h->couple_built[st.w], s.stream));
+    return EGG_OK;
+}
+
+// Second half: once the other type's table is complete, the couple kernel gathers from it into pos_next; read[w] tells the
+// other type's stream that its table may be cleared again.  Jacobi: both types read start-of-pass positions (the grouped
+// copies), and the swap makes the result the start of the sub-step's first collision pass.  prev is not touched.
+int launch_coupling(RelaxedStep &st, RelaxedStep &other) {
+    egg_handle *h = st.h;
+    System &s = h->sys[st.w];
+    const RelaxedBufs &o = h->sys[other.w].rx;
+    HIP_TRY(h, hipStreamWaitEvent(s.stream, h->couple_built[other.w], 0));
+    EggRelaxedCoupleArgs k{st.A.a, EggRxCoupleFields{}};
+    k.a.cell_size = st.couple_cell;
+    k.c.hkey = o.hkey.p;
+    k.c.hstart = o.hstart.p;
+    k.c.sidx = o.sidx.p;
+    k.c.spos = o.spos.p;
+    k.c.swr = o.swr.p;
+    k.c.table_mask = o.table - 1;
+    k.c.white_is_self = st.w == 0;
+    k.c.factor = h->coupling_factor;
+    k.c.compliance = st.couple_c;
+    k.c.eps = h->sys[0].cfg.eps;
+    k.c.solves = st.L.coupled_word ? s.rx.status.p + st.L.coupled() : nullptr;
+    hipLaunchKernelGGL(egg_rx_couple_kernel, dim3((unsigned)((s.n + 255) / 256)), dim3(256), 0, s.stream, k);
+    ++st.launches;
+    HIP_TRY(h, hipEventRecord(h->couple_read[st.w], s.stream));
+    std::swap(st.A.a.pos, st.A.a.pos_next);
+    return EGG_OK;
+}
+
 // the status words on their way to h_status; bad_cell() reads them once the stream has been waited for
 int read_status(RelaxedStep &st) {
     System &s = st.h->sys[st.w];
@@ -411,10 +482,46 @@ int launch_end(RelaxedStep &st) {
     return EGG_OK;
 }
 
+static int relaxed_finish(egg_handle *h, RelaxedStep st[2], int S, int C);
+
+// A step with coupling (factor > 0, both types populated; st: after prepare_step).  The enqueue order is sub-step by
+// sub-step across both types, so that every event a stream waits for has been recorded by then.  Before a type's table
+// is cleared again -- by the sub-step's first collision pass, or by launch_viscosity -- its stream waits until the other
+// type's couple kernel has read it.
+static int relaxed_step_coupled(egg_handle *h, RelaxedStep st[2], int S, int C) {
+    int rc = EGG_OK;
+    for (int w = 0; w < 2; ++w) {
+        if (h->sys[w].n > kRelaxedMaxParticles) return fail(h, EGG_ERR_UNSUPPORTED, EGG_RX_TOO_MANY_TEXT);
+        rc = prepare_type(st[w], C, 0, RelaxedLayout{(size_t)S * C, 0, false}, {}, nullptr);
+        if (rc != EGG_OK) return rc;
+    }
+    if (h->opt_timing)
+        for (int w = 0; w < 2; ++w) HIP_TRY(h, hipEventRecord(h->sys[w].ev0, h->sys[w].stream));
+    for (int sub = 0; sub < S; ++sub) {
+        for (int w = 0; w < 2 && rc == EGG_OK; ++w) rc = launch_substep(st[w], sub);
+        for (int w = 0; w < 2 && rc == EGG_OK; ++w) rc = launch_coupling_tables(st[w]);
+        for (int w = 0; w < 2 && rc == EGG_OK; ++w) rc = launch_coupling(st[w], st[w ^ 1]);
+        for (int w = 0; w < 2 && rc == EGG_OK; ++w) {
+            HIP_TRY(h, hipStreamWaitEvent(h->sys[w].stream, h->couple_read[w ^ 1], 0));
+            for (int c = 0; c < C && rc == EGG_OK; ++c) rc = launch_pass(st[w], sub * C + c);
+            if (rc == EGG_OK && st[w].L.V) rc = launch_viscosity(st[w], sub);
+        }
+        if (rc != EGG_OK) return rc;
+    }
+    for (int w = 0; w < 2; ++w) {
+        rc = launch_end(st[w]);
+        if (rc == EGG_OK) rc = read_status(st[w]);
+        if (rc != EGG_OK) return rc;
+        if (h->opt_timing) HIP_TRY(h, hipEventRecord(h->sys[w].ev1, h->sys[w].stream));
+    }
+    return relaxed_finish(h, st, S, C);
+}
+
 int relaxed_step(egg_handle *h, double delta, int S, int C) {  // L:1722-1989, collision passes relaxed
     RelaxedStep st[2];
     int rc = prepare_step(h, delta, S, st);
     if (rc != EGG_OK) return rc;
+    if (h->coupling_factor > 0.0 && h->sys[0].n > 0 && h->sys[1].n > 0) return relaxed_step_coupled(h, st, S, C);
     for (int w = 0; w < 2; ++w) {
         System &s = h->sys[w];
         if (s.n == 0) continue;
@@ -432,6 +539,11 @@ int relaxed_step(egg_handle *h, double delta, int S, int C) {  // L:1722-1989, c
         if (rc != EGG_OK) return rc;
         if (h->opt_timing) HIP_TRY(h, hipEventRecord(s.ev1, s.stream));
     }
+    return relaxed_finish(h, st, S, C);
+}
+
+// a relaxed step whose launches are all enqueued: wait for both types, then fail on a bad cell or commit
+static int relaxed_finish(egg_handle *h, RelaxedStep st[2], int S, int C) {
     double ms = 0;
     bool bad = false;
     for (int w = 0; w < 2; ++w) {
@@ -475,6 +587,7 @@ void relaxed_commit(egg_handle *h, const RelaxedStep st[2], int S, int C, double
         if (st[w].L.colliders) h->collider_hits[w] += (int64_t)s.rx.h_status.p[st[w].L.hits()];
         if (st[w].L.surfaces) h->collider_grips[w] += (int64_t)s.rx.h_status.p[st[w].L.grips()];
         if (st[w].L.V) h->viscosity_pairs[w] += (int64_t)s.rx.h_status.p[st[w].L.visc()];
+        if (st[w].L.coupled_word) h->coupling_solves += (int64_t)s.rx.h_status.p[st[w].L.coupled()];
         h->stats.follow_solves += s.n * S;
         // the exact path's host copies of the atoms' cells describe older positions now
         s.aabb_valid = s.aabb_on_device = s.disp_valid = false;

@@ -135,6 +135,11 @@ int relaxed_group_step(egg_handle *const *hs, int nh, double delta, int S, int C
             *error = "relaxed order: the handles of the group differ in their viscosity (egg_group_set_viscosity sets all)";
             return EGG_ERR_INVALID_ARGUMENT;
         }
+    for (int k = 0; k < nh; ++k)
+        if (hs[k]->coupling_factor > 0.0) {  // (the halo carries no ghosts of the other type)
+            *error = "relaxed order: white-yolk coupling runs on a single handle only (egg_set_coupling with factor 0 first)";
+            return EGG_ERR_UNSUPPORTED;
+        }
     for (int k = 0; k < nh; ++k) {
         (void)hipSetDevice(hs[k]->device);
         GK_TRY(k, prepare_step(hs[k], delta, S, st[k]));

@@ -120,6 +120,8 @@ int egg_rx_begin(egg_handle *h, double delta, int32_t n_substeps, int32_t n_coll
     if (n_substeps < 1 || n_collision_steps < 1 || std::isnan(delta)) return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_rx_begin: invalid arguments");
     if (h->opt_solver_order != EGG_SOLVER_RELAXED) return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_rx_begin: the handle is not in relaxed order");
     REJECT_IN_FLIGHT(h, "egg_rx_begin");
+    if (h->coupling_factor > 0.0)  // (the halo carries no ghosts of the other type)
+        return fail(h, EGG_ERR_UNSUPPORTED, "egg_rx_begin: white-yolk coupling runs on a single handle only (egg_set_coupling with factor 0 first)");
     (void)hipSetDevice(h->device);
     WireStep &W = wire_of(h);
     const int S = n_substeps, C = n_collision_steps;

@@ -54,6 +54,11 @@
 // rewrites prev.  Positions are not touched.  In a group the ghosts' u arrive in the record words that carry inverse mass
 // and radius in a collision pass (egg_rx_pack_visc_kernel).  Nothing of it runs while both coefficients are zero.
 //
+// With white-yolk coupling (egg_set_coupling; DESIGN.md section 2.7, "Coupling"; one handle only) every sub-step runs one
+// cross-type pass between its begin / mid kernel and its first collision pass: both types build their table at a shared
+// cell size with the insert, scatter and rank kernels above, and egg_rx_couple_kernel moves every particle by the mean of
+// its pairs with the OTHER type's particles, found in the other type's table.  Nothing of it runs while the factor is zero.
+//
 // All arithmetic is IEEE double in the order of the definition: compile with -ffp-contract=off.
 #include <hip/hip_runtime.h>
 #include "eggsim_device.h"
@@ -650,6 +655,98 @@ extern "C" __global__ void __launch_bounds__(256) egg_rx_rank_visc_kernel(EggRel
 extern "C" __global__ void __launch_bounds__(256) egg_rx_rank_group_visc_kernel(EggRelaxedGroupArgs A) { rx_rank_visc<true>(A.a, A.g); }
 extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_visc_kernel(EggRelaxedViscArgs A) { rx_gather_visc<false>(A.a, EggRxGroupFields{}, A.v); }
 extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_visc_kernel(EggRelaxedGroupViscArgs A) { rx_gather_visc<true>(A.a, A.g, A.v); }
+
+// ---- white-yolk coupling ----
+
+// The coupling pass, one thread per grouped slot of the own type (threads of a wave share cells, so the walk over the
+// other type's table is coherent).  Both tables were built at the shared cell size A.cell_size = H, so the 3x3 cells of
+// the particle's own cell hold every particle of the other type within the coupling distance.  Candidates: the other
+// type's particles in those cells, x offset outer, y offset inner, ascending key inside a cell.  Pair (a, b): a is the
+// white particle, b the yolk one, whichever side evaluates it; the arithmetic is rx_gather's collision correction with
+// min_distance = factor (ra + rb) and the coupling compliance.  The white side counts the pairs that fire, one atomic
+// per wave.  Neighbours are read from grouped copies only; the move is written to pos_next.
+extern "C" __global__ void __launch_bounds__(256) egg_rx_couple_kernel(EggRelaxedCoupleArgs K) {
+    const EggRelaxedArgs &A = K.a;
+    const EggRxCoupleFields &O = K.c;
+    const int t = (int)(blockIdx.x * 256 + threadIdx.x);
+    int solves = 0;
+    if (t < A.n) {
+        const int i = A.sidx[t];
+        const double2 p = A.spos[t], wr = A.swr[t];
+        const bool first = O.white_is_self != 0;
+        int32_t cx, cy;
+        (void)rx_cell(p, A.cell_size, cx, cy);  // (a bad cell was flagged by the insert kernel)
+        double sx = 0.0, sy = 0.0;
+        int n_fired = 0;
+        for (int ox = -1; ox <= 1; ++ox) {
+            for (int oy = -1; oy <= 1; ++oy) {
+                const unsigned long long key = rx_key(cx + ox, cy + oy);
+                uint32_t h = rx_hash(key) & O.table_mask;
+                unsigned long long k;
+                while ((k = O.hkey[h]) != key && k != EGG_RX_EMPTY_KEY) h = (h + 1) & O.table_mask;
+                if (k == EGG_RX_EMPTY_KEY) continue;
+                const int st = (int)O.hstart[h], en = (int)O.hstart[h + 1];
+                for (int e = st; e < en; ++e) {
+                    const int j = O.sidx[e];
+                    const double2 q = O.spos[e], wq = O.swr[e];
+                    const double2 pa = first ? p : q, pb = first ? q : p;
+                    const double wa = first ? wr.x : wq.x, wb = first ? wq.x : wr.x;
+                    const double ra = first ? wr.y : wq.y, rb = first ? wq.y : wr.y;
+                    const double wsum = wa + wb;
+                    if (wsum < O.eps) continue;
+                    const double dx = pb.x - pa.x, dy = pb.y - pa.y;
+                    const double d2 = dx * dx + dy * dy;
+                    const double min_distance = O.factor * (ra + rb);
+                    if (!(d2 <= min_distance * min_distance)) continue;
+                    ++n_fired;
+                    solves += first ? 1 : 0;
+                    const double divisor = wsum + O.compliance;
+                    if (divisor < O.eps) {
+                        sx = sx + 0.0;
+                        sy = sy + 0.0;
+                        continue;
+                    }
+                    const double current = sqrt(d2);
+                    const double violation = current - min_distance;
+                    double nx, ny;
+                    if (d2 == 0.0) {  // coincident: by the two keys, b - a = yolk key - white key
+                        const int k8 = (first ? j - i : i - j) & 7;
+                        nx = kRxDirX[k8];
+                        ny = kRxDirY[k8];
+                    } else if (current < O.eps) {
+                        nx = 0.0;
+                        ny = 0.0;
+                    } else {
+                        nx = dx / current;
+                        ny = dy / current;
+                    }
+                    double correction = -violation / divisor;
+                    const double max_correction = fabs(violation);
+                    if (correction < -max_correction) correction = -max_correction;
+                    if (correction > max_correction) correction = max_correction;
+                    if (first) {
+                        sx = sx + -nx * correction * wa;
+                        sy = sy + -ny * correction * wa;
+                    } else {
+                        sx = sx + nx * correction * wb;
+                        sy = sy + ny * correction * wb;
+                    }
+                }
+            }
+        }
+        double2 out = p;
+        if (n_fired > 0) {
+            out.x = p.x + (sx * A.omega) / (double)n_fired;
+            out.y = p.y + (sy * A.omega) / (double)n_fired;
+        }
+        A.pos_next[i] = out;
+    }
+    if (O.white_is_self) {  // (uniform over the launch)
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) solves += __shfl_xor(solves, d, 64);
+        if ((threadIdx.x & 63) == 0 && solves) atomicAdd(O.solves, (unsigned long long)solves);
+    }
+}
 
 // ---- device groups ----
 

@@ -81,6 +81,9 @@ int egg_get_forces(const egg_handle *h, int32_t cap, egg_force *f, int32_t *n);
 int egg_set_viscosity(egg_handle *h, const double c[2]);
 int egg_get_viscosity(const egg_handle *h, double c[2]);
 int egg_get_viscosity_pairs(egg_handle *h, int64_t pairs[2]);
+int egg_set_coupling(egg_handle *h, double factor, double strength);
+int egg_get_coupling(const egg_handle *h, double *factor, double *strength);
+int egg_get_coupling_solves(egg_handle *h, int64_t *solves);
 typedef struct { double friction; double vx, vy; } egg_collider_surface;
 int egg_set_collider_surfaces(egg_handle *h, int32_t n, const egg_collider_surface *s);
 int egg_get_collider_surfaces(const egg_handle *h, int32_t cap, egg_collider_surface *s, int32_t *n);
@@ -567,6 +570,30 @@ function SimulationHandler:viscosity_pairs()
     local pairs = ffi.new("int64_t[2]")
     self:_check(lib.egg_get_viscosity_pairs(self._h, pairs))
     return tonumber(pairs[0]), tonumber(pairs[1])
+end
+
+-- Not in the reference, whose white and yolk never see each other (L:1776-1786): white-yolk coupling of the relaxed step
+-- (egg_set_coupling in include/eggsim.h; DESIGN.md section 2.7, "Coupling").  Relaxed order, one handle only.
+
+--- factor >= 0 (0, the default, = off) and strength in [0, 1] (default 1): before the first collision pass of every
+--- sub-step of a relaxed step, a white and a yolk particle closer than factor * (ra + rb) are pushed apart to that
+--- distance; all pairs of both types couple, whatever their batch
+function SimulationHandler:set_coupling(factor, strength)
+    self:_check(lib.egg_set_coupling(self._h, factor or 0, strength or 1))
+end
+
+--- factor, strength: as stored
+function SimulationHandler:coupling()
+    local f, s = ffi.new("double[1]"), ffi.new("double[1]")
+    self:_check(lib.egg_get_coupling(self._h, f, s))
+    return f[0], s[0]
+end
+
+--- distinct white-yolk pairs that fired over the coupling passes of committed steps
+function SimulationHandler:coupling_solves()
+    local n = ffi.new("int64_t[1]")
+    self:_check(lib.egg_get_coupling_solves(self._h, n))
+    return tonumber(n[0])
 end
 
 function SimulationHandler:draw()

@@ -307,6 +307,39 @@ class _HandlerSurface:
         self._check(self._c("get_viscosity_pairs")(pairs))
         return list(pairs)
 
+    # ------------------------------------------------ white-yolk coupling (egg_set_coupling)
+    _COUPLING_LIMIT = ("coupling: white-yolk coupling runs on a single SimulationHandler only -- the halo of a device group "
+                       "or of sharded ranks carries no ghosts of the other type; only factor 0 (off) is accepted here")
+
+    @staticmethod
+    def _c_coupling(factor, strength):
+        """(factor, strength) as the doubles egg_set_coupling takes; the ranges are checked here as the library checks them"""
+        out = []
+        for name, v in (("factor", factor), ("strength", strength)):
+            try:
+                out.append(float(v))
+            except (TypeError, ValueError):
+                raise EggError("coupling: the %s must be a number, not %r" % (name, v)) from None
+        if not (0.0 <= out[0] < float("inf")):  # (false for a NaN)
+            raise EggError("coupling: the factor %r is not a finite number >= 0" % (out[0],))
+        if not (0.0 <= out[1] <= 1.0):
+            raise EggError("coupling: the strength %r lies outside [0, 1]" % (out[1],))
+        return out[0], out[1]
+
+    def set_coupling(self, factor=0.0, strength=1.0):
+        """SimulationHandler.set_coupling where several handles share a step (SimulationGroup, ShardedSimulationHandler):
+        factor 0 is accepted and changes nothing, anything else raises EggError naming the limit (after the range check)."""
+        factor, strength = self._c_coupling(factor, strength)
+        if factor != 0.0:
+            raise EggError(self._COUPLING_LIMIT)
+
+    def coupling(self):
+        """(factor, strength): always (0.0, 1.0) here, see set_coupling"""
+        return (0.0, 1.0)
+
+    def coupling_solves(self):
+        return 0
+
     def _init_host_state(self, white_config, yolk_config):
         """config tables (validated like the reference, L:1253-1320), hidden constants and render switches; no device"""
         if white_config is None and yolk_config is None:
@@ -711,6 +744,29 @@ class SimulationHandler(_HandlerSurface):
         if getattr(self, "_h", None):
             self._lib.egg_destroy(self._h)
             self._h = None
+
+    def set_coupling(self, factor=0.0, strength=1.0):
+        """White-yolk coupling: one cross-type collision pass per sub-step of a relaxed step, before the sub-step's first
+        collision pass ("Coupling"; relaxed order only).  A white and a yolk particle closer than
+        factor * (ra + rb) are pushed apart to that distance with the collision correction's arithmetic and the
+        compliance of `strength` in [0, 1]; factor 0 = off.  All pairs of both types couple, whatever their batch, and
+        nothing pulls a yolk back to its white.  Raises EggError for a NaN, negative or infinite factor or a strength
+        outside [0, 1] (nothing changes) and for factor > 0 on a handle in exact order; set_solver_order("exact") raises
+        while factor > 0."""
+        factor, strength = self._c_coupling(factor, strength)  # (refused here before any device call)
+        self._check(self._c("set_coupling")(factor, strength))
+
+    def coupling(self):
+        """(factor, strength) as stored"""
+        f, s = C.c_double(), C.c_double()
+        self._check(self._c("get_coupling")(C.byref(f), C.byref(s)))
+        return (f.value, s.value)
+
+    def coupling_solves(self):
+        """distinct white-yolk pairs that fired over the coupling passes of committed steps, since creation"""
+        n = C.c_int64()
+        self._check(self._c("get_coupling_solves")(C.byref(n)))
+        return int(n.value)
 
     def add_many(self, xs, ys, white_radius=None, yolk_radius=None, white_n_particles=None,
                  yolk_n_particles=None):

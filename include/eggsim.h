@@ -528,7 +528,7 @@ int egg_get_forces(const egg_handle *h, int32_t cap, egg_force *f, int32_t *n);
  *   5. otherwise nux = u_i.x + c (sx / sw), nuy = u_i.y + c (sy / sw), prev_i = (p_i.x - nux, p_i.y - nuy): a convex blend of
  *      the particle's displacement and its neighbours' weighted mean, stable for every c in [0, 1].
  * FP64 in exactly this order, no contraction; every comparison is false for a NaN.  Pairs of any batch smooth each other;
- * white and yolk never interact.  pair_solves and max_pass_visits do not change; egg_get_viscosity_pairs counts, per type,
+ * white and yolk do not (their one interaction is egg_set_coupling).  pair_solves and max_pass_visits do not change; egg_get_viscosity_pairs counts, per type,
  * the distinct pairs with d2 < H H over the viscosity passes of committed steps (a failed or discarded step adds nothing).
  * Relaxed order only, as the colliders: a non-zero coefficient on a handle in exact order is EGG_ERR_UNSUPPORTED, and
  * EGG_OPT_SOLVER_ORDER = 0 is EGG_ERR_UNSUPPORTED while a coefficient is not zero; both zero is always accepted.  A
@@ -538,6 +538,43 @@ int egg_get_forces(const egg_handle *h, int32_t cap, egg_force *f, int32_t *n);
 int egg_set_viscosity(egg_handle *h, const double c[2]); /* c[EGG_WHITE], c[EGG_YOLK] */
 int egg_get_viscosity(const egg_handle *h, double c[2]);
 int egg_get_viscosity_pairs(egg_handle *h, int64_t pairs[2]);
+
+/* ---- white-yolk coupling (not in the reference, whose two types never see each other, L:1776-1786; DESIGN.md section
+ * 2.7, "Coupling") ----
+ * One cross-type collision pass per sub-step of a RELAXED step.  A handle holds two doubles that both types share: the
+ * distance `factor` (finite, >= 0; 0, the default, = off) and the `strength` in [0, 1] (default 1).  The pass runs only
+ * while factor > 0 and both types have particles, once per sub-step, BEFORE the sub-step's first collision pass:
+ *   1. pre-solve + follow, both types;  2. the coupling pass, both types;  3. the C collision passes;  4. viscosity.
+ * So colliders and walls keep the last word: a wall's sweep reads `prev`, which the coupling pass does not touch.  It is
+ * a Jacobi pass with constraint averaging like the collision pass:
+ *   cells       H = max(1.0, factor (white max_radius + yolk max_radius)) from the two configs; the cell of a particle is
+ *               floor(x / H), floor(y / H); each type gets a table of its own over the positions the pre-solve + follow
+ *               has just written.  A radius never exceeds its config's max_radius, so every pair within the coupling
+ *               distance lies inside a 3x3 neighbourhood.
+ *   candidates  of particle i of one type: every particle of the OTHER type in i's 3x3 cells, x offset -1..1 outer, y
+ *               offset inner, ascending key inside a cell (the key: the particle's index within its type).
+ *   pair        a is always the white particle, b the yolk one: both sides evaluate one expression, the collision
+ *               correction's, with md = factor (ra + rb), compliance = (1 - strength) / sub_delta^2 (L:1337-1341) and the
+ *               white config's eps.  wsum < eps: skipped, uncounted; d2 <= md md: fires; divisor < eps: zeros;
+ *               current < eps: zero normal; clamp to +-|violation|; a coincident pair (d2 == 0) takes the normal
+ *               DIRS[(b - a) & 7] of the two keys.  White takes (cax, cay), yolk (cbx, cby).
+ *   update      x_i = x_i + (sx omega) / n_i when n_i pairs fired (omega: EGG_OPT_RELAXATION), else the position is
+ *               copied; every pair of the pass reads the start-of-pass positions of both types.
+ * egg_get_coupling_solves: the distinct cross pairs that fired, over committed steps (a failed or discarded step adds
+ * nothing); pair_solves, max_pass_visits and every other counter are unchanged.  A NaN position or a cell beyond +-2^30 at
+ * cell size H fails the step like any bad cell: nothing is committed.  A step whose H H is not finite (an absurd factor)
+ * fails with EGG_ERR_INVALID_ARGUMENT before anything is launched.
+ * ALL pairs of both types couple, whatever their batch: there is no batch tag and no adhesion band -- nothing pulls a yolk
+ * back to its white.  ONE handle only: a device group refuses to step and egg_rx_begin returns EGG_ERR_UNSUPPORTED while
+ * factor > 0 (the halo carries no ghosts of the other type).
+ * Relaxed order only, as viscosity: factor > 0 on a handle in exact order is EGG_ERR_UNSUPPORTED, and
+ * EGG_OPT_SOLVER_ORDER = 0 is EGG_ERR_UNSUPPORTED while factor > 0; factor == 0 is always accepted.  A NaN, negative or
+ * infinite factor, or a strength outside [0, 1], is EGG_ERR_INVALID_ARGUMENT and changes nothing.  Refused while a step is
+ * in flight.  With factor 0, or one type without particles, a step enqueues and launches exactly what it does without;
+ * with coupling a sub-step adds five launches per type. */
+int egg_set_coupling(egg_handle *h, double factor, double strength);
+int egg_get_coupling(const egg_handle *h, double *factor, double *strength);
+int egg_get_coupling_solves(egg_handle *h, int64_t *solves);
 
 /* ---- several GPUs in one process (csrc/eggsim_group.cpp) -------------------------------------------------------
  * The multi-device form of the handle for a host that is ONE process (the LuaJIT wrapper): one egg_handle per device
