@@ -27,7 +27,8 @@ Labels of step 5c, over the lanes the collider has just moved: smooth (its frict
 stick, slide; after a catch the four are caught_smooth, caught_no_tangent, caught_stick, caught_slide.  The collider index
 tells the kind.
 
-Out of scope: NaN positions (a NaN cell fails the step before step 5b matters), the force step and the pair loop."""
+Out of scope: NaN positions (a NaN cell fails the step before step 5b matters) and the force step.  The pair loop has a
+census of its own: tests/pair_census.py, tests/test_pair_census.py, tests/test_gpu_pair_edges.py."""
 import numpy as np
 
 import surface_model as sm

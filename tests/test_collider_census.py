@@ -10,8 +10,8 @@ tests/test_gpu_collider_edges.py runs on the device, checked here on the model a
     of those scenes -- a kernel wrong in that way would fail the device file.
 
 The scenes (the hand table CASES, the oblique wall, the oblique segment, the corner) are defined here and imported by the
-device file.  Out of scope: NaN positions (a NaN cell fails the step before step 5b matters), the force step and the
-pair loop."""
+device file.  Out of scope: NaN positions (a NaN cell fails the step before step 5b matters), the force step.  The
+pair loop has a census of its own: tests/pair_census.py, tests/test_pair_census.py, tests/test_gpu_pair_edges.py."""
 import functools
 
 import numpy as np

@@ -25,8 +25,8 @@ Which test reaches which label of the census (W: a wall, S: a segment):
                                  caught by both in one pass; either list order
   test_device_group, test_sharded_two_ranks   the labels of test_oblique_wall per batch, every handle its share
 
-Out of scope: NaN positions (a NaN cell fails the step before step 5b matters), rx_force and the pair loop of the gather
-kernel."""
+Out of scope: NaN positions (a NaN cell fails the step before step 5b matters), rx_force.  The pair loop of the gather
+kernel has a census of its own: tests/pair_census.py, tests/test_pair_census.py, tests/test_gpu_pair_edges.py."""
 import numpy as np
 import pytest
 
