@@ -463,6 +463,25 @@ struct EggRelaxedCoupleArgs {
     EggRxCoupleFields c;
 };
 
+// White-yolk adhesion (egg_set_adhesion, DESIGN.md section 2.7, "Adhesion"): a same-batch band in the coupling pass.  While
+// it acts (coupling acts and reach > factor) both tables are built at H = max(1.0, reach (white max_radius + yolk
+// max_radius)) through the cohesive rank kernel, which leaves a batch tag per grouped slot -- the atom index, which is one
+// for both types of a handle: their atom lists come from the same live-batch order -- and egg_rx_couple_adh_kernel takes
+// these besides.  A cross pair beyond the coupling distance, of one batch and within reach (ra + rb), is pulled back to
+// the coupling distance through the coupling correction's own arithmetic with the adhesion compliance.
+struct EggRxAdhesionFields {
+    double reach;                        // band: md < d <= reach (ra + rb)
+    double compliance;                   // _strength_to_compliance(adhesion strength, sub_delta)
+    const int32_t *stag;                 // the own type's tags, in grouped order (next to A.spos / A.swr)
+    const int32_t *other_stag;           // the other type's, next to the spos / swr of EggRxCoupleFields
+    unsigned long long *solves;          // one word (white side): cross pairs whose adhesion branch fired in this step
+};
+struct EggRelaxedCoupleAdhArgs {
+    EggRelaxedArgs a;
+    EggRxCoupleFields c;
+    EggRxAdhesionFields d;
+};
+
 // A ghost record: a particle of a sender j that lies within one cell of a receiver k's cell box (40 bytes).  In a viscosity
 // pass the two words inv_mass and radius carry u.x and u.y instead (the receiver's unpack copies them as they are).
 struct EggGhost {

@@ -102,6 +102,7 @@ extern "C" __global__ void egg_rx_rank_visc_kernel(EggRelaxedArgs A);
 extern "C" __global__ void egg_rx_rank_group_visc_kernel(EggRelaxedGroupArgs A);
 extern "C" __global__ void egg_rx_gather_visc_kernel(EggRelaxedViscArgs A);
 extern "C" __global__ void egg_rx_couple_kernel(EggRelaxedCoupleArgs K);
+extern "C" __global__ void egg_rx_couple_adh_kernel(EggRelaxedCoupleAdhArgs K);
 extern "C" __global__ void egg_rx_gather_group_visc_kernel(EggRelaxedGroupViscArgs A);
 extern "C" __global__ void egg_rx_pack_visc_kernel(EggRxPackViscArgs P);
 extern "C" __global__ void egg_rx_wire_pack_visc_kernel(EggRxWirePackViscArgs P);
@@ -445,6 +446,11 @@ struct egg_handle {
     double coupling_factor = 0.0, coupling_strength = 1.0;
     int64_t coupling_solves = 0;
     hipEvent_t couple_built[2] = {nullptr, nullptr}, couple_read[2] = {nullptr, nullptr};
+    // white-yolk adhesion (egg_set_adhesion; a same-batch band in the coupling pass): the reach factor, 0 = off, the
+    // strength, and the cross pairs whose adhesion branch fired in committed steps.  It acts in a step exactly when
+    // coupling acts and reach > factor.
+    double adhesion_reach = 0.0, adhesion_strength = 1.0;
+    int64_t adhesion_solves = 0;
     int opt_force_cell_hash = 0;     // test hook: every launch class keys its cells by the LDS hash table, never the dense grid
     int opt_force_global_state = 0;  // test hook: run every tile through the global-memory-state kernel  // threads per particle in the step kernel's workgroups (pair dataflow spreading)
     hipDeviceProp_t prop{};
@@ -590,6 +596,7 @@ constexpr char kRelaxedBadCellText[] = "relaxed order: a position is NaN or its 
 // halo pass P + sub, and one more word, the last, holds the pairs the viscosity passes counted.  V = 0 is the layout
 // without.  With collider surfaces of which one has friction, or with a wall in the list, one more word behind all of
 // these: the grips.  With coupling one more word behind all of these, on the white type only: the cross pairs that fired.
+// While adhesion acts one more behind that one, on the white type only: the cross pairs that adhered.
 struct RelaxedLayout {
     size_t P = 0, nq = 0;
     bool halo = false;  // ghosts of other handles' particles take part: the group instantiations of the kernels
@@ -601,6 +608,8 @@ struct RelaxedLayout {
     bool walls = false;      // (set by prepare_type: the handle's list holds a wall; implies surfaces)
     bool coupling = false;   // (set by prepare_type: the step runs coupling passes -- no halo, factor > 0, both types populated)
     bool coupled_word = false;  // (set by prepare_type: coupling, and the type is white: it holds the counter word)
+    bool adhesion = false;      // (set by prepare_type: coupling, and the handle's adhesion reach exceeds the coupling factor)
+    bool adhered_word = false;  // (set by prepare_type: adhesion, and the type is white)
     size_t H() const { return P + V; }                                        // passes with a halo
     size_t box(size_t p) const { return 1 + P + 4 * p; }                      // 4 words
     size_t ghosts(size_t p) const { return 1 + P + 4 * H() + p; }
@@ -610,7 +619,8 @@ struct RelaxedLayout {
     size_t visc() const { return hits() + (colliders ? 1 : 0); }
     size_t grips() const { return visc() + (V ? 1 : 0); }
     size_t coupled() const { return grips() + (surfaces ? 1 : 0); }
-    size_t words() const { return coupled() + (coupled_word ? 1 : 0); }
+    size_t adhered() const { return coupled() + (coupled_word ? 1 : 0); }
+    size_t words() const { return adhered() + (adhered_word ? 1 : 0); }
 };
 struct RelaxedStep {  // one type of one handle in a relaxed step
     egg_handle *h = nullptr;
@@ -624,6 +634,7 @@ struct RelaxedStep {  // one type of one handle in a relaxed step
     EggRxForceFields frc{};     // force fields (L.forces): the handle's list, the type's bit
     EggRxViscFields visc{};     // viscosity (L.V): the type's coefficient, the pair counter
     double couple_cell = 0, couple_c = 0;  // coupling (L.coupling): the shared cell size H, the compliance of the strength
+    double adhesion_c = 0;                 // adhesion (L.adhesion): the compliance of its own strength
     int64_t ghost_cap = 0;    // a pass runs over n + ghost_cap entries
     int launches = 0;         // kernel launches so far: into the statistics at the commit
 };

@@ -952,6 +952,8 @@ int egg_set_option(egg_handle *h, int option, double value) {
                 return fail(h, EGG_ERR_UNSUPPORTED, "exact order has no viscosity: set both coefficients to 0 first (egg_set_viscosity)");
             if (value == EGG_SOLVER_EXACT && h->coupling_factor > 0.0)
                 return fail(h, EGG_ERR_UNSUPPORTED, "exact order has no white-yolk coupling: set the factor to 0 first (egg_set_coupling)");
+            if (value == EGG_SOLVER_EXACT && h->adhesion_reach > 0.0)
+                return fail(h, EGG_ERR_UNSUPPORTED, "exact order has no white-yolk adhesion: set the reach to 0 first (egg_set_adhesion)");
             if ((int)value != h->opt_solver_order) {
                 if (value == EGG_SOLVER_EXACT) leave_relaxed(h);
                 else
@@ -1223,6 +1225,36 @@ int egg_get_coupling_solves(egg_handle *h, int64_t *solves) {
     if (!h) return EGG_ERR_INVALID_ARGUMENT;
     if (!solves) return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_get_coupling_solves: solves is NULL");
     *solves = h->coupling_solves;
+    return EGG_OK;
+}
+
+// White-yolk adhesion, the same-batch band of the coupling pass ("Adhesion").  Everything is
+// checked before anything changes.
+int egg_set_adhesion(egg_handle *h, double reach, double strength) {
+    if (!h) return EGG_ERR_INVALID_ARGUMENT;
+    REJECT_IN_FLIGHT(h, "egg_set_adhesion");
+    if (!(reach >= 0.0 && std::isfinite(reach)))
+        return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_adhesion: the reach %g is not a finite number >= 0", reach);
+    if (!(strength >= 0.0 && strength <= 1.0))
+        return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_adhesion: the strength %g lies outside [0, 1]", strength);
+    if (reach > 0.0 && h->opt_solver_order != EGG_SOLVER_RELAXED)
+        return fail(h, EGG_ERR_UNSUPPORTED, "egg_set_adhesion: adhesion needs relaxed order (EGG_OPT_SOLVER_ORDER = 1 first)");
+    h->adhesion_reach = reach == 0.0 ? 0.0 : reach;  // (-0.0 is stored as +0.0)
+    h->adhesion_strength = strength == 0.0 ? 0.0 : strength;
+    return EGG_OK;
+}
+
+int egg_get_adhesion(const egg_handle *h, double *reach, double *strength) {
+    if (!h || !reach || !strength) return EGG_ERR_INVALID_ARGUMENT;
+    *reach = h->adhesion_reach;
+    *strength = h->adhesion_strength;
+    return EGG_OK;
+}
+
+int egg_get_adhesion_solves(egg_handle *h, int64_t *solves) {
+    if (!h) return EGG_ERR_INVALID_ARGUMENT;
+    if (!solves) return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_get_adhesion_solves: solves is NULL");
+    *solves = h->adhesion_solves;
     return EGG_OK;
 }
 

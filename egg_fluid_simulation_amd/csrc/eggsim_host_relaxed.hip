@@ -34,6 +34,10 @@
 // their own streams, so four events order them (built[w], read[w]), and relaxed_step enqueues sub-step by sub-step across
 // both types: a wait on an event that has not been recorded yet waits for nothing.  With the factor zero, or one type
 // empty, a step enqueues and launches what it always did.
+// With white-yolk adhesion acting (egg_set_adhesion, RelaxedLayout::adhesion: coupling, and reach > factor) the same
+// launches run in other instantiations: H covers the band, launch_coupling_tables ranks through the cohesive rank kernel,
+// which leaves the batch tags beside the grouped copies, and launch_coupling runs egg_rx_couple_adh_kernel.  No launch,
+// event or wait is added; with reach <= factor nothing changes at all.
 #include <hipcub/hipcub.hpp>
 
 #include "eggsim_host.h"
@@ -187,6 +191,8 @@ int prepare_type(RelaxedStep &st, int C, size_t ghosts, const RelaxedLayout &L, 
     st.L.V = h->viscosity[st.w] > 0.0 ? L.P / (size_t)C : 0;
     st.L.coupling = !L.halo && h->coupling_factor > 0.0 && h->sys[0].n > 0 && h->sys[1].n > 0;
     st.L.coupled_word = st.L.coupling && st.w == 0;
+    st.L.adhesion = st.L.coupling && h->adhesion_reach > h->coupling_factor;
+    st.L.adhered_word = st.L.adhesion && st.w == 0;
     st.C = C;
     st.ghost_cap = (int64_t)ghosts;
     int rc = reserve_relaxed(h, s, ghosts, st.L.words());
@@ -227,17 +233,22 @@ int prepare_type(RelaxedStep &st, int C, size_t ghosts, const RelaxedLayout &L, 
         st.visc.pairs = r.status.p + st.L.visc();
     }
     if (st.L.coupling) {  // both types share the cell size and the compliance
-        st.couple_cell = std::max(1.0, h->coupling_factor * (h->sys[0].cfg.max_radius + h->sys[1].cfg.max_radius));
+        const double widest = st.L.adhesion ? std::max(h->coupling_factor, h->adhesion_reach) : h->coupling_factor;
+        st.couple_cell = std::max(1.0, widest * (h->sys[0].cfg.max_radius + h->sys[1].cfg.max_radius));
         // a coupling distance is at most H, and the pass squares it: with H H finite nothing in the pair arithmetic overflows
         if (!std::isfinite(st.couple_cell * st.couple_cell))
-            return fail(h, EGG_ERR_INVALID_ARGUMENT, "relaxed order: the coupling cell size %g (factor %g times the two max_radius) has no finite square",
-                        st.couple_cell, h->coupling_factor);
+            return fail(h, EGG_ERR_INVALID_ARGUMENT, "relaxed order: the coupling cell size %g (%s %g times the two max_radius) has no finite square",
+                        st.couple_cell, st.L.adhesion ? "adhesion reach" : "factor", widest);
         const double alpha = 1 - clampd(h->coupling_strength, 0, 1);  // L:1337-1341
         st.couple_c = alpha / (st.env.sub_delta * st.env.sub_delta);
         for (int k = 0; k < 2; ++k) {
             if (!h->couple_built[k]) HIP_TRY(h, hipEventCreateWithFlags(&h->couple_built[k], hipEventDisableTiming));
             if (!h->couple_read[k]) HIP_TRY(h, hipEventCreateWithFlags(&h->couple_read[k], hipEventDisableTiming));
         }
+    }
+    if (st.L.adhesion) {  // the tags share the array of effective cohesion: the table of a coupling pass lives between collision passes
+        HIP_TRY(h, r.stag.reserve(n + ghosts, false, s.stream));
+        st.adhesion_c = (1 - clampd(h->adhesion_strength, 0, 1)) / (st.env.sub_delta * st.env.sub_delta);
     }
     if (!L.halo) return EGG_OK;
     const bool rebuild = r.key_sig != sig || r.ekey.cap < n + ghosts;  // (or a new array)
@@ -429,7 +440,13 @@ int launch_coupling_tables(RelaxedStep &st) {
     size_t bytes = r.scan_bytes;
     HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(r.scan_tmp.p, bytes, r.hcount.p, r.hstart.p, (int)r.table + 1, s.stream));
     hipLaunchKernelGGL(egg_rx_scatter_kernel, grid, block, 0, s.stream, a);
-    hipLaunchKernelGGL(egg_rx_rank_kernel, grid, block, 0, s.stream, a);
+    if (st.L.adhesion) {  // the tag of a grouped slot is its atom index: one number per batch for both types
+        EggRxCohesionFields tags{};
+        tags.stag = r.stag.p;
+        hipLaunchKernelGGL(egg_rx_rank_coh_kernel, grid, block, 0, s.stream, EggRelaxedCohArgs{a, tags});
+    } else {
+        hipLaunchKernelGGL(egg_rx_rank_kernel, grid, block, 0, s.stream, a);
+    }
     st.launches += 4;
     HIP_TRY(h, hipEventRecord(h->couple_built[st.w], s.stream));
     return EGG_OK;
@@ -456,7 +473,18 @@ int launch_coupling(RelaxedStep &st, RelaxedStep &other) {
     k.c.compliance = st.couple_c;
     k.c.eps = h->sys[0].cfg.eps;
     k.c.solves = st.L.coupled_word ? s.rx.status.p + st.L.coupled() : nullptr;
-    hipLaunchKernelGGL(egg_rx_couple_kernel, dim3((unsigned)((s.n + 255) / 256)), dim3(256), 0, s.stream, k);
+    const dim3 grid((unsigned)((s.n + 255) / 256)), block(256);
+    if (st.L.adhesion) {
+        EggRxAdhesionFields d{};
+        d.reach = h->adhesion_reach;
+        d.compliance = st.adhesion_c;
+        d.stag = s.rx.stag.p;
+        d.other_stag = o.stag.p;
+        d.solves = st.L.adhered_word ? s.rx.status.p + st.L.adhered() : nullptr;
+        hipLaunchKernelGGL(egg_rx_couple_adh_kernel, grid, block, 0, s.stream, EggRelaxedCoupleAdhArgs{k.a, k.c, d});
+    } else {
+        hipLaunchKernelGGL(egg_rx_couple_kernel, grid, block, 0, s.stream, k);
+    }
     ++st.launches;
     HIP_TRY(h, hipEventRecord(h->couple_read[st.w], s.stream));
     std::swap(st.A.a.pos, st.A.a.pos_next);
@@ -588,6 +616,7 @@ void relaxed_commit(egg_handle *h, const RelaxedStep st[2], int S, int C, double
         if (st[w].L.surfaces) h->collider_grips[w] += (int64_t)s.rx.h_status.p[st[w].L.grips()];
         if (st[w].L.V) h->viscosity_pairs[w] += (int64_t)s.rx.h_status.p[st[w].L.visc()];
         if (st[w].L.coupled_word) h->coupling_solves += (int64_t)s.rx.h_status.p[st[w].L.coupled()];
+        if (st[w].L.adhered_word) h->adhesion_solves += (int64_t)s.rx.h_status.p[st[w].L.adhered()];
         h->stats.follow_solves += s.n * S;
         // the exact path's host copies of the atoms' cells describe older positions now
         s.aabb_valid = s.aabb_on_device = s.disp_valid = false;

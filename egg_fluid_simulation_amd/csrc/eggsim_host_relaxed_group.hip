@@ -140,6 +140,11 @@ int relaxed_group_step(egg_handle *const *hs, int nh, double delta, int S, int C
             *error = "relaxed order: white-yolk coupling runs on a single handle only (egg_set_coupling with factor 0 first)";
             return EGG_ERR_UNSUPPORTED;
         }
+    for (int k = 0; k < nh; ++k)
+        if (hs[k]->adhesion_reach > 0.0) {  // (a band in the coupling pass, which a group does not run)
+            *error = "relaxed order: white-yolk adhesion runs on a single handle only (egg_set_adhesion with reach 0 first)";
+            return EGG_ERR_UNSUPPORTED;
+        }
     for (int k = 0; k < nh; ++k) {
         (void)hipSetDevice(hs[k]->device);
         GK_TRY(k, prepare_step(hs[k], delta, S, st[k]));

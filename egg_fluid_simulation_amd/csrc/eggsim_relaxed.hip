@@ -58,6 +58,9 @@
 // cross-type pass between its begin / mid kernel and its first collision pass: both types build their table at a shared
 // cell size with the insert, scatter and rank kernels above, and egg_rx_couple_kernel moves every particle by the mean of
 // its pairs with the OTHER type's particles, found in the other type's table.  Nothing of it runs while the factor is zero.
+// With white-yolk adhesion besides (egg_set_adhesion; section 2.7, "Adhesion"; acts while reach > factor) the tables are
+// built at the band's cell size through the cohesive rank kernel, which leaves the batch tags, and the pass runs as
+// egg_rx_couple_adh_kernel: a same-batch cross pair in the band is pulled back to the coupling distance.
 //
 // All arithmetic is IEEE double in the order of the definition: compile with -ffp-contract=off.
 #include <hip/hip_runtime.h>
@@ -665,14 +668,18 @@ extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_visc_kerne
 // white particle, b the yolk one, whichever side evaluates it; the arithmetic is rx_gather's collision correction with
 // min_distance = factor (ra + rb) and the coupling compliance.  The white side counts the pairs that fire, one atomic
 // per wave.  Neighbours are read from grouped copies only; the move is written to pos_next.
-extern "C" __global__ void __launch_bounds__(256) egg_rx_couple_kernel(EggRelaxedCoupleArgs K) {
-    const EggRelaxedArgs &A = K.a;
-    const EggRxCoupleFields &O = K.c;
+// ADH (adhesion acts): a pair that does not couple may adhere -- same batch tag, within reach (ra + rb) -- and then runs
+// the same arithmetic with the adhesion compliance: the target stays min_distance, so the pair is pulled together, never
+// closer than the coupling distance.  A pair fires at most one of the two; the white side counts each kind in its own word.
+template <bool ADH>
+__device__ __forceinline__ void rx_couple(EggRelaxedArgs A, EggRxCoupleFields O, EggRxAdhesionFields Ad) {
     const int t = (int)(blockIdx.x * 256 + threadIdx.x);
     int solves = 0;
+    int adhered = 0;  // (ADH only)
     if (t < A.n) {
         const int i = A.sidx[t];
         const double2 p = A.spos[t], wr = A.swr[t];
+        const int32_t tag = ADH ? Ad.stag[t] : 0;
         const bool first = O.white_is_self != 0;
         int32_t cx, cy;
         (void)rx_cell(p, A.cell_size, cx, cy);  // (a bad cell was flagged by the insert kernel)
@@ -697,10 +704,19 @@ extern "C" __global__ void __launch_bounds__(256) egg_rx_couple_kernel(EggRelaxe
                     const double dx = pb.x - pa.x, dy = pb.y - pa.y;
                     const double d2 = dx * dx + dy * dy;
                     const double min_distance = O.factor * (ra + rb);
-                    if (!(d2 <= min_distance * min_distance)) continue;
+                    bool adheres = false;
+                    if (!(d2 <= min_distance * min_distance)) {
+                        if (!ADH) continue;
+                        const double reach = Ad.reach * (ra + rb);
+                        if (!(Ad.other_stag[e] == tag && d2 <= reach * reach)) continue;
+                        adheres = true;  // adhesion: back to the coupling distance, never closer
+                    }
                     ++n_fired;
-                    solves += first ? 1 : 0;
-                    const double divisor = wsum + O.compliance;
+                    if (ADH && adheres)
+                        adhered += first ? 1 : 0;
+                    else
+                        solves += first ? 1 : 0;
+                    const double divisor = wsum + (ADH && adheres ? Ad.compliance : O.compliance);
                     if (divisor < O.eps) {
                         sx = sx + 0.0;
                         sy = sy + 0.0;
@@ -745,8 +761,16 @@ extern "C" __global__ void __launch_bounds__(256) egg_rx_couple_kernel(EggRelaxe
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) solves += __shfl_xor(solves, d, 64);
         if ((threadIdx.x & 63) == 0 && solves) atomicAdd(O.solves, (unsigned long long)solves);
+        if (ADH) {
+#pragma unroll
+            for (int d = 32; d >= 1; d >>= 1) adhered += __shfl_xor(adhered, d, 64);
+            if ((threadIdx.x & 63) == 0 && adhered) atomicAdd(Ad.solves, (unsigned long long)adhered);
+        }
     }
 }
+
+extern "C" __global__ void __launch_bounds__(256) egg_rx_couple_kernel(EggRelaxedCoupleArgs K) { rx_couple<false>(K.a, K.c, EggRxAdhesionFields{}); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_couple_adh_kernel(EggRelaxedCoupleAdhArgs K) { rx_couple<true>(K.a, K.c, K.d); }
 
 // ---- device groups ----
 

@@ -84,6 +84,9 @@ int egg_get_viscosity_pairs(egg_handle *h, int64_t pairs[2]);
 int egg_set_coupling(egg_handle *h, double factor, double strength);
 int egg_get_coupling(const egg_handle *h, double *factor, double *strength);
 int egg_get_coupling_solves(egg_handle *h, int64_t *solves);
+int egg_set_adhesion(egg_handle *h, double reach, double strength);
+int egg_get_adhesion(const egg_handle *h, double *reach, double *strength);
+int egg_get_adhesion_solves(egg_handle *h, int64_t *solves);
 typedef struct { double friction; double vx, vy; } egg_collider_surface;
 int egg_set_collider_surfaces(egg_handle *h, int32_t n, const egg_collider_surface *s);
 int egg_get_collider_surfaces(const egg_handle *h, int32_t cap, egg_collider_surface *s, int32_t *n);
@@ -593,6 +596,30 @@ end
 function SimulationHandler:coupling_solves()
     local n = ffi.new("int64_t[1]")
     self:_check(lib.egg_get_coupling_solves(self._h, n))
+    return tonumber(n[0])
+end
+
+-- White-yolk adhesion, the same-batch band of the coupling pass (egg_set_adhesion in include/eggsim.h; DESIGN.md section
+-- 2.7, "Adhesion").  Relaxed order, one handle only.
+
+--- reach >= 0 (0, the default, = off) and strength in [0, 1] (default 1): while coupling acts and reach > its factor, a
+--- white and a yolk particle of one batch farther apart than factor * (ra + rb) but within reach * (ra + rb) are pulled
+--- back to the coupling distance, never closer
+function SimulationHandler:set_adhesion(reach, strength)
+    self:_check(lib.egg_set_adhesion(self._h, reach or 0, strength or 1))
+end
+
+--- reach, strength: as stored
+function SimulationHandler:adhesion()
+    local r, s = ffi.new("double[1]"), ffi.new("double[1]")
+    self:_check(lib.egg_get_adhesion(self._h, r, s))
+    return r[0], s[0]
+end
+
+--- distinct white-yolk pairs whose adhesion branch fired over the coupling passes of committed steps
+function SimulationHandler:adhesion_solves()
+    local n = ffi.new("int64_t[1]")
+    self:_check(lib.egg_get_adhesion_solves(self._h, n))
     return tonumber(n[0])
 end
 

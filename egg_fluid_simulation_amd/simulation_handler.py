@@ -340,6 +340,39 @@ class _HandlerSurface:
     def coupling_solves(self):
         return 0
 
+    # ------------------------------------------------ white-yolk adhesion (egg_set_adhesion)
+    _ADHESION_LIMIT = ("adhesion: white-yolk adhesion is a band in the coupling pass, which runs on a single "
+                       "SimulationHandler only; only reach 0 (off) is accepted here")
+
+    @staticmethod
+    def _c_adhesion(reach, strength):
+        """(reach, strength) as the doubles egg_set_adhesion takes; the ranges are checked here as the library checks them"""
+        out = []
+        for name, v in (("reach", reach), ("strength", strength)):
+            try:
+                out.append(float(v))
+            except (TypeError, ValueError):
+                raise EggError("adhesion: the %s must be a number, not %r" % (name, v)) from None
+        if not (0.0 <= out[0] < float("inf")):  # (false for a NaN)
+            raise EggError("adhesion: the reach %r is not a finite number >= 0" % (out[0],))
+        if not (0.0 <= out[1] <= 1.0):
+            raise EggError("adhesion: the strength %r lies outside [0, 1]" % (out[1],))
+        return out[0], out[1]
+
+    def set_adhesion(self, reach=0.0, strength=1.0):
+        """SimulationHandler.set_adhesion where several handles share a step (SimulationGroup, ShardedSimulationHandler):
+        reach 0 is accepted and changes nothing, anything else raises EggError naming the limit (after the range check)."""
+        reach, strength = self._c_adhesion(reach, strength)
+        if reach != 0.0:
+            raise EggError(self._ADHESION_LIMIT)
+
+    def adhesion(self):
+        """(reach, strength): always (0.0, 1.0) here, see set_adhesion"""
+        return (0.0, 1.0)
+
+    def adhesion_solves(self):
+        return 0
+
     def _init_host_state(self, white_config, yolk_config):
         """config tables (validated like the reference, L:1253-1320), hidden constants and render switches; no device"""
         if white_config is None and yolk_config is None:
@@ -766,6 +799,29 @@ class SimulationHandler(_HandlerSurface):
         """distinct white-yolk pairs that fired over the coupling passes of committed steps, since creation"""
         n = C.c_int64()
         self._check(self._c("get_coupling_solves")(C.byref(n)))
+        return int(n.value)
+
+    def set_adhesion(self, reach=0.0, strength=1.0):
+        """White-yolk adhesion: a same-batch band in the coupling pass ("Adhesion"; relaxed order
+        only).  It acts while coupling acts and reach > the coupling factor: a white and a yolk particle of one batch
+        farther apart than factor * (ra + rb) but within reach * (ra + rb) are pulled back to the coupling distance,
+        never closer, with the coupling correction's arithmetic and the compliance of `strength` in [0, 1]; reach 0 = off.
+        reach > 0 while coupling is off is accepted and does nothing.  Raises EggError for a NaN, negative or infinite
+        reach or a strength outside [0, 1] (nothing changes) and for reach > 0 on a handle in exact order;
+        set_solver_order("exact") raises while reach > 0."""
+        reach, strength = self._c_adhesion(reach, strength)  # (refused here before any device call)
+        self._check(self._c("set_adhesion")(reach, strength))
+
+    def adhesion(self):
+        """(reach, strength) as stored"""
+        r, s = C.c_double(), C.c_double()
+        self._check(self._c("get_adhesion")(C.byref(r), C.byref(s)))
+        return (r.value, s.value)
+
+    def adhesion_solves(self):
+        """distinct white-yolk pairs whose adhesion branch fired over the coupling passes of committed steps"""
+        n = C.c_int64()
+        self._check(self._c("get_adhesion_solves")(C.byref(n)))
         return int(n.value)
 
     def add_many(self, xs, ys, white_radius=None, yolk_radius=None, white_n_particles=None,

@@ -576,6 +576,38 @@ int egg_set_coupling(egg_handle *h, double factor, double strength);
 int egg_get_coupling(const egg_handle *h, double *factor, double *strength);
 int egg_get_coupling_solves(egg_handle *h, int64_t *solves);
 
+/* ---- white-yolk adhesion (not in the reference; DESIGN.md section 2.7, "Adhesion") ----
+ * An option of its own beside coupling: a same-batch BAND in the coupling pass, which pulls a yolk back to its white the way
+ * effective cohesion holds one type's batch together.  A handle holds two more doubles: `reach` (finite, >= 0; 0, the
+ * default, = off) and `strength` in [0, 1] (default 1).  Adhesion ACTS in a relaxed step exactly when all three hold:
+ *   1. coupling acts (its factor > 0 and both types have particles);  2. reach > factor;  3. the solver order is relaxed.
+ * When it does not act -- reach == 0, reach <= factor (an empty band), coupling off, one type empty -- a step launches
+ * the kernels it launched before, with the same arguments, in the same enqueue order.  When it acts, the coupling pass
+ * above changes in three places and nowhere else:
+ *   cells       H = max(1.0, max(factor, reach) (white max_radius + yolk max_radius)): both types' tables and the pass use
+ *               it.  Candidates, visit order and the wsum < eps skip are unchanged; a step whose H H is not finite fails
+ *               with EGG_ERR_INVALID_ARGUMENT before anything is launched.
+ *   pair        (a white, b yolk), md = factor (ra + rb), rd = reach (ra + rb), d2 from the start-of-pass positions:
+ *               d2 <= md md: the coupling correction, exactly as without adhesion.  Otherwise, when a and b belong to the
+ *               same batch and d2 <= rd rd: the adhesion branch -- the same expressions in the same order with the TARGET
+ *               distance md and the compliance (1 - strength) / sub_delta^2 of adhesion's own strength.  divisor < eps:
+ *               zeros; current < eps: zero normal; clamp to +-|violation|.  Here violation > 0: the pair is pulled
+ *               together, and its own correction never brings it closer than md.  A pair fires at most one branch; n_i
+ *               counts fires of either kind; shares add in visit order; the update rule is unchanged.
+ *   same batch  two particles are of the same batch iff the same egg_add (egg_import_batch) created them.
+ * egg_get_adhesion_solves: the distinct cross pairs whose adhesion branch fired, over committed steps (a failed or
+ * discarded step adds nothing); egg_get_coupling_solves keeps counting coupling-branch fires only, and every other counter
+ * is unchanged.
+ * The limits are coupling's.  Relaxed order only: reach > 0 on a handle in exact order is EGG_ERR_UNSUPPORTED, and
+ * EGG_OPT_SOLVER_ORDER = 0 is EGG_ERR_UNSUPPORTED while reach > 0; reach == 0 is always accepted.  reach > 0 with
+ * factor == 0 is accepted and does nothing until coupling is on.  A single handle only: a device group refuses to step and
+ * egg_rx_begin returns EGG_ERR_UNSUPPORTED while reach > 0.  A NaN, negative or infinite reach, or a strength outside
+ * [0, 1], is EGG_ERR_INVALID_ARGUMENT and changes nothing.  Refused while a step is in flight.  While it acts a sub-step
+ * launches as many kernels as with coupling alone: the rank and the couple kernel run in their tagged instantiations. */
+int egg_set_adhesion(egg_handle *h, double reach, double strength);
+int egg_get_adhesion(const egg_handle *h, double *reach, double *strength);
+int egg_get_adhesion_solves(egg_handle *h, int64_t *solves);
+
 /* ---- several GPUs in one process (csrc/eggsim_group.cpp) -------------------------------------------------------
  * The multi-device form of the handle for a host that is ONE process (the LuaJIT wrapper): one egg_handle per device
  * behind one egg_group, x-slabs [cuts[k], cuts[k + 1]) of the plane per device (cuts: n_devices + 1 ascending values;
