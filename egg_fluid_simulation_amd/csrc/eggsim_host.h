@@ -54,6 +54,8 @@ extern "C" __global__ void egg_pk_begin_kernel(EggPackedArgs A);
 extern "C" __global__ void egg_pk_mid_kernel(EggPackedArgs A);
 extern "C" __global__ void egg_pk_lists_fresh_kernel(EggPackedArgs A);
 extern "C" __global__ void egg_pk_lists_stale_kernel(EggPackedArgs A);
+extern "C" __global__ void egg_pk_lists_first_kernel(EggPackedArgs A);
+extern "C" __global__ void egg_pk_lists_stale_mid_kernel(EggPackedArgs A);
 extern "C" __global__ void egg_pk_levels_mr16_kernel(EggPackedArgs A);
 extern "C" __global__ void egg_pk_levels_ooo_kernel(EggPackedArgs A);
 extern "C" __global__ void egg_pk_probe_lds_order_kernel(int trials, unsigned long long *bad);
@@ -408,8 +410,23 @@ struct egg_handle {
     int opt_spread = 0;  // threads per particle: 0 = automatic (3 for tiles that have a CU to themselves), else 1..4
     int opt_spin_sleep = -1;  // -1 auto
     bool packed_auto = false;  // the automatic choice, made when the white tiles are formed
-    int opt_tune = 0;         // EGGSIM_TUNE: developer switches (bit 6: levels, sort and executor as separate launches instead of the fused pass)
+    // EGGSIM_TUNE: developer switches, read at egg_create; 0 in normal operation
+    //   bit 6 (64):  levels, sort and executor as separate launches instead of the fused pass
+    //   bit 7 (128): egg_pk_begin_kernel / egg_pk_mid_kernel as launches of their own and the per-step memset of the
+    //                atoms' claim flags, instead of the folded first list pass of every sub-step
+    int opt_tune = 0;
+    int opt_lists_threads[2] = {0, 0};  // EGGSIM_LISTS_THREADS="fresh,stale": threads of the list kernels' workgroups, 0 = retile()'s choice
     int opt_level_walk = 0;   // packed pipeline, EGG_OPT_LEVEL_WALK: 0 by regime, 1 always in order, 2 out of order wherever the probe allows
+    // workgroups of a list kernel a compute unit really admits (registers included), as the runtime reports it for
+    // (kernel, threads, dynamic LDS): asked when tiles are formed, once per combination
+    struct PkResidency {
+        const void *kernel;
+        int threads;
+        size_t lds;
+        int blocks;
+    };
+    std::vector<PkResidency> pk_residency;  // (blocks 0: the runtime gave no answer)
+    bool pk_residency_warned = false;
     DevBuf<uint32_t> simd_claims;   // egg_pk_levexec_kernel: which SIMDs of a compute unit run an executor wave (zero between launches)
     bool lds_lane_ordered = false;  // one ds_add_rtn serves same-address lanes in ascending lane order (probed at create)
     int opt_packed = -1;      // packed pipeline: -1 automatic (large scenes), 0 never, 1 every eligible class

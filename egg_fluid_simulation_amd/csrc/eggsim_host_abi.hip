@@ -85,6 +85,7 @@ int egg_create(const egg_config *white, const egg_config *yolk, int device, egg_
             e = hipFuncSetAttribute((const void *)egg_step_kernel_gl_mg, hipFuncAttributeMaxDynamicSharedMemorySize, (int)want);
         if (e == hipSuccess)
             for (const void *f : {(const void *)egg_pk_lists_fresh_kernel, (const void *)egg_pk_lists_stale_kernel,
+                                  (const void *)egg_pk_lists_first_kernel, (const void *)egg_pk_lists_stale_mid_kernel,
                                   (const void *)egg_pk_exec_kernel, (const void *)egg_pk_exec_chain_kernel,
                                   (const void *)egg_pk_levexec_kernel,
                                   (const void *)egg_pk_sort_kernel, (const void *)egg_pk_levels_mr16_kernel,
@@ -98,6 +99,8 @@ int egg_create(const egg_config *white, const egg_config *yolk, int device, egg_
     (void)hipGetLastError();
     if (const char *e_pk = getenv("EGGSIM_PACKED")) h->opt_packed = atoi(e_pk);  // developer / test override of EGG_OPT_PACKED
     if (const char *e_tn = getenv("EGGSIM_TUNE")) h->opt_tune = atoi(e_tn);
+    if (const char *e_lt = getenv("EGGSIM_LISTS_THREADS"))
+        if (sscanf(e_lt, "%d,%d", &h->opt_lists_threads[0], &h->opt_lists_threads[1]) != 2) h->opt_lists_threads[0] = h->opt_lists_threads[1] = 0;
     if (const char *e_lw = getenv("EGGSIM_LEVEL_WALK")) h->opt_level_walk = std::min(2, std::max(0, atoi(e_lw)));  // developer / test override of EGG_OPT_LEVEL_WALK
     {
         // egg_pk_levels_ooo_kernel ranks the entries of a pair stream with one LDS atomic add per batch and relies on the

@@ -274,19 +274,27 @@ int launch_packed(egg_handle *h, int which, const Env &env, int S, int C) {
         launch_all(-1, [](const PackedClass &) { return egg_pk_plan_kernel; }, tiles_of, c64, no_lds);
         s.pk_plan_dirty = false;
     }
-    launch_all(EGG_PK_KIND_BEGIN, [](const PackedClass &) { return egg_pk_begin_kernel; }, flat_grid, c256, no_lds);
+    // The first list pass of a sub-step does the per-particle work in front of it itself (egg_pk_lists_first_kernel,
+    // egg_pk_lists_stale_mid_kernel); EGGSIM_TUNE bit 7 keeps the launches of their own.
+    const bool fold = !(h->opt_tune & 128);
+    if (!fold) launch_all(EGG_PK_KIND_BEGIN, [](const PackedClass &) { return egg_pk_begin_kernel; }, flat_grid, c256, no_lds);
     int pass_seq = 0;
     for (int sub = 0; sub < S; ++sub) {
-        if (sub > 0) launch_all(EGG_PK_KIND_MID, [](const PackedClass &) { return egg_pk_mid_kernel; }, flat_grid, c256, no_lds);
+        if (sub > 0 && !fold) launch_all(EGG_PK_KIND_MID, [](const PackedClass &) { return egg_pk_mid_kernel; }, flat_grid, c256, no_lds);
         for (int c = 0; c < C; ++c, ++pass_seq) {
             const bool stale = c == 0 && sub > 0;  // hash lists and `collided` survive a sub-step boundary (L:1905-1912)
+            const bool folded = fold && c == 0;    // (a later sub-step's first pass is the stale one)
             for (EggPackedArgs &A : args) {
                 A.pass_seq = pass_seq;
                 A.substep = sub;
                 A.stale = stale ? 1 : 0;
             }
             launch_some(0, stale ? EGG_PK_KIND_LISTS_STALE : EGG_PK_KIND_LISTS_FRESH,
-                        [&](const PackedClass &) { return stale ? egg_pk_lists_stale_kernel : egg_pk_lists_fresh_kernel; }, tiles_of,
+                        [&](const PackedClass &) {
+                            return stale ? (folded ? egg_pk_lists_stale_mid_kernel : egg_pk_lists_stale_kernel)
+                                         : (folded ? egg_pk_lists_first_kernel : egg_pk_lists_fresh_kernel);
+                        },
+                        tiles_of,
                         [stale](const PackedClass &pc) { return stale ? pc.threads_lists_stale : pc.threads_lists; },
                         [stale](const PackedClass &pc) { return stale ? pc.lds_lists_stale : pc.lds_lists; });
             launch_some(1, EGG_PK_KIND_LEVELS, [](const PackedClass &pc) { return pc.levels_ooo ? egg_pk_levels_ooo_kernel : egg_pk_levels_mr16_kernel; },
@@ -337,9 +345,10 @@ int launch_type(egg_handle *h, int which, const Env &env, int S, int C) {
     if (rc != EGG_OK) return rc;
     s.timing_from = which;
     if (h->opt_timing) HIP_TRY(h, hipEventRecord(s.ev0, s.stream));
-    // per-atom "left its claim" flags of the step: the packed pipeline's kernels only ever set them (tiles of the
-    // fused kernels reset their own atoms' flags themselves)
-    if (!s.pk.empty()) HIP_TRY(h, hipMemsetAsync(s.d_atom_fail.p, 0, s.atoms.size() * sizeof(int32_t), s.stream));
+    // per-atom "left its claim" flags of the step: every tile resets its own atoms' flags when it starts -- the fused
+    // kernels' and, in the step's first list pass, the packed pipeline's.  With egg_pk_begin_kernel as a launch of its
+    // own (EGGSIM_TUNE bit 7) the packed kernels only ever set them.
+    if (!s.pk.empty() && (h->opt_tune & 128)) HIP_TRY(h, hipMemsetAsync(s.d_atom_fail.p, 0, s.atoms.size() * sizeof(int32_t), s.stream));
     for (const LaunchClass &lc : s.classes) {
         if (lc.packed >= 0) continue;  // stepped by the packed pipeline below
         EggStepArgs A;

@@ -24,6 +24,36 @@ struct RetileLap {
     }
 };
 
+// Workgroups of `kernel` that the runtime admits per compute unit at (threads, dynamic LDS) -- its answer knows the
+// kernel's registers, which the LDS / wave model of the packed classes does not.  Asked once per combination and
+// handle.  No answer: SIZE_MAX (the caller is left with its model), said once on stderr -- a register-blind model is how
+// the list kernels came to run three workgroups per unit where four were planned.
+static size_t pk_admitted_blocks(egg_handle *h, const void *kernel, int threads, size_t lds) {
+    for (const egg_handle::PkResidency &r : h->pk_residency)
+        if (r.kernel == kernel && r.threads == threads && r.lds == lds) return r.blocks > 0 ? (size_t)r.blocks : SIZE_MAX;
+    int blocks = 0;
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, kernel, threads, lds);
+    if (e != hipSuccess || blocks <= 0) {
+        (void)hipGetLastError();
+        blocks = 0;
+        if (!h->pk_residency_warned)
+            fprintf(stderr, "eggsim: no residency answer for a list kernel at %d threads, %zu B LDS (%s): thread counts are chosen by the LDS / wave model alone\n",
+                    threads, lds, hipGetErrorString(e));
+        h->pk_residency_warned = true;
+    }
+    h->pk_residency.push_back({kernel, threads, lds, blocks});
+    return blocks > 0 ? (size_t)blocks : SIZE_MAX;
+}
+
+// the list kernels that run a pass with `gens` cell generations (1: fresh, 2: stale) in a step of this handle
+static size_t pk_lists_admitted(egg_handle *h, int gens, int threads, size_t lds) {
+    const bool fold = !(h->opt_tune & 128);
+    if (gens == 2)  // (the stale pass is the first of its sub-step: the folded kernel whenever there is one)
+        return pk_admitted_blocks(h, fold ? (const void *)egg_pk_lists_stale_mid_kernel : (const void *)egg_pk_lists_stale_kernel, threads, lds);
+    const size_t plain = pk_admitted_blocks(h, (const void *)egg_pk_lists_fresh_kernel, threads, lds);
+    return fold ? std::min(plain, pk_admitted_blocks(h, (const void *)egg_pk_lists_first_kernel, threads, lds)) : plain;
+}
+
 int retile(egg_handle *h, int which) {
     System &s = h->sys[which];
     RetileLap lap;
@@ -428,11 +458,15 @@ int retile(egg_handle *h, int which) {
             pc.scap = lc.lcap;
             pc.threads_lists = pc.threads_lists_stale = egg_step_threads(lc.nmax, 1);
             // the counting pass keeps up to stage_cap partners per particle in LDS as long as that does not cost a
-            // resident tile per CU (residency: LDS and the 32-wave limit); sized by the stale pass, which holds two cell generations
+            // resident tile per CU (residency: LDS, the 32-wave limit and the kernels' registers); sized by the stale pass, which holds two cell generations
+            // (what the runtime admits: the smaller of the LDS / wave model and its own answer for the kernels of the pass,
+            // which knows their registers -- a list kernel with more than 80 scalar registers gets six or seven waves per
+            // SIMD, not eight, and one 8-wave workgroup per CU less than the model says)
             auto tiles_per_cu = [&](int stage, int gens, int threads) {
                 const size_t lds = egg_pk_lists_lds_bytes(lc.nmax, lc.amax, lc.ccap, lc.use_grid, stage, gens);
                 if (lds > h->lds_limit) return (size_t)0;  // (what a workgroup may have is a little less than the CU's 160 KiB)
-                return std::min<size_t>(kLdsMax / std::max<size_t>(lds, 1), (size_t)2048 / (size_t)threads);
+                const size_t model = std::min<size_t>(kLdsMax / std::max<size_t>(lds, 1), (size_t)2048 / (size_t)threads);
+                return std::min(model, pk_lists_admitted(h, gens, threads, lds));
             };
             for (pc.stage_cap = 16; pc.stage_cap > 0; pc.stage_cap -= 2)
                 if (tiles_per_cu(pc.stage_cap, 2, pc.threads_lists) == tiles_per_cu(0, 2, pc.threads_lists)) break;
@@ -442,6 +476,9 @@ int retile(egg_handle *h, int which) {
             // Fewer threads than particles when that saves a whole round of workgroups: 1,024 dense tiles of 628 particles at
             // 640 threads are three to a CU (32 waves), i.e. two rounds on 256 CUs; at 512 threads four fit -- if the LDS
             // allows -- and one round of workgroups 1.5 x as long wins.  (Cost model: rounds x (1 + particles per thread) / 2.)
+            // Timed again with the residency the runtime reports (profiles/r19_pass_seams.md; config 3, ms per step): the five
+            // fresh passes at 512 / 576 / 640 threads 0.21 / 0.27 / 0.25, the stale pass at 512 / 576 / 640 threads 0.122 /
+            // 0.115 / 0.101 -- the model's 512 and 640 are the fastest of each.
             for (int kind = 0; kind < 2; ++kind) {
                 const int full = egg_step_threads(lc.nmax, 1);
                 int best = full;
@@ -457,6 +494,14 @@ int retile(egg_handle *h, int which) {
                     }
                 }
                 (kind ? pc.threads_lists_stale : pc.threads_lists) = best;
+            }
+            // developer aid (EGGSIM_LISTS_THREADS="fresh,stale", read at egg_create; scripts/gpu_ab.py lt=fresh:stale): time
+            // other thread counts than the cost model's -- any multiple of 64 up to a thread per particle is a valid launch
+            {
+                const int full = egg_step_threads(lc.nmax, 1);
+                auto valid = [&](int t) { return t >= 64 && t <= full && t % 64 == 0; };
+                if (valid(h->opt_lists_threads[0])) pc.threads_lists = h->opt_lists_threads[0];
+                if (valid(h->opt_lists_threads[1])) pc.threads_lists_stale = h->opt_lists_threads[1];
             }
             const size_t meta_mark = s.pk_meta_host.size();
             pc.p_begin = s.pk_n;
@@ -480,6 +525,11 @@ int retile(egg_handle *h, int which) {
                     hx = std::max(hx, c.hi_x);
                     hy = std::max(hy, c.hi_y);
                 }
+                // (the list kernels clip a tile to the class's LDS geometry; the folded first pass is the only one to write a
+                // particle's packed position, so a clipped tile would leave particles unstepped)
+                if (tiles[gt].particles > lc.nmax || a1 - a0 > lc.amax)
+                    return fail(h, EGG_ERR_INTERNAL, "packed class: a tile of %lld particles / %d atoms in a class sized for %d / %d",
+                                (long long)tiles[gt].particles, a1 - a0, lc.nmax, lc.amax);
                 tile_first_particle[(size_t)t] = pn;
                 const int32_t rec[8] = {pn, (int32_t)tiles[gt].particles, a0, a1 - a0, lx - 2, ly - 2,
                                         (int32_t)std::min<int64_t>((int64_t)hx - lx + 4, 65535), (int32_t)std::min<int64_t>((int64_t)hy - ly + 4, 65535)};

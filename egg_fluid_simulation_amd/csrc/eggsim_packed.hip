@@ -22,8 +22,10 @@
 //                  a pair lies in a lower level, so any order inside a level gives the sequential result
 //                  bit for bit; one wave's LDS operations execute in issue order, so no barrier is needed.
 //
-// Around the passes: egg_pk_begin (gather into packed order + pre-solve + follow of the first sub-step,
-// L:1393-1471), egg_pk_mid (post-solve of a sub-step + pre-solve + follow of the next), egg_pk_end
+// Around the passes: the work of egg_pk_begin (gather into packed order + pre-solve + follow of the first sub-step,
+// L:1393-1471) and egg_pk_mid (post-solve of a sub-step + pre-solve + follow of the next) is done by the first list
+// pass of each sub-step (egg_pk_lists_first_kernel, egg_pk_lists_stale_mid_kernel; the two are launches of their own
+// only under EGGSIM_TUNE bit 7), egg_pk_end
 // (post-solve, L:1690-1693, scatter back to particle order, per-atom cell boxes / travel), egg_pk_reduce
 // (per-pass visit counts and slack: one atomic per launch instead of one per tile).
 //
@@ -253,7 +255,10 @@ extern "C" __global__ void __launch_bounds__(256) egg_pk_mid_kernel(EggPackedArg
 
 // ------------------------------------------------------------------------------------------------
 // One collision pass, phase 1: spatial hash + visit lists of a tile.
-template <bool STALE>
+// FOLD: the pass is the first of its sub-step and does, per particle of its tile, what the launch in front of it would
+// (FOLD && !STALE: the first pass of the step, egg_pk_begin_kernel's work; FOLD && STALE: egg_pk_mid_kernel's) -- the
+// positions then make no round trip through memory between the two, and a step has two launches less.
+template <bool STALE, bool FOLD>
 __device__ __forceinline__ void egg_pk_lists_body(const EggPackedArgs &A, const int tile) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int tid = threadIdx.x, nthreads = blockDim.x;
@@ -319,10 +324,51 @@ __device__ __forceinline__ void egg_pk_lists_body(const EggPackedArgs &A, const 
     const int cur = 0, prev = 1;  // LDS generation buffers of this launch
     uint32_t *g_ckey_cur = A.pk_ckey + (size_t)(A.substep & 1) * A.pk_stride + p0;
     const uint32_t *g_ckey_prev = A.pk_ckey + (size_t)((A.substep + 1) & 1) * A.pk_stride + p0;
-    const double2 first_pos = ((const double2 *)A.pk_pos)[p0 + min(tid, max(n - 1, 0))];  // (requested now, used after the next barrier)
+    double2 first_pos = make_double2(0.0, 0.0);  // this thread's first particle (requested now, used after the next barrier)
+    if (!FOLD) first_pos = ((const double2 *)A.pk_pos)[p0 + min(tid, max(n - 1, 0))];
     for (int i = tid; i < n; i += nthreads) {
         t.aslot[i] = A.pk_aslot[p0 + i];
         if (STALE) t.ckey(prev)[i] = g_ckey_prev[i];
+    }
+    bool mine_fast = A.collision_compliance <= 0x1p298;
+    if (FOLD) {
+        if (!STALE) {
+            // the step starts here: the "left its claim" flags of this tile's atoms (set below, by this workgroup only, behind
+            // the next barrier), and -- one workgroup of the class -- the other status block, which nothing touches while
+            // this step runs
+            for (int k = tid; k < na; k += nthreads) A.atom_fail[A.tile_atoms[a_begin + k]] = 0;
+            if (tile == 0 && A.status_next) {
+                unsigned long long *q = (unsigned long long *)A.status_next;
+                for (int w = tid; w < (int)(sizeof(EggStatus) / 8); w += nthreads) q[w] = 0ull;
+                __syncthreads();
+                if (tid == 0) A.status_next->min_slack = 0x7FFFFFFF;
+            }
+        }
+        // pre-solve + follow of the sub-step for every particle of the tile (a thread may own more than one); the cells
+        // below take this thread's first position from the register and any further one from what it stored here
+        for (int i = tid; i < n; i += nthreads) {
+            const int p = p0 + i, atom = A.pk_atom[p];
+            double2 ps, v, out;
+            double im;
+            if (!STALE) {  // gather into packed order (egg_pk_begin_kernel)
+                const int g = A.pk_src[p];
+                ps = make_double2(A.x_in[g], A.y_in[g]);
+                v = make_double2(A.vx_in[g], A.vy_in[g]);
+                const double2 wr = make_double2(A.inv_mass[g], A.radius[g]);
+                im = wr.x;
+                ((double2 *)A.pk_wr)[p] = wr;
+                mine_fast = mine_fast && (wr.x >= A.eps * 0.5) && (wr.x <= 0x1p298) && (fabs(A.overlap_factor * wr.y) <= 0x1p298);
+            } else {  // post-solve of the sub-step that ended (egg_pk_mid_kernel)
+                ps = ((const double2 *)A.pk_pos)[p];
+                const double2 pv = ((const double2 *)A.pk_prev)[p];
+                v = make_double2((ps.x - pv.x) / A.sub_delta, (ps.y - pv.y) / A.sub_delta);
+                im = ((const double2 *)A.pk_wr)[p].x;
+            }
+            egg_pre_follow(A.damping, A.sub_delta, A.eps, A.follow_compliance, ps, v, im, A.atom_tx[atom], A.atom_ty[atom], A.atom_fd[atom], out);
+            ((double2 *)A.pk_prev)[p] = ps;
+            ((double2 *)A.pk_pos)[p] = out;
+            if (i == tid) first_pos = out;
+        }
     }
     // Can every pair of this tile take the hand-expanded arithmetic (pair_needs_reference false for all of them)?
     // Sufficient per particle: eps / 2 <= w <= 2^298 and |overlap * r| <= 2^298, with the compliance <= 2^298: then
@@ -331,12 +377,12 @@ __device__ __forceinline__ void egg_pk_lists_body(const EggPackedArgs &A, const 
     // (masses and radii do not change inside a step: the first list pass of the step decides, the later ones read the
     // answer -- the test costs a 16-byte load per particle, as much as the positions)
     bool all_fast;
-    if (A.pass_seq == 0) {
-        bool mine_fast = A.collision_compliance <= 0x1p298;
-        for (int i = tid; i < n; i += nthreads) {
-            const double2 w = ((const double2 *)A.pk_wr)[p0 + i];
-            mine_fast = mine_fast && (w.x >= A.eps * 0.5) && (w.x <= 0x1p298) && (fabs(A.overlap_factor * w.y) <= 0x1p298);
-        }
+    if ((FOLD && !STALE) || A.pass_seq == 0) {
+        if (!(FOLD && !STALE))  // (the folded first pass has just had every (inverse mass, radius) in its hands)
+            for (int i = tid; i < n; i += nthreads) {
+                const double2 w = ((const double2 *)A.pk_wr)[p0 + i];
+                mine_fast = mine_fast && (w.x >= A.eps * 0.5) && (w.x <= 0x1p298) && (fabs(A.overlap_factor * w.y) <= 0x1p298);
+            }
         all_fast = __syncthreads_and(mine_fast) != 0;
         if (tid == 0) A.tile_fast[tile] = all_fast ? 1 : 0;
     } else {
@@ -486,8 +532,15 @@ __device__ __forceinline__ void egg_pk_lists_body(const EggPackedArgs &A, const 
             (fits && !any_bad) ? total - (int)gsum : 0;
     }
 }
-extern "C" __global__ void __launch_bounds__(1024) egg_pk_lists_fresh_kernel(EggPackedArgs A) { egg_pk_lists_body<false>(A, blockIdx.x); }
-extern "C" __global__ void __launch_bounds__(1024) egg_pk_lists_stale_kernel(EggPackedArgs A) { egg_pk_lists_body<true>(A, blockIdx.x); }
+// (72 scalar registers: with the 106 the compiler takes when left alone a SIMD admits six waves, not eight, and a
+// compute unit three 8-wave workgroups, not the four the host counts on -- see the residency query in retile())
+#define EGG_PK_LISTS_KERNEL extern "C" __global__ void __launch_bounds__(1024) __attribute__((amdgpu_num_sgpr(72)))
+EGG_PK_LISTS_KERNEL egg_pk_lists_fresh_kernel(EggPackedArgs A) { egg_pk_lists_body<false, false>(A, blockIdx.x); }
+EGG_PK_LISTS_KERNEL egg_pk_lists_stale_kernel(EggPackedArgs A) { egg_pk_lists_body<true, false>(A, blockIdx.x); }
+// the first pass of a step (with the work of egg_pk_begin_kernel) and the first pass of a later sub-step (always stale;
+// with the work of egg_pk_mid_kernel); symbols of their own, so that the other passes' code stays what it is
+EGG_PK_LISTS_KERNEL egg_pk_lists_first_kernel(EggPackedArgs A) { egg_pk_lists_body<false, true>(A, blockIdx.x); }
+EGG_PK_LISTS_KERNEL egg_pk_lists_stale_mid_kernel(EggPackedArgs A) { egg_pk_lists_body<true, true>(A, blockIdx.x); }
 
 // ------------------------------------------------------------------------------------------------
 // Phase 2: levels.

@@ -4,7 +4,8 @@
     python scripts/gpu_ab.py --batches 16384 --overlap 1 --variants walk=0 walk=2
 
 A variant is a comma-separated list of key=value: walk (EGG_OPT_LEVEL_WALK), packed (EGG_OPT_PACKED), gp
-(EGG_OPT_GROUP_PARTICLES).  Every variant steps its own handler of the same scene; rounds are interleaved; per
+(EGG_OPT_GROUP_PARTICLES), tune (EGGSIM_TUNE, csrc/eggsim_host.h: 64 separate level / sort / executor launches, 128
+separate begin / mid launches and the per-step memset), lt (EGGSIM_LISTS_THREADS as fresh:stale, e.g. lt=576:640).  Every variant steps its own handler of the same scene; rounds are interleaved; per
 variant: wall ms per step, HIP-event ms of the white stream, and the per-kind launch times (EGG_OPT_TIMING = 2, which
 fences the launches of a kind off from each other: read the SHARES, the wall column has its own rounds without it).
 """
@@ -29,6 +30,11 @@ for name in ("OPT_EXEC", "OPT_PASS"):
 def make(args, variant):
     kvs = dict(kv.split("=") for kv in variant.split(",") if kv)
     os.environ["EGGSIM_TUNE"] = kvs.pop("tune", "0")  # (read by egg_create: developer experiments inside the kernels)
+    lt = kvs.pop("lt", None)  # lt=fresh:stale, threads of the list kernels' workgroups (read by egg_create too)
+    if lt:
+        os.environ["EGGSIM_LISTS_THREADS"] = lt.replace(":", ",")
+    else:
+        os.environ.pop("EGGSIM_LISTS_THREADS", None)
     h = SimulationHandler()
     for k, v in kvs.items():
         h.set_option(OPTS[k], float(v))
@@ -84,6 +90,7 @@ def main():
         print("%-24s wall ms/step: median %.3f min %.3f | white stream ms/step %.3f yolk %.3f | levels/pass %s variants %s redo %d host_ms %s" %
               (v, float(np.median(wall[i])), min(wall[i]), float(np.median(kms[i])), float(np.median(kmy[i])), st["max_levels"], st["pk_variants"], st["redo_steps"],
                ["%.2f" % (x / max(1, st["steps"])) for x in st["host_ms"]]))
+        print("    white stream ms/step per round: " + " ".join("%.3f" % x for x in kms[i]) + "  (spread %.3f)" % (max(kms[i]) - min(kms[i])))
         print("    per kind ms/step: " + "  ".join("%s %.3f" % (k.replace("egg_pk_", "").replace("_kernel", ""), t) for k, t in kinds[i].items()))
     ref = [hs[0].download(WHITE, f) for f in ("x", "y")]
     for i in range(1, len(hs)):

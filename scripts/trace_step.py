@@ -1,6 +1,6 @@
 """Developer: from a rocprofv3 kernel trace (csv), the kernel sequence of ONE step per queue: start offset, duration,
-gap to the previous kernel of the same queue.  A step = the kernels between two egg_pk_begin_kernel launches of the
-busiest queue."""
+gap to the previous kernel of the same queue.  A step = the kernels between two launches of its first kernel on the
+busiest queue: egg_pk_lists_first_kernel (the folded first list pass), or egg_pk_begin_kernel under EGGSIM_TUNE bit 7."""
 import collections
 import csv
 import sys
@@ -12,7 +12,7 @@ busy = collections.Counter()
 for s, e, n, q, g in ks:
     busy[q] += e - s
 main_q = busy.most_common(1)[0][0]
-begins = [s for s, e, n, q, g in ks if q == main_q and n.startswith("egg_pk_begin")]
+begins = [s for s, e, n, q, g in ks if q == main_q and n.startswith(("egg_pk_lists_first", "egg_pk_begin"))]
 t0, t1 = begins[which], begins[which + 1]
 print("step of %.3f ms on queue %s" % ((t1 - t0) / 1e6, main_q))
 last_end = {}
