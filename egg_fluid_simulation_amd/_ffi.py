@@ -208,6 +208,12 @@ _SIGNATURES = {
     "egg_set_adhesion": (C.c_int, [C.c_void_p, C.c_double, C.c_double]),
     "egg_get_adhesion": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "egg_get_adhesion_solves": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "egg_set_containment": (C.c_int, [C.c_void_p, C.c_double, C.c_double]),
+    "egg_get_containment": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "egg_get_containment_hits": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "egg_group_set_containment": (C.c_int, [C.c_void_p, C.c_double, C.c_double]),
+    "egg_group_get_containment": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "egg_group_get_containment_hits": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "egg_group_set_viscosity": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "egg_group_get_viscosity": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
     "egg_group_get_viscosity_pairs": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),

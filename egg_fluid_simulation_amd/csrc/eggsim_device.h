@@ -482,6 +482,30 @@ struct EggRelaxedCoupleAdhArgs {
     EggRxAdhesionFields d;
 };
 
+// Yolk containment (egg_set_containment, DESIGN.md section 2.7, "Containment"): a disc around the centroid of a batch's
+// white, of radius L = factor * (RMS distance of the white from its centroid), that no yolk particle of the batch may
+// leave.  Per sub-step egg_rx_contain_sum_kernel summarises every white atom into (cx, cy, L) -- slice `sub` of
+// summary[S][atoms][3] -- in the fixed FP64 order of the rule, and egg_rx_contain_kernel projects the yolk particles of
+// the same atom index back onto the disc.  The atom index is one for both types of a handle (see adhesion above).
+struct EggRxContainSumArgs {
+    const double2 *pos;                  // the white positions that enter the sub-step's first collision pass
+    const int32_t *atom_offset, *atom_count;
+    int32_t n_atoms;
+    double factor;
+    double *summary;                     // [n_atoms][3] of this sub-step: cx, cy, L
+};
+struct EggRxContainArgs {
+    double2 *pos;                        // the yolk positions that enter the sub-step's first collision pass, rewritten in place
+    const int32_t *p_atom;
+    int32_t n;
+    double strength;
+    const double *summary;               // [n_atoms][3] of this sub-step
+    unsigned long long *hits;            // one word: projections of this step
+    // group only: the cell box of the sub-step's first pass (4 words, filled by the begin / mid kernel), the cell size
+    unsigned long long *box;
+    double cell_size;
+};
+
 // A ghost record: a particle of a sender j that lies within one cell of a receiver k's cell box (40 bytes).  In a viscosity
 // pass the two words inv_mass and radius carry u.x and u.y instead (the receiver's unpack copies them as they are).
 struct EggGhost {

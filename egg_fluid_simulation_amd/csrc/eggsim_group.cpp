@@ -67,6 +67,7 @@ struct egg_group {
     std::vector<egg_collider_surface> surfaces;  // egg_group_set_collider_surfaces: every handle's records, as given
     std::vector<egg_force> forces;          // egg_group_set_forces: every handle's list, as given
     double viscosity[2] = {0.0, 0.0};       // egg_group_set_viscosity: every handle's coefficients
+    double containment[2] = {0.0, 1.0};     // egg_group_set_containment: every handle's (factor, strength)
     int64_t halo_passes = 0, halo_records = 0;  // relaxed group steps: collision passes, ghost records received
     int64_t steps = 0;  // _step calls committed by the group
     // render attributes (never read by the solver): they live here, per global id / per type, so that a hand-over
@@ -611,6 +612,8 @@ int egg_group_set_solver_order(egg_group *g, int32_t order, double relaxation) {
         return gfail(g, EGG_ERR_UNSUPPORTED, "egg_group_set_solver_order: exact order has no force fields: clear the list first (egg_group_set_forces with n = 0)");
     if (order == EGG_SOLVER_EXACT && (g->viscosity[0] != 0.0 || g->viscosity[1] != 0.0))
         return gfail(g, EGG_ERR_UNSUPPORTED, "egg_group_set_solver_order: exact order has no viscosity: set both coefficients to 0 first (egg_group_set_viscosity)");
+    if (order == EGG_SOLVER_EXACT && g->containment[0] > 0.0)
+        return gfail(g, EGG_ERR_UNSUPPORTED, "egg_group_set_solver_order: exact order has no yolk containment: set the factor to 0 first (egg_group_set_containment)");
     if (order == EGG_SOLVER_RELAXED && g->h.size() > 1) {  // the ghost halo reads the other devices' memory
         std::string err;
         const int rc = egghost::relaxed_group_peers(g->h.data(), (int)g->h.size(), &err);
@@ -752,6 +755,35 @@ int egg_group_get_viscosity_pairs(egg_group *g, int64_t pairs[2]) {
         GTRY(g, k, egg_get_viscosity_pairs(g->h[k], one));
         pairs[0] += one[0];
         pairs[1] += one[1];
+    }
+    return EGG_OK;
+}
+
+int egg_group_set_containment(egg_group *g, double factor, double strength) {
+    if (!g || g->h.empty()) return EGG_ERR_INVALID_ARGUMENT;
+    for (size_t k = 0; k < g->h.size(); ++k) {
+        const int rc = egg_set_containment(g->h[k], factor, strength);
+        if (rc < 0) {  // (handle 0 refuses bad values before any handle has changed; a later one: the others go back)
+            for (size_t j = 0; j < k; ++j) (void)egg_set_containment(g->h[j], g->containment[0], g->containment[1]);
+            return gfail(g, rc, "device %d: %s", (int)k, egg_last_error(g->h[k]));
+        }
+    }
+    return egg_get_containment(g->h[0], &g->containment[0], &g->containment[1]);  // (as stored)
+}
+
+int egg_group_get_containment(const egg_group *g, double *factor, double *strength) {
+    if (!g || g->h.empty()) return EGG_ERR_INVALID_ARGUMENT;
+    return egg_get_containment(g->h[0], factor, strength);  // (every handle holds the same values)
+}
+
+int egg_group_get_containment_hits(egg_group *g, int64_t *hits) {
+    if (!g) return EGG_ERR_INVALID_ARGUMENT;
+    if (!hits) return gfail(g, EGG_ERR_INVALID_ARGUMENT, "egg_group_get_containment_hits: hits is NULL");
+    *hits = 0;
+    for (size_t k = 0; k < g->h.size(); ++k) {
+        int64_t one = 0;
+        GTRY(g, k, egg_get_containment_hits(g->h[k], &one));
+        *hits += one;
     }
     return EGG_OK;
 }

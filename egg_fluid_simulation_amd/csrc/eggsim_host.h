@@ -105,6 +105,9 @@ extern "C" __global__ void egg_rx_rank_group_visc_kernel(EggRelaxedGroupArgs A);
 extern "C" __global__ void egg_rx_gather_visc_kernel(EggRelaxedViscArgs A);
 extern "C" __global__ void egg_rx_couple_kernel(EggRelaxedCoupleArgs K);
 extern "C" __global__ void egg_rx_couple_adh_kernel(EggRelaxedCoupleAdhArgs K);
+extern "C" __global__ void egg_rx_contain_sum_kernel(EggRxContainSumArgs K);
+extern "C" __global__ void egg_rx_contain_kernel(EggRxContainArgs K);
+extern "C" __global__ void egg_rx_contain_group_kernel(EggRxContainArgs K);
 extern "C" __global__ void egg_rx_gather_group_visc_kernel(EggRelaxedGroupViscArgs A);
 extern "C" __global__ void egg_rx_pack_visc_kernel(EggRxPackViscArgs P);
 extern "C" __global__ void egg_rx_wire_pack_visc_kernel(EggRxWirePackViscArgs P);
@@ -468,6 +471,13 @@ struct egg_handle {
     // coupling acts and reach > factor.
     double adhesion_reach = 0.0, adhesion_strength = 1.0;
     int64_t adhesion_solves = 0;
+    // yolk containment (egg_set_containment; relaxed order, every path): the factor of the disc's radius over the RMS
+    // radius of a batch's white, 0 = off, the strength, the projections of committed steps, the summaries of a step
+    // ([S][atoms][3]: cx, cy, L) and one event per sub-step (grown on demand): the white stream has written that slice
+    double containment_factor = 0.0, containment_strength = 1.0;
+    int64_t containment_hits = 0;
+    DevBuf<double> contain_summary;
+    std::vector<hipEvent_t> contain_summed;
     int opt_force_cell_hash = 0;     // test hook: every launch class keys its cells by the LDS hash table, never the dense grid
     int opt_force_global_state = 0;  // test hook: run every tile through the global-memory-state kernel  // threads per particle in the step kernel's workgroups (pair dataflow spreading)
     hipDeviceProp_t prop{};
@@ -613,7 +623,8 @@ constexpr char kRelaxedBadCellText[] = "relaxed order: a position is NaN or its 
 // halo pass P + sub, and one more word, the last, holds the pairs the viscosity passes counted.  V = 0 is the layout
 // without.  With collider surfaces of which one has friction, or with a wall in the list, one more word behind all of
 // these: the grips.  With coupling one more word behind all of these, on the white type only: the cross pairs that fired.
-// While adhesion acts one more behind that one, on the white type only: the cross pairs that adhered.
+// While adhesion acts one more behind that one, on the white type only: the cross pairs that adhered.  While containment
+// acts one more behind that one, the last, on the yolk type only: the projections.
 struct RelaxedLayout {
     size_t P = 0, nq = 0;
     bool halo = false;  // ghosts of other handles' particles take part: the group instantiations of the kernels
@@ -627,6 +638,8 @@ struct RelaxedLayout {
     bool coupled_word = false;  // (set by prepare_type: coupling, and the type is white: it holds the counter word)
     bool adhesion = false;      // (set by prepare_type: coupling, and the handle's adhesion reach exceeds the coupling factor)
     bool adhered_word = false;  // (set by prepare_type: adhesion, and the type is white)
+    bool containment = false;    // (set by prepare_type: the handle's containment factor > 0 and both types populated)
+    bool contained_word = false;  // (set by prepare_type: containment, and the type is yolk: it holds the counter word)
     size_t H() const { return P + V; }                                        // passes with a halo
     size_t box(size_t p) const { return 1 + P + 4 * p; }                      // 4 words
     size_t ghosts(size_t p) const { return 1 + P + 4 * H() + p; }
@@ -637,7 +650,8 @@ struct RelaxedLayout {
     size_t grips() const { return visc() + (V ? 1 : 0); }
     size_t coupled() const { return grips() + (surfaces ? 1 : 0); }
     size_t adhered() const { return coupled() + (coupled_word ? 1 : 0); }
-    size_t words() const { return adhered() + (adhered_word ? 1 : 0); }
+    size_t contained() const { return adhered() + (adhered_word ? 1 : 0); }
+    size_t words() const { return contained() + (contained_word ? 1 : 0); }
 };
 struct RelaxedStep {  // one type of one handle in a relaxed step
     egg_handle *h = nullptr;
@@ -665,6 +679,8 @@ int launch_pass(RelaxedStep &st, int p);
 int launch_viscosity(RelaxedStep &st, int sub);
 int launch_coupling_tables(RelaxedStep &st);
 int launch_coupling(RelaxedStep &st, RelaxedStep &other);
+int launch_contain_sum(RelaxedStep &st_white, int sub);
+int launch_contain(RelaxedStep &st_yolk, RelaxedStep &st_white, int sub);
 int read_status(RelaxedStep &st);
 bool bad_cell(const RelaxedStep &st);
 int launch_end(RelaxedStep &st);

@@ -175,6 +175,7 @@ void egg_destroy(egg_handle *h) {
         if (h->couple_built[w]) (void)hipEventDestroy(h->couple_built[w]);
         if (h->couple_read[w]) (void)hipEventDestroy(h->couple_read[w]);
     }
+    for (hipEvent_t e : h->contain_summed) (void)hipEventDestroy(e);
     delete h;
 }
 
@@ -957,6 +958,8 @@ int egg_set_option(egg_handle *h, int option, double value) {
                 return fail(h, EGG_ERR_UNSUPPORTED, "exact order has no white-yolk coupling: set the factor to 0 first (egg_set_coupling)");
             if (value == EGG_SOLVER_EXACT && h->adhesion_reach > 0.0)
                 return fail(h, EGG_ERR_UNSUPPORTED, "exact order has no white-yolk adhesion: set the reach to 0 first (egg_set_adhesion)");
+            if (value == EGG_SOLVER_EXACT && h->containment_factor > 0.0)
+                return fail(h, EGG_ERR_UNSUPPORTED, "exact order has no yolk containment: set the factor to 0 first (egg_set_containment)");
             if ((int)value != h->opt_solver_order) {
                 if (value == EGG_SOLVER_EXACT) leave_relaxed(h);
                 else
@@ -1258,6 +1261,36 @@ int egg_get_adhesion_solves(egg_handle *h, int64_t *solves) {
     if (!h) return EGG_ERR_INVALID_ARGUMENT;
     if (!solves) return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_get_adhesion_solves: solves is NULL");
     *solves = h->adhesion_solves;
+    return EGG_OK;
+}
+
+// Yolk containment, a disc around the centroid of each batch's white ("Containment").  Everything
+// is checked before anything changes.
+int egg_set_containment(egg_handle *h, double factor, double strength) {
+    if (!h) return EGG_ERR_INVALID_ARGUMENT;
+    REJECT_IN_FLIGHT(h, "egg_set_containment");
+    if (!(factor >= 0.0 && std::isfinite(factor)))
+        return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_containment: the factor %g is not a finite number >= 0", factor);
+    if (!(strength >= 0.0 && strength <= 1.0))
+        return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_containment: the strength %g lies outside [0, 1]", strength);
+    if (factor > 0.0 && h->opt_solver_order != EGG_SOLVER_RELAXED)
+        return fail(h, EGG_ERR_UNSUPPORTED, "egg_set_containment: containment needs relaxed order (EGG_OPT_SOLVER_ORDER = 1 first)");
+    h->containment_factor = factor == 0.0 ? 0.0 : factor;  // (-0.0 is stored as +0.0)
+    h->containment_strength = strength == 0.0 ? 0.0 : strength;
+    return EGG_OK;
+}
+
+int egg_get_containment(const egg_handle *h, double *factor, double *strength) {
+    if (!h || !factor || !strength) return EGG_ERR_INVALID_ARGUMENT;
+    *factor = h->containment_factor;
+    *strength = h->containment_strength;
+    return EGG_OK;
+}
+
+int egg_get_containment_hits(egg_handle *h, int64_t *hits) {
+    if (!h) return EGG_ERR_INVALID_ARGUMENT;
+    if (!hits) return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_get_containment_hits: hits is NULL");
+    *hits = h->containment_hits;
     return EGG_OK;
 }
 

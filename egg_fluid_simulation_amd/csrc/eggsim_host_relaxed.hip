@@ -38,6 +38,13 @@
 // launches run in other instantiations: H covers the band, launch_coupling_tables ranks through the cohesive rank kernel,
 // which leaves the batch tags beside the grouped copies, and launch_coupling runs egg_rx_couple_adh_kernel.  No launch,
 // event or wait is added; with reach <= factor nothing changes at all.
+// With yolk containment acting (egg_set_containment, RelaxedLayout::containment: factor > 0 and both types populated, with
+// or without a halo) every sub-step runs two more launches between the coupling pass (or the begin / mid kernel) and the
+// first collision pass: launch_contain_sum on the white stream writes the sub-step's slice of the handle's summaries and
+// records the sub-step's event, launch_contain on the yolk stream waits for it and projects.  One slice and one event per
+// sub-step: every path enqueues the white's launches of a sub-step before the yolk's, so every event has been recorded
+// on the host before its wait is enqueued, and nothing is written while it may still be read.  With the factor zero, or
+// one type empty, a step enqueues and launches what it always did.
 #include <hipcub/hipcub.hpp>
 
 #include "eggsim_host.h"
@@ -193,6 +200,8 @@ int prepare_type(RelaxedStep &st, int C, size_t ghosts, const RelaxedLayout &L, 
     st.L.coupled_word = st.L.coupling && st.w == 0;
     st.L.adhesion = st.L.coupling && h->adhesion_reach > h->coupling_factor;
     st.L.adhered_word = st.L.adhesion && st.w == 0;
+    st.L.containment = h->containment_factor > 0.0 && h->sys[0].n > 0 && h->sys[1].n > 0;
+    st.L.contained_word = st.L.containment && st.w == 1;
     st.C = C;
     st.ghost_cap = (int64_t)ghosts;
     int rc = reserve_relaxed(h, s, ghosts, st.L.words());
@@ -250,6 +259,8 @@ int prepare_type(RelaxedStep &st, int C, size_t ghosts, const RelaxedLayout &L, 
         HIP_TRY(h, r.stag.reserve(n + ghosts, false, s.stream));
         st.adhesion_c = (1 - clampd(h->adhesion_strength, 0, 1)) / (st.env.sub_delta * st.env.sub_delta);
     }
+    if (st.L.containment)  // one slice of (cx, cy, L) per white atom and sub-step, on the handle (both streams use it)
+        HIP_TRY(h, h->contain_summary.reserve(L.P / (size_t)C * h->sys[0].atoms.size() * 3, false, s.stream));
     if (!L.halo) return EGG_OK;
     const bool rebuild = r.key_sig != sig || r.ekey.cap < n + ghosts;  // (or a new array)
     HIP_TRY(h, r.ekey.reserve(n + ghosts, false, s.stream));
@@ -491,6 +502,56 @@ int launch_coupling(RelaxedStep &st, RelaxedStep &other) {
     return EGG_OK;
 }
 
+// Containment of sub-step `sub`, first half (only with L.containment; st: the white type): the summary of every white
+// atom over the positions that enter the sub-step's first collision pass, into slice `sub`, and the sub-step's event.
+int launch_contain_sum(RelaxedStep &st, int sub) {
+    egg_handle *h = st.h;
+    System &s = h->sys[st.w];
+    const size_t na = s.atoms.size();
+    while (h->contain_summed.size() <= (size_t)sub) {
+        hipEvent_t e = nullptr;
+        HIP_TRY(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        h->contain_summed.push_back(e);
+    }
+    EggRxContainSumArgs k{};
+    k.pos = st.A.a.pos;
+    k.atom_offset = s.d_atom_offset.p;
+    k.atom_count = s.d_atom_count.p;
+    k.n_atoms = (int32_t)na;
+    k.factor = h->containment_factor;
+    k.summary = h->contain_summary.p + (size_t)sub * na * 3;
+    hipLaunchKernelGGL(egg_rx_contain_sum_kernel, dim3((unsigned)((na + 3) / 4)), dim3(256), 0, s.stream, k);
+    ++st.launches;
+    HIP_TRY(h, hipEventRecord(h->contain_summed[(size_t)sub], s.stream));
+    return EGG_OK;
+}
+
+// Second half (st: the yolk type): once the summaries of the sub-step are complete, every yolk particle beyond its batch's
+// disc is projected back, in place.  prev is not touched.  With a halo the cells of the written positions go into the box
+// of the sub-step's first pass, before the caller records ev_box or reads the box.
+int launch_contain(RelaxedStep &st, RelaxedStep &white, int sub) {
+    egg_handle *h = st.h;
+    System &s = h->sys[st.w];
+    HIP_TRY(h, hipStreamWaitEvent(s.stream, h->contain_summed[(size_t)sub], 0));
+    EggRxContainArgs k{};
+    k.pos = st.A.a.pos;
+    k.p_atom = s.rx.p_atom.p;
+    k.n = (int32_t)s.n;
+    k.strength = h->containment_strength;
+    k.summary = h->contain_summary.p + (size_t)sub * h->sys[white.w].atoms.size() * 3;
+    k.hits = s.rx.status.p + st.L.contained();
+    const dim3 grid((unsigned)((s.n + 255) / 256)), block(256);
+    if (st.L.halo) {
+        k.box = s.rx.status.p + st.L.box((size_t)sub * st.C);
+        k.cell_size = st.env.cell;
+        hipLaunchKernelGGL(egg_rx_contain_group_kernel, grid, block, 0, s.stream, k);
+    } else {
+        hipLaunchKernelGGL(egg_rx_contain_kernel, grid, block, 0, s.stream, k);
+    }
+    ++st.launches;
+    return EGG_OK;
+}
+
 // the status words on their way to h_status; bad_cell() reads them once the stream has been waited for
 int read_status(RelaxedStep &st) {
     System &s = st.h->sys[st.w];
@@ -528,7 +589,10 @@ static int relaxed_step_coupled(egg_handle *h, RelaxedStep st[2], int S, int C) 
     for (int sub = 0; sub < S; ++sub) {
         for (int w = 0; w < 2 && rc == EGG_OK; ++w) rc = launch_substep(st[w], sub);
         for (int w = 0; w < 2 && rc == EGG_OK; ++w) rc = launch_coupling_tables(st[w]);
-        for (int w = 0; w < 2 && rc == EGG_OK; ++w) rc = launch_coupling(st[w], st[w ^ 1]);
+        for (int w = 0; w < 2 && rc == EGG_OK; ++w) {
+            rc = launch_coupling(st[w], st[w ^ 1]);
+            if (rc == EGG_OK && st[w].L.containment) rc = w == 0 ? launch_contain_sum(st[0], sub) : launch_contain(st[1], st[0], sub);
+        }
         for (int w = 0; w < 2 && rc == EGG_OK; ++w) {
             HIP_TRY(h, hipStreamWaitEvent(h->sys[w].stream, h->couple_read[w ^ 1], 0));
             for (int c = 0; c < C && rc == EGG_OK; ++c) rc = launch_pass(st[w], sub * C + c);
@@ -559,6 +623,7 @@ int relaxed_step(egg_handle *h, double delta, int S, int C) {  // L:1722-1989, c
         if (h->opt_timing) HIP_TRY(h, hipEventRecord(s.ev0, s.stream));
         for (int sub = 0; sub < S && rc == EGG_OK; ++sub) {
             rc = launch_substep(st[w], sub);
+            if (rc == EGG_OK && st[w].L.containment) rc = w == 0 ? launch_contain_sum(st[0], sub) : launch_contain(st[1], st[0], sub);
             for (int c = 0; c < C && rc == EGG_OK; ++c) rc = launch_pass(st[w], sub * C + c);
             if (rc == EGG_OK && st[w].L.V) rc = launch_viscosity(st[w], sub);
         }
@@ -617,6 +682,7 @@ void relaxed_commit(egg_handle *h, const RelaxedStep st[2], int S, int C, double
         if (st[w].L.V) h->viscosity_pairs[w] += (int64_t)s.rx.h_status.p[st[w].L.visc()];
         if (st[w].L.coupled_word) h->coupling_solves += (int64_t)s.rx.h_status.p[st[w].L.coupled()];
         if (st[w].L.adhered_word) h->adhesion_solves += (int64_t)s.rx.h_status.p[st[w].L.adhered()];
+        if (st[w].L.contained_word) h->containment_hits += (int64_t)s.rx.h_status.p[st[w].L.contained()];
         h->stats.follow_solves += s.n * S;
         // the exact path's host copies of the atoms' cells describe older positions now
         s.aabb_valid = s.aabb_on_device = s.disp_valid = false;

@@ -14,6 +14,8 @@
 // its last collision pass: the box is the one that pass's gather recorded, the pack is egg_rx_pack_visc_kernel (the records
 // carry u = pos - prev where a collision pass's carry inverse mass and radius), the unpack is the same and the pass is
 // launch_viscosity.  The events alternate over the exchanges in the order they run.
+// With containment (egg_set_containment) a handle that holds both types runs the two launches of the driver behind the
+// begin / mid kernel of every sub-step; nothing travels between handles for it.
 // Every event is recorded on the host before any wait on it is enqueued: streams of different handles may share a
 // hardware queue, and a wait must never sit in a queue ahead of the work it waits for.  Pass p + 1's pack waits for
 // the receiver's box of p + 1, which the receiver records after it has read pass p's records: a send buffer is never
@@ -133,6 +135,11 @@ int relaxed_group_step(egg_handle *const *hs, int nh, double delta, int S, int C
     for (int k = 1; k < nh; ++k)
         if (memcmp(hs[0]->viscosity, hs[k]->viscosity, sizeof hs[0]->viscosity) != 0) {  // (a ghost's u travels only when its sender smooths)
             *error = "relaxed order: the handles of the group differ in their viscosity (egg_group_set_viscosity sets all)";
+            return EGG_ERR_INVALID_ARGUMENT;
+        }
+    for (int k = 1; k < nh; ++k)
+        if (hs[k]->containment_factor != hs[0]->containment_factor || hs[k]->containment_strength != hs[0]->containment_strength) {
+            *error = "relaxed order: the handles of the group differ in their containment (egg_group_set_containment sets all)";
             return EGG_ERR_INVALID_ARGUMENT;
         }
     for (int k = 0; k < nh; ++k)
@@ -274,6 +281,10 @@ int relaxed_group_step(egg_handle *const *hs, int nh, double delta, int S, int C
             for (size_t m = 0; m < nq; ++m) {
                 (void)hipSetDevice(hs[Q[m]]->device);
                 GK_TRY(Q[m], launch_substep(st[Q[m]][w], sub));
+                // containment is local to a handle: a batch lives wholly on one.  The white type (w = 0) of every sub-step
+                // has been enqueued, and its event recorded, before the yolk's is; ev_box is recorded behind the projection.
+                RelaxedStep *t = st[Q[m]];
+                if (t[w].L.containment) GK_TRY(Q[m], w == 0 ? launch_contain_sum(t[0], sub) : launch_contain(t[1], t[0], sub));
             }
             for (int c = 0; c < C; ++c) {
                 const int rc = halo_pass((size_t)sub * C + c, false, sub);

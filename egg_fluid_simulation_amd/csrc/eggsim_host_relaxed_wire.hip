@@ -170,6 +170,9 @@ int egg_rx_substep(egg_handle *h, int32_t sub) {
     for (int w = 0; w < 2; ++w) {
         if (h->sys[w].n == 0) continue;
         rc = launch_substep(W.st[w], sub);
+        // containment is local to the handle (a batch lives wholly on one rank): white first, so that the sub-step's event
+        // is recorded before the yolk stream waits for it; egg_rx_get_boxes reads the box behind the projection
+        if (rc == EGG_OK && W.st[w].L.containment) rc = w == 0 ? launch_contain_sum(W.st[0], sub) : launch_contain(W.st[1], W.st[0], sub);
         if (rc != EGG_OK) return rc;
     }
     HIP_TRY(h, hipGetLastError());

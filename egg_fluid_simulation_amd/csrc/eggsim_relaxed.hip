@@ -62,6 +62,11 @@
 // built at the band's cell size through the cohesive rank kernel, which leaves the batch tags, and the pass runs as
 // egg_rx_couple_adh_kernel: a same-batch cross pair in the band is pulled back to the coupling distance.
 //
+// With yolk containment (egg_set_containment; section 2.7, "Containment"; any path) every sub-step runs two more kernels in
+// front of its first collision pass: egg_rx_contain_sum_kernel reduces every white atom to (cx, cy, L) in a fixed FP64
+// order, and egg_rx_contain_kernel (egg_rx_contain_group_kernel with a halo) projects the yolk particles of the same atom
+// index that lie beyond L back onto the disc.  Nothing of it runs while the factor is zero.
+//
 // All arithmetic is IEEE double in the order of the definition: compile with -ffp-contract=off.
 #include <hip/hip_runtime.h>
 #include "eggsim_device.h"
@@ -771,6 +776,82 @@ __device__ __forceinline__ void rx_couple(EggRelaxedArgs A, EggRxCoupleFields O,
 
 extern "C" __global__ void __launch_bounds__(256) egg_rx_couple_kernel(EggRelaxedCoupleArgs K) { rx_couple<false>(K.a, K.c, EggRxAdhesionFields{}); }
 extern "C" __global__ void __launch_bounds__(256) egg_rx_couple_adh_kernel(EggRelaxedCoupleAdhArgs K) { rx_couple<true>(K.a, K.c, K.d); }
+
+// ---- yolk containment ----
+
+// wsum of the rule: lane l has added v[o + l], v[o + l + 64], ... in ascending order into an accumulator that started at
+// +0.0; the butterfly a[l] = a[l] + a[l ^ d], d = 32 .. 1, leaves the same bits in every lane (IEEE addition commutes).
+__device__ __forceinline__ double rx_wsum(double a) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) a = a + __shfl_xor(a, d, 64);
+    return a;
+}
+
+// The summary of every white atom for one sub-step: one wave per atom, four atoms per workgroup.  Two phases over the
+// atom's positions, lane l reading entries l, l + 64, ... (neighbouring lanes read neighbouring double2): the sums of x
+// and y, then the sum of the squared distances from the centroid.  cx = wsum(x) / n, cy = wsum(y) / n,
+// L = factor * sqrt(wsum(q) / n); an empty atom contains nothing: L = +inf (the rule defines it; egg_add and
+// egg_import_batch refuse a batch without particles of a type, so no scene reaches it).
+extern "C" __global__ void __launch_bounds__(256) egg_rx_contain_sum_kernel(EggRxContainSumArgs K) {
+    const int a = (int)(blockIdx.x * 4 + (threadIdx.x >> 6));
+    if (a >= K.n_atoms) return;  // (uniform over the wave)
+    const int l = (int)(threadIdx.x & 63);
+    const int o = K.atom_offset[a], n = K.atom_count[a];
+    double ax = 0.0, ay = 0.0;
+    for (int k = l; k < n; k += 64) {
+        const double2 p = K.pos[o + k];
+        ax = ax + p.x;
+        ay = ay + p.y;
+    }
+    const double cx = rx_wsum(ax) / (double)n;
+    const double cy = rx_wsum(ay) / (double)n;
+    double aq = 0.0;
+    for (int k = l; k < n; k += 64) {
+        const double2 p = K.pos[o + k];
+        aq = aq + ((p.x - cx) * (p.x - cx) + (p.y - cy) * (p.y - cy));
+    }
+    const double rho = sqrt(rx_wsum(aq) / (double)n);
+    if (l == 0) {
+        double *s = K.summary + 3 * (size_t)a;
+        s[0] = cx;
+        s[1] = cy;
+        s[2] = n == 0 ? __builtin_inf() : K.factor * rho;
+    }
+}
+
+// The projection: one thread per local yolk particle.  A particle farther than L from the centroid of its batch's white
+// goes to keep = L + (1 - strength) (d - L) from it, along the same ray, in place; every comparison is false for a NaN.
+// The projections are counted, one atomic per wave.  G (the halo paths): the cell of every position written is folded
+// into the cell box of the sub-step's first pass, which the begin / mid kernel has just filled -- a superset of the true
+// box, and extra ghosts are never visited.
+template <bool G>
+__device__ __forceinline__ void rx_contain(const EggRxContainArgs &K) {
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    int hits = 0;
+    double2 out = make_double2(0.0, 0.0);
+    if (i < K.n) {
+        const double *s = K.summary + 3 * (size_t)K.p_atom[i];
+        const double cx = s[0], cy = s[1], L = s[2];
+        const double2 p = K.pos[i];
+        const double dx = p.x - cx, dy = p.y - cy;
+        const double d = sqrt(dx * dx + dy * dy);
+        if (d > L) {  // (d > L >= 0, so d > 0)
+            const double keep = L + (1.0 - K.strength) * (d - L);
+            const double f = keep / d;
+            out = make_double2(cx + dx * f, cy + dy * f);
+            K.pos[i] = out;
+            hits = 1;
+        }
+    }
+    const bool wrote = hits != 0;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) hits += __shfl_xor(hits, d, 64);
+    if ((threadIdx.x & 63) == 0 && hits) atomicAdd(K.hits, (unsigned long long)hits);
+    if (G) rx_box(K.box, wrote, out, K.cell_size);
+}
+
+extern "C" __global__ void __launch_bounds__(256) egg_rx_contain_kernel(EggRxContainArgs K) { rx_contain<false>(K); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_contain_group_kernel(EggRxContainArgs K) { rx_contain<true>(K); }
 
 // ---- device groups ----
 

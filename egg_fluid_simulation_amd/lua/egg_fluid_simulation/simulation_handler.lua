@@ -87,6 +87,9 @@ int egg_get_coupling_solves(egg_handle *h, int64_t *solves);
 int egg_set_adhesion(egg_handle *h, double reach, double strength);
 int egg_get_adhesion(const egg_handle *h, double *reach, double *strength);
 int egg_get_adhesion_solves(egg_handle *h, int64_t *solves);
+int egg_set_containment(egg_handle *h, double factor, double strength);
+int egg_get_containment(const egg_handle *h, double *factor, double *strength);
+int egg_get_containment_hits(egg_handle *h, int64_t *hits);
 typedef struct { double friction; double vx, vy; } egg_collider_surface;
 int egg_set_collider_surfaces(egg_handle *h, int32_t n, const egg_collider_surface *s);
 int egg_get_collider_surfaces(const egg_handle *h, int32_t cap, egg_collider_surface *s, int32_t *n);
@@ -620,6 +623,29 @@ end
 function SimulationHandler:adhesion_solves()
     local n = ffi.new("int64_t[1]")
     self:_check(lib.egg_get_adhesion_solves(self._h, n))
+    return tonumber(n[0])
+end
+
+-- Yolk containment, a disc around the centroid of each batch's white (egg_set_containment in include/eggsim.h; DESIGN.md
+-- section 2.7, "Containment").  Relaxed order; independent of coupling and adhesion.
+
+--- factor >= 0 (0, the default, = off) and strength in [0, 1] (default 1): in every sub-step a yolk particle farther than
+--- L = factor * (RMS radius of its batch's white) from the white's centroid goes back to L + (1 - strength) * (d - L)
+function SimulationHandler:set_containment(factor, strength)
+    self:_check(lib.egg_set_containment(self._h, factor or 0, strength or 1))
+end
+
+--- factor, strength: as stored
+function SimulationHandler:containment()
+    local f, s = ffi.new("double[1]"), ffi.new("double[1]")
+    self:_check(lib.egg_get_containment(self._h, f, s))
+    return f[0], s[0]
+end
+
+--- projections, one per (yolk particle, sub-step), over committed steps
+function SimulationHandler:containment_hits()
+    local n = ffi.new("int64_t[1]")
+    self:_check(lib.egg_get_containment_hits(self._h, n))
     return tonumber(n[0])
 end
 

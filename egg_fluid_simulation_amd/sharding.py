@@ -661,6 +661,22 @@ class ShardedSimulationHandler(_HandlerSurface):
         self.dist.all_reduce(tot, op=self.dist.ReduceOp.SUM)
         return [int(v) for v in tot.tolist()]
 
+    def set_containment(self, factor=0.0, strength=1.0):
+        """SimulationHandler.set_containment on every rank alike (the same call on every rank; relaxed order only).
+        Nothing new travels: a batch lives wholly on one rank, which summarises its white and projects its yolk."""
+        self.local.set_containment(factor, strength)
+
+    def containment(self):
+        return self.local.containment()
+
+    def containment_hits(self):
+        """SimulationHandler.containment_hits summed over the ranks (a collective: every rank calls it)"""
+        if self.world == 1:
+            return self.local.containment_hits()
+        tot = self.torch.tensor([self.local.containment_hits()], dtype=self.torch.int64, device=self.device)
+        self.dist.all_reduce(tot, op=self.dist.ReduceOp.SUM)
+        return int(tot.tolist()[0])
+
     def _viscous(self):
         """the coefficients the local handle holds: what the library decides a step's pass sequence from"""
         return self.local.viscosity()

@@ -373,6 +373,46 @@ class _HandlerSurface:
     def adhesion_solves(self):
         return 0
 
+    # ------------------------------------------------ yolk containment (egg_set_containment)
+    @staticmethod
+    def _c_containment(factor, strength):
+        """(factor, strength) as the doubles egg_set_containment takes; the ranges are checked here as the library checks them"""
+        out = []
+        for name, v in (("factor", factor), ("strength", strength)):
+            try:
+                out.append(float(v))
+            except (TypeError, ValueError):
+                raise EggError("containment: the %s must be a number, not %r" % (name, v)) from None
+        if not (0.0 <= out[0] < float("inf")):  # (false for a NaN)
+            raise EggError("containment: the factor %r is not a finite number >= 0" % (out[0],))
+        if not (0.0 <= out[1] <= 1.0):
+            raise EggError("containment: the strength %r lies outside [0, 1]" % (out[1],))
+        return out[0], out[1]
+
+    def set_containment(self, factor=0.0, strength=1.0):
+        """Yolk containment: a disc around the centroid of each batch's white that no yolk particle of that batch may leave
+        ("Containment"; relaxed order only).  In every sub-step of a relaxed step, after the coupling
+        pass and before the collision passes, the disc's radius is L = factor * (RMS distance of the batch's white from
+        its centroid), and a yolk particle farther out than L is moved back along its ray to
+        L + (1 - strength) * (d - L); factor 0 = off, and 2 and more suit a default egg.  One-way: the white is never
+        moved.  It needs neither coupling nor adhesion, and works on device groups and sharded ranks alike: a batch lives
+        wholly on one handle.  Raises EggError for a NaN, negative or infinite factor or a strength outside [0, 1]
+        (nothing changes) and for factor > 0 in exact order; set_solver_order("exact") raises while factor > 0."""
+        factor, strength = self._c_containment(factor, strength)  # (refused here before any device call)
+        self._check(self._c("set_containment")(factor, strength))
+
+    def containment(self):
+        """(factor, strength) as stored"""
+        f, s = C.c_double(), C.c_double()
+        self._check(self._c("get_containment")(C.byref(f), C.byref(s)))
+        return (f.value, s.value)
+
+    def containment_hits(self):
+        """projections, one per (yolk particle, sub-step), over committed steps, since creation"""
+        n = C.c_int64()
+        self._check(self._c("get_containment_hits")(C.byref(n)))
+        return int(n.value)
+
     def _init_host_state(self, white_config, yolk_config):
         """config tables (validated like the reference, L:1253-1320), hidden constants and render switches; no device"""
         if white_config is None and yolk_config is None:

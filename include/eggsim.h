@@ -608,6 +608,38 @@ int egg_set_adhesion(egg_handle *h, double reach, double strength);
 int egg_get_adhesion(const egg_handle *h, double *reach, double *strength);
 int egg_get_adhesion_solves(egg_handle *h, int64_t *solves);
 
+/* ---- yolk containment (not in the reference; DESIGN.md section 2.7, "Containment") ----
+ * Adhesion is a soft band, not a container.  Containment is the container: a DISC around the centroid of a batch's white,
+ * sized from the white's own spread, that no yolk particle of that batch may leave.  A handle holds two more doubles:
+ * `factor` (finite, >= 0; 0, the default, = off) and `strength` in [0, 1] (default 1).  Containment ACTS in a relaxed step
+ * on a handle when factor > 0 and that handle holds particles of both types; it does not depend on coupling or adhesion.
+ * (Every batch has particles of both types, so a handle holds both or neither: a handle without batches launches nothing more.)
+ * When it does not act a step launches exactly the kernels it launched before, with the same arguments, in the same
+ * enqueue order.  When it acts, every sub-step runs: 1. pre-solve + follow of both types; 2. the coupling pass, if coupling
+ * acts; 3. containment; 4. the collision passes; 5. viscosity, if on.  Colliders and walls keep the last word, and the
+ * positions at the start of the sub-step (which the walls sweep from) are not touched.
+ *   summary     of a batch's white, over the n white positions v[0 .. n) of the batch that enter the sub-step's first
+ *               collision pass.  wsum(v): 64 accumulators a[0 .. 63] start at +0.0; for k = l, l + 64, ... < n ascending,
+ *               a[l] = a[l] + v[k]; then for d = 32, 16, 8, 4, 2, 1: a[l] = a[l] + a[l ^ d] for all l at once; the result
+ *               is a[0].  cx = wsum(x) / n, cy = wsum(y) / n, q[k] = (x[k] - cx) (x[k] - cx) + (y[k] - cy) (y[k] - cy),
+ *               rho = sqrt(wsum(q) / n), L = factor rho; n == 0: L = +inf (defined so that an empty white
+ *               contains nothing; egg_add and egg_import_batch refuse a batch without particles of a type, so it does
+ *               not arise).  IEEE double, no contraction.  This summation order is part of the rule.
+ *   projection  of a yolk particle of the same batch, at the position that would enter the yolk's first collision pass:
+ *               dx = x - cx, dy = y - cy, d = sqrt(dx dx + dy dy); if d > L (false for a NaN):
+ *               keep = L + (1 - strength) (d - L), s = keep / d, x = cx + dx s, y = cy + dy s.  One hit.  No mass test.
+ *   one-way     the white is never moved: a disc, not the white's outline, and it does not hold the white together.
+ * egg_get_containment_hits: the projections, one per (yolk particle, sub-step), over committed steps (a failed or discarded
+ * step adds nothing).  Containment adds no failure path: a NaN in the white gives a NaN centre and every comparison is false.
+ * Relaxed order only: factor > 0 on a handle in exact order is EGG_ERR_UNSUPPORTED, and EGG_OPT_SOLVER_ORDER = 0 is
+ * EGG_ERR_UNSUPPORTED while factor > 0; factor == 0 is always accepted.  A NaN, negative or infinite factor, or a strength
+ * outside [0, 1], is EGG_ERR_INVALID_ARGUMENT and changes nothing.  Refused while a step is in flight.  A batch lives wholly
+ * on one handle, so containment also works on device groups and through egg_rx_* (sharded ranks), where coupling and adhesion
+ * do not.  While it acts a sub-step launches one kernel more per type: the summary on the white, the projection on the yolk. */
+int egg_set_containment(egg_handle *h, double factor, double strength);
+int egg_get_containment(const egg_handle *h, double *factor, double *strength);
+int egg_get_containment_hits(egg_handle *h, int64_t *hits);
+
 /* ---- several GPUs in one process (csrc/eggsim_group.cpp) -------------------------------------------------------
  * The multi-device form of the handle for a host that is ONE process (the LuaJIT wrapper): one egg_handle per device
  * behind one egg_group, x-slabs [cuts[k], cuts[k + 1]) of the plane per device (cuts: n_devices + 1 ascending values;
@@ -673,6 +705,13 @@ int egg_group_get_forces(const egg_group *g, int32_t cap, egg_force *f, int32_t 
 int egg_group_set_viscosity(egg_group *g, const double c[2]);
 int egg_group_get_viscosity(const egg_group *g, double c[2]);
 int egg_group_get_viscosity_pairs(egg_group *g, int64_t pairs[2]);
+/* egg_set_containment for every handle of the group alike, with its rules (relaxed order only; back to exact order only
+ * with the factor zero); refused values change no handle.  A batch lives wholly on one handle: nothing travels for it, and
+ * the results equal one handle's; the hits are summed over the handles.  A group whose handles differ in (factor,
+ * strength) refuses to step. */
+int egg_group_set_containment(egg_group *g, double factor, double strength);
+int egg_group_get_containment(const egg_group *g, double *factor, double *strength);
+int egg_group_get_containment_hits(egg_group *g, int64_t *hits);
 /* cumulative over relaxed group steps, both types: passes with a halo (the collision passes and, while a coefficient is not
  * zero, one viscosity pass per sub-step), ghost records the devices received, their bytes */
 int egg_group_get_halo_counters(const egg_group *g, int64_t *passes, int64_t *records, int64_t *bytes);
