@@ -398,6 +398,47 @@ struct EggRelaxedGroupCohColSrfArgs {
     EggRxSurfaceFields s;
 };
 
+// Collider motion (egg_set_collider_motion, DESIGN.md section 2.7, "Collider motion"): the motion instantiations of the
+// gather kernel (egg_rx_gather*_col_mov_kernel) take these besides the collider and surface fields.  The records are
+// parallel to the collider list, in a small device buffer written when they are set, never per step; a record has the
+// layout of the ABI's egg_collider_motion (16 bytes).  While a motion is not zero the surface records exist for every
+// collider, defaults included, as they do with a wall in the list.
+struct EggMotion {
+    double vx, vy;
+};
+struct EggRxMotionFields {
+    const EggMotion *list;               // [the collider count]; every lane reads the same record
+    double t;                            // the end of the pass's sub-step, from the start of the step: (sub + 1) * sub_delta
+};
+struct EggRelaxedColMovArgs {
+    EggRelaxedArgs a;
+    EggRxColliderFields d;
+    EggRxSurfaceFields s;
+    EggRxMotionFields m;
+};
+struct EggRelaxedGroupColMovArgs {
+    EggRelaxedArgs a;
+    EggRxGroupFields g;
+    EggRxColliderFields d;
+    EggRxSurfaceFields s;
+    EggRxMotionFields m;
+};
+struct EggRelaxedCohColMovArgs {
+    EggRelaxedArgs a;
+    EggRxCohesionFields c;
+    EggRxColliderFields d;
+    EggRxSurfaceFields s;
+    EggRxMotionFields m;
+};
+struct EggRelaxedGroupCohColMovArgs {
+    EggRelaxedArgs a;
+    EggRxGroupFields g;
+    EggRxCohesionFields c;
+    EggRxColliderFields d;
+    EggRxSurfaceFields s;
+    EggRxMotionFields m;
+};
+
 // Force fields (egg_set_forces, DESIGN.md section 2.7, "Forces"): the force instantiations of the kernels that begin a
 // sub-step (egg_rx_begin*_frc_kernel, egg_rx_mid*_frc_kernel) take these besides.  The list is the handle's, in a small
 // device buffer written when it is set; a record has the layout of the ABI's egg_force (40 bytes).

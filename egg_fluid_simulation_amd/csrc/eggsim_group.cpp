@@ -65,6 +65,7 @@ struct egg_group {
     int cohesion = EGG_COHESION_REFERENCE;  // egg_group_set_cohesion: every handle's EGG_OPT_COHESION
     std::vector<egg_collider> colliders;    // egg_group_set_colliders: every handle's list, as given
     std::vector<egg_collider_surface> surfaces;  // egg_group_set_collider_surfaces: every handle's records, as given
+    std::vector<egg_collider_motion> motions;    // egg_group_set_collider_motion: every handle's records, as given
     std::vector<egg_force> forces;          // egg_group_set_forces: every handle's list, as given
     double viscosity[2] = {0.0, 0.0};       // egg_group_set_viscosity: every handle's coefficients
     double containment[2] = {0.0, 1.0};     // egg_group_set_containment: every handle's (factor, strength)
@@ -647,18 +648,26 @@ int egg_group_set_cohesion(egg_group *g, int32_t mode) {
 
 int egg_group_set_colliders(egg_group *g, int32_t n, const egg_collider *c) {
     if (!g) return EGG_ERR_INVALID_ARGUMENT;
+    if (!g->motions.empty() && !g->h.empty()) {  // (committed steps have moved the lists: what a refused call goes back to is the list now)
+        int32_t have = 0;
+        (void)egg_get_colliders(g->h[0], 0, nullptr, &have);
+        g->colliders.resize((size_t)have);
+        (void)egg_get_colliders(g->h[0], have, g->colliders.data(), &have);
+    }
     for (size_t k = 0; k < g->h.size(); ++k) {
         const int rc = egg_set_colliders(g->h[k], n, c);
         if (rc < 0) {  // (handle 0 refuses a bad list before any handle has changed; a later one: the others go back)
             for (size_t j = 0; j < k; ++j) {  // (with their surfaces, which a list that is set resets)
                 (void)egg_set_colliders(g->h[j], (int32_t)g->colliders.size(), g->colliders.data());
                 (void)egg_set_collider_surfaces(g->h[j], (int32_t)g->surfaces.size(), g->surfaces.data());
+                (void)egg_set_collider_motion(g->h[j], (int32_t)g->motions.size(), g->motions.data());
             }
             return gfail(g, rc, "device %d: %s", (int)k, egg_last_error(g->h[k]));
         }
     }
     g->colliders.assign(c, c + (n > 0 ? n : 0));
     g->surfaces.clear();  // (every handle has reset its own)
+    g->motions.clear();
     return EGG_OK;
 }
 
@@ -678,6 +687,24 @@ int egg_group_set_collider_surfaces(egg_group *g, int32_t n, const egg_collider_
 int egg_group_get_collider_surfaces(const egg_group *g, int32_t cap, egg_collider_surface *s, int32_t *n) {
     if (!g || g->h.empty()) return EGG_ERR_INVALID_ARGUMENT;
     return egg_get_collider_surfaces(g->h[0], cap, s, n);  // (as stored: every handle holds the same records)
+}
+
+int egg_group_set_collider_motion(egg_group *g, int32_t n, const egg_collider_motion *m) {
+    if (!g) return EGG_ERR_INVALID_ARGUMENT;
+    for (size_t k = 0; k < g->h.size(); ++k) {
+        const int rc = egg_set_collider_motion(g->h[k], n, m);
+        if (rc < 0) {  // (handle 0 refuses bad records before any handle has changed; a later one: the others go back)
+            for (size_t j = 0; j < k; ++j) (void)egg_set_collider_motion(g->h[j], (int32_t)g->motions.size(), g->motions.data());
+            return gfail(g, rc, "device %d: %s", (int)k, egg_last_error(g->h[k]));
+        }
+    }
+    g->motions.assign(m, m + (n > 0 ? n : 0));
+    return EGG_OK;
+}
+
+int egg_group_get_collider_motion(const egg_group *g, int32_t cap, egg_collider_motion *m, int32_t *n) {
+    if (!g || g->h.empty()) return EGG_ERR_INVALID_ARGUMENT;
+    return egg_get_collider_motion(g->h[0], cap, m, n);  // (as stored: every handle holds the same records)
 }
 
 int egg_group_get_collider_grips(egg_group *g, int64_t grips[2]) {

@@ -96,6 +96,10 @@ extern "C" __global__ void egg_rx_gather_col_wall_kernel(EggRelaxedColSrfArgs A)
 extern "C" __global__ void egg_rx_gather_group_col_wall_kernel(EggRelaxedGroupColSrfArgs A);
 extern "C" __global__ void egg_rx_gather_coh_col_wall_kernel(EggRelaxedCohColSrfArgs A);
 extern "C" __global__ void egg_rx_gather_group_coh_col_wall_kernel(EggRelaxedGroupCohColSrfArgs A);
+extern "C" __global__ void egg_rx_gather_col_mov_kernel(EggRelaxedColMovArgs A);
+extern "C" __global__ void egg_rx_gather_group_col_mov_kernel(EggRelaxedGroupColMovArgs A);
+extern "C" __global__ void egg_rx_gather_coh_col_mov_kernel(EggRelaxedCohColMovArgs A);
+extern "C" __global__ void egg_rx_gather_group_coh_col_mov_kernel(EggRelaxedGroupCohColMovArgs A);
 extern "C" __global__ void egg_rx_begin_frc_kernel(EggRelaxedFrcArgs A);
 extern "C" __global__ void egg_rx_mid_frc_kernel(EggRelaxedFrcArgs A);
 extern "C" __global__ void egg_rx_begin_group_frc_kernel(EggRelaxedGroupFrcArgs A);
@@ -451,6 +455,13 @@ struct egg_handle {
     DevBuf<EggSurface> d_surfaces;
     bool surfaces_grip = false;
     int64_t collider_grips[2] = {0, 0};
+    // collider motion (egg_set_collider_motion): empty = every motion is zero, else one record per collider; the copy on
+    // the device (written when they are set, never per step); whether any component is not zero -- only then does a step
+    // launch the motion instantiations, which read the surface records (d_surfaces then holds one per collider, defaults
+    // included), and only then does a commit advance `colliders` and rewrite d_colliders
+    std::vector<egg_collider_motion> motions;
+    DevBuf<EggMotion> d_motions;
+    bool motions_move = false;
     // force fields (egg_set_forces; relaxed order only): the list as egg_get_forces returns it and its copy on the device
     // (written when the list is set, never per step)
     std::vector<egg_force> forces;
@@ -632,8 +643,9 @@ struct RelaxedLayout {
     bool colliders = false;  // (set by prepare_type: the handle's collider list is not empty)
     bool forces = false;     // (set by prepare_type: the handle's force list is not empty; no status word of its own)
     size_t V = 0;            // (set by prepare_type: the sub-steps, when the type's viscosity coefficient is not zero)
-    bool surfaces = false;   // (set by prepare_type: a collider surface of the handle has friction > 0, or walls)
+    bool surfaces = false;   // (set by prepare_type: a collider surface of the handle has friction > 0, or walls, or motion)
     bool walls = false;      // (set by prepare_type: the handle's list holds a wall; implies surfaces)
+    bool motion = false;     // (set by prepare_type: a collider motion of the handle is not zero; implies surfaces; no word of its own)
     bool coupling = false;   // (set by prepare_type: the step runs coupling passes -- no halo, factor > 0, both types populated)
     bool coupled_word = false;  // (set by prepare_type: coupling, and the type is white: it holds the counter word)
     bool adhesion = false;      // (set by prepare_type: coupling, and the handle's adhesion reach exceeds the coupling factor)
@@ -662,6 +674,7 @@ struct RelaxedStep {  // one type of one handle in a relaxed step
     EggRxCohesionFields coh{};  // effective cohesion (L.cohesion): compliance and factor of the type, the tag arrays
     EggRxColliderFields col{};  // static colliders (L.colliders): the handle's list, the type's bit, the hit counter
     EggRxSurfaceFields srf{};   // collider surfaces (L.surfaces): the handle's records, the sub-step, the grip counter
+    EggRxMotionFields mov{};    // collider motion (L.motion): the handle's records; launch_pass sets the pass's time
     EggRxForceFields frc{};     // force fields (L.forces): the handle's list, the type's bit
     EggRxViscFields visc{};     // viscosity (L.V): the type's coefficient, the pair counter
     double couple_cell = 0, couple_c = 0;  // coupling (L.coupling): the shared cell size H, the compliance of the strength

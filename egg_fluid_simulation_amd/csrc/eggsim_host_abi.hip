@@ -1048,6 +1048,8 @@ int egg_set_colliders(egg_handle *h, int32_t n, const egg_collider *c) {
     h->colliders_wall = wall;
     h->surfaces.clear();  // (the indices no longer mean anything: every surface is the default again)
     h->surfaces_grip = false;
+    h->motions.clear();  // (and every motion zero)
+    h->motions_move = false;
     return EGG_OK;
 }
 
@@ -1089,7 +1091,7 @@ int egg_set_collider_surfaces(egg_handle *h, int32_t n, const egg_collider_surfa
         HIP_TRY(h, hipSetDevice(h->device));
         HIP_TRY(h, h->d_surfaces.reserve(EGG_MAX_COLLIDERS, false, nullptr));
         HIP_TRY(h, hipMemcpy(h->d_surfaces.p, list.data(), (size_t)n * sizeof(egg_collider_surface), hipMemcpyHostToDevice));
-    } else if (h->colliders_wall) {  // (the wall instantiations go on reading the records: the defaults again)
+    } else if (h->colliders_wall || h->motions_move) {  // (the wall and motion instantiations go on reading the records: the defaults again)
         const std::vector<egg_collider_surface> zeros(h->colliders.size(), egg_collider_surface{0.0, 0.0, 0.0});
         HIP_TRY(h, hipSetDevice(h->device));
         HIP_TRY(h, h->d_surfaces.reserve(EGG_MAX_COLLIDERS, false, nullptr));
@@ -1106,6 +1108,52 @@ int egg_get_collider_surfaces(const egg_handle *h, int32_t cap, egg_collider_sur
     if (n) *n = have;
     for (int32_t k = 0; sf && k < std::min(cap, have); ++k)
         sf[k] = h->surfaces.empty() ? egg_collider_surface{0.0, 0.0, 0.0} : h->surfaces[(size_t)k];
+    return EGG_OK;
+}
+
+// Collider motion ("Collider motion"): one record per collider, or none (all zero).  Everything is
+// checked before anything changes; geometry and surfaces stay as they are.
+int egg_set_collider_motion(egg_handle *h, int32_t n, const egg_collider_motion *mo) {
+    if (!h) return EGG_ERR_INVALID_ARGUMENT;
+    REJECT_IN_FLIGHT(h, "egg_set_collider_motion");
+    static_assert(sizeof(egg_collider_motion) == 16 && sizeof(EggMotion) == sizeof(egg_collider_motion), "a motion record is 16 bytes");
+    if (n != 0 && n != (int32_t)h->colliders.size())
+        return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_collider_motion: n = %d, the list holds %d colliders (n is that, or 0)", (int)n,
+                    (int)h->colliders.size());
+    if (n > 0 && !mo) return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_collider_motion: n = %d without records", (int)n);
+    std::vector<egg_collider_motion> list((size_t)n);
+    bool move = false;
+    for (int32_t k = 0; k < n; ++k) {
+        egg_collider_motion &o = list[(size_t)k];
+        o = mo[k];
+        if (!std::isfinite(o.vx) || !std::isfinite(o.vy))
+            return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_collider_motion: collider %d: the velocity (%g, %g) is not finite", (int)k, o.vx,
+                        o.vy);
+        o.vx = o.vx + 0.0;  // (-0.0 is stored as +0.0: handles set alike compare alike)
+        o.vy = o.vy + 0.0;
+        move |= o.vx != 0.0 || o.vy != 0.0;
+    }
+    if (move) {  // (no step is running: every step ends with its streams waited for)
+        HIP_TRY(h, hipSetDevice(h->device));
+        HIP_TRY(h, h->d_motions.reserve(EGG_MAX_COLLIDERS, false, nullptr));
+        HIP_TRY(h, hipMemcpy(h->d_motions.p, list.data(), (size_t)n * sizeof(egg_collider_motion), hipMemcpyHostToDevice));
+        if (h->surfaces.empty()) {  // the motion instantiations read a surface record per collider: the defaults, until some are set
+            const std::vector<egg_collider_surface> zeros((size_t)n, egg_collider_surface{0.0, 0.0, 0.0});
+            HIP_TRY(h, h->d_surfaces.reserve(EGG_MAX_COLLIDERS, false, nullptr));
+            HIP_TRY(h, hipMemcpy(h->d_surfaces.p, zeros.data(), (size_t)n * sizeof(egg_collider_surface), hipMemcpyHostToDevice));
+        }
+    }
+    h->motions.swap(list);
+    h->motions_move = move;
+    return EGG_OK;
+}
+
+int egg_get_collider_motion(const egg_handle *h, int32_t cap, egg_collider_motion *mo, int32_t *n) {
+    if (!h) return EGG_ERR_INVALID_ARGUMENT;
+    const int32_t have = (int32_t)h->colliders.size();
+    if (n) *n = have;
+    for (int32_t k = 0; mo && k < std::min(cap, have); ++k)
+        mo[k] = h->motions.empty() ? egg_collider_motion{0.0, 0.0} : h->motions[(size_t)k];
     return EGG_OK;
 }
 

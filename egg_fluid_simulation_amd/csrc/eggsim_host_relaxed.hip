@@ -22,6 +22,11 @@
 // While the list holds a wall (EGG_COLLIDER_WALL, RelaxedLayout::walls) launch_pass picks the wall twin of the surface
 // instantiation, whether or not a friction is set: RelaxedStep::srf is then always filled, and the handle's records on the
 // device hold one per collider, defaults included.  A list without a wall launches what it launched.
+// While a collider motion is not zero (egg_set_collider_motion, RelaxedLayout::motion) launch_pass picks the motion twin of
+// the instantiation with walls, whether or not the list holds a wall or a friction, and RelaxedStep::mov carries the
+// records and the end time of the pass's sub-step; relaxed_commit advances the handle's stored list by the step and rewrites
+// its copy on the device.  With every motion zero a step launches what it launched, with the same arguments, and a commit
+// touches no list.
 // With force fields (egg_set_forces, RelaxedLayout::forces) launch_substep picks the force instantiation of the begin / mid
 // kernel and RelaxedStep::frc carries the handle's list; with an empty list a step launches what it always launched.
 // With viscosity (egg_set_viscosity, RelaxedLayout::V) every sub-step of a type whose coefficient is not zero ends with
@@ -193,7 +198,8 @@ int prepare_type(RelaxedStep &st, int C, size_t ghosts, const RelaxedLayout &L, 
     st.L.cohesion = h->opt_cohesion == EGG_COHESION_EFFECTIVE;
     st.L.colliders = !h->colliders.empty();
     st.L.walls = st.L.colliders && h->colliders_wall;
-    st.L.surfaces = st.L.colliders && (h->surfaces_grip || st.L.walls);
+    st.L.motion = st.L.colliders && h->motions_move;
+    st.L.surfaces = st.L.colliders && (h->surfaces_grip || st.L.walls || st.L.motion);
     st.L.forces = !h->forces.empty();
     st.L.V = h->viscosity[st.w] > 0.0 ? L.P / (size_t)C : 0;
     st.L.coupling = !L.halo && h->coupling_factor > 0.0 && h->sys[0].n > 0 && h->sys[1].n > 0;
@@ -230,6 +236,8 @@ int prepare_type(RelaxedStep &st, int C, size_t ghosts, const RelaxedLayout &L, 
         st.srf.sub_delta = st.env.sub_delta;
         st.srf.grips = r.status.p + st.L.grips();
     }
+    st.mov = EggRxMotionFields{};
+    if (st.L.motion) st.mov.list = h->d_motions.p;
     st.frc = EggRxForceFields{};
     if (st.L.forces) {
         st.frc.list = h->d_forces.p;
@@ -332,6 +340,7 @@ int launch_pass(RelaxedStep &st, int p) {
                   : st.L.V            ? r.status.p + st.L.box(st.L.P + (size_t)(p / st.C))
                                       : nullptr;
     }
+    if (st.L.motion) st.mov.t = (double)(p / st.C + 1) * st.env.sub_delta;  // the end of the pass's sub-step
     const dim3 grid((unsigned)((s.n + st.ghost_cap + 255) / 256)), block(256);  // (the ghost count is read on the device)
     HIP_TRY(h, hipMemsetAsync(r.hkey.p, 0xFF, (size_t)r.table * 8, s.stream));
     HIP_TRY(h, hipMemsetAsync(r.hcount.p, 0, ((size_t)r.table + 1) * 4, s.stream));
@@ -346,7 +355,10 @@ int launch_pass(RelaxedStep &st, int p) {
         if (st.L.cohesion) {
             const EggRelaxedGroupCohArgs k{a.a, a.g, st.coh};
             hipLaunchKernelGGL(egg_rx_rank_group_coh_kernel, grid, block, 0, s.stream, k);
-            if (st.L.walls)
+            if (st.L.motion)
+                hipLaunchKernelGGL(egg_rx_gather_group_coh_col_mov_kernel, grid, block, 0, s.stream,
+                                   EggRelaxedGroupCohColMovArgs{a.a, a.g, st.coh, st.col, st.srf, st.mov});
+            else if (st.L.walls)
                 hipLaunchKernelGGL(egg_rx_gather_group_coh_col_wall_kernel, grid, block, 0, s.stream,
                                    EggRelaxedGroupCohColSrfArgs{a.a, a.g, st.coh, st.col, st.srf});
             else if (st.L.surfaces)
@@ -358,7 +370,10 @@ int launch_pass(RelaxedStep &st, int p) {
                 hipLaunchKernelGGL(egg_rx_gather_group_coh_kernel, grid, block, 0, s.stream, k);
         } else {
             hipLaunchKernelGGL(egg_rx_rank_group_kernel, grid, block, 0, s.stream, a);
-            if (st.L.walls)
+            if (st.L.motion)
+                hipLaunchKernelGGL(egg_rx_gather_group_col_mov_kernel, grid, block, 0, s.stream,
+                                   EggRelaxedGroupColMovArgs{a.a, a.g, st.col, st.srf, st.mov});
+            else if (st.L.walls)
                 hipLaunchKernelGGL(egg_rx_gather_group_col_wall_kernel, grid, block, 0, s.stream,
                                    EggRelaxedGroupColSrfArgs{a.a, a.g, st.col, st.srf});
             else if (st.L.surfaces)
@@ -374,7 +389,10 @@ int launch_pass(RelaxedStep &st, int p) {
         if (st.L.cohesion) {
             const EggRelaxedCohArgs k{a.a, st.coh};
             hipLaunchKernelGGL(egg_rx_rank_coh_kernel, grid, block, 0, s.stream, k);
-            if (st.L.walls)
+            if (st.L.motion)
+                hipLaunchKernelGGL(egg_rx_gather_coh_col_mov_kernel, grid, block, 0, s.stream,
+                                   EggRelaxedCohColMovArgs{a.a, st.coh, st.col, st.srf, st.mov});
+            else if (st.L.walls)
                 hipLaunchKernelGGL(egg_rx_gather_coh_col_wall_kernel, grid, block, 0, s.stream,
                                    EggRelaxedCohColSrfArgs{a.a, st.coh, st.col, st.srf});
             else if (st.L.surfaces)
@@ -386,7 +404,10 @@ int launch_pass(RelaxedStep &st, int p) {
                 hipLaunchKernelGGL(egg_rx_gather_coh_kernel, grid, block, 0, s.stream, k);
         } else {
             hipLaunchKernelGGL(egg_rx_rank_kernel, grid, block, 0, s.stream, a.a);
-            if (st.L.walls)
+            if (st.L.motion)
+                hipLaunchKernelGGL(egg_rx_gather_col_mov_kernel, grid, block, 0, s.stream,
+                                   EggRelaxedColMovArgs{a.a, st.col, st.srf, st.mov});
+            else if (st.L.walls)
                 hipLaunchKernelGGL(egg_rx_gather_col_wall_kernel, grid, block, 0, s.stream, EggRelaxedColSrfArgs{a.a, st.col, st.srf});
             else if (st.L.surfaces)
                 hipLaunchKernelGGL(egg_rx_gather_col_srf_kernel, grid, block, 0, s.stream, EggRelaxedColSrfArgs{a.a, st.col, st.srf});
@@ -659,6 +680,31 @@ static int relaxed_finish(egg_handle *h, RelaxedStep st[2], int S, int C) {
     return EGG_OK;
 }
 
+// Collider motion at the commit: the stored geometry of every collider becomes the geometry of the step's end, t = S h
+// -- the expression the kernels of the last sub-step evaluated, so the same bits -- and the copy on the device follows.
+// No step is running: every path waits for its streams before it commits.
+static void advance_colliders(egg_handle *h, double t) {
+    for (size_t k = 0; k < h->colliders.size(); ++k) {
+        egg_collider &c = h->colliders[k];
+        const egg_collider_motion &m = h->motions[k];
+        const double ox = t * m.vx, oy = t * m.vy;
+        if (c.kind == EGG_COLLIDER_HALF_PLANE) {
+            c.p[2] = c.p[2] + (c.p[0] * ox + c.p[1] * oy);
+        } else {
+            c.p[0] = c.p[0] + ox;
+            c.p[1] = c.p[1] + oy;
+            if (c.kind == EGG_COLLIDER_SEGMENT || c.kind == EGG_COLLIDER_WALL) {
+                c.p[2] = c.p[2] + ox;
+                c.p[3] = c.p[3] + oy;
+            }
+        }
+    }
+    hipError_t e = hipSetDevice(h->device);
+    if (e == hipSuccess)
+        e = hipMemcpy(h->d_colliders.p, h->colliders.data(), h->colliders.size() * sizeof(egg_collider), hipMemcpyHostToDevice);
+    if (e != hipSuccess) (void)fail(h, EGG_ERR_DEVICE, "relaxed order: the moved colliders did not reach the device: %s", hipGetErrorString(e));
+}
+
 // the commit of a relaxed step whose end kernels have run: flip cur, statistics from the status words read back
 void relaxed_commit(egg_handle *h, const RelaxedStep st[2], int S, int C, double ms) {
     for (int w = 0; w < 2; ++w) {
@@ -688,6 +734,7 @@ void relaxed_commit(egg_handle *h, const RelaxedStep st[2], int S, int C, double
         s.aabb_valid = s.aabb_on_device = s.disp_valid = false;
         s.out_copied = false;
     }
+    if (h->motions_move && !h->colliders.empty()) advance_colliders(h, (double)S * st[0].env.sub_delta);
     h->stats.last_step_kernel_ms = ms;
     if (h->opt_timing) {
         for (int w = 0; w < 2; ++w) h->stats.kernel_ms_sum[w] += h->stats.kernel_ms[w];

@@ -124,6 +124,14 @@ int relaxed_group_step(egg_handle *const *hs, int nh, double delta, int S, int C
             *error = "relaxed order: the handles of the group differ in their collider surfaces (egg_group_set_collider_surfaces sets all)";
             return EGG_ERR_INVALID_ARGUMENT;
         }
+        // (all zeros and none compare alike: neither moves anything)
+        const std::vector<egg_collider_motion> &ma = hs[0]->motions, &mb = hs[k]->motions;
+        const bool same_motion = hs[0]->motions_move == hs[k]->motions_move &&
+                                 (!hs[0]->motions_move || memcmp(ma.data(), mb.data(), ma.size() * sizeof(egg_collider_motion)) == 0);
+        if (!same_motion) {
+            *error = "relaxed order: the handles of the group differ in their collider motion (egg_group_set_collider_motion sets all)";
+            return EGG_ERR_INVALID_ARGUMENT;
+        }
     }
     for (int k = 1; k < nh; ++k) {
         const std::vector<egg_force> &a = hs[0]->forces, &b = hs[k]->forces;

@@ -42,6 +42,11 @@
 // sub-step, prev[me] to the position now, and puts a particle that has crossed it back on the side it started from.  The
 // W = false instantiations are the kernels as they were.
 //
+// While a collider's motion is not zero (egg_set_collider_motion; DESIGN.md section 2.7, "Collider motion") the wall twins
+// run as their motion twins (egg_rx_gather*_col_mov_kernel, which take EggRxMotionFields besides): every collider is
+// where it is at the end of the pass's sub-step, a wall sweeps in its own frame, and friction is taken relative to the
+// moving surface.  Every other instantiation is the kernel as it was.
+//
 // With force fields (egg_set_forces; DESIGN.md section 2.7, "Forces") the kernels that begin a sub-step run in their force
 // instantiations (F = true, egg_rx_begin*_frc_kernel, egg_rx_mid*_frc_kernel): the fields of the handle's list whose mask
 // covers the type accelerate the velocity the pre-solve is about to damp.  The F = false instantiations are the kernels
@@ -117,6 +122,12 @@ __device__ __forceinline__ uint32_t rx_hash(unsigned long long k) {  // the 64-b
     return (uint32_t)k;
 }
 
+// A value every lane of the wave holds alike, back in scalar registers: FP64 arithmetic runs on the vector unit, and what
+// it computes from wave-uniform records would otherwise live in vector registers across the collider's whole rule.
+__device__ __forceinline__ double rx_uniform(double v) {
+    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
+}
+
 // Step 5c of the relaxed pass: position-based Coulomb friction of the collider that has just projected the particle to
 // `out`.  (nx, ny) and pen are the projection's normal and the depth it corrected, pv the particle's position at the
 // start of the sub-step, h the sub-step.  The tangential part of the displacement relative to the surface is removed:
@@ -154,15 +165,43 @@ __device__ __forceinline__ int rx_grip(const EggSurface &sf, double h, double2 p
 // W (with S only): the list may hold walls.  A wall is a segment whose first question is whether the straight path from pv
 // to the position now meets it: then the particle goes back to its radius from the nearest point, on pv's side.  pv does
 // not change inside a sub-step, so every pass sweeps from the same start.
+// Mo (with W only; M below): every collider may move (egg_set_collider_motion; DESIGN.md section 2.7, "Collider motion").
+// The switch is the pointer: every kernel passes either nullptr or the address of its own argument, so after inlining M is
+// a constant and an instantiation without motion holds none of it.  (A sixth template parameter would put the gather's
+// body one call deeper, and the four *_col_kernel instantiations then come out scheduled differently.)  The motion record
+// is read like the collider record; the parameters of the sub-step's end are computed once per collider, in front of the
+// branch on its kind, and go back to scalar registers (rx_uniform); a wall sweeps from pv carried along with it by one
+// sub-step; step 5c takes the surface's velocity plus the motion's and reads the true pv.
 template <bool S, bool W>
-__device__ __forceinline__ int rx_collide(const EggRxColliderFields &Co, const EggRxSurfaceFields &Su, int i, double r,
-                                          double2 pv, double2 &out, int &grips) {
+__device__ __forceinline__ int rx_collide(const EggRxColliderFields &Co, const EggRxSurfaceFields &Su, const EggRxMotionFields *Mo,
+                                          int i, double r, double2 pv, double2 &out, int &grips) {
+    const bool M = W && Mo != nullptr;
     int hits = 0;
     for (int c = 0; c < Co.count; ++c) {
-        const EggCollider col = Co.list[c];
+        EggCollider col = Co.list[c];
         if (!(col.type_mask & Co.type_bit)) continue;
         EggSurface sf{};
         if (S) sf = Su.list[c];
+        double hvx = 0.0, hvy = 0.0;  // (M: how far the collider carries the sub-step's start along, what a moving wall sweeps from)
+        if (M) {  // the geometry at the end of the pass's sub-step, once per collider; step 5c adds the motion to the surface's velocity
+            const EggMotion mo = Mo->list[c];
+            const double ox = Mo->t * mo.vx, oy = Mo->t * mo.vy;
+            if (col.kind == EGG_RX_COLLIDER_HALF_PLANE) {
+                col.p[2] = rx_uniform(col.p[2] + (col.p[0] * ox + col.p[1] * oy));
+            } else {
+                col.p[0] = rx_uniform(col.p[0] + ox);
+                col.p[1] = rx_uniform(col.p[1] + oy);
+                if (col.kind == EGG_RX_COLLIDER_SEGMENT || col.kind == EGG_RX_COLLIDER_WALL) {
+                    col.p[2] = rx_uniform(col.p[2] + ox);
+                    col.p[3] = rx_uniform(col.p[3] + oy);
+                }
+            }
+            hvx = rx_uniform(Su.sub_delta * mo.vx);
+            hvy = rx_uniform(Su.sub_delta * mo.vy);
+            sf.vx = rx_uniform(sf.vx + mo.vx);
+            sf.vy = rx_uniform(sf.vy + mo.vy);
+        }
+        const double2 pw = M ? make_double2(pv.x + hvx, pv.y + hvy) : pv;
         const double x = out.x, y = out.y;
         if (col.kind == EGG_RX_COLLIDER_HALF_PLANE) {  // p = (nx, ny, off): keeps n . pos - off >= r
             const double s = (col.p[0] * x + col.p[1] * y) - (col.p[2] + r);
@@ -188,11 +227,11 @@ __device__ __forceinline__ int rx_collide(const EggRxColliderFields &Co, const E
             cy = col.p[1] + t * ey;
             R = 0.0;
             if (W && col.kind == EGG_RX_COLLIDER_WALL) {  // the sweep: which side the sub-step started on, which side now
-                a0 = ex * (pv.y - col.p[1]) - ey * (pv.x - col.p[0]);
+                a0 = ex * (pw.y - col.p[1]) - ey * (pw.x - col.p[0]);
                 const double a1 = ex * (y - col.p[1]) - ey * (x - col.p[0]);
                 if ((a0 > 0.0 && a1 <= 0.0) || (a0 < 0.0 && a1 >= 0.0)) {  // (a0 != 0, so l2 != 0)
                     const double u = a0 / (a0 - a1);
-                    const double hx = pv.x + u * (x - pv.x), hy = pv.y + u * (y - pv.y);  // where the path meets the line
+                    const double hx = pw.x + u * (x - pw.x), hy = pw.y + u * (y - pw.y);  // where the path meets the line
                     const double tc = ((hx - col.p[0]) * ex + (hy - col.p[1]) * ey) / l2;
                     caught = tc >= 0.0 && tc <= 1.0;  // ... and that is on the wall
                 }
@@ -428,10 +467,12 @@ __device__ __forceinline__ void rx_rank(const EggRelaxedArgs &A, const EggRxGrou
 // -- and then runs the collision correction's arithmetic with the cohesion compliance (one path for both kinds).  D: the
 // new position goes through the colliders before it is written (whether or not a pair fired).  S (with D only): a
 // collider's surface acts right after its projection (step 5c); prev[me] is read once, for that.  W (with S only): the
-// list may hold walls, which sweep from the same prev[me].
+// list may hold walls, which sweep from the same prev[me].  Mo (with W only): not null in the motion instantiations, whose
+// colliders move (rx_collide).
 template <bool G, bool K, bool D, bool S, bool W>
 __device__ __forceinline__ void rx_gather(EggRelaxedArgs A, const EggRxGroupFields &X, const EggRxCohesionFields &Ch,
-                                          const EggRxColliderFields &Co, const EggRxSurfaceFields &Su) {
+                                          const EggRxColliderFields &Co, const EggRxSurfaceFields &Su,
+                                          const EggRxMotionFields *Mo = nullptr) {
     static_assert(D || !S, "surfaces belong to colliders");
     static_assert(S || !W, "the wall instantiations are surface instantiations");
     const int t = (int)(blockIdx.x * 256 + threadIdx.x);
@@ -521,7 +562,7 @@ __device__ __forceinline__ void rx_gather(EggRelaxedArgs A, const EggRxGroupFiel
             out.x = p.x + (sx * A.omega) / (double)n_fired;
             out.y = p.y + (sy * A.omega) / (double)n_fired;
         }
-        if (D) hits = rx_collide<S, W>(Co, Su, i, wr.y, S ? A.prev[me] : make_double2(0.0, 0.0), out, grips);
+        if (D) hits = rx_collide<S, W>(Co, Su, Mo, i, wr.y, S ? A.prev[me] : make_double2(0.0, 0.0), out, grips);
         A.pos_next[me] = out;
         if (G) {
             local = true;
@@ -580,6 +621,12 @@ extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_col_wall_kernel(
 extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_col_wall_kernel(EggRelaxedGroupColSrfArgs A) { rx_gather<true, false, true, true, true>(A.a, A.g, EggRxCohesionFields{}, A.d, A.s); }
 extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_coh_col_wall_kernel(EggRelaxedCohColSrfArgs A) { rx_gather<false, true, true, true, true>(A.a, EggRxGroupFields{}, A.c, A.d, A.s); }
 extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_coh_col_wall_kernel(EggRelaxedGroupCohColSrfArgs A) { rx_gather<true, true, true, true, true>(A.a, A.g, A.c, A.d, A.s); }
+
+// collider motion (colliders, surfaces and walls all on)
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_col_mov_kernel(EggRelaxedColMovArgs A) { rx_gather<false, false, true, true, true>(A.a, EggRxGroupFields{}, EggRxCohesionFields{}, A.d, A.s, &A.m); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_col_mov_kernel(EggRelaxedGroupColMovArgs A) { rx_gather<true, false, true, true, true>(A.a, A.g, EggRxCohesionFields{}, A.d, A.s, &A.m); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_coh_col_mov_kernel(EggRelaxedCohColMovArgs A) { rx_gather<false, true, true, true, true>(A.a, EggRxGroupFields{}, A.c, A.d, A.s, &A.m); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_coh_col_mov_kernel(EggRelaxedGroupCohColMovArgs A) { rx_gather<true, true, true, true, true>(A.a, A.g, A.c, A.d, A.s, &A.m); }
 
 // ---- viscosity ----
 

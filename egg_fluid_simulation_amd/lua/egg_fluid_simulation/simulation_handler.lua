@@ -93,6 +93,9 @@ int egg_get_containment_hits(egg_handle *h, int64_t *hits);
 typedef struct { double friction; double vx, vy; } egg_collider_surface;
 int egg_set_collider_surfaces(egg_handle *h, int32_t n, const egg_collider_surface *s);
 int egg_get_collider_surfaces(const egg_handle *h, int32_t cap, egg_collider_surface *s, int32_t *n);
+typedef struct { double vx, vy; } egg_collider_motion;
+int egg_set_collider_motion(egg_handle *h, int32_t n, const egg_collider_motion *m);
+int egg_get_collider_motion(const egg_handle *h, int32_t cap, egg_collider_motion *m, int32_t *n);
 int egg_get_collider_grips(egg_handle *h, int64_t grips[2]);
 typedef struct egg_group egg_group;
 int egg_group_set_solver_order(egg_group *g, int32_t order, double relaxation);
@@ -512,6 +515,35 @@ function SimulationHandler:collider_grips()
     local grips = ffi.new("int64_t[2]")
     self:_check(lib.egg_get_collider_grips(self._h, grips))
     return tonumber(grips[0]), tonumber(grips[1])
+end
+
+-- Not in the reference: collider motion (egg_set_collider_motion in include/eggsim.h; DESIGN.md section 2.7,
+-- "Collider motion").
+
+--- one motion per collider of the current list: `false` for a collider at rest or `{ vx, vy }`, a rigid velocity in px/s
+--- that the step integrates on the device.  `{}` resets every motion to zero, and so does set_colliders.
+function SimulationHandler:set_collider_motion(motions)
+    local n = #motions
+    local arr = ffi.new("egg_collider_motion[?]", math.max(n, 1))
+    for k = 1, n do  -- (not ipairs: a nil hole must not end the walk short of n)
+        local m = motions[k]
+        if m == false then m = { 0, 0 } end
+        if type(m) ~= "table" or #m ~= 2 then
+            log.error("In SimulationHandler.set_collider_motion: motion " .. k .. ": expected false or { vx, vy }")
+            return
+        end
+        arr[k - 1].vx, arr[k - 1].vy = m[1], m[2]
+    end
+    self:_check(lib.egg_set_collider_motion(self._h, n, arr))
+end
+
+--- the motions as stored, one `{ vx, vy }` per collider (zeros included)
+function SimulationHandler:get_collider_motion()
+    local arr, n = ffi.new("egg_collider_motion[?]", _max_colliders), ffi.new("int32_t[1]")
+    if self:_check(lib.egg_get_collider_motion(self._h, _max_colliders, arr, n)) ~= 0 then return {} end
+    local out = {}
+    for k = 0, n[0] - 1 do out[k + 1] = { arr[k].vx, arr[k].vy } end
+    return out
 end
 
 -- Not in the reference, which has no forces as it has no boundary: force fields of the relaxed step (egg_set_forces in

@@ -635,6 +635,14 @@ class ShardedSimulationHandler(_HandlerSurface):
         self.dist.all_reduce(tot, op=self.dist.ReduceOp.SUM)
         return [int(v) for v in tot.tolist()]
 
+    def set_collider_motion(self, motions):
+        """SimulationHandler.set_collider_motion on every rank alike (the same call on every rank).  Nothing new travels:
+        every rank moves its own copy of the list, in every pass and at every commit, by the same arithmetic."""
+        self.local.set_collider_motion(motions)
+
+    def get_collider_motion(self):
+        return self.local.get_collider_motion()
+
     def set_forces(self, forces):
         """SimulationHandler.set_forces on every rank alike (the same call on every rank; relaxed order only).  Nothing
         new travels: every rank accelerates the particles it owns."""

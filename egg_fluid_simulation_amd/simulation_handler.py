@@ -209,6 +209,45 @@ class _HandlerSurface:
         self._check(self._c("get_collider_grips")(grips))
         return list(grips)
 
+    # ------------------------------------------------ collider motion (egg_set_collider_motion)
+    @staticmethod
+    def _c_motions(motions):
+        """a list with one element per collider -- None (at rest) or (vx, vy) -- as an egg_collider_motion array; shape and
+        finiteness are checked here, before any call into the library"""
+        motions = list(motions)
+        arr = (_ffi.EggColliderMotion * max(len(motions), 1))()
+        for k, mo in enumerate(motions):
+            if mo is None:
+                mo = (0.0, 0.0)
+            try:
+                mo = tuple(float(v) for v in mo)
+            except (TypeError, ValueError):
+                raise EggError("collider motion %d: expected None or (vx, vy), not %r" % (k, mo)) from None
+            if len(mo) != 2:
+                raise EggError("collider motion %d: expected None or (vx, vy), not %r" % (k, mo))
+            if not (math.isfinite(mo[0]) and math.isfinite(mo[1])):
+                raise EggError("collider motion %d: the velocity (%r, %r) is not finite" % (k, mo[0], mo[1]))
+            arr[k].vx, arr[k].vy = mo
+        return len(motions), arr
+
+    def set_collider_motion(self, motions):
+        """One motion per collider of the current list ("Collider motion"): `None` for a collider at
+        rest or `(vx, vy)`, a rigid velocity in px/s.  The step integrates it on the device: every sub-step uses the geometry
+        at its end, a moving wall sweeps in its own frame -- it catches what it passes over and carries it on its front
+        side -- and friction is taken relative to the moving surface, so a collider with mu > 0 drags what it touches.  A
+        committed step advances the list get_colliders returns.  `[]` resets every motion to zero, and so does
+        set_colliders; geometry and surfaces stay.  Raises EggError (nothing changes) for a length that is not the collider
+        count or a velocity that is not finite."""
+        n, arr = self._c_motions(motions)
+        self._check(self._c("set_collider_motion")(n, arr))
+
+    def get_collider_motion(self):
+        """the motions as stored, one `(vx, vy)` per collider (zeros included)"""
+        arr = (_ffi.EggColliderMotion * _ffi.MAX_COLLIDERS)()
+        n = C.c_int32()
+        self._check(self._c("get_collider_motion")(_ffi.MAX_COLLIDERS, arr, C.byref(n)))
+        return [(mo.vx, mo.vy) for mo in arr[:n.value]]
+
     # ------------------------------------------------ force fields (egg_set_forces, DESIGN.md section 2.7)
     @staticmethod
     def _c_forces(forces):

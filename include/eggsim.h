@@ -475,6 +475,37 @@ int egg_get_collider_surfaces(const egg_handle *h, int32_t cap, egg_collider_sur
 /* grips per type since the handle was created, over committed steps only: a step that fails or is discarded adds nothing */
 int egg_get_collider_grips(egg_handle *h, int64_t grips[2]);
 
+/* ---- collider motion: a rigid velocity per collider, integrated on the device ("Collider motion") ----
+ * Every collider of the list may carry a MOTION (vx, vy) in px/s, a rigid translation; the default is zero, and a list
+ * whose motions are all zero behaves as a list without motion and launches exactly the kernels it launches without.  The
+ * stored list is the geometry at the start of the step.  With h the sub-step (delta / n_sub_steps, at least eps), S the
+ * sub-step count and sub the 0-based sub-step, every pass of sub-step sub uses the geometry at the sub-step's end:
+ *   t  = (double)(sub + 1) * h;  ox = t vx, oy = t vy
+ *   HALF_PLANE (nx, ny, off):        off' = off + (nx ox + ny oy)                       (the normal does not change)
+ *   DISC, CONTAINER (cx, cy, R):     cx' = cx + ox, cy' = cy + oy
+ *   SEGMENT, WALL (x0, y0, x1, y1):  x0' = x0 + ox, y0' = y0 + oy, x1' = x1 + ox, y1' = y1 + oy
+ * and step 5b runs on the primed parameters as written above.  A moving WALL takes the side of the sub-step's start in
+ * its own frame: pvx = prev.x + h vx, pvy = prev.y + h vy stand wherever the wall rule reads prev (a0, hx, hy).  A wall
+ * that passes over a particle at rest catches it and carries it on its front side; a particle that moves exactly with the
+ * wall is never caught: a particle that starts a sub-step on one side of a wall cannot end a pass on the other, whichever
+ * of the two moved.  Step 5c takes the surface's velocity plus the motion's, and reads the true prev:
+ *   wx = sf.vx + vx, wy = sf.vy + vy;  ex = (x - prev.x) - h wx, ey = (y - prev.y) - h wy;  the rest as written.
+ * So a moving collider with mu > 0 drags what it touches.  FP64 in exactly this order, no contraction.
+ * When a step is committed the stored geometry of every collider becomes its primed geometry with t = (double)S * h -- the
+ * expression of the last sub-step, so the same bits -- and egg_get_colliders returns it; a failed or discarded step
+ * advances nothing.  Motions and surfaces persist across steps.  Only walls sweep: a fast disc, half-plane or container can
+ * still jump over a particle inside one sub-step.  No rotation, no acceleration: a caller changes a velocity between steps.
+ * egg_set_collider_motion: n must equal the current collider count, or 0 (every motion back to zero).  Everything is
+ * checked before anything changes: EGG_ERR_INVALID_ARGUMENT, with the collider's index in the message, for an n that does
+ * not match or a component that is not finite.  It leaves geometry and surfaces alone; egg_set_colliders resets every
+ * motion to zero, egg_set_collider_surfaces leaves them.  A -0.0 is stored as +0.0.  Refused while a step is in flight. */
+typedef struct {
+    double vx, vy; /* px/s */
+} egg_collider_motion; /* 16 bytes */
+int egg_set_collider_motion(egg_handle *h, int32_t n, const egg_collider_motion *m);
+/* the motions as stored, one per collider (zeros included): the count in *n, min(*n, cap) records copied */
+int egg_get_collider_motion(const egg_handle *h, int32_t cap, egg_collider_motion *m, int32_t *n);
+
 /* ---- force fields (not in the reference, which has no forces as it has no boundary; DESIGN.md section 2.7, "Forces") ----
  * A handle holds an ordered list of at most EGG_MAX_FORCES fields.  The values are accelerations in px/s^2 and do not depend
  * on mass.  In every sub-step of a RELAXED step, for every particle of a type, the force step runs before the pre-solve,
@@ -692,6 +723,11 @@ int egg_group_get_collider_hits(egg_group *g, int64_t hits[2]);
  * egg_group_set_colliders resets the surfaces.  A step is refused while the handles differ.  The grips are summed. */
 int egg_group_set_collider_surfaces(egg_group *g, int32_t n, const egg_collider_surface *s);
 int egg_group_get_collider_surfaces(const egg_group *g, int32_t cap, egg_collider_surface *s, int32_t *n);
+/* egg_set_collider_motion for every handle of the group alike, with its rules; a refused call changes no handle, and
+ * egg_group_set_colliders resets the motions.  A step is refused while the handles differ; every handle advances its
+ * stored geometry alike at the commit. */
+int egg_group_set_collider_motion(egg_group *g, int32_t n, const egg_collider_motion *m);
+int egg_group_get_collider_motion(const egg_group *g, int32_t cap, egg_collider_motion *m, int32_t *n);
 int egg_group_get_collider_grips(egg_group *g, int64_t grips[2]);
 /* egg_set_forces for every handle of the group alike, with its rules (relaxed order only; back to exact order only with
  * an empty list); a refused list changes no handle.  Every device accelerates only the particles it owns: the results
