@@ -112,6 +112,10 @@ class EggColliderMotion(C.Structure):  # egg_collider_motion: the rigid velocity
     _fields_ = [("vx", C.c_double), ("vy", C.c_double)]
 
 
+class EggColliderSpin(C.Structure):  # egg_collider_spin: the pivot and angular velocity of a collider (24 bytes)
+    _fields_ = [("px", C.c_double), ("py", C.c_double), ("omega", C.c_double)]
+
+
 MAX_COLLIDERS = 64  # EGG_MAX_COLLIDERS
 COLLIDER_HALF_PLANE, COLLIDER_DISC, COLLIDER_CONTAINER, COLLIDER_SEGMENT = 0, 1, 2, 3
 COLLIDER_KINDS = ("half_plane", "disc", "container", "segment")  # by EGG_COLLIDER_* value: the kinds 0 .. 3
@@ -197,6 +201,10 @@ _SIGNATURES = {
     "egg_get_collider_motion": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggColliderMotion), C.POINTER(C.c_int32)]),
     "egg_group_set_collider_motion": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggColliderMotion)]),
     "egg_group_get_collider_motion": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggColliderMotion), C.POINTER(C.c_int32)]),
+    "egg_set_collider_spin": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggColliderSpin)]),
+    "egg_get_collider_spin": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggColliderSpin), C.POINTER(C.c_int32)]),
+    "egg_group_set_collider_spin": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggColliderSpin)]),
+    "egg_group_get_collider_spin": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggColliderSpin), C.POINTER(C.c_int32)]),
     "egg_group_set_collider_surfaces": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggColliderSurface)]),
     "egg_group_get_collider_surfaces": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggColliderSurface), C.POINTER(C.c_int32)]),
     "egg_group_get_collider_grips": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),

@@ -439,6 +439,54 @@ struct EggRelaxedGroupCohColMovArgs {
     EggRxMotionFields m;
 };
 
+// Collider spin (egg_set_collider_spin, DESIGN.md section 2.7, "Collider spin"): the spin instantiations of the gather
+// kernel (egg_rx_gather*_col_spin_kernel) take these besides everything a motion instantiation takes.  The records are
+// parallel to the collider list, in a small device buffer written when they are set; a record has the layout of the
+// ABI's egg_collider_spin (24 bytes).  The sines and cosines are the host's (libm): a table the host writes once per step,
+// one row of (cos, sin)(t omega) per sub-step and one of (cos, sin)(h omega), each with a pair per collider.  While a spin
+// is not zero the motion and surface records exist for every collider, zeros and defaults included.
+struct EggSpin {
+    double px, py, omega;
+};
+struct EggRxSpinFields {
+    const EggSpin *list;                 // [the collider count]; every lane reads the same record
+    const double2 *cs;                   // [the collider count]: (cos, sin)(t omega), t the end of the pass's sub-step
+    const double2 *hcs;                  // [the collider count]: (cos, sin)(h omega), one sub-step's turn
+    double ts;                           // the start of the pass's sub-step, from the start of the step: sub * sub_delta
+};
+struct EggRelaxedColSpinArgs {
+    EggRelaxedArgs a;
+    EggRxColliderFields d;
+    EggRxSurfaceFields s;
+    EggRxMotionFields m;
+    EggRxSpinFields r;
+};
+struct EggRelaxedGroupColSpinArgs {
+    EggRelaxedArgs a;
+    EggRxGroupFields g;
+    EggRxColliderFields d;
+    EggRxSurfaceFields s;
+    EggRxMotionFields m;
+    EggRxSpinFields r;
+};
+struct EggRelaxedCohColSpinArgs {
+    EggRelaxedArgs a;
+    EggRxCohesionFields c;
+    EggRxColliderFields d;
+    EggRxSurfaceFields s;
+    EggRxMotionFields m;
+    EggRxSpinFields r;
+};
+struct EggRelaxedGroupCohColSpinArgs {
+    EggRelaxedArgs a;
+    EggRxGroupFields g;
+    EggRxCohesionFields c;
+    EggRxColliderFields d;
+    EggRxSurfaceFields s;
+    EggRxMotionFields m;
+    EggRxSpinFields r;
+};
+
 // Force fields (egg_set_forces, DESIGN.md section 2.7, "Forces"): the force instantiations of the kernels that begin a
 // sub-step (egg_rx_begin*_frc_kernel, egg_rx_mid*_frc_kernel) take these besides.  The list is the handle's, in a small
 // device buffer written when it is set; a record has the layout of the ABI's egg_force (40 bytes).

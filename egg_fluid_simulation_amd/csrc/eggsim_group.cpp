@@ -66,6 +66,7 @@ struct egg_group {
     std::vector<egg_collider> colliders;    // egg_group_set_colliders: every handle's list, as given
     std::vector<egg_collider_surface> surfaces;  // egg_group_set_collider_surfaces: every handle's records, as given
     std::vector<egg_collider_motion> motions;    // egg_group_set_collider_motion: every handle's records, as given
+    std::vector<egg_collider_spin> spins;        // egg_group_set_collider_spin: every handle's records, as given
     std::vector<egg_force> forces;          // egg_group_set_forces: every handle's list, as given
     double viscosity[2] = {0.0, 0.0};       // egg_group_set_viscosity: every handle's coefficients
     double containment[2] = {0.0, 1.0};     // egg_group_set_containment: every handle's (factor, strength)
@@ -648,11 +649,12 @@ int egg_group_set_cohesion(egg_group *g, int32_t mode) {
 
 int egg_group_set_colliders(egg_group *g, int32_t n, const egg_collider *c) {
     if (!g) return EGG_ERR_INVALID_ARGUMENT;
-    if (!g->motions.empty() && !g->h.empty()) {  // (committed steps have moved the lists: what a refused call goes back to is the list now)
+    if ((!g->motions.empty() || !g->spins.empty()) && !g->h.empty()) {  // (committed steps have moved the lists: what a refused call goes back to is the list now)
         int32_t have = 0;
         (void)egg_get_colliders(g->h[0], 0, nullptr, &have);
         g->colliders.resize((size_t)have);
         (void)egg_get_colliders(g->h[0], have, g->colliders.data(), &have);
+        if (!g->spins.empty()) (void)egg_get_collider_spin(g->h[0], have, g->spins.data(), &have);  // (and the pivots)
     }
     for (size_t k = 0; k < g->h.size(); ++k) {
         const int rc = egg_set_colliders(g->h[k], n, c);
@@ -661,6 +663,7 @@ int egg_group_set_colliders(egg_group *g, int32_t n, const egg_collider *c) {
                 (void)egg_set_colliders(g->h[j], (int32_t)g->colliders.size(), g->colliders.data());
                 (void)egg_set_collider_surfaces(g->h[j], (int32_t)g->surfaces.size(), g->surfaces.data());
                 (void)egg_set_collider_motion(g->h[j], (int32_t)g->motions.size(), g->motions.data());
+                (void)egg_set_collider_spin(g->h[j], (int32_t)g->spins.size(), g->spins.data());
             }
             return gfail(g, rc, "device %d: %s", (int)k, egg_last_error(g->h[k]));
         }
@@ -668,6 +671,7 @@ int egg_group_set_colliders(egg_group *g, int32_t n, const egg_collider *c) {
     g->colliders.assign(c, c + (n > 0 ? n : 0));
     g->surfaces.clear();  // (every handle has reset its own)
     g->motions.clear();
+    g->spins.clear();
     return EGG_OK;
 }
 
@@ -705,6 +709,28 @@ int egg_group_set_collider_motion(egg_group *g, int32_t n, const egg_collider_mo
 int egg_group_get_collider_motion(const egg_group *g, int32_t cap, egg_collider_motion *m, int32_t *n) {
     if (!g || g->h.empty()) return EGG_ERR_INVALID_ARGUMENT;
     return egg_get_collider_motion(g->h[0], cap, m, n);  // (as stored: every handle holds the same records)
+}
+
+int egg_group_set_collider_spin(egg_group *g, int32_t n, const egg_collider_spin *s) {
+    if (!g) return EGG_ERR_INVALID_ARGUMENT;
+    if (!g->spins.empty() && !g->h.empty()) {  // (committed steps have moved the pivots: what a refused call goes back to is the records now)
+        int32_t have = 0;
+        (void)egg_get_collider_spin(g->h[0], (int32_t)g->spins.size(), g->spins.data(), &have);
+    }
+    for (size_t k = 0; k < g->h.size(); ++k) {
+        const int rc = egg_set_collider_spin(g->h[k], n, s);
+        if (rc < 0) {  // (handle 0 refuses bad records before any handle has changed; a later one: the others go back)
+            for (size_t j = 0; j < k; ++j) (void)egg_set_collider_spin(g->h[j], (int32_t)g->spins.size(), g->spins.data());
+            return gfail(g, rc, "device %d: %s", (int)k, egg_last_error(g->h[k]));
+        }
+    }
+    g->spins.assign(s, s + (n > 0 ? n : 0));
+    return EGG_OK;
+}
+
+int egg_group_get_collider_spin(const egg_group *g, int32_t cap, egg_collider_spin *s, int32_t *n) {
+    if (!g || g->h.empty()) return EGG_ERR_INVALID_ARGUMENT;
+    return egg_get_collider_spin(g->h[0], cap, s, n);  // (as stored: every handle holds the same records)
 }
 
 int egg_group_get_collider_grips(egg_group *g, int64_t grips[2]) {

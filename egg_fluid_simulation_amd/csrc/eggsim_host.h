@@ -100,6 +100,10 @@ extern "C" __global__ void egg_rx_gather_col_mov_kernel(EggRelaxedColMovArgs A);
 extern "C" __global__ void egg_rx_gather_group_col_mov_kernel(EggRelaxedGroupColMovArgs A);
 extern "C" __global__ void egg_rx_gather_coh_col_mov_kernel(EggRelaxedCohColMovArgs A);
 extern "C" __global__ void egg_rx_gather_group_coh_col_mov_kernel(EggRelaxedGroupCohColMovArgs A);
+extern "C" __global__ void egg_rx_gather_col_spin_kernel(EggRelaxedColSpinArgs A);
+extern "C" __global__ void egg_rx_gather_group_col_spin_kernel(EggRelaxedGroupColSpinArgs A);
+extern "C" __global__ void egg_rx_gather_coh_col_spin_kernel(EggRelaxedCohColSpinArgs A);
+extern "C" __global__ void egg_rx_gather_group_coh_col_spin_kernel(EggRelaxedGroupCohColSpinArgs A);
 extern "C" __global__ void egg_rx_begin_frc_kernel(EggRelaxedFrcArgs A);
 extern "C" __global__ void egg_rx_mid_frc_kernel(EggRelaxedFrcArgs A);
 extern "C" __global__ void egg_rx_begin_group_frc_kernel(EggRelaxedGroupFrcArgs A);
@@ -462,6 +466,17 @@ struct egg_handle {
     std::vector<egg_collider_motion> motions;
     DevBuf<EggMotion> d_motions;
     bool motions_move = false;
+    // collider spin (egg_set_collider_spin): empty = every spin is zero, else one record per collider; the copy on the
+    // device (written when they are set and when a commit has advanced the pivots); whether any omega is not zero -- only
+    // then does a step launch the spin instantiations, which read the motion and surface records (d_motions and d_surfaces
+    // then hold one per collider, zeros and defaults included).  spin_table: the step's sines and cosines as prepare_step
+    // computes them (libm), (cos, sin)(t omega) per sub-step and collider, then (cos, sin)(h omega) per collider; the commit
+    // reads the last sub-step's row, the kernels its copy on the device
+    std::vector<egg_collider_spin> spins;
+    DevBuf<EggSpin> d_spins;
+    bool spins_turn = false;
+    std::vector<double2> spin_table;
+    DevBuf<double2> d_spin_table;
     // force fields (egg_set_forces; relaxed order only): the list as egg_get_forces returns it and its copy on the device
     // (written when the list is set, never per step)
     std::vector<egg_force> forces;
@@ -646,6 +661,7 @@ struct RelaxedLayout {
     bool surfaces = false;   // (set by prepare_type: a collider surface of the handle has friction > 0, or walls, or motion)
     bool walls = false;      // (set by prepare_type: the handle's list holds a wall; implies surfaces)
     bool motion = false;     // (set by prepare_type: a collider motion of the handle is not zero; implies surfaces; no word of its own)
+    bool spin = false;       // (set by prepare_type: a collider spin of the handle is not zero; implies surfaces; no word of its own)
     bool coupling = false;   // (set by prepare_type: the step runs coupling passes -- no halo, factor > 0, both types populated)
     bool coupled_word = false;  // (set by prepare_type: coupling, and the type is white: it holds the counter word)
     bool adhesion = false;      // (set by prepare_type: coupling, and the handle's adhesion reach exceeds the coupling factor)
@@ -674,7 +690,8 @@ struct RelaxedStep {  // one type of one handle in a relaxed step
     EggRxCohesionFields coh{};  // effective cohesion (L.cohesion): compliance and factor of the type, the tag arrays
     EggRxColliderFields col{};  // static colliders (L.colliders): the handle's list, the type's bit, the hit counter
     EggRxSurfaceFields srf{};   // collider surfaces (L.surfaces): the handle's records, the sub-step, the grip counter
-    EggRxMotionFields mov{};    // collider motion (L.motion): the handle's records; launch_pass sets the pass's time
+    EggRxMotionFields mov{};    // collider motion (L.motion or L.spin): the handle's records; launch_pass sets the pass's time
+    EggRxSpinFields spn{};      // collider spin (L.spin): the handle's records and table; launch_pass sets the pass's row
     EggRxForceFields frc{};     // force fields (L.forces): the handle's list, the type's bit
     EggRxViscFields visc{};     // viscosity (L.V): the type's coefficient, the pair counter
     double couple_cell = 0, couple_c = 0;  // coupling (L.coupling): the shared cell size H, the compliance of the strength

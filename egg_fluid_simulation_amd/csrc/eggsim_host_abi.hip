@@ -1050,6 +1050,8 @@ int egg_set_colliders(egg_handle *h, int32_t n, const egg_collider *c) {
     h->surfaces_grip = false;
     h->motions.clear();  // (and every motion zero)
     h->motions_move = false;
+    h->spins.clear();  // (and every spin)
+    h->spins_turn = false;
     return EGG_OK;
 }
 
@@ -1091,7 +1093,7 @@ int egg_set_collider_surfaces(egg_handle *h, int32_t n, const egg_collider_surfa
         HIP_TRY(h, hipSetDevice(h->device));
         HIP_TRY(h, h->d_surfaces.reserve(EGG_MAX_COLLIDERS, false, nullptr));
         HIP_TRY(h, hipMemcpy(h->d_surfaces.p, list.data(), (size_t)n * sizeof(egg_collider_surface), hipMemcpyHostToDevice));
-    } else if (h->colliders_wall || h->motions_move) {  // (the wall and motion instantiations go on reading the records: the defaults again)
+    } else if (h->colliders_wall || h->motions_move || h->spins_turn) {  // (the wall, motion and spin instantiations go on reading the records: the defaults again)
         const std::vector<egg_collider_surface> zeros(h->colliders.size(), egg_collider_surface{0.0, 0.0, 0.0});
         HIP_TRY(h, hipSetDevice(h->device));
         HIP_TRY(h, h->d_surfaces.reserve(EGG_MAX_COLLIDERS, false, nullptr));
@@ -1133,6 +1135,12 @@ int egg_set_collider_motion(egg_handle *h, int32_t n, const egg_collider_motion 
         o.vy = o.vy + 0.0;
         move |= o.vx != 0.0 || o.vy != 0.0;
     }
+    if (!move && h->spins_turn) {  // the spin instantiations go on reading a motion record per collider: zeros
+        const std::vector<egg_collider_motion> zeros(h->colliders.size(), egg_collider_motion{0.0, 0.0});
+        HIP_TRY(h, hipSetDevice(h->device));
+        HIP_TRY(h, h->d_motions.reserve(EGG_MAX_COLLIDERS, false, nullptr));
+        HIP_TRY(h, hipMemcpy(h->d_motions.p, zeros.data(), zeros.size() * sizeof(egg_collider_motion), hipMemcpyHostToDevice));
+    }
     if (move) {  // (no step is running: every step ends with its streams waited for)
         HIP_TRY(h, hipSetDevice(h->device));
         HIP_TRY(h, h->d_motions.reserve(EGG_MAX_COLLIDERS, false, nullptr));
@@ -1154,6 +1162,59 @@ int egg_get_collider_motion(const egg_handle *h, int32_t cap, egg_collider_motio
     if (n) *n = have;
     for (int32_t k = 0; mo && k < std::min(cap, have); ++k)
         mo[k] = h->motions.empty() ? egg_collider_motion{0.0, 0.0} : h->motions[(size_t)k];
+    return EGG_OK;
+}
+
+// Collider spin ("Collider spin"): one record per collider, or none (all zero).  Everything is
+// checked before anything changes; geometry, surfaces and motions stay as they are.
+int egg_set_collider_spin(egg_handle *h, int32_t n, const egg_collider_spin *sp) {
+    if (!h) return EGG_ERR_INVALID_ARGUMENT;
+    REJECT_IN_FLIGHT(h, "egg_set_collider_spin");
+    static_assert(sizeof(egg_collider_spin) == 24 && sizeof(EggSpin) == sizeof(egg_collider_spin), "a spin record is 24 bytes");
+    if (n != 0 && n != (int32_t)h->colliders.size())
+        return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_collider_spin: n = %d, the list holds %d colliders (n is that, or 0)", (int)n,
+                    (int)h->colliders.size());
+    if (n > 0 && !sp) return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_collider_spin: n = %d without records", (int)n);
+    std::vector<egg_collider_spin> list((size_t)n);
+    bool turn = false;
+    for (int32_t k = 0; k < n; ++k) {
+        egg_collider_spin &o = list[(size_t)k];
+        o = sp[k];
+        if (!std::isfinite(o.px) || !std::isfinite(o.py))
+            return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_collider_spin: collider %d: the pivot (%g, %g) is not finite", (int)k, o.px, o.py);
+        if (!std::isfinite(o.omega))
+            return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_collider_spin: collider %d: omega %g is not finite", (int)k, o.omega);
+        o.px = o.px + 0.0;  // (-0.0 is stored as +0.0: handles set alike compare alike)
+        o.py = o.py + 0.0;
+        o.omega = o.omega + 0.0;
+        turn |= o.omega != 0.0;
+    }
+    if (turn) {  // (no step is running: every step ends with its streams waited for)
+        HIP_TRY(h, hipSetDevice(h->device));
+        HIP_TRY(h, h->d_spins.reserve(EGG_MAX_COLLIDERS, false, nullptr));
+        HIP_TRY(h, hipMemcpy(h->d_spins.p, list.data(), (size_t)n * sizeof(egg_collider_spin), hipMemcpyHostToDevice));
+        if (!h->motions_move) {  // the spin instantiations read a motion record per collider: zeros, until some move
+            const std::vector<egg_collider_motion> zeros((size_t)n, egg_collider_motion{0.0, 0.0});
+            HIP_TRY(h, h->d_motions.reserve(EGG_MAX_COLLIDERS, false, nullptr));
+            HIP_TRY(h, hipMemcpy(h->d_motions.p, zeros.data(), (size_t)n * sizeof(egg_collider_motion), hipMemcpyHostToDevice));
+        }
+        if (h->surfaces.empty()) {  // ... and a surface record per collider: the defaults, until some are set
+            const std::vector<egg_collider_surface> zeros((size_t)n, egg_collider_surface{0.0, 0.0, 0.0});
+            HIP_TRY(h, h->d_surfaces.reserve(EGG_MAX_COLLIDERS, false, nullptr));
+            HIP_TRY(h, hipMemcpy(h->d_surfaces.p, zeros.data(), (size_t)n * sizeof(egg_collider_surface), hipMemcpyHostToDevice));
+        }
+    }
+    h->spins.swap(list);
+    h->spins_turn = turn;
+    return EGG_OK;
+}
+
+int egg_get_collider_spin(const egg_handle *h, int32_t cap, egg_collider_spin *sp, int32_t *n) {
+    if (!h) return EGG_ERR_INVALID_ARGUMENT;
+    const int32_t have = (int32_t)h->colliders.size();
+    if (n) *n = have;
+    for (int32_t k = 0; sp && k < std::min(cap, have); ++k)
+        sp[k] = h->spins.empty() ? egg_collider_spin{0.0, 0.0, 0.0} : h->spins[(size_t)k];
     return EGG_OK;
 }
 

@@ -27,6 +27,11 @@
 // records and the end time of the pass's sub-step; relaxed_commit advances the handle's stored list by the step and rewrites
 // its copy on the device.  With every motion zero a step launches what it launched, with the same arguments, and a commit
 // touches no list.
+// While a collider spin is not zero (egg_set_collider_spin, RelaxedLayout::spin) launch_pass picks the spin twin of the
+// motion instantiation, whether or not anything moves, and RelaxedStep::spn carries the records and the sub-step's row of
+// the table of sines and cosines prepare_step has computed with libm and copied to the device -- no launch of its own;
+// relaxed_commit advances the stored list and the stored pivots from the last row.  With every spin zero a step launches
+// what it launched, with the same arguments.
 // With force fields (egg_set_forces, RelaxedLayout::forces) launch_substep picks the force instantiation of the begin / mid
 // kernel and RelaxedStep::frc carries the handle's list; with an empty list a step launches what it always launched.
 // With viscosity (egg_set_viscosity, RelaxedLayout::V) every sub-step of a type whose coefficient is not zero ends with
@@ -181,6 +186,23 @@ int prepare_step(egg_handle *h, double delta, int S, RelaxedStep st[2]) {
         if (rc == EGG_OK) rc = upload_atoms(h, w);
         if (rc != EGG_OK) return rc;
     }
+    if (h->spins_turn && !h->colliders.empty()) {
+        // the step's sines and cosines, by the host's libm (the model's): row sub holds (cos, sin)(t omega) with t the end
+        // of sub-step sub, row S holds (cos, sin)(h omega); a pair per collider.  No step is running, so nothing reads the
+        // copy on the device while it is written.
+        const size_t n = h->colliders.size();
+        h->spin_table.assign(((size_t)S + 1) * n, double2{1.0, 0.0});
+        for (int sub = 0; sub <= S; ++sub) {
+            const double t = sub < S ? (double)(sub + 1) * sub_delta : sub_delta;
+            for (size_t k = 0; k < n; ++k) {
+                const double a = t * h->spins[k].omega;
+                h->spin_table[(size_t)sub * n + k] = double2{cos(a), sin(a)};
+            }
+        }
+        HIP_TRY(h, hipSetDevice(h->device));
+        HIP_TRY(h, h->d_spin_table.reserve(h->spin_table.size(), false, nullptr));
+        HIP_TRY(h, hipMemcpy(h->d_spin_table.p, h->spin_table.data(), h->spin_table.size() * sizeof(double2), hipMemcpyHostToDevice));
+    }
     return EGG_OK;
 }
 
@@ -199,7 +221,8 @@ int prepare_type(RelaxedStep &st, int C, size_t ghosts, const RelaxedLayout &L, 
     st.L.colliders = !h->colliders.empty();
     st.L.walls = st.L.colliders && h->colliders_wall;
     st.L.motion = st.L.colliders && h->motions_move;
-    st.L.surfaces = st.L.colliders && (h->surfaces_grip || st.L.walls || st.L.motion);
+    st.L.spin = st.L.colliders && h->spins_turn;
+    st.L.surfaces = st.L.colliders && (h->surfaces_grip || st.L.walls || st.L.motion || st.L.spin);
     st.L.forces = !h->forces.empty();
     st.L.V = h->viscosity[st.w] > 0.0 ? L.P / (size_t)C : 0;
     st.L.coupling = !L.halo && h->coupling_factor > 0.0 && h->sys[0].n > 0 && h->sys[1].n > 0;
@@ -237,7 +260,12 @@ int prepare_type(RelaxedStep &st, int C, size_t ghosts, const RelaxedLayout &L, 
         st.srf.grips = r.status.p + st.L.grips();
     }
     st.mov = EggRxMotionFields{};
-    if (st.L.motion) st.mov.list = h->d_motions.p;
+    if (st.L.motion || st.L.spin) st.mov.list = h->d_motions.p;
+    st.spn = EggRxSpinFields{};
+    if (st.L.spin) {
+        st.spn.list = h->d_spins.p;
+        st.spn.hcs = h->d_spin_table.p + (L.P / (size_t)C) * h->colliders.size();  // (the row behind the sub-steps')
+    }
     st.frc = EggRxForceFields{};
     if (st.L.forces) {
         st.frc.list = h->d_forces.p;
@@ -340,7 +368,11 @@ int launch_pass(RelaxedStep &st, int p) {
                   : st.L.V            ? r.status.p + st.L.box(st.L.P + (size_t)(p / st.C))
                                       : nullptr;
     }
-    if (st.L.motion) st.mov.t = (double)(p / st.C + 1) * st.env.sub_delta;  // the end of the pass's sub-step
+    if (st.L.motion || st.L.spin) st.mov.t = (double)(p / st.C + 1) * st.env.sub_delta;  // the end of the pass's sub-step
+    if (st.L.spin) {
+        st.spn.cs = h->d_spin_table.p + (size_t)(p / st.C) * h->colliders.size();  // the sub-step's row
+        st.spn.ts = (double)(p / st.C) * st.env.sub_delta;                          // ... and its start
+    }
     const dim3 grid((unsigned)((s.n + st.ghost_cap + 255) / 256)), block(256);  // (the ghost count is read on the device)
     HIP_TRY(h, hipMemsetAsync(r.hkey.p, 0xFF, (size_t)r.table * 8, s.stream));
     HIP_TRY(h, hipMemsetAsync(r.hcount.p, 0, ((size_t)r.table + 1) * 4, s.stream));
@@ -355,7 +387,10 @@ int launch_pass(RelaxedStep &st, int p) {
         if (st.L.cohesion) {
             const EggRelaxedGroupCohArgs k{a.a, a.g, st.coh};
             hipLaunchKernelGGL(egg_rx_rank_group_coh_kernel, grid, block, 0, s.stream, k);
-            if (st.L.motion)
+            if (st.L.spin)
+                hipLaunchKernelGGL(egg_rx_gather_group_coh_col_spin_kernel, grid, block, 0, s.stream,
+                                   EggRelaxedGroupCohColSpinArgs{a.a, a.g, st.coh, st.col, st.srf, st.mov, st.spn});
+            else if (st.L.motion)
                 hipLaunchKernelGGL(egg_rx_gather_group_coh_col_mov_kernel, grid, block, 0, s.stream,
                                    EggRelaxedGroupCohColMovArgs{a.a, a.g, st.coh, st.col, st.srf, st.mov});
             else if (st.L.walls)
@@ -370,7 +405,10 @@ int launch_pass(RelaxedStep &st, int p) {
                 hipLaunchKernelGGL(egg_rx_gather_group_coh_kernel, grid, block, 0, s.stream, k);
         } else {
             hipLaunchKernelGGL(egg_rx_rank_group_kernel, grid, block, 0, s.stream, a);
-            if (st.L.motion)
+            if (st.L.spin)
+                hipLaunchKernelGGL(egg_rx_gather_group_col_spin_kernel, grid, block, 0, s.stream,
+                                   EggRelaxedGroupColSpinArgs{a.a, a.g, st.col, st.srf, st.mov, st.spn});
+            else if (st.L.motion)
                 hipLaunchKernelGGL(egg_rx_gather_group_col_mov_kernel, grid, block, 0, s.stream,
                                    EggRelaxedGroupColMovArgs{a.a, a.g, st.col, st.srf, st.mov});
             else if (st.L.walls)
@@ -389,7 +427,10 @@ int launch_pass(RelaxedStep &st, int p) {
         if (st.L.cohesion) {
             const EggRelaxedCohArgs k{a.a, st.coh};
             hipLaunchKernelGGL(egg_rx_rank_coh_kernel, grid, block, 0, s.stream, k);
-            if (st.L.motion)
+            if (st.L.spin)
+                hipLaunchKernelGGL(egg_rx_gather_coh_col_spin_kernel, grid, block, 0, s.stream,
+                                   EggRelaxedCohColSpinArgs{a.a, st.coh, st.col, st.srf, st.mov, st.spn});
+            else if (st.L.motion)
                 hipLaunchKernelGGL(egg_rx_gather_coh_col_mov_kernel, grid, block, 0, s.stream,
                                    EggRelaxedCohColMovArgs{a.a, st.coh, st.col, st.srf, st.mov});
             else if (st.L.walls)
@@ -404,7 +445,10 @@ int launch_pass(RelaxedStep &st, int p) {
                 hipLaunchKernelGGL(egg_rx_gather_coh_kernel, grid, block, 0, s.stream, k);
         } else {
             hipLaunchKernelGGL(egg_rx_rank_kernel, grid, block, 0, s.stream, a.a);
-            if (st.L.motion)
+            if (st.L.spin)
+                hipLaunchKernelGGL(egg_rx_gather_col_spin_kernel, grid, block, 0, s.stream,
+                                   EggRelaxedColSpinArgs{a.a, st.col, st.srf, st.mov, st.spn});
+            else if (st.L.motion)
                 hipLaunchKernelGGL(egg_rx_gather_col_mov_kernel, grid, block, 0, s.stream,
                                    EggRelaxedColMovArgs{a.a, st.col, st.srf, st.mov});
             else if (st.L.walls)
@@ -683,12 +727,38 @@ static int relaxed_finish(egg_handle *h, RelaxedStep st[2], int S, int C) {
 // Collider motion at the commit: the stored geometry of every collider becomes the geometry of the step's end, t = S h
 // -- the expression the kernels of the last sub-step evaluated, so the same bits -- and the copy on the device follows.
 // No step is running: every path waits for its streams before it commits.
-static void advance_colliders(egg_handle *h, double t) {
-    for (size_t k = 0; k < h->colliders.size(); ++k) {
+// Collider spin: a collider whose omega is not zero turns about its pivot, which rides on its motion, by the (c, s) of the
+// last sub-step's row of the step's table, and its stored pivot becomes the pivot of the step's end; the spin records on
+// the device follow.
+static void advance_colliders(egg_handle *h, double t, int S) {
+    const size_t n = h->colliders.size();
+    for (size_t k = 0; k < n; ++k) {
         egg_collider &c = h->colliders[k];
-        const egg_collider_motion &m = h->motions[k];
+        const egg_collider_motion m = h->motions.empty() ? egg_collider_motion{0.0, 0.0} : h->motions[k];
         const double ox = t * m.vx, oy = t * m.vy;
-        if (c.kind == EGG_COLLIDER_HALF_PLANE) {
+        if (h->spins_turn && h->spins[k].omega != 0.0) {
+            egg_collider_spin &sp = h->spins[k];
+            const double2 cs = h->spin_table[(size_t)(S - 1) * n + k];
+            const double Px = sp.px + ox, Py = sp.py + oy;
+            if (c.kind == EGG_COLLIDER_HALF_PLANE) {
+                const double keep = c.p[2] - (c.p[0] * sp.px + c.p[1] * sp.py);
+                const double nx = cs.x * c.p[0] - cs.y * c.p[1], ny = cs.y * c.p[0] + cs.x * c.p[1];
+                c.p[0] = nx;
+                c.p[1] = ny;
+                c.p[2] = (nx * Px + ny * Py) + keep;
+            } else {
+                const double rx = c.p[0] - sp.px, ry = c.p[1] - sp.py;
+                c.p[0] = Px + (cs.x * rx - cs.y * ry);
+                c.p[1] = Py + (cs.y * rx + cs.x * ry);
+                if (c.kind == EGG_COLLIDER_SEGMENT || c.kind == EGG_COLLIDER_WALL) {
+                    const double qx = c.p[2] - sp.px, qy = c.p[3] - sp.py;
+                    c.p[2] = Px + (cs.x * qx - cs.y * qy);
+                    c.p[3] = Py + (cs.y * qx + cs.x * qy);
+                }
+            }
+            sp.px = Px;
+            sp.py = Py;
+        } else if (c.kind == EGG_COLLIDER_HALF_PLANE) {
             c.p[2] = c.p[2] + (c.p[0] * ox + c.p[1] * oy);
         } else {
             c.p[0] = c.p[0] + ox;
@@ -702,6 +772,8 @@ static void advance_colliders(egg_handle *h, double t) {
     hipError_t e = hipSetDevice(h->device);
     if (e == hipSuccess)
         e = hipMemcpy(h->d_colliders.p, h->colliders.data(), h->colliders.size() * sizeof(egg_collider), hipMemcpyHostToDevice);
+    if (e == hipSuccess && h->spins_turn)
+        e = hipMemcpy(h->d_spins.p, h->spins.data(), h->spins.size() * sizeof(egg_collider_spin), hipMemcpyHostToDevice);
     if (e != hipSuccess) (void)fail(h, EGG_ERR_DEVICE, "relaxed order: the moved colliders did not reach the device: %s", hipGetErrorString(e));
 }
 
@@ -734,7 +806,7 @@ void relaxed_commit(egg_handle *h, const RelaxedStep st[2], int S, int C, double
         s.aabb_valid = s.aabb_on_device = s.disp_valid = false;
         s.out_copied = false;
     }
-    if (h->motions_move && !h->colliders.empty()) advance_colliders(h, (double)S * st[0].env.sub_delta);
+    if ((h->motions_move || h->spins_turn) && !h->colliders.empty()) advance_colliders(h, (double)S * st[0].env.sub_delta, S);
     h->stats.last_step_kernel_ms = ms;
     if (h->opt_timing) {
         for (int w = 0; w < 2; ++w) h->stats.kernel_ms_sum[w] += h->stats.kernel_ms[w];

@@ -133,6 +133,15 @@ int relaxed_group_step(egg_handle *const *hs, int nh, double delta, int S, int C
             return EGG_ERR_INVALID_ARGUMENT;
         }
     }
+    for (int k = 1; k < nh; ++k) {  // (all zeros and none compare alike: neither turns anything)
+        const std::vector<egg_collider_spin> &a = hs[0]->spins, &b = hs[k]->spins;
+        const bool same_spin = hs[0]->spins_turn == hs[k]->spins_turn &&
+                               (!hs[0]->spins_turn || (a.size() == b.size() && memcmp(a.data(), b.data(), a.size() * sizeof(egg_collider_spin)) == 0));
+        if (!same_spin) {
+            *error = "relaxed order: the handles of the group differ in their collider spin (egg_group_set_collider_spin sets all)";
+            return EGG_ERR_INVALID_ARGUMENT;
+        }
+    }
     for (int k = 1; k < nh; ++k) {
         const std::vector<egg_force> &a = hs[0]->forces, &b = hs[k]->forces;
         if (a.size() != b.size() || (!a.empty() && memcmp(a.data(), b.data(), a.size() * sizeof(egg_force)) != 0)) {

@@ -47,6 +47,12 @@
 // where it is at the end of the pass's sub-step, a wall sweeps in its own frame, and friction is taken relative to the
 // moving surface.  Every other instantiation is the kernel as it was.
 //
+// While a collider's spin is not zero (egg_set_collider_spin; DESIGN.md section 2.7, "Collider spin") the motion twins run
+// as their spin twins (egg_rx_gather*_col_spin_kernel, which take EggRxSpinFields besides): a collider with omega != 0 is
+// turned about its pivot, which rides on its motion, by the angle of the sub-step's end -- sines and cosines are the
+// host's --, a turning wall sweeps from the sub-step's start turned along with it by one sub-step, and friction takes the
+// surface's velocity at the contact point.  A collider with omega == 0 takes the motion twin's expressions.
+//
 // With force fields (egg_set_forces; DESIGN.md section 2.7, "Forces") the kernels that begin a sub-step run in their force
 // instantiations (F = true, egg_rx_begin*_frc_kernel, egg_rx_mid*_frc_kernel): the fields of the handle's list whose mask
 // covers the type accelerate the velocity the pre-solve is about to damp.  The F = false instantiations are the kernels
@@ -156,6 +162,28 @@ __device__ __forceinline__ int rx_grip(const EggSurface &sf, double h, double2 p
     return 1;
 }
 
+// Step 5c against a turning collider: the surface's velocity at the point `at` the projection has just produced, about the
+// pivot (Px, Py) of the sub-step's end.  sf.vx / sf.vy already hold the surface's velocity plus the motion's.
+__device__ __forceinline__ EggSurface rx_turning(const EggSurface &sf, double omega, double Px, double Py, const double2 &at) {
+    EggSurface w = sf;
+    w.vx = sf.vx - omega * (at.y - Py);
+    w.vy = sf.vy + omega * (at.x - Px);
+    return w;
+}
+
+// The start pv of the sub-step carried along with a turning wall by one sub-step: about the pivot where it was at the
+// sub-step's start, to the pivot (Px, Py) of its end.  The records are read here once more: nothing of them stays in
+// registers over the collider's whole rule.
+__device__ __forceinline__ double2 rx_carried(const EggRxSpinFields *Sp, const EggRxMotionFields *Mo, int c, double Px, double Py,
+                                              double2 pv) {
+    const EggSpin sp = Sp->list[c];
+    const EggMotion mo = Mo->list[c];
+    const double2 hcs = Sp->hcs[c];  // one sub-step's turn
+    const double psx = rx_uniform(sp.px + Sp->ts * mo.vx), psy = rx_uniform(sp.py + Sp->ts * mo.vy);
+    const double ux = pv.x - psx, uy = pv.y - psy;
+    return make_double2(Px + (hcs.x * ux - hcs.y * uy), Py + (hcs.y * ux + hcs.x * uy));
+}
+
 // Step 5b of the relaxed pass: the colliders of the list whose mask covers the type, in list order, each on the result
 // of the one before it.  i: the particle's key (picks the way out of a disc's centre); r: its radius.  Every lane of a
 // wave reads the same record and takes the same branch on its kind.  Every comparison is false for a NaN: such a
@@ -172,21 +200,59 @@ __device__ __forceinline__ int rx_grip(const EggSurface &sf, double h, double2 p
 // is read like the collider record; the parameters of the sub-step's end are computed once per collider, in front of the
 // branch on its kind, and go back to scalar registers (rx_uniform); a wall sweeps from pv carried along with it by one
 // sub-step; step 5c takes the surface's velocity plus the motion's and reads the true pv.
-template <bool S, bool W>
+// P (with Mo only; Sp): every collider may turn (egg_set_collider_spin; DESIGN.md section 2.7, "Collider spin").  Here the
+// switch is a template parameter, picked by rx_gather from its own pointer: read from the pointer in this function, as M
+// is, it left one addition of the wall and motion instantiations with its operands exchanged.  `turns` is the collider's
+// own omega != 0, alike in every lane: such a collider takes the spin rule, whose primed parameters also go back to
+// scalar registers; any other takes the motion rule as it stands.  Only the carried start of a turning wall and the
+// surface's velocity at the contact point are per lane.
+template <bool S, bool W, bool P>
 __device__ __forceinline__ int rx_collide(const EggRxColliderFields &Co, const EggRxSurfaceFields &Su, const EggRxMotionFields *Mo,
-                                          int i, double r, double2 pv, double2 &out, int &grips) {
+                                          const EggRxSpinFields *Sp, int i, double r, double2 pv, double2 &out, int &grips) {
     const bool M = W && Mo != nullptr;
+    static_assert(W || !P, "the spin instantiations are wall instantiations");
     int hits = 0;
     for (int c = 0; c < Co.count; ++c) {
         EggCollider col = Co.list[c];
         if (!(col.type_mask & Co.type_bit)) continue;
         EggSurface sf{};
         if (S) sf = Su.list[c];
+        bool turns = false;  // (P: this collider's omega is not zero; alike in every lane)
+        double omega = 0.0, Px = 0.0, Py = 0.0;  // (P, read when it turns: the spin, the pivot at the sub-step's end)
         double hvx = 0.0, hvy = 0.0;  // (M: how far the collider carries the sub-step's start along, what a moving wall sweeps from)
         if (M) {  // the geometry at the end of the pass's sub-step, once per collider; step 5c adds the motion to the surface's velocity
             const EggMotion mo = Mo->list[c];
             const double ox = Mo->t * mo.vx, oy = Mo->t * mo.vy;
-            if (col.kind == EGG_RX_COLLIDER_HALF_PLANE) {
+            if (P) {
+                const EggSpin sp = Sp->list[c];
+                turns = ((unsigned long long)__double_as_longlong(sp.omega) << 1) != 0ull;  // (omega != 0, on the scalar unit)
+                if (turns) {  // about the pivot, which rides on the motion; (c, s) of the sub-step's end from the host's table
+                    const double2 cs = Sp->cs[c];
+                    omega = sp.omega;
+                    Px = rx_uniform(sp.px + ox);
+                    Py = rx_uniform(sp.py + oy);
+                    if (col.kind == EGG_RX_COLLIDER_HALF_PLANE) {  // the pivot's signed distance to the plane is kept
+                        const double keep = col.p[2] - (col.p[0] * sp.px + col.p[1] * sp.py);
+                        const double nx = rx_uniform(cs.x * col.p[0] - cs.y * col.p[1]);
+                        const double ny = rx_uniform(cs.y * col.p[0] + cs.x * col.p[1]);
+                        col.p[0] = nx;
+                        col.p[1] = ny;
+                        col.p[2] = rx_uniform((nx * Px + ny * Py) + keep);
+                    } else {
+                        const double rx = col.p[0] - sp.px, ry = col.p[1] - sp.py;
+                        col.p[0] = rx_uniform(Px + (cs.x * rx - cs.y * ry));
+                        col.p[1] = rx_uniform(Py + (cs.y * rx + cs.x * ry));
+                        if (col.kind == EGG_RX_COLLIDER_SEGMENT || col.kind == EGG_RX_COLLIDER_WALL) {
+                            const double qx = col.p[2] - sp.px, qy = col.p[3] - sp.py;
+                            col.p[2] = rx_uniform(Px + (cs.x * qx - cs.y * qy));
+                            col.p[3] = rx_uniform(Py + (cs.y * qx + cs.x * qy));
+                        }
+                    }
+                }
+            }
+            if (P && turns) {
+                // (primed above)
+            } else if (col.kind == EGG_RX_COLLIDER_HALF_PLANE) {
                 col.p[2] = rx_uniform(col.p[2] + (col.p[0] * ox + col.p[1] * oy));
             } else {
                 col.p[0] = rx_uniform(col.p[0] + ox);
@@ -201,7 +267,9 @@ __device__ __forceinline__ int rx_collide(const EggRxColliderFields &Co, const E
             sf.vx = rx_uniform(sf.vx + mo.vx);
             sf.vy = rx_uniform(sf.vy + mo.vy);
         }
-        const double2 pw = M ? make_double2(pv.x + hvx, pv.y + hvy) : pv;
+        const double2 pw = M ? (P && turns && col.kind == EGG_RX_COLLIDER_WALL ? rx_carried(Sp, Mo, c, Px, Py, pv)
+                                                                               : make_double2(pv.x + hvx, pv.y + hvy))
+                             : pv;
         const double x = out.x, y = out.y;
         if (col.kind == EGG_RX_COLLIDER_HALF_PLANE) {  // p = (nx, ny, off): keeps n . pos - off >= r
             const double s = (col.p[0] * x + col.p[1] * y) - (col.p[2] + r);
@@ -209,7 +277,7 @@ __device__ __forceinline__ int rx_collide(const EggRxColliderFields &Co, const E
                 out.x = x - s * col.p[0];
                 out.y = y - s * col.p[1];
                 ++hits;
-                if (S) grips += rx_grip(sf, Su.sub_delta, pv, col.p[0], col.p[1], -s, out);
+                if (S) grips += rx_grip(P && turns ? rx_turning(sf, omega, Px, Py, out) : sf, Su.sub_delta, pv, col.p[0], col.p[1], -s, out);
             }
             continue;
         }
@@ -247,7 +315,7 @@ __device__ __forceinline__ int rx_collide(const EggRxColliderFields &Co, const E
                 out.x = cx + (dx / d) * m;
                 out.y = cy + (dy / d) * m;
                 ++hits;
-                if (S) grips += rx_grip(sf, Su.sub_delta, pv, dx / d, dy / d, d - m, out);
+                if (S) grips += rx_grip(P && turns ? rx_turning(sf, omega, Px, Py, out) : sf, Su.sub_delta, pv, dx / d, dy / d, d - m, out);
             }
         } else {  // disc, p = (cx, cy, R): stays outside
             const double m = R + r;
@@ -273,7 +341,7 @@ __device__ __forceinline__ int rx_collide(const EggRxColliderFields &Co, const E
                 out.x = cx + ux * m;
                 out.y = cy + uy * m;
                 ++hits;
-                if (S) grips += rx_grip(sf, Su.sub_delta, pv, ux, uy, pen, out);
+                if (S) grips += rx_grip(P && turns ? rx_turning(sf, omega, Px, Py, out) : sf, Su.sub_delta, pv, ux, uy, pen, out);
             }
         }
     }
@@ -468,11 +536,11 @@ __device__ __forceinline__ void rx_rank(const EggRelaxedArgs &A, const EggRxGrou
 // new position goes through the colliders before it is written (whether or not a pair fired).  S (with D only): a
 // collider's surface acts right after its projection (step 5c); prev[me] is read once, for that.  W (with S only): the
 // list may hold walls, which sweep from the same prev[me].  Mo (with W only): not null in the motion instantiations, whose
-// colliders move (rx_collide).
+// colliders move (rx_collide).  Sp (with Mo only): not null in the spin instantiations, whose colliders turn besides.
 template <bool G, bool K, bool D, bool S, bool W>
 __device__ __forceinline__ void rx_gather(EggRelaxedArgs A, const EggRxGroupFields &X, const EggRxCohesionFields &Ch,
                                           const EggRxColliderFields &Co, const EggRxSurfaceFields &Su,
-                                          const EggRxMotionFields *Mo = nullptr) {
+                                          const EggRxMotionFields *Mo = nullptr, const EggRxSpinFields *Sp = nullptr) {
     static_assert(D || !S, "surfaces belong to colliders");
     static_assert(S || !W, "the wall instantiations are surface instantiations");
     const int t = (int)(blockIdx.x * 256 + threadIdx.x);
@@ -562,7 +630,11 @@ __device__ __forceinline__ void rx_gather(EggRelaxedArgs A, const EggRxGroupFiel
             out.x = p.x + (sx * A.omega) / (double)n_fired;
             out.y = p.y + (sy * A.omega) / (double)n_fired;
         }
-        if (D) hits = rx_collide<S, W>(Co, Su, Mo, i, wr.y, S ? A.prev[me] : make_double2(0.0, 0.0), out, grips);
+        if (D) {
+            const double2 pv = S ? A.prev[me] : make_double2(0.0, 0.0);
+            hits = W && Sp != nullptr ? rx_collide<S, W, W>(Co, Su, Mo, Sp, i, wr.y, pv, out, grips)
+                                      : rx_collide<S, W, false>(Co, Su, Mo, Sp, i, wr.y, pv, out, grips);
+        }
         A.pos_next[me] = out;
         if (G) {
             local = true;
@@ -627,6 +699,12 @@ extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_col_mov_kernel(E
 extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_col_mov_kernel(EggRelaxedGroupColMovArgs A) { rx_gather<true, false, true, true, true>(A.a, A.g, EggRxCohesionFields{}, A.d, A.s, &A.m); }
 extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_coh_col_mov_kernel(EggRelaxedCohColMovArgs A) { rx_gather<false, true, true, true, true>(A.a, EggRxGroupFields{}, A.c, A.d, A.s, &A.m); }
 extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_coh_col_mov_kernel(EggRelaxedGroupCohColMovArgs A) { rx_gather<true, true, true, true, true>(A.a, A.g, A.c, A.d, A.s, &A.m); }
+
+// collider spin (colliders, surfaces, walls and motion all on)
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_col_spin_kernel(EggRelaxedColSpinArgs A) { rx_gather<false, false, true, true, true>(A.a, EggRxGroupFields{}, EggRxCohesionFields{}, A.d, A.s, &A.m, &A.r); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_col_spin_kernel(EggRelaxedGroupColSpinArgs A) { rx_gather<true, false, true, true, true>(A.a, A.g, EggRxCohesionFields{}, A.d, A.s, &A.m, &A.r); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_coh_col_spin_kernel(EggRelaxedCohColSpinArgs A) { rx_gather<false, true, true, true, true>(A.a, EggRxGroupFields{}, A.c, A.d, A.s, &A.m, &A.r); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_coh_col_spin_kernel(EggRelaxedGroupCohColSpinArgs A) { rx_gather<true, true, true, true, true>(A.a, A.g, A.c, A.d, A.s, &A.m, &A.r); }
 
 // ---- viscosity ----
 

@@ -96,6 +96,9 @@ int egg_get_collider_surfaces(const egg_handle *h, int32_t cap, egg_collider_sur
 typedef struct { double vx, vy; } egg_collider_motion;
 int egg_set_collider_motion(egg_handle *h, int32_t n, const egg_collider_motion *m);
 int egg_get_collider_motion(const egg_handle *h, int32_t cap, egg_collider_motion *m, int32_t *n);
+typedef struct { double px, py, omega; } egg_collider_spin;
+int egg_set_collider_spin(egg_handle *h, int32_t n, const egg_collider_spin *s);
+int egg_get_collider_spin(const egg_handle *h, int32_t cap, egg_collider_spin *s, int32_t *n);
 int egg_get_collider_grips(egg_handle *h, int64_t grips[2]);
 typedef struct egg_group egg_group;
 int egg_group_set_solver_order(egg_group *g, int32_t order, double relaxation);
@@ -543,6 +546,36 @@ function SimulationHandler:get_collider_motion()
     if self:_check(lib.egg_get_collider_motion(self._h, _max_colliders, arr, n)) ~= 0 then return {} end
     local out = {}
     for k = 0, n[0] - 1 do out[k + 1] = { arr[k].vx, arr[k].vy } end
+    return out
+end
+
+-- Not in the reference: collider spin (egg_set_collider_spin in include/eggsim.h; DESIGN.md section 2.7,
+-- "Collider spin").
+
+--- one spin per collider of the current list: `false` for a collider that does not turn or `{ px, py, omega }`, a rigid
+--- angular velocity in rad/s (counter-clockwise positive) about the pivot (px, py) that the step integrates on the device.
+--- `{}` resets every spin to zero, and so does set_colliders.
+function SimulationHandler:set_collider_spin(spins)
+    local n = #spins
+    local arr = ffi.new("egg_collider_spin[?]", math.max(n, 1))
+    for k = 1, n do  -- (not ipairs: a nil hole must not end the walk short of n)
+        local s = spins[k]
+        if s == false then s = { 0, 0, 0 } end
+        if type(s) ~= "table" or #s ~= 3 then
+            log.error("In SimulationHandler.set_collider_spin: spin " .. k .. ": expected false or { px, py, omega }")
+            return
+        end
+        arr[k - 1].px, arr[k - 1].py, arr[k - 1].omega = s[1], s[2], s[3]
+    end
+    self:_check(lib.egg_set_collider_spin(self._h, n, arr))
+end
+
+--- the spins as stored, one `{ px, py, omega }` per collider (zeros included); a committed step advances the pivots
+function SimulationHandler:get_collider_spin()
+    local arr, n = ffi.new("egg_collider_spin[?]", _max_colliders), ffi.new("int32_t[1]")
+    if self:_check(lib.egg_get_collider_spin(self._h, _max_colliders, arr, n)) ~= 0 then return {} end
+    local out = {}
+    for k = 0, n[0] - 1 do out[k + 1] = { arr[k].px, arr[k].py, arr[k].omega } end
     return out
 end
 

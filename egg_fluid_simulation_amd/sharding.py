@@ -643,6 +643,14 @@ class ShardedSimulationHandler(_HandlerSurface):
     def get_collider_motion(self):
         return self.local.get_collider_motion()
 
+    def set_collider_spin(self, spins):
+        """SimulationHandler.set_collider_spin on every rank alike (the same call on every rank).  Nothing new travels:
+        every rank turns its own copy of the list, in every pass and at every commit, by the same arithmetic."""
+        self.local.set_collider_spin(spins)
+
+    def get_collider_spin(self):
+        return self.local.get_collider_spin()
+
     def set_forces(self, forces):
         """SimulationHandler.set_forces on every rank alike (the same call on every rank; relaxed order only).  Nothing
         new travels: every rank accelerates the particles it owns."""

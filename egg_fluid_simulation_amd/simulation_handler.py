@@ -248,6 +248,48 @@ class _HandlerSurface:
         self._check(self._c("get_collider_motion")(_ffi.MAX_COLLIDERS, arr, C.byref(n)))
         return [(mo.vx, mo.vy) for mo in arr[:n.value]]
 
+    # ------------------------------------------------ collider spin (egg_set_collider_spin)
+    @staticmethod
+    def _c_spins(spins):
+        """a list with one element per collider -- None (no spin) or (px, py, omega) -- as an egg_collider_spin array; shape
+        and finiteness are checked here, before any call into the library"""
+        spins = list(spins)
+        arr = (_ffi.EggColliderSpin * max(len(spins), 1))()
+        for k, sp in enumerate(spins):
+            if sp is None:
+                sp = (0.0, 0.0, 0.0)
+            try:
+                sp = tuple(float(v) for v in sp)
+            except (TypeError, ValueError):
+                raise EggError("collider spin %d: expected None or (px, py, omega), not %r" % (k, sp)) from None
+            if len(sp) != 3:
+                raise EggError("collider spin %d: expected None or (px, py, omega), not %r" % (k, sp))
+            if not (math.isfinite(sp[0]) and math.isfinite(sp[1])):
+                raise EggError("collider spin %d: the pivot (%r, %r) is not finite" % (k, sp[0], sp[1]))
+            if not math.isfinite(sp[2]):
+                raise EggError("collider spin %d: omega %r is not finite" % (k, sp[2]))
+            arr[k].px, arr[k].py, arr[k].omega = sp
+        return len(spins), arr
+
+    def set_collider_spin(self, spins):
+        """One spin per collider of the current list ("Collider spin"): `None` for a collider that
+        does not turn or `(px, py, omega)`, a rigid angular velocity in rad/s, counter-clockwise positive, about the pivot
+        (px, py), which rides on the collider's motion.  The step integrates it on the device: every sub-step uses the
+        geometry at its end, a turning wall sweeps in its own frame -- it catches what it passes over -- and friction takes
+        the surface's velocity at the contact point, so a disc spinning about its centre with mu > 0 drags what it touches.
+        A committed step advances the list get_colliders returns and the pivots get_collider_spin returns.  `[]` resets
+        every spin to zero, and so does set_colliders; geometry, surfaces and motions stay.  Raises EggError (nothing
+        changes) for a length that is not the collider count or a component that is not finite."""
+        n, arr = self._c_spins(spins)
+        self._check(self._c("set_collider_spin")(n, arr))
+
+    def get_collider_spin(self):
+        """the spins as stored, one `(px, py, omega)` per collider (zeros included)"""
+        arr = (_ffi.EggColliderSpin * _ffi.MAX_COLLIDERS)()
+        n = C.c_int32()
+        self._check(self._c("get_collider_spin")(_ffi.MAX_COLLIDERS, arr, C.byref(n)))
+        return [(sp.px, sp.py, sp.omega) for sp in arr[:n.value]]
+
     # ------------------------------------------------ force fields (egg_set_forces, DESIGN.md section 2.7)
     @staticmethod
     def _c_forces(forces):

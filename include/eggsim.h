@@ -506,6 +506,44 @@ int egg_set_collider_motion(egg_handle *h, int32_t n, const egg_collider_motion 
 /* the motions as stored, one per collider (zeros included): the count in *n, min(*n, cap) records copied */
 int egg_get_collider_motion(const egg_handle *h, int32_t cap, egg_collider_motion *m, int32_t *n);
 
+/* ---- collider spin: a rigid angular velocity per collider about a pivot ("Collider spin") ----
+ * Every collider of the list may carry a SPIN (px, py, omega): it turns about the pivot (px, py), in px at the start of the
+ * step, at omega rad/s, counter-clockwise positive in the project's x/y.  The default is zero, and a list whose spins are all
+ * zero behaves as a list without spin and launches exactly the kernels it launches without.  A collider whose omega is zero
+ * takes the expressions of collider motion exactly as they stand.  For one whose omega is not zero, with h, S, sub, t, ox, oy
+ * and (vx, vy) as above (its motion, zero by default):
+ *   Px = px + ox, Py = py + oy                                   the pivot rides on the collider's motion
+ *   c = cos(t omega), s = sin(t omega)                           computed on the host (libm), handed to the kernel
+ *   a point (qx, qy) of the stored geometry:  rx = qx - px, ry = qy - py,
+ *                                             qx' = Px + (c rx - s ry), qy' = Py + (s rx + c ry)
+ *   DISC, CONTAINER: the centre is such a point, R unchanged;  SEGMENT, WALL: both end points
+ *   HALF_PLANE (nx, ny, off):  nx' = c nx - s ny, ny' = s nx + c ny,
+ *                              off' = (nx' Px + ny' Py) + (off - (nx px + ny py))   (the pivot's signed distance is kept)
+ * and step 5b runs on the primed parameters.  A turning WALL takes the side of the sub-step's start carried along with it
+ * over ONE sub-step: with ts = (double)sub * h, ch = cos(h omega), sh = sin(h omega) (host, once per step),
+ *   ux = prev.x - (px + ts vx), uy = prev.y - (py + ts vy);  pvx = Px + (ch ux - sh uy), pvy = Py + (sh ux + ch uy)
+ * stand wherever the wall rule reads prev.  Step 5c takes the surface's velocity at the contact point, (x, y) being the
+ * position the projection has just produced, and reads the true prev:
+ *   wx = (sf.vx + vx) - omega (y - Py), wy = (sf.vy + vy) + omega (x - Px)
+ * So a disc that spins about its own centre keeps its geometry and drags what touches it when mu > 0.  FP64 in exactly this
+ * order, no contraction.  When a step is committed the stored geometry, and the stored pivot, become the primed values with
+ * t = (double)S * h, computed on the host from the c, s the last sub-step used, so the same bits; egg_get_colliders and
+ * egg_get_collider_spin return them.  A failed or discarded step advances nothing.  There is no exact-order rule and no
+ * counter of its own: a catch by a turning wall is a hit, a grip is a grip.  No angular acceleration; only walls sweep; a
+ * half-plane's normal is not renormalised after it turns and end points are not re-spaced (DESIGN.md has the drift).
+ * egg_set_collider_spin: n must equal the current collider count, or 0 (every spin back to zero).  Everything is checked
+ * before anything changes: EGG_ERR_INVALID_ARGUMENT, with the collider's index in the message, for an n that does not match
+ * or a component that is not finite.  It leaves geometry, surfaces and motions alone; egg_set_colliders resets every spin
+ * to zero, egg_set_collider_motion and egg_set_collider_surfaces leave them.  A -0.0 is stored as +0.0 and counts as zero.
+ * Refused while a step is in flight. */
+typedef struct {
+    double px, py; /* the pivot, px */
+    double omega;  /* rad/s, counter-clockwise positive */
+} egg_collider_spin; /* 24 bytes */
+int egg_set_collider_spin(egg_handle *h, int32_t n, const egg_collider_spin *s);
+/* the spins as stored, one per collider (zeros included): the count in *n, min(*n, cap) records copied */
+int egg_get_collider_spin(const egg_handle *h, int32_t cap, egg_collider_spin *s, int32_t *n);
+
 /* ---- force fields (not in the reference, which has no forces as it has no boundary; DESIGN.md section 2.7, "Forces") ----
  * A handle holds an ordered list of at most EGG_MAX_FORCES fields.  The values are accelerations in px/s^2 and do not depend
  * on mass.  In every sub-step of a RELAXED step, for every particle of a type, the force step runs before the pre-solve,
@@ -728,6 +766,11 @@ int egg_group_get_collider_surfaces(const egg_group *g, int32_t cap, egg_collide
  * stored geometry alike at the commit. */
 int egg_group_set_collider_motion(egg_group *g, int32_t n, const egg_collider_motion *m);
 int egg_group_get_collider_motion(const egg_group *g, int32_t cap, egg_collider_motion *m, int32_t *n);
+/* egg_set_collider_spin for every handle of the group alike, with its rules; a refused call changes no handle, and
+ * egg_group_set_colliders resets the spins.  A step is refused while the handles differ; every handle advances its stored
+ * geometry and pivots alike at the commit. */
+int egg_group_set_collider_spin(egg_group *g, int32_t n, const egg_collider_spin *s);
+int egg_group_get_collider_spin(const egg_group *g, int32_t cap, egg_collider_spin *s, int32_t *n);
 int egg_group_get_collider_grips(egg_group *g, int64_t grips[2]);
 /* egg_set_forces for every handle of the group alike, with its rules (relaxed order only; back to exact order only with
  * an empty list); a refused list changes no handle.  Every device accelerates only the particles it owns: the results
