@@ -116,6 +116,12 @@ class EggColliderSpin(C.Structure):  # egg_collider_spin: the pivot and angular 
     _fields_ = [("px", C.c_double), ("py", C.c_double), ("omega", C.c_double)]
 
 
+class EggColliderLoad(C.Structure):  # egg_collider_load: the impulse and torque a collider received in a step (24 bytes)
+    _fields_ = [("jx", C.c_double), ("jy", C.c_double), ("torque", C.c_double)]
+
+
+COLLIDER_LOAD_IMPULSE_SCALE = 1048576.0  # EGG_COLLIDER_LOAD_IMPULSE_SCALE, 2^20
+COLLIDER_LOAD_TORQUE_SCALE = 1024.0      # EGG_COLLIDER_LOAD_TORQUE_SCALE, 2^10
 MAX_COLLIDERS = 64  # EGG_MAX_COLLIDERS
 COLLIDER_HALF_PLANE, COLLIDER_DISC, COLLIDER_CONTAINER, COLLIDER_SEGMENT = 0, 1, 2, 3
 COLLIDER_KINDS = ("half_plane", "disc", "container", "segment")  # by EGG_COLLIDER_* value: the kinds 0 .. 3
@@ -205,6 +211,15 @@ _SIGNATURES = {
     "egg_get_collider_spin": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggColliderSpin), C.POINTER(C.c_int32)]),
     "egg_group_set_collider_spin": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggColliderSpin)]),
     "egg_group_get_collider_spin": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggColliderSpin), C.POINTER(C.c_int32)]),
+    "egg_set_collider_loads": (C.c_int, [C.c_void_p, C.c_int]),
+    "egg_get_collider_loads_enabled": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "egg_get_collider_load_sums": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double),
+                                             C.POINTER(C.c_int32)]),
+    "egg_get_collider_loads": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggColliderLoad), C.POINTER(C.c_int32)]),
+    "egg_group_set_collider_loads": (C.c_int, [C.c_void_p, C.c_int]),
+    "egg_group_get_collider_load_sums": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double),
+                                                   C.POINTER(C.c_int32)]),
+    "egg_group_get_collider_loads": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggColliderLoad), C.POINTER(C.c_int32)]),
     "egg_group_set_collider_surfaces": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggColliderSurface)]),
     "egg_group_get_collider_surfaces": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggColliderSurface), C.POINTER(C.c_int32)]),
     "egg_group_get_collider_grips": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),

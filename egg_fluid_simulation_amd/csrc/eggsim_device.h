@@ -487,6 +487,60 @@ struct EggRelaxedGroupCohColSpinArgs {
     EggRxSpinFields r;
 };
 
+// Collider loads (egg_set_collider_loads, DESIGN.md section 2.7, "Collider loads"): the loads instantiations of the gather
+// kernel (egg_rx_gather*_col_load_kernel) take these besides everything a spin instantiation takes.  One instantiation per
+// (group, cohesion) serves every collider flavour: it is the most general one, and the three words below say which of its
+// rules the flavour it stands in for would have run, so that it computes that flavour's bits (no "+ 0.0" of a motion that
+// flavour never added).  The surface records exist for every collider (defaults when none are set); the motion records
+// are read only while `moving` or `turning`, the spin records only while `turning` or `pivots`.
+#define EGG_RX_LOAD_SCALE_IMPULSE 0x1p20  // = EGG_COLLIDER_LOAD_IMPULSE_SCALE of include/eggsim.h
+#define EGG_RX_LOAD_SCALE_TORQUE 0x1p10   // = EGG_COLLIDER_LOAD_TORQUE_SCALE
+#define EGG_RX_LOAD_LIMIT 0x1p53          // a scaled contribution that reaches it (or is not finite) is dropped whole
+struct EggRxLoadFields {
+    unsigned long long *sums;            // [the collider count][3]: int64 sums of (qx, qy, qz), two's complement; both types add
+    unsigned long long *dropped;         // one word: contributions dropped in this step
+    double eps;                          // a particle with !(inverse mass > eps) contributes nothing (the force step's test)
+    int32_t moving;                      // a collider motion of the handle is not zero: the motion rule runs
+    int32_t turning;                     // a collider spin of the handle is not zero: the spin rule runs for such a collider
+    int32_t pivots;                      // the handle holds spin records: the torque is about them (else about the origin)
+};
+struct EggRelaxedColLoadArgs {
+    EggRelaxedArgs a;
+    EggRxColliderFields d;
+    EggRxSurfaceFields s;
+    EggRxMotionFields m;
+    EggRxSpinFields r;
+    EggRxLoadFields l;
+};
+struct EggRelaxedGroupColLoadArgs {
+    EggRelaxedArgs a;
+    EggRxGroupFields g;
+    EggRxColliderFields d;
+    EggRxSurfaceFields s;
+    EggRxMotionFields m;
+    EggRxSpinFields r;
+    EggRxLoadFields l;
+};
+struct EggRelaxedCohColLoadArgs {
+    EggRelaxedArgs a;
+    EggRxCohesionFields c;
+    EggRxColliderFields d;
+    EggRxSurfaceFields s;
+    EggRxMotionFields m;
+    EggRxSpinFields r;
+    EggRxLoadFields l;
+};
+struct EggRelaxedGroupCohColLoadArgs {
+    EggRelaxedArgs a;
+    EggRxGroupFields g;
+    EggRxCohesionFields c;
+    EggRxColliderFields d;
+    EggRxSurfaceFields s;
+    EggRxMotionFields m;
+    EggRxSpinFields r;
+    EggRxLoadFields l;
+};
+
 // Force fields (egg_set_forces, DESIGN.md section 2.7, "Forces"): the force instantiations of the kernels that begin a
 // sub-step (egg_rx_begin*_frc_kernel, egg_rx_mid*_frc_kernel) take these besides.  The list is the handle's, in a small
 // device buffer written when it is set; a record has the layout of the ABI's egg_force (40 bytes).

@@ -733,6 +733,65 @@ int egg_group_get_collider_spin(const egg_group *g, int32_t cap, egg_collider_sp
     return egg_get_collider_spin(g->h[0], cap, s, n);  // (as stored: every handle holds the same records)
 }
 
+int egg_group_set_collider_loads(egg_group *g, int on) {
+    if (!g) return EGG_ERR_INVALID_ARGUMENT;
+    int was = 0;
+    if (!g->h.empty()) (void)egg_get_collider_loads_enabled(g->h[0], &was);
+    for (size_t k = 0; k < g->h.size(); ++k) {
+        const int rc = egg_set_collider_loads(g->h[k], on);
+        if (rc < 0) {  // (a handle with a step in flight: the others go back)
+            for (size_t j = 0; j < k; ++j) (void)egg_set_collider_loads(g->h[j], was);
+            return gfail(g, rc, "device %d: %s", (int)k, egg_last_error(g->h[k]));
+        }
+    }
+    return EGG_OK;
+}
+
+// the integer sums and the dropped counts added over the handles (two's complement: the sum of the handles' sums is the
+// sum over all their contributions); every handle of a committed step holds the same sub-step
+int egg_group_get_collider_load_sums(egg_group *g, int32_t cap, int64_t *sums, int64_t *dropped, double *sub_delta, int32_t *n) {
+    if (!g || g->h.empty()) return EGG_ERR_INVALID_ARGUMENT;
+    int32_t have = 0;
+    (void)egg_get_collider_load_sums(g->h[0], 0, nullptr, nullptr, nullptr, &have);
+    if (n) *n = have;
+    std::vector<uint64_t> total(3 * (size_t)have, 0);
+    std::vector<int64_t> one(3 * (size_t)have, 0);
+    int64_t lost = 0;
+    double hs = 0.0;
+    for (size_t k = 0; k < g->h.size(); ++k) {
+        int64_t d = 0;
+        double s = 0.0;
+        int32_t m = 0;
+        const int rc = egg_get_collider_load_sums(g->h[k], have, one.data(), &d, &s, &m);
+        if (rc < 0) return gfail(g, rc, "device %d: %s", (int)k, egg_last_error(g->h[k]));
+        for (size_t q = 0; q < 3 * (size_t)std::min(have, m); ++q) total[q] += (uint64_t)one[q];
+        lost += d;
+        if (k == 0) hs = s;
+    }
+    for (size_t q = 0; sums && q < 3 * (size_t)std::min(cap, have); ++q) sums[q] = (int64_t)total[q];
+    if (dropped) *dropped = lost;
+    if (sub_delta) *sub_delta = hs;
+    return EGG_OK;
+}
+
+int egg_group_get_collider_loads(egg_group *g, int32_t cap, egg_collider_load *out, int32_t *n) {
+    if (!g || g->h.empty()) return EGG_ERR_INVALID_ARGUMENT;
+    int32_t have = 0;
+    (void)egg_get_collider_load_sums(g->h[0], 0, nullptr, nullptr, nullptr, &have);
+    std::vector<int64_t> sums(3 * (size_t)have, 0);
+    double hs = 0.0;
+    const int rc = egg_group_get_collider_load_sums(g, have, sums.data(), nullptr, &hs, nullptr);
+    if (rc < 0) return rc;
+    if (n) *n = have;
+    for (int32_t k = 0; out && k < std::min(cap, have); ++k) {  // (converted once, with egg_get_collider_loads' two divisions)
+        const bool any = hs > 0.0;
+        out[k].jx = any ? ((double)sums[(size_t)(3 * k)] / EGG_COLLIDER_LOAD_IMPULSE_SCALE) / hs : 0.0;
+        out[k].jy = any ? ((double)sums[(size_t)(3 * k + 1)] / EGG_COLLIDER_LOAD_IMPULSE_SCALE) / hs : 0.0;
+        out[k].torque = any ? ((double)sums[(size_t)(3 * k + 2)] / EGG_COLLIDER_LOAD_TORQUE_SCALE) / hs : 0.0;
+    }
+    return EGG_OK;
+}
+
 int egg_group_get_collider_grips(egg_group *g, int64_t grips[2]) {
     if (!g) return EGG_ERR_INVALID_ARGUMENT;
     if (!grips) return gfail(g, EGG_ERR_INVALID_ARGUMENT, "egg_group_get_collider_grips: grips is NULL");

@@ -104,6 +104,10 @@ extern "C" __global__ void egg_rx_gather_col_spin_kernel(EggRelaxedColSpinArgs A
 extern "C" __global__ void egg_rx_gather_group_col_spin_kernel(EggRelaxedGroupColSpinArgs A);
 extern "C" __global__ void egg_rx_gather_coh_col_spin_kernel(EggRelaxedCohColSpinArgs A);
 extern "C" __global__ void egg_rx_gather_group_coh_col_spin_kernel(EggRelaxedGroupCohColSpinArgs A);
+extern "C" __global__ void egg_rx_gather_col_load_kernel(EggRelaxedColLoadArgs A);
+extern "C" __global__ void egg_rx_gather_group_col_load_kernel(EggRelaxedGroupColLoadArgs A);
+extern "C" __global__ void egg_rx_gather_coh_col_load_kernel(EggRelaxedCohColLoadArgs A);
+extern "C" __global__ void egg_rx_gather_group_coh_col_load_kernel(EggRelaxedGroupCohColLoadArgs A);
 extern "C" __global__ void egg_rx_begin_frc_kernel(EggRelaxedFrcArgs A);
 extern "C" __global__ void egg_rx_mid_frc_kernel(EggRelaxedFrcArgs A);
 extern "C" __global__ void egg_rx_begin_group_frc_kernel(EggRelaxedGroupFrcArgs A);
@@ -477,6 +481,15 @@ struct egg_handle {
     bool spins_turn = false;
     std::vector<double2> spin_table;
     DevBuf<double2> d_spin_table;
+    // collider loads (egg_set_collider_loads): the switch; the step's sums on the device, 3 words per collider and the
+    // dropped word behind them, shared by both types' streams (cleared by prepare_step before either stream starts, read by
+    // relaxed_commit once both have been waited for); the sums, the dropped count and the sub-step of the last committed
+    // step that had the switch on and a list (zeros after egg_set_colliders)
+    bool opt_loads = false;
+    DevBuf<unsigned long long> d_loads;
+    std::vector<int64_t> load_sums;
+    int64_t load_dropped = 0;
+    double load_sub_delta = 0.0;
     // force fields (egg_set_forces; relaxed order only): the list as egg_get_forces returns it and its copy on the device
     // (written when the list is set, never per step)
     std::vector<egg_force> forces;
@@ -662,6 +675,7 @@ struct RelaxedLayout {
     bool walls = false;      // (set by prepare_type: the handle's list holds a wall; implies surfaces)
     bool motion = false;     // (set by prepare_type: a collider motion of the handle is not zero; implies surfaces; no word of its own)
     bool spin = false;       // (set by prepare_type: a collider spin of the handle is not zero; implies surfaces; no word of its own)
+    bool loads = false;      // (set by prepare_type: collider loads are on and the list is not empty; no word here: the sums have a buffer of their own)
     bool coupling = false;   // (set by prepare_type: the step runs coupling passes -- no halo, factor > 0, both types populated)
     bool coupled_word = false;  // (set by prepare_type: coupling, and the type is white: it holds the counter word)
     bool adhesion = false;      // (set by prepare_type: coupling, and the handle's adhesion reach exceeds the coupling factor)
@@ -692,6 +706,8 @@ struct RelaxedStep {  // one type of one handle in a relaxed step
     EggRxSurfaceFields srf{};   // collider surfaces (L.surfaces): the handle's records, the sub-step, the grip counter
     EggRxMotionFields mov{};    // collider motion (L.motion or L.spin): the handle's records; launch_pass sets the pass's time
     EggRxSpinFields spn{};      // collider spin (L.spin): the handle's records and table; launch_pass sets the pass's row
+    EggRxLoadFields lod{};      // collider loads (L.loads): the handle's sums, which rules the list's flavour runs
+    EggRxSurfaceFields lsrf{};  // ... and the surface fields the loads kernels read: srf, or the default records without a counter
     EggRxForceFields frc{};     // force fields (L.forces): the handle's list, the type's bit
     EggRxViscFields visc{};     // viscosity (L.V): the type's coefficient, the pair counter
     double couple_cell = 0, couple_c = 0;  // coupling (L.coupling): the shared cell size H, the compliance of the strength

@@ -1052,6 +1052,9 @@ int egg_set_colliders(egg_handle *h, int32_t n, const egg_collider *c) {
     h->motions_move = false;
     h->spins.clear();  // (and every spin)
     h->spins_turn = false;
+    h->load_sums.assign(3 * h->colliders.size(), 0);  // (the loads belonged to the old list; the switch stays)
+    h->load_dropped = 0;
+    h->load_sub_delta = 0.0;
     return EGG_OK;
 }
 
@@ -1215,6 +1218,50 @@ int egg_get_collider_spin(const egg_handle *h, int32_t cap, egg_collider_spin *s
     if (n) *n = have;
     for (int32_t k = 0; sp && k < std::min(cap, have); ++k)
         sp[k] = h->spins.empty() ? egg_collider_spin{0.0, 0.0, 0.0} : h->spins[(size_t)k];
+    return EGG_OK;
+}
+
+// Collider loads ("Collider loads"): the switch only observes, so it is accepted in either order and
+// with an empty list; the stored loads start again at zero.
+int egg_set_collider_loads(egg_handle *h, int on) {
+    if (!h) return EGG_ERR_INVALID_ARGUMENT;
+    REJECT_IN_FLIGHT(h, "egg_set_collider_loads");
+    static_assert(EGG_COLLIDER_LOAD_IMPULSE_SCALE == EGG_RX_LOAD_SCALE_IMPULSE && EGG_COLLIDER_LOAD_TORQUE_SCALE == EGG_RX_LOAD_SCALE_TORQUE,
+                  "the kernel's load scales are the ABI's");
+    h->opt_loads = on != 0;
+    h->load_sums.assign(3 * h->colliders.size(), 0);
+    h->load_dropped = 0;
+    h->load_sub_delta = 0.0;
+    return EGG_OK;
+}
+
+int egg_get_collider_loads_enabled(const egg_handle *h, int *on) {
+    if (!h || !on) return EGG_ERR_INVALID_ARGUMENT;
+    *on = h->opt_loads ? 1 : 0;
+    return EGG_OK;
+}
+
+int egg_get_collider_load_sums(egg_handle *h, int32_t cap, int64_t *sums, int64_t *dropped, double *sub_delta, int32_t *n) {
+    if (!h) return EGG_ERR_INVALID_ARGUMENT;
+    const int32_t have = (int32_t)h->colliders.size();
+    if (n) *n = have;
+    for (int32_t k = 0; sums && k < 3 * std::min(cap, have); ++k) sums[k] = (size_t)k < h->load_sums.size() ? h->load_sums[(size_t)k] : 0;
+    if (dropped) *dropped = h->load_dropped;
+    if (sub_delta) *sub_delta = h->load_sub_delta;
+    return EGG_OK;
+}
+
+int egg_get_collider_loads(egg_handle *h, int32_t cap, egg_collider_load *out, int32_t *n) {
+    if (!h) return EGG_ERR_INVALID_ARGUMENT;
+    const int32_t have = (int32_t)h->colliders.size();
+    if (n) *n = have;
+    const double hs = h->load_sub_delta;
+    for (int32_t k = 0; out && k < std::min(cap, have); ++k) {
+        const bool any = hs > 0.0 && (size_t)(3 * k + 2) < h->load_sums.size();
+        out[k].jx = any ? ((double)h->load_sums[(size_t)(3 * k)] / EGG_COLLIDER_LOAD_IMPULSE_SCALE) / hs : 0.0;
+        out[k].jy = any ? ((double)h->load_sums[(size_t)(3 * k + 1)] / EGG_COLLIDER_LOAD_IMPULSE_SCALE) / hs : 0.0;
+        out[k].torque = any ? ((double)h->load_sums[(size_t)(3 * k + 2)] / EGG_COLLIDER_LOAD_TORQUE_SCALE) / hs : 0.0;
+    }
     return EGG_OK;
 }
 

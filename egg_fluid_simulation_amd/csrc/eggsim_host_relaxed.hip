@@ -32,6 +32,12 @@
 // the table of sines and cosines prepare_step has computed with libm and copied to the device -- no launch of its own;
 // relaxed_commit advances the stored list and the stored pivots from the last row.  With every spin zero a step launches
 // what it launched, with the same arguments.
+// With collider loads on (egg_set_collider_loads, RelaxedLayout::loads) launch_pass picks the loads instantiation of the
+// gather in place of whichever collider flavour the list would launch, and RelaxedStep::lod tells it which of that
+// flavour's rules to run.  The sums live in a buffer of the handle that both types' streams add into: prepare_step clears
+// it before either stream has work, relaxed_commit reads it once every path has waited for both, and nothing else touches
+// it, so a failed step leaves the values of the step before.  With loads off a step launches what it launched, with the
+// same arguments.
 // With force fields (egg_set_forces, RelaxedLayout::forces) launch_substep picks the force instantiation of the begin / mid
 // kernel and RelaxedStep::frc carries the handle's list; with an empty list a step launches what it always launched.
 // With viscosity (egg_set_viscosity, RelaxedLayout::V) every sub-step of a type whose coefficient is not zero ends with
@@ -203,6 +209,25 @@ int prepare_step(egg_handle *h, double delta, int S, RelaxedStep st[2]) {
         HIP_TRY(h, h->d_spin_table.reserve(h->spin_table.size(), false, nullptr));
         HIP_TRY(h, hipMemcpy(h->d_spin_table.p, h->spin_table.data(), h->spin_table.size() * sizeof(double2), hipMemcpyHostToDevice));
     }
+    if (h->opt_loads && !h->colliders.empty()) {
+        // the step's sums start at zero, before either type's stream has work (no step is running); the loads kernels read a
+        // surface record per collider and, for the pivots, the spin records: whichever the handle's flavour has not put on
+        // the device yet goes there now
+        const size_t n = h->colliders.size();
+        HIP_TRY(h, hipSetDevice(h->device));
+        HIP_TRY(h, h->d_loads.reserve(3 * (size_t)EGG_MAX_COLLIDERS + 1, false, nullptr));
+        const std::vector<unsigned long long> none(3 * n + 1, 0ull);
+        HIP_TRY(h, hipMemcpy(h->d_loads.p, none.data(), none.size() * 8, hipMemcpyHostToDevice));
+        if (!(h->surfaces_grip || h->colliders_wall || h->motions_move || h->spins_turn)) {
+            const std::vector<egg_collider_surface> zeros(n, egg_collider_surface{0.0, 0.0, 0.0});
+            HIP_TRY(h, h->d_surfaces.reserve(EGG_MAX_COLLIDERS, false, nullptr));
+            HIP_TRY(h, hipMemcpy(h->d_surfaces.p, zeros.data(), n * sizeof(egg_collider_surface), hipMemcpyHostToDevice));
+        }
+        if (!h->spins.empty() && !h->spins_turn) {
+            HIP_TRY(h, h->d_spins.reserve(EGG_MAX_COLLIDERS, false, nullptr));
+            HIP_TRY(h, hipMemcpy(h->d_spins.p, h->spins.data(), n * sizeof(egg_collider_spin), hipMemcpyHostToDevice));
+        }
+    }
     return EGG_OK;
 }
 
@@ -223,6 +248,7 @@ int prepare_type(RelaxedStep &st, int C, size_t ghosts, const RelaxedLayout &L, 
     st.L.motion = st.L.colliders && h->motions_move;
     st.L.spin = st.L.colliders && h->spins_turn;
     st.L.surfaces = st.L.colliders && (h->surfaces_grip || st.L.walls || st.L.motion || st.L.spin);
+    st.L.loads = st.L.colliders && h->opt_loads;
     st.L.forces = !h->forces.empty();
     st.L.V = h->viscosity[st.w] > 0.0 ? L.P / (size_t)C : 0;
     st.L.coupling = !L.halo && h->coupling_factor > 0.0 && h->sys[0].n > 0 && h->sys[1].n > 0;
@@ -265,6 +291,22 @@ int prepare_type(RelaxedStep &st, int C, size_t ghosts, const RelaxedLayout &L, 
     if (st.L.spin) {
         st.spn.list = h->d_spins.p;
         st.spn.hcs = h->d_spin_table.p + (L.P / (size_t)C) * h->colliders.size();  // (the row behind the sub-steps')
+    }
+    st.lod = EggRxLoadFields{};
+    st.lsrf = st.srf;
+    if (st.L.loads) {
+        st.lod.sums = h->d_loads.p;
+        st.lod.dropped = h->d_loads.p + 3 * h->colliders.size();
+        st.lod.eps = h->sys[0].cfg.eps;
+        st.lod.moving = st.L.motion ? 1 : 0;
+        st.lod.turning = st.L.spin ? 1 : 0;
+        st.lod.pivots = h->spins.empty() ? 0 : 1;
+        if (!st.L.surfaces) {  // the default records prepare_step has written; no friction, so no grip is ever counted
+            st.lsrf.list = h->d_surfaces.p;
+            st.lsrf.sub_delta = st.env.sub_delta;
+            st.lsrf.grips = nullptr;
+        }
+        if (st.lod.pivots && !st.L.spin) st.spn.list = h->d_spins.p;
     }
     st.frc = EggRxForceFields{};
     if (st.L.forces) {
@@ -387,7 +429,10 @@ int launch_pass(RelaxedStep &st, int p) {
         if (st.L.cohesion) {
             const EggRelaxedGroupCohArgs k{a.a, a.g, st.coh};
             hipLaunchKernelGGL(egg_rx_rank_group_coh_kernel, grid, block, 0, s.stream, k);
-            if (st.L.spin)
+            if (st.L.loads)
+                hipLaunchKernelGGL(egg_rx_gather_group_coh_col_load_kernel, grid, block, 0, s.stream,
+                                   EggRelaxedGroupCohColLoadArgs{a.a, a.g, st.coh, st.col, st.lsrf, st.mov, st.spn, st.lod});
+            else if (st.L.spin)
                 hipLaunchKernelGGL(egg_rx_gather_group_coh_col_spin_kernel, grid, block, 0, s.stream,
                                    EggRelaxedGroupCohColSpinArgs{a.a, a.g, st.coh, st.col, st.srf, st.mov, st.spn});
             else if (st.L.motion)
@@ -405,7 +450,10 @@ int launch_pass(RelaxedStep &st, int p) {
                 hipLaunchKernelGGL(egg_rx_gather_group_coh_kernel, grid, block, 0, s.stream, k);
         } else {
             hipLaunchKernelGGL(egg_rx_rank_group_kernel, grid, block, 0, s.stream, a);
-            if (st.L.spin)
+            if (st.L.loads)
+                hipLaunchKernelGGL(egg_rx_gather_group_col_load_kernel, grid, block, 0, s.stream,
+                                   EggRelaxedGroupColLoadArgs{a.a, a.g, st.col, st.lsrf, st.mov, st.spn, st.lod});
+            else if (st.L.spin)
                 hipLaunchKernelGGL(egg_rx_gather_group_col_spin_kernel, grid, block, 0, s.stream,
                                    EggRelaxedGroupColSpinArgs{a.a, a.g, st.col, st.srf, st.mov, st.spn});
             else if (st.L.motion)
@@ -427,7 +475,10 @@ int launch_pass(RelaxedStep &st, int p) {
         if (st.L.cohesion) {
             const EggRelaxedCohArgs k{a.a, st.coh};
             hipLaunchKernelGGL(egg_rx_rank_coh_kernel, grid, block, 0, s.stream, k);
-            if (st.L.spin)
+            if (st.L.loads)
+                hipLaunchKernelGGL(egg_rx_gather_coh_col_load_kernel, grid, block, 0, s.stream,
+                                   EggRelaxedCohColLoadArgs{a.a, st.coh, st.col, st.lsrf, st.mov, st.spn, st.lod});
+            else if (st.L.spin)
                 hipLaunchKernelGGL(egg_rx_gather_coh_col_spin_kernel, grid, block, 0, s.stream,
                                    EggRelaxedCohColSpinArgs{a.a, st.coh, st.col, st.srf, st.mov, st.spn});
             else if (st.L.motion)
@@ -445,7 +496,10 @@ int launch_pass(RelaxedStep &st, int p) {
                 hipLaunchKernelGGL(egg_rx_gather_coh_kernel, grid, block, 0, s.stream, k);
         } else {
             hipLaunchKernelGGL(egg_rx_rank_kernel, grid, block, 0, s.stream, a.a);
-            if (st.L.spin)
+            if (st.L.loads)
+                hipLaunchKernelGGL(egg_rx_gather_col_load_kernel, grid, block, 0, s.stream,
+                                   EggRelaxedColLoadArgs{a.a, st.col, st.lsrf, st.mov, st.spn, st.lod});
+            else if (st.L.spin)
                 hipLaunchKernelGGL(egg_rx_gather_col_spin_kernel, grid, block, 0, s.stream,
                                    EggRelaxedColSpinArgs{a.a, st.col, st.srf, st.mov, st.spn});
             else if (st.L.motion)
@@ -777,6 +831,23 @@ static void advance_colliders(egg_handle *h, double t, int S) {
     if (e != hipSuccess) (void)fail(h, EGG_ERR_DEVICE, "relaxed order: the moved colliders did not reach the device: %s", hipGetErrorString(e));
 }
 
+// Collider loads at the commit: the step's sums, which both types' streams have added into, become the handle's.  No step
+// is running: every path waits for its streams before it commits, so one blocking copy sees every addition.
+static void take_loads(egg_handle *h, double sub_delta) {
+    const size_t n = h->colliders.size();
+    std::vector<unsigned long long> words(3 * n + 1, 0ull);
+    hipError_t e = hipSetDevice(h->device);
+    if (e == hipSuccess) e = hipMemcpy(words.data(), h->d_loads.p, words.size() * 8, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) {
+        (void)fail(h, EGG_ERR_DEVICE, "relaxed order: the collider loads did not reach the host: %s", hipGetErrorString(e));
+        return;
+    }
+    h->load_sums.resize(3 * n);
+    for (size_t k = 0; k < 3 * n; ++k) h->load_sums[k] = (int64_t)words[k];
+    h->load_dropped = (int64_t)words[3 * n];
+    h->load_sub_delta = sub_delta;
+}
+
 // the commit of a relaxed step whose end kernels have run: flip cur, statistics from the status words read back
 void relaxed_commit(egg_handle *h, const RelaxedStep st[2], int S, int C, double ms) {
     for (int w = 0; w < 2; ++w) {
@@ -806,6 +877,7 @@ void relaxed_commit(egg_handle *h, const RelaxedStep st[2], int S, int C, double
         s.aabb_valid = s.aabb_on_device = s.disp_valid = false;
         s.out_copied = false;
     }
+    if (h->opt_loads && !h->colliders.empty()) take_loads(h, st[0].env.sub_delta);
     if ((h->motions_move || h->spins_turn) && !h->colliders.empty()) advance_colliders(h, (double)S * st[0].env.sub_delta, S);
     h->stats.last_step_kernel_ms = ms;
     if (h->opt_timing) {

@@ -142,6 +142,15 @@ int relaxed_group_step(egg_handle *const *hs, int nh, double delta, int S, int C
             return EGG_ERR_INVALID_ARGUMENT;
         }
     }
+    for (int k = 1; k < nh; ++k) {  // (with loads on the pivots count although nothing turns: the torque is about them)
+        const std::vector<egg_collider_spin> &a = hs[0]->spins, &b = hs[k]->spins;
+        const bool same_pivots = !hs[0]->opt_loads || hs[0]->spins_turn ||
+                                 (a.size() == b.size() && (a.empty() || memcmp(a.data(), b.data(), a.size() * sizeof(egg_collider_spin)) == 0));
+        if (hs[0]->opt_loads != hs[k]->opt_loads || !same_pivots) {
+            *error = "relaxed order: the handles of the group differ in their collider loads (egg_group_set_collider_loads sets all)";
+            return EGG_ERR_INVALID_ARGUMENT;
+        }
+    }
     for (int k = 1; k < nh; ++k) {
         const std::vector<egg_force> &a = hs[0]->forces, &b = hs[k]->forces;
         if (a.size() != b.size() || (!a.empty() && memcmp(a.data(), b.data(), a.size() * sizeof(egg_force)) != 0)) {

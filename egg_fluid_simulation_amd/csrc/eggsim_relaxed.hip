@@ -184,6 +184,43 @@ __device__ __forceinline__ double2 rx_carried(const EggRxSpinFields *Sp, const E
     return make_double2(Px + (hcs.x * ux - hcs.y * uy), Py + (hcs.y * ux + hcs.x * uy));
 }
 
+// Collider loads ("Collider loads"): what collider c has just done to the wave's particles, added to
+// its three sums.  Every lane of the wave calls it (the loads instantiation runs the colliders where the wave is converged);
+// `counts` is this lane's: a particle of this device that the collider has moved and whose inverse mass exceeds eps.  (bx, by)
+// is the position that entered the collider's rule, `at` the one that left it, im the inverse mass, (Px, Py) the pivot.  A wave in
+// which nothing counts returns at once; any other reduces the three integers across its lanes (integer addition: no order)
+// and lane 0 adds them with one atomic each.
+__device__ __forceinline__ void rx_tally(const EggRxLoadFields &Ld, int c, bool counts, double im, double bx, double by,
+                                         const double2 &at, double Px, double Py) {
+    if (__ballot(counts) == 0ull) return;
+    const double m = 1.0 / im;
+    const double ux = m * (bx - at.x);
+    const double uy = m * (by - at.y);
+    const double uz = (at.x - Px) * uy - (at.y - Py) * ux;
+    const double fx = ux * EGG_RX_LOAD_SCALE_IMPULSE, fy = uy * EGG_RX_LOAD_SCALE_IMPULSE, fz = uz * EGG_RX_LOAD_SCALE_TORQUE;
+    // (every comparison is false for a NaN: such a contribution is dropped)
+    const bool ok = counts && fabs(fx) < EGG_RX_LOAD_LIMIT && fabs(fy) < EGG_RX_LOAD_LIMIT && fabs(fz) < EGG_RX_LOAD_LIMIT;
+    long long qx = llrint(ok ? fx : 0.0), qy = llrint(ok ? fy : 0.0), qz = llrint(ok ? fz : 0.0);
+    const bool some = __ballot(ok) != 0ull;
+    const int dropped = __popcll(__ballot(counts && !ok));
+    if (some) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            qx += __shfl_xor(qx, d, 64);
+            qy += __shfl_xor(qy, d, 64);
+            qz += __shfl_xor(qz, d, 64);
+        }
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (some) {
+            atomicAdd(&Ld.sums[3 * c + 0], (unsigned long long)qx);
+            atomicAdd(&Ld.sums[3 * c + 1], (unsigned long long)qy);
+            atomicAdd(&Ld.sums[3 * c + 2], (unsigned long long)qz);
+        }
+        if (dropped) atomicAdd(Ld.dropped, (unsigned long long)dropped);
+    }
+}
+
 // Step 5b of the relaxed pass: the colliders of the list whose mask covers the type, in list order, each on the result
 // of the one before it.  i: the particle's key (picks the way out of a disc's centre); r: its radius.  Every lane of a
 // wave reads the same record and takes the same branch on its kind.  Every comparison is false for a NaN: such a
@@ -206,24 +243,44 @@ __device__ __forceinline__ double2 rx_carried(const EggRxSpinFields *Sp, const E
 // own omega != 0, alike in every lane: such a collider takes the spin rule, whose primed parameters also go back to
 // scalar registers; any other takes the motion rule as it stands.  Only the carried start of a turning wall and the
 // surface's velocity at the contact point are per lane.
-template <bool S, bool W, bool P>
+// L (with P only; Ld): the loads instantiation (egg_set_collider_loads; DESIGN.md section 2.7, "Collider loads"), which
+// stands in for every flavour: whether the motion rule runs and whether a collider may turn are then words of Ld, alike in
+// every lane, so that it evaluates the expressions of the flavour the handle would launch without loads.  Every lane of the
+// wave is in here (one without a particle holds a NaN position, which no collider moves); `free` is the lane's: it holds a
+// particle whose inverse mass im exceeds eps.  After each collider's rule, grip included, rx_tally adds what it did.
+template <bool S, bool W, bool P, bool L = false>
 __device__ __forceinline__ int rx_collide(const EggRxColliderFields &Co, const EggRxSurfaceFields &Su, const EggRxMotionFields *Mo,
-                                          const EggRxSpinFields *Sp, int i, double r, double2 pv, double2 &out, int &grips) {
-    const bool M = W && Mo != nullptr;
+                                          const EggRxSpinFields *Sp, int i, double r, double2 pv, double2 &out, int &grips,
+                                          const EggRxLoadFields *Ld = nullptr, bool free = false, double im = 0.0) {
+    const bool M = W && (L ? Ld->moving != 0 || Ld->turning != 0 : Mo != nullptr);
     static_assert(W || !P, "the spin instantiations are wall instantiations");
+    static_assert(P || !L, "the loads instantiations are spin instantiations");
     int hits = 0;
     for (int c = 0; c < Co.count; ++c) {
         EggCollider col = Co.list[c];
         if (!(col.type_mask & Co.type_bit)) continue;
         EggSurface sf{};
         if (S) sf = Su.list[c];
+        const int before = hits;                // (L: the hits in front of this collider)
+        double LPx = 0.0, LPy = 0.0;            // (L: the pivot the torque is about)
+        if (L && Ld->pivots) {                  // the spin record's pivot riding on the motion, as step 5b computes it
+            const EggSpin sp = Sp->list[c];
+            double ox = 0.0, oy = 0.0;
+            if (M) {
+                const EggMotion mo = Mo->list[c];
+                ox = Mo->t * mo.vx;
+                oy = Mo->t * mo.vy;
+            }
+            LPx = rx_uniform(sp.px + ox);
+            LPy = rx_uniform(sp.py + oy);
+        }
         bool turns = false;  // (P: this collider's omega is not zero; alike in every lane)
         double omega = 0.0, Px = 0.0, Py = 0.0;  // (P, read when it turns: the spin, the pivot at the sub-step's end)
         double hvx = 0.0, hvy = 0.0;  // (M: how far the collider carries the sub-step's start along, what a moving wall sweeps from)
         if (M) {  // the geometry at the end of the pass's sub-step, once per collider; step 5c adds the motion to the surface's velocity
             const EggMotion mo = Mo->list[c];
             const double ox = Mo->t * mo.vx, oy = Mo->t * mo.vy;
-            if (P) {
+            if (P && (!L || Ld->turning)) {
                 const EggSpin sp = Sp->list[c];
                 turns = ((unsigned long long)__double_as_longlong(sp.omega) << 1) != 0ull;  // (omega != 0, on the scalar unit)
                 if (turns) {  // about the pivot, which rides on the motion; (c, s) of the sub-step's end from the host's table
@@ -279,6 +336,7 @@ __device__ __forceinline__ int rx_collide(const EggRxColliderFields &Co, const E
                 ++hits;
                 if (S) grips += rx_grip(P && turns ? rx_turning(sf, omega, Px, Py, out) : sf, Su.sub_delta, pv, col.p[0], col.p[1], -s, out);
             }
+            if (L) rx_tally(*Ld, c, free && hits != before, im, x, y, out, LPx, LPy);
             continue;
         }
         double cx = col.p[0], cy = col.p[1], R = col.p[2];
@@ -344,6 +402,7 @@ __device__ __forceinline__ int rx_collide(const EggRxColliderFields &Co, const E
                 if (S) grips += rx_grip(P && turns ? rx_turning(sf, omega, Px, Py, out) : sf, Su.sub_delta, pv, ux, uy, pen, out);
             }
         }
+        if (L) rx_tally(*Ld, c, free && hits != before, im, x, y, out, LPx, LPy);
     }
     return hits;
 }
@@ -537,12 +596,22 @@ __device__ __forceinline__ void rx_rank(const EggRelaxedArgs &A, const EggRxGrou
 // collider's surface acts right after its projection (step 5c); prev[me] is read once, for that.  W (with S only): the
 // list may hold walls, which sweep from the same prev[me].  Mo (with W only): not null in the motion instantiations, whose
 // colliders move (rx_collide).  Sp (with Mo only): not null in the spin instantiations, whose colliders turn besides.
+// Ld (with Sp only; L below): not null in the loads instantiations (egg_rx_gather*_col_load_kernel), which also sum what
+// every collider does to the particles.  The switch is the pointer, as Mo's is: after inlining L is a constant.  The sums
+// are reduced across the wave, so there the colliders run behind the branch on the slot, where the wave is converged: a lane
+// without a local particle brings a NaN position, which no collider moves, and writes nothing.
 template <bool G, bool K, bool D, bool S, bool W>
 __device__ __forceinline__ void rx_gather(EggRelaxedArgs A, const EggRxGroupFields &X, const EggRxCohesionFields &Ch,
                                           const EggRxColliderFields &Co, const EggRxSurfaceFields &Su,
-                                          const EggRxMotionFields *Mo = nullptr, const EggRxSpinFields *Sp = nullptr) {
+                                          const EggRxMotionFields *Mo = nullptr, const EggRxSpinFields *Sp = nullptr,
+                                          const EggRxLoadFields *Ld = nullptr) {
     static_assert(D || !S, "surfaces belong to colliders");
     static_assert(S || !W, "the wall instantiations are surface instantiations");
+    const bool L = W && Ld != nullptr;
+    bool have = false;     // (L only: the slot holds a local particle; li, lme, lwr, lout are its key, index, (w, r) and position)
+    int li = 0, lme = 0;
+    double2 lwr = make_double2(0.0, 0.0);
+    double2 lout = make_double2(__longlong_as_double(0x7ff8000000000000ll), __longlong_as_double(0x7ff8000000000000ll));
     const int t = (int)(blockIdx.x * 256 + threadIdx.x);
     int pairs = 0;
     int cohered = 0;  // (K only)
@@ -630,16 +699,30 @@ __device__ __forceinline__ void rx_gather(EggRelaxedArgs A, const EggRxGroupFiel
             out.x = p.x + (sx * A.omega) / (double)n_fired;
             out.y = p.y + (sy * A.omega) / (double)n_fired;
         }
-        if (D) {
+        if (D && !L) {
             const double2 pv = S ? A.prev[me] : make_double2(0.0, 0.0);
             hits = W && Sp != nullptr ? rx_collide<S, W, W>(Co, Su, Mo, Sp, i, wr.y, pv, out, grips)
                                       : rx_collide<S, W, false>(Co, Su, Mo, Sp, i, wr.y, pv, out, grips);
         }
-        A.pos_next[me] = out;
+        if (L) {
+            have = true;
+            li = i;
+            lme = me;
+            lwr = wr;
+            lout = out;
+        } else {
+            A.pos_next[me] = out;
+        }
         if (G) {
             local = true;
             gout = out;
         }
+    }
+    if (L) {  // every lane of the wave: the colliders and their loads
+        const double2 pv = have ? A.prev[lme] : lout;
+        hits = rx_collide<S, W, W, W>(Co, Su, Mo, Sp, li, lwr.y, pv, lout, grips, Ld, have && lwr.x > Ld->eps, lwr.x);
+        if (have) A.pos_next[lme] = lout;
+        if (G) gout = lout;
     }
     // pairs counted (each once: by its smaller key, on the device that holds it), one atomic per wave
 #pragma unroll
@@ -705,6 +788,12 @@ extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_col_spin_kernel(
 extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_col_spin_kernel(EggRelaxedGroupColSpinArgs A) { rx_gather<true, false, true, true, true>(A.a, A.g, EggRxCohesionFields{}, A.d, A.s, &A.m, &A.r); }
 extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_coh_col_spin_kernel(EggRelaxedCohColSpinArgs A) { rx_gather<false, true, true, true, true>(A.a, EggRxGroupFields{}, A.c, A.d, A.s, &A.m, &A.r); }
 extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_coh_col_spin_kernel(EggRelaxedGroupCohColSpinArgs A) { rx_gather<true, true, true, true, true>(A.a, A.g, A.c, A.d, A.s, &A.m, &A.r); }
+
+// the loads instantiations (egg_set_collider_loads on): one per (group, cohesion), standing in for every collider flavour
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_col_load_kernel(EggRelaxedColLoadArgs A) { rx_gather<false, false, true, true, true>(A.a, EggRxGroupFields{}, EggRxCohesionFields{}, A.d, A.s, &A.m, &A.r, &A.l); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_col_load_kernel(EggRelaxedGroupColLoadArgs A) { rx_gather<true, false, true, true, true>(A.a, A.g, EggRxCohesionFields{}, A.d, A.s, &A.m, &A.r, &A.l); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_coh_col_load_kernel(EggRelaxedCohColLoadArgs A) { rx_gather<false, true, true, true, true>(A.a, EggRxGroupFields{}, A.c, A.d, A.s, &A.m, &A.r, &A.l); }
+extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_coh_col_load_kernel(EggRelaxedGroupCohColLoadArgs A) { rx_gather<true, true, true, true, true>(A.a, A.g, A.c, A.d, A.s, &A.m, &A.r, &A.l); }
 
 // ---- viscosity ----
 

@@ -100,6 +100,11 @@ typedef struct { double px, py, omega; } egg_collider_spin;
 int egg_set_collider_spin(egg_handle *h, int32_t n, const egg_collider_spin *s);
 int egg_get_collider_spin(const egg_handle *h, int32_t cap, egg_collider_spin *s, int32_t *n);
 int egg_get_collider_grips(egg_handle *h, int64_t grips[2]);
+typedef struct { double jx, jy, torque; } egg_collider_load;
+int egg_set_collider_loads(egg_handle *h, int on);
+int egg_get_collider_loads_enabled(const egg_handle *h, int *on);
+int egg_get_collider_load_sums(egg_handle *h, int32_t cap, int64_t *sums, int64_t *dropped, double *sub_delta, int32_t *n);
+int egg_get_collider_loads(egg_handle *h, int32_t cap, egg_collider_load *out, int32_t *n);
 typedef struct egg_group egg_group;
 int egg_group_set_solver_order(egg_group *g, int32_t order, double relaxation);
 int egg_group_set_cohesion(egg_group *g, int32_t mode);
@@ -577,6 +582,42 @@ function SimulationHandler:get_collider_spin()
     local out = {}
     for k = 0, n[0] - 1 do out[k + 1] = { arr[k].px, arr[k].py, arr[k].omega } end
     return out
+end
+
+-- Not in the reference: collider loads (egg_set_collider_loads in include/eggsim.h; DESIGN.md section 2.7,
+-- "Collider loads").
+
+--- switch collider loads on or off (off by default): while on, a relaxed step with a non-empty list records per collider the
+--- impulse and the torque about its pivot that it received from the particles it moved.  It only observes.
+function SimulationHandler:set_collider_loads(on)
+    self:_check(lib.egg_set_collider_loads(self._h, on and 1 or 0))
+end
+
+function SimulationHandler:get_collider_loads_enabled()
+    local on = ffi.new("int[1]")
+    if self:_check(lib.egg_get_collider_loads_enabled(self._h, on)) ~= 0 then return false end
+    return on[0] ~= 0
+end
+
+--- one `{ jx, jy, torque }` per collider: the impulse in mass px/s and the angular impulse about the collider's pivot in
+--- mass px^2/s it received over the last committed step that recorded loads; the mean force is j / delta
+function SimulationHandler:collider_loads()
+    local arr, n = ffi.new("egg_collider_load[?]", _max_colliders), ffi.new("int32_t[1]")
+    if self:_check(lib.egg_get_collider_loads(self._h, _max_colliders, arr, n)) ~= 0 then return {} end
+    local out = {}
+    for k = 0, n[0] - 1 do out[k + 1] = { arr[k].jx, arr[k].jy, arr[k].torque } end
+    return out
+end
+
+--- the raw sums: `{ { sx, sy, sz }, ... }` as int64 cdata (impulse scaled by 2^20, torque by 2^10), the dropped count and
+--- the sub-step h of the step that produced them
+function SimulationHandler:collider_load_sums()
+    local arr, n = ffi.new("int64_t[?]", 3 * _max_colliders), ffi.new("int32_t[1]")
+    local dropped, h = ffi.new("int64_t[1]"), ffi.new("double[1]")
+    if self:_check(lib.egg_get_collider_load_sums(self._h, _max_colliders, arr, dropped, h, n)) ~= 0 then return {}, 0, 0 end
+    local out = {}
+    for k = 0, n[0] - 1 do out[k + 1] = { arr[3 * k], arr[3 * k + 1], arr[3 * k + 2] } end
+    return out, dropped[0], h[0]
 end
 
 -- Not in the reference, which has no forces as it has no boundary: force fields of the relaxed step (egg_set_forces in

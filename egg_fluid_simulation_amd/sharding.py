@@ -651,6 +651,33 @@ class ShardedSimulationHandler(_HandlerSurface):
     def get_collider_spin(self):
         return self.local.get_collider_spin()
 
+    def set_collider_loads(self, on):
+        """SimulationHandler.set_collider_loads on every rank alike (the same call on every rank).  Nothing new travels:
+        every rank projects only the particles it owns, so only they contribute to its sums."""
+        self.local.set_collider_loads(on)
+
+    def get_collider_loads_enabled(self):
+        return self.local.get_collider_loads_enabled()
+
+    def collider_load_sums(self):
+        """SimulationHandler.collider_load_sums with the int64 sums and the dropped count added over the ranks (a collective:
+        every rank calls it).  Integer addition has no order, so the result equals one handle's bit for bit."""
+        sums, dropped, h = self.local.collider_load_sums()
+        flat = [v for t in sums for v in t] + [dropped]
+        tot = self.torch.tensor(flat, dtype=self.torch.int64, device=self.device)
+        self.dist.all_reduce(tot, op=self.dist.ReduceOp.SUM)
+        flat = [int(v) for v in tot.tolist()]
+        return [tuple(flat[3 * k:3 * k + 3]) for k in range(len(sums))], flat[-1], h
+
+    def collider_loads(self):
+        """SimulationHandler.collider_loads over all ranks (a collective): the summed integers, converted here with the
+        library's two divisions"""
+        sums, _dropped, h = self.collider_load_sums()
+        if not h > 0.0:
+            return [(0.0, 0.0, 0.0)] * len(sums)
+        si, st = _ffi.COLLIDER_LOAD_IMPULSE_SCALE, _ffi.COLLIDER_LOAD_TORQUE_SCALE
+        return [((float(sx) / si) / h, (float(sy) / si) / h, (float(sz) / st) / h) for sx, sy, sz in sums]
+
     def set_forces(self, forces):
         """SimulationHandler.set_forces on every rank alike (the same call on every rank; relaxed order only).  Nothing
         new travels: every rank accelerates the particles it owns."""

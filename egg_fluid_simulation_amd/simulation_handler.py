@@ -290,6 +290,36 @@ class _HandlerSurface:
         self._check(self._c("get_collider_spin")(_ffi.MAX_COLLIDERS, arr, C.byref(n)))
         return [(sp.px, sp.py, sp.omega) for sp in arr[:n.value]]
 
+    # ------------------------------------------------ collider loads (egg_set_collider_loads)
+    def set_collider_loads(self, on):
+        """Switch collider loads on or off ("Collider loads"; off by default).  While on, a relaxed
+        step with a non-empty list records per collider the impulse and the torque about its pivot that it received from
+        the particles it moved.  It only observes: positions and counters are those of the step with loads off.  Accepted
+        in either solver order and with an empty list; the stored loads start again at zero."""
+        self._check(self._c("set_collider_loads")(1 if on else 0))
+        self._collider_loads = bool(on)
+
+    def get_collider_loads_enabled(self):
+        return getattr(self, "_collider_loads", False)
+
+    def collider_load_sums(self):
+        """`(sums, dropped, sub_delta)` of the last committed step that recorded loads: `sums` one `(sx, sy, sz)` of Python
+        ints per collider -- the int64 sums of the quantised contributions, impulse scaled by 2^20 and torque by 2^10 --,
+        the contributions dropped, and the sub-step h of that step (0.0 while no step has recorded any)"""
+        arr = (C.c_int64 * (3 * _ffi.MAX_COLLIDERS))()
+        dropped, h, n = C.c_int64(), C.c_double(), C.c_int32()
+        self._check(self._c("get_collider_load_sums")(_ffi.MAX_COLLIDERS, arr, C.byref(dropped), C.byref(h), C.byref(n)))
+        return [(arr[3 * k], arr[3 * k + 1], arr[3 * k + 2]) for k in range(n.value)], dropped.value, h.value
+
+    def collider_loads(self):
+        """one `(jx, jy, torque)` per collider: the impulse in mass px/s and the angular impulse about the collider's pivot in
+        mass px^2/s that it received over the last committed step that recorded loads; the mean force over a step of
+        length delta is j / delta.  All zeros while no step has recorded any."""
+        arr = (_ffi.EggColliderLoad * _ffi.MAX_COLLIDERS)()
+        n = C.c_int32()
+        self._check(self._c("get_collider_loads")(_ffi.MAX_COLLIDERS, arr, C.byref(n)))
+        return [(ld.jx, ld.jy, ld.torque) for ld in arr[:n.value]]
+
     # ------------------------------------------------ force fields (egg_set_forces, DESIGN.md section 2.7)
     @staticmethod
     def _c_forces(forces):

@@ -544,6 +544,52 @@ int egg_set_collider_spin(egg_handle *h, int32_t n, const egg_collider_spin *s);
 /* the spins as stored, one per collider (zeros included): the count in *n, min(*n, cap) records copied */
 int egg_get_collider_spin(const egg_handle *h, int32_t cap, egg_collider_spin *s, int32_t *n);
 
+/* ---- collider loads: the impulse and torque a collider receives in a step ("Collider loads") ----
+ * Steps 5b and 5c act one way: a collider moves particles and feels nothing.  With collider loads on, a RELAXED step with a
+ * non-empty list also records, per collider, what it did to the particles, with the sign of what the collider feels.  It
+ * only observes: positions and every counter are those of the same step with loads off, bit for bit.
+ * One CONTRIBUTION is counted for every (collider c, particle, pass) in which c moved the particle (a hit) and the particle's
+ * inverse mass im satisfies im > eps (the force step's own test, eps of the white config):
+ *   (bx, by)  the position that entered collider c's rule;  (ax, ay)  the position that left it, step 5c's grip included
+ *   m  = 1.0 / im
+ *   ux = m * (bx - ax),  uy = m * (by - ay)                    the reaction: what the collider feels, in mass px
+ *   (Px, Py)  the pivot of the sub-step: the collider's spin record's (px, py) riding on its motion at the sub-step's end,
+ *             Px = px + t vx, Py = py + t vy, exactly as step 5b computes it, also when omega == 0; (0, 0) when the handle
+ *             holds no spin records
+ *   uz = (ax - Px) * uy - (ay - Py) * ux                       its moment about the pivot, in mass px^2
+ * FP64 in exactly this order, no contraction.  Each contribution is quantised before it is added:
+ *   qx = llrint(ux * EGG_COLLIDER_LOAD_IMPULSE_SCALE),  qy = llrint(uy * EGG_COLLIDER_LOAD_IMPULSE_SCALE),
+ *   qz = llrint(uz * EGG_COLLIDER_LOAD_TORQUE_SCALE)           int64, round to nearest, ties to even
+ * If one of the three scaled values is not finite or reaches 2^53 in magnitude, the contribution is dropped whole and
+ * counted in `dropped`; otherwise the three integers are added to collider c's three sums.  Integer addition is
+ * associative: the sums do not depend on the order of lanes, waves, devices or ranks, so a device group and sharded ranks
+ * equal one handle bit for bit.  Both types add into the same sums (a collider's type mask decides who touches it).  The
+ * resolution is 2^-20 (about 1e-6) mass px for the impulse and 2^-10 (about 1e-3) mass px^2 for the torque; the sums wrap
+ * only beyond 2^63 (DESIGN.md has the bound).
+ * The sums cover ONE step: cleared when a step starts, visible when it commits; a failed or discarded step leaves the values
+ * of the step before.  A collider nothing touched reads exactly 0.  egg_set_colliders keeps the switch and zeroes the
+ * stored loads; egg_set_collider_loads zeroes them too.
+ * egg_set_collider_loads(h, on): off by default; accepted in either solver order and with an empty list (it acts only in a
+ * relaxed step with a non-empty list); refused while a step is in flight.  With loads off a step launches exactly the
+ * kernels it launches today, with the same arguments.
+ * egg_get_collider_load_sums: the raw integers, sums[3 k + 0 .. 2] = (sum qx, sum qy, sum qz) of collider k for min(*n, cap)
+ * colliders, the dropped count and the sub-step h of the step that produced them (0.0 while none has).
+ * egg_get_collider_loads: {jx, jy, torque} with jx = ((double)sx / EGG_COLLIDER_LOAD_IMPULSE_SCALE) / h, jy likewise, and
+ * torque = ((double)sz / EGG_COLLIDER_LOAD_TORQUE_SCALE) / h: the impulse in mass px/s (and the angular impulse in mass
+ * px^2/s) the collider received over the step; all zeros while no step has produced any.  The MEAN FORCE over a step of
+ * length delta is j / delta (and the mean torque is torque / delta).  No exact-order rule, no per-particle or per-type
+ * loads, nothing from containment or coupling. */
+#define EGG_COLLIDER_LOAD_IMPULSE_SCALE 1048576.0 /* 2^20 */
+#define EGG_COLLIDER_LOAD_TORQUE_SCALE 1024.0     /* 2^10 */
+typedef struct {
+    double jx, jy; /* mass px/s */
+    double torque; /* mass px^2/s, counter-clockwise positive in the project's x/y, about the collider's pivot */
+} egg_collider_load; /* 24 bytes */
+int egg_set_collider_loads(egg_handle *h, int on);
+int egg_get_collider_loads_enabled(const egg_handle *h, int *on);
+int egg_get_collider_load_sums(egg_handle *h, int32_t cap, int64_t *sums /* [n][3] */, int64_t *dropped, double *sub_delta, int32_t *n);
+int egg_get_collider_loads(egg_handle *h, int32_t cap, egg_collider_load *out, int32_t *n);
+
 /* ---- force fields (not in the reference, which has no forces as it has no boundary; DESIGN.md section 2.7, "Forces") ----
  * A handle holds an ordered list of at most EGG_MAX_FORCES fields.  The values are accelerations in px/s^2 and do not depend
  * on mass.  In every sub-step of a RELAXED step, for every particle of a type, the force step runs before the pre-solve,
@@ -772,6 +818,12 @@ int egg_group_get_collider_motion(const egg_group *g, int32_t cap, egg_collider_
 int egg_group_set_collider_spin(egg_group *g, int32_t n, const egg_collider_spin *s);
 int egg_group_get_collider_spin(const egg_group *g, int32_t cap, egg_collider_spin *s, int32_t *n);
 int egg_group_get_collider_grips(egg_group *g, int64_t grips[2]);
+/* egg_set_collider_loads for every handle of the group alike.  Every device projects only the particles it owns, so only
+ * they contribute; the integer sums and the dropped counts are added over the handles, then converted once: the results
+ * equal one handle's bit for bit.  A group whose handles differ in the switch refuses to step. */
+int egg_group_set_collider_loads(egg_group *g, int on);
+int egg_group_get_collider_load_sums(egg_group *g, int32_t cap, int64_t *sums /* [n][3] */, int64_t *dropped, double *sub_delta, int32_t *n);
+int egg_group_get_collider_loads(egg_group *g, int32_t cap, egg_collider_load *out, int32_t *n);
 /* egg_set_forces for every handle of the group alike, with its rules (relaxed order only; back to exact order only with
  * an empty list); a refused list changes no handle.  Every device accelerates only the particles it owns: the results
  * equal one handle's.  A group whose handles differ in their lists refuses to step. */

@@ -1,0 +1,97 @@
+"""Relaxed order with collider loads (egg_set_collider_loads, DESIGN.md section 2.7 "Collider loads"): ms per step, wall-clock
+time and HIP-event kernel time (EGG_OPT_TIMING), after a warm-up, over a steady window.  One JSON line per (scene, mode);
+measured the way scripts/gpu_spin_bench.py measures, on its scenes and its collider list.
+
+    python scripts/gpu_loads_bench.py [--steps 200] [--warmup 30] [--scenes config3,separate16k] [--modes unset,off,on]
+                                      [--package-root DIR] [--label TEXT]
+
+scenes: config3 = 4,096 batches, 4 per site (bench.py's); separate16k = 16,384 separate batches.  Both under gravity (one
+uniform field) with the list of scripts/gpu_spin_bench.py: a floor (a wall, friction 0.5) 10 px below the centres of the
+lowest row of batches, a half-plane to the left of the grid and a disc above its middle.
+modes: unset = set_collider_loads is never called (the wall instantiation of the gather kernel; the only mode an earlier
+commit has); off = set_collider_loads(False) (must launch what unset launches); on = set_collider_loads(True) (the loads
+instantiation in the wall flavour); spin_off / spin_on = the list moving and turning as gpu_spin_bench.py's mode `spin`,
+without and with loads (the loads instantiation in the spin flavour).
+--package-root imports the package from another checkout (a build of an earlier commit: mode unset only), so that two
+builds can be compared in one session, alternating.  Run one (scene, mode) per process for a figure that is to be relied on.
+Relaxed numbers are NOT the project's headline: that is bench.py, exact order."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from bench import grid_positions  # noqa: E402
+
+SCENES = {"config3": (4096, 4), "separate16k": (16384, 1)}
+RISES = [(30.0, -6.0), None, None]
+OMEGA = 0.0005
+
+
+def run(scene, mode, steps, warmup):
+    from egg_fluid_simulation_amd import WHITE, YOLK, SimulationHandler, _ffi
+    h = SimulationHandler()
+    h.set_solver_order("relaxed")
+    n, overlap = SCENES[scene]
+    xs, ys, _ = grid_positions(n, overlap=overlap)
+    floor, left, mid = float(max(ys)) + 10.0, float(min(xs)) - 60.0, 0.5 * (float(min(xs)) + float(max(xs)))
+    h.set_colliders([("wall", float(min(xs)) - 1000.0, floor, float(max(xs)) + 1000.0, floor), ("half_plane", 1.0, 0.0, left),
+                     ("disc", mid, float(min(ys)) - 80.0, 20.0)])
+    h.set_collider_surfaces([0.5, None, None])
+    h.set_forces([("uniform", 0.0, 980.0)])
+    if mode.startswith("spin"):
+        h.set_collider_motion(RISES)
+        h.set_collider_spin([(mid, floor, OMEGA), None, None])
+    if mode != "unset":
+        h.set_collider_loads(mode in ("on", "spin_on"))
+    h.add_many(xs, ys, 50, 15)
+    for _ in range(warmup):
+        h.step(1 / 60, 2, 3)
+    h.set_option(_ffi.OPT_TIMING, 1)
+    h.synchronize()
+    s0 = h.stats()
+    t0 = time.perf_counter()
+    kernel_ms = 0.0
+    for _ in range(steps):
+        h.step(1 / 60, 2, 3)
+        kernel_ms += h.stats()["last_step_kernel_ms"]  # the slower of the two types' streams
+    h.synchronize()
+    dt = time.perf_counter() - t0
+    s1 = h.stats()
+    n_w, n_y = h.get_n_particles()
+    out = {"name": scene, "mode": mode, "particles": n_w + n_y, "warmup": warmup, "steps": steps,
+           "ms_per_step": 1e3 * dt / steps, "kernel_ms_per_step": kernel_ms / steps,
+           "kernel_ms_white": s1["kernel_ms_sum"][WHITE] / max(1, s1["timed_steps"]),
+           "kernel_ms_yolk": s1["kernel_ms_sum"][YOLK] / max(1, s1["timed_steps"]),
+           "pair_solves_per_step": (s1["pair_solves"] - s0["pair_solves"]) / steps,
+           "hits_per_step": sum(h.collider_hits()) / (warmup + steps),
+           "grips_per_step": sum(h.collider_grips()) / (warmup + steps),
+           "launches_per_step": (s1["kernel_launches"] - s0["kernel_launches"]) / steps}
+    if mode in ("on", "spin_on"):  # the last step's loads: the floor carries the lowest row
+        sums, dropped, sub = h.collider_load_sums()
+        out.update(load_sums=[list(s) for s in sums], dropped=dropped, floor_jy=h.collider_loads()[0][1])
+    h.close()
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=30)
+    ap.add_argument("--scenes", default="config3,separate16k")
+    ap.add_argument("--modes", default="unset,off,on")
+    ap.add_argument("--package-root", default=None)
+    ap.add_argument("--label", default="")
+    a = ap.parse_args()
+    if a.package_root:
+        sys.path.insert(0, os.path.abspath(a.package_root))
+    for scene in a.scenes.split(","):
+        for mode in a.modes.split(","):
+            print(json.dumps(dict(run(scene, mode, a.steps, a.warmup), label=a.label)), flush=True)
+
+
+if __name__ == "__main__":
+    main()
