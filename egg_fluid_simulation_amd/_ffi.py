@@ -120,6 +120,11 @@ class EggColliderLoad(C.Structure):  # egg_collider_load: the impulse and torque
     _fields_ = [("jx", C.c_double), ("jy", C.c_double), ("torque", C.c_double)]
 
 
+class EggColliderBody(C.Structure):  # egg_collider_body: a collider the device integrates from its own loads (48 bytes)
+    _fields_ = [("inv_mass", C.c_double), ("inv_inertia", C.c_double), ("ax", C.c_double), ("ay", C.c_double),
+                ("drag", C.c_double), ("spin_drag", C.c_double)]
+
+
 COLLIDER_LOAD_IMPULSE_SCALE = 1048576.0  # EGG_COLLIDER_LOAD_IMPULSE_SCALE, 2^20
 COLLIDER_LOAD_TORQUE_SCALE = 1024.0      # EGG_COLLIDER_LOAD_TORQUE_SCALE, 2^10
 MAX_COLLIDERS = 64  # EGG_MAX_COLLIDERS
@@ -216,6 +221,8 @@ _SIGNATURES = {
     "egg_get_collider_load_sums": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double),
                                              C.POINTER(C.c_int32)]),
     "egg_get_collider_loads": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggColliderLoad), C.POINTER(C.c_int32)]),
+    "egg_set_collider_bodies": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggColliderBody)]),
+    "egg_get_collider_bodies": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggColliderBody), C.POINTER(C.c_int32)]),
     "egg_group_set_collider_loads": (C.c_int, [C.c_void_p, C.c_int]),
     "egg_group_get_collider_load_sums": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double),
                                                    C.POINTER(C.c_int32)]),

@@ -541,6 +541,25 @@ struct EggRelaxedGroupCohColLoadArgs {
     EggRxLoadFields l;
 };
 
+// Collider bodies (egg_set_collider_bodies, DESIGN.md section 2.7, "Collider bodies"): egg_rx_bodies_kernel runs once per
+// sub-step of a step in which bodies act, one wave, lane k = collider k.  It rewrites the records the loads instantiations
+// of the gather read -- the list, the motions, the spins and the row of turns -- from the loads the sub-step has added to the
+// sums.  A record has the layout of the ABI's egg_collider_body (48 bytes).
+struct EggBody {
+    double inv_mass, inv_inertia, ax, ay, drag, spin_drag;
+};
+struct EggRxBodiesArgs {
+    EggCollider *list;                   // [count]: becomes the geometry of the sub-step's end
+    EggMotion *motions;                  // [count]
+    EggSpin *spins;                      // [count]
+    double2 *cs;                         // [count]: the turn (c, s) of one sub-step, read by the gathers as both of their rows
+    const EggBody *bodies;               // [count]
+    const unsigned long long *sums;      // [count][3]: the step's load sums so far (EggRxLoadFields::sums)
+    unsigned long long *seen;            // [count][3]: the sums as the sub-step before left them
+    double h;                            // the sub-step
+    int32_t count;
+};
+
 // Force fields (egg_set_forces, DESIGN.md section 2.7, "Forces"): the force instantiations of the kernels that begin a
 // sub-step (egg_rx_begin*_frc_kernel, egg_rx_mid*_frc_kernel) take these besides.  The list is the handle's, in a small
 // device buffer written when it is set; a record has the layout of the ABI's egg_force (40 bytes).

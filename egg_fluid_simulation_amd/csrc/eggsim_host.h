@@ -108,6 +108,7 @@ extern "C" __global__ void egg_rx_gather_col_load_kernel(EggRelaxedColLoadArgs A
 extern "C" __global__ void egg_rx_gather_group_col_load_kernel(EggRelaxedGroupColLoadArgs A);
 extern "C" __global__ void egg_rx_gather_coh_col_load_kernel(EggRelaxedCohColLoadArgs A);
 extern "C" __global__ void egg_rx_gather_group_coh_col_load_kernel(EggRelaxedGroupCohColLoadArgs A);
+extern "C" __global__ void egg_rx_bodies_kernel(EggRxBodiesArgs A);
 extern "C" __global__ void egg_rx_begin_frc_kernel(EggRelaxedFrcArgs A);
 extern "C" __global__ void egg_rx_mid_frc_kernel(EggRelaxedFrcArgs A);
 extern "C" __global__ void egg_rx_begin_group_frc_kernel(EggRelaxedGroupFrcArgs A);
@@ -490,6 +491,18 @@ struct egg_handle {
     std::vector<int64_t> load_sums;
     int64_t load_dropped = 0;
     double load_sub_delta = 0.0;
+    // collider bodies (egg_set_collider_bodies; relaxed order, one handle only): the records as egg_get_collider_bodies
+    // returns them, empty = none; bodies_any = some record frees a translation or a rotation.  A step in which bodies act
+    // (relaxed_step_bodies) puts the records, the row of turns and the sums the sub-step before has seen on the device, and
+    // orders the two types' streams around the integrator with the two events (created by the first such step):
+    // body_ready = the other type's last launch of the sub-step, body_done = the integrator of the sub-step
+    std::vector<egg_collider_body> bodies;
+    bool bodies_any = false;
+    bool bodies_step = false;  // the step being committed had bodies acting: the commit reads the device's records back
+    DevBuf<EggBody> d_bodies;
+    DevBuf<double2> d_body_cs;
+    DevBuf<unsigned long long> d_body_seen;
+    hipEvent_t body_ready = nullptr, body_done = nullptr;
     // force fields (egg_set_forces; relaxed order only): the list as egg_get_forces returns it and its copy on the device
     // (written when the list is set, never per step)
     std::vector<egg_force> forces;
@@ -714,6 +727,7 @@ struct RelaxedStep {  // one type of one handle in a relaxed step
     double adhesion_c = 0;                 // adhesion (L.adhesion): the compliance of its own strength
     int64_t ghost_cap = 0;    // a pass runs over n + ghost_cap entries
     int launches = 0;         // kernel launches so far: into the statistics at the commit
+    bool bodies = false;      // collider bodies act: launch_pass poses every sub-step as the first over the device's records
 };
 // key base of a local atom (batch key, particle count) into *base: EGG_OK, or the status it failed the handle with
 using KeyBaseFn = std::function<int(int64_t, int64_t, int32_t *)>;

@@ -176,6 +176,8 @@ void egg_destroy(egg_handle *h) {
         if (h->couple_read[w]) (void)hipEventDestroy(h->couple_read[w]);
     }
     for (hipEvent_t e : h->contain_summed) (void)hipEventDestroy(e);
+    if (h->body_ready) (void)hipEventDestroy(h->body_ready);
+    if (h->body_done) (void)hipEventDestroy(h->body_done);
     delete h;
 }
 
@@ -1055,6 +1057,8 @@ int egg_set_colliders(egg_handle *h, int32_t n, const egg_collider *c) {
     h->load_sums.assign(3 * h->colliders.size(), 0);  // (the loads belonged to the old list; the switch stays)
     h->load_dropped = 0;
     h->load_sub_delta = 0.0;
+    h->bodies.clear();  // (and no collider is a body)
+    h->bodies_any = false;
     return EGG_OK;
 }
 
@@ -1262,6 +1266,55 @@ int egg_get_collider_loads(egg_handle *h, int32_t cap, egg_collider_load *out, i
         out[k].jy = any ? ((double)h->load_sums[(size_t)(3 * k + 1)] / EGG_COLLIDER_LOAD_IMPULSE_SCALE) / hs : 0.0;
         out[k].torque = any ? ((double)h->load_sums[(size_t)(3 * k + 2)] / EGG_COLLIDER_LOAD_TORQUE_SCALE) / hs : 0.0;
     }
+    return EGG_OK;
+}
+
+// Collider bodies ("Collider bodies"): one record per collider, or none (no collider is a body).
+// Everything is checked before anything changes; geometry, surfaces, motions and spins stay as they are.  Nothing goes to the
+// device here: a step in which bodies act uploads the records it runs on.
+int egg_set_collider_bodies(egg_handle *h, int32_t n, const egg_collider_body *b) {
+    if (!h) return EGG_ERR_INVALID_ARGUMENT;
+    REJECT_IN_FLIGHT(h, "egg_set_collider_bodies");
+    static_assert(sizeof(egg_collider_body) == 48 && sizeof(EggBody) == sizeof(egg_collider_body), "a body record is 48 bytes");
+    if (n != 0 && n != (int32_t)h->colliders.size())
+        return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_collider_bodies: n = %d, the list holds %d colliders (n is that, or 0)", (int)n,
+                    (int)h->colliders.size());
+    if (n > 0 && !b) return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_collider_bodies: n = %d without records", (int)n);
+    std::vector<egg_collider_body> list((size_t)n);
+    bool any = false;
+    for (int32_t k = 0; k < n; ++k) {
+        egg_collider_body &o = list[(size_t)k];
+        o = b[k];
+        if (!std::isfinite(o.inv_mass) || o.inv_mass < 0)
+            return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_collider_bodies: collider %d: inv_mass %g is negative or not finite", (int)k, o.inv_mass);
+        if (!std::isfinite(o.inv_inertia) || o.inv_inertia < 0)
+            return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_collider_bodies: collider %d: inv_inertia %g is negative or not finite", (int)k,
+                        o.inv_inertia);
+        if (!std::isfinite(o.ax) || !std::isfinite(o.ay))
+            return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_collider_bodies: collider %d: the acceleration (%g, %g) is not finite", (int)k, o.ax, o.ay);
+        if (!std::isfinite(o.drag) || o.drag < 0)
+            return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_collider_bodies: collider %d: drag %g is negative or not finite", (int)k, o.drag);
+        if (!std::isfinite(o.spin_drag) || o.spin_drag < 0)
+            return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_collider_bodies: collider %d: spin_drag %g is negative or not finite", (int)k, o.spin_drag);
+        o.inv_mass = o.inv_mass + 0.0;  // (-0.0 is stored as +0.0: handles set alike compare alike)
+        o.inv_inertia = o.inv_inertia + 0.0;
+        o.ax = o.ax + 0.0;
+        o.ay = o.ay + 0.0;
+        o.drag = o.drag + 0.0;
+        o.spin_drag = o.spin_drag + 0.0;
+        any |= o.inv_mass > 0.0 || o.inv_inertia > 0.0;
+    }
+    h->bodies.swap(list);
+    h->bodies_any = any;
+    return EGG_OK;
+}
+
+int egg_get_collider_bodies(const egg_handle *h, int32_t cap, egg_collider_body *b, int32_t *n) {
+    if (!h) return EGG_ERR_INVALID_ARGUMENT;
+    const int32_t have = (int32_t)h->colliders.size();
+    if (n) *n = have;
+    for (int32_t k = 0; b && k < std::min(cap, have); ++k)
+        b[k] = h->bodies.empty() ? egg_collider_body{0.0, 0.0, 0.0, 0.0, 0.0, 0.0} : h->bodies[(size_t)k];
     return EGG_OK;
 }
 

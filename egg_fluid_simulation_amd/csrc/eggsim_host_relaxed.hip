@@ -38,6 +38,12 @@
 // it before either stream has work, relaxed_commit reads it once every path has waited for both, and nothing else touches
 // it, so a failed step leaves the values of the step before.  With loads off a step launches what it launched, with the
 // same arguments.
+// While collider bodies act (egg_set_collider_bodies, RelaxedStep::bodies: some collider is a body, loads are on, the list is
+// not empty) relaxed_step_bodies drives the step: the loads instantiations run with every rule on, launch_pass poses every
+// sub-step as the first of a step over the records on the device, and after the last launch of a sub-step of both types one
+// launch of egg_rx_bodies_kernel rewrites those records from the sums the sub-step has added.  relaxed_commit reads them
+// back in place of advance_colliders; a failed step puts the host's copies back.  With no body a step enqueues and launches
+// what it always did.
 // With force fields (egg_set_forces, RelaxedLayout::forces) launch_substep picks the force instantiation of the begin / mid
 // kernel and RelaxedStep::frc carries the handle's list; with an empty list a step launches what it always launched.
 // With viscosity (egg_set_viscosity, RelaxedLayout::V) every sub-step of a type whose coefficient is not zero ends with
@@ -178,6 +184,56 @@ EggRelaxedArgs relaxed_args(egg_handle *h, int w, const Env &env) {
 
 }  // namespace
 
+// Collider bodies act in a relaxed step of a handle whose list is not empty, holds a body, and records loads.
+static bool bodies_act(const egg_handle *h) { return h->bodies_any && h->opt_loads && !h->colliders.empty(); }
+
+// The records a step with bodies runs on, from the host's copies to the device: the list, and a surface, a motion and a
+// spin record for every collider, defaults and zeros included.  No step is running.
+static int upload_body_records(egg_handle *h) {
+    const size_t n = h->colliders.size();
+    const std::vector<egg_collider_surface> srf = h->surfaces.empty() ? std::vector<egg_collider_surface>(n, egg_collider_surface{0.0, 0.0, 0.0}) : h->surfaces;
+    const std::vector<egg_collider_motion> mov = h->motions.empty() ? std::vector<egg_collider_motion>(n, egg_collider_motion{0.0, 0.0}) : h->motions;
+    const std::vector<egg_collider_spin> spn = h->spins.empty() ? std::vector<egg_collider_spin>(n, egg_collider_spin{0.0, 0.0, 0.0}) : h->spins;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, h->d_surfaces.reserve(EGG_MAX_COLLIDERS, false, nullptr));
+    HIP_TRY(h, h->d_motions.reserve(EGG_MAX_COLLIDERS, false, nullptr));
+    HIP_TRY(h, h->d_spins.reserve(EGG_MAX_COLLIDERS, false, nullptr));
+    HIP_TRY(h, hipMemcpy(h->d_colliders.p, h->colliders.data(), n * sizeof(egg_collider), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(h->d_surfaces.p, srf.data(), n * sizeof(egg_collider_surface), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(h->d_motions.p, mov.data(), n * sizeof(egg_collider_motion), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(h->d_spins.p, spn.data(), n * sizeof(egg_collider_spin), hipMemcpyHostToDevice));
+    return EGG_OK;
+}
+
+// Per step with bodies acting: the records above, the body records, the turn (c, s) of the first sub-step per collider --
+// a free-turning body's by the four lines of the integrator, any other's by libm, (cos, sin)(h omega) -- and `seen`, which
+// starts at zero with the sums.
+static int prepare_bodies(egg_handle *h, double sub_delta) {
+    const size_t n = h->colliders.size();
+    int rc = upload_body_records(h);
+    if (rc != EGG_OK) return rc;
+    std::vector<double2> cs(n);
+    for (size_t k = 0; k < n; ++k) {
+        const double omega = h->spins.empty() ? 0.0 : h->spins[k].omega;
+        if (h->bodies[k].inv_inertia > 0.0) {
+            const double u = 0.5 * (sub_delta * omega);
+            const double den = 1.0 + u * u;
+            cs[k] = double2{(1.0 - u * u) / den, (u + u) / den};
+        } else {
+            const double a = sub_delta * omega;
+            cs[k] = double2{cos(a), sin(a)};
+        }
+    }
+    const std::vector<unsigned long long> none(3 * n, 0ull);
+    HIP_TRY(h, h->d_bodies.reserve(EGG_MAX_COLLIDERS, false, nullptr));
+    HIP_TRY(h, h->d_body_cs.reserve(EGG_MAX_COLLIDERS, false, nullptr));
+    HIP_TRY(h, h->d_body_seen.reserve(3 * (size_t)EGG_MAX_COLLIDERS, false, nullptr));
+    HIP_TRY(h, hipMemcpy(h->d_bodies.p, h->bodies.data(), n * sizeof(egg_collider_body), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(h->d_body_cs.p, cs.data(), n * sizeof(double2), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(h->d_body_seen.p, none.data(), none.size() * 8, hipMemcpyHostToDevice));
+    return EGG_OK;
+}
+
 // per step: the environment scalars of both types (a type without particles has them too: the commit reports its
 // budget), config changes and the atoms
 int prepare_step(egg_handle *h, double delta, int S, RelaxedStep st[2]) {
@@ -228,6 +284,7 @@ int prepare_step(egg_handle *h, double delta, int S, RelaxedStep st[2]) {
             HIP_TRY(h, hipMemcpy(h->d_spins.p, h->spins.data(), n * sizeof(egg_collider_spin), hipMemcpyHostToDevice));
         }
     }
+    if (bodies_act(h)) return prepare_bodies(h, sub_delta);
     return EGG_OK;
 }
 
@@ -414,6 +471,11 @@ int launch_pass(RelaxedStep &st, int p) {
     if (st.L.spin) {
         st.spn.cs = h->d_spin_table.p + (size_t)(p / st.C) * h->colliders.size();  // the sub-step's row
         st.spn.ts = (double)(p / st.C) * st.env.sub_delta;                          // ... and its start
+    }
+    if (st.bodies) {  // every sub-step is the first of a step over the records the integrator has left on the device
+        st.mov.t = st.env.sub_delta;
+        st.spn.cs = h->d_body_cs.p;
+        st.spn.ts = 0.0;
     }
     const dim3 grid((unsigned)((s.n + st.ghost_cap + 255) / 256)), block(256);  // (the ghost count is read on the device)
     HIP_TRY(h, hipMemsetAsync(r.hkey.p, 0xFF, (size_t)r.table * 8, s.stream));
@@ -691,6 +753,7 @@ int launch_end(RelaxedStep &st) {
 }
 
 static int relaxed_finish(egg_handle *h, RelaxedStep st[2], int S, int C);
+static int relaxed_step_bodies(egg_handle *h, RelaxedStep st[2], int S, int C);
 
 // A step with coupling (factor > 0, both types populated; st: after prepare_step).  The enqueue order is sub-step by
 // sub-step across both types, so that every event a stream waits for has been recorded by then.  Before a type's table
@@ -728,10 +791,101 @@ static int relaxed_step_coupled(egg_handle *h, RelaxedStep st[2], int S, int C) 
     return relaxed_finish(h, st, S, C);
 }
 
+// The integrator of sub-step `sub` on the stream of st's type, behind that type's last launch of the sub-step.
+static int launch_bodies(RelaxedStep &st) {
+    egg_handle *h = st.h;
+    EggRxBodiesArgs k{};
+    k.list = h->d_colliders.p;
+    k.motions = h->d_motions.p;
+    k.spins = h->d_spins.p;
+    k.cs = h->d_body_cs.p;
+    k.bodies = h->d_bodies.p;
+    k.sums = h->d_loads.p;
+    k.seen = h->d_body_seen.p;
+    k.h = st.env.sub_delta;
+    k.count = (int32_t)h->colliders.size();
+    hipLaunchKernelGGL(egg_rx_bodies_kernel, dim3(1), dim3(64), 0, h->sys[st.w].stream, k);
+    ++st.launches;
+    return EGG_OK;
+}
+
+// A step in which collider bodies act (st: after prepare_step, which has put the records on the device).  The gathers of
+// both types read the records the integrator writes, so the step is enqueued sub-step by sub-step across both types, with or
+// without coupling.  The integrator runs on the stream of the first populated type (`lead`), behind that type's launches of
+// the sub-step; with both types populated it first waits for body_ready, which the other stream records behind its own last
+// launch of the sub-step, and the other stream waits for body_done before its next gather.  Everything in front of a
+// sub-step's first collision pass -- begin / mid, coupling, containment -- reads no collider and runs ahead of that wait.
+// With one type empty there is one stream and no event.  No host synchronisation inside the step.
+static int relaxed_step_bodies(egg_handle *h, RelaxedStep st[2], int S, int C) {
+    int rc = EGG_OK;
+    const bool on[2] = {h->sys[0].n > 0, h->sys[1].n > 0};
+    const bool both = on[0] && on[1];
+    const int lead = on[0] || !on[1] ? 0 : 1;  // (without a particle the integrators still run: a body falls by its own acceleration)
+    for (int w = 0; w < 2; ++w) {
+        if (!on[w]) continue;
+        if (h->sys[w].n > kRelaxedMaxParticles) return fail(h, EGG_ERR_UNSUPPORTED, EGG_RX_TOO_MANY_TEXT);
+        rc = prepare_type(st[w], C, 0, RelaxedLayout{(size_t)S * C, 0, false}, {}, nullptr);
+        if (rc != EGG_OK) return rc;
+        // the loads instantiation with every rule on, over a motion, a spin and a surface record per collider
+        st[w].bodies = true;
+        st[w].mov.list = h->d_motions.p;
+        st[w].spn.list = h->d_spins.p;
+        st[w].spn.hcs = h->d_body_cs.p;
+        st[w].lod.moving = st[w].lod.turning = st[w].lod.pivots = 1;
+        if (!st[w].L.surfaces) st[w].lsrf.list = h->d_surfaces.p;
+    }
+    if (both) {
+        if (!h->body_ready) HIP_TRY(h, hipEventCreateWithFlags(&h->body_ready, hipEventDisableTiming));
+        if (!h->body_done) HIP_TRY(h, hipEventCreateWithFlags(&h->body_done, hipEventDisableTiming));
+    }
+    const bool coupled = both && st[0].L.coupling;
+    h->bodies_step = true;
+    if (h->opt_timing)
+        for (int w = 0; w < 2; ++w)
+            if (on[w]) HIP_TRY(h, hipEventRecord(h->sys[w].ev0, h->sys[w].stream));
+    for (int sub = 0; sub < S; ++sub) {
+        for (int w = 0; w < 2 && rc == EGG_OK; ++w)
+            if (on[w]) rc = launch_substep(st[w], sub);
+        for (int w = 0; w < 2 && rc == EGG_OK && coupled; ++w) rc = launch_coupling_tables(st[w]);
+        for (int w = 0; w < 2 && rc == EGG_OK; ++w) {
+            if (!on[w]) continue;
+            if (coupled) rc = launch_coupling(st[w], st[w ^ 1]);
+            if (rc == EGG_OK && st[w].L.containment) rc = w == 0 ? launch_contain_sum(st[0], sub) : launch_contain(st[1], st[0], sub);
+        }
+        for (int w = 0; w < 2 && rc == EGG_OK; ++w) {
+            if (!on[w]) continue;
+            if (coupled) HIP_TRY(h, hipStreamWaitEvent(h->sys[w].stream, h->couple_read[w ^ 1], 0));
+            if (both && w != lead && sub > 0) HIP_TRY(h, hipStreamWaitEvent(h->sys[w].stream, h->body_done, 0));
+            for (int c = 0; c < C && rc == EGG_OK; ++c) rc = launch_pass(st[w], sub * C + c);
+            if (rc == EGG_OK && st[w].L.V) rc = launch_viscosity(st[w], sub);
+            if (rc == EGG_OK && both && w != lead) HIP_TRY(h, hipEventRecord(h->body_ready, h->sys[w].stream));
+        }
+        if (rc != EGG_OK) return rc;
+        if (both) HIP_TRY(h, hipStreamWaitEvent(h->sys[lead].stream, h->body_ready, 0));
+        rc = launch_bodies(st[lead]);
+        if (rc != EGG_OK) return rc;
+        if (both) HIP_TRY(h, hipEventRecord(h->body_done, h->sys[lead].stream));
+    }
+    for (int w = 0; w < 2; ++w) {
+        if (!on[w]) continue;
+        rc = launch_end(st[w]);
+        if (rc == EGG_OK) rc = read_status(st[w]);
+        if (rc != EGG_OK) return rc;
+        if (h->opt_timing) HIP_TRY(h, hipEventRecord(h->sys[w].ev1, h->sys[w].stream));
+    }
+    if (!on[lead]) HIP_TRY(h, hipStreamSynchronize(h->sys[lead].stream));  // (relaxed_finish waits for populated types only)
+    return relaxed_finish(h, st, S, C);
+}
+
 int relaxed_step(egg_handle *h, double delta, int S, int C) {  // L:1722-1989, collision passes relaxed
+    h->bodies_step = false;
+    if (h->bodies_any && !h->colliders.empty() && !h->opt_loads)  // (before anything is launched or copied)
+        return fail(h, EGG_ERR_UNSUPPORTED, "relaxed order: collider bodies are integrated from their loads (egg_set_collider_loads with on = 1 first, "
+                                            "or egg_set_collider_bodies with n = 0)");
     RelaxedStep st[2];
     int rc = prepare_step(h, delta, S, st);
     if (rc != EGG_OK) return rc;
+    if (bodies_act(h)) return relaxed_step_bodies(h, st, S, C);
     if (h->coupling_factor > 0.0 && h->sys[0].n > 0 && h->sys[1].n > 0) return relaxed_step_coupled(h, st, S, C);
     for (int w = 0; w < 2; ++w) {
         System &s = h->sys[w];
@@ -771,6 +925,11 @@ static int relaxed_finish(egg_handle *h, RelaxedStep st[2], int S, int C) {
         bad |= bad_cell(st[w]);
     }
     if (bad) {  // nothing is committed: [cur] still holds the state before the step
+        if (h->bodies_step) {  // ... and the records the integrator has rewritten are the host's untouched copies again
+            h->bodies_step = false;
+            const int rc = upload_body_records(h);
+            if (rc != EGG_OK) return rc;
+        }
         h->stats.kernel_launches += st[0].launches + st[1].launches;
         return fail(h, EGG_ERR_UNSUPPORTED, "%s", kRelaxedBadCellText);
     }
@@ -785,6 +944,7 @@ static int relaxed_finish(egg_handle *h, RelaxedStep st[2], int S, int C) {
 // last sub-step's row of the step's table, and its stored pivot becomes the pivot of the step's end; the spin records on
 // the device follow.
 static void advance_colliders(egg_handle *h, double t, int S) {
+    if (h->bodies_step) return;  // (take_bodies has read the device's records, advanced sub-step by sub-step)
     const size_t n = h->colliders.size();
     for (size_t k = 0; k < n; ++k) {
         egg_collider &c = h->colliders[k];
@@ -829,6 +989,25 @@ static void advance_colliders(egg_handle *h, double t, int S) {
     if (e == hipSuccess && h->spins_turn)
         e = hipMemcpy(h->d_spins.p, h->spins.data(), h->spins.size() * sizeof(egg_collider_spin), hipMemcpyHostToDevice);
     if (e != hipSuccess) (void)fail(h, EGG_ERR_DEVICE, "relaxed order: the moved colliders did not reach the device: %s", hipGetErrorString(e));
+}
+
+// Collider bodies at the commit: the list, the motions and the spins as the integrator of the last sub-step left them on
+// the device become the handle's, in place of advance_colliders.  No step is running: every path waits for its streams
+// before it commits, and the integrator ran on one of them.
+static void take_bodies(egg_handle *h) {
+    const size_t n = h->colliders.size();
+    h->motions.resize(n);
+    h->spins.resize(n);
+    hipError_t e = hipSetDevice(h->device);
+    if (e == hipSuccess) e = hipMemcpy(h->colliders.data(), h->d_colliders.p, n * sizeof(egg_collider), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(h->motions.data(), h->d_motions.p, n * sizeof(egg_collider_motion), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(h->spins.data(), h->d_spins.p, n * sizeof(egg_collider_spin), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) (void)fail(h, EGG_ERR_DEVICE, "relaxed order: the collider bodies did not reach the host: %s", hipGetErrorString(e));
+    h->motions_move = h->spins_turn = false;
+    for (size_t k = 0; k < n; ++k) {
+        h->motions_move |= h->motions[k].vx != 0.0 || h->motions[k].vy != 0.0;
+        h->spins_turn |= h->spins[k].omega != 0.0;
+    }
 }
 
 // Collider loads at the commit: the step's sums, which both types' streams have added into, become the handle's.  No step
@@ -878,6 +1057,7 @@ void relaxed_commit(egg_handle *h, const RelaxedStep st[2], int S, int C, double
         s.out_copied = false;
     }
     if (h->opt_loads && !h->colliders.empty()) take_loads(h, st[0].env.sub_delta);
+    if (h->bodies_step) take_bodies(h);
     if ((h->motions_move || h->spins_turn) && !h->colliders.empty()) advance_colliders(h, (double)S * st[0].env.sub_delta, S);
     h->stats.last_step_kernel_ms = ms;
     if (h->opt_timing) {
@@ -886,6 +1066,7 @@ void relaxed_commit(egg_handle *h, const RelaxedStep st[2], int S, int C, double
     }
     h->stats.steps++;
     h->stats.relaxed_steps++;
+    h->bodies_step = false;
 }
 
 void leave_relaxed(egg_handle *h) {

@@ -142,6 +142,12 @@ int relaxed_group_step(egg_handle *const *hs, int nh, double delta, int S, int C
             return EGG_ERR_INVALID_ARGUMENT;
         }
     }
+    for (int k = 0; k < nh; ++k) {  // (the loads would have to be summed across the handles every sub-step)
+        if (hs[k]->bodies_any) {
+            *error = "relaxed order: collider bodies run on a single handle only (egg_set_collider_bodies with n = 0 first)";
+            return EGG_ERR_UNSUPPORTED;
+        }
+    }
     for (int k = 1; k < nh; ++k) {  // (with loads on the pivots count although nothing turns: the torque is about them)
         const std::vector<egg_collider_spin> &a = hs[0]->spins, &b = hs[k]->spins;
         const bool same_pivots = !hs[0]->opt_loads || hs[0]->spins_turn ||

@@ -795,6 +795,94 @@ extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_col_load_k
 extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_coh_col_load_kernel(EggRelaxedCohColLoadArgs A) { rx_gather<false, true, true, true, true>(A.a, EggRxGroupFields{}, A.c, A.d, A.s, &A.m, &A.r, &A.l); }
 extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_coh_col_load_kernel(EggRelaxedGroupCohColLoadArgs A) { rx_gather<true, true, true, true, true>(A.a, A.g, A.c, A.d, A.s, &A.m, &A.r, &A.l); }
 
+// ---- collider bodies ----
+
+// The integrator of collider bodies (egg_set_collider_bodies; DESIGN.md section 2.7, "Collider bodies"): one launch of one
+// wave after the last pass of a sub-step of both types, lane k = collider k.  FP64 in exactly the order of the
+// definition, no contraction: (1) the sub-step's impulse from the int64 sums, (2) the stored geometry and pivot become
+// what the sub-step's gathers used at t = h -- the expressions of the host's advance_colliders, its omega != 0 branch
+// included --, (3) the translation and (4) the rotation of a body, whose next turn is a Cayley rotation: only + - * /, so
+// the host and the model agree with it to the bit.  Plain loads and stores; no atomics, no LDS.
+extern "C" __global__ void __launch_bounds__(64) egg_rx_bodies_kernel(EggRxBodiesArgs A) {
+    const int k = (int)threadIdx.x;
+    if (k >= A.count) return;
+    const double h = A.h;
+    const EggBody b = A.bodies[k];
+    EggCollider c = A.list[k];
+    EggMotion m = A.motions[k];
+    EggSpin sp = A.spins[k];
+    double2 cs = A.cs[k];
+    // 1. the impulse of the sub-step
+    long long d[3];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        const unsigned long long now = A.sums[3 * k + q];
+        d[q] = (long long)(now - A.seen[3 * k + q]);
+        A.seen[3 * k + q] = now;
+    }
+    const double Jx = ((double)d[0] / EGG_RX_LOAD_SCALE_IMPULSE) / h;
+    const double Jy = ((double)d[1] / EGG_RX_LOAD_SCALE_IMPULSE) / h;
+    const double Jz = ((double)d[2] / EGG_RX_LOAD_SCALE_TORQUE) / h;
+    // 2. advance by what the sub-step used
+    const double ox = h * m.vx, oy = h * m.vy;
+    if (sp.omega != 0.0) {
+        const double Px = sp.px + ox, Py = sp.py + oy;
+        if (c.kind == EGG_RX_COLLIDER_HALF_PLANE) {
+            const double keep = c.p[2] - (c.p[0] * sp.px + c.p[1] * sp.py);
+            const double nx = cs.x * c.p[0] - cs.y * c.p[1], ny = cs.y * c.p[0] + cs.x * c.p[1];
+            c.p[0] = nx;
+            c.p[1] = ny;
+            c.p[2] = (nx * Px + ny * Py) + keep;
+        } else {
+            const double rx = c.p[0] - sp.px, ry = c.p[1] - sp.py;
+            c.p[0] = Px + (cs.x * rx - cs.y * ry);
+            c.p[1] = Py + (cs.y * rx + cs.x * ry);
+            if (c.kind == EGG_RX_COLLIDER_SEGMENT || c.kind == EGG_RX_COLLIDER_WALL) {
+                const double qx = c.p[2] - sp.px, qy = c.p[3] - sp.py;
+                c.p[2] = Px + (cs.x * qx - cs.y * qy);
+                c.p[3] = Py + (cs.y * qx + cs.x * qy);
+            }
+        }
+        sp.px = Px;
+        sp.py = Py;
+    } else if (c.kind == EGG_RX_COLLIDER_HALF_PLANE) {
+        c.p[2] = c.p[2] + (c.p[0] * ox + c.p[1] * oy);
+    } else {
+        c.p[0] = c.p[0] + ox;
+        c.p[1] = c.p[1] + oy;
+        if (c.kind == EGG_RX_COLLIDER_SEGMENT || c.kind == EGG_RX_COLLIDER_WALL) {
+            c.p[2] = c.p[2] + ox;
+            c.p[3] = c.p[3] + oy;
+        }
+    }
+    // 3. translation
+    if (b.inv_mass > 0.0) {
+        m.vx = m.vx + Jx * b.inv_mass;
+        m.vy = m.vy + Jy * b.inv_mass;
+        m.vx = m.vx + h * b.ax;
+        m.vy = m.vy + h * b.ay;
+        double f = 1.0 - h * b.drag;
+        if (!(f > 0.0)) f = 0.0;
+        m.vx = m.vx * f;
+        m.vy = m.vy * f;
+    }
+    // 4. rotation
+    if (b.inv_inertia > 0.0) {
+        sp.omega = sp.omega + Jz * b.inv_inertia;
+        double f = 1.0 - h * b.spin_drag;
+        if (!(f > 0.0)) f = 0.0;
+        sp.omega = sp.omega * f;
+        const double u = 0.5 * (h * sp.omega);
+        const double den = 1.0 + u * u;
+        cs.x = (1.0 - u * u) / den;
+        cs.y = (u + u) / den;
+    }
+    A.list[k] = c;
+    A.motions[k] = m;
+    A.spins[k] = sp;
+    A.cs[k] = cs;
+}
+
 // ---- viscosity ----
 
 // The viscous rank kernel: rx_rank's order inside a cell, with u = pos - prev of the entry in the grouped swr slot (a

@@ -105,6 +105,9 @@ int egg_set_collider_loads(egg_handle *h, int on);
 int egg_get_collider_loads_enabled(const egg_handle *h, int *on);
 int egg_get_collider_load_sums(egg_handle *h, int32_t cap, int64_t *sums, int64_t *dropped, double *sub_delta, int32_t *n);
 int egg_get_collider_loads(egg_handle *h, int32_t cap, egg_collider_load *out, int32_t *n);
+typedef struct { double inv_mass, inv_inertia, ax, ay, drag, spin_drag; } egg_collider_body;
+int egg_set_collider_bodies(egg_handle *h, int32_t n, const egg_collider_body *b);
+int egg_get_collider_bodies(const egg_handle *h, int32_t cap, egg_collider_body *b, int32_t *n);
 typedef struct egg_group egg_group;
 int egg_group_set_solver_order(egg_group *g, int32_t order, double relaxation);
 int egg_group_set_cohesion(egg_group *g, int32_t mode);
@@ -581,6 +584,41 @@ function SimulationHandler:get_collider_spin()
     if self:_check(lib.egg_get_collider_spin(self._h, _max_colliders, arr, n)) ~= 0 then return {} end
     local out = {}
     for k = 0, n[0] - 1 do out[k + 1] = { arr[k].px, arr[k].py, arr[k].omega } end
+    return out
+end
+
+-- Not in the reference: collider bodies (egg_set_collider_bodies in include/eggsim.h; DESIGN.md section 2.7,
+-- "Collider bodies").
+
+--- one body per collider of the current list: `false` for a collider that stays kinematic or
+--- `{ inv_mass, inv_inertia [, ax, ay [, drag, spin_drag ] ] }`.  inv_mass > 0 frees the translation, inv_inertia > 0 the rotation
+--- about the collider's spin pivot; in a relaxed step with collider loads on the device integrates every body from the loads
+--- it receives.  `{}` resets, and so does set_colliders.
+function SimulationHandler:set_collider_bodies(bodies)
+    local n = #bodies
+    local arr = ffi.new("egg_collider_body[?]", math.max(n, 1))
+    for k = 1, n do  -- (not ipairs: a nil hole must not end the walk short of n)
+        local b = bodies[k]
+        if b == false then b = { 0, 0 } end
+        if type(b) ~= "table" or (#b ~= 2 and #b ~= 4 and #b ~= 6) then
+            log.error("In SimulationHandler.set_collider_bodies: body " .. k ..
+                ": expected false or { inv_mass, inv_inertia [, ax, ay [, drag, spin_drag ] ] }")
+            return
+        end
+        local o = arr[k - 1]
+        o.inv_mass, o.inv_inertia, o.ax, o.ay, o.drag, o.spin_drag = b[1], b[2], b[3] or 0, b[4] or 0, b[5] or 0, b[6] or 0
+    end
+    self:_check(lib.egg_set_collider_bodies(self._h, n, arr))
+end
+
+--- the bodies as stored, one `{ inv_mass, inv_inertia, ax, ay, drag, spin_drag }` per collider (zeros included)
+function SimulationHandler:get_collider_bodies()
+    local arr, n = ffi.new("egg_collider_body[?]", _max_colliders), ffi.new("int32_t[1]")
+    if self:_check(lib.egg_get_collider_bodies(self._h, _max_colliders, arr, n)) ~= 0 then return {} end
+    local out = {}
+    for k = 0, n[0] - 1 do
+        out[k + 1] = { arr[k].inv_mass, arr[k].inv_inertia, arr[k].ax, arr[k].ay, arr[k].drag, arr[k].spin_drag }
+    end
     return out
 end
 

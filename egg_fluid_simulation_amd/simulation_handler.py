@@ -320,6 +320,49 @@ class _HandlerSurface:
         self._check(self._c("get_collider_loads")(_ffi.MAX_COLLIDERS, arr, C.byref(n)))
         return [(ld.jx, ld.jy, ld.torque) for ld in arr[:n.value]]
 
+    # ------------------------------------------------ collider bodies (egg_set_collider_bodies)
+    _BODIES_LIMIT = ("collider bodies: the device integrates a body from the loads of one handle, so bodies run on a single "
+                     "SimulationHandler only; only lists without a body are accepted here")
+
+    @staticmethod
+    def _c_bodies(bodies):
+        """a list with one element per collider -- None (no body), (inv_mass, inv_inertia), (inv_mass, inv_inertia, ax, ay) or
+        (inv_mass, inv_inertia, ax, ay, drag, spin_drag) -- as an egg_collider_body array; shape, finiteness and signs are
+        checked here, before any call into the library"""
+        bodies = list(bodies)
+        arr = (_ffi.EggColliderBody * max(len(bodies), 1))()
+        names = ("inv_mass", "inv_inertia", "ax", "ay", "drag", "spin_drag")
+        for k, b in enumerate(bodies):
+            if b is None:
+                b = (0.0, 0.0)
+            try:
+                b = tuple(float(v) for v in b)
+            except (TypeError, ValueError):
+                raise EggError("collider body %d: expected None or (inv_mass, inv_inertia[, ax, ay[, drag, spin_drag]]), not %r" % (k, b)) from None
+            if len(b) not in (2, 4, 6):
+                raise EggError("collider body %d: expected None or (inv_mass, inv_inertia[, ax, ay[, drag, spin_drag]]), not %r" % (k, b))
+            b = b + (0.0,) * (6 - len(b))
+            for name, v in zip(names, b):
+                if not math.isfinite(v):
+                    raise EggError("collider body %d: %s %r is not finite" % (k, name, v))
+                if name not in ("ax", "ay") and v < 0.0:
+                    raise EggError("collider body %d: %s %r is negative" % (k, name, v))
+            for name, v in zip(names, b):
+                setattr(arr[k], name, v)
+        return len(bodies), arr
+
+    def set_collider_bodies(self, bodies):
+        """SimulationHandler.set_collider_bodies where several handles share a step (SimulationGroup,
+        ShardedSimulationHandler): a list without a body is accepted and changes nothing, anything else raises EggError naming
+        the limit (after the checks of the records)."""
+        n, arr = self._c_bodies(bodies)
+        if any(arr[k].inv_mass > 0.0 or arr[k].inv_inertia > 0.0 for k in range(n)):
+            raise EggError(self._BODIES_LIMIT)
+
+    def get_collider_bodies(self):
+        """one all-zero record per collider here, see set_collider_bodies"""
+        return [(0.0, 0.0, 0.0, 0.0, 0.0, 0.0)] * len(self.get_colliders())
+
     # ------------------------------------------------ force fields (egg_set_forces, DESIGN.md section 2.7)
     @staticmethod
     def _c_forces(forces):
@@ -928,6 +971,26 @@ class SimulationHandler(_HandlerSurface):
         if getattr(self, "_h", None):
             self._lib.egg_destroy(self._h)
             self._h = None
+
+    def set_collider_bodies(self, bodies):
+        """One body per collider of the current list ("Collider bodies"): `None` for a collider that
+        stays kinematic, or `(inv_mass, inv_inertia[, ax, ay[, drag, spin_drag]])`.  inv_mass > 0 frees the translation,
+        inv_inertia > 0 the rotation about the collider's spin pivot: a plate is `(1 / M, 0)`, a hinge `(0, 1 / I)`, a free
+        ball both.  ax, ay (px/s^2) act on a freed translation; drag and spin_drag are in 1/s.  In a relaxed step with
+        collider loads on, the device integrates every body from the loads it receives, once per sub-step, and a committed
+        step advances what get_colliders, get_collider_motion and get_collider_spin return.  A step with a body and loads
+        off raises EggError (set_collider_loads(True) first).  `[]` resets, and so does set_colliders; geometry, surfaces,
+        motions and spins stay.  Raises EggError (nothing changes) for a length that is not the collider count, a component
+        that is not finite or a negative inv_mass, inv_inertia, drag or spin_drag."""
+        n, arr = self._c_bodies(bodies)  # (refused here before any device call)
+        self._check(self._c("set_collider_bodies")(n, arr))
+
+    def get_collider_bodies(self):
+        """the bodies as stored, one `(inv_mass, inv_inertia, ax, ay, drag, spin_drag)` per collider (zeros included)"""
+        arr = (_ffi.EggColliderBody * _ffi.MAX_COLLIDERS)()
+        n = C.c_int32()
+        self._check(self._c("get_collider_bodies")(_ffi.MAX_COLLIDERS, arr, C.byref(n)))
+        return [(b.inv_mass, b.inv_inertia, b.ax, b.ay, b.drag, b.spin_drag) for b in arr[:n.value]]
 
     def set_coupling(self, factor=0.0, strength=1.0):
         """White-yolk coupling: one cross-type collision pass per sub-step of a relaxed step, before the sub-step's first

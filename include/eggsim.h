@@ -590,6 +590,49 @@ int egg_get_collider_loads_enabled(const egg_handle *h, int *on);
 int egg_get_collider_load_sums(egg_handle *h, int32_t cap, int64_t *sums /* [n][3] */, int64_t *dropped, double *sub_delta, int32_t *n);
 int egg_get_collider_loads(egg_handle *h, int32_t cap, egg_collider_load *out, int32_t *n);
 
+/* ---- collider bodies: colliders the device integrates from their own loads ("Collider bodies") ----
+ * Every collider of the list may carry a BODY {inv_mass, inv_inertia, ax, ay, drag, spin_drag}: inv_mass > 0 frees its
+ * translation, inv_inertia > 0 its rotation about its spin pivot; a collider with both zero is no body and stays kinematic.
+ * A hinge is (0, 1/I), a plate (1/M, 0), a free ball both.  ax, ay (px/s^2) act only when inv_mass > 0; drag and spin_drag are
+ * in 1/s.  Bodies ACT in a step when the order is relaxed, the list is not empty, some collider is a body and collider loads
+ * are on.  A relaxed step with a body, a list and loads off fails before anything is launched with EGG_ERR_UNSUPPORTED
+ * (egg_set_collider_loads first).  With no body a step launches exactly the kernels it launches today, with the same
+ * arguments.
+ * While bodies act every collider has a motion, a spin and a turn (c, s) on the device, zeros included, and every sub-step
+ * runs the rules of collider loads, motion and spin as the FIRST sub-step of a step over those records: the geometry at
+ * t = h, the start at ts = 0, the turn standing for both rows of the table.  After the last pass of a sub-step of both
+ * types (and after viscosity) one kernel does, for every collider k, FP64 in exactly this order, no contraction:
+ *   1. d = sums[k] - seen[k] (three int64), seen[k] = sums[k];
+ *      Jx = ((double)dx / 2^20) / h, Jy likewise, Jz = ((double)dz / 2^10) / h          the sub-step's impulse
+ *   2. the stored geometry and the stored pivot become the primed values of collider motion / collider spin at t = h, with
+ *      the velocity, omega and (c, s) the sub-step used (omega != 0: the spin expressions, and the pivot rides; otherwise the
+ *      motion expressions, and the pivot stays, as at a commit).  The kinematic colliders of the list advance too.
+ *   3. inv_mass > 0:     vx = vx + Jx * inv_mass; vx = vx + h * ax (y likewise);
+ *                        f = 1 - h * drag; if (!(f > 0)) f = 0; vx = vx * f; vy = vy * f
+ *   4. inv_inertia > 0:  omega = omega + Jz * inv_inertia; the same damping with spin_drag; then the next turn
+ *                        u = 0.5 * (h * omega); den = 1 + u * u; c = (1 - u * u) / den; s = (u + u) / den
+ * The turn of a free-turning body is this Cayley rotation, by 2 atan(h omega / 2) instead of h omega: only + - * / occur, so
+ * host, device and the numpy model agree to the bit.  A collider with inv_inertia == 0 keeps the host's libm
+ * (cos, sin)(h omega).  A list with bodies advances sub-step by sub-step, not by (sub + 1) h v from the step's start: equal
+ * to the step without bodies by roundings only, bit for bit at S = 1.  The commit reads the list, the motions and the spins
+ * back: egg_get_colliders, egg_get_collider_motion and egg_get_collider_spin return them; the loads cover the whole step.
+ * A failed step advances nothing.  The coupling is explicit: a body much lighter than what it touches may oscillate
+ * (DESIGN.md has the measured range).  No body-body contact, no exact-order rule.  ONE handle only: a device group refuses
+ * to step and egg_rx_begin returns EGG_ERR_UNSUPPORTED while a handle holds a body.
+ * egg_set_collider_bodies: n must equal the current collider count, or 0 (no collider is a body).  Everything is checked
+ * before anything changes: EGG_ERR_INVALID_ARGUMENT, with the collider's index in the message, for an n that does not match,
+ * a component that is not finite, or a negative inv_mass, inv_inertia, drag or spin_drag.  egg_set_colliders resets the
+ * bodies; egg_set_collider_motion, egg_set_collider_spin and egg_set_collider_surfaces leave them.  A -0.0 is stored as +0.0.
+ * Refused while a step is in flight. */
+typedef struct {
+    double inv_mass, inv_inertia; /* 1 / mass, 1 / (mass px^2); 0 = not freed */
+    double ax, ay;                /* px/s^2, with inv_mass > 0 only */
+    double drag, spin_drag;       /* 1/s */
+} egg_collider_body; /* 48 bytes */
+int egg_set_collider_bodies(egg_handle *h, int32_t n, const egg_collider_body *b);
+/* the bodies as stored, one per collider (zeros included): the count in *n, min(*n, cap) records copied */
+int egg_get_collider_bodies(const egg_handle *h, int32_t cap, egg_collider_body *b, int32_t *n);
+
 /* ---- force fields (not in the reference, which has no forces as it has no boundary; DESIGN.md section 2.7, "Forces") ----
  * A handle holds an ordered list of at most EGG_MAX_FORCES fields.  The values are accelerations in px/s^2 and do not depend
  * on mass.  In every sub-step of a RELAXED step, for every particle of a type, the force step runs before the pre-solve,
