@@ -125,6 +125,11 @@ class EggColliderBody(C.Structure):  # egg_collider_body: a collider the device 
                 ("drag", C.c_double), ("spin_drag", C.c_double)]
 
 
+class EggColliderStyle(C.Structure):  # egg_collider_style: how the headless renderer draws a collider (40 bytes)
+    _fields_ = [("fill", C.c_float * 4), ("line", C.c_float * 4), ("line_width", C.c_float), ("layer", C.c_int32)]
+
+
+COLLIDER_LAYERS = {"under": 0, "over": 1}  # egg_collider_style.layer
 COLLIDER_LOAD_IMPULSE_SCALE = 1048576.0  # EGG_COLLIDER_LOAD_IMPULSE_SCALE, 2^20
 COLLIDER_LOAD_TORQUE_SCALE = 1024.0      # EGG_COLLIDER_LOAD_TORQUE_SCALE, 2^10
 MAX_COLLIDERS = 64  # EGG_MAX_COLLIDERS
@@ -216,6 +221,12 @@ _SIGNATURES = {
     "egg_get_collider_spin": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggColliderSpin), C.POINTER(C.c_int32)]),
     "egg_group_set_collider_spin": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggColliderSpin)]),
     "egg_group_get_collider_spin": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggColliderSpin), C.POINTER(C.c_int32)]),
+    "egg_set_collider_styles": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggColliderStyle)]),
+    "egg_get_collider_styles": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggColliderStyle), C.POINTER(C.c_int32)]),
+    "egg_get_collider_pose": (C.c_int, [C.c_void_p, C.c_double, C.c_int32, C.POINTER(EggCollider), C.POINTER(C.c_int32)]),
+    "egg_group_set_collider_styles": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggColliderStyle)]),
+    "egg_group_get_collider_styles": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggColliderStyle), C.POINTER(C.c_int32)]),
+    "egg_group_get_collider_pose": (C.c_int, [C.c_void_p, C.c_double, C.c_int32, C.POINTER(EggCollider), C.POINTER(C.c_int32)]),
     "egg_set_collider_loads": (C.c_int, [C.c_void_p, C.c_int]),
     "egg_get_collider_loads_enabled": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "egg_get_collider_load_sums": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double),

@@ -256,6 +256,23 @@ struct EggCompositeArgs {
     int32_t use_particle_color, use_lighting;
     EggCompositeLayer layer[2];
 };
+// colliders in the picture (egg_set_collider_styles; DESIGN.md section 2.7, "Collider styles"): the visible colliders of ONE
+// layer at the pose of the frame, in list order -- the host leaves the others out, so a lane's index is a bit of the mask
+#define EGG_DRAW_MAX_COLLIDERS 64  // one wave's width: lane k culls collider k
+struct EggDrawCollider {  // 72 bytes
+    double p[4];       // the pose's parameters
+    int32_t kind;      // EGG_RX_COLLIDER_*
+    float line_width;  // px; 0: no line
+    float fill[4];     // fill[3] == 0: no fill (also where the kind has no inside)
+    float line[4];     // line[3] == 0: no line
+};
+struct EggColliderDrawArgs {
+    float4 *screen;
+    const EggDrawCollider *list;
+    int32_t count;     // 1 .. EGG_DRAW_MAX_COLLIDERS
+    int32_t screen_w, screen_h;
+    double origin_x, origin_y;
+};
 
 // the arguments of up to four launch classes sharing one launch (egg_step_kernel_multi*); unused slots have n_tiles = 0
 struct EggStepArgs4 {

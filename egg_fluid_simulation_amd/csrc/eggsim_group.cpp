@@ -67,6 +67,7 @@ struct egg_group {
     std::vector<egg_collider_surface> surfaces;  // egg_group_set_collider_surfaces: every handle's records, as given
     std::vector<egg_collider_motion> motions;    // egg_group_set_collider_motion: every handle's records, as given
     std::vector<egg_collider_spin> spins;        // egg_group_set_collider_spin: every handle's records, as given
+    std::vector<egg_collider_style> styles;      // egg_group_set_collider_styles: every handle's records, as given
     std::vector<egg_force> forces;          // egg_group_set_forces: every handle's list, as given
     double viscosity[2] = {0.0, 0.0};       // egg_group_set_viscosity: every handle's coefficients
     double containment[2] = {0.0, 1.0};     // egg_group_set_containment: every handle's (factor, strength)
@@ -664,12 +665,14 @@ int egg_group_set_colliders(egg_group *g, int32_t n, const egg_collider *c) {
                 (void)egg_set_collider_surfaces(g->h[j], (int32_t)g->surfaces.size(), g->surfaces.data());
                 (void)egg_set_collider_motion(g->h[j], (int32_t)g->motions.size(), g->motions.data());
                 (void)egg_set_collider_spin(g->h[j], (int32_t)g->spins.size(), g->spins.data());
+                (void)egg_set_collider_styles(g->h[j], (int32_t)g->styles.size(), g->styles.data());
             }
             return gfail(g, rc, "device %d: %s", (int)k, egg_last_error(g->h[k]));
         }
     }
     g->colliders.assign(c, c + (n > 0 ? n : 0));
     g->surfaces.clear();  // (every handle has reset its own)
+    g->styles.clear();
     g->motions.clear();
     g->spins.clear();
     return EGG_OK;
@@ -731,6 +734,30 @@ int egg_group_set_collider_spin(egg_group *g, int32_t n, const egg_collider_spin
 int egg_group_get_collider_spin(const egg_group *g, int32_t cap, egg_collider_spin *s, int32_t *n) {
     if (!g || g->h.empty()) return EGG_ERR_INVALID_ARGUMENT;
     return egg_get_collider_spin(g->h[0], cap, s, n);  // (as stored: every handle holds the same records)
+}
+
+int egg_group_set_collider_styles(egg_group *g, int32_t n, const egg_collider_style *s) {
+    if (!g) return EGG_ERR_INVALID_ARGUMENT;
+    for (size_t k = 0; k < g->h.size(); ++k) {
+        const int rc = egg_set_collider_styles(g->h[k], n, s);
+        if (rc < 0) {  // (handle 0 refuses bad records before any handle has changed; a later one: the others go back)
+            for (size_t j = 0; j < k; ++j) (void)egg_set_collider_styles(g->h[j], (int32_t)g->styles.size(), g->styles.data());
+            return gfail(g, rc, "device %d: %s", (int)k, egg_last_error(g->h[k]));
+        }
+    }
+    g->styles.assign(s, s + (n > 0 ? n : 0));
+    return EGG_OK;
+}
+
+int egg_group_get_collider_styles(const egg_group *g, int32_t cap, egg_collider_style *s, int32_t *n) {
+    if (!g || g->h.empty()) return EGG_ERR_INVALID_ARGUMENT;
+    return egg_get_collider_styles(g->h[0], cap, s, n);  // (as stored: every handle holds the same records)
+}
+
+int egg_group_get_collider_pose(egg_group *g, double alpha, int32_t cap, egg_collider *c, int32_t *n) {
+    if (!g || g->h.empty()) return EGG_ERR_INVALID_ARGUMENT;
+    // (every handle holds and advances the same two lists; the group's alpha, not handle 0's, is what its draw uses)
+    return egg_get_collider_pose(g->h[0], alpha != alpha ? g->alpha : alpha, cap, c, n);
 }
 
 int egg_group_set_collider_loads(egg_group *g, int on) {

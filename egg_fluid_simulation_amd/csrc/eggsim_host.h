@@ -138,6 +138,7 @@ extern "C" __global__ void egg_render_scan_kernel(EggRenderArgs A);
 extern "C" __global__ void egg_render_splat_kernel(EggRenderArgs A);
 extern "C" __global__ void egg_render_composite_kernel(EggCompositeArgs A);
 extern "C" __global__ void egg_render_clear_kernel(float4 *, size_t, float4);
+extern "C" __global__ void egg_render_colliders_kernel(EggColliderDrawArgs A);
 extern "C" __global__ void egg_atom_bounds_kernel(const double *, const double *, const int32_t *, const int32_t *,
                                                    int, double, int32_t *);
 extern "C" __global__ void egg_rederive_kernel(const double *, double *, double *, int, int, double, double, int,
@@ -457,6 +458,11 @@ struct egg_handle {
     bool colliders_wall = false;  // the list holds an EGG_COLLIDER_WALL: a step launches the wall instantiations, which
                                   // read the surface records -- d_surfaces then holds one per collider, defaults included
     int64_t collider_hits[2] = {0, 0};
+    // colliders in the picture (egg_get_collider_pose, egg_set_collider_styles): the list at the start of the last committed
+    // relaxed step -- relaxed_commit copies `colliders` into it before it advances them, egg_set_colliders sets both -- and
+    // the styles, empty = nothing is drawn, else one record per collider.  Host only: a draw uploads the pose it draws.
+    std::vector<egg_collider> colliders_last;
+    std::vector<egg_collider_style> styles;
     // collider surfaces (egg_set_collider_surfaces): empty = every surface is the default, else one record per collider;
     // the copy on the device (written when they are set, never per step); whether any friction > 0 -- only then does a
     // step launch the surface instantiations -- and the grips of committed steps per type
@@ -563,6 +569,7 @@ struct egg_handle {
         int tsize = 0;
         double texture_radius = -1;
         DevBuf<uint32_t> tiles, entries, totals;
+        DevBuf<EggDrawCollider> colliders;  // the visible colliders of the frame: layer 0's at 0, layer 1's at EGG_DRAW_MAX_COLLIDERS
     } render;
 };
 namespace egghost {
@@ -613,8 +620,17 @@ struct RenderSource {
         hipStream_t env_stream = nullptr;      // stream and scratch (16 words) of the environment reductions
         DevBuf<unsigned long long> *d_env = nullptr;
     } t[2];
+    // colliders in the picture (collider_source_of): the two lists the frame's pose is mixed from and the styles; count 0
+    // or no styles: nothing of this is drawn and nothing is launched for it
+    const egg_collider *colliders = nullptr, *colliders_last = nullptr;
+    const egg_collider_style *styles = nullptr;
+    int32_t n_colliders = 0;
 };
 int render_source_of(egg_handle *h, RenderSource &S);  // eggsim_host_render.hip
+// the colliders h holds as the frame's: a handle's own, handle 0's for a group, the render rank's for a sharded scene
+void collider_source_of(const egg_handle *h, RenderSource &S);
+// the pose of egg_get_collider_pose: p = last.p * (1.0 - t) + cur.p * t, kind and mask from cur
+void collider_pose(const egg_collider *last, const egg_collider *cur, int32_t n, double t, egg_collider *out);
 int render_from(RenderSource &S, const egg_render_params *p, float *rgba, const char *name);
 int render_canvas_from(egg_handle *h, egg_handle::Render &R, const char *name, int which, float *rgba, int64_t cap_pixels, int32_t *w,
                        int32_t *hgt, double *x0, double *y0);

@@ -1047,6 +1047,8 @@ int egg_set_colliders(egg_handle *h, int32_t n, const egg_collider *c) {
         HIP_TRY(h, hipMemcpy(h->d_colliders.p, list.data(), (size_t)n * sizeof(egg_collider), hipMemcpyHostToDevice));
     }
     h->colliders.swap(list);
+    h->colliders_last = h->colliders;  // (a teleport is not interpolated: the pose is the new list at every alpha)
+    h->styles.clear();                 // (and nothing is drawn)
     h->colliders_wall = wall;
     h->surfaces.clear();  // (the indices no longer mean anything: every surface is the default again)
     h->surfaces_grip = false;
@@ -1067,6 +1069,65 @@ int egg_get_colliders(const egg_handle *h, int32_t cap, egg_collider *c, int32_t
     const int32_t have = (int32_t)h->colliders.size();
     if (n) *n = have;
     if (c && cap > 0) memcpy(c, h->colliders.data(), (size_t)std::min(cap, have) * sizeof(egg_collider));
+    return EGG_OK;
+}
+
+// Collider styles ("Collider styles"): one record per collider, or none (nothing is drawn).  Host
+// state only: a draw uploads what it draws.  Everything is checked before anything changes.
+int egg_set_collider_styles(egg_handle *h, int32_t n, const egg_collider_style *st) {
+    if (!h) return EGG_ERR_INVALID_ARGUMENT;
+    REJECT_IN_FLIGHT(h, "egg_set_collider_styles");
+    static_assert(sizeof(egg_collider_style) == 40, "a style record is 40 bytes");
+    static_assert(EGG_MAX_COLLIDERS == EGG_DRAW_MAX_COLLIDERS, "one lane of a wave per collider");
+    if (n != 0 && n != (int32_t)h->colliders.size())
+        return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_collider_styles: n = %d, the list holds %d colliders (n is that, or 0)", (int)n,
+                    (int)h->colliders.size());
+    if (n > 0 && !st) return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_collider_styles: n = %d without records", (int)n);
+    std::vector<egg_collider_style> list((size_t)n);
+    for (int32_t k = 0; k < n; ++k) {
+        egg_collider_style &o = list[(size_t)k];
+        o = st[k];
+        for (int q = 0; q < 4; ++q) {
+            if (!(o.fill[q] >= 0.0f && o.fill[q] <= 1.0f))  // (false for a NaN)
+                return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_collider_styles: collider %d: fill component %d is %g, not in [0, 1]", (int)k, q,
+                            (double)o.fill[q]);
+            if (!(o.line[q] >= 0.0f && o.line[q] <= 1.0f))
+                return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_collider_styles: collider %d: line component %d is %g, not in [0, 1]", (int)k, q,
+                            (double)o.line[q]);
+            o.fill[q] = o.fill[q] + 0.0f;  // (-0.0 is stored as +0.0: handles set alike compare alike)
+            o.line[q] = o.line[q] + 0.0f;
+        }
+        if (!(o.line_width >= 0.0f && o.line_width <= 64.0f))
+            return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_collider_styles: collider %d: line width %g is not in [0, 64]", (int)k,
+                        (double)o.line_width);
+        o.line_width = o.line_width + 0.0f;
+        if (o.layer != 0 && o.layer != 1)
+            return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_collider_styles: collider %d: layer %d (0 under the eggs, 1 over them)", (int)k,
+                        (int)o.layer);
+    }
+    h->styles.swap(list);
+    return EGG_OK;
+}
+
+int egg_get_collider_styles(const egg_handle *h, int32_t cap, egg_collider_style *st, int32_t *n) {
+    if (!h) return EGG_ERR_INVALID_ARGUMENT;
+    const int32_t have = (int32_t)h->colliders.size();
+    if (n) *n = have;
+    for (int32_t k = 0; st && k < std::min(cap, have); ++k)
+        st[k] = h->styles.empty() ? egg_collider_style{{0, 0, 0, 0}, {0, 0, 0, 0}, 0, 0} : h->styles[(size_t)k];
+    return EGG_OK;
+}
+
+// The pose a frame draws: the list at the start of the last committed step mixed with the current one.
+int egg_get_collider_pose(egg_handle *h, double alpha, int32_t cap, egg_collider *c, int32_t *n) {
+    if (!h) return EGG_ERR_INVALID_ARGUMENT;
+    const int32_t have = (int32_t)h->colliders.size();
+    if (n) *n = have;
+    if (!c || cap <= 0 || have == 0) return EGG_OK;
+    const double t = std::isnan(alpha) ? h->interpolation_alpha : clampd(alpha, 0, 1);
+    std::vector<egg_collider> pose((size_t)have);
+    collider_pose(h->colliders_last.data(), h->colliders.data(), have, t, pose.data());
+    memcpy(c, pose.data(), (size_t)std::min(cap, have) * sizeof(egg_collider));
     return EGG_OK;
 }
 

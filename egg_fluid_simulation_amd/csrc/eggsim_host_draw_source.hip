@@ -193,6 +193,7 @@ int egg_draw_source_render(egg_handle *h, const egg_render_params *p, const egg_
     S.alpha = interpolation_alpha;
     S.max_radius = std::max(h->sys[0].cfg.max_radius, h->sys[1].cfg.max_radius);
     S.stream = h->sys[0].stream;
+    collider_source_of(h, S);  // (the render rank's own list: every rank holds and advances the same one)
     for (int w = 0; w < 2; ++w) {
         const int rc = need_complete(h, D.t[w], w, "egg_draw_source_render");
         if (rc != EGG_OK) return rc;

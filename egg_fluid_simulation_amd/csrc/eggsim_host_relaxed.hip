@@ -1057,6 +1057,9 @@ void relaxed_commit(egg_handle *h, const RelaxedStep st[2], int S, int C, double
         s.out_copied = false;
     }
     if (h->opt_loads && !h->colliders.empty()) take_loads(h, st[0].env.sub_delta);
+    // the list at the start of this step, for the pose a frame draws (egg_get_collider_pose): taken before either of the two
+    // ways a commit advances the list, whether or not anything moves -- what last_x / last_y are for the particles
+    h->colliders_last = h->colliders;
     if (h->bodies_step) take_bodies(h);
     if ((h->motions_move || h->spins_turn) && !h->colliders.empty()) advance_colliders(h, (double)S * st[0].env.sub_delta, S);
     h->stats.last_step_kernel_ms = ms;

@@ -189,11 +189,77 @@ int render_splat(RenderSource &S, int which, const egg_environment &env, double 
     return EGG_OK;
 }
 
+// Colliders in the picture: the visible colliders of both layers at the pose of t go to the device, layer 0's from
+// entry 0 and layer 1's from entry EGG_DRAW_MAX_COLLIDERS, each in list order; count[] says how many.  Nothing is
+// copied (and nothing will be launched) when no collider of the frame is visible.
+int upload_colliders(RenderSource &S, double t, int32_t count[2]) {
+    egg_handle *h = S.h;
+    count[0] = count[1] = 0;
+    if (!S.styles || S.n_colliders <= 0) return EGG_OK;
+    static_assert(sizeof(EggDrawCollider) == 72, "a drawn collider is 72 bytes");
+    std::vector<egg_collider> pose((size_t)S.n_colliders);
+    collider_pose(S.colliders_last, S.colliders, S.n_colliders, t, pose.data());
+    std::vector<EggDrawCollider> list(2 * EGG_DRAW_MAX_COLLIDERS);
+    for (int32_t k = 0; k < S.n_colliders; ++k) {
+        const egg_collider_style &s = S.styles[k];
+        const egg_collider &c = pose[(size_t)k];
+        const bool inside = c.kind != EGG_COLLIDER_SEGMENT && c.kind != EGG_COLLIDER_WALL;
+        const bool fills = inside && s.fill[3] > 0.0f, lines = s.line[3] > 0.0f && s.line_width > 0.0f;
+        if (!fills && !lines) continue;
+        EggDrawCollider &d = list[(size_t)s.layer * EGG_DRAW_MAX_COLLIDERS + (size_t)count[s.layer]++];
+        memcpy(d.p, c.p, sizeof d.p);
+        d.kind = c.kind;
+        d.line_width = lines ? s.line_width : 0.0f;
+        for (int q = 0; q < 4; ++q) {
+            d.fill[q] = fills ? s.fill[q] : 0.0f;
+            d.line[q] = lines ? s.line[q] : 0.0f;
+        }
+    }
+    if (count[0] + count[1] == 0) return EGG_OK;
+    HIP_TRY(h, S.R->colliders.reserve(list.size(), false, S.stream));
+    HIP_TRY(h, hipMemcpyAsync(S.R->colliders.p, list.data(), list.size() * sizeof(EggDrawCollider), hipMemcpyHostToDevice, S.stream));
+    HIP_TRY(h, hipStreamSynchronize(S.stream));  // (the list is pageable)
+    return EGG_OK;
+}
+
+int render_colliders(RenderSource &S, const egg_render_params *p, int layer, int32_t count) {
+    egg_handle *h = S.h;
+    EggColliderDrawArgs A;
+    memset(&A, 0, sizeof A);
+    A.screen = S.R->screen.p;
+    A.list = S.R->colliders.p + (size_t)layer * EGG_DRAW_MAX_COLLIDERS;
+    A.count = count;
+    A.screen_w = p->screen_w;
+    A.screen_h = p->screen_h;
+    A.origin_x = p->origin_x;
+    A.origin_y = p->origin_y;
+    hipLaunchKernelGGL(egg_render_colliders_kernel,
+                       dim3((unsigned)((p->screen_w + EGG_RENDER_TILE - 1) / EGG_RENDER_TILE), (unsigned)((p->screen_h + EGG_RENDER_TILE - 1) / EGG_RENDER_TILE)),
+                       dim3(256), 0, S.stream, A);
+    HIP_TRY(h, hipGetLastError());
+    h->stats.kernel_launches++;
+    return EGG_OK;
+}
+
 }  // namespace
 
 }  // extern "C"
 
 namespace egghost {
+
+void collider_source_of(const egg_handle *h, RenderSource &S) {
+    S.n_colliders = (int32_t)h->colliders.size();
+    S.colliders = h->colliders.data();
+    S.colliders_last = h->colliders_last.data();
+    S.styles = h->styles.empty() ? nullptr : h->styles.data();
+}
+
+void collider_pose(const egg_collider *last, const egg_collider *cur, int32_t n, double t, egg_collider *out) {
+    for (int32_t k = 0; k < n; ++k) {
+        out[k] = cur[k];  // (kind and mask)
+        for (int q = 0; q < 4; ++q) out[k].p[q] = last[k].p[q] * (1.0 - t) + cur[k].p[q] * t;
+    }
+}
 
 // A handle's own arrays as the renderer's source.
 int render_source_of(egg_handle *h, RenderSource &S) {
@@ -207,6 +273,7 @@ int render_source_of(egg_handle *h, RenderSource &S) {
     S.max_radius = std::max(h->sys[0].cfg.max_radius, h->sys[1].cfg.max_radius);
     S.stream = h->sys[0].stream;
     S.also_wait = h->sys[1].stream;
+    collider_source_of(h, S);
     for (int w = 0; w < 2; ++w) {
         System &s = h->sys[w];
         const int rc = upload_atoms(h, w);
@@ -250,12 +317,17 @@ int render_from(RenderSource &S, const egg_render_params *p, float *rgba, const 
                        make_float4(p->clear[0], p->clear[1], p->clear[2], p->clear[3]));
     HIP_TRY(h, hipGetLastError());
     h->stats.kernel_launches++;
+    const double t = std::isnan(p->interpolation_alpha) ? S.alpha : clampd(p->interpolation_alpha, 0, 1);
+    // colliders in the picture: drawn whether or not the eggs are (the boundary is there before the first step)
+    int32_t n_drawn[2];
+    int rc = upload_colliders(S, t, n_drawn);
+    if (rc != EGG_OK) return rc;
+    if (n_drawn[0] > 0 && (rc = render_colliders(S, p, 0, n_drawn[0])) != EGG_OK) return rc;  // under the eggs
     // the canvases exist from the first _step on and only while both types have particles (L:1936-1938, L:1997-1999, L:2118)
     const bool drawable = S.stepped && S.t[0].n > 0 && S.t[1].n > 0;
     R.canvas_valid = false;
     if (drawable) {
-        const double t = std::isnan(p->interpolation_alpha) ? S.alpha : clampd(p->interpolation_alpha, 0, 1);
-        int rc = render_texture(h, R, S.max_radius, st);
+        rc = render_texture(h, R, S.max_radius, st);
         if (rc != EGG_OK) return rc;
         egg_environment env[2];
         EggCompositeArgs C;
@@ -310,6 +382,7 @@ int render_from(RenderSource &S, const egg_render_params *p, float *rgba, const 
         R.last_w[1] = C.layer[1].w;
         R.last_h[1] = C.layer[1].h;
     }
+    if (n_drawn[1] > 0 && (rc = render_colliders(S, p, 1, n_drawn[1])) != EGG_OK) return rc;  // over the eggs
     if (rgba) HIP_TRY(h, hipMemcpyAsync(rgba, R.screen.p, npx * 16, hipMemcpyDeviceToHost, st));
     HIP_TRY(h, hipStreamSynchronize(st));
     return EGG_OK;

@@ -255,6 +255,7 @@ int group_draw_render(GroupDraw *D, const GroupView &V, const egg_render_params 
     S.alpha = V.alpha;
     S.max_radius = std::max(rh->sys[0].cfg.max_radius, rh->sys[1].cfg.max_radius);
     S.stream = rh->sys[0].stream;
+    collider_source_of(rh, S);  // (every handle of the group holds and advances the same list)
     for (int w = 0; w < 2; ++w) {
         const int rc = gather(D, V, w, kDrawFields, EGG_GATHER_FIELDS, "egg_group_render", error);
         if (rc != EGG_OK) return rc;

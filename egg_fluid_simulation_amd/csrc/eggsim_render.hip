@@ -15,6 +15,10 @@
 // in-order rasteriser produces, independent of scheduling, and no pixel is ever written twice.  The 38 x 38 texture sits
 // in LDS with a zero border ("clampzero" wrap without a branch).  Everything is IEEE float32 without contraction; the
 // CPU model in oracle/render_model.py computes the same expressions in the same order.
+//
+// Not in the reference: colliders in the picture (egg_set_collider_styles; DESIGN.md section 2.7, "Collider styles").
+// egg_render_colliders_kernel draws the visible colliders of one layer onto the screen, after the clear (under the eggs) or
+// after pass 2 (over them); its distances are FP64, its blend pass 2's; tests/collider_draw_model.py is its model.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -307,6 +311,84 @@ extern "C" __global__ void __launch_bounds__(256) egg_render_composite_kernel(Eg
         out = blend_alpha(out, f4(center.x - shadow + specular, center.y - shadow + specular, center.z - shadow + specular, center.w));
     }
     A.screen[(size_t)sy_i * A.screen_w + sx_i] = out;
+}
+
+namespace {
+
+// signed distance of the world point (wx, wy) from a collider at the frame's pose (include/eggsim.h, "collider styles"):
+// negative on the solid side; a segment or wall has none.  FP64 in exactly this order; tests/collider_draw_model.py
+// computes the same expressions.
+__device__ __forceinline__ double collider_sd(const EggDrawCollider &c, double wx, double wy) {
+    if (c.kind == EGG_RX_COLLIDER_HALF_PLANE) return (c.p[0] * wx + c.p[1] * wy) - c.p[2];
+    if (c.kind == EGG_RX_COLLIDER_SEGMENT || c.kind == EGG_RX_COLLIDER_WALL) {
+        const double ex = c.p[2] - c.p[0], ey = c.p[3] - c.p[1];
+        const double l2 = ex * ex + ey * ey;
+        double t = l2 == 0.0 ? 0.0 : ((wx - c.p[0]) * ex + (wy - c.p[1]) * ey) / l2;
+        if (t < 0.0) t = 0.0;
+        if (t > 1.0) t = 1.0;
+        const double qx = c.p[0] + t * ex, qy = c.p[1] + t * ey;
+        const double ddx = wx - qx, ddy = wy - qy;
+        return sqrt(ddx * ddx + ddy * ddy);
+    }
+    const double dx = wx - c.p[0], dy = wy - c.p[1];
+    const double d = sqrt(dx * dx + dy * dy);
+    return c.kind == EGG_RX_COLLIDER_DISC ? d - c.p[2] : c.p[2] - d;
+}
+
+}  // namespace
+
+// The visible colliders of one layer over the screen: one workgroup per 16 x 16 px tile, one thread per pixel, as the
+// composite.  A collider whose coverage at a pixel is zero does not touch the pixel, so leaving out the colliders that
+// cannot reach a tile changes no bit: in every wave lane k takes collider k's distance at the tile's centre, and the
+// ballot is the wave-uniform mask of the colliders the pixel loop walks, in ascending (= list) order, their records read
+// at a uniform index.  sd is 1-Lipschitz in the point (a half-plane's by the length of its unnormalised normal, bounded
+// per axis below), so |sd(pixel) - sd(centre)| <= the tile's half-diagonal; `slack` pays for the rounding of both
+// evaluations, scaled with the magnitudes that enter them.  Every comparison is written so that a NaN keeps the collider.
+extern "C" __global__ void __launch_bounds__(256) egg_render_colliders_kernel(EggColliderDrawArgs A) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    bool reach = false;
+    if (lane < A.count) {  // (no lane leaves before the ballot: the pixels beyond the screen's edge cull too)
+        const EggDrawCollider c = A.list[lane];
+        const double half = 0.5 * (double)(EGG_RENDER_TILE - 1);  // pixel centres lie within 7.5 px of the tile's, per axis
+        const double ccx = ((double)(blockIdx.x * EGG_RENDER_TILE) + 0.5 * (double)EGG_RENDER_TILE) + A.origin_x;
+        const double ccy = ((double)(blockIdx.y * EGG_RENDER_TILE) + 0.5 * (double)EGG_RENDER_TILE) + A.origin_y;
+        const double sd = collider_sd(c, ccx, ccy);
+        const double mag = (fabs(ccx) + fabs(ccy)) + ((fabs(c.p[0]) + fabs(c.p[1])) + (fabs(c.p[2]) + fabs(c.p[3])));
+        const double slack = 1.0 + mag * 0x1p-40;
+        const double spread = (c.kind == EGG_RX_COLLIDER_HALF_PLANE ? (fabs(c.p[0]) + fabs(c.p[1])) * half : 1.4142135623730951 * half) + slack;
+        const bool fills = c.fill[3] > 0.0f;                         // cf > 0 needs sd < 0.5
+        const bool lines = c.line[3] > 0.0f && c.line_width > 0.0f;  // cl > 0 needs |sd| < 0.5 + line_width / 2
+        reach = (fills && !(sd - spread >= 0.5)) || (lines && !(fabs(sd) - spread >= 0.5 + 0.5 * (double)c.line_width));
+    }
+    unsigned long long mask = __ballot(reach);
+    if (mask == 0ull) return;  // (wave-uniform)
+    const int sx_i = blockIdx.x * EGG_RENDER_TILE + (tid & (EGG_RENDER_TILE - 1)), sy_i = blockIdx.y * EGG_RENDER_TILE + tid / EGG_RENDER_TILE;
+    if (sx_i >= A.screen_w || sy_i >= A.screen_h) return;
+    const double wx = ((double)sx_i + 0.5) + A.origin_x, wy = ((double)sy_i + 0.5) + A.origin_y;
+    float4 *px = A.screen + ((size_t)sy_i * A.screen_w + sx_i);
+    float4 out = *px;
+    bool touched = false;
+    while (mask) {
+        const int k = __ffsll(mask) - 1;
+        mask &= mask - 1ull;
+        const EggDrawCollider &c = A.list[k];
+        const double sd = collider_sd(c, wx, wy);
+        if (c.fill[3] > 0.0f) {
+            const float cf = (float)fmin(fmax(0.5 - sd, 0.0), 1.0);
+            if (cf > 0.0f) {
+                out = blend_alpha(out, f4(c.fill[0], c.fill[1], c.fill[2], c.fill[3] * cf));
+                touched = true;
+            }
+        }
+        if (c.line_width > 0.0f && c.line[3] > 0.0f) {
+            const float cl = (float)fmin(fmax((0.5 + 0.5 * (double)c.line_width) - fabs(sd), 0.0), 1.0);
+            if (cl > 0.0f) {
+                out = blend_alpha(out, f4(c.line[0], c.line[1], c.line[2], c.line[3] * cl));
+                touched = true;
+            }
+        }
+    }
+    if (touched) *px = out;
 }
 
 extern "C" __global__ void __launch_bounds__(256) egg_render_clear_kernel(float4 *dst, size_t n, float4 value) {

@@ -108,6 +108,10 @@ int egg_get_collider_loads(egg_handle *h, int32_t cap, egg_collider_load *out, i
 typedef struct { double inv_mass, inv_inertia, ax, ay, drag, spin_drag; } egg_collider_body;
 int egg_set_collider_bodies(egg_handle *h, int32_t n, const egg_collider_body *b);
 int egg_get_collider_bodies(const egg_handle *h, int32_t cap, egg_collider_body *b, int32_t *n);
+typedef struct { float fill[4]; float line[4]; float line_width; int32_t layer; } egg_collider_style;
+int egg_set_collider_styles(egg_handle *h, int32_t n, const egg_collider_style *s);
+int egg_get_collider_styles(const egg_handle *h, int32_t cap, egg_collider_style *s, int32_t *n);
+int egg_get_collider_pose(egg_handle *h, double alpha, int32_t cap, egg_collider *c, int32_t *n);
 typedef struct egg_group egg_group;
 int egg_group_set_solver_order(egg_group *g, int32_t order, double relaxation);
 int egg_group_set_cohesion(egg_group *g, int32_t mode);
@@ -618,6 +622,67 @@ function SimulationHandler:get_collider_bodies()
     local out = {}
     for k = 0, n[0] - 1 do
         out[k + 1] = { arr[k].inv_mass, arr[k].inv_inertia, arr[k].ax, arr[k].ay, arr[k].drag, arr[k].spin_drag }
+    end
+    return out
+end
+
+-- Not in the reference, which has no colliders and draws none: collider styles and the pose a frame draws
+-- (egg_set_collider_styles, egg_get_collider_pose in include/eggsim.h; DESIGN.md section 2.7, "Collider styles").
+
+local _collider_layers = { under = 0, over = 1 }
+local _collider_layer_names = { [0] = "under", "over" }
+
+--- one style per collider of the current list for the headless renderer: `false` for a collider that is not drawn or
+--- `{ fill = { r, g, b, a }, line = { r, g, b, a }, line_width = px, layer = "under" | "over" }`, missing keys meaning no
+--- fill, no line, "under".  `{}` draws nothing, and so does set_colliders.  (A LOVE host draws the colliders itself, at
+--- get_collider_pose: these styles only reach egg_render.)
+function SimulationHandler:set_collider_styles(styles)
+    local n = #styles
+    local arr = ffi.new("egg_collider_style[?]", math.max(n, 1))
+    for k = 1, n do  -- (not ipairs: a nil hole must not end the walk short of n)
+        local s = styles[k]
+        if s == false then s = {} end
+        local layer = type(s) == "table" and _collider_layers[s.layer or "under"]
+        if type(s) ~= "table" or layer == nil or (s.fill and #s.fill ~= 4) or (s.line and #s.line ~= 4) then
+            log.error("In SimulationHandler.set_collider_styles: style " .. k ..
+                ": expected false or { fill = rgba, line = rgba, line_width = px, layer = \"under\" | \"over\" }")
+            return
+        end
+        local o = arr[k - 1]
+        for q = 1, 4 do
+            o.fill[q - 1] = s.fill and s.fill[q] or 0
+            o.line[q - 1] = s.line and s.line[q] or 0
+        end
+        o.line_width, o.layer = s.line_width or 0, layer
+    end
+    self:_check(lib.egg_set_collider_styles(self._h, n, arr))
+end
+
+--- the styles as stored, one table per collider in the shape set_collider_styles takes (an undrawn one: all zero)
+function SimulationHandler:get_collider_styles()
+    local arr, n = ffi.new("egg_collider_style[?]", _max_colliders), ffi.new("int32_t[1]")
+    if self:_check(lib.egg_get_collider_styles(self._h, _max_colliders, arr, n)) ~= 0 then return {} end
+    local out = {}
+    for k = 0, n[0] - 1 do
+        local s = arr[k]
+        out[k + 1] = { fill = { s.fill[0], s.fill[1], s.fill[2], s.fill[3] }, line = { s.line[0], s.line[1], s.line[2], s.line[3] },
+                       line_width = s.line_width, layer = _collider_layer_names[s.layer] }
+    end
+    return out
+end
+
+--- the list a frame draws the colliders at, in the shapes set_colliders takes: every parameter is
+--- `last * (1 - t) + current * t`, `last` the list at the start of the last committed step, t = `alpha` clamped to [0, 1]
+--- or, without one, the handler's interpolation alpha -- the rule :draw() places the particles by.  Call it once per
+--- frame and draw with love.graphics (INTEGRATION.md shows how).
+function SimulationHandler:get_collider_pose(alpha)
+    local arr, n = ffi.new("egg_collider[64]"), ffi.new("int32_t[1]")
+    if self:_check(lib.egg_get_collider_pose(self._h, alpha or (0 / 0), 64, arr, n)) ~= 0 then return {} end
+    local out = {}
+    for k = 0, n[0] - 1 do
+        local c = { _collider_names[arr[k].kind], types = _collider_type_names[arr[k].type_mask] }
+        for q = 1, _collider_n_params[arr[k].kind] do c[q + 1] = arr[k].p[q - 1] end
+        out[k + 1] = c
     end
     return out
 end

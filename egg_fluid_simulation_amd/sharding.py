@@ -651,6 +651,19 @@ class ShardedSimulationHandler(_HandlerSurface):
     def get_collider_spin(self):
         return self.local.get_collider_spin()
 
+    def set_collider_styles(self, styles):
+        """SimulationHandler.set_collider_styles on every rank alike (the same call on every rank).  Nothing new travels:
+        the render rank draws its own copy of the list, which every rank holds and advances by the same arithmetic."""
+        self.local.set_collider_styles(styles)
+
+    def get_collider_styles(self):
+        return self.local.get_collider_styles()
+
+    def get_collider_pose(self, alpha=None):
+        """SimulationHandler.get_collider_pose on this rank's copy of the list (no communication: every rank holds the
+        same two lists); `alpha` None takes this object's interpolation_alpha, as draw() does."""
+        return self.local.get_collider_pose(self._alpha if alpha is None else alpha)
+
     def set_collider_loads(self, on):
         """SimulationHandler.set_collider_loads on every rank alike (the same call on every rank).  Nothing new travels:
         every rank projects only the particles it owns, so only they contribute to its sums."""

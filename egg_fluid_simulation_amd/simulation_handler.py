@@ -290,6 +290,82 @@ class _HandlerSurface:
         self._check(self._c("get_collider_spin")(_ffi.MAX_COLLIDERS, arr, C.byref(n)))
         return [(sp.px, sp.py, sp.omega) for sp in arr[:n.value]]
 
+    # ------------------------------------------------ collider styles and pose (egg_set_collider_styles)
+    _STYLE_DEFAULTS = {"fill": (0.0, 0.0, 0.0, 0.0), "line": (0.0, 0.0, 0.0, 0.0), "line_width": 0.0, "layer": "under"}
+
+    @staticmethod
+    def _c_styles(styles):
+        """a list with one element per collider -- None (undrawn) or a dict {"fill": rgba, "line": rgba, "line_width": w,
+        "layer": "under" | "over"}, missing keys taking the defaults (no fill, no line, under) -- as an egg_collider_style
+        array; shape, names and ranges are checked here, before any call into the library"""
+        styles = list(styles)
+        arr = (_ffi.EggColliderStyle * max(len(styles), 1))()
+        for k, st in enumerate(styles):
+            if st is None:
+                continue  # (all zero: undrawn)
+            if not isinstance(st, dict) or set(st) - set(_HandlerSurface._STYLE_DEFAULTS):
+                raise EggError("collider style %d: expected None or a dict with the keys fill, line, line_width, layer, not %r" % (k, st))
+            st = dict(_HandlerSurface._STYLE_DEFAULTS, **st)
+            for name in ("fill", "line"):
+                try:
+                    rgba = tuple(float(v) for v in st[name])
+                except (TypeError, ValueError):
+                    raise EggError("collider style %d: %s must be (r, g, b, a), not %r" % (k, name, st[name])) from None
+                if len(rgba) != 4 or not all(0.0 <= v <= 1.0 for v in rgba):  # (false for a NaN)
+                    raise EggError("collider style %d: %s must be (r, g, b, a) with every component in [0, 1], not %r" % (k, name, st[name]))
+                getattr(arr[k], name)[:] = rgba
+            try:
+                width = float(st["line_width"])
+            except (TypeError, ValueError):
+                raise EggError("collider style %d: line_width must be a number, not %r" % (k, st["line_width"])) from None
+            if not 0.0 <= width <= 64.0:
+                raise EggError("collider style %d: line_width %r is not in [0, 64]" % (k, st["line_width"]))
+            if not isinstance(st["layer"], str) or st["layer"] not in _ffi.COLLIDER_LAYERS:
+                raise EggError("collider style %d: layer must be 'under' or 'over', not %r" % (k, st["layer"]))
+            arr[k].line_width, arr[k].layer = width, _ffi.COLLIDER_LAYERS[st["layer"]]
+        return len(styles), arr
+
+    def set_collider_styles(self, styles):
+        """One style per collider of the current list ("Collider styles"): `None` for a collider
+        draw() leaves out, or a dict `{"fill": rgba, "line": rgba, "line_width": px, "layer": "under" | "over"}` with
+        defaults for missing keys (no fill, no line, "under").  `fill` colours the solid side (a segment or wall has none),
+        `line` the outline or the segment itself, `line_width` pixels wide (0 .. 64); "under" draws after the clear and
+        before the eggs, "over" after them.  draw() places every collider at the pose get_collider_pose returns for the
+        frame's interpolation alpha.  `[]` draws nothing, and so does set_colliders; with nothing visible draw() launches
+        what it launches without styles.  Raises EggError (nothing changes) for a length that is not the collider count,
+        a component outside [0, 1], a width outside [0, 64] or an unknown layer."""
+        n, arr = self._c_styles(styles)
+        self._check(self._c("set_collider_styles")(n, arr))
+
+    def get_collider_styles(self):
+        """the styles as stored, one dict per collider -- `None` for one that is not visible"""
+        arr = (_ffi.EggColliderStyle * _ffi.MAX_COLLIDERS)()
+        n = C.c_int32()
+        self._check(self._c("get_collider_styles")(_ffi.MAX_COLLIDERS, arr, C.byref(n)))
+        kinds = (_ffi.EggCollider * _ffi.MAX_COLLIDERS)()
+        self._check(self._c("get_colliders")(_ffi.MAX_COLLIDERS, kinds, C.byref(n)))
+        layers = {v: name for name, v in _ffi.COLLIDER_LAYERS.items()}
+        out = []
+        for st, c in zip(arr[:n.value], kinds[:n.value]):
+            inside = c.kind not in (_ffi.COLLIDER_SEGMENT, _ffi.COLLIDER_WALL)
+            visible = (st.fill[3] > 0 and inside) or (st.line[3] > 0 and st.line_width > 0)
+            out.append({"fill": tuple(st.fill), "line": tuple(st.line), "line_width": st.line_width,
+                        "layer": layers[st.layer]} if visible else None)
+        return out
+
+    def get_collider_pose(self, alpha=None):
+        """The list draw() places the colliders at ("Collider styles"), as get_colliders returns
+        it: every parameter is `last * (1 - t) + current * t`, `last` the list at the start of the last committed step,
+        t = `alpha` clamped to [0, 1] or, with None, this object's interpolation_alpha -- the rule draw() places the
+        particles by.  A host that draws the colliders itself reads this once per frame.  set_colliders sets both lists:
+        a teleport is not interpolated."""
+        arr = (_ffi.EggCollider * _ffi.MAX_COLLIDERS)()
+        n = C.c_int32()
+        self._check(self._c("get_collider_pose")(float("nan") if alpha is None else float(alpha), _ffi.MAX_COLLIDERS, arr, C.byref(n)))
+        types = {v: k for k, v in _ffi.COLLIDER_TYPES.items()}
+        return [(_ffi.COLLIDER_NAMES[c.kind],) + tuple(c.p[:len(_ffi.COLLIDER_PARAM_NAMES[c.kind])]) + (types[c.type_mask],)
+                for c in arr[:n.value]]
+
     # ------------------------------------------------ collider loads (egg_set_collider_loads, DESIGN.md section 2.7)
     def set_collider_loads(self, on):
         """Switch collider loads on or off ("Collider loads"; off by default).  While on, a relaxed

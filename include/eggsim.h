@@ -413,7 +413,8 @@ int egg_set_option(egg_handle *h, int option, double value);
  *              viscosity pass rewrites prev only after the sub-step's last collision pass).  The sweep is against the
  *              list as it is: not against a list the caller changes between steps.  A catch adds no counter of its own.
  * Parameters a kind does not use are stored as 0.  The projection has no compliance, mass, friction or omega; velocities
- * follow from the post-solve, so a wall absorbs the normal velocity.  Colliders are not drawn.  Applied in list order, a
+ * follow from the post-solve, so a wall absorbs the normal velocity.  Colliders are drawn only where a style asks for it (egg_set_collider_styles
+ * below; undrawn by default).  Applied in list order, a
  * particle in a corner satisfies the last collider exactly and the earlier ones only approximately.
  * Relaxed order only, as EGG_OPT_COHESION = 1: a non-empty list on a handle in exact order is EGG_ERR_UNSUPPORTED, and
  * EGG_OPT_SOLVER_ORDER = 0 is EGG_ERR_UNSUPPORTED while the list is not empty; an empty list is always accepted.
@@ -632,6 +633,54 @@ typedef struct {
 int egg_set_collider_bodies(egg_handle *h, int32_t n, const egg_collider_body *b);
 /* the bodies as stored, one per collider (zeros included): the count in *n, min(*n, cap) records copied */
 int egg_get_collider_bodies(const egg_handle *h, int32_t cap, egg_collider_body *b, int32_t *n);
+
+/* ---- collider pose and collider styles: colliders in the picture ("Collider styles") ----
+ * Not in the reference, which has no colliders and so draws none.
+ * THE POSE.  Beside the list egg_get_colliders returns, a handle keeps the list as it stood at the START of the last
+ * committed relaxed step -- what last_x / last_y are for the particles.  Every committed relaxed step copies the current
+ * list into it just before the commit advances the list, whether or not anything moves; a failed or discarded step and the
+ * motion, spin, surface and body setters leave it alone; egg_set_colliders sets BOTH lists to the new list, so a teleport
+ * is not interpolated.  egg_get_collider_pose returns the list with every parameter
+ *   p[i] = last.p[i] * (1.0 - t) + cur.p[i] * t        FP64, in exactly this order, on the host,
+ * t = alpha clamped to [0, 1], or the handle's interpolation_alpha where alpha is NaN (as egg_render treats its own);
+ * kind and type_mask are the current list's.  The count goes to *n, min(*n, cap) colliders are copied.  It is the pose the
+ * renderer draws, for a host that draws the colliders itself between two steps.  Two consequences of mixing parameters:
+ *   - a turning collider moves along the chord, not the arc: at 2 rad/s and 60 steps/s the step turns 1/30 rad and the
+ *     chord's midpoint lies 1 - cos(1/60) = 1.4e-4 of the lever arm inside the arc;
+ *   - a half-plane's mixed normal is not renormalised, as it is not after a turn: between two steps of a turning half-plane
+ *     its length is below 1 by the same 1.4e-4.
+ * STYLES.  Every collider of the list may carry a STYLE; the default is undrawn, and a list without a visible style makes
+ * egg_render, egg_group_render and egg_draw_source_render launch exactly what they launch without and return the same bits.
+ * A collider is VISIBLE when fill[3] > 0 and its kind has an inside (HALF_PLANE: the side n . pos < off, DISC: inside,
+ * CONTAINER: outside the circle -- the solid side), or when line[3] > 0 && line_width > 0.  One kernel draws the visible
+ * colliders of layer 0 onto the cleared screen, before the eggs, and one those of layer 1 after the eggs -- whether or not
+ * the eggs are drawable: the boundary is visible before the first step.  Each launch counts in stats.kernel_launches.
+ * Per screen pixel (i, j): wx = ((double)i + 0.5) + origin_x, wy likewise; the visible colliders of the layer in list order,
+ * each at the pose of the frame's t, with the signed distance sd in FP64, in exactly this order, no contraction:
+ *   HALF_PLANE  (nx * wx + ny * wy) - off
+ *   DISC        dx = wx - cx, dy = wy - cy, sqrt(dx * dx + dy * dy) - R;    CONTAINER  R - sqrt(dx * dx + dy * dy)
+ *   SEGMENT, WALL  e, l2, t, q as egg_set_colliders defines them for the position (wx, wy); ddx = wx - qx, ddy = wy - qy,
+ *               sd = sqrt(ddx * ddx + ddy * ddy); no inside
+ *   cf = (float)fmin(fmax(0.5 - sd, 0.0), 1.0), 0 for a kind without an inside;
+ *   cl = (float)fmin(fmax((0.5 + 0.5 * (double)line_width) - fabs(sd), 0.0), 1.0) when line_width > 0, else 0;
+ *   cf > 0 && fill[3] > 0: out = blend(out, (fill.rgb, fill[3] * cf)); then cl > 0 && line[3] > 0: the same with line, cl;
+ *   blend is the "alpha" blend of the composite in float32: rgb = src.rgb * src.a + dst.rgb * (1 - src.a), a = src.a +
+ *   dst.a * (1 - src.a).  A collider whose coverage at a pixel is 0 does not touch the pixel (a -0.0 stays -0.0).
+ * egg_set_collider_styles: n must equal the current collider count, or 0 (nothing is drawn).  Everything is checked before
+ * anything changes: EGG_ERR_INVALID_ARGUMENT, with the collider's index in the message, for an n that does not match, a
+ * colour component that is not finite or outside [0, 1], a width that is not finite or outside [0, 64], a layer other than
+ * 0 or 1.  Accepted in either solver order (it only ever draws a list that exists).  egg_set_colliders resets the styles to
+ * undrawn; the motion, spin, surface, body and load setters leave them.  Refused while a step is in flight. */
+typedef struct {
+    float fill[4];      /* straight-alpha RGBA of the solid side; ignored by SEGMENT and WALL, which have no inside */
+    float line[4];      /* RGBA of the outline / of the segment itself */
+    float line_width;   /* px, 0 .. 64; 0: no line */
+    int32_t layer;      /* 0: under the eggs (after the clear, before the white canvas); 1: over them */
+} egg_collider_style; /* 40 bytes */
+int egg_set_collider_styles(egg_handle *h, int32_t n, const egg_collider_style *s);
+/* the styles as stored, one per collider (undrawn ones all zero): the count in *n, min(*n, cap) records copied */
+int egg_get_collider_styles(const egg_handle *h, int32_t cap, egg_collider_style *s, int32_t *n);
+int egg_get_collider_pose(egg_handle *h, double alpha, int32_t cap, egg_collider *c, int32_t *n);
 
 /* ---- force fields (not in the reference, which has no forces as it has no boundary; DESIGN.md section 2.7, "Forces") ----
  * A handle holds an ordered list of at most EGG_MAX_FORCES fields.  The values are accelerations in px/s^2 and do not depend
@@ -861,6 +910,13 @@ int egg_group_get_collider_motion(const egg_group *g, int32_t cap, egg_collider_
 int egg_group_set_collider_spin(egg_group *g, int32_t n, const egg_collider_spin *s);
 int egg_group_get_collider_spin(const egg_group *g, int32_t cap, egg_collider_spin *s, int32_t *n);
 int egg_group_get_collider_grips(egg_group *g, int64_t grips[2]);
+/* egg_set_collider_styles for every handle of the group alike, with its rules; a refused call changes no handle, and
+ * egg_group_set_colliders resets the styles.  Not in the reference, which draws no colliders.  egg_group_render draws
+ * handle 0's list and styles -- every handle holds and advances the same list -- at the group's interpolation alpha;
+ * egg_group_get_collider_pose is egg_get_collider_pose of handle 0, a NaN alpha standing for the group's own. */
+int egg_group_set_collider_styles(egg_group *g, int32_t n, const egg_collider_style *s);
+int egg_group_get_collider_styles(const egg_group *g, int32_t cap, egg_collider_style *s, int32_t *n);
+int egg_group_get_collider_pose(egg_group *g, double alpha, int32_t cap, egg_collider *c, int32_t *n);
 /* egg_set_collider_loads for every handle of the group alike.  Every device projects only the particles it owns, so only
  * they contribute; the integer sums and the dropped counts are added over the handles, then converted once: the results
  * equal one handle's bit for bit.  A group whose handles differ in the switch refuses to step. */
