@@ -50,6 +50,8 @@ COHESION_REFERENCE, COHESION_EFFECTIVE = 0, 1
 RELAXATION_DEFAULT = 1.8  # EGG_RELAXATION_DEFAULT
 PK_VARIANT_LEVELS_INORDER, PK_VARIANT_LEVELS_OOO, PK_VARIANT_EXEC, PK_VARIANT_EXEC_CHAIN, PK_VARIANT_SORT_LDS, PK_VARIANT_SORT_DIRECT = 1, 2, 4, 8, 16, 32
 PK_VARIANT_PASS_FUSED = 64
+# the eight results egg_selftest_arith_operands returns per operand triple (n, d, x)
+ARITH_COLUMNS = ("div", "sqrt", "root", "rroot", "div_root", "op_div", "op_sqrt", "op_div_sqrt")
 
 CONFIG_FIELDS = ["damping", "follow_strength", "cohesion_strength",
                  "cohesion_interaction_distance_factor", "collision_strength",
@@ -303,6 +305,7 @@ _SIGNATURES = {
     "egg_get_elapsed": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "egg_download_particles": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64]),
     "egg_selftest_arith": (C.c_int, [C.c_void_p, C.c_int64, C.c_uint64, C.POINTER(C.c_int64)]),
+    "egg_selftest_arith_operands": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "egg_get_stats": (C.c_int, [C.c_void_p, C.POINTER(EggStats)]),
     "egg_get_environment": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(EggEnvironment)]),
     "egg_set_option": (C.c_int, [C.c_void_p, C.c_int, C.c_double]),

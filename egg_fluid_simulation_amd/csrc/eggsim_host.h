@@ -49,6 +49,7 @@ extern "C" __global__ void egg_step_kernel_gl_mg(EggStepArgs A);
 extern "C" __global__ void egg_step_kernel_gs_mg(EggStepArgs A);
 extern "C" __global__ void egg_step_kernel_gs(EggStepArgs A);
 extern "C" __global__ void egg_selftest_arith_kernel(unsigned long long, int, unsigned long long *);
+extern "C" __global__ void egg_selftest_arith_operands_kernel(long long, const double *, const double *, const double *, double *);
 extern "C" __global__ void egg_pk_plan_kernel(EggPackedArgs A);
 extern "C" __global__ void egg_pk_begin_kernel(EggPackedArgs A);
 extern "C" __global__ void egg_pk_mid_kernel(EggPackedArgs A);

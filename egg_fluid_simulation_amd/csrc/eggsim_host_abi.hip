@@ -808,6 +808,27 @@ int egg_selftest_arith(egg_handle *h, int64_t n_operand_pairs, uint64_t seed, in
     return EGG_OK;
 }
 
+int egg_selftest_arith_operands(egg_handle *h, int64_t count, const double *n, const double *d, const double *x, double *out) {
+    if (!h || count < 0 || count > ((int64_t)1 << 26) || (count && (!n || !d || !x || !out))) return EGG_ERR_INVALID_ARGUMENT;
+    if (!count) return EGG_OK;
+    (void)hipSetDevice(h->device);
+    hipStream_t st = h->sys[0].stream;
+    DevBuf<double> in, res;  // in: n, d, x one after the other
+    const size_t c = (size_t)count;
+    HIP_TRY(h, in.reserve(3 * c, false, st));
+    HIP_TRY(h, res.reserve(8 * c, false, st));
+    HIP_TRY(h, hipMemcpyAsync(in.p, n, c * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipMemcpyAsync(in.p + c, d, c * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(h, hipMemcpyAsync(in.p + 2 * c, x, c * sizeof(double), hipMemcpyHostToDevice, st));
+    const int threads = 256;
+    hipLaunchKernelGGL(egg_selftest_arith_operands_kernel, dim3((unsigned)((c + threads - 1) / threads)), dim3(threads), 0, st,
+                       (long long)count, in.p, in.p + c, in.p + 2 * c, res.p);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipMemcpyAsync(out, res.p, 8 * c * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(h, hipStreamSynchronize(st));
+    return EGG_OK;
+}
+
 int egg_get_environment(egg_handle *h, int which, egg_environment *out) {
     if (!h || !out || which < 0 || which > 1) return EGG_ERR_INVALID_ARGUMENT;
     HIP_TRY(h, hipSetDevice(h->device));

@@ -245,7 +245,7 @@ extern "C" __global__ void __launch_bounds__(256) egg_pk_mid_kernel(EggPackedArg
     if (p >= A.p_end) return;
     const int atom = A.pk_atom[p];
     const double2 ps = ((const double2 *)A.pk_pos)[p], pv = ((const double2 *)A.pk_prev)[p];
-    double2 v = make_double2((ps.x - pv.x) / A.sub_delta, (ps.y - pv.y) / A.sub_delta);
+    double2 v = make_double2(egg_div(ps.x - pv.x, A.sub_delta), egg_div(ps.y - pv.y, A.sub_delta));
     const double im = ((const double2 *)A.pk_wr)[p].x;
     double2 out;
     egg_pre_follow(A.damping, A.sub_delta, A.eps, A.follow_compliance, ps, v, im, A.atom_tx[atom], A.atom_ty[atom], A.atom_fd[atom], out);
@@ -361,7 +361,7 @@ __device__ __forceinline__ void egg_pk_lists_body(const EggPackedArgs &A, const 
             } else {  // post-solve of the sub-step that ended (egg_pk_mid_kernel)
                 ps = ((const double2 *)A.pk_pos)[p];
                 const double2 pv = ((const double2 *)A.pk_prev)[p];
-                v = make_double2((ps.x - pv.x) / A.sub_delta, (ps.y - pv.y) / A.sub_delta);
+                v = make_double2(egg_div(ps.x - pv.x, A.sub_delta), egg_div(ps.y - pv.y, A.sub_delta));
                 im = ((const double2 *)A.pk_wr)[p].x;
             }
             egg_pre_follow(A.damping, A.sub_delta, A.eps, A.follow_compliance, ps, v, im, A.atom_tx[atom], A.atom_ty[atom], A.atom_fd[atom], out);
@@ -394,8 +394,8 @@ __device__ __forceinline__ void egg_pk_lists_body(const EggPackedArgs &A, const 
     bool bad = false;
     for (int i = tid; i < n; i += nthreads) {
         const double2 ps = i == tid ? first_pos : ((const double2 *)A.pk_pos)[p0 + i];
-        const double fcx = floor(ps.x / A.cell_size);
-        const double fcy = floor(ps.y / A.cell_size);
+        const double fcx = floor(egg_div(ps.x, A.cell_size));
+        const double fcy = floor(egg_div(ps.y, A.cell_size));
         const int32_t *cl = &t.aclaim[4 * t.aslot[i]];
         int cx = (fcx >= -2.0e9 && fcx <= 2.0e9) ? (int)fcx : 0x7FFFFFF0;
         int cy = (fcy >= -2.0e9 && fcy <= 2.0e9) ? (int)fcy : 0x7FFFFFF0;
@@ -1689,12 +1689,12 @@ extern "C" __global__ void __launch_bounds__(256) egg_pk_end_kernel(EggPackedArg
         for (int q = tid; q < cnt; q += nthreads) {
             const int g = A.pk_src[p + q];
             const double2 ps = ((const double2 *)A.pk_pos)[p + q], pv = ((const double2 *)A.pk_prev)[p + q];
-            const double2 v = make_double2((ps.x - pv.x) / A.sub_delta, (ps.y - pv.y) / A.sub_delta);
+            const double2 v = make_double2(egg_div(ps.x - pv.x, A.sub_delta), egg_div(ps.y - pv.y, A.sub_delta));
             A.x_out[g] = ps.x;
             A.y_out[g] = ps.y;
             A.vx_out[g] = v.x;
             A.vy_out[g] = v.y;
-            const double fcx = floor(ps.x / A.cell_size), fcy = floor(ps.y / A.cell_size);
+            const double fcx = floor(egg_div(ps.x, A.cell_size)), fcy = floor(egg_div(ps.y, A.cell_size));
             const int cx = (fcx >= -2.0e9 && fcx <= 2.0e9) ? (int)fcx : 0x7FFFFFF0;
             const int cy = (fcy >= -2.0e9 && fcy <= 2.0e9) ? (int)fcy : 0x7FFFFFF0;
             lo_x = min(lo_x, cx);

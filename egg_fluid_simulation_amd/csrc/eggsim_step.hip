@@ -442,11 +442,11 @@ __device__ __forceinline__ void egg_step_body(const Args &A, const int tile = (i
                     nx = 0.0;
                     ny = 0.0;
                 } else {
-                    nx = dx / current;
-                    ny = dy / current;
+                    nx = egg_div(dx, current);
+                    ny = egg_div(dy, current);
                 }
                 double violation = current - target;
-                double lambda = violation / (im + A.follow_compliance);
+                double lambda = egg_div(violation, im + A.follow_compliance);
                 x = x + nx * lambda * im;
                 y = y + ny * lambda * im;
             }
@@ -479,8 +479,8 @@ __device__ __forceinline__ void egg_step_body(const Args &A, const int tile = (i
             PROF(10)  // hash: clear
             for (int i = tid; i < n; i += nthreads) {
                 double2 ps = t.pos[i];
-                double fcx = floor(ps.x / A.cell_size);
-                double fcy = floor(ps.y / A.cell_size);
+                double fcx = floor(egg_div(ps.x, A.cell_size));
+                double fcy = floor(egg_div(ps.y, A.cell_size));
                 const int32_t *cl = &t.aclaim[4 * t.aslot[i]];
                 // NaN / out-of-range coordinates fail the box test below
                 int cx = (fcx >= -2.0e9 && fcx <= 2.0e9) ? (int)fcx : 0x7FFFFFF0;
@@ -794,7 +794,7 @@ __device__ __forceinline__ void egg_step_body(const Args &A, const int tile = (i
         // ------------------------------------------------ post-solve, L:1690-1693
         for (int i = tid; i < n; i += nthreads) {
             const double2 ps = t.pos[i], pv = regs ? rprev : t.prev[i];
-            const double2 v = make_double2((ps.x - pv.x) / sub_delta, (ps.y - pv.y) / sub_delta);
+            const double2 v = make_double2(egg_div(ps.x - pv.x, sub_delta), egg_div(ps.y - pv.y, sub_delta));
             if (regs)
                 rvel = v;
             else
@@ -817,7 +817,7 @@ __device__ __forceinline__ void egg_step_body(const Args &A, const int tile = (i
         A.y_out[g] = ps.y;
         A.vx_out[g] = v.x;
         A.vy_out[g] = v.y;
-        double fcx = floor(ps.x / A.cell_size), fcy = floor(ps.y / A.cell_size);
+        double fcx = floor(egg_div(ps.x, A.cell_size)), fcy = floor(egg_div(ps.y, A.cell_size));
         int cx = (fcx >= -2.0e9 && fcx <= 2.0e9) ? (int)fcx : 0x7FFFFFF0;
         int cy = (fcy >= -2.0e9 && fcy <= 2.0e9) ? (int)fcy : 0x7FFFFFF0;
         atomicMin(&t.aaabb[4 * k + 0], cx);
@@ -1096,7 +1096,7 @@ extern "C" __global__ void egg_selftest_arith_kernel(unsigned long long seed, in
             v[q] = (sign << 63) | (e << 52) | mant;
         }
         double n = __longlong_as_double((long long)v[0]), d = __longlong_as_double((long long)v[1]);
-        double want = n / d;
+        double want = egg_div(n, d);
         double got = egg_div_with_rcp(n, d, egg_rcp_refined(d));
         if (__double_as_longlong(want) != __double_as_longlong(got)) ++bad;
         // square root: |n| spans [2^-300, 2^300]; its square (up to rounding) spans the sqrt window
@@ -1107,11 +1107,32 @@ extern "C" __global__ void egg_selftest_arith_kernel(unsigned long long seed, in
             // the projection's normalisation: numerator / sqrt(x) through the reciprocal the root core yields
             egg_sqrt_rcp_core(x, gr, rr);
             if (__double_as_longlong(ws) != __double_as_longlong(gr)) ++bad;
-            double wq = d / ws, gq = egg_div_with_rcp(d, gr, rr);
+            double wq = egg_div(d, ws), gq = egg_div_with_rcp(d, gr, rr);
             if (__double_as_longlong(wq) != __double_as_longlong(gq)) ++bad;
         }
     }
     if (bad) atomicAdd(mismatches, bad);
+}
+
+// the same cores on the caller's operand triples (n, d, x), raw: eight results per triple, nothing judged here
+// (egg_selftest_arith_operands; the last three are the operators project_pair_reference and the follow constraint use)
+extern "C" __global__ void egg_selftest_arith_operands_kernel(long long count, const double *n_in, const double *d_in,
+                                                               const double *x_in, double *out) {
+    const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const double n = n_in[i], d = d_in[i], x = x_in[i];
+    double root, rroot;
+    egg_sqrt_rcp_core(x, root, rroot);
+    double *o = out + 8 * i;
+    o[0] = egg_div_with_rcp(n, d, egg_rcp_refined(d));
+    o[1] = egg_sqrt_core(x);
+    o[2] = root;
+    o[3] = rroot;
+    o[4] = egg_div_with_rcp(n, root, rroot);
+    o[5] = egg_div(n, d);
+    const double s = sqrt(x);
+    o[6] = s;
+    o[7] = egg_div(n, s);
 }
 
 // ---------------------------------------------------------------------------
@@ -1127,7 +1148,7 @@ extern "C" __global__ void egg_atom_bounds_kernel(const double *x, const double 
     int g0 = atom_offset[atom], cnt = atom_count[atom];
     int lo_x = 0x7FFFFFFF, lo_y = 0x7FFFFFFF, hi_x = -0x7FFFFFFF, hi_y = -0x7FFFFFFF;
     for (int q = lane; q < cnt; q += EGG_WAVE) {
-        double fcx = floor(x[g0 + q] / cell_size), fcy = floor(y[g0 + q] / cell_size);
+        double fcx = floor(egg_div(x[g0 + q], cell_size)), fcy = floor(egg_div(y[g0 + q], cell_size));
         int cx = (fcx >= -2.0e9 && fcx <= 2.0e9) ? (int)fcx : 0x7FFFFFF0;
         int cy = (fcy >= -2.0e9 && fcy <= 2.0e9) ? (int)fcy : 0x7FFFFFF0;
         lo_x = min(lo_x, cx);
@@ -1159,7 +1180,7 @@ extern "C" __global__ void egg_rederive_kernel(const double *mass_t, double *inv
     double tt = mass_t[i];
     if (do_mass) {
         double mass = min_mass * (1 - tt) + max_mass * tt;
-        inv_mass[i] = 1 / mass;
+        inv_mass[i] = egg_div(1.0, mass);
     }
     if (do_radius) radius[i] = min_radius * (1 - tt) + max_radius * tt;
 }
@@ -1289,6 +1310,6 @@ extern "C" __global__ void egg_centroid_kernel(const double *wx, const double *w
         y = y + yy[o + k];
     }
     double cnt = (double)(c + c2);
-    out_x[b] = x / cnt;
-    out_y[b] = y / cnt;
+    out_x[b] = egg_div(x, cnt);
+    out_y[b] = egg_div(y, cnt);
 }

@@ -132,15 +132,54 @@ __device__ inline uint32_t cell_meta(const Tile &t, int buf, uint32_t key) {
 // projection below sits on the step's critical path, so every instruction counts.  The functions
 // here are the same arithmetic minus the scaling / special-value steps, which are the identity
 // while all operands and results are normal numbers far from the exponent limits.  Inside that
-// window the results are bit-identical to `/` and sqrt() (egg_selftest_arith compares them on
-// random operands on the device); outside it the projection uses the operators.
+// window the results are the correctly rounded quotient and root (egg_selftest_arith compares them on
+// random operands on the device, tests/test_gpu_arith_cases.py on directed ones); outside it the projection
+// uses egg_div() and sqrt().
+//
+// The last place.  v_rcp_f64 and two Newton steps give a FAITHFUL reciprocal, and egg_div_with_rcp rounds every
+// quotient correctly only with the NEAREST one: for divisors 2 - k 2^-52 (measured: k = 3 .. 13) the refined
+// reciprocal is one unit low, and so is the quotient of a numerator 1 / (2 D) from a rounding midpoint -- in the
+// compiler's `/` as well, which is this sequence plus scaling.  egg_rcp_finish makes a reciprocal that a Newton
+// step has just produced the nearest one by comparing exact residuals.
+//  - Such an r is never above the nearest: r = RN(r1 + r1 e1), e1 = RN(1 - d r1).  With e1 exact that is
+//    RN((1 / d)(1 - e1^2)); the rounding of e1 moves it by at most |e1| 2^-53 (relative), no more than e1^2 while
+//    |e1| >= 2^-53, and below that e1 is exact.  So the unrounded value is <= 1 / d, rounding is monotonic, and r is
+//    the nearest reciprocal or, where a midpoint lies in between, its lower neighbour (in magnitude).
+//  - e = 1 - d r is exact for such an r (|e| < 2^-52, its bits end at 2^-105).  r2 = RN(r + 0.75 .. 1.5 units) is
+//    the neighbour above.  The nearer of the two has the smaller residual; e and e2 differ in magnitude by a
+//    multiple of 2^-105 and are both exact wherever they are close.
+__device__ __forceinline__ double egg_rcp_finish(double d, double r) {
+    const double e = __builtin_fma(-d, r, 1.0);
+    const double r2 = __builtin_fma(r, 0x1.8p-53, r);
+    const double e2 = __builtin_fma(-d, r2, 1.0);
+    return __builtin_fabs(e2) < __builtin_fabs(e) ? r2 : r;
+}
 __device__ __forceinline__ double egg_rcp_refined(double d) {
     double r = __builtin_amdgcn_rcp(d);
     double e = __builtin_fma(-d, r, 1.0);
     r = __builtin_fma(r, e, r);
     e = __builtin_fma(-d, r, 1.0);
     r = __builtin_fma(r, e, r);
-    return r;
+    return egg_rcp_finish(d, r);
+}
+// `n / d` correctly rounded, for every division of the exact path that is not hand-expanded: the operator, whose
+// quotient is within one unit of the last place, and the same comparison of exact remainders on the quotient
+// itself.  Operands or quotients near the exponent limits (where a remainder would not be exact) keep the
+// operator's result.
+__device__ __forceinline__ double egg_div(double n, double d) {
+    double q = n / d;
+    const double an = __builtin_fabs(n), ad = __builtin_fabs(d), aq = __builtin_fabs(q);
+    if (an >= 0x1p-800 && an <= 0x1p800 && ad >= 0x1p-800 && ad <= 0x1p800 && aq >= 0x1p-800 && aq <= 0x1p800) {
+        const double rem = __builtin_fma(-d, q, n);
+        if (rem != 0.0) {
+            // |n / d| > |q| exactly when the remainder has the numerator's sign
+            const bool up = (__double_as_longlong(rem) ^ __double_as_longlong(n)) >= 0;
+            const double q2 = __longlong_as_double(__double_as_longlong(q) + (up ? 1 : -1));
+            const double rem2 = __builtin_fma(-d, q2, n);
+            if (__builtin_fabs(rem2) < __builtin_fabs(rem)) q = q2;
+        }
+    }
+    return q;
 }
 __device__ __forceinline__ double egg_div_with_rcp(double n, double d, double r) {
     double q = n * r;
@@ -160,9 +199,11 @@ __device__ __forceinline__ double egg_sqrt_core(double x) {  // valid for x in [
     g = __builtin_fma(d, h, g);
     return g;
 }
-// the same square root, plus a refined reciprocal of the root: the Goldschmidt iteration carries
-// h ~ 1 / (2 sqrt(x)) to ~2^-51, one Newton step on 2h gives the quality of egg_rcp_refined(root) without
-// the v_rcp_f64 and one of its two Newton steps (the quotient below only needs a faithful reciprocal)
+// the same square root, plus the nearest reciprocal of the root: the Goldschmidt iteration carries
+// h ~ 1 / (2 sqrt(x)) to ~2^-51, one Newton step on 2h gives a faithful reciprocal without the v_rcp_f64 and one of
+// its two Newton steps, and egg_rcp_finish its last place.  (Up to round 25 the Newton step was all: for
+// root = 0x1.fffffffffffffp+e the reciprocal came out as 0x1p-1-e, and n / root one unit low;
+// profiles/r26_arith_hard_cases.md.)
 __device__ __forceinline__ void egg_sqrt_rcp_core(double x, double &root, double &rroot) {
     double y = __builtin_amdgcn_rsq(x);
     double g = x * y;
@@ -177,7 +218,7 @@ __device__ __forceinline__ void egg_sqrt_rcp_core(double x, double &root, double
     root = g;
     const double r0 = h + h;
     const double e = __builtin_fma(-g, r0, 1.0);
-    rroot = __builtin_fma(r0, e, r0);
+    rroot = egg_rcp_finish(g, __builtin_fma(r0, e, r0));
 }
 #define EGG_ARITH_LO 0x1p-300
 #define EGG_ARITH_HI 0x1p300
@@ -215,14 +256,14 @@ __device__ __forceinline__ void project_pair_reference(SameBatch same_batch, dou
             nx = 0.0;
             ny = 0.0;
         } else {
-            nx = dx / current;
-            ny = dy / current;
+            nx = egg_div(dx, current);
+            ny = egg_div(dy, current);
         }
         double cax, cay, cbx, cby;
         if (divisor < eps) {
             cax = cay = cbx = cby = 0.0;
         } else {
-            double correction = -violation / divisor;
+            double correction = egg_div(-violation, divisor);
             const double max_correction = fabs(violation);
             if (correction < -max_correction) correction = -max_correction;
             if (correction > max_correction) correction = max_correction;
@@ -573,11 +614,11 @@ __device__ __forceinline__ void egg_pre_follow(double damping, double sub_delta,
             nx = 0.0;
             ny = 0.0;
         } else {
-            nx = dx / current;
-            ny = dy / current;
+            nx = egg_div(dx, current);
+            ny = egg_div(dy, current);
         }
         const double violation = current - target;
-        const double lambda = violation / (im + follow_compliance);
+        const double lambda = egg_div(violation, im + follow_compliance);
         x = x + nx * lambda * im;
         y = y + ny * lambda * im;
     }

@@ -1352,6 +1352,16 @@ class SimulationHandler(_HandlerSurface):
         self._check(self._lib.egg_selftest_arith(self._h, int(n), int(seed), C.byref(bad)))
         return bad.value
 
+    def selftest_arith_operands(self, n, d, x):
+        """the kernel's hand-expanded division and square roots on the caller's operand triples, raw: an array [count, 8]
+        with the columns of _ffi.ARITH_COLUMNS (see egg_selftest_arith_operands); nothing is judged on the device"""
+        n, d, x = (np.ascontiguousarray(v, dtype=np.float64) for v in (n, d, x))
+        if not (n.ndim == 1 and n.shape == d.shape == x.shape):
+            raise EggError("selftest_arith_operands takes three one-dimensional arrays of one length")
+        out = np.empty((n.size, 8), dtype=np.float64)
+        self._check(self._lib.egg_selftest_arith_operands(self._h, n.size, n.ctypes.data, d.ctypes.data, x.ctypes.data, out.ctypes.data))
+        return out
+
     def set_option(self, option, value):
         self._check(self._lib.egg_set_option(self._h, int(option), float(value)))
 

@@ -341,6 +341,14 @@ int egg_get_stats(egg_handle *h, egg_stats *out);
  * the device and returns the number of results that differ in any bit (must be 0). */
 int egg_selftest_arith(egg_handle *h, int64_t n_operand_pairs, uint64_t seed, int64_t *mismatches);
 
+/* Diagnostic: the same expansions on the CALLER's operands, nothing judged on the device.  For each of the `count`
+ * triples (n[i], d[i], x[i]) out[8 i ..] receives: egg_div_with_rcp(n, d, egg_rcp_refined(d)); egg_sqrt_core(x); root and
+ * rroot of egg_sqrt_rcp_core(x); egg_div_with_rcp(n, root, rroot); and what the rest of the exact path divides and roots
+ * with: egg_div(n, d) (the `/` operator with its last place corrected), sqrt(x) and egg_div(n, sqrt(x)).  All four pointers
+ * are host memory.  Operands outside the expansions' windows (|n|, |d| in [2^-300, 2^300], x in [2^-600, 2^600]) give
+ * whatever the expansions make of them. */
+int egg_selftest_arith_operands(egg_handle *h, int64_t count, const double *n, const double *d, const double *x, double *out /* 8 * count */);
+
 /* tuning knobs (not part of the reference surface) */
 enum {
     EGG_OPT_CLAIM_MARGIN_CELLS = 0, /* initial margin around an atom's cells when tiles are formed */

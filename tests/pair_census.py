@@ -43,8 +43,8 @@ position is copied bit for bit) and `averaged_n` for n >= 2 fired pairs.
 clamped to [0, 1] is >= 0, so divisor = wsum + compliance >= wsum >= eps.  (tests/test_pair_census.py checks the label with
 a negative compliance on classify() and pair_shares alone.)
 
-Out of scope: NaN positions (they fail the step at the insert kernel), the exact-order solver, viscosity's own pair
-weights and the force step."""
+Out of scope: NaN positions (they fail the step at the insert kernel), the exact-order solver (tests/exact_census.py has its census),
+viscosity's own pair weights and the force step."""
 import numpy as np
 
 from coupling_model import CouplingMixin

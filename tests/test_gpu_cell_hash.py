@@ -38,11 +38,16 @@ def _handler(egg, white=None, yolk=None, hook=True, **options):
     return h
 
 
+def _bits(a):
+    """the bit patterns: np.array_equal on floats cannot tell -0.0 from +0.0"""
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
 def _same(h, o, tag):
     for w in (WHITE, YOLK):
         for f in STATE:
             a, b = h.download(w, f), o.field(w, f)
-            assert a.shape == b.shape and np.array_equal(a, b), (tag, w, f)
+            assert a.shape == b.shape and np.array_equal(_bits(a), _bits(b)), (tag, w, f)
     assert h.stats()["pair_solves"] == o.total_visited, tag
 
 

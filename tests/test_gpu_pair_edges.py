@@ -36,7 +36,7 @@ branch; W / Y the white / yolk side of the coupling pass):
 Shapes: 4 to 10 particles per type in a hand case and a cut case, one default egg (157 + 15) in the sweep, 615 particles in
 test_unequal_types.  No scene is at the workload's size.  `dead` has no device case (tests/pair_census.py: it cannot occur).
 
-Out of scope: NaN positions (they fail the step at the insert kernel), the exact-order solver, viscosity's own pair
+Out of scope: NaN positions (they fail the step at the insert kernel), the exact-order solver (tests/test_gpu_exact_edges.py), viscosity's own pair
 weights, rx_force, coupling on groups (refused by design)."""
 import numpy as np
 import pytest

@@ -27,9 +27,14 @@ def _dev_state(h, w):
     return np.array([h.download(w, "x"), h.download(w, "y"), h.download(w, "vx"), h.download(w, "vy")])
 
 
+def _bits(a):
+    """the bit patterns: np.array_equal on floats cannot tell -0.0 from +0.0"""
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
 def _assert_close(dev, ref, what):
     assert np.all(np.abs(dev - ref) <= REL_TOL * np.maximum(1.0, np.abs(ref))), what  # the stated tolerance
-    assert np.array_equal(dev, ref), what + ": not bit-exact"  # what the kernel actually achieves
+    assert np.array_equal(_bits(dev), _bits(ref)), what + ": not bit-exact"  # what the kernel actually achieves (the sign of a zero included)
 
 
 @pytest.mark.parametrize("name", GOLDEN_CASES)
