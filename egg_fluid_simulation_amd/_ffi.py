@@ -132,6 +132,10 @@ class EggColliderStyle(C.Structure):  # egg_collider_style: how the headless ren
 
 
 COLLIDER_LAYERS = {"under": 0, "over": 1}  # egg_collider_style.layer
+class EggColliderContact(C.Structure):  # egg_collider_contact: a collider that meets the other colliders (16 bytes)
+    _fields_ = [("restitution", C.c_double), ("on", C.c_int32), ("reserved", C.c_int32)]
+
+
 COLLIDER_LOAD_IMPULSE_SCALE = 1048576.0  # EGG_COLLIDER_LOAD_IMPULSE_SCALE, 2^20
 COLLIDER_LOAD_TORQUE_SCALE = 1024.0      # EGG_COLLIDER_LOAD_TORQUE_SCALE, 2^10
 MAX_COLLIDERS = 64  # EGG_MAX_COLLIDERS
@@ -236,6 +240,9 @@ _SIGNATURES = {
     "egg_get_collider_loads": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggColliderLoad), C.POINTER(C.c_int32)]),
     "egg_set_collider_bodies": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggColliderBody)]),
     "egg_get_collider_bodies": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggColliderBody), C.POINTER(C.c_int32)]),
+    "egg_set_collider_contacts": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggColliderContact), C.c_int32]),
+    "egg_get_collider_contacts": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggColliderContact), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "egg_get_collider_contact_solves": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "egg_group_set_collider_loads": (C.c_int, [C.c_void_p, C.c_int]),
     "egg_group_get_collider_load_sums": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double),
                                                    C.POINTER(C.c_int32)]),

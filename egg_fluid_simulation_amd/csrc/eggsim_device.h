@@ -577,6 +577,28 @@ struct EggRxBodiesArgs {
     int32_t count;
 };
 
+// Collider contacts (egg_set_collider_contacts, DESIGN.md section 2.7, "Collider contacts"): egg_rx_contacts_kernel
+// (eggsim_relaxed_contacts.hip) runs once per sub-step of a step in which contacts act, one wave, directly behind
+// egg_rx_bodies_kernel on its stream, lane k = collider k.  It reads what the integrator has written and changes the
+// velocities, the spins and the turns of bodies only.  A record has the layout of the ABI's egg_collider_contact (16 bytes).
+#define EGG_RX_MAX_CONTACT_LANES 64  // = EGG_MAX_COLLIDERS: one wave holds the list
+struct EggContact {
+    double restitution;
+    int32_t on, reserved;
+};
+struct EggRxContactsArgs {
+    const EggCollider *list;             // [count]: the geometry of the sub-step's end
+    EggMotion *motions;                  // [count]
+    EggSpin *spins;                      // [count]: omega changes, the pivots stay
+    double2 *cs;                         // [count]: the turn of a free-turning body follows its new spin
+    const EggBody *bodies;               // [count]
+    const EggContact *contacts;          // [count]
+    unsigned long long *solves;          // [1]: the step's fires so far (zero at the step's start)
+    double h;                            // the sub-step
+    int32_t count;
+    int32_t iterations;                  // 1 .. 16
+};
+
 // Force fields (egg_set_forces, DESIGN.md section 2.7, "Forces"): the force instantiations of the kernels that begin a
 // sub-step (egg_rx_begin*_frc_kernel, egg_rx_mid*_frc_kernel) take these besides.  The list is the handle's, in a small
 // device buffer written when it is set; a record has the layout of the ABI's egg_force (40 bytes).

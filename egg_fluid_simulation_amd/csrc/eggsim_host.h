@@ -110,6 +110,7 @@ extern "C" __global__ void egg_rx_gather_group_col_load_kernel(EggRelaxedGroupCo
 extern "C" __global__ void egg_rx_gather_coh_col_load_kernel(EggRelaxedCohColLoadArgs A);
 extern "C" __global__ void egg_rx_gather_group_coh_col_load_kernel(EggRelaxedGroupCohColLoadArgs A);
 extern "C" __global__ void egg_rx_bodies_kernel(EggRxBodiesArgs A);
+extern "C" __global__ void egg_rx_contacts_kernel(EggRxContactsArgs A);
 extern "C" __global__ void egg_rx_begin_frc_kernel(EggRelaxedFrcArgs A);
 extern "C" __global__ void egg_rx_mid_frc_kernel(EggRelaxedFrcArgs A);
 extern "C" __global__ void egg_rx_begin_group_frc_kernel(EggRelaxedGroupFrcArgs A);
@@ -510,6 +511,18 @@ struct egg_handle {
     DevBuf<double2> d_body_cs;
     DevBuf<unsigned long long> d_body_seen;
     hipEvent_t body_ready = nullptr, body_done = nullptr;
+    // collider contacts (egg_set_collider_contacts; only where bodies act): the records as egg_get_collider_contacts returns
+    // them, empty = none; contacts_any = some record is on.  A step in which contacts act puts the records on the device and
+    // zeroes the word egg_rx_contacts_kernel counts the step's fires in; the commit adds that word to contact_solves.  The
+    // word lives beside the bodies' records, not in a type's status block: a handle without particles has no such block,
+    // and its bodies meet all the same.
+    std::vector<egg_collider_contact> contacts;
+    int32_t contact_iterations = 4;
+    bool contacts_any = false;
+    bool contacts_step = false;  // the step being committed had contacts acting: the commit reads the word back
+    int64_t contact_solves = 0;
+    DevBuf<EggContact> d_contacts;
+    DevBuf<unsigned long long> d_contact_solves;
     // force fields (egg_set_forces; relaxed order only): the list as egg_get_forces returns it and its copy on the device
     // (written when the list is set, never per step)
     std::vector<egg_force> forces;

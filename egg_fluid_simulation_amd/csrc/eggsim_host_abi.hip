@@ -971,6 +971,8 @@ int egg_set_option(egg_handle *h, int option, double value) {
                 return fail(h, EGG_ERR_INVALID_ARGUMENT, "solver order must be 0 (exact) or 1 (relaxed)");
             if (value == EGG_SOLVER_EXACT && h->opt_cohesion != EGG_COHESION_REFERENCE)
                 return fail(h, EGG_ERR_UNSUPPORTED, "exact order has no effective cohesion: switch cohesion off first (EGG_OPT_COHESION = 0)");
+            if (value == EGG_SOLVER_EXACT && h->contacts_any)
+                return fail(h, EGG_ERR_UNSUPPORTED, "exact order has no collider contacts: clear them first (egg_set_collider_contacts with n = 0)");
             if (value == EGG_SOLVER_EXACT && !h->colliders.empty())
                 return fail(h, EGG_ERR_UNSUPPORTED, "exact order has no colliders: clear the list first (egg_set_colliders with n = 0)");
             if (value == EGG_SOLVER_EXACT && !h->forces.empty())
@@ -1082,6 +1084,8 @@ int egg_set_colliders(egg_handle *h, int32_t n, const egg_collider *c) {
     h->load_sub_delta = 0.0;
     h->bodies.clear();  // (and no collider is a body)
     h->bodies_any = false;
+    h->contacts.clear();  // (and none meets another; the iterations and the counter stay)
+    h->contacts_any = false;
     return EGG_OK;
 }
 
@@ -1397,6 +1401,55 @@ int egg_get_collider_bodies(const egg_handle *h, int32_t cap, egg_collider_body 
     if (n) *n = have;
     for (int32_t k = 0; b && k < std::min(cap, have); ++k)
         b[k] = h->bodies.empty() ? egg_collider_body{0.0, 0.0, 0.0, 0.0, 0.0, 0.0} : h->bodies[(size_t)k];
+    return EGG_OK;
+}
+
+// Collider contacts ("Collider contacts"): one record per collider, or none (no collider meets
+// another).  Everything is checked before anything changes; the bodies and everything else about the list stay as they are.
+// Nothing goes to the device here: a step in which contacts act uploads the records it runs on.
+int egg_set_collider_contacts(egg_handle *h, int32_t n, const egg_collider_contact *c, int32_t iterations) {
+    if (!h) return EGG_ERR_INVALID_ARGUMENT;
+    REJECT_IN_FLIGHT(h, "egg_set_collider_contacts");
+    static_assert(sizeof(egg_collider_contact) == 16 && sizeof(EggContact) == sizeof(egg_collider_contact), "a contact record is 16 bytes");
+    if (n != 0 && n != (int32_t)h->colliders.size())
+        return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_collider_contacts: n = %d, the list holds %d colliders (n is that, or 0)", (int)n,
+                    (int)h->colliders.size());
+    if (n > 0 && !c) return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_collider_contacts: n = %d without records", (int)n);
+    if (iterations < 0 || iterations > 16)
+        return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_collider_contacts: %d iterations (1 .. 16, or 0 for the default of 4)", (int)iterations);
+    std::vector<egg_collider_contact> list((size_t)n);
+    bool any = false;
+    for (int32_t k = 0; k < n; ++k) {
+        egg_collider_contact &o = list[(size_t)k];
+        o = c[k];
+        if (!std::isfinite(o.restitution) || o.restitution < 0.0 || o.restitution > 1.0)
+            return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_collider_contacts: collider %d: the restitution %g lies outside [0, 1]", (int)k, o.restitution);
+        if (o.on != 0 && o.on != 1) return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_collider_contacts: collider %d: on = %d is not 0 or 1", (int)k, (int)o.on);
+        if (o.reserved != 0) return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_collider_contacts: collider %d: reserved = %d is not 0", (int)k, (int)o.reserved);
+        o.restitution = o.restitution + 0.0;  // (-0.0 is stored as +0.0)
+        any |= o.on != 0;
+    }
+    if (any && h->opt_solver_order != EGG_SOLVER_RELAXED)
+        return fail(h, EGG_ERR_UNSUPPORTED, "egg_set_collider_contacts: collider contacts need relaxed order (EGG_OPT_SOLVER_ORDER = 1 first)");
+    h->contacts.swap(list);
+    h->contacts_any = any;
+    h->contact_iterations = iterations == 0 ? 4 : iterations;
+    return EGG_OK;
+}
+
+int egg_get_collider_contacts(const egg_handle *h, int32_t cap, egg_collider_contact *out, int32_t *n, int32_t *iterations) {
+    if (!h) return EGG_ERR_INVALID_ARGUMENT;
+    const int32_t have = (int32_t)h->colliders.size();
+    if (n) *n = have;
+    if (iterations) *iterations = h->contact_iterations;
+    for (int32_t k = 0; out && k < std::min(cap, have); ++k) out[k] = h->contacts.empty() ? egg_collider_contact{0.0, 0, 0} : h->contacts[(size_t)k];
+    return EGG_OK;
+}
+
+int egg_get_collider_contact_solves(egg_handle *h, int64_t *solves) {
+    if (!h) return EGG_ERR_INVALID_ARGUMENT;
+    if (!solves) return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_get_collider_contact_solves: solves is NULL");
+    *solves = h->contact_solves;
     return EGG_OK;
 }
 

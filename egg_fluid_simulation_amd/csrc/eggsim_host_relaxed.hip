@@ -44,6 +44,11 @@
 // launch of egg_rx_bodies_kernel rewrites those records from the sums the sub-step has added.  relaxed_commit reads them
 // back in place of advance_colliders; a failed step puts the host's copies back.  With no body a step enqueues and launches
 // what it always did.
+// While collider contacts act besides (egg_set_collider_contacts: bodies act and some record is on) every launch of the
+// integrator is followed, on the same stream and inside the same bracket of events, by one launch of
+// egg_rx_contacts_kernel (eggsim_relaxed_contacts.hip), which changes the velocities, spins and turns the integrator has
+// left.  prepare_step uploads the contact records and zeroes the word the kernel counts its fires in; relaxed_commit adds
+// that word to the handle's counter.  While contacts do not act a step launches what it launched, with the same arguments.
 // With force fields (egg_set_forces, RelaxedLayout::forces) launch_substep picks the force instantiation of the begin / mid
 // kernel and RelaxedStep::frc carries the handle's list; with an empty list a step launches what it always launched.
 // With viscosity (egg_set_viscosity, RelaxedLayout::V) every sub-step of a type whose coefficient is not zero ends with
@@ -187,6 +192,9 @@ EggRelaxedArgs relaxed_args(egg_handle *h, int w, const Env &env) {
 // Collider bodies act in a relaxed step of a handle whose list is not empty, holds a body, and records loads.
 static bool bodies_act(const egg_handle *h) { return h->bodies_any && h->opt_loads && !h->colliders.empty(); }
 
+// Collider contacts act where bodies act and some contact record is on.
+static bool contacts_act(const egg_handle *h) { return bodies_act(h) && h->contacts_any; }
+
 // The records a step with bodies runs on, from the host's copies to the device: the list, and a surface, a motion and a
 // spin record for every collider, defaults and zeros included.  No step is running.
 static int upload_body_records(egg_handle *h) {
@@ -231,6 +239,17 @@ static int prepare_bodies(egg_handle *h, double sub_delta) {
     HIP_TRY(h, hipMemcpy(h->d_bodies.p, h->bodies.data(), n * sizeof(egg_collider_body), hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(h->d_body_cs.p, cs.data(), n * sizeof(double2), hipMemcpyHostToDevice));
     HIP_TRY(h, hipMemcpy(h->d_body_seen.p, none.data(), none.size() * 8, hipMemcpyHostToDevice));
+    return EGG_OK;
+}
+
+// Per step with contacts acting, after prepare_bodies: the contact records, and the step's fires start at zero.
+static int prepare_contacts(egg_handle *h) {
+    const size_t n = h->colliders.size();
+    const unsigned long long none = 0ull;
+    HIP_TRY(h, h->d_contacts.reserve(EGG_MAX_COLLIDERS, false, nullptr));
+    HIP_TRY(h, h->d_contact_solves.reserve(1, false, nullptr));
+    HIP_TRY(h, hipMemcpy(h->d_contacts.p, h->contacts.data(), n * sizeof(egg_collider_contact), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(h->d_contact_solves.p, &none, 8, hipMemcpyHostToDevice));
     return EGG_OK;
 }
 
@@ -284,7 +303,10 @@ int prepare_step(egg_handle *h, double delta, int S, RelaxedStep st[2]) {
             HIP_TRY(h, hipMemcpy(h->d_spins.p, h->spins.data(), n * sizeof(egg_collider_spin), hipMemcpyHostToDevice));
         }
     }
-    if (bodies_act(h)) return prepare_bodies(h, sub_delta);
+    if (bodies_act(h)) {
+        const int rc = prepare_bodies(h, sub_delta);
+        return rc == EGG_OK && contacts_act(h) ? prepare_contacts(h) : rc;
+    }
     return EGG_OK;
 }
 
@@ -809,6 +831,25 @@ static int launch_bodies(RelaxedStep &st) {
     return EGG_OK;
 }
 
+// The contacts of sub-step `sub`, directly behind its integrator on the same stream: no event of their own.
+static int launch_contacts(RelaxedStep &st) {
+    egg_handle *h = st.h;
+    EggRxContactsArgs k{};
+    k.list = h->d_colliders.p;
+    k.motions = h->d_motions.p;
+    k.spins = h->d_spins.p;
+    k.cs = h->d_body_cs.p;
+    k.bodies = h->d_bodies.p;
+    k.contacts = h->d_contacts.p;
+    k.solves = h->d_contact_solves.p;
+    k.h = st.env.sub_delta;
+    k.count = (int32_t)h->colliders.size();
+    k.iterations = h->contact_iterations;
+    hipLaunchKernelGGL(egg_rx_contacts_kernel, dim3(1), dim3(64), 0, h->sys[st.w].stream, k);
+    ++st.launches;
+    return EGG_OK;
+}
+
 // A step in which collider bodies act (st: after prepare_step, which has put the records on the device).  The gathers of
 // both types read the records the integrator writes, so the step is enqueued sub-step by sub-step across both types, with or
 // without coupling.  The integrator runs on the stream of the first populated type (`lead`), behind that type's launches of
@@ -840,6 +881,7 @@ static int relaxed_step_bodies(egg_handle *h, RelaxedStep st[2], int S, int C) {
     }
     const bool coupled = both && st[0].L.coupling;
     h->bodies_step = true;
+    h->contacts_step = contacts_act(h);
     if (h->opt_timing)
         for (int w = 0; w < 2; ++w)
             if (on[w]) HIP_TRY(h, hipEventRecord(h->sys[w].ev0, h->sys[w].stream));
@@ -863,6 +905,7 @@ static int relaxed_step_bodies(egg_handle *h, RelaxedStep st[2], int S, int C) {
         if (rc != EGG_OK) return rc;
         if (both) HIP_TRY(h, hipStreamWaitEvent(h->sys[lead].stream, h->body_ready, 0));
         rc = launch_bodies(st[lead]);
+        if (rc == EGG_OK && h->contacts_step) rc = launch_contacts(st[lead]);
         if (rc != EGG_OK) return rc;
         if (both) HIP_TRY(h, hipEventRecord(h->body_done, h->sys[lead].stream));
     }
@@ -878,7 +921,7 @@ static int relaxed_step_bodies(egg_handle *h, RelaxedStep st[2], int S, int C) {
 }
 
 int relaxed_step(egg_handle *h, double delta, int S, int C) {  // L:1722-1989, collision passes relaxed
-    h->bodies_step = false;
+    h->bodies_step = h->contacts_step = false;
     if (h->bodies_any && !h->colliders.empty() && !h->opt_loads)  // (before anything is launched or copied)
         return fail(h, EGG_ERR_UNSUPPORTED, "relaxed order: collider bodies are integrated from their loads (egg_set_collider_loads with on = 1 first, "
                                             "or egg_set_collider_bodies with n = 0)");
@@ -926,7 +969,7 @@ static int relaxed_finish(egg_handle *h, RelaxedStep st[2], int S, int C) {
     }
     if (bad) {  // nothing is committed: [cur] still holds the state before the step
         if (h->bodies_step) {  // ... and the records the integrator has rewritten are the host's untouched copies again
-            h->bodies_step = false;
+            h->bodies_step = h->contacts_step = false;  // (the fires of the failed step are never read)
             const int rc = upload_body_records(h);
             if (rc != EGG_OK) return rc;
         }
@@ -1010,6 +1053,16 @@ static void take_bodies(egg_handle *h) {
     }
 }
 
+// Collider contacts at the commit: the fires the step's launches of egg_rx_contacts_kernel have counted join the handle's
+// counter.  No step is running, as for take_bodies.
+static void take_contacts(egg_handle *h) {
+    unsigned long long fires = 0ull;
+    hipError_t e = hipSetDevice(h->device);
+    if (e == hipSuccess) e = hipMemcpy(&fires, h->d_contact_solves.p, 8, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) (void)fail(h, EGG_ERR_DEVICE, "relaxed order: the collider contacts' counter did not reach the host: %s", hipGetErrorString(e));
+    else h->contact_solves += (int64_t)fires;
+}
+
 // Collider loads at the commit: the step's sums, which both types' streams have added into, become the handle's.  No step
 // is running: every path waits for its streams before it commits, so one blocking copy sees every addition.
 static void take_loads(egg_handle *h, double sub_delta) {
@@ -1061,6 +1114,7 @@ void relaxed_commit(egg_handle *h, const RelaxedStep st[2], int S, int C, double
     // ways a commit advances the list, whether or not anything moves -- what last_x / last_y are for the particles
     h->colliders_last = h->colliders;
     if (h->bodies_step) take_bodies(h);
+    if (h->contacts_step) take_contacts(h);
     if ((h->motions_move || h->spins_turn) && !h->colliders.empty()) advance_colliders(h, (double)S * st[0].env.sub_delta, S);
     h->stats.last_step_kernel_ms = ms;
     if (h->opt_timing) {
@@ -1069,7 +1123,7 @@ void relaxed_commit(egg_handle *h, const RelaxedStep st[2], int S, int C, double
     }
     h->stats.steps++;
     h->stats.relaxed_steps++;
-    h->bodies_step = false;
+    h->bodies_step = h->contacts_step = false;
 }
 
 void leave_relaxed(egg_handle *h) {

@@ -148,6 +148,12 @@ int relaxed_group_step(egg_handle *const *hs, int nh, double delta, int S, int C
             return EGG_ERR_UNSUPPORTED;
         }
     }
+    for (int k = 0; k < nh; ++k) {  // (a contact changes a body, and bodies run on one handle)
+        if (hs[k]->contacts_any) {
+            *error = "relaxed order: collider contacts run on a single handle only (egg_set_collider_contacts with n = 0 first)";
+            return EGG_ERR_UNSUPPORTED;
+        }
+    }
     for (int k = 1; k < nh; ++k) {  // (with loads on the pivots count although nothing turns: the torque is about them)
         const std::vector<egg_collider_spin> &a = hs[0]->spins, &b = hs[k]->spins;
         const bool same_pivots = !hs[0]->opt_loads || hs[0]->spins_turn ||

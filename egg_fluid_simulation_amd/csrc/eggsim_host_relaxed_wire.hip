@@ -126,6 +126,8 @@ int egg_rx_begin(egg_handle *h, double delta, int32_t n_substeps, int32_t n_coll
         return fail(h, EGG_ERR_UNSUPPORTED, "egg_rx_begin: white-yolk adhesion runs on a single handle only (egg_set_adhesion with reach 0 first)");
     if (h->bodies_any)
         return fail(h, EGG_ERR_UNSUPPORTED, "egg_rx_begin: collider bodies run on a single handle only (egg_set_collider_bodies with n = 0 first)");
+    if (h->contacts_any)
+        return fail(h, EGG_ERR_UNSUPPORTED, "egg_rx_begin: collider contacts run on a single handle only (egg_set_collider_contacts with n = 0 first)");
     (void)hipSetDevice(h->device);
     WireStep &W = wire_of(h);
     const int S = n_substeps, C = n_collision_steps;

@@ -108,6 +108,10 @@ int egg_get_collider_loads(egg_handle *h, int32_t cap, egg_collider_load *out, i
 typedef struct { double inv_mass, inv_inertia, ax, ay, drag, spin_drag; } egg_collider_body;
 int egg_set_collider_bodies(egg_handle *h, int32_t n, const egg_collider_body *b);
 int egg_get_collider_bodies(const egg_handle *h, int32_t cap, egg_collider_body *b, int32_t *n);
+typedef struct { double restitution; int32_t on; int32_t reserved; } egg_collider_contact;
+int egg_set_collider_contacts(egg_handle *h, int32_t n, const egg_collider_contact *c, int32_t iterations);
+int egg_get_collider_contacts(const egg_handle *h, int32_t cap, egg_collider_contact *out, int32_t *n, int32_t *iterations);
+int egg_get_collider_contact_solves(egg_handle *h, int64_t *solves);
 typedef struct { float fill[4]; float line[4]; float line_width; int32_t layer; } egg_collider_style;
 int egg_set_collider_styles(egg_handle *h, int32_t n, const egg_collider_style *s);
 int egg_get_collider_styles(const egg_handle *h, int32_t cap, egg_collider_style *s, int32_t *n);
@@ -685,6 +689,48 @@ function SimulationHandler:get_collider_pose(alpha)
         out[k + 1] = c
     end
     return out
+end
+
+-- Not in the reference: collider contacts (egg_set_collider_contacts in include/eggsim.h; DESIGN.md section 2.7,
+-- "Collider contacts").
+
+--- one contact per collider of the current list: `false` for a collider that meets no other, `true` (restitution 0) or a
+--- restitution in [0, 1].  Where collider bodies act and some contact is on, every sub-step ends with `iterations`
+--- (1 .. 16, default 4) rounds that keep contact-enabled colliders -- a disc against a half-plane, disc, container, segment or
+--- wall -- from overlapping.  `{}` resets, and so does set_colliders.
+function SimulationHandler:set_collider_contacts(contacts, iterations)
+    local n = #contacts
+    local arr = ffi.new("egg_collider_contact[?]", math.max(n, 1))
+    for k = 1, n do  -- (not ipairs: a nil hole must not end the walk short of n)
+        local c = contacts[k]
+        if c == true then c = 0 end
+        if c ~= false and type(c) ~= "number" then
+            log.error("In SimulationHandler.set_collider_contacts: contact " .. k .. ": expected false, true or a restitution in [0, 1]")
+            return
+        end
+        if c ~= false then
+            arr[k - 1].restitution, arr[k - 1].on = c, 1
+        end
+    end
+    self:_check(lib.egg_set_collider_contacts(self._h, n, arr, iterations or 4))
+end
+
+--- the contacts as stored, one per collider (`false` where off, else the restitution), and the iterations
+function SimulationHandler:get_collider_contacts()
+    local arr, n, it = ffi.new("egg_collider_contact[?]", _max_colliders), ffi.new("int32_t[1]"), ffi.new("int32_t[1]")
+    if self:_check(lib.egg_get_collider_contacts(self._h, _max_colliders, arr, n, it)) ~= 0 then return {}, 4 end
+    local out = {}
+    for k = 0, n[0] - 1 do
+        if arr[k].on ~= 0 then out[k + 1] = arr[k].restitution else out[k + 1] = false end
+    end
+    return out, it[0]
+end
+
+--- the fires of collider contacts, one per (pair, sub-step, iteration), over committed steps
+function SimulationHandler:collider_contact_solves()
+    local out = ffi.new("int64_t[1]")
+    if self:_check(lib.egg_get_collider_contact_solves(self._h, out)) ~= 0 then return 0 end
+    return tonumber(out[0])
 end
 
 -- Not in the reference: collider loads (egg_set_collider_loads in include/eggsim.h; DESIGN.md section 2.7,

@@ -439,6 +439,48 @@ class _HandlerSurface:
         """one all-zero record per collider here, see set_collider_bodies"""
         return [(0.0, 0.0, 0.0, 0.0, 0.0, 0.0)] * len(self.get_colliders())
 
+    # ------------------------------------------------ collider contacts (egg_set_collider_contacts, DESIGN.md section 2.7)
+    _CONTACTS_LIMIT = ("collider contacts: a contact changes a collider body, and bodies run on a single SimulationHandler only; "
+                       "only lists with every contact off are accepted here")
+
+    @staticmethod
+    def _c_contacts(contacts, iterations=4):
+        """a list with one element per collider -- None (off), a restitution in [0, 1], or True (on, restitution 0) -- as an
+        egg_collider_contact array, and the iterations (1 .. 16, or 0 for the default); shape and range are checked here,
+        before any call into the library"""
+        contacts = list(contacts)
+        arr = (_ffi.EggColliderContact * max(len(contacts), 1))()
+        for k, c in enumerate(contacts):
+            if c is None:
+                continue
+            if c is True:
+                c = 0.0
+            if isinstance(c, bool) or not isinstance(c, (int, float)):
+                raise EggError("collider contact %d: expected None, True or a restitution in [0, 1], not %r" % (k, c))
+            c = float(c)
+            if not (math.isfinite(c) and 0.0 <= c <= 1.0):
+                raise EggError("collider contact %d: the restitution %r lies outside [0, 1]" % (k, c))
+            arr[k].restitution, arr[k].on = c, 1
+        if isinstance(iterations, bool) or not isinstance(iterations, int) or not 0 <= iterations <= 16:
+            raise EggError("collider contacts: iterations %r is not an integer in 1 .. 16 (or 0 for the default of 4)" % (iterations,))
+        return len(contacts), arr, iterations
+
+    def set_collider_contacts(self, contacts, iterations=4):
+        """SimulationHandler.set_collider_contacts where several handles share a step (SimulationGroup,
+        ShardedSimulationHandler): a list with every contact off is accepted and changes nothing, anything else raises EggError
+        naming the limit (after the checks of the records)."""
+        n, arr, _ = self._c_contacts(contacts, iterations)
+        if any(arr[k].on for k in range(n)):
+            raise EggError(self._CONTACTS_LIMIT)
+
+    def get_collider_contacts(self):
+        """every contact off here, see set_collider_contacts: `([None, ...], 4)`"""
+        return [None] * len(self.get_colliders()), 4
+
+    def collider_contact_solves(self):
+        """0 here, see set_collider_contacts"""
+        return 0
+
     # ------------------------------------------------ force fields (egg_set_forces, DESIGN.md section 2.7)
     @staticmethod
     def _c_forces(forces):
@@ -1067,6 +1109,32 @@ class SimulationHandler(_HandlerSurface):
         n = C.c_int32()
         self._check(self._c("get_collider_bodies")(_ffi.MAX_COLLIDERS, arr, C.byref(n)))
         return [(b.inv_mass, b.inv_inertia, b.ax, b.ay, b.drag, b.spin_drag) for b in arr[:n.value]]
+
+    def set_collider_contacts(self, contacts, iterations=4):
+        """One contact record per collider of the current list ("Collider contacts"): `None` for a
+        collider that meets no other, a restitution in [0, 1], or `True` (restitution 0).  Where collider bodies act and some
+        record is on, every sub-step ends with `iterations` (1 .. 16; 0 = the default, 4) rounds in which every pair of
+        contact-enabled colliders of which one is a disc -- against a half-plane, disc, container, segment or wall -- and one
+        a body takes the impulse that keeps the next sub-step's pose from overlapping; a pair bounces with the larger of its
+        two restitutions.  A free ball lands on a plate, two balls collide, a ball tips a hinged wall.  No friction between
+        bodies.  `[]` resets, and so does set_colliders; the bodies stay.  Raises EggError (nothing changes) for a length
+        that is not the collider count, a restitution outside [0, 1], iterations outside 0 .. 16, or a contact in exact
+        order."""
+        n, arr, iterations = self._c_contacts(contacts, iterations)  # (refused here before any device call)
+        self._check(self._c("set_collider_contacts")(n, arr, iterations))
+
+    def get_collider_contacts(self):
+        """`(contacts, iterations)`: the contacts as stored, one per collider -- `None` where off, else the restitution"""
+        arr = (_ffi.EggColliderContact * _ffi.MAX_COLLIDERS)()
+        n, iterations = C.c_int32(), C.c_int32()
+        self._check(self._c("get_collider_contacts")(_ffi.MAX_COLLIDERS, arr, C.byref(n), C.byref(iterations)))
+        return [c.restitution if c.on else None for c in arr[:n.value]], iterations.value
+
+    def collider_contact_solves(self):
+        """the fires of collider contacts, one per (pair, sub-step, iteration), over committed steps"""
+        out = C.c_int64()
+        self._check(self._c("get_collider_contact_solves")(C.byref(out)))
+        return out.value
 
     def set_coupling(self, factor=0.0, strength=1.0):
         """White-yolk coupling: one cross-type collision pass per sub-step of a relaxed step, before the sub-step's first

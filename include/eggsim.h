@@ -626,7 +626,7 @@ int egg_get_collider_loads(egg_handle *h, int32_t cap, egg_collider_load *out, i
  * to the step without bodies by roundings only, bit for bit at S = 1.  The commit reads the list, the motions and the spins
  * back: egg_get_colliders, egg_get_collider_motion and egg_get_collider_spin return them; the loads cover the whole step.
  * A failed step advances nothing.  The coupling is explicit: a body much lighter than what it touches may oscillate
- * (DESIGN.md has the measured range).  No body-body contact, no exact-order rule.  ONE handle only: a device group refuses
+ * (DESIGN.md has the measured range).  Bodies meet each other only through collider contacts (below); no exact-order rule.  ONE handle only: a device group refuses
  * to step and egg_rx_begin returns EGG_ERR_UNSUPPORTED while a handle holds a body.
  * egg_set_collider_bodies: n must equal the current collider count, or 0 (no collider is a body).  Everything is checked
  * before anything changes: EGG_ERR_INVALID_ARGUMENT, with the collider's index in the message, for an n that does not match,
@@ -641,6 +641,63 @@ typedef struct {
 int egg_set_collider_bodies(egg_handle *h, int32_t n, const egg_collider_body *b);
 /* the bodies as stored, one per collider (zeros included): the count in *n, min(*n, cap) records copied */
 int egg_get_collider_bodies(const egg_handle *h, int32_t cap, egg_collider_body *b, int32_t *n);
+
+/* ---- collider contacts: bodies that meet the other colliders ("Collider contacts") ----
+ * Every collider of the list may carry a CONTACT record {restitution, on, reserved}: restitution in [0, 1], on 0 or 1,
+ * reserved 0.  Contacts ACT in a step exactly when bodies act (above) and some record is on.  While they do not, a step
+ * launches exactly the kernels it launches today, with the same arguments -- a list with records on but no body, or with
+ * loads off, included.  While they act, every sub-step ends, behind step 4 of collider bodies and on what that step has
+ * written (the stored geometry and pivots of the sub-step's end, the new velocities and spins), with one more kernel.  FP64
+ * in exactly this order, no contraction, + - * / sqrt only, h the sub-step; every comparison is false for a NaN:
+ *   1. the generalised body: collider k has the weights mk = inv_mass, ik = inv_inertia (0 and 0 when it is no body) and at
+ *      a point p the velocity  ux = vx - omega * (py - Py), uy = vy + omega * (px - Px),  P its stored spin pivot
+ *   2. (a, b), a < b, is a PAIR when both are on, one is a disc, the other a half-plane, disc, container, segment or wall,
+ *      and ((ma + ia) + mb) + ib > 0.  From the stored poses: the unit normal n from a to b, the gap g (negative: overlap),
+ *      one contact point p.  Two discs meet along the centre line (coincident centres: DIRS[(b - a) & 7], the rule of
+ *      coincident particles), g = d - (Ra + Rb), p on a's rim; a half-plane along its normal; a container holds the disc
+ *      inside, g = (Rc - R) - d (coincident centres: DIRS likewise); a segment or wall at the closest point of the closed
+ *      segment, end points included (a centre exactly on it: the segment's left normal ((-ey) / l, ex / l)).  Both sides
+ *      evaluate one expression with a the smaller index.  Every other combination is no pair.
+ *   3. one Jacobi iteration with constraint averaging, every pair from the velocities of the iteration's start:
+ *        vn = nx * (ubx - uax) + ny * (uby - uay);  ca = (px - Pax) * ny - (py - Pay) * nx;  wa = ma + ia * (ca * ca);
+ *        cb, wb likewise;  w = wa + wb.  A container with m = Rc - R > 0 first bends its gap to the wall -- a centre that
+ *        slides h vt along a circle leaves it by (h vt)^2 / (2 d) although g + h vn says it stays --: with the velocities
+ *        of the disc at its centre and of the container at its centre, o the unit vector from the one to the other,
+ *        vt = ox * (udy - ucy) - oy * (udx - ucx);  s = h * vt;  q2 = m * m - s * s;  q2 < 0: q2 = 0;  g = sqrt(q2) - d
+ *        (which is (Rc - R) - d when nothing slides).  The pair FIRES when w > 0 and g + h * vn < 0 (speculative: what would overlap
+ *        at the next sub-step's pose), and then
+ *        e = max(ea, eb);  t1 = (-g) / h;  t2 = -(e * vn);  target = t1 > t2 ? t1 : t2;  lam = (target - vn) / w
+ *      b takes the impulse lam n at p, a takes -(lam n).  Collider k sums its impulses J over its partners in ascending
+ *      index (sx, sy, and sz = sz + ((px - Pkx) * Jy - (py - Pky) * Jx)), and with count fired pairs, count > 0:
+ *        mk > 0: vx = vx + (sx * mk) / count (y likewise);   ik > 0: omega = omega + (sz * ik) / count
+ *   4. `iterations` of these, each from the one before; then a collider with ik > 0 recomputes its turn (c, s) from the
+ *      new omega with the four lines of the integrator.
+ * tests/contact_model.py is the definition; the device equals it bit for bit.  Contacts change velocities, spins and turns
+ * only -- no particle, no load sum, no geometry --, so the commit, the read-back and a failed step are those of bodies.
+ * The limits: no friction between bodies (a ball slides on a tilted plate); no pair without a disc; explicit and averaged,
+ * so stacks are soft (DESIGN.md has the measured overlaps); a collider with both weights 0 is never moved and is a
+ * kinematic partner; the pivot of a body rides with it only while its omega != 0 (step 2 of collider bodies), so a free
+ * ball wants a spin, however small.  With e = 0 a body that would cross a partner within the sub-step is stopped where it
+ * is and closes the rest in later sub-steps; it never arrives overlapped, and one that starts overlapped is pushed out in
+ * one sub-step.  ONE handle only, as bodies: a device group refuses to step and egg_rx_begin returns EGG_ERR_UNSUPPORTED
+ * while a handle holds a record that is on; exact order refuses such a list (EGG_ERR_UNSUPPORTED), and EGG_OPT_SOLVER_ORDER
+ * refuses exact order while one is set.
+ * egg_set_collider_contacts: n must equal the current collider count, or 0 (no collider meets another); iterations is
+ * 1 .. 16, or 0 for the default of 4.  Everything is checked before anything changes: EGG_ERR_INVALID_ARGUMENT for an n that
+ * does not match, a restitution that is not finite or outside [0, 1], an on that is not 0 or 1, a reserved that is not 0, or
+ * iterations outside 0 .. 16.  egg_set_colliders with another list clears the records, as it clears the bodies.  Refused
+ * while a step is in flight.
+ * egg_get_collider_contact_solves: the fires, one per (pair, sub-step, iteration), over committed steps; a failed step adds
+ * nothing. */
+typedef struct {
+    double restitution; /* 0 .. 1; a pair takes the larger of its two */
+    int32_t on;         /* 0 or 1 */
+    int32_t reserved;   /* 0 */
+} egg_collider_contact; /* 16 bytes */
+int egg_set_collider_contacts(egg_handle *h, int32_t n, const egg_collider_contact *c, int32_t iterations);
+/* the records as stored, one per collider (off included): the count in *n, min(*n, cap) records copied, the iterations */
+int egg_get_collider_contacts(const egg_handle *h, int32_t cap, egg_collider_contact *out, int32_t *n, int32_t *iterations);
+int egg_get_collider_contact_solves(egg_handle *h, int64_t *solves);
 
 /* ---- collider pose and collider styles: colliders in the picture ("Collider styles") ----
  * Not in the reference, which has no colliders and so draws none.
