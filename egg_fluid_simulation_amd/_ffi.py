@@ -162,6 +162,24 @@ FORCE_PARAMS = (("gx", "gy"), ("cx", "cy", "strength", "R"), ("cx", "cy", "stren
 FORCE_TYPES = COLLIDER_TYPES  # type_mask
 
 
+class EggSensor(C.Structure):  # egg_sensor: a region whose particles a read counts and locates (56 bytes)
+    _fields_ = [("kind", C.c_int32), ("type_mask", C.c_int32), ("p", C.c_double * 6)]
+
+
+class EggSensorReading(C.Structure):  # egg_sensor_reading: int64 count and quantised position sums, [0] white, [1] yolk (48 bytes)
+    _fields_ = [("count", C.c_int64 * 2), ("sx", C.c_int64 * 2), ("sy", C.c_int64 * 2)]
+
+
+MAX_SENSORS = 64  # EGG_MAX_SENSORS
+SENSOR_POSITION_SCALE = 65536.0  # EGG_SENSOR_POSITION_SCALE, 2^16
+SENSOR_HALF_PLANE, SENSOR_DISC, SENSOR_BOX, SENSOR_CAPSULE = 0, 1, 2, 3
+SENSOR_KINDS = ("half_plane", "disc", "box", "capsule")  # by EGG_SENSOR_* value
+# the parameters as stored; the wrappers also take a box as (cx, cy, hx, hy, angle) and convert with the host's cos / sin
+SENSOR_PARAMS = (("nx", "ny", "off"), ("cx", "cy", "R"), ("cx", "cy", "hx", "hy", "ux", "uy"), ("x0", "y0", "x1", "y1", "R"))
+SENSOR_CODES = {n: i for i, n in enumerate(SENSOR_KINDS)}
+SENSOR_TYPES = COLLIDER_TYPES  # type_mask
+
+
 class EggRxBox(C.Structure):  # egg_rx_box: a cell box of the relaxed halo between processes
     _fields_ = [("lo_x", C.c_int32), ("lo_y", C.c_int32), ("hi_x", C.c_int32), ("hi_y", C.c_int32), ("empty", C.c_int32)]
 
@@ -247,6 +265,14 @@ _SIGNATURES = {
     "egg_group_get_collider_load_sums": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double),
                                                    C.POINTER(C.c_int32)]),
     "egg_group_get_collider_loads": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggColliderLoad), C.POINTER(C.c_int32)]),
+    "egg_set_sensors": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggSensor)]),
+    "egg_get_sensors": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggSensor), C.POINTER(C.c_int32)]),
+    "egg_read_sensors": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggSensorReading), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    "egg_read_sensor_batches": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "egg_group_set_sensors": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggSensor)]),
+    "egg_group_get_sensors": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggSensor), C.POINTER(C.c_int32)]),
+    "egg_group_read_sensors": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggSensorReading), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    "egg_group_read_sensor_batches": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "egg_group_set_collider_surfaces": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggColliderSurface)]),
     "egg_group_get_collider_surfaces": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggColliderSurface), C.POINTER(C.c_int32)]),
     "egg_group_get_collider_grips": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),

@@ -849,3 +849,46 @@ struct EggInstanceArgs {
     const float4 *atom_color;     // [n_atoms] the rgba an atom's particles carry
     int32_t n, n_atoms;
 };
+
+// ---------------------------------------------------------------------------------------------
+// Sensors (eggsim_sensors.hip; include/eggsim.h, "sensors"): which committed positions lie inside
+// the handle's regions.  A UNIT is at most EGG_SN_UNIT consecutive particles of ONE atom; one wave takes a unit at a time,
+// a lane a particle of a chunk of 64, and lane k keeps sensor k's sums.  Nothing here is read or written by a step.
+#define EGG_SN_MAX_SENSORS 64        // = EGG_MAX_SENSORS: one lane of a wave per sensor
+#define EGG_SN_UNIT 1024
+#define EGG_SN_SCALE 0x1p16          // = EGG_SENSOR_POSITION_SCALE
+#define EGG_SN_LIMIT 0x1p53          // a scaled coordinate that reaches it (or is not finite) drops the particle
+#define EGG_SN_HALF_PLANE 0
+#define EGG_SN_DISC 1
+#define EGG_SN_BOX 2
+#define EGG_SN_CAPSULE 3
+#define EGG_SN_ROWS 7                // words lane k of a wave leaves: count, sx, sy of white, of yolk; row 6: dropped[lane], lanes 0 and 1
+#define EGG_SN_FINISH_THREADS 1024
+struct EggSensor {  // egg_sensor
+    int32_t kind, type_mask;
+    double p[6];
+};
+struct EggSensorUnit {
+    int32_t offset, count;  // particles [offset, offset + count) of the type's arrays, count in 1 .. EGG_SN_UNIT
+    int32_t type;           // 0 white, 1 yolk
+    int32_t reserved;
+};
+struct EggSensorArgs {
+    const double *x[2], *y[2];        // the committed positions per type
+    const EggSensor *sensors;
+    const EggSensorUnit *units;
+    int32_t n_sensors, n_units;
+    long long *partials;              // totals: [waves][EGG_SN_ROWS][64]
+    int32_t *unit_counts;             // per batch: [n_units][64], lane k the unit's count in sensor k
+};
+struct EggSensorFinishArgs {  // a workgroup per row adds the waves' partials: out[row * 64 + k], row 6 the dropped pair
+    const long long *partials;
+    int32_t n_waves, n_sensors;
+    long long *out;                   // [EGG_SN_ROWS][64]
+};
+struct EggSensorBatchFinishArgs {  // counts[(i * n_sensors + k) * 2 + w] = sum of the units of row r = 2 i + w
+    const int32_t *unit_counts;
+    const int32_t *row_first, *row_units;  // [n_rows]: the units of (listed id, type), none for a type nothing covers
+    int32_t n_rows, n_sensors;
+    int32_t *counts;
+};

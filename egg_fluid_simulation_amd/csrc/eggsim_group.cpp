@@ -68,6 +68,7 @@ struct egg_group {
     std::vector<egg_collider_motion> motions;    // egg_group_set_collider_motion: every handle's records, as given
     std::vector<egg_collider_spin> spins;        // egg_group_set_collider_spin: every handle's records, as given
     std::vector<egg_collider_style> styles;      // egg_group_set_collider_styles: every handle's records, as given
+    std::vector<egg_sensor> sensors;             // egg_group_set_sensors: every handle's list, as given
     std::vector<egg_force> forces;          // egg_group_set_forces: every handle's list, as given
     double viscosity[2] = {0.0, 0.0};       // egg_group_set_viscosity: every handle's coefficients
     double containment[2] = {0.0, 1.0};     // egg_group_set_containment: every handle's (factor, strength)
@@ -815,6 +816,90 @@ int egg_group_get_collider_loads(egg_group *g, int32_t cap, egg_collider_load *o
         out[k].jx = any ? ((double)sums[(size_t)(3 * k)] / EGG_COLLIDER_LOAD_IMPULSE_SCALE) / hs : 0.0;
         out[k].jy = any ? ((double)sums[(size_t)(3 * k + 1)] / EGG_COLLIDER_LOAD_IMPULSE_SCALE) / hs : 0.0;
         out[k].torque = any ? ((double)sums[(size_t)(3 * k + 2)] / EGG_COLLIDER_LOAD_TORQUE_SCALE) / hs : 0.0;
+    }
+    return EGG_OK;
+}
+
+// Sensors (include/eggsim.h, "sensors"): every handle holds the same list and measures the particles it owns.
+int egg_group_set_sensors(egg_group *g, int32_t n, const egg_sensor *sensors) {
+    if (!g) return EGG_ERR_INVALID_ARGUMENT;
+    for (size_t k = 0; k < g->h.size(); ++k) {
+        const int rc = egg_set_sensors(g->h[k], n, sensors);
+        if (rc < 0) {  // (handle 0 refuses a bad list before any handle has changed; a later one: the others go back)
+            for (size_t j = 0; j < k; ++j) (void)egg_set_sensors(g->h[j], (int32_t)g->sensors.size(), g->sensors.data());
+            return gfail(g, rc, "device %d: %s", (int)k, egg_last_error(g->h[k]));
+        }
+    }
+    g->sensors.assign(sensors, sensors + (n > 0 ? n : 0));
+    return EGG_OK;
+}
+
+int egg_group_get_sensors(const egg_group *g, int32_t cap, egg_sensor *out, int32_t *n) {
+    if (!g || g->h.empty()) return EGG_ERR_INVALID_ARGUMENT;
+    return egg_get_sensors(g->h[0], cap, out, n);  // (as stored: every handle holds the same list)
+}
+
+// the readings and the dropped pair added over the handles (two's complement: the sum of the handles' sums is the sum over
+// all their particles)
+int egg_group_read_sensors(egg_group *g, int32_t cap, egg_sensor_reading *readings, int64_t dropped[2], int32_t *n) {
+    if (!g || g->h.empty()) return EGG_ERR_INVALID_ARGUMENT;
+    int32_t have = 0;
+    (void)egg_get_sensors(g->h[0], 0, nullptr, &have);
+    std::vector<uint64_t> total(6 * (size_t)have, 0);
+    std::vector<egg_sensor_reading> one((size_t)have);
+    int64_t lost[2] = {0, 0};
+    for (size_t k = 0; k < g->h.size(); ++k) {
+        int64_t d[2] = {0, 0};
+        int32_t m = 0;
+        const int rc = egg_read_sensors(g->h[k], have, one.data(), d, &m);
+        if (rc < 0) return gfail(g, rc, "device %d: %s", (int)k, egg_last_error(g->h[k]));
+        for (size_t q = 0; q < (size_t)std::min(have, m); ++q)
+            for (int w = 0; w < 2; ++w) {
+                total[6 * q + 0 + (size_t)w] += (uint64_t)one[q].count[w];
+                total[6 * q + 2 + (size_t)w] += (uint64_t)one[q].sx[w];
+                total[6 * q + 4 + (size_t)w] += (uint64_t)one[q].sy[w];
+            }
+        lost[0] += d[0];
+        lost[1] += d[1];
+    }
+    if (n) *n = have;
+    for (size_t q = 0; readings && q < (size_t)std::min(std::max(cap, 0), have); ++q)
+        for (int w = 0; w < 2; ++w) {
+            readings[q].count[w] = (int64_t)total[6 * q + 0 + (size_t)w];
+            readings[q].sx[w] = (int64_t)total[6 * q + 2 + (size_t)w];
+            readings[q].sy[w] = (int64_t)total[6 * q + 4 + (size_t)w];
+        }
+    if (dropped) {
+        dropped[0] = lost[0];
+        dropped[1] = lost[1];
+    }
+    return EGG_OK;
+}
+
+// a batch is answered by the handle that owns it: one call per handle over the ids it holds, scattered into the caller's order
+int egg_group_read_sensor_batches(egg_group *g, int64_t n_ids, const int64_t *ids, int32_t *counts) {
+    if (!g || g->h.empty() || n_ids < 0 || (n_ids > 0 && !ids)) return EGG_ERR_INVALID_ARGUMENT;
+    for (int64_t i = 0; i < n_ids; ++i)  // (before anything is written)
+        if (ids[i] < 1 || ids[i] > (int64_t)g->batch.size() || !g->batch[(size_t)ids[i] - 1].alive)
+            return gfail(g, EGG_ERR_UNKNOWN_ID, "egg_group_read_sensor_batches: no batch with id `%lld`", (long long)ids[i]);
+    int32_t have = 0;
+    (void)egg_get_sensors(g->h[0], 0, nullptr, &have);
+    if (n_ids == 0 || have == 0) return EGG_OK;
+    if (!counts) return gfail(g, EGG_ERR_INVALID_ARGUMENT, "egg_group_read_sensor_batches: counts is NULL");
+    const size_t row = 2 * (size_t)have;
+    for (size_t k = 0; k < g->h.size(); ++k) {
+        std::vector<int64_t> local, where;
+        for (int64_t i = 0; i < n_ids; ++i) {
+            const egg_group::Rec &r = g->batch[(size_t)ids[i] - 1];
+            if (r.owner != (int)k) continue;
+            local.push_back(r.local);
+            where.push_back(i);
+        }
+        if (local.empty()) continue;
+        std::vector<int32_t> part(local.size() * row, 0);
+        const int rc = egg_read_sensor_batches(g->h[k], (int64_t)local.size(), local.data(), part.data());
+        if (rc < 0) return gfail(g, rc, "device %d: %s", (int)k, egg_last_error(g->h[k]));
+        for (size_t q = 0; q < local.size(); ++q) memcpy(counts + (size_t)where[q] * row, part.data() + q * row, row * sizeof(int32_t));
     }
     return EGG_OK;
 }

@@ -14,6 +14,7 @@
 //   eggsim_host_render_group.hip   draw / environment / download of a device group: gather to one device (eggsim_render_group.hip)
 //   eggsim_host_draw_source.hip    the same for a scene sharded over processes: egg_draw_pack on every rank, egg_draw_source_* on one
 //   eggsim_host_instances.hip      egg_get_instances / egg_instances_begin / _end: the instanced-draw record packed on the device
+//   eggsim_host_sensors.hip        egg_set_sensors / egg_read_sensors / egg_read_sensor_batches: the list, the unit tables, the launches
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -134,6 +135,10 @@ extern "C" __global__ void egg_rx_wire_unpack_kernel(EggRxWireUnpackArgs U);
 extern "C" __global__ void egg_group_gather_kernel(EggGatherArgs A);
 extern "C" __global__ void egg_draw_pack_kernel(EggDrawPackArgs A);
 extern "C" __global__ void egg_instances_kernel(EggInstanceArgs A);
+extern "C" __global__ void egg_sensor_sums_kernel(EggSensorArgs A);
+extern "C" __global__ void egg_sensor_units_kernel(EggSensorArgs A);
+extern "C" __global__ void egg_sensor_finish_kernel(EggSensorFinishArgs A);
+extern "C" __global__ void egg_sensor_batch_finish_kernel(EggSensorBatchFinishArgs A);
 extern "C" __global__ void egg_render_count_kernel(EggRenderArgs A);
 extern "C" __global__ void egg_render_fill_kernel(EggRenderArgs A);
 extern "C" __global__ void egg_render_scan_kernel(EggRenderArgs A);
@@ -407,6 +412,7 @@ namespace egghost {
 struct WireStep;  // a relaxed step in flight between egg_rx_begin and egg_rx_end (eggsim_host_relaxed_wire.hip)
 struct DrawSource;  // particles placed by egg_draw_source_place, their canvases and scratch (eggsim_host_draw_source.hip)
 struct InstanceState;  // staging and pinned buffers of egg_get_instances / egg_instances_begin (eggsim_host_instances.hip)
+struct SensorState;  // device copy of the sensor list, unit tables and partials of a read (eggsim_host_sensors.hip)
 }
 using namespace egghost;
 
@@ -569,6 +575,10 @@ struct egg_handle {
     // re-uploads its colour mesh only when this has moved)
     uint64_t color_version = 1;
     std::shared_ptr<egghost::InstanceState> instances;  // allocated by the first egg_get_instances / egg_instances_begin
+    // sensors (egg_set_sensors; either solver order): the list as egg_get_sensors returns it, and what a read needs on the
+    // device, allocated when a list is first set.  No step reads either.
+    std::vector<egg_sensor> sensors;
+    std::shared_ptr<egghost::SensorState> sensor_state;
     // headless renderer (eggsim_render.hip)
     struct Render {
         egg_render_config cfg[2];

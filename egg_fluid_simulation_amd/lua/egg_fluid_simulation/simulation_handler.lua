@@ -116,6 +116,12 @@ typedef struct { float fill[4]; float line[4]; float line_width; int32_t layer; 
 int egg_set_collider_styles(egg_handle *h, int32_t n, const egg_collider_style *s);
 int egg_get_collider_styles(const egg_handle *h, int32_t cap, egg_collider_style *s, int32_t *n);
 int egg_get_collider_pose(egg_handle *h, double alpha, int32_t cap, egg_collider *c, int32_t *n);
+typedef struct { int32_t kind; int32_t type_mask; double p[6]; } egg_sensor;
+typedef struct { int64_t count[2], sx[2], sy[2]; } egg_sensor_reading;
+int egg_set_sensors(egg_handle *h, int32_t n, const egg_sensor *sensors);
+int egg_get_sensors(const egg_handle *h, int32_t cap, egg_sensor *out, int32_t *n);
+int egg_read_sensors(egg_handle *h, int32_t cap, egg_sensor_reading *readings, int64_t dropped[2], int32_t *n);
+int egg_read_sensor_batches(egg_handle *h, int64_t n_ids, const int64_t *ids, int32_t *counts);
 typedef struct egg_group egg_group;
 int egg_group_set_solver_order(egg_group *g, int32_t order, double relaxation);
 int egg_group_set_cohesion(egg_group *g, int32_t mode);
@@ -767,6 +773,109 @@ function SimulationHandler:collider_load_sums()
     local out = {}
     for k = 0, n[0] - 1 do out[k + 1] = { arr[3 * k], arr[3 * k + 1], arr[3 * k + 2] } end
     return out, dropped[0], h[0]
+end
+
+-- Not in the reference: sensors (egg_set_sensors in include/eggsim.h; DESIGN.md section 2.8).  Regions that count and
+-- locate the particles whose centres lie inside them, from the committed positions; either solver order.  They only
+-- observe: a step launches what it launches without them.
+local _sensor_kinds = { half_plane = 0, disc = 1, box = 2, capsule = 3 }
+local _sensor_names = { [0] = "half_plane", "disc", "box", "capsule" }
+local _sensor_n_params = { [0] = 3, 3, 6, 5 }
+local _max_sensors = 64 -- EGG_MAX_SENSORS
+local _sensor_scale = 65536 -- EGG_SENSOR_POSITION_SCALE
+
+--- the ordered list of at most 64 sensors, each `{ "half_plane", nx, ny, off }` (the side the normal points to),
+--- `{ "disc", cx, cy, R }`, `{ "box", cx, cy, hx, hy, angle }` (or `hx, hy, ux, uy` with the first axis),
+--- `{ "capsule", x0, y0, x1, y1, R }`, with an optional `types = "both" | "white" | "yolk"`.  `{}` clears the list.
+function SimulationHandler:set_sensors(sensors)
+    local n = #sensors
+    if n > _max_sensors then
+        log.error("In SimulationHandler.set_sensors: a list holds 0 .. 64 sensors")
+        return
+    end
+    local arr = ffi.new("egg_sensor[?]", math.max(n, 1))
+    for k, s in ipairs(sensors) do
+        local kind = _sensor_kinds[s[1]]
+        local mask = _collider_types[s.types or "both"]
+        local by_angle = kind == 2 and #s == 6
+        if kind == nil or mask == nil or (#s ~= 1 + _sensor_n_params[kind] and not by_angle) then
+            log.error("In SimulationHandler.set_sensors: sensor " .. k .. ": expected { kind, parameters..., types = ... }")
+            return
+        end
+        arr[k - 1].kind, arr[k - 1].type_mask = kind, mask
+        if by_angle then -- the host's cos / sin, as spin does
+            for q = 1, 4 do arr[k - 1].p[q - 1] = s[q + 1] end
+            arr[k - 1].p[4], arr[k - 1].p[5] = math.cos(s[6]), math.sin(s[6])
+        else
+            for q = 1, _sensor_n_params[kind] do arr[k - 1].p[q - 1] = s[q + 1] end
+        end
+    end
+    self:_check(lib.egg_set_sensors(self._h, n, arr))
+end
+
+--- the list as stored, in the shapes set_sensors takes: normals and box axes normalised, a box with its axis
+function SimulationHandler:get_sensors()
+    local arr, n = ffi.new("egg_sensor[?]", _max_sensors), ffi.new("int32_t[1]")
+    if self:_check(lib.egg_get_sensors(self._h, _max_sensors, arr, n)) ~= 0 then return {} end
+    local out = {}
+    for k = 0, n[0] - 1 do
+        local s = { _sensor_names[arr[k].kind], types = _collider_type_names[arr[k].type_mask] }
+        for q = 1, _sensor_n_params[arr[k].kind] do s[q + 1] = arr[k].p[q - 1] end
+        out[k + 1] = s
+    end
+    return out
+end
+
+--- the raw integers of the positions as committed now: `{ { white = { count, sx, sy }, yolk = { count, sx, sy } }, ... }`
+--- as int64 cdata (sx, sy scaled by 2^16), and `{ white, yolk }` dropped.  Every call measures.
+function SimulationHandler:sensor_sums()
+    local arr, n = ffi.new("egg_sensor_reading[?]", _max_sensors), ffi.new("int32_t[1]")
+    local dropped = ffi.new("int64_t[2]")
+    if self:_check(lib.egg_read_sensors(self._h, _max_sensors, arr, dropped, n)) ~= 0 then return {}, { 0, 0 } end
+    local out = {}
+    for k = 0, n[0] - 1 do
+        out[k + 1] = { white = { arr[k].count[0], arr[k].sx[0], arr[k].sy[0] }, yolk = { arr[k].count[1], arr[k].sx[1], arr[k].sy[1] } }
+    end
+    return out, { dropped[0], dropped[1] }
+end
+
+--- per sensor `{ white = { count = n, x = cx, y = cy }, yolk = { ... } }`: the particles inside and their centroid,
+--- `(sx / 2^16) / count`; x and y are nil while the count is 0
+function SimulationHandler:sensors()
+    local sums = self:sensor_sums()
+    local out = {}
+    for k, rec in ipairs(sums) do
+        local one = {}
+        for _, name in ipairs({ "white", "yolk" }) do
+            local count = tonumber(rec[name][1])
+            one[name] = { count = count }
+            if count > 0 then
+                one[name].x = (tonumber(rec[name][2]) / _sensor_scale) / count
+                one[name].y = (tonumber(rec[name][3]) / _sensor_scale) / count
+            end
+        end
+        out[k] = one
+    end
+    return out
+end
+
+--- the counts only, per listed batch: `out[i][k] = { white, yolk }` for id i of `ids` and sensor k; an id may repeat
+function SimulationHandler:sensor_batches(ids)
+    local n_ids = #ids
+    local n = ffi.new("int32_t[1]")
+    if self:_check(lib.egg_get_sensors(self._h, 0, nil, n)) ~= 0 then return {} end
+    local c_ids = ffi.new("int64_t[?]", math.max(n_ids, 1))
+    for i, id in ipairs(ids) do c_ids[i - 1] = id end
+    local counts = ffi.new("int32_t[?]", math.max(n_ids * n[0] * 2, 1))
+    if self:_check(lib.egg_read_sensor_batches(self._h, n_ids, c_ids, counts)) ~= 0 then return {} end
+    local out = {}
+    for i = 0, n_ids - 1 do
+        out[i + 1] = {}
+        for k = 0, n[0] - 1 do
+            out[i + 1][k + 1] = { counts[(i * n[0] + k) * 2], counts[(i * n[0] + k) * 2 + 1] }
+        end
+    end
+    return out
 end
 
 -- Not in the reference, which has no forces as it has no boundary: force fields of the relaxed step (egg_set_forces in

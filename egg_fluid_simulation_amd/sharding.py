@@ -691,6 +691,46 @@ class ShardedSimulationHandler(_HandlerSurface):
         si, st = _ffi.COLLIDER_LOAD_IMPULSE_SCALE, _ffi.COLLIDER_LOAD_TORQUE_SCALE
         return [((float(sx) / si) / h, (float(sy) / si) / h, (float(sz) / st) / h) for sx, sy, sz in sums]
 
+    def set_sensors(self, sensors):
+        """SimulationHandler.set_sensors on every rank alike (the same call on every rank; either solver order).  Nothing
+        travels in a step: every rank measures the particles it owns, when a read asks."""
+        self.local.set_sensors(sensors)
+
+    def get_sensors(self):
+        return self.local.get_sensors()
+
+    def sensor_sums(self):
+        """SimulationHandler.sensor_sums with the integers and the dropped pair added over the ranks (a collective: every
+        rank calls it; one all_reduce of an int64 tensor).  Integer addition has no order, so the result equals one
+        handle's bit for bit."""
+        sums, dropped = self.local.sensor_sums()
+        flat = [v for per_type in sums for rec in per_type for v in rec] + list(dropped)
+        tot = self.torch.tensor(flat, dtype=self.torch.int64, device=self.device)
+        self.dist.all_reduce(tot, op=self.dist.ReduceOp.SUM)
+        flat = [int(v) for v in tot.tolist()]
+        return [(tuple(flat[6 * k:6 * k + 3]), tuple(flat[6 * k + 3:6 * k + 6])) for k in range(len(sums))], flat[-2:]
+
+    def sensors(self):
+        """SimulationHandler.sensors over all ranks (a collective): the summed integers, converted here with the library's
+        two divisions"""
+        return self._sensor_readings(self.sensor_sums()[0])
+
+    def sensor_batches(self, ids):
+        """SimulationHandler.sensor_batches over all ranks (a collective: every rank calls it with the same ids): every rank
+        fills in the batches it holds and zeros elsewhere, one all_reduce of an int64 tensor adds them"""
+        ids = [int(i) for i in ids]
+        for gid in ids:
+            if gid not in self.owner:
+                raise EggError("[ERROR] In SimulationHandler.sensor_batches: no batch with id `%d`" % gid)
+        n_sensors = len(self.local.get_sensors())
+        out = np.zeros((len(ids), n_sensors, 2), dtype=np.int64)
+        mine = [k for k, gid in enumerate(ids) if gid in self.local_id]
+        if mine and n_sensors:
+            out[mine] = self.local.sensor_batches([self.local_id[ids[k]] for k in mine])
+        tot = self.torch.from_numpy(out).to(self.device)
+        self.dist.all_reduce(tot, op=self.dist.ReduceOp.SUM)
+        return tot.cpu().numpy().astype(np.int32)
+
     def set_forces(self, forces):
         """SimulationHandler.set_forces on every rank alike (the same call on every rank; relaxed order only).  Nothing
         new travels: every rank accelerates the particles it owns."""

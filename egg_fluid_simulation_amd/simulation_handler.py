@@ -396,8 +396,112 @@ class _HandlerSurface:
         self._check(self._c("get_collider_loads")(_ffi.MAX_COLLIDERS, arr, C.byref(n)))
         return [(ld.jx, ld.jy, ld.torque) for ld in arr[:n.value]]
 
+    # ------------------------------------------------ sensors (egg_set_sensors)
+    @staticmethod
+    def _c_sensors(sensors):
+        """a list of tuples `(kind, parameters...[, types])` or dicts `{"kind": ..., <parameter names>, "types": ...}` as an
+        egg_sensor array.  A box takes its first axis `ux, uy` or, one value shorter, an `angle` in radians that the host's
+        cos / sin convert.  What only the host can check (shape, names) is checked here, the values by the library."""
+        sensors = list(sensors)
+        if len(sensors) > _ffi.MAX_SENSORS:
+            raise EggError("sensors: a list holds 0 .. %d sensors, not %d" % (_ffi.MAX_SENSORS, len(sensors)))
+        arr = (_ffi.EggSensor * max(len(sensors), 1))()
+        for k, s in enumerate(sensors):
+            if isinstance(s, dict):
+                kind, types = s.get("kind"), s.get("types", "both")
+            else:
+                s = tuple(s)
+                kind = s[0] if s else None
+                types = "both"
+            if not isinstance(kind, str) or kind not in _ffi.SENSOR_CODES:
+                raise EggError("sensor %d: kind must be one of %s, not %r" % (k, ", ".join(_ffi.SENSOR_KINDS), kind))
+            code = _ffi.SENSOR_CODES[kind]
+            names = _ffi.SENSOR_PARAMS[code]
+            by_angle = ("cx", "cy", "hx", "hy", "angle")
+            if isinstance(s, dict):
+                given = set(s) - {"kind", "types"}
+                if code == _ffi.SENSOR_BOX and given == set(by_angle):
+                    names = by_angle
+                if given != set(names):
+                    raise EggError("sensor %d (%s): expected the keys %s" % (k, kind, ", ".join(names)))
+                values = [s[n] for n in names]
+            else:
+                values = list(s[1:])
+                if values and isinstance(values[-1], str):
+                    types = values.pop()
+                if code == _ffi.SENSOR_BOX and len(values) == len(by_angle):
+                    names = by_angle
+                if len(values) != len(names):
+                    raise EggError("sensor %d (%s): expected (%r, %s[, types])" % (k, kind, kind, ", ".join(names)))
+            if not isinstance(types, str) or types not in _ffi.SENSOR_TYPES:
+                raise EggError("sensor %d: types must be 'both', 'white' or 'yolk', not %r" % (k, types))
+            try:
+                values = [float(v) for v in values]
+            except (TypeError, ValueError):
+                raise EggError("sensor %d (%s): the parameters must be numbers" % (k, kind)) from None
+            if names is by_angle:
+                values = values[:4] + [math.cos(values[4]), math.sin(values[4])]
+            arr[k].kind, arr[k].type_mask = code, _ffi.SENSOR_TYPES[types]
+            for q, v in enumerate(values):
+                arr[k].p[q] = v
+        return len(sensors), arr
+
+    def set_sensors(self, sensors):
+        """The ordered list of sensor regions, at most 64 (either solver order):
+        `("half_plane", nx, ny, off)` is the side the normal points to, `("disc", cx, cy, R)`, `("box", cx, cy, hx, hy, angle)`
+        (or `..., ux, uy` for the first axis), `("capsule", x0, y0, x1, y1, R)` a band around a segment; each takes an optional
+        last element (or dict key) types = "both" | "white" | "yolk".  A particle is inside when its centre is.  Sensors only
+        observe: a step launches what it launches without them.  `[]` clears the list.  Raises EggError for a bad list
+        (nothing changes)."""
+        n, arr = self._c_sensors(sensors)
+        self._check(self._c("set_sensors")(n, arr))
+
+    def get_sensors(self):
+        """the list as stored, as tuples `(kind, parameters..., types)`: normals and box axes come back normalised, a box
+        with its axis `ux, uy`"""
+        arr = (_ffi.EggSensor * _ffi.MAX_SENSORS)()
+        n = C.c_int32()
+        self._check(self._c("get_sensors")(_ffi.MAX_SENSORS, arr, C.byref(n)))
+        types = {v: k for k, v in _ffi.SENSOR_TYPES.items()}
+        return [(_ffi.SENSOR_KINDS[s.kind],) + tuple(s.p[:len(_ffi.SENSOR_PARAMS[s.kind])]) + (types[s.type_mask],)
+                for s in arr[:n.value]]
+
+    def sensor_sums(self):
+        """`(sums, dropped)` of the positions as committed now: `sums` holds per sensor `((count, sx, sy), (count, sx, sy))`
+        for (white, yolk) as Python ints -- sx, sy the int64 sums of the coordinates scaled by 2^16 and rounded --, `dropped`
+        the `[white, yolk]` (particle, sensor) incidences left out because a scaled coordinate was not finite or reached 2^53.
+        Every call measures."""
+        arr = (_ffi.EggSensorReading * _ffi.MAX_SENSORS)()
+        dropped, n = (C.c_int64 * 2)(), C.c_int32()
+        self._check(self._c("read_sensors")(_ffi.MAX_SENSORS, arr, dropped, C.byref(n)))
+        return [tuple((r.count[w], r.sx[w], r.sy[w]) for w in (0, 1)) for r in arr[:n.value]], list(dropped)
+
+    @staticmethod
+    def _sensor_readings(sums):
+        """per sensor `{"count": (white, yolk), "centroid": (white, yolk)}` from sensor_sums' integers: a centroid is
+        `(((double)sx / 2^16) / count, ((double)sy / 2^16) / count)`, or None while the count is 0"""
+        scale = _ffi.SENSOR_POSITION_SCALE
+        return [{"count": tuple(c for c, _, _ in per_type),
+                 "centroid": tuple(((float(sx) / scale) / float(c), (float(sy) / scale) / float(c)) if c else None
+                                   for c, sx, sy in per_type)} for per_type in sums]
+
+    def sensors(self):
+        """per sensor `{"count": (white, yolk), "centroid": (white, yolk)}`: how many particles of each type lie inside and
+        where their centroid is (an `(x, y)`, or None while there is none)"""
+        return self._sensor_readings(self.sensor_sums()[0])
+
+    def sensor_batches(self, ids):
+        """an int32 array `[len(ids), n_sensors, 2]`: the particles (white, yolk) of each listed batch inside each sensor, in
+        the order of `ids`; an id may repeat.  Raises EggError for an unknown id."""
+        ids = np.ascontiguousarray([int(i) for i in ids], dtype=np.int64)
+        n = C.c_int32()
+        self._check(self._c("get_sensors")(0, None, C.byref(n)))
+        out = np.zeros((ids.size, n.value, 2), dtype=np.int32)
+        self._check(self._c("read_sensor_batches")(ids.size, ids.ctypes.data, out.ctypes.data))
+        return out
+
     # ------------------------------------------------ collider bodies (egg_set_collider_bodies, DESIGN.md section 2.7)
-    _BODIES_LIMIT = ("collider bodies: the device integrates a body from the loads of one handle, so bodies run on a single "
+    _BODIES_LIMIT =("collider bodies: the device integrates a body from the loads of one handle, so bodies run on a single "
                      "SimulationHandler only; only lists without a body are accepted here")
 
     @staticmethod

@@ -912,6 +912,54 @@ int egg_set_containment(egg_handle *h, double factor, double strength);
 int egg_get_containment(const egg_handle *h, double *factor, double *strength);
 int egg_get_containment_hits(egg_handle *h, int64_t *hits);
 
+/* ---- sensors: count and locate the particles inside caller-set regions (csrc/eggsim_sensors.hip) ----
+ * Not in the reference.  A handle holds an ordered list of at most EGG_MAX_SENSORS regions; a READ reports, per region and
+ * particle type, how many particles lie inside and the integer sums their centroid follows from.  Sensors only observe: a
+ * step with a list set launches exactly the kernels it launches without one, with the same arguments, and a read changes
+ * no particle and no step counter.  They read the COMMITTED positions -- the arrays egg_download_particles returns for
+ * EGG_FIELD_X / EGG_FIELD_Y, not interpolated --, so they work in exact and in relaxed order alike.
+ * A particle of type w at the committed (x, y) is INSIDE sensor k when type_mask has bit w (bit 0 white, bit 1 yolk) and the
+ * test of the kind holds.  FP64 in exactly this order, no contraction; every comparison is false for a NaN, so a NaN
+ * position is inside nothing.  Only the particle's centre counts: its radius is not read.
+ *   HALF_PLANE  p = (nx, ny, off, -, -, -): s = (nx x + ny y) - off; inside iff s >= 0.0.  The side the normal points to: the
+ *               side on which a collider with the same parameters keeps its particles.  The normal is normalised when the
+ *               list is set, by the collider rule (len = sqrt(nx nx + ny ny), nx = nx / len, ny = ny / len); a normal shorter
+ *               than the white config's eps is refused.
+ *   DISC        p = (cx, cy, R, -, -, -): dx = x - cx, dy = y - cy, d2 = dx dx + dy dy; inside iff d2 <= R R.
+ *   BOX         p = (cx, cy, hx, hy, ux, uy): (ux, uy) is the box's first axis, normalised when the list is set as a normal
+ *               is.  dx = x - cx, dy = y - cy, u = dx ux + dy uy, v = dy ux - dx uy; inside iff fabs(u) <= hx && fabs(v) <= hy.
+ *   CAPSULE     p = (x0, y0, x1, y1, R, -): e, l2, t and q exactly as the SEGMENT collider defines them, l2 == 0 included;
+ *               dx = x - qx, dy = y - qy, d2 = dx dx + dy dy; inside iff d2 <= R R.  A band around a wall.
+ * Parameters a kind does not use are stored as 0.
+ * A particle that is inside sensor k contributes count[w] += 1, sx[w] += llrint(x * EGG_SENSOR_POSITION_SCALE),
+ * sy[w] += llrint(y * EGG_SENSOR_POSITION_SCALE) to reading k (int64, round to nearest, ties to even).  If one of the two
+ * scaled values is not finite or reaches 2^53 in magnitude, the particle is left out of all three and dropped[w] counts it,
+ * once for every sensor it is inside: dropped is ONE pair of counters per read, not one per sensor.  The centroid of type w
+ * in sensor k is ((double)sx[w] / EGG_SENSOR_POSITION_SCALE) / (double)count[w], in that order, and likewise for y; there is
+ * none while count[w] == 0.  The resolution is 2^-16 px.  Integer addition is associative: a device group and sharded ranks
+ * answer with one handle's numbers bit for bit.  The sums wrap only beyond 2^63.
+ * egg_set_sensors checks everything before it changes anything and returns EGG_ERR_INVALID_ARGUMENT, with the sensor's index
+ * in the message, for: n outside 0 .. EGG_MAX_SENSORS, an unknown kind, a type_mask that is 0 or has bits beyond 3, a
+ * parameter that is not finite, R, hx or hy < 0, a normal or axis shorter than eps.  n == 0 clears the list.  Accepted in
+ * either solver order; refused while a step is in flight.  egg_get_sensors returns the list as stored, normalised.
+ * egg_read_sensors takes one reading of the state as committed now: min(*n, cap) readings, the two dropped counters.
+ * egg_read_sensor_batches gives the counts only, for the listed batches in the caller's order:
+ * counts[(i * n_sensors + k) * 2 + w] = particles of type w of batch ids[i] inside sensor k.  An unknown id returns
+ * EGG_ERR_UNKNOWN_ID and nothing is written; a repeated id is answered twice.  A dropped particle is not counted here either.
+ * Both reads are refused while a step is in flight, succeed with an empty list (*n = 0, nothing is written to counts) and
+ * with a handle that holds no particles (zeros), and are not cached: every call measures.
+ * Limits: centres only (no radius, no overlap test); no velocity or mass sums; no sensor that rides on a collider (a caller
+ * re-sets the list from egg_get_colliders); at most 64. */
+#define EGG_MAX_SENSORS 64
+#define EGG_SENSOR_POSITION_SCALE 65536.0 /* 2^16 */
+enum { EGG_SENSOR_HALF_PLANE = 0, EGG_SENSOR_DISC = 1, EGG_SENSOR_BOX = 2, EGG_SENSOR_CAPSULE = 3 };
+typedef struct { int32_t kind; int32_t type_mask; double p[6]; } egg_sensor;   /* 56 bytes */
+typedef struct { int64_t count[2], sx[2], sy[2]; } egg_sensor_reading;         /* 48 bytes; [0] white, [1] yolk */
+int egg_set_sensors(egg_handle *h, int32_t n, const egg_sensor *sensors);
+int egg_get_sensors(const egg_handle *h, int32_t cap, egg_sensor *out, int32_t *n);
+int egg_read_sensors(egg_handle *h, int32_t cap, egg_sensor_reading *readings, int64_t dropped[2], int32_t *n);
+int egg_read_sensor_batches(egg_handle *h, int64_t n_ids, const int64_t *ids, int32_t *counts /* [n_ids][n_sensors][2] */);
+
 /* ---- several GPUs in one process (csrc/eggsim_group.cpp) -------------------------------------------------------
  * The multi-device form of the handle for a host that is ONE process (the LuaJIT wrapper): one egg_handle per device
  * behind one egg_group, x-slabs [cuts[k], cuts[k + 1]) of the plane per device (cuts: n_devices + 1 ascending values;
@@ -988,6 +1036,13 @@ int egg_group_get_collider_pose(egg_group *g, double alpha, int32_t cap, egg_col
 int egg_group_set_collider_loads(egg_group *g, int on);
 int egg_group_get_collider_load_sums(egg_group *g, int32_t cap, int64_t *sums /* [n][3] */, int64_t *dropped, double *sub_delta, int32_t *n);
 int egg_group_get_collider_loads(egg_group *g, int32_t cap, egg_collider_load *out, int32_t *n);
+/* egg_set_sensors for every handle of the group alike, with its rules; a refused list changes no handle.  A read adds the
+ * handles' integers (readings and dropped); a batch is answered by the handle that owns it, ids being the group's.  The
+ * results equal one handle's bit for bit. */
+int egg_group_set_sensors(egg_group *g, int32_t n, const egg_sensor *sensors);
+int egg_group_get_sensors(const egg_group *g, int32_t cap, egg_sensor *out, int32_t *n);
+int egg_group_read_sensors(egg_group *g, int32_t cap, egg_sensor_reading *readings, int64_t dropped[2], int32_t *n);
+int egg_group_read_sensor_batches(egg_group *g, int64_t n_ids, const int64_t *ids, int32_t *counts /* [n_ids][n_sensors][2] */);
 /* egg_set_forces for every handle of the group alike, with its rules (relaxed order only; back to exact order only with
  * an empty list); a refused list changes no handle.  Every device accelerates only the particles it owns: the results
  * equal one handle's.  A group whose handles differ in their lists refuses to step. */
