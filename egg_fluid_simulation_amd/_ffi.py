@@ -180,6 +180,24 @@ SENSOR_CODES = {n: i for i, n in enumerate(SENSOR_KINDS)}
 SENSOR_TYPES = COLLIDER_TYPES  # type_mask
 
 
+class EggProbeQuery(C.Structure):  # egg_probe_query: a point or a ray whose one winning particle per type a call reports (48 bytes)
+    _fields_ = [("kind", C.c_int32), ("type_mask", C.c_int32), ("p", C.c_double * 5)]
+
+
+class EggProbeHit(C.Structure):  # egg_probe_hit: the winner of one (probe, type), all zeros while found == 0 (56 bytes)
+    _fields_ = [("id", C.c_int64), ("key", C.c_int64), ("index", C.c_int32), ("found", C.c_int32), ("score", C.c_double),
+                ("x", C.c_double), ("y", C.c_double), ("radius", C.c_double)]
+
+
+MAX_PROBES = 64  # EGG_MAX_PROBES
+PROBE_POINT, PROBE_RAY = 0, 1
+PROBE_KINDS = ("point", "ray")  # by EGG_PROBE_* value
+PROBE_PARAMS = (("x", "y", "reach"), ("x0", "y0", "x1", "y1", "pad"))
+PROBE_DEFAULTS = ((float("inf"),), (0.0,))  # reach, pad: the trailing parameters a tuple may leave out
+PROBE_CODES = {n: i for i, n in enumerate(PROBE_KINDS)}
+PROBE_TYPES = dict(COLLIDER_TYPES)  # type_mask by name; the wrappers take the mask itself (1, 2, 3) as well
+
+
 class EggRxBox(C.Structure):  # egg_rx_box: a cell box of the relaxed halo between processes
     _fields_ = [("lo_x", C.c_int32), ("lo_y", C.c_int32), ("hi_x", C.c_int32), ("hi_y", C.c_int32), ("empty", C.c_int32)]
 
@@ -269,6 +287,8 @@ _SIGNATURES = {
     "egg_get_sensors": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggSensor), C.POINTER(C.c_int32)]),
     "egg_read_sensors": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggSensorReading), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     "egg_read_sensor_batches": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "egg_probe": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggProbeQuery), C.POINTER(EggProbeHit)]),
+    "egg_group_probe": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggProbeQuery), C.POINTER(EggProbeHit)]),
     "egg_group_set_sensors": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggSensor)]),
     "egg_group_get_sensors": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggSensor), C.POINTER(C.c_int32)]),
     "egg_group_read_sensors": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggSensorReading), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),

@@ -892,3 +892,38 @@ struct EggSensorBatchFinishArgs {  // counts[(i * n_sensors + k) * 2 + w] = sum 
     int32_t n_rows, n_sensors;
     int32_t *counts;
 };
+
+// ---------------------------------------------------------------------------------------------
+// Probes (eggsim_probes.hip; include/eggsim.h, "probes"): the ONE committed particle per probe and
+// type that is nearest a point or first along a ray.  The scan walks the sensors' units (EggSensorUnit, at most
+// EGG_SN_UNIT consecutive particles of one atom) with one wave per unit; lane k keeps probe k's best.  Nothing here is read
+// or written by a step.
+#define EGG_PB_MAX_PROBES 64         // = EGG_MAX_PROBES: one lane of a wave per probe
+#define EGG_PB_POINT 0
+#define EGG_PB_RAY 1
+#define EGG_PB_FINISH_THREADS 1024
+#define EGG_PB_FINISH_PROBES 8       // probes of one finishing workgroup: their 8 scores are one 64-byte line of a wave's row
+typedef EggSensorUnit EggScanUnit;   // the unit table is the one the sensors' host side builds (push_units)
+struct EggProbe {  // egg_probe_query
+    int32_t kind, type_mask;
+    double p[5];
+};
+struct EggProbeArgs {
+    const double *x[2], *y[2], *radius[2];  // the committed positions and the radii per type
+    const EggScanUnit *units;               // ascending array index within a type
+    int32_t n_probes, n_units;
+    double *part_score;                     // [2][64][waves]: probe k's best score of a wave per type, rows k < n_probes written
+    int32_t *part_index;                    // [2][64][waves]: its array index in the type, -1 while there is none
+    EggProbe probes[EGG_PB_MAX_PROBES];     // the call's list, in the launch arguments (3 KiB)
+};
+struct EggProbeOut {  // the winner of one (probe, type)
+    double score, x, y, radius;
+    int32_t index, reserved;                // array index in the type, -1: no candidate
+};
+struct EggProbeFinishArgs {  // workgroup (g, w): the best over the waves of probes 8 g .. 8 g + 7 of type w, out[2 k + w]
+    const double *part_score;
+    const int32_t *part_index;
+    const double *x[2], *y[2], *radius[2];
+    int32_t n_waves, n_probes;
+    EggProbeOut *out;                       // [EGG_PB_MAX_PROBES][2]
+};

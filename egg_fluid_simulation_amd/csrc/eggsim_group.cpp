@@ -904,6 +904,30 @@ int egg_group_read_sensor_batches(egg_group *g, int64_t n_ids, const int64_t *id
     return EGG_OK;
 }
 
+// Probes (include/eggsim.h, "probes"): every handle answers for the particles it owns; per (probe, type) the best of those
+// winners by (score, key, index) is the winner one handle with every batch would name.  The group's id of a batch is the key
+// it gave egg_add_many_keyed.  Nothing is written before every handle has answered.
+int egg_group_probe(egg_group *g, int32_t n, const egg_probe_query *probes, egg_probe_hit *hits) {
+    if (!g || g->h.empty()) return EGG_ERR_INVALID_ARGUMENT;
+    const size_t words = n > 0 && n <= EGG_MAX_PROBES ? 2 * (size_t)n : 0;
+    std::vector<egg_probe_hit> best(words), one(std::max<size_t>(words, 1));
+    for (size_t k = 0; k < g->h.size(); ++k) {
+        const int rc = egg_probe(g->h[k], n, probes, hits ? one.data() : nullptr);  // (handle 0 refuses a bad list)
+        if (rc < 0) return gfail(g, rc, "device %d: %s", (int)k, egg_last_error(g->h[k]));
+        for (size_t q = 0; q < words; ++q) {
+            const egg_probe_hit &a = one[q], &b = best[q];
+            if (!a.found) continue;
+            if (!b.found || a.score < b.score ||
+                (a.score == b.score && (a.key < b.key || (a.key == b.key && a.index < b.index))))
+                best[q] = a;
+        }
+    }
+    for (egg_probe_hit &b : best)
+        if (b.found) b.id = b.key;
+    if (words) memcpy(hits, best.data(), words * sizeof(egg_probe_hit));
+    return EGG_OK;
+}
+
 int egg_group_get_collider_grips(egg_group *g, int64_t grips[2]) {
     if (!g) return EGG_ERR_INVALID_ARGUMENT;
     if (!grips) return gfail(g, EGG_ERR_INVALID_ARGUMENT, "egg_group_get_collider_grips: grips is NULL");

@@ -15,6 +15,7 @@
 //   eggsim_host_draw_source.hip    the same for a scene sharded over processes: egg_draw_pack on every rank, egg_draw_source_* on one
 //   eggsim_host_instances.hip      egg_get_instances / egg_instances_begin / _end: the instanced-draw record packed on the device
 //   eggsim_host_sensors.hip        egg_set_sensors / egg_read_sensors / egg_read_sensor_batches: the list, the unit tables, the launches
+//   eggsim_host_probes.hip         egg_probe: the checks, the unit table, the two launches, index -> (batch, key, index in the batch)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -139,6 +140,8 @@ extern "C" __global__ void egg_sensor_sums_kernel(EggSensorArgs A);
 extern "C" __global__ void egg_sensor_units_kernel(EggSensorArgs A);
 extern "C" __global__ void egg_sensor_finish_kernel(EggSensorFinishArgs A);
 extern "C" __global__ void egg_sensor_batch_finish_kernel(EggSensorBatchFinishArgs A);
+extern "C" __global__ void egg_probe_scan_kernel(EggProbeArgs A);
+extern "C" __global__ void egg_probe_finish_kernel(EggProbeFinishArgs A);
 extern "C" __global__ void egg_render_count_kernel(EggRenderArgs A);
 extern "C" __global__ void egg_render_fill_kernel(EggRenderArgs A);
 extern "C" __global__ void egg_render_scan_kernel(EggRenderArgs A);
@@ -413,6 +416,7 @@ struct WireStep;  // a relaxed step in flight between egg_rx_begin and egg_rx_en
 struct DrawSource;  // particles placed by egg_draw_source_place, their canvases and scratch (eggsim_host_draw_source.hip)
 struct InstanceState;  // staging and pinned buffers of egg_get_instances / egg_instances_begin (eggsim_host_instances.hip)
 struct SensorState;  // device copy of the sensor list, unit tables and partials of a read (eggsim_host_sensors.hip)
+struct ProbeState;  // unit table, partials and winners of an egg_probe call (eggsim_host_probes.hip)
 }
 using namespace egghost;
 
@@ -579,6 +583,9 @@ struct egg_handle {
     // device, allocated when a list is first set.  No step reads either.
     std::vector<egg_sensor> sensors;
     std::shared_ptr<egghost::SensorState> sensor_state;
+    // probes (egg_probe; either solver order): what a call needs on the device, allocated by the first call that launches.
+    // A call stores no list and no answer; no step reads this.
+    std::shared_ptr<egghost::ProbeState> probe_state;
     // headless renderer (eggsim_render.hip)
     struct Render {
         egg_render_config cfg[2];
@@ -683,6 +690,8 @@ int append_particles(egg_handle *h, System &s, const ParticleTemplate &tp, int64
 int reserve_out(egg_handle *h, System &s, size_t na);
 hipError_t wait_step(hipStream_t stream);
 int upload_atoms(egg_handle *h, int which);
+// the units of atom a of type w behind `units`: at most EGG_SN_UNIT consecutive particles each (eggsim_host_sensors.hip)
+void push_units(const Atom &a, int w, std::vector<EggScanUnit> &units);
 double cell_size_of(const egg_config &c);  // L:1756-1760
 int fetch_end_aabb(egg_handle *h, System &s);
 

@@ -18,13 +18,13 @@ struct SensorState {
     DevBuf<int32_t> unit_counts, rows, counts;
 };
 
-namespace {
-
-// the units of atom a of type w behind `units`
+// the units of atom a of type w behind `units` (the probes' scan walks the same units: eggsim_host_probes.hip)
 void push_units(const Atom &a, int w, std::vector<EggSensorUnit> &units) {
     for (int32_t at = 0; at < a.count; at += EGG_SN_UNIT)
         units.push_back(EggSensorUnit{a.offset + at, std::min<int32_t>(EGG_SN_UNIT, a.count - at), w, 0});
 }
+
+namespace {
 
 // bit w: some sensor's mask covers type w and the type has particles
 int covered_types(const egg_handle *h) {

@@ -122,6 +122,9 @@ int egg_set_sensors(egg_handle *h, int32_t n, const egg_sensor *sensors);
 int egg_get_sensors(const egg_handle *h, int32_t cap, egg_sensor *out, int32_t *n);
 int egg_read_sensors(egg_handle *h, int32_t cap, egg_sensor_reading *readings, int64_t dropped[2], int32_t *n);
 int egg_read_sensor_batches(egg_handle *h, int64_t n_ids, const int64_t *ids, int32_t *counts);
+typedef struct { int32_t kind; int32_t type_mask; double p[5]; } egg_probe_query;
+typedef struct { int64_t id, key; int32_t index, found; double score, x, y, radius; } egg_probe_hit;
+int egg_probe(egg_handle *h, int32_t n, const egg_probe_query *probes, egg_probe_hit *hits);
 typedef struct egg_group egg_group;
 int egg_group_set_solver_order(egg_group *g, int32_t order, double relaxation);
 int egg_group_set_cohesion(egg_group *g, int32_t mode);
@@ -876,6 +879,75 @@ function SimulationHandler:sensor_batches(ids)
         end
     end
     return out
+end
+
+-- Not in the reference: probes (egg_probe in include/eggsim.h; DESIGN.md section 2.9).  What is here: the ONE particle per
+-- type nearest a point or first along a ray, from the committed state; either solver order.  A call stores nothing and
+-- only observes: a step launches what it launches without it.
+local _probe_kinds = { point = 0, ray = 1 }
+local _probe_n_params = { [0] = 3, 5 }
+local _probe_defaults = { [0] = math.huge, 0 } -- reach, pad: the last parameter may be left out
+local _max_probes = 64 -- EGG_MAX_PROBES
+local _probe_type_names = { [0] = "white", "yolk" }
+
+--- at most 64 probes, each `{ "point", x, y[, reach] }` (reach defaults to infinity) or `{ "ray", x0, y0, x1, y1[, pad] }`
+--- (pad defaults to 0), with an optional `types = "both" | "white" | "yolk"`.  Returns per probe
+--- `{ white = hit_or_nil, yolk = hit_or_nil }`, a hit being `{ id, index, score, x, y, radius }` by name: the batch, the
+--- particle's 0-based index in the batch's run of that type, squared distance (point) or t (ray), and the particle.
+function SimulationHandler:probe(probes)
+    local n = #probes
+    if n > _max_probes then
+        log.error("In SimulationHandler.probe: a call takes 0 .. 64 probes")
+        return {}
+    end
+    local arr = ffi.new("egg_probe_query[?]", math.max(n, 1))
+    for k, q in ipairs(probes) do
+        local kind = _probe_kinds[q[1]]
+        local mask = _collider_types[q.types or "both"]
+        if kind == nil or mask == nil or (#q ~= 1 + _probe_n_params[kind] and #q ~= _probe_n_params[kind]) then
+            log.error("In SimulationHandler.probe: probe " .. k .. ": expected { kind, parameters..., types = ... }")
+            return {}
+        end
+        arr[k - 1].kind, arr[k - 1].type_mask = kind, mask
+        for i = 1, _probe_n_params[kind] do
+            local v = q[i + 1]
+            if v == nil then v = _probe_defaults[kind] end
+            arr[k - 1].p[i - 1] = v
+        end
+    end
+    local hits = ffi.new("egg_probe_hit[?]", math.max(2 * n, 1))
+    if self:_check(lib.egg_probe(self._h, n, arr, hits)) ~= 0 then return {} end
+    local out = {}
+    for k = 0, n - 1 do
+        local one = {}
+        for w = 0, 1 do
+            local t = hits[2 * k + w]
+            if t.found ~= 0 then
+                one[_probe_type_names[w]] = { id = tonumber(t.id), index = t.index, score = t.score, x = t.x, y = t.y, radius = t.radius }
+            end
+        end
+        out[k + 1] = one
+    end
+    return out
+end
+
+-- the lower score of a probe's two hits, an exact tie to white: type_name, hit; nil without a hit
+local function _probe_first(one)
+    if one == nil or (one.white == nil and one.yolk == nil) then return nil end
+    if one.yolk == nil or (one.white ~= nil and not (one.yolk.score < one.white.score)) then return "white", one.white end
+    return "yolk", one.yolk
+end
+
+--- the particle nearest (x, y) within `reach` (default: wherever it is): nil, or type_name and the hit; `types` as in probe
+function SimulationHandler:pick(x, y, reach, types)
+    return _probe_first(self:probe({ { "point", x, y, reach or math.huge, types = types } })[1])
+end
+
+--- the first particle disc (radius + pad) the segment enters: nil, or type_name, the hit and the point of impact x, y
+function SimulationHandler:raycast(x0, y0, x1, y1, pad, types)
+    local name, hit = _probe_first(self:probe({ { "ray", x0, y0, x1, y1, pad or 0, types = types } })[1])
+    if name == nil then return nil end
+    return name, hit, x0 + hit.score * (x1 - x0), y0 + hit.score * (y1 - y0)
 end
 
 -- Not in the reference, which has no forces as it has no boundary: force fields of the relaxed step (egg_set_forces in

@@ -731,6 +731,42 @@ class ShardedSimulationHandler(_HandlerSurface):
         self.dist.all_reduce(tot, op=self.dist.ReduceOp.SUM)
         return tot.cpu().numpy().astype(np.int32)
 
+    def probe(self, probes):
+        """SimulationHandler.probe over all ranks (a collective: every rank calls it with the same list).  Every rank asks its
+        own handle, the ranks all_gather their hit tables (one int64 tensor, the doubles as their bit patterns) and each rank
+        keeps per (probe, type) the best by (score, key, index): one handle's answer bit for bit, with the global id.  Nothing
+        travels in a step."""
+        n, arr = self._c_probes(probes)
+        table = self.local._probe_table(n, arr)
+        mine = np.zeros((n, 2, 7), dtype=np.int64)  # found, key, index, then the bits of score, x, y, radius
+        for k, pair in enumerate(table):
+            for w, t in enumerate(pair):
+                if t is not None:
+                    mine[k, w, :3] = (1, t[1], t[2])
+                    mine[k, w, 3:] = np.array([t[0], t[4], t[5], t[6]], dtype=np.float64).view(np.int64)
+        parts = [mine]
+        if self.world > 1 and n:
+            own = self.torch.from_numpy(mine).to(self.device)
+            got = [self.torch.zeros_like(own) for _ in range(self.world)]
+            self.dist.all_gather(got, own)
+            parts = [q.cpu().numpy() for q in got]
+        best = []
+        for k in range(n):
+            pair = []
+            for w in (0, 1):
+                found = None
+                for part in parts:
+                    rec = part[k, w]
+                    if not rec[0]:
+                        continue
+                    score, x, y, radius = (float(v) for v in rec[3:].view(np.float64))
+                    key, index = int(rec[1]), int(rec[2])  # (the global id of a batch is the key its rank's handle holds)
+                    if found is None or score < found[0] or (score == found[0] and (key, index) < found[1:3]):
+                        found = (score, key, index, key, x, y, radius)
+                pair.append(found)
+            best.append(tuple(pair))
+        return self._probe_hits(best)
+
     def set_forces(self, forces):
         """SimulationHandler.set_forces on every rank alike (the same call on every rank; relaxed order only).  Nothing
         new travels: every rank accelerates the particles it owns."""

@@ -11,6 +11,7 @@ Error conventions (log.lua:9-88): where the reference calls `log.error` /
 """
 import copy
 import ctypes as C
+import collections
 import functools
 import math
 import warnings
@@ -23,6 +24,11 @@ from .default_config import default_configs
 
 class EggError(RuntimeError):
     """The reference's `log.error` (a thrown Lua error)."""
+
+
+# a probe's winner (egg_probe_hit without `found` and `key`): the batch's id, the particle's 0-based index in the batch's run
+# of its type, the score (POINT: squared distance, RAY: t) and the particle's committed x, y, radius
+ProbeHit = collections.namedtuple("ProbeHit", "id index score x y radius")
 
 
 class EggWarning(UserWarning):
@@ -499,6 +505,95 @@ class _HandlerSurface:
         out = np.zeros((ids.size, n.value, 2), dtype=np.int32)
         self._check(self._c("read_sensor_batches")(ids.size, ids.ctypes.data, out.ctypes.data))
         return out
+
+    # ------------------------------------------------ probes (egg_probe)
+    @staticmethod
+    def _probe_mask(types, what):
+        """`types` as a type_mask: "both" | "white" | "yolk", or the mask itself (1 white, 2 yolk, 3 both)"""
+        if isinstance(types, str) and types in _ffi.PROBE_TYPES:
+            return _ffi.PROBE_TYPES[types]
+        if isinstance(types, int) and not isinstance(types, bool) and 1 <= types <= 3:
+            return types
+        raise EggError("%s: types must be 'both', 'white', 'yolk' or a mask 1 .. 3, not %r" % (what, types))
+
+    @staticmethod
+    def _c_probes(probes):
+        """a list of tuples `("point", x, y[, reach[, types]])` / `("ray", x0, y0, x1, y1[, pad[, types]])` as an
+        egg_probe_query array; reach defaults to inf, pad to 0, types to both.  What only the host can check (shape, names)
+        is checked here, the values by the library."""
+        probes = list(probes)
+        if len(probes) > _ffi.MAX_PROBES:
+            raise EggError("probes: a call takes 0 .. %d probes, not %d" % (_ffi.MAX_PROBES, len(probes)))
+        arr = (_ffi.EggProbeQuery * max(len(probes), 1))()
+        for k, q in enumerate(probes):
+            q = tuple(q) if isinstance(q, (tuple, list)) else ()
+            kind = q[0] if q else None
+            if not isinstance(kind, str) or kind not in _ffi.PROBE_CODES:
+                raise EggError("probe %d: kind must be one of %s, not %r" % (k, ", ".join(_ffi.PROBE_KINDS), kind))
+            code = _ffi.PROBE_CODES[kind]
+            names, defaults = _ffi.PROBE_PARAMS[code], _ffi.PROBE_DEFAULTS[code]
+            values, types = list(q[1:]), "both"
+            if len(values) == len(names) + 1 or (values and isinstance(values[-1], str)):  # (types may follow x, y directly)
+                types = values.pop()
+            if not len(names) - len(defaults) <= len(values) <= len(names):
+                raise EggError("probe %d (%s): expected (%r, %s[, %s[, types]])"
+                               % (k, kind, kind, ", ".join(names[:-1]), names[-1]))
+            values += defaults[len(defaults) - (len(names) - len(values)):]
+            mask = _HandlerSurface._probe_mask(types, "probe %d" % k)
+            try:
+                values = [float(v) for v in values]
+            except (TypeError, ValueError):
+                raise EggError("probe %d (%s): the parameters must be numbers" % (k, kind)) from None
+            arr[k].kind, arr[k].type_mask = code, mask
+            for i, v in enumerate(values):
+                arr[k].p[i] = v
+        return len(probes), arr
+
+    def _probe_table(self, n, arr):
+        """the raw answer of one call: per probe `(white, yolk)`, each None or `(score, key, index, id, x, y, radius)`"""
+        hits = (_ffi.EggProbeHit * max(2 * n, 1))()
+        self._check(self._c("probe")(n, arr, hits))
+        return [tuple((t.score, t.key, t.index, t.id, t.x, t.y, t.radius) if t.found else None for t in hits[2 * k:2 * k + 2])
+                for k in range(n)]
+
+    @staticmethod
+    def _probe_hits(table):
+        return [tuple(None if t is None else ProbeHit(t[3], t[2], t[0], t[4], t[5], t[6]) for t in pair) for pair in table]
+
+    def probe(self, probes):
+        """What is here (either solver order): per probe `(white_hit_or_None, yolk_hit_or_None)`, a hit
+        being the ONE winning particle of that type as a `ProbeHit(id, index, score, x, y, radius)`.
+        `("point", x, y[, reach[, types]])` names the particle whose centre is nearest (x, y) within `reach` (default inf;
+        score = squared distance); `("ray", x0, y0, x1, y1[, pad[, types]])` the first disc of radius `radius + pad` the segment
+        enters (score = t in [0, 1]).  types = "both" | "white" | "yolk".  Equal scores go to the older batch, then to the
+        lower index.  Reads the committed state; stores nothing; at most 64 probes.  Raises EggError for a bad list."""
+        n, arr = self._c_probes(probes)
+        return self._probe_hits(self._probe_table(n, arr))
+
+    @staticmethod
+    def _probe_first(pair):
+        """`(type_name, hit)` of the lower score of a probe's two hits, an exact tie to white; None without a hit"""
+        white, yolk = pair
+        if white is None and yolk is None:
+            return None
+        if yolk is None or (white is not None and not yolk.score < white.score):
+            return ("white", white)
+        return ("yolk", yolk)
+
+    def pick(self, x, y, reach=float("inf"), types=3):
+        """the particle nearest (x, y) within `reach`: None or `(type_name, hit)`, the lower score of the two types, an exact
+        tie to white.  `hit.score <= hit.radius ** 2` tells whether the point is ON the particle."""
+        return self._probe_first(self.probe([("point", x, y, reach, types)])[0])
+
+    def raycast(self, x0, y0, x1, y1, pad=0.0, types=3):
+        """the first particle disc (radius + pad) the segment from (x0, y0) to (x1, y1) enters: None or
+        `(type_name, hit, (x, y))` with the point of impact `(x0 + t ex, y0 + t ey)`, t = hit.score"""
+        first = self._probe_first(self.probe([("ray", x0, y0, x1, y1, pad, types)])[0])
+        if first is None:
+            return None
+        x0, y0, x1, y1 = float(x0), float(y0), float(x1), float(y1)
+        t = first[1].score
+        return first + ((x0 + t * (x1 - x0), y0 + t * (y1 - y0)),)
 
     # ------------------------------------------------ collider bodies (egg_set_collider_bodies, DESIGN.md section 2.7)
     _BODIES_LIMIT =("collider bodies: the device integrates a body from the loads of one handle, so bodies run on a single "

@@ -960,6 +960,48 @@ int egg_get_sensors(const egg_handle *h, int32_t cap, egg_sensor *out, int32_t *
 int egg_read_sensors(egg_handle *h, int32_t cap, egg_sensor_reading *readings, int64_t dropped[2], int32_t *n);
 int egg_read_sensor_batches(egg_handle *h, int64_t n_ids, const int64_t *ids, int32_t *counts /* [n_ids][n_sensors][2] */);
 
+/* ---- probes: the nearest particle to a point and the first hit along a ray (csrc/eggsim_probes.hip) ----
+ * Not in the reference.  Sensors answer "what is inside this region" with sums; a probe answers "what is here" with the
+ * IDENTITY of one particle: the egg under the cursor, the first egg a line of sight meets, the particle nearest a utensil's
+ * tip.  A call is STATELESS: the caller passes at most EGG_MAX_PROBES probes with the call and the handle stores neither the
+ * list nor an answer.  Probes only observe: a step launches exactly the kernels it launches without them, and a call changes
+ * no particle and no counter, those of egg_get_stats included.  They read the COMMITTED state -- the arrays
+ * egg_download_particles returns for EGG_FIELD_X / EGG_FIELD_Y / EGG_FIELD_RADIUS, not interpolated --, so they work in
+ * exact and in relaxed order alike.
+ * A particle of type w at the committed (x, y) with radius r is a CANDIDATE of probe k when type_mask has bit w (bit 0 white,
+ * bit 1 yolk) and the rule of the kind holds.  FP64 in exactly this order, no contraction, sqrt and / correctly rounded;
+ * every comparison is false for a NaN, so a NaN position or radius is a candidate for nothing.
+ *   POINT  p = (px, py, reach, -, -): dx = x - px, dy = y - py, d2 = dx dx + dy dy; candidate iff d2 <= reach reach && r == r;
+ *          score = d2.  Only the centre is compared; the hit reports the radius, so a caller who asks "is the cursor ON a
+ *          particle" tests score <= radius * radius itself.  reach is finite and >= 0, or +inf: the nearest, wherever it is.
+ *   RAY    p = (x0, y0, x1, y1, pad): the first disc of radius R = r + pad that the segment from (x0, y0) to (x1, y1) enters.
+ *          fx = x0 - x, fy = y0 - y, c = (fx fx + fy fy) - R R.  If c <= 0.0 the ray starts in or on the disc: candidate with
+ *          t = 0.0.  Otherwise ex = x1 - x0, ey = y1 - y0, l2 = ex ex + ey ey, b = fx ex + fy ey; a miss unless b < 0.0;
+ *          q = b b - l2 c; a miss unless q >= 0.0; t = (-b - sqrt(q)) / l2; a miss unless t <= 1.0.  score = t; the point of
+ *          impact is (x0 + t ex, y0 + t ey).  pad is finite and >= 0; a ray whose l2 is below the white config's eps squared
+ *          (or not finite) is refused.  t is never negative: sqrt(q) <= -b after rounding when c > 0.
+ * Parameters a kind does not use are ignored.
+ * The WINNER of probe k and type w is, among the candidates of type w, the one with the smallest score by < on doubles;
+ * among equal scores the smallest batch key (egg_batch_info.key, the batch's position in the global creation order), then
+ * the smallest index inside the batch's run of that type.  A handle lays its particles out in ascending key, so on one
+ * handle that is the lowest array index; across the handles of a group and across ranks the same rule is well defined.
+ * hits[2 k + w] reports found = 1, the batch's id, its key, the particle's 0-based index in the batch's run of that type (in
+ * download order), the score and the particle's committed x, y, radius.  With no candidate -- also for a type the mask does
+ * not cover -- found = 0 and every other field is 0.
+ * egg_probe checks everything before it launches anything and returns EGG_ERR_INVALID_ARGUMENT, with the probe's index in
+ * the message and hits untouched, for: n outside 0 .. EGG_MAX_PROBES, n > 0 without a list or without hits, an unknown kind,
+ * a type_mask that is 0 or has bits beyond 3, a NaN in a parameter the kind uses, an infinity anywhere but a POINT's reach, a
+ * negative reach or pad, a degenerate ray.  n == 0 succeeds and writes nothing.  A handle without particles answers
+ * found = 0 everywhere and launches nothing; a type that no probe's mask covers contributes no work.  Refused while a step
+ * is in flight (egg_step_begin or egg_rx_begin open).  Nothing is cached: every call measures.
+ * Limits: centres for POINT, discs for RAY; one winner per type, no k-nearest; no probe that rides on a collider; colliders
+ * themselves are not hit; at most 64 per call. */
+#define EGG_MAX_PROBES 64
+enum { EGG_PROBE_POINT = 0, EGG_PROBE_RAY = 1 };
+typedef struct { int32_t kind; int32_t type_mask; double p[5]; } egg_probe_query;                                             /* 48 bytes */
+typedef struct { int64_t id, key; int32_t index, found; double score, x, y, radius; } egg_probe_hit;                          /* 56 bytes */
+int egg_probe(egg_handle *h, int32_t n, const egg_probe_query *probes, egg_probe_hit *hits /* [n][2]: [0] white, [1] yolk */);
+
 /* ---- several GPUs in one process (csrc/eggsim_group.cpp) -------------------------------------------------------
  * The multi-device form of the handle for a host that is ONE process (the LuaJIT wrapper): one egg_handle per device
  * behind one egg_group, x-slabs [cuts[k], cuts[k + 1]) of the plane per device (cuts: n_devices + 1 ascending values;
@@ -1043,6 +1085,11 @@ int egg_group_set_sensors(egg_group *g, int32_t n, const egg_sensor *sensors);
 int egg_group_get_sensors(const egg_group *g, int32_t cap, egg_sensor *out, int32_t *n);
 int egg_group_read_sensors(egg_group *g, int32_t cap, egg_sensor_reading *readings, int64_t dropped[2], int32_t *n);
 int egg_group_read_sensor_batches(egg_group *g, int64_t n_ids, const int64_t *ids, int32_t *counts /* [n_ids][n_sensors][2] */);
+/* egg_probe on every handle of the group with the same list; per (probe, type) the best of the handles' winners by (score,
+ * key, index) is kept, and id is the group's id of the batch (the key the group gave egg_add_many_keyed).  The result equals
+ * one handle that holds every batch, bit for bit, whichever device owns tied batches.  A failure on any handle writes
+ * nothing. */
+int egg_group_probe(egg_group *g, int32_t n, const egg_probe_query *probes, egg_probe_hit *hits /* [n][2] */);
 /* egg_set_forces for every handle of the group alike, with its rules (relaxed order only; back to exact order only with
  * an empty list); a refused list changes no handle.  Every device accelerates only the particles it owns: the results
  * equal one handle's.  A group whose handles differ in their lists refuses to step. */
