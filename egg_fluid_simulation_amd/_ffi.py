@@ -198,6 +198,27 @@ PROBE_CODES = {n: i for i, n in enumerate(PROBE_KINDS)}
 PROBE_TYPES = dict(COLLIDER_TYPES)  # type_mask by name; the wrappers take the mask itself (1, 2, 3) as well
 
 
+class EggFieldSpec(C.Structure):  # egg_field_spec: the grid of one call, nx x ny square cells from (x0, y0) (40 bytes)
+    _fields_ = [("x0", C.c_double), ("y0", C.c_double), ("cell", C.c_double), ("nx", C.c_int32), ("ny", C.c_int32),
+                ("type_mask", C.c_int32), ("path", C.c_int32)]
+
+
+class EggFieldPlanes(C.Structure):  # egg_field_planes: int32 count and int64 svx / svy, each [2][ny][nx]; svx / svy both or neither
+    _fields_ = [("count", C.c_void_p), ("svx", C.c_void_p), ("svy", C.c_void_p)]
+
+
+class EggFieldTotals(C.Structure):  # egg_field_totals: particles per type by fate, and the units of each path (56 bytes)
+    _fields_ = [("inside", C.c_int64 * 2), ("outside", C.c_int64 * 2), ("dropped", C.c_int64 * 2), ("units_tiled", C.c_int32),
+                ("units_direct", C.c_int32)]
+
+
+FIELD_MAX_CELLS = 1 << 20  # EGG_FIELD_MAX_CELLS: nx * ny
+FIELD_VELOCITY_SCALE = 65536.0  # EGG_FIELD_VELOCITY_SCALE, 2^16
+FIELD_PATH_AUTO, FIELD_PATH_DIRECT = 0, 1
+FIELD_PATHS = {"auto": FIELD_PATH_AUTO, "direct": FIELD_PATH_DIRECT}  # direct: test hook, every unit adds particle by particle
+FIELD_TYPES = dict(COLLIDER_TYPES)  # type_mask by name; the wrappers take the mask itself (1, 2, 3) as well
+
+
 class EggRxBox(C.Structure):  # egg_rx_box: a cell box of the relaxed halo between processes
     _fields_ = [("lo_x", C.c_int32), ("lo_y", C.c_int32), ("hi_x", C.c_int32), ("hi_y", C.c_int32), ("empty", C.c_int32)]
 
@@ -289,6 +310,9 @@ _SIGNATURES = {
     "egg_read_sensor_batches": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "egg_probe": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggProbeQuery), C.POINTER(EggProbeHit)]),
     "egg_group_probe": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggProbeQuery), C.POINTER(EggProbeHit)]),
+    "egg_field": (C.c_int, [C.c_void_p, C.POINTER(EggFieldSpec), C.POINTER(EggFieldPlanes), C.POINTER(EggFieldTotals)]),
+    "egg_field_to": (C.c_int, [C.c_void_p, C.POINTER(EggFieldSpec), C.POINTER(EggFieldPlanes), C.POINTER(EggFieldTotals)]),
+    "egg_group_field": (C.c_int, [C.c_void_p, C.POINTER(EggFieldSpec), C.POINTER(EggFieldPlanes), C.POINTER(EggFieldTotals)]),
     "egg_group_set_sensors": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggSensor)]),
     "egg_group_get_sensors": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggSensor), C.POINTER(C.c_int32)]),
     "egg_group_read_sensors": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggSensorReading), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),

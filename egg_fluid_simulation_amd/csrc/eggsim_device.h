@@ -927,3 +927,26 @@ struct EggProbeFinishArgs {  // workgroup (g, w): the best over the waves of pro
     int32_t n_waves, n_probes;
     EggProbeOut *out;                       // [EGG_PB_MAX_PROBES][2]
 };
+
+// ---------------------------------------------------------------------------------------------
+// Fields (eggsim_fields.hip; include/eggsim.h, "fields"): the committed particles binned into a
+// caller-set grid, a count plane and two int64 velocity-sum planes per type.  The scan walks the units of the shared
+// builder (push_units: at most EGG_SN_UNIT consecutive particles of one atom) with one wave per unit.  An atom is one egg's
+// blob, so a unit's particles fall into a small rectangle of cells: where that rectangle holds at most EGG_FD_TILE_CELLS
+// cells the wave sums it in LDS and adds every non-zero word to the planes once.  Nothing here is read or written by a step.
+#define EGG_FD_TILE_CELLS 1024       // cells of a unit's rectangle the tile path holds: 4 KB of counts, 2 x 8 KB of sums
+#define EGG_FD_SCALE 0x1p16          // = EGG_FIELD_VELOCITY_SCALE
+#define EGG_FD_LIMIT 0x1p53          // a scaled velocity that reaches it (or is not finite) drops the particle
+#define EGG_FD_TOTALS 8              // words of the totals: inside, outside, dropped per type, units tiled, units direct
+struct EggFieldArgs {
+    const double *x[2], *y[2];        // the committed positions per type
+    const double *vx[2], *vy[2];      // the committed velocities per type (read by the <true> instantiation only)
+    const EggScanUnit *units;
+    int32_t n_units;
+    int32_t nx, ny;
+    int32_t tile_cells;               // 0 .. EGG_FD_TILE_CELLS: the largest rectangle of the tile path, 0 = every unit direct
+    double x0, y0, inv;               // inv = 1.0 / cell, computed once on the host
+    int32_t *count;                   // [2][ny][nx], zeroed before the launch
+    unsigned long long *svx, *svy;    // [2][ny][nx] two's complement sums, zeroed before the launch (<true> only)
+    unsigned long long *totals;       // [EGG_FD_TOTALS], zeroed before the launch
+};

@@ -928,6 +928,58 @@ int egg_group_probe(egg_group *g, int32_t n, const egg_probe_query *probes, egg_
     return EGG_OK;
 }
 
+// Fields (include/eggsim.h, "fields"): every handle bins the particles it owns into the same grid; the planes and the totals
+// are added on the host (two's complement: the sum of the handles' sums is the sum over all their particles).  Handle 0
+// refuses a bad grid; nothing is written before every handle has answered.
+int egg_group_field(egg_group *g, const egg_field_spec *spec, const egg_field_planes *host_out, egg_field_totals *totals) {
+    if (!g || g->h.empty()) return EGG_ERR_INVALID_ARGUMENT;
+    const bool shaped = spec && spec->nx >= 1 && spec->ny >= 1 && (int64_t)spec->nx * spec->ny <= EGG_FIELD_MAX_CELLS;
+    const size_t words = shaped && host_out ? 2 * (size_t)spec->nx * (size_t)spec->ny : 0;
+    const bool velocity = host_out && host_out->svx && host_out->svy;
+    std::vector<int32_t> count(words, 0), one_count(std::max<size_t>(words, 1));
+    std::vector<uint64_t> svx(velocity ? words : 0, 0), svy(velocity ? words : 0, 0);
+    std::vector<int64_t> one_svx(std::max<size_t>(svx.size(), 1)), one_svy(std::max<size_t>(svy.size(), 1));
+    uint64_t sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (size_t k = 0; k < g->h.size(); ++k) {
+        egg_field_planes one{};
+        if (host_out) {  // (a missing plane stays missing: the handle refuses what it refuses alone)
+            one.count = host_out->count ? one_count.data() : nullptr;
+            one.svx = host_out->svx ? one_svx.data() : nullptr;
+            one.svy = host_out->svy ? one_svy.data() : nullptr;
+        }
+        egg_field_totals t{};
+        const int rc = egg_field(g->h[k], spec, host_out ? &one : nullptr, &t);
+        if (rc < 0) return gfail(g, rc, "device %d: %s", (int)k, egg_last_error(g->h[k]));
+        for (size_t q = 0; q < words; ++q) count[q] = (int32_t)((uint32_t)count[q] + (uint32_t)one_count[q]);
+        for (size_t q = 0; q < svx.size(); ++q) {
+            svx[q] += (uint64_t)one_svx[q];
+            svy[q] += (uint64_t)one_svy[q];
+        }
+        for (int w = 0; w < 2; ++w) {
+            sum[0 + w] += (uint64_t)t.inside[w];
+            sum[2 + w] += (uint64_t)t.outside[w];
+            sum[4 + w] += (uint64_t)t.dropped[w];
+        }
+        sum[6] += (uint64_t)t.units_tiled;
+        sum[7] += (uint64_t)t.units_direct;
+    }
+    memcpy(host_out->count, count.data(), words * sizeof(int32_t));
+    if (velocity) {
+        memcpy(host_out->svx, svx.data(), words * sizeof(int64_t));
+        memcpy(host_out->svy, svy.data(), words * sizeof(int64_t));
+    }
+    if (totals) {
+        for (int w = 0; w < 2; ++w) {
+            totals->inside[w] = (int64_t)sum[0 + w];
+            totals->outside[w] = (int64_t)sum[2 + w];
+            totals->dropped[w] = (int64_t)sum[4 + w];
+        }
+        totals->units_tiled = (int32_t)sum[6];
+        totals->units_direct = (int32_t)sum[7];
+    }
+    return EGG_OK;
+}
+
 int egg_group_get_collider_grips(egg_group *g, int64_t grips[2]) {
     if (!g) return EGG_ERR_INVALID_ARGUMENT;
     if (!grips) return gfail(g, EGG_ERR_INVALID_ARGUMENT, "egg_group_get_collider_grips: grips is NULL");

@@ -16,6 +16,7 @@
 //   eggsim_host_instances.hip      egg_get_instances / egg_instances_begin / _end: the instanced-draw record packed on the device
 //   eggsim_host_sensors.hip        egg_set_sensors / egg_read_sensors / egg_read_sensor_batches: the list, the unit tables, the launches
 //   eggsim_host_probes.hip         egg_probe: the checks, the unit table, the two launches, index -> (batch, key, index in the batch)
+//   eggsim_host_fields.hip         egg_field / egg_field_to: the checks, the unit table, the zeroing, the one launch, the copies back
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -142,6 +143,8 @@ extern "C" __global__ void egg_sensor_finish_kernel(EggSensorFinishArgs A);
 extern "C" __global__ void egg_sensor_batch_finish_kernel(EggSensorBatchFinishArgs A);
 extern "C" __global__ void egg_probe_scan_kernel(EggProbeArgs A);
 extern "C" __global__ void egg_probe_finish_kernel(EggProbeFinishArgs A);
+extern "C" __global__ void egg_field_count_kernel(EggFieldArgs A);
+extern "C" __global__ void egg_field_velocity_kernel(EggFieldArgs A);
 extern "C" __global__ void egg_render_count_kernel(EggRenderArgs A);
 extern "C" __global__ void egg_render_fill_kernel(EggRenderArgs A);
 extern "C" __global__ void egg_render_scan_kernel(EggRenderArgs A);
@@ -417,6 +420,7 @@ struct DrawSource;  // particles placed by egg_draw_source_place, their canvases
 struct InstanceState;  // staging and pinned buffers of egg_get_instances / egg_instances_begin (eggsim_host_instances.hip)
 struct SensorState;  // device copy of the sensor list, unit tables and partials of a read (eggsim_host_sensors.hip)
 struct ProbeState;  // unit table, partials and winners of an egg_probe call (eggsim_host_probes.hip)
+struct FieldState;  // unit table, planes and totals of an egg_field call (eggsim_host_fields.hip)
 }
 using namespace egghost;
 
@@ -586,6 +590,9 @@ struct egg_handle {
     // probes (egg_probe; either solver order): what a call needs on the device, allocated by the first call that launches.
     // A call stores no list and no answer; no step reads this.
     std::shared_ptr<egghost::ProbeState> probe_state;
+    // fields (egg_field / egg_field_to; either solver order): what a call needs on the device, allocated by the first call
+    // that launches.  A call stores no grid and no answer; no step reads this.
+    std::shared_ptr<egghost::FieldState> field_state;
     // headless renderer (eggsim_render.hip)
     struct Render {
         egg_render_config cfg[2];

@@ -125,6 +125,10 @@ int egg_read_sensor_batches(egg_handle *h, int64_t n_ids, const int64_t *ids, in
 typedef struct { int32_t kind; int32_t type_mask; double p[5]; } egg_probe_query;
 typedef struct { int64_t id, key; int32_t index, found; double score, x, y, radius; } egg_probe_hit;
 int egg_probe(egg_handle *h, int32_t n, const egg_probe_query *probes, egg_probe_hit *hits);
+typedef struct { double x0, y0, cell; int32_t nx, ny, type_mask, path; } egg_field_spec;
+typedef struct { int32_t *count; int64_t *svx, *svy; } egg_field_planes;
+typedef struct { int64_t inside[2], outside[2], dropped[2]; int32_t units_tiled, units_direct; } egg_field_totals;
+int egg_field(egg_handle *h, const egg_field_spec *spec, const egg_field_planes *host_out, egg_field_totals *totals);
 typedef struct egg_group egg_group;
 int egg_group_set_solver_order(egg_group *g, int32_t order, double relaxation);
 int egg_group_set_cohesion(egg_group *g, int32_t mode);
@@ -948,6 +952,49 @@ function SimulationHandler:raycast(x0, y0, x1, y1, pad, types)
     local name, hit = _probe_first(self:probe({ { "ray", x0, y0, x1, y1, pad or 0, types = types } })[1])
     if name == nil then return nil end
     return name, hit, x0 + hit.score * (x1 - x0), y0 + hit.score * (y1 - y0)
+end
+
+-- Not in the reference: fields (egg_field in include/eggsim.h; DESIGN.md section 2.10).  The egg as a map: the committed
+-- particles binned by their centres into a caller-set grid; either solver order.  A call stores nothing and only observes.
+local _field_paths = { auto = 0, direct = 1 }
+local _field_max_cells = 1048576 -- EGG_FIELD_MAX_CELLS
+local _field_velocity_scale = 65536 -- EGG_FIELD_VELOCITY_SCALE
+
+--- the grid of `nx` x `ny` square cells of side `cell` whose cell (0, 0) has its lower corner at (x0, y0); `options` may hold
+--- `types = "both" | "white" | "yolk"`, `velocity = true` and `path = "auto" | "direct"` (a test hook).  Returns
+--- `{ nx, ny, count, svx, svy, inside, outside, dropped, units_tiled, units_direct }` by name: `count` an `int32_t` and
+--- `svx`, `svy` (nil without velocity) `int64_t` arrays laid out [2][ny][nx], 0-based, [0] white and [1] yolk -- the word of
+--- type w and cell (ix, iy) is `(w * ny + iy) * nx + ix` --; `inside`, `outside`, `dropped` are `{ white, yolk }` counts.  The
+--- mean velocity of a cell is `(tonumber(svx[i]) / 65536) / count[i]`, see `field_velocity`.
+function SimulationHandler:field(x0, y0, cell, nx, ny, options)
+    options = options or {}
+    local mask = _collider_types[options.types or "both"]
+    local path = _field_paths[options.path or "auto"]
+    if mask == nil or path == nil or type(nx) ~= "number" or type(ny) ~= "number" or nx < 1 or ny < 1 or nx * ny > _field_max_cells
+        or nx ~= math.floor(nx) or ny ~= math.floor(ny) then
+        log.error("In SimulationHandler.field: expected (x0, y0, cell, nx, ny, { types = ..., velocity = ..., path = ... }) with nx * ny in 1 .. 1048576")
+        return nil
+    end
+    local words = 2 * nx * ny
+    local spec = ffi.new("egg_field_spec", { x0 = x0, y0 = y0, cell = cell, nx = nx, ny = ny, type_mask = mask, path = path })
+    local count = ffi.new("int32_t[?]", words)
+    local svx = options.velocity and ffi.new("int64_t[?]", words) or nil
+    local svy = options.velocity and ffi.new("int64_t[?]", words) or nil
+    local planes = ffi.new("egg_field_planes", { count = count, svx = svx, svy = svy })
+    local totals = ffi.new("egg_field_totals")
+    if self:_check(lib.egg_field(self._h, spec, planes, totals)) ~= 0 then return nil end
+    local function pair(a) return { tonumber(a[0]), tonumber(a[1]) } end
+    return { nx = nx, ny = ny, count = count, svx = svx, svy = svy, inside = pair(totals.inside), outside = pair(totals.outside),
+             dropped = pair(totals.dropped), units_tiled = totals.units_tiled, units_direct = totals.units_direct }
+end
+
+--- the mean velocity vx, vy of type `w` (0 white, 1 yolk) in cell (ix, iy) of a field taken with `velocity = true`; nil while
+--- the cell is empty
+function SimulationHandler:field_velocity(field, w, ix, iy)
+    local i = (w * field.ny + iy) * field.nx + ix
+    local n = field.count[i]
+    if n == 0 or field.svx == nil then return nil end
+    return (tonumber(field.svx[i]) / _field_velocity_scale) / n, (tonumber(field.svy[i]) / _field_velocity_scale) / n
 end
 
 -- Not in the reference, which has no forces as it has no boundary: force fields of the relaxed step (egg_set_forces in

@@ -51,7 +51,7 @@ import warnings
 import numpy as np
 
 from . import _ffi
-from .simulation_handler import EggError, EggWarning, _HandlerSurface, _assert_types, _is_nan
+from .simulation_handler import EggError, EggWarning, Field, _HandlerSurface, _assert_types, _is_nan
 
 
 class SlabConflict(RuntimeError):
@@ -766,6 +766,25 @@ class ShardedSimulationHandler(_HandlerSurface):
                 pair.append(found)
             best.append(tuple(pair))
         return self._probe_hits(best)
+
+    def field(self, origin, cell, shape, types="both", velocity=False, path="auto"):
+        """SimulationHandler.field over all ranks (a collective: every rank calls it with the same grid).  Every rank bins the
+        particles it owns; one all_reduce(SUM) per plane and one for the totals add them.  The planes are integers, so the
+        result equals one handle's bit for bit (units_tiled / units_direct count the ranks' units).  Nothing travels in a
+        step.  There is no field_to here: the planes of the ranks live on different devices."""
+        spec = self._c_field_spec(origin, cell, shape, types, path)
+        count, svx, svy, t = self.local._field_planes(spec, bool(velocity))
+        flat = np.array(list(t.inside) + list(t.outside) + list(t.dropped) + [t.units_tiled, t.units_direct], dtype=np.int64)
+        planes = []
+        for plane in (count, svx, svy, flat):
+            if plane is not None and self.world > 1:
+                tot = self.torch.from_numpy(plane).to(self.device)
+                self.dist.all_reduce(tot, op=self.dist.ReduceOp.SUM)
+                plane = tot.cpu().numpy()
+            planes.append(plane)
+        count, svx, svy, flat = planes
+        flat = [int(v) for v in flat]
+        return Field(count, svx, svy, tuple(flat[0:2]), tuple(flat[2:4]), tuple(flat[4:6]), flat[6], flat[7])
 
     def set_forces(self, forces):
         """SimulationHandler.set_forces on every rank alike (the same call on every rank; relaxed order only).  Nothing

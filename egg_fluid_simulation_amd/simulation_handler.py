@@ -31,6 +31,29 @@ class EggError(RuntimeError):
 ProbeHit = collections.namedtuple("ProbeHit", "id index score x y radius")
 
 
+class Field(collections.namedtuple("Field", "count svx svy inside outside dropped units_tiled units_direct")):
+    """The particles binned into a grid (egg_field): `count` an int32 and `svx`, `svy` int64 numpy planes of shape (2, ny, nx),
+    [0] white and [1] yolk, the sums of the velocities scaled by 2^16 and rounded (None without velocity=True); `inside`,
+    `outside`, `dropped` the (white, yolk) particles by fate; `units_tiled`, `units_direct` how the device did the work."""
+    __slots__ = ()
+
+    def velocity(self):
+        """the mean velocity per cell as (2, ny, nx, 2) doubles: `((double)svx / 2^16) / (double)count` and likewise for y,
+        NaN where the count is 0"""
+        if self.svx is None or self.svy is None:
+            raise EggError("Field.velocity: the field was taken without velocity=True")
+        out = np.full(self.count.shape + (2,), np.nan, dtype=np.float64)
+        some = self.count != 0
+        n = self.count[some].astype(np.float64)
+        out[..., 0][some] = (self.svx[some].astype(np.float64) / _ffi.FIELD_VELOCITY_SCALE) / n
+        out[..., 1][some] = (self.svy[some].astype(np.float64) / _ffi.FIELD_VELOCITY_SCALE) / n
+        return out
+
+
+# what egg_field_to reports beside the planes it fills on the device: Field without its planes
+FieldTotals = collections.namedtuple("FieldTotals", "inside outside dropped units_tiled units_direct")
+
+
 class EggWarning(UserWarning):
     """The reference's `log.warning` (a line on stderr)."""
 
@@ -594,6 +617,60 @@ class _HandlerSurface:
         x0, y0, x1, y1 = float(x0), float(y0), float(x1), float(y1)
         t = first[1].score
         return first + ((x0 + t * (x1 - x0), y0 + t * (y1 - y0)),)
+
+    # ------------------------------------------------ fields (egg_field)
+    @staticmethod
+    def _c_field_spec(origin, cell, shape, types, path):
+        """the grid of a call as an egg_field_spec; what only the host can check (shapes, names, types) is checked here,
+        before any call into the library, the values by the library as well"""
+        def pair(v, what, names):
+            v = tuple(v) if isinstance(v, (tuple, list, np.ndarray)) else ()
+            if len(v) != 2:
+                raise EggError("field: %s must be (%s), not %r" % (what, names, v if v else None))
+            return v
+        x0, y0 = pair(origin, "origin", "x0, y0")
+        nx, ny = pair(shape, "shape", "nx, ny")
+        try:
+            x0, y0, cell = float(x0), float(y0), float(cell)
+        except (TypeError, ValueError):
+            raise EggError("field: origin and cell must be numbers") from None
+        for v in (nx, ny):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise EggError("field: shape must be two integers (nx, ny), not %r" % ((nx, ny),))
+        nx, ny = int(nx), int(ny)
+        if nx < 1 or ny < 1 or nx * ny > _ffi.FIELD_MAX_CELLS:
+            raise EggError("field: shape (%d, %d): nx and ny are at least 1 and nx * ny at most %d" % (nx, ny, _ffi.FIELD_MAX_CELLS))
+        if not (math.isfinite(cell) and cell > 0.0 and math.isfinite(1.0 / cell)):
+            raise EggError("field: cell must be finite and above 0, with a finite inverse, not %r" % cell)
+        if not (math.isfinite(x0) and math.isfinite(y0)):
+            raise EggError("field: origin (%r, %r) is not finite" % (x0, y0))
+        mask = _HandlerSurface._probe_mask(types, "field")
+        if not isinstance(path, str) or path not in _ffi.FIELD_PATHS:
+            raise EggError("field: path must be 'auto' or 'direct', not %r" % (path,))
+        return _ffi.EggFieldSpec(x0, y0, cell, nx, ny, mask, _ffi.FIELD_PATHS[path])
+
+    def _field_planes(self, spec, velocity):
+        """one call of this object's entry point into fresh numpy planes: (count, svx, svy, totals)"""
+        count = np.zeros((2, spec.ny, spec.nx), dtype=np.int32)
+        svx = np.zeros((2, spec.ny, spec.nx), dtype=np.int64) if velocity else None
+        svy = np.zeros((2, spec.ny, spec.nx), dtype=np.int64) if velocity else None
+        planes = _ffi.EggFieldPlanes(count.ctypes.data, svx.ctypes.data if velocity else None, svy.ctypes.data if velocity else None)
+        totals = _ffi.EggFieldTotals()
+        self._check(self._c("field")(C.byref(spec), C.byref(planes), C.byref(totals)))
+        return count, svx, svy, totals
+
+    def field(self, origin, cell, shape, types="both", velocity=False, path="auto"):
+        """The egg as a map (either solver order): the committed particles binned into the grid of
+        `shape = (nx, ny)` square cells of side `cell` whose cell (0, 0) has its lower corner at `origin = (x0, y0)`.  Returns a
+        `Field(count, svx, svy, inside, outside, dropped, units_tiled, units_direct)`: numpy planes of shape (2, ny, nx), [0]
+        white and [1] yolk; with `velocity=True` also the int64 sums of the velocities scaled by 2^16, from which
+        `Field.velocity()` derives the mean velocity per cell.  A particle is binned by its centre: cell
+        `(int)((x - x0) * (1 / cell))`, inside iff that value is in [0, nx) -- and likewise for y.  types = "both" | "white" |
+        "yolk"; path = "direct" is a test hook with the same answer.  Reads the committed state; stores nothing.  Raises
+        EggError for a bad grid."""
+        spec = self._c_field_spec(origin, cell, shape, types, path)
+        count, svx, svy, t = self._field_planes(spec, bool(velocity))
+        return Field(count, svx, svy, tuple(t.inside), tuple(t.outside), tuple(t.dropped), t.units_tiled, t.units_direct)
 
     # ------------------------------------------------ collider bodies (egg_set_collider_bodies, DESIGN.md section 2.7)
     _BODIES_LIMIT =("collider bodies: the device integrates a body from the loads of one handle, so bodies run on a single "
@@ -1568,6 +1645,41 @@ class SimulationHandler(_HandlerSurface):
                                                 C.c_void_p(int(color_ptr)) if color_ptr else None, int(cap), C.byref(got),
                                                 C.byref(version)))
         return got.value, int(version.value)
+
+    # ------------------------------------------- fields into planes on the device (egg_field_to)
+    def field_to(self, origin, cell, shape, count, svx=None, svy=None, types="both", path="auto"):
+        """field() into caller-owned planes on this handle's device: `count` an int32 and `svx`, `svy` (both or neither) int64
+        planes of shape (2, ny, nx), contiguous, given as objects with `data_ptr()` (a torch tensor) or as addresses.  The
+        call zeroes them itself and they are complete when it returns; nothing is copied to the host.  Returns
+        `FieldTotals(inside, outside, dropped, units_tiled, units_direct)`.  (A process that uses torch tensors imports torch
+        before this package loads its library: torch brings its own HIP runtime.)"""
+        spec = self._c_field_spec(origin, cell, shape, types, path)
+        if count is None:
+            raise EggError("field_to: count is required")
+        if (svx is None) != (svy is None):
+            raise EggError("field_to: svx and svy are given together or not at all")
+        words = 2 * spec.nx * spec.ny
+
+        def address(plane, what, word, dtype):
+            if plane is None:
+                return None
+            if hasattr(plane, "data_ptr"):
+                if str(getattr(plane, "dtype", dtype)).split(".")[-1] != dtype:
+                    raise EggError("field_to: %s must hold %s, not %s" % (what, dtype, plane.dtype))
+                if hasattr(plane, "numel") and plane.numel() != words:
+                    raise EggError("field_to: %s must hold 2 x %d x %d elements, not %d" % (what, spec.ny, spec.nx, plane.numel()))
+                if hasattr(plane, "is_contiguous") and not plane.is_contiguous():
+                    raise EggError("field_to: %s must be contiguous" % what)
+                plane = plane.data_ptr()
+            if isinstance(plane, bool) or not isinstance(plane, (int, np.integer)) or int(plane) <= 0:
+                raise EggError("field_to: %s must be an object with data_ptr() or an address, not %r" % (what, plane))
+            if int(plane) % word:
+                raise EggError("field_to: %s is not aligned to %d bytes" % (what, word))
+            return int(plane)
+        planes = _ffi.EggFieldPlanes(address(count, "count", 4, "int32"), address(svx, "svx", 8, "int64"), address(svy, "svy", 8, "int64"))
+        t = _ffi.EggFieldTotals()
+        self._check(self._lib.egg_field_to(self._h, C.byref(spec), C.byref(planes), C.byref(t)))
+        return FieldTotals(tuple(t.inside), tuple(t.outside), tuple(t.dropped), t.units_tiled, t.units_direct)
 
     def instances_begin(self, types=(0, 1)):
         """Launch the pack of instances() for `types` and the copy into pinned buffers the handle owns; returns at once.

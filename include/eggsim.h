@@ -1002,6 +1002,57 @@ typedef struct { int32_t kind; int32_t type_mask; double p[5]; } egg_probe_query
 typedef struct { int64_t id, key; int32_t index, found; double score, x, y, radius; } egg_probe_hit;                          /* 56 bytes */
 int egg_probe(egg_handle *h, int32_t n, const egg_probe_query *probes, egg_probe_hit *hits /* [n][2]: [0] white, [1] yolk */);
 
+/* ---- fields: the particles binned into a caller-set grid (csrc/eggsim_fields.hip) ----
+ * Not in the reference.  Sensors answer "what is inside this region", a probe "what is here"; a field answers "where is the
+ * egg" with a MAP: per cell of a regular grid and particle type the number of particles and, on request, the integer sums
+ * their mean velocity follows from -- an occupancy map, a velocity map, an observation tensor.  A call is STATELESS: the
+ * caller passes the grid with the call and the handle stores neither the grid nor an answer; nothing is cached.  Fields only
+ * observe: a step launches exactly the kernels it launches without them, and a call changes no particle; of egg_get_stats
+ * only kernel_launches moves, by one per call that launches.  They read the COMMITTED state -- the arrays
+ * egg_download_particles returns for EGG_FIELD_X / EGG_FIELD_Y / EGG_FIELD_VX / EGG_FIELD_VY, not interpolated --, so they
+ * work in exact and in relaxed order alike.
+ * The grid has nx x ny square cells of side `cell` px, cell (0, 0) with its lower corner at (x0, y0).  Take a particle of
+ * type w whose bit is in type_mask (bit 0 white, bit 1 yolk) at the committed (x, y) with the committed velocity (vx, vy).
+ * FP64 in exactly this order, no contraction: inv = 1.0 / cell, computed ONCE on the host; fx = (x - x0) * inv;
+ * fy = (y - y0) * inv.  The particle is INSIDE iff fx >= 0.0 && fx < (double)nx && fy >= 0.0 && fy < (double)ny; every
+ * comparison is false for a NaN, so a NaN position is outside.  Its cell is ix = (int)fx, iy = (int)fy (truncation; -0.0 is
+ * cell 0), index iy * nx + ix.  Only the particle's centre counts: its radius is not read.
+ *   outside     outside[w] += 1 and nothing else.
+ *   dropped     inside, svx / svy requested, and vx * EGG_FIELD_VELOCITY_SCALE or vy * EGG_FIELD_VELOCITY_SCALE is not
+ *               finite or reaches 2^53 in magnitude: dropped[w] += 1 and nothing else (the sensors' rule).
+ *   counted     otherwise: inside[w] += 1, count[w][cell] += 1, svx[w][cell] += llrint(vx * EGG_FIELD_VELOCITY_SCALE),
+ *               svy[w][cell] += llrint(vy * EGG_FIELD_VELOCITY_SCALE) (int64, round to nearest, ties to even).
+ * Every plane is [2][ny][nx], row-major, [0] white, [1] yolk.  count is required; svx and svy are given together or not at
+ * all, and without them the velocities are not read and dropped is 0.  The planes of a type outside the mask, or without
+ * particles, are all zero.  inside[w] + outside[w] + dropped[w] = the particles of type w, for every w in the mask.  The mean
+ * velocity of a cell is ((double)svx / EGG_FIELD_VELOCITY_SCALE) / (double)count, in that order, and likewise for y; there is
+ * none while the count is 0.  The resolution is 2^-16 px per unit of time.  Integer addition is associative: a device group
+ * and sharded ranks answer with one handle's numbers bit for bit.  Every term is below 2^53 in magnitude, so a cell's sum
+ * wraps only beyond 2^63: not with fewer than 1,024 particles in one cell, whatever their velocities.  count is 32 bits: a
+ * type holds fewer than 2^31 particles.
+ * units_tiled / units_direct tell how the device did the work (units of at most 1,024 particles whose cells were summed on
+ * chip first, or added one by one); they depend on the scene's layout in memory, not only on its particles, and are no
+ * part of the answer.  path = EGG_FIELD_PATH_DIRECT sends every unit down the second way: a test hook, the planes are equal.
+ * egg_field checks everything before it launches or writes anything and returns EGG_ERR_INVALID_ARGUMENT, naming the field,
+ * with planes and totals untouched, for: a NULL spec or NULL planes; nx or ny below 1 or nx * ny above EGG_FIELD_MAX_CELLS;
+ * a cell that is not finite, not above 0 or whose inverse is not finite; x0 or y0 not finite; a type_mask outside 1 .. 3; an
+ * unknown path; count NULL; only one of svx / svy.  totals may be NULL.  Refused while a step is in flight (egg_step_begin
+ * or egg_rx_begin open).  A scene without covered particles zero-fills the planes and launches nothing.
+ * egg_field writes planes in host memory.  egg_field_to writes planes that live on the handle's device (a torch tensor's
+ * data_ptr()): it zeroes them itself, adds into them in place -- no copy -- and returns after the stream is idle, so the
+ * tensor is ready on return.  It refuses, as above, a plane pointer that is not aligned to its word (4 bytes for count, 8
+ * for svx / svy), that is not memory of the handle's device, or whose allocation ends before the plane does.
+ * Limits: centres only (no splat by radius, no area or mass plane); no per-batch planes; no field that rides on a collider;
+ * no egg_field_to for groups or sharded ranks; at most 2^20 cells per call. */
+#define EGG_FIELD_MAX_CELLS (1 << 20)          /* nx * ny */
+#define EGG_FIELD_VELOCITY_SCALE 65536.0       /* 2^16 */
+enum { EGG_FIELD_PATH_AUTO = 0, EGG_FIELD_PATH_DIRECT = 1 };   /* DIRECT: test hook, see the kernel */
+typedef struct { double x0, y0, cell; int32_t nx, ny, type_mask, path; } egg_field_spec;     /* 40 bytes */
+typedef struct { int32_t *count; int64_t *svx, *svy; } egg_field_planes;                     /* each [2][ny][nx], row-major, [0] white [1] yolk */
+typedef struct { int64_t inside[2], outside[2], dropped[2]; int32_t units_tiled, units_direct; } egg_field_totals; /* 56 bytes */
+int egg_field(egg_handle *h, const egg_field_spec *spec, const egg_field_planes *host_out, egg_field_totals *totals);
+int egg_field_to(egg_handle *h, const egg_field_spec *spec, const egg_field_planes *device_out, egg_field_totals *totals);
+
 /* ---- several GPUs in one process (csrc/eggsim_group.cpp) -------------------------------------------------------
  * The multi-device form of the handle for a host that is ONE process (the LuaJIT wrapper): one egg_handle per device
  * behind one egg_group, x-slabs [cuts[k], cuts[k + 1]) of the plane per device (cuts: n_devices + 1 ascending values;
@@ -1090,6 +1141,11 @@ int egg_group_read_sensor_batches(egg_group *g, int64_t n_ids, const int64_t *id
  * one handle that holds every batch, bit for bit, whichever device owns tied batches.  A failure on any handle writes
  * nothing. */
 int egg_group_probe(egg_group *g, int32_t n, const egg_probe_query *probes, egg_probe_hit *hits /* [n][2] */);
+/* egg_field on every handle of the group with the same grid; the handles' planes and totals are added on the host (two's
+ * complement: the sum of the handles' sums is the sum over all their particles).  The result equals one handle that holds
+ * every batch, bit for bit, units_tiled / units_direct aside.  A failure on any handle writes nothing.  There is no
+ * egg_group_field_to: a group's particles live on several devices. */
+int egg_group_field(egg_group *g, const egg_field_spec *spec, const egg_field_planes *host_out, egg_field_totals *totals);
 /* egg_set_forces for every handle of the group alike, with its rules (relaxed order only; back to exact order only with
  * an empty list); a refused list changes no handle.  Every device accelerates only the particles it owns: the results
  * equal one handle's.  A group whose handles differ in their lists refuses to step. */
