@@ -219,6 +219,19 @@ FIELD_PATHS = {"auto": FIELD_PATH_AUTO, "direct": FIELD_PATH_DIRECT}  # direct: 
 FIELD_TYPES = dict(COLLIDER_TYPES)  # type_mask by name; the wrappers take the mask itself (1, 2, 3) as well
 
 
+class EggPiecesSpec(C.Structure):  # egg_pieces_spec: the reach per type in units of (radius[i] + radius[j]) and the type mask (24 bytes)
+    _fields_ = [("reach", C.c_double * 2), ("type_mask", C.c_int32), ("reserved", C.c_int32)]
+
+
+class EggPieceSummary(C.Structure):  # egg_piece_summary: the pieces of one atom and its body's position sums (40 bytes)
+    _fields_ = [("n", C.c_int32), ("pieces", C.c_int32), ("largest", C.c_int32), ("first", C.c_int32), ("singles", C.c_int32),
+                ("dropped", C.c_int32), ("sx", C.c_int64), ("sy", C.c_int64)]
+
+
+PIECES_MAX_ATOM = 4096  # EGG_PIECES_MAX_ATOM: particles of one type of one batch
+PIECES_TYPES = dict(COLLIDER_TYPES)  # type_mask by name; the wrappers take the mask itself (1, 2, 3) as well
+
+
 class EggRxBox(C.Structure):  # egg_rx_box: a cell box of the relaxed halo between processes
     _fields_ = [("lo_x", C.c_int32), ("lo_y", C.c_int32), ("hi_x", C.c_int32), ("hi_y", C.c_int32), ("empty", C.c_int32)]
 
@@ -313,6 +326,8 @@ _SIGNATURES = {
     "egg_field": (C.c_int, [C.c_void_p, C.POINTER(EggFieldSpec), C.POINTER(EggFieldPlanes), C.POINTER(EggFieldTotals)]),
     "egg_field_to": (C.c_int, [C.c_void_p, C.POINTER(EggFieldSpec), C.POINTER(EggFieldPlanes), C.POINTER(EggFieldTotals)]),
     "egg_group_field": (C.c_int, [C.c_void_p, C.POINTER(EggFieldSpec), C.POINTER(EggFieldPlanes), C.POINTER(EggFieldTotals)]),
+    "egg_pieces": (C.c_int, [C.c_void_p, C.POINTER(EggPiecesSpec), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "egg_group_pieces": (C.c_int, [C.c_void_p, C.POINTER(EggPiecesSpec), C.c_int64, C.c_void_p, C.c_void_p]),
     "egg_group_set_sensors": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggSensor)]),
     "egg_group_get_sensors": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggSensor), C.POINTER(C.c_int32)]),
     "egg_group_read_sensors": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggSensorReading), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),

@@ -950,3 +950,33 @@ struct EggFieldArgs {
     unsigned long long *svx, *svy;    // [2][ny][nx] two's complement sums, zeroed before the launch (<true> only)
     unsigned long long *totals;       // [EGG_FD_TOTALS], zeroed before the launch
 };
+
+// ---------------------------------------------------------------------------------------------
+// Pieces (eggsim_pieces.hip; include/eggsim.h, "pieces"): the connected pieces of every requested atom
+// (the particles of one type of one batch) under the link rule d2 <= L * L, L = reach[type] * (radius[i] + radius[j]).  One
+// workgroup per task; the atom's positions, radii, labels and piece sizes stay in dynamic LDS for the whole solve.  Nothing
+// here is read or written by a step.
+#define EGG_PC_MAX_ATOM 4096         // = EGG_PIECES_MAX_ATOM: 32 bytes of LDS per particle, 128 KB of a compute unit's 160
+#define EGG_PC_WAVE_ATOM 512         // atoms up to this size go to the one-wave class, larger ones to the 256-thread class
+#define EGG_PC_BLOCK 256             // threads of the second class
+#define EGG_PC_OWN 4                 // particles a thread tests against one j read from LDS
+#define EGG_PC_LDS_PER_PARTICLE 32   // x, y (16), radius (8), label (4), size (4)
+#define EGG_PC_TAIL 64               // bytes of LDS behind the particles: flags and the waves' partial results
+struct EggPiecesTask {               // one requested atom
+    int32_t offset, count;           // its particles within the type's arrays
+    int32_t type;                    // 0 white, 1 yolk
+    int32_t slot;                    // its record in `out`
+};
+struct EggPieceSummary {             // = egg_piece_summary (40 bytes)
+    int32_t n, pieces, largest, first, singles, dropped;
+    long long sx, sy;
+};
+struct EggPiecesArgs {
+    const double *x[2], *y[2], *radius[2];  // the committed positions and the radii per type
+    const EggPiecesTask *tasks;             // the tasks of this launch's class
+    int32_t n_tasks;
+    double reach[2];
+    EggPieceSummary *out;                   // one record per task, at task.slot; every task has a slot of its own
+    int32_t *labels[2];                     // per type [n] filled with -1 before the launch, or null
+    int32_t *sweeps;                        // sweeps per task at task.slot, or null (a developer figure: it depends on the schedule)
+};

@@ -980,6 +980,49 @@ int egg_group_field(egg_group *g, const egg_field_spec *spec, const egg_field_pl
     return EGG_OK;
 }
 
+// Pieces (include/eggsim.h, "pieces"): a batch lives wholly on one handle, so every id is routed to its owner and the owner's
+// records are copied to the caller's rows.  Nothing is written before every handle has answered.
+int egg_group_pieces(egg_group *g, const egg_pieces_spec *spec, int64_t n_ids, const int64_t *ids, egg_piece_summary *out) {
+    if (!g || g->h.empty()) return EGG_ERR_INVALID_ARGUMENT;
+    if (!spec) return gfail(g, EGG_ERR_INVALID_ARGUMENT, "egg_group_pieces: spec is NULL");
+    if (!out) return gfail(g, EGG_ERR_INVALID_ARGUMENT, "egg_group_pieces: out is NULL");
+    for (int w = 0; w < 2; ++w)  // (checked here as well: a group without a requested batch asks no handle)
+        if (!std::isfinite(spec->reach[w]) || !(spec->reach[w] > 0.0))
+            return gfail(g, EGG_ERR_INVALID_ARGUMENT, "egg_group_pieces: reach[%d] = %g: it is finite and above 0", w, spec->reach[w]);
+    if (spec->type_mask < 1 || spec->type_mask > 3)
+        return gfail(g, EGG_ERR_INVALID_ARGUMENT, "egg_group_pieces: type_mask %d (bit 0 white, bit 1 yolk, never 0)", (int)spec->type_mask);
+    if (n_ids < 0 || (n_ids > 0 && !ids) || (n_ids == 0 && ids))
+        return gfail(g, EGG_ERR_INVALID_ARGUMENT, "egg_group_pieces: n_ids = %lld %s a list (0 and NULL mean every live batch)", (long long)n_ids,
+                     ids ? "with" : "without");
+    for (int64_t i = 0; i < n_ids; ++i)  // (before anything is written)
+        if (ids[i] < 1 || ids[i] > (int64_t)g->batch.size() || !g->batch[(size_t)ids[i] - 1].alive)
+            return gfail(g, EGG_ERR_UNKNOWN_ID, "egg_group_pieces: no batch with id `%lld`", (long long)ids[i]);
+    std::vector<int64_t> every;
+    if (n_ids == 0) {
+        for (size_t i = 0; i < g->batch.size(); ++i)
+            if (g->batch[i].alive) every.push_back((int64_t)i + 1);
+        ids = every.data();
+        n_ids = (int64_t)every.size();
+    }
+    std::vector<egg_piece_summary> all(2 * (size_t)n_ids, egg_piece_summary{});
+    for (size_t k = 0; k < g->h.size(); ++k) {
+        std::vector<int64_t> local, where;
+        for (int64_t i = 0; i < n_ids; ++i) {
+            const egg_group::Rec &r = g->batch[(size_t)ids[i] - 1];
+            if (r.owner != (int)k) continue;
+            local.push_back(r.local);
+            where.push_back(i);
+        }
+        if (local.empty()) continue;
+        std::vector<egg_piece_summary> part(2 * local.size(), egg_piece_summary{});
+        const int rc = egg_pieces(g->h[k], spec, (int64_t)local.size(), local.data(), part.data(), nullptr, nullptr);
+        if (rc < 0) return gfail(g, rc, "device %d: %s", (int)k, egg_last_error(g->h[k]));
+        for (size_t q = 0; q < local.size(); ++q) memcpy(&all[2 * (size_t)where[q]], &part[2 * q], 2 * sizeof(egg_piece_summary));
+    }
+    if (!all.empty()) memcpy(out, all.data(), all.size() * sizeof(egg_piece_summary));
+    return EGG_OK;
+}
+
 int egg_group_get_collider_grips(egg_group *g, int64_t grips[2]) {
     if (!g) return EGG_ERR_INVALID_ARGUMENT;
     if (!grips) return gfail(g, EGG_ERR_INVALID_ARGUMENT, "egg_group_get_collider_grips: grips is NULL");

@@ -17,6 +17,7 @@
 //   eggsim_host_sensors.hip        egg_set_sensors / egg_read_sensors / egg_read_sensor_batches: the list, the unit tables, the launches
 //   eggsim_host_probes.hip         egg_probe: the checks, the unit table, the two launches, index -> (batch, key, index in the batch)
 //   eggsim_host_fields.hip         egg_field / egg_field_to: the checks, the unit table, the zeroing, the one launch, the copies back
+//   eggsim_host_pieces.hip         egg_pieces: the checks, the task table, at most two launches, the one copy of the records back
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -145,6 +146,8 @@ extern "C" __global__ void egg_probe_scan_kernel(EggProbeArgs A);
 extern "C" __global__ void egg_probe_finish_kernel(EggProbeFinishArgs A);
 extern "C" __global__ void egg_field_count_kernel(EggFieldArgs A);
 extern "C" __global__ void egg_field_velocity_kernel(EggFieldArgs A);
+extern "C" __global__ void egg_pieces_wave_kernel(EggPiecesArgs A);
+extern "C" __global__ void egg_pieces_block_kernel(EggPiecesArgs A);
 extern "C" __global__ void egg_render_count_kernel(EggRenderArgs A);
 extern "C" __global__ void egg_render_fill_kernel(EggRenderArgs A);
 extern "C" __global__ void egg_render_scan_kernel(EggRenderArgs A);
@@ -421,6 +424,7 @@ struct InstanceState;  // staging and pinned buffers of egg_get_instances / egg_
 struct SensorState;  // device copy of the sensor list, unit tables and partials of a read (eggsim_host_sensors.hip)
 struct ProbeState;  // unit table, partials and winners of an egg_probe call (eggsim_host_probes.hip)
 struct FieldState;  // unit table, planes and totals of an egg_field call (eggsim_host_fields.hip)
+struct PiecesState;  // task table, records and labels of an egg_pieces call (eggsim_host_pieces.hip)
 }
 using namespace egghost;
 
@@ -593,6 +597,9 @@ struct egg_handle {
     // fields (egg_field / egg_field_to; either solver order): what a call needs on the device, allocated by the first call
     // that launches.  A call stores no grid and no answer; no step reads this.
     std::shared_ptr<egghost::FieldState> field_state;
+    // pieces (egg_pieces; either solver order): what a call needs on the device, allocated by the first call that launches.
+    // A call stores no answer; no step reads this.
+    std::shared_ptr<egghost::PiecesState> pieces_state;
     // headless renderer (eggsim_render.hip)
     struct Render {
         egg_render_config cfg[2];

@@ -129,6 +129,9 @@ typedef struct { double x0, y0, cell; int32_t nx, ny, type_mask, path; } egg_fie
 typedef struct { int32_t *count; int64_t *svx, *svy; } egg_field_planes;
 typedef struct { int64_t inside[2], outside[2], dropped[2]; int32_t units_tiled, units_direct; } egg_field_totals;
 int egg_field(egg_handle *h, const egg_field_spec *spec, const egg_field_planes *host_out, egg_field_totals *totals);
+typedef struct { double reach[2]; int32_t type_mask; int32_t reserved; } egg_pieces_spec;
+typedef struct { int32_t n, pieces, largest, first, singles, dropped; int64_t sx, sy; } egg_piece_summary;
+int egg_pieces(egg_handle *h, const egg_pieces_spec *spec, int64_t n_ids, const int64_t *ids, egg_piece_summary *out, int32_t *white_labels, int32_t *yolk_labels);
 typedef struct egg_group egg_group;
 int egg_group_set_solver_order(egg_group *g, int32_t order, double relaxation);
 int egg_group_set_cohesion(egg_group *g, int32_t mode);
@@ -995,6 +998,83 @@ function SimulationHandler:field_velocity(field, w, ix, iy)
     local n = field.count[i]
     if n == 0 or field.svx == nil then return nil end
     return (tonumber(field.svx[i]) / _field_velocity_scale) / n, (tonumber(field.svy[i]) / _field_velocity_scale) / n
+end
+
+-- Not in the reference: pieces (egg_pieces in include/eggsim.h; DESIGN.md section 2.11).  Is the egg still one egg: the
+-- connected pieces of each batch's white and yolk under the link rule d2 <= (reach * (ra + rb))^2, from the committed
+-- state; either solver order.  A call stores nothing and only observes.
+local _pieces_max_atom = 4096 -- EGG_PIECES_MAX_ATOM
+
+--- the egg_pieces_spec of a call, or nil: `reach` nil (per type max(collision_overlap_factor,
+--- cohesion_interaction_distance_factor) of the config), a number (both types) or `{ white, yolk }`
+function SimulationHandler:_pieces_spec(reach, types, scope)
+    local mask = _collider_types[types or "both"]
+    local rw, ry
+    if reach == nil then
+        rw = math.max(self._white_config.collision_overlap_factor, self._white_config.cohesion_interaction_distance_factor)
+        ry = math.max(self._yolk_config.collision_overlap_factor, self._yolk_config.cohesion_interaction_distance_factor)
+    elseif type(reach) == "table" then
+        rw, ry = reach[1], reach[2]
+    else
+        rw, ry = reach, reach
+    end
+    local function good(v) return type(v) == "number" and v > 0 and v < math.huge end
+    if mask == nil or not good(rw) or not good(ry) then
+        log.error("In SimulationHandler." .. scope .. ": expected (..., reach, types) with reach nil, a number above 0 or { white, yolk } and types \"both\" | \"white\" | \"yolk\"")
+        return nil
+    end
+    return ffi.new("egg_pieces_spec", { reach = { rw, ry }, type_mask = mask })
+end
+
+local function _piece_summary(rec)
+    if rec.n == 0 then return nil end
+    local kept = rec.largest - rec.dropped
+    local one = { n = rec.n, pieces = rec.pieces, largest = rec.largest, first = rec.first, singles = rec.singles, dropped = rec.dropped }
+    if kept > 0 then
+        one.x = (tonumber(rec.sx) / _sensor_scale) / kept
+        one.y = (tonumber(rec.sy) / _sensor_scale) / kept
+    end
+    return one
+end
+
+--- per id of `ids` (nil: every batch of list_ids(), in that order) `{ white = summary or nil, yolk = summary or nil }`, a
+--- summary `{ n, pieces, largest, first, singles, dropped, x, y }` by name: `pieces` connected pieces, `singles` of them of one
+--- particle; the body (the largest piece, the lower label among equals) has `largest` particles, the label `first` and the
+--- centroid `x, y` (nil while every body particle was dropped).  An id may repeat.
+function SimulationHandler:pieces(ids, reach, types)
+    local spec = self:_pieces_spec(reach, types, "pieces")
+    if spec == nil then return nil end
+    local listed = ids or self:list_ids()
+    local n = #listed
+    if n == 0 then return {} end
+    local c_ids = ffi.new("int64_t[?]", n)
+    for i, id in ipairs(listed) do c_ids[i - 1] = id end
+    local out = ffi.new("egg_piece_summary[?]", 2 * n)
+    if self:_check(lib.egg_pieces(self._h, spec, n, c_ids, out, nil, nil)) ~= 0 then return nil end
+    local res = {}
+    for i = 0, n - 1 do res[i + 1] = { white = _piece_summary(out[2 * i]), yolk = _piece_summary(out[2 * i + 1]) } end
+    return res
+end
+
+--- true iff every covered atom of the batch -- its white, its yolk, by `types` -- is one piece
+function SimulationHandler:is_whole(id, reach, types)
+    local res = self:pieces({ id }, reach, types)
+    if res == nil then return nil end
+    return (res[1].white == nil or res[1].white.pieces == 1) and (res[1].yolk == nil or res[1].yolk.pieces == 1)
+end
+
+--- `white, yolk`: 0-based `int32_t` arrays with the label of every particle in particle order -- the lowest index in the
+--- batch among the particles of its piece --, -1 throughout for a type that `types` leaves out; and their lengths
+function SimulationHandler:piece_labels(reach, types)
+    local spec = self:_pieces_spec(reach, types, "piece_labels")
+    if spec == nil then return nil end
+    local n_white, n_yolk = ffi.new("int64_t[1]"), ffi.new("int64_t[1]")
+    if self:_check(lib.egg_get_n_particles(self._h, -1, n_white, n_yolk)) ~= 0 then return nil end
+    local nw, ny = tonumber(n_white[0]), tonumber(n_yolk[0])
+    local white, yolk = ffi.new("int32_t[?]", math.max(nw, 1)), ffi.new("int32_t[?]", math.max(ny, 1))
+    local out = ffi.new("egg_piece_summary[?]", math.max(2 * #self:list_ids(), 1))
+    if self:_check(lib.egg_pieces(self._h, spec, 0, nil, out, white, yolk)) ~= 0 then return nil end
+    return white, yolk, nw, ny
 end
 
 -- Not in the reference, which has no forces as it has no boundary: force fields of the relaxed step (egg_set_forces in

@@ -786,6 +786,26 @@ class ShardedSimulationHandler(_HandlerSurface):
         flat = [int(v) for v in flat]
         return Field(count, svx, svy, tuple(flat[0:2]), tuple(flat[2:4]), tuple(flat[4:6]), flat[6], flat[7])
 
+    def pieces(self, ids=None, reach=None, types="both"):
+        """SimulationHandler.pieces over all ranks (a collective: every rank calls it with the same arguments).  A batch lives
+        wholly on one rank: every rank fills the records of the batches it owns and zeros elsewhere, one all_reduce(SUM) of an
+        int64 table adds them, so the records equal one handle's bit for bit.  Nothing travels in a step.  There is no
+        piece_labels here: the particles of the ranks live in different arrays."""
+        spec = self._c_pieces_spec(reach, types)
+        ids = self.list_ids() if ids is None else [int(i) for i in ids]
+        for gid in ids:
+            if gid not in self.owner:
+                raise EggError("[ERROR] In SimulationHandler.pieces: no batch with id `%d`" % gid)
+        table = np.zeros((len(ids), 2, 8), dtype=np.int64)
+        mine = [k for k, gid in enumerate(ids) if gid in self.local_id]
+        if mine:
+            table[mine] = self.local._piece_table(spec, np.ascontiguousarray([self.local_id[ids[k]] for k in mine], dtype=np.int64))
+        if self.world > 1 and ids:
+            tot = self.torch.from_numpy(table).to(self.device)
+            self.dist.all_reduce(tot, op=self.dist.ReduceOp.SUM)
+            table = tot.cpu().numpy()
+        return self._piece_summaries(table)
+
     def set_forces(self, forces):
         """SimulationHandler.set_forces on every rank alike (the same call on every rank; relaxed order only).  Nothing
         new travels: every rank accelerates the particles it owns."""

@@ -54,6 +54,19 @@ class Field(collections.namedtuple("Field", "count svx svy inside outside droppe
 FieldTotals = collections.namedtuple("FieldTotals", "inside outside dropped units_tiled units_direct")
 
 
+class PieceSummary(collections.namedtuple("PieceSummary", "n pieces largest first singles dropped x y")):
+    """The pieces of one atom -- the particles of one type of one batch -- (egg_pieces): `n` particles in `pieces` connected
+    pieces, `singles` of them of one particle; the body (the largest piece, the lower label among equals) has `largest`
+    particles and the label `first`, its lowest particle index in the batch; `x`, `y` is the body's centroid from the int64
+    sums, `(sx / 2^16) / (largest - dropped)`, None while every body particle was dropped."""
+    __slots__ = ()
+
+
+# egg_piece_summary as a numpy record (40 bytes)
+_PIECE_RECORD = np.dtype([("n", "<i4"), ("pieces", "<i4"), ("largest", "<i4"), ("first", "<i4"), ("singles", "<i4"), ("dropped", "<i4"),
+                          ("sx", "<i8"), ("sy", "<i8")])
+
+
 class EggWarning(UserWarning):
     """The reference's `log.warning` (a line on stderr)."""
 
@@ -671,6 +684,82 @@ class _HandlerSurface:
         spec = self._c_field_spec(origin, cell, shape, types, path)
         count, svx, svy, t = self._field_planes(spec, bool(velocity))
         return Field(count, svx, svy, tuple(t.inside), tuple(t.outside), tuple(t.dropped), t.units_tiled, t.units_direct)
+
+    # ------------------------------------------------ pieces (egg_pieces)
+    def _c_pieces_spec(self, reach, types, what="pieces"):
+        """the reach per type and the mask of a call as an egg_pieces_spec.  reach=None is, per type,
+        max(collision_overlap_factor, cohesion_interaction_distance_factor) of this object's config: the factor the solver
+        sizes its spatial hash by.  A number holds for both types, a pair is (white, yolk)."""
+        mask = _HandlerSurface._probe_mask(types, what)
+        if reach is None:
+            reach = tuple(max(float(cfg["collision_overlap_factor"]), float(cfg["cohesion_interaction_distance_factor"]))
+                          for cfg in (self._white_config, self._yolk_config))
+        elif isinstance(reach, (tuple, list, np.ndarray)):
+            reach = tuple(reach)
+        else:
+            reach = (reach, reach)
+        if len(reach) != 2:
+            raise EggError("%s: reach must be None, a number or (white, yolk), not %r" % (what, reach))
+        try:
+            reach = tuple(float(v) for v in reach)
+        except (TypeError, ValueError):
+            raise EggError("%s: reach must be None, a number or (white, yolk) numbers" % what) from None
+        for v in reach:
+            if not (math.isfinite(v) and v > 0.0):
+                raise EggError("%s: reach must be finite and above 0, not %r" % (what, v))
+        return _ffi.EggPiecesSpec((C.c_double * 2)(*reach), mask, 0)
+
+    @staticmethod
+    def _piece_ids(ids, what="pieces"):
+        """None (every live batch) or the listed ids as a contiguous int64 array"""
+        if ids is None:
+            return None
+        try:
+            return np.ascontiguousarray([int(i) for i in ids], dtype=np.int64)
+        except (TypeError, ValueError):
+            raise EggError("%s: ids must be None or a list of batch ids" % what) from None
+
+    def _piece_table(self, spec, ids):
+        """the raw records of one call of this object's entry point: an int64 array [n, 2, 8] of (n, pieces, largest, first,
+        singles, dropped, sx, sy), `ids` an int64 array (it may be empty: no batch is asked for) or None for every live batch"""
+        n = len(self.list_ids()) if ids is None else ids.size
+        if ids is not None and n == 0:
+            return np.zeros((0, 2, 8), dtype=np.int64)
+        out = np.zeros(max(2 * n, 1), dtype=_PIECE_RECORD)  # (egg_piece_summary, field for field)
+        args = (C.byref(spec), 0, None, out.ctypes.data) if ids is None else (C.byref(spec), n, ids.ctypes.data, out.ctypes.data)
+        if self._PREFIX == "egg_":
+            args += (None, None)
+        self._check(self._c("pieces")(*args))
+        return np.stack([out[name][:2 * n].astype(np.int64) for name in _PIECE_RECORD.names], axis=1).reshape(n, 2, 8)
+
+    @staticmethod
+    def _piece_summaries(table):
+        """per batch `(white, yolk)` of PieceSummary, or None where n == 0: the centroid by the library's two divisions"""
+        scale = _ffi.SENSOR_POSITION_SCALE
+        res = []
+        for pair in np.asarray(table, dtype=np.int64).reshape(-1, 2, 8).tolist():
+            row = []
+            for n, pieces, largest, first, singles, dropped, sx, sy in pair:
+                kept = largest - dropped
+                row.append(None if n == 0 else PieceSummary(n, pieces, largest, first, singles, dropped,
+                                                            (float(sx) / scale) / float(kept) if kept else None,
+                                                            (float(sy) / scale) / float(kept) if kept else None))
+            res.append(tuple(row))
+        return res
+
+    def pieces(self, ids=None, reach=None, types="both"):
+        """Is the egg still one egg (either solver order): per id (None: every batch of list_ids(), in
+        that order) `(white, yolk)`, each a `PieceSummary(n, pieces, largest, first, singles, dropped, x, y)` or None where the
+        batch has no particle of the type or `types` leaves it out.  Two particles of one type of one batch are linked iff
+        `d2 <= (reach * (ra + rb)) ** 2`; a piece is a connected component, the body the largest piece.  reach=None takes, per
+        type, max(collision_overlap_factor, cohesion_interaction_distance_factor) of the config; a number holds for both
+        types, a pair is (white, yolk).  Reads the committed state; stores nothing.  Raises EggError for an unknown id, a bad
+        reach, or a batch with more than 4,096 particles of a covered type."""
+        return self._piece_summaries(self._piece_table(self._c_pieces_spec(reach, types), self._piece_ids(ids)))
+
+    def is_whole(self, id, reach=None, types="both"):
+        """True iff every covered atom of the batch -- its white, its yolk, by `types` -- is ONE piece"""
+        return all(a is None or a.pieces == 1 for a in self.pieces([id], reach, types)[0])
 
     # ------------------------------------------------ collider bodies (egg_set_collider_bodies, DESIGN.md section 2.7)
     _BODIES_LIMIT =("collider bodies: the device integrates a body from the loads of one handle, so bodies run on a single "
@@ -1680,6 +1769,17 @@ class SimulationHandler(_HandlerSurface):
         t = _ffi.EggFieldTotals()
         self._check(self._lib.egg_field_to(self._h, C.byref(spec), C.byref(planes), C.byref(t)))
         return FieldTotals(tuple(t.inside), tuple(t.outside), tuple(t.dropped), t.units_tiled, t.units_direct)
+
+    # ------------------------------------------- pieces: the label of every particle (egg_pieces with label arrays)
+    def piece_labels(self, reach=None, types="both"):
+        """`(white, yolk)` int32 arrays in download() order: the label of every particle -- the lowest index in the batch among
+        the particles of its piece, under pieces()' rule, every batch asked for -- and -1 throughout for a type that `types`
+        leaves out.  One handle only: a group's and sharded ranks' particles live in several arrays."""
+        spec = self._c_pieces_spec(reach, types, "piece_labels")
+        labels = [np.full(int(n), -1, dtype=np.int32) for n in self.get_n_particles()]
+        out = (_ffi.EggPieceSummary * max(2 * len(self.list_ids()), 1))()
+        self._check(self._lib.egg_pieces(self._h, C.byref(spec), 0, None, out, labels[0].ctypes.data, labels[1].ctypes.data))
+        return labels[0], labels[1]
 
     def instances_begin(self, types=(0, 1)):
         """Launch the pack of instances() for `types` and the copy into pinned buffers the handle owns; returns at once.

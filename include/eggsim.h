@@ -1053,6 +1053,45 @@ typedef struct { int64_t inside[2], outside[2], dropped[2]; int32_t units_tiled,
 int egg_field(egg_handle *h, const egg_field_spec *spec, const egg_field_planes *host_out, egg_field_totals *totals);
 int egg_field_to(egg_handle *h, const egg_field_spec *spec, const egg_field_planes *device_out, egg_field_totals *totals);
 
+/* ---- pieces: the connected pieces of each batch (csrc/eggsim_pieces.hip) ----
+ * Not in the reference.  Sensors, probes and fields say how much of the egg is where; pieces answer "is the egg still ONE
+ * egg": has a wall cut it, has the yolk broken, how many particles have strayed, where is the body.  A call is STATELESS,
+ * only observes (of egg_get_stats only kernel_launches moves, by at most 2 per call) and reads the COMMITTED state -- the
+ * arrays egg_download_particles returns for EGG_FIELD_X / EGG_FIELD_Y / EGG_FIELD_RADIUS --, so it works in exact and in
+ * relaxed order alike.  tests/pieces_model.py is the definition in numpy.
+ * An ATOM is the particles of one type (white or yolk) of one live batch, numbered by their index in the batch, 0 .. n - 1
+ * (the index of egg_probe_hit).  Two particles i and j of an atom are LINKED iff d2 <= L * L, FP64 in exactly this order,
+ * no contraction:  dx = x[i] - x[j]; dy = y[i] - y[j]; d2 = dx * dx + dy * dy; L = reach[type] * (radius[i] + radius[j]).
+ * The test is symmetric and false when anything in it is a NaN.  Particles of different batches or types are never linked.
+ * A PIECE is a connected component of that graph; the LABEL of a particle is the lowest index in its piece; the BODY is the
+ * largest piece, among pieces of equal size the one with the lower label.
+ * Per requested batch and type one egg_piece_summary (out[i][0] white, out[i][1] yolk):
+ *   n        particles of the atom; 0 for a type the mask leaves out or the batch lacks, and every other field is then 0
+ *   pieces   number of pieces          largest  particles of the body          first  label of the body
+ *   singles  pieces of exactly one particle
+ *   dropped  body particles left out of the two sums by the sensors' rule: one of x, y times EGG_SENSOR_POSITION_SCALE is
+ *            not finite or reaches 2^53 in magnitude
+ *   sx, sy   int64 sums of llrint(x * EGG_SENSOR_POSITION_SCALE), llrint(y * EGG_SENSOR_POSITION_SCALE) over the body's
+ *            particles that are not dropped; the body's centroid is ((double)sx / EGG_SENSOR_POSITION_SCALE) /
+ *            (double)(largest - dropped), and likewise for y; there is none while largest == dropped.
+ * n_ids = 0 with ids = NULL means every live batch in egg_list_ids order (out then holds that many pairs); an id may
+ * repeat.  white_labels / yolk_labels are NULL or host memory for EVERY particle of the type (egg_download_particles order):
+ * the label of every particle of a requested atom, -1 for a particle of an atom that was not asked for.
+ * Every output is an integer and the fixed point of the labels is unique: the answer does not depend on the schedule, on
+ * the device, or on how a scene is split over handles.
+ * Everything is checked before anything is launched or written: EGG_ERR_INVALID_ARGUMENT for a NULL spec or out, n_ids < 0,
+ * ids NULL with n_ids > 0, a reach that is not finite or not above 0, a type_mask outside 1 .. 3, a step in flight
+ * (egg_step_begin or egg_rx_begin open); EGG_ERR_UNKNOWN_ID for an unknown id; EGG_ERR_UNSUPPORTED, naming the batch and
+ * its count, for a requested atom of a covered type with more than EGG_PIECES_MAX_ATOM particles (the atom is solved in
+ * the LDS of one compute unit).
+ * Limits: no path for larger atoms; the solve tests all pairs of an atom per sweep (no neighbour grid); labels on one
+ * handle only. */
+#define EGG_PIECES_MAX_ATOM 4096
+typedef struct { double reach[2]; int32_t type_mask; int32_t reserved; } egg_pieces_spec;                                     /* 24 bytes */
+typedef struct { int32_t n, pieces, largest, first, singles, dropped; int64_t sx, sy; } egg_piece_summary;                  /* 40 bytes */
+int egg_pieces(egg_handle *h, const egg_pieces_spec *spec, int64_t n_ids, const int64_t *ids,
+               egg_piece_summary *out /* [n][2] */, int32_t *white_labels, int32_t *yolk_labels);
+
 /* ---- several GPUs in one process (csrc/eggsim_group.cpp) -------------------------------------------------------
  * The multi-device form of the handle for a host that is ONE process (the LuaJIT wrapper): one egg_handle per device
  * behind one egg_group, x-slabs [cuts[k], cuts[k + 1]) of the plane per device (cuts: n_devices + 1 ascending values;
@@ -1146,6 +1185,10 @@ int egg_group_probe(egg_group *g, int32_t n, const egg_probe_query *probes, egg_
  * every batch, bit for bit, units_tiled / units_direct aside.  A failure on any handle writes nothing.  There is no
  * egg_group_field_to: a group's particles live on several devices. */
 int egg_group_field(egg_group *g, const egg_field_spec *spec, const egg_field_planes *host_out, egg_field_totals *totals);
+/* egg_pieces without labels: every id is routed to the handle that owns the batch -- a batch lives wholly on one handle --
+ * and the records are written in the caller's order; n_ids = 0 with ids = NULL means every live batch in
+ * egg_group_list_ids order.  The records equal one handle's bit for bit.  A failure on any handle writes nothing. */
+int egg_group_pieces(egg_group *g, const egg_pieces_spec *spec, int64_t n_ids, const int64_t *ids, egg_piece_summary *out /* [n][2] */);
 /* egg_set_forces for every handle of the group alike, with its rules (relaxed order only; back to exact order only with
  * an empty list); a refused list changes no handle.  Every device accelerates only the particles it owns: the results
  * equal one handle's.  A group whose handles differ in their lists refuses to step. */
