@@ -232,6 +232,24 @@ PIECES_MAX_ATOM = 4096  # EGG_PIECES_MAX_ATOM: particles of one type of one batc
 PIECES_TYPES = dict(COLLIDER_TYPES)  # type_mask by name; the wrappers take the mask itself (1, 2, 3) as well
 
 
+class EggImpulse(C.Structure):  # egg_impulse_record: a region, what happens to the velocities inside it, and the batch it is for (96 bytes)
+    _fields_ = [("region", EggSensor), ("action", C.c_int32), ("flags", C.c_int32), ("id", C.c_int64), ("a", C.c_double * 3)]
+
+
+class EggImpulseResult(C.Structure):  # egg_impulse_result: per type the accepted edits, their int64 sums and the skipped ones (64 bytes)
+    _fields_ = [("count", C.c_int64 * 2), ("sdvx", C.c_int64 * 2), ("sdvy", C.c_int64 * 2), ("skipped", C.c_int64 * 2)]
+
+
+MAX_IMPULSES = 64  # EGG_MAX_IMPULSES
+IMPULSE_SCALE = 65536.0  # EGG_IMPULSE_SCALE, 2^16
+IMPULSE_ALL_BATCHES, IMPULSE_NO_BATCH = -1, -2  # EGG_IMPULSE_ALL_BATCHES, EGG_IMPULSE_NO_BATCH
+IMPULSE_KICK, IMPULSE_BLAST, IMPULSE_SWIRL, IMPULSE_BRAKE = 0, 1, 2, 3
+IMPULSE_ACTIONS = ("kick", "blast", "swirl", "brake")  # by EGG_IMPULSE_* value
+IMPULSE_PARAMS = (("ax", "ay"), ("cx", "cy", "s"), ("cx", "cy", "omega"), ("ux", "uy", "k"))
+IMPULSE_CODES = {n: i for i, n in enumerate(IMPULSE_ACTIONS)}
+IMPULSE_LINEAR, IMPULSE_BY_INV_MASS = 1, 2  # flag bits
+
+
 class EggRxBox(C.Structure):  # egg_rx_box: a cell box of the relaxed halo between processes
     _fields_ = [("lo_x", C.c_int32), ("lo_y", C.c_int32), ("hi_x", C.c_int32), ("hi_y", C.c_int32), ("empty", C.c_int32)]
 
@@ -440,6 +458,12 @@ _SIGNATURES = {
 }
 
 EXPORTED_SYMBOLS = sorted(_SIGNATURES)
+# the entry points of include/eggsim_impulse.h, the header include/eggsim.h brings along: with them the library exports 175
+_IMPULSE_SIGNATURES = {
+    "egg_impulse": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggImpulse), C.POINTER(EggImpulseResult)]),
+    "egg_group_impulse": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggImpulse), C.POINTER(EggImpulseResult)]),
+}
+IMPULSE_SYMBOLS = sorted(_IMPULSE_SIGNATURES)
 
 _lib = None
 
@@ -457,7 +481,7 @@ def load():
                 "libeggsim.so not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
                 "or `make -C egg_fluid_simulation_amd/csrc` (needs hipcc; the solver has no CPU path)")
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
+        for name, (res, args) in list(_SIGNATURES.items()) + list(_IMPULSE_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

@@ -892,6 +892,43 @@ struct EggSensorBatchFinishArgs {  // counts[(i * n_sensors + k) * 2 + w] = sum 
     int32_t n_rows, n_sensors;
     int32_t *counts;
 };
+#if defined(__HIPCC__)
+// the test of one sensor record for one position (include/eggsim.h): FP64 in exactly this order, no contraction; every
+// comparison is false for a NaN.  The ONE definition: the sensors read it through sn_inside, the impulses' regions through
+// sn_test, which also hands out the d2 and R of a DISC or CAPSULE (a half-plane and a box leave them untouched).
+static __device__ __forceinline__ bool sn_test(const EggSensor &s, double x, double y, double &d2_out, double &R_out) {
+    if (s.kind == EGG_SN_HALF_PLANE) {
+        const double sd = (s.p[0] * x + s.p[1] * y) - s.p[2];
+        return sd >= 0.0;
+    }
+    if (s.kind == EGG_SN_BOX) {
+        const double dx = x - s.p[0], dy = y - s.p[1];
+        const double u = dx * s.p[4] + dy * s.p[5];
+        const double v = dy * s.p[4] - dx * s.p[5];
+        return fabs(u) <= s.p[2] && fabs(v) <= s.p[3];
+    }
+    double cx = s.p[0], cy = s.p[1], R = s.p[2];
+    if (s.kind == EGG_SN_CAPSULE) {  // the nearest point of the segment, as the SEGMENT collider computes it
+        const double ex = s.p[2] - s.p[0], ey = s.p[3] - s.p[1];
+        const double l2 = ex * ex + ey * ey;
+        double t = l2 == 0.0 ? 0.0 : ((x - s.p[0]) * ex + (y - s.p[1]) * ey) / l2;
+        if (t < 0.0) t = 0.0;
+        if (t > 1.0) t = 1.0;
+        cx = s.p[0] + t * ex;
+        cy = s.p[1] + t * ey;
+        R = s.p[4];
+    }
+    const double dx = x - cx, dy = y - cy;
+    const double d2 = dx * dx + dy * dy;
+    d2_out = d2;
+    R_out = R;
+    return d2 <= R * R;
+}
+static __device__ __forceinline__ bool sn_inside(const EggSensor &s, double x, double y) {
+    double d2, R;
+    return sn_test(s, x, y, d2, R);
+}
+#endif
 
 // ---------------------------------------------------------------------------------------------
 // Probes (eggsim_probes.hip; include/eggsim.h, "probes"): the ONE committed particle per probe and
@@ -979,4 +1016,44 @@ struct EggPiecesArgs {
     EggPieceSummary *out;                   // one record per task, at task.slot; every task has a slot of its own
     int32_t *labels[2];                     // per type [n] filled with -1 before the launch, or null
     int32_t *sweeps;                        // sweeps per task at task.slot, or null (a developer figure: it depends on the schedule)
+};
+
+// ---------------------------------------------------------------------------------------------
+// Impulses (eggsim_impulses.hip; include/eggsim_impulse.h): the committed velocities of the
+// particles inside caller-set regions are edited in place, record after record, and integer totals come back.  The scan
+// walks the units of the shared builder (push_units: at most EGG_SN_UNIT consecutive particles of one atom; `reserved`
+// carries the id of the atom's batch here) with one wave per unit; lane k keeps record k's totals.  The ONLY arrays written
+// are vx and vy of the committed state.  No step launches anything of this.
+#define EGG_IM_MAX 64                // = EGG_MAX_IMPULSES: one lane of a wave per record
+#define EGG_IM_SCALE 0x1p16          // = EGG_IMPULSE_SCALE
+#define EGG_IM_LIMIT 0x1p53          // a scaled change of velocity that reaches it (or is not finite) is skipped
+#define EGG_IM_KICK 0
+#define EGG_IM_BLAST 1
+#define EGG_IM_SWIRL 2
+#define EGG_IM_BRAKE 3
+#define EGG_IM_LINEAR 1
+#define EGG_IM_BY_INV_MASS 2
+#define EGG_IM_ALL_BATCHES (-1ll)
+#define EGG_IM_ROWS 8                // words lane k of a wave leaves: count, sdvx, sdvy, skipped of white, then of yolk
+#define EGG_IM_FINISH_THREADS 1024
+typedef EggSensor EggRegion;         // a record's region is a sensor record, tested by sn_test
+struct EggImpulse {                  // = egg_impulse_record (96 bytes)
+    EggRegion region;
+    int32_t action, flags;
+    long long id;
+    double a[3];
+};
+struct EggImpulseArgs {
+    const double *x[2], *y[2], *inv_mass[2];  // the committed positions and the inverse masses per type (read)
+    double *vx[2], *vy[2];                    // the committed velocities per type (read and written)
+    const EggImpulse *recs;                   // the call's list, checked and normalised
+    const EggScanUnit *units;
+    int32_t n_recs, n_units;
+    int32_t need_inv_mass;                    // some record has EGG_IM_BY_INV_MASS
+    long long *partials;                      // [waves][EGG_IM_ROWS][64], or null: no totals are asked for
+};
+struct EggImpulseFinishArgs {  // a workgroup per row adds the waves' partials: out[row * 64 + k]
+    const long long *partials;
+    int32_t n_waves, n_recs;
+    long long *out;                           // [EGG_IM_ROWS][64]
 };

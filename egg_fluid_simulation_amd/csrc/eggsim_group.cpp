@@ -1023,6 +1023,53 @@ int egg_group_pieces(egg_group *g, const egg_pieces_spec *spec, int64_t n_ids, c
     return EGG_OK;
 }
 
+// Impulses (include/eggsim_impulse.h): every handle edits the particles it owns.  A record's id is the group's: the owner
+// gets its local id, every other handle EGG_IMPULSE_NO_BATCH, so the record is inert there and keeps its place in the order.
+// First every handle checks the list with every record inert, which launches nothing; only then does any handle change a
+// particle.  The totals are integers: the handles' totals added are one handle's.
+int egg_group_impulse(egg_group *g, int32_t n, const egg_impulse_record *list, egg_impulse_result *results) {
+    if (!g || g->h.empty()) return EGG_ERR_INVALID_ARGUMENT;
+    if (n < 0 || n > EGG_MAX_IMPULSES)
+        return gfail(g, EGG_ERR_INVALID_ARGUMENT, "egg_group_impulse: n = %d, a call takes 0 .. %d records", (int)n, EGG_MAX_IMPULSES);
+    if (n > 0 && !list) return gfail(g, EGG_ERR_INVALID_ARGUMENT, "egg_group_impulse: n = %d without a list", (int)n);
+    std::vector<egg_impulse_record> local(list, list + n);
+    for (egg_impulse_record &o : local)
+        if (o.id != EGG_IMPULSE_ALL_BATCHES) o.id = EGG_IMPULSE_NO_BATCH;
+    for (size_t k = 0; k < g->h.size(); ++k) {  // (the checks of every handle, before anything changes)
+        std::vector<egg_impulse_record> inert(local);
+        for (egg_impulse_record &o : inert) o.id = EGG_IMPULSE_NO_BATCH;
+        const int rc = egg_impulse(g->h[k], n, inert.data(), nullptr);
+        if (rc < 0) return gfail(g, rc, "device %d: %s", (int)k, egg_last_error(g->h[k]));
+    }
+    for (int32_t i = 0; i < n; ++i) {
+        const int64_t id = list[i].id;
+        if (id == EGG_IMPULSE_ALL_BATCHES || id == EGG_IMPULSE_NO_BATCH) continue;
+        if (id < 1 || id > (int64_t)g->batch.size() || !g->batch[(size_t)id - 1].alive)
+            return gfail(g, EGG_ERR_UNKNOWN_ID, "egg_group_impulse: record %d: no batch with id `%lld`", (int)i, (long long)id);
+    }
+    std::vector<egg_impulse_result> sum((size_t)n, egg_impulse_result{}), one((size_t)std::max<int32_t>(n, 1));
+    for (size_t k = 0; k < g->h.size(); ++k) {
+        for (int32_t i = 0; i < n; ++i) {
+            const int64_t id = list[i].id;
+            if (id == EGG_IMPULSE_ALL_BATCHES || id == EGG_IMPULSE_NO_BATCH) continue;
+            const egg_group::Rec &r = g->batch[(size_t)id - 1];
+            local[(size_t)i].id = r.owner == (int)k ? r.local : EGG_IMPULSE_NO_BATCH;
+        }
+        const int rc = egg_impulse(g->h[k], n, local.data(), results ? one.data() : nullptr);
+        if (rc < 0) return gfail(g, rc, "device %d: %s", (int)k, egg_last_error(g->h[k]));
+        if (!results) continue;
+        for (int32_t i = 0; i < n; ++i)
+            for (int w = 0; w < 2; ++w) {
+                sum[(size_t)i].count[w] += one[(size_t)i].count[w];
+                sum[(size_t)i].sdvx[w] = (int64_t)((uint64_t)sum[(size_t)i].sdvx[w] + (uint64_t)one[(size_t)i].sdvx[w]);
+                sum[(size_t)i].sdvy[w] = (int64_t)((uint64_t)sum[(size_t)i].sdvy[w] + (uint64_t)one[(size_t)i].sdvy[w]);
+                sum[(size_t)i].skipped[w] += one[(size_t)i].skipped[w];
+            }
+    }
+    if (results && n > 0) memcpy(results, sum.data(), (size_t)n * sizeof(egg_impulse_result));
+    return EGG_OK;
+}
+
 int egg_group_get_collider_grips(egg_group *g, int64_t grips[2]) {
     if (!g) return EGG_ERR_INVALID_ARGUMENT;
     if (!grips) return gfail(g, EGG_ERR_INVALID_ARGUMENT, "egg_group_get_collider_grips: grips is NULL");

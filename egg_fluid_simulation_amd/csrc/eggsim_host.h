@@ -18,6 +18,7 @@
 //   eggsim_host_probes.hip         egg_probe: the checks, the unit table, the two launches, index -> (batch, key, index in the batch)
 //   eggsim_host_fields.hip         egg_field / egg_field_to: the checks, the unit table, the zeroing, the one launch, the copies back
 //   eggsim_host_pieces.hip         egg_pieces: the checks, the task table, at most two launches, the one copy of the records back
+//   eggsim_host_impulses.hip       egg_impulse: the checks, the unit table, at most two launches, the one copy of the totals back
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -148,6 +149,9 @@ extern "C" __global__ void egg_field_count_kernel(EggFieldArgs A);
 extern "C" __global__ void egg_field_velocity_kernel(EggFieldArgs A);
 extern "C" __global__ void egg_pieces_wave_kernel(EggPiecesArgs A);
 extern "C" __global__ void egg_pieces_block_kernel(EggPiecesArgs A);
+extern "C" __global__ void egg_impulse_kernel(EggImpulseArgs A);
+extern "C" __global__ void egg_impulse_quiet_kernel(EggImpulseArgs A);
+extern "C" __global__ void egg_impulse_finish_kernel(EggImpulseFinishArgs A);
 extern "C" __global__ void egg_render_count_kernel(EggRenderArgs A);
 extern "C" __global__ void egg_render_fill_kernel(EggRenderArgs A);
 extern "C" __global__ void egg_render_scan_kernel(EggRenderArgs A);
@@ -425,6 +429,7 @@ struct SensorState;  // device copy of the sensor list, unit tables and partials
 struct ProbeState;  // unit table, partials and winners of an egg_probe call (eggsim_host_probes.hip)
 struct FieldState;  // unit table, planes and totals of an egg_field call (eggsim_host_fields.hip)
 struct PiecesState;  // task table, records and labels of an egg_pieces call (eggsim_host_pieces.hip)
+struct ImpulseState;  // records, unit table, partials and totals of an egg_impulse call (eggsim_host_impulses.hip)
 }
 using namespace egghost;
 
@@ -600,6 +605,9 @@ struct egg_handle {
     // pieces (egg_pieces; either solver order): what a call needs on the device, allocated by the first call that launches.
     // A call stores no answer; no step reads this.
     std::shared_ptr<egghost::PiecesState> pieces_state;
+    // impulses (egg_impulse; either solver order): what a call needs on the device, allocated by the first call that
+    // launches.  A call stores no list and no answer; no step reads this.
+    std::shared_ptr<egghost::ImpulseState> impulse_state;
     // headless renderer (eggsim_render.hip)
     struct Render {
         egg_render_config cfg[2];
@@ -706,6 +714,10 @@ hipError_t wait_step(hipStream_t stream);
 int upload_atoms(egg_handle *h, int which);
 // the units of atom a of type w behind `units`: at most EGG_SN_UNIT consecutive particles each (eggsim_host_sensors.hip)
 void push_units(const Atom &a, int w, std::vector<EggScanUnit> &units);
+// the checks and the normalisation egg_set_sensors applies to one region record, for every caller that takes regions:
+// EGG_OK, or the failure with `what` and the record's index k in the message (eggsim_host_sensors.hip)
+typedef egg_sensor egg_region;
+int check_region(egg_handle *h, const char *what, int32_t k, egg_region &o);
 double cell_size_of(const egg_config &c);  // L:1756-1760
 int fetch_end_aabb(egg_handle *h, System &s);
 

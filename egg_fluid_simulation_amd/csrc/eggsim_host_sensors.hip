@@ -24,6 +24,39 @@ void push_units(const Atom &a, int w, std::vector<EggSensorUnit> &units) {
         units.push_back(EggSensorUnit{a.offset + at, std::min<int32_t>(EGG_SN_UNIT, a.count - at), w, 0});
 }
 
+// The checks and the normalisation of one region record (include/eggsim.h, "sensors"): the rule of egg_set_sensors, shared
+// with every caller that takes regions.  `what` opens the message, k is the record's index.
+int check_region(egg_handle *h, const char *what, int32_t k, egg_region &o) {
+    static const char *const names[4] = {"half-plane", "disc", "box", "capsule"};
+    static const int used_of[4] = {3, 3, 6, 5};
+    if (o.kind < EGG_SENSOR_HALF_PLANE || o.kind > EGG_SENSOR_CAPSULE)
+        return fail(h, EGG_ERR_INVALID_ARGUMENT, "%s %d: unknown kind %d", what, (int)k, (int)o.kind);
+    if (o.type_mask < 1 || o.type_mask > 3)
+        return fail(h, EGG_ERR_INVALID_ARGUMENT, "%s %d: type_mask %d (bit 0 white, bit 1 yolk, never 0)", what, (int)k,
+                    (int)o.type_mask);
+    for (int q = 0; q < 6; ++q) {
+        if (q >= used_of[o.kind]) o.p[q] = 0.0;  // (not a parameter of the kind)
+        if (!std::isfinite(o.p[q]))
+            return fail(h, EGG_ERR_INVALID_ARGUMENT, "%s %d (%s): parameter %d is not finite", what, (int)k, names[o.kind], q);
+    }
+    if (o.kind == EGG_SENSOR_DISC && o.p[2] < 0)
+        return fail(h, EGG_ERR_INVALID_ARGUMENT, "%s %d (disc): radius %g is negative", what, (int)k, o.p[2]);
+    if (o.kind == EGG_SENSOR_CAPSULE && o.p[4] < 0)
+        return fail(h, EGG_ERR_INVALID_ARGUMENT, "%s %d (capsule): radius %g is negative", what, (int)k, o.p[4]);
+    if (o.kind == EGG_SENSOR_BOX && (o.p[2] < 0 || o.p[3] < 0))
+        return fail(h, EGG_ERR_INVALID_ARGUMENT, "%s %d (box): half extent (%g, %g) is negative", what, (int)k, o.p[2], o.p[3]);
+    if (o.kind == EGG_SENSOR_HALF_PLANE || o.kind == EGG_SENSOR_BOX) {  // normalised once, here, as a collider's normal is
+        double *v = o.kind == EGG_SENSOR_BOX ? o.p + 4 : o.p;
+        const double len = std::sqrt(v[0] * v[0] + v[1] * v[1]);
+        if (!(len >= h->sys[0].cfg.eps) || !std::isfinite(len))
+            return fail(h, EGG_ERR_INVALID_ARGUMENT, "%s %d (%s): the %s's length %g is below eps or not finite", what, (int)k,
+                        names[o.kind], o.kind == EGG_SENSOR_BOX ? "axis" : "normal", len);
+        v[0] = v[0] / len;
+        v[1] = v[1] / len;
+    }
+    return EGG_OK;
+}
+
 namespace {
 
 // bit w: some sensor's mask covers type w and the type has particles
@@ -87,33 +120,8 @@ int egg_set_sensors(egg_handle *h, int32_t n, const egg_sensor *sensors) {
     for (int32_t k = 0; k < n; ++k) {
         egg_sensor &o = list[(size_t)k];
         o = sensors[k];
-        static const char *const names[4] = {"half-plane", "disc", "box", "capsule"};
-        static const int used_of[4] = {3, 3, 6, 5};
-        if (o.kind < EGG_SENSOR_HALF_PLANE || o.kind > EGG_SENSOR_CAPSULE)
-            return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_sensors: sensor %d: unknown kind %d", (int)k, (int)o.kind);
-        if (o.type_mask < 1 || o.type_mask > 3)
-            return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_sensors: sensor %d: type_mask %d (bit 0 white, bit 1 yolk, never 0)", (int)k,
-                        (int)o.type_mask);
-        for (int q = 0; q < 6; ++q) {
-            if (q >= used_of[o.kind]) o.p[q] = 0.0;  // (not a parameter of the kind)
-            if (!std::isfinite(o.p[q]))
-                return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_sensors: sensor %d (%s): parameter %d is not finite", (int)k, names[o.kind], q);
-        }
-        if (o.kind == EGG_SENSOR_DISC && o.p[2] < 0)
-            return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_sensors: sensor %d (disc): radius %g is negative", (int)k, o.p[2]);
-        if (o.kind == EGG_SENSOR_CAPSULE && o.p[4] < 0)
-            return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_sensors: sensor %d (capsule): radius %g is negative", (int)k, o.p[4]);
-        if (o.kind == EGG_SENSOR_BOX && (o.p[2] < 0 || o.p[3] < 0))
-            return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_sensors: sensor %d (box): half extent (%g, %g) is negative", (int)k, o.p[2], o.p[3]);
-        if (o.kind == EGG_SENSOR_HALF_PLANE || o.kind == EGG_SENSOR_BOX) {  // normalised once, here, as a collider's normal is
-            double *v = o.kind == EGG_SENSOR_BOX ? o.p + 4 : o.p;
-            const double len = std::sqrt(v[0] * v[0] + v[1] * v[1]);
-            if (!(len >= h->sys[0].cfg.eps) || !std::isfinite(len))
-                return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_set_sensors: sensor %d (%s): the %s's length %g is below eps or not finite", (int)k,
-                            names[o.kind], o.kind == EGG_SENSOR_BOX ? "axis" : "normal", len);
-            v[0] = v[0] / len;
-            v[1] = v[1] / len;
-        }
+        const int rc = check_region(h, "egg_set_sensors: sensor", k, o);
+        if (rc != EGG_OK) return rc;
     }
     if (n > 0) {  // (no step is running: every step ends with its streams waited for)
         HIP_TRY(h, hipSetDevice(h->device));

@@ -18,34 +18,7 @@
 
 namespace {
 
-// the test of one sensor record for one position (include/eggsim.h): FP64 in exactly this order, no contraction; every
-// comparison is false for a NaN
-__device__ __forceinline__ bool sn_inside(const EggSensor &s, double x, double y) {
-    if (s.kind == EGG_SN_HALF_PLANE) {
-        const double sd = (s.p[0] * x + s.p[1] * y) - s.p[2];
-        return sd >= 0.0;
-    }
-    if (s.kind == EGG_SN_BOX) {
-        const double dx = x - s.p[0], dy = y - s.p[1];
-        const double u = dx * s.p[4] + dy * s.p[5];
-        const double v = dy * s.p[4] - dx * s.p[5];
-        return fabs(u) <= s.p[2] && fabs(v) <= s.p[3];
-    }
-    double cx = s.p[0], cy = s.p[1], R = s.p[2];
-    if (s.kind == EGG_SN_CAPSULE) {  // the nearest point of the segment, as the SEGMENT collider computes it
-        const double ex = s.p[2] - s.p[0], ey = s.p[3] - s.p[1];
-        const double l2 = ex * ex + ey * ey;
-        double t = l2 == 0.0 ? 0.0 : ((x - s.p[0]) * ex + (y - s.p[1]) * ey) / l2;
-        if (t < 0.0) t = 0.0;
-        if (t > 1.0) t = 1.0;
-        cx = s.p[0] + t * ex;
-        cy = s.p[1] + t * ey;
-        R = s.p[4];
-    }
-    const double dx = x - cx, dy = y - cy;
-    const double d2 = dx * dx + dy * dy;
-    return d2 <= R * R;
-}
+// (the test of one sensor record for one position is sn_inside of eggsim_device.h: the impulses' regions share it)
 
 __device__ __forceinline__ long long sn_wave_sum(long long v) {
 #pragma unroll

@@ -794,6 +794,23 @@ local _sensor_n_params = { [0] = 3, 3, 6, 5 }
 local _max_sensors = 64 -- EGG_MAX_SENSORS
 local _sensor_scale = 65536 -- EGG_SENSOR_POSITION_SCALE
 
+--- fills one egg_sensor from a region in the shape set_sensors takes (impulse's regions too); false for a malformed one
+local function _fill_region(dst, s)
+    if type(s) ~= "table" then return false end
+    local kind = _sensor_kinds[s[1]]
+    local mask = _collider_types[s.types or "both"]
+    local by_angle = kind == 2 and #s == 6
+    if kind == nil or mask == nil or (#s ~= 1 + _sensor_n_params[kind] and not by_angle) then return false end
+    dst.kind, dst.type_mask = kind, mask
+    if by_angle then -- the host's cos / sin, as spin does
+        for q = 1, 4 do dst.p[q - 1] = s[q + 1] end
+        dst.p[4], dst.p[5] = math.cos(s[6]), math.sin(s[6])
+    else
+        for q = 1, _sensor_n_params[kind] do dst.p[q - 1] = s[q + 1] end
+    end
+    return true
+end
+
 --- the ordered list of at most 64 sensors, each `{ "half_plane", nx, ny, off }` (the side the normal points to),
 --- `{ "disc", cx, cy, R }`, `{ "box", cx, cy, hx, hy, angle }` (or `hx, hy, ux, uy` with the first axis),
 --- `{ "capsule", x0, y0, x1, y1, R }`, with an optional `types = "both" | "white" | "yolk"`.  `{}` clears the list.
@@ -805,19 +822,9 @@ function SimulationHandler:set_sensors(sensors)
     end
     local arr = ffi.new("egg_sensor[?]", math.max(n, 1))
     for k, s in ipairs(sensors) do
-        local kind = _sensor_kinds[s[1]]
-        local mask = _collider_types[s.types or "both"]
-        local by_angle = kind == 2 and #s == 6
-        if kind == nil or mask == nil or (#s ~= 1 + _sensor_n_params[kind] and not by_angle) then
+        if not _fill_region(arr[k - 1], s) then
             log.error("In SimulationHandler.set_sensors: sensor " .. k .. ": expected { kind, parameters..., types = ... }")
             return
-        end
-        arr[k - 1].kind, arr[k - 1].type_mask = kind, mask
-        if by_angle then -- the host's cos / sin, as spin does
-            for q = 1, 4 do arr[k - 1].p[q - 1] = s[q + 1] end
-            arr[k - 1].p[4], arr[k - 1].p[5] = math.cos(s[6]), math.sin(s[6])
-        else
-            for q = 1, _sensor_n_params[kind] do arr[k - 1].p[q - 1] = s[q + 1] end
         end
     end
     self:_check(lib.egg_set_sensors(self._h, n, arr))
@@ -1075,6 +1082,90 @@ function SimulationHandler:piece_labels(reach, types)
     local out = ffi.new("egg_piece_summary[?]", math.max(2 * #self:list_ids(), 1))
     if self:_check(lib.egg_pieces(self._h, spec, 0, nil, out, white, yolk)) ~= 0 then return nil end
     return white, yolk, nw, ny
+end
+
+-- Not in the reference: impulses (egg_impulse in include/eggsim_impulse.h; DESIGN.md section 2.12).  Act on the particles: the
+-- committed velocities of the particles inside a region are edited on the device, now; either solver order.  Only vx and vy
+-- change; nothing is stored.
+-- include/eggsim_impulse.h, the header include/eggsim.h brings along
+ffi.cdef[[
+typedef struct { egg_sensor region; int32_t action, flags; int64_t id; double a[3]; } egg_impulse_record;
+typedef struct { int64_t count[2], sdvx[2], sdvy[2], skipped[2]; } egg_impulse_result;
+int egg_impulse(egg_handle *h, int32_t n, const egg_impulse_record *list, egg_impulse_result *results);
+]]
+local _impulse_actions = { kick = 0, blast = 1, swirl = 2, brake = 3 }
+local _impulse_n_params = { [0] = 2, 3, 3, 3 }
+local _max_impulses = 64 -- EGG_MAX_IMPULSES
+local _impulse_scale = 65536 -- EGG_IMPULSE_SCALE
+local _impulse_all_batches = -1 -- EGG_IMPULSE_ALL_BATCHES
+
+--- an ordered list of at most 64 records `{ action, region, params..., id = nil, linear = false, by_inv_mass = false }`:
+--- `{ "kick", region, ax, ay }`, `{ "blast", region, cx, cy, s }`, `{ "swirl", region, cx, cy, omega }`,
+--- `{ "brake", region, ux, uy, k }`, the region in the shape set_sensors takes.  Returns per record
+--- `{ white = { count, dvx, dvy, skipped }, yolk = { ... } }` by name, dvx / dvy the summed change of velocity in px/s
+--- (`tonumber(sdvx) / 2^16`); with `want_results == false` nothing is finished or copied and the call returns true.
+function SimulationHandler:impulse(records, want_results)
+    local n = #records
+    if n > _max_impulses then
+        log.error("In SimulationHandler.impulse: a call takes 0 .. 64 records")
+        return nil
+    end
+    local arr = ffi.new("egg_impulse_record[?]", math.max(n, 1))
+    for k, r in ipairs(records) do
+        local action = _impulse_actions[r[1]]
+        if action == nil or #r ~= 2 + _impulse_n_params[action] or not _fill_region(arr[k - 1].region, r[2]) then
+            log.error("In SimulationHandler.impulse: record " .. k .. ": expected { action, region, parameters..., id = ..., linear = ..., by_inv_mass = ... }")
+            return nil
+        end
+        arr[k - 1].action = action
+        arr[k - 1].flags = (r.linear and 1 or 0) + (r.by_inv_mass and 2 or 0)
+        arr[k - 1].id = r.id or _impulse_all_batches
+        for q = 1, _impulse_n_params[action] do arr[k - 1].a[q - 1] = r[q + 2] end
+    end
+    if want_results == false then
+        if self:_check(lib.egg_impulse(self._h, n, arr, nil)) ~= 0 then return nil end
+        return true
+    end
+    local out = ffi.new("egg_impulse_result[?]", math.max(n, 1))
+    if self:_check(lib.egg_impulse(self._h, n, arr, out)) ~= 0 then return nil end
+    local res = {}
+    for k = 0, n - 1 do
+        local one = {}
+        for w, name in ipairs({ "white", "yolk" }) do
+            one[name] = { count = tonumber(out[k].count[w - 1]), skipped = tonumber(out[k].skipped[w - 1]),
+                          dvx = tonumber(out[k].sdvx[w - 1]) / _impulse_scale, dvy = tonumber(out[k].sdvy[w - 1]) / _impulse_scale }
+        end
+        res[k + 1] = one
+    end
+    return res
+end
+
+--- the particles inside `region` get (ax, ay) added to their velocity; `opts = { id, linear, by_inv_mass }`
+function SimulationHandler:kick(region, ax, ay, opts)
+    opts = opts or {}
+    local res = self:impulse({ { "kick", region, ax, ay, id = opts.id, linear = opts.linear, by_inv_mass = opts.by_inv_mass } })
+    return res and res[1]
+end
+
+--- a blast of strength s px/s at (cx, cy) that falls off linearly to 0 at the distance R (s < 0 sucks)
+function SimulationHandler:blast(cx, cy, R, s, opts)
+    opts = opts or {}
+    local res = self:impulse({ { "blast", { "disc", cx, cy, R, types = opts.types }, cx, cy, s, id = opts.id, linear = true, by_inv_mass = opts.by_inv_mass } })
+    return res and res[1]
+end
+
+--- the particles within R of (cx, cy) get the velocity of a turn at omega rad/s about it added
+function SimulationHandler:stir(cx, cy, R, omega, opts)
+    opts = opts or {}
+    local res = self:impulse({ { "swirl", { "disc", cx, cy, R, types = opts.types }, cx, cy, omega, id = opts.id, linear = opts.linear } })
+    return res and res[1]
+end
+
+--- the particles inside `region` move their velocity the fraction k (default 1: a stop) towards (ux, uy) (default 0, 0)
+function SimulationHandler:brake(region, k, ux, uy, opts)
+    opts = opts or {}
+    local res = self:impulse({ { "brake", region, ux or 0, uy or 0, k or 1, id = opts.id, linear = opts.linear } })
+    return res and res[1]
 end
 
 -- Not in the reference, which has no forces as it has no boundary: force fields of the relaxed step (egg_set_forces in

@@ -806,6 +806,31 @@ class ShardedSimulationHandler(_HandlerSurface):
             table = tot.cpu().numpy()
         return self._piece_summaries(table)
 
+    def impulse(self, records, results=True):
+        """SimulationHandler.impulse over all ranks (a collective: every rank calls it with the same list).  The ranks agree
+        first: an id no rank owns raises on every rank alike, and every rank has its handle check the list with every record
+        inert, which launches nothing.  Then each rank applies the list to the particles it owns -- a record for a batch of
+        another rank stays in its place, inert -- and one all_reduce(SUM) of an int64 table adds the totals: one handle's,
+        bit for bit.  Nothing travels in a step."""
+        n, arr = self._c_impulses(records)
+        gids = [int(arr[k].id) for k in range(n)]
+        for k, gid in enumerate(gids):
+            if gid not in (_ffi.IMPULSE_ALL_BATCHES, _ffi.IMPULSE_NO_BATCH) and gid not in self.owner:
+                raise EggError("[ERROR] In SimulationHandler.impulse: record %d: no batch with id `%d`" % (k, gid))
+        for k in range(n):
+            arr[k].id = _ffi.IMPULSE_NO_BATCH
+        self.local._impulse_table(n, arr, False)  # (the checks alone; the same verdict on every rank)
+        for k, gid in enumerate(gids):
+            arr[k].id = gid if gid in (_ffi.IMPULSE_ALL_BATCHES, _ffi.IMPULSE_NO_BATCH) else self.local_id.get(gid, _ffi.IMPULSE_NO_BATCH)
+        table = self.local._impulse_table(n, arr, bool(results))
+        if table is None:
+            return None
+        if self.world > 1 and n:
+            tot = self.torch.from_numpy(table).to(self.device)
+            self.dist.all_reduce(tot, op=self.dist.ReduceOp.SUM)
+            table = tot.cpu().numpy()
+        return self._impulse_results(table)
+
     def set_forces(self, forces):
         """SimulationHandler.set_forces on every rank alike (the same call on every rank; relaxed order only).  Nothing
         new travels: every rank accelerates the particles it owns."""

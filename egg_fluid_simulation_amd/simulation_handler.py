@@ -67,6 +67,25 @@ _PIECE_RECORD = np.dtype([("n", "<i4"), ("pieces", "<i4"), ("largest", "<i4"), (
                           ("sx", "<i8"), ("sy", "<i8")])
 
 
+class Impulse(collections.namedtuple("Impulse", "action region a id linear by_inv_mass", defaults=(None, False, False))):
+    """One record of impulse() (egg_impulse_record): `action` = "kick" | "blast" | "swirl" | "brake", `region` a region in the
+    tuple form of set_sensors, `a` the action's parameters -- (ax, ay), (cx, cy, s), (cx, cy, omega), (ux, uy, k) --, `id` a
+    batch id or None for every batch, `linear` the weight 1 - d / R of a disc or capsule, `by_inv_mass` the weight times the
+    particle's inverse mass (kick and blast)."""
+    __slots__ = ()
+
+
+class ImpulseResult(collections.namedtuple("ImpulseResult", "count sdvx sdvy skipped")):
+    """What one record of impulse() did, each field a `(white, yolk)` pair of Python ints: `count` the particles whose
+    velocity it edited, `sdvx`, `sdvy` the int64 sums of their changes of velocity scaled by 2^16 and rounded, `skipped` the
+    particles inside it whose edit was refused because a scaled change was not finite or reached 2^53."""
+    __slots__ = ()
+
+    def dv(self):
+        """the summed change of velocity per type in px/s: `((double)sdvx / 2^16, (double)sdvy / 2^16)` for (white, yolk)"""
+        return tuple((float(sx) / _ffi.IMPULSE_SCALE, float(sy) / _ffi.IMPULSE_SCALE) for sx, sy in zip(self.sdvx, self.sdvy))
+
+
 class EggWarning(UserWarning):
     """The reference's `log.warning` (a line on stderr)."""
 
@@ -760,6 +779,95 @@ class _HandlerSurface:
     def is_whole(self, id, reach=None, types="both"):
         """True iff every covered atom of the batch -- its white, its yolk, by `types` -- is ONE piece"""
         return all(a is None or a.pieces == 1 for a in self.pieces([id], reach, types)[0])
+
+    # ------------------------------------------------ impulses (egg_impulse, DESIGN.md section 2.12)
+    @staticmethod
+    def _c_impulses(records):
+        """a list of Impulse records, or tuples `(action, region, params...[, options])` with options a dict of `id`, `linear`,
+        `by_inv_mass`, as an egg_impulse_record array.  What only the host can check (shape, names) is checked here, the values
+        by the library."""
+        records = list(records)
+        if len(records) > _ffi.MAX_IMPULSES:
+            raise EggError("impulse: a call takes 0 .. %d records, not %d" % (_ffi.MAX_IMPULSES, len(records)))
+        arr = (_ffi.EggImpulse * max(len(records), 1))()
+        for k, r in enumerate(records):
+            if not isinstance(r, Impulse):
+                r = tuple(r) if isinstance(r, (tuple, list)) else ()
+                opts = {}
+                if r and isinstance(r[-1], dict):
+                    opts, r = dict(r[-1]), r[:-1]
+                if len(r) < 2 or set(opts) - {"id", "linear", "by_inv_mass"}:
+                    raise EggError("impulse: record %d: expected (action, region, params...[, {id, linear, by_inv_mass}])" % k)
+                r = Impulse(r[0], r[1], tuple(r[2:]), opts.get("id"), opts.get("linear", False), opts.get("by_inv_mass", False))
+            if not isinstance(r.action, str) or r.action not in _ffi.IMPULSE_CODES:
+                raise EggError("impulse: record %d: action must be one of %s, not %r" % (k, ", ".join(_ffi.IMPULSE_ACTIONS), r.action))
+            code = _ffi.IMPULSE_CODES[r.action]
+            names = _ffi.IMPULSE_PARAMS[code]
+            values = tuple(r.a) if isinstance(r.a, (tuple, list, np.ndarray)) else ()
+            if len(values) != len(names):
+                raise EggError("impulse: record %d (%s): expected the parameters (%s)" % (k, r.action, ", ".join(names)))
+            try:
+                values = [float(v) for v in values]
+            except (TypeError, ValueError):
+                raise EggError("impulse: record %d (%s): the parameters must be numbers" % (k, r.action)) from None
+            try:
+                _, region = _HandlerSurface._c_sensors([r.region])
+            except EggError as e:
+                raise EggError("impulse: record %d: region: %s" % (k, e)) from None
+            if r.id is not None and (isinstance(r.id, bool) or not isinstance(r.id, (int, np.integer))):
+                raise EggError("impulse: record %d: id must be None or a batch id, not %r" % (k, r.id))
+            arr[k].region = region[0]
+            arr[k].action = code
+            arr[k].flags = (_ffi.IMPULSE_LINEAR if r.linear else 0) | (_ffi.IMPULSE_BY_INV_MASS if r.by_inv_mass else 0)
+            arr[k].id = _ffi.IMPULSE_ALL_BATCHES if r.id is None else int(r.id)
+            for q, v in enumerate(values):
+                arr[k].a[q] = v
+        return len(records), arr
+
+    def _impulse_table(self, n, arr, results=True):
+        """one call of this object's entry point: an int64 array [n, 8] of (count, sdvx, sdvy, skipped) x (white, yolk), or
+        None with results=False (the totals are then neither finished nor copied)"""
+        out = (_ffi.EggImpulseResult * max(n, 1))() if results else None
+        self._check(self._c("impulse")(n, arr, out))
+        if not results:
+            return None
+        return np.array([list(r.count) + list(r.sdvx) + list(r.sdvy) + list(r.skipped) for r in out[:n]], dtype=np.int64).reshape(n, 8)
+
+    @staticmethod
+    def _impulse_results(table):
+        return [ImpulseResult(*(tuple(int(v) for v in row[2 * q:2 * q + 2]) for q in range(4))) for row in np.asarray(table).reshape(-1, 8)]
+
+    def impulse(self, records, results=True):
+        """Act on the particles (either solver order): the committed velocities of the particles inside
+        each record's region are edited on the device, record after record, and per record an `ImpulseResult(count, sdvx, sdvy,
+        skipped)` comes back (None with results=False).  A record is an `Impulse(action, region, a, id=None, linear=False,
+        by_inv_mass=False)` or a tuple `(action, region, params...[, {"id": .., "linear": .., "by_inv_mass": ..}])`: "kick" adds
+        w (ax, ay); "blast" adds w s along the unit vector from (cx, cy); "swirl" adds w omega times the arm from (cx, cy) turned
+        a quarter; "brake" moves the velocity the fraction w k towards (ux, uy).  The region takes the tuple form of
+        set_sensors; w is 1, with `linear` 1 - d / R of a disc or capsule, with `by_inv_mass` times the inverse mass.  Only vx, vy
+        change; stores nothing; at most 64 records; refused while a step is in flight.  Raises EggError for a bad list or an
+        unknown id (nothing changes)."""
+        n, arr = self._c_impulses(records)
+        table = self._impulse_table(n, arr, bool(results))
+        return None if table is None else self._impulse_results(table)
+
+    def kick(self, region, ax, ay, id=None, linear=False, by_inv_mass=False):
+        """the particles inside `region` get (ax, ay) added to their velocity: the one ImpulseResult"""
+        return self.impulse([Impulse("kick", region, (ax, ay), id, linear, by_inv_mass)])[0]
+
+    def blast(self, cx, cy, R, s, id=None, by_inv_mass=False, types="both"):
+        """a blast of strength s px/s at (cx, cy) that falls off linearly to 0 at the distance R (s < 0 sucks): the one
+        ImpulseResult"""
+        return self.impulse([Impulse("blast", ("disc", cx, cy, R, types), (cx, cy, s), id, True, by_inv_mass)])[0]
+
+    def stir(self, cx, cy, R, omega, id=None, linear=False, types="both"):
+        """the particles within R of (cx, cy) get the velocity of a turn at omega rad/s about it added: the one ImpulseResult"""
+        return self.impulse([Impulse("swirl", ("disc", cx, cy, R, types), (cx, cy, omega), id, linear, False)])[0]
+
+    def brake(self, region, k=1.0, ux=0.0, uy=0.0, id=None, linear=False):
+        """the particles inside `region` move their velocity the fraction k towards (ux, uy); k = 1 stops them at it: the one
+        ImpulseResult"""
+        return self.impulse([Impulse("brake", region, (ux, uy, k), id, linear, False)])[0]
 
     # ------------------------------------------------ collider bodies (egg_set_collider_bodies, DESIGN.md section 2.7)
     _BODIES_LIMIT =("collider bodies: the device integrates a body from the loads of one handle, so bodies run on a single "

@@ -1372,6 +1372,11 @@ int egg_draw_source_download(egg_handle *h, int which, int field, double *dst, i
  * like egg_draw_source_download it is not refused while a step of the handle is in flight. */
 int egg_draw_source_instances(egg_handle *h, int which, egg_instance *data, float *color, int64_t cap, int64_t *n);
 
+/* ---- impulses: push, blast, stir and brake the particles inside regions: include/eggsim_impulse.h ----
+ * Two more entry points and their records, in a header of their own that this one brings along: a caller includes eggsim.h
+ * and has the whole ABI. */
+#include "eggsim_impulse.h"
+
 #ifdef __cplusplus
 }
 #endif
