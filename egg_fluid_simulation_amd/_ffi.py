@@ -250,6 +250,24 @@ IMPULSE_CODES = {n: i for i, n in enumerate(IMPULSE_ACTIONS)}
 IMPULSE_LINEAR, IMPULSE_BY_INV_MASS = 1, 2  # flag bits
 
 
+class EggMeasureSpec(C.Structure):  # egg_measure_spec: the region (read with EGG_MEASURE_REGION only), the flags and the type mask (64 bytes)
+    _fields_ = [("region", EggSensor), ("flags", C.c_int32), ("type_mask", C.c_int32)]
+
+
+# egg_measure_record, field for field: 24 int64 (192 bytes)
+MEASURE_FIELDS = ("atom", "n", "dropped", "sx", "sy", "sm", "smx", "smy", "spx", "spy", "se", "lo_x", "lo_y", "hi_x", "hi_y", "max_v2",
+                  "ox_q", "oy_q", "dropped_central", "sxx", "sxy", "syy", "sl", "max_reach")
+
+
+class EggMeasureRecord(C.Structure):
+    _fields_ = [(name, C.c_int64) for name in MEASURE_FIELDS]
+
+
+MEASURE_SCALE = 65536.0  # EGG_MEASURE_SCALE, 2^16
+MEASURE_MASS_SCALE = 4294967296.0  # EGG_MEASURE_MASS_SCALE, 2^32
+MEASURE_REGION = 1  # EGG_MEASURE_REGION: flag bit
+
+
 class EggRxBox(C.Structure):  # egg_rx_box: a cell box of the relaxed halo between processes
     _fields_ = [("lo_x", C.c_int32), ("lo_y", C.c_int32), ("hi_x", C.c_int32), ("hi_y", C.c_int32), ("empty", C.c_int32)]
 
@@ -464,6 +482,13 @@ _IMPULSE_SIGNATURES = {
     "egg_group_impulse": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(EggImpulse), C.POINTER(EggImpulseResult)]),
 }
 IMPULSE_SYMBOLS = sorted(_IMPULSE_SIGNATURES)
+# the entry points of include/eggsim_measure.h, brought along the same way: with them the library exports 178
+_MEASURE_SIGNATURES = {
+    "egg_measure": (C.c_int, [C.c_void_p, C.POINTER(EggMeasureSpec), C.c_int64, C.c_void_p, C.c_void_p]),
+    "egg_measure_to": (C.c_int, [C.c_void_p, C.POINTER(EggMeasureSpec), C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]),
+    "egg_group_measure": (C.c_int, [C.c_void_p, C.POINTER(EggMeasureSpec), C.c_int64, C.c_void_p, C.c_void_p]),
+}
+MEASURE_SYMBOLS = sorted(_MEASURE_SIGNATURES)
 
 _lib = None
 
@@ -481,7 +506,7 @@ def load():
                 "libeggsim.so not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
                 "or `make -C egg_fluid_simulation_amd/csrc` (needs hipcc; the solver has no CPU path)")
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(_SIGNATURES.items()) + list(_IMPULSE_SIGNATURES.items()):
+        for name, (res, args) in list(_SIGNATURES.items()) + list(_IMPULSE_SIGNATURES.items()) + list(_MEASURE_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

@@ -1057,3 +1057,29 @@ struct EggImpulseFinishArgs {  // a workgroup per row adds the waves' partials: 
     int32_t n_waves, n_recs;
     long long *out;                           // [EGG_IM_ROWS][64]
 };
+
+// ---------------------------------------------------------------------------------------------
+// Measures (eggsim_measures.hip; include/eggsim_measure.h): per requested atom (the particles of
+// one type of one batch) one record of EGG_MS_FIELDS int64 -- counts, quantised sums of position, mass, momentum and
+// energy, the extremes, and central second moments about an origin the kernel derives from the first pass.  One workgroup
+// per row; a row walks its atom twice.  Read-only on the particle arrays; no step launches anything of this.
+#define EGG_MS_FIELDS 24             // = EGG_MEASURE_FIELDS: int64 words of a record
+#define EGG_MS_SCALE 0x1p16          // = EGG_MEASURE_SCALE
+#define EGG_MS_MASS_SCALE 0x1p32     // = EGG_MEASURE_MASS_SCALE
+#define EGG_MS_LIMIT 0x1p53          // a scaled term that reaches it (or is not finite) drops the particle
+#define EGG_MS_REGION 1              // = EGG_MEASURE_REGION
+#define EGG_MS_BLOCK 256             // threads of a workgroup
+#define EGG_MS_WAVE_ATOM 1024        // atoms up to this size are walked by the first wave alone, larger ones by all four
+struct EggMeasureRow {               // one requested atom
+    int32_t offset, count;           // its particles within the type's arrays, count >= 1
+    int32_t type;                    // 0 white, 1 yolk
+    int32_t slot;                    // its record in `out`: 2 * (index of the id in the call's list) + type
+};
+struct EggMeasureArgs {
+    const double *x[2], *y[2], *vx[2], *vy[2], *radius[2], *inv_mass[2];  // the committed state per type
+    const EggMeasureRow *rows;
+    int32_t n_rows;
+    int32_t use_region;              // spec.flags & EGG_MS_REGION
+    EggRegion region;                // checked and normalised; tested by sn_test, its own type mask included
+    long long *out;                  // [slots][EGG_MS_FIELDS]; a slot without a row is zeroed before the launch
+};

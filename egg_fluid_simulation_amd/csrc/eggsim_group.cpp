@@ -1070,6 +1070,50 @@ int egg_group_impulse(egg_group *g, int32_t n, const egg_impulse_record *list, e
     return EGG_OK;
 }
 
+// Measures (include/eggsim_measure.h): a batch lives wholly on one handle, so every id is routed to its owner and the
+// owner's records are copied to the caller's rows.  First every handle checks the spec with an empty list, which launches
+// nothing; nothing is written before every handle has answered.
+int egg_group_measure(egg_group *g, const egg_measure_spec *spec, int64_t n_ids, const int64_t *ids, egg_measure_record *out) {
+    if (!g || g->h.empty()) return EGG_ERR_INVALID_ARGUMENT;
+    if (!spec) return gfail(g, EGG_ERR_INVALID_ARGUMENT, "egg_group_measure: spec is NULL");
+    if (!out) return gfail(g, EGG_ERR_INVALID_ARGUMENT, "egg_group_measure: out is NULL");
+    if (n_ids < 0 || (n_ids > 0 && !ids))
+        return gfail(g, EGG_ERR_INVALID_ARGUMENT, "egg_group_measure: n_ids = %lld without a list (0 and NULL mean every live batch)", (long long)n_ids);
+    for (size_t k = 0; k < g->h.size(); ++k) {  // (the checks of every handle: flags, mask, region, a step in flight)
+        const int64_t none = 0;
+        egg_measure_record unused;
+        const int rc = egg_measure(g->h[k], spec, 0, &none, &unused);
+        if (rc < 0) return gfail(g, rc, "device %d: %s", (int)k, egg_last_error(g->h[k]));
+    }
+    for (int64_t i = 0; i < n_ids; ++i)  // (before anything is written)
+        if (ids[i] < 1 || ids[i] > (int64_t)g->batch.size() || !g->batch[(size_t)ids[i] - 1].alive)
+            return gfail(g, EGG_ERR_UNKNOWN_ID, "egg_group_measure: no batch with id `%lld`", (long long)ids[i]);
+    std::vector<int64_t> every;
+    if (n_ids == 0 && !ids) {
+        for (size_t i = 0; i < g->batch.size(); ++i)
+            if (g->batch[i].alive) every.push_back((int64_t)i + 1);
+        ids = every.data();
+        n_ids = (int64_t)every.size();
+    }
+    std::vector<egg_measure_record> all(2 * (size_t)n_ids, egg_measure_record{});
+    for (size_t k = 0; k < g->h.size(); ++k) {
+        std::vector<int64_t> local, where;
+        for (int64_t i = 0; i < n_ids; ++i) {
+            const egg_group::Rec &r = g->batch[(size_t)ids[i] - 1];
+            if (r.owner != (int)k) continue;
+            local.push_back(r.local);
+            where.push_back(i);
+        }
+        if (local.empty()) continue;
+        std::vector<egg_measure_record> part(2 * local.size(), egg_measure_record{});
+        const int rc = egg_measure(g->h[k], spec, (int64_t)local.size(), local.data(), part.data());
+        if (rc < 0) return gfail(g, rc, "device %d: %s", (int)k, egg_last_error(g->h[k]));
+        for (size_t q = 0; q < local.size(); ++q) memcpy(&all[2 * (size_t)where[q]], &part[2 * q], 2 * sizeof(egg_measure_record));
+    }
+    if (!all.empty()) memcpy(out, all.data(), all.size() * sizeof(egg_measure_record));
+    return EGG_OK;
+}
+
 int egg_group_get_collider_grips(egg_group *g, int64_t grips[2]) {
     if (!g) return EGG_ERR_INVALID_ARGUMENT;
     if (!grips) return gfail(g, EGG_ERR_INVALID_ARGUMENT, "egg_group_get_collider_grips: grips is NULL");

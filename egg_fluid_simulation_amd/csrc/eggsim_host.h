@@ -19,6 +19,7 @@
 //   eggsim_host_fields.hip         egg_field / egg_field_to: the checks, the unit table, the zeroing, the one launch, the copies back
 //   eggsim_host_pieces.hip         egg_pieces: the checks, the task table, at most two launches, the one copy of the records back
 //   eggsim_host_impulses.hip       egg_impulse: the checks, the unit table, at most two launches, the one copy of the totals back
+//   eggsim_host_measures.hip       egg_measure / egg_measure_to: the checks, the row table, the one launch, the one copy of the records back
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -152,6 +153,7 @@ extern "C" __global__ void egg_pieces_block_kernel(EggPiecesArgs A);
 extern "C" __global__ void egg_impulse_kernel(EggImpulseArgs A);
 extern "C" __global__ void egg_impulse_quiet_kernel(EggImpulseArgs A);
 extern "C" __global__ void egg_impulse_finish_kernel(EggImpulseFinishArgs A);
+extern "C" __global__ void egg_measure_kernel(EggMeasureArgs A);
 extern "C" __global__ void egg_render_count_kernel(EggRenderArgs A);
 extern "C" __global__ void egg_render_fill_kernel(EggRenderArgs A);
 extern "C" __global__ void egg_render_scan_kernel(EggRenderArgs A);
@@ -430,6 +432,7 @@ struct ProbeState;  // unit table, partials and winners of an egg_probe call (eg
 struct FieldState;  // unit table, planes and totals of an egg_field call (eggsim_host_fields.hip)
 struct PiecesState;  // task table, records and labels of an egg_pieces call (eggsim_host_pieces.hip)
 struct ImpulseState;  // records, unit table, partials and totals of an egg_impulse call (eggsim_host_impulses.hip)
+struct MeasureState;  // row table and records of an egg_measure call (eggsim_host_measures.hip)
 }
 using namespace egghost;
 
@@ -608,6 +611,9 @@ struct egg_handle {
     // impulses (egg_impulse; either solver order): what a call needs on the device, allocated by the first call that
     // launches.  A call stores no list and no answer; no step reads this.
     std::shared_ptr<egghost::ImpulseState> impulse_state;
+    // measures (egg_measure / egg_measure_to; either solver order): what a call needs on the device, allocated by the first
+    // call that launches.  A call stores no answer; no step reads this.
+    std::shared_ptr<egghost::MeasureState> measure_state;
     // headless renderer (eggsim_render.hip)
     struct Render {
         egg_render_config cfg[2];

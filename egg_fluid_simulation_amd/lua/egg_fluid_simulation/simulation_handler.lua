@@ -1168,6 +1168,88 @@ function SimulationHandler:brake(region, k, ux, uy, opts)
     return res and res[1]
 end
 
+-- Not in the reference: measures (egg_measure in include/eggsim_measure.h; DESIGN.md section 2.13).  What is this egg doing, as
+-- a body: per batch and type 24 int64 summed on the device -- counts, position, mass, momentum, energy, the box, second
+-- moments, angular momentum and reach -- from the committed state; either solver order.  A call stores nothing and only
+-- observes.
+-- include/eggsim_measure.h, the second header include/eggsim.h brings along (a level-1 long bracket: the third cdef block)
+ffi.cdef[=[
+typedef struct { egg_sensor region; int32_t flags, type_mask; } egg_measure_spec;
+typedef struct {
+    int64_t atom, n, dropped, sx, sy, sm, smx, smy, spx, spy, se, lo_x, lo_y, hi_x, hi_y, max_v2, ox_q, oy_q, dropped_central,
+        sxx, sxy, syy, sl, max_reach;
+} egg_measure_record;
+int egg_measure(egg_handle *h, const egg_measure_spec *spec, int64_t n_ids, const int64_t *ids, egg_measure_record *out);
+]=]
+local _measure_scale = 65536 -- EGG_MEASURE_SCALE
+local _measure_mass_scale = 4294967296 -- EGG_MEASURE_MASS_SCALE
+local _measure_region = 1 -- EGG_MEASURE_REGION
+local _measure_fields = { "atom", "n", "dropped", "sx", "sy", "sm", "smx", "smy", "spx", "spy", "se", "lo_x", "lo_y", "hi_x", "hi_y", "max_v2",
+                          "ox_q", "oy_q", "dropped_central", "sxx", "sxy", "syy", "sl", "max_reach" }
+
+-- a record as a table: the 24 integers by name (as Lua numbers: exact below 2^53) and what the host derives from them
+local function _measure_of(rec)
+    if rec.n == 0 then return nil end
+    local one = {}
+    for _, name in ipairs(_measure_fields) do one[name] = tonumber(rec[name]) end
+    local S = _measure_scale
+    one.kept = one.n - one.dropped
+    one.mass = one.sm / _measure_mass_scale
+    if one.kept > 0 then
+        one.centroid = { (one.sx / S) / one.kept, (one.sy / S) / one.kept }
+        one.bounds = { one.lo_x / S, one.lo_y / S, one.hi_x / S, one.hi_y / S }
+    end
+    one.momentum = { one.spx / S, one.spy / S }
+    if one.mass > 0 then
+        one.center_of_mass = { (one.smx / S) / one.mass, (one.smy / S) / one.mass }
+        one.velocity = { one.momentum[1] / one.mass, one.momentum[2] / one.mass }
+    end
+    one.kinetic_energy = 0.5 * one.se / S
+    one.max_speed = math.sqrt(one.max_v2 / S)
+    one.origin = { one.ox_q / S, one.oy_q / S }
+    one.reach = one.max_reach / S
+    one.spin = one.sl / S
+    local k = one.kept - one.dropped_central
+    if k > 0 then -- the principal standard deviations and the angle of the major axis
+        local cxx, cxy, cyy = (one.sxx / S) / k, (one.sxy / S) / k, (one.syy / S) / k
+        local half, diff = 0.5 * (cxx + cyy), 0.5 * (cxx - cyy)
+        local root = math.sqrt(diff * diff + cxy * cxy)
+        one.axes = { math.sqrt(math.max(half + root, 0)), math.sqrt(math.max(half - root, 0)), 0.5 * math.atan2(2 * cxy, cxx - cyy) }
+    end
+    return one
+end
+
+--- per id of `ids` (nil: every batch of list_ids(), in that order) `{ white = measure or nil, yolk = measure or nil }`, a
+--- measure the 24 integers of egg_measure_record by name plus `kept, mass, centroid, center_of_mass, momentum, velocity,
+--- kinetic_energy, bounds, max_speed, origin, reach, spin, axes`; nil where no particle of the type is measured.  `region` (nil:
+--- the whole atom) takes the shape set_sensors takes; types = "both" | "white" | "yolk".  An id may repeat.
+function SimulationHandler:measure(ids, region, types)
+    local spec = ffi.new("egg_measure_spec")
+    local mask = _collider_types[types or "both"]
+    if mask == nil or (region ~= nil and not _fill_region(spec.region, region)) then
+        log.error("In SimulationHandler.measure: expected (ids, region, types) with region nil or a region as set_sensors takes it and types \"both\" | \"white\" | \"yolk\"")
+        return nil
+    end
+    spec.type_mask = mask
+    spec.flags = region ~= nil and _measure_region or 0
+    local listed = ids or self:list_ids()
+    local n = #listed
+    local c_ids = ffi.new("int64_t[?]", math.max(n, 1))
+    for i, id in ipairs(listed) do c_ids[i - 1] = id end
+    local out = ffi.new("egg_measure_record[?]", math.max(2 * n, 1))
+    if self:_check(lib.egg_measure(self._h, spec, n, c_ids, out)) ~= 0 then return nil end
+    local res = {}
+    for i = 0, n - 1 do res[i + 1] = { white = _measure_of(out[2 * i]), yolk = _measure_of(out[2 * i + 1]) } end
+    return res
+end
+
+--- true iff every covered atom of the batch -- its white, its yolk, by `types` -- has max_speed <= speed
+function SimulationHandler:at_rest(id, speed, types)
+    local res = self:measure({ id }, nil, types)
+    if res == nil then return nil end
+    return (res[1].white == nil or res[1].white.max_speed <= speed) and (res[1].yolk == nil or res[1].yolk.max_speed <= speed)
+end
+
 -- Not in the reference, which has no forces as it has no boundary: force fields of the relaxed step (egg_set_forces in
 -- include/eggsim.h; DESIGN.md section 2.7, "Forces").  Relaxed order only.
 local _force_kinds = { uniform = 0, radial = 1, vortex = 2 }

@@ -831,6 +831,27 @@ class ShardedSimulationHandler(_HandlerSurface):
             table = tot.cpu().numpy()
         return self._impulse_results(table)
 
+    def measure_table(self, ids=None, region=None, types="both"):
+        """SimulationHandler.measure_table over all ranks (a collective: every rank calls it with the same arguments).  A
+        batch lives wholly on one rank: every rank fills the rows of the batches it owns and zeros elsewhere, one
+        all_reduce(SUM) of the int64 table adds them, so the table equals one handle's bit for bit.  Nothing travels in a
+        step.  There is no measure_to here: the tables of the ranks live on different devices."""
+        spec = self._c_measure_spec(region, types, "measure_table")
+        ids = self.list_ids() if ids is None else [int(i) for i in ids]
+        for gid in ids:
+            if gid not in self.owner:
+                raise EggError("[ERROR] In SimulationHandler.measure: no batch with id `%d`" % gid)
+        self.local._measure_check(spec)  # (the same verdict on every rank, whatever it owns)
+        table = np.zeros((len(ids), 2, len(_ffi.MEASURE_FIELDS)), dtype=np.int64)
+        mine = [k for k, gid in enumerate(ids) if gid in self.local_id]
+        if mine:
+            table[mine] = self.local._measure_table(spec, np.ascontiguousarray([self.local_id[ids[k]] for k in mine], dtype=np.int64))
+        if self.world > 1 and ids:
+            tot = self.torch.from_numpy(table).to(self.device)
+            self.dist.all_reduce(tot, op=self.dist.ReduceOp.SUM)
+            table = tot.cpu().numpy()
+        return table
+
     def set_forces(self, forces):
         """SimulationHandler.set_forces on every rank alike (the same call on every rank; relaxed order only).  Nothing
         new travels: every rank accelerates the particles it owns."""

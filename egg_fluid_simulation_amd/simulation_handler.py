@@ -86,6 +86,93 @@ class ImpulseResult(collections.namedtuple("ImpulseResult", "count sdvx sdvy ski
         return tuple((float(sx) / _ffi.IMPULSE_SCALE, float(sy) / _ffi.IMPULSE_SCALE) for sx, sy in zip(self.sdvx, self.sdvy))
 
 
+class Measure(collections.namedtuple("Measure", _ffi.MEASURE_FIELDS)):
+    """One atom -- the particles of one type of one batch -- as a body (egg_measure_record): 24 Python ints, and what the host
+    derives from them.  S = 2^16, SM = 2^32.  `atom` particles, `n` of them measured (all without a region), `dropped` of
+    those left out because a scaled term was not finite or reached 2^53; the sums run over the `kept = n - dropped` others:
+    `sx, sy` of x S, `sm` of m SM, `smx, smy` of m x S, `spx, spy` of m v S, `se` of m v^2 S; `lo_x, lo_y, hi_x, hi_y` the
+    box of the discs and `max_v2` the highest squared speed, times S; `ox_q, oy_q` the centroid truncated to 1 / S, about which
+    `sxx, sxy, syy` sum d d S, `sl` sums m (d x v) S and `max_reach` is the farthest disc edge times S, over the kept
+    particles less `dropped_central`."""
+    __slots__ = ()
+
+    @property
+    def kept(self):
+        return self.n - self.dropped
+
+    @property
+    def mass(self):
+        """sm / SM"""
+        return float(self.sm) / _ffi.MEASURE_MASS_SCALE
+
+    @property
+    def centroid(self):
+        """((sx / S) / kept, (sy / S) / kept): the mean of the centres; None while every particle was dropped"""
+        k = self.kept
+        return ((float(self.sx) / _ffi.MEASURE_SCALE) / k, (float(self.sy) / _ffi.MEASURE_SCALE) / k) if k else None
+
+    @property
+    def center_of_mass(self):
+        """((smx / S) / mass, (smy / S) / mass); None without mass"""
+        m = self.mass
+        return ((float(self.smx) / _ffi.MEASURE_SCALE) / m, (float(self.smy) / _ffi.MEASURE_SCALE) / m) if m > 0.0 else None
+
+    @property
+    def momentum(self):
+        """(spx / S, spy / S)"""
+        return (float(self.spx) / _ffi.MEASURE_SCALE, float(self.spy) / _ffi.MEASURE_SCALE)
+
+    @property
+    def velocity(self):
+        """momentum / mass: the velocity of the centre of mass; None without mass"""
+        m, p = self.mass, self.momentum
+        return (p[0] / m, p[1] / m) if m > 0.0 else None
+
+    @property
+    def kinetic_energy(self):
+        """0.5 * se / S"""
+        return 0.5 * float(self.se) / _ffi.MEASURE_SCALE
+
+    @property
+    def bounds(self):
+        """(lo_x, lo_y, hi_x, hi_y) / S: the rectangle that holds every kept disc; None while every particle was dropped"""
+        s = _ffi.MEASURE_SCALE
+        return (float(self.lo_x) / s, float(self.lo_y) / s, float(self.hi_x) / s, float(self.hi_y) / s) if self.kept else None
+
+    @property
+    def max_speed(self):
+        """sqrt(max_v2 / S)"""
+        return math.sqrt(float(self.max_v2) / _ffi.MEASURE_SCALE)
+
+    @property
+    def origin(self):
+        """(ox_q / S, oy_q / S): the point the second moments, the spin and the reach are about"""
+        return (float(self.ox_q) / _ffi.MEASURE_SCALE, float(self.oy_q) / _ffi.MEASURE_SCALE)
+
+    @property
+    def reach(self):
+        """max_reach / S: the radius of the circle about `origin` that holds every disc"""
+        return float(self.max_reach) / _ffi.MEASURE_SCALE
+
+    @property
+    def spin(self):
+        """sl / S: the angular momentum about `origin`, counter-clockwise positive"""
+        return float(self.sl) / _ffi.MEASURE_SCALE
+
+    def axes(self):
+        """`(major, minor, angle)`: the two principal standard deviations of the centres about `origin` and the angle of the
+        major axis in radians, from the covariance `(sxx, sxy, syy) / S / k` over the k = kept - dropped_central particles;
+        None when k is 0"""
+        k = self.kept - self.dropped_central
+        if k <= 0:
+            return None
+        s = _ffi.MEASURE_SCALE
+        cxx, cxy, cyy = (float(self.sxx) / s) / k, (float(self.sxy) / s) / k, (float(self.syy) / s) / k
+        half, diff = 0.5 * (cxx + cyy), 0.5 * (cxx - cyy)
+        root = math.sqrt(diff * diff + cxy * cxy)
+        return (math.sqrt(max(half + root, 0.0)), math.sqrt(max(half - root, 0.0)), 0.5 * math.atan2(2.0 * cxy, cxx - cyy))
+
+
 class EggWarning(UserWarning):
     """The reference's `log.warning` (a line on stderr)."""
 
@@ -868,6 +955,66 @@ class _HandlerSurface:
         """the particles inside `region` move their velocity the fraction k towards (ux, uy); k = 1 stops them at it: the one
         ImpulseResult"""
         return self.impulse([Impulse("brake", region, (ux, uy, k), id, linear, False)])[0]
+
+    # ------------------------------------------------ measures (egg_measure, DESIGN.md section 2.13)
+    @staticmethod
+    def _c_measure_spec(region, types, what="measure"):
+        """the region (None: every particle of the atom) and the mask of a call as an egg_measure_spec.  The region takes the
+        tuple form of set_sensors; what only the host can check (shape, names) is checked here, the values by the library."""
+        spec = _ffi.EggMeasureSpec()
+        spec.type_mask = _HandlerSurface._probe_mask(types, what)
+        if region is not None:
+            try:
+                _, arr = _HandlerSurface._c_sensors([region])
+            except EggError as e:
+                raise EggError("%s: region: %s" % (what, e)) from None
+            spec.region = arr[0]
+            spec.flags = _ffi.MEASURE_REGION
+        return spec
+
+    def _measure_check(self, spec):
+        """the library's checks of a spec alone: a call with an empty list, which launches and writes nothing"""
+        none = np.zeros(1, dtype=np.int64)
+        self._check(self._c("measure")(C.byref(spec), 0, none.ctypes.data, none.ctypes.data))
+
+    def _measure_table(self, spec, ids):
+        """the raw records of one call of this object's entry point: an int64 array [n, 2, 24], `ids` an int64 array (it may
+        be empty: no batch is asked for) or None for every live batch"""
+        n = len(self.list_ids()) if ids is None else ids.size
+        out = np.zeros((n, 2, len(_ffi.MEASURE_FIELDS)), dtype=np.int64)
+        if ids is not None and n == 0:
+            self._measure_check(spec)
+            return out
+        spare = out if n else np.zeros(1, dtype=np.int64)  # (out is never NULL)
+        self._check(self._c("measure")(C.byref(spec), 0 if ids is None else n, None if ids is None else ids.ctypes.data, spare.ctypes.data))
+        return out
+
+    @staticmethod
+    def _measures(table):
+        """per batch `(white, yolk)` of Measure, or None where n == 0"""
+        return [tuple(None if rec[1] == 0 else Measure(*rec) for rec in pair)
+                for pair in np.asarray(table, dtype=np.int64).reshape(-1, 2, len(_ffi.MEASURE_FIELDS)).tolist()]
+
+    def measure_table(self, ids=None, region=None, types="both"):
+        """measure() as the library's integers: an int64 array [n, 2, 24], [i][0] the white of ids[i] and [i][1] its yolk, the
+        fields in the order of `Measure._fields` (egg_measure_record).  A type `types` leaves out or the batch lacks is all 0."""
+        return self._measure_table(self._c_measure_spec(region, types, "measure_table"), self._piece_ids(ids, "measure_table"))
+
+    def measure(self, ids=None, region=None, types="both"):
+        """What is this egg doing, as a body (either solver order): per id (None: every batch of
+        list_ids(), in that order) `(white, yolk)`, each a `Measure` or None where no particle of the type is measured.  A
+        Measure holds the 24 integers the device sums over the particles of one type of one batch -- counts, position, mass,
+        momentum, twice the kinetic energy, the bounding box, the highest squared speed, second moments, angular momentum and
+        reach about the quantised centroid -- and derives `mass`, `centroid`, `center_of_mass`, `momentum`, `velocity`,
+        `kinetic_energy`, `bounds`, `max_speed`, `reach`, `spin` and `axes()` from them on the host.  With `region` (the tuple form
+        of set_sensors) only the particles inside it are measured.  Reads the committed state; stores nothing; refused while a
+        step is in flight.  Raises EggError for an unknown id or a bad region."""
+        return self._measures(self.measure_table(ids, region, types))
+
+    def at_rest(self, id, speed, types="both"):
+        """True iff every covered atom of the batch -- its white, its yolk, by `types` -- has `max_speed <= speed`"""
+        speed = float(speed)
+        return all(a is None or a.max_speed <= speed for a in self.measure([id], None, types)[0])
 
     # ------------------------------------------------ collider bodies (egg_set_collider_bodies, DESIGN.md section 2.7)
     _BODIES_LIMIT =("collider bodies: the device integrates a body from the loads of one handle, so bodies run on a single "
@@ -1877,6 +2024,35 @@ class SimulationHandler(_HandlerSurface):
         t = _ffi.EggFieldTotals()
         self._check(self._lib.egg_field_to(self._h, C.byref(spec), C.byref(planes), C.byref(t)))
         return FieldTotals(tuple(t.inside), tuple(t.outside), tuple(t.dropped), t.units_tiled, t.units_direct)
+
+    # ------------------------------------------- measures into a table on the device (egg_measure_to)
+    def measure_to(self, out, ids=None, region=None, types="both"):
+        """measure_table() into caller-owned memory on this handle's device: `out` an int64 tensor of at least n x 2 x 24
+        elements, contiguous, given as an object with `data_ptr()` (a torch tensor) or as a `(address, capacity_bytes)` pair.
+        The first n x 2 x 24 words are complete when the call returns; nothing is copied to the host.  Returns n, the number
+        of batches measured.  (A process that uses torch tensors imports torch before this package loads its library.)"""
+        spec = self._c_measure_spec(region, types, "measure_to")
+        ids = self._piece_ids(ids, "measure_to")
+        if hasattr(out, "data_ptr"):
+            if str(getattr(out, "dtype", "int64")).split(".")[-1] != "int64":
+                raise EggError("measure_to: out must hold int64, not %s" % out.dtype)
+            if hasattr(out, "is_contiguous") and not out.is_contiguous():
+                raise EggError("measure_to: out must be contiguous")
+            address, capacity = out.data_ptr(), 8 * int(out.numel())
+        else:
+            try:
+                address, capacity = out
+            except (TypeError, ValueError):
+                raise EggError("measure_to: out must be an object with data_ptr() or (address, capacity_bytes), not %r" % (out,)) from None
+        for v in (address, capacity):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise EggError("measure_to: out must be an object with data_ptr() or (address, capacity_bytes), not %r" % (out,))
+        n = len(self.list_ids()) if ids is None else ids.size
+        if ids is not None and n == 0:
+            return 0
+        self._check(self._lib.egg_measure_to(self._h, C.byref(spec), 0 if ids is None else n, None if ids is None else ids.ctypes.data,
+                                             C.c_void_p(int(address)), int(capacity)))
+        return n
 
     # ------------------------------------------- pieces: the label of every particle (egg_pieces with label arrays)
     def piece_labels(self, reach=None, types="both"):

@@ -1377,6 +1377,10 @@ int egg_draw_source_instances(egg_handle *h, int which, egg_instance *data, floa
  * and has the whole ABI. */
 #include "eggsim_impulse.h"
 
+/* ---- measures: per-batch mass, momentum, energy, extent and shape: include/eggsim_measure.h ----
+ * Three more entry points, their spec and their record, in a header of their own as well. */
+#include "eggsim_measure.h"
+
 #ifdef __cplusplus
 }
 #endif
