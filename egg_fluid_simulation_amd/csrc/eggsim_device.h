@@ -932,7 +932,7 @@ static __device__ __forceinline__ bool sn_inside(const EggSensor &s, double x, d
 
 // ---------------------------------------------------------------------------------------------
 // Probes (eggsim_probes.hip; include/eggsim.h, "probes"): the ONE committed particle per probe and
-// type that is nearest a point or first along a ray.  The scan walks the sensors' units (EggSensorUnit, at most
+// type that is nearest a point or first along a ray.  The scan walks the units of the shared builder (push_units: at most
 // EGG_SN_UNIT consecutive particles of one atom) with one wave per unit; lane k keeps probe k's best.  Nothing here is read
 // or written by a step.
 #define EGG_PB_MAX_PROBES 64         // = EGG_MAX_PROBES: one lane of a wave per probe
@@ -940,7 +940,7 @@ static __device__ __forceinline__ bool sn_inside(const EggSensor &s, double x, d
 #define EGG_PB_RAY 1
 #define EGG_PB_FINISH_THREADS 1024
 #define EGG_PB_FINISH_PROBES 8       // probes of one finishing workgroup: their 8 scores are one 64-byte line of a wave's row
-typedef EggSensorUnit EggScanUnit;   // the unit table is the one the sensors' host side builds (push_units)
+typedef EggSensorUnit EggScanUnit;   // the unit of every scan: the shared host layer builds the tables (push_units, eggsim_host_scan.hip)
 struct EggProbe {  // egg_probe_query
     int32_t kind, type_mask;
     double p[5];

@@ -427,7 +427,39 @@ int group_step_any(egg_group *g, double delta, int S, int C) {
     return EGG_OK;
 }
 
-bool live(const egg_group *g, int64_t id) { return id >= 1 && id <= (int64_t)g->batch.size() && g->batch[(size_t)id - 1].alive; }
+bool group_alive(const egg_group *g, int64_t id) { return id >= 1 && id <= (int64_t)g->batch.size() && g->batch[(size_t)id - 1].alive; }
+
+std::vector<int64_t> group_live_ids(const egg_group *g) {
+    std::vector<int64_t> ids;
+    for (size_t i = 0; i < g->batch.size(); ++i)
+        if (g->batch[i].alive) ids.push_back((int64_t)i + 1);
+    return ids;
+}
+
+// A batch is answered by the handle that owns it.  Per handle: the listed (live) ids it owns, one call(k, n, local ids, part)
+// that fills recs_per_id records per id, and the records scattered into the caller's order.  A negative code of a call is the
+// group's failure; `out` is written only after every handle has answered.
+template <typename Rec, typename Call>
+int route_to_owners(egg_group *g, int64_t n_ids, const int64_t *ids, size_t recs_per_id, Rec *out, Call call) {
+    std::vector<Rec> all((size_t)n_ids * recs_per_id, Rec{});
+    for (size_t k = 0; k < g->h.size(); ++k) {
+        std::vector<int64_t> local, where;
+        for (int64_t i = 0; i < n_ids; ++i) {
+            const egg_group::Rec &r = g->batch[(size_t)ids[i] - 1];
+            if (r.owner != (int)k) continue;
+            local.push_back(r.local);
+            where.push_back(i);
+        }
+        if (local.empty()) continue;
+        std::vector<Rec> part(local.size() * recs_per_id, Rec{});
+        const int rc = call(k, (int64_t)local.size(), local.data(), part.data());
+        if (rc < 0) return gfail(g, rc, "device %d: %s", (int)k, egg_last_error(g->h[k]));
+        for (size_t q = 0; q < local.size(); ++q)
+            memcpy(&all[(size_t)where[q] * recs_per_id], &part[q * recs_per_id], recs_per_id * sizeof(Rec));
+    }
+    if (!all.empty()) memcpy(out, all.data(), all.size() * sizeof(Rec));
+    return EGG_OK;
+}
 
 egghost::GroupView view_of(egg_group *g) {
     egghost::GroupView v;
@@ -528,7 +560,7 @@ int egg_group_add(egg_group *g, double x, double y, double white_radius, double 
 
 int egg_group_remove(egg_group *g, int64_t id) {
     if (!g) return EGG_ERR_INVALID_ARGUMENT;
-    if (id < 1 || id > (int64_t)g->batch.size() || !g->batch[(size_t)id - 1].alive) {
+    if (!group_alive(g, id)) {
         gfail(g, EGG_WARN_UNKNOWN_ID, "egg_group_remove: no batch with id `%lld`", (long long)id);
         return EGG_WARN_UNKNOWN_ID;  // the reference warns and carries on (L:145)
     }
@@ -542,7 +574,7 @@ int egg_group_remove(egg_group *g, int64_t id) {
 
 int egg_group_set_target(egg_group *g, int64_t id, double x, double y) {
     if (!g) return EGG_ERR_INVALID_ARGUMENT;
-    if (id < 1 || id > (int64_t)g->batch.size() || !g->batch[(size_t)id - 1].alive) {
+    if (!group_alive(g, id)) {
         gfail(g, EGG_WARN_UNKNOWN_ID, "egg_group_set_target: no batch with id `%lld`", (long long)id);
         return EGG_WARN_UNKNOWN_ID;  // L:259
     }
@@ -553,7 +585,7 @@ int egg_group_set_target(egg_group *g, int64_t id, double x, double y) {
 
 int egg_group_get_position(egg_group *g, int64_t id, double *x, double *y) {
     if (!g || !x || !y) return EGG_ERR_INVALID_ARGUMENT;
-    if (id < 1 || id > (int64_t)g->batch.size() || !g->batch[(size_t)id - 1].alive)
+    if (!group_alive(g, id))
         return gfail(g, EGG_ERR_UNKNOWN_ID, "egg_group_get_position: no batch with id `%lld`", (long long)id);  // L:286
     const egg_group::Rec &r = g->batch[(size_t)id - 1];
     GTRY(g, r.owner, egg_get_position(g->h[(size_t)r.owner], r.local, x, y));
@@ -561,7 +593,7 @@ int egg_group_get_position(egg_group *g, int64_t id, double *x, double *y) {
 }
 
 int egg_group_owner(const egg_group *g, int64_t id, int32_t *device_index, int64_t *local_id) {
-    if (!g || id < 1 || id > (int64_t)g->batch.size() || !g->batch[(size_t)id - 1].alive) return EGG_ERR_UNKNOWN_ID;
+    if (!g || !group_alive(g, id)) return EGG_ERR_UNKNOWN_ID;
     if (device_index) *device_index = g->batch[(size_t)id - 1].owner;
     if (local_id) *local_id = g->batch[(size_t)id - 1].local;
     return EGG_OK;
@@ -880,28 +912,14 @@ int egg_group_read_sensors(egg_group *g, int32_t cap, egg_sensor_reading *readin
 int egg_group_read_sensor_batches(egg_group *g, int64_t n_ids, const int64_t *ids, int32_t *counts) {
     if (!g || g->h.empty() || n_ids < 0 || (n_ids > 0 && !ids)) return EGG_ERR_INVALID_ARGUMENT;
     for (int64_t i = 0; i < n_ids; ++i)  // (before anything is written)
-        if (ids[i] < 1 || ids[i] > (int64_t)g->batch.size() || !g->batch[(size_t)ids[i] - 1].alive)
-            return gfail(g, EGG_ERR_UNKNOWN_ID, "egg_group_read_sensor_batches: no batch with id `%lld`", (long long)ids[i]);
+        if (!group_alive(g, ids[i])) return gfail(g, EGG_ERR_UNKNOWN_ID, "egg_group_read_sensor_batches: no batch with id `%lld`", (long long)ids[i]);
     int32_t have = 0;
     (void)egg_get_sensors(g->h[0], 0, nullptr, &have);
     if (n_ids == 0 || have == 0) return EGG_OK;
     if (!counts) return gfail(g, EGG_ERR_INVALID_ARGUMENT, "egg_group_read_sensor_batches: counts is NULL");
-    const size_t row = 2 * (size_t)have;
-    for (size_t k = 0; k < g->h.size(); ++k) {
-        std::vector<int64_t> local, where;
-        for (int64_t i = 0; i < n_ids; ++i) {
-            const egg_group::Rec &r = g->batch[(size_t)ids[i] - 1];
-            if (r.owner != (int)k) continue;
-            local.push_back(r.local);
-            where.push_back(i);
-        }
-        if (local.empty()) continue;
-        std::vector<int32_t> part(local.size() * row, 0);
-        const int rc = egg_read_sensor_batches(g->h[k], (int64_t)local.size(), local.data(), part.data());
-        if (rc < 0) return gfail(g, rc, "device %d: %s", (int)k, egg_last_error(g->h[k]));
-        for (size_t q = 0; q < local.size(); ++q) memcpy(counts + (size_t)where[q] * row, part.data() + q * row, row * sizeof(int32_t));
-    }
-    return EGG_OK;
+    return route_to_owners<int32_t>(g, n_ids, ids, 2 * (size_t)have, counts, [&](size_t k, int64_t n, const int64_t *local, int32_t *part) {
+        return egg_read_sensor_batches(g->h[k], n, local, part);
+    });
 }
 
 // Probes (include/eggsim.h, "probes"): every handle answers for the particles it owns; per (probe, type) the best of those
@@ -995,32 +1013,16 @@ int egg_group_pieces(egg_group *g, const egg_pieces_spec *spec, int64_t n_ids, c
         return gfail(g, EGG_ERR_INVALID_ARGUMENT, "egg_group_pieces: n_ids = %lld %s a list (0 and NULL mean every live batch)", (long long)n_ids,
                      ids ? "with" : "without");
     for (int64_t i = 0; i < n_ids; ++i)  // (before anything is written)
-        if (ids[i] < 1 || ids[i] > (int64_t)g->batch.size() || !g->batch[(size_t)ids[i] - 1].alive)
-            return gfail(g, EGG_ERR_UNKNOWN_ID, "egg_group_pieces: no batch with id `%lld`", (long long)ids[i]);
+        if (!group_alive(g, ids[i])) return gfail(g, EGG_ERR_UNKNOWN_ID, "egg_group_pieces: no batch with id `%lld`", (long long)ids[i]);
     std::vector<int64_t> every;
     if (n_ids == 0) {
-        for (size_t i = 0; i < g->batch.size(); ++i)
-            if (g->batch[i].alive) every.push_back((int64_t)i + 1);
+        every = group_live_ids(g);
         ids = every.data();
         n_ids = (int64_t)every.size();
     }
-    std::vector<egg_piece_summary> all(2 * (size_t)n_ids, egg_piece_summary{});
-    for (size_t k = 0; k < g->h.size(); ++k) {
-        std::vector<int64_t> local, where;
-        for (int64_t i = 0; i < n_ids; ++i) {
-            const egg_group::Rec &r = g->batch[(size_t)ids[i] - 1];
-            if (r.owner != (int)k) continue;
-            local.push_back(r.local);
-            where.push_back(i);
-        }
-        if (local.empty()) continue;
-        std::vector<egg_piece_summary> part(2 * local.size(), egg_piece_summary{});
-        const int rc = egg_pieces(g->h[k], spec, (int64_t)local.size(), local.data(), part.data(), nullptr, nullptr);
-        if (rc < 0) return gfail(g, rc, "device %d: %s", (int)k, egg_last_error(g->h[k]));
-        for (size_t q = 0; q < local.size(); ++q) memcpy(&all[2 * (size_t)where[q]], &part[2 * q], 2 * sizeof(egg_piece_summary));
-    }
-    if (!all.empty()) memcpy(out, all.data(), all.size() * sizeof(egg_piece_summary));
-    return EGG_OK;
+    return route_to_owners<egg_piece_summary>(g, n_ids, ids, 2, out, [&](size_t k, int64_t n, const int64_t *local, egg_piece_summary *part) {
+        return egg_pieces(g->h[k], spec, n, local, part, nullptr, nullptr);
+    });
 }
 
 // Impulses (include/eggsim_impulse.h): every handle edits the particles it owns.  A record's id is the group's: the owner
@@ -1044,7 +1046,7 @@ int egg_group_impulse(egg_group *g, int32_t n, const egg_impulse_record *list, e
     for (int32_t i = 0; i < n; ++i) {
         const int64_t id = list[i].id;
         if (id == EGG_IMPULSE_ALL_BATCHES || id == EGG_IMPULSE_NO_BATCH) continue;
-        if (id < 1 || id > (int64_t)g->batch.size() || !g->batch[(size_t)id - 1].alive)
+        if (!group_alive(g, id))
             return gfail(g, EGG_ERR_UNKNOWN_ID, "egg_group_impulse: record %d: no batch with id `%lld`", (int)i, (long long)id);
     }
     std::vector<egg_impulse_result> sum((size_t)n, egg_impulse_result{}), one((size_t)std::max<int32_t>(n, 1));
@@ -1086,32 +1088,16 @@ int egg_group_measure(egg_group *g, const egg_measure_spec *spec, int64_t n_ids,
         if (rc < 0) return gfail(g, rc, "device %d: %s", (int)k, egg_last_error(g->h[k]));
     }
     for (int64_t i = 0; i < n_ids; ++i)  // (before anything is written)
-        if (ids[i] < 1 || ids[i] > (int64_t)g->batch.size() || !g->batch[(size_t)ids[i] - 1].alive)
-            return gfail(g, EGG_ERR_UNKNOWN_ID, "egg_group_measure: no batch with id `%lld`", (long long)ids[i]);
+        if (!group_alive(g, ids[i])) return gfail(g, EGG_ERR_UNKNOWN_ID, "egg_group_measure: no batch with id `%lld`", (long long)ids[i]);
     std::vector<int64_t> every;
     if (n_ids == 0 && !ids) {
-        for (size_t i = 0; i < g->batch.size(); ++i)
-            if (g->batch[i].alive) every.push_back((int64_t)i + 1);
+        every = group_live_ids(g);
         ids = every.data();
         n_ids = (int64_t)every.size();
     }
-    std::vector<egg_measure_record> all(2 * (size_t)n_ids, egg_measure_record{});
-    for (size_t k = 0; k < g->h.size(); ++k) {
-        std::vector<int64_t> local, where;
-        for (int64_t i = 0; i < n_ids; ++i) {
-            const egg_group::Rec &r = g->batch[(size_t)ids[i] - 1];
-            if (r.owner != (int)k) continue;
-            local.push_back(r.local);
-            where.push_back(i);
-        }
-        if (local.empty()) continue;
-        std::vector<egg_measure_record> part(2 * local.size(), egg_measure_record{});
-        const int rc = egg_measure(g->h[k], spec, (int64_t)local.size(), local.data(), part.data());
-        if (rc < 0) return gfail(g, rc, "device %d: %s", (int)k, egg_last_error(g->h[k]));
-        for (size_t q = 0; q < local.size(); ++q) memcpy(&all[2 * (size_t)where[q]], &part[2 * q], 2 * sizeof(egg_measure_record));
-    }
-    if (!all.empty()) memcpy(out, all.data(), all.size() * sizeof(egg_measure_record));
-    return EGG_OK;
+    return route_to_owners<egg_measure_record>(g, n_ids, ids, 2, out, [&](size_t k, int64_t n, const int64_t *local, egg_measure_record *part) {
+        return egg_measure(g->h[k], spec, n, local, part);
+    });
 }
 
 int egg_group_get_collider_grips(egg_group *g, int64_t grips[2]) {
@@ -1245,7 +1231,7 @@ int egg_group_get_config(const egg_group *g, int which, egg_config *cfg) {
 
 int egg_group_get_target(const egg_group *g, int64_t id, double *x, double *y) {  // L:268-278
     if (!g || !x || !y) return EGG_ERR_INVALID_ARGUMENT;
-    if (!live(g, id))
+    if (!group_alive(g, id))
         return gfail(const_cast<egg_group *>(g), EGG_ERR_UNKNOWN_ID, "In SimulationHandler.get_target_position: no batch with id `%lld`", (long long)id);
     const egg_group::Rec &r = g->batch[(size_t)id - 1];
     return egg_get_target(g->h[(size_t)r.owner], r.local, x, y);
@@ -1275,7 +1261,7 @@ int egg_group_get_n_particles(const egg_group *g, int64_t id, int64_t *n_white, 
         }
         return EGG_OK;
     }
-    if (!live(g, id))
+    if (!group_alive(g, id))
         return gfail(const_cast<egg_group *>(g), EGG_ERR_UNKNOWN_ID, "In SimulationHandler:get_n_particles: no batch with id `%lld`", (long long)id);
     const egg_group::Rec &r = g->batch[(size_t)id - 1];
     return egg_get_n_particles(g->h[(size_t)r.owner], r.local, n_white, n_yolk);
@@ -1330,7 +1316,7 @@ int egg_group_set_render_flags(egg_group *g, int32_t use_particle_color, int32_t
 
 int egg_group_set_add_color(egg_group *g, int64_t id, int which, double r, double gr, double b, double a) {
     if (!g || (which != EGG_WHITE && which != EGG_YOLK)) return EGG_ERR_INVALID_ARGUMENT;
-    if (!live(g, id)) return gfail(g, EGG_ERR_UNKNOWN_ID, "egg_group_set_add_color: no batch with id `%lld`", (long long)id);
+    if (!group_alive(g, id)) return gfail(g, EGG_ERR_UNKNOWN_ID, "egg_group_set_add_color: no batch with id `%lld`", (long long)id);
     if (std::isnan(r) || std::isnan(gr) || std::isnan(b) || std::isnan(a))  // L:87-103
         return gfail(g, EGG_ERR_INVALID_ARGUMENT, "In SimulationHandler.add: %s color component is not a number", which == EGG_WHITE ? "white" : "yolk");
     g->own_color[2 * (size_t)(id - 1) + (size_t)which] = 1;
@@ -1346,7 +1332,7 @@ int egg_group_set_color(egg_group *g, int64_t id, int which, double r, double gr
     if (!g || (which != EGG_WHITE && which != EGG_YOLK)) return EGG_ERR_INVALID_ARGUMENT;
     if (std::isnan(r) || std::isnan(gr) || std::isnan(b) || std::isnan(a))
         return gfail(g, EGG_ERR_INVALID_ARGUMENT, "egg_group_set_color: a colour component is not a number");
-    if (!live(g, id))
+    if (!group_alive(g, id))
         return gfail(g, EGG_WARN_UNKNOWN_ID, "In SimulationHandler.%s: no batch with id `%lld`",
                      which == EGG_WHITE ? "set_white_color" : "set_egg_yolk_color", (long long)id);
     const float c[4] = {clamp01(r), clamp01(gr), clamp01(b), clamp01(a)};  // _assert_color (L:300-319)

@@ -637,10 +637,12 @@ int fail(egg_handle *h, int code, const char *fmt, ...);
 
 // state-mutating entry points are refused between egg_step_begin and egg_step_end: the launched step reads the
 // arrays and tiles they would change, and egg_step_end validates / commits exactly what was launched
+// (refuse_in_flight, eggsim_host_scan.hip, holds the two messages: EGG_OK, or the refusal under `name`)
+int refuse_in_flight(egg_handle *h, const char *name);
 #define REJECT_IN_FLIGHT(h, name)                                                                      \
     do {                                                                                               \
-        if ((h)->in_flight) return fail(h, EGG_ERR_INVALID_ARGUMENT, name ": a step is in flight (egg_step_begin without egg_step_end)"); \
-        if ((h)->wire_active) return fail(h, EGG_ERR_INVALID_ARGUMENT, name ": a step is in flight (egg_rx_begin without egg_rx_end)"); \
+        const int _rc = egghost::refuse_in_flight(h, name);                                            \
+        if (_rc != EGG_OK) return _rc;                                                                 \
     } while (0)
 
 #define HIP_TRY(h, expr)                                                                               \
@@ -718,8 +720,55 @@ int append_particles(egg_handle *h, System &s, const ParticleTemplate &tp, int64
 int reserve_out(egg_handle *h, System &s, size_t na);
 hipError_t wait_step(hipStream_t stream);
 int upload_atoms(egg_handle *h, int which);
-// the units of atom a of type w behind `units`: at most EGG_SN_UNIT consecutive particles each (eggsim_host_sensors.hip)
+
+// eggsim_host_scan.hip: what the calls that scan the committed particles between steps share on the host
+int upload_atoms(egg_handle *h);  // both types, white first
+// the units of atom a of type w behind `units`: at most EGG_SN_UNIT consecutive particles each
 void push_units(const Atom &a, int w, std::vector<EggScanUnit> &units);
+// `mask` without the types that have no particles
+int covered_types(const egg_handle *h, int mask);
+// A feature's table of every unit of the types it covers, on the device.  refresh() rebuilds it when the coverage or the
+// atoms of either type moved since it was built and is free otherwise; with_batch_ids puts the id of a unit's batch into
+// its spare word.  Each feature embeds its own: features with different masks would rebuild a shared one in turn.
+struct UnitTable {
+    DevBuf<EggScanUnit> d_units;
+    uint64_t gen[2] = {~0ull, ~0ull};
+    int cover = -1;
+    int32_t n_units = 0;
+    int refresh(egg_handle *h, const char *name, int cover, bool with_batch_ids);
+};
+// workgroups of a grid sized to the device, not to the scene: n, at most per_cu per compute unit; env_name (or null)
+// names a developer override of per_cu, 1 .. 32, read at every call
+int grid_cap(const egg_handle *h, int64_t n, int per_cu_default, const char *env_name);
+// `bytes` from p on lie inside one allocation of h's device
+bool device_range_fits(const egg_handle *h, const void *p, size_t bytes);
+// EGG_OK, or EGG_ERR_UNKNOWN_ID under `name` for the first listed id that names no live batch
+int check_batch_ids(egg_handle *h, const char *name, int64_t n_ids, const int64_t *ids);
+// the id of every live batch, in h->order
+std::vector<int64_t> live_batch_ids(const egg_handle *h);
+// the index into sys[w].atoms of every batch of h->batches, -1 where it has none; ONE map serves both types, which list
+// the live batches in the same (creation) order (the handle's atoms must be current: upload_atoms)
+std::vector<int32_t> atom_of_batch(const egg_handle *h);
+// fn(atom, w, slot) for the atom of every listed (known) id and every type of `mask` that has particles, slot = 2 i + w
+// for entry i of the list; an atom outside its type's arrays is EGG_ERR_INTERNAL under `name`, a non-zero code of fn ends
+// the walk and is returned
+template <typename Fn>
+int for_each_requested_atom(egg_handle *h, const char *name, int mask, int64_t n_ids, const int64_t *ids, Fn fn) {
+    const std::vector<int32_t> atom_of = atom_of_batch(h);
+    for (int64_t i = 0; i < n_ids; ++i) {
+        const int32_t a = atom_of[(size_t)(find_batch(h, ids[i]) - h->batches.data())];
+        for (int w = 0; w < 2; ++w) {
+            if (!(mask >> w & 1) || a < 0) continue;
+            const Atom &at = h->sys[w].atoms[(size_t)a];
+            if (at.count < 1) continue;
+            if (at.offset < 0 || (int64_t)at.offset + at.count > h->sys[w].n)
+                return fail(h, EGG_ERR_INTERNAL, "%s: atom %d of type %d holds %d particles from %d", name, (int)a, w, (int)at.count, (int)at.offset);
+            const int rc = fn(at, w, (int32_t)(2 * i + w));
+            if (rc != EGG_OK) return rc;
+        }
+    }
+    return EGG_OK;
+}
 // the checks and the normalisation egg_set_sensors applies to one region record, for every caller that takes regions:
 // EGG_OK, or the failure with `what` and the record's index k in the message (eggsim_host_sensors.hip)
 typedef egg_sensor egg_region;

@@ -503,20 +503,19 @@ int egg_get_positions_many(egg_handle *h, int64_t n, const int64_t *ids, double 
     if (!h || n < 0 || (n > 0 && (!ids || !xs || !ys))) return EGG_ERR_INVALID_ARGUMENT;
     if (n == 0) return EGG_OK;
     (void)hipSetDevice(h->device);
-    for (int w = 0; w < 2; ++w) {
-        int rc = upload_atoms(h, w);
+    {
+        const int rc = upload_atoms(h);
         if (rc != EGG_OK) return rc;
     }
     // atom of each live batch: both types list live batches in the same (creation) order
-    std::vector<int32_t> atom_of_batch(h->batches.size(), -1);
-    for (size_t k = 0; k < h->sys[0].atoms.size(); ++k) atom_of_batch[(size_t)h->sys[0].atoms[k].batch] = (int32_t)k;
+    const std::vector<int32_t> atom_of = atom_of_batch(h);
     std::vector<int32_t> wo((size_t)n), wc((size_t)n), yo((size_t)n), yc((size_t)n);
     for (int64_t k = 0; k < n; ++k) {
         const Batch *b = find_batch(h, ids[k]);
         if (!b)
             return fail(h, EGG_ERR_UNKNOWN_ID, "In SimulationHandler.get_position: no batch with id `%lld`",
                         (long long)ids[k]);
-        int32_t a = atom_of_batch[(size_t)ids[k] - 1];
+        int32_t a = atom_of[(size_t)ids[k] - 1];
         wo[(size_t)k] = h->sys[0].atoms[(size_t)a].offset;
         wc[(size_t)k] = h->sys[0].atoms[(size_t)a].count;
         yo[(size_t)k] = h->sys[1].atoms[(size_t)a].offset;
@@ -581,12 +580,11 @@ int egg_get_bounds_many(egg_handle *h, int64_t n, const int64_t *ids, double *lo
             s.tiled_cell_size = cell[w];
         }
     }
-    std::vector<int32_t> atom_of_batch(h->batches.size(), -1);
-    for (size_t k = 0; k < h->sys[0].atoms.size(); ++k) atom_of_batch[(size_t)h->sys[0].atoms[k].batch] = (int32_t)k;
+    const std::vector<int32_t> atom_of = atom_of_batch(h);
     for (int64_t k = 0; k < n; ++k) {
         if (!find_batch(h, ids[k]))
             return fail(h, EGG_ERR_UNKNOWN_ID, "egg_get_bounds_many: no batch with id `%lld`", (long long)ids[k]);
-        const int32_t a = atom_of_batch[(size_t)ids[k] - 1];
+        const int32_t a = atom_of[(size_t)ids[k] - 1];
         // the claim of the upcoming step when the tiles are current (egg_prepare_step), else the occupied cells
         const System &sw = h->sys[0], &sy = h->sys[1];
         const bool cw = !sw.tiling_dirty && sw.h_claim.size() == sw.atoms.size();
@@ -608,15 +606,14 @@ int egg_get_claims_many(egg_handle *h, int64_t n, const int64_t *ids, double *bo
     // reuse the bounds path to make sure boxes / claims are current
     int rc = egg_get_bounds_many(h, n, ids, lx.data(), ly.data(), hx.data(), hy.data());
     if (rc != EGG_OK) return rc;
-    std::vector<int32_t> atom_of_batch(h->batches.size(), -1);
-    for (size_t k = 0; k < h->sys[0].atoms.size(); ++k) atom_of_batch[(size_t)h->sys[0].atoms[k].batch] = (int32_t)k;
+    const std::vector<int32_t> atom_of = atom_of_batch(h);
     for (int w = 0; w < 2; ++w) {
         const System &s = h->sys[w];
         const double cell = cell_size_of(s.cfg);
         if (cell_sizes) cell_sizes[w] = cell;
         const bool claims = !s.tiling_dirty && s.h_claim.size() == s.atoms.size();
         for (int64_t k = 0; k < n; ++k) {
-            const int32_t a = atom_of_batch[(size_t)ids[k] - 1];
+            const int32_t a = atom_of[(size_t)ids[k] - 1];
             const Box &b = claims ? s.h_claim[(size_t)a] : s.aabb[(size_t)a];
             double *o = boxes + 8 * k + 4 * w;
             o[0] = b.lo_x * cell;

@@ -1,5 +1,6 @@
-// eggsim_host_fields.hip -- fields (include/eggsim.h, "fields"): the checks of a call, the unit table,
-// the zeroing of the planes and the one launch of eggsim_fields.hip.  egg_field adds into planes the handle reserves and
+// eggsim_host_fields.hip -- fields (include/eggsim.h, "fields"): the checks of a call, the zeroing of
+// the planes and the one launch of eggsim_fields.hip over the unit table of the shared host layer (eggsim_host_scan.hip).
+// egg_field adds into planes the handle reserves and
 // copies every requested plane back once; egg_field_to adds into the caller's planes on the device and copies nothing but
 // the totals.  A call stores no grid and no answer; a step launches nothing of this and takes no argument from it.
 #include "eggsim_host.h"
@@ -7,11 +8,7 @@
 namespace egghost {
 
 struct FieldState {
-    // every unit of every type the last call covered, rebuilt when the atoms or the coverage moved
-    DevBuf<EggScanUnit> d_units;
-    uint64_t units_gen[2] = {~0ull, ~0ull};
-    int units_cover = -1;
-    int32_t n_units = 0;
+    UnitTable units;                      // every unit of every type the last call covered
     DevBuf<int32_t> count;                // egg_field's planes on the device: [2][ny][nx] each, grown on demand
     DevBuf<unsigned long long> svx, svy;
     DevBuf<unsigned long long> totals;    // [EGG_FD_TOTALS]
@@ -24,28 +21,9 @@ namespace {
 // (EGGSIM_FIELD_WAVES_PER_CU: developer override, 1 .. 32; EGGSIM_FIELD_TILE_CELLS: developer override of the tile path's
 // largest rectangle, 0 .. EGG_FD_TILE_CELLS; profiles/r29_fields.md has the sweeps behind the defaults)
 constexpr int kWavesPerCu = 8;
-int field_waves(const egg_handle *h, int64_t n_units) {
-    const char *e = getenv("EGGSIM_FIELD_WAVES_PER_CU");
-    const int per_cu = e ? std::min(32, std::max(1, atoi(e))) : kWavesPerCu;
-    const int64_t most = per_cu * (int64_t)std::max(1, h->prop.multiProcessorCount);
-    return (int)std::min<int64_t>(n_units, most);
-}
 int field_tile_cells() {
     const char *e = getenv("EGGSIM_FIELD_TILE_CELLS");
     return e ? std::min(EGG_FD_TILE_CELLS, std::max(0, atoi(e))) : EGG_FD_TILE_CELLS;
-}
-
-// the whole plane [2][ny][nx] of `word` bytes lies inside one allocation of h's device
-bool plane_fits(const egg_handle *h, const void *p, size_t bytes) {
-    if (!on_device_of(h, p)) return false;
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    const uintptr_t at = (uintptr_t)p, lo = (uintptr_t)base;
-    return at >= lo && bytes <= size && at - lo <= size - bytes;
 }
 
 // Everything is checked before anything is launched or written.  Not cached: every call measures the arrays
@@ -57,8 +35,7 @@ int field_call(egg_handle *h, const char *name, const egg_field_spec *spec, cons
     static_assert(sizeof(egg_field_planes) == 24, "three plane pointers");
     static_assert(EGG_FIELD_VELOCITY_SCALE == EGG_FD_SCALE, "the kernel's scale is the ABI's");
     static_assert(EGG_FD_TILE_CELLS * (4 + 2 * 8) * kWavesPerCu <= (int)kLdsMax, "the wave cap per compute unit fits its LDS");
-    if (h->in_flight) return fail(h, EGG_ERR_INVALID_ARGUMENT, "%s: a step is in flight (egg_step_begin without egg_step_end)", name);
-    if (h->wire_active) return fail(h, EGG_ERR_INVALID_ARGUMENT, "%s: a step is in flight (egg_rx_begin without egg_rx_end)", name);
+    REJECT_IN_FLIGHT(h, name);
     if (!spec) return fail(h, EGG_ERR_INVALID_ARGUMENT, "%s: spec is NULL", name);
     if (!out) return fail(h, EGG_ERR_INVALID_ARGUMENT, "%s: planes is NULL", name);
     if (spec->nx < 1 || spec->ny < 1 || (int64_t)spec->nx * spec->ny > EGG_FIELD_MAX_CELLS)
@@ -83,39 +60,23 @@ int field_call(egg_handle *h, const char *name, const egg_field_spec *spec, cons
         if ((uintptr_t)out->count % 4 != 0) return fail(h, EGG_ERR_INVALID_ARGUMENT, "%s: count is not aligned to 4 bytes", name);
         if (velocity && ((uintptr_t)out->svx % 8 != 0 || (uintptr_t)out->svy % 8 != 0))
             return fail(h, EGG_ERR_INVALID_ARGUMENT, "%s: %s is not aligned to 8 bytes", name, (uintptr_t)out->svx % 8 != 0 ? "svx" : "svy");
-        if (!plane_fits(h, out->count, words * sizeof(int32_t)))
+        if (!device_range_fits(h, out->count, words * sizeof(int32_t)))
             return fail(h, EGG_ERR_INVALID_ARGUMENT, "%s: count is not %zu bytes of memory of device %d", name, words * sizeof(int32_t), h->device);
-        if (velocity && (!plane_fits(h, out->svx, words * sizeof(int64_t)) || !plane_fits(h, out->svy, words * sizeof(int64_t))))
+        if (velocity && (!device_range_fits(h, out->svx, words * sizeof(int64_t)) || !device_range_fits(h, out->svy, words * sizeof(int64_t))))
             return fail(h, EGG_ERR_INVALID_ARGUMENT, "%s: %s is not %zu bytes of memory of device %d", name,
-                        !plane_fits(h, out->svx, words * sizeof(int64_t)) ? "svx" : "svy", words * sizeof(int64_t), h->device);
+                        !device_range_fits(h, out->svx, words * sizeof(int64_t)) ? "svx" : "svy", words * sizeof(int64_t), h->device);
     }
-    int cover = spec->type_mask;
-    for (int w = 0; w < 2; ++w)
-        if (h->sys[w].n == 0) cover &= ~(1 << w);
+    const int cover = covered_types(h, spec->type_mask);
     System &W = h->sys[0], &Y = h->sys[1];
     unsigned long long sums[EGG_FD_TOTALS] = {0, 0, 0, 0, 0, 0, 0, 0};
     int32_t n_units = 0;
     if (cover != 0) {
-        for (int w = 0; w < 2; ++w) {
-            const int rc = upload_atoms(h, w);
-            if (rc != EGG_OK) return rc;
-        }
+        int rc = upload_atoms(h);
+        if (rc != EGG_OK) return rc;
         if (!h->field_state) h->field_state = std::make_shared<FieldState>();
-        FieldState &S = *h->field_state;
-        if (S.units_cover != cover || S.units_gen[0] != W.atoms_gen || S.units_gen[1] != Y.atoms_gen) {
-            std::vector<EggScanUnit> units;
-            for (int w = 0; w < 2; ++w)
-                if (cover >> w & 1)
-                    for (const Atom &a : h->sys[w].atoms) push_units(a, w, units);
-            HIP_TRY(h, S.d_units.reserve(units.size(), false, nullptr));
-            if (!units.empty())
-                HIP_TRY(h, hipMemcpy(S.d_units.p, units.data(), units.size() * sizeof(EggScanUnit), hipMemcpyHostToDevice));
-            S.n_units = (int32_t)units.size();
-            S.units_cover = cover;
-            S.units_gen[0] = W.atoms_gen;
-            S.units_gen[1] = Y.atoms_gen;
-        }
-        n_units = S.n_units;
+        rc = h->field_state->units.refresh(h, name, cover, false);
+        if (rc != EGG_OK) return rc;
+        n_units = h->field_state->units.n_units;
     }
     if (n_units == 0) {  // (nothing to launch: no particles of a type the mask covers)
         if (to_device) {
@@ -157,7 +118,7 @@ int field_call(egg_handle *h, const char *name, const egg_field_spec *spec, cons
             A.vx[w] = s.vx[s.cur].p;
             A.vy[w] = s.vy[s.cur].p;
         }
-        A.units = S.d_units.p;
+        A.units = S.units.d_units.p;
         A.n_units = n_units;
         A.nx = spec->nx;
         A.ny = spec->ny;
@@ -174,7 +135,7 @@ int field_call(egg_handle *h, const char *name, const egg_field_spec *spec, cons
             HIP_TRY(h, hipMemsetAsync(A.svy, 0, words * sizeof(int64_t), W.stream));
         }
         HIP_TRY(h, hipMemsetAsync(A.totals, 0, sizeof sums, W.stream));
-        const int waves = field_waves(h, n_units);
+        const int waves = grid_cap(h, n_units, kWavesPerCu, "EGGSIM_FIELD_WAVES_PER_CU");
         if (velocity)
             hipLaunchKernelGGL(egg_field_velocity_kernel, dim3((unsigned)waves), dim3(EGG_WAVE), 0, W.stream, A);
         else

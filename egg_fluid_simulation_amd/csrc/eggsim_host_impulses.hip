@@ -1,5 +1,5 @@
-// eggsim_host_impulses.hip -- impulses (include/eggsim_impulse.h): the checks of a call, the
-// unit table and the launches of eggsim_impulses.hip.  A call copies its records up (and the unit table, when the atoms
+// eggsim_host_impulses.hip -- impulses (include/eggsim_impulse.h): the checks of a call and the
+// launches of eggsim_impulses.hip over the unit table of the shared host layer (eggsim_host_scan.hip).  A call copies its records up (and the unit table, when the atoms
 // moved since the last call), launches the edit and, when totals are asked for, the finishing kernel, and copies the
 // totals back once.  It stores no list and no answer; a step launches nothing of this and takes no argument from it.
 #include "eggsim_host.h"
@@ -8,10 +8,7 @@ namespace egghost {
 
 struct ImpulseState {
     DevBuf<EggImpulse> d_recs;       // the call's records, checked and normalised
-    // the unit table: every unit of both types with the id of its batch, rebuilt when the atoms moved
-    DevBuf<EggScanUnit> d_units;
-    std::vector<EggScanUnit> units;  // its host copy: which types and batches a call can reach
-    uint64_t units_gen[2] = {~0ull, ~0ull};
+    UnitTable units;                 // every unit of both types, with the id of its batch
     DevBuf<long long> partials, out;
 };
 
@@ -19,10 +16,6 @@ namespace {
 
 // the grid is sized to the device, not to the scene: kWavesPerCu one-wave workgroups per compute unit at the most
 constexpr int kWavesPerCu = 8;
-int impulse_waves(const egg_handle *h, int64_t n_units) {
-    const int64_t most = kWavesPerCu * (int64_t)std::max(1, h->prop.multiProcessorCount);
-    return (int)std::min<int64_t>(n_units, most);
-}
 
 }  // namespace
 }  // namespace egghost
@@ -43,8 +36,7 @@ int egg_impulse(egg_handle *h, int32_t n, const egg_impulse_record *list, egg_im
                       EGG_IMPULSE_BRAKE == EGG_IM_BRAKE && EGG_IMPULSE_LINEAR == EGG_IM_LINEAR && EGG_IMPULSE_BY_INV_MASS == EGG_IM_BY_INV_MASS &&
                       EGG_IMPULSE_ALL_BATCHES == EGG_IM_ALL_BATCHES,
                   "the kernel's actions, flags and sentinel are the ABI's");
-    if (h->in_flight) return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_impulse: a step is in flight (egg_step_begin without egg_step_end)");
-    if (h->wire_active) return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_impulse: a step is in flight (egg_rx_begin without egg_rx_end)");
+    REJECT_IN_FLIGHT(h, "egg_impulse");
     if (n < 0 || n > EGG_MAX_IMPULSES)
         return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_impulse: n = %d, a call takes 0 .. %d records", (int)n, EGG_MAX_IMPULSES);
     if (n > 0 && !list) return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_impulse: n = %d without a list", (int)n);
@@ -88,39 +80,17 @@ int egg_impulse(egg_handle *h, int32_t n, const egg_impulse_record *list, egg_im
     System &W = h->sys[0], &Y = h->sys[1];
     if (n == 0 || W.n + Y.n == 0) return EGG_OK;
     (void)hipSetDevice(h->device);
-    for (int w = 0; w < 2; ++w) {
-        const int rc = upload_atoms(h, w);
-        if (rc != EGG_OK) return rc;
-    }
+    int rc = upload_atoms(h);
+    if (rc != EGG_OK) return rc;
     if (!h->impulse_state) h->impulse_state = std::make_shared<ImpulseState>();
     ImpulseState &S = *h->impulse_state;
-    if (S.units_gen[0] != W.atoms_gen || S.units_gen[1] != Y.atoms_gen) {
-        S.units_gen[0] = S.units_gen[1] = ~0ull;  // (until the table below is complete)
-        S.units.clear();
-        for (int w = 0; w < 2; ++w)
-            for (const Atom &a : h->sys[w].atoms) {
-                if (a.count < 1) continue;
-                if ((int64_t)a.offset + a.count > h->sys[w].n)
-                    return fail(h, EGG_ERR_INTERNAL, "egg_impulse: an atom of type %d holds %d particles from %d", w, (int)a.count, (int)a.offset);
-                const size_t first = S.units.size();
-                push_units(a, w, S.units);
-                // (a unit's spare word carries the id of its batch in THIS table only: ids are 1 + the index into h->batches)
-                const int64_t id = h->batches[(size_t)a.batch].id;
-                if (id < 1 || id > (int64_t)std::numeric_limits<int32_t>::max())
-                    return fail(h, EGG_ERR_INTERNAL, "egg_impulse: batch id %lld does not fit a unit's 32-bit word", (long long)id);
-                for (size_t q = first; q < S.units.size(); ++q) S.units[q].reserved = (int32_t)id;
-            }
-        HIP_TRY(h, S.d_units.reserve(S.units.size(), false, nullptr));
-        if (!S.units.empty())
-            HIP_TRY(h, hipMemcpy(S.d_units.p, S.units.data(), S.units.size() * sizeof(EggScanUnit), hipMemcpyHostToDevice));
-        S.units_gen[0] = W.atoms_gen;
-        S.units_gen[1] = Y.atoms_gen;
-    }
+    rc = S.units.refresh(h, "egg_impulse", 3, true);
+    if (rc != EGG_OK) return rc;
     // a list whose every record names no batch (a member of a group asked to check it) launches nothing
     bool reach = false;
     for (const egg_impulse_record &o : recs) reach |= o.id != EGG_IMPULSE_NO_BATCH;
-    if (S.units.empty() || !reach) return EGG_OK;
-    const int waves = impulse_waves(h, (int64_t)S.units.size());
+    if (S.units.n_units == 0 || !reach) return EGG_OK;
+    const int waves = grid_cap(h, S.units.n_units, kWavesPerCu, nullptr);
     HIP_TRY(h, S.d_recs.reserve(EGG_MAX_IMPULSES, false, nullptr));
     if (results) {
         HIP_TRY(h, S.partials.reserve((size_t)waves * EGG_IM_ROWS * EGG_WAVE, false, nullptr));
@@ -138,9 +108,9 @@ int egg_impulse(egg_handle *h, int32_t n, const egg_impulse_record *list, egg_im
         A.inv_mass[w] = s.inv_mass.p;
     }
     A.recs = S.d_recs.p;
-    A.units = S.d_units.p;
+    A.units = S.units.d_units.p;
     A.n_recs = n;
-    A.n_units = (int32_t)S.units.size();
+    A.n_units = S.units.n_units;
     A.need_inv_mass = need_inv_mass ? 1 : 0;
     A.partials = results ? S.partials.p : nullptr;
     if (results)

@@ -1,5 +1,6 @@
 // eggsim_host_measures.hip -- measures (include/eggsim_measure.h): the checks of a call, the row
-// table and the one launch of eggsim_measures.hip.  A call copies one row table up (none when the atoms, the mask and the
+// table and the one launch of eggsim_measures.hip, over the shared host layer of eggsim_host_scan.hip (the id list, the walk
+// over its atoms, the test of the caller's device memory).  A call copies one row table up (none when the atoms, the mask and the
 // id list are those of the last call) and, for egg_measure, the records back once; egg_measure_to leaves them in the
 // caller's memory on the device.  It stores no answer; a step launches nothing of this and takes no argument from it.
 #include "eggsim_host.h"
@@ -19,19 +20,6 @@ struct MeasureState {
 
 namespace {
 
-// `bytes` from p on lie inside one allocation of h's device
-bool table_fits(const egg_handle *h, const void *p, size_t bytes) {
-    if (!on_device_of(h, p)) return false;
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    const uintptr_t at = (uintptr_t)p, lo = (uintptr_t)base;
-    return at >= lo && bytes <= size && at - lo <= size - bytes;
-}
-
 // Everything is checked before anything is launched or written.  Not cached: every call measures the arrays
 // egg_download_particles would return now.
 int measure_call(egg_handle *h, const char *name, const egg_measure_spec *spec, int64_t n_ids, const int64_t *ids, void *out,
@@ -41,8 +29,7 @@ int measure_call(egg_handle *h, const char *name, const egg_measure_spec *spec, 
     static_assert(EGG_MEASURE_FIELDS == EGG_MS_FIELDS && EGG_MEASURE_REGION == EGG_MS_REGION, "the kernel's record and flag are the ABI's");
     static_assert(EGG_MEASURE_SCALE == EGG_MS_SCALE && EGG_MEASURE_MASS_SCALE == EGG_MS_MASS_SCALE, "the kernel's scales are the ABI's");
     static_assert(sizeof(EggRegion) == sizeof(egg_region), "a region is a region");
-    if (h->in_flight) return fail(h, EGG_ERR_INVALID_ARGUMENT, "%s: a step is in flight (egg_step_begin without egg_step_end)", name);
-    if (h->wire_active) return fail(h, EGG_ERR_INVALID_ARGUMENT, "%s: a step is in flight (egg_rx_begin without egg_rx_end)", name);
+    REJECT_IN_FLIGHT(h, name);
     if (!spec) return fail(h, EGG_ERR_INVALID_ARGUMENT, "%s: spec is NULL", name);
     if (!out) return fail(h, EGG_ERR_INVALID_ARGUMENT, "%s: out is NULL", name);
     if (n_ids < 0 || (n_ids > 0 && !ids))
@@ -58,12 +45,12 @@ int measure_call(egg_handle *h, const char *name, const egg_measure_spec *spec, 
         const int rc = check_region(h, what.c_str(), 0, region);
         if (rc != EGG_OK) return rc;
     }
-    for (int64_t i = 0; i < n_ids; ++i)
-        if (!find_batch(h, ids[i])) return fail(h, EGG_ERR_UNKNOWN_ID, "%s: no batch with id `%lld`", name, (long long)ids[i]);
+    int rc = check_batch_ids(h, name, n_ids, ids);
+    if (rc != EGG_OK) return rc;
     const bool all = n_ids == 0 && !ids;
     std::vector<int64_t> every;
     if (all) {
-        for (int32_t bi : h->order) every.push_back(h->batches[(size_t)bi].id);
+        every = live_batch_ids(h);
         ids = every.data();
         n_ids = (int64_t)every.size();
     }
@@ -76,40 +63,25 @@ int measure_call(egg_handle *h, const char *name, const egg_measure_spec *spec, 
         if (capacity_bytes < 0 || (uint64_t)capacity_bytes < (uint64_t)bytes)
             return fail(h, EGG_ERR_INVALID_ARGUMENT, "%s: capacity_bytes = %lld, %lld batches take %zu", name, (long long)capacity_bytes,
                         (long long)n_ids, bytes);
-        if (!table_fits(h, out, bytes))
+        if (!device_range_fits(h, out, bytes))
             return fail(h, EGG_ERR_INVALID_ARGUMENT, "%s: device_out is not %zu bytes of memory of device %d", name, bytes, h->device);
     }
     if (n_ids == 0) return EGG_OK;  // (an empty list, or no live batch: nothing to launch and nothing to write)
     System &W = h->sys[0], &Y = h->sys[1];
-    for (int w = 0; w < 2; ++w) {
-        const int rc = upload_atoms(h, w);
-        if (rc != EGG_OK) return rc;
-    }
+    rc = upload_atoms(h);
+    if (rc != EGG_OK) return rc;
     if (!h->measure_state) h->measure_state = std::make_shared<MeasureState>();
     MeasureState &S = *h->measure_state;
     const bool cached = S.rows_gen[0] == W.atoms_gen && S.rows_gen[1] == Y.atoms_gen && S.rows_mask == spec->type_mask && S.rows_all == all &&
                         (all || (S.rows_ids.size() == (size_t)n_ids && std::equal(S.rows_ids.begin(), S.rows_ids.end(), ids)));
     if (!cached) {
         S.rows_gen[0] = S.rows_gen[1] = ~0ull;  // (until the table below is complete)
-        // atom of each live batch: both types list live batches in the same (creation) order
-        std::vector<int32_t> atom_of_batch[2];
-        for (int w = 0; w < 2; ++w) {
-            atom_of_batch[w].assign(h->batches.size(), -1);
-            for (size_t a = 0; a < h->sys[w].atoms.size(); ++a) atom_of_batch[w][(size_t)h->sys[w].atoms[a].batch] = (int32_t)a;
-        }
         std::vector<EggMeasureRow> rows;
-        for (int64_t i = 0; i < n_ids; ++i) {
-            const size_t bi = (size_t)(find_batch(h, ids[i]) - h->batches.data());
-            for (int w = 0; w < 2; ++w) {
-                const int32_t a = atom_of_batch[w][bi];
-                if (!(spec->type_mask >> w & 1) || a < 0) continue;
-                const Atom &at = h->sys[w].atoms[(size_t)a];
-                if (at.count < 1) continue;
-                if (at.offset < 0 || (int64_t)at.offset + at.count > h->sys[w].n)
-                    return fail(h, EGG_ERR_INTERNAL, "%s: atom %d of type %d holds %d particles from %d", name, (int)a, w, (int)at.count, (int)at.offset);
-                rows.push_back(EggMeasureRow{at.offset, at.count, w, (int32_t)(2 * i + w)});
-            }
-        }
+        rc = for_each_requested_atom(h, name, spec->type_mask, n_ids, ids, [&](const Atom &at, int w, int32_t slot) {
+            rows.push_back(EggMeasureRow{at.offset, at.count, w, slot});
+            return (int)EGG_OK;
+        });
+        if (rc != EGG_OK) return rc;
         HIP_TRY(h, S.d_rows.reserve(rows.size(), false, nullptr));
         if (!rows.empty()) HIP_TRY(h, hipMemcpy(S.d_rows.p, rows.data(), rows.size() * sizeof(EggMeasureRow), hipMemcpyHostToDevice));
         S.n_rows = (int32_t)rows.size();

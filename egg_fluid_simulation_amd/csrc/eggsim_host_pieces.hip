@@ -1,5 +1,6 @@
 // eggsim_host_pieces.hip -- pieces (include/eggsim.h, "pieces"): the checks of a call, the task table
-// and the launches of eggsim_pieces.hip, one per class of atoms present.  A call copies one task table up (none when it
+// and the launches of eggsim_pieces.hip, one per class of atoms present, over the shared host layer of eggsim_host_scan.hip
+// (the id list, the walk over its atoms, the grid cap).  A call copies one task table up (none when it
 // asks for every live batch and neither the atoms nor the mask moved since the last such call) and the records back once.
 // It stores no answer; a step launches nothing of this and takes no argument from it.
 #include "eggsim_host.h"
@@ -25,12 +26,6 @@ namespace {
 // beyond that are taken in a grid stride.  (EGGSIM_PIECES_GROUPS_PER_CU: developer override, 1 .. 32;
 // profiles/r30_pieces.md has the sweep behind the default)
 constexpr int kGroupsPerCu = 16;
-int pieces_groups(const egg_handle *h, int64_t n_tasks) {
-    const char *e = getenv("EGGSIM_PIECES_GROUPS_PER_CU");
-    const int per_cu = e ? std::min(32, std::max(1, atoi(e))) : kGroupsPerCu;
-    const int64_t most = per_cu * (int64_t)std::max(1, h->prop.multiProcessorCount);
-    return (int)std::min<int64_t>(n_tasks, most);
-}
 
 size_t pieces_lds(int32_t largest) { return (size_t)EGG_PC_LDS_PER_PARTICLE * (size_t)largest + EGG_PC_TAIL; }
 
@@ -50,15 +45,14 @@ int egg_pieces(egg_handle *h, const egg_pieces_spec *spec, int64_t n_ids, const 
     static_assert(EGG_PIECES_MAX_ATOM == EGG_PC_MAX_ATOM, "the kernel's cap is the ABI's");
     static_assert((size_t)EGG_PC_LDS_PER_PARTICLE * EGG_PC_MAX_ATOM + EGG_PC_TAIL <= kLdsMax, "the largest atom fits a compute unit's LDS");
     static_assert(EGG_PC_WAVE_ATOM <= EGG_PC_MAX_ATOM, "the classes");
-    if (h->in_flight) return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_pieces: a step is in flight (egg_step_begin without egg_step_end)");
-    if (h->wire_active) return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_pieces: a step is in flight (egg_rx_begin without egg_rx_end)");
+    REJECT_IN_FLIGHT(h, "egg_pieces");
     if (!spec) return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_pieces: spec is NULL");
     if (!out) return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_pieces: out is NULL");
     if (n_ids < 0 || (n_ids > 0 && !ids) || (n_ids == 0 && ids))
         return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_pieces: n_ids = %lld %s a list (0 and NULL mean every live batch)", (long long)n_ids,
                     ids ? "with" : "without");
-    for (int64_t i = 0; i < n_ids; ++i)
-        if (!find_batch(h, ids[i])) return fail(h, EGG_ERR_UNKNOWN_ID, "egg_pieces: no batch with id `%lld`", (long long)ids[i]);
+    int rc = check_batch_ids(h, "egg_pieces", n_ids, ids);
+    if (rc != EGG_OK) return rc;
     for (int w = 0; w < 2; ++w)
         if (!std::isfinite(spec->reach[w]) || !(spec->reach[w] > 0.0))
             return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_pieces: reach[%d] = %g: it is finite and above 0", w, spec->reach[w]);
@@ -67,7 +61,7 @@ int egg_pieces(egg_handle *h, const egg_pieces_spec *spec, int64_t n_ids, const 
     const bool all = n_ids == 0;
     std::vector<int64_t> every;
     if (all) {
-        for (int32_t bi : h->order) every.push_back(h->batches[(size_t)bi].id);
+        every = live_batch_ids(h);
         ids = every.data();
         n_ids = (int64_t)every.size();
     }
@@ -84,37 +78,25 @@ int egg_pieces(egg_handle *h, const egg_pieces_spec *spec, int64_t n_ids, const 
     System &W = h->sys[0], &Y = h->sys[1];
     std::vector<egg_piece_summary> records(2 * (size_t)n_ids, egg_piece_summary{});
     (void)hipSetDevice(h->device);
-    for (int w = 0; w < 2; ++w) {
-        const int rc = upload_atoms(h, w);
-        if (rc != EGG_OK) return rc;
-    }
+    rc = upload_atoms(h);
+    if (rc != EGG_OK) return rc;
     if (!h->pieces_state) h->pieces_state = std::make_shared<PiecesState>();
     PiecesState &S = *h->pieces_state;
     const bool cached = all && S.table_is_all && S.all_mask == spec->type_mask && S.all_gen[0] == W.atoms_gen && S.all_gen[1] == Y.atoms_gen;
     if (!cached) {
         S.table_is_all = false;  // (until the table below is complete)
-        // atom of each live batch: both types list live batches in the same (creation) order
-        std::vector<int32_t> atom_of_batch[2];
-        for (int w = 0; w < 2; ++w) {
-            atom_of_batch[w].assign(h->batches.size(), -1);
-            for (size_t a = 0; a < h->sys[w].atoms.size(); ++a) atom_of_batch[w][(size_t)h->sys[w].atoms[a].batch] = (int32_t)a;
-        }
         std::vector<EggPiecesTask> tasks[2];
         int32_t largest[2] = {0, 0};
-        for (int64_t i = 0; i < n_ids; ++i) {
-            const size_t bi = (size_t)(find_batch(h, ids[i]) - h->batches.data());
-            for (int w = 0; w < 2; ++w) {
-                const int32_t a = atom_of_batch[w][bi];
-                if (!(spec->type_mask >> w & 1) || a < 0) continue;
-                const Atom &at = h->sys[w].atoms[(size_t)a];
-                if (at.count < 1) continue;
-                if (at.count > EGG_PC_MAX_ATOM || (int64_t)at.offset + at.count > h->sys[w].n)
-                    return fail(h, EGG_ERR_INTERNAL, "egg_pieces: atom %d of type %d holds %d particles from %d", (int)a, w, (int)at.count, (int)at.offset);
-                const int c = at.count <= EGG_PC_WAVE_ATOM ? 0 : 1;
-                tasks[c].push_back(EggPiecesTask{at.offset, at.count, w, (int32_t)(2 * i + w)});
-                largest[c] = std::max(largest[c], at.count);
-            }
-        }
+        rc = for_each_requested_atom(h, "egg_pieces", spec->type_mask, n_ids, ids, [&](const Atom &at, int w, int32_t slot) {
+            if (at.count > EGG_PC_MAX_ATOM)
+                return fail(h, EGG_ERR_INTERNAL, "egg_pieces: atom %d of type %d holds %d particles from %d", (int)(&at - h->sys[w].atoms.data()), w,
+                            (int)at.count, (int)at.offset);
+            const int c = at.count <= EGG_PC_WAVE_ATOM ? 0 : 1;
+            tasks[c].push_back(EggPiecesTask{at.offset, at.count, w, slot});
+            largest[c] = std::max(largest[c], at.count);
+            return (int)EGG_OK;
+        });
+        if (rc != EGG_OK) return rc;
         for (int c = 0; c < 2; ++c) {
             S.n_class[c] = (int32_t)tasks[c].size();
             S.max_class[c] = largest[c];
@@ -171,7 +153,7 @@ int egg_pieces(egg_handle *h, const egg_pieces_spec *spec, int64_t n_ids, const 
             if (S.n_class[c] == 0) continue;
             A.tasks = S.d_tasks.p + (c ? S.n_class[0] : 0);
             A.n_tasks = S.n_class[c];
-            const unsigned groups = (unsigned)pieces_groups(h, S.n_class[c]);
+            const unsigned groups = (unsigned)grid_cap(h, S.n_class[c], kGroupsPerCu, "EGGSIM_PIECES_GROUPS_PER_CU");
             const size_t lds = pieces_lds(S.max_class[c]);
             if (c == 0)
                 hipLaunchKernelGGL(egg_pieces_wave_kernel, dim3(groups), dim3(EGG_WAVE), lds, W.stream, A);

@@ -1,17 +1,13 @@
-// eggsim_host_probes.hip -- probes (include/eggsim.h, "probes"): the checks of a call, the unit table and
-// the launches of eggsim_probes.hip, and the way back from a winning array index to (batch, key, index in the batch).  A call
-// is two launches on the white stream and one copy back; it stores no list and no answer, a step launches nothing of this
-// and takes no argument from it.
+// eggsim_host_probes.hip -- probes (include/eggsim.h, "probes"): the checks of a call, the launches of
+// eggsim_probes.hip over the unit table of the shared host layer (eggsim_host_scan.hip), and the way back from a winning
+// array index to (batch, key, index in the batch).  A call is two launches on the white stream and one copy back; it stores
+// no list and no answer, a step launches nothing of this and takes no argument from it.
 #include "eggsim_host.h"
 
 namespace egghost {
 
 struct ProbeState {
-    // every unit of every type some probe of the last call covered, rebuilt when the atoms or the coverage moved
-    DevBuf<EggScanUnit> d_units;
-    uint64_t units_gen[2] = {~0ull, ~0ull};
-    int units_cover = -1;
-    int32_t n_units = 0;
+    UnitTable units;  // every unit of every type some probe of the last call covered
     DevBuf<double> part_score;
     DevBuf<int32_t> part_index;
     DevBuf<EggProbeOut> out;
@@ -20,16 +16,8 @@ struct ProbeState {
 namespace {
 
 // the grid is sized to the device, not to the scene: kWavesPerCu one-wave workgroups per compute unit at the most
-// (EGGSIM_PROBE_WAVES_PER_CU: developer override, 1 .. 32, read once; profiles/r28_probes.md has the sweep behind the default)
+// (EGGSIM_PROBE_WAVES_PER_CU: developer override, 1 .. 32; profiles/r28_probes.md has the sweep behind the default)
 constexpr int kWavesPerCu = 16;
-int probe_waves(const egg_handle *h, int64_t n_units) {
-    static const int per_cu = [] {
-        const char *e = getenv("EGGSIM_PROBE_WAVES_PER_CU");
-        return e ? std::min(32, std::max(1, atoi(e))) : kWavesPerCu;
-    }();
-    const int64_t most = per_cu * (int64_t)std::max(1, h->prop.multiProcessorCount);
-    return (int)std::min<int64_t>(n_units, most);
-}
 
 }  // namespace
 }  // namespace egghost
@@ -80,32 +68,18 @@ int egg_probe(egg_handle *h, int32_t n, const egg_probe_query *probes, egg_probe
     }
     if (n == 0) return EGG_OK;
     std::vector<egg_probe_hit> found((size_t)n * 2);  // (zeros: found = 0)
-    for (int w = 0; w < 2; ++w)
-        if (h->sys[w].n == 0) cover &= ~(1 << w);
+    cover = covered_types(h, cover);
     if (cover != 0) {  // (else nothing to launch: no particles of a type some probe covers)
         (void)hipSetDevice(h->device);
-        for (int w = 0; w < 2; ++w) {
-            const int rc = upload_atoms(h, w);
-            if (rc != EGG_OK) return rc;
-        }
+        int rc = upload_atoms(h);
+        if (rc != EGG_OK) return rc;
         if (!h->probe_state) h->probe_state = std::make_shared<ProbeState>();
         ProbeState &S = *h->probe_state;
         System &W = h->sys[0], &Y = h->sys[1];
-        if (S.units_cover != cover || S.units_gen[0] != W.atoms_gen || S.units_gen[1] != Y.atoms_gen) {
-            std::vector<EggScanUnit> units;
-            for (int w = 0; w < 2; ++w)
-                if (cover >> w & 1)
-                    for (const Atom &a : h->sys[w].atoms) push_units(a, w, units);
-            HIP_TRY(h, S.d_units.reserve(units.size(), false, nullptr));
-            if (!units.empty())
-                HIP_TRY(h, hipMemcpy(S.d_units.p, units.data(), units.size() * sizeof(EggScanUnit), hipMemcpyHostToDevice));
-            S.n_units = (int32_t)units.size();
-            S.units_cover = cover;
-            S.units_gen[0] = W.atoms_gen;
-            S.units_gen[1] = Y.atoms_gen;
-        }
-        if (S.n_units > 0) {
-            const int waves = probe_waves(h, S.n_units);
+        rc = S.units.refresh(h, "egg_probe", cover, false);
+        if (rc != EGG_OK) return rc;
+        if (S.units.n_units > 0) {
+            const int waves = grid_cap(h, S.units.n_units, kWavesPerCu, "EGGSIM_PROBE_WAVES_PER_CU");
             HIP_TRY(h, S.part_score.reserve((size_t)waves * 2 * EGG_WAVE, false, nullptr));
             HIP_TRY(h, S.part_index.reserve((size_t)waves * 2 * EGG_WAVE, false, nullptr));
             HIP_TRY(h, S.out.reserve((size_t)EGG_MAX_PROBES * 2, false, nullptr));
@@ -118,9 +92,9 @@ int egg_probe(egg_handle *h, int32_t n, const egg_probe_query *probes, egg_probe
                 A.y[w] = F.y[w] = s.y[s.cur].p;
                 A.radius[w] = F.radius[w] = s.radius.p;
             }
-            A.units = S.d_units.p;
+            A.units = S.units.d_units.p;
             A.n_probes = F.n_probes = n;
-            A.n_units = S.n_units;
+            A.n_units = S.units.n_units;
             A.part_score = S.part_score.p;
             A.part_index = S.part_index.p;
             memcpy(A.probes, probes, (size_t)n * sizeof(egg_probe_query));

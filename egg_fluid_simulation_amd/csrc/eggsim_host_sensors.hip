@@ -1,28 +1,19 @@
-// eggsim_host_sensors.hip -- sensors (include/eggsim.h, "sensors"): the list, the unit tables and the
-// launches of eggsim_sensors.hip.  A read is two launches on the white stream and one copy back; a step launches nothing
-// of this and takes no argument from it.
+// eggsim_host_sensors.hip -- sensors (include/eggsim.h, "sensors"): the list, the check of a region
+// record, the per-batch unit table and the launches of eggsim_sensors.hip, over the shared host layer of
+// eggsim_host_scan.hip (the unit table of the totals, the grid cap, the id list).  A read is two launches on the white
+// stream and one copy back; a step launches nothing of this and takes no argument from it.
 #include "eggsim_host.h"
 
 namespace egghost {
 
 struct SensorState {
     DevBuf<EggSensor> d_sensors;        // written when the list is set, never per read
-    // the totals' unit table: every unit of every type some sensor covers, rebuilt when the atoms or the coverage moved
-    DevBuf<EggSensorUnit> d_units;
-    uint64_t units_gen[2] = {~0ull, ~0ull};
-    int units_cover = -1;
-    int32_t n_units = 0;
+    UnitTable units;                    // the totals': every unit of every type some sensor covers
     DevBuf<long long> partials, out;
     // the per-batch read: built for the listed ids of every call
     DevBuf<EggSensorUnit> d_batch_units;
     DevBuf<int32_t> unit_counts, rows, counts;
 };
-
-// the units of atom a of type w behind `units` (the probes' scan walks the same units: eggsim_host_probes.hip)
-void push_units(const Atom &a, int w, std::vector<EggSensorUnit> &units) {
-    for (int32_t at = 0; at < a.count; at += EGG_SN_UNIT)
-        units.push_back(EggSensorUnit{a.offset + at, std::min<int32_t>(EGG_SN_UNIT, a.count - at), w, 0});
-}
 
 // The checks and the normalisation of one region record (include/eggsim.h, "sensors"): the rule of egg_set_sensors, shared
 // with every caller that takes regions.  `what` opens the message, k is the record's index.
@@ -60,25 +51,16 @@ int check_region(egg_handle *h, const char *what, int32_t k, egg_region &o) {
 namespace {
 
 // bit w: some sensor's mask covers type w and the type has particles
-int covered_types(const egg_handle *h) {
+int sensor_cover(const egg_handle *h) {
     int cover = 0;
     for (const egg_sensor &s : h->sensors) cover |= s.type_mask;
-    for (int w = 0; w < 2; ++w)
-        if (h->sys[w].n == 0) cover &= ~(1 << w);
-    return cover;
+    return covered_types(h, cover);
 }
 
 // the grid is sized to the device, not to the scene: kWavesPerCu one-wave workgroups per compute unit at the most
-// (EGGSIM_SENSOR_WAVES_PER_CU: developer override, 1 .. 32, read once; profiles/r27_sensors.md has the sweep behind the default)
+// (EGGSIM_SENSOR_WAVES_PER_CU: developer override, 1 .. 32; profiles/r27_sensors.md has the sweep behind the default)
 constexpr int kWavesPerCu = 8;
-int sensor_waves(const egg_handle *h, int64_t n_units) {
-    static const int per_cu = [] {
-        const char *e = getenv("EGGSIM_SENSOR_WAVES_PER_CU");
-        return e ? std::min(32, std::max(1, atoi(e))) : kWavesPerCu;
-    }();
-    const int64_t most = per_cu * (int64_t)std::max(1, h->prop.multiProcessorCount);
-    return (int)std::min<int64_t>(n_units, most);
-}
+int sensor_waves(const egg_handle *h, int64_t n_units) { return grid_cap(h, n_units, kWavesPerCu, "EGGSIM_SENSOR_WAVES_PER_CU"); }
 
 void sensor_args(egg_handle *h, SensorState &S, EggSensorArgs &A) {
     A = EggSensorArgs{};
@@ -89,12 +71,6 @@ void sensor_args(egg_handle *h, SensorState &S, EggSensorArgs &A) {
     }
     A.sensors = S.d_sensors.p;
     A.n_sensors = (int32_t)h->sensors.size();
-}
-
-int refuse_in_flight(egg_handle *h, const char *name) {
-    if (h->in_flight) return fail(h, EGG_ERR_INVALID_ARGUMENT, "%s: a step is in flight (egg_step_begin without egg_step_end)", name);
-    if (h->wire_active) return fail(h, EGG_ERR_INVALID_ARGUMENT, "%s: a step is in flight (egg_rx_begin without egg_rx_end)", name);
-    return EGG_OK;
 }
 
 }  // namespace
@@ -144,10 +120,7 @@ int egg_get_sensors(const egg_handle *h, int32_t cap, egg_sensor *out, int32_t *
 // Not cached: every call measures the arrays egg_download_particles would return now.
 int egg_read_sensors(egg_handle *h, int32_t cap, egg_sensor_reading *readings, int64_t dropped[2], int32_t *n) {
     if (!h) return EGG_ERR_INVALID_ARGUMENT;
-    {
-        const int rc = refuse_in_flight(h, "egg_read_sensors");
-        if (rc != EGG_OK) return rc;
-    }
+    REJECT_IN_FLIGHT(h, "egg_read_sensors");
     const int32_t have = (int32_t)h->sensors.size();
     if (n) *n = have;
     if (dropped) dropped[0] = dropped[1] = 0;
@@ -155,36 +128,27 @@ int egg_read_sensors(egg_handle *h, int32_t cap, egg_sensor_reading *readings, i
     if (give > 0) memset(readings, 0, (size_t)give * sizeof(egg_sensor_reading));
     if (have == 0) return EGG_OK;
     (void)hipSetDevice(h->device);
-    for (int w = 0; w < 2; ++w) {
-        const int rc = upload_atoms(h, w);
+    {
+        const int rc = upload_atoms(h);
         if (rc != EGG_OK) return rc;
     }
-    const int cover = covered_types(h);
+    const int cover = sensor_cover(h);
     if (cover == 0) return EGG_OK;  // (nothing to launch: no particles, or no sensor covers a type that has some)
     SensorState &S = *h->sensor_state;
     System &W = h->sys[0], &Y = h->sys[1];
-    if (S.units_cover != cover || S.units_gen[0] != W.atoms_gen || S.units_gen[1] != Y.atoms_gen) {
-        std::vector<EggSensorUnit> units;
-        for (int w = 0; w < 2; ++w)
-            if (cover >> w & 1)
-                for (const Atom &a : h->sys[w].atoms) push_units(a, w, units);
-        HIP_TRY(h, S.d_units.reserve(units.size(), false, nullptr));
-        if (!units.empty())
-            HIP_TRY(h, hipMemcpy(S.d_units.p, units.data(), units.size() * sizeof(EggSensorUnit), hipMemcpyHostToDevice));
-        S.n_units = (int32_t)units.size();
-        S.units_cover = cover;
-        S.units_gen[0] = W.atoms_gen;
-        S.units_gen[1] = Y.atoms_gen;
+    {
+        const int rc = S.units.refresh(h, "egg_read_sensors", cover, false);
+        if (rc != EGG_OK) return rc;
     }
-    if (S.n_units == 0) return EGG_OK;
-    const int waves = sensor_waves(h, S.n_units);
+    if (S.units.n_units == 0) return EGG_OK;
+    const int waves = sensor_waves(h, S.units.n_units);
     HIP_TRY(h, S.partials.reserve((size_t)waves * EGG_SN_ROWS * EGG_WAVE, false, nullptr));
     HIP_TRY(h, S.out.reserve((size_t)EGG_SN_ROWS * EGG_WAVE, false, nullptr));
     HIP_TRY(h, hipStreamSynchronize(Y.stream));
     EggSensorArgs A;
     sensor_args(h, S, A);
-    A.units = S.d_units.p;
-    A.n_units = S.n_units;
+    A.units = S.units.d_units.p;
+    A.n_units = S.units.n_units;
     A.partials = S.partials.p;
     hipLaunchKernelGGL(egg_sensor_sums_kernel, dim3((unsigned)waves), dim3(EGG_WAVE), 0, W.stream, A);
     HIP_TRY(h, hipGetLastError());
@@ -211,13 +175,11 @@ int egg_read_sensors(egg_handle *h, int32_t cap, egg_sensor_reading *readings, i
 
 int egg_read_sensor_batches(egg_handle *h, int64_t n_ids, const int64_t *ids, int32_t *counts) {
     if (!h || n_ids < 0 || (n_ids > 0 && !ids)) return EGG_ERR_INVALID_ARGUMENT;
-    {
-        const int rc = refuse_in_flight(h, "egg_read_sensor_batches");
+    REJECT_IN_FLIGHT(h, "egg_read_sensor_batches");
+    {  // (before anything is written)
+        const int rc = check_batch_ids(h, "egg_read_sensor_batches", n_ids, ids);
         if (rc != EGG_OK) return rc;
     }
-    for (int64_t i = 0; i < n_ids; ++i)  // (before anything is written)
-        if (!find_batch(h, ids[i]))
-            return fail(h, EGG_ERR_UNKNOWN_ID, "egg_read_sensor_batches: no batch with id `%lld`", (long long)ids[i]);
     const int32_t have = (int32_t)h->sensors.size();
     if (n_ids == 0 || have == 0) return EGG_OK;
     if (!counts) return fail(h, EGG_ERR_INVALID_ARGUMENT, "egg_read_sensor_batches: counts is NULL");
@@ -226,24 +188,22 @@ int egg_read_sensor_batches(egg_handle *h, int64_t n_ids, const int64_t *ids, in
     const size_t words = (size_t)n_ids * (size_t)have * 2;
     memset(counts, 0, words * sizeof(int32_t));
     (void)hipSetDevice(h->device);
-    for (int w = 0; w < 2; ++w) {
-        const int rc = upload_atoms(h, w);
+    {
+        const int rc = upload_atoms(h);
         if (rc != EGG_OK) return rc;
     }
-    const int cover = covered_types(h);
+    const int cover = sensor_cover(h);
     if (cover == 0) return EGG_OK;
     SensorState &S = *h->sensor_state;
     System &W = h->sys[0], &Y = h->sys[1];
-    // atom of each live batch: both types list live batches in the same (creation) order.  A batch listed twice has its
-    // units once and two rows that point at them.
-    std::vector<int32_t> atom_of_batch(h->batches.size(), -1);
-    for (size_t a = 0; a < W.atoms.size(); ++a) atom_of_batch[(size_t)W.atoms[a].batch] = (int32_t)a;
+    // a batch listed twice has its units once and two rows that point at them
+    const std::vector<int32_t> atom_of = atom_of_batch(h);
     std::vector<int32_t> first_of_atom[2];
     std::vector<EggSensorUnit> units;
     std::vector<int32_t> rows(4 * (size_t)n_ids, 0);  // [2 n_ids] first unit, then [2 n_ids] unit count
-    for (int w = 0; w < 2; ++w) first_of_atom[w].assign(W.atoms.size(), -1);
+    for (int w = 0; w < 2; ++w) first_of_atom[w].assign(h->sys[w].atoms.size(), -1);
     for (int64_t i = 0; i < n_ids; ++i) {
-        const int32_t a = atom_of_batch[(size_t)ids[i] - 1];
+        const int32_t a = atom_of[(size_t)ids[i] - 1];
         for (int w = 0; w < 2; ++w) {
             if (!(cover >> w & 1) || a < 0) continue;
             const Atom &at = h->sys[w].atoms[(size_t)a];

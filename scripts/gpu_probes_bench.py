@@ -12,8 +12,8 @@ reach of 32 px on a diagonal across the grid; `inf`, the same points with reach 
 scene.  The YARDSTICK is what a caller does on a build without probes for the same answer: download of x, y, radius and
 batch_id of both types and the model's rule in numpy (tests/probe_model.py), on the same state in the same run; its hits
 are checked against the call's, field for field.  The yardstick's repeats are a fifth of the call's.
-sweep: the `inf` workload of config3 only, for the grid cap this process runs with (EGGSIM_PROBE_WAVES_PER_CU, read once
-per process: run one process per value).
+sweep: the `inf` workload of config3 only, for the grid cap this process runs with (EGGSIM_PROBE_WAVES_PER_CU, read at
+every call, as every such override is: one process per value still keeps the values' records apart).
 trace: exactly `repeats` calls per (scene config3, workload, count) and nothing else that launches a probe kernel, to be
 run under a kernel trace; --summarise reads the trace's CSV back, cuts the probe kernels' records into those groups by their
 order and prints the median time of the scan and of the finishing kernel per group."""

@@ -13,7 +13,8 @@ vectorised numpy (`numpy_sums`, `numpy_batches`), on the same state in the same 
 read's.  The yardstick's repeats are a fifth of the read's (it is some hundred times slower).
 steps: ms per step over a steady window with the list never set (`unset`, the only mode an earlier commit has) and with 64
 sensors set and never read (`set`); --package-root imports the package from another checkout (mode unset only), so that two
-builds can be compared in one session, alternating."""
+builds can be compared in one session, alternating.
+The grid cap's developer override (EGGSIM_SENSOR_WAVES_PER_CU) is read at every call, as every such override is."""
 import argparse
 import json
 import os

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from scan_surface import OBSERVER_UNITS, in_flight_messages_have_one_home, sources
 from test_abi import _prototypes
 
 CSRC = os.path.join(ROOT, "egg_fluid_simulation_amd", "csrc")
@@ -116,7 +117,14 @@ def test_the_kernels_exist_and_no_step_unit_names_them():
     assert "sizeof(egg_field_spec) == 40" in host and "sizeof(egg_field_totals) == 56" in host and "EGG_FIELD_VELOCITY_SCALE == EGG_FD_SCALE" in host
     assert "<= (int)kLdsMax" in host and "constexpr int kWavesPerCu = 8;" in host  # (the wave cap per compute unit fits its LDS)
     # the unit table is the shared builder's, and its state is this feature's own
-    assert "push_units(a, w, units)" in host and "struct FieldState {" in host and "units_gen" in host and "atoms_gen" in host
+    scan = _read(CSRC, "eggsim_host_scan.hip")
+    assert re.search(r"struct FieldState \{\n\s*UnitTable units;", host) and "->units.refresh(h, name, cover, false)" in host
+    refresh = scan[scan.index("int UnitTable::refresh("):]
+    refresh = refresh[:refresh.index("\n}\n")]
+    key = "if (cover == want && gen[0] == h->sys[0].atoms_gen && gen[1] == h->sys[1].atoms_gen) return EGG_OK;"
+    assert key in refresh and "gen[0] = gen[1] = ~0ull;" in refresh and "push_units(a, w, units);" in refresh
+    assert refresh.index(key) < refresh.index("gen[0] = gen[1] = ~0ull;") < refresh.index("push_units(a, w,")  # invalidated, then rebuilt
+    assert refresh.index("hipMemcpy(d_units.p") < refresh.index("gen[0] = h->sys[0].atoms_gen;")              # remembered last
     assert "std::shared_ptr<egghost::FieldState> field_state;" in host_h
     # nothing of a step knows about fields: no step kernel, no step driver, no commit -- and no unit but the fields' own, the
     # two shared headers and the group
@@ -127,7 +135,8 @@ def test_the_kernels_exist_and_no_step_unit_names_them():
             assert "egg_field" not in text and "EggField" not in text and "field_state" not in text and "FieldState" not in text, unit
             assert "EGG_FD_" not in text, unit
     # the refusals, where the source states them: everything is checked before the first launch and before anything is written
-    assert "a step is in flight (egg_step_begin without egg_step_end)" in host and "a step is in flight (egg_rx_begin without egg_rx_end)" in host
+    assert host.index("REJECT_IN_FLIGHT(h, name);") < host.index("return fail(")  # (the first refusal of a call)
+    in_flight_messages_have_one_home()
     assert "opt_solver_order" not in host  # (either order)
     last_check = max(m.start() for m in re.finditer(r'return fail\(h, EGG_ERR_INVALID_ARGUMENT', host))
     assert last_check < host.index("hipLaunchKernelGGL(") and last_check < host.index("hipMemsetAsync(") and last_check < host.index("memset(out->count")
@@ -139,6 +148,32 @@ def test_the_kernels_exist_and_no_step_unit_names_them():
     twin = group[group.index("int egg_group_field("):]
     twin = twin[:twin.index("\n}\n")]
     assert "egg_field(g->h[k], spec," in twin and twin.index("return gfail(") < twin.index("memcpy(host_out->count")
+
+
+def test_what_the_observers_share_has_one_home():
+    units = sources()
+    scan = units["eggsim_host_scan.hip"]
+    in_flight_messages_have_one_home()
+    assert sum(source.count("egg_rx_begin without egg_rx_end)") for source in units.values()) == 1
+    assert sum(source.count("hipMemGetAddressRange(") for source in units.values()) == 1 and "hipMemGetAddressRange(" in scan
+    for unit in OBSERVER_UNITS:
+        assert "multiProcessorCount" not in units[unit], unit
+        assert "REJECT_IN_FLIGHT(h, " in units[unit] and "refuse_in_flight" not in units[unit], unit
+    assert "multiProcessorCount" in scan[scan.index("int grid_cap("):scan.index("bool device_range_fits(")]
+    # the map from a batch to its atom is filled in one function, and every other unit asks that function
+    assigned = [(unit, m.start()) for unit, source in units.items() for m in re.finditer(r"atom_of_batch\[[^;]*\] = ", source)]
+    assert len(assigned) == 1 and assigned[0][0] == "eggsim_host_scan.hip", assigned
+    start = scan.index("atom_of_batch(const egg_handle *h) {")
+    assert start < assigned[0][1] < start + scan[start:].index("\n}\n")
+    # the unit builder, the unit table and the id lists: defined once (the walk over a list's atoms as a template in the
+    # header), named by no feature
+    for line in ("void push_units(const Atom &a, int w, std::vector<EggScanUnit> &units) {", "int UnitTable::refresh(", "int covered_types(",
+                 "int check_batch_ids(", "std::vector<int64_t> live_batch_ids(", "int upload_atoms(egg_handle *h) {"):
+        assert sum(source.count(line) for unit, source in units.items() if not unit.endswith(".h")) == 1 and line in scan, line
+    assert sum(source.count("int for_each_requested_atom(") for source in units.values()) == 1
+    assert "int for_each_requested_atom(" in units["eggsim_host.h"]
+    makefile = _read(CSRC, "Makefile")
+    assert makefile.count("eggsim_host_scan.hip") == 1
 
 
 def test_python_classes_have_the_methods_with_equal_parameter_lists():

@@ -10,6 +10,7 @@ import pytest
 
 import measure_model as mm
 from conftest import ROOT
+from scan_surface import in_flight_messages_have_one_home
 from test_abi import _prototypes
 
 CSRC = os.path.join(ROOT, "egg_fluid_simulation_amd", "csrc")
@@ -108,9 +109,13 @@ def test_the_kernel_exists_and_nothing_else_names_it():
     # the host side: the ABI's constants are the kernel's, the table is kept by the atoms, the mask and the list, the checks
     # come before the first launch and before anything is written, only kernel_launches moves
     for line in ("sizeof(egg_measure_spec) == 64", "sizeof(egg_measure_record) == 192", "EGG_MEASURE_SCALE == EGG_MS_SCALE",
-                 "struct MeasureState {", "atoms_gen", "check_region(h, what.c_str(), 0, region)", "on_device_of(h, p)", "hipMemGetAddressRange(",
-                 "a step is in flight (egg_step_begin without egg_step_end)", "a step is in flight (egg_rx_begin without egg_rx_end)"):
+                 "struct MeasureState {", "atoms_gen", "check_region(h, what.c_str(), 0, region)", "device_range_fits(h, out, bytes)"):
         assert line in host, line
+    scan = _read(CSRC, "eggsim_host_scan.hip")
+    fits = scan[scan.index("bool device_range_fits("):]
+    assert "on_device_of(h, p)" in fits[:fits.index("\n}\n")] and "hipMemGetAddressRange(" in fits[:fits.index("\n}\n")]
+    assert host.index("REJECT_IN_FLIGHT(h, name);") < host.index("return fail(")  # (the first refusal of a call)
+    in_flight_messages_have_one_home()
     assert "std::shared_ptr<egghost::MeasureState> measure_state;" in host_h and "opt_solver_order" not in host
     last_check = max(m.start() for m in re.finditer(r"return fail\(h, EGG_ERR_(INVALID_ARGUMENT|UNKNOWN_ID)", host))
     assert last_check < host.index("hipLaunchKernelGGL(") and last_check < host.index("hipMemsetAsync(") and last_check < host.index("upload_atoms(")
@@ -125,7 +130,10 @@ def test_the_kernel_exists_and_nothing_else_names_it():
     group = _read(CSRC, "eggsim_group.cpp")
     twin = group[group.index("int egg_group_measure("):]
     twin = twin[:twin.index("\n}\n")]
-    assert "egg_measure(g->h[k], spec," in twin and "r.owner != (int)k" in twin and twin.rindex("return gfail(") < twin.index("memcpy(out,")
+    assert "egg_measure(g->h[k], spec," in twin and "route_to_owners<" in twin and twin.rindex("return gfail(") < twin.index("route_to_owners<")
+    route = group[group.index("int route_to_owners("):]
+    route = route[:route.index("\n}\n")]
+    assert "r.owner != (int)k" in route and route.rindex("return gfail(") < route.index("memcpy(out,")  # (written after every handle answered)
 
 
 def test_python_classes_have_the_methods():

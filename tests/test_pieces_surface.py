@@ -10,6 +10,7 @@ import re
 import pytest
 
 from conftest import ROOT
+from scan_surface import in_flight_messages_have_one_home
 from test_abi import _prototypes
 
 CSRC = os.path.join(ROOT, "egg_fluid_simulation_amd", "csrc")
@@ -111,18 +112,25 @@ def test_the_kernels_exist_and_no_step_unit_names_them():
             assert "egg_pieces" not in text and "EggPiece" not in text and "pieces_state" not in text and "PiecesState" not in text, unit
             assert "EGG_PC_" not in text, unit
     # the refusals, where the source states them: everything is checked before the first launch and before anything is written
-    assert "a step is in flight (egg_step_begin without egg_step_end)" in host and "a step is in flight (egg_rx_begin without egg_rx_end)" in host
+    assert host.index('REJECT_IN_FLIGHT(h, "egg_pieces");') < host.index("return fail(")  # (the first refusal of a call)
+    in_flight_messages_have_one_home()
     assert "opt_solver_order" not in host  # (either order)
     last_check = max(m.start() for m in re.finditer(r"return fail\(h, EGG_ERR_(INVALID_ARGUMENT|UNKNOWN_ID|UNSUPPORTED), \"egg_pieces: (?!the device)", host))
     assert last_check < host.index("hipLaunchKernelGGL(") and last_check < host.index("hipMemsetAsync(") and last_check < host.index("memcpy(out,")
     assert last_check < host.index("upload_atoms(") and host.index("memcpy(out,") > host.index("hipStreamSynchronize(W.stream)")
     assert host.count("h->stats.kernel_launches += 1;") == 1 and "h->stats." not in host.replace("h->stats.kernel_launches += 1;", "")
-    for name in ("spec is NULL", "out is NULL", "no batch with id", "it is finite and above 0", "type_mask %d", "an atom holds at most %d"):
+    for name in ("spec is NULL", "out is NULL", 'check_batch_ids(h, "egg_pieces", n_ids, ids)', "it is finite and above 0", "type_mask %d",
+                 "an atom holds at most %d"):
         assert name in host, name
+    assert 'return fail(h, EGG_ERR_UNKNOWN_ID, "%s: no batch with id `%lld`", name, (long long)ids[i]);' in _read(CSRC, "eggsim_host_scan.hip")
+    assert host.index("check_batch_ids(") < host.index("reach[%d] = %g")  # (an unknown id is refused before the reach and the mask)
     group = _read(CSRC, "eggsim_group.cpp")
     twin = group[group.index("int egg_group_pieces("):]
     twin = twin[:twin.index("\n}\n")]
-    assert "egg_pieces(g->h[k], spec," in twin and "r.owner != (int)k" in twin and twin.rindex("return gfail(") < twin.index("memcpy(out,")
+    assert "egg_pieces(g->h[k], spec," in twin and "route_to_owners<" in twin and twin.rindex("return gfail(") < twin.index("route_to_owners<")
+    route = group[group.index("int route_to_owners("):]
+    route = route[:route.index("\n}\n")]
+    assert "r.owner != (int)k" in route and route.rindex("return gfail(") < route.index("memcpy(out,")  # (written after every handle answered)
 
 
 def test_python_classes_have_the_methods():

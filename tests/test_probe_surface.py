@@ -104,7 +104,13 @@ def test_the_kernels_exist_and_no_step_unit_names_them():
     assert "sizeof(egg_probe_query) == 48" in host and "sizeof(egg_probe_hit) == 56" in host and "sizeof(EggProbeArgs) <= 4096" in host
     assert "EGG_MAX_PROBES == EGG_PB_MAX_PROBES" in host and "EGG_PROBE_RAY == EGG_PB_RAY" in host
     # the unit table is the shared builder's, and its state is this feature's own
-    assert "push_units(a, w, units)" in host and "struct ProbeState {" in host and "units_gen" in host and "atoms_gen" in host
+    scan = _read(CSRC, "eggsim_host_scan.hip")
+    assert re.search(r"struct ProbeState \{\n\s*UnitTable units;", host) and 'S.units.refresh(h, "egg_probe", cover, false)' in host
+    refresh = scan[scan.index("int UnitTable::refresh("):]
+    refresh = refresh[:refresh.index("\n}\n")]
+    key = "if (cover == want && gen[0] == h->sys[0].atoms_gen && gen[1] == h->sys[1].atoms_gen) return EGG_OK;"
+    assert key in refresh and "gen[0] = gen[1] = ~0ull;" in refresh and "push_units(a, w, units);" in refresh
+    assert refresh.index(key) < refresh.index("gen[0] = gen[1] = ~0ull;") < refresh.index("push_units(a, w,")  # invalidated, then rebuilt
     assert "std::shared_ptr<egghost::ProbeState> probe_state;" in host_h
     # nothing of a step knows about probes: no step kernel, no step driver, no commit -- and no unit but the probes' own, the
     # two shared headers and the group

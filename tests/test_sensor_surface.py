@@ -114,7 +114,7 @@ def test_the_kernels_exist_and_no_step_unit_names_them():
     setter = host[host.index("int egg_set_sensors("):host.index("int egg_get_sensors(")]
     assert 'REJECT_IN_FLIGHT(h, "egg_set_sensors");' in setter and "opt_solver_order" not in setter  # (either order)
     assert setter.index("h->sensors.swap(list);") > max(m.start() for m in re.finditer(r"return fail\(", setter))  # checked, then changed
-    assert 'refuse_in_flight(h, "egg_read_sensors")' in host and 'refuse_in_flight(h, "egg_read_sensor_batches")' in host
+    assert 'REJECT_IN_FLIGHT(h, "egg_read_sensors");' in host and 'REJECT_IN_FLIGHT(h, "egg_read_sensor_batches");' in host
 
 
 def test_python_classes_have_the_methods_with_equal_parameter_lists():
