@@ -107,6 +107,27 @@ int gfail(egg_group *g, int code, const char *fmt, ...) {
         if (_rc < 0) return gfail(g, _rc, "device %d: %s", (int)(k), egg_last_error((g)->h[(size_t)(k)]));       \
     } while (0)
 
+// A list every handle holds alike, set on all of them: set(h, n, records) on every handle, then `stored`, the group's
+// copy, takes the new records.  A handle that refuses (handle 0 refuses bad records before any handle has changed; a later
+// one is a handle somebody drives by hand) fails the group with its text: the handles before it go back to `stored`, and
+// to whatever else `also` puts back on a handle, and `stored` stays as it was.
+template <class R>
+int set_on_every_handle(egg_group *g, int (*set)(egg_handle *, int32_t, const R *), int32_t n, const R *records, std::vector<R> &stored,
+                        void (*also)(const egg_group *, egg_handle *) = nullptr) {
+    for (size_t k = 0; k < g->h.size(); ++k) {
+        const int rc = set(g->h[k], n, records);
+        if (rc < 0) {
+            for (size_t j = 0; j < k; ++j) {
+                (void)set(g->h[j], (int32_t)stored.size(), stored.data());
+                if (also) also(g, g->h[j]);
+            }
+            return gfail(g, rc, "device %d: %s", (int)k, egg_last_error(g->h[k]));
+        }
+    }
+    stored.assign(records, records + (n > 0 ? n : 0));
+    return EGG_OK;
+}
+
 int slab_of(const egg_group *g, double x) {
     int k = 0;
     const int n = (int)g->h.size();
@@ -690,20 +711,14 @@ int egg_group_set_colliders(egg_group *g, int32_t n, const egg_collider *c) {
         (void)egg_get_colliders(g->h[0], have, g->colliders.data(), &have);
         if (!g->spins.empty()) (void)egg_get_collider_spin(g->h[0], have, g->spins.data(), &have);  // (and the pivots)
     }
-    for (size_t k = 0; k < g->h.size(); ++k) {
-        const int rc = egg_set_colliders(g->h[k], n, c);
-        if (rc < 0) {  // (handle 0 refuses a bad list before any handle has changed; a later one: the others go back)
-            for (size_t j = 0; j < k; ++j) {  // (with their surfaces, which a list that is set resets)
-                (void)egg_set_colliders(g->h[j], (int32_t)g->colliders.size(), g->colliders.data());
-                (void)egg_set_collider_surfaces(g->h[j], (int32_t)g->surfaces.size(), g->surfaces.data());
-                (void)egg_set_collider_motion(g->h[j], (int32_t)g->motions.size(), g->motions.data());
-                (void)egg_set_collider_spin(g->h[j], (int32_t)g->spins.size(), g->spins.data());
-                (void)egg_set_collider_styles(g->h[j], (int32_t)g->styles.size(), g->styles.data());
-            }
-            return gfail(g, rc, "device %d: %s", (int)k, egg_last_error(g->h[k]));
-        }
-    }
-    g->colliders.assign(c, c + (n > 0 ? n : 0));
+    const int rc = set_on_every_handle(g, egg_set_colliders, n, c, g->colliders, [](const egg_group *g, egg_handle *h) {
+        // (a handle that goes back to the list gets back the records a list that is set resets)
+        (void)egg_set_collider_surfaces(h, (int32_t)g->surfaces.size(), g->surfaces.data());
+        (void)egg_set_collider_motion(h, (int32_t)g->motions.size(), g->motions.data());
+        (void)egg_set_collider_spin(h, (int32_t)g->spins.size(), g->spins.data());
+        (void)egg_set_collider_styles(h, (int32_t)g->styles.size(), g->styles.data());
+    });
+    if (rc < 0) return rc;
     g->surfaces.clear();  // (every handle has reset its own)
     g->styles.clear();
     g->motions.clear();
@@ -713,15 +728,7 @@ int egg_group_set_colliders(egg_group *g, int32_t n, const egg_collider *c) {
 
 int egg_group_set_collider_surfaces(egg_group *g, int32_t n, const egg_collider_surface *s) {
     if (!g) return EGG_ERR_INVALID_ARGUMENT;
-    for (size_t k = 0; k < g->h.size(); ++k) {
-        const int rc = egg_set_collider_surfaces(g->h[k], n, s);
-        if (rc < 0) {  // (handle 0 refuses bad records before any handle has changed; a later one: the others go back)
-            for (size_t j = 0; j < k; ++j) (void)egg_set_collider_surfaces(g->h[j], (int32_t)g->surfaces.size(), g->surfaces.data());
-            return gfail(g, rc, "device %d: %s", (int)k, egg_last_error(g->h[k]));
-        }
-    }
-    g->surfaces.assign(s, s + (n > 0 ? n : 0));
-    return EGG_OK;
+    return set_on_every_handle(g, egg_set_collider_surfaces, n, s, g->surfaces);
 }
 
 int egg_group_get_collider_surfaces(const egg_group *g, int32_t cap, egg_collider_surface *s, int32_t *n) {
@@ -731,15 +738,7 @@ int egg_group_get_collider_surfaces(const egg_group *g, int32_t cap, egg_collide
 
 int egg_group_set_collider_motion(egg_group *g, int32_t n, const egg_collider_motion *m) {
     if (!g) return EGG_ERR_INVALID_ARGUMENT;
-    for (size_t k = 0; k < g->h.size(); ++k) {
-        const int rc = egg_set_collider_motion(g->h[k], n, m);
-        if (rc < 0) {  // (handle 0 refuses bad records before any handle has changed; a later one: the others go back)
-            for (size_t j = 0; j < k; ++j) (void)egg_set_collider_motion(g->h[j], (int32_t)g->motions.size(), g->motions.data());
-            return gfail(g, rc, "device %d: %s", (int)k, egg_last_error(g->h[k]));
-        }
-    }
-    g->motions.assign(m, m + (n > 0 ? n : 0));
-    return EGG_OK;
+    return set_on_every_handle(g, egg_set_collider_motion, n, m, g->motions);
 }
 
 int egg_group_get_collider_motion(const egg_group *g, int32_t cap, egg_collider_motion *m, int32_t *n) {
@@ -753,15 +752,7 @@ int egg_group_set_collider_spin(egg_group *g, int32_t n, const egg_collider_spin
         int32_t have = 0;
         (void)egg_get_collider_spin(g->h[0], (int32_t)g->spins.size(), g->spins.data(), &have);
     }
-    for (size_t k = 0; k < g->h.size(); ++k) {
-        const int rc = egg_set_collider_spin(g->h[k], n, s);
-        if (rc < 0) {  // (handle 0 refuses bad records before any handle has changed; a later one: the others go back)
-            for (size_t j = 0; j < k; ++j) (void)egg_set_collider_spin(g->h[j], (int32_t)g->spins.size(), g->spins.data());
-            return gfail(g, rc, "device %d: %s", (int)k, egg_last_error(g->h[k]));
-        }
-    }
-    g->spins.assign(s, s + (n > 0 ? n : 0));
-    return EGG_OK;
+    return set_on_every_handle(g, egg_set_collider_spin, n, s, g->spins);
 }
 
 int egg_group_get_collider_spin(const egg_group *g, int32_t cap, egg_collider_spin *s, int32_t *n) {
@@ -771,15 +762,7 @@ int egg_group_get_collider_spin(const egg_group *g, int32_t cap, egg_collider_sp
 
 int egg_group_set_collider_styles(egg_group *g, int32_t n, const egg_collider_style *s) {
     if (!g) return EGG_ERR_INVALID_ARGUMENT;
-    for (size_t k = 0; k < g->h.size(); ++k) {
-        const int rc = egg_set_collider_styles(g->h[k], n, s);
-        if (rc < 0) {  // (handle 0 refuses bad records before any handle has changed; a later one: the others go back)
-            for (size_t j = 0; j < k; ++j) (void)egg_set_collider_styles(g->h[j], (int32_t)g->styles.size(), g->styles.data());
-            return gfail(g, rc, "device %d: %s", (int)k, egg_last_error(g->h[k]));
-        }
-    }
-    g->styles.assign(s, s + (n > 0 ? n : 0));
-    return EGG_OK;
+    return set_on_every_handle(g, egg_set_collider_styles, n, s, g->styles);
 }
 
 int egg_group_get_collider_styles(const egg_group *g, int32_t cap, egg_collider_style *s, int32_t *n) {
@@ -855,15 +838,7 @@ int egg_group_get_collider_loads(egg_group *g, int32_t cap, egg_collider_load *o
 // Sensors (include/eggsim.h, "sensors"): every handle holds the same list and measures the particles it owns.
 int egg_group_set_sensors(egg_group *g, int32_t n, const egg_sensor *sensors) {
     if (!g) return EGG_ERR_INVALID_ARGUMENT;
-    for (size_t k = 0; k < g->h.size(); ++k) {
-        const int rc = egg_set_sensors(g->h[k], n, sensors);
-        if (rc < 0) {  // (handle 0 refuses a bad list before any handle has changed; a later one: the others go back)
-            for (size_t j = 0; j < k; ++j) (void)egg_set_sensors(g->h[j], (int32_t)g->sensors.size(), g->sensors.data());
-            return gfail(g, rc, "device %d: %s", (int)k, egg_last_error(g->h[k]));
-        }
-    }
-    g->sensors.assign(sensors, sensors + (n > 0 ? n : 0));
-    return EGG_OK;
+    return set_on_every_handle(g, egg_set_sensors, n, sensors, g->sensors);
 }
 
 int egg_group_get_sensors(const egg_group *g, int32_t cap, egg_sensor *out, int32_t *n) {
@@ -1133,15 +1108,7 @@ int egg_group_get_collider_hits(egg_group *g, int64_t hits[2]) {
 
 int egg_group_set_forces(egg_group *g, int32_t n, const egg_force *f) {
     if (!g) return EGG_ERR_INVALID_ARGUMENT;
-    for (size_t k = 0; k < g->h.size(); ++k) {
-        const int rc = egg_set_forces(g->h[k], n, f);
-        if (rc < 0) {  // (handle 0 refuses a bad list before any handle has changed; a later one: the others go back)
-            for (size_t j = 0; j < k; ++j) (void)egg_set_forces(g->h[j], (int32_t)g->forces.size(), g->forces.data());
-            return gfail(g, rc, "device %d: %s", (int)k, egg_last_error(g->h[k]));
-        }
-    }
-    g->forces.assign(f, f + (n > 0 ? n : 0));
-    return EGG_OK;
+    return set_on_every_handle(g, egg_set_forces, n, f, g->forces);
 }
 
 int egg_group_get_forces(const egg_group *g, int32_t cap, egg_force *f, int32_t *n) {

@@ -433,6 +433,8 @@ struct FieldState;  // unit table, planes and totals of an egg_field call (eggsi
 struct PiecesState;  // task table, records and labels of an egg_pieces call (eggsim_host_pieces.hip)
 struct ImpulseState;  // records, unit table, partials and totals of an egg_impulse call (eggsim_host_impulses.hip)
 struct MeasureState;  // row table and records of an egg_measure call (eggsim_host_measures.hip)
+// egg_handle::collider_dirty: the tables sync_collider_records has to copy (eggsim_host_colliders.hip)
+enum : unsigned { kDirtyList = 1u, kDirtySurfaces = 2u, kDirtyMotions = 4u, kDirtySpins = 8u, kDirtyAllTables = 15u };
 }
 using namespace egghost;
 
@@ -479,12 +481,17 @@ struct egg_handle {
     int opt_solver_order = 0;       // EGG_OPT_SOLVER_ORDER: 0 exact (the reference's pair order), 1 relaxed
     double opt_relaxation = EGG_RELAXATION_DEFAULT;  // EGG_OPT_RELAXATION: omega of the relaxed pass
     int opt_cohesion = 0;           // EGG_OPT_COHESION: 0 dead as in the reference, 1 effective (relaxed order only)
-    // static colliders (egg_set_colliders; relaxed order only): the list as egg_get_colliders returns it, its copy on the
-    // device (written when the list is set, never per step), and the hits of committed steps per type
+    // static colliders (egg_set_colliders; relaxed order only): the list as egg_get_colliders returns it, and the hits of
+    // committed steps per type.
+    // THE RULE of the four tables on the device (eggsim_host_colliders.hip, sync_collider_records): while the list is not
+    // empty, d_colliders, d_surfaces, d_motions and d_spins each hold one record per collider -- the host's where it has
+    // one, the default or zero record where the host's vector is empty.  Whoever changes a host copy, or lets the device
+    // run ahead of it, sets the table's bit in collider_dirty; prepare_step copies the marked tables before a step's first
+    // launch, and nothing else writes them from the host.
     std::vector<egg_collider> colliders;
     DevBuf<EggCollider> d_colliders;
-    bool colliders_wall = false;  // the list holds an EGG_COLLIDER_WALL: a step launches the wall instantiations, which
-                                  // read the surface records -- d_surfaces then holds one per collider, defaults included
+    unsigned collider_dirty = 0;  // kDirtyList | kDirtySurfaces | kDirtyMotions | kDirtySpins
+    bool colliders_wall = false;  // the list holds an EGG_COLLIDER_WALL: a step launches the wall instantiations
     int64_t collider_hits[2] = {0, 0};
     // colliders in the picture (egg_get_collider_pose, egg_set_collider_styles): the list at the start of the last committed
     // relaxed step -- relaxed_commit copies `colliders` into it before it advances them, egg_set_colliders sets both -- and
@@ -492,25 +499,21 @@ struct egg_handle {
     std::vector<egg_collider> colliders_last;
     std::vector<egg_collider_style> styles;
     // collider surfaces (egg_set_collider_surfaces): empty = every surface is the default, else one record per collider;
-    // the copy on the device (written when they are set, never per step); whether any friction > 0 -- only then does a
-    // step launch the surface instantiations -- and the grips of committed steps per type
+    // whether any friction > 0 -- only then does a step launch the surface instantiations -- and the grips of committed
+    // steps per type
     std::vector<egg_collider_surface> surfaces;
     DevBuf<EggSurface> d_surfaces;
     bool surfaces_grip = false;
     int64_t collider_grips[2] = {0, 0};
-    // collider motion (egg_set_collider_motion): empty = every motion is zero, else one record per collider; the copy on
-    // the device (written when they are set, never per step); whether any component is not zero -- only then does a step
-    // launch the motion instantiations, which read the surface records (d_surfaces then holds one per collider, defaults
-    // included), and only then does a commit advance `colliders` and rewrite d_colliders
+    // collider motion (egg_set_collider_motion): empty = every motion is zero, else one record per collider; whether any
+    // component is not zero -- only then does a step launch the motion instantiations and a commit advance `colliders`
     std::vector<egg_collider_motion> motions;
     DevBuf<EggMotion> d_motions;
     bool motions_move = false;
-    // collider spin (egg_set_collider_spin): empty = every spin is zero, else one record per collider; the copy on the
-    // device (written when they are set and when a commit has advanced the pivots); whether any omega is not zero -- only
-    // then does a step launch the spin instantiations, which read the motion and surface records (d_motions and d_surfaces
-    // then hold one per collider, zeros and defaults included).  spin_table: the step's sines and cosines as prepare_step
-    // computes them (libm), (cos, sin)(t omega) per sub-step and collider, then (cos, sin)(h omega) per collider; the commit
-    // reads the last sub-step's row, the kernels its copy on the device
+    // collider spin (egg_set_collider_spin): empty = every spin is zero, else one record per collider; whether any omega is
+    // not zero -- only then does a step launch the spin instantiations and a commit advance the pivots.  spin_table: the
+    // step's sines and cosines as prepare_step computes them (libm), (cos, sin)(t omega) per sub-step and collider, then
+    // (cos, sin)(h omega) per collider; the commit reads the last sub-step's row, the kernels its copy on the device
     std::vector<egg_collider_spin> spins;
     DevBuf<EggSpin> d_spins;
     bool spins_turn = false;
@@ -862,6 +865,9 @@ struct RelaxedStep {  // one type of one handle in a relaxed step
 // key base of a local atom (batch key, particle count) into *base: EGG_OK, or the status it failed the handle with
 using KeyBaseFn = std::function<int(int64_t, int64_t, int32_t *)>;
 int prepare_step(egg_handle *h, double delta, int S, RelaxedStep st[2]);
+// eggsim_host_colliders.hip: establishes the rule of the four collider tables (egg_handle::collider_dirty) for a handle
+// whose list is not empty.  No step may be running.
+int sync_collider_records(egg_handle *h);
 int prepare_type(RelaxedStep &st, int C, size_t ghosts, const RelaxedLayout &L, const std::vector<uint64_t> &sig,
                  const KeyBaseFn &base_of);
 int launch_substep(RelaxedStep &st, int sub);

@@ -24,8 +24,8 @@
 // device hold one per collider, defaults included.  A list without a wall launches what it launched.
 // While a collider motion is not zero (egg_set_collider_motion, RelaxedLayout::motion) launch_pass picks the motion twin of
 // the instantiation with walls, whether or not the list holds a wall or a friction, and RelaxedStep::mov carries the
-// records and the end time of the pass's sub-step; relaxed_commit advances the handle's stored list by the step and rewrites
-// its copy on the device.  With every motion zero a step launches what it launched, with the same arguments, and a commit
+// records and the end time of the pass's sub-step; relaxed_commit advances the handle's stored list by the step and marks
+// it dirty, so the next step's prepare_step rewrites its copy on the device.  With every motion zero a step launches what it launched, with the same arguments, and a commit
 // touches no list.
 // While a collider spin is not zero (egg_set_collider_spin, RelaxedLayout::spin) launch_pass picks the spin twin of the
 // motion instantiation, whether or not anything moves, and RelaxedStep::spn carries the records and the sub-step's row of
@@ -42,7 +42,7 @@
 // not empty) relaxed_step_bodies drives the step: the loads instantiations run with every rule on, launch_pass poses every
 // sub-step as the first of a step over the records on the device, and after the last launch of a sub-step of both types one
 // launch of egg_rx_bodies_kernel rewrites those records from the sums the sub-step has added.  relaxed_commit reads them
-// back in place of advance_colliders; a failed step puts the host's copies back.  With no body a step enqueues and launches
+// back in place of advance_colliders; after a failed step the next one puts the host's copies back.  With no body a step enqueues and launches
 // what it always did.
 // While collider contacts act besides (egg_set_collider_contacts: bodies act and some record is on) every launch of the
 // integrator is followed, on the same stream and inside the same bracket of events, by one launch of
@@ -195,31 +195,14 @@ static bool bodies_act(const egg_handle *h) { return h->bodies_any && h->opt_loa
 // Collider contacts act where bodies act and some contact record is on.
 static bool contacts_act(const egg_handle *h) { return bodies_act(h) && h->contacts_any; }
 
-// The records a step with bodies runs on, from the host's copies to the device: the list, and a surface, a motion and a
-// spin record for every collider, defaults and zeros included.  No step is running.
-static int upload_body_records(egg_handle *h) {
-    const size_t n = h->colliders.size();
-    const std::vector<egg_collider_surface> srf = h->surfaces.empty() ? std::vector<egg_collider_surface>(n, egg_collider_surface{0.0, 0.0, 0.0}) : h->surfaces;
-    const std::vector<egg_collider_motion> mov = h->motions.empty() ? std::vector<egg_collider_motion>(n, egg_collider_motion{0.0, 0.0}) : h->motions;
-    const std::vector<egg_collider_spin> spn = h->spins.empty() ? std::vector<egg_collider_spin>(n, egg_collider_spin{0.0, 0.0, 0.0}) : h->spins;
-    HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, h->d_surfaces.reserve(EGG_MAX_COLLIDERS, false, nullptr));
-    HIP_TRY(h, h->d_motions.reserve(EGG_MAX_COLLIDERS, false, nullptr));
-    HIP_TRY(h, h->d_spins.reserve(EGG_MAX_COLLIDERS, false, nullptr));
-    HIP_TRY(h, hipMemcpy(h->d_colliders.p, h->colliders.data(), n * sizeof(egg_collider), hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(h->d_surfaces.p, srf.data(), n * sizeof(egg_collider_surface), hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(h->d_motions.p, mov.data(), n * sizeof(egg_collider_motion), hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(h->d_spins.p, spn.data(), n * sizeof(egg_collider_spin), hipMemcpyHostToDevice));
-    return EGG_OK;
-}
-
-// Per step with bodies acting: the records above, the body records, the turn (c, s) of the first sub-step per collider --
-// a free-turning body's by the four lines of the integrator, any other's by libm, (cos, sin)(h omega) -- and `seen`, which
-// starts at zero with the sums.
+// Per step with bodies acting, over the collider tables prepare_step has synchronised: the body records, the turn (c, s) of
+// the first sub-step per collider -- a free-turning body's by the four lines of the integrator, any other's by libm,
+// (cos, sin)(h omega) -- and `seen`, which starts at zero with the sums.  The integrator is about to rewrite the list, the
+// motions and the spins on the device: they are marked dirty here and take_bodies clears the marks, so a step that is not
+// committed -- a failed one -- leaves them for the next step to put the host's untouched copies back.
 static int prepare_bodies(egg_handle *h, double sub_delta) {
     const size_t n = h->colliders.size();
-    int rc = upload_body_records(h);
-    if (rc != EGG_OK) return rc;
+    h->collider_dirty |= kDirtyList | kDirtyMotions | kDirtySpins;
     std::vector<double2> cs(n);
     for (size_t k = 0; k < n; ++k) {
         const double omega = h->spins.empty() ? 0.0 : h->spins[k].omega;
@@ -267,6 +250,10 @@ int prepare_step(egg_handle *h, double delta, int S, RelaxedStep st[2]) {
         if (rc == EGG_OK) rc = upload_atoms(h, w);
         if (rc != EGG_OK) return rc;
     }
+    if (!h->colliders.empty()) {  // the collider tables of the device, before either type's stream has work (no step is running)
+        const int rc = sync_collider_records(h);
+        if (rc != EGG_OK) return rc;
+    }
     if (h->spins_turn && !h->colliders.empty()) {
         // the step's sines and cosines, by the host's libm (the model's): row sub holds (cos, sin)(t omega) with t the end
         // of sub-step sub, row S holds (cos, sin)(h omega); a pair per collider.  No step is running, so nothing reads the
@@ -285,23 +272,12 @@ int prepare_step(egg_handle *h, double delta, int S, RelaxedStep st[2]) {
         HIP_TRY(h, hipMemcpy(h->d_spin_table.p, h->spin_table.data(), h->spin_table.size() * sizeof(double2), hipMemcpyHostToDevice));
     }
     if (h->opt_loads && !h->colliders.empty()) {
-        // the step's sums start at zero, before either type's stream has work (no step is running); the loads kernels read a
-        // surface record per collider and, for the pivots, the spin records: whichever the handle's flavour has not put on
-        // the device yet goes there now
+        // the step's sums start at zero, before either type's stream has work (no step is running)
         const size_t n = h->colliders.size();
         HIP_TRY(h, hipSetDevice(h->device));
         HIP_TRY(h, h->d_loads.reserve(3 * (size_t)EGG_MAX_COLLIDERS + 1, false, nullptr));
         const std::vector<unsigned long long> none(3 * n + 1, 0ull);
         HIP_TRY(h, hipMemcpy(h->d_loads.p, none.data(), none.size() * 8, hipMemcpyHostToDevice));
-        if (!(h->surfaces_grip || h->colliders_wall || h->motions_move || h->spins_turn)) {
-            const std::vector<egg_collider_surface> zeros(n, egg_collider_surface{0.0, 0.0, 0.0});
-            HIP_TRY(h, h->d_surfaces.reserve(EGG_MAX_COLLIDERS, false, nullptr));
-            HIP_TRY(h, hipMemcpy(h->d_surfaces.p, zeros.data(), n * sizeof(egg_collider_surface), hipMemcpyHostToDevice));
-        }
-        if (!h->spins.empty() && !h->spins_turn) {
-            HIP_TRY(h, h->d_spins.reserve(EGG_MAX_COLLIDERS, false, nullptr));
-            HIP_TRY(h, hipMemcpy(h->d_spins.p, h->spins.data(), n * sizeof(egg_collider_spin), hipMemcpyHostToDevice));
-        }
     }
     if (bodies_act(h)) {
         const int rc = prepare_bodies(h, sub_delta);
@@ -380,7 +356,7 @@ int prepare_type(RelaxedStep &st, int C, size_t ghosts, const RelaxedLayout &L, 
         st.lod.moving = st.L.motion ? 1 : 0;
         st.lod.turning = st.L.spin ? 1 : 0;
         st.lod.pivots = h->spins.empty() ? 0 : 1;
-        if (!st.L.surfaces) {  // the default records prepare_step has written; no friction, so no grip is ever counted
+        if (!st.L.surfaces) {  // the records as they are on the device: no friction, so no grip is ever counted
             st.lsrf.list = h->d_surfaces.p;
             st.lsrf.sub_delta = st.env.sub_delta;
             st.lsrf.grips = nullptr;
@@ -968,11 +944,9 @@ static int relaxed_finish(egg_handle *h, RelaxedStep st[2], int S, int C) {
         bad |= bad_cell(st[w]);
     }
     if (bad) {  // nothing is committed: [cur] still holds the state before the step
-        if (h->bodies_step) {  // ... and the records the integrator has rewritten are the host's untouched copies again
-            h->bodies_step = h->contacts_step = false;  // (the fires of the failed step are never read)
-            const int rc = upload_body_records(h);
-            if (rc != EGG_OK) return rc;
-        }
+        // ... and the records the integrator has rewritten stay marked dirty (prepare_bodies): the next step runs on the
+        // host's untouched copies again.  The fires of the failed step are never read.
+        h->bodies_step = h->contacts_step = false;
         h->stats.kernel_launches += st[0].launches + st[1].launches;
         return fail(h, EGG_ERR_UNSUPPORTED, "%s", kRelaxedBadCellText);
     }
@@ -981,11 +955,11 @@ static int relaxed_finish(egg_handle *h, RelaxedStep st[2], int S, int C) {
 }
 
 // Collider motion at the commit: the stored geometry of every collider becomes the geometry of the step's end, t = S h
-// -- the expression the kernels of the last sub-step evaluated, so the same bits -- and the copy on the device follows.
-// No step is running: every path waits for its streams before it commits.
+// -- the expression the kernels of the last sub-step evaluated, so the same bits -- and the list is marked dirty: the copy
+// on the device follows before the next step's first launch (sync_collider_records).
 // Collider spin: a collider whose omega is not zero turns about its pivot, which rides on its motion, by the (c, s) of the
-// last sub-step's row of the step's table, and its stored pivot becomes the pivot of the step's end; the spin records on
-// the device follow.
+// last sub-step's row of the step's table, and its stored pivot becomes the pivot of the step's end; the spin records are
+// marked dirty with the list.
 static void advance_colliders(egg_handle *h, double t, int S) {
     if (h->bodies_step) return;  // (take_bodies has read the device's records, advanced sub-step by sub-step)
     const size_t n = h->colliders.size();
@@ -1026,12 +1000,7 @@ static void advance_colliders(egg_handle *h, double t, int S) {
             }
         }
     }
-    hipError_t e = hipSetDevice(h->device);
-    if (e == hipSuccess)
-        e = hipMemcpy(h->d_colliders.p, h->colliders.data(), h->colliders.size() * sizeof(egg_collider), hipMemcpyHostToDevice);
-    if (e == hipSuccess && h->spins_turn)
-        e = hipMemcpy(h->d_spins.p, h->spins.data(), h->spins.size() * sizeof(egg_collider_spin), hipMemcpyHostToDevice);
-    if (e != hipSuccess) (void)fail(h, EGG_ERR_DEVICE, "relaxed order: the moved colliders did not reach the device: %s", hipGetErrorString(e));
+    h->collider_dirty |= h->spins_turn ? kDirtyList | kDirtySpins : kDirtyList;
 }
 
 // Collider bodies at the commit: the list, the motions and the spins as the integrator of the last sub-step left them on
@@ -1046,6 +1015,7 @@ static void take_bodies(egg_handle *h) {
     if (e == hipSuccess) e = hipMemcpy(h->motions.data(), h->d_motions.p, n * sizeof(egg_collider_motion), hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(h->spins.data(), h->d_spins.p, n * sizeof(egg_collider_spin), hipMemcpyDeviceToHost);
     if (e != hipSuccess) (void)fail(h, EGG_ERR_DEVICE, "relaxed order: the collider bodies did not reach the host: %s", hipGetErrorString(e));
+    else h->collider_dirty &= ~(kDirtyList | kDirtyMotions | kDirtySpins);  // (host and device hold the same records again)
     h->motions_move = h->spins_turn = false;
     for (size_t k = 0; k < n; ++k) {
         h->motions_move |= h->motions[k].vx != 0.0 || h->motions[k].vy != 0.0;

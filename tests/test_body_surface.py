@@ -41,7 +41,7 @@ def test_header_declares_the_entry_points_and_the_struct():
     device_h = _read(CSRC, "eggsim_device.h")
     body = re.search(r"struct EggBody \{([^}]*)\}", device_h).group(1)
     assert re.findall(r"(\w+)[,;]", body) == FIELDS
-    assert "sizeof(egg_collider_body) == 48 && sizeof(EggBody) == sizeof(egg_collider_body)" in _read(CSRC, "eggsim_host_abi.hip")
+    assert "sizeof(egg_collider_body) == 48 && sizeof(EggBody) == sizeof(egg_collider_body)" in _read(CSRC, "eggsim_host_colliders.hip")
     # the definition, where a C caller reads it
     for phrase in ("d = sums[k] - seen[k] (three int64), seen[k] = sums[k]", "Jx = ((double)dx / 2^20) / h", "vx = vx + Jx * inv_mass; vx = vx + h * ax",
                    "f = 1 - h * drag; if (!(f > 0)) f = 0", "u = 0.5 * (h * omega); den = 1 + u * u; c = (1 - u * u) / den; s = (u + u) / den",
@@ -71,20 +71,30 @@ def test_the_kernel_exists_and_only_a_step_with_bodies_launches_it():
     driver = host[host.index("static int relaxed_step_bodies(egg_handle *h, RelaxedStep st[2], int S, int C) {"):host.index("int relaxed_step(egg_handle *h")]
     assert "hipEventDisableTiming" in driver and "hipDeviceSynchronize" not in driver
     assert driver.count("hipStreamSynchronize") == 1  # (only for a handle without particles, after the last launch)
-    # the commit reads the records back in place of advance_colliders; a failed step puts the host's copies back
+    # the commit reads the records back in place of advance_colliders; after a failed step the next one puts the host's
+    # copies back: preparing the step marks the three tables the integrator rewrites, and only take_bodies clears the marks
     commit = host[host.index("void relaxed_commit("):]
     assert "if (h->bodies_step) take_bodies(h);" in commit
     assert "if (h->bodies_step) return;" in host[host.index("static void advance_colliders("):host.index("// Collider bodies at the commit")]
+    prepare = host[host.index("static int prepare_bodies(egg_handle *h"):host.index("// Per step with contacts acting")]
+    assert "h->collider_dirty |= kDirtyList | kDirtyMotions | kDirtySpins;" in prepare
+    assert host.count("h->collider_dirty &= ~") == 1
+    assert "h->collider_dirty &= ~(kDirtyList | kDirtyMotions | kDirtySpins);" in host[host.index("static void take_bodies("):host.index("// Collider contacts at the commit")]
     finish = host[host.index("static int relaxed_finish(egg_handle *h, RelaxedStep st[2], int S, int C) {"):host.index("static void advance_colliders(")]
-    assert "upload_body_records(h)" in finish
+    assert "collider_dirty" not in finish and "hipMemcpy" not in finish
+    step = host[host.index("int prepare_step(egg_handle *h"):host.index("int prepare_type(RelaxedStep &st")]
+    assert step.index("sync_collider_records(h)") < step.index("prepare_bodies(h, sub_delta)")
     assert "st.L.loads = st.L.colliders && h->opt_loads;" in host  # (how loads are derived has not changed)
 
 
 def test_the_refusals_stand_in_the_sources():
-    abi = _read(CSRC, "eggsim_host_abi.hip")
+    abi = _read(CSRC, "eggsim_host_colliders.hip")
     setter = abi[abi.index("int egg_set_collider_bodies("):abi.index("int egg_get_collider_bodies(")]
-    assert 'REJECT_IN_FLIGHT(h, "egg_set_collider_bodies");' in setter
-    assert setter.index("h->bodies.swap(list);") > max(setter.index(m) for m in ("is negative or not finite", "is not finite", "n = %d without records"))
+    # the in-flight refusal and the "n = %d without records" check stand in the preface every setter of records opens with
+    preface = abi[abi.index("int check_records(egg_handle *h, const char *name"):abi.index("// The getters' answer")]
+    assert "REJECT_IN_FLIGHT(h, name);" in preface and '"%s: n = %d without records", name' in preface
+    assert 'check_records(h, "egg_set_collider_bodies", n, b);\n    if (rc != EGG_OK) return rc;' in setter
+    assert setter.index("h->bodies.swap(list);") > max(setter.index(m) for m in ("is negative or not finite", "is not finite", "check_records("))
     assert setter.count("collider %d:") == 5 and "o.inv_mass = o.inv_mass + 0.0;" in setter
     assert "hipMemcpy" not in setter  # (a step in which bodies act uploads what it runs on)
     lists = abi[abi.index("int egg_set_colliders("):abi.index("int egg_get_colliders(")]

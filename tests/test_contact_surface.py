@@ -40,7 +40,7 @@ def test_header_declares_the_entry_points_and_the_struct():
     device_h = _read(CSRC, "eggsim_device.h")
     record = re.search(r"struct EggContact \{([^}]*)\}", device_h).group(1)
     assert re.findall(r"(\w+)[,;]", record) == ["restitution", "on", "reserved"]
-    assert "sizeof(egg_collider_contact) == 16 && sizeof(EggContact) == sizeof(egg_collider_contact)" in _read(CSRC, "eggsim_host_abi.hip")
+    assert "sizeof(egg_collider_contact) == 16 && sizeof(EggContact) == sizeof(egg_collider_contact)" in _read(CSRC, "eggsim_host_colliders.hip")
     # the rule, its place in the sub-step and the limits, where a C caller reads them
     for phrase in ("behind step 4 of collider bodies", "exactly when bodies act (above) and some record is on",
                    "launches exactly the kernels it launches today, with the same arguments", "((ma + ia) + mb) + ib > 0",
@@ -86,17 +86,21 @@ def test_the_kernel_exists_and_only_a_step_with_contacts_launches_it():
 
 
 def test_the_refusals_stand_in_the_sources():
-    abi = _read(CSRC, "eggsim_host_abi.hip")
+    abi = _read(CSRC, "eggsim_host_colliders.hip")
     setter = abi[abi.index("int egg_set_collider_contacts("):abi.index("int egg_get_collider_contacts(")]
-    assert 'REJECT_IN_FLIGHT(h, "egg_set_collider_contacts");' in setter
+    # the in-flight refusal and the "n = %d without records" check stand in the preface every setter of records opens with
+    preface = abi[abi.index("int check_records(egg_handle *h, const char *name"):abi.index("// The getters' answer")]
+    assert "REJECT_IN_FLIGHT(h, name);" in preface and '"%s: n = %d without records", name' in preface
+    assert 'check_records(h, "egg_set_collider_contacts", n, c);\n    if (rc != EGG_OK) return rc;' in setter
     assert setter.index("h->contacts.swap(list);") > max(setter.index(m) for m in ("lies outside [0, 1]", "is not 0 or 1", "reserved = %d is not 0",
-                                                                                      "n = %d without records", "iterations (1 .. 16", "need relaxed order"))
+                                                                                      "check_records(", "iterations (1 .. 16", "need relaxed order"))
     assert "EGG_ERR_UNSUPPORTED" in setter and "iterations == 0 ? 4 : iterations" in setter
     assert "hipMemcpy" not in setter  # (a step in which contacts act uploads what it runs on)
     lists = abi[abi.index("int egg_set_colliders("):abi.index("int egg_get_colliders(")]
     assert "h->contacts.clear();" in lists and "h->contacts_any = false;" in lists
     assert lists.index("h->bodies.clear();") < lists.index("h->contacts.clear();")
-    order = abi[abi.index("case EGG_OPT_SOLVER_ORDER:"):abi.index("case EGG_OPT_RELAXATION:")]
+    core = _read(CSRC, "eggsim_host_abi.hip")
+    order = core[core.index("case EGG_OPT_SOLVER_ORDER:"):core.index("case EGG_OPT_RELAXATION:")]
     assert "value == EGG_SOLVER_EXACT && h->contacts_any" in order and "exact order has no collider contacts" in order
     for name in ("egg_set_collider_motion", "egg_set_collider_spin", "egg_set_collider_surfaces", "egg_set_collider_bodies"):  # these leave the records alone
         other = abi[abi.index("int %s(" % name):]

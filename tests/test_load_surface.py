@@ -54,7 +54,7 @@ def test_header_declares_the_entry_points_the_scales_and_the_struct():
     assert "#define EGG_RX_LOAD_SCALE_IMPULSE 0x1p20" in device_h and "#define EGG_RX_LOAD_SCALE_TORQUE 0x1p10" in device_h
     assert "#define EGG_RX_LOAD_LIMIT 0x1p53" in device_h
     assert "EGG_COLLIDER_LOAD_IMPULSE_SCALE == EGG_RX_LOAD_SCALE_IMPULSE && EGG_COLLIDER_LOAD_TORQUE_SCALE == EGG_RX_LOAD_SCALE_TORQUE" in \
-        _read(CSRC, "eggsim_host_abi.hip")
+        _read(CSRC, "eggsim_host_colliders.hip")
     fields = re.search(r"struct EggRxLoadFields \{([^}]*)\}", device_h).group(1)
     assert re.findall(r"(\w+);", re.sub(r"//[^\n]*", "", fields)) == ["sums", "dropped", "eps", "moving", "turning", "pivots"]
     for args in KERNELS.values():  # everything a spin twin takes, and the load fields
@@ -94,7 +94,7 @@ def test_the_kernels_exist_and_only_a_step_with_loads_launches_them():
 
 
 def test_the_refusals_stand_in_the_sources():
-    abi = _read(CSRC, "eggsim_host_abi.hip")
+    abi = _read(CSRC, "eggsim_host_colliders.hip")
     setter = abi[abi.index("int egg_set_collider_loads("):abi.index("int egg_get_collider_loads_enabled(")]
     assert 'REJECT_IN_FLIGHT(h, "egg_set_collider_loads");' in setter
     assert "opt_solver_order" not in setter and "colliders.empty()" not in setter  # (either order, any list: it only observes)
