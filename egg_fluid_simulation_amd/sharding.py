@@ -607,6 +607,32 @@ class ShardedSimulationHandler(_HandlerSurface):
     def get_cohesion(self):
         return getattr(self, "_cohesion", "reference")
 
+    # ------------------------------------------------ what the reads below share
+    def _all_reduce_sum(self, values):
+        """`values`, a list or numpy array of integers, added over the ranks: the same shape as int64 after ONE all_reduce(SUM)
+        of an int64 tensor on self.device (a collective: every rank calls it with the same shape).  Integer addition has no
+        order, so the sum equals one handle's bit for bit.  A one-rank object gets its own values back and needs no process
+        group; nothing travels for an empty table either."""
+        values = np.ascontiguousarray(values, dtype=np.int64)
+        if self.world == 1 or values.size == 0:
+            return values
+        tot = self.torch.from_numpy(values).to(self.device)
+        self.dist.all_reduce(tot, op=self.dist.ReduceOp.SUM)
+        return tot.cpu().numpy()
+
+    def _owner_table(self, ids, unknown, shape, rows):
+        """an int64 table [len(ids)] + shape over all ranks: every global id of `ids` is checked against the owners (the
+        EggError text is `unknown` % the id, raised on every rank before anything travels), the rows of the batches this rank
+        holds come from `rows(their local ids)` -- called on every rank, with an empty list where it holds none --, the others
+        stay zero, and _all_reduce_sum adds the ranks"""
+        for gid in ids:
+            if gid not in self.owner:
+                raise EggError(unknown % gid)
+        table = np.zeros((len(ids),) + tuple(shape), dtype=np.int64)
+        mine = [k for k, gid in enumerate(ids) if gid in self.local_id]
+        table[mine] = rows([self.local_id[ids[k]] for k in mine])
+        return self._all_reduce_sum(table)
+
     def set_colliders(self, colliders):
         """SimulationHandler.set_colliders on every rank alike (the same call on every rank; relaxed order only).  Nothing
         new travels: every rank projects the particles it owns, before their positions go out as ghosts."""
@@ -617,9 +643,7 @@ class ShardedSimulationHandler(_HandlerSurface):
 
     def collider_hits(self):
         """SimulationHandler.collider_hits summed over the ranks (a collective: every rank calls it)"""
-        tot = self.torch.tensor(self.local.collider_hits(), dtype=self.torch.int64, device=self.device)
-        self.dist.all_reduce(tot, op=self.dist.ReduceOp.SUM)
-        return [int(v) for v in tot.tolist()]
+        return self._all_reduce_sum(self.local.collider_hits()).tolist()
 
     def set_collider_surfaces(self, surfaces):
         """SimulationHandler.set_collider_surfaces on every rank alike (the same call on every rank).  Nothing new travels:
@@ -631,9 +655,7 @@ class ShardedSimulationHandler(_HandlerSurface):
 
     def collider_grips(self):
         """SimulationHandler.collider_grips summed over the ranks (a collective: every rank calls it)"""
-        tot = self.torch.tensor(self.local.collider_grips(), dtype=self.torch.int64, device=self.device)
-        self.dist.all_reduce(tot, op=self.dist.ReduceOp.SUM)
-        return [int(v) for v in tot.tolist()]
+        return self._all_reduce_sum(self.local.collider_grips()).tolist()
 
     def set_collider_motion(self, motions):
         """SimulationHandler.set_collider_motion on every rank alike (the same call on every rank).  Nothing new travels:
@@ -676,10 +698,7 @@ class ShardedSimulationHandler(_HandlerSurface):
         """SimulationHandler.collider_load_sums with the int64 sums and the dropped count added over the ranks (a collective:
         every rank calls it).  Integer addition has no order, so the result equals one handle's bit for bit."""
         sums, dropped, h = self.local.collider_load_sums()
-        flat = [v for t in sums for v in t] + [dropped]
-        tot = self.torch.tensor(flat, dtype=self.torch.int64, device=self.device)
-        self.dist.all_reduce(tot, op=self.dist.ReduceOp.SUM)
-        flat = [int(v) for v in tot.tolist()]
+        flat = self._all_reduce_sum([v for t in sums for v in t] + [dropped]).tolist()
         return [tuple(flat[3 * k:3 * k + 3]) for k in range(len(sums))], flat[-1], h
 
     def collider_loads(self):
@@ -704,10 +723,7 @@ class ShardedSimulationHandler(_HandlerSurface):
         rank calls it; one all_reduce of an int64 tensor).  Integer addition has no order, so the result equals one
         handle's bit for bit."""
         sums, dropped = self.local.sensor_sums()
-        flat = [v for per_type in sums for rec in per_type for v in rec] + list(dropped)
-        tot = self.torch.tensor(flat, dtype=self.torch.int64, device=self.device)
-        self.dist.all_reduce(tot, op=self.dist.ReduceOp.SUM)
-        flat = [int(v) for v in tot.tolist()]
+        flat = self._all_reduce_sum([v for per_type in sums for rec in per_type for v in rec] + list(dropped)).tolist()
         return [(tuple(flat[6 * k:6 * k + 3]), tuple(flat[6 * k + 3:6 * k + 6])) for k in range(len(sums))], flat[-2:]
 
     def sensors(self):
@@ -718,18 +734,10 @@ class ShardedSimulationHandler(_HandlerSurface):
     def sensor_batches(self, ids):
         """SimulationHandler.sensor_batches over all ranks (a collective: every rank calls it with the same ids): every rank
         fills in the batches it holds and zeros elsewhere, one all_reduce of an int64 tensor adds them"""
-        ids = [int(i) for i in ids]
-        for gid in ids:
-            if gid not in self.owner:
-                raise EggError("[ERROR] In SimulationHandler.sensor_batches: no batch with id `%d`" % gid)
         n_sensors = len(self.local.get_sensors())
-        out = np.zeros((len(ids), n_sensors, 2), dtype=np.int64)
-        mine = [k for k, gid in enumerate(ids) if gid in self.local_id]
-        if mine and n_sensors:
-            out[mine] = self.local.sensor_batches([self.local_id[ids[k]] for k in mine])
-        tot = self.torch.from_numpy(out).to(self.device)
-        self.dist.all_reduce(tot, op=self.dist.ReduceOp.SUM)
-        return tot.cpu().numpy().astype(np.int32)
+        table = self._owner_table([int(i) for i in ids], "[ERROR] In SimulationHandler.sensor_batches: no batch with id `%d`", (n_sensors, 2),
+                                  lambda lids: self.local.sensor_batches(lids) if lids and n_sensors else 0)
+        return table.astype(np.int32)
 
     def probe(self, probes):
         """SimulationHandler.probe over all ranks (a collective: every rank calls it with the same list).  Every rank asks its
@@ -777,14 +785,10 @@ class ShardedSimulationHandler(_HandlerSurface):
         flat = np.array(list(t.inside) + list(t.outside) + list(t.dropped) + [t.units_tiled, t.units_direct], dtype=np.int64)
         planes = []
         for plane in (count, svx, svy, flat):
-            if plane is not None and self.world > 1:
-                tot = self.torch.from_numpy(plane).to(self.device)
-                self.dist.all_reduce(tot, op=self.dist.ReduceOp.SUM)
-                plane = tot.cpu().numpy()
-            planes.append(plane)
+            planes.append(None if plane is None else self._all_reduce_sum(plane))
         count, svx, svy, flat = planes
-        flat = [int(v) for v in flat]
-        return Field(count, svx, svy, tuple(flat[0:2]), tuple(flat[2:4]), tuple(flat[4:6]), flat[6], flat[7])
+        flat = flat.tolist()
+        return Field(count.astype(np.int32), svx, svy, tuple(flat[0:2]), tuple(flat[2:4]), tuple(flat[4:6]), flat[6], flat[7])
 
     def pieces(self, ids=None, reach=None, types="both"):
         """SimulationHandler.pieces over all ranks (a collective: every rank calls it with the same arguments).  A batch lives
@@ -793,17 +797,8 @@ class ShardedSimulationHandler(_HandlerSurface):
         piece_labels here: the particles of the ranks live in different arrays."""
         spec = self._c_pieces_spec(reach, types)
         ids = self.list_ids() if ids is None else [int(i) for i in ids]
-        for gid in ids:
-            if gid not in self.owner:
-                raise EggError("[ERROR] In SimulationHandler.pieces: no batch with id `%d`" % gid)
-        table = np.zeros((len(ids), 2, 8), dtype=np.int64)
-        mine = [k for k, gid in enumerate(ids) if gid in self.local_id]
-        if mine:
-            table[mine] = self.local._piece_table(spec, np.ascontiguousarray([self.local_id[ids[k]] for k in mine], dtype=np.int64))
-        if self.world > 1 and ids:
-            tot = self.torch.from_numpy(table).to(self.device)
-            self.dist.all_reduce(tot, op=self.dist.ReduceOp.SUM)
-            table = tot.cpu().numpy()
+        table = self._owner_table(ids, "[ERROR] In SimulationHandler.pieces: no batch with id `%d`", (2, 8),
+                                  lambda lids: self.local._piece_table(spec, np.ascontiguousarray(lids, dtype=np.int64)))
         return self._piece_summaries(table)
 
     def impulse(self, records, results=True):
@@ -823,13 +818,7 @@ class ShardedSimulationHandler(_HandlerSurface):
         for k, gid in enumerate(gids):
             arr[k].id = gid if gid in (_ffi.IMPULSE_ALL_BATCHES, _ffi.IMPULSE_NO_BATCH) else self.local_id.get(gid, _ffi.IMPULSE_NO_BATCH)
         table = self.local._impulse_table(n, arr, bool(results))
-        if table is None:
-            return None
-        if self.world > 1 and n:
-            tot = self.torch.from_numpy(table).to(self.device)
-            self.dist.all_reduce(tot, op=self.dist.ReduceOp.SUM)
-            table = tot.cpu().numpy()
-        return self._impulse_results(table)
+        return None if table is None else self._impulse_results(self._all_reduce_sum(table))
 
     def measure_table(self, ids=None, region=None, types="both"):
         """SimulationHandler.measure_table over all ranks (a collective: every rank calls it with the same arguments).  A
@@ -837,20 +826,12 @@ class ShardedSimulationHandler(_HandlerSurface):
         all_reduce(SUM) of the int64 table adds them, so the table equals one handle's bit for bit.  Nothing travels in a
         step.  There is no measure_to here: the tables of the ranks live on different devices."""
         spec = self._c_measure_spec(region, types, "measure_table")
+
+        def rows(lids):
+            self.local._measure_check(spec)  # (the same verdict on every rank, whatever it owns)
+            return self.local._measure_table(spec, np.ascontiguousarray(lids, dtype=np.int64)) if lids else 0
         ids = self.list_ids() if ids is None else [int(i) for i in ids]
-        for gid in ids:
-            if gid not in self.owner:
-                raise EggError("[ERROR] In SimulationHandler.measure: no batch with id `%d`" % gid)
-        self.local._measure_check(spec)  # (the same verdict on every rank, whatever it owns)
-        table = np.zeros((len(ids), 2, len(_ffi.MEASURE_FIELDS)), dtype=np.int64)
-        mine = [k for k, gid in enumerate(ids) if gid in self.local_id]
-        if mine:
-            table[mine] = self.local._measure_table(spec, np.ascontiguousarray([self.local_id[ids[k]] for k in mine], dtype=np.int64))
-        if self.world > 1 and ids:
-            tot = self.torch.from_numpy(table).to(self.device)
-            self.dist.all_reduce(tot, op=self.dist.ReduceOp.SUM)
-            table = tot.cpu().numpy()
-        return table
+        return self._owner_table(ids, "[ERROR] In SimulationHandler.measure: no batch with id `%d`", (2, len(_ffi.MEASURE_FIELDS)), rows)
 
     def set_forces(self, forces):
         """SimulationHandler.set_forces on every rank alike (the same call on every rank; relaxed order only).  Nothing
@@ -872,11 +853,7 @@ class ShardedSimulationHandler(_HandlerSurface):
 
     def viscosity_pairs(self):
         """SimulationHandler.viscosity_pairs summed over the ranks (a collective: every rank calls it)"""
-        if self.world == 1:
-            return self.local.viscosity_pairs()
-        tot = self.torch.tensor(self.local.viscosity_pairs(), dtype=self.torch.int64, device=self.device)
-        self.dist.all_reduce(tot, op=self.dist.ReduceOp.SUM)
-        return [int(v) for v in tot.tolist()]
+        return self._all_reduce_sum(self.local.viscosity_pairs()).tolist()
 
     def set_containment(self, factor=0.0, strength=1.0):
         """SimulationHandler.set_containment on every rank alike (the same call on every rank; relaxed order only).
@@ -888,11 +865,7 @@ class ShardedSimulationHandler(_HandlerSurface):
 
     def containment_hits(self):
         """SimulationHandler.containment_hits summed over the ranks (a collective: every rank calls it)"""
-        if self.world == 1:
-            return self.local.containment_hits()
-        tot = self.torch.tensor([self.local.containment_hits()], dtype=self.torch.int64, device=self.device)
-        self.dist.all_reduce(tot, op=self.dist.ReduceOp.SUM)
-        return int(tot.tolist()[0])
+        return int(self._all_reduce_sum([self.local.containment_hits()])[0])
 
     def _viscous(self):
         """the coefficients the local handle holds: what the library decides a step's pass sequence from"""

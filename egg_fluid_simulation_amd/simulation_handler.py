@@ -228,6 +228,35 @@ _SOLVER_KEYS = ["damping", "follow_strength", "cohesion_strength", "cohesion_int
                 "collision_strength", "collision_overlap_factor", "min_mass", "max_mass", "min_radius",
                 "max_radius"]
 
+# What differs between the three tagged kind lists (set_colliders, set_sensors, set_forces), as data for _c_kind_list and
+# _kind_tuples.  `word` names a record in the messages; `codes` kind -> code, `names` code -> kind, `params` code -> parameter
+# names and `types` name -> type_mask are the tables of _ffi; `limit` the most records a list holds, where the host checks it;
+# `loose_types`: the last string of a tuple is its types whatever the tuple's length (else only where the tuple is one value
+# too long for its kind); `alt` code -> (other parameter names, their conversion to the stored ones).
+_KindList = collections.namedtuple("_KindList", "word struct codes names params types limit loose_types alt")
+_COLLIDER_LIST = _KindList("collider", _ffi.EggCollider, _ffi.COLLIDER_CODES, _ffi.COLLIDER_NAMES, _ffi.COLLIDER_PARAM_NAMES,
+                           _ffi.COLLIDER_TYPES, None, False, {})
+_SENSOR_LIST = _KindList("sensor", _ffi.EggSensor, _ffi.SENSOR_CODES, _ffi.SENSOR_KINDS, _ffi.SENSOR_PARAMS, _ffi.SENSOR_TYPES,
+                         _ffi.MAX_SENSORS, True,
+                         {_ffi.SENSOR_BOX: (("cx", "cy", "hx", "hy", "angle"), lambda v: v[:4] + [math.cos(v[4]), math.sin(v[4])])})
+_FORCE_LIST = _KindList("field", _ffi.EggForce, {n: i for i, n in enumerate(_ffi.FORCE_KINDS)}, _ffi.FORCE_KINDS, _ffi.FORCE_PARAMS,
+                        _ffi.FORCE_TYPES, None, False, {})
+
+# A record of fixed shape per collider, as data for _c_records and _get_records.  `what` names it in the messages and `form` is
+# what they say was expected; `lengths` the accepted lengths, a shorter one padded with zeros (None is the first length of
+# zeros); `number`: a bare number is the first field; `checks`, in order, (field indices, the text where one of them is not
+# finite, the text where one is negative or None where that is allowed), each text formatted with the fields' values.
+_Record = collections.namedtuple("_Record", "what form struct fields lengths number checks")
+_SURFACE = _Record("collider surface", "None, a number mu or (mu, vx, vy)", _ffi.EggColliderSurface, ("friction", "vx", "vy"), (3,), True, ())
+_MOTION = _Record("collider motion", "None or (vx, vy)", _ffi.EggColliderMotion, ("vx", "vy"), (2,), False,
+                  (((0, 1), "the velocity (%r, %r) is not finite", None),))
+_SPIN = _Record("collider spin", "None or (px, py, omega)", _ffi.EggColliderSpin, ("px", "py", "omega"), (3,), False,
+                (((0, 1), "the pivot (%r, %r) is not finite", None), ((2,), "omega %r is not finite", None)))
+_BODY = _Record("collider body", "None or (inv_mass, inv_inertia[, ax, ay[, drag, spin_drag]])", _ffi.EggColliderBody,
+                ("inv_mass", "inv_inertia", "ax", "ay", "drag", "spin_drag"), (2, 4, 6), False,
+                tuple(((q,), name + " %r is not finite", None if name in ("ax", "ay") else name + " %r is negative")
+                      for q, name in enumerate(("inv_mass", "inv_inertia", "ax", "ay", "drag", "spin_drag"))))
+
 
 class _HandlerSurface:
     """The part of the reference's class that SimulationHandler (one device handle, `egg_*`) and SimulationGroup (a device
@@ -243,45 +272,141 @@ class _HandlerSurface:
         """the C entry point `name` of this object's kind, bound to its handle"""
         return functools.partial(getattr(self._lib, self._PREFIX + name), self._ptr())
 
-    # ------------------------------------------------ static colliders (egg_set_colliders, DESIGN.md section 2.7)
+    # ------------------------------------------------ what the setters and getters below share
     @staticmethod
-    def _c_colliders(colliders):
-        """a list of tuples `(kind, a, b, c[, d][, types])` or dicts `{"kind": ..., <parameter names>, "types": ...}` as an
-        egg_collider array; what only the host can check (shape, names) is checked here, the values by the library"""
-        colliders = list(colliders)
-        arr = (_ffi.EggCollider * max(len(colliders), 1))()
-        for k, c in enumerate(colliders):
+    def _c_kind_list(kl, items):
+        """a list of tuples `(kind, parameters...[, types])` or dicts `{"kind": ..., <parameter names>, "types": ...}` as an array
+        of `kl.struct` (kind, type_mask, p[]); what only the host can check (shape, names) is checked here, the values by the
+        library"""
+        items = list(items)
+        if kl.limit is not None and len(items) > kl.limit:
+            raise EggError("%ss: a list holds 0 .. %d %ss, not %d" % (kl.word, kl.limit, kl.word, len(items)))
+        arr = (kl.struct * max(len(items), 1))()
+        word, codes, params, masks, alt, loose = kl.word, kl.codes, kl.params, kl.types, kl.alt, kl.loose_types
+        for k, c in enumerate(items):
             if isinstance(c, dict):
                 kind, types = c.get("kind"), c.get("types", "both")
             else:
                 c = tuple(c)
                 kind = c[0] if c else None
                 types = "both"
-            if not isinstance(kind, str) or kind not in _ffi.COLLIDER_CODES:
-                raise EggError("collider %d: kind must be one of %s, not %r" % (k, ", ".join(_ffi.COLLIDER_CODES), kind))
-            code = _ffi.COLLIDER_CODES[kind]
-            names = _ffi.COLLIDER_PARAM_NAMES[code]
+            if not isinstance(kind, str) or kind not in codes:
+                raise EggError("%s %d: kind must be one of %s, not %r" % (word, k, ", ".join(codes), kind))
+            code = codes[kind]
+            names, other = params[code], alt.get(code)
             if isinstance(c, dict):
-                extra = set(c) - set(names) - {"kind", "types"}
-                if extra or not all(n in c for n in names):
-                    raise EggError("collider %d (%s): expected the keys %s" % (k, kind, ", ".join(names)))
+                given = set(c) - {"kind", "types"}
+                if other is not None and given == set(other[0]):
+                    names = other[0]
+                if given != set(names):
+                    raise EggError("%s %d (%s): expected the keys %s" % (word, k, kind, ", ".join(names)))
                 values = [c[n] for n in names]
             else:
                 values = list(c[1:])
-                if len(values) == len(names) + 1 and isinstance(values[-1], str):
+                if values and isinstance(values[-1], str) and (loose or len(values) == len(names) + 1):
                     types = values.pop()
+                if other is not None and len(values) == len(other[0]):
+                    names = other[0]
                 if len(values) != len(names):
-                    raise EggError("collider %d (%s): expected (%r, %s[, types])" % (k, kind, kind, ", ".join(names)))
-            if not isinstance(types, str) or types not in _ffi.COLLIDER_TYPES:
-                raise EggError("collider %d: types must be 'both', 'white' or 'yolk', not %r" % (k, types))
+                    raise EggError("%s %d (%s): expected (%r, %s[, types])" % (word, k, kind, kind, ", ".join(names)))
+            if not isinstance(types, str) or types not in masks:
+                raise EggError("%s %d: types must be 'both', 'white' or 'yolk', not %r" % (word, k, types))
             try:
                 values = [float(v) for v in values]
             except (TypeError, ValueError):
-                raise EggError("collider %d (%s): the parameters must be numbers" % (k, kind)) from None
-            arr[k].kind, arr[k].type_mask = code, _ffi.COLLIDER_TYPES[types]
+                raise EggError("%s %d (%s): the parameters must be numbers" % (word, k, kind)) from None
+            if other is not None and names is other[0]:
+                values = other[1](values)
+            arr[k].kind, arr[k].type_mask = code, masks[types]
             for q, v in enumerate(values):
                 arr[k].p[q] = v
-        return len(colliders), arr
+        return len(items), arr
+
+    @staticmethod
+    def _kind_tuples(kl, records):
+        """_c_kind_list backwards: the records as tuples `(kind, parameters..., types)`"""
+        types = {v: k for k, v in kl.types.items()}
+        return [(kl.names[c.kind],) + tuple(c.p[:len(kl.params[c.kind])]) + (types[c.type_mask],) for c in records]
+
+    @staticmethod
+    def _c_records(rec, items):
+        """a list with one element per collider -- None, a tuple of one of `rec.lengths` or, with `rec.number`, a number -- as
+        an array of `rec.struct`; shape, finiteness and signs are checked here, before any call into the library"""
+        items = list(items)
+        arr = (rec.struct * max(len(items), 1))()
+        for k, v in enumerate(items):
+            if v is None:
+                v = (0.0,) * rec.lengths[0]
+            elif rec.number and isinstance(v, (int, float)):
+                v = (v,) + (0.0,) * (len(rec.fields) - 1)
+            try:
+                v = tuple(float(x) for x in v)
+            except (TypeError, ValueError):
+                raise EggError("%s %d: expected %s, not %r" % (rec.what, k, rec.form, v)) from None
+            if len(v) not in rec.lengths:
+                raise EggError("%s %d: expected %s, not %r" % (rec.what, k, rec.form, v))
+            v += (0.0,) * (len(rec.fields) - len(v))
+            for at, not_finite, negative in rec.checks:
+                part = tuple(v[q] for q in at)
+                if not all(math.isfinite(x) for x in part):
+                    raise EggError("%s %d: %s" % (rec.what, k, not_finite % part))
+                if negative is not None and any(x < 0.0 for x in part):
+                    raise EggError("%s %d: %s" % (rec.what, k, negative % part))
+            for name, x in zip(rec.fields, v):
+                setattr(arr[k], name, x)
+        return len(items), arr
+
+    def _get_array(self, call, struct, cap):
+        """the records an entry point `call(cap, array, &n)` of this object stores"""
+        arr = (struct * cap)()
+        n = C.c_int32()
+        self._check(call(cap, arr, C.byref(n)))
+        return arr[:n.value]
+
+    def _get_records(self, call, struct, fields):
+        """one tuple of `fields` per collider from `call`"""
+        return [tuple(getattr(r, f) for f in fields) for r in self._get_array(call, struct, _ffi.MAX_COLLIDERS)]
+
+    @staticmethod
+    def _c_range_pair(what, first, a, strength):
+        """(factor | reach, strength) as the two doubles a setter of `what` takes; the ranges are checked here as the library
+        checks them"""
+        out = []
+        for name, v in ((first, a), ("strength", strength)):
+            try:
+                out.append(float(v))
+            except (TypeError, ValueError):
+                raise EggError("%s: the %s must be a number, not %r" % (what, name, v)) from None
+        if not (0.0 <= out[0] < float("inf")):  # (false for a NaN)
+            raise EggError("%s: the %s %r is not a finite number >= 0" % (what, first, out[0]))
+        if not (0.0 <= out[1] <= 1.0):
+            raise EggError("%s: the strength %r lies outside [0, 1]" % (what, out[1]))
+        return out[0], out[1]
+
+    def _get_pair(self, call):
+        """the two doubles `call(&a, &b)` stores"""
+        a, b = C.c_double(), C.c_double()
+        self._check(call(C.byref(a), C.byref(b)))
+        return (a.value, b.value)
+
+    def _get_count(self, call):
+        """the int64 counter `call(&n)` stores"""
+        n = C.c_int64()
+        self._check(call(C.byref(n)))
+        return int(n.value)
+
+    def _get_counts(self, call):
+        """the int64[2] counters, [white, yolk], that `call(v)` fills"""
+        v = (C.c_int64 * 2)()
+        self._check(call(v))
+        return list(v)
+
+    # ------------------------------------------------ static colliders (egg_set_colliders, DESIGN.md section 2.7)
+    @staticmethod
+    def _c_colliders(colliders):
+        """a list of tuples `(kind, a, b, c[, d][, types])` or dicts `{"kind": ..., <parameter names>, "types": ...}` as an
+        egg_collider array; what only the host can check (shape, names) is checked here, the values by the library"""
+        return _HandlerSurface._c_kind_list(_COLLIDER_LIST, colliders)
 
     def set_colliders(self, colliders):
         """The ordered list of static colliders, at most 64 ("Colliders"; relaxed order only):
@@ -299,39 +424,18 @@ class _HandlerSurface:
 
     def get_colliders(self):
         """the list as stored, as tuples `(kind, parameters..., types)`: a half-plane's normal comes back normalised"""
-        arr = (_ffi.EggCollider * _ffi.MAX_COLLIDERS)()
-        n = C.c_int32()
-        self._check(self._c("get_colliders")(_ffi.MAX_COLLIDERS, arr, C.byref(n)))
-        types = {v: k for k, v in _ffi.COLLIDER_TYPES.items()}
-        return [(_ffi.COLLIDER_NAMES[c.kind],) + tuple(c.p[:len(_ffi.COLLIDER_PARAM_NAMES[c.kind])]) + (types[c.type_mask],)
-                for c in arr[:n.value]]
+        return self._kind_tuples(_COLLIDER_LIST, self._get_array(self._c("get_colliders"), _ffi.EggCollider, _ffi.MAX_COLLIDERS))
 
     def collider_hits(self):
         """[white, yolk]: how often a collider moved a particle in a pass of a committed step, since creation"""
-        hits = (C.c_int64 * 2)()
-        self._check(self._c("get_collider_hits")(hits))
-        return list(hits)
+        return self._get_counts(self._c("get_collider_hits"))
 
     # ------------------------------------------------ collider surfaces (egg_set_collider_surfaces, DESIGN.md section 2.7)
     @staticmethod
     def _c_surfaces(surfaces):
         """a list with one element per collider -- None (the default surface), a number mu, or (mu, vx, vy) -- as an
         egg_collider_surface array; the shape is checked here, the values by the library"""
-        surfaces = list(surfaces)
-        arr = (_ffi.EggColliderSurface * max(len(surfaces), 1))()
-        for k, sf in enumerate(surfaces):
-            if sf is None:
-                sf = (0.0, 0.0, 0.0)
-            elif isinstance(sf, (int, float)):
-                sf = (sf, 0.0, 0.0)
-            try:
-                sf = tuple(float(v) for v in sf)
-            except (TypeError, ValueError):
-                raise EggError("collider surface %d: expected None, a number mu or (mu, vx, vy), not %r" % (k, sf)) from None
-            if len(sf) != 3:
-                raise EggError("collider surface %d: expected None, a number mu or (mu, vx, vy), not %r" % (k, sf))
-            arr[k].friction, arr[k].vx, arr[k].vy = sf
-        return len(surfaces), arr
+        return _HandlerSurface._c_records(_SURFACE, surfaces)
 
     def set_collider_surfaces(self, surfaces):
         """One surface per collider of the current list ("Collider surfaces"): `None` for the default,
@@ -346,37 +450,18 @@ class _HandlerSurface:
 
     def get_collider_surfaces(self):
         """the surfaces as stored, one `(mu, vx, vy)` per collider (defaults included)"""
-        arr = (_ffi.EggColliderSurface * _ffi.MAX_COLLIDERS)()
-        n = C.c_int32()
-        self._check(self._c("get_collider_surfaces")(_ffi.MAX_COLLIDERS, arr, C.byref(n)))
-        return [(sf.friction, sf.vx, sf.vy) for sf in arr[:n.value]]
+        return self._get_records(self._c("get_collider_surfaces"), _SURFACE.struct, _SURFACE.fields)
 
     def collider_grips(self):
         """[white, yolk]: friction applications (stick or slide) in the passes of committed steps, since creation"""
-        grips = (C.c_int64 * 2)()
-        self._check(self._c("get_collider_grips")(grips))
-        return list(grips)
+        return self._get_counts(self._c("get_collider_grips"))
 
     # ------------------------------------------------ collider motion (egg_set_collider_motion, DESIGN.md section 2.7)
     @staticmethod
     def _c_motions(motions):
         """a list with one element per collider -- None (at rest) or (vx, vy) -- as an egg_collider_motion array; shape and
         finiteness are checked here, before any call into the library"""
-        motions = list(motions)
-        arr = (_ffi.EggColliderMotion * max(len(motions), 1))()
-        for k, mo in enumerate(motions):
-            if mo is None:
-                mo = (0.0, 0.0)
-            try:
-                mo = tuple(float(v) for v in mo)
-            except (TypeError, ValueError):
-                raise EggError("collider motion %d: expected None or (vx, vy), not %r" % (k, mo)) from None
-            if len(mo) != 2:
-                raise EggError("collider motion %d: expected None or (vx, vy), not %r" % (k, mo))
-            if not (math.isfinite(mo[0]) and math.isfinite(mo[1])):
-                raise EggError("collider motion %d: the velocity (%r, %r) is not finite" % (k, mo[0], mo[1]))
-            arr[k].vx, arr[k].vy = mo
-        return len(motions), arr
+        return _HandlerSurface._c_records(_MOTION, motions)
 
     def set_collider_motion(self, motions):
         """One motion per collider of the current list ("Collider motion"): `None` for a collider at
@@ -391,33 +476,14 @@ class _HandlerSurface:
 
     def get_collider_motion(self):
         """the motions as stored, one `(vx, vy)` per collider (zeros included)"""
-        arr = (_ffi.EggColliderMotion * _ffi.MAX_COLLIDERS)()
-        n = C.c_int32()
-        self._check(self._c("get_collider_motion")(_ffi.MAX_COLLIDERS, arr, C.byref(n)))
-        return [(mo.vx, mo.vy) for mo in arr[:n.value]]
+        return self._get_records(self._c("get_collider_motion"), _MOTION.struct, _MOTION.fields)
 
     # ------------------------------------------------ collider spin (egg_set_collider_spin, DESIGN.md section 2.7)
     @staticmethod
     def _c_spins(spins):
         """a list with one element per collider -- None (no spin) or (px, py, omega) -- as an egg_collider_spin array; shape
         and finiteness are checked here, before any call into the library"""
-        spins = list(spins)
-        arr = (_ffi.EggColliderSpin * max(len(spins), 1))()
-        for k, sp in enumerate(spins):
-            if sp is None:
-                sp = (0.0, 0.0, 0.0)
-            try:
-                sp = tuple(float(v) for v in sp)
-            except (TypeError, ValueError):
-                raise EggError("collider spin %d: expected None or (px, py, omega), not %r" % (k, sp)) from None
-            if len(sp) != 3:
-                raise EggError("collider spin %d: expected None or (px, py, omega), not %r" % (k, sp))
-            if not (math.isfinite(sp[0]) and math.isfinite(sp[1])):
-                raise EggError("collider spin %d: the pivot (%r, %r) is not finite" % (k, sp[0], sp[1]))
-            if not math.isfinite(sp[2]):
-                raise EggError("collider spin %d: omega %r is not finite" % (k, sp[2]))
-            arr[k].px, arr[k].py, arr[k].omega = sp
-        return len(spins), arr
+        return _HandlerSurface._c_records(_SPIN, spins)
 
     def set_collider_spin(self, spins):
         """One spin per collider of the current list ("Collider spin"): `None` for a collider that
@@ -433,10 +499,7 @@ class _HandlerSurface:
 
     def get_collider_spin(self):
         """the spins as stored, one `(px, py, omega)` per collider (zeros included)"""
-        arr = (_ffi.EggColliderSpin * _ffi.MAX_COLLIDERS)()
-        n = C.c_int32()
-        self._check(self._c("get_collider_spin")(_ffi.MAX_COLLIDERS, arr, C.byref(n)))
-        return [(sp.px, sp.py, sp.omega) for sp in arr[:n.value]]
+        return self._get_records(self._c("get_collider_spin"), _SPIN.struct, _SPIN.fields)
 
     # ------------------------------------------------ collider styles and pose (egg_set_collider_styles, DESIGN.md section 2.7)
     _STYLE_DEFAULTS = {"fill": (0.0, 0.0, 0.0, 0.0), "line": (0.0, 0.0, 0.0, 0.0), "line_width": 0.0, "layer": "under"}
@@ -487,14 +550,11 @@ class _HandlerSurface:
 
     def get_collider_styles(self):
         """the styles as stored, one dict per collider -- `None` for one that is not visible"""
-        arr = (_ffi.EggColliderStyle * _ffi.MAX_COLLIDERS)()
-        n = C.c_int32()
-        self._check(self._c("get_collider_styles")(_ffi.MAX_COLLIDERS, arr, C.byref(n)))
-        kinds = (_ffi.EggCollider * _ffi.MAX_COLLIDERS)()
-        self._check(self._c("get_colliders")(_ffi.MAX_COLLIDERS, kinds, C.byref(n)))
+        arr = self._get_array(self._c("get_collider_styles"), _ffi.EggColliderStyle, _ffi.MAX_COLLIDERS)
+        kinds = self._get_array(self._c("get_colliders"), _ffi.EggCollider, _ffi.MAX_COLLIDERS)
         layers = {v: name for name, v in _ffi.COLLIDER_LAYERS.items()}
         out = []
-        for st, c in zip(arr[:n.value], kinds[:n.value]):
+        for st, c in zip(arr, kinds):
             inside = c.kind not in (_ffi.COLLIDER_SEGMENT, _ffi.COLLIDER_WALL)
             visible = (st.fill[3] > 0 and inside) or (st.line[3] > 0 and st.line_width > 0)
             out.append({"fill": tuple(st.fill), "line": tuple(st.line), "line_width": st.line_width,
@@ -507,12 +567,8 @@ class _HandlerSurface:
         t = `alpha` clamped to [0, 1] or, with None, this object's interpolation_alpha -- the rule draw() places the
         particles by.  A host that draws the colliders itself reads this once per frame.  set_colliders sets both lists:
         a teleport is not interpolated."""
-        arr = (_ffi.EggCollider * _ffi.MAX_COLLIDERS)()
-        n = C.c_int32()
-        self._check(self._c("get_collider_pose")(float("nan") if alpha is None else float(alpha), _ffi.MAX_COLLIDERS, arr, C.byref(n)))
-        types = {v: k for k, v in _ffi.COLLIDER_TYPES.items()}
-        return [(_ffi.COLLIDER_NAMES[c.kind],) + tuple(c.p[:len(_ffi.COLLIDER_PARAM_NAMES[c.kind])]) + (types[c.type_mask],)
-                for c in arr[:n.value]]
+        call = functools.partial(self._c("get_collider_pose"), float("nan") if alpha is None else float(alpha))
+        return self._kind_tuples(_COLLIDER_LIST, self._get_array(call, _ffi.EggCollider, _ffi.MAX_COLLIDERS))
 
     # ------------------------------------------------ collider loads (egg_set_collider_loads, DESIGN.md section 2.7)
     def set_collider_loads(self, on):
@@ -539,10 +595,7 @@ class _HandlerSurface:
         """one `(jx, jy, torque)` per collider: the impulse in mass px/s and the angular impulse about the collider's pivot in
         mass px^2/s that it received over the last committed step that recorded loads; the mean force over a step of
         length delta is j / delta.  All zeros while no step has recorded any."""
-        arr = (_ffi.EggColliderLoad * _ffi.MAX_COLLIDERS)()
-        n = C.c_int32()
-        self._check(self._c("get_collider_loads")(_ffi.MAX_COLLIDERS, arr, C.byref(n)))
-        return [(ld.jx, ld.jy, ld.torque) for ld in arr[:n.value]]
+        return self._get_records(self._c("get_collider_loads"), _ffi.EggColliderLoad, ("jx", "jy", "torque"))
 
     # ------------------------------------------------ sensors (egg_set_sensors, DESIGN.md section 2.8)
     @staticmethod
@@ -550,49 +603,7 @@ class _HandlerSurface:
         """a list of tuples `(kind, parameters...[, types])` or dicts `{"kind": ..., <parameter names>, "types": ...}` as an
         egg_sensor array.  A box takes its first axis `ux, uy` or, one value shorter, an `angle` in radians that the host's
         cos / sin convert.  What only the host can check (shape, names) is checked here, the values by the library."""
-        sensors = list(sensors)
-        if len(sensors) > _ffi.MAX_SENSORS:
-            raise EggError("sensors: a list holds 0 .. %d sensors, not %d" % (_ffi.MAX_SENSORS, len(sensors)))
-        arr = (_ffi.EggSensor * max(len(sensors), 1))()
-        for k, s in enumerate(sensors):
-            if isinstance(s, dict):
-                kind, types = s.get("kind"), s.get("types", "both")
-            else:
-                s = tuple(s)
-                kind = s[0] if s else None
-                types = "both"
-            if not isinstance(kind, str) or kind not in _ffi.SENSOR_CODES:
-                raise EggError("sensor %d: kind must be one of %s, not %r" % (k, ", ".join(_ffi.SENSOR_KINDS), kind))
-            code = _ffi.SENSOR_CODES[kind]
-            names = _ffi.SENSOR_PARAMS[code]
-            by_angle = ("cx", "cy", "hx", "hy", "angle")
-            if isinstance(s, dict):
-                given = set(s) - {"kind", "types"}
-                if code == _ffi.SENSOR_BOX and given == set(by_angle):
-                    names = by_angle
-                if given != set(names):
-                    raise EggError("sensor %d (%s): expected the keys %s" % (k, kind, ", ".join(names)))
-                values = [s[n] for n in names]
-            else:
-                values = list(s[1:])
-                if values and isinstance(values[-1], str):
-                    types = values.pop()
-                if code == _ffi.SENSOR_BOX and len(values) == len(by_angle):
-                    names = by_angle
-                if len(values) != len(names):
-                    raise EggError("sensor %d (%s): expected (%r, %s[, types])" % (k, kind, kind, ", ".join(names)))
-            if not isinstance(types, str) or types not in _ffi.SENSOR_TYPES:
-                raise EggError("sensor %d: types must be 'both', 'white' or 'yolk', not %r" % (k, types))
-            try:
-                values = [float(v) for v in values]
-            except (TypeError, ValueError):
-                raise EggError("sensor %d (%s): the parameters must be numbers" % (k, kind)) from None
-            if names is by_angle:
-                values = values[:4] + [math.cos(values[4]), math.sin(values[4])]
-            arr[k].kind, arr[k].type_mask = code, _ffi.SENSOR_TYPES[types]
-            for q, v in enumerate(values):
-                arr[k].p[q] = v
-        return len(sensors), arr
+        return _HandlerSurface._c_kind_list(_SENSOR_LIST, sensors)
 
     def set_sensors(self, sensors):
         """The ordered list of sensor regions, at most 64 (either solver order):
@@ -607,12 +618,7 @@ class _HandlerSurface:
     def get_sensors(self):
         """the list as stored, as tuples `(kind, parameters..., types)`: normals and box axes come back normalised, a box
         with its axis `ux, uy`"""
-        arr = (_ffi.EggSensor * _ffi.MAX_SENSORS)()
-        n = C.c_int32()
-        self._check(self._c("get_sensors")(_ffi.MAX_SENSORS, arr, C.byref(n)))
-        types = {v: k for k, v in _ffi.SENSOR_TYPES.items()}
-        return [(_ffi.SENSOR_KINDS[s.kind],) + tuple(s.p[:len(_ffi.SENSOR_PARAMS[s.kind])]) + (types[s.type_mask],)
-                for s in arr[:n.value]]
+        return self._kind_tuples(_SENSOR_LIST, self._get_array(self._c("get_sensors"), _ffi.EggSensor, _ffi.MAX_SENSORS))
 
     def sensor_sums(self):
         """`(sums, dropped)` of the positions as committed now: `sums` holds per sensor `((count, sx, sy), (count, sx, sy))`
@@ -1025,27 +1031,7 @@ class _HandlerSurface:
         """a list with one element per collider -- None (no body), (inv_mass, inv_inertia), (inv_mass, inv_inertia, ax, ay) or
         (inv_mass, inv_inertia, ax, ay, drag, spin_drag) -- as an egg_collider_body array; shape, finiteness and signs are
         checked here, before any call into the library"""
-        bodies = list(bodies)
-        arr = (_ffi.EggColliderBody * max(len(bodies), 1))()
-        names = ("inv_mass", "inv_inertia", "ax", "ay", "drag", "spin_drag")
-        for k, b in enumerate(bodies):
-            if b is None:
-                b = (0.0, 0.0)
-            try:
-                b = tuple(float(v) for v in b)
-            except (TypeError, ValueError):
-                raise EggError("collider body %d: expected None or (inv_mass, inv_inertia[, ax, ay[, drag, spin_drag]]), not %r" % (k, b)) from None
-            if len(b) not in (2, 4, 6):
-                raise EggError("collider body %d: expected None or (inv_mass, inv_inertia[, ax, ay[, drag, spin_drag]]), not %r" % (k, b))
-            b = b + (0.0,) * (6 - len(b))
-            for name, v in zip(names, b):
-                if not math.isfinite(v):
-                    raise EggError("collider body %d: %s %r is not finite" % (k, name, v))
-                if name not in ("ax", "ay") and v < 0.0:
-                    raise EggError("collider body %d: %s %r is negative" % (k, name, v))
-            for name, v in zip(names, b):
-                setattr(arr[k], name, v)
-        return len(bodies), arr
+        return _HandlerSurface._c_records(_BODY, bodies)
 
     def set_collider_bodies(self, bodies):
         """SimulationHandler.set_collider_bodies where several handles share a step (SimulationGroup,
@@ -1106,40 +1092,7 @@ class _HandlerSurface:
     def _c_forces(forces):
         """a list of tuples `(kind, parameters...[, types])` or dicts `{"kind": ..., <parameter names>, "types": ...}` as an
         egg_force array; what only the host can check (shape, names) is checked here, the values by the library"""
-        forces = list(forces)
-        arr = (_ffi.EggForce * max(len(forces), 1))()
-        for k, f in enumerate(forces):
-            if isinstance(f, dict):
-                kind, types = f.get("kind"), f.get("types", "both")
-            else:
-                f = tuple(f)
-                kind = f[0] if f else None
-                types = "both"
-            if kind not in _ffi.FORCE_KINDS:
-                raise EggError("field %d: kind must be one of %s, not %r" % (k, ", ".join(_ffi.FORCE_KINDS), kind))
-            code = _ffi.FORCE_KINDS.index(kind)
-            names = _ffi.FORCE_PARAMS[code]
-            if isinstance(f, dict):
-                extra = set(f) - set(names) - {"kind", "types"}
-                if extra or not all(n in f for n in names):
-                    raise EggError("field %d (%s): expected the keys %s" % (k, kind, ", ".join(names)))
-                values = [f[n] for n in names]
-            else:
-                values = list(f[1:])
-                if len(values) == len(names) + 1 and isinstance(values[-1], str):
-                    types = values.pop()
-                if len(values) != len(names):
-                    raise EggError("field %d (%s): expected (%r, %s[, types])" % (k, kind, kind, ", ".join(names)))
-            if not isinstance(types, str) or types not in _ffi.FORCE_TYPES:
-                raise EggError("field %d: types must be 'both', 'white' or 'yolk', not %r" % (k, types))
-            try:
-                values = [float(v) for v in values]
-            except (TypeError, ValueError):
-                raise EggError("field %d (%s): the parameters must be numbers" % (k, kind)) from None
-            arr[k].kind, arr[k].type_mask = code, _ffi.FORCE_TYPES[types]
-            for q, v in enumerate(values):
-                arr[k].p[q] = v
-        return len(forces), arr
+        return _HandlerSurface._c_kind_list(_FORCE_LIST, forces)
 
     def set_forces(self, forces):
         """The ordered list of force fields, at most 16 ("Forces"; relaxed order only), as
@@ -1155,12 +1108,7 @@ class _HandlerSurface:
 
     def get_forces(self):
         """the list as stored, as tuples `(kind, parameters..., types)`"""
-        arr = (_ffi.EggForce * _ffi.MAX_FORCES)()
-        n = C.c_int32()
-        self._check(self._c("get_forces")(_ffi.MAX_FORCES, arr, C.byref(n)))
-        types = {v: k for k, v in _ffi.FORCE_TYPES.items()}
-        return [(_ffi.FORCE_KINDS[f.kind],) + tuple(f.p[:len(_ffi.FORCE_PARAMS[f.kind])]) + (types[f.type_mask],)
-                for f in arr[:n.value]]
+        return self._kind_tuples(_FORCE_LIST, self._get_array(self._c("get_forces"), _ffi.EggForce, _ffi.MAX_FORCES))
 
     # ------------------------------------------------ viscosity (egg_set_viscosity, DESIGN.md section 2.7)
     @staticmethod
@@ -1195,9 +1143,7 @@ class _HandlerSurface:
 
     def viscosity_pairs(self):
         """[white, yolk]: distinct pairs within the cell size, over the viscosity passes of committed steps, since creation"""
-        pairs = (C.c_int64 * 2)()
-        self._check(self._c("get_viscosity_pairs")(pairs))
-        return list(pairs)
+        return self._get_counts(self._c("get_viscosity_pairs"))
 
     # ------------------------------------------------ white-yolk coupling (egg_set_coupling, DESIGN.md section 2.7)
     _COUPLING_LIMIT = ("coupling: white-yolk coupling runs on a single SimulationHandler only -- the halo of a device group "
@@ -1206,17 +1152,7 @@ class _HandlerSurface:
     @staticmethod
     def _c_coupling(factor, strength):
         """(factor, strength) as the doubles egg_set_coupling takes; the ranges are checked here as the library checks them"""
-        out = []
-        for name, v in (("factor", factor), ("strength", strength)):
-            try:
-                out.append(float(v))
-            except (TypeError, ValueError):
-                raise EggError("coupling: the %s must be a number, not %r" % (name, v)) from None
-        if not (0.0 <= out[0] < float("inf")):  # (false for a NaN)
-            raise EggError("coupling: the factor %r is not a finite number >= 0" % (out[0],))
-        if not (0.0 <= out[1] <= 1.0):
-            raise EggError("coupling: the strength %r lies outside [0, 1]" % (out[1],))
-        return out[0], out[1]
+        return _HandlerSurface._c_range_pair("coupling", "factor", factor, strength)
 
     def set_coupling(self, factor=0.0, strength=1.0):
         """SimulationHandler.set_coupling where several handles share a step (SimulationGroup, ShardedSimulationHandler):
@@ -1239,17 +1175,7 @@ class _HandlerSurface:
     @staticmethod
     def _c_adhesion(reach, strength):
         """(reach, strength) as the doubles egg_set_adhesion takes; the ranges are checked here as the library checks them"""
-        out = []
-        for name, v in (("reach", reach), ("strength", strength)):
-            try:
-                out.append(float(v))
-            except (TypeError, ValueError):
-                raise EggError("adhesion: the %s must be a number, not %r" % (name, v)) from None
-        if not (0.0 <= out[0] < float("inf")):  # (false for a NaN)
-            raise EggError("adhesion: the reach %r is not a finite number >= 0" % (out[0],))
-        if not (0.0 <= out[1] <= 1.0):
-            raise EggError("adhesion: the strength %r lies outside [0, 1]" % (out[1],))
-        return out[0], out[1]
+        return _HandlerSurface._c_range_pair("adhesion", "reach", reach, strength)
 
     def set_adhesion(self, reach=0.0, strength=1.0):
         """SimulationHandler.set_adhesion where several handles share a step (SimulationGroup, ShardedSimulationHandler):
@@ -1269,17 +1195,7 @@ class _HandlerSurface:
     @staticmethod
     def _c_containment(factor, strength):
         """(factor, strength) as the doubles egg_set_containment takes; the ranges are checked here as the library checks them"""
-        out = []
-        for name, v in (("factor", factor), ("strength", strength)):
-            try:
-                out.append(float(v))
-            except (TypeError, ValueError):
-                raise EggError("containment: the %s must be a number, not %r" % (name, v)) from None
-        if not (0.0 <= out[0] < float("inf")):  # (false for a NaN)
-            raise EggError("containment: the factor %r is not a finite number >= 0" % (out[0],))
-        if not (0.0 <= out[1] <= 1.0):
-            raise EggError("containment: the strength %r lies outside [0, 1]" % (out[1],))
-        return out[0], out[1]
+        return _HandlerSurface._c_range_pair("containment", "factor", factor, strength)
 
     def set_containment(self, factor=0.0, strength=1.0):
         """Yolk containment: a disc around the centroid of each batch's white that no yolk particle of that batch may leave
@@ -1295,15 +1211,11 @@ class _HandlerSurface:
 
     def containment(self):
         """(factor, strength) as stored"""
-        f, s = C.c_double(), C.c_double()
-        self._check(self._c("get_containment")(C.byref(f), C.byref(s)))
-        return (f.value, s.value)
+        return self._get_pair(self._c("get_containment"))
 
     def containment_hits(self):
         """projections, one per (yolk particle, sub-step), over committed steps, since creation"""
-        n = C.c_int64()
-        self._check(self._c("get_containment_hits")(C.byref(n)))
-        return int(n.value)
+        return self._get_count(self._c("get_containment_hits"))
 
     def _init_host_state(self, white_config, yolk_config):
         """config tables (validated like the reference, L:1253-1320), hidden constants and render switches; no device"""
@@ -1725,10 +1637,7 @@ class SimulationHandler(_HandlerSurface):
 
     def get_collider_bodies(self):
         """the bodies as stored, one `(inv_mass, inv_inertia, ax, ay, drag, spin_drag)` per collider (zeros included)"""
-        arr = (_ffi.EggColliderBody * _ffi.MAX_COLLIDERS)()
-        n = C.c_int32()
-        self._check(self._c("get_collider_bodies")(_ffi.MAX_COLLIDERS, arr, C.byref(n)))
-        return [(b.inv_mass, b.inv_inertia, b.ax, b.ay, b.drag, b.spin_drag) for b in arr[:n.value]]
+        return self._get_records(self._c("get_collider_bodies"), _BODY.struct, _BODY.fields)
 
     def set_collider_contacts(self, contacts, iterations=4):
         """One contact record per collider of the current list ("Collider contacts"): `None` for a
@@ -1752,9 +1661,7 @@ class SimulationHandler(_HandlerSurface):
 
     def collider_contact_solves(self):
         """the fires of collider contacts, one per (pair, sub-step, iteration), over committed steps"""
-        out = C.c_int64()
-        self._check(self._c("get_collider_contact_solves")(C.byref(out)))
-        return out.value
+        return self._get_count(self._c("get_collider_contact_solves"))
 
     def set_coupling(self, factor=0.0, strength=1.0):
         """White-yolk coupling: one cross-type collision pass per sub-step of a relaxed step, before the sub-step's first
@@ -1769,15 +1676,11 @@ class SimulationHandler(_HandlerSurface):
 
     def coupling(self):
         """(factor, strength) as stored"""
-        f, s = C.c_double(), C.c_double()
-        self._check(self._c("get_coupling")(C.byref(f), C.byref(s)))
-        return (f.value, s.value)
+        return self._get_pair(self._c("get_coupling"))
 
     def coupling_solves(self):
         """distinct white-yolk pairs that fired over the coupling passes of committed steps, since creation"""
-        n = C.c_int64()
-        self._check(self._c("get_coupling_solves")(C.byref(n)))
-        return int(n.value)
+        return self._get_count(self._c("get_coupling_solves"))
 
     def set_adhesion(self, reach=0.0, strength=1.0):
         """White-yolk adhesion: a same-batch band in the coupling pass ("Adhesion"; relaxed order
@@ -1792,15 +1695,11 @@ class SimulationHandler(_HandlerSurface):
 
     def adhesion(self):
         """(reach, strength) as stored"""
-        r, s = C.c_double(), C.c_double()
-        self._check(self._c("get_adhesion")(C.byref(r), C.byref(s)))
-        return (r.value, s.value)
+        return self._get_pair(self._c("get_adhesion"))
 
     def adhesion_solves(self):
         """distinct white-yolk pairs whose adhesion branch fired over the coupling passes of committed steps"""
-        n = C.c_int64()
-        self._check(self._c("get_adhesion_solves")(C.byref(n)))
-        return int(n.value)
+        return self._get_count(self._c("get_adhesion_solves"))
 
     def add_many(self, xs, ys, white_radius=None, yolk_radius=None, white_n_particles=None,
                  yolk_n_particles=None):

@@ -262,7 +262,7 @@ def test_python_classes_have_the_methods_and_check_what_only_the_host_can():
             assert list(inspect.signature(getattr(cls, name)).parameters) == params, (cls.__name__, name)
     assert SimulationGroup._PREFIX == "egg_group_" and SimulationGroup.impulse is SimulationHandler.impulse
     src = inspect.getsource(ShardedSimulationHandler.impulse)
-    assert src.count("self.dist.all_reduce(") == 1 and "ReduceOp.SUM" in src and "self.local._impulse_table(" in src and "IMPULSE_NO_BATCH" in src
+    assert src.count("self._all_reduce_sum(") == 1 and "self.dist" not in src and "self.local._impulse_table(" in src and "IMPULSE_NO_BATCH" in src
     n, arr = SimulationHandler._c_impulses([Impulse("blast", ("disc", 1.0, 2.0, 3.0, "yolk"), (1.0, 2.0, -4.0), 7, True, True),
                                             ("brake", ("box", 0.0, 0.0, 2.0, 1.0, 0.0), 0.5, 0.25, 1.0), ("kick", ("half_plane", 0.0, 2.0, 1.0), 1.0, 2.0, {"id": 3})])
     assert n == 3 and (arr[0].action, arr[0].flags, arr[0].id, list(arr[0].a)) == (1, 3, 7, [1.0, 2.0, -4.0])

@@ -149,7 +149,7 @@ def test_python_classes_have_the_methods():
     assert not hasattr(SimulationGroup, "measure_to") and not hasattr(ShardedSimulationHandler, "measure_to")
     assert SimulationGroup._PREFIX == "egg_group_" and SimulationGroup.measure_table is SimulationHandler.measure_table
     src = inspect.getsource(ShardedSimulationHandler.measure_table)
-    assert src.count("self.dist.all_reduce(") == 1 and "ReduceOp.SUM" in src and "self.local._measure_table(" in src and "self.local._measure_check(" in src
+    assert src.count("self._owner_table(") == 1 and "self.dist" not in src and "self.local._measure_table(" in src and "self.local._measure_check(" in src
     assert ShardedSimulationHandler.measure is SimulationHandler.measure and ShardedSimulationHandler.at_rest is SimulationHandler.at_rest
     assert Measure._fields == mm.FIELDS
     for name in ("kept", "mass", "centroid", "center_of_mass", "momentum", "velocity", "kinetic_energy", "bounds", "max_speed", "origin", "reach", "spin"):

@@ -127,7 +127,7 @@ def test_python_classes_have_the_methods_with_equal_parameter_lists():
     assert SimulationGroup._PREFIX == "egg_group_" and SimulationGroup.sensor_sums is SimulationHandler.sensor_sums
     for name in ("sensor_sums", "sensor_batches"):
         src = inspect.getsource(getattr(ShardedSimulationHandler, name))
-        assert "self.local.%s(" % name in src and src.count("all_reduce(") == 1 and "int64" in src, name
+        assert "self.local.%s(" % name in src and src.count("self._all_reduce_sum(") + src.count("self._owner_table(") == 1 and "int64" in src, name
     assert "self.local.set_sensors(sensors)" in inspect.getsource(ShardedSimulationHandler.set_sensors)
     assert "_sensor_readings" in inspect.getsource(ShardedSimulationHandler.sensors)
 
