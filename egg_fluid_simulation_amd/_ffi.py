@@ -268,6 +268,27 @@ MEASURE_MASS_SCALE = 4294967296.0  # EGG_MEASURE_MASS_SCALE, 2^32
 MEASURE_REGION = 1  # EGG_MEASURE_REGION: flag bit
 
 
+class EggCoverSpec(C.Structure):  # egg_cover_spec: the grid of one call, the factor on the radii, the types and the path (48 bytes)
+    _fields_ = [("x0", C.c_double), ("y0", C.c_double), ("cell", C.c_double), ("scale", C.c_double), ("nx", C.c_int32), ("ny", C.c_int32),
+                ("type_mask", C.c_int32), ("path", C.c_int32)]
+
+
+class EggCoverPlanes(C.Structure):  # egg_cover_planes: int32 cover and int32 owner (or NULL), each [2][ny][nx] (16 bytes)
+    _fields_ = [("cover", C.c_void_p), ("owner", C.c_void_p)]
+
+
+class EggCoverTotals(C.Structure):  # egg_cover_totals: particles per type by fate, covered cells, and the units of each path (112 bytes)
+    _fields_ = [("inside", C.c_int64 * 2), ("outside", C.c_int64 * 2), ("dropped", C.c_int64 * 2), ("hits", C.c_int64 * 2),
+                ("covered", C.c_int64 * 2), ("covered_both", C.c_int64), ("covered_any", C.c_int64), ("units_lanes", C.c_int32),
+                ("units_wave", C.c_int32), ("units_direct", C.c_int32), ("reserved", C.c_int32)]
+
+
+COVER_MAX_CELLS = 1 << 20  # EGG_COVER_MAX_CELLS: nx * ny
+COVER_MAX_SPAN = 64.0  # EGG_COVER_MAX_SPAN: scale * radius / cell
+COVER_OWNER_KEYS = 0x100  # EGG_COVER_OWNER_KEYS: flag bit of spec.path, the owner plane holds keys in place of ids
+COVER_PATHS = {"auto": 0, "direct": 1, "lanes": 2, "wave": 3}  # EGG_COVER_PATH_*; all but auto are test hooks
+
+
 class EggRxBox(C.Structure):  # egg_rx_box: a cell box of the relaxed halo between processes
     _fields_ = [("lo_x", C.c_int32), ("lo_y", C.c_int32), ("hi_x", C.c_int32), ("hi_y", C.c_int32), ("empty", C.c_int32)]
 
@@ -489,6 +510,13 @@ _MEASURE_SIGNATURES = {
     "egg_group_measure": (C.c_int, [C.c_void_p, C.POINTER(EggMeasureSpec), C.c_int64, C.c_void_p, C.c_void_p]),
 }
 MEASURE_SYMBOLS = sorted(_MEASURE_SIGNATURES)
+# the entry points of include/eggsim_cover.h, brought along the same way: with them the library exports 181
+_COVER_SIGNATURES = {
+    "egg_cover": (C.c_int, [C.c_void_p, C.POINTER(EggCoverSpec), C.POINTER(EggCoverPlanes), C.POINTER(EggCoverTotals)]),
+    "egg_cover_to": (C.c_int, [C.c_void_p, C.POINTER(EggCoverSpec), C.POINTER(EggCoverPlanes), C.POINTER(EggCoverTotals)]),
+    "egg_group_cover": (C.c_int, [C.c_void_p, C.POINTER(EggCoverSpec), C.POINTER(EggCoverPlanes), C.POINTER(EggCoverTotals)]),
+}
+COVER_SYMBOLS = sorted(_COVER_SIGNATURES)
 
 _lib = None
 
@@ -506,7 +534,8 @@ def load():
                 "libeggsim.so not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
                 "or `make -C egg_fluid_simulation_amd/csrc` (needs hipcc; the solver has no CPU path)")
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(_SIGNATURES.items()) + list(_IMPULSE_SIGNATURES.items()) + list(_MEASURE_SIGNATURES.items()):
+        for name, (res, args) in list(_SIGNATURES.items()) + list(_IMPULSE_SIGNATURES.items()) + list(_MEASURE_SIGNATURES.items()) + \
+                list(_COVER_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

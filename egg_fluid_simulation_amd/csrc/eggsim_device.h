@@ -1083,3 +1083,37 @@ struct EggMeasureArgs {
     EggRegion region;                // checked and normalised; tested by sn_test, its own type mask included
     long long *out;                  // [slots][EGG_MS_FIELDS]; a slot without a row is zeroed before the launch
 };
+
+// ---------------------------------------------------------------------------------------------
+// Cover (eggsim_cover.hip; include/eggsim_cover.h): every committed particle's disc of radius
+// scale * radius rastered into a caller-set grid -- per cell and type how many discs cover the cell's centre and, on request,
+// the smallest batch id among them.  The scan walks the units of the shared builder (push_units: at most EGG_SN_UNIT
+// consecutive particles of one atom) with one wave per unit.  A unit has ONE batch, so a tile holds counts only and the
+// owner -- the unit's label in its spare word: its batch's id, or its key -- is written where the tile is flushed.  Read-only on the particle
+// arrays; no step launches anything of this.
+#define EGG_CV_TILE_CELLS 4096       // cells of a unit's union rectangle the tile paths hold: 16 KB of counts
+#define EGG_CV_LANES_CELLS 784       // the largest footprint (cells of a disc's rectangle, 28 x 28) of the lane-per-particle path
+#define EGG_CV_WAVE_CELLS 784        // the largest footprint of the wave-per-particle path: no wider than the lanes' bound, because
+                                     // the sweep (profiles/r35_cover.md) found no footprint at which that path wins; beyond it: direct
+#define EGG_CV_MAX_SPAN 64.0         // = EGG_COVER_MAX_SPAN: R * inv beyond it drops the particle
+#define EGG_CV_TOTALS 16             // words of the totals: inside, outside, dropped, hits per type, units lanes, wave, direct,
+                                     // then (the finishing kernel) covered per type, covered_both, covered_any, one spare
+#define EGG_CV_FINISH_THREADS 256
+struct EggCoverArgs {
+    const double *x[2], *y[2], *radius[2];  // the committed positions and the radii per type
+    const EggScanUnit *units;         // `reserved`: what a unit's discs write into the owner plane
+    int32_t n_units;
+    int32_t nx, ny;
+    int32_t tile_cells;               // 0 .. EGG_CV_TILE_CELLS: the largest union rectangle of the tile paths, 0 = every unit direct
+    int32_t lanes_cells;              // the largest footprint of the lanes path: 0 = never, INT32_MAX = wherever the tile fits
+    int32_t wave_cells;               // the largest footprint of the wave path, taken above lanes_cells; a larger footprint: direct
+    double x0, y0, cell, inv, scale;  // inv = 1.0 / cell, computed once on the host
+    int32_t *cover;                   // [2][ny][nx], zeroed before the launch
+    uint32_t *owner;                  // [2][ny][nx], preset to 0xFFFFFFFF before the launch, or null
+    unsigned long long *totals;       // [EGG_CV_TOTALS], zeroed before the launch
+};
+struct EggCoverFinishArgs {           // covered[2], covered_both, covered_any from the finished cover planes
+    const int32_t *cover;             // [2][cells]
+    int64_t cells;                    // nx * ny
+    unsigned long long *totals;       // words 11 .. 14
+};

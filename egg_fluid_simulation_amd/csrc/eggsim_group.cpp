@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "../../include/eggsim.h"
+#include "eggsim_cover_merge.h"
 #include "eggsim_group_draw.h"
 
 namespace egghost {  // eggsim_host_relaxed_group.hip
@@ -1073,6 +1074,48 @@ int egg_group_measure(egg_group *g, const egg_measure_spec *spec, int64_t n_ids,
     return route_to_owners<egg_measure_record>(g, n_ids, ids, 2, out, [&](size_t k, int64_t n, const int64_t *local, egg_measure_record *part) {
         return egg_measure(g->h[k], spec, n, local, part);
     });
+}
+
+// Cover (include/eggsim_cover.h): every handle rasters the particles it owns into the same grid; eggsim_cover_merge.h adds
+// the cover planes, merges the owner planes -- taken as keys: a batch's key on its handle is the group's id -- by unsigned
+// minimum and recounts
+// covered, covered_both and covered_any from the merged planes; the other totals are added.  Handle 0 refuses a bad grid;
+// nothing is written before every handle has answered.
+int egg_group_cover(egg_group *g, const egg_cover_spec *spec, const egg_cover_planes *host_planes, egg_cover_totals *totals) {
+    if (!g || g->h.empty()) return EGG_ERR_INVALID_ARGUMENT;
+    const bool shaped = spec && spec->nx >= 1 && spec->ny >= 1 && (int64_t)spec->nx * spec->ny <= EGG_COVER_MAX_CELLS;
+    const size_t words = shaped && host_planes && host_planes->cover ? 2 * (size_t)spec->nx * (size_t)spec->ny : 0;
+    const bool with_owner = host_planes && host_planes->owner;
+    std::vector<int32_t> cover(words, 0), one_cover(std::max<size_t>(words, 1)), one_owner(with_owner ? std::max<size_t>(words, 1) : 0);
+    std::vector<uint32_t> owner(with_owner ? words : 0, 0xFFFFFFFFu);
+    egg_cover_totals sum{};
+    egg_cover_spec keyed = spec ? *spec : egg_cover_spec{};
+    keyed.path |= EGG_COVER_OWNER_KEYS;  // (a batch's key on its handle is the group's id)
+    for (size_t k = 0; k < g->h.size(); ++k) {
+        egg_cover_planes one{};
+        if (host_planes) {  // (a missing plane stays missing: the handle refuses what it refuses alone)
+            one.cover = host_planes->cover ? one_cover.data() : nullptr;
+            one.owner = with_owner ? one_owner.data() : nullptr;
+        }
+        egg_cover_totals t{};
+        const int rc = egg_cover(g->h[k], spec ? &keyed : nullptr, host_planes ? &one : nullptr, &t);
+        if (rc < 0) return gfail(g, rc, "device %d: %s", (int)k, egg_last_error(g->h[k]));
+        eggcover::merge_planes(words, cover.data(), with_owner ? owner.data() : nullptr, one_cover.data(), with_owner ? one_owner.data() : nullptr);
+        for (int w = 0; w < 2; ++w) {
+            sum.inside[w] += t.inside[w];
+            sum.outside[w] += t.outside[w];
+            sum.dropped[w] += t.dropped[w];
+            sum.hits[w] += t.hits[w];
+        }
+        sum.units_lanes += t.units_lanes;
+        sum.units_wave += t.units_wave;
+        sum.units_direct += t.units_direct;
+    }
+    eggcover::recount(words / 2, cover.data(), sum.covered, &sum.covered_both, &sum.covered_any);
+    memcpy(host_planes->cover, cover.data(), words * sizeof(int32_t));
+    if (with_owner) memcpy(host_planes->owner, owner.data(), words * sizeof(int32_t));
+    if (totals) *totals = sum;
+    return EGG_OK;
 }
 
 int egg_group_get_collider_grips(egg_group *g, int64_t grips[2]) {

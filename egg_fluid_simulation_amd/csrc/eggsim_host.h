@@ -20,6 +20,7 @@
 //   eggsim_host_pieces.hip         egg_pieces: the checks, the task table, at most two launches, the one copy of the records back
 //   eggsim_host_impulses.hip       egg_impulse: the checks, the unit table, at most two launches, the one copy of the totals back
 //   eggsim_host_measures.hip       egg_measure / egg_measure_to: the checks, the row table, the one launch, the one copy of the records back
+//   eggsim_host_cover.hip          egg_cover / egg_cover_to: the checks, the unit table, the presets, the two launches, the copies back
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -154,6 +155,8 @@ extern "C" __global__ void egg_impulse_kernel(EggImpulseArgs A);
 extern "C" __global__ void egg_impulse_quiet_kernel(EggImpulseArgs A);
 extern "C" __global__ void egg_impulse_finish_kernel(EggImpulseFinishArgs A);
 extern "C" __global__ void egg_measure_kernel(EggMeasureArgs A);
+extern "C" __global__ void egg_cover_kernel(EggCoverArgs A);
+extern "C" __global__ void egg_cover_finish_kernel(EggCoverFinishArgs A);
 extern "C" __global__ void egg_render_count_kernel(EggRenderArgs A);
 extern "C" __global__ void egg_render_fill_kernel(EggRenderArgs A);
 extern "C" __global__ void egg_render_scan_kernel(EggRenderArgs A);
@@ -433,6 +436,7 @@ struct FieldState;  // unit table, planes and totals of an egg_field call (eggsi
 struct PiecesState;  // task table, records and labels of an egg_pieces call (eggsim_host_pieces.hip)
 struct ImpulseState;  // records, unit table, partials and totals of an egg_impulse call (eggsim_host_impulses.hip)
 struct MeasureState;  // row table and records of an egg_measure call (eggsim_host_measures.hip)
+struct CoverState;  // unit table, planes and totals of an egg_cover call (eggsim_host_cover.hip)
 // egg_handle::collider_dirty: the tables sync_collider_records has to copy (eggsim_host_colliders.hip)
 enum : unsigned { kDirtyList = 1u, kDirtySurfaces = 2u, kDirtyMotions = 4u, kDirtySpins = 8u, kDirtyAllTables = 15u };
 }
@@ -617,6 +621,9 @@ struct egg_handle {
     // measures (egg_measure / egg_measure_to; either solver order): what a call needs on the device, allocated by the first
     // call that launches.  A call stores no answer; no step reads this.
     std::shared_ptr<egghost::MeasureState> measure_state;
+    // cover (egg_cover / egg_cover_to; either solver order): what a call needs on the device, allocated by the first call
+    // that launches.  A call stores no grid and no answer; no step reads this.
+    std::shared_ptr<egghost::CoverState> cover_state;
     // headless renderer (eggsim_render.hip)
     struct Render {
         egg_render_config cfg[2];
@@ -732,8 +739,10 @@ void push_units(const Atom &a, int w, std::vector<EggScanUnit> &units);
 int covered_types(const egg_handle *h, int mask);
 // A feature's table of every unit of the types it covers, on the device.  refresh() rebuilds it when the coverage or the
 // atoms of either type moved since it was built and is free otherwise; with_batch_ids puts the id of a unit's batch into
-// its spare word.  Each feature embeds its own: features with different masks would rebuild a shared one in turn.
+// its spare word -- or, in a table whose by_key is set (once, by the feature that embeds it), the batch's key.  Each feature
+// embeds its own: features with different masks would rebuild a shared one in turn.
 struct UnitTable {
+    bool by_key = false;
     DevBuf<EggScanUnit> d_units;
     uint64_t gen[2] = {~0ull, ~0ull};
     int cover = -1;

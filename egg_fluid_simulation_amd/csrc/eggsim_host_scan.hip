@@ -45,10 +45,10 @@ int UnitTable::refresh(egg_handle *h, const char *name, int want, bool with_batc
             const size_t first = units.size();
             push_units(a, w, units);
             if (!with_batch_ids) continue;
-            // (a unit's spare word carries the id of its batch: ids are 1 + the index into h->batches)
-            const int64_t id = h->batches[(size_t)a.batch].id;
-            if (id < 1 || id > (int64_t)std::numeric_limits<int32_t>::max())
-                return fail(h, EGG_ERR_INTERNAL, "%s: batch id %lld does not fit a unit's 32-bit word", name, (long long)id);
+            // (a unit's spare word carries the id of its batch: ids are 1 + the index into h->batches; or its key, from 0)
+            const int64_t id = by_key ? h->batches[(size_t)a.batch].key : h->batches[(size_t)a.batch].id;
+            if (id < (by_key ? 0 : 1) || id > (int64_t)std::numeric_limits<int32_t>::max())
+                return fail(h, EGG_ERR_INTERNAL, "%s: batch %s %lld does not fit a unit's 32-bit word", name, by_key ? "key" : "id", (long long)id);
             for (size_t q = first; q < units.size(); ++q) units[q].reserved = (int32_t)id;
         }
     }

@@ -1250,6 +1250,57 @@ function SimulationHandler:at_rest(id, speed, types)
     return (res[1].white == nil or res[1].white.max_speed <= speed) and (res[1].yolk == nil or res[1].yolk.max_speed <= speed)
 end
 
+-- Not in the reference: cover (egg_cover in include/eggsim_cover.h; DESIGN.md section 2.14).  The floor under the egg: every
+-- committed particle's disc of radius scale * radius rastered into a caller-set grid -- per cell and type how many discs lie
+-- over the cell's centre and, on request, the oldest batch among them; either solver order.  A call stores nothing and only
+-- observes.
+-- include/eggsim_cover.h, the third header include/eggsim.h brings along (declared from a string: the blocks above stay three)
+local _cover_decls = [==[
+typedef struct { double x0, y0, cell, scale; int32_t nx, ny, type_mask, path; } egg_cover_spec;
+typedef struct { int32_t *cover; int32_t *owner; } egg_cover_planes;
+typedef struct {
+    int64_t inside[2], outside[2], dropped[2], hits[2], covered[2], covered_both, covered_any;
+    int32_t units_lanes, units_wave, units_direct, reserved;
+} egg_cover_totals;
+int egg_cover(egg_handle *h, const egg_cover_spec *spec, const egg_cover_planes *host_planes, egg_cover_totals *totals);
+]==]
+ffi.cdef(_cover_decls)
+local _cover_paths = { auto = 0, direct = 1, lanes = 2, wave = 3 }
+local _cover_max_cells = 1048576 -- EGG_COVER_MAX_CELLS
+
+--- the grid of `nx` x `ny` square cells of side `cell` whose cell (0, 0) has its lower corner at (x0, y0); `options` may hold
+--- `scale` (1: the simulated discs, 12: the discs as they are drawn), `types = "both" | "white" | "yolk"`, `owner = true` and
+--- `path = "auto" | "direct" | "lanes" | "wave"` (test hooks).  Returns `{ nx, ny, cell, cover, owner, inside, outside, dropped,
+--- hits, covered, covered_both, covered_any, area, units_lanes, units_wave, units_direct }` by name: `cover` and `owner` (nil
+--- without owner; -1: no disc) `int32_t` arrays laid out [2][ny][nx], 0-based, [0] white and [1] yolk -- the word of type w and
+--- cell (ix, iy) is `(w * ny + iy) * nx + ix` --; `inside` .. `covered` are `{ white, yolk }` counts and `area` is
+--- `{ white, yolk, both, any }` in px^2.
+function SimulationHandler:cover(x0, y0, cell, nx, ny, options)
+    options = options or {}
+    local mask = _collider_types[options.types or "both"]
+    local path = _cover_paths[options.path or "auto"]
+    local scale = options.scale or 1.0
+    if mask == nil or path == nil or type(scale) ~= "number" or type(nx) ~= "number" or type(ny) ~= "number" or nx < 1 or ny < 1
+        or nx * ny > _cover_max_cells or nx ~= math.floor(nx) or ny ~= math.floor(ny) then
+        log.error("In SimulationHandler.cover: expected (x0, y0, cell, nx, ny, { scale = ..., types = ..., owner = ..., path = ... }) with nx * ny in 1 .. 1048576")
+        return nil
+    end
+    local words = 2 * nx * ny
+    local spec = ffi.new("egg_cover_spec", { x0 = x0, y0 = y0, cell = cell, scale = scale, nx = nx, ny = ny, type_mask = mask, path = path })
+    local cover = ffi.new("int32_t[?]", words)
+    local owner = options.owner and ffi.new("int32_t[?]", words) or nil
+    local planes = ffi.new("egg_cover_planes", { cover = cover, owner = owner })
+    local totals = ffi.new("egg_cover_totals")
+    if self:_check(lib.egg_cover(self._h, spec, planes, totals)) ~= 0 then return nil end
+    local function pair(a) return { tonumber(a[0]), tonumber(a[1]) } end
+    local covered, both, any = pair(totals.covered), tonumber(totals.covered_both), tonumber(totals.covered_any)
+    local a = cell * cell
+    return { nx = nx, ny = ny, cell = cell, cover = cover, owner = owner, inside = pair(totals.inside), outside = pair(totals.outside),
+             dropped = pair(totals.dropped), hits = pair(totals.hits), covered = covered, covered_both = both, covered_any = any,
+             area = { covered[1] * a, covered[2] * a, both * a, any * a },
+             units_lanes = totals.units_lanes, units_wave = totals.units_wave, units_direct = totals.units_direct }
+end
+
 -- Not in the reference, which has no forces as it has no boundary: force fields of the relaxed step (egg_set_forces in
 -- include/eggsim.h; DESIGN.md section 2.7, "Forces").  Relaxed order only.
 local _force_kinds = { uniform = 0, radial = 1, vortex = 2 }

@@ -51,7 +51,9 @@ import warnings
 import numpy as np
 
 from . import _ffi
-from .simulation_handler import EggError, EggWarning, Field, _HandlerSurface, _assert_types, _is_nan
+from .simulation_handler import Cover, EggError, EggWarning, Field, _HandlerSurface, _assert_types, _is_nan
+
+_COVER_NO_OWNER = 1 << 62  # "no disc here" in an owner plane while the ranks merge it: above every id
 
 
 class SlabConflict(RuntimeError):
@@ -789,6 +791,36 @@ class ShardedSimulationHandler(_HandlerSurface):
         count, svx, svy, flat = planes
         flat = flat.tolist()
         return Field(count.astype(np.int32), svx, svy, tuple(flat[0:2]), tuple(flat[2:4]), tuple(flat[4:6]), flat[6], flat[7])
+
+    def cover(self, origin, cell, shape, scale=1.0, types="both", owner=False, path="auto"):
+        """SimulationHandler.cover over all ranks (a collective: every rank calls it with the same grid).  Every rank rasters
+        the particles it owns; one all_reduce(SUM) adds the cover plane and the additive totals, one all_reduce(MIN) merges
+        the owner plane -- taken as keys (the global id of a batch is the key its rank's handle holds), "none" mapped to the
+        largest value -- and covered, covered_both and
+        covered_any are recounted locally from the merged plane: one handle's answer, bit for bit (units_* count the ranks'
+        units).  Nothing travels in a step.  There is no cover_to here: the planes of the ranks live on different devices."""
+        spec = self._c_cover_spec(origin, cell, shape, scale, types, path)
+        spec.path |= _ffi.COVER_OWNER_KEYS
+        plane, own, t = self.local._cover_planes(spec, bool(owner))
+        flat = list(t.inside) + list(t.outside) + list(t.dropped) + list(t.hits) + [t.units_lanes, t.units_wave, t.units_direct]
+        both = self._all_reduce_sum(np.concatenate([plane.ravel().astype(np.int64), np.array(flat, dtype=np.int64)]))
+        plane, flat = both[:plane.size].reshape(plane.shape).astype(np.int32), both[plane.size:].tolist()
+        if own is not None:
+            own = self._all_reduce_min(np.where(own < 0, _COVER_NO_OWNER, own.astype(np.int64)))
+            own = np.where(own == _COVER_NO_OWNER, -1, own).astype(np.int32)
+        a, b = plane[0] > 0, plane[1] > 0
+        return Cover(plane, own, spec.cell, tuple(flat[0:2]), tuple(flat[2:4]), tuple(flat[4:6]), tuple(flat[6:8]), (int(a.sum()), int(b.sum())),
+                     int((a & b).sum()), int((a | b).sum()), flat[8], flat[9], flat[10])
+
+    def _all_reduce_min(self, values):
+        """`values`, an int64 numpy array, merged over the ranks by minimum: ONE all_reduce(MIN) of an int64 tensor on
+        self.device (a collective).  A one-rank object gets its own values back and needs no process group."""
+        values = np.ascontiguousarray(values, dtype=np.int64)
+        if self.world == 1 or values.size == 0:
+            return values
+        low = self.torch.from_numpy(values).to(self.device)
+        self.dist.all_reduce(low, op=self.dist.ReduceOp.MIN)
+        return low.cpu().numpy()
 
     def pieces(self, ids=None, reach=None, types="both"):
         """SimulationHandler.pieces over all ranks (a collective: every rank calls it with the same arguments).  A batch lives

@@ -173,6 +173,30 @@ class Measure(collections.namedtuple("Measure", _ffi.MEASURE_FIELDS)):
         return (math.sqrt(max(half + root, 0.0)), math.sqrt(max(half - root, 0.0)), 0.5 * math.atan2(2.0 * cxy, cxx - cyy))
 
 
+class Cover(collections.namedtuple("Cover", "cover owner cell inside outside dropped hits covered covered_both covered_any "
+                                   "units_lanes units_wave units_direct")):
+    """The particles' discs rastered into a grid (egg_cover): `cover` an int32 numpy plane of shape (2, ny, nx), [0] white and
+    [1] yolk, the number of discs over each cell's centre; `owner` the smallest batch id among them, -1 where there is none
+    (None without owner=True); `cell` the side of a cell; `inside`, `outside`, `dropped`, `hits`, `covered` the (white, yolk)
+    particles by fate, covered (disc, cell) pairs and covered cells; `covered_both`, `covered_any` the cells under both types
+    and under either; `units_lanes`, `units_wave`, `units_direct` how the device did the work."""
+    __slots__ = ()
+
+    def area(self):
+        """the covered area in px^2 as (white, yolk, both, any): cells * cell * cell"""
+        a = self.cell * self.cell
+        return (self.covered[0] * a, self.covered[1] * a, self.covered_both * a, self.covered_any * a)
+
+    def depth(self):
+        """the mean number of discs over a covered cell as (white, yolk): hits / covered, NaN where nothing is covered"""
+        return tuple(h / c if c else float("nan") for h, c in zip(self.hits, self.covered))
+
+
+# what egg_cover_to reports beside the planes it fills on the device: Cover without its planes
+CoverTotals = collections.namedtuple("CoverTotals", "cell inside outside dropped hits covered covered_both covered_any "
+                                                    "units_lanes units_wave units_direct")
+
+
 class EggWarning(UserWarning):
     """The reference's `log.warning` (a line on stderr)."""
 
@@ -796,6 +820,65 @@ class _HandlerSurface:
         spec = self._c_field_spec(origin, cell, shape, types, path)
         count, svx, svy, t = self._field_planes(spec, bool(velocity))
         return Field(count, svx, svy, tuple(t.inside), tuple(t.outside), tuple(t.dropped), t.units_tiled, t.units_direct)
+
+    # ------------------------------------------------ cover (egg_cover)
+    @staticmethod
+    def _c_cover_spec(origin, cell, shape, scale, types, path, what="cover"):
+        """the grid of a call as an egg_cover_spec; what only the host can check (shapes, names, types) is checked here,
+        before any call into the library, the values by the library as well"""
+        def pair(v, name, names):
+            v = tuple(v) if isinstance(v, (tuple, list, np.ndarray)) else ()
+            if len(v) != 2:
+                raise EggError("%s: %s must be (%s), not %r" % (what, name, names, v if v else None))
+            return v
+        x0, y0 = pair(origin, "origin", "x0, y0")
+        nx, ny = pair(shape, "shape", "nx, ny")
+        try:
+            x0, y0, cell, scale = float(x0), float(y0), float(cell), float(scale)
+        except (TypeError, ValueError):
+            raise EggError("%s: origin, cell and scale must be numbers" % what) from None
+        for v in (nx, ny):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise EggError("%s: shape must be two integers (nx, ny), not %r" % (what, (nx, ny)))
+        nx, ny = int(nx), int(ny)
+        if nx < 1 or ny < 1 or nx * ny > _ffi.COVER_MAX_CELLS:
+            raise EggError("%s: shape (%d, %d): nx and ny are at least 1 and nx * ny at most %d" % (what, nx, ny, _ffi.COVER_MAX_CELLS))
+        if not (math.isfinite(cell) and cell > 0.0 and math.isfinite(1.0 / cell)):
+            raise EggError("%s: cell must be finite and above 0, with a finite inverse, not %r" % (what, cell))
+        if not (math.isfinite(x0) and math.isfinite(y0)):
+            raise EggError("%s: origin (%r, %r) is not finite" % (what, x0, y0))
+        if not (math.isfinite(scale) and scale > 0.0):
+            raise EggError("%s: scale must be finite and above 0, not %r" % (what, scale))
+        mask = _HandlerSurface._probe_mask(types, what)
+        if not isinstance(path, str) or path not in _ffi.COVER_PATHS:
+            raise EggError("%s: path must be 'auto', 'direct', 'lanes' or 'wave', not %r" % (what, path))
+        return _ffi.EggCoverSpec(x0, y0, cell, scale, nx, ny, mask, _ffi.COVER_PATHS[path])
+
+    def _cover_planes(self, spec, owner):
+        """one call of this object's entry point into fresh numpy planes: (cover, owner, totals)"""
+        cover = np.zeros((2, spec.ny, spec.nx), dtype=np.int32)
+        own = np.zeros((2, spec.ny, spec.nx), dtype=np.int32) if owner else None
+        planes = _ffi.EggCoverPlanes(cover.ctypes.data, own.ctypes.data if owner else None)
+        totals = _ffi.EggCoverTotals()
+        self._check(self._c("cover")(C.byref(spec), C.byref(planes), C.byref(totals)))
+        return cover, own, totals
+
+    @staticmethod
+    def _cover_totals(spec, t):
+        return (spec.cell, tuple(t.inside), tuple(t.outside), tuple(t.dropped), tuple(t.hits), tuple(t.covered), t.covered_both, t.covered_any,
+                t.units_lanes, t.units_wave, t.units_direct)
+
+    def cover(self, origin, cell, shape, scale=1.0, types="both", owner=False, path="auto"):
+        """The floor under the egg (either solver order): every committed particle's disc of radius
+        `scale * radius` rastered into the grid of `shape = (nx, ny)` square cells of side `cell` whose cell (0, 0) has its
+        lower corner at `origin = (x0, y0)`.  Returns a `Cover`: `cover` an int32 plane of shape (2, ny, nx), [0] white and [1]
+        yolk, counting the discs over each cell's CENTRE; with `owner=True` also the smallest batch id among them (-1: none);
+        the totals, and `Cover.area()` in px^2.  scale = 1 is the simulated disc, 12 the disc as it is drawn; a disc of more
+        than 64 cells in radius is dropped.  types = "both" | "white" | "yolk"; path = "direct" | "lanes" | "wave" are test
+        hooks with the same planes.  Reads the committed state; stores nothing.  Raises EggError for a bad grid."""
+        spec = self._c_cover_spec(origin, cell, shape, scale, types, path)
+        cover, own, t = self._cover_planes(spec, bool(owner))
+        return Cover(cover, own, *self._cover_totals(spec, t))
 
     # ------------------------------------------------ pieces (egg_pieces, DESIGN.md section 2.11)
     def _c_pieces_spec(self, reach, types, what="pieces"):
@@ -1923,6 +2006,36 @@ class SimulationHandler(_HandlerSurface):
         t = _ffi.EggFieldTotals()
         self._check(self._lib.egg_field_to(self._h, C.byref(spec), C.byref(planes), C.byref(t)))
         return FieldTotals(tuple(t.inside), tuple(t.outside), tuple(t.dropped), t.units_tiled, t.units_direct)
+
+    # ------------------------------------------- cover into planes on the device (egg_cover_to)
+    def cover_to(self, origin, cell, shape, cover, owner=None, scale=1.0, types="both", path="auto"):
+        """cover() into caller-owned planes on this handle's device: `cover` and, if wanted, `owner` int32 planes of shape
+        (2, ny, nx), contiguous, given as objects with `data_ptr()` (a torch tensor) or as addresses.  The call zeroes and
+        presets them itself and they are complete when it returns; nothing but the totals is copied to the host.  Returns
+        `CoverTotals`.  (A process that uses torch tensors imports torch before this package loads its library.)"""
+        spec = self._c_cover_spec(origin, cell, shape, scale, types, path, "cover_to")
+        if cover is None:
+            raise EggError("cover_to: cover is required")
+        words = 2 * spec.nx * spec.ny
+
+        def address(plane, what):
+            if plane is None:
+                return None
+            if hasattr(plane, "data_ptr"):
+                if str(getattr(plane, "dtype", "int32")).split(".")[-1] != "int32":
+                    raise EggError("cover_to: %s must hold int32, not %s" % (what, plane.dtype))
+                if hasattr(plane, "numel") and plane.numel() != words:
+                    raise EggError("cover_to: %s must hold 2 x %d x %d elements, not %d" % (what, spec.ny, spec.nx, plane.numel()))
+                if hasattr(plane, "is_contiguous") and not plane.is_contiguous():
+                    raise EggError("cover_to: %s must be contiguous" % what)
+                plane = plane.data_ptr()
+            if isinstance(plane, bool) or not isinstance(plane, (int, np.integer)) or int(plane) <= 0:
+                raise EggError("cover_to: %s must be an object with data_ptr() or an address, not %r" % (what, plane))
+            return int(plane)
+        planes = _ffi.EggCoverPlanes(address(cover, "cover"), address(owner, "owner"))
+        t = _ffi.EggCoverTotals()
+        self._check(self._lib.egg_cover_to(self._h, C.byref(spec), C.byref(planes), C.byref(t)))
+        return CoverTotals(*self._cover_totals(spec, t))
 
     # ------------------------------------------- measures into a table on the device (egg_measure_to)
     def measure_to(self, out, ids=None, region=None, types="both"):

@@ -1381,6 +1381,10 @@ int egg_draw_source_instances(egg_handle *h, int which, egg_instance *data, floa
  * Three more entry points, their spec and their record, in a header of their own as well. */
 #include "eggsim_measure.h"
 
+/* ---- cover: the particles' discs rastered into a grid -- area, depth, owner map: include/eggsim_cover.h ----
+ * Three more entry points, their spec, planes and totals, in a header of their own as well. */
+#include "eggsim_cover.h"
+
 #ifdef __cplusplus
 }
 #endif
