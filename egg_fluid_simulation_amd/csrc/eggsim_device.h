@@ -327,15 +327,6 @@ struct EggRxCohesionFields {
     int32_t *stag;                       // [n + ghost capacity] tag of a grouped slot, next to spos / swr
     unsigned long long *solves;          // one word: pairs whose cohesion branch fired in this step
 };
-struct EggRelaxedCohArgs {
-    EggRelaxedArgs a;
-    EggRxCohesionFields c;
-};
-struct EggRelaxedGroupCohArgs {
-    EggRelaxedArgs a;
-    EggRxGroupFields g;
-    EggRxCohesionFields c;
-};
 
 // Static colliders (egg_set_colliders, DESIGN.md section 2.7, "Colliders"): the collider instantiations of the gather
 // kernel (egg_rx_gather*_col_kernel) take these besides.  The list is the handle's, in a small device buffer written when
@@ -356,26 +347,6 @@ struct EggRxColliderFields {
     int32_t type_bit;                    // 1 white, 2 yolk: a collider applies when its type_mask has the bit
     unsigned long long *hits;            // one word: (collider, particle, pass) triples that moved a particle in this step
 };
-struct EggRelaxedColArgs {
-    EggRelaxedArgs a;
-    EggRxColliderFields d;
-};
-struct EggRelaxedGroupColArgs {
-    EggRelaxedArgs a;
-    EggRxGroupFields g;
-    EggRxColliderFields d;
-};
-struct EggRelaxedCohColArgs {
-    EggRelaxedArgs a;
-    EggRxCohesionFields c;
-    EggRxColliderFields d;
-};
-struct EggRelaxedGroupCohColArgs {
-    EggRelaxedArgs a;
-    EggRxGroupFields g;
-    EggRxCohesionFields c;
-    EggRxColliderFields d;
-};
 
 // Collider surfaces (egg_set_collider_surfaces, DESIGN.md section 2.7, "Collider surfaces"): the surface instantiations of
 // the gather kernel (egg_rx_gather*_col_srf_kernel) take these besides the collider fields.  The records are parallel to
@@ -390,30 +361,6 @@ struct EggRxSurfaceFields {
     double sub_delta;                    // h of step 5c
     unsigned long long *grips;           // one word: friction applications (stick or slide) in this step
 };
-struct EggRelaxedColSrfArgs {
-    EggRelaxedArgs a;
-    EggRxColliderFields d;
-    EggRxSurfaceFields s;
-};
-struct EggRelaxedGroupColSrfArgs {
-    EggRelaxedArgs a;
-    EggRxGroupFields g;
-    EggRxColliderFields d;
-    EggRxSurfaceFields s;
-};
-struct EggRelaxedCohColSrfArgs {
-    EggRelaxedArgs a;
-    EggRxCohesionFields c;
-    EggRxColliderFields d;
-    EggRxSurfaceFields s;
-};
-struct EggRelaxedGroupCohColSrfArgs {
-    EggRelaxedArgs a;
-    EggRxGroupFields g;
-    EggRxCohesionFields c;
-    EggRxColliderFields d;
-    EggRxSurfaceFields s;
-};
 
 // Collider motion (egg_set_collider_motion, DESIGN.md section 2.7, "Collider motion"): the motion instantiations of the
 // gather kernel (egg_rx_gather*_col_mov_kernel) take these besides the collider and surface fields.  The records are
@@ -426,34 +373,6 @@ struct EggMotion {
 struct EggRxMotionFields {
     const EggMotion *list;               // [the collider count]; every lane reads the same record
     double t;                            // the end of the pass's sub-step, from the start of the step: (sub + 1) * sub_delta
-};
-struct EggRelaxedColMovArgs {
-    EggRelaxedArgs a;
-    EggRxColliderFields d;
-    EggRxSurfaceFields s;
-    EggRxMotionFields m;
-};
-struct EggRelaxedGroupColMovArgs {
-    EggRelaxedArgs a;
-    EggRxGroupFields g;
-    EggRxColliderFields d;
-    EggRxSurfaceFields s;
-    EggRxMotionFields m;
-};
-struct EggRelaxedCohColMovArgs {
-    EggRelaxedArgs a;
-    EggRxCohesionFields c;
-    EggRxColliderFields d;
-    EggRxSurfaceFields s;
-    EggRxMotionFields m;
-};
-struct EggRelaxedGroupCohColMovArgs {
-    EggRelaxedArgs a;
-    EggRxGroupFields g;
-    EggRxCohesionFields c;
-    EggRxColliderFields d;
-    EggRxSurfaceFields s;
-    EggRxMotionFields m;
 };
 
 // Collider spin (egg_set_collider_spin, DESIGN.md section 2.7, "Collider spin"): the spin instantiations of the gather
@@ -470,38 +389,6 @@ struct EggRxSpinFields {
     const double2 *cs;                   // [the collider count]: (cos, sin)(t omega), t the end of the pass's sub-step
     const double2 *hcs;                  // [the collider count]: (cos, sin)(h omega), one sub-step's turn
     double ts;                           // the start of the pass's sub-step, from the start of the step: sub * sub_delta
-};
-struct EggRelaxedColSpinArgs {
-    EggRelaxedArgs a;
-    EggRxColliderFields d;
-    EggRxSurfaceFields s;
-    EggRxMotionFields m;
-    EggRxSpinFields r;
-};
-struct EggRelaxedGroupColSpinArgs {
-    EggRelaxedArgs a;
-    EggRxGroupFields g;
-    EggRxColliderFields d;
-    EggRxSurfaceFields s;
-    EggRxMotionFields m;
-    EggRxSpinFields r;
-};
-struct EggRelaxedCohColSpinArgs {
-    EggRelaxedArgs a;
-    EggRxCohesionFields c;
-    EggRxColliderFields d;
-    EggRxSurfaceFields s;
-    EggRxMotionFields m;
-    EggRxSpinFields r;
-};
-struct EggRelaxedGroupCohColSpinArgs {
-    EggRelaxedArgs a;
-    EggRxGroupFields g;
-    EggRxCohesionFields c;
-    EggRxColliderFields d;
-    EggRxSurfaceFields s;
-    EggRxMotionFields m;
-    EggRxSpinFields r;
 };
 
 // Collider loads (egg_set_collider_loads, DESIGN.md section 2.7, "Collider loads"): the loads instantiations of the gather
@@ -520,42 +407,6 @@ struct EggRxLoadFields {
     int32_t moving;                      // a collider motion of the handle is not zero: the motion rule runs
     int32_t turning;                     // a collider spin of the handle is not zero: the spin rule runs for such a collider
     int32_t pivots;                      // the handle holds spin records: the torque is about them (else about the origin)
-};
-struct EggRelaxedColLoadArgs {
-    EggRelaxedArgs a;
-    EggRxColliderFields d;
-    EggRxSurfaceFields s;
-    EggRxMotionFields m;
-    EggRxSpinFields r;
-    EggRxLoadFields l;
-};
-struct EggRelaxedGroupColLoadArgs {
-    EggRelaxedArgs a;
-    EggRxGroupFields g;
-    EggRxColliderFields d;
-    EggRxSurfaceFields s;
-    EggRxMotionFields m;
-    EggRxSpinFields r;
-    EggRxLoadFields l;
-};
-struct EggRelaxedCohColLoadArgs {
-    EggRelaxedArgs a;
-    EggRxCohesionFields c;
-    EggRxColliderFields d;
-    EggRxSurfaceFields s;
-    EggRxMotionFields m;
-    EggRxSpinFields r;
-    EggRxLoadFields l;
-};
-struct EggRelaxedGroupCohColLoadArgs {
-    EggRelaxedArgs a;
-    EggRxGroupFields g;
-    EggRxCohesionFields c;
-    EggRxColliderFields d;
-    EggRxSurfaceFields s;
-    EggRxMotionFields m;
-    EggRxSpinFields r;
-    EggRxLoadFields l;
 };
 
 // Collider bodies (egg_set_collider_bodies, DESIGN.md section 2.7, "Collider bodies"): egg_rx_bodies_kernel runs once per
@@ -615,15 +466,6 @@ struct EggRxForceFields {
     int32_t count;
     int32_t type_bit;                    // 1 white, 2 yolk: a field acts when its type_mask has the bit
 };
-struct EggRelaxedFrcArgs {
-    EggRelaxedArgs a;
-    EggRxForceFields f;
-};
-struct EggRelaxedGroupFrcArgs {
-    EggRelaxedArgs a;
-    EggRxGroupFields g;
-    EggRxForceFields f;
-};
 
 // Viscosity (egg_set_viscosity, DESIGN.md section 2.7, "Viscosity"): one more pass per sub-step, after its last collision
 // pass.  insert / scan / scatter are the collision pass's; the viscous rank kernel (egg_rx_rank*_visc_kernel) writes every
@@ -633,15 +475,73 @@ struct EggRxViscFields {
     double c;                            // the type's coefficient, in (0, 1]
     unsigned long long *pairs;           // one word: distinct pairs within the cell size, over the step's viscosity passes
 };
-struct EggRelaxedViscArgs {
+
+// The ONE argument record of every flavoured kernel of a pass: the base arguments and every field group above.  A kernel
+// reads the groups its row below names and nothing else; a group the step's switches leave off stays zero, and a field
+// no kernel reads costs the device nothing.  (g.gwr in a viscosity pass: the ghosts' u.)
+struct EggRxPassArgs {
     EggRelaxedArgs a;
+    EggRxGroupFields g;
+    EggRxCohesionFields c;
+    EggRxColliderFields d;
+    EggRxSurfaceFields s;
+    EggRxMotionFields m;
+    EggRxSpinFields r;
+    EggRxLoadFields l;
+    EggRxForceFields f;
     EggRxViscFields v;
 };
-struct EggRelaxedGroupViscArgs {
-    EggRelaxedArgs a;
-    EggRxGroupFields g;  // (gwr: the ghosts' u)
-    EggRxViscFields v;
+static_assert(sizeof(EggRxPassArgs) <= 4096, "a kernel's arguments are limited to 4 KB");
+
+// The flavour of a collision pass's gather, by what the handle's collider list asks for; a later one includes the rules of
+// the ones before it, and the loads flavour stands in for all of them.
+enum EggRxFlavour {
+    EGG_RX_NONE, EGG_RX_COL, EGG_RX_SRF, EGG_RX_WALL, EGG_RX_MOV, EGG_RX_SPIN, EGG_RX_LOAD, EGG_RX_FLAVOURS
 };
+
+// The ONE list of the flavoured kernels; each takes EggRxPassArgs A.  Their definitions (eggsim_relaxed.hip), their
+// declarations and the host's table of gathers (eggsim_host.h) are expansions of it.
+//   GATHER(name, G, K, flavour, D, S, W, Mo, Sp, Ld): rx_gather<G, K, D, S, W> with the group fields (G), the cohesion
+//     fields (K), the collider fields (D) and the surface fields (S) of A -- an empty constant where the column is 0 -- and
+//     with &A.m (Mo), &A.r (Sp), &A.l (Ld) -- null where the column is 0.  The host launches table[G][K][flavour].
+//   OTHER(name, call): the kernel's body is the call.
+#define EGG_RX_PASS_KERNELS(GATHER, OTHER)                                                                            \
+    GATHER(egg_rx_gather_kernel,                     0, 0, EGG_RX_NONE, 0, 0, 0, 0, 0, 0)                              \
+    GATHER(egg_rx_gather_group_kernel,               1, 0, EGG_RX_NONE, 0, 0, 0, 0, 0, 0)                              \
+    GATHER(egg_rx_gather_coh_kernel,                 0, 1, EGG_RX_NONE, 0, 0, 0, 0, 0, 0)                              \
+    GATHER(egg_rx_gather_group_coh_kernel,           1, 1, EGG_RX_NONE, 0, 0, 0, 0, 0, 0)                              \
+    GATHER(egg_rx_gather_col_kernel,                 0, 0, EGG_RX_COL,  1, 0, 0, 0, 0, 0)                              \
+    GATHER(egg_rx_gather_group_col_kernel,           1, 0, EGG_RX_COL,  1, 0, 0, 0, 0, 0)                              \
+    GATHER(egg_rx_gather_coh_col_kernel,             0, 1, EGG_RX_COL,  1, 0, 0, 0, 0, 0)                              \
+    GATHER(egg_rx_gather_group_coh_col_kernel,       1, 1, EGG_RX_COL,  1, 0, 0, 0, 0, 0)                              \
+    GATHER(egg_rx_gather_col_srf_kernel,             0, 0, EGG_RX_SRF,  1, 1, 0, 0, 0, 0)                              \
+    GATHER(egg_rx_gather_group_col_srf_kernel,       1, 0, EGG_RX_SRF,  1, 1, 0, 0, 0, 0)                              \
+    GATHER(egg_rx_gather_coh_col_srf_kernel,         0, 1, EGG_RX_SRF,  1, 1, 0, 0, 0, 0)                              \
+    GATHER(egg_rx_gather_group_coh_col_srf_kernel,   1, 1, EGG_RX_SRF,  1, 1, 0, 0, 0, 0)                              \
+    GATHER(egg_rx_gather_col_wall_kernel,            0, 0, EGG_RX_WALL, 1, 1, 1, 0, 0, 0)                              \
+    GATHER(egg_rx_gather_group_col_wall_kernel,      1, 0, EGG_RX_WALL, 1, 1, 1, 0, 0, 0)                              \
+    GATHER(egg_rx_gather_coh_col_wall_kernel,        0, 1, EGG_RX_WALL, 1, 1, 1, 0, 0, 0)                              \
+    GATHER(egg_rx_gather_group_coh_col_wall_kernel,  1, 1, EGG_RX_WALL, 1, 1, 1, 0, 0, 0)                              \
+    GATHER(egg_rx_gather_col_mov_kernel,             0, 0, EGG_RX_MOV,  1, 1, 1, 1, 0, 0)                              \
+    GATHER(egg_rx_gather_group_col_mov_kernel,       1, 0, EGG_RX_MOV,  1, 1, 1, 1, 0, 0)                              \
+    GATHER(egg_rx_gather_coh_col_mov_kernel,         0, 1, EGG_RX_MOV,  1, 1, 1, 1, 0, 0)                              \
+    GATHER(egg_rx_gather_group_coh_col_mov_kernel,   1, 1, EGG_RX_MOV,  1, 1, 1, 1, 0, 0)                              \
+    GATHER(egg_rx_gather_col_spin_kernel,            0, 0, EGG_RX_SPIN, 1, 1, 1, 1, 1, 0)                              \
+    GATHER(egg_rx_gather_group_col_spin_kernel,      1, 0, EGG_RX_SPIN, 1, 1, 1, 1, 1, 0)                              \
+    GATHER(egg_rx_gather_coh_col_spin_kernel,        0, 1, EGG_RX_SPIN, 1, 1, 1, 1, 1, 0)                              \
+    GATHER(egg_rx_gather_group_coh_col_spin_kernel,  1, 1, EGG_RX_SPIN, 1, 1, 1, 1, 1, 0)                              \
+    GATHER(egg_rx_gather_col_load_kernel,            0, 0, EGG_RX_LOAD, 1, 1, 1, 1, 1, 1)                              \
+    GATHER(egg_rx_gather_group_col_load_kernel,      1, 0, EGG_RX_LOAD, 1, 1, 1, 1, 1, 1)                              \
+    GATHER(egg_rx_gather_coh_col_load_kernel,        0, 1, EGG_RX_LOAD, 1, 1, 1, 1, 1, 1)                              \
+    GATHER(egg_rx_gather_group_coh_col_load_kernel,  1, 1, EGG_RX_LOAD, 1, 1, 1, 1, 1, 1)                              \
+    OTHER(egg_rx_rank_coh_kernel,         rx_rank<false, true>(A.a, EggRxGroupFields{}, A.c))                          \
+    OTHER(egg_rx_rank_group_coh_kernel,   rx_rank<true, true>(A.a, A.g, A.c))                                          \
+    OTHER(egg_rx_begin_frc_kernel,        rx_begin<false, true>(A.a, EggRxGroupFields{}, A.f))                         \
+    OTHER(egg_rx_begin_group_frc_kernel,  rx_begin<true, true>(A.a, A.g, A.f))                                         \
+    OTHER(egg_rx_mid_frc_kernel,          rx_mid<false, true>(A.a, EggRxGroupFields{}, A.f))                           \
+    OTHER(egg_rx_mid_group_frc_kernel,    rx_mid<true, true>(A.a, A.g, A.f))                                           \
+    OTHER(egg_rx_gather_visc_kernel,      rx_gather_visc<false>(A.a, EggRxGroupFields{}, A.v))                         \
+    OTHER(egg_rx_gather_group_visc_kernel, rx_gather_visc<true>(A.a, A.g, A.v))
 
 // White-yolk coupling (egg_set_coupling, DESIGN.md section 2.7, "Coupling"): one cross-type pass per sub-step, before its
 // first collision pass.  Both types build their cell table at the shared cell size H (insert / scan / scatter / rank are

@@ -81,56 +81,24 @@ extern "C" __global__ void egg_rx_end_kernel(EggRelaxedArgs A);
 extern "C" __global__ void egg_rx_insert_kernel(EggRelaxedArgs A);
 extern "C" __global__ void egg_rx_scatter_kernel(EggRelaxedArgs A);
 extern "C" __global__ void egg_rx_rank_kernel(EggRelaxedArgs A);
-extern "C" __global__ void egg_rx_gather_kernel(EggRelaxedArgs A);
 extern "C" __global__ void egg_rx_begin_group_kernel(EggRelaxedGroupArgs A);
 extern "C" __global__ void egg_rx_mid_group_kernel(EggRelaxedGroupArgs A);
 extern "C" __global__ void egg_rx_insert_group_kernel(EggRelaxedGroupArgs A);
 extern "C" __global__ void egg_rx_scatter_group_kernel(EggRelaxedGroupArgs A);
 extern "C" __global__ void egg_rx_rank_group_kernel(EggRelaxedGroupArgs A);
-extern "C" __global__ void egg_rx_gather_group_kernel(EggRelaxedGroupArgs A);
-extern "C" __global__ void egg_rx_rank_coh_kernel(EggRelaxedCohArgs A);
-extern "C" __global__ void egg_rx_gather_coh_kernel(EggRelaxedCohArgs A);
-extern "C" __global__ void egg_rx_rank_group_coh_kernel(EggRelaxedGroupCohArgs A);
-extern "C" __global__ void egg_rx_gather_group_coh_kernel(EggRelaxedGroupCohArgs A);
-extern "C" __global__ void egg_rx_gather_col_kernel(EggRelaxedColArgs A);
-extern "C" __global__ void egg_rx_gather_group_col_kernel(EggRelaxedGroupColArgs A);
-extern "C" __global__ void egg_rx_gather_coh_col_kernel(EggRelaxedCohColArgs A);
-extern "C" __global__ void egg_rx_gather_group_coh_col_kernel(EggRelaxedGroupCohColArgs A);
-extern "C" __global__ void egg_rx_gather_col_srf_kernel(EggRelaxedColSrfArgs A);
-extern "C" __global__ void egg_rx_gather_group_col_srf_kernel(EggRelaxedGroupColSrfArgs A);
-extern "C" __global__ void egg_rx_gather_coh_col_srf_kernel(EggRelaxedCohColSrfArgs A);
-extern "C" __global__ void egg_rx_gather_group_coh_col_srf_kernel(EggRelaxedGroupCohColSrfArgs A);
-extern "C" __global__ void egg_rx_gather_col_wall_kernel(EggRelaxedColSrfArgs A);
-extern "C" __global__ void egg_rx_gather_group_col_wall_kernel(EggRelaxedGroupColSrfArgs A);
-extern "C" __global__ void egg_rx_gather_coh_col_wall_kernel(EggRelaxedCohColSrfArgs A);
-extern "C" __global__ void egg_rx_gather_group_coh_col_wall_kernel(EggRelaxedGroupCohColSrfArgs A);
-extern "C" __global__ void egg_rx_gather_col_mov_kernel(EggRelaxedColMovArgs A);
-extern "C" __global__ void egg_rx_gather_group_col_mov_kernel(EggRelaxedGroupColMovArgs A);
-extern "C" __global__ void egg_rx_gather_coh_col_mov_kernel(EggRelaxedCohColMovArgs A);
-extern "C" __global__ void egg_rx_gather_group_coh_col_mov_kernel(EggRelaxedGroupCohColMovArgs A);
-extern "C" __global__ void egg_rx_gather_col_spin_kernel(EggRelaxedColSpinArgs A);
-extern "C" __global__ void egg_rx_gather_group_col_spin_kernel(EggRelaxedGroupColSpinArgs A);
-extern "C" __global__ void egg_rx_gather_coh_col_spin_kernel(EggRelaxedCohColSpinArgs A);
-extern "C" __global__ void egg_rx_gather_group_coh_col_spin_kernel(EggRelaxedGroupCohColSpinArgs A);
-extern "C" __global__ void egg_rx_gather_col_load_kernel(EggRelaxedColLoadArgs A);
-extern "C" __global__ void egg_rx_gather_group_col_load_kernel(EggRelaxedGroupColLoadArgs A);
-extern "C" __global__ void egg_rx_gather_coh_col_load_kernel(EggRelaxedCohColLoadArgs A);
-extern "C" __global__ void egg_rx_gather_group_coh_col_load_kernel(EggRelaxedGroupCohColLoadArgs A);
+// the flavoured kernels: the 28 gathers, the cohesive rank kernels, the force begin / mid kernels, the viscosity gathers
+#define EGG_RX_DECLARE(name, ...) extern "C" __global__ void name(EggRxPassArgs A);
+EGG_RX_PASS_KERNELS(EGG_RX_DECLARE, EGG_RX_DECLARE)
+#undef EGG_RX_DECLARE
 extern "C" __global__ void egg_rx_bodies_kernel(EggRxBodiesArgs A);
 extern "C" __global__ void egg_rx_contacts_kernel(EggRxContactsArgs A);
-extern "C" __global__ void egg_rx_begin_frc_kernel(EggRelaxedFrcArgs A);
-extern "C" __global__ void egg_rx_mid_frc_kernel(EggRelaxedFrcArgs A);
-extern "C" __global__ void egg_rx_begin_group_frc_kernel(EggRelaxedGroupFrcArgs A);
-extern "C" __global__ void egg_rx_mid_group_frc_kernel(EggRelaxedGroupFrcArgs A);
 extern "C" __global__ void egg_rx_rank_visc_kernel(EggRelaxedArgs A);
 extern "C" __global__ void egg_rx_rank_group_visc_kernel(EggRelaxedGroupArgs A);
-extern "C" __global__ void egg_rx_gather_visc_kernel(EggRelaxedViscArgs A);
 extern "C" __global__ void egg_rx_couple_kernel(EggRelaxedCoupleArgs K);
 extern "C" __global__ void egg_rx_couple_adh_kernel(EggRelaxedCoupleAdhArgs K);
 extern "C" __global__ void egg_rx_contain_sum_kernel(EggRxContainSumArgs K);
 extern "C" __global__ void egg_rx_contain_kernel(EggRxContainArgs K);
 extern "C" __global__ void egg_rx_contain_group_kernel(EggRxContainArgs K);
-extern "C" __global__ void egg_rx_gather_group_visc_kernel(EggRelaxedGroupViscArgs A);
 extern "C" __global__ void egg_rx_pack_visc_kernel(EggRxPackViscArgs P);
 extern "C" __global__ void egg_rx_wire_pack_visc_kernel(EggRxWirePackViscArgs P);
 extern "C" __global__ void egg_rx_gkey_kernel(const int32_t *, const int32_t *, const int32_t *, int, int32_t *);
@@ -534,7 +502,7 @@ struct egg_handle {
     double load_sub_delta = 0.0;
     // collider bodies (egg_set_collider_bodies; relaxed order, one handle only): the records as egg_get_collider_bodies
     // returns them, empty = none; bodies_any = some record frees a translation or a rotation.  A step in which bodies act
-    // (relaxed_step_bodies) puts the records, the row of turns and the sums the sub-step before has seen on the device, and
+    // (relaxed_step, bodies_act) puts the records, the row of turns and the sums the sub-step before has seen on the device, and
     // orders the two types' streams around the integrator with the two events (created by the first such step):
     // body_ready = the other type's last launch of the sub-step, body_done = the integrator of the sub-step
     std::vector<egg_collider_body> bodies;
@@ -855,16 +823,19 @@ struct RelaxedStep {  // one type of one handle in a relaxed step
     int w = 0, C = 0;
     Env env{};
     RelaxedLayout L;
-    EggRelaxedGroupArgs A{};  // (A.g stays null without a halo)
-    EggRxCohesionFields coh{};  // effective cohesion (L.cohesion): compliance and factor of the type, the tag arrays
-    EggRxColliderFields col{};  // static colliders (L.colliders): the handle's list, the type's bit, the hit counter
-    EggRxSurfaceFields srf{};   // collider surfaces (L.surfaces): the handle's records, the sub-step, the grip counter
-    EggRxMotionFields mov{};    // collider motion (L.motion or L.spin): the handle's records; launch_pass sets the pass's time
-    EggRxSpinFields spn{};      // collider spin (L.spin): the handle's records and table; launch_pass sets the pass's row
-    EggRxLoadFields lod{};      // collider loads (L.loads): the handle's sums, which rules the list's flavour runs
-    EggRxSurfaceFields lsrf{};  // ... and the surface fields the loads kernels read: srf, or the default records without a counter
-    EggRxForceFields frc{};     // force fields (L.forces): the handle's list, the type's bit
-    EggRxViscFields visc{};     // viscosity (L.V): the type's coefficient, the pair counter
+    // The one argument record (prepare_type fills it; a group whose switch is off stays zero):
+    //   A.a  the base arguments                     A.g  the halo's arrays (L.halo)
+    //   A.c  effective cohesion (L.cohesion): compliance and factor of the type, the tag arrays
+    //   A.d  static colliders (L.colliders): the handle's list, the type's bit, the hit counter
+    //   A.s  collider surfaces (L.surfaces, or L.loads): the handle's records, the sub-step, the grip counter
+    //   A.m  collider motion (L.motion or L.spin): the handle's records; launch_pass sets the pass's time
+    //   A.r  collider spin (L.spin): the handle's records and table; launch_pass sets the pass's row
+    //   A.l  collider loads (L.loads): the handle's sums, which rules the list's flavour runs
+    //   A.f  force fields (L.forces): the handle's list, the type's bit
+    //   A.v  viscosity (L.V): the type's coefficient, the pair counter
+    EggRxPassArgs A{};
+    EggRelaxedGroupArgs group_args() const { return EggRelaxedGroupArgs{A.a, A.g}; }  // what the unflavoured group kernels take
+    EggRxFlavour flavour = EGG_RX_NONE;  // of the collision passes' gather (prepare_type, from L)
     double couple_cell = 0, couple_c = 0;  // coupling (L.coupling): the shared cell size H, the compliance of the strength
     double adhesion_c = 0;                 // adhesion (L.adhesion): the compliance of its own strength
     int64_t ghost_cap = 0;    // a pass runs over n + ghost_cap entries

@@ -9,69 +9,63 @@
 //   relaxed_step (below)                                one handle, everything enqueued in one go
 //   relaxed_group_step (eggsim_host_relaxed_group.hip)  the handles of a device group; adds the peer halo between passes
 //   egg_rx_* (eggsim_host_relaxed_wire.hip)             one handle per process; the host carries the halo between calls
-// With a halo (RelaxedLayout::halo) the entries of a pass are the local particles plus ghosts and the kernels are the
-// group instantiations; without, the plain ones.  Nothing else differs, and the three paths agree bit for bit.
-// With effective cohesion (EGG_OPT_COHESION = 1, RelaxedLayout::cohesion) launch_pass picks the cohesive instantiations
-// of the rank and gather kernels and RelaxedStep::coh carries the type's compliance, factor and tag arrays; a step with
-// cohesion off launches what it always launched, so all three paths pick cohesion up from here.
-// With static colliders (egg_set_colliders, RelaxedLayout::colliders) launch_pass picks the collider instantiation of the
-// gather kernel and RelaxedStep::col carries the handle's list; with an empty list a step launches what it always launched.
-// With collider surfaces (egg_set_collider_surfaces, RelaxedLayout::surfaces) of which at least one has friction > 0
-// launch_pass picks the surface twin of the collider instantiation and RelaxedStep::srf carries the records; while every
-// friction is zero -- a surface velocity alone does nothing -- a step launches what it launches without surfaces.
-// While the list holds a wall (EGG_COLLIDER_WALL, RelaxedLayout::walls) launch_pass picks the wall twin of the surface
-// instantiation, whether or not a friction is set: RelaxedStep::srf is then always filled, and the handle's records on the
-// device hold one per collider, defaults included.  A list without a wall launches what it launched.
-// While a collider motion is not zero (egg_set_collider_motion, RelaxedLayout::motion) launch_pass picks the motion twin of
-// the instantiation with walls, whether or not the list holds a wall or a friction, and RelaxedStep::mov carries the
-// records and the end time of the pass's sub-step; relaxed_commit advances the handle's stored list by the step and marks
-// it dirty, so the next step's prepare_step rewrites its copy on the device.  With every motion zero a step launches what it launched, with the same arguments, and a commit
-// touches no list.
-// While a collider spin is not zero (egg_set_collider_spin, RelaxedLayout::spin) launch_pass picks the spin twin of the
-// motion instantiation, whether or not anything moves, and RelaxedStep::spn carries the records and the sub-step's row of
-// the table of sines and cosines prepare_step has computed with libm and copied to the device -- no launch of its own;
-// relaxed_commit advances the stored list and the stored pivots from the last row.  With every spin zero a step launches
-// what it launched, with the same arguments.
-// With collider loads on (egg_set_collider_loads, RelaxedLayout::loads) launch_pass picks the loads instantiation of the
-// gather in place of whichever collider flavour the list would launch, and RelaxedStep::lod tells it which of that
-// flavour's rules to run.  The sums live in a buffer of the handle that both types' streams add into: prepare_step clears
-// it before either stream has work, relaxed_commit reads it once every path has waited for both, and nothing else touches
-// it, so a failed step leaves the values of the step before.  With loads off a step launches what it launched, with the
-// same arguments.
-// While collider bodies act (egg_set_collider_bodies, RelaxedStep::bodies: some collider is a body, loads are on, the list is
-// not empty) relaxed_step_bodies drives the step: the loads instantiations run with every rule on, launch_pass poses every
-// sub-step as the first of a step over the records on the device, and after the last launch of a sub-step of both types one
-// launch of egg_rx_bodies_kernel rewrites those records from the sums the sub-step has added.  relaxed_commit reads them
-// back in place of advance_colliders; after a failed step the next one puts the host's copies back.  With no body a step enqueues and launches
-// what it always did.
-// While collider contacts act besides (egg_set_collider_contacts: bodies act and some record is on) every launch of the
-// integrator is followed, on the same stream and inside the same bracket of events, by one launch of
-// egg_rx_contacts_kernel (eggsim_relaxed_contacts.hip), which changes the velocities, spins and turns the integrator has
-// left.  prepare_step uploads the contact records and zeroes the word the kernel counts its fires in; relaxed_commit adds
-// that word to the handle's counter.  While contacts do not act a step launches what it launched, with the same arguments.
-// With force fields (egg_set_forces, RelaxedLayout::forces) launch_substep picks the force instantiation of the begin / mid
-// kernel and RelaxedStep::frc carries the handle's list; with an empty list a step launches what it always launched.
-// With viscosity (egg_set_viscosity, RelaxedLayout::V) every sub-step of a type whose coefficient is not zero ends with
-// launch_viscosity, one more pass of the driver -- insert, scan, scatter, the viscous rank kernel, the viscosity gather --
-// and the sub-step's last collision pass records the cell box that pass's halo needs; RelaxedStep::visc carries the
-// coefficient and the pair counter.  With both coefficients zero a step launches what it always launched.
-// With white-yolk coupling (egg_set_coupling, RelaxedLayout::coupling: factor > 0, both types populated, no halo) every
-// sub-step runs a cross-type pass between its begin / mid kernel and its first collision pass: launch_coupling_tables
-// builds the type's table at the shared cell size H, launch_coupling walks the OTHER type's table.  The two types run on
-// their own streams, so four events order them (built[w], read[w]), and relaxed_step enqueues sub-step by sub-step across
-// both types: a wait on an event that has not been recorded yet waits for nothing.  With the factor zero, or one type
-// empty, a step enqueues and launches what it always did.
-// With white-yolk adhesion acting (egg_set_adhesion, RelaxedLayout::adhesion: coupling, and reach > factor) the same
-// launches run in other instantiations: H covers the band, launch_coupling_tables ranks through the cohesive rank kernel,
-// which leaves the batch tags beside the grouped copies, and launch_coupling runs egg_rx_couple_adh_kernel.  No launch,
-// event or wait is added; with reach <= factor nothing changes at all.
-// With yolk containment acting (egg_set_containment, RelaxedLayout::containment: factor > 0 and both types populated, with
-// or without a halo) every sub-step runs two more launches between the coupling pass (or the begin / mid kernel) and the
-// first collision pass: launch_contain_sum on the white stream writes the sub-step's slice of the handle's summaries and
-// records the sub-step's event, launch_contain on the yolk stream waits for it and projects.  One slice and one event per
-// sub-step: every path enqueues the white's launches of a sub-step before the yolk's, so every event has been recorded
-// on the host before its wait is enqueued, and nothing is written while it may still be read.  With the factor zero, or
-// one type empty, a step enqueues and launches what it always did.
+// With a halo the entries of a pass are the local particles plus ghosts; nothing else differs, and the three paths agree
+// bit for bit.
+//
+// The step's switches (RelaxedLayout L and RelaxedStep, eggsim_host.h; prepare_type sets them).  With a switch off a step
+// enqueues and launches what it launched without it, with the same arguments; all three paths pick a switch up from here.
+// "Flavour" is the gather of a collision pass, table[halo][cohesion][flavour] over the one kernel list of eggsim_device.h; the
+// last column names the event or the status word the switch adds (words: RelaxedLayout).
+//
+// switch          on while                                      what it changes                                  adds
+// --------------  --------------------------------------------  -----------------------------------------------  ----------------------
+// L.halo          a group or wire step: ghosts of other         the group instantiations of every kernel; the     per pass a cell box, a
+//                 handles' particles take part                  entries of a pass are local particles + ghosts    ghost count, sent counts
+// L.cohesion      EGG_OPT_COHESION = 1 (effective)              the cohesive rank kernel and the cohesive row     word cohered()
+//                                                               of gathers; A.c: compliance, factor, tag arrays
+// L.colliders     egg_set_colliders: the list is not empty      flavour COL; A.d: the list, the type's bit        word hits()
+// L.surfaces      egg_set_collider_surfaces: a friction > 0     flavour SRF; A.s: the records (one per collider,  word grips()
+//                 (a surface velocity alone does nothing), or   defaults included, while walls, motion or spin)
+//                 walls, motion or spin
+// L.walls         the list holds an EGG_COLLIDER_WALL           flavour WALL, whether or not a friction is set    -
+// L.motion        egg_set_collider_motion: one is not zero      flavour MOV; A.m: the records and the end time    -
+//                                                               of the pass's sub-step; relaxed_commit advances
+//                                                               the stored list and marks it dirty
+// L.spin          egg_set_collider_spin: one is not zero        flavour SPIN; A.r: the records and the sub-step's -
+//                                                               row of the table of sines and cosines prepare_step
+//                                                               computes with libm and copies (no launch); the
+//                                                               commit advances the list and the pivots
+// L.loads         egg_set_collider_loads on, list not empty     flavour LOAD in place of whichever the list would -  (the sums have a
+//                                                               launch; A.l says which of its rules to run; A.s   buffer of the handle:
+//                                                               always filled (no grip word without surfaces)     cleared by prepare_step,
+//                                                                                                                 read by relaxed_commit)
+// st.bodies       egg_set_collider_bodies: a collider is a      the step is enqueued across both types; LOAD with events body_ready,
+//                 body, loads on, list not empty                every rule on; launch_pass poses every sub-step   body_done
+//                                                               as the first over the device's records; one
+//                                                               egg_rx_bodies_kernel per sub-step rewrites them;
+//                                                               the commit reads them back (take_bodies)
+// h->contacts_step  egg_set_collider_contacts: bodies act and   one egg_rx_contacts_kernel directly behind every  a counter word of the
+//                 a record is on                                integrator launch, same stream, same events       handle (take_contacts)
+// L.forces        egg_set_forces: the list is not empty         the force instantiation of begin / mid; A.f       -
+// L.V             egg_set_viscosity: the type's coefficient     launch_viscosity ends every sub-step: cell table, word visc(); with a halo
+//                 is not zero                                   viscous rank kernel, viscosity gather (5          V more halo passes
+//                                                               launches); A.v; the sub-step's last collision
+//                                                               pass records the box that pass's halo needs
+// L.coupling      egg_set_coupling: factor > 0, both types      the step is enqueued across both types; per       events built[w], read[w];
+//                 populated, no halo                            sub-step launch_coupling_tables (4 launches, the  word coupled() (white)
+//                                                               shared cell size H) and launch_coupling (1),
+//                                                               which walks the OTHER type's table
+// L.adhesion      egg_set_adhesion: coupling, reach > factor    the same launches in other instantiations: H      word adhered() (white)
+//                                                               covers the band, the tables rank through the
+//                                                               cohesive rank kernel, egg_rx_couple_adh_kernel
+// L.containment   egg_set_containment: factor > 0, both types   two launches per sub-step in front of its first   one event per sub-step
+//                 populated, with or without a halo             pass: launch_contain_sum (white stream, the       (contain_summed);
+//                                                               sub-step's slice of summaries), launch_contain    word contained() (yolk)
+//                                                               (yolk stream, waits for it and projects)
+//
+// Every path enqueues the white's launches of a sub-step before the yolk's, so every event has been recorded on the host
+// before its wait is enqueued -- a wait on an event that has not been recorded yet waits for nothing -- and nothing is
+// written while it may still be read.
 #include <hipcub/hipcub.hpp>
 
 #include "eggsim_host.h"
@@ -79,6 +73,21 @@
 namespace egghost {
 
 namespace {
+
+// the gathers of EGG_RX_PASS_KERNELS (eggsim_device.h) by [halo][cohesion][flavour]: every row of the list fills its one slot
+using RxPassKernel = void (*)(EggRxPassArgs);
+struct RxGatherTable {
+    RxPassKernel k[2][2][EGG_RX_FLAVOURS];
+};
+#define EGG_RX_SLOT(name, G, K, flavour, ...) t.k[G][K][flavour] = name;
+#define EGG_RX_NO_SLOT(name, ...)
+const RxGatherTable kRxGather = [] {
+    RxGatherTable t{};
+    EGG_RX_PASS_KERNELS(EGG_RX_SLOT, EGG_RX_NO_SLOT)
+    return t;
+}();
+#undef EGG_RX_SLOT
+#undef EGG_RX_NO_SLOT
 
 // buffers of one type for n particles and `ghosts` ghost entries; the cell table has at least 2 (n + ghosts) slots (a
 // probe always finds a free one); `words` status words
@@ -317,62 +326,56 @@ int prepare_type(RelaxedStep &st, int C, size_t ghosts, const RelaxedLayout &L, 
     int rc = reserve_relaxed(h, s, ghosts, st.L.words());
     if (rc == EGG_OK) rc = upload_relaxed_targets(h, s);
     if (rc != EGG_OK) return rc;
+    st.A = EggRxPassArgs{};
     st.A.a = relaxed_args(h, st.w, st.env);
-    st.A.g = EggRxGroupFields{};
-    st.coh = EggRxCohesionFields{};
+    // the gather's flavour: the loads instantiation stands in for every other; else the last switch on, which includes the ones before it
+    st.flavour = st.L.loads      ? EGG_RX_LOAD
+                 : st.L.spin     ? EGG_RX_SPIN
+                 : st.L.motion   ? EGG_RX_MOV
+                 : st.L.walls    ? EGG_RX_WALL
+                 : st.L.surfaces ? EGG_RX_SRF
+                 : st.L.colliders ? EGG_RX_COL
+                                  : EGG_RX_NONE;
     if (st.L.cohesion) {  // the tag of a particle without a halo is its atom; with one, the atom's key base (below)
         HIP_TRY(h, r.stag.reserve(n + ghosts, false, s.stream));
-        st.coh.compliance = st.env.cohesion_c;
-        st.coh.factor = s.cfg.cohesion_interaction_distance_factor;
-        st.coh.stag = r.stag.p;
-        st.coh.solves = r.status.p + st.L.cohered();
+        st.A.c.compliance = st.env.cohesion_c;
+        st.A.c.factor = s.cfg.cohesion_interaction_distance_factor;
+        st.A.c.stag = r.stag.p;
+        st.A.c.solves = r.status.p + st.L.cohered();
     }
-    st.col = EggRxColliderFields{};
     if (st.L.colliders) {
-        st.col.list = h->d_colliders.p;
-        st.col.count = (int32_t)h->colliders.size();
-        st.col.type_bit = 1 << st.w;
-        st.col.hits = r.status.p + st.L.hits();
+        st.A.d.list = h->d_colliders.p;
+        st.A.d.count = (int32_t)h->colliders.size();
+        st.A.d.type_bit = 1 << st.w;
+        st.A.d.hits = r.status.p + st.L.hits();
     }
-    st.srf = EggRxSurfaceFields{};
-    if (st.L.surfaces) {
-        st.srf.list = h->d_surfaces.p;
-        st.srf.sub_delta = st.env.sub_delta;
-        st.srf.grips = r.status.p + st.L.grips();
+    if (st.L.surfaces || st.L.loads) {  // (loads alone: the records as they are on the device: no friction, so no grip is ever counted)
+        st.A.s.list = h->d_surfaces.p;
+        st.A.s.sub_delta = st.env.sub_delta;
+        st.A.s.grips = st.L.surfaces ? r.status.p + st.L.grips() : nullptr;
     }
-    st.mov = EggRxMotionFields{};
-    if (st.L.motion || st.L.spin) st.mov.list = h->d_motions.p;
-    st.spn = EggRxSpinFields{};
+    if (st.L.motion || st.L.spin) st.A.m.list = h->d_motions.p;
     if (st.L.spin) {
-        st.spn.list = h->d_spins.p;
-        st.spn.hcs = h->d_spin_table.p + (L.P / (size_t)C) * h->colliders.size();  // (the row behind the sub-steps')
+        st.A.r.list = h->d_spins.p;
+        st.A.r.hcs = h->d_spin_table.p + (L.P / (size_t)C) * h->colliders.size();  // (the row behind the sub-steps')
     }
-    st.lod = EggRxLoadFields{};
-    st.lsrf = st.srf;
     if (st.L.loads) {
-        st.lod.sums = h->d_loads.p;
-        st.lod.dropped = h->d_loads.p + 3 * h->colliders.size();
-        st.lod.eps = h->sys[0].cfg.eps;
-        st.lod.moving = st.L.motion ? 1 : 0;
-        st.lod.turning = st.L.spin ? 1 : 0;
-        st.lod.pivots = h->spins.empty() ? 0 : 1;
-        if (!st.L.surfaces) {  // the records as they are on the device: no friction, so no grip is ever counted
-            st.lsrf.list = h->d_surfaces.p;
-            st.lsrf.sub_delta = st.env.sub_delta;
-            st.lsrf.grips = nullptr;
-        }
-        if (st.lod.pivots && !st.L.spin) st.spn.list = h->d_spins.p;
+        st.A.l.sums = h->d_loads.p;
+        st.A.l.dropped = h->d_loads.p + 3 * h->colliders.size();
+        st.A.l.eps = h->sys[0].cfg.eps;
+        st.A.l.moving = st.L.motion ? 1 : 0;
+        st.A.l.turning = st.L.spin ? 1 : 0;
+        st.A.l.pivots = h->spins.empty() ? 0 : 1;
+        if (st.A.l.pivots && !st.L.spin) st.A.r.list = h->d_spins.p;
     }
-    st.frc = EggRxForceFields{};
     if (st.L.forces) {
-        st.frc.list = h->d_forces.p;
-        st.frc.count = (int32_t)h->forces.size();
-        st.frc.type_bit = 1 << st.w;
+        st.A.f.list = h->d_forces.p;
+        st.A.f.count = (int32_t)h->forces.size();
+        st.A.f.type_bit = 1 << st.w;
     }
-    st.visc = EggRxViscFields{};
     if (st.L.V) {
-        st.visc.c = h->viscosity[st.w];
-        st.visc.pairs = r.status.p + st.L.visc();
+        st.A.v.c = h->viscosity[st.w];
+        st.A.v.pairs = r.status.p + st.L.visc();
     }
     if (st.L.coupling) {  // both types share the cell size and the compliance
         const double widest = st.L.adhesion ? std::max(h->coupling_factor, h->adhesion_reach) : h->coupling_factor;
@@ -420,8 +423,8 @@ int prepare_type(RelaxedStep &st, int C, size_t ghosts, const RelaxedLayout &L, 
     st.A.g.gwr = r.gwr.p;
     if (st.L.cohesion) {
         HIP_TRY(h, r.gtag.reserve(std::max<size_t>(ghosts, 1), false, s.stream));
-        st.coh.atom_tag = r.abase.p;
-        st.coh.gtag = r.gtag.p;
+        st.A.c.atom_tag = r.abase.p;
+        st.A.c.gtag = r.gtag.p;
     }
     return EGG_OK;
 }
@@ -432,20 +435,39 @@ int launch_substep(RelaxedStep &st, int sub) {
     System &s = st.h->sys[st.w];
     const dim3 grid((unsigned)((s.n + 255) / 256)), block(256);
     if (sub == 0) HIP_TRY(st.h, hipMemsetAsync(s.rx.status.p, 0, st.L.words() * 8, s.stream));
-    if (st.L.halo) {
-        st.A.g.box = s.rx.status.p + st.L.box((size_t)sub * st.C);
-        if (st.L.forces)
-            hipLaunchKernelGGL(sub == 0 ? egg_rx_begin_group_frc_kernel : egg_rx_mid_group_frc_kernel, grid, block, 0, s.stream,
-                               EggRelaxedGroupFrcArgs{st.A.a, st.A.g, st.frc});
-        else
-            hipLaunchKernelGGL(sub == 0 ? egg_rx_begin_group_kernel : egg_rx_mid_group_kernel, grid, block, 0, s.stream, st.A);
-    } else if (st.L.forces) {
-        hipLaunchKernelGGL(sub == 0 ? egg_rx_begin_frc_kernel : egg_rx_mid_frc_kernel, grid, block, 0, s.stream,
-                           EggRelaxedFrcArgs{st.A.a, st.frc});
+    if (st.L.halo) st.A.g.box = s.rx.status.p + st.L.box((size_t)sub * st.C);
+    if (st.L.forces) {
+        const RxPassKernel frc[2][2] = {{egg_rx_mid_frc_kernel, egg_rx_begin_frc_kernel}, {egg_rx_mid_group_frc_kernel, egg_rx_begin_group_frc_kernel}};
+        hipLaunchKernelGGL(frc[st.L.halo][sub == 0], grid, block, 0, s.stream, st.A);
+    } else if (st.L.halo) {
+        hipLaunchKernelGGL(sub == 0 ? egg_rx_begin_group_kernel : egg_rx_mid_group_kernel, grid, block, 0, s.stream, st.group_args());
     } else {
         hipLaunchKernelGGL(sub == 0 ? egg_rx_begin_kernel : egg_rx_mid_kernel, grid, block, 0, s.stream, st.A.a);
     }
     ++st.launches;
+    return EGG_OK;
+}
+
+// The cell table of a pass over n + ghost_cap entries (the ghost count is read on the device) from the positions in
+// a.a.pos, at the cell size in a.a.cell_size: two memsets, insert, the scan of the counts, scatter.  With a halo the group
+// instantiations.  Two launches; the caller counts them with its own.
+static int launch_cell_table(RelaxedStep &st, const EggRxPassArgs &a, dim3 grid, dim3 block) {
+    egg_handle *h = st.h;
+    System &s = h->sys[st.w];
+    RelaxedBufs &r = s.rx;
+    const EggRelaxedGroupArgs ga{a.a, a.g};
+    HIP_TRY(h, hipMemsetAsync(r.hkey.p, 0xFF, (size_t)r.table * 8, s.stream));
+    HIP_TRY(h, hipMemsetAsync(r.hcount.p, 0, ((size_t)r.table + 1) * 4, s.stream));
+    if (st.L.halo)
+        hipLaunchKernelGGL(egg_rx_insert_group_kernel, grid, block, 0, s.stream, ga);
+    else
+        hipLaunchKernelGGL(egg_rx_insert_kernel, grid, block, 0, s.stream, a.a);
+    size_t bytes = r.scan_bytes;
+    HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(r.scan_tmp.p, bytes, r.hcount.p, r.hstart.p, (int)r.table + 1, s.stream));
+    if (st.L.halo)
+        hipLaunchKernelGGL(egg_rx_scatter_group_kernel, grid, block, 0, s.stream, ga);
+    else
+        hipLaunchKernelGGL(egg_rx_scatter_kernel, grid, block, 0, s.stream, a.a);
     return EGG_OK;
 }
 
@@ -457,7 +479,7 @@ int launch_pass(RelaxedStep &st, int p) {
     egg_handle *h = st.h;
     System &s = h->sys[st.w];
     RelaxedBufs &r = s.rx;
-    EggRelaxedGroupArgs &a = st.A;
+    EggRxPassArgs &a = st.A;
     a.a.pass = p;
     if (st.L.halo) {
         a.g.n_ghost = r.status.p + st.L.ghosts((size_t)p);
@@ -465,116 +487,26 @@ int launch_pass(RelaxedStep &st, int p) {
                   : st.L.V            ? r.status.p + st.L.box(st.L.P + (size_t)(p / st.C))
                                       : nullptr;
     }
-    if (st.L.motion || st.L.spin) st.mov.t = (double)(p / st.C + 1) * st.env.sub_delta;  // the end of the pass's sub-step
+    if (st.L.motion || st.L.spin) a.m.t = (double)(p / st.C + 1) * st.env.sub_delta;  // the end of the pass's sub-step
     if (st.L.spin) {
-        st.spn.cs = h->d_spin_table.p + (size_t)(p / st.C) * h->colliders.size();  // the sub-step's row
-        st.spn.ts = (double)(p / st.C) * st.env.sub_delta;                          // ... and its start
+        a.r.cs = h->d_spin_table.p + (size_t)(p / st.C) * h->colliders.size();  // the sub-step's row
+        a.r.ts = (double)(p / st.C) * st.env.sub_delta;                          // ... and its start
     }
     if (st.bodies) {  // every sub-step is the first of a step over the records the integrator has left on the device
-        st.mov.t = st.env.sub_delta;
-        st.spn.cs = h->d_body_cs.p;
-        st.spn.ts = 0.0;
+        a.m.t = st.env.sub_delta;
+        a.r.cs = h->d_body_cs.p;
+        a.r.ts = 0.0;
     }
     const dim3 grid((unsigned)((s.n + st.ghost_cap + 255) / 256)), block(256);  // (the ghost count is read on the device)
-    HIP_TRY(h, hipMemsetAsync(r.hkey.p, 0xFF, (size_t)r.table * 8, s.stream));
-    HIP_TRY(h, hipMemsetAsync(r.hcount.p, 0, ((size_t)r.table + 1) * 4, s.stream));
-    if (st.L.halo)
-        hipLaunchKernelGGL(egg_rx_insert_group_kernel, grid, block, 0, s.stream, a);
+    const int rc = launch_cell_table(st, a, grid, block);
+    if (rc != EGG_OK) return rc;
+    if (st.L.cohesion)
+        hipLaunchKernelGGL(st.L.halo ? egg_rx_rank_group_coh_kernel : egg_rx_rank_coh_kernel, grid, block, 0, s.stream, a);
+    else if (st.L.halo)
+        hipLaunchKernelGGL(egg_rx_rank_group_kernel, grid, block, 0, s.stream, st.group_args());
     else
-        hipLaunchKernelGGL(egg_rx_insert_kernel, grid, block, 0, s.stream, a.a);
-    size_t bytes = r.scan_bytes;
-    HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(r.scan_tmp.p, bytes, r.hcount.p, r.hstart.p, (int)r.table + 1, s.stream));
-    if (st.L.halo) {
-        hipLaunchKernelGGL(egg_rx_scatter_group_kernel, grid, block, 0, s.stream, a);
-        if (st.L.cohesion) {
-            const EggRelaxedGroupCohArgs k{a.a, a.g, st.coh};
-            hipLaunchKernelGGL(egg_rx_rank_group_coh_kernel, grid, block, 0, s.stream, k);
-            if (st.L.loads)
-                hipLaunchKernelGGL(egg_rx_gather_group_coh_col_load_kernel, grid, block, 0, s.stream,
-                                   EggRelaxedGroupCohColLoadArgs{a.a, a.g, st.coh, st.col, st.lsrf, st.mov, st.spn, st.lod});
-            else if (st.L.spin)
-                hipLaunchKernelGGL(egg_rx_gather_group_coh_col_spin_kernel, grid, block, 0, s.stream,
-                                   EggRelaxedGroupCohColSpinArgs{a.a, a.g, st.coh, st.col, st.srf, st.mov, st.spn});
-            else if (st.L.motion)
-                hipLaunchKernelGGL(egg_rx_gather_group_coh_col_mov_kernel, grid, block, 0, s.stream,
-                                   EggRelaxedGroupCohColMovArgs{a.a, a.g, st.coh, st.col, st.srf, st.mov});
-            else if (st.L.walls)
-                hipLaunchKernelGGL(egg_rx_gather_group_coh_col_wall_kernel, grid, block, 0, s.stream,
-                                   EggRelaxedGroupCohColSrfArgs{a.a, a.g, st.coh, st.col, st.srf});
-            else if (st.L.surfaces)
-                hipLaunchKernelGGL(egg_rx_gather_group_coh_col_srf_kernel, grid, block, 0, s.stream,
-                                   EggRelaxedGroupCohColSrfArgs{a.a, a.g, st.coh, st.col, st.srf});
-            else if (st.L.colliders)
-                hipLaunchKernelGGL(egg_rx_gather_group_coh_col_kernel, grid, block, 0, s.stream, EggRelaxedGroupCohColArgs{a.a, a.g, st.coh, st.col});
-            else
-                hipLaunchKernelGGL(egg_rx_gather_group_coh_kernel, grid, block, 0, s.stream, k);
-        } else {
-            hipLaunchKernelGGL(egg_rx_rank_group_kernel, grid, block, 0, s.stream, a);
-            if (st.L.loads)
-                hipLaunchKernelGGL(egg_rx_gather_group_col_load_kernel, grid, block, 0, s.stream,
-                                   EggRelaxedGroupColLoadArgs{a.a, a.g, st.col, st.lsrf, st.mov, st.spn, st.lod});
-            else if (st.L.spin)
-                hipLaunchKernelGGL(egg_rx_gather_group_col_spin_kernel, grid, block, 0, s.stream,
-                                   EggRelaxedGroupColSpinArgs{a.a, a.g, st.col, st.srf, st.mov, st.spn});
-            else if (st.L.motion)
-                hipLaunchKernelGGL(egg_rx_gather_group_col_mov_kernel, grid, block, 0, s.stream,
-                                   EggRelaxedGroupColMovArgs{a.a, a.g, st.col, st.srf, st.mov});
-            else if (st.L.walls)
-                hipLaunchKernelGGL(egg_rx_gather_group_col_wall_kernel, grid, block, 0, s.stream,
-                                   EggRelaxedGroupColSrfArgs{a.a, a.g, st.col, st.srf});
-            else if (st.L.surfaces)
-                hipLaunchKernelGGL(egg_rx_gather_group_col_srf_kernel, grid, block, 0, s.stream,
-                                   EggRelaxedGroupColSrfArgs{a.a, a.g, st.col, st.srf});
-            else if (st.L.colliders)
-                hipLaunchKernelGGL(egg_rx_gather_group_col_kernel, grid, block, 0, s.stream, EggRelaxedGroupColArgs{a.a, a.g, st.col});
-            else
-                hipLaunchKernelGGL(egg_rx_gather_group_kernel, grid, block, 0, s.stream, a);
-        }
-    } else {
-        hipLaunchKernelGGL(egg_rx_scatter_kernel, grid, block, 0, s.stream, a.a);
-        if (st.L.cohesion) {
-            const EggRelaxedCohArgs k{a.a, st.coh};
-            hipLaunchKernelGGL(egg_rx_rank_coh_kernel, grid, block, 0, s.stream, k);
-            if (st.L.loads)
-                hipLaunchKernelGGL(egg_rx_gather_coh_col_load_kernel, grid, block, 0, s.stream,
-                                   EggRelaxedCohColLoadArgs{a.a, st.coh, st.col, st.lsrf, st.mov, st.spn, st.lod});
-            else if (st.L.spin)
-                hipLaunchKernelGGL(egg_rx_gather_coh_col_spin_kernel, grid, block, 0, s.stream,
-                                   EggRelaxedCohColSpinArgs{a.a, st.coh, st.col, st.srf, st.mov, st.spn});
-            else if (st.L.motion)
-                hipLaunchKernelGGL(egg_rx_gather_coh_col_mov_kernel, grid, block, 0, s.stream,
-                                   EggRelaxedCohColMovArgs{a.a, st.coh, st.col, st.srf, st.mov});
-            else if (st.L.walls)
-                hipLaunchKernelGGL(egg_rx_gather_coh_col_wall_kernel, grid, block, 0, s.stream,
-                                   EggRelaxedCohColSrfArgs{a.a, st.coh, st.col, st.srf});
-            else if (st.L.surfaces)
-                hipLaunchKernelGGL(egg_rx_gather_coh_col_srf_kernel, grid, block, 0, s.stream,
-                                   EggRelaxedCohColSrfArgs{a.a, st.coh, st.col, st.srf});
-            else if (st.L.colliders)
-                hipLaunchKernelGGL(egg_rx_gather_coh_col_kernel, grid, block, 0, s.stream, EggRelaxedCohColArgs{a.a, st.coh, st.col});
-            else
-                hipLaunchKernelGGL(egg_rx_gather_coh_kernel, grid, block, 0, s.stream, k);
-        } else {
-            hipLaunchKernelGGL(egg_rx_rank_kernel, grid, block, 0, s.stream, a.a);
-            if (st.L.loads)
-                hipLaunchKernelGGL(egg_rx_gather_col_load_kernel, grid, block, 0, s.stream,
-                                   EggRelaxedColLoadArgs{a.a, st.col, st.lsrf, st.mov, st.spn, st.lod});
-            else if (st.L.spin)
-                hipLaunchKernelGGL(egg_rx_gather_col_spin_kernel, grid, block, 0, s.stream,
-                                   EggRelaxedColSpinArgs{a.a, st.col, st.srf, st.mov, st.spn});
-            else if (st.L.motion)
-                hipLaunchKernelGGL(egg_rx_gather_col_mov_kernel, grid, block, 0, s.stream,
-                                   EggRelaxedColMovArgs{a.a, st.col, st.srf, st.mov});
-            else if (st.L.walls)
-                hipLaunchKernelGGL(egg_rx_gather_col_wall_kernel, grid, block, 0, s.stream, EggRelaxedColSrfArgs{a.a, st.col, st.srf});
-            else if (st.L.surfaces)
-                hipLaunchKernelGGL(egg_rx_gather_col_srf_kernel, grid, block, 0, s.stream, EggRelaxedColSrfArgs{a.a, st.col, st.srf});
-            else if (st.L.colliders)
-                hipLaunchKernelGGL(egg_rx_gather_col_kernel, grid, block, 0, s.stream, EggRelaxedColArgs{a.a, st.col});
-            else
-                hipLaunchKernelGGL(egg_rx_gather_kernel, grid, block, 0, s.stream, a.a);
-        }
-    }
+        hipLaunchKernelGGL(egg_rx_rank_kernel, grid, block, 0, s.stream, a.a);
+    hipLaunchKernelGGL(kRxGather.k[st.L.halo][st.L.cohesion][st.flavour], grid, block, 0, s.stream, a);
     st.launches += 5;
     std::swap(a.a.pos, a.a.pos_next);  // Jacobi: the next pass starts from this one's result
     return EGG_OK;
@@ -584,58 +516,41 @@ int launch_pass(RelaxedStep &st, int p) {
 // pass over the same entries -- with a halo the ghosts of halo pass P + sub, whose records carry u -- then the viscous rank
 // kernel and the viscosity gather, which rewrites prev.  Positions stay: nothing is swapped and no box is recorded.
 int launch_viscosity(RelaxedStep &st, int sub) {
-    egg_handle *h = st.h;
-    System &s = h->sys[st.w];
-    RelaxedBufs &r = s.rx;
-    EggRelaxedGroupArgs &a = st.A;
+    System &s = st.h->sys[st.w];
+    EggRxPassArgs &a = st.A;
     if (st.L.halo) {
-        a.g.n_ghost = r.status.p + st.L.ghosts(st.L.P + (size_t)sub);
+        a.g.n_ghost = s.rx.status.p + st.L.ghosts(st.L.P + (size_t)sub);
         a.g.box = nullptr;
     }
     const dim3 grid((unsigned)((s.n + st.ghost_cap + 255) / 256)), block(256);  // (the ghost count is read on the device)
-    HIP_TRY(h, hipMemsetAsync(r.hkey.p, 0xFF, (size_t)r.table * 8, s.stream));
-    HIP_TRY(h, hipMemsetAsync(r.hcount.p, 0, ((size_t)r.table + 1) * 4, s.stream));
+    const int rc = launch_cell_table(st, a, grid, block);
+    if (rc != EGG_OK) return rc;
     if (st.L.halo)
-        hipLaunchKernelGGL(egg_rx_insert_group_kernel, grid, block, 0, s.stream, a);
+        hipLaunchKernelGGL(egg_rx_rank_group_visc_kernel, grid, block, 0, s.stream, st.group_args());
     else
-        hipLaunchKernelGGL(egg_rx_insert_kernel, grid, block, 0, s.stream, a.a);
-    size_t bytes = r.scan_bytes;
-    HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(r.scan_tmp.p, bytes, r.hcount.p, r.hstart.p, (int)r.table + 1, s.stream));
-    if (st.L.halo) {
-        hipLaunchKernelGGL(egg_rx_scatter_group_kernel, grid, block, 0, s.stream, a);
-        hipLaunchKernelGGL(egg_rx_rank_group_visc_kernel, grid, block, 0, s.stream, a);
-        hipLaunchKernelGGL(egg_rx_gather_group_visc_kernel, grid, block, 0, s.stream, EggRelaxedGroupViscArgs{a.a, a.g, st.visc});
-    } else {
-        hipLaunchKernelGGL(egg_rx_scatter_kernel, grid, block, 0, s.stream, a.a);
         hipLaunchKernelGGL(egg_rx_rank_visc_kernel, grid, block, 0, s.stream, a.a);
-        hipLaunchKernelGGL(egg_rx_gather_visc_kernel, grid, block, 0, s.stream, EggRelaxedViscArgs{a.a, st.visc});
-    }
+    hipLaunchKernelGGL(st.L.halo ? egg_rx_gather_group_visc_kernel : egg_rx_gather_visc_kernel, grid, block, 0, s.stream, a);
     st.launches += 5;
     return EGG_OK;
 }
 
-// The coupling pass of a sub-step, first half (only with L.coupling): the type's cell table over the positions its
-// begin / mid kernel has just written, at the shared cell size H, into the table buffers of the collision passes (free
-// until the sub-step's first one).  built[w] tells the other type's stream that the table is complete.
+// The coupling pass of a sub-step, first half (only with L.coupling, so without a halo): the type's cell table over the
+// positions its begin / mid kernel has just written, at the shared cell size H, into the table buffers of the collision
+// passes (free until the sub-step's first one).  built[w] tells the other type's stream that the table is complete.
 int launch_coupling_tables(RelaxedStep &st) {
     egg_handle *h = st.h;
     System &s = h->sys[st.w];
-    RelaxedBufs &r = s.rx;
-    EggRelaxedArgs a = st.A.a;
-    a.cell_size = st.couple_cell;
+    EggRxPassArgs a = st.A;
+    a.a.cell_size = st.couple_cell;
     const dim3 grid((unsigned)((s.n + 255) / 256)), block(256);
-    HIP_TRY(h, hipMemsetAsync(r.hkey.p, 0xFF, (size_t)r.table * 8, s.stream));
-    HIP_TRY(h, hipMemsetAsync(r.hcount.p, 0, ((size_t)r.table + 1) * 4, s.stream));
-    hipLaunchKernelGGL(egg_rx_insert_kernel, grid, block, 0, s.stream, a);
-    size_t bytes = r.scan_bytes;
-    HIP_TRY(h, hipcub::DeviceScan::ExclusiveSum(r.scan_tmp.p, bytes, r.hcount.p, r.hstart.p, (int)r.table + 1, s.stream));
-    hipLaunchKernelGGL(egg_rx_scatter_kernel, grid, block, 0, s.stream, a);
+    const int rc = launch_cell_table(st, a, grid, block);
+    if (rc != EGG_OK) return rc;
     if (st.L.adhesion) {  // the tag of a grouped slot is its atom index: one number per batch for both types
-        EggRxCohesionFields tags{};
-        tags.stag = r.stag.p;
-        hipLaunchKernelGGL(egg_rx_rank_coh_kernel, grid, block, 0, s.stream, EggRelaxedCohArgs{a, tags});
+        a.c = EggRxCohesionFields{};
+        a.c.stag = s.rx.stag.p;
+        hipLaunchKernelGGL(egg_rx_rank_coh_kernel, grid, block, 0, s.stream, a);
     } else {
-        hipLaunchKernelGGL(egg_rx_rank_kernel, grid, block, 0, s.stream, a);
+        hipLaunchKernelGGL(egg_rx_rank_kernel, grid, block, 0, s.stream, a.a);
     }
     st.launches += 4;
     HIP_TRY(h, hipEventRecord(h->couple_built[st.w], s.stream));
@@ -751,43 +666,6 @@ int launch_end(RelaxedStep &st) {
 }
 
 static int relaxed_finish(egg_handle *h, RelaxedStep st[2], int S, int C);
-static int relaxed_step_bodies(egg_handle *h, RelaxedStep st[2], int S, int C);
-
-// A step with coupling (factor > 0, both types populated; st: after prepare_step).  The enqueue order is sub-step by
-// sub-step across both types, so that every event a stream waits for has been recorded by then.  Before a type's table
-// is cleared again -- by the sub-step's first collision pass, or by launch_viscosity -- its stream waits until the other
-// type's couple kernel has read it.
-static int relaxed_step_coupled(egg_handle *h, RelaxedStep st[2], int S, int C) {
-    int rc = EGG_OK;
-    for (int w = 0; w < 2; ++w) {
-        if (h->sys[w].n > kRelaxedMaxParticles) return fail(h, EGG_ERR_UNSUPPORTED, EGG_RX_TOO_MANY_TEXT);
-        rc = prepare_type(st[w], C, 0, RelaxedLayout{(size_t)S * C, 0, false}, {}, nullptr);
-        if (rc != EGG_OK) return rc;
-    }
-    if (h->opt_timing)
-        for (int w = 0; w < 2; ++w) HIP_TRY(h, hipEventRecord(h->sys[w].ev0, h->sys[w].stream));
-    for (int sub = 0; sub < S; ++sub) {
-        for (int w = 0; w < 2 && rc == EGG_OK; ++w) rc = launch_substep(st[w], sub);
-        for (int w = 0; w < 2 && rc == EGG_OK; ++w) rc = launch_coupling_tables(st[w]);
-        for (int w = 0; w < 2 && rc == EGG_OK; ++w) {
-            rc = launch_coupling(st[w], st[w ^ 1]);
-            if (rc == EGG_OK && st[w].L.containment) rc = w == 0 ? launch_contain_sum(st[0], sub) : launch_contain(st[1], st[0], sub);
-        }
-        for (int w = 0; w < 2 && rc == EGG_OK; ++w) {
-            HIP_TRY(h, hipStreamWaitEvent(h->sys[w].stream, h->couple_read[w ^ 1], 0));
-            for (int c = 0; c < C && rc == EGG_OK; ++c) rc = launch_pass(st[w], sub * C + c);
-            if (rc == EGG_OK && st[w].L.V) rc = launch_viscosity(st[w], sub);
-        }
-        if (rc != EGG_OK) return rc;
-    }
-    for (int w = 0; w < 2; ++w) {
-        rc = launch_end(st[w]);
-        if (rc == EGG_OK) rc = read_status(st[w]);
-        if (rc != EGG_OK) return rc;
-        if (h->opt_timing) HIP_TRY(h, hipEventRecord(h->sys[w].ev1, h->sys[w].stream));
-    }
-    return relaxed_finish(h, st, S, C);
-}
 
 // The integrator of sub-step `sub` on the stream of st's type, behind that type's last launch of the sub-step.
 static int launch_bodies(RelaxedStep &st) {
@@ -826,64 +704,79 @@ static int launch_contacts(RelaxedStep &st) {
     return EGG_OK;
 }
 
-// A step in which collider bodies act (st: after prepare_step, which has put the records on the device).  The gathers of
-// both types read the records the integrator writes, so the step is enqueued sub-step by sub-step across both types, with or
-// without coupling.  The integrator runs on the stream of the first populated type (`lead`), behind that type's launches of
-// the sub-step; with both types populated it first waits for body_ready, which the other stream records behind its own last
-// launch of the sub-step, and the other stream waits for body_done before its next gather.  Everything in front of a
-// sub-step's first collision pass -- begin / mid, coupling, containment -- reads no collider and runs ahead of that wait.
-// With one type empty there is one stream and no event.  No host synchronisation inside the step.
-static int relaxed_step_bodies(egg_handle *h, RelaxedStep st[2], int S, int C) {
+// Sub-step `sub` of the types in `on`, enqueued in the one order every step has: begin / mid; with coupling the tables, then
+// the couple kernels; containment; then per type the waits, the collision passes and viscosity; with bodies the integrator
+// and the contacts.  Called with both types it enqueues across them phase by phase, white first, so that every event a
+// stream waits for -- built, read, summed, body_ready, body_done -- has been recorded on the host by then.
+//   coupling: before a type's table is cleared again -- by the sub-step's first collision pass, or by launch_viscosity --
+//     its stream waits until the other type's couple kernel has read it.
+//   bodies: the gathers of both types read the records the integrator writes.  It runs on the stream of the first populated
+//     type (`lead`), behind that type's launches of the sub-step; with both types populated it first waits for body_ready,
+//     which the other stream records behind its own last launch of the sub-step, and the other stream waits for body_done
+//     before its next gather.  Everything in front of a sub-step's first collision pass -- begin / mid, coupling,
+//     containment -- reads no collider and runs ahead of that wait.  With one type empty there is one stream and no event.
+// No host synchronisation inside the step.
+static int enqueue_substep(egg_handle *h, RelaxedStep st[2], const bool on[2], int sub, int C, bool bodies) {
     int rc = EGG_OK;
-    const bool on[2] = {h->sys[0].n > 0, h->sys[1].n > 0};
     const bool both = on[0] && on[1];
+    const bool coupled = both && st[0].L.coupling;
     const int lead = on[0] || !on[1] ? 0 : 1;  // (without a particle the integrators still run: a body falls by its own acceleration)
+    for (int w = 0; w < 2 && rc == EGG_OK; ++w)
+        if (on[w]) rc = launch_substep(st[w], sub);
+    for (int w = 0; w < 2 && rc == EGG_OK && coupled; ++w) rc = launch_coupling_tables(st[w]);
+    for (int w = 0; w < 2 && rc == EGG_OK; ++w) {
+        if (!on[w]) continue;
+        if (coupled) rc = launch_coupling(st[w], st[w ^ 1]);
+        if (rc == EGG_OK && st[w].L.containment) rc = w == 0 ? launch_contain_sum(st[0], sub) : launch_contain(st[1], st[0], sub);
+    }
+    for (int w = 0; w < 2 && rc == EGG_OK; ++w) {
+        if (!on[w]) continue;
+        if (coupled) HIP_TRY(h, hipStreamWaitEvent(h->sys[w].stream, h->couple_read[w ^ 1], 0));
+        if (bodies && both && w != lead && sub > 0) HIP_TRY(h, hipStreamWaitEvent(h->sys[w].stream, h->body_done, 0));
+        for (int c = 0; c < C && rc == EGG_OK; ++c) rc = launch_pass(st[w], sub * C + c);
+        if (rc == EGG_OK && st[w].L.V) rc = launch_viscosity(st[w], sub);
+        if (rc == EGG_OK && bodies && both && w != lead) HIP_TRY(h, hipEventRecord(h->body_ready, h->sys[w].stream));
+    }
+    if (rc != EGG_OK || !bodies) return rc;
+    if (both) HIP_TRY(h, hipStreamWaitEvent(h->sys[lead].stream, h->body_ready, 0));
+    rc = launch_bodies(st[lead]);
+    if (rc == EGG_OK && h->contacts_step) rc = launch_contacts(st[lead]);
+    if (rc != EGG_OK) return rc;
+    if (both) HIP_TRY(h, hipEventRecord(h->body_done, h->sys[lead].stream));
+    return EGG_OK;
+}
+
+// The whole step of the types in `on` (st: after prepare_step): their arguments, every sub-step, the end kernels and the
+// status words on their way to the host.
+static int enqueue_types(egg_handle *h, RelaxedStep st[2], const bool on[2], int S, int C, bool bodies) {
+    int rc = EGG_OK;
     for (int w = 0; w < 2; ++w) {
         if (!on[w]) continue;
         if (h->sys[w].n > kRelaxedMaxParticles) return fail(h, EGG_ERR_UNSUPPORTED, EGG_RX_TOO_MANY_TEXT);
         rc = prepare_type(st[w], C, 0, RelaxedLayout{(size_t)S * C, 0, false}, {}, nullptr);
         if (rc != EGG_OK) return rc;
-        // the loads instantiation with every rule on, over a motion, a spin and a surface record per collider
+        if (!bodies) continue;
+        // the loads instantiation with every rule on, over a motion, a spin and a surface record per collider (A.s has them: loads are on)
         st[w].bodies = true;
-        st[w].mov.list = h->d_motions.p;
-        st[w].spn.list = h->d_spins.p;
-        st[w].spn.hcs = h->d_body_cs.p;
-        st[w].lod.moving = st[w].lod.turning = st[w].lod.pivots = 1;
-        if (!st[w].L.surfaces) st[w].lsrf.list = h->d_surfaces.p;
+        st[w].A.m.list = h->d_motions.p;
+        st[w].A.r.list = h->d_spins.p;
+        st[w].A.r.hcs = h->d_body_cs.p;
+        st[w].A.l.moving = st[w].A.l.turning = st[w].A.l.pivots = 1;
     }
-    if (both) {
+    if (bodies && on[0] && on[1]) {
         if (!h->body_ready) HIP_TRY(h, hipEventCreateWithFlags(&h->body_ready, hipEventDisableTiming));
         if (!h->body_done) HIP_TRY(h, hipEventCreateWithFlags(&h->body_done, hipEventDisableTiming));
     }
-    const bool coupled = both && st[0].L.coupling;
-    h->bodies_step = true;
-    h->contacts_step = contacts_act(h);
+    if (bodies) {
+        h->bodies_step = true;
+        h->contacts_step = contacts_act(h);
+    }
     if (h->opt_timing)
         for (int w = 0; w < 2; ++w)
             if (on[w]) HIP_TRY(h, hipEventRecord(h->sys[w].ev0, h->sys[w].stream));
     for (int sub = 0; sub < S; ++sub) {
-        for (int w = 0; w < 2 && rc == EGG_OK; ++w)
-            if (on[w]) rc = launch_substep(st[w], sub);
-        for (int w = 0; w < 2 && rc == EGG_OK && coupled; ++w) rc = launch_coupling_tables(st[w]);
-        for (int w = 0; w < 2 && rc == EGG_OK; ++w) {
-            if (!on[w]) continue;
-            if (coupled) rc = launch_coupling(st[w], st[w ^ 1]);
-            if (rc == EGG_OK && st[w].L.containment) rc = w == 0 ? launch_contain_sum(st[0], sub) : launch_contain(st[1], st[0], sub);
-        }
-        for (int w = 0; w < 2 && rc == EGG_OK; ++w) {
-            if (!on[w]) continue;
-            if (coupled) HIP_TRY(h, hipStreamWaitEvent(h->sys[w].stream, h->couple_read[w ^ 1], 0));
-            if (both && w != lead && sub > 0) HIP_TRY(h, hipStreamWaitEvent(h->sys[w].stream, h->body_done, 0));
-            for (int c = 0; c < C && rc == EGG_OK; ++c) rc = launch_pass(st[w], sub * C + c);
-            if (rc == EGG_OK && st[w].L.V) rc = launch_viscosity(st[w], sub);
-            if (rc == EGG_OK && both && w != lead) HIP_TRY(h, hipEventRecord(h->body_ready, h->sys[w].stream));
-        }
+        rc = enqueue_substep(h, st, on, sub, C, bodies);
         if (rc != EGG_OK) return rc;
-        if (both) HIP_TRY(h, hipStreamWaitEvent(h->sys[lead].stream, h->body_ready, 0));
-        rc = launch_bodies(st[lead]);
-        if (rc == EGG_OK && h->contacts_step) rc = launch_contacts(st[lead]);
-        if (rc != EGG_OK) return rc;
-        if (both) HIP_TRY(h, hipEventRecord(h->body_done, h->sys[lead].stream));
     }
     for (int w = 0; w < 2; ++w) {
         if (!on[w]) continue;
@@ -892,10 +785,12 @@ static int relaxed_step_bodies(egg_handle *h, RelaxedStep st[2], int S, int C) {
         if (rc != EGG_OK) return rc;
         if (h->opt_timing) HIP_TRY(h, hipEventRecord(h->sys[w].ev1, h->sys[w].stream));
     }
-    if (!on[lead]) HIP_TRY(h, hipStreamSynchronize(h->sys[lead].stream));  // (relaxed_finish waits for populated types only)
-    return relaxed_finish(h, st, S, C);
+    return EGG_OK;
 }
 
+// One handle, everything enqueued in one go.  With coupling (factor > 0, both types populated) or with collider bodies the
+// streams of the two types wait for each other's events, so the step is enqueued sub-step by sub-step across both types;
+// otherwise type by type over all sub-steps, white first.
 int relaxed_step(egg_handle *h, double delta, int S, int C) {  // L:1722-1989, collision passes relaxed
     h->bodies_step = h->contacts_step = false;
     if (h->bodies_any && !h->colliders.empty() && !h->opt_loads)  // (before anything is launched or copied)
@@ -904,27 +799,18 @@ int relaxed_step(egg_handle *h, double delta, int S, int C) {  // L:1722-1989, c
     RelaxedStep st[2];
     int rc = prepare_step(h, delta, S, st);
     if (rc != EGG_OK) return rc;
-    if (bodies_act(h)) return relaxed_step_bodies(h, st, S, C);
-    if (h->coupling_factor > 0.0 && h->sys[0].n > 0 && h->sys[1].n > 0) return relaxed_step_coupled(h, st, S, C);
-    for (int w = 0; w < 2; ++w) {
-        System &s = h->sys[w];
-        if (s.n == 0) continue;
-        if (s.n > kRelaxedMaxParticles) return fail(h, EGG_ERR_UNSUPPORTED, EGG_RX_TOO_MANY_TEXT);
-        rc = prepare_type(st[w], C, 0, RelaxedLayout{(size_t)S * C, 0, false}, {}, nullptr);
-        if (rc != EGG_OK) return rc;
-        if (h->opt_timing) HIP_TRY(h, hipEventRecord(s.ev0, s.stream));
-        for (int sub = 0; sub < S && rc == EGG_OK; ++sub) {
-            rc = launch_substep(st[w], sub);
-            if (rc == EGG_OK && st[w].L.containment) rc = w == 0 ? launch_contain_sum(st[0], sub) : launch_contain(st[1], st[0], sub);
-            for (int c = 0; c < C && rc == EGG_OK; ++c) rc = launch_pass(st[w], sub * C + c);
-            if (rc == EGG_OK && st[w].L.V) rc = launch_viscosity(st[w], sub);
-        }
-        if (rc == EGG_OK) rc = launch_end(st[w]);
-        if (rc == EGG_OK) rc = read_status(st[w]);
-        if (rc != EGG_OK) return rc;
-        if (h->opt_timing) HIP_TRY(h, hipEventRecord(s.ev1, s.stream));
+    const bool on[2] = {h->sys[0].n > 0, h->sys[1].n > 0};
+    const bool bodies = bodies_act(h);
+    if (bodies || (h->coupling_factor > 0.0 && on[0] && on[1])) {
+        rc = enqueue_types(h, st, on, S, C, bodies);
+        const int lead = on[0] || !on[1] ? 0 : 1;
+        if (rc == EGG_OK && bodies && !on[lead]) HIP_TRY(h, hipStreamSynchronize(h->sys[lead].stream));  // (relaxed_finish waits for populated types only)
+    } else {
+        const bool white[2] = {on[0], false}, yolk[2] = {false, on[1]};
+        rc = enqueue_types(h, st, white, S, C, false);
+        if (rc == EGG_OK) rc = enqueue_types(h, st, yolk, S, C, false);
     }
-    return relaxed_finish(h, st, S, C);
+    return rc == EGG_OK ? relaxed_finish(h, st, S, C) : rc;
 }
 
 // a relaxed step whose launches are all enqueued: wait for both types, then fail on a bad cell or commit

@@ -261,7 +261,7 @@ int relaxed_group_step(egg_handle *const *hs, int nh, double delta, int S, int C
                 pk.ekey = s.rx.ekey.p;
                 if (st[j][w].L.cohesion) {
                     pk.p_atom = s.rx.p_atom.p;
-                    pk.atom_tag = st[j][w].coh.atom_tag;
+                    pk.atom_tag = st[j][w].A.c.atom_tag;
                 }
                 for (size_t mk = 0; mk < nq; ++mk) {
                     if (mk == mj) continue;

@@ -258,7 +258,7 @@ int egg_rx_pack(egg_handle *h, int32_t pass, int32_t n_dest, const egg_rx_box *b
         pk.ekey = r.ekey.p;
         if (W.st[w].L.cohesion) {
             pk.p_atom = r.p_atom.p;
-            pk.atom_tag = W.st[w].coh.atom_tag;
+            pk.atom_tag = W.st[w].A.c.atom_tag;
         }
         pk.stride = (long long)stride;
         for (size_t k0 = 0; k0 < nd; k0 += EGG_RX_MAX_GROUP) {

@@ -455,7 +455,8 @@ extern "C" __global__ void __launch_bounds__(256) egg_rx_atoms_kernel(const int3
 }
 
 // The kernels that take part in a device group come in two instantiations: G = false is the single handle's (the key
-// is the index, no ghosts, no box; EggRelaxedArgs alone), G = true the group's (EggRelaxedGroupArgs).  The G = false
+// is the index, no ghosts, no box; EggRelaxedArgs alone), G = true the group's (EggRelaxedGroupArgs; the flavoured
+// kernels of either kind take EggRxPassArgs, see EGG_RX_PASS_KERNELS below).  The G = false
 // instantiations compile to the same instructions as the kernels before groups existed.  (rx_insert and rx_gather
 // take the arguments by value: by reference, the compiler schedules them differently.)
 // F: the force fields act on the velocity before the pre-solve (rx_force); the F = false instantiations compile to the
@@ -501,16 +502,10 @@ __device__ __forceinline__ void rx_mid(const EggRelaxedArgs &A, const EggRxGroup
 // Start of a step: pre-solve + follow of the first sub-step from the committed state.
 extern "C" __global__ void __launch_bounds__(256) egg_rx_begin_kernel(EggRelaxedArgs A) { rx_begin<false, false>(A, EggRxGroupFields{}, EggRxForceFields{}); }
 extern "C" __global__ void __launch_bounds__(256) egg_rx_begin_group_kernel(EggRelaxedGroupArgs A) { rx_begin<true, false>(A.a, A.g, EggRxForceFields{}); }
-// force fields
-extern "C" __global__ void __launch_bounds__(256) egg_rx_begin_frc_kernel(EggRelaxedFrcArgs A) { rx_begin<false, true>(A.a, EggRxGroupFields{}, A.f); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_begin_group_frc_kernel(EggRelaxedGroupFrcArgs A) { rx_begin<true, true>(A.a, A.g, A.f); }
 
 // Between two sub-steps: post-solve of the one (L:1690-1693), pre-solve + follow of the next.
 extern "C" __global__ void __launch_bounds__(256) egg_rx_mid_kernel(EggRelaxedArgs A) { rx_mid<false, false>(A, EggRxGroupFields{}, EggRxForceFields{}); }
 extern "C" __global__ void __launch_bounds__(256) egg_rx_mid_group_kernel(EggRelaxedGroupArgs A) { rx_mid<true, false>(A.a, A.g, EggRxForceFields{}); }
-// force fields
-extern "C" __global__ void __launch_bounds__(256) egg_rx_mid_frc_kernel(EggRelaxedFrcArgs A) { rx_mid<false, true>(A.a, EggRxGroupFields{}, A.f); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_mid_group_frc_kernel(EggRelaxedGroupFrcArgs A) { rx_mid<true, true>(A.a, A.g, A.f); }
 
 // End of the step: post-solve of the last sub-step into the [cur ^ 1] arrays -- unless a pass flagged a bad cell: the
 // step then fails and [cur ^ 1] keeps the positions at the start of the last committed step (EGG_FIELD_LAST_X / Y).
@@ -752,48 +747,7 @@ extern "C" __global__ void __launch_bounds__(256) egg_rx_scatter_kernel(EggRelax
 extern "C" __global__ void __launch_bounds__(256) egg_rx_scatter_group_kernel(EggRelaxedGroupArgs A) { rx_scatter<true>(A.a, A.g); }
 extern "C" __global__ void __launch_bounds__(256) egg_rx_rank_kernel(EggRelaxedArgs A) { rx_rank<false, false>(A, EggRxGroupFields{}, EggRxCohesionFields{}); }
 extern "C" __global__ void __launch_bounds__(256) egg_rx_rank_group_kernel(EggRelaxedGroupArgs A) { rx_rank<true, false>(A.a, A.g, EggRxCohesionFields{}); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_kernel(EggRelaxedArgs A) { rx_gather<false, false, false, false, false>(A, EggRxGroupFields{}, EggRxCohesionFields{}, EggRxColliderFields{}, EggRxSurfaceFields{}); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_kernel(EggRelaxedGroupArgs A) { rx_gather<true, false, false, false, false>(A.a, A.g, EggRxCohesionFields{}, EggRxColliderFields{}, EggRxSurfaceFields{}); }
-// effective cohesion
-extern "C" __global__ void __launch_bounds__(256) egg_rx_rank_coh_kernel(EggRelaxedCohArgs A) { rx_rank<false, true>(A.a, EggRxGroupFields{}, A.c); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_rank_group_coh_kernel(EggRelaxedGroupCohArgs A) { rx_rank<true, true>(A.a, A.g, A.c); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_coh_kernel(EggRelaxedCohArgs A) { rx_gather<false, true, false, false, false>(A.a, EggRxGroupFields{}, A.c, EggRxColliderFields{}, EggRxSurfaceFields{}); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_coh_kernel(EggRelaxedGroupCohArgs A) { rx_gather<true, true, false, false, false>(A.a, A.g, A.c, EggRxColliderFields{}, EggRxSurfaceFields{}); }
-// static colliders
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_col_kernel(EggRelaxedColArgs A) { rx_gather<false, false, true, false, false>(A.a, EggRxGroupFields{}, EggRxCohesionFields{}, A.d, EggRxSurfaceFields{}); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_col_kernel(EggRelaxedGroupColArgs A) { rx_gather<true, false, true, false, false>(A.a, A.g, EggRxCohesionFields{}, A.d, EggRxSurfaceFields{}); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_coh_col_kernel(EggRelaxedCohColArgs A) { rx_gather<false, true, true, false, false>(A.a, EggRxGroupFields{}, A.c, A.d, EggRxSurfaceFields{}); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_coh_col_kernel(EggRelaxedGroupCohColArgs A) { rx_gather<true, true, true, false, false>(A.a, A.g, A.c, A.d, EggRxSurfaceFields{}); }
-
-// collider surfaces
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_col_srf_kernel(EggRelaxedColSrfArgs A) { rx_gather<false, false, true, true, false>(A.a, EggRxGroupFields{}, EggRxCohesionFields{}, A.d, A.s); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_col_srf_kernel(EggRelaxedGroupColSrfArgs A) { rx_gather<true, false, true, true, false>(A.a, A.g, EggRxCohesionFields{}, A.d, A.s); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_coh_col_srf_kernel(EggRelaxedCohColSrfArgs A) { rx_gather<false, true, true, true, false>(A.a, EggRxGroupFields{}, A.c, A.d, A.s); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_coh_col_srf_kernel(EggRelaxedGroupCohColSrfArgs A) { rx_gather<true, true, true, true, false>(A.a, A.g, A.c, A.d, A.s); }
-
-// walls (the arguments are the surface instantiations')
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_col_wall_kernel(EggRelaxedColSrfArgs A) { rx_gather<false, false, true, true, true>(A.a, EggRxGroupFields{}, EggRxCohesionFields{}, A.d, A.s); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_col_wall_kernel(EggRelaxedGroupColSrfArgs A) { rx_gather<true, false, true, true, true>(A.a, A.g, EggRxCohesionFields{}, A.d, A.s); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_coh_col_wall_kernel(EggRelaxedCohColSrfArgs A) { rx_gather<false, true, true, true, true>(A.a, EggRxGroupFields{}, A.c, A.d, A.s); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_coh_col_wall_kernel(EggRelaxedGroupCohColSrfArgs A) { rx_gather<true, true, true, true, true>(A.a, A.g, A.c, A.d, A.s); }
-
-// collider motion (colliders, surfaces and walls all on)
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_col_mov_kernel(EggRelaxedColMovArgs A) { rx_gather<false, false, true, true, true>(A.a, EggRxGroupFields{}, EggRxCohesionFields{}, A.d, A.s, &A.m); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_col_mov_kernel(EggRelaxedGroupColMovArgs A) { rx_gather<true, false, true, true, true>(A.a, A.g, EggRxCohesionFields{}, A.d, A.s, &A.m); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_coh_col_mov_kernel(EggRelaxedCohColMovArgs A) { rx_gather<false, true, true, true, true>(A.a, EggRxGroupFields{}, A.c, A.d, A.s, &A.m); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_coh_col_mov_kernel(EggRelaxedGroupCohColMovArgs A) { rx_gather<true, true, true, true, true>(A.a, A.g, A.c, A.d, A.s, &A.m); }
-
-// collider spin (colliders, surfaces, walls and motion all on)
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_col_spin_kernel(EggRelaxedColSpinArgs A) { rx_gather<false, false, true, true, true>(A.a, EggRxGroupFields{}, EggRxCohesionFields{}, A.d, A.s, &A.m, &A.r); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_col_spin_kernel(EggRelaxedGroupColSpinArgs A) { rx_gather<true, false, true, true, true>(A.a, A.g, EggRxCohesionFields{}, A.d, A.s, &A.m, &A.r); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_coh_col_spin_kernel(EggRelaxedCohColSpinArgs A) { rx_gather<false, true, true, true, true>(A.a, EggRxGroupFields{}, A.c, A.d, A.s, &A.m, &A.r); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_coh_col_spin_kernel(EggRelaxedGroupCohColSpinArgs A) { rx_gather<true, true, true, true, true>(A.a, A.g, A.c, A.d, A.s, &A.m, &A.r); }
-
-// the loads instantiations (egg_set_collider_loads on): one per (group, cohesion), standing in for every collider flavour
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_col_load_kernel(EggRelaxedColLoadArgs A) { rx_gather<false, false, true, true, true>(A.a, EggRxGroupFields{}, EggRxCohesionFields{}, A.d, A.s, &A.m, &A.r, &A.l); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_col_load_kernel(EggRelaxedGroupColLoadArgs A) { rx_gather<true, false, true, true, true>(A.a, A.g, EggRxCohesionFields{}, A.d, A.s, &A.m, &A.r, &A.l); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_coh_col_load_kernel(EggRelaxedCohColLoadArgs A) { rx_gather<false, true, true, true, true>(A.a, EggRxGroupFields{}, A.c, A.d, A.s, &A.m, &A.r, &A.l); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_coh_col_load_kernel(EggRelaxedGroupCohColLoadArgs A) { rx_gather<true, true, true, true, true>(A.a, A.g, A.c, A.d, A.s, &A.m, &A.r, &A.l); }
+// (the cohesive rank kernels and the 28 gathers: EGG_RX_PASS_KERNELS, expanded behind the viscosity pass)
 
 // ---- collider bodies ----
 
@@ -963,8 +917,22 @@ __device__ __forceinline__ void rx_gather_visc(EggRelaxedArgs A, const EggRxGrou
 
 extern "C" __global__ void __launch_bounds__(256) egg_rx_rank_visc_kernel(EggRelaxedArgs A) { rx_rank_visc<false>(A, EggRxGroupFields{}); }
 extern "C" __global__ void __launch_bounds__(256) egg_rx_rank_group_visc_kernel(EggRelaxedGroupArgs A) { rx_rank_visc<true>(A.a, A.g); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_visc_kernel(EggRelaxedViscArgs A) { rx_gather_visc<false>(A.a, EggRxGroupFields{}, A.v); }
-extern "C" __global__ void __launch_bounds__(256) egg_rx_gather_group_visc_kernel(EggRelaxedGroupViscArgs A) { rx_gather_visc<true>(A.a, A.g, A.v); }
+
+// ---- the flavoured kernels ----
+
+// Every kernel of EGG_RX_PASS_KERNELS (eggsim_device.h), under its own name.  A column of a gather's row is a literal 0 or
+// 1, so each wrapper hands rx_gather the constants the column stands for: an empty group, or no pointer at all.
+#define EGG_RX_DEFINE_GATHER(name, G, K, flavour, D, S, W, Mo, Sp, Ld)                                                 \
+    extern "C" __global__ void __launch_bounds__(256) name(EggRxPassArgs A) {                                          \
+        rx_gather<G, K, D, S, W>(A.a, G ? A.g : EggRxGroupFields{}, K ? A.c : EggRxCohesionFields{},                    \
+                                 D ? A.d : EggRxColliderFields{}, S ? A.s : EggRxSurfaceFields{}, Mo ? &A.m : nullptr, \
+                                 Sp ? &A.r : nullptr, Ld ? &A.l : nullptr);                                            \
+    }
+#define EGG_RX_DEFINE_OTHER(name, ...) \
+    extern "C" __global__ void __launch_bounds__(256) name(EggRxPassArgs A) { __VA_ARGS__; }
+EGG_RX_PASS_KERNELS(EGG_RX_DEFINE_GATHER, EGG_RX_DEFINE_OTHER)
+#undef EGG_RX_DEFINE_GATHER
+#undef EGG_RX_DEFINE_OTHER
 
 // ---- white-yolk coupling ----
 

@@ -62,13 +62,19 @@ def test_the_kernel_exists_and_only_a_step_with_bodies_launches_it():
     assert "if (k >= A.count) return;" in body
     # one wave, one launch, from the bodies driver only; the driver is chosen by what the handle holds
     assert host.count("hipLaunchKernelGGL(egg_rx_bodies_kernel, dim3(1), dim3(64)") == 1
-    assert host.count("launch_bodies(") == 2 and host.count("relaxed_step_bodies(") == 3  # (declared, defined, called)
+    assert host.count("launch_bodies(") == 2 and host.count("enqueue_substep(") == 2  # (each defined, and called from one place)
     assert "static bool bodies_act(const egg_handle *h) { return h->bodies_any && h->opt_loads && !h->colliders.empty(); }" in host
     step = host[host.index("int relaxed_step(egg_handle *h"):host.index("// a relaxed step whose launches are all enqueued")]
     assert step.index("if (h->bodies_any && !h->colliders.empty() && !h->opt_loads)") < step.index("prepare_step(")  # before anything is launched
     assert "egg_set_collider_loads" in step and "EGG_ERR_UNSUPPORTED" in step
-    assert "if (bodies_act(h)) return relaxed_step_bodies(h, st, S, C);" in step
-    driver = host[host.index("static int relaxed_step_bodies(egg_handle *h, RelaxedStep st[2], int S, int C) {"):host.index("int relaxed_step(egg_handle *h")]
+    assert "const bool bodies = bodies_act(h);" in step and "enqueue_types(h, st, on, S, C, bodies);" in step
+    assert step.index("if (bodies || (h->coupling_factor > 0.0 && on[0] && on[1])) {") < step.index("enqueue_types(h, st, on, S, C, bodies);")
+    # the one driver: the sub-step body, the whole step of a set of types, and relaxed_step, which calls it
+    driver = host[host.index("static int enqueue_substep(egg_handle *h, RelaxedStep st[2], const bool on[2], int sub, int C, bool bodies) {"):
+                  host.index("// a relaxed step whose launches are all enqueued")]
+    assert driver.index("static int enqueue_types(") < driver.index("int relaxed_step(egg_handle *h")
+    substep = driver[:driver.index("static int enqueue_types(")]
+    assert "if (rc != EGG_OK || !bodies) return rc;" in substep and substep.index("|| !bodies) return rc;") < substep.index("launch_bodies(st[lead])")
     assert "hipEventDisableTiming" in driver and "hipDeviceSynchronize" not in driver
     assert driver.count("hipStreamSynchronize") == 1  # (only for a handle without particles, after the last launch)
     # the commit reads the records back in place of advance_colliders; after a failed step the next one puts the host's
@@ -157,7 +163,7 @@ def test_the_wrapper_checks_before_any_device_call():
 def test_the_documents_describe_the_rule():
     design = _read(ROOT, "DESIGN.md")
     part = design[design.index("#### Collider bodies"):design.index("#### Forces")]
-    for phrase in ("egg_rx_bodies_kernel", "relaxed_step_bodies", "Cayley", "2 atan(h omega / 2)", "seen[k] = sums[k]", "body_ready", "body_done",
+    for phrase in ("egg_rx_bodies_kernel", "enqueue_substep", "Cayley", "2 atan(h omega / 2)", "seen[k] = sums[k]", "body_ready", "body_done",
                    "The plate experiment", "explicit", "bit-equal at `S = 1`", "profiles/r24_bodies.md", "ONE handle only"):
         assert phrase in part, phrase
     limits = design[design.index("## 7. Limits"):]

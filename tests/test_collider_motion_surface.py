@@ -20,11 +20,12 @@ PROTOS = {
     "egg_group_set_collider_motion": "int egg_group_set_collider_motion(egg_group *g, int32_t n, const egg_collider_motion *m);",
     "egg_group_get_collider_motion": "int egg_group_get_collider_motion(const egg_group *g, int32_t cap, egg_collider_motion *m, int32_t *n);",
 }
+# kernel: (G, K) of its row in the one kernel list -- its place in the host's table beside the motion flavour
 KERNELS = {
-    "egg_rx_gather_col_mov_kernel": "EggRelaxedColMovArgs",
-    "egg_rx_gather_group_col_mov_kernel": "EggRelaxedGroupColMovArgs",
-    "egg_rx_gather_coh_col_mov_kernel": "EggRelaxedCohColMovArgs",
-    "egg_rx_gather_group_coh_col_mov_kernel": "EggRelaxedGroupCohColMovArgs",
+    "egg_rx_gather_col_mov_kernel": (False, False),
+    "egg_rx_gather_group_col_mov_kernel": (True, False),
+    "egg_rx_gather_coh_col_mov_kernel": (False, True),
+    "egg_rx_gather_group_coh_col_mov_kernel": (True, True),
 }
 
 
@@ -127,13 +128,17 @@ def test_lua_wrapper_and_documents_name_the_methods():
 
 
 def test_the_four_kernels_and_their_launches():
-    kernels, driver, host_h = _read(CSRC, "eggsim_relaxed.hip"), _read(CSRC, "eggsim_host_relaxed.hip"), _read(CSRC, "eggsim_host.h")
-    for name, args in KERNELS.items():
-        assert kernels.count(name) == 1 and "__launch_bounds__(256) %s(%s A)" % (name, args) in kernels, name
-        assert host_h.count("void %s(%s A);" % (name, args)) == 1, name
-        assert driver.count(name) == 1 and len(re.findall(r"hipLaunchKernelGGL\(%s," % name, driver)) == 1, name
-    # the motion instantiations are the only ones that are given the motion fields
-    assert len(re.findall(r"&A\.m\)", kernels)) == 4
-    assert sorted(re.findall(r"void (egg_rx_\w*mov\w*)\(", host_h)) == sorted(KERNELS)
+    import rx_kernel_list
+    kernels = _read(CSRC, "eggsim_relaxed.hip")
+    rows = rx_kernel_list.assert_expansions()  # (every row is defined, declared to the host and in its table once)
+    for name, (G, K) in KERNELS.items():  # rx_gather<G, K, true, true, true> with the motion fields, without spin and load fields
+        assert rows[name] == dict(G=G, K=K, flavour="EGG_RX_MOV", D=True, S=True, W=True, Mo=True, Sp=False, Ld=False), name
+    # the motion instantiations are the only ones that are given the motion fields and nothing beyond them
+    assert sorted(n for n, r in rows.items() if r["Mo"] and not r["Sp"]) == sorted(KERNELS)
+    assert sorted(n for n, r in rows.items() if r["flavour"] == "EGG_RX_MOV") == sorted(n for n in rows if "mov" in n) == sorted(KERNELS)
+    # a motion outranks walls, surfaces and colliders; a spin and loads outrank it
+    order = rx_kernel_list.flavour_precedence()
+    at = order.index(("motion", "EGG_RX_MOV"))
+    assert [f for _, f in order[:at]] == ["EGG_RX_LOAD", "EGG_RX_SPIN"] and order[at + 1] == ("walls", "EGG_RX_WALL")
     # the gather keeps its five template parameters
     assert "template <bool G, bool K, bool D, bool S, bool W>\n__device__ __forceinline__ void rx_gather(" in kernels

@@ -20,11 +20,12 @@ PROTOS = {
     "egg_group_set_collider_spin": "int egg_group_set_collider_spin(egg_group *g, int32_t n, const egg_collider_spin *s);",
     "egg_group_get_collider_spin": "int egg_group_get_collider_spin(const egg_group *g, int32_t cap, egg_collider_spin *s, int32_t *n);",
 }
+# kernel: (G, K) of its row in the one kernel list -- its place in the host's table beside the spin flavour
 KERNELS = {
-    "egg_rx_gather_col_spin_kernel": "EggRelaxedColSpinArgs",
-    "egg_rx_gather_group_col_spin_kernel": "EggRelaxedGroupColSpinArgs",
-    "egg_rx_gather_coh_col_spin_kernel": "EggRelaxedCohColSpinArgs",
-    "egg_rx_gather_group_coh_col_spin_kernel": "EggRelaxedGroupCohColSpinArgs",
+    "egg_rx_gather_col_spin_kernel": (False, False),
+    "egg_rx_gather_group_col_spin_kernel": (True, False),
+    "egg_rx_gather_coh_col_spin_kernel": (False, True),
+    "egg_rx_gather_group_coh_col_spin_kernel": (True, True),
 }
 
 
@@ -52,10 +53,12 @@ def test_header_declares_the_four_entry_points_and_the_struct():
     assert re.search(r"struct EggSpin \{\s*double px, py, omega;\s*\};", device_h)
     fields = re.search(r"struct EggRxSpinFields \{([^}]*)\}", device_h).group(1)
     assert re.findall(r"(\w+);", re.sub(r"//[^\n]*", "", fields)) == ["list", "cs", "hcs", "ts"]
-    for args in KERNELS.values():  # everything a motion twin takes, and the spin fields
-        body = re.search(r"struct %s \{([^}]*)\}" % args, device_h).group(1)
-        twin = re.search(r"struct %s \{([^}]*)\}" % args.replace("Spin", "Mov"), device_h).group(1)
-        assert body.split() == twin.split() + ["EggRxSpinFields", "r;"], args
+    import rx_kernel_list
+    rows = rx_kernel_list.gather_rows()
+    for name in KERNELS:  # everything a motion twin takes, and the spin fields (A.r of the one record)
+        assert rows[name] == dict(rows[name.replace("_spin_", "_mov_")], flavour="EGG_RX_SPIN", Sp=True), name
+    record = re.search(r"struct EggRxPassArgs \{([^}]*)\}", device_h).group(1)
+    assert "EggRxMotionFields m;\n    EggRxSpinFields r;\n" in record
     # the rules of the setter, where a C caller reads them
     for phrase in ("egg_set_colliders resets every spin", "egg_set_collider_motion and egg_set_collider_surfaces leave them",
                    "A -0.0 is stored as +0.0 and counts as zero", "Refused while a step is in flight",
@@ -145,19 +148,19 @@ def test_lua_wrapper_and_documents_name_the_methods():
 
 
 def test_the_four_kernels_and_their_launches():
-    kernels, driver, host_h = _read(CSRC, "eggsim_relaxed.hip"), _read(CSRC, "eggsim_host_relaxed.hip"), _read(CSRC, "eggsim_host.h")
-    for name, args in KERNELS.items():
-        assert kernels.count(name) == 1 and "__launch_bounds__(256) %s(%s A)" % (name, args) in kernels, name
-        assert host_h.count("void %s(%s A);" % (name, args)) == 1, name
-        assert driver.count(name) == 1 and len(re.findall(r"hipLaunchKernelGGL\(%s," % name, driver)) == 1, name
-    # the spin instantiations are the only ones that are given the spin fields, and they get the motion fields too
-    assert len(re.findall(r"&A\.m, &A\.r\)", kernels)) == 4 and len(re.findall(r"&A\.r\)", kernels)) == 4
-    assert sorted(re.findall(r"void (egg_rx_\w*spin\w*)\(", host_h)) == sorted(KERNELS)
-    # a spin twin is picked in front of its motion twin, by a flag of its own
-    for name in KERNELS:
-        twin = name.replace("_spin_", "_mov_")
-        assert re.search(r"if \(st\.L\.spin\)\s*hipLaunchKernelGGL\(%s,[^;]*;\s*else if \(st\.L\.motion\)\s*hipLaunchKernelGGL\(%s," % (name, twin),
-                         driver), name
+    import rx_kernel_list
+    kernels, driver = _read(CSRC, "eggsim_relaxed.hip"), _read(CSRC, "eggsim_host_relaxed.hip")
+    rows = rx_kernel_list.assert_expansions()  # (every row is defined, declared to the host and in its table once)
+    for name, (G, K) in KERNELS.items():  # rx_gather<G, K, true, true, true> with the motion and the spin fields, without load fields
+        assert rows[name] == dict(G=G, K=K, flavour="EGG_RX_SPIN", D=True, S=True, W=True, Mo=True, Sp=True, Ld=False), name
+    # the spin instantiations are the only ones that are given the spin fields and no load fields, and they get the motion fields too
+    assert sorted(n for n, r in rows.items() if r["Sp"] and not r["Ld"]) == sorted(KERNELS)
+    assert all(r["Mo"] for r in rows.values() if r["Sp"])
+    assert sorted(n for n, r in rows.items() if r["flavour"] == "EGG_RX_SPIN") == sorted(n for n in rows if "spin" in n) == sorted(KERNELS)
+    # a spin twin is picked in front of its motion twin, by a flag of its own; only loads outrank it
+    order = rx_kernel_list.flavour_precedence()
+    at = order.index(("spin", "EGG_RX_SPIN"))
+    assert order[:at] == [("loads", "EGG_RX_LOAD")] and order[at + 1] == ("motion", "EGG_RX_MOV")
     # sines and cosines are the host's: the kernels call none
     assert not re.search(r"\b(sin|cos|sincos)\(", re.sub(r"//[^\n]*", "", kernels))
     assert "cos(a), sin(a)" in driver

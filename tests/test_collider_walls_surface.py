@@ -53,15 +53,22 @@ def test_no_entry_point_option_stats_field_or_argument_struct_was_added():
     # four new gather instantiations, on the surface instantiations' argument structs
     device_h = open(os.path.join(CSRC, "eggsim_device.h")).read()
     assert not re.search(r"struct \w*Wall\w*", device_h)
-    host_h = open(os.path.join(CSRC, "eggsim_host.h")).read()
-    walls = re.findall(r"void (egg_rx_\w*wall\w*)\((\w+) A\);", host_h)
-    assert walls == [("egg_rx_gather_col_wall_kernel", "EggRelaxedColSrfArgs"), ("egg_rx_gather_group_col_wall_kernel", "EggRelaxedGroupColSrfArgs"),
-                     ("egg_rx_gather_coh_col_wall_kernel", "EggRelaxedCohColSrfArgs"),
-                     ("egg_rx_gather_group_coh_col_wall_kernel", "EggRelaxedGroupCohColSrfArgs")]
-    kernels = open(os.path.join(CSRC, "eggsim_relaxed.hip")).read()
-    driver = open(os.path.join(CSRC, "eggsim_host_relaxed.hip")).read()
-    for name, _ in walls:
-        assert kernels.count(name + "(") == 1 and driver.count("hipLaunchKernelGGL(" + name + ",") == 1, name
+    # (rows of the one kernel list: defined, declared to the host and put into its table by the list's expansions)
+    import rx_kernel_list
+    rows = rx_kernel_list.assert_expansions()
+    walls = [name for name in rows if "wall" in name]
+    assert walls == ["egg_rx_gather_col_wall_kernel", "egg_rx_gather_group_col_wall_kernel", "egg_rx_gather_coh_col_wall_kernel",
+                     "egg_rx_gather_group_coh_col_wall_kernel"]
+    assert [n for n, r in rows.items() if r["flavour"] == "EGG_RX_WALL"] == walls  # (in the table under the walls' flavour, nowhere else)
+    for name in walls:  # the surface instantiations' arguments -- the same groups, no pointer more -- and W = true
+        srf = rows[name.replace("_wall_", "_srf_")]
+        assert rows[name] == dict(srf, flavour="EGG_RX_WALL", W=True) and not srf["W"], name
+        assert (rows[name]["G"], rows[name]["K"]) == ("_group" in name, "_coh" in name), name
+        assert rows[name]["D"] and rows[name]["S"] and not (rows[name]["Mo"] or rows[name]["Sp"] or rows[name]["Ld"]), name
+    # a wall in the list outranks a friction and nothing else
+    order = rx_kernel_list.flavour_precedence()
+    assert order[order.index(("walls", "EGG_RX_WALL")) + 1] == ("surfaces", "EGG_RX_SRF")
+    assert [f for _, f in order[:order.index(("walls", "EGG_RX_WALL"))]] == ["EGG_RX_LOAD", "EGG_RX_SPIN", "EGG_RX_MOV"]
 
 
 def test_python_classes_take_the_kind_and_check_its_shape_like_a_segments():

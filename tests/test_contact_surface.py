@@ -71,10 +71,11 @@ def test_the_kernel_exists_and_only_a_step_with_contacts_launches_it():
     assert host.count("hipLaunchKernelGGL(egg_rx_contacts_kernel, dim3(1), dim3(64)") == 1
     assert host.count("launch_contacts(") == 2  # (defined, called)
     assert "static bool contacts_act(const egg_handle *h) { return bodies_act(h) && h->contacts_any; }" in host
-    driver = host[host.index("static int relaxed_step_bodies(egg_handle *h, RelaxedStep st[2], int S, int C) {"):host.index("int relaxed_step(egg_handle *h")]
+    driver = host[host.index("static int enqueue_substep(egg_handle *h, RelaxedStep st[2], const bool on[2], int sub, int C, bool bodies) {"):
+                  host.index("// a relaxed step whose launches are all enqueued")]
     behind = driver[driver.index("rc = launch_bodies(st[lead]);"):driver.index("hipEventRecord(h->body_done")]
     assert "if (rc == EGG_OK && h->contacts_step) rc = launch_contacts(st[lead]);" in behind and "hipStreamWaitEvent" not in behind
-    assert "hipEventCreate" not in host[host.index("static int launch_contacts("):host.index("// A step in which collider bodies act")]
+    assert "hipEventCreate" not in host[host.index("static int launch_contacts("):host.index("// Sub-step `sub` of the types in `on`")]
     # prepare_step uploads the records, the commit adds the counter, a failed step reads nothing
     prepare = host[host.index("int prepare_step(egg_handle *h"):host.index("int prepare_type(RelaxedStep &st")]
     assert "contacts_act(h) ? prepare_contacts(h) : rc" in prepare

@@ -22,11 +22,12 @@ PROTOS = {
                                         "int64_t *dropped, double *sub_delta, int32_t *n);",
     "egg_group_get_collider_loads": "int egg_group_get_collider_loads(egg_group *g, int32_t cap, egg_collider_load *out, int32_t *n);",
 }
+# kernel: (G, K) of its row in the one kernel list -- its place in the host's table beside the loads flavour
 KERNELS = {
-    "egg_rx_gather_col_load_kernel": "EggRelaxedColLoadArgs",
-    "egg_rx_gather_group_col_load_kernel": "EggRelaxedGroupColLoadArgs",
-    "egg_rx_gather_coh_col_load_kernel": "EggRelaxedCohColLoadArgs",
-    "egg_rx_gather_group_coh_col_load_kernel": "EggRelaxedGroupCohColLoadArgs",
+    "egg_rx_gather_col_load_kernel": (False, False),
+    "egg_rx_gather_group_col_load_kernel": (True, False),
+    "egg_rx_gather_coh_col_load_kernel": (False, True),
+    "egg_rx_gather_group_coh_col_load_kernel": (True, True),
 }
 
 
@@ -57,10 +58,12 @@ def test_header_declares_the_entry_points_the_scales_and_the_struct():
         _read(CSRC, "eggsim_host_colliders.hip")
     fields = re.search(r"struct EggRxLoadFields \{([^}]*)\}", device_h).group(1)
     assert re.findall(r"(\w+);", re.sub(r"//[^\n]*", "", fields)) == ["sums", "dropped", "eps", "moving", "turning", "pivots"]
-    for args in KERNELS.values():  # everything a spin twin takes, and the load fields
-        body = re.search(r"struct %s \{([^}]*)\}" % args, device_h).group(1)
-        twin = re.search(r"struct %s \{([^}]*)\}" % args.replace("Load", "Spin"), device_h).group(1)
-        assert body.split() == twin.split() + ["EggRxLoadFields", "l;"], args
+    import rx_kernel_list
+    rows = rx_kernel_list.gather_rows()
+    for name in KERNELS:  # the load row passes everything its spin row passes, and beyond it the load fields (A.l of the one record) alone
+        assert rows[name] == dict(rows[name.replace("_load_", "_spin_")], flavour="EGG_RX_LOAD", Ld=True), name
+    record = re.search(r"struct EggRxPassArgs \{([^}]*)\}", device_h).group(1)
+    assert "EggRxSpinFields r;\n    EggRxLoadFields l;\n" in record
     # the definition, where a C caller reads it
     for phrase in ("ux = m * (bx - ax),  uy = m * (by - ay)", "uz = (ax - Px) * uy - (ay - Py) * ux", "m  = 1.0 / im",
                    "qz = llrint(uz * EGG_COLLIDER_LOAD_TORQUE_SCALE)", "reaches 2^53 in magnitude, the contribution is dropped whole",
@@ -73,13 +76,16 @@ def test_header_declares_the_entry_points_the_scales_and_the_struct():
 
 def test_the_kernels_exist_and_only_a_step_with_loads_launches_them():
     kernels = _read(CSRC, "eggsim_relaxed.hip")
-    host_h = _read(CSRC, "eggsim_host.h")
     host = _read(CSRC, "eggsim_host_relaxed.hip")
-    for name, args in KERNELS.items():
-        assert 'extern "C" __global__ void __launch_bounds__(256) %s(%s A)' % (name, args) in kernels, name
-        assert 'extern "C" __global__ void %s(%s A);' % (name, args) in host_h, name
-        assert re.search(r"if \(st\.L\.loads\)\s+hipLaunchKernelGGL\(%s, grid, block, 0, s\.stream," % name, host), name
-    assert len(re.findall(r"if \(st\.L\.loads\)\s+hipLaunchKernelGGL\(", host)) == 4 and host.count("else if (st.L.spin)") == 4
+    import rx_kernel_list
+    rows = rx_kernel_list.assert_expansions()  # (every row is defined, declared to the host and in its table once)
+    for name, (G, K) in KERNELS.items():  # rx_gather<G, K, true, true, true> with the motion, spin and load fields
+        assert rows[name] == dict(G=G, K=K, flavour="EGG_RX_LOAD", D=True, S=True, W=True, Mo=True, Sp=True, Ld=True), name
+    assert sorted(n for n, r in rows.items() if r["Ld"]) == sorted(n for n, r in rows.items() if r["flavour"] == "EGG_RX_LOAD") == sorted(KERNELS)
+    # only a step with loads launches them, and such a step launches no other gather: the switch is tested first
+    order = rx_kernel_list.flavour_precedence()
+    assert order[0] == ("loads", "EGG_RX_LOAD") and order[1] == ("spin", "EGG_RX_SPIN")
+    assert [f for _, f in order].count("EGG_RX_LOAD") == 1
     assert "st.L.loads = st.L.colliders && h->opt_loads;" in host
     # no per-lane atomics on the sums: the three adds sit behind the wave's lane 0, and a wave nothing counted in returns
     tally = kernels[kernels.index("void rx_tally("):kernels.index("// Step 5b of the relaxed pass")]
