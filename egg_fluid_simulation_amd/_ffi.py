@@ -289,6 +289,23 @@ COVER_OWNER_KEYS = 0x100  # EGG_COVER_OWNER_KEYS: flag bit of spec.path, the own
 COVER_PATHS = {"auto": 0, "direct": 1, "lanes": 2, "wave": 3}  # EGG_COVER_PATH_*; all but auto are test hooks
 
 
+class EggTouchSpec(C.Structure):  # egg_touch_spec: the reach per type in units of (ra + rb), the type mask and the flags (24 bytes)
+    _fields_ = [("reach", C.c_double * 2), ("type_mask", C.c_int32), ("flags", C.c_int32)]
+
+
+class EggTouchQuery(C.Structure):  # egg_touch_query: the key a query leaves out (-1: none), its type and its number of discs (16 bytes)
+    _fields_ = [("key", C.c_int64), ("type", C.c_int32), ("count", C.c_int32)]
+
+
+class EggTouchRecord(C.Structure):  # egg_touch_record: one (slot, other batch) with a touching pair (40 bytes)
+    _fields_ = [("slot", C.c_int32), ("pairs", C.c_int32), ("particles", C.c_int32), ("dropped", C.c_int32), ("other", C.c_int64),
+                ("sx", C.c_int64), ("sy", C.c_int64)]
+
+
+TOUCH_BY_KEYS = 1  # EGG_TOUCH_BY_KEYS: flag bit of spec.flags, `other` and the queries' keys are batch keys in place of ids
+TOUCH_MAX_QUERY = 1 << 20  # EGG_TOUCH_MAX_QUERY: discs of one query
+
+
 class EggRxBox(C.Structure):  # egg_rx_box: a cell box of the relaxed halo between processes
     _fields_ = [("lo_x", C.c_int32), ("lo_y", C.c_int32), ("hi_x", C.c_int32), ("hi_y", C.c_int32), ("empty", C.c_int32)]
 
@@ -517,6 +534,14 @@ _COVER_SIGNATURES = {
     "egg_group_cover": (C.c_int, [C.c_void_p, C.POINTER(EggCoverSpec), C.POINTER(EggCoverPlanes), C.POINTER(EggCoverTotals)]),
 }
 COVER_SYMBOLS = sorted(_COVER_SIGNATURES)
+# the entry points of include/eggsim_touch.h, brought along the same way: with them the library exports 184
+_TOUCH_SIGNATURES = {
+    "egg_touches": (C.c_int, [C.c_void_p, C.POINTER(EggTouchSpec), C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]),
+    "egg_touches_of": (C.c_int, [C.c_void_p, C.POINTER(EggTouchSpec), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                 C.c_void_p, C.POINTER(C.c_int64)]),
+    "egg_group_touches": (C.c_int, [C.c_void_p, C.POINTER(EggTouchSpec), C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]),
+}
+TOUCH_SYMBOLS = sorted(_TOUCH_SIGNATURES)
 
 _lib = None
 
@@ -535,7 +560,7 @@ def load():
                 "or `make -C egg_fluid_simulation_amd/csrc` (needs hipcc; the solver has no CPU path)")
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in list(_SIGNATURES.items()) + list(_IMPULSE_SIGNATURES.items()) + list(_MEASURE_SIGNATURES.items()) + \
-                list(_COVER_SIGNATURES.items()):
+                list(_COVER_SIGNATURES.items()) + list(_TOUCH_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

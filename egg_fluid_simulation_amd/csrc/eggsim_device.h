@@ -1017,3 +1017,54 @@ struct EggCoverFinishArgs {           // covered[2], covered_both, covered_any f
     int64_t cells;                    // nx * ny
     unsigned long long *totals;       // words 11 .. 14
 };
+
+// ---------------------------------------------------------------------------------------------
+// Touches (eggsim_touches.hip; include/eggsim_touch.h): which batches touch which, how much and
+// where.  A QUERY is a set of discs of one type with a key; the queries of a call are taken in ROUNDS of at most
+// EGG_TC_ROUND, one lane of a wave per query.  A gather kernel writes a round's table -- from the handle's own arrays or from
+// discs the caller uploaded, so the scan has one input form --, the scan walks the units of the shared builder (push_units:
+// at most EGG_SN_UNIT consecutive particles of one atom; `reserved` the id, or the key, of the unit's batch) with one wave
+// per unit.  Read-only on the particle arrays; no step launches anything of this.
+#define EGG_TC_ROUND 64              // queries of one round: one lane of a wave per query
+#define EGG_TC_OWN (EGG_SN_UNIT / EGG_WAVE)  // particles of a unit a lane keeps in registers: 16, one bit each in the touched mask
+#define EGG_TC_FIRST_RECORDS 256     // records the device buffer holds before a call has asked for more
+struct EggTouchSource {  // one query as the host lists it
+    int32_t offset, count;           // discs [offset, offset + count) of the source arrays of `type`, count >= 1
+    int32_t type, slot;              // 0 white, 1 yolk; slot = 2 i + type for entry i of the caller's list
+    long long key;                   // the batch the query leaves out: an id or a key as the units carry it, or -1 for none
+    long long first;                 // the first disc of the query in the round's disc table
+};
+struct EggTouchQuery {   // one query of a round, as the gather kernel leaves it (72 bytes)
+    long long first;                 // its discs in the disc table
+    int32_t count, type, slot, empty;  // empty: no centre without a NaN in x, or none in y -- the query touches nothing
+    long long key;
+    double lo_x, lo_y, hi_x, hi_y;   // the box of its centres, every coordinate that is not a NaN
+    double rmax;                     // the largest |r| that is not a NaN
+};
+struct EggTouchDisc {    // one disc of a round (48 bytes)
+    double x, y, r;
+    long long qx, qy;                // rint(x * EGG_SN_SCALE), rint(y * EGG_SN_SCALE); 0 where dropped
+    long long dropped;               // 1: a scaled coordinate reaches EGG_SN_LIMIT or is not finite
+};
+struct EggTouchGatherArgs {
+    const double *x[2], *y[2], *r[2];  // the source arrays per type: the handle's committed arrays, or the uploaded discs twice
+    const EggTouchSource *sources;   // the round's queries
+    int32_t n_queries;               // 1 .. EGG_TC_ROUND
+    EggTouchQuery *queries;          // [EGG_TC_ROUND]
+    EggTouchDisc *discs;
+};
+struct EggTouchRecord {  // egg_touch_record: a partial record of one (unit, query)
+    int32_t slot, pairs, particles, dropped;
+    long long other, sx, sy;
+};
+struct EggTouchArgs {
+    const double *x[2], *y[2], *radius[2];  // the committed positions and the radii per type
+    const EggScanUnit *units;        // `reserved`: the id, or the key, of the unit's batch
+    int32_t n_units, n_queries;      // n_queries of this round, 1 .. EGG_TC_ROUND
+    double reach[2];
+    EggTouchRecord *out;             // [cap]
+    int32_t cap;
+    int32_t *cursor;                 // records asked for so far: it keeps counting past cap
+    // (the round's queries and discs are kernel parameters of their own, const and __restrict__: eggsim_touches.hip)
+    unsigned long long *candidates;  // developer counter (or null): the (unit, query) pairs the cull let through
+};

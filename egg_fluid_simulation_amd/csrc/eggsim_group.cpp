@@ -1118,6 +1118,123 @@ int egg_group_cover(egg_group *g, const egg_cover_spec *spec, const egg_cover_pl
     return EGG_OK;
 }
 
+// Touches (include/eggsim_touch.h): a query's batch lives wholly on one handle, its partners on any.  Per handle: the listed
+// batches it owns go through egg_touches, the others through egg_touches_of with their discs -- x, y and radius of
+// egg_export_batch, what a hand-over reads -- and their key; everything by keys, a batch's key on its handle being the
+// group's id.  The records of one (slot, other) are added and sorted.  First every handle checks the spec with an empty list
+// of queries, which launches nothing; nothing is written before every handle has answered.
+int egg_group_touches(egg_group *g, const egg_touch_spec *spec, int64_t n_ids, const int64_t *ids, int64_t cap, egg_touch_record *out,
+                      int64_t *n_out) {
+    if (!g || g->h.empty()) return EGG_ERR_INVALID_ARGUMENT;
+    if (!n_out) return gfail(g, EGG_ERR_INVALID_ARGUMENT, "egg_group_touches: n_out is NULL");
+    if (cap < 0 || (cap > 0 && !out))
+        return gfail(g, EGG_ERR_INVALID_ARGUMENT, "egg_group_touches: cap = %lld %s a buffer", (long long)cap, out ? "with" : "without");
+    if (n_ids < 0 || (n_ids > 0 && !ids) || (n_ids == 0 && ids))
+        return gfail(g, EGG_ERR_INVALID_ARGUMENT, "egg_group_touches: n_ids = %lld %s a list (0 and NULL mean every live batch)", (long long)n_ids,
+                     ids ? "with" : "without");
+    egg_touch_spec keyed = spec ? *spec : egg_touch_spec{};
+    keyed.flags |= EGG_TOUCH_BY_KEYS;
+    for (size_t k = 0; k < g->h.size(); ++k) {  // (the checks of every handle: the spec, a step in flight)
+        int64_t none = 0;
+        const int rc = egg_touches_of(g->h[k], spec ? &keyed : nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, &none);
+        if (rc < 0) return gfail(g, rc, "device %d: %s", (int)k, egg_last_error(g->h[k]));
+    }
+    for (int64_t i = 0; i < n_ids; ++i)  // (before anything is written)
+        if (!group_alive(g, ids[i])) return gfail(g, EGG_ERR_UNKNOWN_ID, "egg_group_touches: no batch with id `%lld`", (long long)ids[i]);
+    std::vector<int64_t> every;
+    if (n_ids == 0) {
+        every = group_live_ids(g);
+        ids = every.data();
+        n_ids = (int64_t)every.size();
+    }
+    // the discs of every listed batch, read once from its owner: [type] x, y, r
+    struct Discs {
+        std::vector<double> x[2], y[2], r[2];
+    };
+    std::map<int64_t, Discs> discs;
+    if (g->h.size() > 1)
+        for (int64_t i = 0; i < n_ids; ++i) {
+            if (discs.count(ids[i])) continue;
+            const egg_group::Rec &rec = g->batch[(size_t)ids[i] - 1];
+            int64_t n[2] = {0, 0};
+            GTRY(g, rec.owner, egg_get_n_particles(g->h[(size_t)rec.owner], rec.local, &n[0], &n[1]));
+            std::vector<double> state[2] = {std::vector<double>(9 * (size_t)n[0] + 1), std::vector<double>(9 * (size_t)n[1] + 1)};
+            egg_batch_info info{};
+            GTRY(g, rec.owner, egg_export_batch(g->h[(size_t)rec.owner], rec.local, &info, state[0].data(), state[1].data()));
+            Discs &d = discs[ids[i]];
+            for (int w = 0; w < 2; ++w) {  // (field-major: x, y, vx, vy, last_x, last_y, inv_mass, radius, mass_t)
+                const size_t m = (size_t)n[w];
+                d.x[w].assign(state[w].begin(), state[w].begin() + m);
+                d.y[w].assign(state[w].begin() + m, state[w].begin() + 2 * m);
+                d.r[w].assign(state[w].begin() + 7 * m, state[w].begin() + 8 * m);
+            }
+        }
+    std::map<std::pair<int32_t, int64_t>, egg_touch_record> sum;
+    std::vector<egg_touch_record> part(1024);
+    for (size_t k = 0; k < g->h.size(); ++k) {
+        std::vector<int64_t> local, where;            // the listed batches handle k owns, and their entries
+        std::vector<egg_touch_query> queries;          // the others, one query per type
+        std::vector<int64_t> q_where;
+        std::vector<double> x, y, r;
+        for (int64_t i = 0; i < n_ids; ++i) {
+            const egg_group::Rec &rec = g->batch[(size_t)ids[i] - 1];
+            if (rec.owner == (int)k) {
+                local.push_back(rec.local);
+                where.push_back(i);
+                continue;
+            }
+            const Discs &d = discs[ids[i]];
+            for (int w = 0; w < 2; ++w) {
+                queries.push_back(egg_touch_query{ids[i], w, (int32_t)d.x[w].size()});
+                q_where.push_back(i);
+                x.insert(x.end(), d.x[w].begin(), d.x[w].end());
+                y.insert(y.end(), d.y[w].begin(), d.y[w].end());
+                r.insert(r.end(), d.r[w].begin(), d.r[w].end());
+            }
+        }
+        for (int form = 0; form < 2; ++form) {
+            if (form == 0 ? local.empty() : queries.empty()) continue;
+            int64_t n = 0;
+            int rc = 0;
+            for (int attempt = 0; attempt < 2; ++attempt) {  // (a short buffer: once more with the size the call named)
+                rc = form == 0 ? egg_touches(g->h[k], &keyed, (int64_t)local.size(), local.data(), (int64_t)part.size(), part.data(), &n)
+                               : egg_touches_of(g->h[k], &keyed, (int64_t)queries.size(), queries.data(), x.data(), y.data(), r.data(),
+                                                (int64_t)part.size(), part.data(), &n);
+                if (rc >= 0 || n <= (int64_t)part.size()) break;
+                part.resize((size_t)n);
+            }
+            if (rc < 0) return gfail(g, rc, "device %d: %s", (int)k, egg_last_error(g->h[k]));
+            for (int64_t q = 0; q < n; ++q) {
+                egg_touch_record p = part[(size_t)q];
+                // the handle's slot is 2 j + w over ITS list: entry j of `local`, or query j of `queries` (whose type is w)
+                const int w = p.slot & 1;
+                const int64_t entry = form == 0 ? where[(size_t)(p.slot >> 1)] : q_where[(size_t)(p.slot >> 1)];
+                p.slot = (int32_t)(2 * entry + w);
+                auto at = sum.find({p.slot, p.other});
+                if (at == sum.end()) {
+                    sum.emplace(std::make_pair(p.slot, p.other), p);
+                    continue;
+                }
+                egg_touch_record &o = at->second;
+                if ((int64_t)o.pairs + p.pairs > (int64_t)std::numeric_limits<int32_t>::max())
+                    return gfail(g, EGG_ERR_UNSUPPORTED, "egg_group_touches: the pairs of slot %d with batch %lld do not fit 31 bits", (int)p.slot,
+                                 (long long)p.other);
+                o.pairs += p.pairs;
+                o.particles += p.particles;
+                o.dropped += p.dropped;
+                o.sx = (int64_t)((uint64_t)o.sx + (uint64_t)p.sx);
+                o.sy = (int64_t)((uint64_t)o.sy + (uint64_t)p.sy);
+            }
+        }
+    }
+    *n_out = (int64_t)sum.size();
+    if ((int64_t)sum.size() > cap)
+        return gfail(g, EGG_ERR_INVALID_ARGUMENT, "egg_group_touches: the answer holds %lld records, the buffer %lld", (long long)sum.size(), (long long)cap);
+    int64_t at = 0;
+    for (const auto &kv : sum) out[at++] = kv.second;  // (the map's order: slot, then other)
+    return EGG_OK;
+}
+
 int egg_group_get_collider_grips(egg_group *g, int64_t grips[2]) {
     if (!g) return EGG_ERR_INVALID_ARGUMENT;
     if (!grips) return gfail(g, EGG_ERR_INVALID_ARGUMENT, "egg_group_get_collider_grips: grips is NULL");

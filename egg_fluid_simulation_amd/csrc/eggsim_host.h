@@ -21,6 +21,7 @@
 //   eggsim_host_impulses.hip       egg_impulse: the checks, the unit table, at most two launches, the one copy of the totals back
 //   eggsim_host_measures.hip       egg_measure / egg_measure_to: the checks, the row table, the one launch, the one copy of the records back
 //   eggsim_host_cover.hip          egg_cover / egg_cover_to: the checks, the unit table, the presets, the two launches, the copies back
+//   eggsim_host_touches.hip        egg_touches / egg_touches_of: the checks, the queries, the rounds of two launches, the merge of the records
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -125,6 +126,8 @@ extern "C" __global__ void egg_impulse_finish_kernel(EggImpulseFinishArgs A);
 extern "C" __global__ void egg_measure_kernel(EggMeasureArgs A);
 extern "C" __global__ void egg_cover_kernel(EggCoverArgs A);
 extern "C" __global__ void egg_cover_finish_kernel(EggCoverFinishArgs A);
+extern "C" __global__ void egg_touch_gather_kernel(EggTouchGatherArgs A);
+extern "C" __global__ void egg_touch_kernel(EggTouchArgs A, const EggTouchQuery *__restrict__ Q, const EggTouchDisc *__restrict__ D);
 extern "C" __global__ void egg_render_count_kernel(EggRenderArgs A);
 extern "C" __global__ void egg_render_fill_kernel(EggRenderArgs A);
 extern "C" __global__ void egg_render_scan_kernel(EggRenderArgs A);
@@ -405,6 +408,7 @@ struct PiecesState;  // task table, records and labels of an egg_pieces call (eg
 struct ImpulseState;  // records, unit table, partials and totals of an egg_impulse call (eggsim_host_impulses.hip)
 struct MeasureState;  // row table and records of an egg_measure call (eggsim_host_measures.hip)
 struct CoverState;  // unit table, planes and totals of an egg_cover call (eggsim_host_cover.hip)
+struct TouchState;  // unit tables, the round's tables and the record buffer of an egg_touches call (eggsim_host_touches.hip)
 // egg_handle::collider_dirty: the tables sync_collider_records has to copy (eggsim_host_colliders.hip)
 enum : unsigned { kDirtyList = 1u, kDirtySurfaces = 2u, kDirtyMotions = 4u, kDirtySpins = 8u, kDirtyAllTables = 15u };
 }
@@ -592,6 +596,9 @@ struct egg_handle {
     // cover (egg_cover / egg_cover_to; either solver order): what a call needs on the device, allocated by the first call
     // that launches.  A call stores no grid and no answer; no step reads this.
     std::shared_ptr<egghost::CoverState> cover_state;
+    // touches (egg_touches / egg_touches_of; either solver order): what a call needs on the device, allocated by the first
+    // call that launches; the record buffer keeps the size the largest answer asked for.  A call stores no answer; no step reads this.
+    std::shared_ptr<egghost::TouchState> touch_state;
     // headless renderer (eggsim_render.hip)
     struct Render {
         egg_render_config cfg[2];

@@ -121,6 +121,13 @@ class SimulationGroup(_HandlerSurface):
         self._check(self._lib.egg_group_get_halo_counters(self._g, C.byref(p), C.byref(r), C.byref(b)))
         return dict(passes=p.value, records=r.value, bytes=b.value)
 
+    # touches_of: there is no group entry point -- the discs go to every handle, by keys (a batch's key on its handle is the
+    # group's id), and the tables are added
+    _TOUCH_OF_FLAGS = _ffi.TOUCH_BY_KEYS
+
+    def _touch_of_tables(self, spec, queries, n_queries, x, y, r):
+        return [h._touch_of_table(spec, queries, n_queries, x, y, r) for h in self.handles]
+
     def particles(self, which, fields=("x", "y")):
         """{global id: (x[n], y[n])} over all devices (the batches of a handle are laid out in ascending global id);
         `fields` picks other per-particle fields (SimulationHandler.download names)"""

@@ -1301,6 +1301,116 @@ function SimulationHandler:cover(x0, y0, cell, nx, ny, options)
              units_lanes = totals.units_lanes, units_wave = totals.units_wave, units_direct = totals.units_direct }
 end
 
+-- Not in the reference as a call: touches (egg_touches in include/eggsim_touch.h; DESIGN.md section 2.15).  Which eggs touch
+-- which, how much and where: two particles of one type in different batches touch iff d2 <= (reach * (ra + rb))^2, the
+-- predicate of the collision branch (L:1632-1653) when reach is the type's collision_overlap_factor; either solver order.  A
+-- call stores nothing and only observes.
+-- include/eggsim_touch.h, the fourth header include/eggsim.h brings along (declared from a string: the blocks above stay three)
+local _touch_decls = [==[
+typedef struct { double reach[2]; int32_t type_mask, flags; } egg_touch_spec;
+typedef struct { int64_t key; int32_t type, count; } egg_touch_query;
+typedef struct { int32_t slot, pairs, particles, dropped; int64_t other, sx, sy; } egg_touch_record;
+int egg_touches(egg_handle *h, const egg_touch_spec *spec, int64_t n_ids, const int64_t *ids, int64_t cap, egg_touch_record *out, int64_t *n_out);
+int egg_touches_of(egg_handle *h, const egg_touch_spec *spec, int64_t n_queries, const egg_touch_query *queries, const double *x,
+                   const double *y, const double *r, int64_t cap, egg_touch_record *out, int64_t *n_out);
+]==]
+ffi.cdef(_touch_decls)
+
+--- the egg_touch_spec of a call, or nil: `reach` nil (per type the config's collision_overlap_factor), a number (both types)
+--- or `{ white, yolk }`
+function SimulationHandler:_touch_spec(reach, types, scope)
+    if reach == nil then
+        reach = { self._white_config.collision_overlap_factor, self._yolk_config.collision_overlap_factor }
+    end
+    local pieces = self:_pieces_spec(reach, types, scope) -- (the same checks: a reach above 0 and finite, a known mask)
+    if pieces == nil then return nil end
+    return ffi.new("egg_touch_spec", { reach = { pieces.reach[0], pieces.reach[1] }, type_mask = pieces.type_mask, flags = 0 })
+end
+
+--- the records of one answer as `n` lists `{ white = {}, yolk = {} }` of `{ other, pairs, particles, dropped, x, y }` by name, in
+--- ascending `other`; `call(cap, out, n_out)` is the entry point with everything before its buffer bound.  n_out is always the
+--- size of the answer: a call whose buffer was short is made once more with that size.
+function SimulationHandler:_touch_lists(n, call)
+    local cap, n_out = 256, ffi.new("int64_t[1]")
+    local out, rc
+    while true do
+        out = ffi.new("egg_touch_record[?]", math.max(cap, 1))
+        n_out[0] = 0
+        rc = call(cap, out, n_out)
+        if rc < 0 and tonumber(n_out[0]) > cap then cap = tonumber(n_out[0]) else break end
+    end
+    if self:_check(rc) ~= 0 then return nil end
+    local res = {}
+    for i = 1, n do res[i] = { white = {}, yolk = {} } end
+    for k = 0, tonumber(n_out[0]) - 1 do
+        local rec = out[k]
+        local kept = rec.pairs - rec.dropped
+        local one = { other = tonumber(rec.other), pairs = rec.pairs, particles = rec.particles, dropped = rec.dropped }
+        if kept > 0 then
+            one.x = (tonumber(rec.sx) / (2 * kept)) / _sensor_scale
+            one.y = (tonumber(rec.sy) / (2 * kept)) / _sensor_scale
+        end
+        local side = res[math.floor(rec.slot / 2) + 1]
+        table.insert(rec.slot % 2 == 0 and side.white or side.yolk, one)
+    end
+    return res
+end
+
+--- per id of `ids` (nil: every batch of list_ids(), in that order; an id may repeat) `{ white = {...}, yolk = {...} }`: the OTHER
+--- batches with a particle of that type touching one of this batch's, each `{ other, pairs, particles, dropped, x, y }` --
+--- `pairs` touching pairs over `particles` distinct particles of the other batch, the contact point `x, y` (nil while every
+--- pair was dropped).  Never across types, never inside a batch (pieces() covers that).
+function SimulationHandler:touches(ids, reach, types)
+    local spec = self:_touch_spec(reach, types, "touches")
+    if spec == nil then return nil end
+    local listed = ids or self:list_ids()
+    local n = #listed
+    if n == 0 then return {} end
+    local c_ids = ffi.new("int64_t[?]", n)
+    for i, id in ipairs(listed) do c_ids[i - 1] = id end
+    return self:_touch_lists(n, function(cap, out, n_out) return lib.egg_touches(self._h, spec, n, c_ids, cap, out, n_out) end)
+end
+
+--- true iff batch `a` touches batch `b` in a covered type; with b nil the sorted ids of the batches that touch `a`
+function SimulationHandler:touching(a, b, reach, types)
+    local res = self:touches({ a }, reach, types)
+    if res == nil then return nil end
+    local seen, others = {}, {}
+    for _, side in ipairs({ res[1].white, res[1].yolk }) do
+        for _, t in ipairs(side) do
+            if not seen[t.other] then
+                seen[t.other] = true
+                table.insert(others, t.other)
+            end
+        end
+    end
+    table.sort(others)
+    if b == nil then return others end
+    return seen[b] == true
+end
+
+--- what a caller-set list of discs `{ { x, y, r }, ... }` of the type `types` ("white" or "yolk"; default "white") touches:
+--- `{ white = {...}, yolk = {...} }` as touches() gives for one id.  A batch whose id equals `key` is left out; nil leaves none out.
+function SimulationHandler:touches_of(discs, reach, types, key)
+    types = types or "white"
+    local spec = self:_touch_spec(reach, types, "touches_of")
+    if spec == nil then return nil end
+    if types ~= "white" and types ~= "yolk" then
+        log.error("In SimulationHandler.touches_of: types is \"white\" or \"yolk\"")
+        return nil
+    end
+    local n = #discs
+    local x, y, r = ffi.new("double[?]", math.max(n, 1)), ffi.new("double[?]", math.max(n, 1)), ffi.new("double[?]", math.max(n, 1))
+    for i, d in ipairs(discs) do x[i - 1], y[i - 1], r[i - 1] = d[1], d[2], d[3] end
+    local w = types == "white" and 0 or 1
+    local query = ffi.new("egg_touch_query[1]", { { key = key or -1, type = w, count = n } })
+    local res = self:_touch_lists(1, function(cap, out, n_out)
+        return lib.egg_touches_of(self._h, spec, 1, query, x, y, r, cap, out, n_out)
+    end)
+    if res == nil then return nil end
+    return res[1]
+end
+
 -- Not in the reference, which has no forces as it has no boundary: force fields of the relaxed step (egg_set_forces in
 -- include/eggsim.h; DESIGN.md section 2.7, "Forces").  Relaxed order only.
 local _force_kinds = { uniform = 0, radial = 1, vortex = 2 }

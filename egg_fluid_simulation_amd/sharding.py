@@ -833,6 +833,62 @@ class ShardedSimulationHandler(_HandlerSurface):
                                   lambda lids: self.local._piece_table(spec, np.ascontiguousarray(lids, dtype=np.int64)))
         return self._piece_summaries(table)
 
+    # ------------------------------------------------ touches (egg_touches / egg_touches_of)
+    def _touch_gather(self, table):
+        """the ranks' tables of touch records as one (a collective): all_gather of the rows -- every int64 as its two 32-bit
+        halves, which a float64 holds exactly --, the rows of one (entry, type, other) added and sorted"""
+        t = np.asarray(table, dtype=np.int64).reshape(-1, 8)
+        if self.world == 1:
+            return self._merge_touch_tables([t])
+        parts = self._all_gather_rows(np.concatenate([t >> 32, t & 0xFFFFFFFF], axis=1).astype(np.float64))
+        return self._merge_touch_tables([(p[:, :8].astype(np.int64) << 32) | p[:, 8:].astype(np.int64) for p in parts])
+
+    def _touch_table(self, spec, ids):
+        """SimulationHandler._touch_table over all ranks (a collective: every rank calls it with the same arguments).  A
+        query's batch lives wholly on one rank, its partners on any: the owners publish their queries' discs -- rows 0, 1 and 7
+        of export_batch: x, y, radius -- in one all_gather, every rank scans its own particles (egg_touches for the batches it
+        owns, egg_touches_of with the others' discs and their keys), and the record tables are gathered and added: one
+        handle's table, bit for bit.  Ids are global ids, which are the keys.  Nothing travels in a step."""
+        spec = _ffi.EggTouchSpec(spec.reach, spec.type_mask, spec.flags | _ffi.TOUCH_BY_KEYS)
+        ids = self.list_ids() if ids is None else [int(i) for i in ids]
+        for gid in ids:
+            if gid not in self.owner:
+                raise EggError("[ERROR] In SimulationHandler.touches: no batch with id `%d`" % gid)
+        rows = [np.zeros((0, 5))]
+        if self.world > 1:
+            for gid in sorted(set(ids) & set(self.local_id)):
+                _info, ws, ys = self.local.export_batch(self.local_id[gid])
+                for w, st in ((0, ws), (1, ys)):
+                    rows.append(np.stack([np.full(st.shape[1], float(gid)), np.full(st.shape[1], float(w)), st[0], st[1], st[7]], axis=1))
+        parts = self._all_gather_rows(np.concatenate(rows)) if self.world > 1 else []
+        discs = {}
+        for p in parts:
+            for w in (0, 1):
+                sel = p[p[:, 1] == w]
+                for gid in np.unique(sel[:, 0]).tolist():
+                    discs[(int(gid), w)] = sel[sel[:, 0] == gid][:, 2:]
+        tables = []
+        mine = [k for k, gid in enumerate(ids) if gid in self.local_id]
+        if mine:
+            t = self.local._touch_table(spec, np.ascontiguousarray([self.local_id[ids[k]] for k in mine], dtype=np.int64))
+            t[:, 0] = np.asarray(mine, dtype=np.int64)[t[:, 0]]
+            tables.append(t)
+        others = [k for k, gid in enumerate(ids) if gid not in self.local_id]
+        if others:  # two queries per entry, white then yolk: a record's slot >> 1 is 2 j + w
+            got = [discs.get((ids[k], w), np.zeros((0, 3))) for k in others for w in (0, 1)]
+            queries = (_ffi.EggTouchQuery * len(got))(*[_ffi.EggTouchQuery(ids[others[q // 2]], q % 2, d.shape[0]) for q, d in enumerate(got)])
+            xyr = np.concatenate(got)
+            t = self.local._touch_of_table(spec, queries, len(got), *(np.ascontiguousarray(xyr[:, c]) for c in range(3)))
+            t[:, 0] = np.asarray(others, dtype=np.int64)[t[:, 0] // 2]
+            tables.append(t)
+        return self._touch_gather(self._merge_touch_tables(tables))
+
+    _TOUCH_OF_FLAGS = _ffi.TOUCH_BY_KEYS
+
+    def _touch_of_tables(self, spec, queries, n_queries, x, y, r):
+        """SimulationHandler.touches_of over all ranks (a collective): every rank scans its own particles, by keys"""
+        return [self._touch_gather(self.local._touch_of_table(spec, queries, n_queries, x, y, r))]
+
     def impulse(self, records, results=True):
         """SimulationHandler.impulse over all ranks (a collective: every rank calls it with the same list).  The ranks agree
         first: an id no rank owns raises on every rank alike, and every rank has its handle check the list with every record

@@ -62,6 +62,19 @@ class PieceSummary(collections.namedtuple("PieceSummary", "n pieces largest firs
     __slots__ = ()
 
 
+class Touch(collections.namedtuple("Touch", "other pairs particles dropped x y")):
+    """One batch that touches a query (egg_touch_record): `other` its id, `pairs` the touching (query particle, other particle)
+    pairs, `particles` the distinct particles of the other batch among them, `dropped` the pairs whose scaled coordinates were
+    not finite or reached 2^53; `x`, `y` the contact point from the int64 sums, `sx / (2 * (pairs - dropped)) / 2^16`, None
+    while every pair was dropped."""
+    __slots__ = ()
+
+
+# egg_touch_record as a numpy record (40 bytes)
+_TOUCH_RECORD = np.dtype([("slot", "<i4"), ("pairs", "<i4"), ("particles", "<i4"), ("dropped", "<i4"), ("other", "<i8"), ("sx", "<i8"),
+                          ("sy", "<i8")])
+
+
 # egg_piece_summary as a numpy record (40 bytes)
 _PIECE_RECORD = np.dtype([("n", "<i4"), ("pieces", "<i4"), ("largest", "<i4"), ("first", "<i4"), ("singles", "<i4"), ("dropped", "<i4"),
                           ("sx", "<i8"), ("sy", "<i8")])
@@ -955,6 +968,132 @@ class _HandlerSurface:
     def is_whole(self, id, reach=None, types="both"):
         """True iff every covered atom of the batch -- its white, its yolk, by `types` -- is ONE piece"""
         return all(a is None or a.pieces == 1 for a in self.pieces([id], reach, types)[0])
+
+    # ------------------------------------------------ touches (egg_touches, DESIGN.md section 2.15)
+    def _c_touch_spec(self, reach, types, what="touches", flags=0):
+        """the reach per type, the mask and the flags of a call as an egg_touch_spec.  reach=None is, per type, the
+        collision_overlap_factor of this object's config: a touch is then exactly a pair the solver's collision branch acts
+        on.  A number holds for both types, a pair is (white, yolk)."""
+        if reach is None:
+            reach = tuple(float(cfg["collision_overlap_factor"]) for cfg in (self._white_config, self._yolk_config))
+        spec = self._c_pieces_spec(reach, types, what)  # (the same checks: a reach finite and above 0, a known mask)
+        return _ffi.EggTouchSpec((C.c_double * 2)(*spec.reach), spec.type_mask, int(flags))
+
+    def _touch_records(self, call):
+        """the records of one answer as an int64 array [n, 8] of (entry, type, other, pairs, particles, dropped, sx, sy):
+        `call(cap, out, n_out)` is the entry point with everything before its buffer bound.  *n_out is always the size of the
+        answer: a call whose buffer was short is made once more with that size."""
+        cap, n = 256, C.c_int64(0)
+        while True:
+            out = np.zeros(max(cap, 1), dtype=_TOUCH_RECORD)
+            rc = call(cap, out.ctypes.data, C.byref(n))
+            if rc < 0 and n.value > cap:
+                cap = n.value
+                continue
+            self._check(rc)
+            rec = out[:n.value]
+            return np.stack([rec["slot"].astype(np.int64) >> 1, rec["slot"].astype(np.int64) & 1] +
+                            [rec[name].astype(np.int64) for name in ("other", "pairs", "particles", "dropped", "sx", "sy")], axis=1).reshape(-1, 8)
+
+    def _touch_table(self, spec, ids):
+        """one call of this object's egg_touches: `ids` an int64 array (it may be empty: no batch is asked for) or None for every
+        live batch"""
+        if ids is not None and ids.size == 0:
+            return np.zeros((0, 8), dtype=np.int64)
+        head = (C.byref(spec), 0, None) if ids is None else (C.byref(spec), ids.size, ids.ctypes.data)
+        return self._touch_records(functools.partial(self._c("touches"), *head))
+
+    @staticmethod
+    def _merge_touch_tables(tables):
+        """tables of several handles or ranks as one: the rows of one (entry, type, other) added -- every field is additive over
+        any split of the other batch's particles -- and sorted"""
+        rows = np.concatenate([np.asarray(t, dtype=np.int64).reshape(-1, 8) for t in tables] + [np.zeros((0, 8), dtype=np.int64)])
+        if rows.shape[0] == 0:
+            return rows
+        keys, inverse = np.unique(rows[:, :3], axis=0, return_inverse=True)
+        out = np.zeros((keys.shape[0], 8), dtype=np.int64)
+        out[:, :3] = keys
+        np.add.at(out[:, 3:], np.asarray(inverse).reshape(-1), rows[:, 3:])  # (int64 wraps as the library's sums do)
+        return out
+
+    @staticmethod
+    def _touch_lists(table, n):
+        """per entry 0 .. n - 1 `(white, yolk)`, each the list of Touch of that query in ascending `other`"""
+        scale = _ffi.SENSOR_POSITION_SCALE
+        res = [([], []) for _ in range(n)]
+        for entry, w, other, pairs, particles, dropped, sx, sy in np.asarray(table, dtype=np.int64).reshape(-1, 8).tolist():
+            kept = pairs - dropped
+            res[entry][w].append(Touch(other, pairs, particles, dropped, (float(sx) / (2.0 * kept)) / scale if kept > 0 else None,
+                                       (float(sy) / (2.0 * kept)) / scale if kept > 0 else None))
+        return res
+
+    def touch_table(self, ids=None, reach=None, types="both"):
+        """touches() as its raw records: an int64 array [n, 8] of (entry, type, other, pairs, particles, dropped, sx, sy), ordered
+        by (entry, type, other); `entry` is the index into `ids` (None: list_ids()), `type` 0 white and 1 yolk."""
+        return self._touch_table(self._c_touch_spec(reach, types, "touch_table"), self._piece_ids(ids, "touch_table"))
+
+    def touches(self, ids=None, reach=None, types="both"):
+        """Which eggs touch which, how much and where (either solver order): per id (None: every batch
+        of list_ids(), in that order; ids may repeat) `(white, yolk)`, each the list of `Touch(other, pairs, particles, dropped,
+        x, y)` of the OTHER batches with a particle of that type touching one of this batch's, in ascending id.  Particles a and
+        b of one type touch iff `d2 <= (reach * (ra + rb)) ** 2`; reach=None takes the type's collision_overlap_factor, so that
+        a touch is a pair the solver's collision branch acts on; a number holds for both types, a pair is (white, yolk).  Never
+        across types, never inside a batch (pieces() covers that).  Reads the committed state; stores nothing.  Raises EggError
+        for an unknown id or a bad reach."""
+        ids = self._piece_ids(ids, "touches")
+        n = len(self.list_ids()) if ids is None else ids.size
+        return self._touch_lists(self._touch_table(self._c_touch_spec(reach, types), ids), n)
+
+    def touching(self, a, b=None, reach=None, types="both"):
+        """True iff batch `a` touches batch `b` in a covered type; with b=None the sorted ids of the batches that touch `a`"""
+        others = sorted(set(self.touch_table([a], reach, types)[:, 2].tolist()))
+        if b is None:
+            return others
+        if int(b) not in self.list_ids():
+            raise EggError("[ERROR] In SimulationHandler.touching: no batch with id `%s`" % (b,))
+        return int(b) in others
+
+    @staticmethod
+    def _c_touch_discs(discs, types, key, what="touches_of"):
+        """a caller's discs as the arguments of egg_touches_of: `discs` an array [n, 3] of (x, y, r), or a pair (white discs,
+        yolk discs) of such arrays when types is "both"; returns (queries, n_queries, x, y, r)"""
+        mask = _HandlerSurface._probe_mask(types, what)
+        try:
+            if mask == 3:
+                white, yolk = discs
+                parts = [np.asarray(white, dtype=np.float64).reshape(-1, 3), np.asarray(yolk, dtype=np.float64).reshape(-1, 3)]
+            else:
+                parts = [np.asarray(discs, dtype=np.float64).reshape(-1, 3)]
+            key = int(key)
+        except (TypeError, ValueError):
+            raise EggError("%s: discs must be an array [n, 3] of (x, y, r), or (white, yolk) of them for both types; key an id" % what) from None
+        kinds = (0, 1) if mask == 3 else (mask - 1,)
+        queries = (_ffi.EggTouchQuery * len(parts))(*[_ffi.EggTouchQuery(key, w, p.shape[0]) for w, p in zip(kinds, parts)])
+        xyr = np.concatenate(parts)
+        if not np.isfinite(xyr[:, 2]).all():
+            raise EggError("%s: a radius is not finite" % what)
+        return queries, len(parts), np.ascontiguousarray(xyr[:, 0]), np.ascontiguousarray(xyr[:, 1]), np.ascontiguousarray(xyr[:, 2])
+
+    def _touch_of_table(self, spec, queries, n_queries, x, y, r):
+        """one call of egg_touches_of on this handle"""
+        return self._touch_records(functools.partial(self._lib.egg_touches_of, self._h, C.byref(spec), n_queries, C.cast(queries, C.c_void_p),
+                                                     x.ctypes.data, y.ctypes.data, r.ctypes.data))
+
+    def _touch_of_tables(self, spec, queries, n_queries, x, y, r):
+        """the tables of egg_touches_of of every handle behind this object (one here)"""
+        return [self._touch_of_table(spec, queries, n_queries, x, y, r)]
+
+    def touches_of(self, discs, reach=None, types="white", key=-1):
+        """What a caller-set list of discs touches: `discs` an array [n, 3] of (x, y, r) of the type `types` -- or, with
+        types="both", a pair (white discs, yolk discs) --; returns `(white, yolk)` lists of Touch as touches() does for one id.
+        A batch whose id equals `key` is left out (the discs are that batch's own, say); -1 leaves none out."""
+        spec = self._c_touch_spec(reach, types, "touches_of", self._TOUCH_OF_FLAGS)
+        queries, n, x, y, r = self._c_touch_discs(discs, types, key)
+        table = self._merge_touch_tables(self._touch_of_tables(spec, queries, n, x, y, r))
+        table[:, 0] = 0  # (the one query per type: entry 0)
+        return self._touch_lists(table, 1)[0]
+
+    _TOUCH_OF_FLAGS = 0
 
     # ------------------------------------------------ impulses (egg_impulse, DESIGN.md section 2.12)
     @staticmethod

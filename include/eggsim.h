@@ -1385,6 +1385,10 @@ int egg_draw_source_instances(egg_handle *h, int which, egg_instance *data, floa
  * Three more entry points, their spec, planes and totals, in a header of their own as well. */
 #include "eggsim_cover.h"
 
+/* ---- touches: which eggs touch which, how much and where: include/eggsim_touch.h ----
+ * Three more entry points, their spec, their query and their record, in a header of their own as well. */
+#include "eggsim_touch.h"
+
 #ifdef __cplusplus
 }
 #endif
